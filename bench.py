@@ -5,14 +5,24 @@ One "step" = one pass of the hot path (cc_correct_soft_batch_dev: LLR frames res
 hard decisions + iteration index + status) over one batch.  Prints ONE JSON line on rank 0.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--ebno 4.0] [--batch-log2 20]
+                  [--dump-outputs DIR] [--full]
   (N > 1: launched by torch.distributed.run, one rank per GPU; frames are independent, so ranks
    shard the batch with no data-path collective -> weak scaling; timing = max over ranks.)
 
+A plain run sets up, warms up, times the K steps, verifies the last step's output (below), writes it
+with --dump-outputs and prints the line.  --full adds what takes runs of its own: the attainable HBM
+rate (roofline.measured_copy_GBs), cpu_baseline and the secondary workloads.
+
 roofline.achieved = algorithmic HBM bytes per launch (4n LLR bytes in + n hard bytes out + 6 B
 iters/status per frame) / average kernel duration measured with HIP events on the
-launch stream.  cpu_baseline = the real reference (oracle/_ref, built from /root/reference in the
-dev container) or, if that prebuilt library is absent, the plain-C oracle, timed on a bounded sample
-of the same frames on one host core.
+launch stream.  cpu_baseline (--full) = the real reference (oracle/_ref, built by oracle/Makefile where
+the reference sources are present) or, if that prebuilt library is absent, the plain-C oracle, timed on
+a bounded sample of the same frames on one host core.
+
+--dump-outputs DIR writes what the caller of the timed path receives from the last timed step, for a
+fixed seeded sample of DUMP_FRAMES frames (rank 0's shard), as float32: DIR/hard.npy (frames x n hard
+decisions), DIR/iters.npy (iteration index), DIR/status.npy (0 = converged).  The inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -34,6 +44,9 @@ HBM_PEAK_GBS = 8000.0  # MI355X spec (MI355X_MICROARCH.md); ~6300 measured attai
 # with the ISA count / PMC pass it came from (profiles/tools/isa_mix.py), never constants in this file.  A kernel
 # without an entry gets no valu_issue object.
 SIMDS, CLOCK_HZ = 256 * 4, 2.4e9
+
+# --dump-outputs: frames sampled from the batch (hard decisions of 2^15 frames x 255 in f32 = 33 MB)
+DUMP_FRAMES, DUMP_SEED = 1 << 15, 0
 
 
 def valu_mix(kernel):
@@ -218,6 +231,19 @@ def verify_batch(torch, code, y, hard, iters, status, iterations, stop_rule, sam
     return res
 
 
+def dump_outputs(torch, out_dir, hard, iters, status):
+    """--dump-outputs: the fixed seeded frame sample of the last step's outputs, as float32 .npy files."""
+    B = hard.shape[0]
+    if B <= DUMP_FRAMES:
+        idx = np.arange(B)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(B, DUMP_FRAMES, replace=False))
+    idx = torch.from_numpy(idx).to(hard.device)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("hard", hard), ("iters", iters), ("status", status)):
+        np.save(os.path.join(out_dir, name + ".npy"), t[idx].to(torch.float32).cpu().numpy())
+
+
 CPU_WORKER = r"""
 import sys, time
 import numpy as np
@@ -291,12 +317,18 @@ def main():
     ap.add_argument("--batch-log2", type=int, default=20)
     ap.add_argument("--iterations", type=int, default=20)
     ap.add_argument("--stop-rule", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (seeded frame sample) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the HBM copy rate, the CPU baseline and the secondary workloads")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary workloads")
     # rehearsal of the N > 1 flow on a one-GPU box: control collectives over gloo, every rank on device 0
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--single-device", action="store_true")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # plain `python bench.py --gpus N`: start the ranks ourselves, as a CHILD process and before this process
@@ -379,19 +411,23 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(torch, args.dump_outputs, hard, iters, status)
 
-    # attainable HBM bandwidth on this box: device-to-device copy of the LLR batch (read + write bytes)
-    scratch = torch.empty_like(y)
-    scratch.copy_(y)
-    torch.cuda.synchronize()
-    ca, cb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ca.record(stream)
-    for _ in range(5):
+    copy_gbs = None
+    if args.full:
+        # attainable HBM bandwidth on this box: device-to-device copy of the LLR batch (read + write bytes)
+        scratch = torch.empty_like(y)
         scratch.copy_(y)
-    cb.record(stream)
-    torch.cuda.synchronize()
-    copy_gbs = 2 * y.numel() * 4 * 5 / (ca.elapsed_time(cb) * 1e-3) / 1e9
-    del scratch
+        torch.cuda.synchronize()
+        ca, cb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ca.record(stream)
+        for _ in range(5):
+            scratch.copy_(y)
+        cb.record(stream)
+        torch.cuda.synchronize()
+        copy_gbs = 2 * y.numel() * 4 * 5 / (ca.elapsed_time(cb) * 1e-3) / 1e9
+        del scratch
 
     verification = verify_batch(torch, code, y, hard, iters, status, args.iterations, args.stop_rule)
     if dist is not None:  # every rank's shard must pass
@@ -442,7 +478,7 @@ def main():
                 "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": achieved / HBM_PEAK_GBS, "traffic": measured_traffic(name.value.decode(), args.batch_log2),
                 "kernel": name.value.decode(), "kernel_ms": kernel_ms, "algorithmic_bytes_per_frame": bytes_per_frame,
-                "measured_copy_GBs": copy_gbs,  # attainable HBM rate on this box (d2d copy, read + write)
+                "measured_copy_GBs": copy_gbs,  # attainable HBM rate on this box (d2d copy, read + write); --full
                 "note": "the path is bound by instruction issue (one instruction per ~7 cycles and wavefront at two waves "
                         "per SIMD, profiles/r03_experiments.md E14), not by HBM (SURVEY F4): %.1f min-sum iterations per "
                         "frame on average" % mean_iters,
@@ -460,11 +496,12 @@ def main():
                 "note": "fraction of all SIMD issue cycles spent issuing this kernel's VALU instructions; mix from "
                         "profiles/kernel_valu_mix.json",
             }
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only: the other ranks would idle at the barrier
+        # rank 0 at N = 1 only: the other ranks would idle at the barrier
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(y[:32768].cpu().numpy(), args.iterations)
         else:
             out["cpu_baseline"] = None
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             del y, hard
             out["secondary"] = secondary_workloads(torch, cc, capi, dev)
         print(json.dumps(out))

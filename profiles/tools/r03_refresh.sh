@@ -4,7 +4,7 @@
 set -e
 cd $GRAFT_REPO_ROOT
 OUT=$GRAFT_REPO_ROOT/gpurun_out/r03_refresh; rm -rf $OUT; mkdir -p $OUT
-echo "== bench"; timeout -k 10 600 python3 bench.py > $OUT/final_bench.json 2> $OUT/final_bench.err; python3 profiles/benchline.py $OUT/final_bench.json
+echo "== bench"; timeout -k 10 600 python3 bench.py --full > $OUT/final_bench.json 2> $OUT/final_bench.err; python3 profiles/benchline.py $OUT/final_bench.json
 echo "== side benches"
 python3 profiles/tools/hard_bench.py > $OUT/hard_bench.txt 2>&1
 python3 profiles/tools/codes_bench.py > $OUT/codes_bench.txt 2>&1
