@@ -38,6 +38,9 @@ struct MinSumParams {
   // pass handed on, [2] frames of the sample that did not stop, [3] list overflow.  The device's choice: two passes iff
   // ctl[2] * 8 < sample (first pass), and its result is used iff the list did not overflow either (everything after it).
   uint32_t *ctl = nullptr;
+  // diagonal kernel: the call's frame pool, POOL_WORDS device words zeroed on the launch's stream before it (one launch
+  // per pool; minsum_diag_impl.hpp, "Frames are drawn from a pool per CALL")
+  uint32_t *pool = nullptr;
   unsigned sample = 0;
   uint32_t *list = nullptr;   // frames handed on
   unsigned list_cap = 0;
@@ -52,6 +55,9 @@ struct MinSumParams {
   uint16_t *iters2 = nullptr;
   int32_t *status2 = nullptr;
 };
+
+constexpr unsigned POOL_SHARDS = 32;                 // shard counters of a frame pool,
+constexpr size_t POOL_WORDS = POOL_SHARDS * 32;      // one per 128-byte line
 
 #if defined(__HIPCC__)
 __device__ __forceinline__ bool two_pass_sampled(const MinSumParams &p) { return p.ctl[2] * 8u < p.sample; }
@@ -154,9 +160,9 @@ MinSumParams minsum_params(const cc_code *code);
 bool minsum_shortcuts_enabled();
 bool minsum_diag_supported(const cc_code *code);
 // the general diagonal kernel over a compacted batch whose size only the device knows (ctl[1], at most cap frames);
-// ctl: four zeroed device words (MinSumParams::ctl), the producer counts into ctl[1]
-int launch_minsum_diag_compact(const cc_code *code, uint32_t *d_ctl, unsigned cap, const float *d_llr, uint8_t *d_hard,
-                               uint16_t *d_iters, int32_t *d_status, hipStream_t stream);
+// ctl: four zeroed device words (MinSumParams::ctl), the producer counts into ctl[1]; pool: POOL_WORDS zeroed words
+int launch_minsum_diag_compact(const cc_code *code, uint32_t *d_ctl, uint32_t *d_pool, unsigned cap, const float *d_llr,
+                               uint8_t *d_hard, uint16_t *d_iters, int32_t *d_status, hipStream_t stream);
 std::string minsum_diag_name(const cc_code *code);
 int launch_minsum_diag(const cc_code *code, const MinSumParams &p, const float *d_llr, const uint16_t *d_er,
                        const uint32_t *d_er_off, uint8_t *d_hard, float *d_L, uint16_t *d_iters, int32_t *d_status,

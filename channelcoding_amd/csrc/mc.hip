@@ -340,7 +340,9 @@ struct McWorkspace {
   uint8_t *sent = nullptr, *msg = nullptr, *hard = nullptr;
   uint16_t *iters = nullptr;
   int32_t *status = nullptr, *nerr = nullptr;
-  uint32_t *list = nullptr;  // [chunk + 64]: 64 control words (MinSumParams::ctl in the first four), then the frame list
+  // [64 + POOL_WORDS + chunk]: 64 control words (MinSumParams::ctl in the first four), the decoder's frame pool, then the
+  // frame list
+  uint32_t *list = nullptr;
   // recorded behind the last work enqueued on the buffers: the lock only covers the ENQUEUE, so a later call on
   // another stream first waits (on the device) for this event before it overwrites them
   hipEvent_t done = nullptr;
@@ -385,7 +387,7 @@ static int ensure_workspace(cc_code *code, size_t chunk) {
   CC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&w.iters), chunk * sizeof(uint16_t)));
   CC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&w.status), chunk * sizeof(int32_t)));
   CC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&w.nerr), chunk * sizeof(int32_t)));
-  CC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&w.list), (chunk + 64) * sizeof(uint32_t)));
+  CC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&w.list), (chunk + 64 + POOL_WORDS) * sizeof(uint32_t)));
   w.chunk = chunk;
   return CC_OK;
 }
@@ -476,8 +478,8 @@ int mc_run(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, s
         rc = launch_sent_words(code, seed, first_frame + done, m, w.sent, w.msg, stream);
         if (rc != CC_OK) return rc;
       }
-      uint32_t *ctl = w.list, *list = w.list + 64;
-      CC_HIP_TRY(hipMemsetAsync(ctl, 0, 64 * sizeof(uint32_t), stream));
+      uint32_t *ctl = w.list, *pool = w.list + 64, *list = w.list + 64 + POOL_WORDS;
+      CC_HIP_TRY(hipMemsetAsync(ctl, 0, (64 + POOL_WORDS) * sizeof(uint32_t), stream));
       const float sigma = static_cast<float>(cc_sigma(code, ebno_db));
       const unsigned long long wg = (m + 31) / 32, cap = static_cast<unsigned long long>(code->num_cus) * 8;
       hipLaunchKernelGGL(awgn_precheck_kernel, dim3(static_cast<int>(wg < cap ? wg : cap)), dim3(256), 0, stream, w.llr, list,
@@ -487,7 +489,7 @@ int mc_run(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, s
                          reinterpret_cast<unsigned long long *>(d_counters));
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) return hip_fail(e, "awgn pre-check kernel launch");
-      rc = launch_minsum_diag_compact(code, ctl, static_cast<unsigned>(m), w.llr, w.hard, w.iters, w.status, stream);
+      rc = launch_minsum_diag_compact(code, ctl, pool, static_cast<unsigned>(m), w.llr, w.hard, w.iters, w.status, stream);
       if (rc != CC_OK) return rc;
       const unsigned long long blocks = (m + 15) / 16, max_grid = static_cast<unsigned long long>(code->num_cus) * 8;
       hipLaunchKernelGGL(count_kernel, dim3(static_cast<int>(blocks < max_grid ? blocks : max_grid)), dim3(256), 0, stream,

@@ -297,8 +297,10 @@ int launch_two_pass(const cc_code *code, const DiagEntry *e, const MinSumParams 
                     uint16_t *d_iters, int32_t *d_status, size_t B, hipStream_t stream) {
   const size_t n = code->tab.n, cap = B / 4, sample = 4096;
   auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
-  const size_t o_list = 256, o_llr = o_list + up(cap * 4), o_hard = o_llr + up(cap * n * 4), o_it = o_hard + up(cap * n),
-               o_st = o_it + up(cap * 2), total = o_st + up(cap * 4);
+  // control words, then one frame pool per kernel launch (the sample's runs, the first pass, the general kernel)
+  constexpr size_t max_runs = 4, o_pool = 256, pool_bytes = POOL_WORDS * 4;
+  const size_t o_list = o_pool + (max_runs + 2) * pool_bytes, o_llr = o_list + up(cap * 4), o_hard = o_llr + up(cap * n * 4),
+               o_it = o_hard + up(cap * n), o_st = o_it + up(cap * 2), total = o_st + up(cap * 4);
   uint8_t *ws = nullptr;
   CC_HIP_TRY(workspace_alloc(code, reinterpret_cast<void **>(&ws), total, stream));
   uint32_t *ctl = reinterpret_cast<uint32_t *>(ws), *list = reinterpret_cast<uint32_t *>(ws + o_list);
@@ -307,7 +309,7 @@ int launch_two_pass(const cc_code *code, const DiagEntry *e, const MinSumParams 
   uint16_t *it2 = reinterpret_cast<uint16_t *>(ws + o_it);
   int32_t *st2 = reinterpret_cast<int32_t *>(ws + o_st);
   int rc = CC_OK;
-  hipError_t he = hipMemsetAsync(ctl, 0, 256, stream);
+  hipError_t he = hipMemsetAsync(ctl, 0, o_list, stream);
   if (he != hipSuccess) rc = hip_fail(he, "two-pass control words");
   MinSumParams q = p;
   q.ctl = ctl;
@@ -319,15 +321,17 @@ int launch_two_pass(const cc_code *code, const DiagEntry *e, const MinSumParams 
   // the sample: four runs of 1024 frames spread over the batch (an ordered batch -- SNR sweep, clean frames first --
   // would fool a leading sample into a first pass that overflows its list)
   q.first_pass = 2;
-  const size_t runs = B >= 16 * sample ? 4 : 1, per = sample / runs, hop = (B / runs) & ~static_cast<size_t>(63);
+  const size_t runs = B >= 16 * sample ? max_runs : 1, per = sample / runs, hop = (B / runs) & ~static_cast<size_t>(63);
   for (size_t r = 0; r < runs && rc == CC_OK; ++r) {
     const size_t at = r * hop;
+    q.pool = reinterpret_cast<uint32_t *>(ws + o_pool + r * pool_bytes);
     rc = launcher(e, q)(code, q, d_llr + at * n, nullptr, nullptr, d_hard + at * n, nullptr, d_iters ? d_iters + at : nullptr,
                         d_status ? d_status + at : nullptr, per, stream);
   }
   if (rc == CC_OK) {
     q.first_pass = 1;  // first pass over everything (returns at once unless the sample says so)
     q.gate = 1;
+    q.pool = reinterpret_cast<uint32_t *>(ws + o_pool + max_runs * pool_bytes);
     rc = launcher(e, q)(code, q, d_llr, nullptr, nullptr, d_hard, nullptr, d_iters, d_status, B, stream);
   }
   if (rc == CC_OK) {
@@ -339,6 +343,7 @@ int launch_two_pass(const cc_code *code, const DiagEntry *e, const MinSumParams 
     q.first_pass = 0;
     q.gate = -1;
     q.dual = 1;
+    q.pool = reinterpret_cast<uint32_t *>(ws + o_pool + (max_runs + 1) * pool_bytes);
     q.llr2 = llr2;
     q.hard2 = hard2;
     q.iters2 = it2;
@@ -368,12 +373,13 @@ bool minsum_shortcuts_enabled() {
   return v;
 }
 
-int launch_minsum_diag_compact(const cc_code *code, uint32_t *d_ctl, unsigned cap, const float *d_llr, uint8_t *d_hard,
-                               uint16_t *d_iters, int32_t *d_status, hipStream_t stream) {
+int launch_minsum_diag_compact(const cc_code *code, uint32_t *d_ctl, uint32_t *d_pool, unsigned cap, const float *d_llr,
+                               uint8_t *d_hard, uint16_t *d_iters, int32_t *d_status, hipStream_t stream) {
   const DiagEntry *e = diag_entry(code->tab);
   if (!e) return CC_ERR_UNSUPPORTED;
   MinSumParams q = minsum_params(code);
   q.ctl = d_ctl;  // [2] = [3] = 0: "two passes in effect", [1] = frames in the compact batch
+  q.pool = d_pool;
   q.sample = 1;
   q.list_cap = cap;
   q.gate = -1;
@@ -398,7 +404,16 @@ int launch_minsum_diag(const cc_code *code, const MinSumParams &p, const float *
   if (two_pass_enabled() && plain && p.stop_rule != CC_STOP_AS_SHIPPED && p.iterations >= 2 && d_er_off == nullptr &&
       d_L == nullptr && work >= 1.5e9)
     return launch_two_pass(code, e, p, d_llr, d_hard, d_iters, d_status, B, stream);
-  return launcher(e, p)(code, p, d_llr, d_er, d_er_off, d_hard, d_L, d_iters, d_status, B, stream);
+  uint32_t *pool = nullptr;
+  CC_HIP_TRY(workspace_alloc(code, reinterpret_cast<void **>(&pool), POOL_WORDS * 4, stream));
+  int rc = CC_OK;
+  const hipError_t he = hipMemsetAsync(pool, 0, POOL_WORDS * 4, stream);
+  if (he != hipSuccess) rc = hip_fail(he, "frame pool");
+  MinSumParams q = p;
+  q.pool = pool;
+  if (rc == CC_OK) rc = launcher(e, q)(code, q, d_llr, d_er, d_er_off, d_hard, d_L, d_iters, d_status, B, stream);
+  (void)hipFreeAsync(pool, stream);
+  return rc;
 }
 
 }  // namespace ccamd

@@ -327,8 +327,9 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
   char *stg = smem + 4 * WAVE_BYTES + 1024 + wid * (CPL * 256);
   const uint32_t stg_lds = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(reinterpret_cast<size_t>(stg)));
   cbits[threadIdx.x] = colbits[threadIdx.x];
-  __shared__ unsigned wg_next;  // ordinal of the workgroup's next unassigned frame (see take_frame below)
-  if (threadIdx.x == 0) wg_next = 2 * 4 * (64 / LPF);  // every lane group starts with two frames of its own
+  constexpr bool POOL = !SINGLE && LPF == 16;  // how frames are dealt, see below
+  __shared__ unsigned wg_next;  // (round-3 deal) ordinal of the workgroup's next unassigned frame (see take_frame below)
+  if (!POOL && threadIdx.x == 0) wg_next = 2 * 4 * (64 / LPF);  // every lane group starts with two frames of its own
   __syncthreads();
 
   const int n = p.n;
@@ -371,13 +372,45 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
     for (int d = 0; d < D; ++d) aWR[d] = aCY[d] + (oddf ? 4 : 0);
   }
 
-  const unsigned long long ngroups = static_cast<unsigned long long>(gridDim.x) * 4 * FPW;
-  // Frames are dealt to WORKGROUPS statically (workgroup b owns the frames b GPW + u + k ngroups, u < GPW = 16 or 32
-  // lane groups, k = 0, 1, ...: the same set as round 2) and to the lane groups of a workgroup DYNAMICALLY: a group that
-  // has finished takes the workgroup's next frame off a counter in LDS.  With a fixed share per group the kernel ended
-  // when the unluckiest of 8192 groups had run its 128 frames -- at 4 dB (1 .. 20 iterations per frame) ~9 % after the
-  // average one, and a wavefront executes its row block as long as ANY of its four groups has work.
+  // Which lane group decodes which frame.  POOL (the general kernel of the 16-lanes-per-frame geometries, n = 255):
+  // frames are drawn from a pool per CALL.  Round 3 (E22) dealt every workgroup a fixed share and let its lane groups
+  // draw from that share through a counter in LDS; the kernel then ended on the workgroup whose share needed the most
+  // iterations while the SIMDs of the others idled (E44).  The pool is split into S <= POOL_SHARDS shards (one counter
+  // per 128-byte line of p.pool, zeroed on the stream before the launch), workgroup b drawing from shard b mod S: one
+  // counter word serves ~88 draws per microsecond, and this kernel decodes up to ~250 frames per microsecond.  Shard s
+  // holds the frames s + S o, o = 0, 1, ...; every lane group of the shard's W_s workgroups starts with two ordinals of
+  // its own (o < 2 W_s GPW) and takes the next ones off the counter, one per frame.  A draw is consumed one frame later,
+  // so the atomic's round trip hides behind a whole frame instead of stalling the wavefront.  The two ordinals a group
+  // holds live in LDS (they are needed only when a frame ends, and registers are what the row block is short of); only
+  // the draw in flight sits in a register.  Every frame is written at its own index: the results do not depend on the
+  // order of the draws.
+  // Otherwise (the message-free kernel, and the geometries of 8 lanes per frame: 500 .. 1000 frames per microsecond,
+  // more than the pool's counters serve, E44) the round-3 deal: frames dealt to WORKGROUPS statically (workgroup b owns
+  // the frames b GPW + u + k ngroups, u < GPW lane groups, k = 0, 1, ...) and to the lane groups of a workgroup
+  // DYNAMICALLY, off a counter in LDS.
   constexpr unsigned GPW = 4 * FPW;  // lane groups per workgroup
+  const unsigned S = gridDim.x < POOL_SHARDS ? gridDim.x : POOL_SHARDS, shard = blockIdx.x % S, Ws = (gridDim.x - shard + S - 1) / S;
+  const unsigned obase = 2 * Ws * GPW;  // ordinals the counter hands out start here
+  auto frame_of = [&](unsigned o) -> unsigned long long { return static_cast<unsigned long long>(o) * S + shard; };
+  // (the counter's address is made opaque to the compiler's uniformity analysis: a draw by a uniform address is turned
+  // into one atomic plus a broadcast of its result, which would wait for the round trip right here)
+  auto draw = [&]() -> unsigned {
+    uint32_t line = shard * 32;
+    asm volatile("" : "+v"(line));
+    return atomicAdd(p.pool + line, 1u);
+  };
+  // the ordinal drawn by the group's leader one frame ago, for the whole group
+  auto drawn = [&](unsigned o) -> unsigned {
+    return obase + static_cast<unsigned>(__builtin_amdgcn_ds_bpermute((lane & ~(LPF - 1)) * 4, static_cast<int>(o)));
+  };
+  __shared__ uint2 ords[POOL ? GPW : 1];  // [lane group of the workgroup] = {frame being decoded, frame staged while it is}
+  uint2 &my_ords = ords[POOL ? wid * FPW + fl : 0];
+  unsigned opd = 0;  // the leader's draw for the frame after the staged one (valid in lane lam == 0 only)
+  // (SCMS1 with its bit words next to the messages uses the draw at once: one more register live across the row
+  //  block costs spills there)
+  constexpr bool PREDRAW = !(VARIANT == CC_ALG_SCMS1 && K * D < 160);
+  // round-3 deal
+  const unsigned long long ngroups = static_cast<unsigned long long>(gridDim.x) * GPW;
   auto ordinal_frame = [&](unsigned o) -> unsigned long long {
     return static_cast<unsigned long long>(blockIdx.x) * GPW + (o % GPW) + static_cast<unsigned long long>(o / GPW) * ngroups;
   };
@@ -388,8 +421,16 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
     o = static_cast<unsigned>(__builtin_amdgcn_ds_bpermute((lane & ~(LPF - 1)) * 4, static_cast<int>(o)));
     return ordinal_frame(o);
   };
-  unsigned long long frame = (static_cast<unsigned long long>(blockIdx.x) * 4 + wid) * FPW + fl;
-  unsigned long long nextf = frame + ngroups;  // staged while `frame` is being decoded
+  unsigned long long frame, nextf;  // (round-3 deal) the frame being decoded, the one staged while it is
+  if constexpr (POOL) {
+    const unsigned ofr = (blockIdx.x / S) * GPW + wid * FPW + fl;
+    if (lam == 0) my_ords = make_uint2(ofr, ofr + Ws * GPW);
+    frame = frame_of(ofr);
+    nextf = frame_of(ofr + Ws * GPW);
+  } else {
+    frame = (static_cast<unsigned long long>(blockIdx.x) * 4 + wid) * FPW + fl;
+    nextf = frame + ngroups;
+  }
   bool active = frame < B;
   unsigned it = 0;
   // SCMS2 (soft_decision.h:273-282) needs the previous variable->check message q of every edge AS A VALUE
@@ -518,6 +559,7 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     setup(frame);
     stage(nextf);
+    if (POOL && PREDRAW && lam == 0) opd = draw();
   }
 
   while (__any(active)) {
@@ -906,9 +948,10 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
 #endif
     const bool finished = SINGLE || ok || (it + 1 >= p.iterations);
     if (finished && active) {
-      const unsigned long long done = frame;
+      const uint2 od = POOL ? my_ords : make_uint2(0u, 0u);
+      const unsigned long long done = POOL ? frame_of(od.x) : frame;
       const unsigned done_it = ok ? it : p.iterations;  // (SINGLE without convergence: Iterations == 1)
-      frame = nextf;
+      frame = POOL ? frame_of(od.y) : nextf;
       active = frame < B;
       uint8_t *hp = hard + done * n + lam;
       float *Lp = Lout ? Lout + done * n + lam : nullptr;
@@ -968,8 +1011,18 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
         }
       }
       if (active) {  // after the reads of STG above have been consumed
-        nextf = take_frame();
-        stage(nextf);
+        if constexpr (POOL) {
+          if (!PREDRAW && lam == 0) opd = draw();
+          const unsigned nx = drawn(opd);
+          stage(frame_of(nx));
+          if (lam == 0) {
+            my_ords = make_uint2(od.y, nx);
+            if (PREDRAW) opd = draw();
+          }
+        } else {
+          nextf = take_frame();
+          stage(nextf);
+        }
       }
     } else {
       ++it;
@@ -1000,13 +1053,19 @@ int launch_diag_geometry(const cc_code *code, const MinSumParams &p, const float
     set_last_error("minsum_diag: only the last owned column of a lane may lie beyond the frame");
     return CC_ERR_UNSUPPORTED;
   }
+  if (p.pool == nullptr || B >= (1ull << 32)) {  // (frame ordinals are 32-bit words: B / S + 2 W_s GPW + draws)
+    set_last_error("minsum_diag: no frame pool, or more than 2^32 frames in one call");
+    return CC_ERR_UNSUPPORTED;
+  }
   const DiagGeometry g{0, 0, PARTIAL ? 1u : static_cast<unsigned>(LPF * D), D, LPF, CPL, SCMS};
   const size_t lds = minsum_diag_lds_bytes(g);
   const unsigned long long blocks_needed = (B + 4 * FPW - 1) / (4 * FPW);
-  unsigned long long per_cu = (160 * 1024) / lds;  // resident workgroups: LDS, then the register budget (OCC waves per SIMD)
+  // resident workgroups: LDS (+ the static ordinals of the frame pool), then the register budget (OCC waves per SIMD)
+  constexpr size_t ords_bytes = LPF == 16 ? 4 * FPW * sizeof(uint2) : 0;
+  unsigned long long per_cu = (160 * 1024) / (lds + ords_bytes);
   const unsigned long long occ = p.variant == CC_ALG_SCMS2 ? static_cast<unsigned long long>(OCC_S) : OCC;
   if ((p.variant == CC_ALG_SCMS2 && Q_ONLY_2) || (p.variant == CC_ALG_SCMS1 && Q_ONLY_1))
-    per_cu = (160 * 1024) / (lds + 4 * FPW * K * sizeof(uint2));  // + row_state (static)
+    per_cu = (160 * 1024) / (lds + ords_bytes + 4 * FPW * K * sizeof(uint2));  // + row_state (static)
   if (per_cu > occ) per_cu = occ;
   const unsigned long long max_grid = static_cast<unsigned long long>(code->num_cus) * per_cu;
   const int grid = static_cast<int>(blocks_needed < max_grid ? blocks_needed : max_grid);
