@@ -21,6 +21,7 @@ STOP_AS_SHIPPED, STOP_PUBLISHED, STOP_PARITY = 0, 1, 2
 DEVICE_CURRENT, DEVICE_NONE = -1, -2
 FRAME_OK, FRAME_NOT_CONVERGED, FRAME_LOCATOR, FRAME_RECHECK, FRAME_ERASURES = range(5)
 MC_FRAMES, MC_WORD_ERRORS, MC_BIT_ERRORS, MC_FAILURES, MC_UNDETECTED, MC_ITER_SUM, MC_CHANNEL_BIT_ERRORS = range(7)
+MC_CHANNEL_ERASURES = 7
 MC_ITER_HIST, MC_NCOUNTERS = 8, 64
 
 SOFT_ALGS = (ALG_MS, ALG_NMS, ALG_OMS, ALG_SCMS1, ALG_SCMS2, ALG_2DNMS)
@@ -76,6 +77,10 @@ _SIGNATURES = {
     "cc_mc_run_dev": (C.c_int, [_VP, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP, _VP]),
     "cc_awgn_llr_dev": (C.c_int, [_VP, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP, _VP, _VP]),
     "cc_sigma": (C.c_double, [_VP, C.c_double]),
+    "cc_mc_run_discrete_dev": (C.c_int, [_VP, C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP,
+                                         _VP]),
+    "cc_discrete_channel_dev": (C.c_int, [_VP, C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int,
+                                          _VP, _VP, _VP, _VP, _VP]),
     "cc_encode_batch_u16": (C.c_int, [_VP, _VP, _VP, C.c_size_t]),
     "cc_encode_batch_u16_dev": (C.c_int, [_VP, _VP, _VP, C.c_size_t, _VP]),
     "cc_correct_hard_batch_u16": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t]),

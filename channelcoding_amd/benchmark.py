@@ -1,8 +1,8 @@
 """Command line of the reference's simulation driver (src/simulation/benchmark.c++) on the GPU path.
 
-    python -m channelcoding_amd.benchmark [--simulation awgn|bitflip] [--algorithm NAME|all]...
+    python -m channelcoding_amd.benchmark [--simulation awgn|bitflip|bsc|bec] [--algorithm NAME|all]...
                                           [--k 5|6|7|all]... [--dmin 3|5|7|9|11|all]... [--seed N | --seed-time]
-                                          [--threads N] [--log-dir DIR]
+                                          [--threads N] [--log-dir DIR] [--p VALUE]... [--max-samples N]
 
 Same options, same decoder registry (benchmark.c++:23-166: primitive_bch<k, dmin<d>, A> for k in 5..7,
 d in 3,5,7,9 and the nine algorithm tags, min-sum family with 50 iterations, NMS 8/10, OMS 1/100) and the same
@@ -13,13 +13,17 @@ simulation and writes "<to_string()>.log" in the reference's two-column format.
 Where the reference spreads the decoders over a pool of CPU threads (--threads, :435-439), every simulation
 here is batched on the GPU; launched under torch.distributed.run the frames of each Eb/N0 point are sharded over
 the ranks' GPUs (montecarlo.awgn_simulation).  --threads is accepted and ignored.
+
+--simulation bsc / bec is new: the binary symmetric and the binary erasure channel the reference leaves as a TODO
+(montecarlo.discrete_simulation), over the points given with --p (default 10^(-k/4), k = 4 .. 16), each decoder
+writing "<to_string()>.<bsc|bec>.log".
 """
 import argparse
 import sys
 import time
 
 from . import codes as cc
-from .montecarlo import awgn_simulation, bitflip_simulation
+from .montecarlo import awgn_simulation, bitflip_simulation, discrete_simulation
 
 POWERS = (5, 6, 7)
 DISTANCES = (3, 5, 7, 9)
@@ -63,7 +67,8 @@ def reported_distances():
 
 
 def usage_text():
-    lines = ["--simulation [awgn|bitflip]  Choose the simulation to run. The default is AWGN.",
+    lines = ["--simulation [awgn|bitflip|bsc|bec]",
+             "                             Choose the simulation to run. The default is AWGN.",
              "--algorithm <name>           Choose algorithm:"]
     lines += ["  " + a for a in ALGORITHMS]
     lines += ["--k <num>                    Choose code length n = 2^k - 1;"] + ["  %d" % k for k in POWERS]
@@ -73,6 +78,9 @@ def usage_text():
               "--threads <num>              Accepted for compatibility; simulations are batched on the GPU(s).",
               "--stop-rule <0|1|2>          Min-sum stop rule: 0 as shipped, 1 published, 2 GF(2) parity (default).",
               "--log-dir <dir>              Where the <decoder>.log files go (default: current directory).",
+              "--p <value>                  bsc / bec: error / erasure probability of a point; may be given several",
+              "                             times. The default is 10^(-k/4) for k = 4 .. 16.",
+              "--max-samples <num>          awgn / bsc / bec: cap on the frames of one point.",
               "",
               "algorithm, k, and dmin can be specified multiple times.",
               "For all other options, giving them multiple times results in the last value being used."]
@@ -119,7 +127,8 @@ def main(argv=None):
     ap.add_argument("--stop-rule", type=int, default=2)
     ap.add_argument("--log-dir", default=".")
     ap.add_argument("--errors", type=int, default=0, help="bitflip: largest number of flipped bits")
-    ap.add_argument("--max-samples", type=int, default=None, help="awgn: cap on frames per Eb/N0 point")
+    ap.add_argument("--max-samples", type=int, default=None, help="awgn / bsc / bec: cap on frames per point")
+    ap.add_argument("--p", "-p", type=float, action="append", default=None, help="bsc / bec: channel probability")
     ap.add_argument("--help", "-h", action="store_true")
     args, unknown = ap.parse_known_args(argv)
     if args.help or unknown:
@@ -128,7 +137,7 @@ def main(argv=None):
         print(usage_text())
         return 1
     sim = args.simulation.lower()
-    if sim not in ("awgn", "bitflip"):
+    if sim not in ("awgn", "bitflip", "bsc", "bec"):
         print("Don't know the simulation type '%s'" % sim, file=sys.stderr)
         print(usage_text())
         return 1
@@ -157,6 +166,10 @@ def main(argv=None):
         t0 = time.perf_counter()
         if sim == "awgn":
             res = awgn_simulation(code, seed=seed, log_dir=args.log_dir, max_samples=args.max_samples)()
+            frames = sum(r["frames"] for r in res)
+        elif sim in ("bsc", "bec"):
+            res = discrete_simulation(code, sim, points=args.p, seed=seed, log_dir=args.log_dir,
+                                      max_samples=args.max_samples)()
             frames = sum(r["frames"] for r in res)
         else:
             if rank == 0:

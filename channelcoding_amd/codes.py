@@ -262,6 +262,29 @@ class cyclic:
     def sigma(self, ebno_db):
         return capi.lib().cc_sigma(self._h, float(ebno_db))
 
+    def discrete_channel(self, p_error, p_erasure, seed, first_frame, frames, random_codewords=False):
+        """Frames [first_frame, first_frame + frames) of the discrete memoryless channel (cc_discrete_channel_dev) on
+        the current device: a dict of torch tensors recv (frames, n) uint8, erasures (int16 positions, the CSR values
+        trimmed to off[-1]), erasure_offsets (frames + 1,) int32 and sent (frames, n) uint8.  With p_erasure > 0 the
+        int32 offsets bound one call to frames * n < 2^31 (ValueError otherwise: split the call)."""
+        import torch
+        frames = int(frames)
+        if p_erasure > 0 and frames * self.n >= 1 << 31:
+            raise ValueError("discrete_channel: frames * n must stay below 2^31 with erasures (int32 offsets)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        recv = torch.empty((frames, self.n), dtype=torch.uint8, device=dev)
+        sent = torch.empty((frames, self.n), dtype=torch.uint8, device=dev)
+        off = torch.zeros(frames + 1, dtype=torch.int32, device=dev)
+        er = torch.empty(max(1, frames * self.n), dtype=torch.int16, device=dev) if p_erasure > 0 else None
+        rc = capi.lib().cc_discrete_channel_dev(self._h, float(p_error), float(p_erasure), int(seed), int(first_frame),
+                                                frames, int(bool(random_codewords)), _ptr(recv), _ptr(er),
+                                                _ptr(off) if er is not None else None, _ptr(sent),
+                                                _stream_handle(recv))
+        capi.check(rc, "cc_discrete_channel_dev")
+        total = int(off[-1]) if er is not None else 0
+        erasures = er[:total] if er is not None else torch.empty(0, dtype=torch.int16, device=dev)
+        return dict(recv=recv, erasures=erasures, erasure_offsets=off, sent=sent)
+
     # ---- batch API (numpy host arrays or torch CUDA tensors) ----
     # ---- q > 8: 16-bit symbols (numpy uint16 on the host, torch int16 / uint16 on the device) ----
     def _wide_map(self, x, width_in, width_out, host_fn, dev_fn):

@@ -1248,6 +1248,59 @@ int cc_awgn_llr_dev(const cc_code *code, double ebno_db, uint64_t seed, uint64_t
                  static_cast<hipStream_t>(stream));
 }
 
+// the discrete channels serve every q <= 8 handle the decoders serve; the checks of the two entry points
+static int discrete_supported(const cc_code *code, double p_error, double p_erasure, int random_codewords) {
+  if (!std::isfinite(p_error) || !std::isfinite(p_erasure) || p_error < 0.0 || p_erasure < 0.0 ||
+      p_error + p_erasure > 1.0) {
+    set_last_error("p_error and p_erasure must be finite, >= 0 and sum to <= 1");
+    return CC_ERR_INVALID_ARGUMENT;
+  }
+  if (needs_code(code) != CC_OK) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = not_wide(code)) return rc;
+  if (code->device == CC_DEVICE_NONE) return CC_ERR_NO_DEVICE;
+  if (code->tab.family == CC_FAMILY_RS && (code->desc.mu != 1 || code->desc.step != 1)) {
+    set_last_error("RS error values on the device assume roots alpha^1..alpha^2t (mu = step = 1), as rs.h:55-69 does");
+    return CC_ERR_UNSUPPORTED;
+  }
+  if (p_erasure > 0.0 && code->desc.algorithm == CC_ALG_PGZ && code->tab.family == CC_FAMILY_RS) {
+    set_last_error("The PGZ-Algorithm does not support erasure decoding");  // hard_decision.h:66-68
+    return CC_ERR_UNSUPPORTED;
+  }
+  if (random_codewords && code->desc.coding != CC_CODING_DIVISION && code->desc.coding != CC_CODING_MULTIPLICATION)
+    return CC_ERR_INVALID_ARGUMENT;
+  return CC_OK;
+}
+
+int cc_mc_run_discrete_dev(const cc_code *code, double p_error, double p_erasure, uint64_t seed, uint64_t first_frame,
+                           size_t frames, int random_codewords, uint64_t *d_counters, void *stream) {
+  if (!code || !d_counters) return CC_ERR_INVALID_ARGUMENT;
+  const int rc = discrete_supported(code, p_error, p_erasure, random_codewords);
+  if (rc != CC_OK) return rc;
+  DeviceGuard guard(code->device);
+  return mc_run_discrete(const_cast<cc_code *>(code), p_error, p_erasure, seed, first_frame, frames, random_codewords,
+                         d_counters, static_cast<hipStream_t>(stream));
+}
+
+int cc_discrete_channel_dev(const cc_code *code, double p_error, double p_erasure, uint64_t seed, uint64_t first_frame,
+                            size_t frames, int random_codewords, uint8_t *d_recv, uint16_t *d_erasures,
+                            uint32_t *d_erasure_offsets, uint8_t *d_sent, void *stream) {
+  if (!code || (frames && !d_recv)) return CC_ERR_INVALID_ARGUMENT;
+  if ((d_erasures == nullptr) != (d_erasure_offsets == nullptr)) return CC_ERR_INVALID_ARGUMENT;
+  if (!d_erasures && p_erasure > 0.0) {
+    set_last_error("p_erasure > 0 needs the erasure list buffers");
+    return CC_ERR_INVALID_ARGUMENT;
+  }
+  if (d_erasures && static_cast<unsigned long long>(frames) * code->tab.n > 0xFFFFFFFFull) {
+    set_last_error("the erasure offsets are 32-bit: frames * n must stay below 2^32 in one call");
+    return CC_ERR_INVALID_ARGUMENT;
+  }
+  const int rc = discrete_supported(code, p_error, p_erasure, random_codewords);
+  if (rc != CC_OK) return rc;
+  DeviceGuard guard(code->device);
+  return mc_discrete(const_cast<cc_code *>(code), p_error, p_erasure, seed, first_frame, frames, random_codewords, d_recv,
+                     d_erasures, d_erasure_offsets, d_sent, static_cast<hipStream_t>(stream));
+}
+
 int cc_diag_table(const cc_code *code, uint16_t *out, size_t cap, uint32_t *D, uint32_t *LPF, uint32_t *links) {
   if (!code || !out) return -1;
   if (code->matrix_only || code->wide || !code->custom_H.empty()) return 0;

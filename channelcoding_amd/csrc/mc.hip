@@ -544,4 +544,411 @@ int mc_awgn(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, 
   return w.fence_out(stream);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Discrete memoryless channels (BSC, BEC, both at once; for RS the q-ary symmetric and the symbol erasure channel).
+//
+//   class     symbol j of global frame gf draws u = word (j & 3) of Philox counter (gf_lo, gf_hi, j >> 2, 2):
+//             u < E erased, E <= u < E + P in error, intact otherwise (E = round(p_erasure 2^32), P = round(p_error
+//             2^32), computed on the host in 64 bits).  Domains 0 (AWGN noise) and 1 (BCH message bits) are untouched.
+//   value     e = 1 + ((v (q_sym - 1)) >> 32), v = word (j & 3) of counter (gf_lo, gf_hi, j >> 2, 3): uniform over the
+//             non-zero symbols (always 1 for BCH).  Received = sent ^ e; an erased position receives 0.
+//   soft      min-sum handles take +1 / -1 for a received 0 / 1 (bitflip_simulation, simulation.c++:190-191) and +0.0f
+//             where erased: a zero LLR is what an erasure is to min-sum.
+//   messages  BCH: random_bits_kernel + launch_encode_bits (the words of cc_awgn_llr_dev for the same seed and frame);
+//             RS: symbol i = low q bits of word (i & 3) of counter (gf_lo, gf_hi, i >> 2, 4), then launch_encode.
+//   erasures  CSR for the hard decoders, built on the device: per-frame counts (channel kernel), an exclusive scan over
+//             the chunk (tiles of 1024 frames, then one workgroup over the tile sums), and a second pass that draws the
+//             same class words again and writes each frame's positions in ascending order.
+namespace {
+
+constexpr int SCAN_TILE = 1024;  // frames per workgroup of discrete_scan_tiles_kernel (4 per thread)
+
+// Sum over the lanes of a frame's group (G lanes, aligned inside the wavefront) of a per-lane count c in 0 .. 4, and the
+// part of it held by the group's lanes below this one: three ballots instead of a shuffle ladder.  Lanes of other
+// groups may be inactive (a group's frame loop ends on its own), they never enter the group's mask.
+struct GroupCount {
+  uint32_t total, below;
+};
+__device__ __forceinline__ GroupCount group_count(uint32_t c, int group_log2) {
+  const int lane = threadIdx.x & 63;
+  const unsigned long long group = (group_log2 == 6 ? ~0ull : ((1ull << (1 << group_log2)) - 1ull))
+                                   << (lane & ~((1 << group_log2) - 1));
+  const unsigned long long below = group & ((1ull << lane) - 1ull);
+  GroupCount r{0u, 0u};
+#pragma unroll
+  for (int b = 0; b < 3; ++b) {
+    const unsigned long long m = __ballot((c >> b) & 1u);
+    r.total += static_cast<uint32_t>(__popcll(m & group)) << b;
+    r.below += static_cast<uint32_t>(__popcll(m & below)) << b;
+  }
+  return r;
+}
+
+// The 4 bytes at base[at .. at + 4) as one little-endian word, read with aligned dword loads: frames are n bytes apart, so
+// three of four lanes' slices start off a dword boundary, where a single dword load would be an unaligned one.  Falls
+// back to byte loads where an aligned pair would reach outside [base, base + size).
+__device__ __forceinline__ uint32_t load4_aligned(const uint8_t *__restrict__ base, unsigned long long at,
+                                                  unsigned long long size) {
+  const uint32_t sh = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(base + at) & 3u);
+  if (at >= sh && at - sh + 8 <= size) {
+    const uint32_t *p = reinterpret_cast<const uint32_t *>(base + (at - sh));
+    const uint32_t w0 = p[0];
+    return sh ? __builtin_amdgcn_alignbyte(p[1], w0, sh) : w0;
+  }
+  return static_cast<uint32_t>(base[at]) | static_cast<uint32_t>(base[at + 1]) << 8 |
+         static_cast<uint32_t>(base[at + 2]) << 16 | static_cast<uint32_t>(base[at + 3]) << 24;
+}
+
+// G = lanes per frame (power of two >= ceil(n / 4)), lane q of a group owns symbols 4q .. 4q + 3, as in awgn_kernel.
+// Every lane of a group stays in the loop (also a lane with 4q >= n, which owns nothing) so that the group's erasure
+// count sees all of them.  soft != nullptr: +-1 / 0 floats, else bytes into recv; er_count: per-frame erasure counts
+// (nullptr: no erasure list wanted).  Channel errors (not erased) and erasures: one 64-bit atomic each per wavefront.
+__global__ void __launch_bounds__(256)
+discrete_kernel(float *__restrict__ soft, uint8_t *__restrict__ recv, uint32_t *__restrict__ er_count,
+                const uint8_t *__restrict__ sent, int n, int group_log2, uint32_t qm1, unsigned long long first_frame,
+                unsigned long long frames, unsigned long long E, unsigned long long EP, uint32_t k0, uint32_t k1,
+                unsigned long long *__restrict__ counters) {
+  const int G = 1 << group_log2;
+  const unsigned long long tid = static_cast<unsigned long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  const unsigned long long stride = (static_cast<unsigned long long>(gridDim.x) * blockDim.x) >> group_log2;
+  const int qd = static_cast<int>(tid & static_cast<unsigned long long>(G - 1));
+  const int j0 = 4 * qd, cnt = n - j0 < 4 ? (n - j0 > 0 ? n - j0 : 0) : 4;
+  unsigned c_err = 0, c_ers = 0;
+  for (unsigned long long f = tid >> group_log2; f < frames; f += stride) {
+    const unsigned long long gf = first_frame + f;
+    const uint32_t g0 = static_cast<uint32_t>(gf), g1 = static_cast<uint32_t>(gf >> 32);
+    unsigned erased = 0, wrong = 0;  // bit s: symbol j0 + s
+    if (cnt) {
+      const Philox u = philox4x32_10(g0, g1, static_cast<uint32_t>(qd), 2u, k0, k1);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const unsigned long long x = u.c[s];
+        erased |= (s < cnt && x < E) ? 1u << s : 0u;
+        wrong |= (s < cnt && x >= E && x < EP) ? 1u << s : 0u;
+      }
+      uint32_t e[4] = {1u, 1u, 1u, 1u};
+      if (wrong && qm1 > 1) {
+        const Philox v = philox4x32_10(g0, g1, static_cast<uint32_t>(qd), 3u, k0, k1);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) e[s] = 1u + static_cast<uint32_t>((static_cast<unsigned long long>(v.c[s]) * qm1) >> 32);
+      }
+      c_ers += static_cast<unsigned>(__builtin_popcount(erased));
+      c_err += static_cast<unsigned>(__builtin_popcount(wrong));
+      const unsigned long long at = f * n + j0;
+      uint32_t c[4] = {0u, 0u, 0u, 0u}, r[4];
+      if (sent) {
+        if (cnt == 4) {
+#pragma unroll
+          for (int s = 0; s < 4; ++s) c[s] = sent[at + s];
+        } else {
+          for (int s = 0; s < cnt; ++s) c[s] = sent[at + s];
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s) r[s] = ((erased >> s) & 1u) ? 0u : ((wrong >> s) & 1u) ? c[s] ^ e[s] : c[s];
+      if (cnt == 4) {
+        if (soft) {
+#pragma unroll
+          for (int s = 0; s < 4; ++s) soft[at + s] = ((erased >> s) & 1u) ? 0.0f : r[s] ? -1.0f : 1.0f;
+        } else {
+#pragma unroll
+          for (int s = 0; s < 4; ++s) recv[at + s] = static_cast<uint8_t>(r[s]);
+        }
+      } else {
+        for (int s = 0; s < cnt; ++s) {
+          if (soft) soft[at + s] = ((erased >> s) & 1u) ? 0.0f : r[s] ? -1.0f : 1.0f;
+          else recv[at + s] = static_cast<uint8_t>(r[s]);
+        }
+      }
+    }
+    if (er_count) {
+      const GroupCount gc = group_count(static_cast<uint32_t>(__builtin_popcount(erased)), group_log2);
+      if (qd == 0) er_count[f] = gc.total;
+    }
+  }
+  if (counters) {
+    for (int m = 32; m >= 1; m >>= 1) {
+      c_err += __shfl_xor(c_err, m, 64);
+      c_ers += __shfl_xor(c_ers, m, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+      if (c_err) atomicAdd(&counters[CC_MC_CHANNEL_BIT_ERRORS], static_cast<unsigned long long>(c_err));
+      if (c_ers) atomicAdd(&counters[CC_MC_CHANNEL_ERASURES], static_cast<unsigned long long>(c_ers));
+    }
+  }
+}
+
+__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t x) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t t = __shfl_up(x, d, 64);
+    if (lane >= d) x += t;
+  }
+  return x;
+}
+
+// local[f] = exclusive prefix of count[] inside f's tile of SCAN_TILE frames; tile_sum[tile] = the tile's total
+__global__ void __launch_bounds__(256)
+discrete_scan_tiles_kernel(const uint32_t *__restrict__ count, uint32_t *__restrict__ local,
+                           uint32_t *__restrict__ tile_sum, unsigned long long frames) {
+  __shared__ uint32_t wsum[4];
+  const unsigned long long f0 = static_cast<unsigned long long>(blockIdx.x) * SCAN_TILE + 4 * threadIdx.x;
+  uint32_t c[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) c[i] = f0 + i < frames ? count[f0 + i] : 0u;
+  const uint32_t s = c[0] + c[1] + c[2] + c[3];
+  const uint32_t x = wave_inclusive_scan(s);
+  const int wid = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 63) wsum[wid] = x;
+  __syncthreads();
+  uint32_t e = x - s;
+  for (int w = 0; w < wid; ++w) e += wsum[w];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if (f0 + i < frames) local[f0 + i] = e;
+    e += c[i];
+  }
+  if (threadIdx.x == 255) tile_sum[blockIdx.x] = e;
+}
+
+// one workgroup: tile_sum[] (at most 1024 tiles) -> exclusive tile bases, plus *carry (the entries already listed by
+// earlier chunks of the same call, nullptr: none); *total = carry + all erasures of the chunk
+__global__ void __launch_bounds__(1024)
+discrete_scan_sums_kernel(uint32_t *__restrict__ tile_sum, unsigned ntiles, const uint32_t *carry, uint32_t *total) {
+  __shared__ uint32_t wsum[16];
+  const uint32_t s = threadIdx.x < ntiles ? tile_sum[threadIdx.x] : 0u;
+  const uint32_t x = wave_inclusive_scan(s);
+  const int wid = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 63) wsum[wid] = x;
+  __syncthreads();
+  uint32_t e = (carry ? *carry : 0u) + x - s;
+  for (int w = 0; w < wid; ++w) e += wsum[w];
+  if (threadIdx.x < ntiles) tile_sum[threadIdx.x] = e;
+  if (threadIdx.x == 1023) *total = e + s;
+}
+
+// off[f] = local[f] + tile_base[f / SCAN_TILE]; the frame's erased positions (the class words of discrete_kernel drawn
+// again) go to erasures[off[f] ..] in ascending order: lane q's share starts after the erasures of lanes 0 .. q-1 of its
+// group.  Frames without erasures skip the draw.
+__global__ void __launch_bounds__(256)
+discrete_positions_kernel(uint16_t *__restrict__ erasures, uint32_t *__restrict__ off, const uint32_t *__restrict__ count,
+                          const uint32_t *__restrict__ local, const uint32_t *__restrict__ tile_base, int n,
+                          int group_log2, unsigned long long first_frame, unsigned long long frames,
+                          unsigned long long E, uint32_t k0, uint32_t k1) {
+  const int G = 1 << group_log2;
+  const unsigned long long tid = static_cast<unsigned long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  const unsigned long long stride = (static_cast<unsigned long long>(gridDim.x) * blockDim.x) >> group_log2;
+  const int qd = static_cast<int>(tid & static_cast<unsigned long long>(G - 1));
+  const int j0 = 4 * qd, cnt = n - j0 < 4 ? (n - j0 > 0 ? n - j0 : 0) : 4;
+  for (unsigned long long f = tid >> group_log2; f < frames; f += stride) {
+    const uint32_t base = local[f] + tile_base[f / SCAN_TILE];
+    if (qd == 0) off[f] = base;
+    if (count[f] == 0) continue;  // uniform over the group
+    const unsigned long long gf = first_frame + f;
+    unsigned erased = 0;
+    if (cnt) {
+      const Philox u = philox4x32_10(static_cast<uint32_t>(gf), static_cast<uint32_t>(gf >> 32),
+                                     static_cast<uint32_t>(qd), 2u, k0, k1);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) erased |= (s < cnt && static_cast<unsigned long long>(u.c[s]) < E) ? 1u << s : 0u;
+    }
+    uint16_t *dst = erasures + base + group_count(static_cast<uint32_t>(__builtin_popcount(erased)), group_log2).below;
+    for (int s = 0; s < cnt; ++s)
+      if ((erased >> s) & 1u) *dst++ = static_cast<uint16_t>(j0 + s);
+  }
+}
+
+// RS messages: symbol i of frame f = the low q bits of word (i & 3) of Philox counter (f, i >> 2, 4)
+__global__ void __launch_bounds__(256)
+random_symbols_kernel(uint8_t *__restrict__ msg, int l, int group_log2, uint32_t mask, unsigned long long first_frame,
+                      unsigned long long frames, uint32_t k0, uint32_t k1) {
+  const int G = 1 << group_log2;
+  const unsigned long long tid = static_cast<unsigned long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  const unsigned long long stride = (static_cast<unsigned long long>(gridDim.x) * blockDim.x) >> group_log2;
+  const int qd = static_cast<int>(tid & static_cast<unsigned long long>(G - 1));
+  if (4 * qd >= l) return;
+  const int cnt = l - 4 * qd < 4 ? l - 4 * qd : 4;
+  for (unsigned long long f = tid >> group_log2; f < frames; f += stride) {
+    const unsigned long long gf = first_frame + f;
+    const Philox p = philox4x32_10(static_cast<uint32_t>(gf), static_cast<uint32_t>(gf >> 32), static_cast<uint32_t>(qd),
+                                   4u, k0, k1);
+    uint8_t *dst = msg + f * l + 4 * qd;
+    for (int s = 0; s < cnt; ++s) dst[s] = static_cast<uint8_t>(p.c[s] & mask);
+  }
+}
+
+int log2_lanes(int symbols) {  // smallest G = 2^k with 4 G >= symbols
+  int g = 0;
+  while ((4 << g) < symbols) ++g;
+  return g;
+}
+
+struct DiscreteThresholds {
+  unsigned long long E, EP;  // erased below E, in error in [E, EP)
+};
+
+DiscreteThresholds discrete_thresholds(double p_error, double p_erasure) {
+  const unsigned long long E = static_cast<unsigned long long>(std::llround(p_erasure * 4294967296.0));
+  const unsigned long long P = static_cast<unsigned long long>(std::llround(p_error * 4294967296.0));
+  return DiscreteThresholds{E, E + P};
+}
+
+// transmitted words of frames [first, first + frames): BCH as on the AWGN route, RS from message symbols (domain 4)
+int launch_discrete_sent(const cc_code *code, uint64_t seed, uint64_t first_frame, size_t frames, uint8_t *d_sent,
+                         uint8_t *d_msg_scratch, hipStream_t stream) {
+  if (code->tab.family != CC_FAMILY_RS)
+    return launch_sent_words(code, seed, first_frame, frames, d_sent, d_msg_scratch, stream);
+  const int l = static_cast<int>(code->tab.l), g = log2_lanes(l);
+  const unsigned long long items = static_cast<unsigned long long>(frames) << g;
+  hipLaunchKernelGGL(random_symbols_kernel, dim3(grid_for(code, items)), dim3(256), 0, stream, d_msg_scratch, l, g,
+                     (1u << code->tab.q) - 1u, static_cast<unsigned long long>(first_frame),
+                     static_cast<unsigned long long>(frames), static_cast<uint32_t>(seed),
+                     static_cast<uint32_t>(seed >> 32));
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "random symbols kernel launch");
+  return launch_encode(code, d_msg_scratch, d_sent, frames, stream);
+}
+
+// The channel over frames [first, first + m), m <= 2^20 (the scan's two levels cover 1024 x 1024 frames).  er != nullptr:
+// the erasure CSR into er / off[0 .. m], with count, local (m words each) and tiles (m / 1024 + 1 words) as scratch and
+// carry = the entries already in er (nullptr: 0).
+struct DiscreteIO {
+  float *soft = nullptr;
+  uint8_t *recv = nullptr;
+  uint16_t *er = nullptr;
+  uint32_t *off = nullptr, *count = nullptr, *local = nullptr, *tiles = nullptr;
+  const uint32_t *carry = nullptr;
+};
+
+int launch_discrete(const cc_code *code, DiscreteThresholds th, uint64_t seed, uint64_t first_frame, size_t m,
+                    const uint8_t *sent, const DiscreteIO &io, unsigned long long *d_counters, hipStream_t stream) {
+  const int n = static_cast<int>(code->tab.n), g = log2_lanes(n);
+  const uint32_t qm1 = code->tab.family == CC_FAMILY_RS ? (1u << code->tab.q) - 1u : 1u;
+  const uint32_t k0 = static_cast<uint32_t>(seed), k1 = static_cast<uint32_t>(seed >> 32);
+  const unsigned long long first = first_frame, frames = m, items = frames << g;
+  const int grid = grid_for(code, items);
+  hipLaunchKernelGGL(discrete_kernel, dim3(grid), dim3(256), 0, stream, io.soft, io.recv, io.er ? io.count : nullptr,
+                     sent, n, g, qm1, first, frames, th.E, th.EP, k0, k1, d_counters);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "discrete channel kernel launch");
+  if (!io.er) return CC_OK;
+  const unsigned ntiles = static_cast<unsigned>((frames + SCAN_TILE - 1) / SCAN_TILE);
+  hipLaunchKernelGGL(discrete_scan_tiles_kernel, dim3(ntiles), dim3(256), 0, stream, io.count, io.local, io.tiles, frames);
+  hipLaunchKernelGGL(discrete_scan_sums_kernel, dim3(1), dim3(1024), 0, stream, io.tiles, ntiles, io.carry, io.off + m);
+  hipLaunchKernelGGL(discrete_positions_kernel, dim3(grid), dim3(256), 0, stream, io.er, io.off, io.count, io.local,
+                     io.tiles, n, g, first, frames, th.E, k0, k1);
+  e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "erasure list kernel launch");
+  return CC_OK;
+}
+
+constexpr size_t DISCRETE_CHUNK = size_t(1) << 20;  // the scan's reach: SCAN_TILE x 1024 frames
+
+}  // namespace
+
+// Monte-Carlo over the discrete channel: the route of mc_run (lock, workspace, chunks, one counting pass).  Inside the
+// workspace's 4 n bytes per frame of w.llr: the received bytes (n per frame) and, 16-byte aligned behind them, the
+// erasure positions (at most 2 n bytes per frame) -- or the +-1 / 0 floats of a min-sum handle.  Erasure counts and
+// tile-local prefixes use w.nerr / w.status before the decoder writes them, the offsets and tile sums w.list.
+int mc_run_discrete(cc_code *code, double p_error, double p_erasure, uint64_t seed, uint64_t first_frame, size_t frames,
+                    int random_codewords, uint64_t *d_counters, hipStream_t stream) {
+  if (frames == 0) return CC_OK;
+  const size_t chunk = frames < DISCRETE_CHUNK ? frames : DISCRETE_CHUNK;
+  if (!code->mc) code->mc = new McWorkspace();
+  std::lock_guard<std::mutex> guard(code->mc->lock);
+  int rc = ensure_workspace(code, chunk < 16 ? 16 : chunk);  // >= 16 frames: bytes + aligned positions fit in 4 n
+  if (rc != CC_OK) return rc;
+  McWorkspace &w = *code->mc;
+  rc = w.fence_in(stream);
+  if (rc != CC_OK) return rc;
+  const size_t n = code->tab.n;
+  const DiscreteThresholds th = discrete_thresholds(p_error, p_erasure);
+  unsigned long long *counters = reinterpret_cast<unsigned long long *>(d_counters);
+  for (size_t done = 0; done < frames; done += chunk) {
+    const size_t m = frames - done < chunk ? frames - done : chunk;
+    uint8_t *sent = random_codewords ? w.sent : nullptr;
+    if (random_codewords) {
+      rc = launch_discrete_sent(code, seed, first_frame + done, m, w.sent, w.msg, stream);
+      if (rc != CC_OK) return rc;
+    }
+    DiscreteIO io;
+    if (code->soft) {
+      io.soft = w.llr;
+    } else {
+      io.recv = reinterpret_cast<uint8_t *>(w.llr);
+      if (th.E) {  // (no erasure can be drawn with E = 0: no list, NULL erasures for the decoder)
+        io.er = reinterpret_cast<uint16_t *>(io.recv + ((m * n + 15) & ~size_t(15)));
+        io.off = w.list;
+        io.tiles = w.list + m + 1;
+        io.count = reinterpret_cast<uint32_t *>(w.nerr);
+        io.local = reinterpret_cast<uint32_t *>(w.status);
+      }
+    }
+    rc = launch_discrete(code, th, seed, first_frame + done, m, sent, io, counters, stream);
+    if (rc != CC_OK) return rc;
+    if (code->soft)
+      rc = launch_minsum(code, w.llr, nullptr, nullptr, w.hard, nullptr, w.iters, w.status, m, stream);
+    else if (io.er && code->desc.algorithm == CC_ALG_PGZ)  // the BCH two-trial rule, as cc_correct_hard_batch_dev
+      rc = launch_pgz_erasures(code, io.recv, io.er, io.off, w.hard, w.nerr, w.status, m, stream);
+    else
+      rc = launch_algebraic(code, false, io.recv, io.er, io.off, w.hard, w.nerr, w.status, m, stream);
+    if (rc != CC_OK) return rc;
+    const unsigned long long blocks = (m + 15) / 16;
+    const unsigned long long max_grid = static_cast<unsigned long long>(code->num_cus) * 8;
+    hipLaunchKernelGGL(count_kernel, dim3(static_cast<int>(blocks < max_grid ? blocks : max_grid)), dim3(256), 0, stream,
+                       w.hard, sent, code->soft ? w.iters : nullptr, w.status, static_cast<int>(n),
+                       code->desc.iterations, static_cast<unsigned long long>(m), counters);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "count kernel launch");
+  }
+  return w.fence_out(stream);
+}
+
+// cc_discrete_channel_dev: channel only, chunked; the erasure list of the whole call is one CSR (each chunk's scan
+// starts from the entries of the chunks before it, read on the device)
+int mc_discrete(cc_code *code, double p_error, double p_erasure, uint64_t seed, uint64_t first_frame, size_t frames,
+                int random_codewords, uint8_t *d_recv, uint16_t *d_erasures, uint32_t *d_erasure_offsets,
+                uint8_t *d_sent, hipStream_t stream) {
+  if (frames == 0) {
+    if (d_erasure_offsets) CC_HIP_TRY(hipMemsetAsync(d_erasure_offsets, 0, sizeof(uint32_t), stream));
+    return CC_OK;
+  }
+  const size_t chunk = frames < DISCRETE_CHUNK ? frames : DISCRETE_CHUNK;
+  if (!code->mc) code->mc = new McWorkspace();
+  std::lock_guard<std::mutex> guard(code->mc->lock);
+  int rc = ensure_workspace(code, chunk);
+  if (rc != CC_OK) return rc;
+  McWorkspace &w = *code->mc;
+  rc = w.fence_in(stream);
+  if (rc != CC_OK) return rc;
+  const size_t n = code->tab.n;
+  const DiscreteThresholds th = discrete_thresholds(p_error, p_erasure);
+  for (size_t done = 0; done < frames; done += chunk) {
+    const size_t m = frames - done < chunk ? frames - done : chunk;
+    uint8_t *sent = d_sent ? d_sent + done * n : nullptr;
+    if (random_codewords) {
+      if (!sent) sent = w.sent;
+      rc = launch_discrete_sent(code, seed, first_frame + done, m, sent, w.msg, stream);
+      if (rc != CC_OK) return rc;
+    } else if (sent) {
+      CC_HIP_TRY(hipMemsetAsync(sent, 0, m * n, stream));
+      sent = nullptr;  // all-zero transmission: the channel kernel reads no word
+    }
+    DiscreteIO io;
+    io.recv = d_recv + done * n;
+    if (d_erasures) {
+      io.er = d_erasures;
+      io.off = d_erasure_offsets + done;
+      io.tiles = w.list;
+      io.count = reinterpret_cast<uint32_t *>(w.nerr);
+      io.local = reinterpret_cast<uint32_t *>(w.status);
+      io.carry = done ? d_erasure_offsets + done : nullptr;
+    }
+    rc = launch_discrete(code, th, seed, first_frame + done, m, sent, io, nullptr, stream);
+    if (rc != CC_OK) return rc;
+  }
+  return w.fence_out(stream);
+}
+
 }  // namespace ccamd

@@ -1,4 +1,4 @@
-"""Batched AWGN Monte-Carlo harness, sharded over the GPUs of one node.
+"""Batched AWGN (and discrete-channel) Monte-Carlo harness, sharded over the GPUs of one node.
 
 Replaces ``awgn_simulation`` (src/simulation/simulation.h:71-83, simulation.c++:83-150 of the
 reference).  What is kept: the Eb/N0 ladder (start just above the Shannon limit of the code's rate,
@@ -12,6 +12,9 @@ What is new: frames of one point are independent, so rank r of W decodes the con
 device from (seed, global frame index)), and ONE all-reduce (RCCL over xGMI for CUDA tensors, gloo on
 CPU) of the 64-word counter vector per point gives every rank the totals -- which the adaptive sample
 count of the next point needs.  Totals are bit-identical for any number of ranks.
+
+discrete_simulation runs the same harness over the BSC, the BEC or both at once (cc_mc_run_discrete_dev; for RS codes
+the q-ary symmetric and the symbol erasure channel), on a ladder of channel probabilities.
 
 The ladder's start point follows the reference's own Shannon-limit look-up ``ebno()`` (simulation.c++:21-70)
 including its indexing (see `reference_ebno`), so every "<decoder>.log" starts on the line the reference's does.
@@ -134,7 +137,87 @@ class DeviceBackend:
         return counters  # stays on the device: reduced with RCCL
 
 
-class awgn_simulation:
+class _ShardedSimulation:
+    """What the AWGN and the discrete-channel ladders share: the shard of this rank, the one all-reduce per point,
+    rank 0's log file (its success agreed with every rank before the first collective) and the adaptive ladder."""
+
+    counter_names = COUNTER_NAMES
+
+    def _dist(self):
+        try:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized():
+                return dist
+        except ImportError:
+            pass
+        return None
+
+    def _counters(self, point, frames, point_index):
+        """The reduced counters of `frames` frames of one point, sharded over the ranks."""
+        dist = self._dist()
+        rank, world = (dist.get_rank(), dist.get_world_size()) if dist else (0, 1)
+        first, count = shard(frames, rank, world)
+        # every point draws from its own stretch of the global frame sequence
+        base = point_index << 40
+        counters = self.backend.run(point, self.seed, base + first, count)
+        if dist:
+            dist.all_reduce(counters, op=dist.ReduceOp.SUM)  # the path's only exchange step
+        c = counters.cpu().numpy() if hasattr(counters, "cpu") else np.asarray(counters)
+        res = {k: int(c[i]) for k, i in self.counter_names.items()}
+        res["iter_hist"] = [int(v) for v in c[capi.MC_ITER_HIST:]]
+        return res
+
+    def _agree(self, ok, seed):
+        """Rank 0's decision (log file opened or not) and its seed, made known to every rank BEFORE the first
+        collective of the ladder: a rank that raised alone would leave the others blocked in the all-reduce."""
+        dist = self._dist()
+        if dist is None:
+            return ok, seed
+        import torch
+        device = getattr(self.backend, "device", None)
+        if device is None or dist.get_backend() != "nccl":
+            device = "cpu"
+        # the seed travels as two 31-bit halves + sign-free high part: int64 holds any 64-bit seed bit pattern
+        t = torch.tensor([int(ok), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=torch.int64, device=device)
+        dist.broadcast(t, src=0)
+        v = t.cpu().tolist()
+        return bool(v[0]), int(v[1]) | (int(v[2]) << 32)
+
+    def _ladder(self, log_name, column, row_value):
+        """Every point of self.points() with the adaptive sample count; rank 0 writes the reference-format log
+        `log_name` whose first column, headed `column`, shows row_value(point)."""
+        dist = self._dist()
+        rank = dist.get_rank() if dist else 0
+        log, error = None, None
+        if self.log_dir is not None and rank == 0:
+            path = os.path.join(self.log_dir, log_name)
+            try:
+                if os.path.exists(path):
+                    raise RuntimeError("File %s already exists." % path)  # simulation.c++:72-81
+                log = open(path, "w")
+                log.write("%7s %21s\n" % (column, "wer"))
+            except (OSError, RuntimeError) as e:
+                error = e
+        ok, self.seed = self._agree(error is None, self.seed)
+        if not ok:  # every rank leaves together
+            raise error if error is not None else RuntimeError("rank 0 could not open the log file")
+        wer, results = 0.5, []
+        for idx, point in enumerate(self.points()):
+            n = samples(wer) if self.samples_per_point is None else int(self.samples_per_point)
+            if self.max_samples:
+                n = min(n, self.max_samples)
+            res = self.run_point(point, n, idx)
+            results.append(res)
+            wer = res["wer"]
+            if log:
+                log.write("%7s %s\n" % ("%.6g" % row_value(point), "%16.15e" % res["wer"]))
+                log.flush()
+        if log:
+            log.close()
+        return results
+
+
+class awgn_simulation(_ShardedSimulation):
     """awgn_simulation(decoder, step = 0.5, seed = 0) -- simulation.h:71-83."""
 
     def __init__(self, code, step=0.5, seed=0, random_codewords=False, backend=None, log_dir=None,
@@ -157,80 +240,115 @@ class awgn_simulation:
             e += self.step
         return out
 
-    def _dist(self):
-        try:
-            import torch.distributed as dist
-            if dist.is_available() and dist.is_initialized():
-                return dist
-        except ImportError:
-            pass
-        return None
-
     def run_point(self, ebno_db, frames, point_index=0):
         """Decode `frames` frames of one Eb/N0 point, sharded over the ranks; returns the reduced counters."""
-        dist = self._dist()
-        rank, world = (dist.get_rank(), dist.get_world_size()) if dist else (0, 1)
-        first, count = shard(frames, rank, world)
-        # every point draws from its own stretch of the global frame sequence
-        base = point_index << 40
-        counters = self.backend.run(ebno_db, self.seed, base + first, count)
-        if dist:
-            dist.all_reduce(counters, op=dist.ReduceOp.SUM)  # the path's only exchange step
-        c = counters.cpu().numpy() if hasattr(counters, "cpu") else np.asarray(counters)
-        res = {k: int(c[i]) for k, i in COUNTER_NAMES.items()}
-        res["iter_hist"] = [int(v) for v in c[capi.MC_ITER_HIST:]]
+        res = self._counters(ebno_db, frames, point_index)
         res["ebno"] = ebno_db
         res["wer"] = res["word_errors"] / max(1, res["frames"])
         res["ber"] = res["bit_errors"] / max(1, res["frames"] * self.code.n)
         return res
 
-    def _agree(self, ok, seed):
-        """Rank 0's decision (log file opened or not) and its seed, made known to every rank BEFORE the first
-        collective of the ladder: a rank that raised alone would leave the others blocked in the all-reduce."""
-        dist = self._dist()
-        if dist is None:
-            return ok, seed
-        import torch
-        device = getattr(self.backend, "device", None)
-        if device is None or dist.get_backend() != "nccl":
-            device = "cpu"
-        # the seed travels as two 31-bit halves + sign-free high part: int64 holds any 64-bit seed bit pattern
-        t = torch.tensor([int(ok), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=torch.int64, device=device)
-        dist.broadcast(t, src=0)
-        v = t.cpu().tolist()
-        return bool(v[0]), int(v[1]) | (int(v[2]) << 32)
-
     def __call__(self):
         """awgn_simulation::operator()(): the whole ladder; rank 0 writes the reference-format log."""
-        dist = self._dist()
-        rank = dist.get_rank() if dist else 0
-        log, error = None, None
-        if self.log_dir is not None and rank == 0:
-            path = os.path.join(self.log_dir, self.code.to_string() + ".log")
-            try:
-                if os.path.exists(path):
-                    raise RuntimeError("File %s already exists." % path)  # simulation.c++:72-81
-                log = open(path, "w")
-                log.write("%7s %21s\n" % ("ebno", "wer"))
-            except (OSError, RuntimeError) as e:
-                error = e
-        ok, self.seed = self._agree(error is None, self.seed)
-        if not ok:  # every rank leaves together
-            raise error if error is not None else RuntimeError("rank 0 could not open the log file")
-        wer, results = 0.5, []
-        for idx, ebno in enumerate(self.points()):
-            n = samples(wer) if self.samples_per_point is None else int(self.samples_per_point)
-            if self.max_samples:
-                n = min(n, self.max_samples)
-            res = self.run_point(ebno, n, idx)
-            results.append(res)
-            wer = res["wer"]
-            if log:
-                log.write("%7s %s\n" % ("%.6g" % ebno, "%16.15e" % res["wer"]))
-                log.flush()
-        if log:
-            log.close()
-        return results
+        return self._ladder(self.code.to_string() + ".log", "ebno", lambda ebno: ebno)
+
+
+# ---- discrete memoryless channels (cc_mc_run_discrete_dev): the BSC and BEC the reference's README leaves as a TODO --
+CHANNELS = ("bsc", "bec", "bsec")
+DISCRETE_COUNTER_NAMES = dict(COUNTER_NAMES, channel_erasures=capi.MC_CHANNEL_ERASURES)
+
+
+def discrete_ladder():
+    """The default points: 10^(-k/4) for k = 4 .. 16, from 0.1 down to 1e-4 (noisiest first)."""
+    return [10.0 ** (-k / 4.0) for k in range(4, 17)]
+
+
+def channel_probabilities(channel, point):
+    """(p_error, p_erasure) of one point: p for bsc, the erasure probability for bec, a (p, erasure) pair for bsec;
+    ValueError unless both are finite, >= 0 and sum to <= 1 (the device's own check, made before any collective)."""
+    if channel == "bsc":
+        p, e = float(point), 0.0
+    elif channel == "bec":
+        p, e = 0.0, float(point)
+    elif channel == "bsec":
+        p, e = (float(v) for v in point)
+    else:
+        raise ValueError("unknown channel %r (one of %s)" % (channel, ", ".join(CHANNELS)))
+    if not (math.isfinite(p) and math.isfinite(e) and p >= 0.0 and e >= 0.0 and p + e <= 1.0):
+        raise ValueError("bad channel point %r: probabilities must be finite, >= 0 and sum to <= 1" % (point,))
+    return p, e
+
+
+class DiscreteBackend:
+    """Counts one shard of one channel point on this rank's GPU through cc_mc_run_discrete_dev."""
+
+    def __init__(self, code, channel="bsc", random_codewords=False):
+        import torch
+        self.torch = torch
+        self.code = code
+        self.channel = channel
+        self.random_codewords = bool(random_codewords)
+        self.device = torch.device("cuda", torch.cuda.current_device())
+
+    def run(self, point, seed, first_frame, frames):
+        torch = self.torch
+        p_error, p_erasure = channel_probabilities(self.channel, point)
+        counters = torch.zeros(capi.MC_NCOUNTERS, dtype=torch.int64, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = capi.lib().cc_mc_run_discrete_dev(self.code._h, p_error, p_erasure, int(seed), int(first_frame),
+                                               int(frames), int(self.random_codewords),
+                                               C.c_void_p(counters.data_ptr()), stream)
+        capi.check(rc, "cc_mc_run_discrete_dev")
+        return counters  # stays on the device: reduced with RCCL
+
+
+class discrete_simulation(_ShardedSimulation):
+    """Word-error rate over a ladder of discrete-channel points, sharded like awgn_simulation.
+
+    channel "bsc": points are error probabilities p; "bec": erasure probabilities; "bsec": (p, erasure) pairs.  For RS
+    codes the same points give the q-ary symmetric and the symbol erasure channel.  Default points: discrete_ladder()
+    (for bsec the pairs (x, x)).  Rank 0 writes "<to_string()>.<channel>.log", its first column the point's p (the
+    erasure probability for bec).
+
+    Random codewords by default, unlike awgn_simulation: an erased position receives 0, which for the all-zero word is
+    the symbol sent, so a decoder that reads erased positions as they are (RS BM / Euklid, BCH BM / Euklid, min-sum)
+    would see a codeword in every frame without errors, whatever the number of erasures."""
+
+    counter_names = DISCRETE_COUNTER_NAMES
+
+    def __init__(self, code, channel="bsc", points=None, seed=0, random_codewords=True, backend=None, log_dir=None,
+                 max_samples=None, samples_per_point=None):
+        self.channel = str(channel).lower()
+        if self.channel not in CHANNELS:
+            raise ValueError("unknown channel %r (one of %s)" % (channel, ", ".join(CHANNELS)))
+        if points is None:
+            points = discrete_ladder()
+            if self.channel == "bsec":
+                points = [(x, x) for x in points]
+        self._points = [tuple(pt) if self.channel == "bsec" else float(pt) for pt in points]
+        for pt in self._points:
+            channel_probabilities(self.channel, pt)
+        self.code = code
+        self.seed = int(seed)
+        self.backend = backend if backend is not None else DiscreteBackend(code, self.channel, random_codewords)
+        self.log_dir = log_dir
+        self.max_samples = max_samples
+        self.samples_per_point = samples_per_point
+
+    def points(self):
+        return list(self._points)
+
+    def run_point(self, point, frames, point_index=0):
+        """Decode `frames` frames of one channel point, sharded over the ranks; returns the reduced counters."""
+        res = self._counters(point, frames, point_index)
+        res["p_error"], res["p_erasure"] = channel_probabilities(self.channel, point)
+        res["wer"] = res["word_errors"] / max(1, res["frames"])
+        res["ber"] = res["bit_errors"] / max(1, res["frames"] * self.code.n)  # wrong symbols per symbol for RS
+        return res
+
+    def __call__(self):
+        row = (lambda pt: pt[0]) if self.channel == "bsec" else (lambda pt: pt)
+        return self._ladder("%s.%s.log" % (self.code.to_string(), self.channel), "p", row)
 
 
 class bitflip_simulation:

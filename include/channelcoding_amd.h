@@ -222,8 +222,10 @@ enum {
   CC_MC_FAILURES = 3,    /* decoder reported failure                                                      */
   CC_MC_UNDETECTED = 4,  /* decoder reported success with a wrong word                                    */
   CC_MC_ITER_SUM = 5,    /* sum of iterations run (min-sum), 0 for algebraic                              */
-  CC_MC_CHANNEL_BIT_ERRORS = 6, /* raw hard-decision errors before decoding                               */
-  CC_MC_RESERVED = 7,
+  CC_MC_CHANNEL_BIT_ERRORS = 6, /* raw hard-decision errors before decoding (discrete channels: symbols drawn
+                                   in error and not erased)                                                   */
+  CC_MC_CHANNEL_ERASURES = 7,   /* symbols erased by the channel (discrete channels; 0 on the AWGN route)   */
+  CC_MC_RESERVED = CC_MC_CHANNEL_ERASURES, /* the slot's former name                                          */
   CC_MC_ITER_HIST = 8,   /* [8 + i] = frames that returned at iteration index i, i <= 55                  */
   CC_MC_NCOUNTERS = 64
 };
@@ -233,6 +235,38 @@ int cc_mc_run_dev(const cc_code *code, double ebno_db, uint64_t seed, uint64_t f
 int cc_awgn_llr_dev(const cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
                     int random_codewords, float *d_llr, uint8_t *d_sent, void *stream);
 double cc_sigma(const cc_code *code, double ebno_db); /* simulation.c++:83-85 */
+
+/* ---- batched Monte-Carlo over discrete memoryless channels: the BSC and the BEC the reference's README leaves as a
+ *      TODO, both at once, and for RS codes the q-ary symmetric and the symbol erasure channel.  A symbol is erased
+ *      with probability p_erasure, in error with probability p_error, intact otherwise (both finite, >= 0, sum <= 1).
+ *      Symbol j of global frame gf draws u = word (j & 3) of Philox4x32-10, counter (gf_lo, gf_hi, j >> 2, 2), key
+ *      (seed_lo, seed_hi): u < E erased, E <= u < E + P in error, with E = round(p_erasure 2^32), P = round(p_error
+ *      2^32) in 64 bits.  An error adds e = 1 + ((v (q_sym - 1)) >> 32), v = word (j & 3) of counter (.., j >> 2, 3):
+ *      uniform over the non-zero symbols of GF(2^q) (q_sym = 2^q for RS, 2 for BCH, where e = 1).  Received symbol =
+ *      sent ^ e; an erased position receives 0 (the decoders ignore it: cyclic.h:261-262, the two-trial rule of
+ *      bch.h:97-149 fills it itself).  Min-sum handles decode +1 / -1 for a received 0 / 1 (simulation.c++:190-191)
+ *      and +0.0 where erased; hard handles the received symbols with the erasure list.
+ *      Transmitted words (random_codewords != 0): BCH the words of cc_awgn_llr_dev for the same seed and frame
+ *      (message bits in Philox domain 1); RS message symbol i = the low q bits of word (i & 3) of counter
+ *      (.., i >> 2, 4), encoded; random_codewords = 0 sends the all-zero word (then the 0 of an erased position is
+ *      the symbol sent: use random codewords where erasures matter).  Philox domain 0 (AWGN noise) is not used.
+ *      Counters as cc_mc_run_dev; CC_MC_CHANNEL_BIT_ERRORS counts the symbols drawn in error,
+ *      CC_MC_CHANNEL_ERASURES the erased ones, CC_MC_BIT_ERRORS the wrong symbols of the decoded words.  A frame's
+ *      channel output depends only on (seed, p_error, p_erasure, global frame index).
+ *      BCH and RS handles with q <= 8.  CC_ERR_INVALID_ARGUMENT: bad probabilities, NULL counters, a handle of
+ *      cc_minsum_create, random codewords with a coding the encoder cannot do.  CC_ERR_UNSUPPORTED: q > 8, RS with
+ *      mu / step != 1, an RS handle with the PGZ tag and p_erasure > 0 ("The PGZ-Algorithm does not support erasure
+ *      decoding", hard_decision.h:66-68). ---- */
+int cc_mc_run_discrete_dev(const cc_code *code, double p_error, double p_erasure, uint64_t seed,
+                           uint64_t first_frame, size_t frames, int random_codewords, uint64_t *d_counters,
+                           void *stream);
+/* channel only: d_recv frames*n bytes; d_erasures capacity frames*n (NULL allowed iff p_erasure == 0);
+ * d_erasure_offsets frames+1 words (NULL iff d_erasures is NULL): frame f's erased positions, ascending, are
+ * d_erasures[off[f] .. off[f+1]); d_sent frames*n or NULL.  The offsets of one call are 32-bit: with an erasure list
+ * frames*n must stay below 2^32 (CC_ERR_INVALID_ARGUMENT otherwise; split the call, each part a CSR of its own). */
+int cc_discrete_channel_dev(const cc_code *code, double p_error, double p_erasure, uint64_t seed,
+                            uint64_t first_frame, size_t frames, int random_codewords, uint8_t *d_recv,
+                            uint16_t *d_erasures, uint32_t *d_erasure_offsets, uint8_t *d_sent, void *stream);
 
 /* ---- fields GF(2^q) with q = 9 .. 15 (galois.h:44-53: "uint16_t allows galois fields up to 2^15"): symbols are
  *      16 bits wide, n = 2^q - 1 <= 32767.  Hard-decision algorithms (PGZ as bounded-distance BM, BM, Euklid), with
