@@ -69,7 +69,7 @@ def decode(code, ch, frames):
 
 
 def channel_np(code, p, e, seed, first, frames, random_cw):
-    q_sym = 256 if code.family == capi.FAMILY_RS else 2
+    q_sym = 1 << code.q if code.family == capi.FAMILY_RS else 2
     sent = None
     if random_cw:
         msg = (rs_message_symbols(seed, first, frames, code.l, code.q) if code.family == capi.FAMILY_RS
@@ -80,12 +80,27 @@ def channel_np(code, p, e, seed, first, frames, random_cw):
 
 
 # ---- the channel, symbol for symbol ----
-@pytest.mark.parametrize("which", ["bch", "rs"])
+# every frame length: G = 2, 4, .. 64 lanes per frame (group_count's ballot masks, group_log2 = 1 .. 6); RS over GF(2^q)
+# for every q (error values uniform over the 2^q - 1 non-zero symbols)
+GEOMETRIES = {
+    "bch": lambda: cc.primitive_bch(8, cc.errors(3), cc.berlekamp_massey_tag()),
+    "rs": lambda: cc.rs(8, cc.errors(16), cc.berlekamp_massey_tag()),
+    "bch7": lambda: cc.primitive_bch(3, cc.errors(1), cc.berlekamp_massey_tag()),
+    "bch15": lambda: cc.primitive_bch(4, cc.errors(2), cc.berlekamp_massey_tag()),
+    "bch63": lambda: cc.primitive_bch(6, cc.errors(3), cc.berlekamp_massey_tag()),
+    "bch127": lambda: cc.primitive_bch(7, cc.errors(4), cc.berlekamp_massey_tag()),
+    "rs15": lambda: cc.rs(4, cc.errors(3), cc.berlekamp_massey_tag()),
+    "rs31": lambda: cc.rs(5, cc.errors(4), cc.berlekamp_massey_tag()),
+    "rs63": lambda: cc.rs(6, cc.errors(8), cc.berlekamp_massey_tag()),
+    "rs127": lambda: cc.rs(7, cc.errors(8), cc.berlekamp_massey_tag()),
+}
+
+
+@pytest.mark.parametrize("which", list(GEOMETRIES))
 @pytest.mark.parametrize("random_cw", [False, True])
 @pytest.mark.parametrize("p,e", [(0.03, 0.05), (0.02, 0.0), (0.0, 0.1)])
 def test_channel_equals_numpy(which, random_cw, p, e):
-    code = (cc.primitive_bch(8, cc.errors(3), cc.berlekamp_massey_tag()) if which == "bch"
-            else cc.rs(8, cc.errors(16), cc.berlekamp_massey_tag()))
+    code = GEOMETRIES[which]()
     seed, first, frames = 0x1234567890AB, (1 << 41) + 987654321, 300
     ch = code.discrete_channel(p, e, seed, first, frames, random_cw)
     recv, erased, wrong, sent = channel_np(code, p, e, seed, first, frames, random_cw)
@@ -96,10 +111,13 @@ def test_channel_equals_numpy(which, random_cw, p, e):
     assert np.array_equal(ch["erasures"].cpu().numpy().astype(np.int64), vals)
     if e == 0:
         assert ch["erasures"].numel() == 0 and int(ch["erasure_offsets"].abs().sum()) == 0
+    if p > 0 and code.family == capi.FAMILY_RS:  # the error values reach every non-zero symbol of GF(2^q) and no other
+        vals = (ch["recv"] ^ ch["sent"]).cpu().numpy()[wrong]
+        assert vals.min() >= 1 and vals.max() < 1 << code.q
     if random_cw:
         chk = code.correct_batch(sent)
         assert (chk["status"] == 0).all() and (chk["nerr"] == 0).all()  # the transmitted words are codewords
-        if which == "bch":  # the words of cc_awgn_llr_dev for the same seed and frames
+        if code.family == capi.FAMILY_BCH:  # the words of cc_awgn_llr_dev for the same seed and frames
             assert np.array_equal(awgn_sent(code, seed, first, frames).cpu().numpy(), sent)
 
 
@@ -131,6 +149,20 @@ def test_channel_csr_across_chunks_and_calls():
     assert np.array_equal(whole["recv"][-200:].cpu().numpy(), recv)
 
 
+def test_channel_csr_across_chunks_small_code():
+    """More than DISCRETE_CHUNK frames of RS(15,9) (four lanes per frame) in one call: the CSR built across chunks, the
+    RS messages and the error values over GF(16), all against numpy."""
+    code = cc.rs(4, cc.errors(3), cc.berlekamp_massey_tag())
+    seed, first, frames = (3 << 32) + 1, (1 << 32) - 7777, BIG + 4321
+    ch = code.discrete_channel(0.02, 0.04, seed, first, frames, True)
+    recv, erased, _, sent = channel_np(code, 0.02, 0.04, seed, first, frames, True)
+    assert np.array_equal(ch["sent"].cpu().numpy(), sent)
+    assert np.array_equal(ch["recv"].cpu().numpy(), recv)
+    vals, off = erasure_csr(erased)
+    assert np.array_equal(ch["erasure_offsets"].cpu().numpy().astype(np.int64), off)
+    assert np.array_equal(ch["erasures"].cpu().numpy().astype(np.int64), vals)
+
+
 # ---- counters against a host count ----
 BCH = lambda tag: cc.primitive_bch(8, cc.errors(3), tag)  # noqa: E731  BCH(255,231)
 RS = lambda tag: cc.rs(8, cc.errors(16), tag)  # noqa: E731      RS(255,223)
@@ -151,6 +183,13 @@ CASES = [
     ("rs-euklid-bec", lambda: RS(cc.euklid_tag()), 0.0, 0.11, True),
     ("rs-bm-bsec", lambda: RS(cc.berlekamp_massey_tag()), 0.03, 0.05, True),
     ("rs-euklid-bsec", lambda: RS(cc.euklid_tag()), 0.03, 0.05, False),
+    # below GF(2^8): 16, 8 and 4 lanes per frame, error values over GF(64) and GF(16)
+    ("bch63-bm-bsec", lambda: cc.primitive_bch(6, cc.errors(3), cc.berlekamp_massey_tag()), 0.01, 0.01, True),
+    ("bch63-ms-bsec", lambda: cc.primitive_bch(6, cc.errors(3), cc.min_sum_tag(20)), 0.01, 0.01, True),
+    ("rs15-bm-bsec", lambda: cc.rs(4, cc.errors(3), cc.berlekamp_massey_tag()), 0.03, 0.05, True),
+    ("rs15-euklid-bsec", lambda: cc.rs(4, cc.errors(3), cc.euklid_tag()), 0.03, 0.05, False),
+    ("rs63-bm-bsec", lambda: cc.rs(6, cc.errors(8), cc.berlekamp_massey_tag()), 0.03, 0.05, True),
+    ("rs63-euklid-bsec", lambda: cc.rs(6, cc.errors(8), cc.euklid_tag()), 0.03, 0.05, False),
 ]
 
 

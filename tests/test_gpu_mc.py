@@ -9,8 +9,30 @@ import pytest
 import channelcoding_amd as cc
 from channelcoding_amd import capi
 from channelcoding_amd.montecarlo import DeviceBackend, awgn_simulation, shard
+from awgn_model import awgn_reference
+from checkers import BCH as ORC_BCH, Oracle
+from test_discrete_host import bch_message_bits
 
 pytestmark = pytest.mark.gpu
+
+# |z_dev - z_ref| of the device channel against the float64 model (tests/awgn_model.py): v_log_f32, v_sqrt_f32,
+# v_cos_f32 / v_sin_f32 and the float32 rounding of y.  Measured on gfx950 over 3000 frames of every BCH length
+# 7 .. 255 and 40000 frames of n = 255: at most 1.0e-6 (|y_dev - y_ref| at most 5.3e-7).  A layout or formula defect
+# moves values by O(sigma), a 0.1 % error of sigma by 1e-3 |z| sigma.
+Z_TOL = 4e-6
+
+
+def tau(sigma):
+    assert Z_TOL * sigma <= 1e-4 * sigma
+    return Z_TOL * sigma
+
+
+def sigma_f32(code, ebno):
+    return float(np.float32(code.sigma(ebno)))
+
+
+def oracle_of(code):
+    return Oracle(ORC_BCH, code.q, code.t, coding=int(code._desc.coding))
 
 
 def awgn(code, ebno, seed, first, frames, random_cw):
@@ -60,31 +82,170 @@ def test_channel_statistics_and_determinism():
 def test_mc_counters_match_host_count(tag, random_cw):
     code = cc.primitive_bch(8, cc.errors(3), tag)
     frames, seed, first, ebno = 70000, 3, 5000, 5.0  # > one 2^16 chunk
-    c = mc(code, ebno, seed, first, frames, random_cw)
-    llr, sent = awgn(code, ebno, seed, first, frames, random_cw)
-    res = code.correct_batch(llr)
-    out, st = res["out"], res["status"]
-    biterr = (out != sent).sum(dim=1)
-    failed = st != 0
-    assert c[capi.MC_FRAMES] == frames
-    assert c[capi.MC_BIT_ERRORS] == int(biterr.sum())
-    assert c[capi.MC_FAILURES] == int(failed.sum())
-    assert c[capi.MC_WORD_ERRORS] == int((failed | (biterr > 0)).sum())
-    assert c[capi.MC_UNDETECTED] == int((~failed & (biterr > 0)).sum())
-    assert c[capi.MC_CHANNEL_BIT_ERRORS] == int(((llr < 0) != (sent != 0)).sum())
-    if tag.soft:
-        it = res["iters"].to(int)
-        run = it + 1
-        run[failed] = tag.iterations
-        assert c[capi.MC_ITER_SUM] == int(run.sum())
-        hist = np.bincount(it[~failed].cpu().numpy(), minlength=56)[:56]
-        assert np.array_equal(c[capi.MC_ITER_HIST:capi.MC_ITER_HIST + 56], hist)
+    c, _ = check_counters(code, ebno, seed, first, frames, random_cw, require_work=False)
     # sharding independence: 1 rank == sum over 3 ranks
     total = np.zeros_like(c)
     for r in range(3):
         lo, cnt = shard(frames, r, 3)
         total += mc(code, ebno, seed, first + lo, cnt, random_cw)
     assert np.array_equal(total, c)
+
+
+# ---- the channel against the float64 model, one BCH code per field ----
+BIG = 1 << 20  # the chunk of mc_run / mc_awgn
+BCH_PER_FIELD = [(3, 1), (4, 2), (5, 3), (6, 3), (7, 4), (8, 3), (7, 9)]  # (7,4) .. (255,231); (127,71): 56 parity bits
+
+
+def check_channel(code, ebno, seed, first, frames, words):
+    """cc_awgn_llr_dev against awgn_reference.  words: "zero", or the coding tag of the handle's random codewords, whose
+    words must be the plain-C oracle's encoding of the device's message bits."""
+    llr, sent = awgn(code, ebno, seed, first, frames, words != "zero")
+    y, s = llr.cpu().numpy(), sent.cpu().numpy()
+    if words == "zero":
+        assert not s.any()
+    else:
+        assert np.array_equal(s, oracle_of(code).encode(bch_message_bits(seed, first, frames, code.l)))
+    sig = sigma_f32(code, ebno)
+    y_ref = awgn_reference(code.n, sig, seed, first, frames, s)
+    t = tau(sig)
+    err = np.abs(y - y_ref)
+    assert err.max() <= t, (float(err.max()), t)
+    sure = np.abs(y_ref) > t
+    assert np.array_equal((y < 0)[sure], (y_ref < 0)[sure])
+
+
+@pytest.mark.parametrize("words", ["zero", "division", "multiplication"])
+@pytest.mark.parametrize("q,t", BCH_PER_FIELD, ids=["%d-%d" % (2 ** q - 1, t) for q, t in BCH_PER_FIELD])
+def test_channel_equals_float64_model(q, t, words):
+    import math
+    code = cc.primitive_bch(q, cc.errors(t), cc.berlekamp_massey_tag(),
+                            coding="multiplication" if words == "multiplication" else "division")
+    assert code.rate == code.l / code.n
+    for ebno in (1.0, 3.0, 5.5, 8.0):  # simulation.c++:83-85 in float64
+        want = 1.0 / math.sqrt(2.0 * code.rate * 10.0 ** (ebno / 10.0))
+        assert abs(code.sigma(ebno) - want) <= 2 * math.ulp(want)
+    seed = (7 << 32) + 99
+    check_channel(code, 3.0, seed, (1 << 32) - 1000, 3000, words)  # the counter's low word wraps inside the call
+    check_channel(code, 5.5, seed, (5 << 40) + 17, 500, words)
+
+
+def test_channel_across_the_chunk_of_a_long_call():
+    """More than 2^20 random codewords of BCH(31,16) in one call: mc_awgn's chunk loop and its sent / llr offsets."""
+    code = cc.primitive_bch(5, cc.errors(3), cc.berlekamp_massey_tag())
+    seed, first, frames, ebno = 0xABCDEF0123, (1 << 33) + 5, BIG + 1500, 3.0
+    llr, sent = awgn(code, ebno, seed, first, frames, True)
+    sig, o = sigma_f32(code, ebno), oracle_of(code)
+    for lo, hi in ((0, 200), (BIG - 200, BIG + 200), (frames - 200, frames)):
+        y, s = llr[lo:hi].cpu().numpy(), sent[lo:hi].cpu().numpy()
+        assert np.array_equal(s, o.encode(bch_message_bits(seed, first + lo, hi - lo, code.l)))
+        assert np.abs(y - awgn_reference(code.n, sig, seed, first + lo, hi - lo, s)).max() <= tau(sig)
+
+
+# ---- counters against host counts on every geometry ----
+def check_counters(code, ebno, seed, first, frames, random_cw, require_work=True):
+    """cc_mc_run_dev's counters against (1) the same frames through the batch API, exactly, (2) the channel bit errors
+    of the float64 model and (3) the plain-C oracle's decoding: every frame (hard decoders, <= 70000 frames) or a sample
+    (min-sum: the first 2000 frames, up to 500 failed ones and the 300 longest-running converged ones)."""
+    c = mc(code, ebno, seed, first, frames, random_cw)
+    llr, sent = awgn(code, ebno, seed, first, frames, random_cw)
+    res = code.correct_batch(llr)
+    y, s = llr.cpu().numpy(), sent.cpu().numpy()
+    out, st = res["out"].cpu().numpy(), res["status"].cpu().numpy()
+    alg = code.algorithm
+    biterr = (out != s).sum(axis=1)
+    failed = st != 0
+    assert c[capi.MC_FRAMES] == frames
+    assert c[capi.MC_BIT_ERRORS] == int(biterr.sum())
+    assert c[capi.MC_FAILURES] == int(failed.sum())
+    assert c[capi.MC_WORD_ERRORS] == int((failed | (biterr > 0)).sum())
+    assert c[capi.MC_UNDETECTED] == int((~failed & (biterr > 0)).sum())
+    assert c[capi.MC_CHANNEL_ERASURES] == 0
+    if require_work:
+        assert 0 < c[capi.MC_WORD_ERRORS] < frames / 2
+    if alg.soft:
+        it = res["iters"].cpu().numpy().astype(np.int64)
+        run = np.where(failed, alg.iterations, it + 1)
+        assert c[capi.MC_ITER_SUM] == int(run.sum())
+        hist = np.bincount(it[~failed], minlength=64)
+        assert np.array_equal(c[capi.MC_ITER_HIST:capi.MC_ITER_HIST + 56], hist[:56])  # later iterations: ITER_SUM only
+    else:
+        assert c[capi.MC_ITER_SUM] == 0 and not c[capi.MC_ITER_HIST:].any()
+    # channel bit errors: the model's hard decisions outside the tau band, the device's inside it
+    sig = sigma_f32(code, ebno)
+    y_ref = awgn_reference(code.n, sig, seed, first, frames, s)
+    t = tau(sig)
+    assert np.abs(y - y_ref).max() <= t
+    band, bits = np.abs(y_ref) <= t, s != 0
+    model = int((((y_ref < 0) != bits) & ~band).sum()) + int((((y < 0) != bits) & band).sum())
+    assert c[capi.MC_CHANNEL_BIT_ERRORS] == model == int(((y < 0) != bits).sum())
+    # the decoder against the oracle
+    o = oracle_of(code)
+    if not alg.soft:
+        whole = frames <= 70000
+        idx = np.arange(frames) if whole else np.unique(np.r_[0:20000, BIG - 10000:min(BIG + 10000, frames),
+                                                              frames - 20000:frames])
+        oout, _, ost, _ = o.correct_hard(alg.alg, y[idx])
+        assert np.array_equal(failed[idx], ost != 0)
+        assert np.array_equal(out[idx], oout)
+        if whole:
+            oerr, ofail = (oout != s).sum(axis=1), ost != 0
+            assert c[capi.MC_BIT_ERRORS] == int(oerr.sum()) and c[capi.MC_FAILURES] == int(ofail.sum())
+            assert c[capi.MC_WORD_ERRORS] == int((ofail | (oerr > 0)).sum())
+    else:
+        longest = np.argsort(np.where(failed, -1, it), kind="stable")[-300:]
+        idx = np.unique(np.r_[np.arange(min(2000, frames)), np.flatnonzero(failed)[:500], longest])
+        ob, _, oit, ost = o.minsum(alg.alg - capi.ALG_MS, alg.iterations, y[idx], alpha=alg.alpha, beta=alg.beta,
+                                   stop=int(code._desc.stop_rule), fast=True)
+        assert np.array_equal(out[idx], ob)
+        assert np.array_equal(failed[idx], ost != 0)
+        assert np.array_equal(it[idx], oit.astype(np.int64))
+    return c, res
+
+
+def _bch(q, t, tag, **kw):
+    return lambda: cc.primitive_bch(q, cc.errors(t), tag(), **kw)
+
+
+MULT = dict(coding="multiplication")
+# (name, handle, Eb/N0, random codewords): every field q = 3 .. 8, every decoder, every stop rule, both coding tags.
+# The published rule (O1) stops on the all-zero word only: its cases transmit that word.
+MC_CASES = [
+    ("7-4-bm-zero", _bch(3, 1, cc.berlekamp_massey_tag), 3.0, False),
+    ("7-4-ms-div", _bch(3, 1, lambda: cc.min_sum_tag(20)), 2.0, True),
+    ("15-7-pgz-mult", _bch(4, 2, cc.peterson_gorenstein_zierler_tag, **MULT), 3.0, True),
+    ("15-7-nms-published-zero", _bch(4, 2, lambda: cc.normalized_min_sum_tag(20, (4, 5)), stop_rule=capi.STOP_PUBLISHED),
+     2.0, False),
+    ("31-16-euklid-div", _bch(5, 3, cc.euklid_tag), 3.0, True),
+    ("31-16-oms-shipped-mult", _bch(5, 3, lambda: cc.offset_min_sum_tag(30, (1, 10)), stop_rule=capi.STOP_AS_SHIPPED,
+                                    **MULT), 5.0, True),
+    ("63-45-scms1-div", _bch(6, 3, lambda: cc.self_correcting_1_min_sum_tag(20)), 4.0, True),
+    ("63-45-bm-mult", _bch(6, 3, cc.berlekamp_massey_tag, **MULT), 4.0, True),
+    ("127-99-scms2-published-zero", _bch(7, 4, lambda: cc.self_correcting_2_min_sum_tag(20),
+                                         stop_rule=capi.STOP_PUBLISHED), 5.0, False),
+    ("127-99-pgz-div", _bch(7, 4, cc.peterson_gorenstein_zierler_tag), 4.0, True),
+    ("127-71-bm-div", _bch(7, 9, cc.berlekamp_massey_tag), 4.0, True),  # 56 parity bits: launch_encode
+    ("255-223-ms-div", _bch(8, 4, lambda: cc.min_sum_tag(20)), 6.0, True),  # 6 dB: the pre-check route
+    ("255-231-2dnms-shipped-mult", _bch(8, 3, lambda: cc.normalized_2d_min_sum_tag(20), stop_rule=capi.STOP_AS_SHIPPED,
+                                        **MULT), 6.0, True),
+    ("31-16-ms60-late", _bch(5, 3, lambda: cc.min_sum_tag(60)), 2.0, False),
+]
+
+
+@pytest.mark.parametrize("name,make,ebno,random_cw", MC_CASES, ids=[x[0] for x in MC_CASES])
+def test_mc_counters_on_every_geometry(name, make, ebno, random_cw):
+    code = make()
+    c, res = check_counters(code, ebno, 0x5EED00000003, (1 << 32) - 30000, 70000, random_cw)
+    if name.endswith("late"):  # frames converging after iteration 55 enter ITER_SUM, not the histogram
+        it, ok = res["iters"].cpu().numpy().astype(np.int64), res["status"].cpu().numpy() == 0
+        late = it[ok] > 55
+        assert late.any()
+        assert int(c[capi.MC_ITER_HIST:].sum()) == int(ok.sum() - late.sum())
+
+
+def test_mc_counters_across_the_chunk_of_a_long_call():
+    """More than 2^20 frames of BCH(15,7) in one cc_mc_run_dev call: two chunks of mc_run."""
+    code = cc.primitive_bch(4, cc.errors(2), cc.berlekamp_massey_tag())
+    check_counters(code, 3.0, 41, 1 << 36, BIG + 3000, True)
 
 
 def test_awgn_simulation_ladder(tmp_path):
