@@ -160,9 +160,11 @@ class cyclic:
     family = None
 
     def __init__(self, q, capability, algorithm=None, coding="division", mu=1, step=1,
-                 stop_rule=capi.STOP_PARITY, device=None, H=None, modular_polynomial=None):
+                 stop_rule=capi.STOP_PARITY, device=None, H=None, modular_polynomial=None, n=None):
         """modular_polynomial: math::modular_polynomial<> (galois.h:23-25), bit i = coefficient of x^i; None = the
-        default of galois.h:18-20, which exists for q <= 8 only.  q > 8: symbols are numpy uint16 / torch int16."""
+        default of galois.h:18-20, which exists for q <= 8 only.  q > 8: symbols are numpy uint16 / torch int16.
+        n: code length; None (or 2^q - 1) = full length, k < n < 2^q - 1 = the code shortened to n symbols (the
+        words of the full code that are zero at positions n .. 2^q - 2, cut to n symbols)."""
         if isinstance(capability, int):
             capability = errors(capability)
         algorithm = algorithm if algorithm is not None else peterson_gorenstein_zierler_tag()
@@ -183,6 +185,7 @@ class cyclic:
         d.stop_rule = int(stop_rule)
         d.device = capi.DEVICE_CURRENT if device is None else int(device)
         d.modular_polynomial = int(modular_polynomial or 0)
+        d.n = int(n or 0)
         self.wide = int(q) > 8
         self._desc = d
         h = C.c_void_p()
@@ -190,7 +193,7 @@ class cyclic:
             capi.check(lib.cc_code_create(C.byref(d), C.byref(h)), "cc_code_create")
         else:  # min_sum<float, U>(matrix, y, tag) on a caller-supplied parity-check matrix, e.g. H_alt()
             Hm = np.ascontiguousarray(H, np.uint8)
-            if Hm.ndim != 2 or Hm.shape[1] != (1 << int(q)) - 1:
+            if Hm.ndim != 2 or Hm.shape[1] != (int(n) if n else (1 << int(q)) - 1):
                 raise ValueError("H must be a (rows, n) matrix")
             capi.check(lib.cc_code_create_with_H(C.byref(d), _ptr(Hm), Hm.shape[0], C.byref(h)),
                        "cc_code_create_with_H")

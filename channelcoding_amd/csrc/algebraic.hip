@@ -70,7 +70,7 @@ algebraic_kernel(const AlgebraicTables *__restrict__ T, int alg, const void *__r
   const int dbg_stop = (alg >> 8) & 0xFF;  // timing experiments only (CC_AMD_ALG_STOP): 1 after syndromes, 2 after BM, 3 after roots
   const bool redo = (alg >> 16) & 1;       // only the frames another path left with a non-zero status (launch_algebraic)
   alg &= 0xFF;
-  const int n = T->n, nroots = T->nroots, nn = n;  // full-length codes: n = 2^q - 1
+  const int n = T->n, nroots = T->nroots, nn = T->nf;  // frame length, field order (n < nn: a shortened code)
   const int t2 = nroots;
   const bool is_rs = T->family == CC_FAMILY_RS;
   const unsigned long long wave = static_cast<unsigned long long>(blockIdx.x) * 4 + wid;
@@ -104,7 +104,7 @@ algebraic_kernel(const AlgebraicTables *__restrict__ T, int alg, const void *__r
       if (FLOAT_IN)
         sym[c] = valid[c] ? (static_cast<const float *>(in_raw)[frame * n + p] < 0.0f ? 1u : 0u) : 0u;
       else
-        sym[c] = valid[c] ? (static_cast<const uint8_t *>(in_raw)[frame * n + p] & static_cast<uint32_t>(n)) : 0u;
+        sym[c] = valid[c] ? (static_cast<const uint8_t *>(in_raw)[frame * n + p] & static_cast<uint32_t>(nn)) : 0u;
     }
     uint32_t nerase = 0, ebase = 0;
     if (er_off != nullptr) {

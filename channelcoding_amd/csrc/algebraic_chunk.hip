@@ -73,7 +73,7 @@ algebraic_chunk_kernel(const AlgebraicTables *__restrict__ T, int alg, const voi
   const int dbg_stop = alg >> 8;  // timing experiments only (CC_AMD_ALG_STOP): 1 after syndromes, 2 after BM, 3 after roots
   alg &= 0xFF;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int n = T->n, nn = n, t2 = T->nroots, nc = t2 + 1;
+  const int n = T->n, nn = T->nf, t2 = T->nroots, nc = t2 + 1;
   const bool is_rs = T->family == CC_FAMILY_RS;
   const ChunkLayout lay = chunk_layout(t2, FPW);
   uint8_t *base = smem + 1792 + wid * lay.bytes;
@@ -110,7 +110,7 @@ algebraic_chunk_kernel(const AlgebraicTables *__restrict__ T, int alg, const voi
       if (FLOAT_IN)  // hard decision of a signed sequence: cyclic.h:163-173, codes.h:43-52
         sym[c] = valid[c] ? (static_cast<const float *>(in_raw)[frame * n + p] < 0.0f ? 1u : 0u) : 0u;
       else
-        sym[c] = valid[c] ? (static_cast<const uint8_t *>(in_raw)[frame * n + p] & static_cast<uint32_t>(n)) : 0u;
+        sym[c] = valid[c] ? (static_cast<const uint8_t *>(in_raw)[frame * n + p] & static_cast<uint32_t>(nn)) : 0u;
     }
   };
 
@@ -448,7 +448,7 @@ chunk_bm_kernel(const AlgebraicTables *__restrict__ T, int dbg_stop, const uint8
   __syncthreads();
   constexpr int FPW = 64, U = 4;  // U coefficients per trip of the two inner loops (8: measured slower)
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), f = lane;
-  const int nn = T->n, t2 = T->nroots, nc = t2 + 1;
+  const int nn = T->nf, t2 = T->nroots, nc = t2 + 1;
   const BmLayout lay = bm_layout(t2);
   uint8_t *base = smem + 1536 + wid * lay.bytes;
   uint16_t *SL = reinterpret_cast<uint16_t *>(base + lay.SL);
@@ -625,7 +625,7 @@ chunk_bm_reg_kernel(const AlgebraicTables *__restrict__ T, int dbg_stop, const u
   lg2[threadIdx.x] = threadIdx.x ? T->log[threadIdx.x] : kLogZero;
   __syncthreads();
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), f = lane;
-  const uint32_t nn = static_cast<uint32_t>(T->n);
+  const uint32_t nn = static_cast<uint32_t>(T->nf);
   uint8_t *LV = smem + 1536 + wid * (17 * 64);  // lambda_0 .. lambda_16 as bytes [m][64] for the transposition
 
   const unsigned long long nchunks = (B + FPW - 1) / FPW;
@@ -766,7 +766,7 @@ chunk_fix_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t *
   const int dbg_stop = alg >> 8;
   alg &= 0xFF;
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int n = T->n, nn = n, t2 = T->nroots, nc = t2 + 1;
+  const int n = T->n, nn = T->nf, t2 = T->nroots, nc = t2 + 1;
   const bool is_rs = T->family == CC_FAMILY_RS;
   uint8_t *base = smem + 1792 + wid * 320;
   uint16_t *CSL = reinterpret_cast<uint16_t *>(base);  // u16 [64] log S_j
@@ -1022,7 +1022,10 @@ chunk_fixl_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t 
     uint32_t R[8];  // bit j of R[k]: position 32 k + j is a root
 #pragma unroll
     for (int k = 0; k < 8; ++k) R[k] = rootsT[(group * 8 + k) * 32 + bit];
-    R[7] &= 0x7FFFFFFFu;  // there is no position 255
+    // positions n .. 255 do not exist (255: GF(256) has 255 positions; a shortened code has n < 255): a root there is
+    // not counted, so a locator with one fails below
+#pragma unroll
+    for (int k = 0; k < 8; ++k) R[k] &= n >= 32 * (k + 1) ? ~0u : (n <= 32 * k ? 0u : (1u << (n - 32 * k)) - 1u);
     uint32_t cnt = 0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) cnt += __builtin_popcount(R[k]);

@@ -63,7 +63,7 @@ algebraic_long_kernel(const AlgebraicTables *__restrict__ T, int alg, const void
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
   LongScratch &W = scratch[wid];
-  const int n = T->n, nn = n, t2 = T->nroots;
+  const int n = T->n, nn = T->nf, t2 = T->nroots;
   const bool is_rs = T->family == CC_FAMILY_RS;
   const unsigned long long wave = static_cast<unsigned long long>(blockIdx.x) * 4 + wid;
   const unsigned long long nwaves = static_cast<unsigned long long>(gridDim.x) * 4;
@@ -92,7 +92,7 @@ algebraic_long_kernel(const AlgebraicTables *__restrict__ T, int alg, const void
       if (FLOAT_IN)  // hard decision of a signed sequence: cyclic.h:163-173, codes.h:43-52
         sym[c] = valid[c] ? (static_cast<const float *>(in_raw)[frame * n + p] < 0.0f ? 1u : 0u) : 0u;
       else
-        sym[c] = valid[c] ? (static_cast<const uint8_t *>(in_raw)[frame * n + p] & static_cast<uint32_t>(n)) : 0u;
+        sym[c] = valid[c] ? (static_cast<const uint8_t *>(in_raw)[frame * n + p] & static_cast<uint32_t>(nn)) : 0u;
     }
     uint32_t nerase = 0, ebase = 0;
     if (er_off != nullptr) {

@@ -508,7 +508,9 @@ bool bitslice_supported(const cc_code *code) {
   }();
   if (disabled || !code->field) return false;
   const CodeTables &t = code->tab;
-  if (t.q != 8 || t.n != 255 || code->field->poly != kPoly) return false;
+  // (a shortened code, n < 255: bitslice_fused_syndrome_kernel loads frames of n symbols and zero-fills the planes of
+  // positions n .. 255; chunk_fixl_kernel / chunk_fix_kernel count only roots below n)
+  if (t.q != 8 || t.n > 255 || code->field->poly != kPoly) return false;
   const size_t t2 = t.roots.size();
   // Round 2 kept codes with fewer than 8 syndromes on the table kernels (the fixed passes over the batch cost more than
   // the table arithmetic they replaced, r02 E10); with the fused syndrome kernel and the round-3 corrector the planes
@@ -581,7 +583,7 @@ int launch_bitslice_roots_transpose(const void *d_masks, void *d_rootsT, size_t 
 }
 
 bool bitslice_encode_supported(const cc_code *code) {
-  if (!bitslice_supported(code) || code->desc.coding != CC_CODING_DIVISION) return false;
+  if (!bitslice_supported(code) || code->desc.coding != CC_CODING_DIVISION || code->tab.n != 255) return false;
   const size_t k = code->tab.roots.size();  // the generator is the product of the (x - root_j): k = 2t parity symbols
   return code->tab.family == CC_FAMILY_RS && code->tab.k == k && (k == 16 || k == 32);
 }

@@ -391,9 +391,11 @@ static int code_create_impl(const cc_desc *desc, const uint8_t *customH, uint32_
       return CC_ERR_UNSUPPORTED;
     }
   }
-  if (!matrix_only && desc->n != 0 && desc->n != (1u << desc->q) - 1) {
-    set_last_error("shortened codes (N != 2^q-1) are not supported");
-    return CC_ERR_UNSUPPORTED;
+  // shortened codes: k < N < 2^q - 1 (k is known once g is built, below)
+  const bool shortened = !matrix_only && desc->n != 0 && desc->n != (1u << desc->q) - 1;
+  if (shortened && desc->n > (1u << desc->q) - 1) {
+    set_last_error("shortened length must satisfy k < N <= 2^q - 1");
+    return CC_ERR_INVALID_ARGUMENT;
   }
   int dev = desc->device;
   if (dev != CC_DEVICE_NONE) {
@@ -411,6 +413,7 @@ static int code_create_impl(const cc_desc *desc, const uint8_t *customH, uint32_
   std::unique_ptr<cc_code, void (*)(cc_code *)> code(new (std::nothrow) cc_code(), &cc_code_destroy);
   if (!code) return CC_ERR_OUT_OF_MEMORY;
   code->desc = *desc;
+  code->shortened = shortened;
   code->device = dev;
   code->matrix_only = matrix_only;
   try {
@@ -442,6 +445,7 @@ static int code_create_impl(const cc_desc *desc, const uint8_t *customH, uint32_
       code->field.reset(new Field(desc->q, desc->modular_polynomial));
       code->tab = build_code(*code->field, desc->family, desc->t, desc->mu, desc->step);
     }
+    if (shortened) shorten(code->tab, desc->n);  // (tab16 keeps the full code's polynomials; wide_dev gets n = N below)
   } catch (const std::invalid_argument &e) {
     set_last_error(e.what());
     return CC_ERR_INVALID_ARGUMENT;
@@ -460,6 +464,13 @@ static int code_create_impl(const cc_desc *desc, const uint8_t *customH, uint32_
     code->ms_rows = custom_rows;
     for (uint8_t v : code->custom_H)
       if (v > 1) code->tab.binary_h = false;
+  } else if (shortened && code->soft && code->tab.binary_h) {
+    // min-sum over H[:, :N]: the banded rows cut at column N are no longer shifts of one row (the diagonal kernels'
+    // premise), so the generic kernel runs them as an explicit matrix
+    const CodeTables &s = code->tab;
+    code->custom_H.assign(static_cast<size_t>(s.k) * s.n, 0);
+    for (unsigned i = 0; i < s.k; ++i)
+      for (unsigned j = i; j < s.n; ++j) code->custom_H[static_cast<size_t>(i) * s.n + j] = s.row0[j - i];
   }
   {
     const char *fg = std::getenv("CC_AMD_FORCE_GENERIC");
@@ -584,9 +595,10 @@ static int code_create_impl(const cc_desc *desc, const uint8_t *customH, uint32_
     wt.log = code->d_wide + ne;
     wt.g = code->d_wide + 2 * ne;
     for (size_t i = 0; i < w.root_powers.size() && i < 64; ++i) wt.root_log[i] = w.root_powers[i];
-    wt.n = w.n;
+    wt.n = code->tab.n;  // frame length: N for a shortened code
     wt.k = w.k;
-    wt.l = w.l;
+    wt.l = code->tab.l;
+    wt.nf = w.n;
     wt.t = w.t;
     wt.nroots = static_cast<uint32_t>(w.roots.size());
     wt.q = w.q;
@@ -607,9 +619,10 @@ static int code_create_impl(const cc_desc *desc, const uint8_t *customH, uint32_
   a.nroots = static_cast<int>(t.roots.size());
   a.family = t.family;
   a.q = static_cast<int>(t.q);
+  a.nf = static_cast<int>(code->field->n);  // a.n < a.nf: a shortened code
   CC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&code->d_alg), sizeof a));
   CC_HIP_TRY(hipMemcpy(code->d_alg, &a, sizeof a, hipMemcpyHostToDevice));
-  if (desc->coding == CC_CODING_DIVISION) {
+  if (desc->coding == CC_CODING_DIVISION) {  // (shortened: k x (N - k), the first columns of the full code's table)
     const std::vector<uint8_t> pt = build_parity_table(*code->field, t);
     CC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&code->d_parity), pt.size()));
     CC_HIP_TRY(hipMemcpy(code->d_parity, pt.data(), pt.size(), hipMemcpyHostToDevice));
@@ -728,8 +741,10 @@ int cc_get_H(const cc_code *c, uint8_t *H) {
     std::memcpy(H, c->custom_H.data(), c->custom_H.size());
     return CC_OK;
   }
+  // H[i][j] = row0[j - i] (banded: the cyclic wrap of cyclic.h:346-359 only meets zeros of row0); a shortened code
+  // keeps the first N columns
   for (unsigned i = 0; i < c->tab.k; ++i)
-    for (unsigned j = 0; j < n; ++j) H[i * n + j] = c->tab.row0[(j + n - i) % n];
+    for (unsigned j = 0; j < n; ++j) H[i * n + j] = j >= i ? c->tab.row0[j - i] : 0;
   return CC_OK;
 }
 
@@ -902,7 +917,7 @@ static int hard_host(const cc_code *code, bool float_in, const void *in, const u
   const size_t n = code->tab.n;
   if (!float_in) {  // Element(v) throws for v outside the field, galois.h:149-152
     const uint8_t *b = static_cast<const uint8_t *>(in);
-    const uint8_t mask = static_cast<uint8_t>(~code->tab.n);
+    const uint8_t mask = static_cast<uint8_t>(~((1u << code->tab.q) - 1));
     for (size_t i = 0; i < B * n; ++i)
       if (b[i] & mask) return CC_ERR_NOT_IN_FIELD;
   }
@@ -986,7 +1001,7 @@ static int byte_map_host(const cc_code *code, bool encode, const uint8_t *src, u
   const size_t n = code->tab.n, l = code->tab.l;
   const size_t in_w = encode ? l : n, out_w = encode ? n : l;
   if (encode) {  // Element(e) throws for values outside the field, galois.h:149-152 via cyclic.h:300-301
-    const uint8_t mask = static_cast<uint8_t>(~code->tab.n);
+    const uint8_t mask = static_cast<uint8_t>(~((1u << code->tab.q) - 1));
     for (size_t i = 0; i < B * in_w; ++i)
       if (src[i] & mask) return CC_ERR_NOT_IN_FIELD;
   }
@@ -1129,7 +1144,7 @@ static int wide_map_host(const cc_code *code, int kind, const uint16_t *src, uin
   const size_t in_w = kind == 0 ? l : n, out_w = kind == 0 ? n : l;
   if (kind == 0)
     for (size_t i = 0; i < B * in_w; ++i)
-      if (src[i] > n) return CC_ERR_NOT_IN_FIELD;  // Element(e) throws, galois.h:149-152
+      if (src[i] > (1u << code->tab.q) - 1) return CC_ERR_NOT_IN_FIELD;  // Element(e) throws, galois.h:149-152
   DeviceGuard guard(code->device);
   StageLock sl(code);
   if (sl.rc != CC_OK) return sl.rc;
@@ -1172,7 +1187,7 @@ int cc_correct_hard_batch_u16(const cc_code *code, const uint16_t *in, const uin
   if (B == 0) return CC_OK;
   const size_t n = code->tab.n;
   for (size_t i = 0; i < B * n; ++i)
-    if (in[i] > n) return CC_ERR_NOT_IN_FIELD;
+    if (in[i] > (1u << code->tab.q) - 1) return CC_ERR_NOT_IN_FIELD;
   if (erasures) {
     const size_t ne = erasure_offsets[B];
     for (size_t e = 0; e < ne; ++e)

@@ -73,6 +73,8 @@ struct AlgebraicTables {
   uint8_t g[256];
   uint8_t roots_log[64];
   int n, k, l, t, nroots, family, q;
+  int nf;  // field order 2^q - 1: exponent arithmetic and the symbol mask.  n = frame length: nf, or N of a code
+           // shortened to N symbols (positions N .. nf-1 are zero: the root search counts only roots below n)
 };
 
 // q = 9..15 (wide.hip): tables in global memory, passed to the kernels by value
@@ -81,6 +83,7 @@ struct WideTables {
   const uint16_t *g = nullptr;                    // k + 1 coefficients
   uint32_t root_log[64] = {0};
   uint32_t n = 0, k = 0, l = 0, t = 0, nroots = 0, q = 0;
+  uint32_t nf = 0;  // field order 2^q - 1; n = frame length (< nf: a shortened code, see AlgebraicTables)
   int family = 0;
 };
 
@@ -125,6 +128,10 @@ struct cc_code {
   int num_cus = 256;
   bool force_generic = false;  // CC_AMD_FORCE_GENERIC=1: A/B the generic kernel against the fast one
   std::string name;
+  // Shortened code (cc_desc.n = N < 2^q - 1): `tab` holds the code of length N (n = N, l = N - k, H's first N
+  // columns), h_alg / wide_dev carry n = N next to the field order nf, and every kernel runs on frames of N symbols;
+  // min-sum runs over H[:, :N] (custom_H).  `shortened` is what tells it apart from a full-length code.
+  bool shortened = false;
 };
 
 namespace ccamd {

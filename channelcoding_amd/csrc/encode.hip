@@ -38,7 +38,7 @@ encode_division_kernel(const AlgebraicTables *__restrict__ T, const uint8_t *__r
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const int j = lane + 64 * c;
-      m[c] = j < l ? (msg[f * l + j] & static_cast<uint32_t>(n)) : 0u;
+      m[c] = j < l ? (msg[f * l + j] & static_cast<uint32_t>(T->nf)) : 0u;
       lm[c] = lg[m[c]];
     }
     for (int i0 = 0; i0 < k; i0 += 4) {
@@ -128,7 +128,7 @@ encode_bch_planes_kernel(const uint8_t *__restrict__ PT, const uint8_t *__restri
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const int j = lane + 64 * c;
-      m[c] = j < l ? (msg[f * l + j] & static_cast<uint32_t>(n)) : 0u;
+      m[c] = j < l ? (msg[f * l + j] & ((1u << q) - 1u)) : 0u;
     }
     uint32_t par = 0;  // parity symbol of position `lane` (lane < k), assembled plane by plane
     for (int b = 0; b < q; ++b) {
@@ -164,7 +164,7 @@ encode_multiplication_kernel(const AlgebraicTables *__restrict__ T, const uint8_
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const int j = lane + 64 * c;
-      a[wid][j] = j < l ? static_cast<uint8_t>(msg[f * l + j] & n) : 0;
+      a[wid][j] = j < l ? static_cast<uint8_t>(msg[f * l + j] & T->nf) : 0;
     }
     uint32_t acc[4] = {0, 0, 0, 0};
     for (int d = 0; d <= k; ++d) {  // c_p = sum_d g_d a_{p-d}
@@ -227,7 +227,7 @@ extract_multiplication_kernel(const AlgebraicTables *__restrict__ T, const uint8
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const int p = lane + 64 * c;
-      rem[wid][p] = p < n ? static_cast<uint8_t>(cw[f * n + p] & n) : 0;
+      rem[wid][p] = p < n ? static_cast<uint8_t>(cw[f * n + p] & T->nf) : 0;
     }
     __builtin_amdgcn_wave_barrier();
     for (int i = n - 1; i >= k; --i) {

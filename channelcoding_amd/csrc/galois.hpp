@@ -195,4 +195,19 @@ CodeTablesT<T> build_code(const FieldT<T> &f, int family, unsigned t, unsigned m
   return c;
 }
 
+// The code shortened to N symbols (k < N <= n): the mother code's words whose positions N .. n-1 (the top information
+// positions) are zero, cut to their first N symbols.  g, h, the roots and dmin stay the mother code's; H keeps its
+// first N columns.  The reference's N slot (cyclic.h:66-69) is a TODO there: this definition is ours.
+template <typename T>
+void shorten(CodeTablesT<T> &c, unsigned N) {
+  // (no dmin <= N test: dmin is the mother's designed distance, which over-counts for RS -- 2t + 2 -- and every
+  // k < N is a valid length; the mother itself passed the test)
+  if (N <= c.k || N > c.n) throw std::invalid_argument("shortened length must satisfy k < N <= 2^q - 1");
+  c.n = N;
+  c.l = N - c.k;
+  c.row0.resize(N);
+  c.row0_support.erase(std::remove_if(c.row0_support.begin(), c.row0_support.end(), [N](unsigned j) { return j >= N; }),
+                       c.row0_support.end());
+}
+
 }  // namespace ccamd

@@ -39,6 +39,9 @@ const DiagEntry kDiagGeometries[] = {
 // the object of the geometry that carries the variant of `p`
 DiagLaunch launcher(const DiagEntry *e, const MinSumParams &p) { return e->launch[diag_variant_part(p.variant, e->parts)]; }
 const DiagEntry *diag_entry(const CodeTables &t) {
+  // full-length codes only: a shortened code's banded rows are cut at column N, so it could match a geometry's
+  // (n, k, w) with a different matrix
+  if (t.n != (1u << t.q) - 1) return nullptr;
   for (const DiagEntry &e : kDiagGeometries)
     if (t.n == e.geo.n && t.k == e.geo.k && t.row0_support.size() == e.geo.w) return &e;
   return nullptr;

@@ -44,7 +44,7 @@ wide_correct_kernel(WideTables T, int alg, const uint16_t *__restrict__ in, cons
   WideScratch &W = scratch[wid];
   const uint16_t *__restrict__ ex = T.exp;
   const uint16_t *__restrict__ lg = T.log;
-  const uint32_t n = T.n, nn = T.n, t2 = T.nroots;
+  const uint32_t n = T.n, nn = T.nf, t2 = T.nroots;  // frame length, field order (n < nn: a shortened code)
   const bool is_rs = T.family == CC_FAMILY_RS;
   const unsigned long long wave = static_cast<unsigned long long>(blockIdx.x) * 4 + wid;
   const unsigned long long nwaves = static_cast<unsigned long long>(gridDim.x) * 4;
@@ -66,7 +66,7 @@ wide_correct_kernel(WideTables T, int alg, const uint16_t *__restrict__ in, cons
     for (uint32_t j0 = 0; j0 < t2; j0 += 4) {
       uint32_t acc[4] = {0, 0, 0, 0};
       for (uint32_t p = lane; p < n; p += 64) {
-        const uint32_t b = src[p] & n;
+        const uint32_t b = src[p] & nn;
         if (j0 == 0) dst[p] = static_cast<uint16_t>(b);
         if (b) {
           const uint32_t lb = lg[b];
@@ -235,7 +235,7 @@ __global__ void __launch_bounds__(256)
 wide_encode_kernel(WideTables T, const uint16_t *__restrict__ msg, uint16_t *__restrict__ cw, unsigned long long B) {
   extern __shared__ uint16_t rem_all[];  // 4 waves x (k + 1)
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const uint32_t n = T.n, k = T.k, l = T.l, nn = T.n;
+  const uint32_t n = T.n, k = T.k, l = T.l, nn = T.nf;
   uint16_t *rem = rem_all + wid * (k + 1);
   const uint16_t *__restrict__ ex = T.exp;
   const uint16_t *__restrict__ lg = T.log;

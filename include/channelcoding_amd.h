@@ -92,7 +92,13 @@ typedef struct cc_desc {
   int32_t family;       /* cc_family                                                           */
   uint32_t q;           /* GF(2^q), 2..15; q > 8: name modular_polynomial below, use the _u16 calls */
   uint32_t t;           /* errors<t>; for dmin<d> pass (d-1)/2 (codes.h:14-26)                 */
-  uint32_t n;           /* 0 or 2^q-1 (the reference's N is a TODO there too, cyclic.h:66)     */
+  uint32_t n;           /* code length: 0 or 2^q-1 = full length; k < n < 2^q-1 = the code     *
+                         * shortened to n symbols: the full code's words that are zero at the  *
+                         * top positions n..2^q-2, cut to n symbols (our definition: the        *
+                         * reference's N is a TODO, cyclic.h:66-69).  cc_n = n, cc_l = n - k;   *
+                         * g, h, roots, dmin are the full code's; H, H_alt its first n columns. *
+                         * A locator root at a position >= n fails it (CC_FRAME_LOCATOR).     *
+                         * Symbols are still checked against GF(2^q), not against n.           */
   uint32_t mu, step;    /* RS only: roots alpha^(mu + i*step), rs.h:18-39; use 1, 1            */
   int32_t coding;       /* cc_coding                                                           */
   int32_t algorithm;    /* cc_algorithm                                                        */

@@ -291,7 +291,8 @@ template <int Family, unsigned q, typename Capability, typename Algorithm, unsig
 class code_base {
   static_assert(std::is_base_of<coding_tag, Coding>::value, "Coding must be division_tag or multiplication_tag");
   static_assert(std::is_base_of<algorithm_tag, Algorithm>::value, "Algorithm must be an algorithm tag");
-  static_assert(N == (1u << q) - 1, "shortened codes are not supported by the device path");
+  // N < 2^q - 1: the code shortened to N symbols (cc_desc.n; the reference's slot, a TODO there, cyclic.h:66-69)
+  static_assert(0 < N && N <= (1u << q) - 1, "code length N must satisfy 0 < N <= 2^q - 1");
 
 public:
   using Element = math::ef_element<2, q>;  // (q > 8: through default_modular_polynomial<q>, see namespace math)
@@ -317,6 +318,7 @@ public:
     d.t = t;
     d.mu = mu;
     d.step = step;
+    d.n = N;
     d.coding = Coding::cc_coding;
     d.algorithm = Algorithm::cc_alg;
     d.iterations = Algorithm::iterations;
