@@ -89,6 +89,18 @@ _SIGNATURES = {
     "cc_extract_batch_u16_dev": (C.c_int, [_VP, _VP, _VP, C.c_size_t, _VP]),
     "cc_get_poly_u16": (C.c_int, [_VP, C.c_int, _VP, C.c_size_t]),
     "cc_q": (C.c_uint32, [_VP]),
+    "cc_packed_bytes": (C.c_int, [_VP, C.c_int]),
+    "cc_packed_route": (C.c_int, [_VP, C.c_size_t]),
+    "cc_packed_map_route": (C.c_int, [_VP, C.c_int]),
+    "cc_pack_bits_dev": (C.c_int, [_VP, C.c_int, C.c_size_t, _VP, C.c_size_t, _VP]),
+    "cc_unpack_bits_dev": (C.c_int, [_VP, C.c_size_t, _VP, C.c_int, C.c_size_t, _VP]),
+    "cc_encode_packed_batch": (C.c_int, [_VP, _VP, _VP, C.c_size_t]),
+    "cc_encode_packed_batch_dev": (C.c_int, [_VP, _VP, _VP, C.c_size_t, _VP]),
+    "cc_correct_hard_packed_batch": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t]),
+    "cc_correct_hard_packed_batch_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "cc_extract_packed_batch": (C.c_int, [_VP, _VP, _VP, C.c_size_t]),
+    "cc_extract_packed_batch_dev": (C.c_int, [_VP, _VP, _VP, C.c_size_t, _VP]),
+    "cc_decode_hard_packed_batch": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t]),
     "cc_diag_table": (C.c_int, [_VP, _VP, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                 C.POINTER(C.c_uint32)]),
     "cc_kernel_info": (C.c_int, [_VP, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),

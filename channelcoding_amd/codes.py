@@ -155,6 +155,62 @@ def _erasure_csr(erasures, B, n):
     return vals, off
 
 
+def _torch_symbol_dtypes():
+    import torch
+    return (torch.uint8, torch.int16) + ((torch.uint16,) if hasattr(torch, "uint16") else ())
+
+
+def pack_bits(a):
+    """One symbol per bit, shape (..., n) -> packed uint8, shape (..., ceil(n / 8)): the coefficient of x^p in bit p & 7
+    of byte p >> 3 (numpy.packbits(bitorder="little")); bit 0 of each symbol counts, pad bits are 0.  numpy arrays on the
+    host; torch device tensors (uint8, or 16-bit for the symbols of q > 8) through cc_pack_bits_dev on the current
+    stream."""
+    if _is_torch(a) and a.is_cuda:
+        import torch
+        a = a.contiguous()
+        if a.dtype not in _torch_symbol_dtypes():
+            raise TypeError("pack_bits takes uint8 symbols or 16-bit integer symbols")
+        n = a.shape[-1]
+        B = a.numel() // n if n else 0
+        out = torch.empty(a.shape[:-1] + ((n + 7) // 8,), dtype=torch.uint8, device=a.device)
+        with torch.cuda.device(a.device):
+            capi.check(capi.lib().cc_pack_bits_dev(_ptr(a), a.element_size(), n, _ptr(out), B, _stream_handle(a)),
+                       "cc_pack_bits_dev")
+        return out
+    if _is_torch(a):
+        import torch
+        return torch.from_numpy(pack_bits(a.numpy()))
+    a = np.asarray(a)
+    return np.packbits((a & 1).astype(np.uint8), axis=-1, bitorder="little")
+
+
+def unpack_bits(a, n, dtype=None):
+    """Packed uint8, shape (..., ceil(n / 8)) -> one symbol per bit, shape (..., n); pad bits are ignored.  dtype: uint8
+    (default) or a 16-bit type for the symbols of q > 8."""
+    n = int(n)
+    if a.shape[-1] != (n + 7) // 8:
+        raise CcError(capi.ERR_LENGTH, "unpack_bits")
+    if _is_torch(a) and a.is_cuda:
+        import torch
+        a = a.contiguous()
+        if a.dtype != torch.uint8:
+            raise TypeError("packed words are uint8")
+        dtype = dtype or torch.uint8
+        if dtype not in _torch_symbol_dtypes():
+            raise TypeError("unpack_bits gives uint8 symbols or 16-bit integer symbols")
+        out = torch.empty(a.shape[:-1] + (n,), dtype=dtype, device=a.device)
+        B = out.numel() // n if n else 0
+        with torch.cuda.device(a.device):
+            capi.check(capi.lib().cc_unpack_bits_dev(_ptr(a), n, _ptr(out), out.element_size(), B, _stream_handle(a)),
+                       "cc_unpack_bits_dev")
+        return out
+    if _is_torch(a):
+        import torch
+        return torch.from_numpy(unpack_bits(a.numpy(), n)).to(dtype or torch.uint8)
+    a = np.ascontiguousarray(a, np.uint8)
+    return np.unpackbits(a, axis=-1, count=n, bitorder="little").astype(dtype or np.uint8)
+
+
 class cyclic:
     """Common part of primitive_bch and rs (cyclic::cyclic<...>, cyclic.h:67-386)."""
     family = None
@@ -288,6 +344,110 @@ class cyclic:
         erasures = er[:total] if er is not None else torch.empty(0, dtype=torch.int16, device=dev)
         return dict(recv=recv, erasures=erasures, erasure_offsets=off, sent=sent)
 
+    # ---- packed bits (binary BCH codes with a hard algorithm): uint8 (B, ceil(n / 8)), see pack_bits ----
+    def _packed_width(self, which):
+        p = capi.lib().cc_packed_bytes(self._h, which)
+        if p < 0:
+            raise CcError(-p, "cc_packed_bytes")
+        return p
+
+    @property
+    def packed_bytes(self):
+        """Bytes of a packed codeword, ceil(n / 8)."""
+        return self._packed_width(0)
+
+    @property
+    def packed_message_bytes(self):
+        """Bytes of a packed message, ceil(l / 8)."""
+        return self._packed_width(1)
+
+    def packed_route(self, B):
+        """1 if correct_batch(packed=True) of B frames without erasures decodes the packed words natively, 0 if it goes
+        through unpack / byte route / pack (cc_packed_route)."""
+        r = capi.lib().cc_packed_route(self._h, int(B))
+        if r < 0:
+            raise CcError(-r, "cc_packed_route")
+        return r
+
+    def packed_map_route(self, which):
+        """1 if encode_batch (which = 0) / extract_batch (which = 1) with packed=True works on the packed words
+        themselves, 0 if it goes through unpack / byte route / pack (cc_packed_map_route)."""
+        r = capi.lib().cc_packed_map_route(self._h, int(which))
+        if r < 0:
+            raise CcError(-r, "cc_packed_map_route")
+        return r
+
+    def _packed_map(self, x, which_in, name):
+        lib = capi.lib()
+        w_in, w_out = self._packed_width(which_in), self._packed_width(1 - which_in)
+        if _is_torch(x):
+            import torch
+            x = x.contiguous()
+            if x.dtype != torch.uint8 or x.shape[-1] != w_in:
+                raise CcError(capi.ERR_LENGTH, name)
+            B = x.numel() // w_in
+            out = torch.empty((B, w_out), dtype=torch.uint8, device=x.device)
+            capi.check(getattr(lib, name + "_dev")(self._h, _ptr(x), _ptr(out), B, _stream_handle(x)), name + "_dev")
+            return out
+        x = np.ascontiguousarray(x, np.uint8)
+        if x.shape[-1] != w_in:
+            raise CcError(capi.ERR_LENGTH, name)
+        x = x.reshape(-1, w_in)
+        out = np.zeros((x.shape[0], w_out), np.uint8)
+        capi.check(getattr(lib, name)(self._h, _ptr(x), _ptr(out), x.shape[0]), name)
+        return out
+
+    def _packed_correct(self, b, erasures, out=None):
+        lib = capi.lib()
+        P = self._packed_width(0)
+        if b.shape[-1] != P:
+            raise CcError(capi.ERR_LENGTH, "correct_batch")
+        if _is_torch(b):
+            import torch
+            given = b
+            if out is b and not b.is_contiguous():
+                raise TypeError("decoding in place needs a contiguous tensor")
+            b = b.contiguous()
+            if b.dtype != torch.uint8:
+                raise TypeError("packed words are uint8")
+            B = b.numel() // P
+            dev = b.device
+            er = off = None
+            if erasures is not None:
+                ev, eo = _erasure_csr(erasures, B, self.n)
+                if ev is not None:
+                    ev = ev if ev.size else np.zeros(1, ev.dtype)
+                    er = torch.from_numpy(ev.astype(np.int16)).to(dev)
+                    off = torch.from_numpy(eo.astype(np.int32)).to(dev)
+            if out is None:
+                out = torch.empty((B, P), dtype=torch.uint8, device=dev)
+            elif out is given:  # decoding in place: the (contiguous) input itself
+                out = b
+            elif not (_is_torch(out) and out.dtype == torch.uint8 and out.device == dev and out.is_contiguous()
+                      and tuple(out.shape) == (B, P)):
+                raise TypeError("out= must be a contiguous uint8 tensor of shape (B, packed_bytes) on the input's device")
+            nerr = torch.empty(B, dtype=torch.int32, device=dev)
+            status = torch.empty(B, dtype=torch.int32, device=dev)
+            capi.check(lib.cc_correct_hard_packed_batch_dev(self._h, _ptr(b), _ptr(er), _ptr(off), _ptr(out), _ptr(nerr),
+                                                            _ptr(status), B, _stream_handle(b)),
+                       "cc_correct_hard_packed_batch_dev")
+            return dict(out=out, status=status, nerr=nerr)
+        if out is b and not (isinstance(b, np.ndarray) and b.dtype == np.uint8 and b.flags.c_contiguous):
+            raise TypeError("decoding in place needs a contiguous uint8 array")
+        b = np.ascontiguousarray(b, np.uint8).reshape(-1, P)
+        B = b.shape[0]
+        er, off = _erasure_csr(erasures, B, self.n)
+        if out is None:
+            out = np.zeros((B, P), np.uint8)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous
+                  and out.flags.writeable and out.shape == (B, P)):
+            raise TypeError("out= must be a contiguous writable uint8 array of shape (B, packed_bytes)")
+        nerr = np.zeros(B, np.int32)
+        status = np.zeros(B, np.int32)
+        capi.check(lib.cc_correct_hard_packed_batch(self._h, _ptr(b), _ptr(er), _ptr(off), _ptr(out), _ptr(nerr),
+                                                    _ptr(status), B), "cc_correct_hard_packed_batch")
+        return dict(out=out, status=status, nerr=nerr)
+
     # ---- batch API (numpy host arrays or torch CUDA tensors) ----
     # ---- q > 8: 16-bit symbols (numpy uint16 on the host, torch int16 / uint16 on the device) ----
     def _wide_map(self, x, width_in, width_out, host_fn, dev_fn):
@@ -344,8 +504,11 @@ class cyclic:
                                                  _ptr(status), B), "cc_correct_hard_batch_u16")
         return dict(out=out, status=status, nerr=nerr)
 
-    def encode_batch(self, msg):
+    def encode_batch(self, msg, packed=False):
+        """packed=True: uint8 (B, packed_message_bytes) -> uint8 (B, packed_bytes), see pack_bits."""
         lib = capi.lib()
+        if packed:
+            return self._packed_map(msg, 1, "cc_encode_packed_batch")
         if self.wide:
             return self._wide_map(msg, self.l, self.n, "cc_encode_batch_u16", "cc_encode_batch_u16_dev")
         if _is_torch(msg):
@@ -366,8 +529,10 @@ class cyclic:
         capi.check(lib.cc_encode_batch(self._h, _ptr(msg), _ptr(cw), msg.shape[0]), "cc_encode_batch")
         return cw
 
-    def extract_batch(self, cw):
+    def extract_batch(self, cw, packed=False):
         lib = capi.lib()
+        if packed:
+            return self._packed_map(cw, 0, "cc_extract_packed_batch")
         if self.wide:
             return self._wide_map(cw, self.n, self.l, "cc_extract_batch_u16", "cc_extract_batch_u16_dev")
         if _is_torch(cw):
@@ -383,9 +548,15 @@ class cyclic:
         capi.check(lib.cc_extract_batch(self._h, _ptr(cw), _ptr(msg), cw.shape[0]), "cc_extract_batch")
         return msg
 
-    def correct_batch(self, b, erasures=None, want_L=False):
-        """Returns a dict: out (B,n) u8, status (B,) i32, and nerr (hard) or iters [+ L] (soft)."""
+    def correct_batch(self, b, erasures=None, want_L=False, packed=False, out=None):
+        """Returns a dict: out (B,n) u8, status (B,) i32, and nerr (hard) or iters [+ L] (soft).
+        packed=True (binary BCH codes, hard algorithms): b and out are uint8 (B, packed_bytes), see pack_bits; out= names
+        the buffer the corrected packed words go to (b itself decodes in place)."""
         lib = capi.lib()
+        if packed:
+            return self._packed_correct(b, erasures, out)
+        if out is not None:
+            raise TypeError("out= goes with packed=True")
         soft_alg = self.algorithm.soft
         if self.wide and not soft_alg:  # (min-sum takes LLRs and returns bits whatever the symbol width)
             return self._wide_correct(b, erasures)
@@ -463,8 +634,26 @@ class cyclic:
             raise TypeError("hard decoding takes uint8 symbols or float32 soft values")
         return dict(out=out, status=status, nerr=nerr)
 
-    def decode_batch(self, b, erasures=None):
-        """decode = correct + message extraction (cyclic.h:313-327); host arrays go through cc_decode_*_batch."""
+    def decode_batch(self, b, erasures=None, packed=False):
+        """decode = correct + message extraction (cyclic.h:313-327); host arrays go through cc_decode_*_batch.
+        packed=True: b, out and msg are packed uint8 words, see pack_bits."""
+        if packed:
+            if _is_torch(b):
+                res = self._packed_correct(b, erasures)
+                res["msg"] = self.extract_batch(res["out"], packed=True)
+                return res
+            P, Pm = self._packed_width(0), self._packed_width(1)
+            b = np.ascontiguousarray(b, np.uint8)
+            if b.shape[-1] != P:
+                raise CcError(capi.ERR_LENGTH, "decode_batch")
+            b = b.reshape(-1, P)
+            B = b.shape[0]
+            er, off = _erasure_csr(erasures, B, self.n)
+            msg, out = np.zeros((B, Pm), np.uint8), np.zeros((B, P), np.uint8)
+            nerr, status = np.zeros(B, np.int32), np.zeros(B, np.int32)
+            capi.check(capi.lib().cc_decode_hard_packed_batch(self._h, _ptr(b), _ptr(er), _ptr(off), _ptr(msg), _ptr(out),
+                                                              _ptr(nerr), _ptr(status), B), "cc_decode_hard_packed_batch")
+            return dict(out=out, msg=msg, status=status, nerr=nerr)
         if _is_torch(b):
             res = self.correct_batch(b, erasures)
             res["msg"] = self.extract_batch(res["out"])

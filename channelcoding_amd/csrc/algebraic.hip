@@ -416,20 +416,24 @@ int launch_pgz_erasures(const cc_code *code, const uint8_t *d_in, const uint16_t
   return rc;
 }
 
+// The bit-plane chain is seven launches with a floor of 60 .. 100 us per call; below ~4e5 frame-syndromes one
+// wavefront per frame is faster (profiles/tools/hard_size_sweep.py: RS(255,223) 2^12 frames 32 vs 102 us,
+// BCH(255,231) 2^14 frames 24 vs 65 us; equal at 2^14 / 2^16 frames)
+bool planes_small_call(const cc_code *code, size_t B) {
+  static const size_t planes_min_work = [] {
+    const char *e = std::getenv("CC_AMD_PLANES_MIN_WORK");
+    return e ? static_cast<size_t>(std::strtoull(e, nullptr, 10)) : static_cast<size_t>(3) << 17;
+  }();
+  return bitslice_supported(code) && B * code->tab.roots.size() < planes_min_work;
+}
+
 int launch_algebraic(const cc_code *code, bool float_in, const void *d_in, const uint16_t *d_er,
                      const uint32_t *d_er_off, uint8_t *d_out, int32_t *d_nerr, int32_t *d_status, size_t B,
                      hipStream_t stream) {
   if (B == 0) return CC_OK;
   if (algebraic_long_needed(code, d_er_off != nullptr))
     return launch_algebraic_long(code, float_in, d_in, d_er, d_er_off, d_out, d_nerr, d_status, B, stream);
-  // The bit-plane chain is seven launches with a floor of 60 .. 100 us per call; below ~4e5 frame-syndromes one
-  // wavefront per frame is faster (profiles/tools/hard_size_sweep.py: RS(255,223) 2^12 frames 32 vs 102 us,
-  // BCH(255,231) 2^14 frames 24 vs 65 us; equal at 2^14 / 2^16 frames)
-  static const size_t planes_min_work = [] {
-    const char *e = std::getenv("CC_AMD_PLANES_MIN_WORK");
-    return e ? static_cast<size_t>(std::strtoull(e, nullptr, 10)) : static_cast<size_t>(3) << 17;
-  }();
-  const bool small_call = bitslice_supported(code) && B * code->tab.roots.size() < planes_min_work;
+  const bool small_call = planes_small_call(code, B);
   if (algebraic_chunk_supported(code, d_er_off != nullptr) && !small_call)
     return launch_algebraic_chunk(code, float_in, d_in, d_er, d_er_off, d_out, d_nerr, d_status, B, stream);
   // The Euklid tag WITH erasures on a bit-plane code: the chain first, as bounded-distance Berlekamp-Massey -- a frame

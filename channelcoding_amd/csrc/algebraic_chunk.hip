@@ -23,11 +23,7 @@
 #include "wave_ops.hpp"
 
 namespace ccamd {
-int launch_bitslice_chien(const void *d_lamp, void *d_masks, size_t B, bool long_locators, hipStream_t stream);  // bitslice.hip
-int launch_bitslice_roots_transpose(const void *d_masks, void *d_rootsT, size_t B, hipStream_t stream);
 namespace {
-
-constexpr uint32_t kLogZero = 512;  // log of 0: ex[kLogZero + anything < 512] = 0
 
 __device__ __forceinline__ uint32_t lane63(uint32_t v) { return __builtin_amdgcn_readlane(v, 63); }
 __device__ __forceinline__ uint32_t wave_umax(uint32_t v) { return ~lane63(wave_umin(~v)); }
@@ -1216,6 +1212,43 @@ static int launch_chunk_fpw(const cc_code *code, bool float_in, const void *d_in
   return CC_OK;
 }
 
+// Berlekamp-Massey over chunks of 64 frames behind the bit-plane syndromes (synd: [block of 64 groups][j][group][32]
+// bytes): locators as logs (llg), degree / L (meta), dirty masks, locator planes for the root search (lamp).  Shared by
+// the byte chain below and the packed chain (packed.hip).
+int launch_chunk_bm(const cc_code *code, const uint8_t *d_synd, const uint16_t *d_er, const uint32_t *d_er_off,
+                    uint16_t *d_llg, uint16_t *d_meta, unsigned long long *d_mask, uint8_t *d_lamp, int ncoef,
+                    uint32_t *d_nleft, int32_t *d_nerr, int32_t *d_status, size_t B, hipStream_t stream) {
+  const int t2 = static_cast<int>(code->tab.roots.size());
+  const unsigned long long chunks = (B + 63) / 64;
+  const int dbg_stop = alg_stop_stage();
+  const unsigned long long Bq = B, blocks_needed = (chunks + 3) / 4;
+  const size_t lds = 1536 + 4 * static_cast<size_t>(bm_layout(t2).bytes);
+  unsigned long long per_cu = (160 * 1024) / lds;
+  if (per_cu < 1) per_cu = 1;
+  const unsigned long long max_grid = static_cast<unsigned long long>(code->num_cus) * per_cu;
+  const int grid = static_cast<int>(blocks_needed < max_grid ? blocks_needed : max_grid);
+  hipError_t e = hipSuccess;
+  if (lds > 48 * 1024)
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&chunk_bm_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            static_cast<int>(lds));
+  if (e == hipSuccess) {
+    const unsigned long long reg_cap = static_cast<unsigned long long>(code->num_cus) * 3;
+    const int reg_grid = static_cast<int>(blocks_needed < reg_cap ? blocks_needed : reg_cap);
+    if (t2 == 32 && !d_er_off)  // (with erasures the recurrence starts per lane at i = rho: the LDS form below)
+      hipLaunchKernelGGL((chunk_bm_reg_kernel<32>), dim3(reg_grid), dim3(256), 0, stream, code->d_alg, dbg_stop, d_synd,
+                         d_llg, d_meta, d_mask, reinterpret_cast<uint4 *>(d_lamp), d_nleft, d_nerr, d_status, Bq);
+    else if (t2 == 16 && !d_er_off)
+      hipLaunchKernelGGL((chunk_bm_reg_kernel<16>), dim3(reg_grid), dim3(256), 0, stream, code->d_alg, dbg_stop, d_synd,
+                         d_llg, d_meta, d_mask, reinterpret_cast<uint4 *>(d_lamp), d_nleft, d_nerr, d_status, Bq);
+    else
+      hipLaunchKernelGGL(chunk_bm_kernel, dim3(grid), dim3(256), lds, stream, code->d_alg, dbg_stop, d_synd, d_er, d_er_off,
+                         d_llg, d_meta, d_mask, reinterpret_cast<uint4 *>(d_lamp), ncoef, d_nleft, d_nerr, d_status, Bq);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) return hip_fail(e, "chunk Berlekamp-Massey kernel launch");
+  return CC_OK;
+}
+
 // syndromes on bit planes (bitslice.hip), Berlekamp-Massey over chunks of 64 frames, root search on planes, corrections
 static int launch_chunk_bitsliced(const cc_code *code, bool float_in, const void *d_in, const uint16_t *d_er,
                                   const uint32_t *d_er_off, uint8_t *d_out, int32_t *d_nerr, int32_t *d_status, size_t B,
@@ -1249,37 +1282,16 @@ static int launch_chunk_bitsliced(const cc_code *code, bool float_in, const void
   if (rc == CC_OK) {
     const int dbg_stop = alg_stop_stage();
     const unsigned long long Bq = B, blocks_needed = (chunks + 3) / 4;
-    const size_t lds = 1536 + 4 * static_cast<size_t>(bm_layout(t2).bytes);
-    unsigned long long per_cu = (160 * 1024) / lds;
-    if (per_cu < 1) per_cu = 1;
-    unsigned long long max_grid = static_cast<unsigned long long>(code->num_cus) * per_cu;
-    int grid = static_cast<int>(blocks_needed < max_grid ? blocks_needed : max_grid);
+    rc = launch_chunk_bm(code, d_synd, d_er, d_er_off, d_llg, d_meta, d_mask, d_lamp, ncoef, d_nleft, d_nerr, d_status, B, stream);
+    if (rc == CC_OK) rc = launch_bitslice_chien(d_lamp, d_roots, B, long_loc, stream);
     hipError_t e = hipSuccess;
-    if (lds > 48 * 1024)
-      e = hipFuncSetAttribute(reinterpret_cast<const void *>(&chunk_bm_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              static_cast<int>(lds));
-    if (e == hipSuccess) {
-      const unsigned long long reg_cap = static_cast<unsigned long long>(code->num_cus) * 3;
-      const int reg_grid = static_cast<int>(blocks_needed < reg_cap ? blocks_needed : reg_cap);
-      if (t2 == 32 && !d_er_off)  // (with erasures the recurrence starts per lane at i = rho: the LDS form below)
-        hipLaunchKernelGGL((chunk_bm_reg_kernel<32>), dim3(reg_grid), dim3(256), 0, stream, code->d_alg, dbg_stop, d_synd,
-                           d_llg, d_meta, d_mask, reinterpret_cast<uint4 *>(d_lamp), d_nleft, d_nerr, d_status, Bq);
-      else if (t2 == 16 && !d_er_off)
-        hipLaunchKernelGGL((chunk_bm_reg_kernel<16>), dim3(reg_grid), dim3(256), 0, stream, code->d_alg, dbg_stop, d_synd,
-                           d_llg, d_meta, d_mask, reinterpret_cast<uint4 *>(d_lamp), d_nleft, d_nerr, d_status, Bq);
-      else
-        hipLaunchKernelGGL(chunk_bm_kernel, dim3(grid), dim3(256), lds, stream, code->d_alg, dbg_stop, d_synd, d_er, d_er_off,
-                           d_llg, d_meta, d_mask, reinterpret_cast<uint4 *>(d_lamp), ncoef, d_nleft, d_nerr, d_status, Bq);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess && launch_bitslice_chien(d_lamp, d_roots, B, long_loc, stream) != CC_OK) e = hipErrorLaunchFailure;
-    if (e == hipSuccess) {
-      max_grid = static_cast<unsigned long long>(code->num_cus) * 8;
-      grid = static_cast<int>(blocks_needed < max_grid ? blocks_needed : max_grid);
+    if (rc == CC_OK) {
+      const unsigned long long max_grid = static_cast<unsigned long long>(code->num_cus) * 8;
+      const int grid = static_cast<int>(blocks_needed < max_grid ? blocks_needed : max_grid);
       const bool four = dbg_stop == 0;
       if (four) {  // one lane per frame; what it cannot settle goes on through d_left
-        if (launch_bitslice_roots_transpose(d_roots, d_rootsT, B, stream) != CC_OK) e = hipErrorLaunchFailure;
-        if (e == hipSuccess) {
+        rc = launch_bitslice_roots_transpose(d_roots, d_rootsT, B, stream);
+        if (rc == CC_OK) {
           static const int fixl_per_cu[2] = {[] {  // resident workgroups per CU: registers and LDS of the built kernels
                                                int v = 0;
                                                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, chunk_fixl_kernel<16>, 256, 0) != hipSuccess || v < 1) v = 3;
@@ -1303,7 +1315,7 @@ static int launch_chunk_bitsliced(const cc_code *code, bool float_in, const void
           e = hipGetLastError();
         }
       }
-      if (e == hipSuccess) {
+      if (rc == CC_OK && e == hipSuccess) {
         hipLaunchKernelGGL(chunk_fix_kernel, dim3(grid), dim3(256), 0, stream, code->d_alg,
                            code->desc.algorithm | (dbg_stop << 8), d_synd, d_llg, d_meta, four ? d_left : d_mask,
                            reinterpret_cast<const uint32_t *>(d_roots), four ? d_nleft : nullptr, d_er_off, long_loc ? 24 : 16,
@@ -1311,7 +1323,7 @@ static int launch_chunk_bitsliced(const cc_code *code, bool float_in, const void
         e = hipGetLastError();
       }
     }
-    if (e != hipSuccess) rc = hip_fail(e, "algebraic chunk kernels launch");
+    if (rc == CC_OK && e != hipSuccess) rc = hip_fail(e, "algebraic chunk kernels launch");
   }
   (void)hipFreeAsync(ws, stream);
   return rc;

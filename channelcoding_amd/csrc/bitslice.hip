@@ -44,26 +44,6 @@ using namespace bitplane;
 constexpr int kFusedGroups = 8, kFusedThreads = 512;
 constexpr size_t kFusedLdsBytes = 32 * 2 * 64 * sizeof(uint4);  // 64 KB: two workgroups per CU, four wavefronts per SIMD
 
-template <int E> __device__ __forceinline__ void times_alpha_e(uint32_t (&x)[8]) {  // x <- x alpha^E
-  const uint32_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  horner<E>(x, zero);
-}
-// part += alpha^E * (part of the lane CTRL names: the next segment, two or four further)
-template <int E, int CTRL> __device__ __forceinline__ void fold_segments(uint32_t (&part)[8]) {
-  uint32_t t[8];
-#pragma unroll
-  for (int b = 0; b < 8; ++b) t[b] = part[b];
-  times_alpha_e<E>(t);
-#pragma unroll
-  for (int b = 0; b < 8; ++b)
-    part[b] ^= static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(t[b]), CTRL, 0xF, 0xF, false));
-}
-template <int J> __device__ __forceinline__ void fold_all(uint32_t (&part)[8]) {  // valid in the lanes of segment 0
-  fold_segments<(32 * J) % 255, 0xB1>(part);   // quad_perm [1,0,3,2]: segment s ^ 1
-  fold_segments<(64 * J) % 255, 0x4E>(part);   // quad_perm [2,3,0,1]: segment s ^ 2
-  fold_segments<(128 * J) % 255, 0x104>(part);  // row_shl:4: segment s + 4
-}
-
 // syndromes J0+1 .. J0+4 of the workgroup's groups: lane = (group lane >> 3, segment lane & 7)
 // RAW keeps the result on planes ([block][j][group][8]) for the encoder's interpolation
 template <int J0, bool RAW>
@@ -484,17 +464,7 @@ bitslice_roots_transpose_kernel(const uint4 *__restrict__ masks, uint4 *__restri
     const uint4 v = masks[t * 8 + i];
     w[4 * i] = v.x, w[4 * i + 1] = v.y, w[4 * i + 2] = v.z, w[4 * i + 3] = v.w;
   }
-#pragma unroll
-  for (int sh = 16; sh >= 1; sh >>= 1) {  // exchange bit `sh` of the word index with bit `sh` of the bit position
-    const uint32_t m = sh == 16 ? 0x0000FFFFu : sh == 8 ? 0x00FF00FFu : sh == 4 ? 0x0F0F0F0Fu : sh == 2 ? 0x33333333u : 0x55555555u;
-#pragma unroll
-    for (int k = 0; k < 32; ++k) {
-      if (k & sh) continue;
-      const uint32_t x = ((w[k] >> sh) ^ w[k + sh]) & m;
-      w[k + sh] ^= x;
-      w[k] ^= x << sh;
-    }
-  }
+  transpose32(w);
 #pragma unroll
   for (int i = 0; i < 8; ++i) rootsT[t * 8 + i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
 }

@@ -1228,6 +1228,219 @@ int cc_correct_hard_batch_u16(const cc_code *code, const uint16_t *in, const uin
   return st.drain();
 }
 
+/* ------------------------------ packed bits (packed.hip) ------------------------------ */
+
+// binary BCH handles with a hard-decision algorithm; everything else has no packed form
+static int packed_supported(const cc_code *code) {
+  if (code->matrix_only) {
+    set_last_error("packed words need a code: a handle of cc_minsum_create has a parity-check matrix only");
+    return CC_ERR_UNSUPPORTED;
+  }
+  if (code->tab.family != CC_FAMILY_BCH) {
+    set_last_error("packed words are defined for binary (BCH) codes: an RS symbol has q bits");
+    return CC_ERR_UNSUPPORTED;
+  }
+  if (code->soft) {
+    set_last_error("packed words go with the hard-decision algorithms: a min-sum handle takes channel values");
+    return CC_ERR_UNSUPPORTED;
+  }
+  return CC_OK;
+}
+static int packed_ready(const cc_code *code) {
+  if (int rc = packed_supported(code)) return rc;
+  if (code->device == CC_DEVICE_NONE) return CC_ERR_NO_DEVICE;
+  return CC_OK;
+}
+static size_t packed_width(size_t bits) { return (bits + 7) / 8; }
+
+int cc_packed_bytes(const cc_code *code, int which) {
+  if (!code || which < 0 || which > 1) return -CC_ERR_INVALID_ARGUMENT;
+  if (int rc = packed_supported(code)) return -rc;
+  return static_cast<int>(packed_width(which == 0 ? code->tab.n : code->tab.l));
+}
+
+int cc_pack_bits_dev(const void *d_symbols, int width, size_t n, uint8_t *d_packed, size_t B, void *stream) {
+  if ((width != 1 && width != 2) || n > 0x7FFFFFFFu || (B && n && (!d_symbols || !d_packed))) return CC_ERR_INVALID_ARGUMENT;
+  return launch_pack_bits(d_symbols, width, n, d_packed, B, static_cast<hipStream_t>(stream));
+}
+
+int cc_unpack_bits_dev(const uint8_t *d_packed, size_t n, void *d_symbols, int width, size_t B, void *stream) {
+  if ((width != 1 && width != 2) || n > 0x7FFFFFFFu || (B && n && (!d_symbols || !d_packed))) return CC_ERR_INVALID_ARGUMENT;
+  return launch_unpack_bits(d_packed, n, d_symbols, width, B, static_cast<hipStream_t>(stream));
+}
+
+// the refusals of the byte / 16-bit route, unchanged
+static int packed_hard_supported(const cc_code *code, bool erasures) {
+  if (int rc = packed_ready(code)) return rc;
+  return code->wide ? wide_hard_supported(code, erasures) : hard_supported(code, erasures);
+}
+
+int cc_packed_route(const cc_code *code, size_t B) {
+  if (!code) return -CC_ERR_INVALID_ARGUMENT;
+  if (int rc = packed_hard_supported(code, false)) return -rc;
+  return packed_native_supported(code, B) ? 1 : 0;
+}
+
+// Generic route of a packed call: unpack into workspace of the handle's pool (bytes, 16-bit words for q > 8), the
+// router of the byte / 16-bit entry points, pack.  kind 0 = encode, 1 = extract, 2 = correct.
+static int packed_generic_dev(const cc_code *code, int kind, const uint8_t *d_src, const uint16_t *d_er, const uint32_t *d_off,
+                              uint8_t *d_dst, int32_t *d_nerr, int32_t *d_status, size_t B, hipStream_t stream) {
+  if (B == 0) return CC_OK;
+  const size_t n = code->tab.n, l = code->tab.l, width = code->wide ? 2 : 1;
+  const size_t in_w = kind == 0 ? l : n, out_w = kind == 1 ? l : n;
+  // words without erasures are corrected in place, as a byte call with out == in (it then skips its copy of the words)
+  const bool in_place = kind == 2 && !d_er && !code->wide;
+  const size_t in_bytes = (B * in_w * width + 255) & ~static_cast<size_t>(255);
+  uint8_t *ws = nullptr;
+  CC_HIP_TRY(workspace_alloc(code, reinterpret_cast<void **>(&ws), in_bytes + (in_place ? 0 : B * out_w * width) + 16, stream));
+  uint8_t *a = ws, *b = in_place ? ws : ws + in_bytes;
+  int rc = launch_unpack_bits(d_src, in_w, a, static_cast<int>(width), B, stream);
+  if (rc == CC_OK) {
+    if (code->wide) {
+      const uint16_t *a16 = reinterpret_cast<const uint16_t *>(a);
+      uint16_t *b16 = reinterpret_cast<uint16_t *>(b);
+      rc = kind == 0   ? launch_wide_encode(code, a16, b16, B, stream)
+           : kind == 1 ? launch_wide_extract(code, a16, b16, B, stream)
+                       : launch_wide_correct(code, a16, d_er, d_off, b16, d_nerr, d_status, B, stream);
+    } else if (kind == 0) {
+      rc = launch_encode(code, a, b, B, stream);
+    } else if (kind == 1) {
+      rc = launch_extract(code, a, b, B, stream);
+    } else if (d_er && code->desc.algorithm == CC_ALG_PGZ) {
+      rc = launch_pgz_erasures(code, a, d_er, d_off, b, d_nerr, d_status, B, stream);
+    } else {
+      rc = launch_algebraic(code, false, a, d_er, d_off, b, d_nerr, d_status, B, stream);
+    }
+  }
+  if (rc == CC_OK) rc = launch_pack_bits(b, static_cast<int>(width), out_w, d_dst, B, stream);
+  (void)hipFreeAsync(ws, stream);
+  return rc;
+}
+
+static int packed_correct_dev(const cc_code *code, const uint8_t *d_in, const uint16_t *d_er, const uint32_t *d_off,
+                              uint8_t *d_out, int32_t *d_nerr, int32_t *d_status, size_t B, hipStream_t stream) {
+  if (!d_er && packed_native_supported(code, B)) return launch_packed_correct(code, d_in, d_out, d_nerr, d_status, B, stream);
+  return packed_generic_dev(code, 2, d_in, d_er, d_off, d_out, d_nerr, d_status, B, stream);
+}
+
+// encode (kind 0) / extract (kind 1): division coding on the packed words themselves, anything else the generic way
+static int packed_map_dev(const cc_code *code, int kind, const uint8_t *d_src, uint8_t *d_dst, size_t B, hipStream_t stream) {
+  if (kind == 0 && packed_encode_native(code)) return launch_packed_encode(code, d_src, d_dst, B, stream);
+  if (kind == 1 && packed_extract_native(code)) return launch_packed_extract(code, d_src, d_dst, B, stream);
+  return packed_generic_dev(code, kind, d_src, nullptr, nullptr, d_dst, nullptr, nullptr, B, stream);
+}
+
+int cc_packed_map_route(const cc_code *code, int which) {
+  if (!code || which < 0 || which > 1) return -CC_ERR_INVALID_ARGUMENT;
+  if (int rc = packed_ready(code)) return -rc;
+  return (which == 0 ? packed_encode_native(code) : packed_extract_native(code)) ? 1 : 0;
+}
+
+int cc_encode_packed_batch_dev(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, void *stream) {
+  if (!code || (B && (!d_msg || !d_cw))) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = packed_ready(code)) return rc;
+  DeviceGuard guard(code->device);
+  return packed_map_dev(code, 0, d_msg, d_cw, B, static_cast<hipStream_t>(stream));
+}
+
+int cc_extract_packed_batch_dev(const cc_code *code, const uint8_t *d_cw, uint8_t *d_msg, size_t B, void *stream) {
+  if (!code || (B && (!d_cw || !d_msg))) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = packed_ready(code)) return rc;
+  DeviceGuard guard(code->device);
+  return packed_map_dev(code, 1, d_cw, d_msg, B, static_cast<hipStream_t>(stream));
+}
+
+int cc_correct_hard_packed_batch_dev(const cc_code *code, const uint8_t *d_in, const uint16_t *d_erasures,
+                                     const uint32_t *d_erasure_offsets, uint8_t *d_out, int32_t *d_nerr,
+                                     int32_t *d_status, size_t B, void *stream) {
+  if (!code || (B && (!d_in || !d_out))) return CC_ERR_INVALID_ARGUMENT;
+  if ((d_erasures == nullptr) != (d_erasure_offsets == nullptr)) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = packed_hard_supported(code, d_erasures != nullptr)) return rc;
+  DeviceGuard guard(code->device);
+  return packed_correct_dev(code, d_in, d_erasures, d_erasure_offsets, d_out, d_nerr, d_status, B,
+                            static_cast<hipStream_t>(stream));
+}
+
+// host pointers: the chunked staging of the byte entry points; kind as packed_generic_dev
+static int packed_host(const cc_code *code, int kind, const uint8_t *src, const uint16_t *erasures,
+                       const uint32_t *erasure_offsets, uint8_t *dst, int32_t *nerr, int32_t *status, size_t B) {
+  if (!code || (B && (!src || !dst))) return CC_ERR_INVALID_ARGUMENT;
+  if ((erasures == nullptr) != (erasure_offsets == nullptr)) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = kind == 2 ? packed_hard_supported(code, erasures != nullptr) : packed_ready(code)) return rc;
+  if (B == 0) return CC_OK;
+  const size_t n = code->tab.n, l = code->tab.l;
+  const size_t in_w = packed_width(kind == 0 ? l : n), out_w = packed_width(kind == 1 ? l : n);
+  if (erasures) {
+    const size_t ne = erasure_offsets[B];
+    for (size_t e = 0; e < ne; ++e)
+      if (erasures[e] >= n) return CC_ERR_INVALID_ARGUMENT;
+  }
+  DeviceGuard guard(code->device);
+  StageLock sl(code);
+  if (sl.rc != CC_OK) return sl.rc;
+  HostStage &st = *sl.st;
+  const size_t CH = chunk_frames(n * (code->wide ? 2 : 1), B);  // (the generic route's workspace is what a chunk costs)
+  if (B > 2 * CH)
+    if (int rc_fs = st.fresh_streams()) return rc_fs;
+  const bool dma_in = HostStage::dma_ready(src), dma_out = HostStage::dma_ready(dst),
+             dma_ne = nerr && HostStage::dma_ready(nerr), dma_st = status && HostStage::dma_ready(status);
+  size_t k = 0;
+  for (size_t c0 = 0; c0 < B; c0 += CH, ++k) {
+    const int slot = static_cast<int>(k & 1);
+    const size_t m = B - c0 < CH ? B - c0 : CH;
+    hipStream_t s = st.stream[slot];
+    if (int r = st.retire(slot)) return r;
+    uint8_t *d_src = nullptr, *d_dst = nullptr;
+    int32_t *d_nerr = nullptr, *d_status = nullptr;
+    const uint16_t *d_er = nullptr;
+    const uint32_t *d_off = nullptr;
+    if (int r = st.get(slot, 0, m * in_w, &d_src)) return r;
+    if (int r = st.get(slot, 1, m * out_w, &d_dst)) return r;
+    if (int r = st.upload(slot, 0, d_src, src + c0 * in_w, m * in_w, dma_in)) return r;
+    int rc;
+    if (kind == 2) {
+      if (int r = st.get(slot, 2, m, &d_nerr)) return r;
+      if (int r = st.get(slot, 3, m, &d_status)) return r;
+      if (int r = upload_erasures(st, slot, 5, erasures, erasure_offsets, c0, m, &d_er, &d_off)) return r;
+      rc = packed_correct_dev(code, d_src, d_er, d_off, d_dst, d_nerr, d_status, m, s);
+    } else {
+      rc = packed_map_dev(code, kind, d_src, d_dst, m, s);
+    }
+    if (rc != CC_OK) return rc;
+    if (int r = st.download(slot, 1, dst + c0 * out_w, d_dst, m * out_w, dma_out)) return r;
+    if (nerr)
+      if (int r = st.download(slot, 2, nerr + c0, d_nerr, m * sizeof(int32_t), dma_ne)) return r;
+    if (status)
+      if (int r = st.download(slot, 3, status + c0, d_status, m * sizeof(int32_t), dma_st)) return r;
+  }
+  return st.drain();
+}
+
+int cc_encode_packed_batch(const cc_code *code, const uint8_t *msg, uint8_t *cw, size_t B) {
+  return packed_host(code, 0, msg, nullptr, nullptr, cw, nullptr, nullptr, B);
+}
+int cc_extract_packed_batch(const cc_code *code, const uint8_t *cw, uint8_t *msg, size_t B) {
+  return packed_host(code, 1, cw, nullptr, nullptr, msg, nullptr, nullptr, B);
+}
+int cc_correct_hard_packed_batch(const cc_code *code, const uint8_t *in, const uint16_t *erasures,
+                                 const uint32_t *erasure_offsets, uint8_t *out, int32_t *nerr, int32_t *status, size_t B) {
+  return packed_host(code, 2, in, erasures, erasure_offsets, out, nerr, status, B);
+}
+
+int cc_decode_hard_packed_batch(const cc_code *code, const uint8_t *in, const uint16_t *erasures,
+                                const uint32_t *erasure_offsets, uint8_t *msg, uint8_t *words, int32_t *nerr,
+                                int32_t *status, size_t B) {
+  if (!code || (B && (!in || !msg))) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = packed_supported(code)) return rc;
+  std::vector<uint8_t> tmp;
+  if (!words && B) {
+    tmp.resize(B * packed_width(code->tab.n));
+    words = tmp.data();
+  }
+  if (int rc = cc_correct_hard_packed_batch(code, in, erasures, erasure_offsets, words, nerr, status, B)) return rc;
+  return cc_extract_packed_batch(code, words, msg, B);
+}
+
 /* ------------------------------ Monte-Carlo ------------------------------ */
 
 static int mc_supported(const cc_code *code) {

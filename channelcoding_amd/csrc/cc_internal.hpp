@@ -194,6 +194,14 @@ int launch_bitslice_syndromes(const cc_code *code, bool float_in, const void *d_
                               hipStream_t stream);
 bool bitslice_encode_supported(const cc_code *code);
 int launch_bitslice_encode(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, hipStream_t stream);
+// the stages of the bit-plane chain that the packed chain (packed.hip) shares with the byte chain
+int launch_bitslice_chien(const void *d_lamp, void *d_masks, size_t B, bool long_locators, hipStream_t stream);
+int launch_bitslice_roots_transpose(const void *d_masks, void *d_rootsT, size_t B, hipStream_t stream);
+constexpr uint32_t kLogZero = 512;  // log of 0 in the locators the Berlekamp-Massey kernels write (llg): ex[kLogZero + anything < 512] = 0
+int launch_chunk_bm(const cc_code *code, const uint8_t *d_synd, const uint16_t *d_er, const uint32_t *d_er_off,
+                    uint16_t *d_llg, uint16_t *d_meta, unsigned long long *d_mask, uint8_t *d_lamp, int ncoef,
+                    uint32_t *d_nleft, int32_t *d_nerr, int32_t *d_status, size_t B, hipStream_t stream);
+bool planes_small_call(const cc_code *code, size_t B);  // algebraic.hip: below CC_AMD_PLANES_MIN_WORK the chain is not taken
 int launch_pgz_erasures(const cc_code *code, const uint8_t *d_in, const uint16_t *d_er, const uint32_t *d_er_off,
                         uint8_t *d_out, int32_t *d_nerr, int32_t *d_status, size_t B, hipStream_t stream);
 // the object (part) of a geometry that carries a min-sum variant when the geometry is split over `parts` objects
@@ -216,6 +224,16 @@ std::vector<uint8_t> build_parity_table(const Field &f, const CodeTables &t);
 int launch_encode(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, hipStream_t stream);
 int launch_encode_bits(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, hipStream_t stream);
 int launch_extract(const cc_code *code, const uint8_t *d_cw, uint8_t *d_msg, size_t B, hipStream_t stream);
+// packed.hip: n bits in ceil(n / 8) bytes, bit p & 7 of byte p >> 3 = coefficient of x^p
+int launch_pack_bits(const void *d_sym, int width, size_t n, uint8_t *d_packed, size_t B, hipStream_t stream);
+int launch_unpack_bits(const uint8_t *d_packed, size_t n, void *d_sym, int width, size_t B, hipStream_t stream);
+bool packed_native_supported(const cc_code *code, size_t B);
+int launch_packed_correct(const cc_code *code, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nerr, int32_t *d_status,
+                          size_t B, hipStream_t stream);
+bool packed_encode_native(const cc_code *code);   // division coding, n - l <= 32 parity bits, q <= 8
+bool packed_extract_native(const cc_code *code);  // division coding, any q
+int launch_packed_encode(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, hipStream_t stream);
+int launch_packed_extract(const cc_code *code, const uint8_t *d_cw, uint8_t *d_msg, size_t B, hipStream_t stream);
 // mc.hip (Monte-Carlo calls on one handle must be issued on one stream at a time: they share a workspace)
 int mc_run(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
            uint64_t *d_counters, hipStream_t stream);

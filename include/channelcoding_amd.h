@@ -293,6 +293,50 @@ int cc_extract_batch_u16_dev(const cc_code *code, const uint16_t *d_cw, uint16_t
 int cc_get_poly_u16(const cc_code *code, int which, uint16_t *out, size_t cap);
 uint32_t cc_q(const cc_code *code);
 
+/* ---- packed bits: binary BCH words as callers keep them (a NAND page, a BBFRAME).  The same members as above --
+ *      cyclic::encode cyclic.h:289-311, correct cyclic.h:207-252, decode cyclic.h:313-327 -- on another container:
+ *      a frame of a code of length n is P = ceil(n / 8) bytes, the coefficient of x^p (index p of the byte API) is bit
+ *      p & 7 of byte p >> 3, least significant bit first (numpy.packbits(frame, bitorder="little")); frames are
+ *      contiguous at pitch P; a packed message is the same with l in place of n.  Pad bits (positions n .. 8P - 1) are
+ *      IGNORED ON INPUT AND WRITTEN AS 0 ON OUTPUT.  A shortened code uses its own n = N.
+ *      Contract: for every frame, unpacking the output of a packed call gives byte for byte what the byte (q <= 8) or
+ *      _u16 (q > 8) call returns for the unpacked input, with identical nerr and status -- failing frames (out = the
+ *      received word), the CC_FRAME_* classes, the shortened-code rule, the two-trial PGZ rule with erasures and the
+ *      refusals of the byte route included.  A bit has no symbol width: these are the same functions for q = 3 .. 15.
+ *      Only BCH handles with a hard-decision algorithm qualify; RS handles, min-sum handles and handles of
+ *      cc_minsum_create answer CC_ERR_UNSUPPORTED (cc_last_error says why), before any device is asked for.
+ *      Erasures are the CSR of cc_correct_hard_batch; out may be the same buffer as in.
+ *      Routes: calls the byte route would send down the bit-plane chain of GF(2^8) -- n <= 255, no
+ *      erasures, above the small-call threshold -- are decoded from the packed words natively, division-coded
+ *      codes are extracted (any q) and, with n - l <= 32 parity bits and q <= 8, encoded on the packed words; every
+ *      other call is unpacked into workspace of the handle, sent through the byte / 16-bit router and packed again.
+ *      CC_AMD_PACKED_NATIVE=0 (read once) sends everything the second way. ---- */
+/* bytes of a packed codeword (which = 0) or message (which = 1); a negative cc_status if the handle does not qualify */
+int cc_packed_bytes(const cc_code *code, int which);
+/* 1: a packed hard-decode call of B frames without erasures takes the native route under the settings in force,
+ * 0: the generic one; a negative cc_status where the call itself would be refused */
+int cc_packed_route(const cc_code *code, size_t B);
+/* the same for cc_encode_packed_batch (which = 0) and cc_extract_packed_batch (which = 1) */
+int cc_packed_map_route(const cc_code *code, int which);
+/* one symbol per bit (width = 1: bytes, width = 2: 16-bit words; bit 0 of each symbol counts) <-> packed, B frames of n
+ * bits, on the current device; exactly B * n symbols and B * ceil(n / 8) bytes are touched.  No handle is needed. */
+int cc_pack_bits_dev(const void *d_symbols, int width, size_t n, uint8_t *d_packed, size_t B, void *stream);
+int cc_unpack_bits_dev(const uint8_t *d_packed, size_t n, void *d_symbols, int width, size_t B, void *stream);
+int cc_encode_packed_batch(const cc_code *code, const uint8_t *msg /* B*P(l) */, uint8_t *cw /* B*P(n) */, size_t B);
+int cc_encode_packed_batch_dev(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, void *stream);
+int cc_correct_hard_packed_batch(const cc_code *code, const uint8_t *in /* B*P(n) */, const uint16_t *erasures,
+                                 const uint32_t *erasure_offsets, uint8_t *out /* B*P(n) */, int32_t *nerr,
+                                 int32_t *status, size_t B);
+int cc_correct_hard_packed_batch_dev(const cc_code *code, const uint8_t *d_in, const uint16_t *d_erasures,
+                                     const uint32_t *d_erasure_offsets, uint8_t *d_out, int32_t *d_nerr,
+                                     int32_t *d_status, size_t B, void *stream);
+int cc_extract_packed_batch(const cc_code *code, const uint8_t *cw /* B*P(n) */, uint8_t *msg /* B*P(l) */, size_t B);
+int cc_extract_packed_batch_dev(const cc_code *code, const uint8_t *d_cw, uint8_t *d_msg, size_t B, void *stream);
+/* correct + extract as cc_decode_hard_batch; words (B*P(n)) may be NULL */
+int cc_decode_hard_packed_batch(const cc_code *code, const uint8_t *in, const uint16_t *erasures,
+                                const uint32_t *erasure_offsets, uint8_t *msg, uint8_t *words, int32_t *nerr,
+                                int32_t *status, size_t B);
+
 /* ---- introspection for the benchmark: name and launch geometry of the kernel a call would use ---- */
 int cc_kernel_info(const cc_code *code, char *name, size_t cap, uint32_t *frames_per_workgroup,
                    uint32_t *threads_per_workgroup, uint32_t *lds_bytes);
