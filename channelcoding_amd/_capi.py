@@ -23,6 +23,7 @@ FRAME_OK, FRAME_NOT_CONVERGED, FRAME_LOCATOR, FRAME_RECHECK, FRAME_ERASURES = ra
 MC_FRAMES, MC_WORD_ERRORS, MC_BIT_ERRORS, MC_FAILURES, MC_UNDETECTED, MC_ITER_SUM, MC_CHANNEL_BIT_ERRORS = range(7)
 MC_CHANNEL_ERASURES = 7
 MC_ITER_HIST, MC_NCOUNTERS = 8, 64
+HARD_ROUTE_WAVE, HARD_ROUTE_CHUNK, HARD_ROUTE_PLANES, HARD_ROUTE_LONG, HARD_ROUTE_WIDE, HARD_ROUTE_TRIALS = range(6)
 
 SOFT_ALGS = (ALG_MS, ALG_NMS, ALG_OMS, ALG_SCMS1, ALG_SCMS2, ALG_2DNMS)
 HARD_ALGS = (ALG_PGZ, ALG_BM, ALG_EUKLID)
@@ -89,6 +90,7 @@ _SIGNATURES = {
     "cc_extract_batch_u16_dev": (C.c_int, [_VP, _VP, _VP, C.c_size_t, _VP]),
     "cc_get_poly_u16": (C.c_int, [_VP, C.c_int, _VP, C.c_size_t]),
     "cc_q": (C.c_uint32, [_VP]),
+    "cc_hard_route": (C.c_int, [_VP, C.c_size_t, C.c_int]),
     "cc_packed_bytes": (C.c_int, [_VP, C.c_int]),
     "cc_packed_route": (C.c_int, [_VP, C.c_size_t]),
     "cc_packed_map_route": (C.c_int, [_VP, C.c_int]),

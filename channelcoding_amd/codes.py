@@ -369,6 +369,14 @@ class cyclic:
             raise CcError(-r, "cc_packed_route")
         return r
 
+    def hard_route(self, B, erasures=False):
+        """The kernels a hard-decode call of B frames takes (cc_hard_route): capi.HARD_ROUTE_WAVE / CHUNK / PLANES / LONG /
+        WIDE / TRIALS; raises where the call itself would be refused."""
+        r = capi.lib().cc_hard_route(self._h, int(B), int(bool(erasures)))
+        if r < 0:
+            raise CcError(-r, "cc_hard_route")
+        return r
+
     def packed_map_route(self, which):
         """1 if encode_batch (which = 0) / extract_batch (which = 1) with packed=True works on the packed words
         themselves, 0 if it goes through unpack / byte route / pack (cc_packed_map_route)."""

@@ -52,7 +52,11 @@ __device__ __forceinline__ uint32_t shift_up(uint32_t v) {
   return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x138 /* wave_shr:1 */, 0xF, 0xF, true));
 }
 
-template <bool FLOAT_IN>
+// TW: an RS code with roots alpha^(mu + i step) other than alpha^1 .. alpha^2t.  With Z = alpha^(step p)
+// and Y = e alpha^(mu p) the syndromes are S_i = sum Y Z^i whatever (mu, step) is, so the locator stage is the same;
+// the roots are tested at Z^-1, the erasure pre-load takes Z, and Forney's quotient Y / Z = e alpha^((mu - step) p) is
+// scaled by alpha^(twist p).  TW = false is the code as it was (Z = X = alpha^p, twist = 0).
+template <bool FLOAT_IN, bool TW>
 __global__ void __launch_bounds__(256)
 algebraic_kernel(const AlgebraicTables *__restrict__ T, int alg, const void *__restrict__ in_raw,
                  const uint16_t *__restrict__ er, const uint32_t *__restrict__ er_off, uint8_t *__restrict__ out,
@@ -92,7 +96,11 @@ algebraic_kernel(const AlgebraicTables *__restrict__ T, int alg, const void *__r
     e0[c] = static_cast<uint32_t>((r0 * p) % nn);
     dstep[c] = static_cast<uint32_t>((step * p) % nn);
     xinv[c] = static_cast<uint32_t>((nn - (p % nn)) % nn);  // log of X^-1 for X = alpha^p
+    if (TW) xinv[c] = (static_cast<uint32_t>(nn) - dstep[c]) % static_cast<uint32_t>(nn);  // log of Z^-1
   }
+  const int twist = TW ? T->twist : 0;
+  // log of the locator Z = alpha^(step p) of position p
+  auto zlog = [&](uint32_t p) -> uint32_t { return (static_cast<uint32_t>(step) * (p % nn)) % nn; };
 
   for (unsigned long long frame = wave; frame < B; frame += nwaves) {
     if (redo && status_out[frame] == CC_FRAME_OK) continue;  // wave-uniform
@@ -152,7 +160,7 @@ algebraic_kernel(const AlgebraicTables *__restrict__ T, int alg, const void *__r
         // r_prev = S(x) u(x), r_cur = x^2t, w_prev = u, w_cur = 0; divide until deg r_cur < (2t + rho) / 2;
         // lambda = w_cur / w_cur(0).  One long-division step per loop trip, at most 2t + rho trips.
         uint32_t u = (lane == 0) ? 1u : 0u;
-        for (uint32_t e = 0; e < nerase; ++e) u ^= gmul(ex[er[ebase + e] % nn], shift_up(u));  // :171-172
+        for (uint32_t e = 0; e < nerase; ++e) u ^= gmul(ex[TW ? zlog(er[ebase + e]) : er[ebase + e] % nn], shift_up(u));  // :171-172
         uint32_t rp = 0;  // S(x) * u(x): coefficient j = sum_m S_{j-m} u_m
         for (int m = 0; m <= rho; ++m) {
           const uint32_t um = __builtin_amdgcn_readlane(u, m);
@@ -189,7 +197,7 @@ algebraic_kernel(const AlgebraicTables *__restrict__ T, int alg, const void *__r
       // ---- Berlekamp-Massey, hard_decision.h:116-155 (lane j <-> coefficient j) ----
       lam = (lane == 0) ? 1u : 0u;
       for (uint32_t e = 0; e < nerase; ++e) {  // lambda *= (1 + alpha^erasure x), :128-131
-        const uint32_t X = ex[er[ebase + e] % nn];
+        const uint32_t X = ex[TW ? zlog(er[ebase + e]) : er[ebase + e] % nn];
         lam ^= gmul(X, shift_up(lam));
       }
       uint32_t bpoly = lam;
@@ -263,14 +271,15 @@ algebraic_kernel(const AlgebraicTables *__restrict__ T, int alg, const void *__r
           if (isroot[c]) W.rp[rank[c]] = static_cast<uint8_t>(lane + 64 * c);
         uint32_t y = 0;
         if (lane < deg) {
-          const uint32_t p = W.rp[lane];
-          const uint32_t xi = p ? static_cast<uint32_t>(nn) - p : 0u;
+          const uint32_t p = W.rp[lane], zl = TW ? zlog(p) : p;
+          const uint32_t xi = zl ? static_cast<uint32_t>(nn) - zl : 0u;
           const uint32_t x2 = (2 * xi) % static_cast<uint32_t>(nn);
           uint32_t num = 0, den = 0;
           for (int j = deg - 1; j >= 0; --j) num = gmul_pow(num, xi) ^ W.om[j];
           const int mtop = (deg & 1) ? deg : deg - 1;
           for (int m = mtop; m >= 1; m -= 2) den = gmul_pow(den, x2) ^ W.lam[m];
           y = (num && den) ? ex[lg[num] + nn - lg[den]] : 0u;
+          if (TW) y = gmul_pow(y, (static_cast<uint32_t>(twist) * p) % nn);
         }
         W.val[lane] = static_cast<uint8_t>(y);
 #pragma unroll
@@ -427,21 +436,32 @@ bool planes_small_call(const cc_code *code, size_t B) {
   return bitslice_supported(code) && B * code->tab.roots.size() < planes_min_work;
 }
 
+// The route of a call of B frames: launch_algebraic (below) switches on this, cc_hard_route reports it.
+// CC_HARD_ROUTE_PLANES with erasures and the Euklid tag means "the chain first, Sugiyama over the frames it leaves".
+int algebraic_route(const cc_code *code, size_t B, bool erasures) {
+  if (algebraic_long_needed(code, erasures)) return CC_HARD_ROUTE_LONG;
+  const bool small_call = planes_small_call(code, B);
+  if (algebraic_chunk_supported(code, erasures) && !small_call)
+    return bitslice_supported(code) ? CC_HARD_ROUTE_PLANES : CC_HARD_ROUTE_CHUNK;
+  if (erasures && code->desc.algorithm == CC_ALG_EUKLID && bitslice_supported(code) && !small_call) return CC_HARD_ROUTE_PLANES;
+  return CC_HARD_ROUTE_WAVE;
+}
+
 int launch_algebraic(const cc_code *code, bool float_in, const void *d_in, const uint16_t *d_er,
                      const uint32_t *d_er_off, uint8_t *d_out, int32_t *d_nerr, int32_t *d_status, size_t B,
                      hipStream_t stream) {
   if (B == 0) return CC_OK;
-  if (algebraic_long_needed(code, d_er_off != nullptr))
+  const int route = algebraic_route(code, B, d_er_off != nullptr);
+  if (route == CC_HARD_ROUTE_LONG)
     return launch_algebraic_long(code, float_in, d_in, d_er, d_er_off, d_out, d_nerr, d_status, B, stream);
-  const bool small_call = planes_small_call(code, B);
-  if (algebraic_chunk_supported(code, d_er_off != nullptr) && !small_call)
-    return launch_algebraic_chunk(code, float_in, d_in, d_er, d_er_off, d_out, d_nerr, d_status, B, stream);
   // The Euklid tag WITH erasures on a bit-plane code: the chain first, as bounded-distance Berlekamp-Massey -- a frame
   // it corrects lies within the capability (2e + rho <= 2t), where the key equation has one solution and Sugiyama's
   // remainder sequence finds the same one -- then Sugiyama itself (the kernel below, in place on the output) over the
   // frames the chain left with a non-zero status: the hopeless ones, and the ones hard_decision.h:176's integer stop
   // rule lets the reference decode beyond the capability when rho is odd (E39).
-  const bool chain_first = d_er_off != nullptr && code->desc.algorithm == CC_ALG_EUKLID && bitslice_supported(code) && !small_call;
+  const bool chain_first = route == CC_HARD_ROUTE_PLANES && d_er_off != nullptr && code->desc.algorithm == CC_ALG_EUKLID;
+  if ((route == CC_HARD_ROUTE_PLANES || route == CC_HARD_ROUTE_CHUNK) && !chain_first)
+    return launch_algebraic_chunk(code, float_in, d_in, d_er, d_er_off, d_out, d_nerr, d_status, B, stream);
   int32_t *st_tmp = nullptr;
   if (chain_first) {
     if (d_status == nullptr) {
@@ -474,12 +494,14 @@ int launch_algebraic(const cc_code *code, bool float_in, const void *d_in, const
   // the erasure locator enters the start polynomials.
   const int alg_eff = (code->desc.algorithm == CC_ALG_EUKLID && d_er_off == nullptr) ? CC_ALG_PGZ : code->desc.algorithm;
   const int alg_arg = alg_eff | (dbg_stop << 8) | (chain_first ? 1 << 16 : 0);
-  if (float_in)
-    hipLaunchKernelGGL(algebraic_kernel<true>, dim3(grid), dim3(256), 0, stream, code->d_alg, alg_arg, d_in,
-                       d_er, d_er_off, d_out, d_nerr, d_status, Bq);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, code->d_alg, alg_arg, d_in, d_er, d_er_off, d_out,
+                       d_nerr, d_status, Bq);
+  };
+  if (rs_twisted(code))
+    float_in ? launch(algebraic_kernel<true, true>) : launch(algebraic_kernel<false, true>);
   else
-    hipLaunchKernelGGL(algebraic_kernel<false>, dim3(grid), dim3(256), 0, stream, code->d_alg, alg_arg,
-                       d_in, d_er, d_er_off, d_out, d_nerr, d_status, Bq);
+    float_in ? launch(algebraic_kernel<true, false>) : launch(algebraic_kernel<false, false>);
   hipError_t e = hipGetLastError();
   if (st_tmp) (void)hipFreeAsync(st_tmp, stream);
   if (e != hipSuccess) return hip_fail(e, "algebraic kernel launch");

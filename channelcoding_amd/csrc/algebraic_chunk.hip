@@ -52,7 +52,9 @@ __host__ __device__ inline ChunkLayout chunk_layout(int t2, int fpw) {
   return c;
 }
 
-template <bool FLOAT_IN, int FPW>
+// TW: an RS code with roots alpha^(mu + i step) other than alpha^1 .. alpha^2t (algebraic.hip): roots tested
+// at Z^-1 = alpha^(-step p), Forney's quotient scaled by alpha^(twist p); TW = false is the code as it was
+template <bool FLOAT_IN, int FPW, bool TW>
 __global__ void __launch_bounds__(256, 4)
 algebraic_chunk_kernel(const AlgebraicTables *__restrict__ T, int alg, const void *__restrict__ in_raw,
                        uint8_t *__restrict__ out, int32_t *__restrict__ nerr_out, int32_t *__restrict__ status_out,
@@ -93,7 +95,9 @@ algebraic_chunk_kernel(const AlgebraicTables *__restrict__ T, int alg, const voi
     e0[c] = static_cast<uint32_t>((r0 * p) % nn);
     dstep[c] = static_cast<uint32_t>((step * p) % nn);
     xinv[c] = static_cast<uint32_t>((nn - (p % nn)) % nn);
+    if (TW) xinv[c] = (static_cast<uint32_t>(nn) - dstep[c]) % static_cast<uint32_t>(nn);  // log of Z^-1
   }
+  const uint32_t twist = TW ? static_cast<uint32_t>(T->twist) : 0u;
   uint32_t dk[4][4];  // (k + 1) * dstep mod nn, k = 0..3
 #pragma unroll
   for (int c = 0; c < 4; ++c)
@@ -339,8 +343,8 @@ algebraic_chunk_kernel(const AlgebraicTables *__restrict__ T, int alg, const voi
           const uint32_t oml = lg2[om];
           uint32_t y = 0;
           if (lane < deg) {
-            const uint32_t p = RP[lane];
-            const uint32_t xi = p ? static_cast<uint32_t>(nn) - p : 0u;  // log X^-1
+            const uint32_t p = RP[lane], zl = TW ? (static_cast<uint32_t>(step) * p) % static_cast<uint32_t>(nn) : p;
+            const uint32_t xi = zl ? static_cast<uint32_t>(nn) - zl : 0u;  // log X^-1
             uint32_t x2 = 2 * xi;
             x2 = umin32(x2, x2 - static_cast<uint32_t>(nn));
             uint32_t num = 0, den = 0, e = 0;
@@ -356,6 +360,7 @@ algebraic_chunk_kernel(const AlgebraicTables *__restrict__ T, int alg, const voi
               e = umin32(e, e - static_cast<uint32_t>(nn));
             }
             y = (num && den) ? ex[lg[num] + nn - lg[den]] : 0u;
+            if (TW) y = y ? ex[lg[y] + (twist * p) % static_cast<uint32_t>(nn)] : 0u;
           }
           VAL[lane] = static_cast<uint8_t>(y);
 #pragma unroll
@@ -738,6 +743,7 @@ chunk_bm_reg_kernel(const AlgebraicTables *__restrict__ T, int dbg_stop, const u
 // of a 64-frame chunk at a time.  All polynomial arithmetic on logs with log 0 = 512 (no zero tests): a term
 // lambda_m X^-m is ex[log lambda_m + (m * log X^-1 mod nn)], the exponent advancing by one add + one wrap per
 // coefficient; wave-uniform coefficients come from a register by v_readlane, not from LDS.
+template <bool TW>  // TW: RS roots alpha^(mu + i step) other than alpha^1 .. alpha^2t, as in algebraic_chunk_kernel
 __global__ void __launch_bounds__(256)
 chunk_fix_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t *__restrict__ synd,
                  const uint16_t *__restrict__ llg, const uint16_t *__restrict__ meta,
@@ -779,7 +785,9 @@ chunk_fix_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t *
     e0[c] = static_cast<uint32_t>((r0 * p) % nn);
     dstep[c] = static_cast<uint32_t>((step * p) % nn);
     xinv[c] = static_cast<uint32_t>((nn - (p % nn)) % nn);
+    if (TW) xinv[c] = (static_cast<uint32_t>(nn) - dstep[c]) % static_cast<uint32_t>(nn);  // log of Z^-1
   }
+  const uint32_t twist = TW ? static_cast<uint32_t>(T->twist) : 0u;
 
   const unsigned long long nchunks = (B + 63) / 64;
   const unsigned long long wave = static_cast<unsigned long long>(blockIdx.x) * 4 + wid;
@@ -883,8 +891,8 @@ chunk_fix_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t *
         const uint32_t oml = lg2[om];
         uint32_t y = 0;
         if (lane < deg) {
-          const uint32_t p = RP[lane];
-          const uint32_t xi = p ? static_cast<uint32_t>(nn) - p : 0u;  // log X^-1
+          const uint32_t p = RP[lane], zl = TW ? (static_cast<uint32_t>(step) * p) % static_cast<uint32_t>(nn) : p;
+          const uint32_t xi = zl ? static_cast<uint32_t>(nn) - zl : 0u;  // log X^-1
           uint32_t x2 = 2 * xi;
           x2 = umin32(x2, x2 - static_cast<uint32_t>(nn));
           uint32_t num = 0, den = 0, e = 0;
@@ -900,6 +908,7 @@ chunk_fix_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t *
             e += x2;
           }
           y = (num && den) ? ex[lg[num] + nn - lg[den]] : 0u;
+          if (TW) y = y ? ex[lg[y] + (twist * p) % static_cast<uint32_t>(nn)] : 0u;
         }
         VAL[lane] = static_cast<uint8_t>(y);
 #pragma unroll
@@ -960,7 +969,9 @@ chunk_fix_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t *
 // the error loop serves up to 64 frames.  Frames that need the general treatment -- locator longer than 16, or L != deg (the re-check has to be
 // evaluated) -- go to chunk_fix_kernel through `left`.
 // MD = longest locator served here: 16 (= t of the largest code; calls without erasures), 24 for calls with erasures
-template <int MD>
+// TW: RS roots alpha^mu .. alpha^(mu + 2t - 1) with mu != 1 (the plane chain serves step = 1 only, so Z = X): one more
+// log-add per located error, the factor alpha^(twist p) on Forney's quotient
+template <int MD, bool TW>
 __global__ void __launch_bounds__(256)
 chunk_fixl_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t *__restrict__ synd,
                   const uint16_t *__restrict__ llg, const uint16_t *__restrict__ meta,
@@ -982,6 +993,7 @@ chunk_fixl_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t 
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), f = lane;
   const int n = T->n, t2 = T->nroots, nc = t2 + 1;
   const bool is_rs = T->family == CC_FAMILY_RS;
+  const uint32_t twist = TW ? static_cast<uint32_t>(T->twist) : 0u;
 #ifdef CC_AMD_EXPERIMENTS  // CC_EXP_FIXL bits: 1 no load/store of the symbols (16 no load, 32 no store), 2 no Forney sums, 4 no error loop, 8 no omega
   const int xf = alg >> 8;
   alg &= 0xFF;
@@ -1113,7 +1125,7 @@ chunk_fixl_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t 
           den ^= exl[ll[m] + ee];
           ee += x2;
         }
-        y = (num && den) ? exl[lg[num] + kN - lg[den]] : 0u;
+        y = (num && den) ? exl[lg[num] + kN - lg[den] + (TW ? (twist * p) % kN : 0u)] : 0u;
       }
       // (an atomic XOR on the surrounding dword instead of the load / store pair was measured slower: 942 vs 1024 M)
       if (has && y && !(xf & 33)) out[frame * n + p] = static_cast<uint8_t>(sym ^ y);
@@ -1192,21 +1204,17 @@ static int launch_chunk_fpw(const cc_code *code, bool float_in, const void *d_in
   const unsigned long long Bq = B;
   const int alg_arg = code->desc.algorithm | (alg_stop_stage() << 8);
   hipError_t e = hipSuccess;
-  if (float_in) {
+  auto launch = [&](auto kernel) {
     if (lds > 48 * 1024)
-      e = hipFuncSetAttribute(reinterpret_cast<const void *>(&algebraic_chunk_kernel<true, FPW>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+      e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              static_cast<int>(lds));
     if (e == hipSuccess)
-      hipLaunchKernelGGL((algebraic_chunk_kernel<true, FPW>), dim3(grid), dim3(256), lds, stream, code->d_alg,
-                         alg_arg, d_in, d_out, d_nerr, d_status, Bq);
-  } else {
-    if (lds > 48 * 1024)
-      e = hipFuncSetAttribute(reinterpret_cast<const void *>(&algebraic_chunk_kernel<false, FPW>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (e == hipSuccess)
-      hipLaunchKernelGGL((algebraic_chunk_kernel<false, FPW>), dim3(grid), dim3(256), lds, stream, code->d_alg,
-                         alg_arg, d_in, d_out, d_nerr, d_status, Bq);
-  }
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, stream, code->d_alg, alg_arg, d_in, d_out, d_nerr, d_status, Bq);
+  };
+  if (rs_twisted(code))
+    float_in ? launch(&algebraic_chunk_kernel<true, FPW, true>) : launch(&algebraic_chunk_kernel<false, FPW, true>);
+  else
+    float_in ? launch(&algebraic_chunk_kernel<true, FPW, false>) : launch(&algebraic_chunk_kernel<false, FPW, false>);
   if (e == hipSuccess) e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "algebraic chunk kernel launch");
   return CC_OK;
@@ -1264,6 +1272,7 @@ static int launch_chunk_bitsliced(const cc_code *code, bool float_in, const void
   // planes, the long instantiations of the root search and of the corrector; without erasures a correctable locator
   // has degree <= t <= 16
   const bool long_loc = d_er_off != nullptr && t2 > 16;
+  const bool tw = rs_twisted(code);  // (on this chain: mu = 0, step = 1 -- bitslice_supported)
   const int ncoef = long_loc ? 25 : 17;
   const size_t lamp_bytes = G64 * ncoef * 32, roots_bytes = G64 * 256 * 4, left_bytes = mask_bytes;
   uint8_t *ws = nullptr;  // stream-ordered and pool-cached: no device-wide synchronisation, no allocation after the first call
@@ -1292,34 +1301,36 @@ static int launch_chunk_bitsliced(const cc_code *code, bool float_in, const void
       if (four) {  // one lane per frame; what it cannot settle goes on through d_left
         rc = launch_bitslice_roots_transpose(d_roots, d_rootsT, B, stream);
         if (rc == CC_OK) {
-          static const int fixl_per_cu[2] = {[] {  // resident workgroups per CU: registers and LDS of the built kernels
-                                               int v = 0;
-                                               if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, chunk_fixl_kernel<16>, 256, 0) != hipSuccess || v < 1) v = 3;
-                                               return v;
-                                             }(),
-                                             [] {
-                                               int v = 0;
-                                               if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, chunk_fixl_kernel<24>, 256, 0) != hipSuccess || v < 1) v = 2;
-                                               return v;
-                                             }()};
-          const unsigned long long lcap = static_cast<unsigned long long>(code->num_cus) * fixl_per_cu[long_loc];
+          // resident workgroups per CU: registers and LDS of the built kernels ([twisted roots][long locators])
+          auto per_cu = [](auto kernel, int fallback) {
+            int v = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kernel, 256, 0) != hipSuccess || v < 1) v = fallback;
+            return v;
+          };
+          static const int fixl_per_cu[2][2] = {
+              {per_cu(chunk_fixl_kernel<16, false>, 3), per_cu(chunk_fixl_kernel<24, false>, 2)},
+              {per_cu(chunk_fixl_kernel<16, true>, 3), per_cu(chunk_fixl_kernel<24, true>, 2)}};
+          const unsigned long long lcap = static_cast<unsigned long long>(code->num_cus) * fixl_per_cu[tw][long_loc];
           const int lgrid = static_cast<int>(blocks_needed < lcap ? blocks_needed : lcap);
-          if (long_loc)
-            hipLaunchKernelGGL(chunk_fixl_kernel<24>, dim3(lgrid), dim3(256), 0, stream, code->d_alg,
-                               code->desc.algorithm | fixl_exp(), d_synd, d_llg, d_meta, d_mask,
-                               reinterpret_cast<const uint32_t *>(d_rootsT), d_left, d_nleft, d_er_off, d_out, d_nerr, d_status, Bq);
+          auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(lgrid), dim3(256), 0, stream, code->d_alg, code->desc.algorithm | fixl_exp(), d_synd,
+                               d_llg, d_meta, d_mask, reinterpret_cast<const uint32_t *>(d_rootsT), d_left, d_nleft, d_er_off,
+                               d_out, d_nerr, d_status, Bq);
+          };
+          if (tw)
+            long_loc ? launch(chunk_fixl_kernel<24, true>) : launch(chunk_fixl_kernel<16, true>);
           else
-            hipLaunchKernelGGL(chunk_fixl_kernel<16>, dim3(lgrid), dim3(256), 0, stream, code->d_alg,
-                               code->desc.algorithm | fixl_exp(), d_synd, d_llg, d_meta, d_mask,
-                               reinterpret_cast<const uint32_t *>(d_rootsT), d_left, d_nleft, d_er_off, d_out, d_nerr, d_status, Bq);
+            long_loc ? launch(chunk_fixl_kernel<24, false>) : launch(chunk_fixl_kernel<16, false>);
           e = hipGetLastError();
         }
       }
       if (rc == CC_OK && e == hipSuccess) {
-        hipLaunchKernelGGL(chunk_fix_kernel, dim3(grid), dim3(256), 0, stream, code->d_alg,
-                           code->desc.algorithm | (dbg_stop << 8), d_synd, d_llg, d_meta, four ? d_left : d_mask,
-                           reinterpret_cast<const uint32_t *>(d_roots), four ? d_nleft : nullptr, d_er_off, long_loc ? 24 : 16,
-                           d_out, d_nerr, d_status, Bq);
+        auto launch = [&](auto kernel) {
+          hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, code->d_alg, code->desc.algorithm | (dbg_stop << 8),
+                             d_synd, d_llg, d_meta, four ? d_left : d_mask, reinterpret_cast<const uint32_t *>(d_roots),
+                             four ? d_nleft : nullptr, d_er_off, long_loc ? 24 : 16, d_out, d_nerr, d_status, Bq);
+        };
+        tw ? launch(chunk_fix_kernel<true>) : launch(chunk_fix_kernel<false>);
         e = hipGetLastError();
       }
     }

@@ -48,7 +48,7 @@ __device__ __forceinline__ void poly_shift_up(uint32_t (&v)[4], int lane) {
   }
 }
 
-template <bool FLOAT_IN>
+template <bool FLOAT_IN, bool TW>  // TW: RS roots other than alpha^1 .. alpha^2t, see algebraic_kernel
 __global__ void __launch_bounds__(256)
 algebraic_long_kernel(const AlgebraicTables *__restrict__ T, int alg, const void *__restrict__ in_raw,
                       const uint16_t *__restrict__ er, const uint32_t *__restrict__ er_off, uint8_t *__restrict__ out,
@@ -82,7 +82,10 @@ algebraic_long_kernel(const AlgebraicTables *__restrict__ T, int alg, const void
     e0[c] = static_cast<uint32_t>((r0 * p) % nn);
     dstep[c] = static_cast<uint32_t>((step * p) % nn);
     xinv[c] = static_cast<uint32_t>((nn - (p % nn)) % nn);  // log of X^-1 for X = alpha^p
+    if (TW) xinv[c] = (static_cast<uint32_t>(nn) - dstep[c]) % static_cast<uint32_t>(nn);  // log of Z^-1, Z = alpha^(step p)
   }
+  const int twist = TW ? T->twist : 0;
+  auto zlog = [&](uint32_t p) -> uint32_t { return (static_cast<uint32_t>(step) * (p % nn)) % nn; };
 
   for (unsigned long long frame = wave; frame < B; frame += nwaves) {
     uint32_t sym[4];
@@ -136,7 +139,7 @@ algebraic_long_kernel(const AlgebraicTables *__restrict__ T, int alg, const void
       // ---- Berlekamp-Massey, hard_decision.h:116-155; coefficient lane + 64 c of lambda / b in register c ----
       uint32_t lam[4] = {lane == 0 ? 1u : 0u, 0u, 0u, 0u};
       for (uint32_t e = 0; e < nerase; ++e) {  // lambda *= (1 + alpha^erasure x), :128-131
-        const uint32_t X = ex[er[ebase + e] % nn];
+        const uint32_t X = ex[TW ? zlog(er[ebase + e]) : er[ebase + e] % nn];
         uint32_t sh[4] = {lam[0], lam[1], lam[2], lam[3]};
         poly_shift_up(sh, lane);
 #pragma unroll
@@ -227,14 +230,15 @@ algebraic_long_kernel(const AlgebraicTables *__restrict__ T, int alg, const void
           const int eidx = lane + 64 * c;
           uint32_t y = 0;
           if (eidx < deg) {
-            const uint32_t p = W.rp[eidx];
-            const uint32_t xi = p ? static_cast<uint32_t>(nn) - p : 0u;
+            const uint32_t p = W.rp[eidx], zl = TW ? zlog(p) : p;
+            const uint32_t xi = zl ? static_cast<uint32_t>(nn) - zl : 0u;
             const uint32_t x2 = (2 * xi) % static_cast<uint32_t>(nn);
             uint32_t num = 0, den = 0;
             for (int j = deg - 1; j >= 0; --j) num = gmul_pow(num, xi) ^ W.om[j];
             const int mtop = (deg & 1) ? deg : deg - 1;
             for (int m = mtop; m >= 1; m -= 2) den = gmul_pow(den, x2) ^ W.lam[m];
             y = (num && den) ? ex[lg[num] + nn - lg[den]] : 0u;
+            if (TW) y = gmul_pow(y, (static_cast<uint32_t>(twist) * p) % nn);
           }
           W.val[eidx] = static_cast<uint8_t>(y);
         }
@@ -307,12 +311,14 @@ int launch_algebraic_long(const cc_code *code, bool float_in, const void *d_in, 
   const unsigned long long max_grid = static_cast<unsigned long long>(code->num_cus) * 16;
   const int grid = static_cast<int>(blocks_needed < max_grid ? blocks_needed : max_grid);
   const unsigned long long Bq = B;
-  if (float_in)
-    hipLaunchKernelGGL(algebraic_long_kernel<true>, dim3(grid), dim3(256), 0, stream, code->d_alg, code->desc.algorithm,
-                       d_in, d_er, d_er_off, d_out, d_nerr, d_status, Bq);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, code->d_alg, code->desc.algorithm, d_in, d_er, d_er_off,
+                       d_out, d_nerr, d_status, Bq);
+  };
+  if (rs_twisted(code))
+    float_in ? launch(algebraic_long_kernel<true, true>) : launch(algebraic_long_kernel<false, true>);
   else
-    hipLaunchKernelGGL(algebraic_long_kernel<false>, dim3(grid), dim3(256), 0, stream, code->d_alg, code->desc.algorithm,
-                       d_in, d_er, d_er_off, d_out, d_nerr, d_status, Bq);
+    float_in ? launch(algebraic_long_kernel<true, false>) : launch(algebraic_long_kernel<false, false>);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "algebraic long kernel launch");
   return CC_OK;

@@ -18,7 +18,8 @@
 // ((gb 2t + j) 64 + gl) 32 + 4k + i.
 //
 // Field: GF(2^8) with the default modular polynomial 0x11d (galois.h:18-20), consecutive roots alpha^1 .. alpha^2t
-// (mu = step = 1), n = 255.  Everything else stays on the table kernels.
+// (mu = step = 1) or, for RS codes, alpha^0 .. alpha^(2t-1) (mu = 0, step = 1: the first tap is a template parameter,
+// times alpha^0 is the identity network), n <= 255.  Everything else stays on the table kernels.
 #include <cstdlib>
 #include <utility>
 
@@ -44,9 +45,10 @@ using namespace bitplane;
 constexpr int kFusedGroups = 8, kFusedThreads = 512;
 constexpr size_t kFusedLdsBytes = 32 * 2 * 64 * sizeof(uint4);  // 64 KB: two workgroups per CU, four wavefronts per SIMD
 
-// syndromes J0+1 .. J0+4 of the workgroup's groups: lane = (group lane >> 3, segment lane & 7)
+// syndromes number J0 .. J0+3 of the workgroup's groups, the evaluations at alpha^(MU + J0) .. alpha^(MU + J0 + 3):
+// lane = (group lane >> 3, segment lane & 7)
 // RAW keeps the result on planes ([block][j][group][8]) for the encoder's interpolation
-template <int J0, bool RAW>
+template <int J0, bool RAW, int MU>
 __device__ __forceinline__ void fused_syndromes4(const uint4 *__restrict__ lds, uint8_t *__restrict__ synd,
                                                  unsigned long long group0, unsigned long long G, int t2) {
   const int lane = threadIdx.x & 63, g = lane >> 3, seg = lane & 7;
@@ -56,10 +58,10 @@ __device__ __forceinline__ void fused_syndromes4(const uint4 *__restrict__ lds, 
 #pragma unroll
     for (int b = 0; b < 8; ++b) s[j][b] = 0;
   auto all4 = [&](const uint32_t (&r)[8]) {
-    horner<J0 + 1>(s[0], r);
-    horner<J0 + 2>(s[1], r);
-    horner<J0 + 3>(s[2], r);
-    horner<J0 + 4>(s[3], r);
+    horner<J0 + MU>(s[0], r);
+    horner<J0 + MU + 1>(s[1], r);
+    horner<J0 + MU + 2>(s[2], r);
+    horner<J0 + MU + 3>(s[3], r);
   };
   // two positions per trip (the in-place update needs no register copies); i >> 2 is the same for both
   for (int i = 31; i >= 1; i -= 2) {
@@ -71,10 +73,10 @@ __device__ __forceinline__ void fused_syndromes4(const uint4 *__restrict__ lds, 
     all4(r0);
     all4(r1);
   }
-  fold_all<J0 + 1>(s[0]);
-  fold_all<J0 + 2>(s[1]);
-  fold_all<J0 + 3>(s[2]);
-  fold_all<J0 + 4>(s[3]);
+  fold_all<J0 + MU>(s[0]);
+  fold_all<J0 + MU + 1>(s[1]);
+  fold_all<J0 + MU + 2>(s[2]);
+  fold_all<J0 + MU + 3>(s[3]);
   const unsigned long long gg = group0 + g;
   if (seg != 0 || gg >= G) return;
 #pragma unroll
@@ -90,7 +92,7 @@ __device__ __forceinline__ void fused_syndromes4(const uint4 *__restrict__ lds, 
 // decoding: n_in = n, off = 0.  Encoding (RAW): the n_in message symbols of a frame go to the positions off .. n - 1 of
 // its codeword (cyclic.h:29-40) -- in `out` and on the planes, whose positions below off stay zero -- and the result is
 // (a x^k)(alpha^j) on planes for bitslice_parity_kernel.
-template <bool FLOAT_IN, bool RAW>
+template <bool FLOAT_IN, bool RAW, int MU>
 __global__ void __launch_bounds__(kFusedThreads, 4)
 bitslice_fused_syndrome_kernel(const void *in_raw, uint8_t *out, uint8_t *__restrict__ synd, unsigned long long B,
                                unsigned long long G, int n, int t2, int n_in, int off) {
@@ -169,20 +171,20 @@ bitslice_fused_syndrome_kernel(const void *in_raw, uint8_t *out, uint8_t *__rest
   __syncthreads();
   if (4 * wid >= t2 || (xs & 2)) return;
   switch (wid) {
-    case 0: fused_syndromes4<0, RAW>(lds, synd, group0, G, t2); break;
-    case 1: fused_syndromes4<4, RAW>(lds, synd, group0, G, t2); break;
-    case 2: fused_syndromes4<8, RAW>(lds, synd, group0, G, t2); break;
-    case 3: fused_syndromes4<12, RAW>(lds, synd, group0, G, t2); break;
-    case 4: fused_syndromes4<16, RAW>(lds, synd, group0, G, t2); break;
-    case 5: fused_syndromes4<20, RAW>(lds, synd, group0, G, t2); break;
-    case 6: fused_syndromes4<24, RAW>(lds, synd, group0, G, t2); break;
-    default: fused_syndromes4<28, RAW>(lds, synd, group0, G, t2); break;
+    case 0: fused_syndromes4<0, RAW, MU>(lds, synd, group0, G, t2); break;
+    case 1: fused_syndromes4<4, RAW, MU>(lds, synd, group0, G, t2); break;
+    case 2: fused_syndromes4<8, RAW, MU>(lds, synd, group0, G, t2); break;
+    case 3: fused_syndromes4<12, RAW, MU>(lds, synd, group0, G, t2); break;
+    case 4: fused_syndromes4<16, RAW, MU>(lds, synd, group0, G, t2); break;
+    case 5: fused_syndromes4<20, RAW, MU>(lds, synd, group0, G, t2); break;
+    case 6: fused_syndromes4<24, RAW, MU>(lds, synd, group0, G, t2); break;
+    default: fused_syndromes4<28, RAW, MU>(lds, synd, group0, G, t2); break;
   }
 }
 
 // ---------------- systematic encoding by evaluation and interpolation ----------------
-// c(x) = a(x) x^k + r(x), deg r < k = 2t, and c(alpha^j) = 0 for j = 1 .. 2t: with E_j = (a x^k)(alpha^j) from the
-// Horner kernel above, r is the polynomial with r(alpha^j) = E_j, i.e. r_i = sum_j W[i][j] E_j with W the inverse of
+// c(x) = a(x) x^k + r(x), deg r < k = 2t, and c(alpha^j) = 0 for j = MU .. MU + 2t - 1: with E_j = (a x^k)(alpha^j) from
+// the Horner kernel above, r is the polynomial with r(alpha^j) = E_j, i.e. r_i = sum_j W[i][j] E_j with W the inverse of
 // the Vandermonde matrix V[j][i] = alpha^(j i) -- k^2 multiplications by constants per frame instead of k (n - k),
 // and constants are XOR networks on the planes.  Same codeword as the division (the remainder is unique).
 struct Gf256 {
@@ -199,14 +201,14 @@ struct Gf256 {
   constexpr uint8_t mul(uint8_t a, uint8_t b) const { return (a && b) ? exp[log[a] + log[b]] : 0; }
   constexpr uint8_t inv(uint8_t a) const { return exp[255 - log[a]]; }
 };
-template <int K> struct InverseVandermonde {
+template <int K, int MU> struct InverseVandermonde {
   uint8_t w[K][K];
   constexpr InverseVandermonde() : w{} {
     Gf256 f;
     uint8_t v[K][K] = {};
     for (int j = 0; j < K; ++j)
       for (int i = 0; i < K; ++i) {
-        v[j][i] = f.exp[((j + 1) * i) % 255];
+        v[j][i] = f.exp[((j + MU) * i) % 255];
         w[j][i] = i == j;
       }
     for (int c = 0; c < K; ++c) {  // Gauss-Jordan (V is invertible: distinct evaluation points)
@@ -235,7 +237,7 @@ template <int K> struct InverseVandermonde {
     }
   }
 };
-template <int K> inline constexpr InverseVandermonde<K> kInvV{};
+template <int K, int MU> inline constexpr InverseVandermonde<K, MU> kInvV{};
 
 constexpr uint32_t times_const(uint32_t c, uint32_t v) {  // c * v in GF(2^8)
   uint32_t r = 0;
@@ -253,15 +255,15 @@ template <int C> __device__ __forceinline__ void mac(uint32_t (&acc)[8], const u
     for (int c = 0; c < 8; ++c)
       if ((times_const(C, 1u << c) >> b) & 1u) acc[b] ^= e[c];
 }
-template <int K, int I0, int J, int... I>
+template <int K, int MU, int I0, int J, int... I>
 __device__ __forceinline__ void interp_column(uint32_t (&acc)[8][8], const uint32_t (&e)[8], std::integer_sequence<int, I...>) {
-  (mac<kInvV<K>.w[I0 + I][J]>(acc[I], e), ...);
+  (mac<kInvV<K, MU>.w[I0 + I][J]>(acc[I], e), ...);
 }
-template <int K, int I0, int J>
+template <int K, int MU, int I0, int J>
 __device__ __forceinline__ void interp_one(uint32_t (&acc)[8][8], const uint4 *__restrict__ ev) {
   const uint4 a = ev[static_cast<unsigned long long>(J) * 128], b = ev[static_cast<unsigned long long>(J) * 128 + 1];
   const uint32_t e[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  interp_column<K, I0, J>(acc, e, std::make_integer_sequence<int, 8>());
+  interp_column<K, MU, I0, J>(acc, e, std::make_integer_sequence<int, 8>());
   if (J % 4 == 3) {  // cut the XOR expressions here: reassociation across all K evaluations would keep every one of them live
 #pragma unroll
     for (int i = 0; i < 8; ++i)
@@ -269,12 +271,12 @@ __device__ __forceinline__ void interp_one(uint32_t (&acc)[8][8], const uint4 *_
       for (int b = 0; b < 8; ++b) asm volatile("" : "+v"(acc[i][b]));
   }
 }
-template <int K, int I0, int... J>
+template <int K, int MU, int I0, int... J>
 __device__ __forceinline__ void interp_all(uint32_t (&acc)[8][8], const uint4 *__restrict__ ev, std::integer_sequence<int, J...>) {
-  (interp_one<K, I0, J>(acc, ev), ...);
+  (interp_one<K, MU, I0, J>(acc, ev), ...);
 }
 // parity symbols I0 .. I0+7 of the 32 frames of group g -> cw[frame][I0 .. I0+7]
-template <int K, int I0>
+template <int K, int MU, int I0>
 __device__ __forceinline__ void parity8(const uint4 *__restrict__ evals, uint8_t *__restrict__ cw, unsigned long long g,
                                         unsigned long long B, int n) {
   uint32_t acc[8][8];
@@ -282,7 +284,7 @@ __device__ __forceinline__ void parity8(const uint4 *__restrict__ evals, uint8_t
   for (int i = 0; i < 8; ++i)
 #pragma unroll
     for (int b = 0; b < 8; ++b) acc[i][b] = 0;
-  interp_all<K, I0>(acc, evals + ((g >> 6) * K * 64 + (g & 63)) * 2, std::make_integer_sequence<int, K>());
+  interp_all<K, MU, I0>(acc, evals + ((g >> 6) * K * 64 + (g & 63)) * 2, std::make_integer_sequence<int, K>());
 #pragma unroll
   for (int i = 0; i < 8; ++i) butterfly(acc[i]);  // word k of symbol i = its bytes for the frames {k, 8+k, 16+k, 24+k}
 #pragma unroll
@@ -302,7 +304,7 @@ __device__ __forceinline__ void parity8(const uint4 *__restrict__ evals, uint8_t
       __builtin_memcpy(cw + frame * static_cast<unsigned long long>(n) + I0, w, 8);
     }
 }
-template <int K>
+template <int K, int MU>
 __global__ void __launch_bounds__(256)
 bitslice_parity_kernel(const uint4 *__restrict__ evals, uint8_t *__restrict__ cw, unsigned long long B, unsigned long long G,
                        int n) {
@@ -311,14 +313,14 @@ bitslice_parity_kernel(const uint4 *__restrict__ evals, uint8_t *__restrict__ cw
   if (g >= G) return;
   if constexpr (K == 32) {
     switch (wid) {
-      case 0: parity8<K, 0>(evals, cw, g, B, n); break;
-      case 1: parity8<K, 8>(evals, cw, g, B, n); break;
-      case 2: parity8<K, 16>(evals, cw, g, B, n); break;
-      default: parity8<K, 24>(evals, cw, g, B, n); break;
+      case 0: parity8<K, MU, 0>(evals, cw, g, B, n); break;
+      case 1: parity8<K, MU, 8>(evals, cw, g, B, n); break;
+      case 2: parity8<K, MU, 16>(evals, cw, g, B, n); break;
+      default: parity8<K, MU, 24>(evals, cw, g, B, n); break;
     }
   } else {
-    if (wid == 0) parity8<K, 0>(evals, cw, g, B, n);
-    else parity8<K, 8>(evals, cw, g, B, n);
+    if (wid == 0) parity8<K, MU, 0>(evals, cw, g, B, n);
+    else parity8<K, MU, 8>(evals, cw, g, B, n);
   }
 }
 
@@ -494,8 +496,12 @@ bool bitslice_supported(const cc_code *code) {
   constexpr size_t min_t2 = 2;
 #endif
   if (t2 < min_t2 || t2 > 32 || t.root_powers.size() != t2) return false;
+  // consecutive roots from alpha^1, or -- RS only -- from alpha^0 (the <MU = 0> instantiations); any other (mu, step)
+  // runs on the table kernels
+  const unsigned mu = t.root_powers[0];
+  if (mu != 1 && !(mu == 0 && t.family == CC_FAMILY_RS)) return false;
   for (size_t j = 0; j < t2; ++j)
-    if (t.root_powers[j] != j + 1) return false;
+    if (t.root_powers[j] != j + mu) return false;
   return true;
 }
 
@@ -510,19 +516,17 @@ int launch_bitslice_syndromes(const cc_code *code, bool float_in, const void *d_
   const unsigned long long G = (B + 31) / 32, Bq = B;
   const unsigned grid = static_cast<unsigned>((G + kFusedGroups - 1) / kFusedGroups);
   hipError_t e = hipSuccess;
-  if (float_in) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&bitslice_fused_syndrome_kernel<true, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kFusedLdsBytes));
+  auto launch = [&](auto kernel) {
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            static_cast<int>(kFusedLdsBytes));
     if (e == hipSuccess)
-      hipLaunchKernelGGL((bitslice_fused_syndrome_kernel<true, false>), dim3(grid), dim3(kFusedThreads), kFusedLdsBytes, stream,
-                         d_in, d_out, d_synd, Bq, G, n, t2, n & 0xFFFF, 0);
-  } else {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&bitslice_fused_syndrome_kernel<false, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kFusedLdsBytes));
-    if (e == hipSuccess)
-      hipLaunchKernelGGL((bitslice_fused_syndrome_kernel<false, false>), dim3(grid), dim3(kFusedThreads), kFusedLdsBytes, stream,
-                         d_in, d_out, d_synd, Bq, G, n, t2, n & 0xFFFF, 0);
-  }
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(kFusedThreads), kFusedLdsBytes, stream, d_in, d_out, d_synd, Bq, G, n, t2,
+                         n & 0xFFFF, 0);
+  };
+  if (code->tab.root_powers[0] == 0)  // first root alpha^0
+    float_in ? launch(&bitslice_fused_syndrome_kernel<true, false, 0>) : launch(&bitslice_fused_syndrome_kernel<false, false, 0>);
+  else
+    float_in ? launch(&bitslice_fused_syndrome_kernel<true, false, 1>) : launch(&bitslice_fused_syndrome_kernel<false, false, 1>);
   if (e == hipSuccess) e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "bitslice fused syndrome kernel launch");
   return CC_OK;
@@ -568,20 +572,27 @@ int launch_bitslice_encode(const cc_code *code, const uint8_t *d_msg, uint8_t *d
   uint8_t *d_eval = nullptr;  // stream-ordered and pool-cached
   CC_HIP_TRY(workspace_alloc(code, reinterpret_cast<void **>(&d_eval), eval_bytes, stream));
   // message -> codeword body and planes in LDS -> evaluations at the 2t roots (the fused kernel of the decoder, RAW)
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&bitslice_fused_syndrome_kernel<false, true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kFusedLdsBytes));
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL((bitslice_fused_syndrome_kernel<false, true>), dim3(static_cast<unsigned>((G + kFusedGroups - 1) / kFusedGroups)),
-                       dim3(kFusedThreads), kFusedLdsBytes, stream, static_cast<const void *>(d_msg), d_cw, d_eval, Bq, G, n, k, l, k);
-    e = hipGetLastError();
-  }
+  const bool mu0 = code->tab.root_powers[0] == 0;  // first root alpha^0
+  hipError_t e = hipSuccess;
+  auto evaluate = [&](auto kernel) {
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            static_cast<int>(kFusedLdsBytes));
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>((G + kFusedGroups - 1) / kFusedGroups)), dim3(kFusedThreads),
+                         kFusedLdsBytes, stream, static_cast<const void *>(d_msg), d_cw, d_eval, Bq, G, n, k, l, k);
+      e = hipGetLastError();
+    }
+  };
+  mu0 ? evaluate(&bitslice_fused_syndrome_kernel<false, true, 0>) : evaluate(&bitslice_fused_syndrome_kernel<false, true, 1>);
   if (e == hipSuccess) {  // interpolation of the remainder
+    auto interpolate = [&](auto kernel, int threads) {
+      hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>((G + 63) / 64)), dim3(threads), 0, stream,
+                         reinterpret_cast<const uint4 *>(d_eval), d_cw, Bq, G, n);
+    };
     if (k == 32)
-      hipLaunchKernelGGL((bitslice_parity_kernel<32>), dim3(static_cast<unsigned>((G + 63) / 64)), dim3(256), 0, stream,
-                         reinterpret_cast<const uint4 *>(d_eval), d_cw, Bq, G, n);
+      mu0 ? interpolate(bitslice_parity_kernel<32, 0>, 256) : interpolate(bitslice_parity_kernel<32, 1>, 256);
     else
-      hipLaunchKernelGGL((bitslice_parity_kernel<16>), dim3(static_cast<unsigned>((G + 63) / 64)), dim3(128), 0, stream,
-                         reinterpret_cast<const uint4 *>(d_eval), d_cw, Bq, G, n);
+      mu0 ? interpolate(bitslice_parity_kernel<16, 0>, 128) : interpolate(bitslice_parity_kernel<16, 1>, 128);
     e = hipGetLastError();
   }
   (void)hipFreeAsync(d_eval, stream);

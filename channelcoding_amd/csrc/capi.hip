@@ -359,6 +359,24 @@ void cc_desc_init(cc_desc *d) {
   d->device = -1;
 }
 
+// RS roots alpha^(mu + i step), i < 2t, that the hard decoders serve: step coprime to 2^q - 1, so that
+// Z = alpha^(step p) names the position p, and no exponent beyond 2^q - 2 -- the reference's from_power reduces modulo
+// 2^q, not 2^q - 1, and past that point the root set is no arithmetic progression any more
+static bool rs_roots_in_scope(unsigned q, unsigned t, unsigned mu, unsigned step) {
+  const unsigned long long nf = (1ull << q) - 1;
+  unsigned long long a = step, b = nf;
+  while (b) {
+    const unsigned long long r = a % b;
+    a = b;
+    b = r;
+  }
+  if (a != 1) return false;  // (step = 0 included)
+  return mu + (2ull * t - 1) * step <= nf - 1;
+}
+static const char kRsRootsRefused[] =
+    "RS hard decoding serves roots alpha^(mu + i step) with gcd(step, 2^q - 1) = 1 and mu + (2t - 1) step <= 2^q - 2; "
+    "a step that shares a factor with 2^q - 1 and exponents that wrap are not supported";
+
 static int code_create_impl(const cc_desc *desc, const uint8_t *customH, uint32_t custom_rows, uint32_t custom_cols,
                             cc_code **out) {
   if (!desc || !out || desc->struct_size != sizeof(cc_desc)) return CC_ERR_INVALID_ARGUMENT;
@@ -386,8 +404,8 @@ static int code_create_impl(const cc_desc *desc, const uint8_t *customH, uint32_
       set_last_error("hard algorithms: one lane per syndrome, t <= 32");
       return CC_ERR_UNSUPPORTED;
     }
-    if (desc->family == CC_FAMILY_RS && (desc->mu != 1 || desc->step != 1)) {
-      set_last_error("RS hard decoding with mu / step != 1 is not supported");
+    if (desc->family == CC_FAMILY_RS && !rs_roots_in_scope(desc->q, desc->t, desc->mu, desc->step)) {
+      set_last_error(kRsRootsRefused);
       return CC_ERR_UNSUPPORTED;
     }
   }
@@ -620,6 +638,12 @@ static int code_create_impl(const cc_desc *desc, const uint8_t *customH, uint32_
   a.family = t.family;
   a.q = static_cast<int>(t.q);
   a.nf = static_cast<int>(code->field->n);  // a.n < a.nf: a shortened code
+  a.step = 1;
+  a.twist = 0;
+  if (t.family == CC_FAMILY_RS && rs_roots_in_scope(desc->q, desc->t, desc->mu, desc->step)) {
+    a.step = static_cast<int>(desc->step);
+    a.twist = static_cast<int>((desc->step + a.nf - desc->mu % a.nf) % a.nf);
+  }
   CC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&code->d_alg), sizeof a));
   CC_HIP_TRY(hipMemcpy(code->d_alg, &a, sizeof a, hipMemcpyHostToDevice));
   if (desc->coding == CC_CODING_DIVISION) {  // (shortened: k x (N - k), the first columns of the full code's table)
@@ -833,17 +857,20 @@ int cc_correct_soft_batch(const cc_code *code, const float *llr, const uint16_t 
 
 /* ------------------------------ hard decode ------------------------------ */
 
+static int wide_hard_supported(const cc_code *code, bool erasures);
+
 static int hard_supported(const cc_code *code, bool erasures) {
   if (int rc = not_wide(code)) return rc;
   if (code->soft) {
     set_last_error("code was created with a min-sum algorithm; use cc_correct_soft_batch");
     return CC_ERR_INVALID_ARGUMENT;
   }
-  if (code->device == CC_DEVICE_NONE) return CC_ERR_NO_DEVICE;
   // more than 64 syndromes, the Euklid tag with 2t > 63 and erasure decoding with 2t > 32 (Euklid) run
   // algebraic_long.hip (four locator coefficients per lane) -- launch_algebraic routes them
-  if (code->tab.family == CC_FAMILY_RS && (code->desc.mu != 1 || code->desc.step != 1)) {
-    set_last_error("RS error values on the device assume roots alpha^1..alpha^2t (mu = step = 1), as rs.h:55-69 does");
+  // (what the decoders refuse is a property of the code and the call: answered before a device is asked for, so that a
+  //  CC_DEVICE_NONE handle tells "refused" from "would run")
+  if (code->tab.family == CC_FAMILY_RS && !rs_roots_in_scope(code->desc.q, code->desc.t, code->desc.mu, code->desc.step)) {
+    set_last_error(kRsRootsRefused);
     return CC_ERR_UNSUPPORTED;
   }
   if (erasures && code->desc.algorithm == CC_ALG_PGZ && code->tab.family == CC_FAMILY_RS) {
@@ -852,6 +879,7 @@ static int hard_supported(const cc_code *code, bool erasures) {
     set_last_error("The PGZ-Algorithm does not support erasure decoding");
     return CC_ERR_UNSUPPORTED;
   }
+  if (code->device == CC_DEVICE_NONE) return CC_ERR_NO_DEVICE;
   return CC_OK;
 }
 
@@ -868,6 +896,20 @@ int cc_correct_hard_batch_dev(const cc_code *code, const uint8_t *d_in, const ui
                                static_cast<hipStream_t>(stream));
   return launch_algebraic(code, false, d_in, d_erasures, d_erasure_offsets, d_out, d_nerr, d_status, B,
                           static_cast<hipStream_t>(stream));
+}
+
+int cc_hard_route(const cc_code *code, size_t B, int with_erasures) {
+  if (!code) return -CC_ERR_INVALID_ARGUMENT;
+  const bool erasures = with_erasures != 0;
+  if (code->wide) {
+    if (code->soft) return -CC_ERR_INVALID_ARGUMENT;
+    if (int rc = wide_hard_supported(code, erasures)) return -rc;  // (refusals before the device, as hard_supported)
+    if (code->device == CC_DEVICE_NONE) return -CC_ERR_NO_DEVICE;
+    return erasures && code->desc.algorithm == CC_ALG_PGZ ? CC_HARD_ROUTE_TRIALS : CC_HARD_ROUTE_WIDE;
+  }
+  if (int rc = hard_supported(code, erasures)) return -rc;
+  if (erasures && code->desc.algorithm == CC_ALG_PGZ) return CC_HARD_ROUTE_TRIALS;
+  return algebraic_route(code, B, erasures);
 }
 
 // bit = (x < 0) of a soft value (cyclic.h:163-184) as a byte: the Peterson-Gorenstein-Zierler erasure rule of
@@ -1109,6 +1151,13 @@ static int wide_ready(const cc_code *code) {
   return CC_OK;
 }
 
+// the hard-decode calls: what the decoders refuse is answered before a device is asked for, as hard_supported does
+static int wide_correct_ready(const cc_code *code, bool erasures) {
+  if (!code->wide) return wide_ready(code);
+  if (int rc = wide_hard_supported(code, erasures)) return rc;
+  return wide_ready(code);
+}
+
 int cc_encode_batch_u16_dev(const cc_code *code, const uint16_t *d_msg, uint16_t *d_cw, size_t B, void *stream) {
   if (!code || (B && (!d_msg || !d_cw))) return CC_ERR_INVALID_ARGUMENT;
   if (int rc = wide_ready(code)) return rc;
@@ -1128,8 +1177,7 @@ int cc_correct_hard_batch_u16_dev(const cc_code *code, const uint16_t *d_in, con
                                   int32_t *d_status, size_t B, void *stream) {
   if (!code || (B && (!d_in || !d_out))) return CC_ERR_INVALID_ARGUMENT;
   if ((d_erasures == nullptr) != (d_erasure_offsets == nullptr)) return CC_ERR_INVALID_ARGUMENT;
-  if (int rc = wide_ready(code)) return rc;
-  if (int rc = wide_hard_supported(code, d_erasures != nullptr)) return rc;
+  if (int rc = wide_correct_ready(code, d_erasures != nullptr)) return rc;
   DeviceGuard guard(code->device);
   return launch_wide_correct(code, d_in, d_erasures, d_erasure_offsets, d_out, d_nerr, d_status, B,
                              static_cast<hipStream_t>(stream));
@@ -1182,8 +1230,7 @@ int cc_correct_hard_batch_u16(const cc_code *code, const uint16_t *in, const uin
                               size_t B) {
   if (!code || (B && (!in || !out))) return CC_ERR_INVALID_ARGUMENT;
   if ((erasures == nullptr) != (erasure_offsets == nullptr)) return CC_ERR_INVALID_ARGUMENT;
-  if (int rc = wide_ready(code)) return rc;
-  if (int rc = wide_hard_supported(code, erasures != nullptr)) return rc;
+  if (int rc = wide_correct_ready(code, erasures != nullptr)) return rc;
   if (B == 0) return CC_OK;
   const size_t n = code->tab.n;
   for (size_t i = 0; i < B * n; ++i)
@@ -1487,7 +1534,7 @@ static int discrete_supported(const cc_code *code, double p_error, double p_eras
   if (int rc = not_wide(code)) return rc;
   if (code->device == CC_DEVICE_NONE) return CC_ERR_NO_DEVICE;
   if (code->tab.family == CC_FAMILY_RS && (code->desc.mu != 1 || code->desc.step != 1)) {
-    set_last_error("RS error values on the device assume roots alpha^1..alpha^2t (mu = step = 1), as rs.h:55-69 does");
+    set_last_error("the Monte-Carlo routes serve RS codes with roots alpha^1..alpha^2t (mu = step = 1) only");
     return CC_ERR_UNSUPPORTED;
   }
   if (p_erasure > 0.0 && code->desc.algorithm == CC_ALG_PGZ && code->tab.family == CC_FAMILY_RS) {

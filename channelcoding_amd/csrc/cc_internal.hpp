@@ -75,6 +75,9 @@ struct AlgebraicTables {
   int n, k, l, t, nroots, family, q;
   int nf;  // field order 2^q - 1: exponent arithmetic and the symbol mask.  n = frame length: nf, or N of a code
            // shortened to N symbols (positions N .. nf-1 are zero: the root search counts only roots below n)
+  // RS roots alpha^(mu + i step): the locator of position p is Z = alpha^(step p), and the error value is
+  // Forney's quotient times alpha^(twist p), twist = (step - mu) mod nf.  1 and 0 for mu = step = 1 and for BCH.
+  int step, twist;
 };
 
 // q = 9..15 (wide.hip): tables in global memory, passed to the kernels by value
@@ -85,6 +88,9 @@ struct WideTables {
   uint32_t n = 0, k = 0, l = 0, t = 0, nroots = 0, q = 0;
   uint32_t nf = 0;  // field order 2^q - 1; n = frame length (< nf: a shortened code, see AlgebraicTables)
   int family = 0;
+  // (RS roots alpha^(mu + i step): the struct travels by value, so the kernel takes step and twist off root_log --
+  //  mu = root_log[0], step = root_log[1] - root_log[0] for every code the decoder admits -- and the kernel arguments
+  //  of the mu = step = 1 instantiation stay where they were)
 };
 
 }  // namespace ccamd
@@ -135,6 +141,11 @@ struct cc_code {
 };
 
 namespace ccamd {
+
+// an RS code whose roots are not alpha^1 .. alpha^2t: the <TW = true> instantiations of the table kernels
+inline bool rs_twisted(const cc_code *code) {
+  return code->tab.family == CC_FAMILY_RS && (code->desc.mu != 1 || code->desc.step != 1);
+}
 
 inline hipError_t workspace_alloc(const cc_code *code, void **p, size_t bytes, hipStream_t stream) {
   return code->pool ? hipMallocFromPoolAsync(p, bytes, code->pool, stream) : hipMallocAsync(p, bytes, stream);
@@ -201,6 +212,7 @@ constexpr uint32_t kLogZero = 512;  // log of 0 in the locators the Berlekamp-Ma
 int launch_chunk_bm(const cc_code *code, const uint8_t *d_synd, const uint16_t *d_er, const uint32_t *d_er_off,
                     uint16_t *d_llg, uint16_t *d_meta, unsigned long long *d_mask, uint8_t *d_lamp, int ncoef,
                     uint32_t *d_nleft, int32_t *d_nerr, int32_t *d_status, size_t B, hipStream_t stream);
+int algebraic_route(const cc_code *code, size_t B, bool erasures);  // algebraic.hip: the CC_HARD_ROUTE_* launch_algebraic takes
 bool planes_small_call(const cc_code *code, size_t B);  // algebraic.hip: below CC_AMD_PLANES_MIN_WORK the chain is not taken
 int launch_pgz_erasures(const cc_code *code, const uint8_t *d_in, const uint16_t *d_er, const uint32_t *d_er_off,
                         uint8_t *d_out, int32_t *d_nerr, int32_t *d_status, size_t B, hipStream_t stream);

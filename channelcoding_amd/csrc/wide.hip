@@ -35,6 +35,10 @@ __device__ __forceinline__ uint32_t shift_up_w(uint32_t v) {
   return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x138 /* wave_shr:1 */, 0xF, 0xF, true));
 }
 
+// TW: an RS code with roots alpha^(mu + i step) other than alpha^1 .. alpha^2t (algebraic.hip): the locator
+// of position p is Z = alpha^(step p) -- roots tested at Z^-1, erasure pre-load with Z -- and Forney's quotient is scaled
+// by alpha^(twist p); TW = false is the code as it was
+template <bool TW>
 __global__ void __launch_bounds__(256)
 wide_correct_kernel(WideTables T, int alg, const uint16_t *__restrict__ in, const uint16_t *__restrict__ er,
                     const uint32_t *__restrict__ er_off, uint16_t *__restrict__ out, int32_t *__restrict__ nerr_out,
@@ -52,6 +56,9 @@ wide_correct_kernel(WideTables T, int alg, const uint16_t *__restrict__ in, cons
   auto gmul_pow = [&](uint32_t a, uint32_t e) -> uint32_t { return a ? ex[lg[a] + e] : 0u; };  // a alpha^e, e < nn
   const uint32_t r0 = T.root_log[0];
   const uint32_t step = t2 > 1 ? (T.root_log[1] + nn - r0) % nn : 0u;
+  const uint32_t twist = TW ? (step + nn - r0) % nn : 0u;  // (step - mu) mod nn: root_log[0] = mu, no exponent wraps
+  // log of the locator Z = alpha^(step p) of position p < nn
+  auto zlog = [&](uint32_t p) -> uint32_t { return static_cast<uint32_t>((static_cast<unsigned long long>(step) * p) % nn); };
 
   for (unsigned long long frame = wave; frame < B; frame += nwaves) {
     const uint16_t *src = in + frame * n;
@@ -99,7 +106,7 @@ wide_correct_kernel(WideTables T, int alg, const uint16_t *__restrict__ in, cons
       if (alg == CC_ALG_EUKLID) {
         // ---- Euklid / Sugiyama with erasures, hard_decision.h:157-196 (lane j <-> coefficient j) ----
         uint32_t u = (lane == 0) ? 1u : 0u;
-        for (uint32_t e = 0; e < nerase; ++e) u ^= gmul(ex[er[ebase + e] % nn], shift_up_w(u));
+        for (uint32_t e = 0; e < nerase; ++e) u ^= gmul(ex[TW ? zlog(er[ebase + e] % nn) : er[ebase + e] % nn], shift_up_w(u));
         uint32_t rp = 0;
         for (int m = 0; m <= rho; ++m) {
           const uint32_t um = __builtin_amdgcn_readlane(u, m);
@@ -134,7 +141,7 @@ wide_correct_kernel(WideTables T, int alg, const uint16_t *__restrict__ in, cons
       } else {
         // ---- Berlekamp-Massey, hard_decision.h:116-155 (lane j <-> coefficient j) ----
         lam = (lane == 0) ? 1u : 0u;
-        for (uint32_t e = 0; e < nerase; ++e) lam ^= gmul(ex[er[ebase + e] % nn], shift_up_w(lam));  // :128-131
+        for (uint32_t e = 0; e < nerase; ++e) lam ^= gmul(ex[TW ? zlog(er[ebase + e] % nn) : er[ebase + e] % nn], shift_up_w(lam));  // :128-131
         uint32_t bpoly = lam;
         int l = rho;
         for (int i = rho; i < static_cast<int>(t2); ++i) {
@@ -167,7 +174,8 @@ wide_correct_kernel(WideTables T, int alg, const uint16_t *__restrict__ in, cons
           const uint32_t p = base + lane;
           uint32_t acc = 0;
           if (p < n) {
-            const uint32_t xi = p ? nn - p : 0u;  // log of X^-1 for X = alpha^p
+            const uint32_t zl = TW ? zlog(p) : p;
+            const uint32_t xi = zl ? nn - zl : 0u;  // log of X^-1 for X = alpha^p
             acc = lead;
             for (int j = deg - 1; j >= 0; --j) acc = gmul_pow(acc, xi) ^ W.lam[j];
           }
@@ -195,14 +203,15 @@ wide_correct_kernel(WideTables T, int alg, const uint16_t *__restrict__ in, cons
         W.om[lane] = static_cast<uint16_t>(om);
         y = 0;
         if (lane < deg) {
-          const uint32_t p = W.rp[lane];
-          const uint32_t xi = p ? nn - p : 0u;
+          const uint32_t p = W.rp[lane], zl = TW ? zlog(p) : p;
+          const uint32_t xi = zl ? nn - zl : 0u;
           const uint32_t x2 = (2 * xi) % nn;
           uint32_t num = 0, den = 0;
           for (int j = deg - 1; j >= 0; --j) num = gmul_pow(num, xi) ^ W.om[j];
           const int mtop = (deg & 1) ? deg : deg - 1;
           for (int m = mtop; m >= 1; m -= 2) den = gmul_pow(den, x2) ^ W.lam[m];
           y = (num && den) ? ex[lg[num] + nn - lg[den]] : 0u;
+          if (TW) y = gmul_pow(y, static_cast<uint32_t>((static_cast<unsigned long long>(twist) * p) % nn));
         }
       }
       if (status == CC_FRAME_OK) W.val[lane] = static_cast<uint16_t>(lane < deg ? y : 0u);
@@ -289,9 +298,12 @@ int launch_wide_correct(const cc_code *code, const uint16_t *d_in, const uint16_
   if (d_off && code->desc.algorithm == CC_ALG_PGZ)  // BCH only (capi.hip refuses RS): the two-trial rule below
     return launch_wide_pgz_erasures(code, d_in, d_er, d_off, d_out, d_nerr, d_status, B, stream);
   const unsigned long long blocks = (B + 3) / 4, max_grid = static_cast<unsigned long long>(code->num_cus) * 8;
-  hipLaunchKernelGGL(wide_correct_kernel, dim3(static_cast<int>(blocks < max_grid ? blocks : max_grid)), dim3(256), 0,
-                     stream, code->wide_dev, code->desc.algorithm, d_in, d_er, d_off, d_out, d_nerr, d_status,
-                     static_cast<unsigned long long>(B));
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(static_cast<int>(blocks < max_grid ? blocks : max_grid)), dim3(256), 0, stream,
+                       code->wide_dev, code->desc.algorithm, d_in, d_er, d_off, d_out, d_nerr, d_status,
+                       static_cast<unsigned long long>(B));
+  };
+  rs_twisted(code) ? launch(wide_correct_kernel<true>) : launch(wide_correct_kernel<false>);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? CC_OK : hip_fail(e, "wide_correct_kernel launch");
 }

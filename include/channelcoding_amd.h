@@ -99,7 +99,12 @@ typedef struct cc_desc {
                          * g, h, roots, dmin are the full code's; H, H_alt its first n columns. *
                          * A locator root at a position >= n fails it (CC_FRAME_LOCATOR).     *
                          * Symbols are still checked against GF(2^q), not against n.           */
-  uint32_t mu, step;    /* RS only: roots alpha^(mu + i*step), rs.h:18-39; use 1, 1            */
+  uint32_t mu, step;    /* RS only: roots alpha^(mu + i*step), i < 2t, rs.h:18-39.  Encoding,   *
+                         * extraction and syndromes: any.  Hard decoding: step    *
+                         * coprime to 2^q-1 and mu + (2t-1)*step <= 2^q-2, e.g. 0, 1 (DVB, ATSC, *
+                         * 802.3) or 1, 1; refused: a step sharing a factor with 2^q-1, exponents*
+                         * that wrap (CCSDS 112, 11), PGZ with erasures, the Monte-Carlo calls     *
+                         * unless 1, 1.  GF(2^8) bit planes serve 0, 1 and 1, 1, tables the rest.  */
   int32_t coding;       /* cc_coding                                                           */
   int32_t algorithm;    /* cc_algorithm                                                        */
   uint32_t iterations;  /* min-sum only: the tag's Iterations                                  */
@@ -188,6 +193,17 @@ int cc_correct_hard_f32_batch(const cc_code *code, const float *in /* B*n */, co
 int cc_correct_hard_f32_batch_dev(const cc_code *code, const float *d_in, const uint16_t *d_erasures,
                                   const uint32_t *d_erasure_offsets, uint8_t *d_out, int32_t *d_nerr,
                                   int32_t *d_status, size_t B, void *stream);
+/* The kernels a hard-decode call of B frames (with_erasures != 0: with an erasure list) takes under the settings in
+ * force, or a negative cc_status where the call itself would be refused (the _u16 calls for a q > 8 handle). */
+enum {
+  CC_HARD_ROUTE_WAVE = 0,   /* one wavefront per frame, tables in LDS (small calls, few syndromes, Sugiyama) */
+  CC_HARD_ROUTE_CHUNK = 1,  /* table kernels, Berlekamp-Massey with one lane per frame                      */
+  CC_HARD_ROUTE_PLANES = 2, /* GF(2^8) bit-plane chain: roots alpha^1.. or, RS, alpha^0.. (mu = 0, step = 1) */
+  CC_HARD_ROUTE_LONG = 3,   /* more than 64 syndromes, long Euklid / erasure locators                        */
+  CC_HARD_ROUTE_WIDE = 4,   /* q > 8: 16-bit symbols, tables in global memory                                */
+  CC_HARD_ROUTE_TRIALS = 5  /* BCH, PGZ tag with erasures: two trials without erasures (bch.h:97-149)        */
+};
+int cc_hard_route(const cc_code *code, size_t B, int with_erasures);
 
 /* ---- soft-decision correct: cyclic::correct_(soft_decision_tag) cyclic.h:254-267 -> min_sum
  *      soft_decision.h:161-295.  hard = b (B*n bytes, 0/1), L = a-posteriori values (B*n floats, may be
@@ -261,7 +277,8 @@ double cc_sigma(const cc_code *code, double ebno_db); /* simulation.c++:83-85 */
  *      channel output depends only on (seed, p_error, p_erasure, global frame index).
  *      BCH and RS handles with q <= 8.  CC_ERR_INVALID_ARGUMENT: bad probabilities, NULL counters, a handle of
  *      cc_minsum_create, random codewords with a coding the encoder cannot do.  CC_ERR_UNSUPPORTED: q > 8, RS with
- *      mu / step != 1, an RS handle with the PGZ tag and p_erasure > 0 ("The PGZ-Algorithm does not support erasure
+ *      mu / step != 1 (the hard-decode entry points serve more root conventions, see cc_desc.mu; the Monte-Carlo
+ *      calls do not yet), an RS handle with the PGZ tag and p_erasure > 0 ("The PGZ-Algorithm does not support erasure
  *      decoding", hard_decision.h:66-68). ---- */
 int cc_mc_run_discrete_dev(const cc_code *code, double p_error, double p_erasure, uint64_t seed,
                            uint64_t first_frame, size_t frames, int random_codewords, uint64_t *d_counters,
