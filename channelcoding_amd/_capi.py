@@ -103,6 +103,23 @@ _SIGNATURES = {
     "cc_extract_packed_batch": (C.c_int, [_VP, _VP, _VP, C.c_size_t]),
     "cc_extract_packed_batch_dev": (C.c_int, [_VP, _VP, _VP, C.c_size_t, _VP]),
     "cc_decode_hard_packed_batch": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t]),
+    "cc_interleaved_route": (C.c_int, [_VP, C.c_size_t, C.c_uint32, C.c_int]),
+    "cc_interleaved_map_route": (C.c_int, [_VP, C.c_int, C.c_uint32]),
+    "cc_interleave_dev": (C.c_int, [_VP, C.c_int, C.c_size_t, C.c_uint32, _VP, C.c_size_t, _VP]),
+    "cc_deinterleave_dev": (C.c_int, [_VP, C.c_int, C.c_size_t, C.c_uint32, _VP, C.c_size_t, _VP]),
+    "cc_encode_interleaved_batch": (C.c_int, [_VP, _VP, _VP, C.c_size_t, C.c_uint32]),
+    "cc_encode_interleaved_batch_dev": (C.c_int, [_VP, _VP, _VP, C.c_size_t, C.c_uint32, _VP]),
+    "cc_correct_hard_interleaved_batch": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, C.c_uint32]),
+    "cc_correct_hard_interleaved_batch_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, C.c_uint32, _VP]),
+    "cc_extract_interleaved_batch": (C.c_int, [_VP, _VP, _VP, C.c_size_t, C.c_uint32]),
+    "cc_extract_interleaved_batch_dev": (C.c_int, [_VP, _VP, _VP, C.c_size_t, C.c_uint32, _VP]),
+    "cc_decode_hard_interleaved_batch": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, C.c_uint32]),
+    "cc_encode_interleaved_batch_u16": (C.c_int, [_VP, _VP, _VP, C.c_size_t, C.c_uint32]),
+    "cc_encode_interleaved_batch_u16_dev": (C.c_int, [_VP, _VP, _VP, C.c_size_t, C.c_uint32, _VP]),
+    "cc_correct_hard_interleaved_batch_u16": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, C.c_uint32]),
+    "cc_correct_hard_interleaved_batch_u16_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, C.c_uint32, _VP]),
+    "cc_extract_interleaved_batch_u16": (C.c_int, [_VP, _VP, _VP, C.c_size_t, C.c_uint32]),
+    "cc_extract_interleaved_batch_u16_dev": (C.c_int, [_VP, _VP, _VP, C.c_size_t, C.c_uint32, _VP]),
     "cc_diag_table": (C.c_int, [_VP, _VP, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                 C.POINTER(C.c_uint32)]),
     "cc_kernel_info": (C.c_int, [_VP, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),

@@ -211,6 +211,52 @@ def unpack_bits(a, n, dtype=None):
     return np.unpackbits(a, axis=-1, count=n, bitorder="little").astype(dtype or np.uint8)
 
 
+def _interleave_move(x, I, to_interleaved):
+    I = int(I)
+    if I < 1 or I > 256:
+        raise CcError(capi.ERR_INVALID_ARGUMENT, "interleave")
+    if to_interleaved:
+        if x.ndim != 2 or x.shape[0] % I:
+            raise CcError(capi.ERR_INVALID_ARGUMENT, "interleave")
+        B, n = x.shape
+        shape = (B // I, n, I)
+    else:
+        if x.ndim != 3 or x.shape[2] != I:
+            raise CcError(capi.ERR_INVALID_ARGUMENT, "deinterleave")
+        n = x.shape[1]
+        B = x.shape[0] * I
+        shape = (B, n)
+    if _is_torch(x) and x.is_cuda:
+        import torch
+        x = x.contiguous()
+        if x.dtype not in _torch_symbol_dtypes():
+            raise TypeError("interleave / deinterleave take uint8 symbols or 16-bit integer symbols")
+        out = torch.empty(shape, dtype=x.dtype, device=x.device)
+        fn = "cc_interleave_dev" if to_interleaved else "cc_deinterleave_dev"
+        with torch.cuda.device(x.device):
+            capi.check(getattr(capi.lib(), fn)(_ptr(x), x.element_size(), n, I, _ptr(out), B, _stream_handle(x)), fn)
+        return out
+    if _is_torch(x):
+        import torch
+        return torch.from_numpy(_interleave_move(x.numpy(), I, to_interleaved))
+    x = np.asarray(x)
+    if to_interleaved:
+        return np.ascontiguousarray(x.reshape(B // I, I, n).transpose(0, 2, 1))
+    return np.ascontiguousarray(x.transpose(0, 2, 1)).reshape(B, n)
+
+
+def interleave(x, I):
+    """Frame-major symbols, shape (B, n), B a multiple of I -> symbol-interleaved blocks, shape (B / I, n, I): symbol p of
+    frame b I + j at [b, p, j].  numpy arrays on the host; torch device tensors (uint8, or 16-bit for the
+    symbols of q > 8) through cc_interleave_dev on the current stream."""
+    return _interleave_move(x, I, True)
+
+
+def deinterleave(x, I):
+    """Symbol-interleaved blocks, shape (B / I, n, I) -> frame-major symbols, shape (B, n); see interleave."""
+    return _interleave_move(x, I, False)
+
+
 class cyclic:
     """Common part of primitive_bch and rs (cyclic::cyclic<...>, cyclic.h:67-386)."""
     family = None
@@ -456,6 +502,90 @@ class cyclic:
                                                     _ptr(status), B), "cc_correct_hard_packed_batch")
         return dict(out=out, status=status, nerr=nerr)
 
+    # ---- symbol-interleaved blocks: arrays of shape (B / I, n, I), messages (B / I, l, I) ----
+    def interleaved_route(self, B, I, erasures=False):
+        """1 if correct_batch(interleave=I) of B frames decodes the interleaved blocks natively, 0 if it goes through
+        de-interleave / plain route / interleave (cc_interleaved_route); raises where the call would be refused."""
+        r = capi.lib().cc_interleaved_route(self._h, int(B), int(I), int(bool(erasures)))
+        if r < 0:
+            raise CcError(-r, "cc_interleaved_route")
+        return r
+
+    def interleaved_map_route(self, which, I):
+        """The same for encode_batch (which = 0) / extract_batch (which = 1) with interleave=I."""
+        r = capi.lib().cc_interleaved_map_route(self._h, int(which), int(I))
+        if r < 0:
+            raise CcError(-r, "cc_interleaved_map_route")
+        return r
+
+    def _interleaved(self, kind, x, I, erasures=None, out=None):
+        """kind 0 = encode, 1 = extract, 2 = correct on blocks of shape (B / I, width, I)"""
+        lib = capi.lib()
+        I = int(I)
+        name = ("cc_encode_interleaved_batch", "cc_extract_interleaved_batch", "cc_correct_hard_interleaved_batch")[kind]
+        name += "_u16" if self.wide else ""
+        w_in, w_out = (self.l if kind == 0 else self.n), (self.l if kind == 1 else self.n)
+        if x.ndim != 3 or x.shape[1] != w_in or x.shape[2] != I:
+            raise CcError(capi.ERR_LENGTH, name)
+        blocks = x.shape[0]
+        B = blocks * I
+        shape = (blocks, w_out, I)
+        if _is_torch(x):
+            import torch
+            given = x
+            if out is x and not x.is_contiguous():
+                raise TypeError("decoding in place needs a contiguous tensor")
+            x = x.contiguous()
+            if x.element_size() != (2 if self.wide else 1) or x.dtype not in _torch_symbol_dtypes():
+                raise TypeError("interleave= takes uint8 symbols (16-bit integer symbols for q > 8)")
+            dev = x.device
+            if out is None:
+                out = torch.empty(shape, dtype=x.dtype, device=dev)
+            elif kind != 2:
+                raise TypeError("out= goes with correct_batch")
+            elif out is given:
+                out = x
+            elif not (_is_torch(out) and out.dtype == x.dtype and out.device == dev and out.is_contiguous()
+                      and tuple(out.shape) == shape):
+                raise TypeError("out= must be a contiguous tensor of the input's shape, dtype and device")
+            st = _stream_handle(x)
+            if kind != 2:
+                capi.check(getattr(lib, name + "_dev")(self._h, _ptr(x), _ptr(out), B, I, st), name + "_dev")
+                return out
+            er = off = None
+            if erasures is not None:
+                ev, eo = _erasure_csr(erasures, B, self.n)
+                if ev is not None:
+                    ev = ev if ev.size else np.zeros(1, ev.dtype)
+                    er = torch.from_numpy(ev.astype(np.int16)).to(dev)
+                    off = torch.from_numpy(eo.astype(np.int32)).to(dev)
+            nerr = torch.empty(B, dtype=torch.int32, device=dev)
+            status = torch.empty(B, dtype=torch.int32, device=dev)
+            capi.check(getattr(lib, name + "_dev")(self._h, _ptr(x), _ptr(er), _ptr(off), _ptr(out), _ptr(nerr), _ptr(status),
+                                                   B, I, st), name + "_dev")
+            return dict(out=out, status=status, nerr=nerr)
+        dt = np.uint16 if self.wide else np.uint8
+        if not isinstance(x, np.ndarray) or x.dtype.kind in "fi":
+            raise TypeError("interleave= takes unsigned symbols")
+        if out is x and not (x.dtype == dt and x.flags.c_contiguous):
+            raise TypeError("decoding in place needs a contiguous array of the code's symbol type")
+        x = np.ascontiguousarray(x, dt)
+        if out is None:
+            out = np.zeros(shape, dt)
+        elif kind != 2:
+            raise TypeError("out= goes with correct_batch")
+        elif not (isinstance(out, np.ndarray) and out.dtype == dt and out.flags.c_contiguous and out.flags.writeable
+                  and out.shape == shape):
+            raise TypeError("out= must be a contiguous writable array of the input's shape and the code's symbol type")
+        if kind != 2:
+            capi.check(getattr(lib, name)(self._h, _ptr(x), _ptr(out), B, I), name)
+            return out
+        er, off = _erasure_csr(erasures, B, self.n)
+        nerr = np.zeros(B, np.int32)
+        status = np.zeros(B, np.int32)
+        capi.check(getattr(lib, name)(self._h, _ptr(x), _ptr(er), _ptr(off), _ptr(out), _ptr(nerr), _ptr(status), B, I), name)
+        return dict(out=out, status=status, nerr=nerr)
+
     # ---- batch API (numpy host arrays or torch CUDA tensors) ----
     # ---- q > 8: 16-bit symbols (numpy uint16 on the host, torch int16 / uint16 on the device) ----
     def _wide_map(self, x, width_in, width_out, host_fn, dev_fn):
@@ -512,9 +642,14 @@ class cyclic:
                                                  _ptr(status), B), "cc_correct_hard_batch_u16")
         return dict(out=out, status=status, nerr=nerr)
 
-    def encode_batch(self, msg, packed=False):
-        """packed=True: uint8 (B, packed_message_bytes) -> uint8 (B, packed_bytes), see pack_bits."""
+    def encode_batch(self, msg, packed=False, interleave=None):
+        """packed=True: uint8 (B, packed_message_bytes) -> uint8 (B, packed_bytes), see pack_bits.
+        interleave=I: symbol-interleaved blocks, (B / I, l, I) -> (B / I, n, I), see interleave()."""
         lib = capi.lib()
+        if interleave is not None:
+            if packed:
+                raise TypeError("interleave= does not combine with packed=True")
+            return self._interleaved(0, msg, interleave)
         if packed:
             return self._packed_map(msg, 1, "cc_encode_packed_batch")
         if self.wide:
@@ -537,8 +672,13 @@ class cyclic:
         capi.check(lib.cc_encode_batch(self._h, _ptr(msg), _ptr(cw), msg.shape[0]), "cc_encode_batch")
         return cw
 
-    def extract_batch(self, cw, packed=False):
+    def extract_batch(self, cw, packed=False, interleave=None):
+        """interleave=I: symbol-interleaved blocks, (B / I, n, I) -> (B / I, l, I), see interleave()."""
         lib = capi.lib()
+        if interleave is not None:
+            if packed:
+                raise TypeError("interleave= does not combine with packed=True")
+            return self._interleaved(1, cw, interleave)
         if packed:
             return self._packed_map(cw, 0, "cc_extract_packed_batch")
         if self.wide:
@@ -556,15 +696,21 @@ class cyclic:
         capi.check(lib.cc_extract_batch(self._h, _ptr(cw), _ptr(msg), cw.shape[0]), "cc_extract_batch")
         return msg
 
-    def correct_batch(self, b, erasures=None, want_L=False, packed=False, out=None):
+    def correct_batch(self, b, erasures=None, want_L=False, packed=False, out=None, interleave=None):
         """Returns a dict: out (B,n) u8, status (B,) i32, and nerr (hard) or iters [+ L] (soft).
         packed=True (binary BCH codes, hard algorithms): b and out are uint8 (B, packed_bytes), see pack_bits; out= names
-        the buffer the corrected packed words go to (b itself decodes in place)."""
+        the buffer the corrected packed words go to (b itself decodes in place).
+        interleave=I (hard algorithms): b and out are symbol-interleaved blocks of shape (B / I, n, I), see interleave();
+        status, nerr and the erasure lists are per frame f = b I + j, as without it; out= as with packed=True."""
         lib = capi.lib()
+        if interleave is not None:
+            if packed:
+                raise TypeError("interleave= does not combine with packed=True")
+            return self._interleaved(2, b, interleave, erasures, out)
         if packed:
             return self._packed_correct(b, erasures, out)
         if out is not None:
-            raise TypeError("out= goes with packed=True")
+            raise TypeError("out= goes with packed=True or interleave=")
         soft_alg = self.algorithm.soft
         if self.wide and not soft_alg:  # (min-sum takes LLRs and returns bits whatever the symbol width)
             return self._wide_correct(b, erasures)
@@ -642,9 +788,31 @@ class cyclic:
             raise TypeError("hard decoding takes uint8 symbols or float32 soft values")
         return dict(out=out, status=status, nerr=nerr)
 
-    def decode_batch(self, b, erasures=None, packed=False):
+    def decode_batch(self, b, erasures=None, packed=False, interleave=None):
         """decode = correct + message extraction (cyclic.h:313-327); host arrays go through cc_decode_*_batch.
-        packed=True: b, out and msg are packed uint8 words, see pack_bits."""
+        packed=True: b, out and msg are packed uint8 words, see pack_bits.
+        interleave=I: b and out are blocks of shape (B / I, n, I), msg (B / I, l, I), see interleave()."""
+        if interleave is not None:
+            if packed:
+                raise TypeError("interleave= does not combine with packed=True")
+            I = int(interleave)
+            if _is_torch(b) or self.wide:
+                res = self._interleaved(2, b, I, erasures)
+                res["msg"] = self._interleaved(1, res["out"], I)
+                return res
+            if not isinstance(b, np.ndarray) or b.dtype.kind in "fi":
+                raise TypeError("interleave= takes unsigned symbols")
+            if b.ndim != 3 or b.shape[1] != self.n or b.shape[2] != I:
+                raise CcError(capi.ERR_LENGTH, "decode_batch")
+            b = np.ascontiguousarray(b, np.uint8)
+            B = b.shape[0] * I
+            er, off = _erasure_csr(erasures, B, self.n)
+            msg, out = np.zeros((b.shape[0], self.l, I), np.uint8), np.zeros(b.shape, np.uint8)
+            nerr, status = np.zeros(B, np.int32), np.zeros(B, np.int32)
+            capi.check(capi.lib().cc_decode_hard_interleaved_batch(self._h, _ptr(b), _ptr(er), _ptr(off), _ptr(msg), _ptr(out),
+                                                                   _ptr(nerr), _ptr(status), B, I),
+                       "cc_decode_hard_interleaved_batch")
+            return dict(out=out, msg=msg, status=status, nerr=nerr)
         if packed:
             if _is_torch(b):
                 res = self._packed_correct(b, erasures)

@@ -743,7 +743,10 @@ chunk_bm_reg_kernel(const AlgebraicTables *__restrict__ T, int dbg_stop, const u
 // of a 64-frame chunk at a time.  All polynomial arithmetic on logs with log 0 = 512 (no zero tests): a term
 // lambda_m X^-m is ex[log lambda_m + (m * log X^-1 mod nn)], the exponent advancing by one add + one wrap per
 // coefficient; wave-uniform coefficients come from a register by v_readlane, not from LDS.
-template <bool TW>  // TW: RS roots alpha^(mu + i step) other than alpha^1 .. alpha^2t, as in algebraic_chunk_kernel
+// IL: `out` holds symbol-interleaved blocks of depth il = alg >> 16: symbol p of frame f is byte
+// (f / il) il n + p il + f % il instead of f n + p (the depth travels in `alg`, so the kernel arguments of the plain
+// instantiations stay what they were)
+template <bool TW, bool IL = false>  // TW: RS roots alpha^(mu + i step) other than alpha^1 .. alpha^2t, as in algebraic_chunk_kernel
 __global__ void __launch_bounds__(256)
 chunk_fix_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t *__restrict__ synd,
                  const uint16_t *__restrict__ llg, const uint16_t *__restrict__ meta,
@@ -765,6 +768,11 @@ chunk_fix_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t *
   lg2[threadIdx.x] = threadIdx.x ? T->log[threadIdx.x] : kLogZero;
   lg[threadIdx.x] = T->log[threadIdx.x];
   __syncthreads();
+  unsigned long long il = 1;
+  if constexpr (IL) {
+    il = static_cast<unsigned>(alg) >> 16;
+    alg &= 0xFFFF;
+  }
   const int dbg_stop = alg >> 8;
   alg &= 0xFF;
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -821,6 +829,8 @@ chunk_fix_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t *
     while (s0 >= 0) {
       const int s = s0;
       const unsigned long long frame = first + s;
+      unsigned long long fb = 0;  // IL: the frame's symbol p is out[fb + p il]
+      if constexpr (IL) fb = (frame / il) * il * n + frame % il;
       const uint32_t sv = sv0, cll = cll0;
       const int deg = __builtin_amdgcn_readfirstlane(md0) & 0xFF, len = __builtin_amdgcn_readfirstlane(md0) >> 8;
       s0 = pop(todo);
@@ -872,7 +882,10 @@ chunk_fix_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t *
         if (status == CC_FRAME_OK) {  // the symbols to patch: fetched now, needed after the error values
 #pragma unroll
           for (int c = 0; c < 4; ++c)
-            if (isroot[c]) sym[c] = out[frame * n + lane + 64 * c];
+            if (isroot[c]) {
+              if constexpr (IL) sym[c] = out[fb + (lane + 64 * c) * il];
+              else sym[c] = out[frame * n + lane + 64 * c];
+            }
         }
       }
       if (dbg_stop == 3) status = CC_FRAME_LOCATOR;
@@ -950,7 +963,10 @@ chunk_fix_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t *
       const bool ok = status == CC_FRAME_OK;
 #pragma unroll
       for (int c = 0; c < 4; ++c)
-        if (ok && corr[c]) out[frame * n + lane + 64 * c] = static_cast<uint8_t>(sym[c] ^ corr[c]);
+        if (ok && corr[c]) {
+          if constexpr (IL) out[fb + (lane + 64 * c) * il] = static_cast<uint8_t>(sym[c] ^ corr[c]);
+          else out[frame * n + lane + 64 * c] = static_cast<uint8_t>(sym[c] ^ corr[c]);
+        }
       if (lane == 0) {
         if (nerr_out) nerr_out[frame] = ok ? nerr : -1;
         if (status_out) status_out[frame] = status;
@@ -971,7 +987,8 @@ chunk_fix_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t *
 // MD = longest locator served here: 16 (= t of the largest code; calls without erasures), 24 for calls with erasures
 // TW: RS roots alpha^mu .. alpha^(mu + 2t - 1) with mu != 1 (the plane chain serves step = 1 only, so Z = X): one more
 // log-add per located error, the factor alpha^(twist p) on Forney's quotient
-template <int MD, bool TW>
+// IL: symbol-interleaved blocks of depth il = alg >> 16, as in chunk_fix_kernel
+template <int MD, bool TW, bool IL = false>
 __global__ void __launch_bounds__(256)
 chunk_fixl_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t *__restrict__ synd,
                   const uint16_t *__restrict__ llg, const uint16_t *__restrict__ meta,
@@ -994,6 +1011,11 @@ chunk_fixl_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t 
   const int n = T->n, t2 = T->nroots, nc = t2 + 1;
   const bool is_rs = T->family == CC_FAMILY_RS;
   const uint32_t twist = TW ? static_cast<uint32_t>(T->twist) : 0u;
+  uint32_t il = 1;
+  if constexpr (IL) {
+    il = static_cast<uint32_t>(alg) >> 16;
+    alg &= 0xFFFF;
+  }
 #ifdef CC_AMD_EXPERIMENTS  // CC_EXP_FIXL bits: 1 no load/store of the symbols (16 no load, 32 no store), 2 no Forney sums, 4 no error loop, 8 no omega
   const int xf = alg >> 8;
   alg &= 0xFF;
@@ -1067,6 +1089,16 @@ chunk_fixl_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t 
     // memory counter retires in order, so a load issued after a store would wait for that store's acknowledgement on
     // every trip (measured: 272 us for the kernel with load and store alternating, 150 / 165 us with only one of them).
     const uint8_t *obase = out + first * n;  // wave-uniform base + 32-bit lane offset
+    // the lane's frame within the chunk's blocks: symbol p at obase[fo + p * il]; offsets fit 32 bits (at most 64 blocks
+    // of il n <= 16 * 255 bytes); IL: the base is the first block the chunk touches
+    uint32_t fo = static_cast<uint32_t>(f * n);
+    if constexpr (IL) {
+      const unsigned long long b0 = first / il;
+      const uint32_t jj = static_cast<uint32_t>(first - b0 * il) + static_cast<uint32_t>(f), bi = jj / il;
+      obase = out + b0 * il * n;
+      fo = bi * il * static_cast<uint32_t>(n) + (jj - bi * il);
+    }
+    uint8_t *const wbase = out + (obase - out);  // (IL only: the plain store keeps its own address arithmetic)
     uint32_t ll[MD + 1], ol[MD], sl[MD];  // log lambda_m, log omega_j, log S_j (kZ for zero); j < MD: omega_j, j < deg <= MD, needs no more
     {
       for (int e0 = 0; e0 < MD; e0 += 4) {
@@ -1074,7 +1106,7 @@ chunk_fixl_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t 
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const bool has = static_cast<uint32_t>(e0 + u) < have;
-          sy[u] = has ? obase[static_cast<uint32_t>(f * n) + PL[(e0 + u) * 64 + lane]] : 0u;
+          sy[u] = has ? obase[fo + PL[(e0 + u) * 64 + lane] * il] : 0u;
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) PL[(MD + e0 + u) * 64 + lane] = static_cast<uint8_t>(sy[u]);
@@ -1128,7 +1160,11 @@ chunk_fixl_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t 
         y = (num && den) ? exl[lg[num] + kN - lg[den] + (TW ? (twist * p) % kN : 0u)] : 0u;
       }
       // (an atomic XOR on the surrounding dword instead of the load / store pair was measured slower: 942 vs 1024 M)
-      if (has && y && !(xf & 33)) out[frame * n + p] = static_cast<uint8_t>(sym ^ y);
+      if constexpr (IL) {
+        if (has && y && !(xf & 33)) wbase[fo + p * il] = static_cast<uint8_t>(sym ^ y);
+      } else {
+        if (has && y && !(xf & 33)) out[frame * n + p] = static_cast<uint8_t>(sym ^ y);
+      }
     }
     __builtin_amdgcn_wave_barrier();  // the list is reused by the next chunk
   }
@@ -1260,7 +1296,7 @@ int launch_chunk_bm(const cc_code *code, const uint8_t *d_synd, const uint16_t *
 // syndromes on bit planes (bitslice.hip), Berlekamp-Massey over chunks of 64 frames, root search on planes, corrections
 static int launch_chunk_bitsliced(const cc_code *code, bool float_in, const void *d_in, const uint16_t *d_er,
                                   const uint32_t *d_er_off, uint8_t *d_out, int32_t *d_nerr, int32_t *d_status, size_t B,
-                                  hipStream_t stream) {
+                                  hipStream_t stream, int il) {
   const int t2 = static_cast<int>(code->tab.roots.size()), nc = t2 + 1;
   const unsigned long long G = (B + 31) / 32, chunks = (B + 63) / 64;
   const size_t G64 = static_cast<size_t>((G + 63) / 64) * 64;  // syndromes, locators and root masks are laid out in blocks of 64 groups
@@ -1287,7 +1323,10 @@ static int launch_chunk_bitsliced(const cc_code *code, bool float_in, const void
   unsigned long long *d_left = reinterpret_cast<unsigned long long *>(d_roots + roots_bytes);
   uint32_t *d_nleft = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(d_left) + left_bytes);
   uint8_t *d_rootsT = reinterpret_cast<uint8_t *>(d_nleft) + 256;
-  int rc = launch_bitslice_syndromes(code, float_in, d_in, d_out, d_synd, B, stream);
+  // il > 1: symbol-interleaved words -- the loader of the syndrome kernel and the two correctors address
+  // the blocks themselves; syndromes, locators and root masks are per frame, as ever
+  const int il_arg = il > 1 ? il << 16 : 0;
+  int rc = launch_bitslice_syndromes(code, float_in, d_in, d_out, d_synd, B, stream, il);
   if (rc == CC_OK) {
     const int dbg_stop = alg_stop_stage();
     const unsigned long long Bq = B, blocks_needed = (chunks + 3) / 4;
@@ -1313,11 +1352,13 @@ static int launch_chunk_bitsliced(const cc_code *code, bool float_in, const void
           const unsigned long long lcap = static_cast<unsigned long long>(code->num_cus) * fixl_per_cu[tw][long_loc];
           const int lgrid = static_cast<int>(blocks_needed < lcap ? blocks_needed : lcap);
           auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(lgrid), dim3(256), 0, stream, code->d_alg, code->desc.algorithm | fixl_exp(), d_synd,
+            hipLaunchKernelGGL(kernel, dim3(lgrid), dim3(256), 0, stream, code->d_alg, code->desc.algorithm | fixl_exp() | il_arg, d_synd,
                                d_llg, d_meta, d_mask, reinterpret_cast<const uint32_t *>(d_rootsT), d_left, d_nleft, d_er_off,
                                d_out, d_nerr, d_status, Bq);
           };
-          if (tw)
+          if (il > 1)  // (no erasures: locators up to degree 16)
+            tw ? launch(chunk_fixl_kernel<16, true, true>) : launch(chunk_fixl_kernel<16, false, true>);
+          else if (tw)
             long_loc ? launch(chunk_fixl_kernel<24, true>) : launch(chunk_fixl_kernel<16, true>);
           else
             long_loc ? launch(chunk_fixl_kernel<24, false>) : launch(chunk_fixl_kernel<16, false>);
@@ -1326,11 +1367,14 @@ static int launch_chunk_bitsliced(const cc_code *code, bool float_in, const void
       }
       if (rc == CC_OK && e == hipSuccess) {
         auto launch = [&](auto kernel) {
-          hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, code->d_alg, code->desc.algorithm | (dbg_stop << 8),
+          hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, code->d_alg, code->desc.algorithm | (dbg_stop << 8) | il_arg,
                              d_synd, d_llg, d_meta, four ? d_left : d_mask, reinterpret_cast<const uint32_t *>(d_roots),
                              four ? d_nleft : nullptr, d_er_off, long_loc ? 24 : 16, d_out, d_nerr, d_status, Bq);
         };
-        tw ? launch(chunk_fix_kernel<true>) : launch(chunk_fix_kernel<false>);
+        if (il > 1)
+          tw ? launch(chunk_fix_kernel<true, true>) : launch(chunk_fix_kernel<false, true>);
+        else
+          tw ? launch(chunk_fix_kernel<true>) : launch(chunk_fix_kernel<false>);
         e = hipGetLastError();
       }
     }
@@ -1342,10 +1386,14 @@ static int launch_chunk_bitsliced(const cc_code *code, bool float_in, const void
 
 int launch_algebraic_chunk(const cc_code *code, bool float_in, const void *d_in, const uint16_t *d_er,
                            const uint32_t *d_er_off, uint8_t *d_out, int32_t *d_nerr, int32_t *d_status, size_t B,
-                           hipStream_t stream) {
+                           hipStream_t stream, int il) {
   if (B == 0) return CC_OK;
   if (bitslice_supported(code))
-    return launch_chunk_bitsliced(code, float_in, d_in, d_er, d_er_off, d_out, d_nerr, d_status, B, stream);
+    return launch_chunk_bitsliced(code, float_in, d_in, d_er, d_er_off, d_out, d_nerr, d_status, B, stream, il);
+  if (il > 1) {
+    set_last_error("interleaved words are addressed by the bit-plane chain only");
+    return CC_ERR_INVALID_ARGUMENT;
+  }
   return launch_chunk_fpw<32>(code, float_in, d_in, d_out, d_nerr, d_status, B, stream);
 }
 

@@ -89,10 +89,114 @@ __device__ __forceinline__ void fused_syndromes4(const uint4 *__restrict__ lds, 
   }
 }
 
+// The interleaved loader of bitslice_fused_syndrome_kernel<.., IL = true> (see there): group g of the calling wavefront,
+// depth il.  RUN = bytes moved at a time: il itself where it divides 32, else 1.
+template <int RUN>
+__device__ __forceinline__ void interleaved_load_run(const uint8_t *in, uint8_t *out, uint4 *lds, bool copy, unsigned long long g,
+                                                     int frames, int n, int n_in, int off, int il) {
+  const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // frame f0 + i of the group: block b0 + bi, place ji in it -- (bi, ji) walk from (0, j0); offsets within the group's
+  // blocks fit 32 bits (at most 32 blocks of il n <= 16 * 255 bytes)
+  const unsigned long long f0 = g * 32, b0 = f0 / static_cast<unsigned>(il);
+  const int j0 = static_cast<int>(f0 - b0 * il);
+  const uint8_t *src = in + b0 * static_cast<unsigned long long>(il) * n_in;
+  uint8_t *dst = out + b0 * static_cast<unsigned long long>(il) * n + static_cast<unsigned>(off * il);
+#pragma unroll 1
+  for (int c = 0; c < 4; ++c) {
+    const int pi = lane + 64 * c;  // input position; position off + pi of the codeword
+    if (pi >= n_in) break;
+    uint32_t d[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // byte i = symbol pi of frame f0 + i
+    const uint32_t po = static_cast<uint32_t>(pi * il);
+    if constexpr (RUN == 1) {
+      int bi = 0, ji = j0;
+#pragma unroll
+      for (int i = 0; i < 32; ++i) {
+        if (i < frames) {
+          const uint32_t v = src[static_cast<uint32_t>(bi * il * n_in + ji) + po];
+          if (copy) dst[static_cast<uint32_t>(bi * il * n + ji) + po] = static_cast<uint8_t>(v);
+          d[i >> 2] |= v << (8 * (i & 3));
+        }
+        if (++ji == il) ji = 0, ++bi;
+      }
+    } else {  // (j0 = 0: a group starts a block)
+#pragma unroll
+      for (int r = 0; r < 32 / RUN; ++r) {
+        if (r * RUN >= frames) break;  // (B is a multiple of il: a partial group ends with a whole block)
+        const uint8_t *s = src + static_cast<uint32_t>(r * il * n_in) + po;
+        uint8_t *o = dst + static_cast<uint32_t>(r * il * n) + po;
+        if constexpr (RUN == 16) {
+          uint4 v;
+          __builtin_memcpy(&v, s, 16);
+          if (copy) __builtin_memcpy(o, &v, 16);
+          d[4 * r] = v.x, d[4 * r + 1] = v.y, d[4 * r + 2] = v.z, d[4 * r + 3] = v.w;
+        } else if constexpr (RUN == 8) {
+          uint2 v;
+          __builtin_memcpy(&v, s, 8);
+          if (copy) __builtin_memcpy(o, &v, 8);
+          d[2 * r] = v.x, d[2 * r + 1] = v.y;
+        } else if constexpr (RUN == 4) {
+          uint32_t v;
+          __builtin_memcpy(&v, s, 4);
+          if (copy) __builtin_memcpy(o, &v, 4);
+          d[r] = v;
+        } else {
+          uint16_t v;
+          __builtin_memcpy(&v, s, 2);
+          if (copy) __builtin_memcpy(o, &v, 2);
+          d[r >> 1] |= static_cast<uint32_t>(v) << (16 * (r & 1));
+        }
+      }
+    }
+    uint32_t w[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {  // word k = the bytes of the frames {k, 8+k, 16+k, 24+k}: byte k & 3 of dwords k >> 2, + 2, + 4, + 6
+      const uint32_t sel = 0x0c0c0000u | static_cast<uint32_t>((4 + (k & 3)) << 8) | static_cast<uint32_t>(k & 3);
+      const uint32_t lo = __builtin_amdgcn_perm(d[2 + (k >> 2)], d[k >> 2], sel), hi = __builtin_amdgcn_perm(d[6 + (k >> 2)], d[4 + (k >> 2)], sel);
+      w[k] = __builtin_amdgcn_perm(hi, lo, 0x05040100u);
+    }
+    butterfly(w);  // word b, bit f = bit b of the symbol of frame f
+    const int p = off + pi, i = p & 31;
+    uint4 *slot = lds + (i * 2) * 64 + 8 * (p >> 5) + (wid ^ (i >> 2));
+    slot[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    slot[64] = make_uint4(w[4], w[5], w[6], w[7]);
+  }
+}
+__device__ __forceinline__ void interleaved_load(const uint8_t *in, uint8_t *out, uint4 *lds, bool copy, unsigned long long g,
+                                                 unsigned long long G, unsigned long long B, int n, int n_in, int off, int il) {
+  const int frames = g >= G ? 0 : static_cast<int>((B - g * 32) < 32ull ? (B - g * 32) : 32ull);
+  if (frames == 0) {  // a group past the batch: zero planes, as the plain loader leaves them
+    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (int pi = lane; pi < n_in; pi += 64) {
+      const int p = off + pi, i = p & 31;
+      uint4 *slot = lds + (i * 2) * 64 + 8 * (p >> 5) + (wid ^ (i >> 2));
+      slot[0] = make_uint4(0, 0, 0, 0);
+      slot[64] = make_uint4(0, 0, 0, 0);
+    }
+    return;
+  }
+  switch (il) {  // wave-uniform
+    case 16: interleaved_load_run<16>(in, out, lds, copy, g, frames, n, n_in, off, il); break;
+    case 8: interleaved_load_run<8>(in, out, lds, copy, g, frames, n, n_in, off, il); break;
+    case 4: interleaved_load_run<4>(in, out, lds, copy, g, frames, n, n_in, off, il); break;
+    case 2: interleaved_load_run<2>(in, out, lds, copy, g, frames, n, n_in, off, il); break;
+    default: interleaved_load_run<1>(in, out, lds, copy, g, frames, n, n_in, off, il); break;
+  }
+}
+
 // decoding: n_in = n, off = 0.  Encoding (RAW): the n_in message symbols of a frame go to the positions off .. n - 1 of
 // its codeword (cyclic.h:29-40) -- in `out` and on the planes, whose positions below off stay zero -- and the result is
 // (a x^k)(alpha^j) on planes for bitslice_parity_kernel.
-template <bool FLOAT_IN, bool RAW, int MU>
+//
+// IL: the words are symbol-interleaved blocks of depth il = off >> 16, 2 <= il <= 16 (the depth travels in
+// the high half of `off` so that the kernel arguments of the plain instantiations stay what they were): symbol p of
+// frame f = b il + j is byte b il n + p il + j.  There a lane owns the POSITIONS lane, lane + 64, .. of its group's 32
+// frames instead of four positions of every frame: one position of consecutive frames is il adjacent bytes, so for
+// il = 2, 4, 8, 16 (divisors of 32: a group is whole blocks, and b il n + p il is a multiple of il) a lane moves runs
+// of il bytes and the 64 lanes of an instruction cover 64 il consecutive bytes; any other depth goes byte by byte
+// (blocks straddle the groups, a run starts anywhere), the lanes of an instruction il bytes apart.  Either way the 32
+// bytes of a position arrive in frame order, and the same three v_perm per word as below make "byte of the frames
+// {k, 8+k, 16+k, 24+k}" of them.  Same planes in LDS, same everything behind them.
+template <bool FLOAT_IN, bool RAW, int MU, bool IL = false>
 __global__ void __launch_bounds__(kFusedThreads, 4)
 bitslice_fused_syndrome_kernel(const void *in_raw, uint8_t *out, uint8_t *__restrict__ synd, unsigned long long B,
                                unsigned long long G, int n, int t2, int n_in, int off) {
@@ -111,12 +215,19 @@ bitslice_fused_syndrome_kernel(const void *in_raw, uint8_t *out, uint8_t *__rest
 #endif
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const unsigned long long group0 = static_cast<unsigned long long>(blockIdx.x) * kFusedGroups;
+  int il = 1;
+  if constexpr (IL) {
+    il = off >> 16;
+    off &= 0xFFFF;
+  }
   // positions n .. 255 do not exist, positions below off carry nothing yet (the parity symbols): zero planes
   for (int k = threadIdx.x; k < (256 - n + off) * 16; k += kFusedThreads) {
     const int z = k >> 4, p = z < off ? z : n + (z - off), i = p & 31;
     lds[(i * 2 + ((k >> 3) & 1)) * 64 + 8 * (p >> 5) + (k & 7)] = make_uint4(0, 0, 0, 0);
   }
-  {  // ---- wavefront = group: lane l owns the four input symbols q .. q+3, q = min(4 l, n_in - 4): one (unaligned) dword per
+  if constexpr (IL) {
+    interleaved_load(static_cast<const uint8_t *>(in_raw), out, lds, copy, group0 + wid, G, B, n, n_in, off, il);
+  } else {  // ---- wavefront = group: lane l owns the four input symbols q .. q+3, q = min(4 l, n_in - 4): one (unaligned) dword per
      //      frame and lane; the last lane re-does symbols of its neighbour (same values) ----
     const unsigned long long g = group0 + wid, f0 = g * 32;
     const int frames = g >= G ? 0 : static_cast<int>((B - f0) < 32ull ? (B - f0) : 32ull);
@@ -275,10 +386,19 @@ template <int K, int MU, int I0, int... J>
 __device__ __forceinline__ void interp_all(uint32_t (&acc)[8][8], const uint4 *__restrict__ ev, std::integer_sequence<int, J...>) {
   (interp_one<K, MU, I0, J>(acc, ev), ...);
 }
-// parity symbols I0 .. I0+7 of the 32 frames of group g -> cw[frame][I0 .. I0+7]
-template <int K, int MU, int I0>
+// parity symbols I0 .. I0+7 of the 32 frames of group g -> cw[frame][I0 .. I0+7]; IL: to the interleaved places of
+// depth il = n >> 16, eight single bytes il apart
+template <int K, int MU, int I0, bool IL>
 __device__ __forceinline__ void parity8(const uint4 *__restrict__ evals, uint8_t *__restrict__ cw, unsigned long long g,
                                         unsigned long long B, int n) {
+  uint32_t il = 1, j0 = 0;
+  unsigned long long b0 = 0;
+  if constexpr (IL) {
+    il = static_cast<uint32_t>(n) >> 16;
+    n &= 0xFFFF;
+    b0 = g * 32 / il;
+    j0 = static_cast<uint32_t>(g * 32 - b0 * il);
+  }
   uint32_t acc[8][8];
 #pragma unroll
   for (int i = 0; i < 8; ++i)
@@ -301,10 +421,17 @@ __device__ __forceinline__ void parity8(const uint4 *__restrict__ evals, uint8_t
         const uint32_t hi = __builtin_amdgcn_perm(acc[4 * half + 3][k], acc[4 * half + 2][k], sel);
         w[half] = __builtin_amdgcn_perm(hi, lo, 0x05040100u);
       }
+      if constexpr (IL) {
+        const uint32_t jj = j0 + 8 * h + k, bi = jj / il;
+        uint8_t *dst = cw + (b0 + bi) * il * static_cast<unsigned long long>(n) + (jj - bi * il) + I0 * il;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) dst[i * il] = static_cast<uint8_t>(w[i >> 2] >> (8 * (i & 3)));
+        continue;
+      }
       __builtin_memcpy(cw + frame * static_cast<unsigned long long>(n) + I0, w, 8);
     }
 }
-template <int K, int MU>
+template <int K, int MU, bool IL = false>
 __global__ void __launch_bounds__(256)
 bitslice_parity_kernel(const uint4 *__restrict__ evals, uint8_t *__restrict__ cw, unsigned long long B, unsigned long long G,
                        int n) {
@@ -313,14 +440,14 @@ bitslice_parity_kernel(const uint4 *__restrict__ evals, uint8_t *__restrict__ cw
   if (g >= G) return;
   if constexpr (K == 32) {
     switch (wid) {
-      case 0: parity8<K, MU, 0>(evals, cw, g, B, n); break;
-      case 1: parity8<K, MU, 8>(evals, cw, g, B, n); break;
-      case 2: parity8<K, MU, 16>(evals, cw, g, B, n); break;
-      default: parity8<K, MU, 24>(evals, cw, g, B, n); break;
+      case 0: parity8<K, MU, 0, IL>(evals, cw, g, B, n); break;
+      case 1: parity8<K, MU, 8, IL>(evals, cw, g, B, n); break;
+      case 2: parity8<K, MU, 16, IL>(evals, cw, g, B, n); break;
+      default: parity8<K, MU, 24, IL>(evals, cw, g, B, n); break;
     }
   } else {
-    if (wid == 0) parity8<K, MU, 0>(evals, cw, g, B, n);
-    else parity8<K, MU, 8>(evals, cw, g, B, n);
+    if (wid == 0) parity8<K, MU, 0, IL>(evals, cw, g, B, n);
+    else parity8<K, MU, 8, IL>(evals, cw, g, B, n);
   }
 }
 
@@ -507,7 +634,7 @@ bool bitslice_supported(const cc_code *code) {
 
 // synd: G64 * t2 * 32 bytes, G64 = ceil(B / 2048) * 64 groups of 32 frames; `out` receives the copy of the words
 int launch_bitslice_syndromes(const cc_code *code, bool float_in, const void *d_in, uint8_t *d_out, uint8_t *d_synd, size_t B,
-                              hipStream_t stream) {
+                              hipStream_t stream, int il) {
   int n = static_cast<int>(code->tab.n);
   const int t2 = static_cast<int>(code->tab.roots.size());
 #ifdef CC_AMD_EXPERIMENTS
@@ -521,9 +648,12 @@ int launch_bitslice_syndromes(const cc_code *code, bool float_in, const void *d_
                             static_cast<int>(kFusedLdsBytes));
     if (e == hipSuccess)
       hipLaunchKernelGGL(kernel, dim3(grid), dim3(kFusedThreads), kFusedLdsBytes, stream, d_in, d_out, d_synd, Bq, G, n, t2,
-                         n & 0xFFFF, 0);
+                         n & 0xFFFF, il > 1 ? il << 16 : 0);
   };
-  if (code->tab.root_powers[0] == 0)  // first root alpha^0
+  if (il > 1)  // symbol-interleaved words (bytes only: float_in has no interleaved entry point)
+    code->tab.root_powers[0] == 0 ? launch(&bitslice_fused_syndrome_kernel<false, false, 0, true>)
+                                  : launch(&bitslice_fused_syndrome_kernel<false, false, 1, true>);
+  else if (code->tab.root_powers[0] == 0)  // first root alpha^0
     float_in ? launch(&bitslice_fused_syndrome_kernel<true, false, 0>) : launch(&bitslice_fused_syndrome_kernel<false, false, 0>);
   else
     float_in ? launch(&bitslice_fused_syndrome_kernel<true, false, 1>) : launch(&bitslice_fused_syndrome_kernel<false, false, 1>);
@@ -564,7 +694,7 @@ bool bitslice_encode_supported(const cc_code *code) {
 
 // systematic encoder (cyclic.h:29-40, division_tag) on bit planes: message -> planes and codeword body, evaluations
 // at the 2t roots, interpolation of the remainder
-int launch_bitslice_encode(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, hipStream_t stream) {
+int launch_bitslice_encode(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, hipStream_t stream, int il) {
   const int n = static_cast<int>(code->tab.n), k = static_cast<int>(code->tab.k), l = static_cast<int>(code->tab.l);
   const unsigned long long G = (B + 31) / 32, Bq = B;
   const size_t G64 = static_cast<size_t>((G + 63) / 64) * 64;
@@ -579,17 +709,26 @@ int launch_bitslice_encode(const cc_code *code, const uint8_t *d_msg, uint8_t *d
                             static_cast<int>(kFusedLdsBytes));
     if (e == hipSuccess) {
       hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>((G + kFusedGroups - 1) / kFusedGroups)), dim3(kFusedThreads),
-                         kFusedLdsBytes, stream, static_cast<const void *>(d_msg), d_cw, d_eval, Bq, G, n, k, l, k);
+                         kFusedLdsBytes, stream, static_cast<const void *>(d_msg), d_cw, d_eval, Bq, G, n, k, l,
+                         il > 1 ? k | (il << 16) : k);
       e = hipGetLastError();
     }
   };
-  mu0 ? evaluate(&bitslice_fused_syndrome_kernel<false, true, 0>) : evaluate(&bitslice_fused_syndrome_kernel<false, true, 1>);
+  if (il > 1)  // message and codeword are symbol-interleaved blocks of depth il
+    mu0 ? evaluate(&bitslice_fused_syndrome_kernel<false, true, 0, true>) : evaluate(&bitslice_fused_syndrome_kernel<false, true, 1, true>);
+  else
+    mu0 ? evaluate(&bitslice_fused_syndrome_kernel<false, true, 0>) : evaluate(&bitslice_fused_syndrome_kernel<false, true, 1>);
   if (e == hipSuccess) {  // interpolation of the remainder
     auto interpolate = [&](auto kernel, int threads) {
       hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>((G + 63) / 64)), dim3(threads), 0, stream,
-                         reinterpret_cast<const uint4 *>(d_eval), d_cw, Bq, G, n);
+                         reinterpret_cast<const uint4 *>(d_eval), d_cw, Bq, G, il > 1 ? n | (il << 16) : n);
     };
-    if (k == 32)
+    if (il > 1) {
+      if (k == 32)
+        mu0 ? interpolate(bitslice_parity_kernel<32, 0, true>, 256) : interpolate(bitslice_parity_kernel<32, 1, true>, 256);
+      else
+        mu0 ? interpolate(bitslice_parity_kernel<16, 0, true>, 128) : interpolate(bitslice_parity_kernel<16, 1, true>, 128);
+    } else if (k == 32)
       mu0 ? interpolate(bitslice_parity_kernel<32, 0>, 256) : interpolate(bitslice_parity_kernel<32, 1>, 256);
     else
       mu0 ? interpolate(bitslice_parity_kernel<16, 0>, 128) : interpolate(bitslice_parity_kernel<16, 1>, 128);

@@ -1328,6 +1328,23 @@ int cc_packed_route(const cc_code *code, size_t B) {
   return packed_native_supported(code, B) ? 1 : 0;
 }
 
+// The router of the byte / 16-bit _dev entry points on frame-major device buffers: kind 0 = encode, 1 = extract,
+// 2 = correct.  The generic routes of the packed and of the interleaved calls go through it.
+static int plain_route_dev(const cc_code *code, int kind, const uint8_t *a, const uint16_t *d_er, const uint32_t *d_off, uint8_t *b,
+                           int32_t *d_nerr, int32_t *d_status, size_t B, hipStream_t stream) {
+  if (code->wide) {
+    const uint16_t *a16 = reinterpret_cast<const uint16_t *>(a);
+    uint16_t *b16 = reinterpret_cast<uint16_t *>(b);
+    return kind == 0   ? launch_wide_encode(code, a16, b16, B, stream)
+           : kind == 1 ? launch_wide_extract(code, a16, b16, B, stream)
+                       : launch_wide_correct(code, a16, d_er, d_off, b16, d_nerr, d_status, B, stream);
+  }
+  if (kind == 0) return launch_encode(code, a, b, B, stream);
+  if (kind == 1) return launch_extract(code, a, b, B, stream);
+  if (d_er && code->desc.algorithm == CC_ALG_PGZ) return launch_pgz_erasures(code, a, d_er, d_off, b, d_nerr, d_status, B, stream);
+  return launch_algebraic(code, false, a, d_er, d_off, b, d_nerr, d_status, B, stream);
+}
+
 // Generic route of a packed call: unpack into workspace of the handle's pool (bytes, 16-bit words for q > 8), the
 // router of the byte / 16-bit entry points, pack.  kind 0 = encode, 1 = extract, 2 = correct.
 static int packed_generic_dev(const cc_code *code, int kind, const uint8_t *d_src, const uint16_t *d_er, const uint32_t *d_off,
@@ -1342,23 +1359,7 @@ static int packed_generic_dev(const cc_code *code, int kind, const uint8_t *d_sr
   CC_HIP_TRY(workspace_alloc(code, reinterpret_cast<void **>(&ws), in_bytes + (in_place ? 0 : B * out_w * width) + 16, stream));
   uint8_t *a = ws, *b = in_place ? ws : ws + in_bytes;
   int rc = launch_unpack_bits(d_src, in_w, a, static_cast<int>(width), B, stream);
-  if (rc == CC_OK) {
-    if (code->wide) {
-      const uint16_t *a16 = reinterpret_cast<const uint16_t *>(a);
-      uint16_t *b16 = reinterpret_cast<uint16_t *>(b);
-      rc = kind == 0   ? launch_wide_encode(code, a16, b16, B, stream)
-           : kind == 1 ? launch_wide_extract(code, a16, b16, B, stream)
-                       : launch_wide_correct(code, a16, d_er, d_off, b16, d_nerr, d_status, B, stream);
-    } else if (kind == 0) {
-      rc = launch_encode(code, a, b, B, stream);
-    } else if (kind == 1) {
-      rc = launch_extract(code, a, b, B, stream);
-    } else if (d_er && code->desc.algorithm == CC_ALG_PGZ) {
-      rc = launch_pgz_erasures(code, a, d_er, d_off, b, d_nerr, d_status, B, stream);
-    } else {
-      rc = launch_algebraic(code, false, a, d_er, d_off, b, d_nerr, d_status, B, stream);
-    }
-  }
+  if (rc == CC_OK) rc = plain_route_dev(code, kind, a, d_er, d_off, b, d_nerr, d_status, B, stream);
   if (rc == CC_OK) rc = launch_pack_bits(b, static_cast<int>(width), out_w, d_dst, B, stream);
   (void)hipFreeAsync(ws, stream);
   return rc;
@@ -1486,6 +1487,239 @@ int cc_decode_hard_packed_batch(const cc_code *code, const uint8_t *in, const ui
   }
   if (int rc = cc_correct_hard_packed_batch(code, in, erasures, erasure_offsets, words, nerr, status, B)) return rc;
   return cc_extract_packed_batch(code, words, msg, B);
+}
+
+/* ------------------------------ symbol-interleaved blocks (interleave.hip) ------------------------------ */
+
+// what the interleaved form adds to the refusals of the plain call
+static int interleave_args(const cc_code *code, size_t B, uint32_t I) {
+  if (code->matrix_only) {
+    set_last_error("interleaved blocks need a code: a handle of cc_minsum_create has a parity-check matrix only");
+    return CC_ERR_INVALID_ARGUMENT;
+  }
+  if (I == 0 || I > kInterleaveMax) {
+    set_last_error("the interleaving depth is 1 .. 256");
+    return CC_ERR_INVALID_ARGUMENT;
+  }
+  if (B % I != 0) {
+    set_last_error("the number of frames must be a multiple of the interleaving depth");
+    return CC_ERR_INVALID_ARGUMENT;
+  }
+  return CC_OK;
+}
+// the refusals of the plain call of the same kind (0 = encode, 1 = extract, 2 = correct) and symbol width, in its order
+static int interleaved_ready(const cc_code *code, int kind, int width, bool erasures) {
+  if (width == 2) return kind == 2 ? wide_correct_ready(code, erasures) : wide_ready(code);
+  if (kind == 2) return hard_supported(code, erasures);
+  if (int rc = not_wide(code)) return rc;
+  if (code->device == CC_DEVICE_NONE) return CC_ERR_NO_DEVICE;
+  return CC_OK;
+}
+
+int cc_interleave_dev(const void *d_in, int width, size_t n, uint32_t I, void *d_out, size_t B, void *stream) {
+  if ((width != 1 && width != 2) || n > 0x7FFFFFu || I == 0 || I > kInterleaveMax || B % I != 0 ||
+      (B && n && (!d_in || !d_out || d_in == d_out)))
+    return CC_ERR_INVALID_ARGUMENT;
+  return launch_interleave(d_in, width, n, I, d_out, B, true, static_cast<hipStream_t>(stream));
+}
+int cc_deinterleave_dev(const void *d_in, int width, size_t n, uint32_t I, void *d_out, size_t B, void *stream) {
+  if ((width != 1 && width != 2) || n > 0x7FFFFFu || I == 0 || I > kInterleaveMax || B % I != 0 ||
+      (B && n && (!d_in || !d_out || d_in == d_out)))
+    return CC_ERR_INVALID_ARGUMENT;
+  return launch_interleave(d_in, width, n, I, d_out, B, false, static_cast<hipStream_t>(stream));
+}
+
+int cc_interleaved_route(const cc_code *code, size_t B, uint32_t I, int with_erasures) {
+  if (!code) return -CC_ERR_INVALID_ARGUMENT;
+  if (int rc = interleave_args(code, B, I)) return -rc;
+  if (int rc = interleaved_ready(code, 2, code->wide ? 2 : 1, with_erasures != 0)) return -rc;
+  if (I == 1) return 1;  // the plain call: nothing is transposed
+  return interleaved_native_supported(code, B, I, with_erasures != 0) ? 1 : 0;
+}
+int cc_interleaved_map_route(const cc_code *code, int which, uint32_t I) {
+  if (!code || which < 0 || which > 1) return -CC_ERR_INVALID_ARGUMENT;
+  if (int rc = interleave_args(code, 0, I)) return -rc;
+  if (int rc = interleaved_ready(code, which, code->wide ? 2 : 1, false)) return -rc;
+  if (I == 1) return 1;
+  return (which == 0 ? interleaved_encode_native(code, I) : interleaved_extract_native(code, I)) ? 1 : 0;
+}
+
+// One interleaved call on device buffers (kind as plain_route_dev; symbols of the handle's width).  Depth 1 is the
+// plain call.  Native: the bit-plane chain / the strided copy on the blocks themselves.  Generic: de-interleave into
+// workspace of the handle's pool, the plain router, interleave the result.
+static int interleaved_dev(const cc_code *code, int kind, const void *d_src, const uint16_t *d_er, const uint32_t *d_off,
+                           void *d_dst, int32_t *d_nerr, int32_t *d_status, size_t B, size_t I, hipStream_t stream) {
+  if (B == 0) return CC_OK;
+  const uint8_t *src = static_cast<const uint8_t *>(d_src);
+  uint8_t *dst = static_cast<uint8_t *>(d_dst);
+  if (I == 1) return plain_route_dev(code, kind, src, d_er, d_off, dst, d_nerr, d_status, B, stream);
+  if (kind == 0 && interleaved_encode_native(code, I)) return launch_bitslice_encode(code, src, dst, B, stream, static_cast<int>(I));
+  if (kind == 1 && interleaved_extract_native(code, I)) return launch_interleaved_extract(code, src, dst, B, I, stream);
+  if (kind == 2 && interleaved_native_supported(code, B, I, d_er != nullptr))
+    return launch_algebraic_chunk(code, false, src, nullptr, nullptr, dst, d_nerr, d_status, B, stream, static_cast<int>(I));
+  const size_t n = code->tab.n, l = code->tab.l, width = code->wide ? 2 : 1;
+  const size_t in_w = kind == 0 ? l : n, out_w = kind == 1 ? l : n;
+  // words without erasures are corrected in place, as a byte call with out == in (it then skips its copy of the words)
+  const bool in_place = kind == 2 && !d_er && !code->wide;
+  const size_t in_bytes = (B * in_w * width + 255) & ~static_cast<size_t>(255);
+  uint8_t *ws = nullptr;
+  CC_HIP_TRY(workspace_alloc(code, reinterpret_cast<void **>(&ws), in_bytes + (in_place ? 0 : B * out_w * width) + 16, stream));
+  uint8_t *a = ws, *b = in_place ? ws : ws + in_bytes;
+  int rc = launch_interleave(src, static_cast<int>(width), in_w, I, a, B, false, stream);
+  if (rc == CC_OK) rc = plain_route_dev(code, kind, a, d_er, d_off, b, d_nerr, d_status, B, stream);
+  if (rc == CC_OK) rc = launch_interleave(b, static_cast<int>(width), out_w, I, dst, B, true, stream);
+  (void)hipFreeAsync(ws, stream);
+  return rc;
+}
+
+// the _dev entry points: null pointers, the new refusals, the plain call's refusals, the call
+static int interleaved_entry_dev(const cc_code *code, int kind, int width, const void *d_src, const uint16_t *d_er,
+                                 const uint32_t *d_off, void *d_dst, int32_t *d_nerr, int32_t *d_status, size_t B, uint32_t I,
+                                 void *stream) {
+  if (!code || (B && (!d_src || !d_dst))) return CC_ERR_INVALID_ARGUMENT;
+  if ((d_er == nullptr) != (d_off == nullptr)) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = interleave_args(code, B, I)) return rc;
+  if (int rc = interleaved_ready(code, kind, width, d_er != nullptr)) return rc;
+  DeviceGuard guard(code->device);
+  return interleaved_dev(code, kind, d_src, d_er, d_off, d_dst, d_nerr, d_status, B, I, static_cast<hipStream_t>(stream));
+}
+
+int cc_encode_interleaved_batch_dev(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, uint32_t interleave,
+                                    void *stream) {
+  return interleaved_entry_dev(code, 0, 1, d_msg, nullptr, nullptr, d_cw, nullptr, nullptr, B, interleave, stream);
+}
+int cc_extract_interleaved_batch_dev(const cc_code *code, const uint8_t *d_cw, uint8_t *d_msg, size_t B, uint32_t interleave,
+                                     void *stream) {
+  return interleaved_entry_dev(code, 1, 1, d_cw, nullptr, nullptr, d_msg, nullptr, nullptr, B, interleave, stream);
+}
+int cc_correct_hard_interleaved_batch_dev(const cc_code *code, const uint8_t *d_in, const uint16_t *d_erasures,
+                                          const uint32_t *d_erasure_offsets, uint8_t *d_out, int32_t *d_nerr,
+                                          int32_t *d_status, size_t B, uint32_t interleave, void *stream) {
+  return interleaved_entry_dev(code, 2, 1, d_in, d_erasures, d_erasure_offsets, d_out, d_nerr, d_status, B, interleave, stream);
+}
+int cc_encode_interleaved_batch_u16_dev(const cc_code *code, const uint16_t *d_msg, uint16_t *d_cw, size_t B,
+                                        uint32_t interleave, void *stream) {
+  return interleaved_entry_dev(code, 0, 2, d_msg, nullptr, nullptr, d_cw, nullptr, nullptr, B, interleave, stream);
+}
+int cc_extract_interleaved_batch_u16_dev(const cc_code *code, const uint16_t *d_cw, uint16_t *d_msg, size_t B,
+                                         uint32_t interleave, void *stream) {
+  return interleaved_entry_dev(code, 1, 2, d_cw, nullptr, nullptr, d_msg, nullptr, nullptr, B, interleave, stream);
+}
+int cc_correct_hard_interleaved_batch_u16_dev(const cc_code *code, const uint16_t *d_in, const uint16_t *d_erasures,
+                                              const uint32_t *d_erasure_offsets, uint16_t *d_out, int32_t *d_nerr,
+                                              int32_t *d_status, size_t B, uint32_t interleave, void *stream) {
+  return interleaved_entry_dev(code, 2, 2, d_in, d_erasures, d_erasure_offsets, d_out, d_nerr, d_status, B, interleave, stream);
+}
+
+// host pointers: the chunked staging of the plain entry points, a chunk being whole blocks; the checks of symbol
+// values against the field and of erasure positions against n are the plain call's (the order of the symbols does not
+// matter to them)
+static int interleaved_host(const cc_code *code, int kind, int width, const void *src, const uint16_t *erasures,
+                            const uint32_t *erasure_offsets, void *dst, int32_t *nerr, int32_t *status, size_t B, uint32_t I) {
+  if (!code || (B && (!src || !dst))) return CC_ERR_INVALID_ARGUMENT;
+  if ((erasures == nullptr) != (erasure_offsets == nullptr)) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = interleave_args(code, B, I)) return rc;
+  if (int rc = interleaved_ready(code, kind, width, erasures != nullptr)) return rc;
+  if (B == 0) return CC_OK;
+  const size_t n = code->tab.n, l = code->tab.l, w = static_cast<size_t>(width);
+  const size_t in_w = kind == 0 ? l : n, out_w = kind == 1 ? l : n;
+  if (kind != 1) {  // Element(v) throws for v outside the field, galois.h:149-152
+    const uint32_t top = (1u << code->tab.q) - 1;
+    if (width == 2) {
+      const uint16_t *v = static_cast<const uint16_t *>(src);
+      for (size_t i = 0; i < B * in_w; ++i)
+        if (v[i] > top) return CC_ERR_NOT_IN_FIELD;
+    } else {
+      const uint8_t *v = static_cast<const uint8_t *>(src);
+      for (size_t i = 0; i < B * in_w; ++i)
+        if (v[i] > top) return CC_ERR_NOT_IN_FIELD;
+    }
+  }
+  if (erasures) {
+    const size_t ne = erasure_offsets[B];
+    for (size_t e = 0; e < ne; ++e)
+      if (erasures[e] >= n) return CC_ERR_INVALID_ARGUMENT;
+  }
+  DeviceGuard guard(code->device);
+  StageLock sl(code);
+  if (sl.rc != CC_OK) return sl.rc;
+  HostStage &st = *sl.st;
+  size_t CH = chunk_frames(n * w, B) / I * I;  // whole blocks
+  if (CH < I) CH = I;
+  if (B > 2 * CH)
+    if (int rc_fs = st.fresh_streams()) return rc_fs;
+  const bool dma_in = HostStage::dma_ready(src), dma_out = HostStage::dma_ready(dst),
+             dma_ne = nerr && HostStage::dma_ready(nerr), dma_st = status && HostStage::dma_ready(status);
+  const uint8_t *sb = static_cast<const uint8_t *>(src);
+  uint8_t *db = static_cast<uint8_t *>(dst);
+  size_t k = 0;
+  for (size_t c0 = 0; c0 < B; c0 += CH, ++k) {
+    const int slot = static_cast<int>(k & 1);
+    const size_t m = B - c0 < CH ? B - c0 : CH;
+    hipStream_t s = st.stream[slot];
+    if (int r = st.retire(slot)) return r;
+    uint8_t *d_src = nullptr, *d_dst = nullptr;
+    int32_t *d_nerr = nullptr, *d_status = nullptr;
+    const uint16_t *d_er = nullptr;
+    const uint32_t *d_off = nullptr;
+    if (int r = st.get(slot, 0, m * in_w * w, &d_src)) return r;
+    if (int r = st.get(slot, 1, m * out_w * w, &d_dst)) return r;
+    if (int r = st.upload(slot, 0, d_src, sb + c0 * in_w * w, m * in_w * w, dma_in)) return r;
+    if (kind == 2) {
+      if (int r = st.get(slot, 2, m, &d_nerr)) return r;
+      if (int r = st.get(slot, 3, m, &d_status)) return r;
+      if (int r = upload_erasures(st, slot, 5, erasures, erasure_offsets, c0, m, &d_er, &d_off)) return r;
+    }
+    if (int r = interleaved_dev(code, kind, d_src, d_er, d_off, d_dst, d_nerr, d_status, m, I, s)) return r;
+    if (int r = st.download(slot, 1, db + c0 * out_w * w, d_dst, m * out_w * w, dma_out)) return r;
+    if (nerr)
+      if (int r = st.download(slot, 2, nerr + c0, d_nerr, m * sizeof(int32_t), dma_ne)) return r;
+    if (status)
+      if (int r = st.download(slot, 3, status + c0, d_status, m * sizeof(int32_t), dma_st)) return r;
+  }
+  return st.drain();
+}
+
+int cc_encode_interleaved_batch(const cc_code *code, const uint8_t *msg, uint8_t *cw, size_t B, uint32_t interleave) {
+  return interleaved_host(code, 0, 1, msg, nullptr, nullptr, cw, nullptr, nullptr, B, interleave);
+}
+int cc_extract_interleaved_batch(const cc_code *code, const uint8_t *cw, uint8_t *msg, size_t B, uint32_t interleave) {
+  return interleaved_host(code, 1, 1, cw, nullptr, nullptr, msg, nullptr, nullptr, B, interleave);
+}
+int cc_correct_hard_interleaved_batch(const cc_code *code, const uint8_t *in, const uint16_t *erasures,
+                                      const uint32_t *erasure_offsets, uint8_t *out, int32_t *nerr, int32_t *status, size_t B,
+                                      uint32_t interleave) {
+  return interleaved_host(code, 2, 1, in, erasures, erasure_offsets, out, nerr, status, B, interleave);
+}
+int cc_encode_interleaved_batch_u16(const cc_code *code, const uint16_t *msg, uint16_t *cw, size_t B, uint32_t interleave) {
+  return interleaved_host(code, 0, 2, msg, nullptr, nullptr, cw, nullptr, nullptr, B, interleave);
+}
+int cc_extract_interleaved_batch_u16(const cc_code *code, const uint16_t *cw, uint16_t *msg, size_t B, uint32_t interleave) {
+  return interleaved_host(code, 1, 2, cw, nullptr, nullptr, msg, nullptr, nullptr, B, interleave);
+}
+int cc_correct_hard_interleaved_batch_u16(const cc_code *code, const uint16_t *in, const uint16_t *erasures,
+                                          const uint32_t *erasure_offsets, uint16_t *out, int32_t *nerr, int32_t *status,
+                                          size_t B, uint32_t interleave) {
+  return interleaved_host(code, 2, 2, in, erasures, erasure_offsets, out, nerr, status, B, interleave);
+}
+
+int cc_decode_hard_interleaved_batch(const cc_code *code, const uint8_t *in, const uint16_t *erasures,
+                                     const uint32_t *erasure_offsets, uint8_t *msg, uint8_t *words, int32_t *nerr,
+                                     int32_t *status, size_t B, uint32_t interleave) {
+  if (!code || (B && (!in || !msg))) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = interleave_args(code, B, interleave)) return rc;
+  if (int rc = not_wide(code)) return rc;
+  if (code->soft) {  // (as cc_decode_hard_batch)
+    set_last_error("min-sum needs a signed (soft) input sequence");
+    return CC_ERR_INVALID_ARGUMENT;
+  }
+  std::vector<uint8_t> tmp;
+  if (!words && B) {
+    tmp.resize(B * code->tab.n);
+    words = tmp.data();
+  }
+  if (int rc = cc_correct_hard_interleaved_batch(code, in, erasures, erasure_offsets, words, nerr, status, B, interleave)) return rc;
+  return cc_extract_interleaved_batch(code, words, msg, B, interleave);
 }
 
 /* ------------------------------ Monte-Carlo ------------------------------ */

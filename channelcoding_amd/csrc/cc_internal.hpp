@@ -196,15 +196,16 @@ int launch_algebraic(const cc_code *code, bool float_in, const void *d_in, const
                      hipStream_t stream);
 // algebraic_chunk.hip: BM / PGZ without erasures, Berlekamp-Massey with one lane per frame
 bool algebraic_chunk_supported(const cc_code *code, bool erasures);
+// il > 1 (bit-plane chain without erasures only): d_in and d_out are symbol-interleaved blocks of depth il
 int launch_algebraic_chunk(const cc_code *code, bool float_in, const void *d_in, const uint16_t *d_er,
                            const uint32_t *d_er_off, uint8_t *d_out, int32_t *d_nerr, int32_t *d_status, size_t B,
-                           hipStream_t stream);
+                           hipStream_t stream, int il = 1);
 // bitslice.hip: syndromes of GF(2^8) codes on bit planes (32 frames per register)
 bool bitslice_supported(const cc_code *code);
 int launch_bitslice_syndromes(const cc_code *code, bool float_in, const void *d_in, uint8_t *d_out, uint8_t *d_synd, size_t B,
-                              hipStream_t stream);
+                              hipStream_t stream, int il = 1);
 bool bitslice_encode_supported(const cc_code *code);
-int launch_bitslice_encode(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, hipStream_t stream);
+int launch_bitslice_encode(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, hipStream_t stream, int il = 1);
 // the stages of the bit-plane chain that the packed chain (packed.hip) shares with the byte chain
 int launch_bitslice_chien(const void *d_lamp, void *d_masks, size_t B, bool long_locators, hipStream_t stream);
 int launch_bitslice_roots_transpose(const void *d_masks, void *d_rootsT, size_t B, hipStream_t stream);
@@ -246,6 +247,15 @@ bool packed_encode_native(const cc_code *code);   // division coding, n - l <= 3
 bool packed_extract_native(const cc_code *code);  // division coding, any q
 int launch_packed_encode(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, hipStream_t stream);
 int launch_packed_extract(const cc_code *code, const uint8_t *d_cw, uint8_t *d_msg, size_t B, hipStream_t stream);
+// interleave.hip: I codewords woven symbol by symbol, symbol p of frame b I + j at b I n + p I + j
+constexpr size_t kInterleaveMax = 256;        // depths the interface takes
+constexpr size_t kInterleaveNativeMax = 16;   // depths the bit-plane chain addresses itself
+int launch_interleave(const void *d_in, int width, size_t n, size_t I, void *d_out, size_t B, bool to_interleaved,
+                      hipStream_t stream);
+bool interleaved_native_supported(const cc_code *code, size_t B, size_t I, bool erasures);
+bool interleaved_encode_native(const cc_code *code, size_t I);   // where bitslice_encode_supported holds
+bool interleaved_extract_native(const cc_code *code, size_t I);  // division coding, any q
+int launch_interleaved_extract(const cc_code *code, const void *d_cw, void *d_msg, size_t B, size_t I, hipStream_t stream);
 // mc.hip (Monte-Carlo calls on one handle must be issued on one stream at a time: they share a workspace)
 int mc_run(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
            uint64_t *d_counters, hipStream_t stream);

@@ -354,6 +354,70 @@ int cc_decode_hard_packed_batch(const cc_code *code, const uint8_t *in, const ui
                                 const uint32_t *erasure_offsets, uint8_t *msg, uint8_t *words, int32_t *nerr,
                                 int32_t *status, size_t B);
 
+/* ---- symbol-interleaved blocks: codewords as deployed Reed-Solomon systems store them (an OTU row of ITU-T G.709:
+ *      16 byte-interleaved RS(255,239) words; CCSDS RS(255,223) at depth 1 .. 5 or 8; the columns of a product code).
+ *      A call of depth I (`interleave`, 1 <= I <= 256) and B frames, B a multiple of I: block b holds the frames
+ *      f = b I + j, j = 0 .. I-1, and symbol p of frame f (index p = coefficient of x^p, as everywhere in this API) is at
+ *      symbol index b I n + p I + j of the buffer -- the array [B / I][n][I] read contiguously.  A shortened code uses
+ *      its own n = N; interleaved messages are the same with l in place of n.  nerr, status and the erasure CSR
+ *      (erasure_offsets[f] .. [f+1], positions 0 .. n-1 within the codeword) are indexed by f, as in the plain calls.
+ *      A stream stored highest power first is this layout read backwards (p -> n-1-p, j -> I-1-j): reverse the buffer,
+ *      there is no reversed variant.
+ *      Contract: for every frame, de-interleaving the output of an interleaved call gives symbol for symbol what the
+ *      plain call (cc_encode_batch, cc_correct_hard_batch, cc_extract_batch, cc_decode_hard_batch, their _u16 and _dev
+ *      forms) returns for the de-interleaved input, with identical nerr and status -- failing frames (out = the
+ *      received word), every CC_FRAME_* class, the shortened-code rule, the two-trial PGZ rule with erasures, the RS
+ *      root conventions (cc_desc.mu / step), the checks of symbol values and erasure positions, and out == in included.
+ *      Every refusal of the plain call is the interleaved call's, with the same status and cc_last_error text, before a
+ *      device is asked for.  CC_ERR_INVALID_ARGUMENT in addition: I = 0, I > 256, B not a multiple of I, a handle of
+ *      cc_minsum_create.  Depth 1 is the plain call.
+ *      Routes: hard-decode calls the plain router would send down the bit-plane chain of GF(2^8)
+ *      without an erasure list are decoded from the interleaved block natively for I = 2 .. 16 (no de-interleaved copy
+ *      of the words exists), RS(255, 255 - 2t) with 2t = 16 or 32 is encoded the same way, division-coded words are
+ *      extracted by a strided copy (any q); every other call is de-interleaved into workspace of the handle, sent
+ *      through the plain router and interleaved again.  CC_AMD_INTERLEAVED_NATIVE=0 (read once) sends everything the
+ *      second way.  Not offered interleaved: min-sum, the f32 hard entry points, the Monte-Carlo calls, packed words. ---- */
+/* 1: a hard-decode call of B frames at depth I takes the native route under the settings in force (depth 1: the plain
+ * call, reported as 1), 0: the generic one; a negative cc_status where the call itself would be refused */
+int cc_interleaved_route(const cc_code *code, size_t B, uint32_t interleave, int with_erasures);
+/* the same for the encode (which = 0) and extract (which = 1) calls */
+int cc_interleaved_map_route(const cc_code *code, int which, uint32_t interleave);
+/* frame-major [B][n] -> interleaved [B / I][n][I] and back, symbols of width 1 or 2 bytes, on the current device; d_out
+ * must not be d_in; exactly B * n symbols are touched.  No handle is needed. */
+int cc_interleave_dev(const void *d_in, int width, size_t n, uint32_t interleave, void *d_out, size_t B, void *stream);
+int cc_deinterleave_dev(const void *d_in, int width, size_t n, uint32_t interleave, void *d_out, size_t B, void *stream);
+int cc_encode_interleaved_batch(const cc_code *code, const uint8_t *msg /* B*l */, uint8_t *cw /* B*n */, size_t B,
+                                uint32_t interleave);
+int cc_encode_interleaved_batch_dev(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, uint32_t interleave,
+                                    void *stream);
+int cc_correct_hard_interleaved_batch(const cc_code *code, const uint8_t *in /* B*n */, const uint16_t *erasures,
+                                      const uint32_t *erasure_offsets, uint8_t *out /* B*n */, int32_t *nerr,
+                                      int32_t *status, size_t B, uint32_t interleave);
+int cc_correct_hard_interleaved_batch_dev(const cc_code *code, const uint8_t *d_in, const uint16_t *d_erasures,
+                                          const uint32_t *d_erasure_offsets, uint8_t *d_out, int32_t *d_nerr,
+                                          int32_t *d_status, size_t B, uint32_t interleave, void *stream);
+int cc_extract_interleaved_batch(const cc_code *code, const uint8_t *cw /* B*n */, uint8_t *msg /* B*l */, size_t B,
+                                 uint32_t interleave);
+int cc_extract_interleaved_batch_dev(const cc_code *code, const uint8_t *d_cw, uint8_t *d_msg, size_t B, uint32_t interleave,
+                                     void *stream);
+/* correct + extract as cc_decode_hard_batch: msg is an interleaved block of messages, words (interleaved) may be NULL */
+int cc_decode_hard_interleaved_batch(const cc_code *code, const uint8_t *in, const uint16_t *erasures,
+                                     const uint32_t *erasure_offsets, uint8_t *msg, uint8_t *words, int32_t *nerr,
+                                     int32_t *status, size_t B, uint32_t interleave);
+/* q = 9 .. 15: 16-bit symbols */
+int cc_encode_interleaved_batch_u16(const cc_code *code, const uint16_t *msg, uint16_t *cw, size_t B, uint32_t interleave);
+int cc_encode_interleaved_batch_u16_dev(const cc_code *code, const uint16_t *d_msg, uint16_t *d_cw, size_t B,
+                                        uint32_t interleave, void *stream);
+int cc_correct_hard_interleaved_batch_u16(const cc_code *code, const uint16_t *in, const uint16_t *erasures,
+                                          const uint32_t *erasure_offsets, uint16_t *out, int32_t *nerr, int32_t *status,
+                                          size_t B, uint32_t interleave);
+int cc_correct_hard_interleaved_batch_u16_dev(const cc_code *code, const uint16_t *d_in, const uint16_t *d_erasures,
+                                              const uint32_t *d_erasure_offsets, uint16_t *d_out, int32_t *d_nerr,
+                                              int32_t *d_status, size_t B, uint32_t interleave, void *stream);
+int cc_extract_interleaved_batch_u16(const cc_code *code, const uint16_t *cw, uint16_t *msg, size_t B, uint32_t interleave);
+int cc_extract_interleaved_batch_u16_dev(const cc_code *code, const uint16_t *d_cw, uint16_t *d_msg, size_t B,
+                                         uint32_t interleave, void *stream);
+
 /* ---- introspection for the benchmark: name and launch geometry of the kernel a call would use ---- */
 int cc_kernel_info(const cc_code *code, char *name, size_t cap, uint32_t *frames_per_workgroup,
                    uint32_t *threads_per_workgroup, uint32_t *lds_bytes);
