@@ -4,18 +4,16 @@
 // entry points stage through device memory and call the _dev ones; there is no
 // CPU decode path in this library.
 #include <algorithm>
-#include <atomic>
 #include <cmath>
-#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
 #include <stdexcept>
-#include <thread>
 #include <vector>
 
 #include "cc_internal.hpp"
+#include "host_stage.hpp"
 
 namespace ccamd {
 
@@ -25,6 +23,7 @@ int hip_fail(hipError_t e, const char *what) {
   g_last_error = std::string(what) + ": " + hipGetErrorString(e);
   return CC_ERR_HIP;
 }
+void host_stage_free(HostStage *st) { delete st; }  // (the destructor waits for the streams and frees the buffers)
 
 namespace {
 
@@ -42,265 +41,26 @@ struct DeviceGuard {
   }
 };
 
-}  // namespace (anonymous)
-// Staging of the host-pointer entry points ("no hidden allocation per call; thread-safe per
-// stream").  Owned by the handle, created on first use: two private streams and, per stream, grow-only device
-// buffers.  A host-pointer call cuts the batch into chunks that alternate between the two streams -- the upload of
-// chunk k + 1 overlaps the kernel and the download of chunk k -- and waits for ITS streams only
-// (hipStreamSynchronize, never hipDeviceSynchronize: other streams of the caller keep running).  Calls on one
-// handle are serialised by `lock`; different handles are independent.
-// Copies between pageable caller memory and the page-locked staging ring are plain memcpy calls spread over a few
-// worker threads (one thread moves ~10 GB/s, the DMA engine 55 GB/s; round 2 handed pageable pointers to
-// hipMemcpyAsync, which then blocks the calling thread until the data has moved and with it the pipeline:
-// profiles/r02_host_path.txt, 49 ms for what upload and kernel together should do in 31).  Process-wide, created on
-// first use, never joined (the workers touch no HIP state and sleep on a condition variable).
-class CopyPool {
- public:
-  static CopyPool &get() {
-    static CopyPool *pool = new CopyPool();
-    return *pool;
-  }
-  void copy(void *dst, const void *src, size_t bytes) {
-    const size_t piece = 4u << 20;
-    if (bytes <= piece || workers_ == 0) {
-      std::memcpy(dst, src, bytes);
-      return;
-    }
-    const size_t parts = std::min<size_t>((bytes + piece - 1) / piece, static_cast<size_t>(workers_) + 1);
-    const size_t each = ((bytes + parts - 1) / parts + 4095) & ~static_cast<size_t>(4095);
-    std::atomic<int> left{0};
-    std::mutex dm;
-    std::condition_variable dcv;
-    size_t off = each;  // the caller's own share is [0, each)
-    {
-      std::lock_guard<std::mutex> g(m_);
-      for (; off < bytes; off += each) {
-        const size_t len = std::min(each, bytes - off);
-        ++left;
-        jobs_.push_back(Job{static_cast<char *>(dst) + off, static_cast<const char *>(src) + off, len, &left, &dm, &dcv});
-      }
-    }
-    cv_.notify_all();
-    std::memcpy(dst, src, std::min(each, bytes));
-    std::unique_lock<std::mutex> lk(dm);
-    dcv.wait(lk, [&] { return left.load() == 0; });
-  }
-
- private:
-  struct Job {
-    char *dst;
-    const char *src;
-    size_t len;
-    std::atomic<int> *left;
-    std::mutex *dm;
-    std::condition_variable *dcv;
-  };
-  CopyPool() {
-    const unsigned hc = std::thread::hardware_concurrency();
-    workers_ = hc >= 16 ? 7 : hc >= 8 ? 5 : hc >= 4 ? 2 : 0;  // 3 / 7 / 15 workers: 35 / 33 / 32 ms per 2^20 frames at 4 dB
-    for (int i = 0; i < workers_; ++i) std::thread([this] { run(); }).detach();
-  }
-  void run() {
-    for (;;) {
-      Job j;
-      {
-        std::unique_lock<std::mutex> lk(m_);
-        cv_.wait(lk, [&] { return !jobs_.empty(); });
-        j = jobs_.back();
-        jobs_.pop_back();
-      }
-      std::memcpy(j.dst, j.src, j.len);
-      {
-        std::lock_guard<std::mutex> g(*j.dm);  // the waiter cannot leave (and destroy dm / dcv) between the two lines
-        if (j.left->fetch_sub(1) == 1) j.dcv->notify_one();
-      }
-    }
-  }
-  std::mutex m_;
-  std::condition_variable cv_;
-  std::vector<Job> jobs_;
-  int workers_ = 0;
-};
-
-struct HostStage {
-  std::mutex lock;
-  hipStream_t stream[2] = {nullptr, nullptr};
-  struct Buf {
-    void *p = nullptr;
-    size_t cap = 0;
-  };
-  Buf buf[2][8];
-  Buf pin[2][8];  // page-locked twins of buf for pageable caller memory (same slot / index)
-  struct Pending {
-    void *dst;
-    const void *src;
-    size_t bytes;
-  };
-  std::vector<Pending> pending[2];  // results waiting in pin[slot][*] for their stream to finish
-  int init() {
-    for (hipStream_t &s : stream)
-      if (!s) CC_HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    return CC_OK;
-  }
-  // A call of several chunks starts on a fresh pair of streams.  Measured (profiles/r03_host_path.txt,
-  // profiles/tools/host_path_trace.py): once a stream pair has been through a call whose chunks were fed from the host
-  // side with gaps (pageable caller memory), every later call on that pair runs its copies and kernels one after the
-  // other -- 46 ms for 2^20 frames at 4 dB where the same call on new streams takes 25 -- for the rest of the process;
-  // rocprofv3's copy trace shows the transfers of the fast case on the DMA engines next to the kernels.  Creating two
-  // streams costs ~40 us, so calls of one or two chunks (below ~64 MiB) keep the pair they have.
-  int fresh_streams() {
-    for (hipStream_t &s : stream)
-      if (s) {
-        CC_HIP_TRY(hipStreamSynchronize(s));
-        CC_HIP_TRY(hipStreamDestroy(s));
-        s = nullptr;
-      }
-    return init();
-  }
-  template <typename T>
-  int get(int slot, int idx, size_t count, T **out) {  // grow-only; contents are not preserved
-    Buf &b = buf[slot][idx];
-    const size_t bytes = count * sizeof(T) + 16;
-    if (bytes > b.cap) {
-      CC_HIP_TRY(hipStreamSynchronize(stream[slot]));
-      if (b.p) (void)hipFree(b.p);
-      b.p = nullptr;
-      b.cap = 0;
-      const size_t want = bytes + bytes / 4;  // grow by 25 % so that slowly growing batches do not reallocate each time
-      CC_HIP_TRY(hipMalloc(&b.p, want));
-      b.cap = want;
-    }
-    *out = static_cast<T *>(b.p);
-    return CC_OK;
-  }
-  int get_pinned(int slot, int idx, size_t bytes, void **out) {
-    Buf &b = pin[slot][idx];
-    if (bytes > b.cap) {
-      if (b.p) (void)hipHostFree(b.p);
-      b.p = nullptr;
-      b.cap = 0;
-      const size_t want = bytes + bytes / 4;
-      CC_HIP_TRY(hipHostMalloc(&b.p, want, hipHostMallocDefault));
-      b.cap = want;
-    }
-    *out = b.p;
-    return CC_OK;
-  }
-  // is the caller's buffer something the DMA engines reach directly (page-locked / registered / device memory)?
-  static bool dma_ready(const void *p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-      (void)hipGetLastError();  // plain malloc'ed memory: "invalid value", not an error of ours
-      return false;
-    }
-    return a.type == hipMemoryTypeHost || a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-  }
-  // host -> device on the slot's stream; `direct` = dma_ready(h_src base), decided once per call
-  int upload(int slot, int idx, void *d_dst, const void *h_src, size_t bytes, bool direct) {
-    if (bytes == 0) return CC_OK;
-    if (!direct) {
-      void *ring = nullptr;
-      if (int rc = get_pinned(slot, idx, bytes, &ring)) return rc;
-      CopyPool::get().copy(ring, h_src, bytes);
-      h_src = ring;
-    }
-    CC_HIP_TRY(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, stream[slot]));
-    return CC_OK;
-  }
-  // device -> host behind the slot's kernels; a pageable destination receives its bytes in retire()
-  int download(int slot, int idx, void *h_dst, const void *d_src, size_t bytes, bool direct) {
-    if (bytes == 0) return CC_OK;
-    if (direct) {
-      CC_HIP_TRY(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, stream[slot]));
-      return CC_OK;
-    }
-    void *ring = nullptr;
-    if (int rc = get_pinned(slot, idx, bytes, &ring)) return rc;
-    CC_HIP_TRY(hipMemcpyAsync(ring, d_src, bytes, hipMemcpyDeviceToHost, stream[slot]));
-    pending[slot].push_back(Pending{h_dst, ring, bytes});
-    return CC_OK;
-  }
-  // wait for everything enqueued on the slot and hand its staged results to the caller's buffers
-  int retire(int slot) {
-    if (!stream[slot]) return CC_OK;
-    const hipError_t e = hipStreamSynchronize(stream[slot]);
-    if (e == hipSuccess)
-      for (const Pending &q : pending[slot]) CopyPool::get().copy(q.dst, q.src, q.bytes);
-    pending[slot].clear();
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize (host staging)");
-    return CC_OK;
-  }
-  int drain() {
-    const int a = retire(0), b = retire(1);
-    return a != CC_OK ? a : b;
-  }
-};
-void host_stage_free(HostStage *st) {
-  if (!st) return;
-  for (int slot = 0; slot < 2; ++slot) {
-    if (st->stream[slot]) (void)hipStreamSynchronize(st->stream[slot]);
-    for (HostStage::Buf &b : st->buf[slot])
-      if (b.p) (void)hipFree(b.p);
-    for (HostStage::Buf &b : st->pin[slot])
-      if (b.p) (void)hipHostFree(b.p);
-    if (st->stream[slot]) (void)hipStreamDestroy(st->stream[slot]);
-  }
-  delete st;
-}
-namespace {
-
-// the handle's staging object (created on first use) with its lock held for the duration of one host-pointer call
-struct StageLock {
-  HostStage *st = nullptr;
-  std::unique_lock<std::mutex> held;
-  int rc = CC_OK;
-  explicit StageLock(const cc_code *code) {
-    {
-      std::lock_guard<std::mutex> g(code->lazy_lock);
-      if (!code->stage) code->stage = new HostStage();
-      st = code->stage;
-    }
-    held = std::unique_lock<std::mutex>(st->lock);
-    rc = st->init();
-  }
-  // every way out of a host-pointer call, error paths included, leaves nothing in flight that still writes to the
-  // caller's buffers or reads the staging buffers (a second wait on idle streams costs microseconds)
-  ~StageLock() {
-    if (st && held.owns_lock()) (void)st->drain();
-  }
-};
-// frames per chunk: about 32 MiB of the widest per-frame stream, at least 16 frames
-size_t chunk_frames(size_t bytes_per_frame, size_t B) {
-  static const size_t chunk_bytes = [] {  // CC_AMD_HOST_CHUNK_BYTES: tests force many small chunks
-    const char *e = std::getenv("CC_AMD_HOST_CHUNK_BYTES");
-    const long long v = e ? std::atoll(e) : 0;
-    return v > 0 ? static_cast<size_t>(v) : static_cast<size_t>(32u << 20);
-  }();
-  size_t ch = chunk_bytes / (bytes_per_frame ? bytes_per_frame : 1);
-  if (ch < 16) ch = 16;
-  return ch < B ? ch : B;
-}
-// uploads the erasure lists of frames [c0, c0 + m) and returns device pointers with which the kernels index them
-// by the GLOBAL offsets: d_er is shifted back by off[c0] elements (only [off[c0], off[c0 + m]) is ever read)
-int upload_erasures(HostStage &st, int slot, int idx, const uint16_t *erasures, const uint32_t *offsets, size_t c0,
-                    size_t m, const uint16_t **d_er, const uint32_t **d_off) {
-  *d_er = nullptr;
-  *d_off = nullptr;
-  if (!erasures) return CC_OK;
-  const size_t e0 = offsets[c0], ne = offsets[c0 + m] - e0;
-  uint16_t *er = nullptr;
-  uint32_t *off = nullptr;
-  if (int rc = st.get(slot, idx, ne + 1, &er)) return rc;
-  if (int rc = st.get(slot, idx + 1, m + 1, &off)) return rc;
-  if (ne) CC_HIP_TRY(hipMemcpyAsync(er, erasures + e0, ne * sizeof(uint16_t), hipMemcpyHostToDevice, st.stream[slot]));
-  CC_HIP_TRY(hipMemcpyAsync(off, offsets + c0, (m + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st.stream[slot]));
-  *d_er = er - e0;
-  *d_off = off;
-  return CC_OK;
-}
-
 bool is_soft(int alg) { return alg >= CC_ALG_MS && alg <= CC_ALG_2DNMS; }
 bool is_hard(int alg) { return alg >= CC_ALG_PGZ && alg <= CC_ALG_EUKLID; }
+
+// the input checks of the host-pointer entry points
+// erasure positions < n: copy.at(erasure) would throw, cyclic.h:261
+bool erasures_in_range(const uint16_t *erasures, const uint32_t *offsets, size_t B, size_t n) {
+  if (!erasures) return true;
+  const size_t ne = offsets[B];
+  for (size_t e = 0; e < ne; ++e)
+    if (erasures[e] >= n) return false;
+  return true;
+}
+// symbols inside GF(2^q): Element(v) throws for v outside the field, galois.h:149-152 (encode: via cyclic.h:300-301)
+template <typename T>
+bool symbols_in_field(const T *p, size_t count, unsigned q) {
+  const uint32_t top = (1u << q) - 1;
+  for (size_t i = 0; i < count; ++i)
+    if (p[i] > top) return false;
+  return true;
+}
 
 const char *alg_name(int alg) {
   switch (alg) {  // Algorithm::to_string(): hard_decision.h:15-24, soft_decision.h:20-73
@@ -315,6 +75,57 @@ const char *alg_name(int alg) {
     case CC_ALG_2DNMS: return "2DNMS";
     default: return "?";
   }
+}
+
+// The router of the byte / 16-bit _dev entry points on frame-major device buffers: kind 0 = encode, 1 = extract,
+// 2 = correct.  The generic routes of the packed and of the interleaved calls go through it.
+int plain_route_dev(const cc_code *code, int kind, const uint8_t *a, const uint16_t *d_er, const uint32_t *d_off, uint8_t *b,
+                           int32_t *d_nerr, int32_t *d_status, size_t B, hipStream_t stream) {
+  if (code->wide) {
+    const uint16_t *a16 = reinterpret_cast<const uint16_t *>(a);
+    uint16_t *b16 = reinterpret_cast<uint16_t *>(b);
+    return kind == 0   ? launch_wide_encode(code, a16, b16, B, stream)
+           : kind == 1 ? launch_wide_extract(code, a16, b16, B, stream)
+                       : launch_wide_correct(code, a16, d_er, d_off, b16, d_nerr, d_status, B, stream);
+  }
+  if (kind == 0) return launch_encode(code, a, b, B, stream);
+  if (kind == 1) return launch_extract(code, a, b, B, stream);
+  if (d_er && code->desc.algorithm == CC_ALG_PGZ) return launch_pgz_erasures(code, a, d_er, d_off, b, d_nerr, d_status, B, stream);
+  return launch_algebraic(code, false, a, d_er, d_off, b, d_nerr, d_status, B, stream);
+}
+
+// The generic route of a packed and of an interleaved call (kind as plain_route_dev): convert_in(a, in_w, width) brings
+// the caller's words into workspace of the handle's pool as frame-major symbols (bytes, 16-bit words for q > 8), the
+// plain router runs on them, convert_out(b, out_w, width) brings the result into the caller's form.
+template <typename ConvertIn, typename ConvertOut>
+int through_workspace(const cc_code *code, int kind, ConvertIn convert_in, ConvertOut convert_out, const uint16_t *d_er,
+                      const uint32_t *d_off, int32_t *d_nerr, int32_t *d_status, size_t B, hipStream_t stream) {
+  if (B == 0) return CC_OK;
+  const size_t n = code->tab.n, l = code->tab.l, width = code->wide ? 2 : 1;
+  const size_t in_w = kind == 0 ? l : n, out_w = kind == 1 ? l : n;
+  // words without erasures are corrected in place, as a byte call with out == in (it then skips its copy of the words)
+  const bool in_place = kind == 2 && !d_er && !code->wide;
+  const size_t in_bytes = (B * in_w * width + 255) & ~static_cast<size_t>(255);
+  uint8_t *ws = nullptr;
+  CC_HIP_TRY(workspace_alloc(code, reinterpret_cast<void **>(&ws), in_bytes + (in_place ? 0 : B * out_w * width) + 16, stream));
+  uint8_t *a = ws, *b = in_place ? ws : ws + in_bytes;
+  int rc = convert_in(a, in_w, static_cast<int>(width));
+  if (rc == CC_OK) rc = plain_route_dev(code, kind, a, d_er, d_off, b, d_nerr, d_status, B, stream);
+  if (rc == CC_OK) rc = convert_out(b, out_w, static_cast<int>(width));
+  (void)hipFreeAsync(ws, stream);
+  return rc;
+}
+
+// decode = correct + extract: the corrected words go to the caller's `words` or to a temporary of word_bytes per frame
+template <typename Correct, typename Extract>
+int correct_then_extract(size_t B, size_t word_bytes, uint8_t *words, Correct correct, Extract extract) {
+  std::vector<uint8_t> tmp;
+  if (!words && B) {
+    tmp.resize(B * word_bytes);
+    words = tmp.data();
+  }
+  if (int rc = correct(words)) return rc;
+  return extract(words);
 }
 
 }  // namespace
@@ -806,52 +617,17 @@ int cc_correct_soft_batch(const cc_code *code, const float *llr, const uint16_t 
   if (code->device == CC_DEVICE_NONE) return CC_ERR_NO_DEVICE;
   if (B == 0) return CC_OK;
   const size_t n = code->tab.n;
-  if (erasures) {
-    const size_t ne = erasure_offsets[B];
-    for (size_t e = 0; e < ne; ++e)
-      if (erasures[e] >= n) return CC_ERR_INVALID_ARGUMENT;  // copy.at(erasure) would throw, cyclic.h:261
-  }
+  if (!erasures_in_range(erasures, erasure_offsets, B, n)) return CC_ERR_INVALID_ARGUMENT;
   DeviceGuard guard(code->device);
-  StageLock sl(code);
-  if (sl.rc != CC_OK) return sl.rc;
-  HostStage &st = *sl.st;
-  const size_t CH = chunk_frames(n * sizeof(float), B);
-  if (B > 2 * CH)
-    if (int rc_fs = st.fresh_streams()) return rc_fs;
-  // pageable caller memory goes through the page-locked ring (HostStage::upload / download); buffers the DMA engines
-  // reach themselves (hipHostMalloc, hipHostRegister) are used in place
-  const bool dma_in = HostStage::dma_ready(llr), dma_out = HostStage::dma_ready(hard),
-             dma_it = iters && HostStage::dma_ready(iters), dma_st = status && HostStage::dma_ready(status);
-  size_t k = 0;
-  for (size_t c0 = 0; c0 < B; c0 += CH, ++k) {
-    const int slot = static_cast<int>(k & 1);
-    const size_t m = B - c0 < CH ? B - c0 : CH;
-    hipStream_t s = st.stream[slot];
-    if (int rc = st.retire(slot)) return rc;  // the chunk that used this slot's buffers two turns ago is home
-    float *d_llr = nullptr, *d_L = nullptr;
-    uint8_t *d_hard = nullptr;
-    uint16_t *d_iters = nullptr;
-    int32_t *d_status = nullptr;
-    const uint16_t *d_er = nullptr;
-    const uint32_t *d_off = nullptr;
-    if (int rc = st.get(slot, 0, m * n, &d_llr)) return rc;
-    if (int rc = st.get(slot, 1, m * n, &d_hard)) return rc;
-    if (int rc = st.get(slot, 2, m, &d_iters)) return rc;
-    if (int rc = st.get(slot, 3, m, &d_status)) return rc;
-    if (L)
-      if (int rc = st.get(slot, 4, m * n, &d_L)) return rc;
-    if (int rc = st.upload(slot, 0, d_llr, llr + c0 * n, m * n * sizeof(float), dma_in)) return rc;
-    if (int rc = upload_erasures(st, slot, 5, erasures, erasure_offsets, c0, m, &d_er, &d_off)) return rc;
-    if (int rc = launch_minsum(code, d_llr, d_er, d_off, d_hard, d_L, d_iters, d_status, m, s)) return rc;
-    if (int rc = st.download(slot, 1, hard + c0 * n, d_hard, m * n, dma_out)) return rc;
-    if (L)
-      if (int rc = st.download(slot, 4, L + c0 * n, d_L, m * n * sizeof(float), HostStage::dma_ready(L))) return rc;
-    if (iters)
-      if (int rc = st.download(slot, 2, iters + c0, d_iters, m * sizeof(uint16_t), dma_it)) return rc;
-    if (status)
-      if (int rc = st.download(slot, 3, status + c0, d_status, m * sizeof(int32_t), dma_st)) return rc;
-  }
-  return st.drain();
+  // (iters and status get device buffers whether wanted or not: the kernels write them; L only when wanted)
+  const StagedStream streams[] = {stage_in(0, llr, n * sizeof(float)), stage_out(1, hard, n), stage_out(2, iters, sizeof(uint16_t)),
+                                  stage_out(3, status, sizeof(int32_t)), stage_out(4, L, n * sizeof(float))};
+  return staged_call(code, B, n * sizeof(float), 1, streams, L ? 5 : 4, erasures, erasure_offsets,
+                     [&](size_t m, void *const *d, const uint16_t *d_er, const uint32_t *d_off, hipStream_t s) {
+                       return launch_minsum(code, static_cast<const float *>(d[0]), d_er, d_off, static_cast<uint8_t *>(d[1]),
+                                            static_cast<float *>(d[4]), static_cast<uint16_t *>(d[2]),
+                                            static_cast<int32_t *>(d[3]), m, s);
+                     });
 }
 
 
@@ -957,51 +733,17 @@ static int hard_host(const cc_code *code, bool float_in, const void *in, const u
   if (rc != CC_OK) return rc;
   if (B == 0) return CC_OK;
   const size_t n = code->tab.n;
-  if (!float_in) {  // Element(v) throws for v outside the field, galois.h:149-152
-    const uint8_t *b = static_cast<const uint8_t *>(in);
-    const uint8_t mask = static_cast<uint8_t>(~((1u << code->tab.q) - 1));
-    for (size_t i = 0; i < B * n; ++i)
-      if (b[i] & mask) return CC_ERR_NOT_IN_FIELD;
-  }
-  if (erasures) {
-    const size_t ne = erasure_offsets[B];
-    for (size_t e = 0; e < ne; ++e)
-      if (erasures[e] >= n) return CC_ERR_INVALID_ARGUMENT;
-  }
+  if (!float_in && !symbols_in_field(static_cast<const uint8_t *>(in), B * n, code->tab.q)) return CC_ERR_NOT_IN_FIELD;
+  if (!erasures_in_range(erasures, erasure_offsets, B, n)) return CC_ERR_INVALID_ARGUMENT;
   DeviceGuard guard(code->device);
-  StageLock sl(code);
-  if (sl.rc != CC_OK) return sl.rc;
-  HostStage &st = *sl.st;
   const size_t esz = float_in ? sizeof(float) : 1;
-  const size_t CH = chunk_frames(n * esz, B);
-  if (B > 2 * CH)
-    if (int rc_fs = st.fresh_streams()) return rc_fs;
-  const bool dma_in = HostStage::dma_ready(in), dma_out = HostStage::dma_ready(out),
-             dma_ne = nerr && HostStage::dma_ready(nerr), dma_st = status && HostStage::dma_ready(status);
-  size_t k = 0;
-  for (size_t c0 = 0; c0 < B; c0 += CH, ++k) {
-    const int slot = static_cast<int>(k & 1);
-    const size_t m = B - c0 < CH ? B - c0 : CH;
-    hipStream_t s = st.stream[slot];
-    if (int r = st.retire(slot)) return r;
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    int32_t *d_nerr = nullptr, *d_status = nullptr;
-    const uint16_t *d_er = nullptr;
-    const uint32_t *d_off = nullptr;
-    if (int r = st.get(slot, 0, m * n * esz, &d_in)) return r;
-    if (int r = st.get(slot, 1, m * n, &d_out)) return r;
-    if (int r = st.get(slot, 2, m, &d_nerr)) return r;
-    if (int r = st.get(slot, 3, m, &d_status)) return r;
-    if (int r = st.upload(slot, 0, d_in, static_cast<const uint8_t *>(in) + c0 * n * esz, m * n * esz, dma_in)) return r;
-    if (int r = upload_erasures(st, slot, 5, erasures, erasure_offsets, c0, m, &d_er, &d_off)) return r;
-    if (int r = hard_dev(code, float_in, d_in, d_er, d_off, d_out, d_nerr, d_status, m, s)) return r;
-    if (int r = st.download(slot, 1, out + c0 * n, d_out, m * n, dma_out)) return r;
-    if (nerr)
-      if (int r = st.download(slot, 2, nerr + c0, d_nerr, m * sizeof(int32_t), dma_ne)) return r;
-    if (status)
-      if (int r = st.download(slot, 3, status + c0, d_status, m * sizeof(int32_t), dma_st)) return r;
-  }
-  return st.drain();
+  const StagedStream streams[] = {stage_in(0, in, n * esz), stage_out(1, out, n), stage_out(2, nerr, sizeof(int32_t)),
+                                  stage_out(3, status, sizeof(int32_t))};
+  return staged_call(code, B, n * esz, 1, streams, 4, erasures, erasure_offsets,
+                     [&](size_t m, void *const *d, const uint16_t *d_er, const uint32_t *d_off, hipStream_t s) {
+                       return hard_dev(code, float_in, d[0], d_er, d_off, static_cast<uint8_t *>(d[1]),
+                                       static_cast<int32_t *>(d[2]), static_cast<int32_t *>(d[3]), m, s);
+                     });
 }
 
 int cc_correct_hard_batch(const cc_code *code, const uint8_t *in, const uint16_t *erasures,
@@ -1042,34 +784,15 @@ static int byte_map_host(const cc_code *code, bool encode, const uint8_t *src, u
   if (B == 0) return CC_OK;
   const size_t n = code->tab.n, l = code->tab.l;
   const size_t in_w = encode ? l : n, out_w = encode ? n : l;
-  if (encode) {  // Element(e) throws for values outside the field, galois.h:149-152 via cyclic.h:300-301
-    const uint8_t mask = static_cast<uint8_t>(~((1u << code->tab.q) - 1));
-    for (size_t i = 0; i < B * in_w; ++i)
-      if (src[i] & mask) return CC_ERR_NOT_IN_FIELD;
-  }
+  if (encode && !symbols_in_field(src, B * in_w, code->tab.q)) return CC_ERR_NOT_IN_FIELD;
   DeviceGuard guard(code->device);
-  StageLock sl(code);
-  if (sl.rc != CC_OK) return sl.rc;
-  HostStage &st = *sl.st;
-  const size_t CH = chunk_frames(n, B);
-  if (B > 2 * CH)
-    if (int rc_fs = st.fresh_streams()) return rc_fs;
-  const bool dma_in = HostStage::dma_ready(src), dma_out = HostStage::dma_ready(dst);
-  size_t k = 0;
-  for (size_t c0 = 0; c0 < B; c0 += CH, ++k) {
-    const int slot = static_cast<int>(k & 1);
-    const size_t m = B - c0 < CH ? B - c0 : CH;
-    hipStream_t s = st.stream[slot];
-    if (int r = st.retire(slot)) return r;
-    uint8_t *d_src = nullptr, *d_dst = nullptr;
-    if (int r = st.get(slot, 0, m * in_w, &d_src)) return r;
-    if (int r = st.get(slot, 1, m * out_w, &d_dst)) return r;
-    if (int r = st.upload(slot, 0, d_src, src + c0 * in_w, m * in_w, dma_in)) return r;
-    const int rc = encode ? launch_encode(code, d_src, d_dst, m, s) : launch_extract(code, d_src, d_dst, m, s);
-    if (rc != CC_OK) return rc;
-    if (int r = st.download(slot, 1, dst + c0 * out_w, d_dst, m * out_w, dma_out)) return r;
-  }
-  return st.drain();
+  const StagedStream streams[] = {stage_in(0, src, in_w), stage_out(1, dst, out_w)};
+  return staged_call(code, B, n, 1, streams, 2, nullptr, nullptr,
+                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t s) {
+                       const uint8_t *d_src = static_cast<const uint8_t *>(d[0]);
+                       uint8_t *d_dst = static_cast<uint8_t *>(d[1]);
+                       return encode ? launch_encode(code, d_src, d_dst, m, s) : launch_extract(code, d_src, d_dst, m, s);
+                     });
 }
 
 int cc_encode_batch(const cc_code *code, const uint8_t *msg, uint8_t *cw, size_t B) {
@@ -1088,26 +811,19 @@ static int decode_host(const cc_code *code, bool float_in, const void *in, const
   if (needs_code(code) != CC_OK) return CC_ERR_INVALID_ARGUMENT;
   if (int rc = not_wide(code)) return rc;
   if (B == 0) return CC_OK;
-  std::vector<uint8_t> tmp;
-  if (!words) {
-    tmp.resize(B * code->tab.n);
-    words = tmp.data();
+  if (code->soft && !float_in) {
+    set_last_error("min-sum needs a signed (soft) input sequence");
+    return CC_ERR_INVALID_ARGUMENT;
   }
-  int rc;
-  if (code->soft) {
-    if (!float_in) {
-      set_last_error("min-sum needs a signed (soft) input sequence");
-      return CC_ERR_INVALID_ARGUMENT;
-    }
-    rc = cc_correct_soft_batch(code, static_cast<const float *>(in), erasures, erasure_offsets, words, nullptr, iters,
-                               status, B);
-  } else if (float_in) {
-    rc = cc_correct_hard_f32_batch(code, static_cast<const float *>(in), erasures, erasure_offsets, words, nerr, status, B);
-  } else {
-    rc = cc_correct_hard_batch(code, static_cast<const uint8_t *>(in), erasures, erasure_offsets, words, nerr, status, B);
-  }
-  if (rc != CC_OK) return rc;
-  return cc_extract_batch(code, words, msg, B);
+  return correct_then_extract(
+      B, code->tab.n, words,
+      [&](uint8_t *w) {
+        if (code->soft)
+          return cc_correct_soft_batch(code, static_cast<const float *>(in), erasures, erasure_offsets, w, nullptr, iters, status, B);
+        if (float_in) return cc_correct_hard_f32_batch(code, static_cast<const float *>(in), erasures, erasure_offsets, w, nerr, status, B);
+        return cc_correct_hard_batch(code, static_cast<const uint8_t *>(in), erasures, erasure_offsets, w, nerr, status, B);
+      },
+      [&](const uint8_t *w) { return cc_extract_batch(code, w, msg, B); });
 }
 
 int cc_decode_hard_batch(const cc_code *code, const uint8_t *in, const uint16_t *erasures,
@@ -1190,32 +906,15 @@ static int wide_map_host(const cc_code *code, int kind, const uint16_t *src, uin
   if (B == 0) return CC_OK;
   const size_t n = code->tab.n, l = code->tab.l;
   const size_t in_w = kind == 0 ? l : n, out_w = kind == 0 ? n : l;
-  if (kind == 0)
-    for (size_t i = 0; i < B * in_w; ++i)
-      if (src[i] > (1u << code->tab.q) - 1) return CC_ERR_NOT_IN_FIELD;  // Element(e) throws, galois.h:149-152
+  if (kind == 0 && !symbols_in_field(src, B * in_w, code->tab.q)) return CC_ERR_NOT_IN_FIELD;
   DeviceGuard guard(code->device);
-  StageLock sl(code);
-  if (sl.rc != CC_OK) return sl.rc;
-  HostStage &st = *sl.st;
-  const size_t CH = chunk_frames(n * 2, B);
-  if (B > 2 * CH)
-    if (int rc_fs = st.fresh_streams()) return rc_fs;
-  const bool dma_in = HostStage::dma_ready(src), dma_out = HostStage::dma_ready(dst);
-  size_t k = 0;
-  for (size_t c0 = 0; c0 < B; c0 += CH, ++k) {
-    const int slot = static_cast<int>(k & 1);
-    const size_t m = B - c0 < CH ? B - c0 : CH;
-    hipStream_t s = st.stream[slot];
-    if (int r = st.retire(slot)) return r;
-    uint16_t *d_src = nullptr, *d_dst = nullptr;
-    if (int r = st.get(slot, 0, m * in_w, &d_src)) return r;
-    if (int r = st.get(slot, 1, m * out_w, &d_dst)) return r;
-    if (int r = st.upload(slot, 0, d_src, src + c0 * in_w, m * in_w * 2, dma_in)) return r;
-    const int rc = kind == 0 ? launch_wide_encode(code, d_src, d_dst, m, s) : launch_wide_extract(code, d_src, d_dst, m, s);
-    if (rc != CC_OK) return rc;
-    if (int r = st.download(slot, 1, dst + c0 * out_w, d_dst, m * out_w * 2, dma_out)) return r;
-  }
-  return st.drain();
+  const StagedStream streams[] = {stage_in(0, src, in_w * 2), stage_out(1, dst, out_w * 2)};
+  return staged_call(code, B, n * 2, 1, streams, 2, nullptr, nullptr,
+                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t s) {
+                       const uint16_t *d_src = static_cast<const uint16_t *>(d[0]);
+                       uint16_t *d_dst = static_cast<uint16_t *>(d[1]);
+                       return kind == 0 ? launch_wide_encode(code, d_src, d_dst, m, s) : launch_wide_extract(code, d_src, d_dst, m, s);
+                     });
 }
 
 int cc_encode_batch_u16(const cc_code *code, const uint16_t *msg, uint16_t *cw, size_t B) {
@@ -1233,46 +932,16 @@ int cc_correct_hard_batch_u16(const cc_code *code, const uint16_t *in, const uin
   if (int rc = wide_correct_ready(code, erasures != nullptr)) return rc;
   if (B == 0) return CC_OK;
   const size_t n = code->tab.n;
-  for (size_t i = 0; i < B * n; ++i)
-    if (in[i] > (1u << code->tab.q) - 1) return CC_ERR_NOT_IN_FIELD;
-  if (erasures) {
-    const size_t ne = erasure_offsets[B];
-    for (size_t e = 0; e < ne; ++e)
-      if (erasures[e] >= n) return CC_ERR_INVALID_ARGUMENT;
-  }
+  if (!symbols_in_field(in, B * n, code->tab.q)) return CC_ERR_NOT_IN_FIELD;
+  if (!erasures_in_range(erasures, erasure_offsets, B, n)) return CC_ERR_INVALID_ARGUMENT;
   DeviceGuard guard(code->device);
-  StageLock sl(code);
-  if (sl.rc != CC_OK) return sl.rc;
-  HostStage &st = *sl.st;
-  const size_t CH = chunk_frames(n * 2, B);
-  if (B > 2 * CH)
-    if (int rc_fs = st.fresh_streams()) return rc_fs;
-  const bool dma_in = HostStage::dma_ready(in), dma_out = HostStage::dma_ready(out),
-             dma_ne = nerr && HostStage::dma_ready(nerr), dma_st = status && HostStage::dma_ready(status);
-  size_t k = 0;
-  for (size_t c0 = 0; c0 < B; c0 += CH, ++k) {
-    const int slot = static_cast<int>(k & 1);
-    const size_t m = B - c0 < CH ? B - c0 : CH;
-    hipStream_t s = st.stream[slot];
-    if (int r = st.retire(slot)) return r;
-    uint16_t *d_in = nullptr, *d_out = nullptr;
-    int32_t *d_nerr = nullptr, *d_status = nullptr;
-    const uint16_t *d_er = nullptr;
-    const uint32_t *d_off = nullptr;
-    if (int r = st.get(slot, 0, m * n, &d_in)) return r;
-    if (int r = st.get(slot, 1, m * n, &d_out)) return r;
-    if (int r = st.get(slot, 2, m, &d_nerr)) return r;
-    if (int r = st.get(slot, 3, m, &d_status)) return r;
-    if (int r = st.upload(slot, 0, d_in, in + c0 * n, m * n * 2, dma_in)) return r;
-    if (int r = upload_erasures(st, slot, 5, erasures, erasure_offsets, c0, m, &d_er, &d_off)) return r;
-    if (int r = launch_wide_correct(code, d_in, d_er, d_off, d_out, d_nerr, d_status, m, s)) return r;
-    if (int r = st.download(slot, 1, out + c0 * n, d_out, m * n * 2, dma_out)) return r;
-    if (nerr)
-      if (int r = st.download(slot, 2, nerr + c0, d_nerr, m * sizeof(int32_t), dma_ne)) return r;
-    if (status)
-      if (int r = st.download(slot, 3, status + c0, d_status, m * sizeof(int32_t), dma_st)) return r;
-  }
-  return st.drain();
+  const StagedStream streams[] = {stage_in(0, in, n * 2), stage_out(1, out, n * 2), stage_out(2, nerr, sizeof(int32_t)),
+                                  stage_out(3, status, sizeof(int32_t))};
+  return staged_call(code, B, n * 2, 1, streams, 4, erasures, erasure_offsets,
+                     [&](size_t m, void *const *d, const uint16_t *d_er, const uint32_t *d_off, hipStream_t s) {
+                       return launch_wide_correct(code, static_cast<const uint16_t *>(d[0]), d_er, d_off, static_cast<uint16_t *>(d[1]),
+                                                  static_cast<int32_t *>(d[2]), static_cast<int32_t *>(d[3]), m, s);
+                     });
 }
 
 /* ------------------------------ packed bits (packed.hip) ------------------------------ */
@@ -1328,41 +997,13 @@ int cc_packed_route(const cc_code *code, size_t B) {
   return packed_native_supported(code, B) ? 1 : 0;
 }
 
-// The router of the byte / 16-bit _dev entry points on frame-major device buffers: kind 0 = encode, 1 = extract,
-// 2 = correct.  The generic routes of the packed and of the interleaved calls go through it.
-static int plain_route_dev(const cc_code *code, int kind, const uint8_t *a, const uint16_t *d_er, const uint32_t *d_off, uint8_t *b,
-                           int32_t *d_nerr, int32_t *d_status, size_t B, hipStream_t stream) {
-  if (code->wide) {
-    const uint16_t *a16 = reinterpret_cast<const uint16_t *>(a);
-    uint16_t *b16 = reinterpret_cast<uint16_t *>(b);
-    return kind == 0   ? launch_wide_encode(code, a16, b16, B, stream)
-           : kind == 1 ? launch_wide_extract(code, a16, b16, B, stream)
-                       : launch_wide_correct(code, a16, d_er, d_off, b16, d_nerr, d_status, B, stream);
-  }
-  if (kind == 0) return launch_encode(code, a, b, B, stream);
-  if (kind == 1) return launch_extract(code, a, b, B, stream);
-  if (d_er && code->desc.algorithm == CC_ALG_PGZ) return launch_pgz_erasures(code, a, d_er, d_off, b, d_nerr, d_status, B, stream);
-  return launch_algebraic(code, false, a, d_er, d_off, b, d_nerr, d_status, B, stream);
-}
-
-// Generic route of a packed call: unpack into workspace of the handle's pool (bytes, 16-bit words for q > 8), the
-// router of the byte / 16-bit entry points, pack.  kind 0 = encode, 1 = extract, 2 = correct.
+// generic route of a packed call: unpack, the router of the byte / 16-bit entry points, pack
 static int packed_generic_dev(const cc_code *code, int kind, const uint8_t *d_src, const uint16_t *d_er, const uint32_t *d_off,
                               uint8_t *d_dst, int32_t *d_nerr, int32_t *d_status, size_t B, hipStream_t stream) {
-  if (B == 0) return CC_OK;
-  const size_t n = code->tab.n, l = code->tab.l, width = code->wide ? 2 : 1;
-  const size_t in_w = kind == 0 ? l : n, out_w = kind == 1 ? l : n;
-  // words without erasures are corrected in place, as a byte call with out == in (it then skips its copy of the words)
-  const bool in_place = kind == 2 && !d_er && !code->wide;
-  const size_t in_bytes = (B * in_w * width + 255) & ~static_cast<size_t>(255);
-  uint8_t *ws = nullptr;
-  CC_HIP_TRY(workspace_alloc(code, reinterpret_cast<void **>(&ws), in_bytes + (in_place ? 0 : B * out_w * width) + 16, stream));
-  uint8_t *a = ws, *b = in_place ? ws : ws + in_bytes;
-  int rc = launch_unpack_bits(d_src, in_w, a, static_cast<int>(width), B, stream);
-  if (rc == CC_OK) rc = plain_route_dev(code, kind, a, d_er, d_off, b, d_nerr, d_status, B, stream);
-  if (rc == CC_OK) rc = launch_pack_bits(b, static_cast<int>(width), out_w, d_dst, B, stream);
-  (void)hipFreeAsync(ws, stream);
-  return rc;
+  return through_workspace(
+      code, kind, [&](uint8_t *a, size_t in_w, int width) { return launch_unpack_bits(d_src, in_w, a, width, B, stream); },
+      [&](const uint8_t *b, size_t out_w, int width) { return launch_pack_bits(b, width, out_w, d_dst, B, stream); }, d_er, d_off,
+      d_nerr, d_status, B, stream);
 }
 
 static int packed_correct_dev(const cc_code *code, const uint8_t *d_in, const uint16_t *d_er, const uint32_t *d_off,
@@ -1409,7 +1050,7 @@ int cc_correct_hard_packed_batch_dev(const cc_code *code, const uint8_t *d_in, c
                             static_cast<hipStream_t>(stream));
 }
 
-// host pointers: the chunked staging of the byte entry points; kind as packed_generic_dev
+// host pointers: the chunked staging of the byte entry points; kind as plain_route_dev
 static int packed_host(const cc_code *code, int kind, const uint8_t *src, const uint16_t *erasures,
                        const uint32_t *erasure_offsets, uint8_t *dst, int32_t *nerr, int32_t *status, size_t B) {
   if (!code || (B && (!src || !dst))) return CC_ERR_INVALID_ARGUMENT;
@@ -1418,50 +1059,19 @@ static int packed_host(const cc_code *code, int kind, const uint8_t *src, const 
   if (B == 0) return CC_OK;
   const size_t n = code->tab.n, l = code->tab.l;
   const size_t in_w = packed_width(kind == 0 ? l : n), out_w = packed_width(kind == 1 ? l : n);
-  if (erasures) {
-    const size_t ne = erasure_offsets[B];
-    for (size_t e = 0; e < ne; ++e)
-      if (erasures[e] >= n) return CC_ERR_INVALID_ARGUMENT;
-  }
+  if (!erasures_in_range(erasures, erasure_offsets, B, n)) return CC_ERR_INVALID_ARGUMENT;
   DeviceGuard guard(code->device);
-  StageLock sl(code);
-  if (sl.rc != CC_OK) return sl.rc;
-  HostStage &st = *sl.st;
-  const size_t CH = chunk_frames(n * (code->wide ? 2 : 1), B);  // (the generic route's workspace is what a chunk costs)
-  if (B > 2 * CH)
-    if (int rc_fs = st.fresh_streams()) return rc_fs;
-  const bool dma_in = HostStage::dma_ready(src), dma_out = HostStage::dma_ready(dst),
-             dma_ne = nerr && HostStage::dma_ready(nerr), dma_st = status && HostStage::dma_ready(status);
-  size_t k = 0;
-  for (size_t c0 = 0; c0 < B; c0 += CH, ++k) {
-    const int slot = static_cast<int>(k & 1);
-    const size_t m = B - c0 < CH ? B - c0 : CH;
-    hipStream_t s = st.stream[slot];
-    if (int r = st.retire(slot)) return r;
-    uint8_t *d_src = nullptr, *d_dst = nullptr;
-    int32_t *d_nerr = nullptr, *d_status = nullptr;
-    const uint16_t *d_er = nullptr;
-    const uint32_t *d_off = nullptr;
-    if (int r = st.get(slot, 0, m * in_w, &d_src)) return r;
-    if (int r = st.get(slot, 1, m * out_w, &d_dst)) return r;
-    if (int r = st.upload(slot, 0, d_src, src + c0 * in_w, m * in_w, dma_in)) return r;
-    int rc;
-    if (kind == 2) {
-      if (int r = st.get(slot, 2, m, &d_nerr)) return r;
-      if (int r = st.get(slot, 3, m, &d_status)) return r;
-      if (int r = upload_erasures(st, slot, 5, erasures, erasure_offsets, c0, m, &d_er, &d_off)) return r;
-      rc = packed_correct_dev(code, d_src, d_er, d_off, d_dst, d_nerr, d_status, m, s);
-    } else {
-      rc = packed_map_dev(code, kind, d_src, d_dst, m, s);
-    }
-    if (rc != CC_OK) return rc;
-    if (int r = st.download(slot, 1, dst + c0 * out_w, d_dst, m * out_w, dma_out)) return r;
-    if (nerr)
-      if (int r = st.download(slot, 2, nerr + c0, d_nerr, m * sizeof(int32_t), dma_ne)) return r;
-    if (status)
-      if (int r = st.download(slot, 3, status + c0, d_status, m * sizeof(int32_t), dma_st)) return r;
-  }
-  return st.drain();
+  const StagedStream streams[] = {stage_in(0, src, in_w), stage_out(1, dst, out_w), stage_out(2, nerr, sizeof(int32_t)),
+                                  stage_out(3, status, sizeof(int32_t))};
+  // a chunk is sized by the symbols, not by the packed words: the generic route's workspace is what a chunk costs
+  return staged_call(code, B, n * (code->wide ? 2 : 1), 1, streams, kind == 2 ? 4 : 2, erasures, erasure_offsets,
+                     [&](size_t m, void *const *d, const uint16_t *d_er, const uint32_t *d_off, hipStream_t s) {
+                       const uint8_t *d_src = static_cast<const uint8_t *>(d[0]);
+                       uint8_t *d_dst = static_cast<uint8_t *>(d[1]);
+                       if (kind != 2) return packed_map_dev(code, kind, d_src, d_dst, m, s);
+                       return packed_correct_dev(code, d_src, d_er, d_off, d_dst, static_cast<int32_t *>(d[2]),
+                                                 static_cast<int32_t *>(d[3]), m, s);
+                     });
 }
 
 int cc_encode_packed_batch(const cc_code *code, const uint8_t *msg, uint8_t *cw, size_t B) {
@@ -1480,13 +1090,10 @@ int cc_decode_hard_packed_batch(const cc_code *code, const uint8_t *in, const ui
                                 int32_t *status, size_t B) {
   if (!code || (B && (!in || !msg))) return CC_ERR_INVALID_ARGUMENT;
   if (int rc = packed_supported(code)) return rc;
-  std::vector<uint8_t> tmp;
-  if (!words && B) {
-    tmp.resize(B * packed_width(code->tab.n));
-    words = tmp.data();
-  }
-  if (int rc = cc_correct_hard_packed_batch(code, in, erasures, erasure_offsets, words, nerr, status, B)) return rc;
-  return cc_extract_packed_batch(code, words, msg, B);
+  return correct_then_extract(
+      B, packed_width(code->tab.n), words,
+      [&](uint8_t *w) { return cc_correct_hard_packed_batch(code, in, erasures, erasure_offsets, w, nerr, status, B); },
+      [&](const uint8_t *w) { return cc_extract_packed_batch(code, w, msg, B); });
 }
 
 /* ------------------------------ symbol-interleaved blocks (interleave.hip) ------------------------------ */
@@ -1557,19 +1164,10 @@ static int interleaved_dev(const cc_code *code, int kind, const void *d_src, con
   if (kind == 1 && interleaved_extract_native(code, I)) return launch_interleaved_extract(code, src, dst, B, I, stream);
   if (kind == 2 && interleaved_native_supported(code, B, I, d_er != nullptr))
     return launch_algebraic_chunk(code, false, src, nullptr, nullptr, dst, d_nerr, d_status, B, stream, static_cast<int>(I));
-  const size_t n = code->tab.n, l = code->tab.l, width = code->wide ? 2 : 1;
-  const size_t in_w = kind == 0 ? l : n, out_w = kind == 1 ? l : n;
-  // words without erasures are corrected in place, as a byte call with out == in (it then skips its copy of the words)
-  const bool in_place = kind == 2 && !d_er && !code->wide;
-  const size_t in_bytes = (B * in_w * width + 255) & ~static_cast<size_t>(255);
-  uint8_t *ws = nullptr;
-  CC_HIP_TRY(workspace_alloc(code, reinterpret_cast<void **>(&ws), in_bytes + (in_place ? 0 : B * out_w * width) + 16, stream));
-  uint8_t *a = ws, *b = in_place ? ws : ws + in_bytes;
-  int rc = launch_interleave(src, static_cast<int>(width), in_w, I, a, B, false, stream);
-  if (rc == CC_OK) rc = plain_route_dev(code, kind, a, d_er, d_off, b, d_nerr, d_status, B, stream);
-  if (rc == CC_OK) rc = launch_interleave(b, static_cast<int>(width), out_w, I, dst, B, true, stream);
-  (void)hipFreeAsync(ws, stream);
-  return rc;
+  return through_workspace(
+      code, kind, [&](uint8_t *a, size_t in_w, int width) { return launch_interleave(src, width, in_w, I, a, B, false, stream); },
+      [&](const uint8_t *b, size_t out_w, int width) { return launch_interleave(b, width, out_w, I, dst, B, true, stream); }, d_er,
+      d_off, d_nerr, d_status, B, stream);
 }
 
 // the _dev entry points: null pointers, the new refusals, the plain call's refusals, the call
@@ -1623,61 +1221,18 @@ static int interleaved_host(const cc_code *code, int kind, int width, const void
   if (B == 0) return CC_OK;
   const size_t n = code->tab.n, l = code->tab.l, w = static_cast<size_t>(width);
   const size_t in_w = kind == 0 ? l : n, out_w = kind == 1 ? l : n;
-  if (kind != 1) {  // Element(v) throws for v outside the field, galois.h:149-152
-    const uint32_t top = (1u << code->tab.q) - 1;
-    if (width == 2) {
-      const uint16_t *v = static_cast<const uint16_t *>(src);
-      for (size_t i = 0; i < B * in_w; ++i)
-        if (v[i] > top) return CC_ERR_NOT_IN_FIELD;
-    } else {
-      const uint8_t *v = static_cast<const uint8_t *>(src);
-      for (size_t i = 0; i < B * in_w; ++i)
-        if (v[i] > top) return CC_ERR_NOT_IN_FIELD;
-    }
-  }
-  if (erasures) {
-    const size_t ne = erasure_offsets[B];
-    for (size_t e = 0; e < ne; ++e)
-      if (erasures[e] >= n) return CC_ERR_INVALID_ARGUMENT;
-  }
+  if (kind != 1 && !(width == 2 ? symbols_in_field(static_cast<const uint16_t *>(src), B * in_w, code->tab.q)
+                                : symbols_in_field(static_cast<const uint8_t *>(src), B * in_w, code->tab.q)))
+    return CC_ERR_NOT_IN_FIELD;
+  if (!erasures_in_range(erasures, erasure_offsets, B, n)) return CC_ERR_INVALID_ARGUMENT;
   DeviceGuard guard(code->device);
-  StageLock sl(code);
-  if (sl.rc != CC_OK) return sl.rc;
-  HostStage &st = *sl.st;
-  size_t CH = chunk_frames(n * w, B) / I * I;  // whole blocks
-  if (CH < I) CH = I;
-  if (B > 2 * CH)
-    if (int rc_fs = st.fresh_streams()) return rc_fs;
-  const bool dma_in = HostStage::dma_ready(src), dma_out = HostStage::dma_ready(dst),
-             dma_ne = nerr && HostStage::dma_ready(nerr), dma_st = status && HostStage::dma_ready(status);
-  const uint8_t *sb = static_cast<const uint8_t *>(src);
-  uint8_t *db = static_cast<uint8_t *>(dst);
-  size_t k = 0;
-  for (size_t c0 = 0; c0 < B; c0 += CH, ++k) {
-    const int slot = static_cast<int>(k & 1);
-    const size_t m = B - c0 < CH ? B - c0 : CH;
-    hipStream_t s = st.stream[slot];
-    if (int r = st.retire(slot)) return r;
-    uint8_t *d_src = nullptr, *d_dst = nullptr;
-    int32_t *d_nerr = nullptr, *d_status = nullptr;
-    const uint16_t *d_er = nullptr;
-    const uint32_t *d_off = nullptr;
-    if (int r = st.get(slot, 0, m * in_w * w, &d_src)) return r;
-    if (int r = st.get(slot, 1, m * out_w * w, &d_dst)) return r;
-    if (int r = st.upload(slot, 0, d_src, sb + c0 * in_w * w, m * in_w * w, dma_in)) return r;
-    if (kind == 2) {
-      if (int r = st.get(slot, 2, m, &d_nerr)) return r;
-      if (int r = st.get(slot, 3, m, &d_status)) return r;
-      if (int r = upload_erasures(st, slot, 5, erasures, erasure_offsets, c0, m, &d_er, &d_off)) return r;
-    }
-    if (int r = interleaved_dev(code, kind, d_src, d_er, d_off, d_dst, d_nerr, d_status, m, I, s)) return r;
-    if (int r = st.download(slot, 1, db + c0 * out_w * w, d_dst, m * out_w * w, dma_out)) return r;
-    if (nerr)
-      if (int r = st.download(slot, 2, nerr + c0, d_nerr, m * sizeof(int32_t), dma_ne)) return r;
-    if (status)
-      if (int r = st.download(slot, 3, status + c0, d_status, m * sizeof(int32_t), dma_st)) return r;
-  }
-  return st.drain();
+  const StagedStream streams[] = {stage_in(0, src, in_w * w), stage_out(1, dst, out_w * w), stage_out(2, nerr, sizeof(int32_t)),
+                                  stage_out(3, status, sizeof(int32_t))};
+  return staged_call(code, B, n * w, I, streams, kind == 2 ? 4 : 2, erasures, erasure_offsets,  // chunks of whole blocks
+                     [&](size_t m, void *const *d, const uint16_t *d_er, const uint32_t *d_off, hipStream_t s) {
+                       return interleaved_dev(code, kind, d[0], d_er, d_off, d[1], static_cast<int32_t *>(d[2]),
+                                              static_cast<int32_t *>(d[3]), m, I, s);
+                     });
 }
 
 int cc_encode_interleaved_batch(const cc_code *code, const uint8_t *msg, uint8_t *cw, size_t B, uint32_t interleave) {
@@ -1713,13 +1268,10 @@ int cc_decode_hard_interleaved_batch(const cc_code *code, const uint8_t *in, con
     set_last_error("min-sum needs a signed (soft) input sequence");
     return CC_ERR_INVALID_ARGUMENT;
   }
-  std::vector<uint8_t> tmp;
-  if (!words && B) {
-    tmp.resize(B * code->tab.n);
-    words = tmp.data();
-  }
-  if (int rc = cc_correct_hard_interleaved_batch(code, in, erasures, erasure_offsets, words, nerr, status, B, interleave)) return rc;
-  return cc_extract_interleaved_batch(code, words, msg, B, interleave);
+  return correct_then_extract(
+      B, code->tab.n, words,
+      [&](uint8_t *w) { return cc_correct_hard_interleaved_batch(code, in, erasures, erasure_offsets, w, nerr, status, B, interleave); },
+      [&](const uint8_t *w) { return cc_extract_interleaved_batch(code, w, msg, B, interleave); });
 }
 
 /* ------------------------------ Monte-Carlo ------------------------------ */

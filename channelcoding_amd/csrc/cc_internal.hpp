@@ -98,7 +98,7 @@ struct WideTables {
 namespace ccamd {
 struct McWorkspace;
 void mc_workspace_free(McWorkspace *w);
-struct HostStage;  // capi.hip: staging of the host-pointer entry points (private streams, grow-only device buffers)
+struct HostStage;  // host_stage.hpp: staging of the host-pointer entry points (private streams, grow-only device buffers)
 void host_stage_free(HostStage *s);
 }  // namespace ccamd
 

@@ -1,5 +1,6 @@
-"""PCIe-inclusive rate of the host-pointer entry point cc_correct_soft_batch (never the headline `value`):
-caller-owned, pre-touched buffers passed straight to the C ABI -- pageable and page-locked."""
+"""PCIe-inclusive rates of the host-pointer entry points (never the headline `value`): caller-owned, pre-touched
+buffers passed straight to the C ABI.  cc_correct_soft_batch with pageable and page-locked buffers, then the byte paths
+cc_correct_hard_batch and cc_encode_batch of RS(255,223) with pageable buffers."""
 import ctypes as C
 import os
 import sys
@@ -44,3 +45,35 @@ for log2b, ebno in ((10, 4.0), (14, 4.0), (16, 4.0), (18, 4.0), (20, 4.0), (20, 
         dt = run(yp, hp, ip, sp, B)
         print("page-locked buffers, B=2^%d, %.0f dB: %.2f M frames/s  (%.2f ms, %.2f GB/s of LLR in)" % (
             log2b, ebno, B / dt / 1e6, dt * 1e3, B * 1020 / dt / 1e9), flush=True)
+
+
+# the byte paths: RS(255,223) BM, 2^20 frames, 0..16 symbol errors per frame (4096 distinct frames, tiled)
+rs = cc.rs(8, cc.errors(16), cc.berlekamp_massey_tag())
+B = 1 << 20
+msg = np.tile(rng.integers(0, 256, (4096, rs.l)).astype(np.uint8), (B // 4096, 1))
+cw = np.ones((B, rs.n), np.uint8)
+noise = np.zeros((4096, rs.n), np.uint8)
+for f in range(4096):
+    pos = rng.choice(rs.n, int(rng.integers(0, 17)), replace=False)
+    noise[f, pos] = rng.integers(1, 256, len(pos))
+
+
+def timed(call, reps=3):
+    assert call() == 0
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        assert call() == 0
+    return (time.perf_counter() - t0) / reps
+
+
+dt = timed(lambda: lib.cc_encode_batch(rs._h, P(msg), P(cw), B))
+print("pageable buffers, B=2^20, RS(255,223) cc_encode_batch: %.2f M frames/s  (%.2f ms, %.2f GB/s of codewords out)" % (
+    B / dt / 1e6, dt * 1e3, B * rs.n / dt / 1e9), flush=True)
+rx = cw ^ np.tile(noise, (B // 4096, 1))
+out = np.ones((B, rs.n), np.uint8)
+nerr = np.ones(B, np.int32)
+status = np.ones(B, np.int32)
+dt = timed(lambda: lib.cc_correct_hard_batch(rs._h, P(rx), None, None, P(out), P(nerr), P(status), B))
+assert (status == 0).all() and np.array_equal(out, cw)
+print("pageable buffers, B=2^20, RS(255,223) BM cc_correct_hard_batch, 0..16 errors: %.2f M frames/s  (%.2f ms, %.2f GB/s of words in)" % (
+    B / dt / 1e6, dt * 1e3, B * rs.n / dt / 1e9), flush=True)

@@ -230,6 +230,90 @@ print("ok")
     assert run.returncode == 0 and "ok" in run.stdout, run.stdout[-2000:] + run.stderr[-2000:]
 
 
+def test_host_entry_points_in_chunks_other_routes():
+    """The same for the host-pointer routes the test above does not reach: hard decoding of channel values (also the
+    PGZ two-trial rule, which makes a byte image of the signs first), the packed calls (a chunk is sized by n, not by
+    the packed width: 3000 frames are five chunks), the 16-bit calls (19 frames of 2046 bytes per chunk: 6, 2 and 1
+    chunks, both sides of the fresh-streams rule) and a page-locked caller buffer, which is not staged."""
+    import subprocess
+    import sys
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    script = r"""
+import sys, numpy as np, torch
+sys.path.insert(0, %r); sys.path.insert(0, %r + "/tests")
+import channelcoding_amd as cc
+rng = np.random.default_rng(9)
+host = lambda t: t.cpu().numpy()
+def same(a, b, keys, what):
+    for k in keys:
+        assert np.array_equal(a[k], host(b[k])), (what, k)
+bm = cc.primitive_bch(6, cc.errors(3), cc.berlekamp_massey_tag())
+pgz = cc.primitive_bch(6, cc.errors(3), cc.peterson_gorenstein_zierler_tag())
+ragged = lambda B: [sorted(rng.choice(63, int(rng.integers(0, 4)), replace=False).tolist()) for _ in range(B)]
+# hard decoding of channel values
+for B in (3000, 17, 1):
+    y = (1.0 + 0.6 * rng.standard_normal((B, 63))).astype(np.float32)
+    per = ragged(B)
+    for name, code in (("bm", bm), ("pgz", pgz)):
+        same(code.correct_batch(y, erasures=per), code.correct_batch(torch.from_numpy(y).cuda(), erasures=per),
+             ("out", "status", "nerr"), ("f32", name, B))
+# packed words
+for B in (3000, 17):
+    msg = cc.pack_bits(rng.integers(0, 2, (B, 45)).astype(np.uint8))
+    cw = bm.encode_batch(msg, packed=True)
+    assert cw.shape == (B, 8) and np.array_equal(cw, host(bm.encode_batch(torch.from_numpy(msg).cuda(), packed=True))), B
+    got = bm.extract_batch(cw, packed=True)
+    assert np.array_equal(got, host(bm.extract_batch(torch.from_numpy(cw).cuda(), packed=True))) and np.array_equal(got, msg), B
+    rx = cw.copy()
+    for f in range(B):
+        for p in rng.choice(63, int(rng.integers(0, 5)), replace=False).tolist():
+            rx[f, p >> 3] ^= 1 << (p & 7)
+    d_rx = torch.from_numpy(rx).cuda()
+    for per in (None, ragged(B)):
+        same(bm.correct_batch(rx, erasures=per, packed=True), bm.correct_batch(d_rx, erasures=per, packed=True),
+             ("out", "status", "nerr"), ("packed correct", B, per is None))
+        same(bm.decode_batch(rx, erasures=per, packed=True), bm.decode_batch(d_rx, erasures=per, packed=True),
+             ("out", "msg", "status", "nerr"), ("packed decode", B, per is None))
+# 16-bit symbols
+rs10 = cc.rs(10, cc.errors(4), cc.berlekamp_massey_tag(), modular_polynomial=0x409)
+dev16 = lambda a: torch.from_numpy(a.view(np.int16)).cuda()
+host16 = lambda t: t.cpu().numpy().view(np.uint16)
+for B in (100, 30, 1):
+    msg = rng.integers(0, 1024, (B, 1015)).astype(np.uint16)
+    cw = rs10.encode_batch(msg)
+    assert cw.dtype == np.uint16 and np.array_equal(cw, host16(rs10.encode_batch(dev16(msg)))), B
+    got = rs10.extract_batch(cw)
+    assert np.array_equal(got, host16(rs10.extract_batch(dev16(cw)))) and np.array_equal(got, msg), B
+    rx = cw.copy()
+    per = [sorted(rng.choice(1023, int(rng.integers(0, 4)), replace=False).tolist()) for _ in range(B)]
+    for f in range(B):
+        for p in rng.choice(1023, int(rng.integers(0, 5)), replace=False):
+            rx[f, p] ^= int(rng.integers(1, 1024))
+    a, b = rs10.correct_batch(rx, erasures=per), rs10.correct_batch(dev16(rx), erasures=per)
+    assert np.array_equal(a["out"], host16(b["out"])), B
+    same(a, b, ("status", "nerr"), ("u16 correct", B))
+# page-locked caller memory goes to the DMA engines as it is
+soft = cc.primitive_bch(6, cc.errors(3), cc.min_sum_tag(10))
+B = 3000
+y = (1.0 + 0.6 * rng.standard_normal((B, 63))).astype(np.float32)
+per = ragged(B)
+y_pin = torch.from_numpy(y).pin_memory().numpy()
+a, b = soft.correct_batch(y_pin, erasures=per, want_L=True), soft.correct_batch(y, erasures=per, want_L=True)
+for k in ("out", "status", "iters", "L"):
+    assert np.array_equal(a[k], b[k]), ("page-locked soft", k)
+sym = (y < 0).astype(np.uint8)
+sym_pin = torch.from_numpy(sym).pin_memory().numpy()
+a, b = bm.correct_batch(sym_pin, erasures=per), bm.correct_batch(sym, erasures=per)
+for k in ("out", "status", "nerr"):
+    assert np.array_equal(a[k], b[k]), ("page-locked hard", k)
+print("ok")
+""" % (root, root)
+    env = dict(os.environ, CC_AMD_HOST_CHUNK_BYTES="40000")
+    run = subprocess.run([sys.executable, "-c", script], capture_output=True, text=True, env=env, timeout=600)
+    assert run.returncode == 0 and "ok" in run.stdout, run.stdout[-2000:] + run.stderr[-2000:]
+
+
 def test_pgz_erasure_two_trial_rule_bch():
     """bch.h:97-149: PGZ + erasures decodes twice (erasures := 0, := 1) and keeps the result with fewer errors."""
     o = Oracle(BCH, 6, 3)
