@@ -38,6 +38,18 @@ class Desc(C.Structure):
     ]
 
 
+class BurstChannel(C.Structure):
+    """cc_burst_channel: the Gilbert-Elliott channel along blocks of depth `interleave`."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("interleave", C.c_uint32), ("p_gb", C.c_double), ("p_bg", C.c_double),
+        ("p_error_good", C.c_double), ("p_error_bad", C.c_double),
+    ]
+
+    def __init__(self, interleave=1, p_gb=0.0, p_bg=0.0, p_error_good=0.0, p_error_bad=0.0):
+        super().__init__(C.sizeof(BurstChannel), int(interleave), float(p_gb), float(p_bg), float(p_error_good),
+                         float(p_error_bad))
+
+
 class CcError(RuntimeError):
     def __init__(self, status, where):
         self.status = status
@@ -82,6 +94,10 @@ _SIGNATURES = {
                                          _VP]),
     "cc_discrete_channel_dev": (C.c_int, [_VP, C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int,
                                           _VP, _VP, _VP, _VP, _VP]),
+    "cc_mc_run_burst_dev": (C.c_int, [_VP, C.POINTER(BurstChannel), C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP,
+                                      _VP]),
+    "cc_burst_channel_dev": (C.c_int, [_VP, C.POINTER(BurstChannel), C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP,
+                                       _VP, _VP, _VP]),
     "cc_encode_batch_u16": (C.c_int, [_VP, _VP, _VP, C.c_size_t]),
     "cc_encode_batch_u16_dev": (C.c_int, [_VP, _VP, _VP, C.c_size_t, _VP]),
     "cc_correct_hard_batch_u16": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t]),

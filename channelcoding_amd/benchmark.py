@@ -1,8 +1,9 @@
 """Command line of the reference's simulation driver (src/simulation/benchmark.c++) on the GPU path.
 
-    python -m channelcoding_amd.benchmark [--simulation awgn|bitflip|bsc|bec] [--algorithm NAME|all]...
+    python -m channelcoding_amd.benchmark [--simulation awgn|bitflip|bsc|bec|burst] [--algorithm NAME|all]...
                                           [--k 5|6|7|all]... [--dmin 3|5|7|9|11|all]... [--seed N | --seed-time]
                                           [--threads N] [--log-dir DIR] [--p VALUE]... [--max-samples N]
+                                          [--interleave I] [--p-gb VALUE] [--p-bg VALUE] [--p-good VALUE]
 
 Same options, same decoder registry (benchmark.c++:23-166: primitive_bch<k, dmin<d>, A> for k in 5..7,
 d in 3,5,7,9 and the nine algorithm tags, min-sum family with 50 iterations, NMS 8/10, OMS 1/100) and the same
@@ -17,13 +18,18 @@ the ranks' GPUs (montecarlo.awgn_simulation).  --threads is accepted and ignored
 --simulation bsc / bec is new: the binary symmetric and the binary erasure channel the reference leaves as a TODO
 (montecarlo.discrete_simulation), over the points given with --p (default 10^(-k/4), k = 4 .. 16), each decoder
 writing "<to_string()>.<bsc|bec>.log".
+
+--simulation burst is new as well: the two-state Gilbert-Elliott channel run along symbol-interleaved blocks of depth
+--interleave (montecarlo.burst_simulation), with the transition probabilities --p-gb (good -> bad) and --p-bg (bad ->
+good) per transmitted symbol and the symbol error probability --p-good of the good state; the points given with --p are
+the error probabilities of the bad state.  Each decoder writes "<to_string()>.burst.log".
 """
 import argparse
 import sys
 import time
 
 from . import codes as cc
-from .montecarlo import awgn_simulation, bitflip_simulation, discrete_simulation
+from .montecarlo import awgn_simulation, bitflip_simulation, burst_simulation, discrete_simulation
 
 POWERS = (5, 6, 7)
 DISTANCES = (3, 5, 7, 9)
@@ -67,7 +73,7 @@ def reported_distances():
 
 
 def usage_text():
-    lines = ["--simulation [awgn|bitflip|bsc|bec]",
+    lines = ["--simulation [awgn|bitflip|bsc|bec|burst]",
              "                             Choose the simulation to run. The default is AWGN.",
              "--algorithm <name>           Choose algorithm:"]
     lines += ["  " + a for a in ALGORITHMS]
@@ -78,9 +84,14 @@ def usage_text():
               "--threads <num>              Accepted for compatibility; simulations are batched on the GPU(s).",
               "--stop-rule <0|1|2>          Min-sum stop rule: 0 as shipped, 1 published, 2 GF(2) parity (default).",
               "--log-dir <dir>              Where the <decoder>.log files go (default: current directory).",
-              "--p <value>                  bsc / bec: error / erasure probability of a point; may be given several",
-              "                             times. The default is 10^(-k/4) for k = 4 .. 16.",
-              "--max-samples <num>          awgn / bsc / bec: cap on the frames of one point.",
+              "--p <value>                  bsc / bec: error / erasure probability of a point (burst: the error",
+              "                             probability of the bad state); may be given several times. The default",
+              "                             is 10^(-k/4) for k = 4 .. 16.",
+              "--interleave <num>           burst: depth of the symbol-interleaved blocks, 1 .. 256. The default is 1.",
+              "--p-gb <value>               burst: probability good -> bad per symbol. The default is 0.01.",
+              "--p-bg <value>               burst: probability bad -> good per symbol. The default is 0.1.",
+              "--p-good <value>             burst: symbol error probability of the good state. The default is 0.",
+              "--max-samples <num>          awgn / bsc / bec / burst: cap on the frames of one point.",
               "",
               "algorithm, k, and dmin can be specified multiple times.",
               "For all other options, giving them multiple times results in the last value being used."]
@@ -129,6 +140,10 @@ def main(argv=None):
     ap.add_argument("--errors", type=int, default=0, help="bitflip: largest number of flipped bits")
     ap.add_argument("--max-samples", type=int, default=None, help="awgn / bsc / bec: cap on frames per point")
     ap.add_argument("--p", "-p", type=float, action="append", default=None, help="bsc / bec: channel probability")
+    ap.add_argument("--interleave", type=int, default=1, help="burst: depth of the interleaved blocks")
+    ap.add_argument("--p-gb", type=float, default=0.01, help="burst: P(good -> bad) per symbol")
+    ap.add_argument("--p-bg", type=float, default=0.1, help="burst: P(bad -> good) per symbol")
+    ap.add_argument("--p-good", type=float, default=0.0, help="burst: symbol error probability of the good state")
     ap.add_argument("--help", "-h", action="store_true")
     args, unknown = ap.parse_known_args(argv)
     if args.help or unknown:
@@ -137,7 +152,7 @@ def main(argv=None):
         print(usage_text())
         return 1
     sim = args.simulation.lower()
-    if sim not in ("awgn", "bitflip", "bsc", "bec"):
+    if sim not in ("awgn", "bitflip", "bsc", "bec", "burst"):
         print("Don't know the simulation type '%s'" % sim, file=sys.stderr)
         print(usage_text())
         return 1
@@ -170,6 +185,11 @@ def main(argv=None):
         elif sim in ("bsc", "bec"):
             res = discrete_simulation(code, sim, points=args.p, seed=seed, log_dir=args.log_dir,
                                       max_samples=args.max_samples)()
+            frames = sum(r["frames"] for r in res)
+        elif sim == "burst":
+            res = burst_simulation(code, interleave=args.interleave, p_gb=args.p_gb, p_bg=args.p_bg,
+                                   p_error_good=args.p_good, points=args.p, seed=seed, log_dir=args.log_dir,
+                                   max_samples=args.max_samples)()
             frames = sum(r["frames"] for r in res)
         else:
             if rank == 0:

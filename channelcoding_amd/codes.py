@@ -257,6 +257,25 @@ def deinterleave(x, I):
     return _interleave_move(x, I, False)
 
 
+def burst_channel(code, interleave=1, p_gb=0.0, p_bg=1.0, p_error_good=0.0, p_error_bad=0.5, seed=0, first_frame=0,
+                  frames=0, random_codewords=False):
+    """Frames [first_frame, first_frame + frames) of the Gilbert-Elliott burst channel (cc_burst_channel_dev) along
+    blocks of depth `interleave` on the current device; frames and first_frame are multiples of the depth.  Returns
+    (recv, sent, state): torch uint8 tensors of shape (frames / interleave, n, interleave) -- recv and sent in the
+    interleaved layout (deinterleave() gives the frames), state 0 good / 1 bad for every transmitted symbol."""
+    import torch
+    I, frames = int(interleave), int(frames)
+    ch = capi.BurstChannel(I, p_gb, p_bg, p_error_good, p_error_bad)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    shape = (frames // I if 1 <= I <= 256 else 0, code.n, I)
+    recv, sent, state = (torch.empty(shape, dtype=torch.uint8, device=dev) for _ in range(3))
+    rc = capi.lib().cc_burst_channel_dev(code._h, C.byref(ch), int(seed), int(first_frame), frames,
+                                         int(bool(random_codewords)), _ptr(recv), _ptr(sent), _ptr(state),
+                                         _stream_handle(recv))
+    capi.check(rc, "cc_burst_channel_dev")
+    return recv, sent, state
+
+
 class cyclic:
     """Common part of primitive_bch and rs (cyclic::cyclic<...>, cyclic.h:67-386)."""
     family = None

@@ -1362,6 +1362,63 @@ int cc_discrete_channel_dev(const cc_code *code, double p_error, double p_erasur
                      d_erasures, d_erasure_offsets, d_sent, static_cast<hipStream_t>(stream));
 }
 
+// the burst channel serves the handles of the discrete route; every argument is checked before a device is asked for
+static int burst_supported(const cc_code *code, const cc_burst_channel *ch, uint64_t first_frame, size_t frames,
+                           int random_codewords) {
+  if (!ch || ch->struct_size != sizeof(cc_burst_channel)) {
+    set_last_error("cc_burst_channel: NULL, or struct_size is not sizeof(cc_burst_channel)");
+    return CC_ERR_INVALID_ARGUMENT;
+  }
+  if (ch->interleave < 1 || ch->interleave > kInterleaveMax) {
+    set_last_error("the interleaving depth is 1 .. 256");
+    return CC_ERR_INVALID_ARGUMENT;
+  }
+  if (frames % ch->interleave || first_frame % ch->interleave) {
+    set_last_error("frames and first_frame must be multiples of the interleaving depth");
+    return CC_ERR_INVALID_ARGUMENT;
+  }
+  for (double p : {ch->p_gb, ch->p_bg, ch->p_error_good, ch->p_error_bad})
+    if (!std::isfinite(p) || p < 0.0 || p > 1.0) {
+      set_last_error("p_gb, p_bg, p_error_good and p_error_bad must be finite and in [0, 1]");
+      return CC_ERR_INVALID_ARGUMENT;
+    }
+  if (ch->p_gb + ch->p_bg == 0.0) {
+    set_last_error("p_gb + p_bg must be > 0: the chain needs a stationary distribution");
+    return CC_ERR_INVALID_ARGUMENT;
+  }
+  if (needs_code(code) != CC_OK) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = not_wide(code)) return rc;
+  if (code->tab.family == CC_FAMILY_RS && (code->desc.mu != 1 || code->desc.step != 1)) {
+    set_last_error("the Monte-Carlo routes serve RS codes with roots alpha^1..alpha^2t (mu = step = 1) only");
+    return CC_ERR_UNSUPPORTED;
+  }
+  if (random_codewords && code->desc.coding != CC_CODING_DIVISION && code->desc.coding != CC_CODING_MULTIPLICATION)
+    return CC_ERR_INVALID_ARGUMENT;
+  if (code->device == CC_DEVICE_NONE) return CC_ERR_NO_DEVICE;
+  return CC_OK;
+}
+
+int cc_mc_run_burst_dev(const cc_code *code, const cc_burst_channel *ch, uint64_t seed, uint64_t first_frame,
+                        size_t frames, int random_codewords, uint64_t *d_counters, void *stream) {
+  if (!code || !d_counters) return CC_ERR_INVALID_ARGUMENT;
+  const int rc = burst_supported(code, ch, first_frame, frames, random_codewords);
+  if (rc != CC_OK) return rc;
+  DeviceGuard guard(code->device);
+  return mc_run_burst(const_cast<cc_code *>(code), *ch, seed, first_frame, frames, random_codewords, d_counters,
+                      static_cast<hipStream_t>(stream));
+}
+
+int cc_burst_channel_dev(const cc_code *code, const cc_burst_channel *ch, uint64_t seed, uint64_t first_frame,
+                         size_t frames, int random_codewords, uint8_t *d_recv, uint8_t *d_sent, uint8_t *d_state,
+                         void *stream) {
+  if (!code || (frames && !d_recv)) return CC_ERR_INVALID_ARGUMENT;
+  const int rc = burst_supported(code, ch, first_frame, frames, random_codewords);
+  if (rc != CC_OK) return rc;
+  DeviceGuard guard(code->device);
+  return mc_burst(const_cast<cc_code *>(code), *ch, seed, first_frame, frames, random_codewords, d_recv, d_sent, d_state,
+                  static_cast<hipStream_t>(stream));
+}
+
 int cc_diag_table(const cc_code *code, uint16_t *out, size_t cap, uint32_t *D, uint32_t *LPF, uint32_t *links) {
   if (!code || !out) return -1;
   if (code->matrix_only || code->wide || !code->custom_H.empty()) return 0;

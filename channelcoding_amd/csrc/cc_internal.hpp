@@ -266,6 +266,11 @@ int mc_run_discrete(cc_code *code, double p_error, double p_erasure, uint64_t se
 int mc_discrete(cc_code *code, double p_error, double p_erasure, uint64_t seed, uint64_t first_frame, size_t frames,
                 int random_codewords, uint8_t *d_recv, uint16_t *d_erasures, uint32_t *d_erasure_offsets,
                 uint8_t *d_sent, hipStream_t stream);
+// (ch checked by the caller: depth 1 .. 256, frames and first_frame multiples of it, probabilities in [0, 1])
+int mc_run_burst(cc_code *code, const cc_burst_channel &ch, uint64_t seed, uint64_t first_frame, size_t frames,
+                 int random_codewords, uint64_t *d_counters, hipStream_t stream);
+int mc_burst(cc_code *code, const cc_burst_channel &ch, uint64_t seed, uint64_t first_frame, size_t frames,
+             int random_codewords, uint8_t *d_recv, uint8_t *d_sent, uint8_t *d_state, hipStream_t stream);
 int minsum_kernel_info(const cc_code *code, std::string &name, uint32_t &frames_per_wg, uint32_t &threads,
                        uint32_t &lds);
 

@@ -951,4 +951,293 @@ int mc_discrete(cc_code *code, double p_error, double p_erasure, uint64_t seed, 
   return w.fence_out(stream);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Gilbert-Elliott burst channel along the transmission order of symbol-interleaved blocks.
+//
+//   block     global block gb = gf / I holds the frames gb I .. gb I + I - 1; its N = n I symbols are sent in the order of
+//             the interleaved layout, t = p I + j being symbol p of frame j.  Every block runs a chain of its own from the
+//             stationary distribution: its output depends on (seed, parameters, I, gb) only.
+//   draws     Philox counter (gb_lo, gb_hi, c2, domain), word t & 3 of c2 = t >> 2: domain 5 the transition word a_t
+//             (good -> bad iff a_t < GB, bad -> good iff a_t < BG; c2 = 0xFFFFFFFF, word 0 < S: the chain starts bad),
+//             domain 6 the error word (u_t < PB in the bad state, < PG in the good one), domain 7 the error value as on
+//             the discrete channels.  Symbol t sees the state BEFORE the transition a_t.
+//   scan      a step is a map {good, bad} -> {good, bad}: two bits, bit s = the image of state s.  Maps compose
+//             associatively, so the chain is a prefix scan: a lane composes the maps of its four symbols, the lanes of a
+//             block's group scan the composites with shuffles, and the map before a lane, applied to the state the pass was
+//             entered in, is the state of the lane's first symbol.
+namespace {
+
+constexpr uint32_t MAP_IDENTITY = 2u;  // good -> good (bit 0 clear), bad -> bad (bit 1 set)
+
+__device__ __forceinline__ uint32_t map_apply(uint32_t m, uint32_t s) { return (m >> s) & 1u; }
+// first f, then g
+__device__ __forceinline__ uint32_t map_compose(uint32_t f, uint32_t g) {
+  return map_apply(g, f & 1u) | map_apply(g, (f >> 1) & 1u) << 1;
+}
+
+struct BurstThresholds {
+  unsigned long long GB, BG, PG, PB, S;
+};
+
+// 4 bytes to base[at .. at + 4): one dword store where the address allows it
+__device__ __forceinline__ void store4(uint8_t *__restrict__ base, unsigned long long at, const uint32_t v[4]) {
+  uint8_t *dst = base + at;
+  if ((reinterpret_cast<uintptr_t>(dst) & 3u) == 0) {
+    *reinterpret_cast<uint32_t *>(dst) = v[0] | v[1] << 8 | v[2] << 16 | v[3] << 24;
+  } else {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) dst[s] = static_cast<uint8_t>(v[s]);
+  }
+}
+
+// G = 2^group_log2 lanes per block (the smallest power of two >= ceil(N / 4), at most a wavefront): lane q owns the four
+// transmission indices 4 (pass G + q) .. + 3 of its block, a block longer than 4 G = 256 symbols runs in `passes` passes
+// and carries the last lane's exit state into the next.  Every lane of the grid makes the same number of trips and passes
+// (the shuffles of the scan want whole groups), a group without a block left runs them on identity maps.
+// sent: frame-major words of the chunk (nullptr: the all-zero word).  Frame-major output (frame_major != 0, the Monte-Carlo
+// route): symbol t of block b to (b I + t % I) n + t / I of recv, or +-1 floats to soft.  Otherwise (channel only) recv,
+// sent_out and state (the latter two may be nullptr) in transmission order, b N + t.
+__global__ void __launch_bounds__(256)
+burst_kernel(float *__restrict__ soft, uint8_t *__restrict__ recv, uint8_t *__restrict__ sent_out,
+             uint8_t *__restrict__ state, const uint8_t *__restrict__ sent, int n, int I, int group_log2, int passes,
+             int frame_major, uint32_t qm1, unsigned long long first_block, unsigned long long blocks,
+             BurstThresholds th, uint32_t k0, uint32_t k1, unsigned long long *__restrict__ counters) {
+  const int G = 1 << group_log2;
+  const uint32_t N = static_cast<uint32_t>(n) * static_cast<uint32_t>(I);
+  const unsigned long long tid = static_cast<unsigned long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  const unsigned long long ngroups = (static_cast<unsigned long long>(gridDim.x) * blockDim.x) >> group_log2;
+  const unsigned long long group = tid >> group_log2;
+  const int qd = static_cast<int>(tid & static_cast<unsigned long long>(G - 1));
+  const unsigned long long trips = (blocks + ngroups - 1) / ngroups;
+  // (p, j) = (t / I, t % I) of the lane's first symbol: divided once here, advanced by additions from pass to pass
+  const uint32_t p_first = static_cast<uint32_t>(4 * qd) / static_cast<uint32_t>(I);
+  const uint32_t j_first = static_cast<uint32_t>(4 * qd) % static_cast<uint32_t>(I);
+  const uint32_t p_pass = static_cast<uint32_t>(4 * G) / static_cast<uint32_t>(I);
+  const uint32_t j_pass = static_cast<uint32_t>(4 * G) % static_cast<uint32_t>(I);
+  unsigned c_err = 0;
+  uint32_t start_bad = 0;  // lane q: whether the block of trip (tr & ~(G - 1)) + q starts in the bad state
+  for (unsigned long long tr = 0; tr < trips; ++tr) {
+    // the start draw is one word per block: every G trips lane q draws it for the group's block of trip tr + q
+    if ((tr & static_cast<unsigned long long>(G - 1)) == 0) {
+      const unsigned long long gb = first_block + group + (tr + qd) * ngroups;
+      const Philox i0 = philox4x32_10(static_cast<uint32_t>(gb), static_cast<uint32_t>(gb >> 32), 0xFFFFFFFFu, 5u, k0, k1);
+      start_bad = static_cast<unsigned long long>(i0.c[0]) < th.S ? 1u : 0u;
+    }
+    uint32_t carry = __shfl(start_bad, static_cast<int>(tr & static_cast<unsigned long long>(G - 1)), G);
+    const unsigned long long b = group + tr * ngroups;
+    const bool live = b < blocks;
+    const unsigned long long gb = first_block + b, at_block = b * N;
+    const uint32_t g0 = static_cast<uint32_t>(gb), g1 = static_cast<uint32_t>(gb >> 32);
+    uint32_t p0 = p_first, j0 = j_first;
+    for (int ps = 0; ps < passes; ++ps) {
+      const uint32_t c2 = static_cast<uint32_t>(ps * G + qd), t0 = 4 * c2;
+      const int cnt = !live || t0 >= N ? 0 : N - t0 < 4 ? static_cast<int>(N - t0) : 4;
+      uint32_t step[4] = {MAP_IDENTITY, MAP_IDENTITY, MAP_IDENTITY, MAP_IDENTITY}, mine = MAP_IDENTITY;
+      if (cnt) {
+        const Philox a = philox4x32_10(g0, g1, c2, 5u, k0, k1);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const unsigned long long x = a.c[s];
+          if (s < cnt) step[s] = (x < th.GB ? 1u : 0u) | (x < th.BG ? 0u : 2u);
+        }
+        mine = map_compose(map_compose(step[0], step[1]), map_compose(step[2], step[3]));
+      }
+      uint32_t incl = mine;
+      for (int d = 1; d < G; d <<= 1) {
+        const uint32_t lower = __shfl_up(incl, d, G);
+        if (qd >= d) incl = map_compose(lower, incl);
+      }
+      const uint32_t before = __shfl_up(incl, 1, G), last = __shfl(incl, G - 1, G);
+      uint32_t st = map_apply(qd ? before : MAP_IDENTITY, carry);  // the state of symbol t0
+      carry = map_apply(last, carry);
+      if (cnt) {
+        const Philox u = philox4x32_10(g0, g1, c2, 6u, k0, k1);
+        uint32_t bad[4] = {0u, 0u, 0u, 0u};
+        unsigned wrong = 0;  // bit s: symbol t0 + s
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          bad[s] = st;
+          wrong |= (s < cnt && static_cast<unsigned long long>(u.c[s]) < (st ? th.PB : th.PG)) ? 1u << s : 0u;
+          st = map_apply(step[s], st);
+        }
+        uint32_t e[4] = {1u, 1u, 1u, 1u};
+        if (wrong && qm1 > 1) {
+          const Philox v = philox4x32_10(g0, g1, c2, 7u, k0, k1);
+#pragma unroll
+          for (int s = 0; s < 4; ++s) e[s] = 1u + static_cast<uint32_t>((static_cast<unsigned long long>(v.c[s]) * qm1) >> 32);
+        }
+        c_err += static_cast<unsigned>(__builtin_popcount(wrong));
+        // where the four symbols lie in the frame-major chunk: frame j of the block, position p
+        uint32_t fm[4], p = p0, j = j0;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          fm[s] = j * static_cast<uint32_t>(n) + p;
+          if (++j == static_cast<uint32_t>(I)) {
+            j = 0;
+            ++p;
+          }
+        }
+        uint32_t c[4] = {0u, 0u, 0u, 0u}, r[4];
+        if (sent) {
+#pragma unroll
+          for (int s = 0; s < 4; ++s)
+            if (s < cnt) c[s] = sent[at_block + fm[s]];
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) r[s] = ((wrong >> s) & 1u) ? c[s] ^ e[s] : c[s];
+        if (frame_major) {
+#pragma unroll
+          for (int s = 0; s < 4; ++s) {
+            if (s >= cnt) continue;
+            if (soft) soft[at_block + fm[s]] = r[s] ? -1.0f : 1.0f;
+            else recv[at_block + fm[s]] = static_cast<uint8_t>(r[s]);
+          }
+        } else if (cnt == 4) {
+          store4(recv, at_block + t0, r);
+          if (sent_out) store4(sent_out, at_block + t0, c);
+          if (state) store4(state, at_block + t0, bad);
+        } else {
+          for (int s = 0; s < cnt; ++s) {
+            recv[at_block + t0 + s] = static_cast<uint8_t>(r[s]);
+            if (sent_out) sent_out[at_block + t0 + s] = static_cast<uint8_t>(c[s]);
+            if (state) state[at_block + t0 + s] = static_cast<uint8_t>(bad[s]);
+          }
+        }
+      }
+      p0 += p_pass;
+      j0 += j_pass;
+      if (j0 >= static_cast<uint32_t>(I)) {
+        j0 -= static_cast<uint32_t>(I);
+        ++p0;
+      }
+    }
+  }
+  if (counters) {
+    for (int m = 32; m >= 1; m >>= 1) c_err += __shfl_xor(c_err, m, 64);
+    if ((threadIdx.x & 63) == 0 && c_err)
+      atomicAdd(&counters[CC_MC_CHANNEL_BIT_ERRORS], static_cast<unsigned long long>(c_err));
+  }
+}
+
+BurstThresholds burst_thresholds(const cc_burst_channel &ch) {
+  auto fix = [](double x) { return static_cast<unsigned long long>(std::llround(x * 4294967296.0)); };
+  return BurstThresholds{fix(ch.p_gb), fix(ch.p_bg), fix(ch.p_error_good), fix(ch.p_error_bad),
+                         fix(ch.p_gb / (ch.p_gb + ch.p_bg))};
+}
+
+struct BurstIO {
+  float *soft = nullptr;
+  uint8_t *recv = nullptr, *sent_out = nullptr, *state = nullptr;
+  bool frame_major = false;
+};
+
+// the channel over the m / I blocks of frames [first_frame, first_frame + m), both multiples of I
+int launch_burst(const cc_code *code, const cc_burst_channel &ch, uint64_t seed, uint64_t first_frame, size_t m,
+                 const uint8_t *sent, const BurstIO &io, unsigned long long *d_counters, hipStream_t stream) {
+  const int n = static_cast<int>(code->tab.n), I = static_cast<int>(ch.interleave);
+  const int N = n * I, g = N > 256 ? 6 : log2_lanes(N), passes = (N + (4 << g) - 1) / (4 << g);
+  const uint32_t qm1 = code->tab.family == CC_FAMILY_RS ? (1u << code->tab.q) - 1u : 1u;
+  const unsigned long long blocks = m / ch.interleave, items = blocks << g;
+  // depth 1 is frame-major as it is: the dword stores of the transmission-order branch serve it
+  const bool fm = io.frame_major && (I > 1 || io.soft);
+  hipLaunchKernelGGL(burst_kernel, dim3(grid_for(code, items)), dim3(256), 0, stream, io.soft, io.recv, io.sent_out,
+                     io.state, sent, n, I, g, passes, fm ? 1 : 0, qm1,
+                     static_cast<unsigned long long>(first_frame / ch.interleave), blocks, burst_thresholds(ch),
+                     static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), d_counters);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "burst channel kernel launch");
+  return CC_OK;
+}
+
+// the largest multiple of I within the chunk of the discrete route
+size_t burst_chunk(size_t frames, uint32_t I) {
+  const size_t cap = DISCRETE_CHUNK / I * I;
+  return frames < cap ? frames : cap;
+}
+
+}  // namespace
+
+// Monte-Carlo over the burst channel: the route of mc_run_discrete (lock, workspace, fence, one counting pass per chunk)
+// with chunks of whole blocks.  The channel kernel writes the received symbols frame-major, so the plain decoders and
+// count_kernel take them as they take the discrete channel's; received bytes (or the +-1 floats of a min-sum handle)
+// in w.llr.
+int mc_run_burst(cc_code *code, const cc_burst_channel &ch, uint64_t seed, uint64_t first_frame, size_t frames,
+                 int random_codewords, uint64_t *d_counters, hipStream_t stream) {
+  if (frames == 0) return CC_OK;
+  const size_t chunk = burst_chunk(frames, ch.interleave);
+  if (!code->mc) code->mc = new McWorkspace();
+  std::lock_guard<std::mutex> guard(code->mc->lock);
+  int rc = ensure_workspace(code, chunk);
+  if (rc != CC_OK) return rc;
+  McWorkspace &w = *code->mc;
+  rc = w.fence_in(stream);
+  if (rc != CC_OK) return rc;
+  const size_t n = code->tab.n;
+  unsigned long long *counters = reinterpret_cast<unsigned long long *>(d_counters);
+  for (size_t done = 0; done < frames; done += chunk) {
+    const size_t m = frames - done < chunk ? frames - done : chunk;
+    uint8_t *sent = random_codewords ? w.sent : nullptr;
+    if (random_codewords) {
+      rc = launch_discrete_sent(code, seed, first_frame + done, m, w.sent, w.msg, stream);
+      if (rc != CC_OK) return rc;
+    }
+    BurstIO io;
+    io.frame_major = true;
+    if (code->soft) io.soft = w.llr;
+    else io.recv = reinterpret_cast<uint8_t *>(w.llr);
+    rc = launch_burst(code, ch, seed, first_frame + done, m, sent, io, counters, stream);
+    if (rc != CC_OK) return rc;
+    if (code->soft)
+      rc = launch_minsum(code, w.llr, nullptr, nullptr, w.hard, nullptr, w.iters, w.status, m, stream);
+    else
+      rc = launch_algebraic(code, false, io.recv, nullptr, nullptr, w.hard, w.nerr, w.status, m, stream);
+    if (rc != CC_OK) return rc;
+    const unsigned long long blocks = (m + 15) / 16;
+    const unsigned long long max_grid = static_cast<unsigned long long>(code->num_cus) * 8;
+    hipLaunchKernelGGL(count_kernel, dim3(static_cast<int>(blocks < max_grid ? blocks : max_grid)), dim3(256), 0, stream,
+                       w.hard, sent, code->soft ? w.iters : nullptr, w.status, static_cast<int>(n),
+                       code->desc.iterations, static_cast<unsigned long long>(m), counters);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "count kernel launch");
+  }
+  return w.fence_out(stream);
+}
+
+// cc_burst_channel_dev: channel only, chunked in whole blocks; the transmitted words are made frame-major in the
+// workspace and leave the channel kernel in transmission order
+int mc_burst(cc_code *code, const cc_burst_channel &ch, uint64_t seed, uint64_t first_frame, size_t frames,
+             int random_codewords, uint8_t *d_recv, uint8_t *d_sent, uint8_t *d_state, hipStream_t stream) {
+  if (frames == 0) return CC_OK;
+  const size_t chunk = burst_chunk(frames, ch.interleave);
+  if (!code->mc) code->mc = new McWorkspace();
+  std::lock_guard<std::mutex> guard(code->mc->lock);
+  int rc = CC_OK;
+  if (random_codewords) {
+    rc = ensure_workspace(code, chunk);
+    if (rc != CC_OK) return rc;
+  }
+  McWorkspace &w = *code->mc;
+  rc = w.fence_in(stream);
+  if (rc != CC_OK) return rc;
+  const size_t n = code->tab.n;
+  for (size_t done = 0; done < frames; done += chunk) {
+    const size_t m = frames - done < chunk ? frames - done : chunk;
+    BurstIO io;
+    io.recv = d_recv + done * n;
+    io.state = d_state ? d_state + done * n : nullptr;
+    const uint8_t *sent = nullptr;
+    if (random_codewords) {
+      rc = launch_discrete_sent(code, seed, first_frame + done, m, w.sent, w.msg, stream);
+      if (rc != CC_OK) return rc;
+      sent = w.sent;
+      io.sent_out = d_sent ? d_sent + done * n : nullptr;
+    } else if (d_sent) {
+      CC_HIP_TRY(hipMemsetAsync(d_sent + done * n, 0, m * n, stream));
+    }
+    rc = launch_burst(code, ch, seed, first_frame + done, m, sent, io, nullptr, stream);
+    if (rc != CC_OK) return rc;
+  }
+  return w.fence_out(stream);
+}
+
 }  // namespace ccamd

@@ -14,7 +14,8 @@ CPU) of the 64-word counter vector per point gives every rank the totals -- whic
 count of the next point needs.  Totals are bit-identical for any number of ranks.
 
 discrete_simulation runs the same harness over the BSC, the BEC or both at once (cc_mc_run_discrete_dev; for RS codes
-the q-ary symmetric and the symbol erasure channel), on a ladder of channel probabilities.
+the q-ary symmetric and the symbol erasure channel), on a ladder of channel probabilities; burst_simulation over the
+two-state Gilbert-Elliott channel run along symbol-interleaved blocks (cc_mc_run_burst_dev), sharded in whole blocks.
 
 The ladder's start point follows the reference's own Shannon-limit look-up ``ebno()`` (simulation.c++:21-70)
 including its indexing (see `reference_ebno`), so every "<decoder>.log" starts on the line the reference's does.
@@ -117,6 +118,12 @@ def shard(total, rank, world):
     return lo, hi - lo
 
 
+def shard_blocks(total, rank, world, interleave):
+    """`shard` cut at multiples of `interleave`: the contiguous range of whole blocks owned by `rank`."""
+    lo, count = shard(total // interleave, rank, world)
+    return lo * interleave, count * interleave
+
+
 class DeviceBackend:
     """Counts one shard of one Eb/N0 point on this rank's GPU through cc_mc_run_dev."""
 
@@ -138,10 +145,11 @@ class DeviceBackend:
 
 
 class _ShardedSimulation:
-    """What the AWGN and the discrete-channel ladders share: the shard of this rank, the one all-reduce per point,
+    """What the AWGN, the discrete-channel and the burst-channel ladders share: the shard of this rank, the one all-reduce per point,
     rank 0's log file (its success agreed with every rank before the first collective) and the adaptive ladder."""
 
     counter_names = COUNTER_NAMES
+    interleave = 1  # frames are counted and sharded in whole blocks of this many (burst_simulation)
 
     def _dist(self):
         try:
@@ -156,9 +164,10 @@ class _ShardedSimulation:
         """The reduced counters of `frames` frames of one point, sharded over the ranks."""
         dist = self._dist()
         rank, world = (dist.get_rank(), dist.get_world_size()) if dist else (0, 1)
-        first, count = shard(frames, rank, world)
-        # every point draws from its own stretch of the global frame sequence
-        base = point_index << 40
+        I = self.interleave
+        first, count = shard_blocks(-(-frames // I) * I, rank, world, I)
+        # every point draws from its own stretch of the global frame sequence, from a block boundary on
+        base = (point_index << 40) // I * I
         counters = self.backend.run(point, self.seed, base + first, count)
         if dist:
             dist.all_reduce(counters, op=dist.ReduceOp.SUM)  # the path's only exchange step
@@ -349,6 +358,81 @@ class discrete_simulation(_ShardedSimulation):
     def __call__(self):
         row = (lambda pt: pt[0]) if self.channel == "bsec" else (lambda pt: pt)
         return self._ladder("%s.%s.log" % (self.code.to_string(), self.channel), "p", row)
+
+
+# ---- the Gilbert-Elliott burst channel along interleaved blocks (cc_mc_run_burst_dev) ----
+class BurstBackend:
+    """Counts one shard of one burst-channel point on this rank's GPU through cc_mc_run_burst_dev; a point is the symbol
+    error probability of the bad state."""
+
+    def __init__(self, code, interleave=1, p_gb=0.0, p_bg=1.0, p_error_good=0.0, random_codewords=False):
+        import torch
+        self.torch = torch
+        self.code = code
+        self.interleave, self.p_gb, self.p_bg, self.p_error_good = int(interleave), p_gb, p_bg, p_error_good
+        self.random_codewords = bool(random_codewords)
+        self.device = torch.device("cuda", torch.cuda.current_device())
+
+    def run(self, point, seed, first_frame, frames):
+        torch = self.torch
+        ch = capi.BurstChannel(self.interleave, self.p_gb, self.p_bg, self.p_error_good, point)
+        counters = torch.zeros(capi.MC_NCOUNTERS, dtype=torch.int64, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = capi.lib().cc_mc_run_burst_dev(self.code._h, C.byref(ch), int(seed), int(first_frame), int(frames),
+                                            int(self.random_codewords), C.c_void_p(counters.data_ptr()), stream)
+        capi.check(rc, "cc_mc_run_burst_dev")
+        return counters  # stays on the device: reduced with RCCL
+
+
+def _probability(value, what):
+    p = float(value)
+    if not (math.isfinite(p) and 0.0 <= p <= 1.0):
+        raise ValueError("bad %s %r: a probability must be finite and in [0, 1]" % (what, value))
+    return p
+
+
+class burst_simulation(_ShardedSimulation):
+    """Word-error rate over the two-state Gilbert-Elliott channel run along symbol-interleaved blocks of depth
+    `interleave` -- what an interleaver of that depth buys on a channel with memory.  p_gb / p_bg: the transition
+    probabilities good -> bad / bad -> good per transmitted symbol; a point is p_error_bad, the symbol error probability
+    in the bad state (default points: discrete_ladder()), p_error_good that of the good state.  The frames of a point are
+    rounded up to whole blocks and the ranks' shards cut at blocks.  Rank 0 writes "<to_string()>.burst.log"."""
+
+    counter_names = DISCRETE_COUNTER_NAMES
+
+    def __init__(self, code, interleave=1, p_gb=0.01, p_bg=0.1, p_error_good=0.0, p_error_bad=None, points=None, seed=0,
+                 random_codewords=True, backend=None, log_dir=None, max_samples=None, samples_per_point=None):
+        self.interleave = int(interleave)
+        if not 1 <= self.interleave <= 256:
+            raise ValueError("the interleaving depth is 1 .. 256")
+        self.p_gb, self.p_bg = _probability(p_gb, "p_gb"), _probability(p_bg, "p_bg")
+        self.p_error_good = _probability(p_error_good, "p_error_good")
+        if self.p_gb + self.p_bg == 0.0:
+            raise ValueError("p_gb + p_bg must be > 0")
+        if points is None:
+            points = discrete_ladder() if p_error_bad is None else [p_error_bad]
+        self._points = [_probability(pt, "point") for pt in points]
+        self.code = code
+        self.seed = int(seed)
+        self.backend = backend if backend is not None else BurstBackend(
+            code, self.interleave, self.p_gb, self.p_bg, self.p_error_good, random_codewords)
+        self.log_dir = log_dir
+        self.max_samples = max_samples
+        self.samples_per_point = samples_per_point
+
+    def points(self):
+        return list(self._points)
+
+    def run_point(self, point, frames, point_index=0):
+        """Decode `frames` frames (rounded up to whole blocks) of one point, sharded over the ranks."""
+        res = self._counters(point, frames, point_index)
+        res["p_error_bad"], res["interleave"] = point, self.interleave
+        res["wer"] = res["word_errors"] / max(1, res["frames"])
+        res["ber"] = res["bit_errors"] / max(1, res["frames"] * self.code.n)  # wrong symbols per symbol for RS
+        return res
+
+    def __call__(self):
+        return self._ladder("%s.burst.log" % self.code.to_string(), "p", lambda pt: pt)
 
 
 class bitflip_simulation:

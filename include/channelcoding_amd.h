@@ -291,6 +291,41 @@ int cc_discrete_channel_dev(const cc_code *code, double p_error, double p_erasur
                             uint64_t first_frame, size_t frames, int random_codewords, uint8_t *d_recv,
                             uint16_t *d_erasures, uint32_t *d_erasure_offsets, uint8_t *d_sent, void *stream);
 
+/* ---- batched Monte-Carlo over a channel with memory: the two-state Gilbert-Elliott channel (Gilbert, BSTJ 39, 1960;
+ *      Elliott, BSTJ 42, 1963), run along the transmission order of symbol-interleaved blocks (below: block gb = gf / I
+ *      holds the global frames gb I .. gb I + I - 1, its N = n I symbols are sent in the order of the layout, index
+ *      t = p I + j being symbol p of frame j) -- the channel on which interleaving depth matters.  `frames` and
+ *      `first_frame` are multiples of I.  Every block runs a chain of its own from the stationary distribution, so a
+ *      block's channel output depends only on (seed, the parameters, I, gb), not on sharding or chunking.
+ *      Thresholds, on the host in 64 bits: X = llround(x 2^32) for GB (p_gb), BG (p_bg), PG (p_error_good), PB
+ *      (p_error_bad) and S (p_gb / (p_gb + p_bg), divided in double); a draw compares a 32-bit word, zero-extended,
+ *      against one: 1.0 is always, 0.0 never.  Philox4x32-10, key (seed_lo, seed_hi), counter (gb_lo, gb_hi, c2, domain):
+ *        domain 5, c2 = 0xFFFFFFFF   the chain starts bad (s_0 = 1) iff word 0 < S
+ *        domain 5, c2 = t >> 2        word t & 3 = a_t: from good, s_t+1 is bad iff a_t < GB; from bad, good iff a_t < BG
+ *        domain 6, c2 = t >> 2        word t & 3 = u_t: symbol t is in error iff u_t < (s_t bad ? PB : PG)
+ *        domain 7, c2 = t >> 2        word t & 3 = v_t: the error value e = 1 + ((v_t (q_sym - 1)) >> 32), as above
+ *      Symbol t sees s_t, the state before the transition a_t.  Received = sent ^ e where in error; no erasures.
+ *      Transmitted words, handles served and counters as cc_mc_run_discrete_dev (CC_MC_CHANNEL_BIT_ERRORS = symbols drawn
+ *      in error, CC_MC_CHANNEL_ERASURES stays 0); min-sum handles decode +1 / -1 for a received 0 / 1.
+ *      CC_ERR_INVALID_ARGUMENT: NULL ch / counters / d_recv, a wrong struct_size, I = 0 or I > 256, frames or first_frame
+ *      no multiple of I, a probability outside [0, 1] or not finite, p_gb + p_bg == 0, a handle of cc_minsum_create,
+ *      random codewords with a coding the encoder cannot do.  CC_ERR_UNSUPPORTED: q > 8, RS with mu / step != 1. ---- */
+typedef struct cc_burst_channel {
+  uint32_t struct_size;             /* = sizeof(cc_burst_channel) */
+  uint32_t interleave;              /* I, 1 .. 256: depth of the blocks the chain runs along */
+  double p_gb, p_bg;                /* P(good -> bad), P(bad -> good) per transmitted symbol */
+  double p_error_good, p_error_bad; /* symbol error probability in each state */
+} cc_burst_channel;
+/* channel only.  d_recv and d_sent (may be NULL) are in the interleaved layout [frames/I][n][I], i.e. in transmission
+ * order; depth 1 is frame-major.  d_state (may be NULL): one byte per transmitted symbol, 0 good / 1 bad, same order. */
+int cc_burst_channel_dev(const cc_code *code, const cc_burst_channel *ch, uint64_t seed, uint64_t first_frame,
+                         size_t frames, int random_codewords, uint8_t *d_recv, uint8_t *d_sent, uint8_t *d_state,
+                         void *stream);
+/* channel -> decode with the handle's algorithm -> count: exactly what the channel-only call, cc_deinterleave_dev, the
+ * plain decode and a comparison with the words sent count */
+int cc_mc_run_burst_dev(const cc_code *code, const cc_burst_channel *ch, uint64_t seed, uint64_t first_frame,
+                        size_t frames, int random_codewords, uint64_t *d_counters, void *stream);
+
 /* ---- fields GF(2^q) with q = 9 .. 15 (galois.h:44-53: "uint16_t allows galois fields up to 2^15"): symbols are
  *      16 bits wide, n = 2^q - 1 <= 32767.  Hard-decision algorithms (PGZ as bounded-distance BM, BM, Euklid), with
  *      erasures; division_tag coding.  The byte entry points above return CC_ERR_UNSUPPORTED on such a handle and
@@ -376,7 +411,8 @@ int cc_decode_hard_packed_batch(const cc_code *code, const uint8_t *in, const ui
  *      of the words exists), RS(255, 255 - 2t) with 2t = 16 or 32 is encoded the same way, division-coded words are
  *      extracted by a strided copy (any q); every other call is de-interleaved into workspace of the handle, sent
  *      through the plain router and interleaved again.  CC_AMD_INTERLEAVED_NATIVE=0 (read once) sends everything the
- *      second way.  Not offered interleaved: min-sum, the f32 hard entry points, the Monte-Carlo calls, packed words. ---- */
+ *      second way.  Not offered interleaved: min-sum, the f32 hard entry points, the Monte-Carlo calls (but for the burst
+ *      channel above, which runs along the blocks), packed words. ---- */
 /* 1: a hard-decode call of B frames at depth I takes the native route under the settings in force (depth 1: the plain
  * call, reported as 1), 0: the generic one; a negative cc_status where the call itself would be refused */
 int cc_interleaved_route(const cc_code *code, size_t B, uint32_t interleave, int with_erasures);
