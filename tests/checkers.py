@@ -1,6 +1,8 @@
 """ctypes bindings for the two CHECKERS (test infrastructure only):
 
 * ``Oracle``  -- oracle/libcc_oracle.so, the repo's plain-C restatement.
+* ``WideOracle`` -- oracle/libcc_oracle_wide.so, the algebraic half of the same restatement built with 16-bit
+  symbols (q <= 15, caller-named modular polynomial).
 * ``RefLib``  -- oracle/_ref/libccref_o{0,1}.so, the real reference compiled by
   oracle/Makefile (present only where it has been built; it travels to the GPU
   box as a prebuilt file, /root/reference itself does not).
@@ -203,6 +205,144 @@ class Oracle:
                                            len(er), _ptr(b[i]), _ptr(L[i]), C.byref(it))
             iters[i] = it.value
         return b, L, iters, status
+
+
+class OrcwCode(C.Structure):
+    _fields_ = [
+        ("family", C.c_int), ("q", C.c_int), ("t", C.c_int), ("n", C.c_int), ("k", C.c_int), ("l", C.c_int),
+        ("dmin", C.c_int), ("mu", C.c_int), ("step", C.c_int), ("coding", C.c_int), ("size", C.c_int),
+        ("poly", C.c_uint),
+        ("exp_", C.c_uint16 * 65536), ("log_", C.c_uint16 * 65536),
+        ("g", C.c_uint16 * 32768), ("glen", C.c_int), ("h", C.c_uint16 * 32768), ("hlen", C.c_int),
+        ("roots", C.c_uint16 * 256), ("nroots", C.c_int),
+    ]
+
+
+FRAME_ERASURES = 4
+
+
+class WideOracle:
+    """One code of the 16-bit build of the plain-C oracle (oracle/cc_oracle_wide.c): GF(2^q), q = 2 .. 15, symbols
+    uint16; poly = 0 takes the q <= 8 default of the byte build.  The interface of Oracle, plus:
+
+    * erasures may be one list per frame (a sequence of sequences, as many as frames);
+    * RS roots other than (mu, step) = (1, 1): g, h, roots, encode, extract and syndromes are the C build's for that
+      code; correct_hard decodes through the equivalence of tests/rs_roots_model.py (T^-1 . (1, 1) decode . T), the
+      project's stated checker for such codes -- the reference's own rs::error_values fails them (DESIGN 4.9);
+    * more than 2t erasures under the BM / Euklid tags: CC_FRAME_ERASURES on a word with a non-zero syndrome, the word
+      untouched ("more erasures than 2t": no reference behaviour exists there).
+    correct_hard(..., raw=True) is the C function as it stands, without the last two rules: what is compared with the
+    byte build."""
+    _lib = None
+
+    @classmethod
+    def lib(cls):
+        if cls._lib is None:
+            path = os.path.join(ORACLE_DIR, "libcc_oracle_wide.so")
+            if not os.path.exists(path):
+                build_oracle()
+            cls._lib = C.CDLL(path)
+            cls._lib.orcw_code_sizeof.restype = C.c_size_t
+            assert cls._lib.orcw_code_sizeof() == C.sizeof(OrcwCode)
+        return cls._lib
+
+    def __init__(self, family, q, t, poly=0, mu=1, step=1, coding=0):
+        self.c = OrcwCode()
+        rc = self.lib().orcw_code_init(C.byref(self.c), family, q, t, mu, step, coding, C.c_uint(poly))
+        if rc != 0:
+            raise ValueError("orcw_code_init failed: %d" % rc)
+        for name in ("family", "q", "t", "n", "k", "l", "dmin", "mu", "step", "poly"):
+            setattr(self, name, getattr(self.c, name))
+        as_np = lambda a, m: np.frombuffer(a, np.uint16, m).copy()
+        self.g, self.h = as_np(self.c.g, self.c.glen), as_np(self.c.h, self.c.hlen)
+        self.roots = as_np(self.c.roots, self.c.nroots)
+        self.exp, self.log = as_np(self.c.exp_, 2 * self.c.size), as_np(self.c.log_, 2 * self.c.size)
+        self._o11 = None
+
+    def to_string(self, alg_name):
+        buf = C.create_string_buffer(128)
+        self.lib().orcw_to_string(C.byref(self.c), alg_name.encode(), buf, 128)
+        return buf.value.decode()
+
+    def encode(self, msg):
+        msg = np.ascontiguousarray(msg, np.uint16)
+        single = msg.ndim == 1
+        msg = msg.reshape(-1, self.l)
+        cw = np.zeros((msg.shape[0], self.n), np.uint16)
+        for i in range(msg.shape[0]):
+            rc = self.lib().orcw_encode(C.byref(self.c), _ptr(msg[i]), _ptr(cw[i]))
+            assert rc == 0, rc
+        return cw[0] if single else cw
+
+    def extract(self, cw):
+        cw = np.ascontiguousarray(cw, np.uint16).reshape(-1, self.n)
+        out = np.zeros((cw.shape[0], self.l), np.uint16)
+        for i in range(cw.shape[0]):
+            self.lib().orcw_extract(C.byref(self.c), _ptr(cw[i]), _ptr(out[i]))
+        return out
+
+    def syndromes(self, b):
+        b = np.ascontiguousarray(b, np.uint16)
+        S = np.zeros(self.c.nroots, np.uint16)
+        self.lib().orcw_syndromes(C.byref(self.c), _ptr(b), _ptr(S))
+        return S
+
+    def locator(self, alg, S, erasures=()):
+        er = np.asarray(erasures, np.uint16)
+        sig = np.zeros(2048, np.uint16)
+        ns, ub = C.c_int(), C.c_int()
+        st = self.lib().orcw_locator(C.byref(self.c), alg, _ptr(np.ascontiguousarray(S, np.uint16)),
+                                     _ptr(er) if len(er) else None, len(er), _ptr(sig), C.byref(ns), C.byref(ub))
+        return st, sig[: ns.value].copy(), ub.value
+
+    @staticmethod
+    def per_frame(erasures, B):
+        """erasures as one list per frame: None / () / a flat list (the same for every frame) / one list per frame"""
+        if erasures is None or len(erasures) == 0:
+            return [()] * B
+        if np.ndim(erasures[0]) == 0:
+            return [list(erasures)] * B
+        assert len(erasures) == B
+        return [list(e) for e in erasures]
+
+    def _raw(self, alg, frames, per):
+        B = frames.shape[0]
+        out = np.zeros((B, self.n), np.uint16)
+        nerr, status, ub = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+        ne, u = C.c_int(), C.c_int()
+        fn = self.lib().orcw_correct_hard
+        for i in range(B):
+            er = np.asarray(per[i], np.uint16)
+            status[i] = fn(C.byref(self.c), alg, _ptr(frames[i]), _ptr(er) if len(er) else None, len(er),
+                           _ptr(out[i]), C.byref(ne), C.byref(u))
+            nerr[i], ub[i] = ne.value, u.value
+        return out, nerr, status, ub
+
+    def correct_hard(self, alg, frames, erasures=(), raw=False):
+        """frames: (B, n) symbols, or float32 (sign -> bit).  Returns out (B, n) u16, nerr, status, ref_ub (B,) i32."""
+        frames = np.ascontiguousarray(frames)
+        if frames.dtype == np.float32:
+            frames = (frames < 0)  # codes.h:43-52
+        frames = np.ascontiguousarray(frames.astype(np.uint16).reshape(-1, self.n))
+        B = frames.shape[0]
+        per = self.per_frame(erasures, B)
+        if raw:
+            return self._raw(alg, frames, per)
+        if (self.mu, self.step) == (1, 1) or self.family != RS:
+            out, nerr, status, ub = self._raw(alg, frames, per)
+        else:
+            import rs_roots_model as M
+            if self._o11 is None:
+                self._o11 = WideOracle(RS, self.q, self.t, self.poly, coding=self.c.coding)
+            o11, nf = self._o11, self.n
+            per11 = [[M.position(p, nf, self.step) for p in e] for e in per]
+            out, nerr, status, ub = o11._raw(alg, M.T(frames, o11.exp, o11.log, nf, self.mu, self.step), per11)
+            out = M.T_inv(out, o11.exp, o11.log, nf, self.mu, self.step)
+        if alg != PGZ or self.family != BCH:  # (BCH + PGZ: bch.h:105-107 is in the C code)
+            for i in range(B):
+                if len(per[i]) > 2 * self.t and self.syndromes(frames[i]).any():
+                    out[i], nerr[i], status[i], ub[i] = frames[i], -1, FRAME_ERASURES, 0
+        return out, nerr, status, ub
 
 
 class RefLib:

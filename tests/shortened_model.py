@@ -8,9 +8,10 @@ nerr = -1.  BCH with the PGZ tag and erasures: the two-trial rule of bch.h:97-14
 Min-sum: over H[:, :N].
 
 `Shortened(mother, N)` takes any full-length model with encode(msg), extract(cw) and correct_hard(alg, frames,
-erasures) on (B, n) arrays: checkers.Oracle (q <= 8), or `Device` below, the device's own full-length
-decoder (q > 8, where there is no oracle: the suite pins that path to the reference's goldens, tests/golden/wide.npz;
-and erasure decoding, which it decodes as one batch so that both handles take the same route).
+erasures) on (B, n) arrays: checkers.Oracle (q <= 8), checkers.WideOracle (16-bit symbols, q <= 15: the same
+restatement built over uint16, pinned by tests/test_wide_oracle.py), or `Device` below, the device's own full-length
+decoder (a second opinion next to the oracle: it decodes the whole batch in one call, so that both handles take the same
+route).
 """
 import numpy as np
 
@@ -76,7 +77,11 @@ class Shortened:
 
     def _plain(self, alg, frame, er):
         """one frame, the mother's decoder on the padded word with the virtual-position rule"""
-        if len(er) > 2 * self.t:  # the device refuses more erasures than 2t (bch.h:105-107) whatever the tag
+        if len(er) > 2 * self.t:  # the device refuses more erasures than 2t (bch.h:105-107) whatever the tag,
+            # on a word with a non-zero syndrome; a codeword comes back as it is (DESIGN 2)
+            _, clean_nerr, clean_st, _ = self.m.correct_hard(alg, pad(frame[None, :], self.m.n), [])
+            if int(clean_st[0]) == FRAME_OK and int(clean_nerr[0]) == 0:
+                return self._hard(frame).copy(), 0, FRAME_OK
             return self._hard(frame).copy(), -1, FRAME_ERASURES
         out, nerr, st, _ = self.m.correct_hard(alg, pad(frame[None, :], self.m.n), er)
         out, nerr, st = out[0], int(nerr[0]), int(st[0])

@@ -11,6 +11,9 @@ import numpy as np
 import pytest
 import torch
 
+import shortened_model as S
+from checkers import BCH, BM, EUKLID, PGZ, WideOracle
+
 import channelcoding_amd as cc
 from channelcoding_amd import capi
 
@@ -187,10 +190,22 @@ def test_native_against_generic_in_a_child_process(tmp_path):
 def test_generic_route_reach(q, t, N, poly, tag):
     code = make(q, t, N, tag, poly)
     rng = np.random.default_rng(100 * q + t)
+    model = None
+    if poly is not None:  # the 16-bit handles: the same frames against the 16-bit oracle as well
+        model = WideOracle(BCH, q, t, poly)
+        model = S.Shortened(model, N) if N else model
     for B in (1, 33, 700):
         assert code.packed_route(B) == 0
         _, rx, _ = received(code, rng, B, t + 3)
-        check_equal(code, rx, dirty_pad=B == 33)
+        want = check_equal(code, rx, dirty_pad=B == 33)
+        if model is not None:
+            alg = {"PGZ": PGZ, "BM": BM, "EUKLID": EUKLID}[tag]
+            m_out, m_nerr, m_st = model.correct_hard(alg, rx)[:3]
+            assert np.array_equal(want["status"] == 0, m_st == 0)
+            assert np.array_equal(want["out"], np.where((m_st == 0)[:, None], m_out, rx))
+            assert np.array_equal(want["nerr"], np.where(m_st == 0, m_nerr, -1))
+            if alg == BM:
+                assert np.array_equal(want["status"], S.native_status(m_st, want["status"]) if N else m_st)
     # torch: int16 symbols on the 16-bit handles
     _, rx, _ = received(code, rng, 65, t + 3)
     want = code.correct_batch(rx)

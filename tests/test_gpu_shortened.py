@@ -8,7 +8,7 @@ import pytest
 import channelcoding_amd as cc
 from channelcoding_amd import capi
 from awgn_model import awgn_reference
-from checkers import BCH, BM, EUKLID, PGZ, RS, Oracle
+from checkers import BCH, BM, EUKLID, PGZ, RS, Oracle, WideOracle
 import shortened_model as S
 from test_discrete_host import bch_message_bits
 from test_gpu_discrete_mc import decode as discrete_decode, erased_mask, mc as discrete_mc
@@ -217,7 +217,9 @@ WIDE = [(BCH, 14, 12, 3000, 0x402B), (RS, 10, 6, 600, 0x409)]
 
 @pytest.mark.parametrize("family,q,t,N,poly", WIDE)
 def test_wide_against_full_length_device(family, q, t, N, poly):
+    """against the device's own full-length decode, and on the same frames against the 16-bit oracle"""
     rng = np.random.default_rng(q)
+    mm = S.Shortened(WideOracle(family, q, t, poly), N)
     for alg in (BM, EUKLID, PGZ):
         full = make(family, q, t, None, alg, modular_polynomial=poly)
         m = S.Shortened(S.Device(full), N)
@@ -225,8 +227,8 @@ def test_wide_against_full_length_device(family, q, t, N, poly):
         hi = 2 if family == BCH else 1 << q
         msg = rng.integers(0, hi, (40, m.l)).astype(np.uint16)
         cw = np.asarray(code.encode_batch(msg))
-        assert np.array_equal(cw, m.encode(msg))
-        assert np.array_equal(np.asarray(code.extract_batch(cw)), msg)
+        assert np.array_equal(cw, m.encode(msg)) and np.array_equal(cw, mm.encode(msg))
+        assert np.array_equal(np.asarray(code.extract_batch(cw)), msg) and np.array_equal(mm.extract(cw), msg)
         rx = cw.copy()
         for f in range(40):
             if f % 5 == 4:
@@ -234,11 +236,15 @@ def test_wide_against_full_length_device(family, q, t, N, poly):
                 continue
             for p in rng.choice(N, int(rng.integers(0, t + 3)), replace=False):
                 rx[f, p] ^= 1 if family == BCH else int(rng.integers(1, hi))
-        check(code.correct_batch(rx), m, alg, rx, None)
+        res = code.correct_batch(rx)
+        check(res, m, alg, rx, None)
+        check(res, mm, alg, rx, None)
         if alg == PGZ and family == RS:
             continue
         per = erasure_lists(rng, m, 40)
-        check(code.correct_batch(rx, erasures=per), m, alg, rx, per)
+        res = code.correct_batch(rx, erasures=per)
+        check(res, m, alg, rx, per)
+        check(res, mm, alg, rx, per)
 
 
 # ---- min-sum over H[:, :N] ----
