@@ -428,7 +428,9 @@ class cyclic:
 
     def packed_route(self, B):
         """1 if correct_batch(packed=True) of B frames without erasures decodes the packed words natively, 0 if it goes
-        through unpack / byte route / pack (cc_packed_route)."""
+        through unpack / byte route / pack (cc_packed_route).  Native: the GF(2^8) calls of the bit-plane chain, and for
+        q = 9 .. 15 the BM and PGZ tags with t <= 31 in calls of at least CC_AMD_PACKED_LONG_MIN_FRAMES (default 1024)
+        frames; the Euklid tag, t = 32 and smaller calls of those codes answer 0.  Both routes return the same result."""
         r = capi.lib().cc_packed_route(self._h, int(B))
         if r < 0:
             raise CcError(-r, "cc_packed_route")
@@ -718,7 +720,9 @@ class cyclic:
     def correct_batch(self, b, erasures=None, want_L=False, packed=False, out=None, interleave=None):
         """Returns a dict: out (B,n) u8, status (B,) i32, and nerr (hard) or iters [+ L] (soft).
         packed=True (binary BCH codes, hard algorithms): b and out are uint8 (B, packed_bytes), see pack_bits; out= names
-        the buffer the corrected packed words go to (b itself decodes in place).
+        the buffer the corrected packed words go to (b itself decodes in place).  The long codes (q = 9 .. 15, BM / PGZ,
+        t <= 31, no erasures) are decoded from the packed words themselves in calls of device tensors of at least
+        CC_AMD_PACKED_LONG_MIN_FRAMES frames, see packed_route.
         interleave=I (hard algorithms): b and out are symbol-interleaved blocks of shape (B / I, n, I), see interleave();
         status, nerr and the erasure lists are per frame f = b I + j, as without it; out= as with packed=True."""
         lib = capi.lib()

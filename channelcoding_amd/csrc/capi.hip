@@ -1008,7 +1008,9 @@ static int packed_generic_dev(const cc_code *code, int kind, const uint8_t *d_sr
 
 static int packed_correct_dev(const cc_code *code, const uint8_t *d_in, const uint16_t *d_er, const uint32_t *d_off,
                               uint8_t *d_out, int32_t *d_nerr, int32_t *d_status, size_t B, hipStream_t stream) {
-  if (!d_er && packed_native_supported(code, B)) return launch_packed_correct(code, d_in, d_out, d_nerr, d_status, B, stream);
+  if (!d_er && packed_native_supported(code, B))
+    return code->wide ? launch_packed_long_correct(code, d_in, d_out, d_nerr, d_status, B, stream)
+                      : launch_packed_correct(code, d_in, d_out, d_nerr, d_status, B, stream);
   return packed_generic_dev(code, 2, d_in, d_er, d_off, d_out, d_nerr, d_status, B, stream);
 }
 
@@ -1063,12 +1065,20 @@ static int packed_host(const cc_code *code, int kind, const uint8_t *src, const 
   DeviceGuard guard(code->device);
   const StagedStream streams[] = {stage_in(0, src, in_w), stage_out(1, dst, out_w), stage_out(2, nerr, sizeof(int32_t)),
                                   stage_out(3, status, sizeof(int32_t))};
-  // a chunk is sized by the symbols, not by the packed words: the generic route's workspace is what a chunk costs
-  return staged_call(code, B, n * (code->wide ? 2 : 1), 1, streams, kind == 2 ? 4 : 2, erasures, erasure_offsets,
+  // a chunk is sized by the symbols, not by the packed words: the generic route's workspace is what a chunk costs.
+  // A 16-bit handle's call that takes the native route (packed_long.hip) has no such workspace: the route is decided
+  // once, for the B frames of the call as cc_packed_route(code, B) reports it, its chunks are sized by the packed words
+  // and every chunk, a short last one included, runs the native kernel.
+  const bool long_native = kind == 2 && !erasures && code->wide && packed_native_supported(code, B);
+  return staged_call(code, B, long_native ? in_w : n * (code->wide ? 2 : 1), 1, streams, kind == 2 ? 4 : 2, erasures,
+                     erasure_offsets,
                      [&](size_t m, void *const *d, const uint16_t *d_er, const uint32_t *d_off, hipStream_t s) {
                        const uint8_t *d_src = static_cast<const uint8_t *>(d[0]);
                        uint8_t *d_dst = static_cast<uint8_t *>(d[1]);
                        if (kind != 2) return packed_map_dev(code, kind, d_src, d_dst, m, s);
+                       if (long_native)
+                         return launch_packed_long_correct(code, d_src, d_dst, static_cast<int32_t *>(d[2]),
+                                                           static_cast<int32_t *>(d[3]), m, s);
                        return packed_correct_dev(code, d_src, d_er, d_off, d_dst, static_cast<int32_t *>(d[2]),
                                                  static_cast<int32_t *>(d[3]), m, s);
                      });

@@ -243,6 +243,10 @@ int launch_unpack_bits(const uint8_t *d_packed, size_t n, void *d_sym, int width
 bool packed_native_supported(const cc_code *code, size_t B);
 int launch_packed_correct(const cc_code *code, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nerr, int32_t *d_status,
                           size_t B, hipStream_t stream);
+// packed_long.hip: the packed words of a 16-bit handle (q = 9 .. 15), BM / PGZ tag, t <= 31, B >= CC_AMD_PACKED_LONG_MIN_FRAMES
+bool packed_long_supported(const cc_code *code, size_t B);
+int launch_packed_long_correct(const cc_code *code, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nerr, int32_t *d_status,
+                               size_t B, hipStream_t stream);
 bool packed_encode_native(const cc_code *code);   // division coding, n - l <= 32 parity bits, q <= 8
 bool packed_extract_native(const cc_code *code);  // division coding, any q
 int launch_packed_encode(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, hipStream_t stream);

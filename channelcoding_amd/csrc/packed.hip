@@ -425,9 +425,12 @@ int launch_packed_extract(const cc_code *code, const uint8_t *d_cw, uint8_t *d_m
   return CC_OK;
 }
 
-// exactly the calls launch_algebraic sends to the bit-plane chain (no erasures), unless CC_AMD_PACKED_NATIVE=0
+// exactly the calls launch_algebraic sends to the bit-plane chain (no erasures), and on the 16-bit handles the calls
+// packed_long.hip serves, unless CC_AMD_PACKED_NATIVE=0
 bool packed_native_supported(const cc_code *code, size_t B) {
-  if (packed_native_disabled() || code->wide || code->soft || code->matrix_only || code->tab.family != CC_FAMILY_BCH) return false;
+  if (packed_native_disabled()) return false;
+  if (code->wide) return packed_long_supported(code, B);
+  if (code->soft || code->matrix_only || code->tab.family != CC_FAMILY_BCH) return false;
   if (B == 0 || algebraic_long_needed(code, false)) return false;
   return bitslice_supported(code) && algebraic_chunk_supported(code, false) && !planes_small_call(code, B);
 }

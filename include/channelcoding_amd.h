@@ -360,9 +360,15 @@ uint32_t cc_q(const cc_code *code);
  *      Erasures are the CSR of cc_correct_hard_batch; out may be the same buffer as in.
  *      Routes: calls the byte route would send down the bit-plane chain of GF(2^8) -- n <= 255, no
  *      erasures, above the small-call threshold -- are decoded from the packed words natively, division-coded
- *      codes are extracted (any q) and, with n - l <= 32 parity bits and q <= 8, encoded on the packed words; every
- *      other call is unpacked into workspace of the handle, sent through the byte / 16-bit router and packed again.
- *      CC_AMD_PACKED_NATIVE=0 (read once) sends everything the second way. ---- */
+ *      codes are extracted (any q) and, with n - l <= 32 parity bits and q <= 8, encoded on the packed words.  The
+ *      long codes, q = 9 .. 15, are decoded from the packed words natively -- no symbol-per-bit copy
+ *      exists -- for the Berlekamp-Massey and PGZ tags, t <= 31, without an erasure list, at any length (full or
+ *      shortened), in calls of at least CC_AMD_PACKED_LONG_MIN_FRAMES frames (read once; default 1024); the Euklid
+ *      tag, t = 32, erasure lists and smaller calls go the generic way (measured, DESIGN.md 4.8.1: 16 .. 22 times the
+ *      generic route's rate for GF(2^13) / GF(2^14) codes at 2^16 frames, 5.7 / 4.7 times for BCH(1023,1003) /
+ *      BCH(511,484), faster at every call size from 256 frames on; 1024 is the floor of one frame per SIMD).
+ *      Every other call is unpacked into workspace of the handle, sent through the byte / 16-bit router and packed again; both routes give the same bytes, nerr
+ *      and status.  CC_AMD_PACKED_NATIVE=0 (read once) sends everything the second way. ---- */
 /* bytes of a packed codeword (which = 0) or message (which = 1); a negative cc_status if the handle does not qualify */
 int cc_packed_bytes(const cc_code *code, int which);
 /* 1: a packed hard-decode call of B frames without erasures takes the native route under the settings in force,
