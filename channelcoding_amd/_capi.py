@@ -50,6 +50,15 @@ class BurstChannel(C.Structure):
                          float(p_error_bad))
 
 
+class BurstDetector(C.Structure):
+    """cc_burst_detector: flags a symbol of the burst channel with p_detect in the bad state, p_false_alarm in the good."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("p_detect", C.c_double),
+                ("p_false_alarm", C.c_double)]
+
+    def __init__(self, p_detect=0.0, p_false_alarm=0.0):
+        super().__init__(C.sizeof(BurstDetector), 0, float(p_detect), float(p_false_alarm))
+
+
 class CcError(RuntimeError):
     def __init__(self, status, where):
         self.status = status
@@ -98,6 +107,10 @@ _SIGNATURES = {
                                       _VP]),
     "cc_burst_channel_dev": (C.c_int, [_VP, C.POINTER(BurstChannel), C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP,
                                        _VP, _VP, _VP]),
+    "cc_mc_run_burst_erasure_dev": (C.c_int, [_VP, C.POINTER(BurstChannel), C.POINTER(BurstDetector), C.c_uint64,
+                                              C.c_uint64, C.c_size_t, C.c_int, _VP, _VP]),
+    "cc_burst_erasure_channel_dev": (C.c_int, [_VP, C.POINTER(BurstChannel), C.POINTER(BurstDetector), C.c_uint64,
+                                               C.c_uint64, C.c_size_t, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "cc_encode_batch_u16": (C.c_int, [_VP, _VP, _VP, C.c_size_t]),
     "cc_encode_batch_u16_dev": (C.c_int, [_VP, _VP, _VP, C.c_size_t, _VP]),
     "cc_correct_hard_batch_u16": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t]),

@@ -4,6 +4,7 @@
                                           [--k 5|6|7|all]... [--dmin 3|5|7|9|11|all]... [--seed N | --seed-time]
                                           [--threads N] [--log-dir DIR] [--p VALUE]... [--max-samples N]
                                           [--interleave I] [--p-gb VALUE] [--p-bg VALUE] [--p-good VALUE]
+                                          [--p-detect VALUE] [--p-false-alarm VALUE]
 
 Same options, same decoder registry (benchmark.c++:23-166: primitive_bch<k, dmin<d>, A> for k in 5..7,
 d in 3,5,7,9 and the nine algorithm tags, min-sum family with 50 iterations, NMS 8/10, OMS 1/100) and the same
@@ -22,7 +23,9 @@ writing "<to_string()>.<bsc|bec>.log".
 --simulation burst is new as well: the two-state Gilbert-Elliott channel run along symbol-interleaved blocks of depth
 --interleave (montecarlo.burst_simulation), with the transition probabilities --p-gb (good -> bad) and --p-bg (bad ->
 good) per transmitted symbol and the symbol error probability --p-good of the good state; the points given with --p are
-the error probabilities of the bad state.  Each decoder writes "<to_string()>.burst.log".
+the error probabilities of the bad state.  Each decoder writes "<to_string()>.burst.log".  --p-detect / --p-false-alarm
+add a burst detector: a symbol is flagged with that probability in the bad / good state and handed to the decoder as an
+erasure; the default, 0 and 0, is errors-only decoding.
 """
 import argparse
 import sys
@@ -91,6 +94,9 @@ def usage_text():
               "--p-gb <value>               burst: probability good -> bad per symbol. The default is 0.01.",
               "--p-bg <value>               burst: probability bad -> good per symbol. The default is 0.1.",
               "--p-good <value>             burst: symbol error probability of the good state. The default is 0.",
+              "--p-detect <value>           burst: P(symbol flagged | bad state) of a burst detector whose flags are erasures",
+              "                             to the decoder. The default is 0.",
+              "--p-false-alarm <value>      burst: P(symbol flagged | good state). The default is 0.",
               "--max-samples <num>          awgn / bsc / bec / burst: cap on the frames of one point.",
               "",
               "algorithm, k, and dmin can be specified multiple times.",
@@ -144,6 +150,8 @@ def main(argv=None):
     ap.add_argument("--p-gb", type=float, default=0.01, help="burst: P(good -> bad) per symbol")
     ap.add_argument("--p-bg", type=float, default=0.1, help="burst: P(bad -> good) per symbol")
     ap.add_argument("--p-good", type=float, default=0.0, help="burst: symbol error probability of the good state")
+    ap.add_argument("--p-detect", type=float, default=0.0, help="burst: P(flag | bad state) of the burst detector")
+    ap.add_argument("--p-false-alarm", type=float, default=0.0, help="burst: P(flag | good state)")
     ap.add_argument("--help", "-h", action="store_true")
     args, unknown = ap.parse_known_args(argv)
     if args.help or unknown:
@@ -187,9 +195,12 @@ def main(argv=None):
                                       max_samples=args.max_samples)()
             frames = sum(r["frames"] for r in res)
         elif sim == "burst":
+            detector = {}
+            if args.p_detect or args.p_false_alarm:
+                detector = dict(p_detect=args.p_detect, p_false_alarm=args.p_false_alarm)
             res = burst_simulation(code, interleave=args.interleave, p_gb=args.p_gb, p_bg=args.p_bg,
                                    p_error_good=args.p_good, points=args.p, seed=seed, log_dir=args.log_dir,
-                                   max_samples=args.max_samples)()
+                                   max_samples=args.max_samples, **detector)()
             frames = sum(r["frames"] for r in res)
         else:
             if rank == 0:

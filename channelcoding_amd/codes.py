@@ -276,6 +276,32 @@ def burst_channel(code, interleave=1, p_gb=0.0, p_bg=1.0, p_error_good=0.0, p_er
     return recv, sent, state
 
 
+def burst_erasure_channel(code, interleave, p_gb, p_bg, p_error_good, p_error_bad, p_detect, p_false_alarm, seed=0,
+                          first_frame=0, frames=0, random_codewords=True):
+    """burst_channel with a burst detector (cc_burst_erasure_channel_dev): a symbol is flagged with probability p_detect
+    in the bad state and p_false_alarm in the good one, and a flagged symbol is received as 0.  Returns a dict of torch
+    tensors: recv, sent, state and flag (0 / 1), uint8 of shape (frames / interleave, n, interleave) in transmission
+    order, and the erasure list per frame in frame-major numbering f = b I + j (the rows of deinterleave(recv)) as
+    discrete_channel gives it: erasures (int16 positions, ascending within a frame, trimmed to off[-1]) and
+    erasure_offsets (frames + 1,) int32.  The int32 offsets bound one call to frames * n < 2^31."""
+    import torch
+    I, frames = int(interleave), int(frames)
+    if frames * code.n >= 1 << 31:
+        raise ValueError("burst_erasure_channel: frames * n must stay below 2^31 (int32 offsets)")
+    ch = capi.BurstChannel(I, p_gb, p_bg, p_error_good, p_error_bad)
+    det = capi.BurstDetector(p_detect, p_false_alarm)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    shape = (frames // I if 1 <= I <= 256 else 0, code.n, I)
+    recv, sent, state, flag = (torch.empty(shape, dtype=torch.uint8, device=dev) for _ in range(4))
+    off = torch.zeros(frames + 1, dtype=torch.int32, device=dev)
+    er = torch.empty(max(1, frames * code.n), dtype=torch.int16, device=dev)
+    rc = capi.lib().cc_burst_erasure_channel_dev(code._h, C.byref(ch), C.byref(det), int(seed), int(first_frame), frames,
+                                                 int(bool(random_codewords)), _ptr(recv), _ptr(sent), _ptr(state),
+                                                 _ptr(flag), _ptr(er), _ptr(off), _stream_handle(recv))
+    capi.check(rc, "cc_burst_erasure_channel_dev")
+    return dict(recv=recv, sent=sent, state=state, flag=flag, erasures=er[:int(off[-1])], erasure_offsets=off)
+
+
 class cyclic:
     """Common part of primitive_bch and rs (cyclic::cyclic<...>, cyclic.h:67-386)."""
     family = None

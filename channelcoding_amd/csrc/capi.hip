@@ -1373,7 +1373,7 @@ int cc_discrete_channel_dev(const cc_code *code, double p_error, double p_erasur
 }
 
 // the burst channel serves the handles of the discrete route; every argument is checked before a device is asked for
-static int burst_supported(const cc_code *code, const cc_burst_channel *ch, uint64_t first_frame, size_t frames,
+static int burst_arguments(const cc_code *code, const cc_burst_channel *ch, uint64_t first_frame, size_t frames,
                            int random_codewords) {
   if (!ch || ch->struct_size != sizeof(cc_burst_channel)) {
     set_last_error("cc_burst_channel: NULL, or struct_size is not sizeof(cc_burst_channel)");
@@ -1404,6 +1404,51 @@ static int burst_supported(const cc_code *code, const cc_burst_channel *ch, uint
   }
   if (random_codewords && code->desc.coding != CC_CODING_DIVISION && code->desc.coding != CC_CODING_MULTIPLICATION)
     return CC_ERR_INVALID_ARGUMENT;
+  return CC_OK;
+}
+
+static int burst_supported(const cc_code *code, const cc_burst_channel *ch, uint64_t first_frame, size_t frames,
+                           int random_codewords) {
+  if (int rc = burst_arguments(code, ch, first_frame, frames, random_codewords)) return rc;
+  if (code->device == CC_DEVICE_NONE) return CC_ERR_NO_DEVICE;
+  return CC_OK;
+}
+
+// the detector's checks come after every check of the burst channel and, like them, before a device is asked for
+static int burst_erasure_supported(const cc_code *code, const cc_burst_channel *ch, const cc_burst_detector *det,
+                                   uint64_t first_frame, size_t frames, int random_codewords, const void *d_erasures,
+                                   const void *d_erasure_offsets) {
+  if (int rc = burst_arguments(code, ch, first_frame, frames, random_codewords)) return rc;
+  if (!det) {
+    set_last_error("cc_burst_detector: NULL");
+    return CC_ERR_INVALID_ARGUMENT;
+  }
+  if (det->struct_size != sizeof(cc_burst_detector)) {
+    set_last_error("cc_burst_detector: struct_size is not sizeof(cc_burst_detector)");
+    return CC_ERR_INVALID_ARGUMENT;
+  }
+  if (det->reserved != 0) {
+    set_last_error("cc_burst_detector: reserved must be 0");
+    return CC_ERR_INVALID_ARGUMENT;
+  }
+  for (double p : {det->p_detect, det->p_false_alarm})
+    if (!std::isfinite(p) || p < 0.0 || p > 1.0) {
+      set_last_error("p_detect and p_false_alarm must be finite and in [0, 1]");
+      return CC_ERR_INVALID_ARGUMENT;
+    }
+  if ((d_erasures == nullptr) != (d_erasure_offsets == nullptr)) {
+    set_last_error("the erasure list buffers: both or neither");
+    return CC_ERR_INVALID_ARGUMENT;
+  }
+  if (d_erasures && static_cast<unsigned long long>(frames) * code->tab.n > 0xFFFFFFFFull) {
+    set_last_error("the erasure offsets are 32-bit: frames * n must stay below 2^32 in one call");
+    return CC_ERR_INVALID_ARGUMENT;
+  }
+  const bool on = std::llround(det->p_detect * 4294967296.0) != 0 || std::llround(det->p_false_alarm * 4294967296.0) != 0;
+  if (on && code->desc.algorithm == CC_ALG_PGZ && code->tab.family == CC_FAMILY_RS) {
+    set_last_error("The PGZ-Algorithm does not support erasure decoding");  // hard_decision.h:66-68
+    return CC_ERR_UNSUPPORTED;
+  }
   if (code->device == CC_DEVICE_NONE) return CC_ERR_NO_DEVICE;
   return CC_OK;
 }
@@ -1427,6 +1472,30 @@ int cc_burst_channel_dev(const cc_code *code, const cc_burst_channel *ch, uint64
   DeviceGuard guard(code->device);
   return mc_burst(const_cast<cc_code *>(code), *ch, seed, first_frame, frames, random_codewords, d_recv, d_sent, d_state,
                   static_cast<hipStream_t>(stream));
+}
+
+int cc_mc_run_burst_erasure_dev(const cc_code *code, const cc_burst_channel *ch, const cc_burst_detector *det,
+                                uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
+                                uint64_t *d_counters, void *stream) {
+  if (!code || !d_counters) return CC_ERR_INVALID_ARGUMENT;
+  const int rc = burst_erasure_supported(code, ch, det, first_frame, frames, random_codewords, nullptr, nullptr);
+  if (rc != CC_OK) return rc;
+  DeviceGuard guard(code->device);
+  return mc_run_burst_erasure(const_cast<cc_code *>(code), *ch, *det, seed, first_frame, frames, random_codewords,
+                              d_counters, static_cast<hipStream_t>(stream));
+}
+
+int cc_burst_erasure_channel_dev(const cc_code *code, const cc_burst_channel *ch, const cc_burst_detector *det,
+                                 uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
+                                 uint8_t *d_recv, uint8_t *d_sent, uint8_t *d_state, uint8_t *d_flag,
+                                 uint16_t *d_erasures, uint32_t *d_erasure_offsets, void *stream) {
+  if (!code || (frames && !d_recv)) return CC_ERR_INVALID_ARGUMENT;
+  const int rc = burst_erasure_supported(code, ch, det, first_frame, frames, random_codewords, d_erasures,
+                                         d_erasure_offsets);
+  if (rc != CC_OK) return rc;
+  DeviceGuard guard(code->device);
+  return mc_burst_erasure(const_cast<cc_code *>(code), *ch, *det, seed, first_frame, frames, random_codewords, d_recv,
+                          d_sent, d_state, d_flag, d_erasures, d_erasure_offsets, static_cast<hipStream_t>(stream));
 }
 
 int cc_diag_table(const cc_code *code, uint16_t *out, size_t cap, uint32_t *D, uint32_t *LPF, uint32_t *links) {

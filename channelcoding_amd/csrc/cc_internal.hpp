@@ -275,6 +275,14 @@ int mc_run_burst(cc_code *code, const cc_burst_channel &ch, uint64_t seed, uint6
                  int random_codewords, uint64_t *d_counters, hipStream_t stream);
 int mc_burst(cc_code *code, const cc_burst_channel &ch, uint64_t seed, uint64_t first_frame, size_t frames,
              int random_codewords, uint8_t *d_recv, uint8_t *d_sent, uint8_t *d_state, hipStream_t stream);
+// (det checked by the caller as well: probabilities in [0, 1]; the CSR pointers both or neither, frames * n < 2^32 with them)
+int mc_run_burst_erasure(cc_code *code, const cc_burst_channel &ch, const cc_burst_detector &det, uint64_t seed,
+                         uint64_t first_frame, size_t frames, int random_codewords, uint64_t *d_counters,
+                         hipStream_t stream);
+int mc_burst_erasure(cc_code *code, const cc_burst_channel &ch, const cc_burst_detector &det, uint64_t seed,
+                     uint64_t first_frame, size_t frames, int random_codewords, uint8_t *d_recv, uint8_t *d_sent,
+                     uint8_t *d_state, uint8_t *d_flag, uint16_t *d_erasures, uint32_t *d_erasure_offsets,
+                     hipStream_t stream);
 int minsum_kernel_info(const cc_code *code, std::string &name, uint32_t &frames_per_wg, uint32_t &threads,
                        uint32_t &lds);
 

@@ -978,6 +978,9 @@ __device__ __forceinline__ uint32_t map_compose(uint32_t f, uint32_t g) {
 struct BurstThresholds {
   unsigned long long GB, BG, PG, PB, S;
 };
+struct DetectorThresholds {
+  unsigned long long DB, DG;  // flagged below DB in the bad state, below DG in the good one
+};
 
 // 4 bytes to base[at .. at + 4): one dword store where the address allows it
 __device__ __forceinline__ void store4(uint8_t *__restrict__ base, unsigned long long at, const uint32_t v[4]) {
@@ -997,11 +1000,17 @@ __device__ __forceinline__ void store4(uint8_t *__restrict__ base, unsigned long
 // sent: frame-major words of the chunk (nullptr: the all-zero word).  Frame-major output (frame_major != 0, the Monte-Carlo
 // route): symbol t of block b to (b I + t % I) n + t / I of recv, or +-1 floats to soft.  Otherwise (channel only) recv,
 // sent_out and state (the latter two may be nullptr) in transmission order, b N + t.
+// DET: the burst detector.  One more Philox call per four symbols (domain 8): symbol t is flagged iff
+// d_t < (s_t bad ? det.DB : det.DG).  A flagged symbol is received as 0 (+0.0f for soft) and counts as an erasure, an
+// unflagged one in error as a channel error.  One flag byte (0 / 1) per symbol: to flag_t in transmission order and to
+// flag_fm frame-major, at the address the frame-major received byte has (either may be nullptr).
+template <bool DET>
 __global__ void __launch_bounds__(256)
 burst_kernel(float *__restrict__ soft, uint8_t *__restrict__ recv, uint8_t *__restrict__ sent_out,
              uint8_t *__restrict__ state, const uint8_t *__restrict__ sent, int n, int I, int group_log2, int passes,
              int frame_major, uint32_t qm1, unsigned long long first_block, unsigned long long blocks,
-             BurstThresholds th, uint32_t k0, uint32_t k1, unsigned long long *__restrict__ counters) {
+             BurstThresholds th, uint32_t k0, uint32_t k1, unsigned long long *__restrict__ counters,
+             DetectorThresholds det, uint8_t *__restrict__ flag_t, uint8_t *__restrict__ flag_fm) {
   const int G = 1 << group_log2;
   const uint32_t N = static_cast<uint32_t>(n) * static_cast<uint32_t>(I);
   const unsigned long long tid = static_cast<unsigned long long>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -1014,7 +1023,7 @@ burst_kernel(float *__restrict__ soft, uint8_t *__restrict__ recv, uint8_t *__re
   const uint32_t j_first = static_cast<uint32_t>(4 * qd) % static_cast<uint32_t>(I);
   const uint32_t p_pass = static_cast<uint32_t>(4 * G) / static_cast<uint32_t>(I);
   const uint32_t j_pass = static_cast<uint32_t>(4 * G) % static_cast<uint32_t>(I);
-  unsigned c_err = 0;
+  unsigned c_err = 0, c_ers = 0;
   uint32_t start_bad = 0;  // lane q: whether the block of trip (tr & ~(G - 1)) + q starts in the bad state
   for (unsigned long long tr = 0; tr < trips; ++tr) {
     // the start draw is one word per block: every G trips lane q draws it for the group's block of trip tr + q
@@ -1060,6 +1069,18 @@ burst_kernel(float *__restrict__ soft, uint8_t *__restrict__ recv, uint8_t *__re
           wrong |= (s < cnt && static_cast<unsigned long long>(u.c[s]) < (st ? th.PB : th.PG)) ? 1u << s : 0u;
           st = map_apply(step[s], st);
         }
+        unsigned flagged = 0;  // bit s: symbol t0 + s
+        uint32_t fl[4] = {0u, 0u, 0u, 0u};
+        if constexpr (DET) {
+          const Philox d = philox4x32_10(g0, g1, c2, 8u, k0, k1);
+#pragma unroll
+          for (int s = 0; s < 4; ++s) {
+            fl[s] = (s < cnt && static_cast<unsigned long long>(d.c[s]) < (bad[s] ? det.DB : det.DG)) ? 1u : 0u;
+            flagged |= fl[s] << s;
+          }
+          c_ers += static_cast<unsigned>(__builtin_popcount(flagged));
+          wrong &= ~flagged;  // the error draw stands, but nothing of it is received or counted
+        }
         uint32_t e[4] = {1u, 1u, 1u, 1u};
         if (wrong && qm1 > 1) {
           const Philox v = philox4x32_10(g0, g1, c2, 7u, k0, k1);
@@ -1084,23 +1105,34 @@ burst_kernel(float *__restrict__ soft, uint8_t *__restrict__ recv, uint8_t *__re
             if (s < cnt) c[s] = sent[at_block + fm[s]];
         }
 #pragma unroll
-        for (int s = 0; s < 4; ++s) r[s] = ((wrong >> s) & 1u) ? c[s] ^ e[s] : c[s];
+        for (int s = 0; s < 4; ++s) r[s] = ((wrong >> s) & 1u) ? c[s] ^ e[s] : (DET && fl[s]) ? 0u : c[s];
         if (frame_major) {
 #pragma unroll
           for (int s = 0; s < 4; ++s) {
             if (s >= cnt) continue;
-            if (soft) soft[at_block + fm[s]] = r[s] ? -1.0f : 1.0f;
+            if (soft) soft[at_block + fm[s]] = (DET && fl[s]) ? 0.0f : r[s] ? -1.0f : 1.0f;
             else recv[at_block + fm[s]] = static_cast<uint8_t>(r[s]);
           }
         } else if (cnt == 4) {
           store4(recv, at_block + t0, r);
           if (sent_out) store4(sent_out, at_block + t0, c);
           if (state) store4(state, at_block + t0, bad);
+          if constexpr (DET)
+            if (flag_t) store4(flag_t, at_block + t0, fl);
         } else {
           for (int s = 0; s < cnt; ++s) {
             recv[at_block + t0 + s] = static_cast<uint8_t>(r[s]);
             if (sent_out) sent_out[at_block + t0 + s] = static_cast<uint8_t>(c[s]);
             if (state) state[at_block + t0 + s] = static_cast<uint8_t>(bad[s]);
+            if constexpr (DET)
+              if (flag_t) flag_t[at_block + t0 + s] = static_cast<uint8_t>(fl[s]);
+          }
+        }
+        if constexpr (DET) {
+          if (flag_fm) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+              if (s < cnt) flag_fm[at_block + fm[s]] = static_cast<uint8_t>(fl[s]);
           }
         }
       }
@@ -1116,6 +1148,11 @@ burst_kernel(float *__restrict__ soft, uint8_t *__restrict__ recv, uint8_t *__re
     for (int m = 32; m >= 1; m >>= 1) c_err += __shfl_xor(c_err, m, 64);
     if ((threadIdx.x & 63) == 0 && c_err)
       atomicAdd(&counters[CC_MC_CHANNEL_BIT_ERRORS], static_cast<unsigned long long>(c_err));
+    if constexpr (DET) {
+      for (int m = 32; m >= 1; m >>= 1) c_ers += __shfl_xor(c_ers, m, 64);
+      if ((threadIdx.x & 63) == 0 && c_ers)
+        atomicAdd(&counters[CC_MC_CHANNEL_ERASURES], static_cast<unsigned long long>(c_ers));
+    }
   }
 }
 
@@ -1129,23 +1166,113 @@ struct BurstIO {
   float *soft = nullptr;
   uint8_t *recv = nullptr, *sent_out = nullptr, *state = nullptr;
   bool frame_major = false;
+  // detector route only: flag bytes in transmission order / frame-major (the map the erasure list is built from)
+  uint8_t *flag_t = nullptr, *flag_fm = nullptr;
 };
 
-// the channel over the m / I blocks of frames [first_frame, first_frame + m), both multiples of I
+DetectorThresholds detector_thresholds(const cc_burst_detector &det) {
+  auto fix = [](double x) { return static_cast<unsigned long long>(std::llround(x * 4294967296.0)); };
+  return DetectorThresholds{fix(det.p_detect), fix(det.p_false_alarm)};
+}
+
+// the channel over the m / I blocks of frames [first_frame, first_frame + m), both multiples of I; det != nullptr: the
+// detector variant of the kernel
 int launch_burst(const cc_code *code, const cc_burst_channel &ch, uint64_t seed, uint64_t first_frame, size_t m,
-                 const uint8_t *sent, const BurstIO &io, unsigned long long *d_counters, hipStream_t stream) {
+                 const uint8_t *sent, const BurstIO &io, unsigned long long *d_counters, hipStream_t stream,
+                 const DetectorThresholds *det = nullptr) {
   const int n = static_cast<int>(code->tab.n), I = static_cast<int>(ch.interleave);
   const int N = n * I, g = N > 256 ? 6 : log2_lanes(N), passes = (N + (4 << g) - 1) / (4 << g);
   const uint32_t qm1 = code->tab.family == CC_FAMILY_RS ? (1u << code->tab.q) - 1u : 1u;
   const unsigned long long blocks = m / ch.interleave, items = blocks << g;
   // depth 1 is frame-major as it is: the dword stores of the transmission-order branch serve it
   const bool fm = io.frame_major && (I > 1 || io.soft);
-  hipLaunchKernelGGL(burst_kernel, dim3(grid_for(code, items)), dim3(256), 0, stream, io.soft, io.recv, io.sent_out,
-                     io.state, sent, n, I, g, passes, fm ? 1 : 0, qm1,
-                     static_cast<unsigned long long>(first_frame / ch.interleave), blocks, burst_thresholds(ch),
-                     static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), d_counters);
+  uint8_t *flag_t = io.flag_t, *flag_fm = io.flag_fm;
+  if (I == 1 && !flag_t) {  // one order: the dword stores again
+    flag_t = flag_fm;
+    flag_fm = nullptr;
+  }
+  if (det)
+    hipLaunchKernelGGL(burst_kernel<true>, dim3(grid_for(code, items)), dim3(256), 0, stream, io.soft, io.recv,
+                       io.sent_out, io.state, sent, n, I, g, passes, fm ? 1 : 0, qm1,
+                       static_cast<unsigned long long>(first_frame / ch.interleave), blocks, burst_thresholds(ch),
+                       static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), d_counters, *det, flag_t, flag_fm);
+  else
+    hipLaunchKernelGGL(burst_kernel<false>, dim3(grid_for(code, items)), dim3(256), 0, stream, io.soft, io.recv,
+                       io.sent_out, io.state, sent, n, I, g, passes, fm ? 1 : 0, qm1,
+                       static_cast<unsigned long long>(first_frame / ch.interleave), blocks, burst_thresholds(ch),
+                       static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), d_counters, DetectorThresholds{0, 0},
+                       static_cast<uint8_t *>(nullptr), static_cast<uint8_t *>(nullptr));
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "burst channel kernel launch");
+  return CC_OK;
+}
+
+// The erasure list of the detector route, from the frame-major flag map (one byte per symbol, 0 / 1, frame f at f n) with
+// the lane groups of discrete_positions_kernel: lane q of a frame's group owns positions 4q .. 4q + 3.  Bit s of the
+// result: position 4q + s is flagged.
+__device__ __forceinline__ unsigned flags_of_lane(const uint8_t *__restrict__ map, unsigned long long at, int cnt,
+                                                  unsigned long long size) {
+  unsigned flagged = 0;
+  if (cnt == 4) {
+    const uint32_t w = load4_aligned(map, at, size);
+    flagged = (w & 1u) | ((w >> 7) & 2u) | ((w >> 14) & 4u) | ((w >> 21) & 8u);
+  } else {
+    for (int s = 0; s < cnt; ++s) flagged |= static_cast<unsigned>(map[at + s] & 1u) << s;  // the ragged tail of a frame
+  }
+  return flagged;
+}
+
+// count[f] = the flagged positions of frame f (what discrete_kernel writes to er_count)
+__global__ void __launch_bounds__(256)
+flag_count_kernel(uint32_t *__restrict__ count, const uint8_t *__restrict__ map, int n, int group_log2,
+                  unsigned long long frames) {
+  const int G = 1 << group_log2;
+  const unsigned long long tid = static_cast<unsigned long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  const unsigned long long stride = (static_cast<unsigned long long>(gridDim.x) * blockDim.x) >> group_log2;
+  const int qd = static_cast<int>(tid & static_cast<unsigned long long>(G - 1));
+  const int j0 = 4 * qd, cnt = n - j0 < 4 ? (n - j0 > 0 ? n - j0 : 0) : 4;
+  for (unsigned long long f = tid >> group_log2; f < frames; f += stride) {
+    const unsigned flagged = flags_of_lane(map, f * n + j0, cnt, frames * n);
+    const GroupCount gc = group_count(static_cast<uint32_t>(__builtin_popcount(flagged)), group_log2);
+    if (qd == 0) count[f] = gc.total;
+  }
+}
+
+// discrete_positions_kernel with the flag map in place of the class draw; frames without a flag skip the second read
+__global__ void __launch_bounds__(256)
+flag_positions_kernel(uint16_t *__restrict__ erasures, uint32_t *__restrict__ off, const uint32_t *__restrict__ count,
+                      const uint32_t *__restrict__ local, const uint32_t *__restrict__ tile_base,
+                      const uint8_t *__restrict__ map, int n, int group_log2, unsigned long long frames) {
+  const int G = 1 << group_log2;
+  const unsigned long long tid = static_cast<unsigned long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  const unsigned long long stride = (static_cast<unsigned long long>(gridDim.x) * blockDim.x) >> group_log2;
+  const int qd = static_cast<int>(tid & static_cast<unsigned long long>(G - 1));
+  const int j0 = 4 * qd, cnt = n - j0 < 4 ? (n - j0 > 0 ? n - j0 : 0) : 4;
+  for (unsigned long long f = tid >> group_log2; f < frames; f += stride) {
+    const uint32_t base = local[f] + tile_base[f / SCAN_TILE];
+    if (qd == 0) off[f] = base;
+    if (count[f] == 0) continue;  // uniform over the group
+    const unsigned flagged = flags_of_lane(map, f * n + j0, cnt, frames * n);
+    uint16_t *dst = erasures + base + group_count(static_cast<uint32_t>(__builtin_popcount(flagged)), group_log2).below;
+    for (int s = 0; s < cnt; ++s)
+      if ((flagged >> s) & 1u) *dst++ = static_cast<uint16_t>(j0 + s);
+  }
+}
+
+// The CSR of the m <= 2^20 frames whose flags are in map: er / off[0 .. m], with count, local (m words each) and tiles
+// (m / 1024 + 1 words) as scratch and carry = the entries already in er (nullptr: 0), as launch_discrete builds it.
+int launch_flag_list(const cc_code *code, const uint8_t *map, size_t m, const DiscreteIO &io, hipStream_t stream) {
+  const int n = static_cast<int>(code->tab.n), g = log2_lanes(n);
+  const unsigned long long frames = m;
+  const int grid = grid_for(code, frames << g);
+  const unsigned ntiles = static_cast<unsigned>((frames + SCAN_TILE - 1) / SCAN_TILE);
+  hipLaunchKernelGGL(flag_count_kernel, dim3(grid), dim3(256), 0, stream, io.count, map, n, g, frames);
+  hipLaunchKernelGGL(discrete_scan_tiles_kernel, dim3(ntiles), dim3(256), 0, stream, io.count, io.local, io.tiles, frames);
+  hipLaunchKernelGGL(discrete_scan_sums_kernel, dim3(1), dim3(1024), 0, stream, io.tiles, ntiles, io.carry, io.off + m);
+  hipLaunchKernelGGL(flag_positions_kernel, dim3(grid), dim3(256), 0, stream, io.er, io.off, io.count, io.local, io.tiles,
+                     map, n, g, frames);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "flag list kernel launch");
   return CC_OK;
 }
 
@@ -1236,6 +1363,131 @@ int mc_burst(cc_code *code, const cc_burst_channel &ch, uint64_t seed, uint64_t 
     }
     rc = launch_burst(code, ch, seed, first_frame + done, m, sent, io, nullptr, stream);
     if (rc != CC_OK) return rc;
+  }
+  return w.fence_out(stream);
+}
+
+// Monte-Carlo with the burst detector: mc_run_burst with the flagged symbols handed to the decoder as
+// erasures, decoded as mc_run_discrete decodes.  Received bytes and, 16-byte aligned behind them, the positions (at most
+// 2 n bytes per frame) in w.llr as on the discrete route; the frame-major flag map in w.hard, which the decoder
+// overwrites once the list kernels have read it (one stream); counts and tile prefixes in w.nerr / w.status before the
+// decoder writes them, offsets and tile sums in w.list.  A min-sum handle gets +0.0f at a flag and needs no list.
+int mc_run_burst_erasure(cc_code *code, const cc_burst_channel &ch, const cc_burst_detector &det, uint64_t seed,
+                         uint64_t first_frame, size_t frames, int random_codewords, uint64_t *d_counters,
+                         hipStream_t stream) {
+  const DetectorThresholds dt = detector_thresholds(det);
+  if ((dt.DB | dt.DG) == 0)  // no symbol can be flagged: the errors-only route, NULL erasures for the decoder
+    return mc_run_burst(code, ch, seed, first_frame, frames, random_codewords, d_counters, stream);
+  if (frames == 0) return CC_OK;
+  const size_t chunk = burst_chunk(frames, ch.interleave);
+  if (!code->mc) code->mc = new McWorkspace();
+  std::lock_guard<std::mutex> guard(code->mc->lock);
+  int rc = ensure_workspace(code, chunk < 16 ? 16 : chunk);  // >= 16 frames: bytes + aligned positions fit in 4 n
+  if (rc != CC_OK) return rc;
+  McWorkspace &w = *code->mc;
+  rc = w.fence_in(stream);
+  if (rc != CC_OK) return rc;
+  const size_t n = code->tab.n;
+  unsigned long long *counters = reinterpret_cast<unsigned long long *>(d_counters);
+  for (size_t done = 0; done < frames; done += chunk) {
+    const size_t m = frames - done < chunk ? frames - done : chunk;
+    uint8_t *sent = random_codewords ? w.sent : nullptr;
+    if (random_codewords) {
+      rc = launch_discrete_sent(code, seed, first_frame + done, m, w.sent, w.msg, stream);
+      if (rc != CC_OK) return rc;
+    }
+    BurstIO io;
+    DiscreteIO list;
+    io.frame_major = true;
+    if (code->soft) {
+      io.soft = w.llr;
+    } else {
+      io.recv = reinterpret_cast<uint8_t *>(w.llr);
+      io.flag_fm = w.hard;
+      list.er = reinterpret_cast<uint16_t *>(io.recv + ((m * n + 15) & ~size_t(15)));
+      list.off = w.list;
+      list.tiles = w.list + m + 1;
+      list.count = reinterpret_cast<uint32_t *>(w.nerr);
+      list.local = reinterpret_cast<uint32_t *>(w.status);
+    }
+    rc = launch_burst(code, ch, seed, first_frame + done, m, sent, io, counters, stream, &dt);
+    if (rc != CC_OK) return rc;
+    if (code->soft) {
+      rc = launch_minsum(code, w.llr, nullptr, nullptr, w.hard, nullptr, w.iters, w.status, m, stream);
+    } else {
+      rc = launch_flag_list(code, io.flag_fm, m, list, stream);
+      if (rc != CC_OK) return rc;
+      if (code->desc.algorithm == CC_ALG_PGZ)  // the BCH two-trial rule, as cc_correct_hard_batch_dev
+        rc = launch_pgz_erasures(code, io.recv, list.er, list.off, w.hard, w.nerr, w.status, m, stream);
+      else
+        rc = launch_algebraic(code, false, io.recv, list.er, list.off, w.hard, w.nerr, w.status, m, stream);
+    }
+    if (rc != CC_OK) return rc;
+    const unsigned long long blocks = (m + 15) / 16;
+    const unsigned long long max_grid = static_cast<unsigned long long>(code->num_cus) * 8;
+    hipLaunchKernelGGL(count_kernel, dim3(static_cast<int>(blocks < max_grid ? blocks : max_grid)), dim3(256), 0, stream,
+                       w.hard, sent, code->soft ? w.iters : nullptr, w.status, static_cast<int>(n),
+                       code->desc.iterations, static_cast<unsigned long long>(m), counters);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "count kernel launch");
+  }
+  return w.fence_out(stream);
+}
+
+// cc_burst_erasure_channel_dev: mc_burst with the flags (transmission order, d_flag may be nullptr) and, where the CSR
+// buffers are given, one frame-major CSR over all chunks of the call (each chunk's scan starts from the entries of the
+// chunks before it, read on the device, as in mc_discrete); the frame-major flag map of a chunk in w.hard.
+int mc_burst_erasure(cc_code *code, const cc_burst_channel &ch, const cc_burst_detector &det, uint64_t seed,
+                     uint64_t first_frame, size_t frames, int random_codewords, uint8_t *d_recv, uint8_t *d_sent,
+                     uint8_t *d_state, uint8_t *d_flag, uint16_t *d_erasures, uint32_t *d_erasure_offsets,
+                     hipStream_t stream) {
+  const DetectorThresholds dt = detector_thresholds(det);
+  const size_t n = code->tab.n;
+  if ((dt.DB | dt.DG) == 0 || frames == 0) {  // nothing flagged: the errors-only channel, an empty list
+    if (d_erasure_offsets) CC_HIP_TRY(hipMemsetAsync(d_erasure_offsets, 0, (frames + 1) * sizeof(uint32_t), stream));
+    if (d_flag && frames) CC_HIP_TRY(hipMemsetAsync(d_flag, 0, frames * n, stream));
+    return mc_burst(code, ch, seed, first_frame, frames, random_codewords, d_recv, d_sent, d_state, stream);
+  }
+  const size_t chunk = burst_chunk(frames, ch.interleave);
+  if (!code->mc) code->mc = new McWorkspace();
+  std::lock_guard<std::mutex> guard(code->mc->lock);
+  int rc = CC_OK;
+  if (random_codewords || d_erasures) {
+    rc = ensure_workspace(code, chunk);
+    if (rc != CC_OK) return rc;
+  }
+  McWorkspace &w = *code->mc;
+  rc = w.fence_in(stream);
+  if (rc != CC_OK) return rc;
+  for (size_t done = 0; done < frames; done += chunk) {
+    const size_t m = frames - done < chunk ? frames - done : chunk;
+    BurstIO io;
+    io.recv = d_recv + done * n;
+    io.state = d_state ? d_state + done * n : nullptr;
+    io.flag_t = d_flag ? d_flag + done * n : nullptr;
+    io.flag_fm = d_erasures ? w.hard : nullptr;
+    const uint8_t *sent = nullptr;
+    if (random_codewords) {
+      rc = launch_discrete_sent(code, seed, first_frame + done, m, w.sent, w.msg, stream);
+      if (rc != CC_OK) return rc;
+      sent = w.sent;
+      io.sent_out = d_sent ? d_sent + done * n : nullptr;
+    } else if (d_sent) {
+      CC_HIP_TRY(hipMemsetAsync(d_sent + done * n, 0, m * n, stream));
+    }
+    rc = launch_burst(code, ch, seed, first_frame + done, m, sent, io, nullptr, stream, &dt);
+    if (rc != CC_OK) return rc;
+    if (d_erasures) {
+      DiscreteIO list;
+      list.er = d_erasures;
+      list.off = d_erasure_offsets + done;
+      list.tiles = w.list;
+      list.count = reinterpret_cast<uint32_t *>(w.nerr);
+      list.local = reinterpret_cast<uint32_t *>(w.status);
+      list.carry = done ? d_erasure_offsets + done : nullptr;
+      rc = launch_flag_list(code, w.hard, m, list, stream);
+      if (rc != CC_OK) return rc;
+    }
   }
   return w.fence_out(stream);
 }

@@ -15,7 +15,9 @@ count of the next point needs.  Totals are bit-identical for any number of ranks
 
 discrete_simulation runs the same harness over the BSC, the BEC or both at once (cc_mc_run_discrete_dev; for RS codes
 the q-ary symmetric and the symbol erasure channel), on a ladder of channel probabilities; burst_simulation over the
-two-state Gilbert-Elliott channel run along symbol-interleaved blocks (cc_mc_run_burst_dev), sharded in whole blocks.
+two-state Gilbert-Elliott channel run along symbol-interleaved blocks (cc_mc_run_burst_dev), sharded in whole blocks;
+with a burst detector (p_detect, p_false_alarm) the flagged symbols go to the decoder as erasures
+(cc_mc_run_burst_erasure_dev).
 
 The ladder's start point follows the reference's own Shannon-limit look-up ``ebno()`` (simulation.c++:21-70)
 including its indexing (see `reference_ebno`), so every "<decoder>.log" starts on the line the reference's does.
@@ -192,9 +194,10 @@ class _ShardedSimulation:
         v = t.cpu().tolist()
         return bool(v[0]), int(v[1]) | (int(v[2]) << 32)
 
-    def _ladder(self, log_name, column, row_value):
+    def _ladder(self, log_name, column, row_value, header_note=""):
         """Every point of self.points() with the adaptive sample count; rank 0 writes the reference-format log
-        `log_name` whose first column, headed `column`, shows row_value(point)."""
+        `log_name` whose first column, headed `column`, shows row_value(point); header_note is appended to the header
+        line."""
         dist = self._dist()
         rank = dist.get_rank() if dist else 0
         log, error = None, None
@@ -204,7 +207,7 @@ class _ShardedSimulation:
                 if os.path.exists(path):
                     raise RuntimeError("File %s already exists." % path)  # simulation.c++:72-81
                 log = open(path, "w")
-                log.write("%7s %21s\n" % (column, "wer"))
+                log.write("%7s %21s%s\n" % (column, "wer", header_note))
             except (OSError, RuntimeError) as e:
                 error = e
         ok, self.seed = self._agree(error is None, self.seed)
@@ -363,13 +366,16 @@ class discrete_simulation(_ShardedSimulation):
 # ---- the Gilbert-Elliott burst channel along interleaved blocks (cc_mc_run_burst_dev) ----
 class BurstBackend:
     """Counts one shard of one burst-channel point on this rank's GPU through cc_mc_run_burst_dev; a point is the symbol
-    error probability of the bad state."""
+    error probability of the bad state.  With a burst detector (p_detect or p_false_alarm not 0) through
+    cc_mc_run_burst_erasure_dev: the flagged symbols are erasures to the decoder."""
 
-    def __init__(self, code, interleave=1, p_gb=0.0, p_bg=1.0, p_error_good=0.0, random_codewords=False):
+    def __init__(self, code, interleave=1, p_gb=0.0, p_bg=1.0, p_error_good=0.0, random_codewords=False, *,
+                 p_detect=0.0, p_false_alarm=0.0):
         import torch
         self.torch = torch
         self.code = code
         self.interleave, self.p_gb, self.p_bg, self.p_error_good = int(interleave), p_gb, p_bg, p_error_good
+        self.p_detect, self.p_false_alarm = p_detect, p_false_alarm
         self.random_codewords = bool(random_codewords)
         self.device = torch.device("cuda", torch.cuda.current_device())
 
@@ -378,9 +384,16 @@ class BurstBackend:
         ch = capi.BurstChannel(self.interleave, self.p_gb, self.p_bg, self.p_error_good, point)
         counters = torch.zeros(capi.MC_NCOUNTERS, dtype=torch.int64, device=self.device)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = capi.lib().cc_mc_run_burst_dev(self.code._h, C.byref(ch), int(seed), int(first_frame), int(frames),
-                                            int(self.random_codewords), C.c_void_p(counters.data_ptr()), stream)
-        capi.check(rc, "cc_mc_run_burst_dev")
+        if self.p_detect == 0.0 and self.p_false_alarm == 0.0:
+            rc = capi.lib().cc_mc_run_burst_dev(self.code._h, C.byref(ch), int(seed), int(first_frame), int(frames),
+                                                int(self.random_codewords), C.c_void_p(counters.data_ptr()), stream)
+            capi.check(rc, "cc_mc_run_burst_dev")
+        else:
+            det = capi.BurstDetector(self.p_detect, self.p_false_alarm)
+            rc = capi.lib().cc_mc_run_burst_erasure_dev(self.code._h, C.byref(ch), C.byref(det), int(seed),
+                                                        int(first_frame), int(frames), int(self.random_codewords),
+                                                        C.c_void_p(counters.data_ptr()), stream)
+            capi.check(rc, "cc_mc_run_burst_erasure_dev")
         return counters  # stays on the device: reduced with RCCL
 
 
@@ -396,12 +409,18 @@ class burst_simulation(_ShardedSimulation):
     `interleave` -- what an interleaver of that depth buys on a channel with memory.  p_gb / p_bg: the transition
     probabilities good -> bad / bad -> good per transmitted symbol; a point is p_error_bad, the symbol error probability
     in the bad state (default points: discrete_ladder()), p_error_good that of the good state.  The frames of a point are
-    rounded up to whole blocks and the ranks' shards cut at blocks.  Rank 0 writes "<to_string()>.burst.log"."""
+    rounded up to whole blocks and the ranks' shards cut at blocks.  Rank 0 writes "<to_string()>.burst.log".
+    p_detect / p_false_alarm: a burst detector that flags a symbol with these probabilities in the bad / good state; the
+    flagged symbols are erasures to the decoder (cc_mc_run_burst_erasure_dev) and the log's header line names the
+    detector.  Both 0 (the default): no detector, errors-only decoding, the log as it always was."""
 
     counter_names = DISCRETE_COUNTER_NAMES
 
     def __init__(self, code, interleave=1, p_gb=0.01, p_bg=0.1, p_error_good=0.0, p_error_bad=None, points=None, seed=0,
-                 random_codewords=True, backend=None, log_dir=None, max_samples=None, samples_per_point=None):
+                 random_codewords=True, backend=None, log_dir=None, max_samples=None, samples_per_point=None, *,
+                 p_detect=0.0, p_false_alarm=0.0):
+        self.p_detect = _probability(p_detect, "p_detect")
+        self.p_false_alarm = _probability(p_false_alarm, "p_false_alarm")
         self.interleave = int(interleave)
         if not 1 <= self.interleave <= 256:
             raise ValueError("the interleaving depth is 1 .. 256")
@@ -415,7 +434,8 @@ class burst_simulation(_ShardedSimulation):
         self.code = code
         self.seed = int(seed)
         self.backend = backend if backend is not None else BurstBackend(
-            code, self.interleave, self.p_gb, self.p_bg, self.p_error_good, random_codewords)
+            code, self.interleave, self.p_gb, self.p_bg, self.p_error_good, random_codewords,
+            p_detect=self.p_detect, p_false_alarm=self.p_false_alarm)
         self.log_dir = log_dir
         self.max_samples = max_samples
         self.samples_per_point = samples_per_point
@@ -427,12 +447,17 @@ class burst_simulation(_ShardedSimulation):
         """Decode `frames` frames (rounded up to whole blocks) of one point, sharded over the ranks."""
         res = self._counters(point, frames, point_index)
         res["p_error_bad"], res["interleave"] = point, self.interleave
+        if self.p_detect or self.p_false_alarm:
+            res["p_detect"], res["p_false_alarm"] = self.p_detect, self.p_false_alarm
         res["wer"] = res["word_errors"] / max(1, res["frames"])
         res["ber"] = res["bit_errors"] / max(1, res["frames"] * self.code.n)  # wrong symbols per symbol for RS
         return res
 
     def __call__(self):
-        return self._ladder("%s.burst.log" % self.code.to_string(), "p", lambda pt: pt)
+        note = ""
+        if self.p_detect or self.p_false_alarm:
+            note = "  detector p_detect=%.6g p_false_alarm=%.6g" % (self.p_detect, self.p_false_alarm)
+        return self._ladder("%s.burst.log" % self.code.to_string(), "p", lambda pt: pt, note)
 
 
 class bitflip_simulation:

@@ -326,6 +326,45 @@ int cc_burst_channel_dev(const cc_code *code, const cc_burst_channel *ch, uint64
 int cc_mc_run_burst_dev(const cc_code *code, const cc_burst_channel *ch, uint64_t seed, uint64_t first_frame,
                         size_t frames, int random_codewords, uint64_t *d_counters, void *stream);
 
+/* ---- the burst channel with a burst detector: a receiver that flags the symbols of a burst and hands them to the
+ *      decoder as erasures (an erasure costs one unit of the 2t budget, an error two).  Everything of the burst channel
+ *      above stays -- blocks, transmission order t = p I + j, one chain per block, domains 5, 6 and 7, thresholds, the
+ *      words sent.  Added, with DB = llround(p_detect 2^32) and DG = llround(p_false_alarm 2^32) taken on the host in 64
+ *      bits and compared against the zero-extended word (1.0 flags always, 0.0 never):
+ *        domain 8, c2 = t >> 2        word t & 3 = d_t: symbol t is FLAGGED iff d_t < (s_t bad ? DB : DG)
+ *      The draws of domains 6 and 7 do not depend on the flags.  A flagged symbol is received as 0, as an erased position
+ *      of the discrete channels is; an unflagged symbol as sent ^ e where it is in error.  A min-sum handle gets +0.0 at a
+ *      flagged symbol; a hard handle the received symbols with the flagged positions as its erasure list (BCH with the PGZ
+ *      tag: the two-trial rule).  A frame with more than 2t flags gets the status the decoders give it and counts as a
+ *      failure.  CC_MC_CHANNEL_ERASURES counts the flagged symbols, CC_MC_CHANNEL_BIT_ERRORS the symbols in error that are
+ *      not flagged, every other counter is as cc_mc_run_burst_dev counts it.  DB = DG = 0: no list is built, the decoder
+ *      is handed NULL, and every output and counter equals that of the two entry points above for the same arguments.
+ *      Refused: everything cc_mc_run_burst_dev / cc_burst_channel_dev refuse, in their order; then, still before a device
+ *      is asked for, CC_ERR_INVALID_ARGUMENT for a NULL det, a wrong struct_size, a non-zero reserved, a probability
+ *      outside [0, 1] or not finite, exactly one of the two CSR pointers NULL, frames * n >= 2^32 with a list;
+ *      CC_ERR_UNSUPPORTED for an RS handle with the PGZ tag when DB | DG != 0 ("The PGZ-Algorithm does not support
+ *      erasure decoding"). ---- */
+typedef struct cc_burst_detector {
+  uint32_t struct_size;  /* = sizeof(cc_burst_detector) = 24 */
+  uint32_t reserved;     /* 0 */
+  double p_detect;       /* P(flag | bad state)  */
+  double p_false_alarm;  /* P(flag | good state) */
+} cc_burst_detector;
+/* channel only.  d_recv, d_sent, d_state and d_flag (one byte per transmitted symbol, 0 / 1) are in transmission order
+ * [frames/I][n][I]; d_sent, d_state and d_flag may be NULL.  The erasure list is a CSR PER FRAME in frame-major numbering,
+ * f = b I + j (the index of cc_deinterleave_dev and of the cc_*_interleaved_batch_dev calls): frame f's flagged positions
+ * p, ascending, are d_erasures[off[f] .. off[f+1]); d_erasure_offsets frames + 1 words, d_erasures capacity frames * n;
+ * both NULL or neither; one CSR covers the whole call. */
+int cc_burst_erasure_channel_dev(const cc_code *code, const cc_burst_channel *ch, const cc_burst_detector *det,
+                                 uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
+                                 uint8_t *d_recv, uint8_t *d_sent, uint8_t *d_state, uint8_t *d_flag,
+                                 uint16_t *d_erasures, uint32_t *d_erasure_offsets, void *stream);
+/* channel -> erase the flagged symbols -> decode with the handle's algorithm -> count: exactly what the channel-only
+ * call, cc_deinterleave_dev, the plain decode with the per-frame lists and a comparison with the words sent count */
+int cc_mc_run_burst_erasure_dev(const cc_code *code, const cc_burst_channel *ch, const cc_burst_detector *det,
+                                uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
+                                uint64_t *d_counters, void *stream);
+
 /* ---- fields GF(2^q) with q = 9 .. 15 (galois.h:44-53: "uint16_t allows galois fields up to 2^15"): symbols are
  *      16 bits wide, n = 2^q - 1 <= 32767.  Hard-decision algorithms (PGZ as bounded-distance BM, BM, Euklid), with
  *      erasures; division_tag coding.  The byte entry points above return CC_ERR_UNSUPPORTED on such a handle and

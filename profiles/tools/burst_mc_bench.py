@@ -9,6 +9,12 @@ average symbol error rate as the yardstick of the same session, and the word-err
     python profiles/tools/burst_mc_bench.py --stats STATS.csv     channel / count / decoder split of the kernel time of a
                                                                   `rocprofv3 --kernel-trace --stats` run, and the time of
                                                                   burst_kernel over that of discrete_kernel
+    python profiles/tools/burst_mc_bench.py --p-detect 0.9 --p-false-alarm 0.002
+                                                                  with a burst detector: cc_mc_run_burst_erasure_dev (the
+                                                                  flagged symbols are erasures to the decoder) alternating
+                                                                  with cc_mc_run_burst_dev, the errors-only route, on the
+                                                                  same handle and channel; --route erasure for the
+                                                                  detector route alone; --stats then adds the list stage
 """
 import argparse
 import csv
@@ -34,6 +40,8 @@ WORKLOADS = {
 CHANNEL = ("burst_kernel", "discrete_kernel", "random_symbols_kernel", "random_bits_kernel", "encode",
            "bitslice_fused_syndrome_kernel<false, true>", "bitslice_parity_kernel")
 COUNT = ("count_kernel",)
+LIST = ("flag_count_kernel", "flag_positions_kernel", "discrete_scan_tiles_kernel", "discrete_scan_sums_kernel",
+        "discrete_positions_kernel")
 
 
 def average_error_rate():
@@ -63,6 +71,33 @@ def timed(runs, frames, reps):
     return out
 
 
+def bench_detector(names, reps, route, p_detect, p_false_alarm):
+    """the detector route against the errors-only route of the same handle, channel and session"""
+    from channelcoding_amd import capi
+    from channelcoding_amd.montecarlo import BurstBackend
+    print("# (p_gb, p_bg, p_good, p_bad) = (%g, %g, %g, %g), detector (p_detect, p_false_alarm) = (%g, %g); %d frames, %d "
+          "rounds, the two routes alternating" % (P_GB, P_BG, P_GOOD, P_BAD, p_detect, p_false_alarm, FRAMES, reps),
+          flush=True)
+    for name in names or WORKLOADS:
+        family, t, I = WORKLOADS[name]
+        h = make(family, t)
+        plain = BurstBackend(h, I, P_GB, P_BG, P_GOOD, random_codewords=True)
+        flagged = BurstBackend(h, I, P_GB, P_BG, P_GOOD, random_codewords=True, p_detect=p_detect,
+                               p_false_alarm=p_false_alarm)
+        runs = {}
+        if route in ("both", "erasure"):
+            runs["erasure"] = lambda f: flagged.run(P_BAD, 0, 0, f)
+        if route in ("both", "burst"):
+            runs["burst"] = lambda f: plain.run(P_BAD, 0, 0, f)
+        for kind, (times, c) in timed(runs, FRAMES, reps).items():
+            best, med = min(times), statistics.median(times)
+            print("%-10s %-8s %s I=%d: %8.2f M frames/s best (%.2f ms), %8.2f median  wer=%.4g  channel errors %.4g, "
+                  "erasures %.4g per frame" % (name, kind, h.to_string(), I, FRAMES / best / 1e6, best * 1e3,
+                                               FRAMES / med / 1e6, int(c[capi.MC_WORD_ERRORS]) / FRAMES,
+                                               int(c[capi.MC_CHANNEL_BIT_ERRORS]) / FRAMES,
+                                               int(c[capi.MC_CHANNEL_ERASURES]) / FRAMES), flush=True)
+
+
 def bench(names, reps, route):
     from channelcoding_amd import capi
     from channelcoding_amd.montecarlo import BurstBackend, DiscreteBackend
@@ -87,7 +122,7 @@ def bench(names, reps, route):
 
 
 def stats(path):
-    groups = {"channel": 0, "count": 0, "decoder": 0}
+    groups = {"channel": 0, "list": 0, "count": 0, "decoder": 0}
     names = {k: [] for k in groups}
     single = {"burst_kernel": 0, "discrete_kernel": 0}
     with open(path) as f:
@@ -98,7 +133,8 @@ def stats(path):
             for k in single:
                 if k in name:
                     single[k] += ns
-            g = "channel" if any(k in name for k in CHANNEL) else "count" if any(k in name for k in COUNT) else "decoder"
+            g = ("list" if any(k in name for k in LIST) else "channel" if any(k in name for k in CHANNEL)
+                 else "count" if any(k in name for k in COUNT) else "decoder")
             groups[g] += ns
             names[g].append("%s (%.2f ms)" % (name[:60], ns / 1e6))
     total = sum(groups.values())
@@ -116,11 +152,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", action="append", choices=sorted(WORKLOADS))
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--route", choices=("both", "burst", "discrete"), default="both")
+    ap.add_argument("--route", choices=("both", "burst", "discrete", "erasure"), default="both")
+    ap.add_argument("--p-detect", type=float, default=0.0)
+    ap.add_argument("--p-false-alarm", type=float, default=0.0)
     ap.add_argument("--stats")
     a = ap.parse_args()
     if a.stats:
         stats(a.stats)
+    elif a.p_detect or a.p_false_alarm:
+        bench_detector(a.only, a.reps, a.route, a.p_detect, a.p_false_alarm)
     else:
         bench(a.only, a.reps, a.route)
 
