@@ -366,9 +366,14 @@ struct McWorkspace {
 
 void mc_workspace_free(McWorkspace *w) { delete w; }
 
-static int ensure_workspace(cc_code *code, size_t chunk) {
+// the handle's workspace, created on first use: the one place that creates it
+static McWorkspace &mc_workspace(const cc_code *code) {
+  std::lock_guard<std::mutex> g(code->lazy_lock);
   if (!code->mc) code->mc = new McWorkspace();
-  McWorkspace &w = *code->mc;
+  return *code->mc;
+}
+
+static int ensure_workspace(const cc_code *code, McWorkspace &w, size_t chunk) {
   if (w.chunk >= chunk) return CC_OK;
   const size_t n = code->tab.n, l = code->tab.l;
   for (void **p : {reinterpret_cast<void **>(&w.llr), reinterpret_cast<void **>(&w.sent),
@@ -392,6 +397,27 @@ static int ensure_workspace(cc_code *code, size_t chunk) {
   return CC_OK;
 }
 
+// The skeleton of every Monte-Carlo and channel call: under the workspace's lock, buffers for workspace_frames frames
+// (0: the call uses none of them), the wait for the call before, body(w, done, m) for the frames [done, done + m) of
+// each chunk, and the event the next call waits for.  A failing body ends the call where it stands.
+template <class Body>
+static int mc_chunked(const cc_code *code, size_t frames, size_t chunk, size_t workspace_frames, hipStream_t stream,
+                      Body body) {
+  McWorkspace &w = mc_workspace(code);
+  std::lock_guard<std::mutex> guard(w.lock);
+  int rc = workspace_frames ? ensure_workspace(code, w, workspace_frames) : CC_OK;
+  if (rc != CC_OK) return rc;
+  rc = w.fence_in(stream);
+  if (rc != CC_OK) return rc;
+  for (size_t done = 0; done < frames; done += chunk) {
+    rc = body(w, done, frames - done < chunk ? frames - done : chunk);
+    if (rc != CC_OK) return rc;
+  }
+  return w.fence_out(stream);
+}
+
+constexpr size_t MC_CHUNK = size_t(1) << 20;  // ~1.6 GB of workspace for n = 255: long launches, short tails
+
 // the transmitted words of frames [first, first + frames): random messages through the device encoder
 static int launch_sent_words(const cc_code *code, uint64_t seed, uint64_t first_frame, size_t frames, uint8_t *d_sent,
                              uint8_t *d_msg_scratch, hipStream_t stream) {
@@ -404,6 +430,47 @@ static int launch_sent_words(const cc_code *code, uint64_t seed, uint64_t first_
   hipLaunchKernelGGL(random_bits_kernel, dim3(grid_for(code, items)), dim3(256), 0, stream, d_msg_scratch, l, bits_log2,
                      static_cast<unsigned long long>(first_frame), static_cast<unsigned long long>(frames), k0, k1);
   return launch_encode_bits(code, d_msg_scratch, d_sent, frames, stream);
+}
+
+namespace {
+int launch_discrete_sent(const cc_code *code, uint64_t seed, uint64_t first_frame, size_t frames, uint8_t *d_sent,
+                         uint8_t *d_msg_scratch, hipStream_t stream);
+}
+
+// What the channel kernel of frames [first, first + m) reads as the transmitted words, to *sent.  Random codewords: made
+// in `words` (launch_discrete_sent).  Otherwise the all-zero word, nullptr: no word to keep, nothing to read back, and a
+// caller's buffer `zeroed` (may be nullptr) cleared.
+static int transmitted_words(const cc_code *code, uint64_t seed, uint64_t first_frame, size_t m, int random_codewords,
+                             uint8_t *words, uint8_t *d_msg_scratch, uint8_t *zeroed, hipStream_t stream,
+                             const uint8_t **sent) {
+  *sent = random_codewords ? words : nullptr;
+  if (random_codewords) return launch_discrete_sent(code, seed, first_frame, m, words, d_msg_scratch, stream);
+  if (zeroed) CC_HIP_TRY(hipMemsetAsync(zeroed, 0, m * code->tab.n, stream));
+  return CC_OK;
+}
+
+// the decoder over the m frames in w.llr (floats for a min-sum handle, bytes for a hard one, with the erasure CSR
+// er / off or nullptr): decisions to w.hard, w.iters or w.nerr, w.status
+static int launch_decoder(const cc_code *code, McWorkspace &w, const uint16_t *er, const uint32_t *off, size_t m,
+                          hipStream_t stream) {
+  if (code->soft) return launch_minsum(code, w.llr, nullptr, nullptr, w.hard, nullptr, w.iters, w.status, m, stream);
+  const uint8_t *recv = reinterpret_cast<const uint8_t *>(w.llr);
+  if (er && code->desc.algorithm == CC_ALG_PGZ)  // the BCH two-trial rule, as cc_correct_hard_batch_dev
+    return launch_pgz_erasures(code, recv, er, off, w.hard, w.nerr, w.status, m, stream);
+  return launch_algebraic(code, false, recv, er, off, w.hard, w.nerr, w.status, m, stream);
+}
+
+// the counting pass over the decoder's output for m frames; list / list_count: the compact batch of the pre-check route
+static int launch_count(const cc_code *code, McWorkspace &w, const uint8_t *sent, size_t m, uint64_t *d_counters,
+                        hipStream_t stream, const uint32_t *list = nullptr, const uint32_t *list_count = nullptr) {
+  const unsigned long long blocks = (m + 15) / 16, max_grid = static_cast<unsigned long long>(code->num_cus) * 8;
+  hipLaunchKernelGGL(count_kernel, dim3(static_cast<int>(blocks < max_grid ? blocks : max_grid)), dim3(256), 0, stream,
+                     w.hard, sent, code->soft ? w.iters : nullptr, w.status, static_cast<int>(code->tab.n),
+                     code->desc.iterations, static_cast<unsigned long long>(m),
+                     reinterpret_cast<unsigned long long *>(d_counters), list, list_count);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "count kernel launch");
+  return CC_OK;
 }
 
 // The pre-check route (awgn_precheck_kernel) serves the diagonal min-sum kernels of the n = 129..256 codes and pays
@@ -422,22 +489,13 @@ static bool mc_precheck_pays(const cc_code *code, double ebno_db) {
   return std::pow(1.0 - pbit, static_cast<double>(n)) >= 0.25;
 }
 
-// writes y (and the transmitted words when d_sent != nullptr) for frames [first, first + frames)
-int launch_awgn(const cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
-                int random_codewords, float *d_llr, uint8_t *d_sent, uint8_t *d_msg_scratch, hipStream_t stream,
-                unsigned long long *d_counters = nullptr, bool hard_bytes = false) {
-  if (frames == 0) return CC_OK;
+// writes y for frames [first, first + frames) of the words `sent` (nullptr: the all-zero word)
+static int launch_awgn(const cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
+                       float *d_llr, const uint8_t *sent, hipStream_t stream, unsigned long long *d_counters = nullptr,
+                       bool hard_bytes = false) {
   const int n = static_cast<int>(code->tab.n);
   const float sigma = static_cast<float>(cc_sigma(code, ebno_db));  // normal_distribution<float>(1.0, float(sigma))
   const uint32_t k0 = static_cast<uint32_t>(seed), k1 = static_cast<uint32_t>(seed >> 32);
-  const uint8_t *sent = nullptr;
-  if (random_codewords) {
-    const int rc = launch_sent_words(code, seed, first_frame, frames, d_sent, d_msg_scratch, stream);
-    if (rc != CC_OK) return rc;
-    sent = d_sent;
-  } else if (d_sent) {
-    CC_HIP_TRY(hipMemsetAsync(d_sent, 0, frames * static_cast<size_t>(n), stream));
-  }
   int group_log2 = 0;
   while ((4 << group_log2) < n) ++group_log2;
   const unsigned long long items = static_cast<unsigned long long>(frames) << group_log2;
@@ -457,91 +515,56 @@ int launch_awgn(const cc_code *code, double ebno_db, uint64_t seed, uint64_t fir
 int mc_run(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
            uint64_t *d_counters, hipStream_t stream) {
   if (frames == 0) return CC_OK;
-  const size_t chunk_max = size_t(1) << 20;  // ~1.6 GB of workspace for n = 255: long launches, short tails
-  const size_t chunk = frames < chunk_max ? frames : chunk_max;
-  if (!code->mc) code->mc = new McWorkspace();
-  std::lock_guard<std::mutex> guard(code->mc->lock);
-  int rc = ensure_workspace(code, chunk);
-  if (rc != CC_OK) return rc;
-  McWorkspace &w = *code->mc;
-  rc = w.fence_in(stream);
-  if (rc != CC_OK) return rc;
+  const size_t chunk = frames < MC_CHUNK ? frames : MC_CHUNK;
   const int n = static_cast<int>(code->tab.n);
   const bool precheck = mc_precheck_pays(code, ebno_db);
-  for (size_t done = 0; done < frames; done += chunk) {
-    const size_t m = frames - done < chunk ? frames - done : chunk;
-    // all-zero transmission (simulation.c++:113-125): no word to keep, nothing to clear or to read back
-    uint8_t *sent = random_codewords ? w.sent : nullptr;
-    if (precheck) {
-      // transmitted words first (random codewords), then channel + pre-check, the decoder on what is left, the counts
-      if (random_codewords) {
-        rc = launch_sent_words(code, seed, first_frame + done, m, w.sent, w.msg, stream);
-        if (rc != CC_OK) return rc;
-      }
-      uint32_t *ctl = w.list, *pool = w.list + 64, *list = w.list + 64 + POOL_WORDS;
-      CC_HIP_TRY(hipMemsetAsync(ctl, 0, (64 + POOL_WORDS) * sizeof(uint32_t), stream));
-      const float sigma = static_cast<float>(cc_sigma(code, ebno_db));
-      const unsigned long long wg = (m + 31) / 32, cap = static_cast<unsigned long long>(code->num_cus) * 8;
-      hipLaunchKernelGGL(awgn_precheck_kernel, dim3(static_cast<int>(wg < cap ? wg : cap)), dim3(256), 0, stream, w.llr, list,
-                         ctl, sent, code->d_colbits, n, code->desc.stop_rule,
-                         static_cast<unsigned long long>(first_frame + done), static_cast<unsigned long long>(m), sigma,
-                         static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32),
-                         reinterpret_cast<unsigned long long *>(d_counters));
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return hip_fail(e, "awgn pre-check kernel launch");
-      rc = launch_minsum_diag_compact(code, ctl, pool, static_cast<unsigned>(m), w.llr, w.hard, w.iters, w.status, stream);
+  unsigned long long *counters = reinterpret_cast<unsigned long long *>(d_counters);
+  return mc_chunked(code, frames, chunk, chunk, stream, [&](McWorkspace &w, size_t done, size_t m) -> int {
+    const uint8_t *sent;
+    int rc = transmitted_words(code, seed, first_frame + done, m, random_codewords, w.sent, w.msg, nullptr, stream, &sent);
+    if (rc != CC_OK) return rc;
+    if (!precheck) {
+      // (a hard-decision decoder takes bits from the channel: the hard decisions as bytes in the same buffer)
+      rc = launch_awgn(code, ebno_db, seed, first_frame + done, m, w.llr, sent, stream, counters, !code->soft);
       if (rc != CC_OK) return rc;
-      const unsigned long long blocks = (m + 15) / 16, max_grid = static_cast<unsigned long long>(code->num_cus) * 8;
-      hipLaunchKernelGGL(count_kernel, dim3(static_cast<int>(blocks < max_grid ? blocks : max_grid)), dim3(256), 0, stream,
-                         w.hard, sent, w.iters, w.status, n, code->desc.iterations, static_cast<unsigned long long>(m),
-                         reinterpret_cast<unsigned long long *>(d_counters), list, ctl + 1);
-      e = hipGetLastError();
-      if (e != hipSuccess) return hip_fail(e, "count kernel launch");
-      continue;
+      rc = launch_decoder(code, w, nullptr, nullptr, m, stream);
+      if (rc != CC_OK) return rc;
+      return launch_count(code, w, sent, m, d_counters, stream);
     }
-    // (a hard-decision decoder takes bits from the channel: the hard decisions as bytes in the same buffer)
-    rc = launch_awgn(code, ebno_db, seed, first_frame + done, m, random_codewords, w.llr, sent, w.msg, stream,
-                     reinterpret_cast<unsigned long long *>(d_counters), !code->soft);
-    if (rc != CC_OK) return rc;
-    if (code->soft)
-      rc = launch_minsum(code, w.llr, nullptr, nullptr, w.hard, nullptr, w.iters, w.status, m, stream);
-    else
-      rc = launch_algebraic(code, false, w.llr, nullptr, nullptr, w.hard, w.nerr, w.status, m, stream);
-    if (rc != CC_OK) return rc;
-    const unsigned long long blocks = (m + 15) / 16;
-    const unsigned long long max_grid = static_cast<unsigned long long>(code->num_cus) * 8;
-    hipLaunchKernelGGL(count_kernel, dim3(static_cast<int>(blocks < max_grid ? blocks : max_grid)), dim3(256), 0, stream,
-                       w.hard, sent, code->soft ? w.iters : nullptr, w.status, n, code->desc.iterations,
-                       static_cast<unsigned long long>(m), reinterpret_cast<unsigned long long *>(d_counters));
+    // channel + pre-check, the decoder on what is left, the counts
+    uint32_t *ctl = w.list, *pool = w.list + 64, *list = w.list + 64 + POOL_WORDS;
+    CC_HIP_TRY(hipMemsetAsync(ctl, 0, (64 + POOL_WORDS) * sizeof(uint32_t), stream));
+    const float sigma = static_cast<float>(cc_sigma(code, ebno_db));
+    const unsigned long long wg = (m + 31) / 32, cap = static_cast<unsigned long long>(code->num_cus) * 8;
+    hipLaunchKernelGGL(awgn_precheck_kernel, dim3(static_cast<int>(wg < cap ? wg : cap)), dim3(256), 0, stream, w.llr, list,
+                       ctl, sent, code->d_colbits, n, code->desc.stop_rule,
+                       static_cast<unsigned long long>(first_frame + done), static_cast<unsigned long long>(m), sigma,
+                       static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), counters);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "count kernel launch");
-  }
-  return w.fence_out(stream);
+    if (e != hipSuccess) return hip_fail(e, "awgn pre-check kernel launch");
+    rc = launch_minsum_diag_compact(code, ctl, pool, static_cast<unsigned>(m), w.llr, w.hard, w.iters, w.status, stream);
+    if (rc != CC_OK) return rc;
+    return launch_count(code, w, sent, m, d_counters, stream, list, ctl + 1);
+  });
 }
-
 
 // cc_awgn_llr_dev: channel only, chunked so that the message scratch stays bounded
 int mc_awgn(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
             float *d_llr, uint8_t *d_sent, hipStream_t stream) {
   if (frames == 0) return CC_OK;
-  if (!random_codewords) return launch_awgn(code, ebno_db, seed, first_frame, frames, 0, d_llr, d_sent, nullptr, stream);
-  const size_t chunk_max = size_t(1) << 20;  // ~1.6 GB of workspace for n = 255: long launches, short tails
-  const size_t chunk = frames < chunk_max ? frames : chunk_max;
-  if (!code->mc) code->mc = new McWorkspace();
-  std::lock_guard<std::mutex> guard(code->mc->lock);
-  int rc = ensure_workspace(code, chunk);
-  if (rc != CC_OK) return rc;
-  McWorkspace &w = *code->mc;
-  rc = w.fence_in(stream);
-  if (rc != CC_OK) return rc;
   const size_t n = code->tab.n;
-  for (size_t done = 0; done < frames; done += chunk) {
-    const size_t m = frames - done < chunk ? frames - done : chunk;
-    uint8_t *sent = d_sent ? d_sent + done * n : w.sent;
-    rc = launch_awgn(code, ebno_db, seed, first_frame + done, m, 1, d_llr + done * n, sent, w.msg, stream);
-    if (rc != CC_OK) return rc;
+  if (!random_codewords) {  // one launch, no buffer of the workspace
+    const uint8_t *sent;
+    const int rc = transmitted_words(code, seed, first_frame, frames, 0, nullptr, nullptr, d_sent, stream, &sent);
+    return rc != CC_OK ? rc : launch_awgn(code, ebno_db, seed, first_frame, frames, d_llr, sent, stream);
   }
-  return w.fence_out(stream);
+  const size_t chunk = frames < MC_CHUNK ? frames : MC_CHUNK;
+  return mc_chunked(code, frames, chunk, chunk, stream, [&](McWorkspace &w, size_t done, size_t m) -> int {
+    const uint8_t *sent;
+    const int rc = transmitted_words(code, seed, first_frame + done, m, 1, d_sent ? d_sent + done * n : w.sent, w.msg,
+                                     nullptr, stream, &sent);
+    return rc != CC_OK ? rc : launch_awgn(code, ebno_db, seed, first_frame + done, m, d_llr + done * n, sent, stream);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -810,9 +833,7 @@ int launch_discrete_sent(const cc_code *code, uint64_t seed, uint64_t first_fram
   return launch_encode(code, d_msg_scratch, d_sent, frames, stream);
 }
 
-// The channel over frames [first, first + m), m <= 2^20 (the scan's two levels cover 1024 x 1024 frames).  er != nullptr:
-// the erasure CSR into er / off[0 .. m], with count, local (m words each) and tiles (m / 1024 + 1 words) as scratch and
-// carry = the entries already in er (nullptr: 0).
+// what the channel writes (soft or recv) and where an erasure CSR and its scratch sit (er == nullptr: no list)
 struct DiscreteIO {
   float *soft = nullptr;
   uint8_t *recv = nullptr;
@@ -821,6 +842,46 @@ struct DiscreteIO {
   const uint32_t *carry = nullptr;
 };
 
+// The erasure list of m frames placed in the workspace, behind the received bytes of a hard handle: inside the 4 n bytes
+// per frame of w.llr the received bytes (n per frame) and, 16-byte aligned behind them, the positions (at most 2 n bytes
+// per frame); counts and tile-local prefixes in w.nerr / w.status until the decoder writes them, offsets and tile sums in
+// w.list.
+DiscreteIO workspace_list(McWorkspace &w, size_t m, size_t n) {
+  DiscreteIO io;
+  io.er = reinterpret_cast<uint16_t *>(reinterpret_cast<uint8_t *>(w.llr) + ((m * n + 15) & ~size_t(15)));
+  io.off = w.list;
+  io.tiles = w.list + m + 1;
+  io.count = reinterpret_cast<uint32_t *>(w.nerr);
+  io.local = reinterpret_cast<uint32_t *>(w.status);
+  return io;
+}
+// the frames a workspace with that list is made for: from 16 frames on the bytes and the aligned positions fit in 4 n
+size_t workspace_frames_with_list(size_t chunk) { return chunk < 16 ? 16 : chunk; }
+
+// The erasure list of the chunk [done, done + m) placed in the caller's buffers, one CSR over all chunks of the call: the
+// chunk's scan starts from the entries of the chunks before it, read on the device; scratch from the workspace.
+DiscreteIO caller_list(McWorkspace &w, uint16_t *d_erasures, uint32_t *d_erasure_offsets, size_t done) {
+  DiscreteIO io;
+  io.er = d_erasures;
+  io.off = d_erasure_offsets + done;
+  io.tiles = w.list;
+  io.count = reinterpret_cast<uint32_t *>(w.nerr);
+  io.local = reinterpret_cast<uint32_t *>(w.status);
+  io.carry = done ? d_erasure_offsets + done : nullptr;
+  return io;
+}
+
+// io.count[0 .. m) -> tile-local prefixes in io.local, tile bases in io.tiles, the total (with the carry) in io.off[m]
+void launch_list_scan(const DiscreteIO &io, size_t m, hipStream_t stream) {
+  const unsigned long long frames = m;
+  const unsigned ntiles = static_cast<unsigned>((frames + SCAN_TILE - 1) / SCAN_TILE);
+  hipLaunchKernelGGL(discrete_scan_tiles_kernel, dim3(ntiles), dim3(256), 0, stream, io.count, io.local, io.tiles, frames);
+  hipLaunchKernelGGL(discrete_scan_sums_kernel, dim3(1), dim3(1024), 0, stream, io.tiles, ntiles, io.carry, io.off + m);
+}
+
+// The channel over frames [first, first + m), m <= 2^20 (the scan's two levels cover 1024 x 1024 frames).  er != nullptr:
+// the erasure CSR into er / off[0 .. m], with count, local (m words each) and tiles (m / 1024 + 1 words) as scratch and
+// carry = the entries already in er (nullptr: 0).
 int launch_discrete(const cc_code *code, DiscreteThresholds th, uint64_t seed, uint64_t first_frame, size_t m,
                     const uint8_t *sent, const DiscreteIO &io, unsigned long long *d_counters, hipStream_t stream) {
   const int n = static_cast<int>(code->tab.n), g = log2_lanes(n);
@@ -833,9 +894,7 @@ int launch_discrete(const cc_code *code, DiscreteThresholds th, uint64_t seed, u
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "discrete channel kernel launch");
   if (!io.er) return CC_OK;
-  const unsigned ntiles = static_cast<unsigned>((frames + SCAN_TILE - 1) / SCAN_TILE);
-  hipLaunchKernelGGL(discrete_scan_tiles_kernel, dim3(ntiles), dim3(256), 0, stream, io.count, io.local, io.tiles, frames);
-  hipLaunchKernelGGL(discrete_scan_sums_kernel, dim3(1), dim3(1024), 0, stream, io.tiles, ntiles, io.carry, io.off + m);
+  launch_list_scan(io, m, stream);
   hipLaunchKernelGGL(discrete_positions_kernel, dim3(grid), dim3(256), 0, stream, io.er, io.off, io.count, io.local,
                      io.tiles, n, g, first, frames, th.E, k0, k1);
   e = hipGetLastError();
@@ -847,66 +906,35 @@ constexpr size_t DISCRETE_CHUNK = size_t(1) << 20;  // the scan's reach: SCAN_TI
 
 }  // namespace
 
-// Monte-Carlo over the discrete channel: the route of mc_run (lock, workspace, chunks, one counting pass).  Inside the
-// workspace's 4 n bytes per frame of w.llr: the received bytes (n per frame) and, 16-byte aligned behind them, the
-// erasure positions (at most 2 n bytes per frame) -- or the +-1 / 0 floats of a min-sum handle.  Erasure counts and
-// tile-local prefixes use w.nerr / w.status before the decoder writes them, the offsets and tile sums w.list.
+// Monte-Carlo over the discrete channel: the route of mc_run with the received bytes (or the +-1 / 0 floats of a min-sum
+// handle) in w.llr and, for a hard handle, the erasure list behind them (workspace_list).
 int mc_run_discrete(cc_code *code, double p_error, double p_erasure, uint64_t seed, uint64_t first_frame, size_t frames,
                     int random_codewords, uint64_t *d_counters, hipStream_t stream) {
   if (frames == 0) return CC_OK;
-  const size_t chunk = frames < DISCRETE_CHUNK ? frames : DISCRETE_CHUNK;
-  if (!code->mc) code->mc = new McWorkspace();
-  std::lock_guard<std::mutex> guard(code->mc->lock);
-  int rc = ensure_workspace(code, chunk < 16 ? 16 : chunk);  // >= 16 frames: bytes + aligned positions fit in 4 n
-  if (rc != CC_OK) return rc;
-  McWorkspace &w = *code->mc;
-  rc = w.fence_in(stream);
-  if (rc != CC_OK) return rc;
-  const size_t n = code->tab.n;
+  const size_t chunk = frames < DISCRETE_CHUNK ? frames : DISCRETE_CHUNK, n = code->tab.n;
   const DiscreteThresholds th = discrete_thresholds(p_error, p_erasure);
-  unsigned long long *counters = reinterpret_cast<unsigned long long *>(d_counters);
-  for (size_t done = 0; done < frames; done += chunk) {
-    const size_t m = frames - done < chunk ? frames - done : chunk;
-    uint8_t *sent = random_codewords ? w.sent : nullptr;
-    if (random_codewords) {
-      rc = launch_discrete_sent(code, seed, first_frame + done, m, w.sent, w.msg, stream);
-      if (rc != CC_OK) return rc;
-    }
+  return mc_chunked(code, frames, chunk, workspace_frames_with_list(chunk), stream,
+                    [&](McWorkspace &w, size_t done, size_t m) -> int {
+    const uint8_t *sent;
+    int rc = transmitted_words(code, seed, first_frame + done, m, random_codewords, w.sent, w.msg, nullptr, stream, &sent);
+    if (rc != CC_OK) return rc;
     DiscreteIO io;
     if (code->soft) {
       io.soft = w.llr;
     } else {
+      if (th.E) io = workspace_list(w, m, n);  // (no erasure can be drawn with E = 0: no list, NULL erasures)
       io.recv = reinterpret_cast<uint8_t *>(w.llr);
-      if (th.E) {  // (no erasure can be drawn with E = 0: no list, NULL erasures for the decoder)
-        io.er = reinterpret_cast<uint16_t *>(io.recv + ((m * n + 15) & ~size_t(15)));
-        io.off = w.list;
-        io.tiles = w.list + m + 1;
-        io.count = reinterpret_cast<uint32_t *>(w.nerr);
-        io.local = reinterpret_cast<uint32_t *>(w.status);
-      }
     }
-    rc = launch_discrete(code, th, seed, first_frame + done, m, sent, io, counters, stream);
+    rc = launch_discrete(code, th, seed, first_frame + done, m, sent, io,
+                         reinterpret_cast<unsigned long long *>(d_counters), stream);
     if (rc != CC_OK) return rc;
-    if (code->soft)
-      rc = launch_minsum(code, w.llr, nullptr, nullptr, w.hard, nullptr, w.iters, w.status, m, stream);
-    else if (io.er && code->desc.algorithm == CC_ALG_PGZ)  // the BCH two-trial rule, as cc_correct_hard_batch_dev
-      rc = launch_pgz_erasures(code, io.recv, io.er, io.off, w.hard, w.nerr, w.status, m, stream);
-    else
-      rc = launch_algebraic(code, false, io.recv, io.er, io.off, w.hard, w.nerr, w.status, m, stream);
+    rc = launch_decoder(code, w, io.er, io.off, m, stream);
     if (rc != CC_OK) return rc;
-    const unsigned long long blocks = (m + 15) / 16;
-    const unsigned long long max_grid = static_cast<unsigned long long>(code->num_cus) * 8;
-    hipLaunchKernelGGL(count_kernel, dim3(static_cast<int>(blocks < max_grid ? blocks : max_grid)), dim3(256), 0, stream,
-                       w.hard, sent, code->soft ? w.iters : nullptr, w.status, static_cast<int>(n),
-                       code->desc.iterations, static_cast<unsigned long long>(m), counters);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "count kernel launch");
-  }
-  return w.fence_out(stream);
+    return launch_count(code, w, sent, m, d_counters, stream);
+  });
 }
 
-// cc_discrete_channel_dev: channel only, chunked; the erasure list of the whole call is one CSR (each chunk's scan
-// starts from the entries of the chunks before it, read on the device)
+// cc_discrete_channel_dev: channel only, chunked; the erasure list of the whole call is one CSR (caller_list)
 int mc_discrete(cc_code *code, double p_error, double p_erasure, uint64_t seed, uint64_t first_frame, size_t frames,
                 int random_codewords, uint8_t *d_recv, uint16_t *d_erasures, uint32_t *d_erasure_offsets,
                 uint8_t *d_sent, hipStream_t stream) {
@@ -914,41 +942,19 @@ int mc_discrete(cc_code *code, double p_error, double p_erasure, uint64_t seed, 
     if (d_erasure_offsets) CC_HIP_TRY(hipMemsetAsync(d_erasure_offsets, 0, sizeof(uint32_t), stream));
     return CC_OK;
   }
-  const size_t chunk = frames < DISCRETE_CHUNK ? frames : DISCRETE_CHUNK;
-  if (!code->mc) code->mc = new McWorkspace();
-  std::lock_guard<std::mutex> guard(code->mc->lock);
-  int rc = ensure_workspace(code, chunk);
-  if (rc != CC_OK) return rc;
-  McWorkspace &w = *code->mc;
-  rc = w.fence_in(stream);
-  if (rc != CC_OK) return rc;
-  const size_t n = code->tab.n;
+  const size_t chunk = frames < DISCRETE_CHUNK ? frames : DISCRETE_CHUNK, n = code->tab.n;
   const DiscreteThresholds th = discrete_thresholds(p_error, p_erasure);
-  for (size_t done = 0; done < frames; done += chunk) {
-    const size_t m = frames - done < chunk ? frames - done : chunk;
-    uint8_t *sent = d_sent ? d_sent + done * n : nullptr;
-    if (random_codewords) {
-      if (!sent) sent = w.sent;
-      rc = launch_discrete_sent(code, seed, first_frame + done, m, sent, w.msg, stream);
-      if (rc != CC_OK) return rc;
-    } else if (sent) {
-      CC_HIP_TRY(hipMemsetAsync(sent, 0, m * n, stream));
-      sent = nullptr;  // all-zero transmission: the channel kernel reads no word
-    }
-    DiscreteIO io;
-    io.recv = d_recv + done * n;
-    if (d_erasures) {
-      io.er = d_erasures;
-      io.off = d_erasure_offsets + done;
-      io.tiles = w.list;
-      io.count = reinterpret_cast<uint32_t *>(w.nerr);
-      io.local = reinterpret_cast<uint32_t *>(w.status);
-      io.carry = done ? d_erasure_offsets + done : nullptr;
-    }
-    rc = launch_discrete(code, th, seed, first_frame + done, m, sent, io, nullptr, stream);
+  return mc_chunked(code, frames, chunk, chunk, stream, [&](McWorkspace &w, size_t done, size_t m) -> int {
+    uint8_t *out = d_sent ? d_sent + done * n : nullptr;
+    const uint8_t *sent;
+    const int rc = transmitted_words(code, seed, first_frame + done, m, random_codewords, out ? out : w.sent, w.msg, out,
+                                     stream, &sent);
     if (rc != CC_OK) return rc;
-  }
-  return w.fence_out(stream);
+    DiscreteIO io;
+    if (d_erasures) io = caller_list(w, d_erasures, d_erasure_offsets, done);
+    io.recv = d_recv + done * n;
+    return launch_discrete(code, th, seed, first_frame + done, m, sent, io, nullptr, stream);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1191,17 +1197,14 @@ int launch_burst(const cc_code *code, const cc_burst_channel &ch, uint64_t seed,
     flag_t = flag_fm;
     flag_fm = nullptr;
   }
-  if (det)
-    hipLaunchKernelGGL(burst_kernel<true>, dim3(grid_for(code, items)), dim3(256), 0, stream, io.soft, io.recv,
-                       io.sent_out, io.state, sent, n, I, g, passes, fm ? 1 : 0, qm1,
-                       static_cast<unsigned long long>(first_frame / ch.interleave), blocks, burst_thresholds(ch),
-                       static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), d_counters, *det, flag_t, flag_fm);
-  else
-    hipLaunchKernelGGL(burst_kernel<false>, dim3(grid_for(code, items)), dim3(256), 0, stream, io.soft, io.recv,
-                       io.sent_out, io.state, sent, n, I, g, passes, fm ? 1 : 0, qm1,
-                       static_cast<unsigned long long>(first_frame / ch.interleave), blocks, burst_thresholds(ch),
-                       static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), d_counters, DetectorThresholds{0, 0},
-                       static_cast<uint8_t *>(nullptr), static_cast<uint8_t *>(nullptr));
+  auto launch = [&](auto kernel, DetectorThresholds thresholds, uint8_t *to_flag_t, uint8_t *to_flag_fm) {
+    hipLaunchKernelGGL(kernel, dim3(grid_for(code, items)), dim3(256), 0, stream, io.soft, io.recv, io.sent_out, io.state,
+                       sent, n, I, g, passes, fm ? 1 : 0, qm1, static_cast<unsigned long long>(first_frame / ch.interleave),
+                       blocks, burst_thresholds(ch), static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32),
+                       d_counters, thresholds, to_flag_t, to_flag_fm);
+  };
+  if (det) launch(burst_kernel<true>, *det, flag_t, flag_fm);
+  else launch(burst_kernel<false>, DetectorThresholds{0, 0}, nullptr, nullptr);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "burst channel kernel launch");
   return CC_OK;
@@ -1265,10 +1268,8 @@ int launch_flag_list(const cc_code *code, const uint8_t *map, size_t m, const Di
   const int n = static_cast<int>(code->tab.n), g = log2_lanes(n);
   const unsigned long long frames = m;
   const int grid = grid_for(code, frames << g);
-  const unsigned ntiles = static_cast<unsigned>((frames + SCAN_TILE - 1) / SCAN_TILE);
   hipLaunchKernelGGL(flag_count_kernel, dim3(grid), dim3(256), 0, stream, io.count, map, n, g, frames);
-  hipLaunchKernelGGL(discrete_scan_tiles_kernel, dim3(ntiles), dim3(256), 0, stream, io.count, io.local, io.tiles, frames);
-  hipLaunchKernelGGL(discrete_scan_sums_kernel, dim3(1), dim3(1024), 0, stream, io.tiles, ntiles, io.carry, io.off + m);
+  launch_list_scan(io, m, stream);
   hipLaunchKernelGGL(flag_positions_kernel, dim3(grid), dim3(256), 0, stream, io.er, io.off, io.count, io.local, io.tiles,
                      map, n, g, frames);
   hipError_t e = hipGetLastError();
@@ -1282,120 +1283,22 @@ size_t burst_chunk(size_t frames, uint32_t I) {
   return frames < cap ? frames : cap;
 }
 
-}  // namespace
-
-// Monte-Carlo over the burst channel: the route of mc_run_discrete (lock, workspace, fence, one counting pass per chunk)
-// with chunks of whole blocks.  The channel kernel writes the received symbols frame-major, so the plain decoders and
-// count_kernel take them as they take the discrete channel's; received bytes (or the +-1 floats of a min-sum handle)
-// in w.llr.
-int mc_run_burst(cc_code *code, const cc_burst_channel &ch, uint64_t seed, uint64_t first_frame, size_t frames,
-                 int random_codewords, uint64_t *d_counters, hipStream_t stream) {
+// Monte-Carlo over the burst channel: the route of mc_run_discrete with chunks of whole blocks.  The channel kernel
+// writes the received symbols frame-major, so the plain decoders and count_kernel take them as they take the discrete
+// channel's; received bytes (or the +-1 / 0 floats of a min-sum handle) in w.llr.  det != nullptr, the burst detector
+// (DESIGN 4.5c): the flagged symbols go to a hard decoder as erasures, the list behind the received bytes as on the
+// discrete route (workspace_list), built from the frame-major flag map in w.hard, which the decoder overwrites once the
+// list kernels have read it (one stream).  A min-sum handle gets +0.0f at a flag and needs no list.  det == nullptr: the
+// errors-only kernel, NULL erasures for the decoder.
+int run_burst(cc_code *code, const cc_burst_channel &ch, const DetectorThresholds *det, uint64_t seed,
+              uint64_t first_frame, size_t frames, int random_codewords, uint64_t *d_counters, hipStream_t stream) {
   if (frames == 0) return CC_OK;
-  const size_t chunk = burst_chunk(frames, ch.interleave);
-  if (!code->mc) code->mc = new McWorkspace();
-  std::lock_guard<std::mutex> guard(code->mc->lock);
-  int rc = ensure_workspace(code, chunk);
-  if (rc != CC_OK) return rc;
-  McWorkspace &w = *code->mc;
-  rc = w.fence_in(stream);
-  if (rc != CC_OK) return rc;
-  const size_t n = code->tab.n;
-  unsigned long long *counters = reinterpret_cast<unsigned long long *>(d_counters);
-  for (size_t done = 0; done < frames; done += chunk) {
-    const size_t m = frames - done < chunk ? frames - done : chunk;
-    uint8_t *sent = random_codewords ? w.sent : nullptr;
-    if (random_codewords) {
-      rc = launch_discrete_sent(code, seed, first_frame + done, m, w.sent, w.msg, stream);
-      if (rc != CC_OK) return rc;
-    }
-    BurstIO io;
-    io.frame_major = true;
-    if (code->soft) io.soft = w.llr;
-    else io.recv = reinterpret_cast<uint8_t *>(w.llr);
-    rc = launch_burst(code, ch, seed, first_frame + done, m, sent, io, counters, stream);
+  const size_t chunk = burst_chunk(frames, ch.interleave), n = code->tab.n;
+  return mc_chunked(code, frames, chunk, det ? workspace_frames_with_list(chunk) : chunk, stream,
+                    [&](McWorkspace &w, size_t done, size_t m) -> int {
+    const uint8_t *sent;
+    int rc = transmitted_words(code, seed, first_frame + done, m, random_codewords, w.sent, w.msg, nullptr, stream, &sent);
     if (rc != CC_OK) return rc;
-    if (code->soft)
-      rc = launch_minsum(code, w.llr, nullptr, nullptr, w.hard, nullptr, w.iters, w.status, m, stream);
-    else
-      rc = launch_algebraic(code, false, io.recv, nullptr, nullptr, w.hard, w.nerr, w.status, m, stream);
-    if (rc != CC_OK) return rc;
-    const unsigned long long blocks = (m + 15) / 16;
-    const unsigned long long max_grid = static_cast<unsigned long long>(code->num_cus) * 8;
-    hipLaunchKernelGGL(count_kernel, dim3(static_cast<int>(blocks < max_grid ? blocks : max_grid)), dim3(256), 0, stream,
-                       w.hard, sent, code->soft ? w.iters : nullptr, w.status, static_cast<int>(n),
-                       code->desc.iterations, static_cast<unsigned long long>(m), counters);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "count kernel launch");
-  }
-  return w.fence_out(stream);
-}
-
-// cc_burst_channel_dev: channel only, chunked in whole blocks; the transmitted words are made frame-major in the
-// workspace and leave the channel kernel in transmission order
-int mc_burst(cc_code *code, const cc_burst_channel &ch, uint64_t seed, uint64_t first_frame, size_t frames,
-             int random_codewords, uint8_t *d_recv, uint8_t *d_sent, uint8_t *d_state, hipStream_t stream) {
-  if (frames == 0) return CC_OK;
-  const size_t chunk = burst_chunk(frames, ch.interleave);
-  if (!code->mc) code->mc = new McWorkspace();
-  std::lock_guard<std::mutex> guard(code->mc->lock);
-  int rc = CC_OK;
-  if (random_codewords) {
-    rc = ensure_workspace(code, chunk);
-    if (rc != CC_OK) return rc;
-  }
-  McWorkspace &w = *code->mc;
-  rc = w.fence_in(stream);
-  if (rc != CC_OK) return rc;
-  const size_t n = code->tab.n;
-  for (size_t done = 0; done < frames; done += chunk) {
-    const size_t m = frames - done < chunk ? frames - done : chunk;
-    BurstIO io;
-    io.recv = d_recv + done * n;
-    io.state = d_state ? d_state + done * n : nullptr;
-    const uint8_t *sent = nullptr;
-    if (random_codewords) {
-      rc = launch_discrete_sent(code, seed, first_frame + done, m, w.sent, w.msg, stream);
-      if (rc != CC_OK) return rc;
-      sent = w.sent;
-      io.sent_out = d_sent ? d_sent + done * n : nullptr;
-    } else if (d_sent) {
-      CC_HIP_TRY(hipMemsetAsync(d_sent + done * n, 0, m * n, stream));
-    }
-    rc = launch_burst(code, ch, seed, first_frame + done, m, sent, io, nullptr, stream);
-    if (rc != CC_OK) return rc;
-  }
-  return w.fence_out(stream);
-}
-
-// Monte-Carlo with the burst detector: mc_run_burst with the flagged symbols handed to the decoder as
-// erasures, decoded as mc_run_discrete decodes.  Received bytes and, 16-byte aligned behind them, the positions (at most
-// 2 n bytes per frame) in w.llr as on the discrete route; the frame-major flag map in w.hard, which the decoder
-// overwrites once the list kernels have read it (one stream); counts and tile prefixes in w.nerr / w.status before the
-// decoder writes them, offsets and tile sums in w.list.  A min-sum handle gets +0.0f at a flag and needs no list.
-int mc_run_burst_erasure(cc_code *code, const cc_burst_channel &ch, const cc_burst_detector &det, uint64_t seed,
-                         uint64_t first_frame, size_t frames, int random_codewords, uint64_t *d_counters,
-                         hipStream_t stream) {
-  const DetectorThresholds dt = detector_thresholds(det);
-  if ((dt.DB | dt.DG) == 0)  // no symbol can be flagged: the errors-only route, NULL erasures for the decoder
-    return mc_run_burst(code, ch, seed, first_frame, frames, random_codewords, d_counters, stream);
-  if (frames == 0) return CC_OK;
-  const size_t chunk = burst_chunk(frames, ch.interleave);
-  if (!code->mc) code->mc = new McWorkspace();
-  std::lock_guard<std::mutex> guard(code->mc->lock);
-  int rc = ensure_workspace(code, chunk < 16 ? 16 : chunk);  // >= 16 frames: bytes + aligned positions fit in 4 n
-  if (rc != CC_OK) return rc;
-  McWorkspace &w = *code->mc;
-  rc = w.fence_in(stream);
-  if (rc != CC_OK) return rc;
-  const size_t n = code->tab.n;
-  unsigned long long *counters = reinterpret_cast<unsigned long long *>(d_counters);
-  for (size_t done = 0; done < frames; done += chunk) {
-    const size_t m = frames - done < chunk ? frames - done : chunk;
-    uint8_t *sent = random_codewords ? w.sent : nullptr;
-    if (random_codewords) {
-      rc = launch_discrete_sent(code, seed, first_frame + done, m, w.sent, w.msg, stream);
-      if (rc != CC_OK) return rc;
-    }
     BurstIO io;
     DiscreteIO list;
     io.frame_major = true;
@@ -1403,93 +1306,87 @@ int mc_run_burst_erasure(cc_code *code, const cc_burst_channel &ch, const cc_bur
       io.soft = w.llr;
     } else {
       io.recv = reinterpret_cast<uint8_t *>(w.llr);
-      io.flag_fm = w.hard;
-      list.er = reinterpret_cast<uint16_t *>(io.recv + ((m * n + 15) & ~size_t(15)));
-      list.off = w.list;
-      list.tiles = w.list + m + 1;
-      list.count = reinterpret_cast<uint32_t *>(w.nerr);
-      list.local = reinterpret_cast<uint32_t *>(w.status);
+      if (det) {
+        io.flag_fm = w.hard;
+        list = workspace_list(w, m, n);
+      }
     }
-    rc = launch_burst(code, ch, seed, first_frame + done, m, sent, io, counters, stream, &dt);
+    rc = launch_burst(code, ch, seed, first_frame + done, m, sent, io, reinterpret_cast<unsigned long long *>(d_counters),
+                      stream, det);
     if (rc != CC_OK) return rc;
-    if (code->soft) {
-      rc = launch_minsum(code, w.llr, nullptr, nullptr, w.hard, nullptr, w.iters, w.status, m, stream);
-    } else {
+    if (list.er) {
       rc = launch_flag_list(code, io.flag_fm, m, list, stream);
       if (rc != CC_OK) return rc;
-      if (code->desc.algorithm == CC_ALG_PGZ)  // the BCH two-trial rule, as cc_correct_hard_batch_dev
-        rc = launch_pgz_erasures(code, io.recv, list.er, list.off, w.hard, w.nerr, w.status, m, stream);
-      else
-        rc = launch_algebraic(code, false, io.recv, list.er, list.off, w.hard, w.nerr, w.status, m, stream);
     }
+    rc = launch_decoder(code, w, list.er, list.off, m, stream);
     if (rc != CC_OK) return rc;
-    const unsigned long long blocks = (m + 15) / 16;
-    const unsigned long long max_grid = static_cast<unsigned long long>(code->num_cus) * 8;
-    hipLaunchKernelGGL(count_kernel, dim3(static_cast<int>(blocks < max_grid ? blocks : max_grid)), dim3(256), 0, stream,
-                       w.hard, sent, code->soft ? w.iters : nullptr, w.status, static_cast<int>(n),
-                       code->desc.iterations, static_cast<unsigned long long>(m), counters);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "count kernel launch");
-  }
-  return w.fence_out(stream);
+    return launch_count(code, w, sent, m, d_counters, stream);
+  });
 }
 
-// cc_burst_erasure_channel_dev: mc_burst with the flags (transmission order, d_flag may be nullptr) and, where the CSR
-// buffers are given, one frame-major CSR over all chunks of the call (each chunk's scan starts from the entries of the
-// chunks before it, read on the device, as in mc_discrete); the frame-major flag map of a chunk in w.hard.
+// The burst channel alone, chunked in whole blocks; the transmitted words are made frame-major in the workspace and leave
+// the channel kernel in transmission order.  det != nullptr: the flags as well (transmission order, d_flag may be
+// nullptr) and, where the CSR buffers are given, one frame-major CSR over all chunks of the call (caller_list), from the
+// frame-major flag map of a chunk in w.hard.  det == nullptr: d_flag and the CSR buffers are nullptr.
+int burst_channel(cc_code *code, const cc_burst_channel &ch, const DetectorThresholds *det, uint64_t seed,
+                  uint64_t first_frame, size_t frames, int random_codewords, uint8_t *d_recv, uint8_t *d_sent,
+                  uint8_t *d_state, uint8_t *d_flag, uint16_t *d_erasures, uint32_t *d_erasure_offsets,
+                  hipStream_t stream) {
+  if (frames == 0) return CC_OK;
+  const size_t chunk = burst_chunk(frames, ch.interleave), n = code->tab.n;
+  return mc_chunked(code, frames, chunk, random_codewords || d_erasures ? chunk : 0, stream,
+                    [&](McWorkspace &w, size_t done, size_t m) -> int {
+    uint8_t *out = d_sent ? d_sent + done * n : nullptr;
+    const uint8_t *sent;
+    int rc = transmitted_words(code, seed, first_frame + done, m, random_codewords, w.sent, w.msg, out, stream, &sent);
+    if (rc != CC_OK) return rc;
+    BurstIO io;
+    io.recv = d_recv + done * n;
+    io.sent_out = sent ? out : nullptr;
+    io.state = d_state ? d_state + done * n : nullptr;
+    io.flag_t = d_flag ? d_flag + done * n : nullptr;
+    io.flag_fm = d_erasures ? w.hard : nullptr;
+    rc = launch_burst(code, ch, seed, first_frame + done, m, sent, io, nullptr, stream, det);
+    if (rc != CC_OK || !d_erasures) return rc;
+    return launch_flag_list(code, w.hard, m, caller_list(w, d_erasures, d_erasure_offsets, done), stream);
+  });
+}
+
+}  // namespace
+
+int mc_run_burst(cc_code *code, const cc_burst_channel &ch, uint64_t seed, uint64_t first_frame, size_t frames,
+                 int random_codewords, uint64_t *d_counters, hipStream_t stream) {
+  return run_burst(code, ch, nullptr, seed, first_frame, frames, random_codewords, d_counters, stream);
+}
+
+// cc_burst_channel_dev
+int mc_burst(cc_code *code, const cc_burst_channel &ch, uint64_t seed, uint64_t first_frame, size_t frames,
+             int random_codewords, uint8_t *d_recv, uint8_t *d_sent, uint8_t *d_state, hipStream_t stream) {
+  return burst_channel(code, ch, nullptr, seed, first_frame, frames, random_codewords, d_recv, d_sent, d_state, nullptr,
+                       nullptr, nullptr, stream);
+}
+
+int mc_run_burst_erasure(cc_code *code, const cc_burst_channel &ch, const cc_burst_detector &det, uint64_t seed,
+                         uint64_t first_frame, size_t frames, int random_codewords, uint64_t *d_counters,
+                         hipStream_t stream) {
+  const DetectorThresholds dt = detector_thresholds(det);  // both 0: no symbol can be flagged, the errors-only route
+  return run_burst(code, ch, (dt.DB | dt.DG) ? &dt : nullptr, seed, first_frame, frames, random_codewords, d_counters,
+                   stream);
+}
+
+// cc_burst_erasure_channel_dev
 int mc_burst_erasure(cc_code *code, const cc_burst_channel &ch, const cc_burst_detector &det, uint64_t seed,
                      uint64_t first_frame, size_t frames, int random_codewords, uint8_t *d_recv, uint8_t *d_sent,
                      uint8_t *d_state, uint8_t *d_flag, uint16_t *d_erasures, uint32_t *d_erasure_offsets,
                      hipStream_t stream) {
   const DetectorThresholds dt = detector_thresholds(det);
-  const size_t n = code->tab.n;
-  if ((dt.DB | dt.DG) == 0 || frames == 0) {  // nothing flagged: the errors-only channel, an empty list
-    if (d_erasure_offsets) CC_HIP_TRY(hipMemsetAsync(d_erasure_offsets, 0, (frames + 1) * sizeof(uint32_t), stream));
-    if (d_flag && frames) CC_HIP_TRY(hipMemsetAsync(d_flag, 0, frames * n, stream));
-    return mc_burst(code, ch, seed, first_frame, frames, random_codewords, d_recv, d_sent, d_state, stream);
-  }
-  const size_t chunk = burst_chunk(frames, ch.interleave);
-  if (!code->mc) code->mc = new McWorkspace();
-  std::lock_guard<std::mutex> guard(code->mc->lock);
-  int rc = CC_OK;
-  if (random_codewords || d_erasures) {
-    rc = ensure_workspace(code, chunk);
-    if (rc != CC_OK) return rc;
-  }
-  McWorkspace &w = *code->mc;
-  rc = w.fence_in(stream);
-  if (rc != CC_OK) return rc;
-  for (size_t done = 0; done < frames; done += chunk) {
-    const size_t m = frames - done < chunk ? frames - done : chunk;
-    BurstIO io;
-    io.recv = d_recv + done * n;
-    io.state = d_state ? d_state + done * n : nullptr;
-    io.flag_t = d_flag ? d_flag + done * n : nullptr;
-    io.flag_fm = d_erasures ? w.hard : nullptr;
-    const uint8_t *sent = nullptr;
-    if (random_codewords) {
-      rc = launch_discrete_sent(code, seed, first_frame + done, m, w.sent, w.msg, stream);
-      if (rc != CC_OK) return rc;
-      sent = w.sent;
-      io.sent_out = d_sent ? d_sent + done * n : nullptr;
-    } else if (d_sent) {
-      CC_HIP_TRY(hipMemsetAsync(d_sent + done * n, 0, m * n, stream));
-    }
-    rc = launch_burst(code, ch, seed, first_frame + done, m, sent, io, nullptr, stream, &dt);
-    if (rc != CC_OK) return rc;
-    if (d_erasures) {
-      DiscreteIO list;
-      list.er = d_erasures;
-      list.off = d_erasure_offsets + done;
-      list.tiles = w.list;
-      list.count = reinterpret_cast<uint32_t *>(w.nerr);
-      list.local = reinterpret_cast<uint32_t *>(w.status);
-      list.carry = done ? d_erasure_offsets + done : nullptr;
-      rc = launch_flag_list(code, w.hard, m, list, stream);
-      if (rc != CC_OK) return rc;
-    }
-  }
-  return w.fence_out(stream);
+  if ((dt.DB | dt.DG) != 0 && frames != 0)
+    return burst_channel(code, ch, &dt, seed, first_frame, frames, random_codewords, d_recv, d_sent, d_state, d_flag,
+                         d_erasures, d_erasure_offsets, stream);
+  // nothing flagged: the errors-only channel, an empty list
+  if (d_erasure_offsets) CC_HIP_TRY(hipMemsetAsync(d_erasure_offsets, 0, (frames + 1) * sizeof(uint32_t), stream));
+  if (d_flag && frames) CC_HIP_TRY(hipMemsetAsync(d_flag, 0, frames * code->tab.n, stream));
+  return mc_burst(code, ch, seed, first_frame, frames, random_codewords, d_recv, d_sent, d_state, stream);
 }
 
 }  // namespace ccamd
