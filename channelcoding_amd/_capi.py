@@ -103,6 +103,8 @@ _SIGNATURES = {
                                          _VP]),
     "cc_discrete_channel_dev": (C.c_int, [_VP, C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int,
                                           _VP, _VP, _VP, _VP, _VP]),
+    "cc_mc_run_bsc_packed_dev": (C.c_int, [_VP, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP, _VP]),
+    "cc_bsc_packed_channel_dev": (C.c_int, [_VP, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP, _VP, _VP]),
     "cc_mc_run_burst_dev": (C.c_int, [_VP, C.POINTER(BurstChannel), C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP,
                                       _VP]),
     "cc_burst_channel_dev": (C.c_int, [_VP, C.POINTER(BurstChannel), C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP,

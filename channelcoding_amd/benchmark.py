@@ -4,7 +4,7 @@
                                           [--k 5|6|7|all]... [--dmin 3|5|7|9|11|all]... [--seed N | --seed-time]
                                           [--threads N] [--log-dir DIR] [--p VALUE]... [--max-samples N]
                                           [--interleave I] [--p-gb VALUE] [--p-bg VALUE] [--p-good VALUE]
-                                          [--p-detect VALUE] [--p-false-alarm VALUE]
+                                          [--p-detect VALUE] [--p-false-alarm VALUE] [--packed]
 
 Same options, same decoder registry (benchmark.c++:23-166: primitive_bch<k, dmin<d>, A> for k in 5..7,
 d in 3,5,7,9 and the nine algorithm tags, min-sum family with 50 iterations, NMS 8/10, OMS 1/100) and the same
@@ -18,7 +18,8 @@ the ranks' GPUs (montecarlo.awgn_simulation).  --threads is accepted and ignored
 
 --simulation bsc / bec is new: the binary symmetric and the binary erasure channel the reference leaves as a TODO
 (montecarlo.discrete_simulation), over the points given with --p (default 10^(-k/4), k = 4 .. 16), each decoder
-writing "<to_string()>.<bsc|bec>.log".
+writing "<to_string()>.<bsc|bec>.log".  --simulation bsc --packed runs the BSC on packed words
+(montecarlo.discrete_simulation(packed=True)): the same channel, counters and log, an eighth of the bytes.
 
 --simulation burst is new as well: the two-state Gilbert-Elliott channel run along symbol-interleaved blocks of depth
 --interleave (montecarlo.burst_simulation), with the transition probabilities --p-gb (good -> bad) and --p-bg (bad ->
@@ -97,6 +98,7 @@ def usage_text():
               "--p-detect <value>           burst: P(symbol flagged | bad state) of a burst detector whose flags are erasures",
               "                             to the decoder. The default is 0.",
               "--p-false-alarm <value>      burst: P(symbol flagged | good state). The default is 0.",
+              "--packed                     bsc: channel, decoder and counts on packed words (hard-decision algorithms).",
               "--max-samples <num>          awgn / bsc / bec / burst: cap on the frames of one point.",
               "",
               "algorithm, k, and dmin can be specified multiple times.",
@@ -152,6 +154,7 @@ def main(argv=None):
     ap.add_argument("--p-good", type=float, default=0.0, help="burst: symbol error probability of the good state")
     ap.add_argument("--p-detect", type=float, default=0.0, help="burst: P(flag | bad state) of the burst detector")
     ap.add_argument("--p-false-alarm", type=float, default=0.0, help="burst: P(flag | good state)")
+    ap.add_argument("--packed", action="store_true", help="bsc: the route on packed words")
     ap.add_argument("--help", "-h", action="store_true")
     args, unknown = ap.parse_known_args(argv)
     if args.help or unknown:
@@ -162,6 +165,10 @@ def main(argv=None):
     sim = args.simulation.lower()
     if sim not in ("awgn", "bitflip", "bsc", "bec", "burst"):
         print("Don't know the simulation type '%s'" % sim, file=sys.stderr)
+        print(usage_text())
+        return 1
+    if args.packed and sim != "bsc":
+        print("--packed goes with --simulation bsc", file=sys.stderr)
         print(usage_text())
         return 1
     chosen = select(args.algorithm, args.k, args.dmin)
@@ -191,8 +198,9 @@ def main(argv=None):
             res = awgn_simulation(code, seed=seed, log_dir=args.log_dir, max_samples=args.max_samples)()
             frames = sum(r["frames"] for r in res)
         elif sim in ("bsc", "bec"):
+            packed = dict(packed=True) if args.packed else {}
             res = discrete_simulation(code, sim, points=args.p, seed=seed, log_dir=args.log_dir,
-                                      max_samples=args.max_samples)()
+                                      max_samples=args.max_samples, **packed)()
             frames = sum(r["frames"] for r in res)
         elif sim == "burst":
             detector = {}

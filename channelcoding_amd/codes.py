@@ -302,6 +302,23 @@ def burst_erasure_channel(code, interleave, p_gb, p_bg, p_error_good, p_error_ba
     return dict(recv=recv, sent=sent, state=state, flag=flag, erasures=er[:int(off[-1])], erasure_offsets=off)
 
 
+def bsc_packed_channel(code, p, seed=0, first_frame=0, frames=0, random_codewords=False):
+    """Frames [first_frame, first_frame + frames) of the binary symmetric channel on packed words
+    (cc_bsc_packed_channel_dev) on the current device, for any binary BCH code, q = 3 .. 15: bit for bit the BSC of
+    discrete_channel(p, 0), in the container of pack_bits.  Returns recv, a torch uint8 tensor of shape
+    (frames, code.packed_bytes) with the pad bits 0 -- and with random_codewords the pair (recv, sent), sent the packed
+    words transmitted (without, the all-zero word is sent)."""
+    import torch
+    frames = int(frames)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    recv = torch.empty((frames, code.packed_bytes), dtype=torch.uint8, device=dev)
+    sent = torch.empty_like(recv) if random_codewords else None
+    rc = capi.lib().cc_bsc_packed_channel_dev(code._h, float(p), int(seed), int(first_frame), frames,
+                                              int(bool(random_codewords)), _ptr(recv), _ptr(sent), _stream_handle(recv))
+    capi.check(rc, "cc_bsc_packed_channel_dev")
+    return (recv, sent) if random_codewords else recv
+
+
 class cyclic:
     """Common part of primitive_bch and rs (cyclic::cyclic<...>, cyclic.h:67-386)."""
     family = None

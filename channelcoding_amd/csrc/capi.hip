@@ -1021,6 +1021,21 @@ static int packed_map_dev(const cc_code *code, int kind, const uint8_t *d_src, u
   return packed_generic_dev(code, kind, d_src, nullptr, nullptr, d_dst, nullptr, nullptr, B, stream);
 }
 
+// what mc.hip's packed Monte-Carlo route calls (cc_internal.hpp); not part of the ABI
+}  // extern "C"
+#pragma GCC visibility pop
+namespace ccamd {
+int packed_correct_route(const cc_code *code, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nerr, int32_t *d_status,
+                         size_t B, hipStream_t stream) {
+  return packed_correct_dev(code, d_in, nullptr, nullptr, d_out, d_nerr, d_status, B, stream);
+}
+int packed_encode_route(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, hipStream_t stream) {
+  return packed_map_dev(code, 0, d_msg, d_cw, B, stream);
+}
+}  // namespace ccamd
+#pragma GCC visibility push(default)
+extern "C" {
+
 int cc_packed_map_route(const cc_code *code, int which) {
   if (!code || which < 0 || which > 1) return -CC_ERR_INVALID_ARGUMENT;
   if (int rc = packed_ready(code)) return -rc;
@@ -1370,6 +1385,40 @@ int cc_discrete_channel_dev(const cc_code *code, double p_error, double p_erasur
   DeviceGuard guard(code->device);
   return mc_discrete(const_cast<cc_code *>(code), p_error, p_erasure, seed, first_frame, frames, random_codewords, d_recv,
                      d_erasures, d_erasure_offsets, d_sent, static_cast<hipStream_t>(stream));
+}
+
+// The BSC on packed words serves the handles of the packed calls; every refusal comes before a device is asked for.
+// decode: the call runs the decoder, whose own refusals (the 16-bit route's bounds on the Euklid tag) are the call's.
+static int bsc_packed_supported(const cc_code *code, double p_error, int random_codewords, bool decode) {
+  if (int rc = packed_supported(code)) return rc;
+  if (!std::isfinite(p_error) || p_error < 0.0 || p_error > 1.0) {
+    set_last_error("p_error must be finite and in [0, 1]");
+    return CC_ERR_INVALID_ARGUMENT;
+  }
+  if (random_codewords && code->desc.coding != CC_CODING_DIVISION && code->desc.coding != CC_CODING_MULTIPLICATION)
+    return CC_ERR_INVALID_ARGUMENT;
+  if (decode && code->wide)
+    if (int rc = wide_hard_supported(code, false)) return rc;
+  if (code->device == CC_DEVICE_NONE) return CC_ERR_NO_DEVICE;
+  return CC_OK;
+}
+
+int cc_mc_run_bsc_packed_dev(const cc_code *code, double p_error, uint64_t seed, uint64_t first_frame, size_t frames,
+                             int random_codewords, uint64_t *d_counters, void *stream) {
+  if (!code || !d_counters) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = bsc_packed_supported(code, p_error, random_codewords, true)) return rc;
+  DeviceGuard guard(code->device);
+  return mc_run_bsc_packed(const_cast<cc_code *>(code), p_error, seed, first_frame, frames, random_codewords, d_counters,
+                           static_cast<hipStream_t>(stream));
+}
+
+int cc_bsc_packed_channel_dev(const cc_code *code, double p_error, uint64_t seed, uint64_t first_frame, size_t frames,
+                              int random_codewords, uint8_t *d_recv, uint8_t *d_sent, void *stream) {
+  if (!code || !d_recv) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = bsc_packed_supported(code, p_error, random_codewords, false)) return rc;
+  DeviceGuard guard(code->device);
+  return mc_bsc_packed(const_cast<cc_code *>(code), p_error, seed, first_frame, frames, random_codewords, d_recv, d_sent,
+                       static_cast<hipStream_t>(stream));
 }
 
 // the burst channel serves the handles of the discrete route; every argument is checked before a device is asked for

@@ -283,6 +283,24 @@ int mc_burst_erasure(cc_code *code, const cc_burst_channel &ch, const cc_burst_d
                      uint64_t first_frame, size_t frames, int random_codewords, uint8_t *d_recv, uint8_t *d_sent,
                      uint8_t *d_state, uint8_t *d_flag, uint16_t *d_erasures, uint32_t *d_erasure_offsets,
                      hipStream_t stream);
+// The BSC on packed words: the only container of these two is the packed word, P = ceil(n / 8) bytes per
+// frame.  Binary BCH handles with a hard-decision tag, q = 3 .. 15 (checked by the caller, with p in [0, 1]).
+int mc_run_bsc_packed(cc_code *code, double p_error, uint64_t seed, uint64_t first_frame, size_t frames,
+                      int random_codewords, uint64_t *d_counters, hipStream_t stream);
+int mc_bsc_packed(cc_code *code, double p_error, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
+                  uint8_t *d_recv, uint8_t *d_sent, hipStream_t stream);
+// mc_packed.hip: the kernels of the two above.  threshold = llround(p 2^32); sent == nullptr: the all-zero word
+int launch_bsc_packed(const cc_code *code, unsigned long long threshold, uint64_t seed, uint64_t first_frame, size_t frames,
+                      const uint8_t *d_sent, uint8_t *d_recv, unsigned long long *d_counters, hipStream_t stream);
+int launch_random_packed_messages(const cc_code *code, uint64_t seed, uint64_t first_frame, size_t frames, uint8_t *d_msg,
+                                  hipStream_t stream);
+int launch_count_packed(const cc_code *code, const uint8_t *d_decoded, const uint8_t *d_sent, const int32_t *d_status,
+                        size_t frames, unsigned long long *d_counters, hipStream_t stream);
+// capi.hip: the routers behind cc_correct_hard_packed_batch_dev (without an erasure list; d_out may be d_in) and
+// cc_encode_packed_batch_dev
+int packed_correct_route(const cc_code *code, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nerr, int32_t *d_status,
+                         size_t B, hipStream_t stream);
+int packed_encode_route(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, hipStream_t stream);
 int minsum_kernel_info(const cc_code *code, std::string &name, uint32_t &frames_per_wg, uint32_t &threads,
                        uint32_t &lds);
 

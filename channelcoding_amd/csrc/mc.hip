@@ -12,37 +12,15 @@
 //   counters  word / bit / failure / undetected / channel-bit errors and the iteration histogram,
 //             accumulated in LDS per workgroup and flushed with one 64-bit atomic per counter.
 #include <cmath>
+#include <cstdlib>
 #include <mutex>
 
 #include "cc_internal.hpp"
+#include "philox.hpp"
 #include "wave_ops.hpp"
 
 namespace ccamd {
 namespace {
-
-struct Philox {
-  uint32_t c[4];
-};
-
-__device__ __forceinline__ Philox philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                                uint32_t k1) {
-  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    // one v_mad_u64_u32 per product instead of a mul_lo / mul_hi pair (both quarter rate)
-    const uint64_t p0 = static_cast<uint64_t>(M0) * c0, p1 = static_cast<uint64_t>(M1) * c2;
-    const uint32_t hi0 = static_cast<uint32_t>(p0 >> 32), lo0 = static_cast<uint32_t>(p0);
-    const uint32_t hi1 = static_cast<uint32_t>(p1 >> 32), lo1 = static_cast<uint32_t>(p1);
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-    c0 = n0;
-    c1 = n1;
-    c2 = n2;
-    c3 = n3;
-    k0 += W0;
-    k1 += W1;
-  }
-  return Philox{{c0, c1, c2, c3}};
-}
 
 // Box-Muller on the hardware transcendentals: v_log_f32 (log2), v_sqrt_f32, v_sin_f32 / v_cos_f32 take their
 // argument in turns, so no range reduction is needed for u2 in [0, 1).
@@ -343,6 +321,13 @@ struct McWorkspace {
   // [64 + POOL_WORDS + chunk]: 64 control words (MinSumParams::ctl in the first four), the decoder's frame pool, then the
   // frame list
   uint32_t *list = nullptr;
+  // the packed route (mc_run_bsc_packed) has buffers of its own, none of them a symbol per bit: received / decoded words
+  // and nerr / status for `chunk` frames, the words sent and their messages once a call with random codewords asked
+  struct Packed {
+    size_t chunk = 0;
+    uint8_t *recv = nullptr, *sent = nullptr, *msg = nullptr;
+    int32_t *nerr = nullptr, *status = nullptr;
+  } pk;
   // recorded behind the last work enqueued on the buffers: the lock only covers the ENQUEUE, so a later call on
   // another stream first waits (on the device) for this event before it overwrites them
   hipEvent_t done = nullptr;
@@ -359,7 +344,9 @@ struct McWorkspace {
     if (done) (void)hipEventDestroy(done);
     for (void *p : {static_cast<void *>(llr), static_cast<void *>(sent), static_cast<void *>(msg),
                     static_cast<void *>(hard), static_cast<void *>(iters), static_cast<void *>(status),
-                    static_cast<void *>(nerr), static_cast<void *>(list)})
+                    static_cast<void *>(nerr), static_cast<void *>(list), static_cast<void *>(pk.recv),
+                    static_cast<void *>(pk.sent), static_cast<void *>(pk.msg), static_cast<void *>(pk.nerr),
+                    static_cast<void *>(pk.status)})
       if (p) (void)hipFree(p);
   }
 };
@@ -400,12 +387,12 @@ static int ensure_workspace(const cc_code *code, McWorkspace &w, size_t chunk) {
 // The skeleton of every Monte-Carlo and channel call: under the workspace's lock, buffers for workspace_frames frames
 // (0: the call uses none of them), the wait for the call before, body(w, done, m) for the frames [done, done + m) of
 // each chunk, and the event the next call waits for.  A failing body ends the call where it stands.
-template <class Body>
-static int mc_chunked(const cc_code *code, size_t frames, size_t chunk, size_t workspace_frames, hipStream_t stream,
-                      Body body) {
+// ensure(w) brings the buffers the bodies use to their size.
+template <class Ensure, class Body>
+static int mc_chunked_with(const cc_code *code, size_t frames, size_t chunk, hipStream_t stream, Ensure ensure, Body body) {
   McWorkspace &w = mc_workspace(code);
   std::lock_guard<std::mutex> guard(w.lock);
-  int rc = workspace_frames ? ensure_workspace(code, w, workspace_frames) : CC_OK;
+  int rc = ensure(w);
   if (rc != CC_OK) return rc;
   rc = w.fence_in(stream);
   if (rc != CC_OK) return rc;
@@ -414,6 +401,13 @@ static int mc_chunked(const cc_code *code, size_t frames, size_t chunk, size_t w
     if (rc != CC_OK) return rc;
   }
   return w.fence_out(stream);
+}
+template <class Body>
+static int mc_chunked(const cc_code *code, size_t frames, size_t chunk, size_t workspace_frames, hipStream_t stream,
+                      Body body) {
+  return mc_chunked_with(
+      code, frames, chunk, stream,
+      [&](McWorkspace &w) { return workspace_frames ? ensure_workspace(code, w, workspace_frames) : CC_OK; }, body);
 }
 
 constexpr size_t MC_CHUNK = size_t(1) << 20;  // ~1.6 GB of workspace for n = 255: long launches, short tails
@@ -1387,6 +1381,120 @@ int mc_burst_erasure(cc_code *code, const cc_burst_channel &ch, const cc_burst_d
   if (d_erasure_offsets) CC_HIP_TRY(hipMemsetAsync(d_erasure_offsets, 0, (frames + 1) * sizeof(uint32_t), stream));
   if (d_flag && frames) CC_HIP_TRY(hipMemsetAsync(d_flag, 0, frames * code->tab.n, stream));
   return mc_burst(code, ch, seed, first_frame, frames, random_codewords, d_recv, d_sent, d_state, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The BSC on packed words (kernels in mc_packed.hip): the route of mc_run_discrete with the packed word as
+// its only container.  Per frame of a chunk the workspace holds P(n) bytes of received / decoded words, 8 bytes of nerr /
+// status and, with random codewords, P(n) bytes of words sent and P(l) of messages.
+namespace {
+
+constexpr size_t PACKED_MC_CHUNK = size_t(1) << 20;          // frames, as the other routes
+constexpr size_t PACKED_GENERIC_BYTES = size_t(32) << 20;    // symbols of a chunk on the generic route (host_stage.hpp)
+
+// Frames per chunk: 32 MiB of received words (CC_AMD_PACKED_MC_CHUNK_MB: tests force several chunks), 2^20 at the most.
+// A chunk whose decoder (decode) or encoder (random) goes the generic way is unpacked into workspace of the handle's
+// pool, a symbol per bit: it is bounded as the host packed calls bound their chunks, by 32 MiB of symbols, 16 frames at
+// least.  Both routes give the same words, so where the bound falls does not show in any result.
+size_t packed_mc_chunk(const cc_code *code, size_t frames, bool decode, bool random) {
+  static const size_t chunk_bytes = [] {
+    const char *e = std::getenv("CC_AMD_PACKED_MC_CHUNK_MB");
+    const long long v = e ? std::atoll(e) : 0;
+    return (v > 0 ? static_cast<size_t>(v) : size_t(32)) << 20;
+  }();
+  const size_t n = code->tab.n, P = (n + 7) / 8;
+  size_t chunk = chunk_bytes / P;
+  if (chunk > PACKED_MC_CHUNK) chunk = PACKED_MC_CHUNK;
+  if (chunk < 1) chunk = 1;
+  if (chunk > frames) chunk = frames;
+  if ((decode && !packed_native_supported(code, chunk)) || (random && !packed_encode_native(code))) {
+    size_t generic = PACKED_GENERIC_BYTES / (n * (code->wide ? 2 : 1));
+    if (generic < 16) generic = 16;
+    if (chunk > generic) chunk = generic;
+  }
+  return chunk;
+}
+
+int ensure_packed_workspace(const cc_code *code, McWorkspace &w, size_t chunk, bool decode, bool words) {
+  McWorkspace::Packed &pk = w.pk;
+  if (pk.chunk >= chunk && (!decode || pk.recv) && (!words || pk.sent)) return CC_OK;
+  decode = decode || pk.recv;
+  words = words || pk.sent;
+  if (chunk < pk.chunk) chunk = pk.chunk;
+  for (void **p : {reinterpret_cast<void **>(&pk.recv), reinterpret_cast<void **>(&pk.sent), reinterpret_cast<void **>(&pk.msg),
+                   reinterpret_cast<void **>(&pk.nerr), reinterpret_cast<void **>(&pk.status)})
+    if (*p) {
+      (void)hipFree(*p);
+      *p = nullptr;
+    }
+  pk.chunk = 0;
+  const size_t P = (code->tab.n + 7) / 8, Pm = (code->tab.l + 7) / 8;
+  if (decode) {
+    CC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pk.recv), chunk * P));
+    CC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pk.nerr), chunk * sizeof(int32_t)));
+    CC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pk.status), chunk * sizeof(int32_t)));
+  }
+  if (words) {
+    CC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pk.sent), chunk * P));
+    CC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pk.msg), chunk * Pm));
+  }
+  pk.chunk = chunk;
+  return CC_OK;
+}
+
+// the packed words sent as frames [first, first + m): random messages (domain 1) through the packed encoder's router
+int launch_packed_sent(const cc_code *code, McWorkspace &w, uint64_t seed, uint64_t first_frame, size_t m, uint8_t *d_sent,
+                       hipStream_t stream) {
+  const int rc = launch_random_packed_messages(code, seed, first_frame, m, w.pk.msg, stream);
+  return rc != CC_OK ? rc : packed_encode_route(code, w.pk.msg, d_sent, m, stream);
+}
+
+unsigned long long bsc_threshold(double p_error) {
+  return static_cast<unsigned long long>(std::llround(p_error * 4294967296.0));
+}
+
+}  // namespace
+
+int mc_run_bsc_packed(cc_code *code, double p_error, uint64_t seed, uint64_t first_frame, size_t frames,
+                      int random_codewords, uint64_t *d_counters, hipStream_t stream) {
+  if (frames == 0) return CC_OK;
+  const bool random = random_codewords != 0;
+  const size_t chunk = packed_mc_chunk(code, frames, true, random);
+  const unsigned long long threshold = bsc_threshold(p_error);
+  unsigned long long *counters = reinterpret_cast<unsigned long long *>(d_counters);
+  return mc_chunked_with(
+      code, frames, chunk, stream, [&](McWorkspace &w) { return ensure_packed_workspace(code, w, chunk, true, random); },
+      [&](McWorkspace &w, size_t done, size_t m) -> int {
+        const uint8_t *sent = random ? w.pk.sent : nullptr;
+        int rc = random ? launch_packed_sent(code, w, seed, first_frame + done, m, w.pk.sent, stream) : CC_OK;
+        if (rc != CC_OK) return rc;
+        rc = launch_bsc_packed(code, threshold, seed, first_frame + done, m, sent, w.pk.recv, counters, stream);
+        if (rc != CC_OK) return rc;
+        rc = packed_correct_route(code, w.pk.recv, w.pk.recv, w.pk.nerr, w.pk.status, m, stream);  // in place
+        if (rc != CC_OK) return rc;
+        return launch_count_packed(code, w.pk.recv, sent, w.pk.status, m, counters, stream);
+      });
+}
+
+// cc_bsc_packed_channel_dev: channel only
+int mc_bsc_packed(cc_code *code, double p_error, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
+                  uint8_t *d_recv, uint8_t *d_sent, hipStream_t stream) {
+  if (frames == 0) return CC_OK;
+  const size_t P = (code->tab.n + 7) / 8;
+  const unsigned long long threshold = bsc_threshold(p_error);
+  if (!random_codewords) {  // one launch, no buffer of the workspace
+    if (d_sent) CC_HIP_TRY(hipMemsetAsync(d_sent, 0, frames * P, stream));
+    return launch_bsc_packed(code, threshold, seed, first_frame, frames, nullptr, d_recv, nullptr, stream);
+  }
+  const size_t chunk = packed_mc_chunk(code, frames, false, true);
+  return mc_chunked_with(
+      code, frames, chunk, stream, [&](McWorkspace &w) { return ensure_packed_workspace(code, w, chunk, false, true); },
+      [&](McWorkspace &w, size_t done, size_t m) -> int {
+        uint8_t *sent = d_sent ? d_sent + done * P : w.pk.sent;
+        const int rc = launch_packed_sent(code, w, seed, first_frame + done, m, sent, stream);
+        if (rc != CC_OK) return rc;
+        return launch_bsc_packed(code, threshold, seed, first_frame + done, m, sent, d_recv + done * P, nullptr, stream);
+      });
 }
 
 }  // namespace ccamd

@@ -14,7 +14,8 @@ CPU) of the 64-word counter vector per point gives every rank the totals -- whic
 count of the next point needs.  Totals are bit-identical for any number of ranks.
 
 discrete_simulation runs the same harness over the BSC, the BEC or both at once (cc_mc_run_discrete_dev; for RS codes
-the q-ary symmetric and the symbol erasure channel), on a ladder of channel probabilities; burst_simulation over the
+the q-ary symmetric and the symbol erasure channel), on a ladder of channel probabilities -- with packed=True the BSC on
+packed words (cc_mc_run_bsc_packed_dev), which serves the binary BCH codes of every q = 3 .. 15; burst_simulation over the
 two-state Gilbert-Elliott channel run along symbol-interleaved blocks (cc_mc_run_burst_dev), sharded in whole blocks;
 with a burst detector (p_detect, p_false_alarm) the flagged symbols go to the decoder as erasures
 (cc_mc_run_burst_erasure_dev).
@@ -314,6 +315,35 @@ class DiscreteBackend:
         return counters  # stays on the device: reduced with RCCL
 
 
+class PackedBscBackend:
+    """Counts one shard of one BSC point on this rank's GPU through cc_mc_run_bsc_packed_dev: the packed word is the only
+    container, so binary BCH codes of every q = 3 .. 15 run, the long ones (q > 8) included."""
+
+    def __init__(self, code, random_codewords=False):
+        import torch
+        self.torch = torch
+        self.code = code
+        self.random_codewords = bool(random_codewords)
+        self.device = torch.device("cuda", torch.cuda.current_device())
+
+    def run(self, point, seed, first_frame, frames):
+        torch = self.torch
+        p_error, _ = channel_probabilities("bsc", point)
+        counters = torch.zeros(capi.MC_NCOUNTERS, dtype=torch.int64, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = capi.lib().cc_mc_run_bsc_packed_dev(self.code._h, p_error, int(seed), int(first_frame), int(frames),
+                                                 int(self.random_codewords), C.c_void_p(counters.data_ptr()), stream)
+        capi.check(rc, "cc_mc_run_bsc_packed_dev")
+        return counters  # stays on the device: reduced with RCCL
+
+
+def hard_decision_p(code, ebno_db):
+    """The crossover probability a hard-decision decoder sees behind BPSK over AWGN at this Eb/N0:
+    p = 1/2 erfc(1 / (sigma sqrt 2)) = Q(1 / sigma) with sigma = code.sigma(ebno_db) (cc_sigma, the sigma of
+    awgn_simulation) -- the point of discrete_simulation(channel="bsc") for a user who thinks in Eb/N0."""
+    return 0.5 * math.erfc(1.0 / (code.sigma(ebno_db) * math.sqrt(2.0)))
+
+
 class discrete_simulation(_ShardedSimulation):
     """Word-error rate over a ladder of discrete-channel points, sharded like awgn_simulation.
 
@@ -324,15 +354,23 @@ class discrete_simulation(_ShardedSimulation):
 
     Random codewords by default, unlike awgn_simulation: an erased position receives 0, which for the all-zero word is
     the symbol sent, so a decoder that reads erased positions as they are (RS BM / Euklid, BCH BM / Euklid, min-sum)
-    would see a codeword in every frame without errors, whatever the number of erasures."""
+    would see a codeword in every frame without errors, whatever the number of erasures.
+
+    packed=True (channel "bsc" only, binary BCH codes with a hard-decision tag): the same ladder through
+    cc_mc_run_bsc_packed_dev (PackedBscBackend), whose only container is the packed word -- the route of the long codes,
+    q = 9 .. 15, and for q <= 8 the same channel and counters at an eighth of the bytes.  Log name and sharding as ever."""
 
     counter_names = DISCRETE_COUNTER_NAMES
 
     def __init__(self, code, channel="bsc", points=None, seed=0, random_codewords=True, backend=None, log_dir=None,
-                 max_samples=None, samples_per_point=None):
+                 max_samples=None, samples_per_point=None, packed=False):
         self.channel = str(channel).lower()
         if self.channel not in CHANNELS:
             raise ValueError("unknown channel %r (one of %s)" % (channel, ", ".join(CHANNELS)))
+        self.packed = bool(packed)
+        if self.packed and self.channel != "bsc":
+            raise ValueError("packed=True runs the BSC only: channel %r has erasures, which packed words cannot carry"
+                             % channel)
         if points is None:
             points = discrete_ladder()
             if self.channel == "bsec":
@@ -342,7 +380,10 @@ class discrete_simulation(_ShardedSimulation):
             channel_probabilities(self.channel, pt)
         self.code = code
         self.seed = int(seed)
-        self.backend = backend if backend is not None else DiscreteBackend(code, self.channel, random_codewords)
+        if backend is None:
+            backend = PackedBscBackend(code, random_codewords) if self.packed else \
+                DiscreteBackend(code, self.channel, random_codewords)
+        self.backend = backend
         self.log_dir = log_dir
         self.max_samples = max_samples
         self.samples_per_point = samples_per_point

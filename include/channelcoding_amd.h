@@ -369,7 +369,8 @@ int cc_mc_run_burst_erasure_dev(const cc_code *code, const cc_burst_channel *ch,
  *      16 bits wide, n = 2^q - 1 <= 32767.  Hard-decision algorithms (PGZ as bounded-distance BM, BM, Euklid), with
  *      erasures; division_tag coding.  The byte entry points above return CC_ERR_UNSUPPORTED on such a handle and
  *      these return it on a q <= 8 handle.  Min-sum serves BCH codes up to q = 11 (n <= 2047) through the byte entry points
- *      (bits and LLRs have no symbol width); the Monte-Carlo calls do not apply. ---- */
+ *      (bits and LLRs have no symbol width); the Monte-Carlo calls do not apply, but for the two on packed words below
+ *      (cc_mc_run_bsc_packed_dev, cc_bsc_packed_channel_dev), which serve every binary BCH code. ---- */
 int cc_encode_batch_u16(const cc_code *code, const uint16_t *msg /* B*l */, uint16_t *cw /* B*n */, size_t B);
 int cc_encode_batch_u16_dev(const cc_code *code, const uint16_t *d_msg, uint16_t *d_cw, size_t B, void *stream);
 int cc_correct_hard_batch_u16(const cc_code *code, const uint16_t *in /* B*n symbols */, const uint16_t *erasures,
@@ -433,6 +434,39 @@ int cc_extract_packed_batch_dev(const cc_code *code, const uint8_t *d_cw, uint8_
 int cc_decode_hard_packed_batch(const cc_code *code, const uint8_t *in, const uint16_t *erasures,
                                 const uint32_t *erasure_offsets, uint8_t *msg, uint8_t *words, int32_t *nerr,
                                 int32_t *status, size_t B);
+
+/* ---- Monte-Carlo over the binary symmetric channel on packed words: channel -> decode -> count with
+ *      the packed word as the only container -- received / decoded words, the words sent (random codewords only) and
+ *      nerr / status per frame, 2 P(n) + P(l) + 8 bytes of device memory per frame of a chunk at the most and never a
+ *      symbol per bit -- so the long codes, q = 9 .. 15, can be simulated at all and BCH(255,231) moves 32 bytes per
+ *      word instead of 255.
+ *      Handles: exactly those of the packed calls above -- BCH with a hard-decision tag, q = 3 .. 15, full length or
+ *      shortened; RS handles, min-sum handles and handles of cc_minsum_create answer CC_ERR_UNSUPPORTED with the text of
+ *      the packed calls.  CC_ERR_INVALID_ARGUMENT: p not finite or outside [0, 1], NULL counters, NULL d_recv, random
+ *      codewords with a coding the encoder cannot do.  Every refusal comes before a device is asked for.
+ *      Channel: the BSC of cc_mc_run_discrete_dev, bit for bit.  Bit j of global frame gf is flipped iff word (j & 3) of
+ *      Philox4x32-10 counter (gf_lo, gf_hi, j >> 2, 2), key (seed_lo, seed_hi), zero-extended, is below
+ *      P = llround(p 2^32), taken on the host in 64 bits (P = 2^32 flips everything).  For every q <= 8 handle unpacking
+ *      the output of cc_bsc_packed_channel_dev gives the bytes of cc_discrete_channel_dev(.., p, 0, ..); the same
+ *      sentence defines the channel for q > 8.  Container as above: pitch P(n), LSB first, pad bits written as 0.
+ *      Transmitted words: random_codewords = 0 sends the all-zero word; otherwise message bit j is the bit of Philox
+ *      domain 1 that cc_awgn_llr_dev uses (bit j & 31 of word (j >> 5) & 3 of counter (gf_lo, gf_hi, j >> 7, 1): a packed
+ *      message dword is one Philox word), encoded by the route cc_encode_packed_batch_dev takes.
+ *      Decoding: the router behind cc_correct_hard_packed_batch_dev, in place.
+ *      Counters (slots of cc_mc_run_dev): CC_MC_FRAMES; CC_MC_WORD_ERRORS decoded != sent or status != 0;
+ *      CC_MC_BIT_ERRORS the wrong bits among the n code bits (a failed frame counts its output, the received word);
+ *      CC_MC_FAILURES and CC_MC_UNDETECTED as cc_mc_run_dev; CC_MC_CHANNEL_BIT_ERRORS the bits drawn flipped;
+ *      CC_MC_ITER_SUM, CC_MC_CHANNEL_ERASURES and the histogram are not touched.  A call's counters depend only on
+ *      (seed, p, random_codewords, the set of global frames): sharding and chunking do not show.
+ *      A chunk is 32 MiB of received words (CC_AMD_PACKED_MC_CHUNK_MB, read once, sets another figure), 2^20 frames
+ *      at the most; where a chunk's decoder or encoder goes the generic way the workspace of that route bounds it. ---- */
+int
+cc_mc_run_bsc_packed_dev(const cc_code *code, double p_error, uint64_t seed, uint64_t first_frame, size_t frames,
+                         int random_codewords, uint64_t *d_counters, void *stream);
+/* channel only: d_recv frames*P(n) bytes, d_sent frames*P(n) bytes or NULL */
+int
+cc_bsc_packed_channel_dev(const cc_code *code, double p_error, uint64_t seed, uint64_t first_frame, size_t frames,
+                          int random_codewords, uint8_t *d_recv, uint8_t *d_sent, void *stream);
 
 /* ---- symbol-interleaved blocks: codewords as deployed Reed-Solomon systems store them (an OTU row of ITU-T G.709:
  *      16 byte-interleaved RS(255,239) words; CCSDS RS(255,223) at depth 1 .. 5 or 8; the columns of a product code).
