@@ -25,7 +25,6 @@
 namespace ccamd {
 namespace {
 
-__device__ __forceinline__ uint32_t lane63(uint32_t v) { return __builtin_amdgcn_readlane(v, 63); }
 __device__ __forceinline__ uint32_t wave_umax(uint32_t v) { return ~lane63(wave_umin(~v)); }
 
 struct ChunkLayout {  // byte offsets inside one wavefront's LDS region

@@ -642,7 +642,7 @@ static int hard_supported(const cc_code *code, bool erasures) {
     return CC_ERR_INVALID_ARGUMENT;
   }
   // more than 64 syndromes, the Euklid tag with 2t > 63 and erasure decoding with 2t > 32 (Euklid) run
-  // algebraic_long.hip (four locator coefficients per lane) -- launch_algebraic routes them
+  // algebraic_kernel<.., 4> (four locator coefficients per lane) -- launch_algebraic routes them
   // (what the decoders refuse is a property of the code and the call: answered before a device is asked for, so that a
   //  CC_DEVICE_NONE handle tells "refused" from "would run")
   if (code->tab.family == CC_FAMILY_RS && !rs_roots_in_scope(code->desc.q, code->desc.t, code->desc.mu, code->desc.step)) {

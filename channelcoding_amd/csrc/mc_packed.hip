@@ -13,32 +13,11 @@
 // No kernel reads or writes a byte outside the frames * P bytes of a buffer: whole dwords where they lie inside the
 // frame (unaligned: P need not be a multiple of 4, and frames with P < 4 exist), the tail of a frame byte by byte.
 #include "cc_internal.hpp"
+#include "packed_words.hpp"
 #include "philox.hpp"
 
 namespace ccamd {
 namespace {
-
-// dword s of a packed frame of P bytes; bytes from P on read as zero (and are not touched)
-__device__ __forceinline__ uint32_t mp_load_word(const uint8_t *frame, int s, int P) {
-  uint32_t v = 0;
-  if (4 * s + 4 <= P) {
-    __builtin_memcpy(&v, frame + 4 * s, 4);
-  } else {
-    for (int b = 0; 4 * s + b < P; ++b) v |= static_cast<uint32_t>(frame[4 * s + b]) << (8 * b);
-  }
-  return v;
-}
-__device__ __forceinline__ void mp_store_word(uint8_t *frame, int s, int P, uint32_t v) {
-  if (4 * s + 4 <= P) {
-    __builtin_memcpy(frame + 4 * s, &v, 4);
-  } else {
-    for (int b = 0; 4 * s + b < P; ++b) frame[4 * s + b] = static_cast<uint8_t>(v >> (8 * b));
-  }
-}
-// the bits of dword s that are positions below n
-__device__ __forceinline__ uint32_t mp_word_mask(int s, int n) {
-  return n >= 32 * (s + 1) ? ~0u : (n <= 32 * s ? 0u : (1u << (n - 32 * s)) - 1u);
-}
 
 // task = (frame, dword of the packed message)
 __global__ void __launch_bounds__(256)
@@ -53,7 +32,7 @@ random_packed_kernel(uint8_t *__restrict__ msg, int l, int Pm, unsigned long lon
                                    static_cast<uint32_t>(d >> 2), 1u, k0, k1);
     const int w = d & 3;
     const uint32_t word = w == 0 ? p.c[0] : w == 1 ? p.c[1] : w == 2 ? p.c[2] : p.c[3];
-    mp_store_word(msg + f * Pm, d, Pm, word & mp_word_mask(d, l));
+    store_word(msg + f * Pm, d, Pm, word & word_mask(d, l));
   }
 }
 
@@ -87,11 +66,11 @@ bsc_packed_kernel(uint8_t *__restrict__ recv, const uint8_t *__restrict__ sent, 
         for (int s = 0; s < 4; ++s) flips |= (u.c[s] < t32 ? 1u : 0u) << (4 * c + s);
       }
       flips |= all;
-      const uint32_t nm = mp_word_mask(w, n);
+      const uint32_t nm = word_mask(w, n);
       flips &= nm;
       c_err += static_cast<unsigned>(__builtin_popcount(flips));
-      const uint32_t word = sent ? mp_load_word(sent + at, w, P) & nm : 0u;
-      mp_store_word(recv + at, w, P, word ^ flips);
+      const uint32_t word = sent ? load_word(sent + at, w, P) & nm : 0u;
+      store_word(recv + at, w, P, word ^ flips);
     }
   }
   if (counters) {
@@ -123,9 +102,9 @@ count_packed_kernel(const uint8_t *__restrict__ decoded, const uint8_t *__restri
     if (live) {
       const unsigned long long at = f * static_cast<unsigned long long>(P);
       for (int w = qd; w < W; w += G) {
-        uint32_t x = mp_load_word(decoded + at, w, P);
-        if (sent) x ^= mp_load_word(sent + at, w, P);
-        cnt += static_cast<unsigned>(__builtin_popcount(x & mp_word_mask(w, n)));
+        uint32_t x = load_word(decoded + at, w, P);
+        if (sent) x ^= load_word(sent + at, w, P);
+        cnt += static_cast<unsigned>(__builtin_popcount(x & word_mask(w, n)));
       }
     }
     for (int m = G >> 1; m >= 1; m >>= 1) cnt += __shfl_xor(cnt, m, 64);  // (partners stay inside the aligned group)

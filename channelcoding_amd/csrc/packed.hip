@@ -23,33 +23,12 @@
 
 #include "bitplane.hpp"
 #include "cc_internal.hpp"
+#include "packed_words.hpp"
 
 namespace ccamd {
 namespace {
 
 using namespace bitplane;
-
-// dword s of a packed frame of P bytes; bytes from P on read as zero (and are not touched)
-__device__ __forceinline__ uint32_t load_word(const uint8_t *frame, int s, int P) {
-  uint32_t v = 0;
-  if (4 * s + 4 <= P) {
-    __builtin_memcpy(&v, frame + 4 * s, 4);
-  } else {
-    for (int b = 0; 4 * s + b < P; ++b) v |= static_cast<uint32_t>(frame[4 * s + b]) << (8 * b);
-  }
-  return v;
-}
-__device__ __forceinline__ void store_word(uint8_t *frame, int s, int P, uint32_t v) {
-  if (4 * s + 4 <= P) {
-    __builtin_memcpy(frame + 4 * s, &v, 4);
-  } else {
-    for (int b = 0; 4 * s + b < P; ++b) frame[4 * s + b] = static_cast<uint8_t>(v >> (8 * b));
-  }
-}
-// the bits of dword s that are positions below n
-__device__ __forceinline__ uint32_t word_mask(int s, int n) {
-  return n >= 32 * (s + 1) ? ~0u : (n <= 32 * s ? 0u : (1u << (n - 32 * s)) - 1u);
-}
 
 // ---------------- one symbol per bit <-> packed ----------------
 // task = (frame, dword of the packed frame): 32 symbols.  Bytes: four symbols per (unaligned) dword, their bits 0

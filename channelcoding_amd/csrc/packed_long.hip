@@ -27,51 +27,13 @@
 #include <cstdlib>
 
 #include "cc_internal.hpp"
-#include "wave_ops.hpp"
+#include "packed_words.hpp"
+#include "wave_decode.hpp"
 
 namespace ccamd {
 namespace {
 
 constexpr int kLongMaxWaves = 16;  // per workgroup
-
-__device__ __forceinline__ uint32_t pl_load_word(const uint8_t *frame, int s, int P) {
-  uint32_t v = 0;
-  if (4 * s + 4 <= P) {
-    __builtin_memcpy(&v, frame + 4 * s, 4);
-  } else {
-    for (int b = 0; 4 * s + b < P; ++b) v |= static_cast<uint32_t>(frame[4 * s + b]) << (8 * b);
-  }
-  return v;
-}
-__device__ __forceinline__ void pl_store_word(uint8_t *frame, int s, int P, uint32_t v) {
-  if (4 * s + 4 <= P) {
-    __builtin_memcpy(frame + 4 * s, &v, 4);
-  } else {
-    for (int b = 0; 4 * s + b < P; ++b) frame[4 * s + b] = static_cast<uint8_t>(v >> (8 * b));
-  }
-}
-__device__ __forceinline__ uint32_t pl_word_mask(int s, int n) {
-  return n >= 32 * (s + 1) ? ~0u : (n <= 32 * s ? 0u : (1u << (n - 32 * s)) - 1u);
-}
-
-// x mod (2^q - 1) for x < 2^26: 2^q = 1, so the high part folds onto the low one
-__device__ __forceinline__ uint32_t modnn(uint32_t x, uint32_t nn, uint32_t q) {
-  x = (x & nn) + (x >> q);
-  x = (x & nn) + (x >> q);
-  x = (x & nn) + (x >> q);
-  x = (x & nn) + (x >> q);
-  return x >= nn ? x - nn : x;
-}
-// a + b mod nn for a, b < nn
-__device__ __forceinline__ uint32_t addnn(uint32_t a, uint32_t b, uint32_t nn) {
-  const uint32_t s = a + b;
-  return umin32(s, s - nn);  // s - nn wraps to a large value where s < nn
-}
-
-__device__ __forceinline__ uint32_t lane63(uint32_t v) { return __builtin_amdgcn_readlane(v, 63); }
-__device__ __forceinline__ uint32_t shift_up(uint32_t v) {
-  return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x138 /* wave_shr:1 */, 0xF, 0xF, true));
-}
 
 struct LongScratch {  // per wavefront
   uint16_t S[64];
@@ -180,8 +142,7 @@ packed_long_correct_kernel(WideTables T, int alg, const uint8_t *in, uint8_t *ou
   __syncthreads();
 
   LongScratch &W = scratch[wid];
-  auto gmul = [&](uint32_t a, uint32_t b) -> uint32_t { return (a && b) ? ex[addnn(lg[a], lg[b], nn)] : 0u; };
-  auto gmul_pow = [&](uint32_t a, uint32_t e) -> uint32_t { return a ? ex[addnn(lg[a], e, nn)] : 0u; };  // a alpha^e, e < nn
+  const SingleField<uint16_t> F{ex, lg, nn};
   const int Wd = (P + 3) / 4;
   const bool copy = out != in;
   const unsigned long long wave = static_cast<unsigned long long>(blockIdx.x) * nwave + wid;
@@ -201,8 +162,8 @@ packed_long_correct_kernel(WideTables T, int alg, const uint8_t *in, uint8_t *ou
         st[jj] = __builtin_amdgcn_readfirstlane(es[s0 + jj]);
       }
       for (int w = lane; w < Wd; w += 64) {
-        const uint32_t v = pl_load_word(src, w, P) & pl_word_mask(w, static_cast<int>(n));
-        if (s0 == 0 && (copy || w == Wd - 1)) pl_store_word(dst, w, P, v);
+        const uint32_t v = load_word(src, w, P) & word_mask(w, static_cast<int>(n));
+        if (s0 == 0 && (copy || w == Wd - 1)) store_word(dst, w, P, v);
         uint32_t x0 = 0, x1 = 0;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
@@ -213,7 +174,7 @@ packed_long_correct_kernel(WideTables T, int alg, const uint8_t *in, uint8_t *ou
         const uint32_t xs[4] = {x0 & 0xFFFFu, x0 >> 16, x1 & 0xFFFFu, x1 >> 16};
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
-          acc[jj] ^= gmul_pow(xs[jj], e[jj]);
+          acc[jj] ^= F.mul_pow(xs[jj], e[jj]);
           e[jj] = addnn(e[jj], st[jj], nn);
         }
       }
@@ -244,27 +205,11 @@ packed_long_correct_kernel(WideTables T, int alg, const uint8_t *in, uint8_t *ou
         }
       }
       __builtin_amdgcn_wave_barrier();
-      // ---- Berlekamp-Massey, hard_decision.h:116-155 (lane j <-> coefficient j), as wide_correct_kernel without erasures ----
-      uint32_t lam = (lane == 0) ? 1u : 0u;
-      uint32_t bpoly = lam;
-      int l = 0;
-      for (int i = 0; i < static_cast<int>(t2); ++i) {
-        bpoly = shift_up(bpoly);
-        const bool in_sum = lane >= 1 && lane <= l && lane <= i;
-        const uint32_t sij = in_sum ? W.S[i - lane] : 0u;
-        const uint32_t delta = (lane63(wave_xor(gmul(lam, sij))) ^ W.S[i]) & 0xFFFFu;
-        if (delta != 0) {  // wave-uniform
-          const uint32_t tnew = lam ^ gmul(delta, bpoly);
-          if (2 * l <= i) {
-            bpoly = lam ? ex[addnn(lg[lam], nn - lg[delta], nn)] : 0u;
-            l = i - l + 1;
-          }
-          lam = tnew;
-        }
-      }
-      const unsigned long long nz = __ballot(lam != 0);
-      deg = 63 - __builtin_clzll(nz | 1ull);
-      W.lam[lane] = static_cast<uint16_t>(lam);
+      // ---- Berlekamp-Massey (lane j <-> coefficient j), no erasures ----
+      uint32_t lam[1] = {lane == 0 ? 1u : 0u};
+      berlekamp_massey<1>(F, lam, W.S, static_cast<int>(t2), 0, 0xFFFFu);
+      deg = locator_degree<1>(lam);
+      W.lam[lane] = static_cast<uint16_t>(lam[0]);
       __builtin_amdgcn_wave_barrier();
       if (alg == CC_ALG_PGZ && 2 * deg > static_cast<int>(t2)) status = CC_FRAME_LOCATOR;  // bounded distance
       if (deg < 1) status = CC_FRAME_LOCATOR;  // cyclic.h:145-147
@@ -276,27 +221,7 @@ packed_long_correct_kernel(WideTables T, int alg, const uint8_t *in, uint8_t *ou
         else if (deg <= 8) count = chien_running<8>(ex, lg, cs, W, nn, q, n, deg, lane);
         else if (deg <= 16) count = chien_running<16>(ex, lg, cs, W, nn, q, n, deg, lane);
         else if (deg <= 32) count = chien_running<32>(ex, lg, cs, W, nn, q, n, deg, lane);
-        else {  // Horner's rule, as wide_correct_kernel
-          count = 0;
-          const unsigned long long below = (1ull << lane) - 1ull;
-          const uint32_t lead = W.lam[deg];
-          for (uint32_t base = 0; base < n; base += 64) {
-            const uint32_t p = base + lane;
-            uint32_t acc = 0;
-            if (p < n) {
-              const uint32_t xi = p ? nn - p : 0u;
-              acc = lead;
-              for (int j = deg - 1; j >= 0; --j) acc = gmul_pow(acc, xi) ^ W.lam[j];
-            }
-            const bool root = p < n && acc == 0;
-            const unsigned long long mk = __ballot(root);
-            if (root) {
-              const int rank = count + __builtin_popcountll(mk & below);
-              if (rank < 64) W.rp[rank] = static_cast<uint16_t>(p);
-            }
-            count += __builtin_popcountll(mk);
-          }
-        }
+        else count = horner_root_search(F, W.lam, deg, n, [](uint32_t p) { return p; }, W.rp);
         nerr = count;
         if (count != deg) status = CC_FRAME_LOCATOR;  // cyclic.h:134-143
         __builtin_amdgcn_wave_barrier();

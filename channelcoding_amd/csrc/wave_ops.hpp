@@ -81,6 +81,11 @@ __device__ __forceinline__ uint32_t wave_or(uint32_t v) {
   v = dpp_or<0x143, 0xC>(v);
   return v;
 }
-
+// the value of lane 63 (where the reductions above leave their result), wave-uniform
+__device__ __forceinline__ uint32_t lane63(uint32_t v) { return __builtin_amdgcn_readlane(v, 63); }
+// lane j <- lane j-1, lane 0 <- 0   (multiplication by x of a polynomial with coefficient j in lane j)
+__device__ __forceinline__ uint32_t shift_up(uint32_t v) {
+  return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x138 /* wave_shr:1 */, 0xF, 0xF, true));
+}
 
 }  // namespace ccamd

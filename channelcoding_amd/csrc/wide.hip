@@ -7,17 +7,18 @@
 // walks the positions p = lane + 64 c from HBM / L2, and the log / antilog tables (up to 256 KB) stay in global
 // memory behind the vector cache instead of LDS.
 //   syndromes   S_j = sum_p b_p alpha^(r_j p), four syndromes per pass over the frame       (cyclic.h:53-63)
-//   locator     Berlekamp-Massey with erasure pre-load / Euklid (Sugiyama), lane j = coefficient j
-//               (hard_decision.h:116-196); the PGZ tag runs as BM + degree bound, as in algebraic.hip
-//   roots       lambda(alpha^-p) = 0 by Horner, ranks of the roots from ballots            (cyclic.h:126-159)
-//   values      all ones (bch.h:80-83) / Forney for RS (the reference's Gauss elimination, rs.h:41-78, has the
-//               same unique solution)
+//   locator     Berlekamp-Massey with erasure pre-load / Euklid (Sugiyama), lane j = coefficient j; the PGZ tag runs
+//               as BM + degree bound, as in algebraic.hip
+//   roots       lambda(alpha^-p) = 0 by Horner, ranks of the roots from ballots
+//   values      all ones for BCH / Forney for RS
+//               (these three are the steps of wave_decode.hpp, shared with algebraic.hip and packed_long.hip, on a
+//               view of the global tables; their references are given there)
 //   re-check    syndromes of the error pattern = received syndromes, one lane per syndrome  (cyclic.h:243-248)
 // Encoding (division_tag, cyclic.h:35-40): the remainder of a(x) x^k by g(x) in a k-stage feedback register kept in
 // LDS, one message symbol per step, lanes = register stages.  Throughput is not the point of this path (the
 // reference itself cannot instantiate a code with q > 8 without an edit); results are pinned like the byte path.
 #include "cc_internal.hpp"
-#include "wave_ops.hpp"
+#include "wave_decode.hpp"
 
 namespace ccamd {
 namespace {
@@ -29,11 +30,6 @@ struct WideScratch {
   uint16_t rp[64];
   uint16_t val[64];
 };
-
-__device__ __forceinline__ uint32_t bcast63w(uint32_t v) { return __builtin_amdgcn_readlane(v, 63); }
-__device__ __forceinline__ uint32_t shift_up_w(uint32_t v) {
-  return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x138 /* wave_shr:1 */, 0xF, 0xF, true));
-}
 
 // TW: an RS code with roots alpha^(mu + i step) other than alpha^1 .. alpha^2t (algebraic.hip): the locator
 // of position p is Z = alpha^(step p) -- roots tested at Z^-1, erasure pre-load with Z -- and Forney's quotient is scaled
@@ -52,8 +48,7 @@ wide_correct_kernel(WideTables T, int alg, const uint16_t *__restrict__ in, cons
   const bool is_rs = T.family == CC_FAMILY_RS;
   const unsigned long long wave = static_cast<unsigned long long>(blockIdx.x) * 4 + wid;
   const unsigned long long nwaves = static_cast<unsigned long long>(gridDim.x) * 4;
-  auto gmul = [&](uint32_t a, uint32_t b) -> uint32_t { return (a && b) ? ex[lg[a] + lg[b]] : 0u; };
-  auto gmul_pow = [&](uint32_t a, uint32_t e) -> uint32_t { return a ? ex[lg[a] + e] : 0u; };  // a alpha^e, e < nn
+  const DoubledField<uint16_t> F{ex, lg, nn};
   const uint32_t r0 = T.root_log[0];
   const uint32_t step = t2 > 1 ? (T.root_log[1] + nn - r0) % nn : 0u;
   const uint32_t twist = TW ? (step + nn - r0) % nn : 0u;  // (step - mu) mod nn: root_log[0] = mu, no exponent wraps
@@ -89,7 +84,7 @@ wide_correct_kernel(WideTables T, int alg, const uint16_t *__restrict__ in, cons
       }
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) {
-        const uint32_t s = bcast63w(wave_xor(acc[jj])) & 0xFFFFu;
+        const uint32_t s = lane63(wave_xor(acc[jj])) & 0xFFFFu;
         if (j0 + jj < t2) {
           any_syndrome |= s;
           if (lane == 0) W.S[j0 + jj] = static_cast<uint16_t>(s);
@@ -101,94 +96,21 @@ wide_correct_kernel(WideTables T, int alg, const uint16_t *__restrict__ in, cons
     if (any_syndrome != 0 && nerase > t2) {
       status = CC_FRAME_ERASURES;  // bch.h:105-107
     } else if (any_syndrome != 0) {  // wave-uniform
-      uint32_t lam;
+      // ---- error locator, lane j <-> coefficient j: Euklid (Sugiyama) or Berlekamp-Massey on the erasure locator ----
       const int rho = static_cast<int>(nerase);
-      if (alg == CC_ALG_EUKLID) {
-        // ---- Euklid / Sugiyama with erasures, hard_decision.h:157-196 (lane j <-> coefficient j) ----
-        uint32_t u = (lane == 0) ? 1u : 0u;
-        for (uint32_t e = 0; e < nerase; ++e) u ^= gmul(ex[TW ? zlog(er[ebase + e] % nn) : er[ebase + e] % nn], shift_up_w(u));
-        uint32_t rp = 0;
-        for (int m = 0; m <= rho; ++m) {
-          const uint32_t um = __builtin_amdgcn_readlane(u, m);
-          const uint32_t sj = (lane >= m && static_cast<uint32_t>(lane - m) < t2) ? W.S[lane - m] : 0u;
-          rp ^= gmul(um, sj);
-        }
-        uint32_t rc = (static_cast<uint32_t>(lane) == t2) ? 1u : 0u, wp = u, wc = 0u;
-        const int max_deg = (static_cast<int>(t2) + rho) / 2;
-        auto degree_of = [&](uint32_t v) { return 63 - __builtin_clzll(__ballot(v != 0) | 1ull) - ((__ballot(v != 0) == 0) ? 1 : 0); };
-        int guard = 0;
-        while (degree_of(rc) >= max_deg && guard++ < 130) {
-          const int dr = degree_of(rc);
-          const uint32_t lead = __builtin_amdgcn_readlane(rc, dr);
-          uint32_t rem = rp, wn = wp;
-          for (int pos = degree_of(rem); pos >= dr; --pos) {
-            const uint32_t top = __builtin_amdgcn_readlane(rem, pos);
-            if (top == 0) continue;
-            const uint32_t coef = ex[lg[top] + nn - lg[lead]];
-            const int sh = pos - dr;
-            const uint32_t rc_sh = __shfl(rc, lane - sh, 64), wc_sh = __shfl(wc, lane - sh, 64);
-            rem ^= (lane >= sh) ? gmul(coef, rc_sh) : 0u;
-            wn ^= (lane >= sh) ? gmul(coef, wc_sh) : 0u;
-          }
-          rp = rc;
-          rc = rem;
-          wp = wc;
-          wc = wn;
-        }
-        const uint32_t w0 = __builtin_amdgcn_readlane(wc, 0);
-        if (w0 == 0) status = CC_FRAME_LOCATOR;  // "Cannot invert last element", :191-192
-        lam = (w0 && wc) ? ex[lg[wc] + nn - lg[w0]] : 0u;
-      } else {
-        // ---- Berlekamp-Massey, hard_decision.h:116-155 (lane j <-> coefficient j) ----
-        lam = (lane == 0) ? 1u : 0u;
-        for (uint32_t e = 0; e < nerase; ++e) lam ^= gmul(ex[TW ? zlog(er[ebase + e] % nn) : er[ebase + e] % nn], shift_up_w(lam));  // :128-131
-        uint32_t bpoly = lam;
-        int l = rho;
-        for (int i = rho; i < static_cast<int>(t2); ++i) {
-          bpoly = shift_up_w(bpoly);
-          const bool in_sum = lane >= 1 && lane <= l && lane <= i;
-          const uint32_t sij = in_sum ? W.S[i - lane] : 0u;
-          const uint32_t delta = (bcast63w(wave_xor(gmul(lam, sij))) ^ W.S[i]) & 0xFFFFu;
-          if (delta != 0) {  // wave-uniform
-            const uint32_t tnew = lam ^ gmul(delta, bpoly);
-            if (2 * l <= i + rho) {
-              bpoly = lam ? ex[lg[lam] + nn - lg[delta]] : 0u;
-              l = i + rho - l + 1;
-            }
-            lam = tnew;
-          }
-        }
-      }
-      const unsigned long long nz = __ballot(lam != 0);
-      deg = 63 - __builtin_clzll(nz | 1ull);
-      W.lam[lane] = static_cast<uint16_t>(lam);
+      uint32_t lam[1] = {lane == 0 ? 1u : 0u};
+      erasure_preload<1>(F, lam, nerase, [&](uint32_t e) { return TW ? zlog(er[ebase + e] % nn) : er[ebase + e] % nn; });
+      if (alg == CC_ALG_EUKLID) lam[0] = sugiyama(F, W.S, lam[0], static_cast<int>(t2), rho, status);
+      else berlekamp_massey<1>(F, lam, W.S, static_cast<int>(t2), rho, 0xFFFFu);
+      deg = locator_degree<1>(lam);
+      W.lam[lane] = static_cast<uint16_t>(lam[0]);
       if (alg == CC_ALG_PGZ && 2 * deg - rho > static_cast<int>(t2)) status = CC_FRAME_LOCATOR;  // bounded distance
       if (deg < 1) status = CC_FRAME_LOCATOR;  // cyclic.h:145-147
 
       // ---- root search: position p is in error iff lambda(alpha^-p) = 0 ----
       if (status == CC_FRAME_OK) {
-        int count = 0;
-        const unsigned long long below = (1ull << lane) - 1ull;
-        const uint32_t lead = W.lam[deg];
-        for (uint32_t base = 0; base < n; base += 64) {  // wave-uniform trip count
-          const uint32_t p = base + lane;
-          uint32_t acc = 0;
-          if (p < n) {
-            const uint32_t zl = TW ? zlog(p) : p;
-            const uint32_t xi = zl ? nn - zl : 0u;  // log of X^-1 for X = alpha^p
-            acc = lead;
-            for (int j = deg - 1; j >= 0; --j) acc = gmul_pow(acc, xi) ^ W.lam[j];
-          }
-          const bool root = p < n && acc == 0;
-          const unsigned long long mk = __ballot(root);
-          if (root) {
-            const int rank = count + __builtin_popcountll(mk & below);
-            if (rank < 64) W.rp[rank] = static_cast<uint16_t>(p);
-          }
-          count += __builtin_popcountll(mk);
-        }
-        nerr = count;
-        if (count != deg) status = CC_FRAME_LOCATOR;  // cyclic.h:134-143
+        nerr = horner_root_search(F, W.lam, deg, n, [&](uint32_t p) { return TW ? zlog(p) : p; }, W.rp);
+        if (nerr != deg) status = CC_FRAME_LOCATOR;  // cyclic.h:134-143
       }
 
       // ---- error values: one lane per located error ----
@@ -198,20 +120,13 @@ wide_correct_kernel(WideTables T, int alg, const uint16_t *__restrict__ in, cons
         for (int m = 0; m <= deg; ++m) {
           const uint32_t lm = W.lam[m];
           const uint32_t s = (lane >= m && lane < deg && static_cast<uint32_t>(lane - m) < t2) ? W.S[lane - m] : 0u;
-          om ^= gmul(lm, s);
+          om ^= F.mul(lm, s);
         }
         W.om[lane] = static_cast<uint16_t>(om);
         y = 0;
         if (lane < deg) {
-          const uint32_t p = W.rp[lane], zl = TW ? zlog(p) : p;
-          const uint32_t xi = zl ? nn - zl : 0u;
-          const uint32_t x2 = (2 * xi) % nn;
-          uint32_t num = 0, den = 0;
-          for (int j = deg - 1; j >= 0; --j) num = gmul_pow(num, xi) ^ W.om[j];
-          const int mtop = (deg & 1) ? deg : deg - 1;
-          for (int m = mtop; m >= 1; m -= 2) den = gmul_pow(den, x2) ^ W.lam[m];
-          y = (num && den) ? ex[lg[num] + nn - lg[den]] : 0u;
-          if (TW) y = gmul_pow(y, static_cast<uint32_t>((static_cast<unsigned long long>(twist) * p) % nn));
+          const uint32_t p = W.rp[lane];
+          y = forney_value<TW>(F, W.lam, W.om, deg, p, TW ? zlog(p) : p, twist);
         }
       }
       if (status == CC_FRAME_OK) W.val[lane] = static_cast<uint16_t>(lane < deg ? y : 0u);
@@ -223,7 +138,7 @@ wide_correct_kernel(WideTables T, int alg, const uint16_t *__restrict__ in, cons
           const uint32_t rj = (r0 + static_cast<uint32_t>(lane) * step) % nn;
           for (int i = 0; i < deg; ++i) {
             const uint32_t e = static_cast<uint32_t>((static_cast<unsigned long long>(rj) * W.rp[i]) % nn);
-            sj ^= gmul_pow(W.val[i], e);
+            sj ^= F.mul_pow(W.val[i], e);
           }
           sj ^= W.S[lane];
         }
@@ -295,7 +210,7 @@ wide_extract_kernel(const uint16_t *__restrict__ cw, uint16_t *__restrict__ msg,
 int launch_wide_correct(const cc_code *code, const uint16_t *d_in, const uint16_t *d_er, const uint32_t *d_off,
                         uint16_t *d_out, int32_t *d_nerr, int32_t *d_status, size_t B, hipStream_t stream) {
   if (B == 0) return CC_OK;
-  if (d_off && code->desc.algorithm == CC_ALG_PGZ)  // BCH only (capi.hip refuses RS): the two-trial rule below
+  if (d_off && code->desc.algorithm == CC_ALG_PGZ)  // BCH only (capi.hip refuses RS): the two-trial rule, algebraic.hip
     return launch_wide_pgz_erasures(code, d_in, d_er, d_off, d_out, d_nerr, d_status, B, stream);
   const unsigned long long blocks = (B + 3) / 4, max_grid = static_cast<unsigned long long>(code->num_cus) * 8;
   auto launch = [&](auto kernel) {
@@ -306,91 +221,6 @@ int launch_wide_correct(const cc_code *code, const uint16_t *d_in, const uint16_
   rs_twisted(code) ? launch(wide_correct_kernel<true>) : launch(wide_correct_kernel<false>);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? CC_OK : hip_fail(e, "wide_correct_kernel launch");
-}
-
-// ---- primitive_bch::correct with PGZ and erasures on 16-bit symbols, bch.h:97-149 (width-agnostic there): decode twice
-//      with the erased positions forced to 0 and to 1, keep the result with fewer corrected errors (the first wins
-//      ties).  Same rule as launch_pgz_erasures of the byte path (algebraic.hip); the trials run without erasures. ----
-namespace {
-__global__ void __launch_bounds__(256)
-wide_force_erasures_kernel(const uint16_t *__restrict__ in, const uint16_t *__restrict__ er,
-                           const uint32_t *__restrict__ er_off, uint16_t *__restrict__ in0, uint16_t *__restrict__ in1,
-                           uint32_t n, unsigned long long B) {
-  const int lane = threadIdx.x & 63;
-  const unsigned long long wave = static_cast<unsigned long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
-  const unsigned long long nwaves = static_cast<unsigned long long>(gridDim.x) * 4;
-  for (unsigned long long f = wave; f < B; f += nwaves) {
-    for (uint32_t p = lane; p < n; p += 64) {
-      const uint16_t v = in[f * n + p];
-      in0[f * n + p] = v;
-      in1[f * n + p] = v;
-    }
-    __builtin_amdgcn_wave_barrier();
-    for (uint32_t e = er_off[f] + lane; e < er_off[f + 1]; e += 64) {  // (the copies above are this wave's own stores)
-      in0[f * n + er[e]] = 0;
-      in1[f * n + er[e]] = 1;
-    }
-  }
-}
-__global__ void __launch_bounds__(256)
-wide_select_trial_kernel(const uint16_t *__restrict__ in, const uint32_t *__restrict__ er_off, uint16_t *__restrict__ out0,
-                         int32_t *__restrict__ nerr0, int32_t *__restrict__ st0, const uint16_t *__restrict__ out1,
-                         const int32_t *__restrict__ nerr1, const int32_t *__restrict__ st1, uint32_t n, uint32_t t2,
-                         unsigned long long B) {
-  const int lane = threadIdx.x & 63;
-  const unsigned long long wave = static_cast<unsigned long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
-  const unsigned long long nwaves = static_cast<unsigned long long>(gridDim.x) * 4;
-  for (unsigned long long f = wave; f < B; f += nwaves) {
-    const uint32_t ne = er_off[f + 1] - er_off[f];
-    if (ne == 0) continue;  // trial 0 decoded the untouched word: the plain path (bch.h:100-101)
-    const int s0 = st0[f], s1 = st1[f], e0 = nerr0[f], e1 = nerr1[f];
-    int pick, status;
-    if (ne > t2) {
-      pick = -1;
-      status = CC_FRAME_ERASURES;  // bch.h:105-107
-    } else if (s0 != CC_FRAME_OK && s1 != CC_FRAME_OK) {
-      pick = -1;
-      status = CC_FRAME_LOCATOR;  // "Erasure decoding failed."
-    } else {
-      pick = (s0 != CC_FRAME_OK || (s1 == CC_FRAME_OK && e1 < e0)) ? 1 : 0;
-      status = CC_FRAME_OK;
-    }
-    for (uint32_t p = lane; p < n; p += 64) {
-      const uint16_t v = pick < 0 ? in[f * n + p] : (pick == 1 ? out1[f * n + p] : out0[f * n + p]);
-      out0[f * n + p] = v;
-    }
-    if (lane == 0) {
-      nerr0[f] = pick < 0 ? -1 : (pick == 1 ? e1 : e0);
-      st0[f] = status;
-    }
-  }
-}
-}  // namespace
-
-int launch_wide_pgz_erasures(const cc_code *code, const uint16_t *d_in, const uint16_t *d_er, const uint32_t *d_off,
-                             uint16_t *d_out, int32_t *d_nerr, int32_t *d_status, size_t B, hipStream_t stream) {
-  if (B == 0) return CC_OK;
-  const size_t n = code->tab.n;
-  uint16_t *in0 = nullptr;
-  int32_t *aux = nullptr;  // nerr0, st0 (when the caller passed none), nerr1, st1
-  CC_HIP_TRY(workspace_alloc(code, reinterpret_cast<void **>(&in0), 3 * B * n * sizeof(uint16_t), stream));
-  uint16_t *in1 = in0 + B * n, *out1 = in1 + B * n;
-  CC_HIP_TRY(workspace_alloc(code, reinterpret_cast<void **>(&aux), 4 * B * sizeof(int32_t), stream));
-  int32_t *nerr0 = d_nerr ? d_nerr : aux, *st0 = d_status ? d_status : aux + B, *nerr1 = aux + 2 * B, *st1 = aux + 3 * B;
-  const unsigned long long Bq = B;
-  const int grid = code->num_cus * 8;
-  hipLaunchKernelGGL(wide_force_erasures_kernel, dim3(grid), dim3(256), 0, stream, d_in, d_er, d_off, in0, in1,
-                     static_cast<uint32_t>(n), Bq);
-  int rc = launch_wide_correct(code, in0, nullptr, nullptr, d_out, nerr0, st0, B, stream);
-  if (rc == CC_OK) rc = launch_wide_correct(code, in1, nullptr, nullptr, out1, nerr1, st1, B, stream);
-  if (rc == CC_OK) {
-    hipLaunchKernelGGL(wide_select_trial_kernel, dim3(grid), dim3(256), 0, stream, d_in, d_off, d_out, nerr0, st0, out1,
-                       nerr1, st1, static_cast<uint32_t>(n), code->wide_dev.nroots, Bq);
-    if (hipGetLastError() != hipSuccess) rc = CC_ERR_HIP;
-  }
-  (void)hipFreeAsync(in0, stream);
-  (void)hipFreeAsync(aux, stream);
-  return rc;
 }
 
 int launch_wide_encode(const cc_code *code, const uint16_t *d_msg, uint16_t *d_cw, size_t B, hipStream_t stream) {

@@ -179,7 +179,10 @@ int cc_encode_batch_dev(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw
  *      bch.h:85-160.  Erasures in CSR form: frame f owns erasures[erasure_offsets[f] .. erasure_offsets[f+1]);
  *      both pointers NULL = no erasures.  out = corrected word (= hard-decided input when the frame fails),
  *      nerr = number of corrected symbols or -1, status = CC_FRAME_*.  nerr/status may be NULL.  out may be the
- *      same buffer as in (decoding in place; the _dev form then skips its copy of the words). ---- */
+ *      same buffer as in (decoding in place; the _dev form then skips its copy of the words).
+ *      Erased positions lie below n: the host-pointer forms return CC_ERR_INVALID_ARGUMENT otherwise; a device list
+ *      is not read on the host, and positions >= n in a device list are ignored by the PGZ trials (bch.h:97-149),
+ *      on byte and on 16-bit symbols (cc_correct_hard_batch_u16_dev) alike. ---- */
 int cc_correct_hard_batch(const cc_code *code, const uint8_t *in /* B*n symbols */, const uint16_t *erasures,
                           const uint32_t *erasure_offsets, uint8_t *out /* B*n */, int32_t *nerr, int32_t *status,
                           size_t B);

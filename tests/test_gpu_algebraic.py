@@ -419,7 +419,7 @@ def test_extreme_code_parameters(fam, q, t, frames):
     for alg in (PGZ, BM, EUKLID):
         code = cls(q, cc.errors(t), TAGS[alg]())
         assert np.array_equal(code.encode_batch(o.extract(cw)), cw)
-        # (Euklid at t = 32 needs coefficient 64 of x^2t: algebraic_long.hip, four coefficients per lane)
+        # (Euklid at t = 32 needs coefficient 64 of x^2t: algebraic_kernel<.., 4>, four coefficients per lane)
         check_against_oracle(code.correct_batch(rx), o, alg, rx)
 
 
@@ -440,7 +440,7 @@ def check_erasure_frames(code, o, alg, rxe, ers):
 @pytest.mark.parametrize("fam,t,frames", [(RS, 33, 120), (RS, 40, 100), (RS, 64, 80), (RS, 100, 40), (RS, 120, 30),
                                           (BCH, 40, 100), (BCH, 43, 60), (BCH, 63, 60)])
 def test_more_than_64_syndromes(fam, t, frames):
-    """errors<t> with t > 32 (bch.h:28-46, rs.h:18-28 instantiate any t): algebraic_long.hip, every tag, 0 .. t + 3
+    """errors<t> with t > 32 (bch.h:28-46, rs.h:18-28 instantiate any t): algebraic_kernel<.., 4>, every tag, 0 .. t + 3
     errors per frame, against the oracle frame for frame; then the same codes with erasures (BM and Euklid: erasure
     pre-load hard_decision.h:128-131, :171-172), and Euklid with erasures at t = 20 and 32 (2t > 32: the Sugiyama
     kernel's lane budget ends there)."""

@@ -308,7 +308,7 @@ def test_encode_extract_decode(q, t, N, poly, coding):
 @pytest.mark.parametrize("q,t,N", NATIVE)
 def test_empty_batches_and_exact_allocations(q, t, N):
     """B = 0 returns empty outputs.  A batch that ends on the last byte of its allocation: the kernels move whole dwords
-    only where they lie inside the frame and the tail of a frame byte by byte (packed.hip: load_word / store_word), so
+    only where they lie inside the frame and the tail of a frame byte by byte (packed_words.hpp: load_word / store_word), so
     B * P bytes from the allocator are all a call needs -- for P = 25 and 13 too."""
     code = make(q, t, N, "BM")
     P = code.packed_bytes

@@ -277,6 +277,50 @@ def test_erasures_on_several_fields(fam, q, t, alg):
     assert np.array_equal(out, res["out"])
 
 
+@pytest.mark.parametrize("q", [9, 8])
+def test_pgz_trials_ignore_positions_outside_the_frame(q):
+    """A device erasure list is not read on the host, so positions >= n reach the two-trial rule (bch.h:97-149) as they
+    are: force_erasures_kernel skips them.  BCH, t = 2, shortened to n = 100, PGZ tag, 8 frames with 0 .. 3 valid
+    positions each plus the entries n, n + 5 and 65535: words, nerr and status equal those of the call without the three.
+    q = 9: cc_correct_hard_batch_u16_dev; q = 8: the byte route, cc_correct_hard_batch_dev -- one kernel serves both."""
+    import torch
+    n, B = 100, 8
+    kw = dict(modular_polynomial=POLY[9]) if q == 9 else {}
+    code = cc.primitive_bch(q, cc.errors(2), cc.peterson_gorenstein_zierler_tag(), n=n, **kw)
+    assert code.n == n
+    rng = np.random.default_rng(9100 + q)
+    dt = np.uint16 if q == 9 else np.uint8
+    rx = np.asarray(code.encode_batch(rng.integers(0, 2, (B, code.l)).astype(dt))).astype(dt)
+    valid = []
+    for f in range(B):
+        pos = rng.choice(n, f % 4 + 1, replace=False)  # the erased positions, then one plain error
+        valid.append(sorted(int(p) for p in pos[: f % 4]))
+        for p in pos:
+            rx[f, p] ^= 1
+    valid[1] = [n - 1]
+    d_rx = torch.from_numpy(rx.view(np.int16) if q == 9 else rx).cuda()
+    entry = getattr(capi.lib(), "cc_correct_hard_batch_u16_dev" if q == 9 else "cc_correct_hard_batch_dev")
+    P = lambda t: C.c_void_p(t.data_ptr())
+
+    def run(per):
+        er = torch.from_numpy(np.array([p for l in per for p in l], np.uint16).view(np.int16)).cuda()
+        off = torch.from_numpy(np.cumsum([0] + [len(l) for l in per]).astype(np.uint32).view(np.int32)).cuda()
+        # guard words around the output: nothing outside the B * n symbols may change
+        out = torch.full((B + 2, n), 0x55, dtype=d_rx.dtype, device="cuda")
+        nerr, st = (torch.full((B,), 99, dtype=torch.int32, device="cuda") for _ in range(2))
+        capi.check(entry(code._h, P(d_rx), P(er), P(off), P(out[1]), P(nerr), P(st), B, None), "correct")
+        torch.cuda.synchronize()
+        assert (out[0] == 0x55).all() and (out[B + 1] == 0x55).all()
+        return out[1: B + 1].cpu().numpy(), nerr.cpu().numpy(), st.cpu().numpy()
+
+    want = run(valid)
+    assert (want[2] == 0).sum() >= B // 2 and (want[1] > 0).any()  # the lists matter: frames decode through the trials
+    for order in (lambda l: l + [n, n + 5, 65535], lambda l: [65535, n] + l + [n + 5]):
+        got = run([order(l) for l in valid])
+        for g, w in zip(got, want):
+            assert np.array_equal(g, w)
+
+
 # ---- launch geometry ----
 def test_launch_geometry():
     """RS(511,503), BM: B = 1, 3, 4, 5, 63 (four waves per workgroup, one scratch each) and more frames than the grid
