@@ -14,12 +14,19 @@
 //
 // (Round 3: the Euklid tag and, on the bit-plane chain, erasures are served here too -- algebraic_chunk_supported.)  Same results as that kernel bit for
 // bit (tests/test_gpu_algebraic.py runs both through CC_AMD_NO_CHUNK=1).
+//
+// The stages exist once, as inline templates in front of the kernels: table staging (stage_*), position_exponents,
+// bm_lds (stage B, and chunk_bm_kernel behind the bit-plane syndromes), chunk_prologue / export_locator_planes (both
+// Berlekamp-Massey kernels of the plane chain), and the correction stage -- locator_at_positions, rank_roots,
+// forney_values, recheck_mismatch -- over a table view (stage C, and chunk_fix_kernel).  The format of the arrays the
+// plane chain keeps in HBM, its workspace and the decision every corrector starts with are chunk_chain.hpp's.
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
 
 #include "bitplane.hpp"
 #include "cc_internal.hpp"
+#include "chunk_chain.hpp"
 #include "wave_ops.hpp"
 
 namespace ccamd {
@@ -27,8 +34,279 @@ namespace {
 
 __device__ __forceinline__ uint32_t wave_umax(uint32_t v) { return ~lane63(wave_umin(~v)); }
 
+// ---------------- tables in LDS ----------------
+// Staged by the 256 threads of a workgroup; the caller's __syncthreads() follows.
+//   ex   [1024]  antilog table, zero from 512 on: with log 0 = kLogZero = 512 a product is ex[log a + log b], no zero tests
+//   lg2  [256]   u16 logs with log 0 = `zero` (kLogZero beside ex, kLongZero beside exl)
+//   lg   [256]   plain log table (log 0 = 0)
+//   exl  [size]  alpha^i for i < kLongZero, zero from there on: long enough for a Horner / Chien exponent that is never
+//                wrapped -- index = log of the coefficient (<= 254, or kLongZero for a zero coefficient) + up to 32 steps
+//                of <= 254 (GF(2^8) only: the bit-plane chain)
+constexpr uint32_t kLongZero = 8448;
+__device__ __forceinline__ void stage_ex(const AlgebraicTables *T, uint8_t *ex) {
+  for (int i = threadIdx.x; i < 1024; i += 256) ex[i] = i < 512 ? T->exp[i] : 0;
+}
+__device__ __forceinline__ void stage_log16(const AlgebraicTables *T, uint16_t *lg2, uint32_t zero = kLogZero) {
+  lg2[threadIdx.x] = static_cast<uint16_t>(threadIdx.x ? T->log[threadIdx.x] : zero);
+}
+__device__ __forceinline__ void stage_log(const AlgebraicTables *T, uint8_t *lg) { lg[threadIdx.x] = T->log[threadIdx.x]; }
+__device__ __forceinline__ void stage_exl(const AlgebraicTables *T, uint8_t *exl, uint32_t size) {
+  for (uint32_t i = threadIdx.x; i < size; i += 256) exl[i] = i < kLongZero ? T->exp[i % 255u] : 0;
+}
+struct LogTables {
+  const uint8_t *ex;
+  const uint16_t *lg2;
+  const uint8_t *lg;
+};
+
+// per-lane exponent bookkeeping (roots alpha^(r0 + j step)) of the positions p = lane + 64 c; returns step.
+// TW: an RS code with roots alpha^(mu + i step) other than alpha^1 .. alpha^2t (algebraic.hip, DESIGN 4.9): roots tested
+// at Z^-1 = alpha^(-step p), Forney's quotient scaled by alpha^(twist p); TW = false is the code as it was
+template <bool TW>
+__device__ __forceinline__ int position_exponents(const AlgebraicTables *T, int lane, uint32_t (&e0)[4], uint32_t (&dstep)[4],
+                                                  uint32_t (&xinv)[4], bool (&valid)[4]) {
+  const int n = T->n, nn = T->nf, t2 = T->nroots;
+  const int r0 = T->roots_log[0];
+  const int step = t2 > 1 ? (T->roots_log[1] + nn - r0) % nn : 0;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const int p = lane + 64 * c;
+    valid[c] = p < n;
+    e0[c] = static_cast<uint32_t>((r0 * p) % nn);
+    dstep[c] = static_cast<uint32_t>((step * p) % nn);
+    xinv[c] = static_cast<uint32_t>((nn - (p % nn)) % nn);
+    if (TW) xinv[c] = (static_cast<uint32_t>(nn) - dstep[c]) % static_cast<uint32_t>(nn);  // log of Z^-1
+  }
+  return step;
+}
+
+// ---------------- Berlekamp-Massey in LDS, one lane per frame (hard_decision.h:116-155) ----------------
+// Column f = lane & (FPW - 1) of SL (log S_j), LL (log lambda_m) and BL (log b_m), all [row][FPW]; everything in the log
+// domain (log 0 = kLogZero).  `mine`: the lane has a frame to solve; rho erasures of that frame at er[ebase ..] (er =
+// nullptr: none).  Leaves log lambda in LL, returns the LFSR length L and the degree of lambda.  With FPW = 32 the lanes
+// 32 .. 63 alias the columns of lanes 0 .. 31: `mine` is false there and they write nothing.
+template <int FPW>
+__device__ __forceinline__ int bm_lds(const uint8_t *ex, const uint16_t *lg2, const uint16_t *SL, uint16_t *LL, uint16_t *BL,
+                                      int t2, int nn, bool mine, uint32_t rho, const uint16_t *er, uint32_t ebase, int &deg) {
+  constexpr int U = 4;  // U coefficients per trip of the two inner loops (8: measured slower)
+  const int lane = threadIdx.x & 63, f = lane & (FPW - 1), nc = t2 + 1;
+  const bool col = lane < FPW;
+  if (col)
+    for (int m = 0; m < nc; ++m) LL[m * FPW + f] = static_cast<uint16_t>(m == 0 ? 0 : kLogZero);  // lambda = 1
+  // lambda *= (1 + alpha^p x) for every erased position p, :128-131; the recurrence then starts at i = rho with
+  // b = lambda and L = rho
+  const int rmax = er ? static_cast<int>(wave_umax(mine ? rho : 0u)) : 0;
+  for (int e = 0; e < rmax; ++e) {
+    const bool act = mine && static_cast<uint32_t>(e) < rho;
+    const uint32_t px = act ? static_cast<uint32_t>(er[ebase + e]) % static_cast<uint32_t>(nn) : 0u;
+    for (int m = e + 1; m >= 1; --m) {
+      const uint32_t nv = ex[LL[m * FPW + f]] ^ ex[LL[(m - 1) * FPW + f] + px];
+      if (act) LL[m * FPW + f] = lg2[nv];
+    }
+  }
+  if (col)
+    for (int m = 0; m < nc; ++m) BL[m * FPW + f] = LL[m * FPW + f];
+  const int irho = static_cast<int>(rho);
+  int l = irho, shift = 0;  // b is stored unshifted; b(x) x^shift is the polynomial of the recurrence
+  int lw = rmax;            // longest register in the wavefront: max(lw, cap) after every step (cap covers all that grew)
+  for (int i = 0; i < t2; ++i) {
+    const bool started = i >= irho;  // (a lane with erasures joins at step rho)
+    shift += started ? 1 : 0;        // b = b * x, :134
+    uint32_t d = ex[SL[i * FPW + f]];
+    const int mm = i < lw ? i : lw;
+    // discrepancy :139-141; lambda_m = 0 (log 512) for m > L, and L <= i: running past mm in blocks of U adds zeros
+    for (int m0 = 1; m0 <= mm; m0 += U) {
+      uint32_t la[U], sa[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int m = m0 + u < nc ? m0 + u : nc - 1;
+        la[u] = LL[m * FPW + f];
+        sa[u] = SL[(i - m > 0 ? i - m : 0) * FPW + f];
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) d ^= ex[la[u] + sa[u]];
+    }
+    const bool upd = mine && started && d != 0;
+    const bool grow = upd && 2 * l <= i + irho;  // :145
+    const uint32_t ld = lg2[d];
+    const uint32_t linv = static_cast<uint32_t>(nn) - ld;  // log of d^-1 (or nn for d = 1: wrapped below)
+    const int lnew = grow ? i + irho + 1 - l : l;
+    const int cap = static_cast<int>(wave_umax(upd ? static_cast<uint32_t>(lnew) : 0u));
+    if (__any(upd)) {
+      // lambda += d * b * x^shift, and where the register grows b := lambda_old / d; descending m so that the
+      // shifted reads of the old b (index m - shift < m) happen before that index is overwritten.
+      // U coefficients per trip, all reads before the look-ups before the writes: a read of b at m - shift
+      // always precedes the write of that index in the sequential order too.
+      for (int m1 = cap; m1 >= 0; m1 -= U) {
+        uint32_t lold[U], bt[U], nv[U], ln[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int m = m1 - u > 0 ? m1 - u : 0, bi = m1 - u - shift;
+          lold[u] = LL[m * FPW + f];
+          bt[u] = bi >= 0 ? BL[(bi >= 0 ? bi : 0) * FPW + f] : kLogZero;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) nv[u] = ex[lold[u]] ^ ex[ld + bt[u]];
+#pragma unroll
+        for (int u = 0; u < U; ++u) ln[u] = lg2[nv[u]];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int m = m1 - u;
+          if (m < 0) break;  // wave-uniform
+          if (upd) LL[m * FPW + f] = static_cast<uint16_t>(ln[u]);
+          if (grow) {
+            uint32_t q = lold[u] + linv;
+            q = q >= static_cast<uint32_t>(nn) ? q - nn : q;
+            BL[m * FPW + f] = static_cast<uint16_t>(lold[u] >= kLogZero ? kLogZero : q);
+          }
+        }
+      }
+    }
+    if (grow) {
+      l = lnew;
+      shift = 0;
+    }
+    lw = cap > lw ? cap : lw;
+  }
+  deg = 0;
+  for (int m = t2; m >= 1; --m)
+    if (deg == 0 && LL[m * FPW + f] != kLogZero) deg = m;
+  return l;
+}
+
+// ---------------- the correction stage: roots, error values, re-check ----------------
+// One frame per wavefront trip, lane l owns the positions l + 64 c.  All polynomial arithmetic on logs with log 0 =
+// kLogZero (no zero tests): a term lambda_m X^-m is "antilog of log lambda_m + m log X^-1", the exponent advancing once
+// per coefficient; wave-uniform coefficients come from a register (lane m of cll holds log lambda_m) by v_readlane.
+// A view says which antilog table serves such a term and whether the exponent is wrapped -- nothing else.
+struct WrappedView {  // ex, exponents kept below nn: one add and one wrap per coefficient
+  const uint8_t *ex;
+  uint32_t nn;
+  __device__ __forceinline__ uint32_t term(uint32_t l, uint32_t e) const { return ex[l + e]; }
+  __device__ __forceinline__ void advance(uint32_t &e, uint32_t by) const {
+    e += by;
+    e = umin32(e, e - nn);
+  }
+};
+struct LongView {  // exl, exponents never wrapped
+  const uint8_t *exl;
+  __device__ __forceinline__ uint32_t term(uint32_t l, uint32_t e) const { return exl[(l >= kLogZero ? kLongZero : l) + e]; }
+  __device__ __forceinline__ void advance(uint32_t &e, uint32_t by) const { e += by; }
+};
+struct FixScratch {  // of the frame being corrected, per wavefront
+  uint16_t *CSL;     // [64] log S_j
+  uint8_t *CS, *RP, *VAL;  // [64] each: S_j, positions of the located errors, their values
+};
+
+// acc[c] ^= lambda(alpha^-p): position p is in error iff the sum is 0 (cyclic.h:126-150)
+template <class View>
+__device__ __forceinline__ void locator_at_positions(const View &V, uint32_t cll, int deg, const uint32_t (&xinv)[4],
+                                                     uint32_t (&acc)[4]) {
+  uint32_t e[4] = {0, 0, 0, 0};
+  for (int m = 0; m <= deg; ++m) {
+    const uint32_t lm = __builtin_amdgcn_readlane(cll, m);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      acc[c] ^= V.term(lm, e[c]);
+      V.advance(e[c], xinv[c]);
+    }
+  }
+}
+
+// roots = the valid positions with acc = 0; rank = index of a root among the frame's roots; returns their number
+__device__ __forceinline__ int rank_roots(int lane, const bool (&valid)[4], const uint32_t (&acc)[4], uint32_t (&isroot)[4],
+                                          uint32_t (&rank)[4]) {
+  uint32_t count = 0;
+  const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    isroot[c] = (valid[c] && acc[c] == 0) ? 1u : 0u;
+    const unsigned long long mk = __ballot(isroot[c] != 0);
+    rank[c] = count + static_cast<uint32_t>(__builtin_popcountll(mk & below));
+    count += static_cast<uint32_t>(__builtin_popcountll(mk));
+  }
+  return static_cast<int>(count);
+}
+
+// error values of an RS frame by Forney (rs.h:41-78), one lane per located error; S.CSL holds the frame's log S_j
+template <bool TW, class View>
+__device__ __forceinline__ void forney_values(const View &V, const LogTables &Tb, const FixScratch &S, int lane, uint32_t cll,
+                                              int deg, int t2, int nn, int step, uint32_t twist, const uint32_t (&isroot)[4],
+                                              const uint32_t (&rank)[4], uint32_t (&corr)[4]) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+    if (isroot[c]) S.RP[rank[c]] = static_cast<uint8_t>(lane + 64 * c);
+  uint32_t om = 0;  // omega_j = sum_{m<=j} S_{j-m} lambda_m, j < deg
+  for (int m = 0; m <= deg; ++m) {
+    const uint32_t lm = __builtin_amdgcn_readlane(cll, m);
+    const bool in = lane >= m && lane < deg && lane - m < t2;
+    om ^= in ? Tb.ex[lm + S.CSL[in ? lane - m : 0]] : 0u;
+  }
+  const uint32_t oml = Tb.lg2[om];
+  uint32_t y = 0;
+  if (lane < deg) {
+    const uint32_t p = S.RP[lane], zl = TW ? (static_cast<uint32_t>(step) * p) % static_cast<uint32_t>(nn) : p;
+    const uint32_t xi = zl ? static_cast<uint32_t>(nn) - zl : 0u;  // log X^-1
+    uint32_t x2 = 2 * xi;
+    x2 = umin32(x2, x2 - static_cast<uint32_t>(nn));
+    uint32_t num = 0, den = 0, e = 0;
+    for (int j = 0; j < deg; ++j) {  // omega(X^-1)
+      num ^= V.term(__builtin_amdgcn_readlane(oml, j), e);
+      V.advance(e, xi);
+    }
+    e = 0;
+    for (int m = 1; m <= deg; m += 2) {  // lambda'(X^-1) = sum_{m odd} lambda_m X^-(m-1)
+      den ^= V.term(__builtin_amdgcn_readlane(cll, m), e);
+      V.advance(e, x2);
+    }
+    y = (num && den) ? Tb.ex[Tb.lg[num] + nn - Tb.lg[den]] : 0u;
+    if (TW) y = y ? Tb.ex[Tb.lg[y] + (twist * p) % static_cast<uint32_t>(nn)] : 0u;
+  }
+  S.VAL[lane] = static_cast<uint8_t>(y);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) corr[c] = isroot[c] ? S.VAL[rank[c]] : 0u;
+}
+
+// re-check (cyclic.h:243-248): do the syndromes of the correction equal the frame's (CS)?  Four per reduction.
+__device__ __forceinline__ bool recheck_mismatch(const LogTables &Tb, const uint8_t *CS, const uint32_t (&corr)[4],
+                                                 const uint32_t (&e0)[4], const uint32_t (&dstep)[4], int t2, int nn) {
+  uint32_t ly[4], ev[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    ly[c] = Tb.lg[corr[c]];
+    ev[c] = e0[c];
+  }
+  uint32_t mismatch = 0;
+  for (int j0 = 0; j0 < t2; j0 += 4) {
+    uint32_t packed = 0, want = 0;
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      uint32_t term = 0;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        term ^= corr[c] ? Tb.ex[ly[c] + ev[c]] : 0u;
+        ev[c] += dstep[c];
+        ev[c] = ev[c] >= static_cast<uint32_t>(nn) ? ev[c] - nn : ev[c];
+      }
+      if (j0 + jj < t2) {
+        packed |= term << (8 * jj);
+        want |= static_cast<uint32_t>(CS[j0 + jj]) << (8 * jj);
+      }
+    }
+    mismatch |= lane63(wave_xor(packed)) ^ want;
+  }
+  return mismatch != 0;
+}
+
+// the set bits of a mask, lowest first; -1 when none is left
+__device__ __forceinline__ int pop_lowest(unsigned long long &m) {
+  const int i = m ? __builtin_ctzll(m) : -1;
+  m &= m - 1;
+  return i;
+}
+
 struct ChunkLayout {  // byte offsets inside one wavefront's LDS region
-  int SL, LL, BL, SV, LV, DEG, LEN, CSL, CLL, OML, CS, RP, VAL, bytes;
+  int SL, LL, BL, SV, DEG, LEN, CSL, CS, RP, VAL, bytes;
 };
 __host__ __device__ inline ChunkLayout chunk_layout(int t2, int fpw) {
   ChunkLayout c;
@@ -37,23 +315,20 @@ __host__ __device__ inline ChunkLayout chunk_layout(int t2, int fpw) {
   c.LL = c.SL + 2 * t2 * fpw;    // u16 [nc][fpw]   log lambda_m
   c.BL = c.LL + 2 * nc * fpw;    // u16 [nc][fpw]   log b_m
   c.SV = c.BL + 2 * nc * fpw;    // u8  [t2][fpw]   S_j
-  c.LV = c.SV + t2 * fpw;        // u8  [nc][fpw]   lambda_m
-  c.DEG = c.LV + nc * fpw;       // u8  [fpw]       deg lambda
+  c.DEG = c.SV + t2 * fpw;       // u8  [fpw]       deg lambda
   c.LEN = c.DEG + fpw;           // u8  [fpw]       LFSR length L
   // stage C scratch for the frame being corrected (contiguous copies of its column)
   c.CSL = (c.LEN + fpw + 1) & ~1;  // u16 [64]   log S_j
-  c.CLL = c.CSL + 128;             // u16 [72]   log lambda_m
-  c.OML = c.CLL + 144;             // u16 [64]   log omega_j
-  c.CS = c.OML + 128;              // u8  [64]   S_j
+  // (272 bytes follow that held copies of log lambda and log omega nothing read -- both live in registers, lane m of
+  // cll / oml; the arrays behind keep their offsets)
+  c.CS = c.CSL + 128 + 272;        // u8  [64]   S_j
   c.RP = c.CS + 64;                // u8  [64]   positions of the located errors
   c.VAL = c.RP + 64;               // u8  [64]   their values
   c.bytes = (c.VAL + 64 + 15) & ~15;
   return c;
 }
 
-// TW: an RS code with roots alpha^(mu + i step) other than alpha^1 .. alpha^2t (algebraic.hip, DESIGN 4.9): roots tested
-// at Z^-1 = alpha^(-step p), Forney's quotient scaled by alpha^(twist p); TW = false is the code as it was
-template <bool FLOAT_IN, int FPW, bool TW>
+template <bool FLOAT_IN, int FPW, bool TW>  // TW: see position_exponents
 __global__ void __launch_bounds__(256, 4)
 algebraic_chunk_kernel(const AlgebraicTables *__restrict__ T, int alg, const void *__restrict__ in_raw,
                        uint8_t *__restrict__ out, int32_t *__restrict__ nerr_out, int32_t *__restrict__ status_out,
@@ -61,10 +336,10 @@ algebraic_chunk_kernel(const AlgebraicTables *__restrict__ T, int alg, const voi
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   uint8_t *ex = smem;                                            // [1024]
   uint16_t *lg2 = reinterpret_cast<uint16_t *>(smem + 1024);     // [256]
-  uint8_t *lg = smem + 1536;                                     // [256] plain log table (log 0 = 0), stages A / C
-  for (int i = threadIdx.x; i < 1024; i += 256) ex[i] = i < 512 ? T->exp[i] : 0;
-  lg2[threadIdx.x] = threadIdx.x ? T->log[threadIdx.x] : kLogZero;
-  lg[threadIdx.x] = T->log[threadIdx.x];
+  uint8_t *lg = smem + 1536;                                     // [256] stages A / C
+  stage_ex(T, ex);
+  stage_log16(T, lg2);
+  stage_log(T, lg);
   __syncthreads();
 
   const int dbg_stop = alg >> 8;  // timing experiments only (CC_AMD_ALG_STOP): 1 after syndromes, 2 after BM, 3 after roots
@@ -77,25 +352,14 @@ algebraic_chunk_kernel(const AlgebraicTables *__restrict__ T, int alg, const voi
   uint16_t *SL = reinterpret_cast<uint16_t *>(base + lay.SL);
   uint16_t *LL = reinterpret_cast<uint16_t *>(base + lay.LL);
   uint16_t *BL = reinterpret_cast<uint16_t *>(base + lay.BL);
-  uint8_t *SV = base + lay.SV, *LV = base + lay.LV, *DEG = base + lay.DEG, *LEN = base + lay.LEN;
-  uint16_t *CSL = reinterpret_cast<uint16_t *>(base + lay.CSL);
-  uint16_t *CLL = reinterpret_cast<uint16_t *>(base + lay.CLL);
-  uint8_t *CS = base + lay.CS, *RP = base + lay.RP, *VAL = base + lay.VAL;
+  uint8_t *SV = base + lay.SV, *DEG = base + lay.DEG, *LEN = base + lay.LEN;
+  const FixScratch S{reinterpret_cast<uint16_t *>(base + lay.CSL), base + lay.CS, base + lay.RP, base + lay.VAL};
+  const LogTables Tb{ex, lg2, lg};
+  const WrappedView V{ex, static_cast<uint32_t>(nn)};
 
-  // per-lane exponent bookkeeping (roots alpha^(r0 + j step)): position p = lane + 64 c
-  const int r0 = T->roots_log[0];
-  const int step = t2 > 1 ? (T->roots_log[1] + nn - r0) % nn : 0;
   uint32_t e0[4], dstep[4], xinv[4];
   bool valid[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const int p = lane + 64 * c;
-    valid[c] = p < n;
-    e0[c] = static_cast<uint32_t>((r0 * p) % nn);
-    dstep[c] = static_cast<uint32_t>((step * p) % nn);
-    xinv[c] = static_cast<uint32_t>((nn - (p % nn)) % nn);
-    if (TW) xinv[c] = (static_cast<uint32_t>(nn) - dstep[c]) % static_cast<uint32_t>(nn);  // log of Z^-1
-  }
+  const int step = position_exponents<TW>(T, lane, e0, dstep, xinv, valid);
   const uint32_t twist = TW ? static_cast<uint32_t>(T->twist) : 0u;
   uint32_t dk[4][4];  // (k + 1) * dstep mod nn, k = 0..3
 #pragma unroll
@@ -189,88 +453,22 @@ algebraic_chunk_kernel(const AlgebraicTables *__restrict__ T, int alg, const voi
     }
     __builtin_amdgcn_wave_barrier();
 
-    // ---------------- B: Berlekamp-Massey, one lane per frame (hard_decision.h:116-155) ----------------
+    // ---------------- B: Berlekamp-Massey, one lane per frame (bm_lds; no erasures on this chain) ----------------
     if (smask != 0) {  // wave-uniform
-      const int f = lane & (FPW - 1);
       const bool mine = lane < FPW && ((smask >> lane) & 1ull);
-      if (lane < FPW) {
-        for (int m = 0; m < nc; ++m) {  // lambda = b = 1
-          LV[m * FPW + f] = m == 0;
-          LL[m * FPW + f] = static_cast<uint16_t>(m == 0 ? 0 : kLogZero);
-          BL[m * FPW + f] = static_cast<uint16_t>(m == 0 ? 0 : kLogZero);
-        }
-      }
-      int l = 0, shift = 0;  // b is stored unshifted; b(x) x^shift is the polynomial of the recurrence
-      for (int i = 0; i < t2; ++i) {
-        shift += 1;  // b = b * x, :134
-        const int lw = static_cast<int>(wave_umax(mine ? static_cast<uint32_t>(l) : 0u));
-        // discrepancy :139-141; lambda_m = 0 (log 512) beyond its degree, so no per-lane bound is needed
-        uint32_t d = SV[i * FPW + f];
-        const int mm = i < lw ? i : lw;
-        // lambda_m = 0 (log 512) for m > L, and L <= i: running past mm in blocks of four adds zeros
-        for (int m0 = 1; m0 <= mm; m0 += 4) {
-          uint32_t la[4], sa[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int m = m0 + u < nc ? m0 + u : nc - 1;
-            la[u] = LL[m * FPW + f];
-            sa[u] = SL[(i - m > 0 ? i - m : 0) * FPW + f];
-          }
-#pragma unroll
-          for (int u = 0; u < 4; ++u) d ^= ex[la[u] + sa[u]];
-        }
-        const bool upd = mine && d != 0;
-        const bool grow = upd && 2 * l <= i;  // :145 (rho = 0)
-        const uint32_t ld = lg2[d];
-        const uint32_t linv = static_cast<uint32_t>(nn) - ld;  // log of d^-1 (or nn for d = 1: wrapped below)
-        const int lnew = grow ? i + 1 - l : l;
-        const int cap = static_cast<int>(wave_umax(upd ? static_cast<uint32_t>(lnew) : 0u));
-        if (__any(upd)) {
-          // lambda += d * b * x^shift, and where the register grows b := lambda_old / d; descending m so that the
-          // shifted reads of the old b (index m - shift < m) happen before that index is overwritten
-          for (int m = cap; m >= 0; --m) {
-            const uint32_t lold = LL[m * FPW + f];
-            const uint32_t lv = LV[m * FPW + f];
-            const int bi = m - shift;
-            const uint32_t bt = bi >= 0 ? BL[(bi >= 0 ? bi : 0) * FPW + f] : kLogZero;
-            const uint32_t nv = lv ^ ex[ld + bt];
-            if (upd) {
-              LV[m * FPW + f] = static_cast<uint8_t>(nv);
-              LL[m * FPW + f] = lg2[nv];
-            }
-            if (grow) {
-              uint32_t q = lold + linv;
-              q = q >= static_cast<uint32_t>(nn) ? q - nn : q;
-              BL[m * FPW + f] = static_cast<uint16_t>(lold >= kLogZero ? kLogZero : q);
-            }
-          }
-        }
-        if (grow) {
-          l = lnew;
-          shift = 0;
-        }
-      }
+      int deg;
+      const int l = bm_lds<FPW>(ex, lg2, SL, LL, BL, t2, nn, mine, 0u, nullptr, 0u, deg);
       if (mine) {
-        int deg = 0;
-        for (int m = t2; m >= 1; --m)
-          if (deg == 0 && LV[m * FPW + f] != 0) deg = m;
-        DEG[f] = static_cast<uint8_t>(deg);
-        LEN[f] = static_cast<uint8_t>(l);
+        DEG[lane] = static_cast<uint8_t>(deg);
+        LEN[lane] = static_cast<uint8_t>(l);
       }
     }
     __builtin_amdgcn_wave_barrier();
 
     // ---------------- C: roots, error values, re-check, store ----------------
-    // All polynomial arithmetic on logs with log 0 = 512 (no zero tests): a term lambda_m X^-m is
-    // ex[log lambda_m + (m * log X^-1 mod nn)], the exponent advancing by one add + one wrap per coefficient.
     // only frames with a non-zero syndrome are visited (the others were stored in stage A); two in flight
-    auto pop = [](unsigned long long &m) {
-      const int i = m ? __builtin_ctzll(m) : -1;
-      m &= m - 1;
-      return i;
-    };
     unsigned long long todo = smask;
-    int s0 = pop(todo), s1 = pop(todo);
+    int s0 = pop_lowest(todo), s1 = pop_lowest(todo);
     uint32_t q0[4] = {0, 0, 0, 0}, q1[4] = {0, 0, 0, 0};
     if (s0 >= 0) load_symbols(first + s0, q0);
     if (s1 >= 0) load_symbols(first + s1, q1);
@@ -284,119 +482,35 @@ algebraic_chunk_kernel(const AlgebraicTables *__restrict__ T, int alg, const voi
         q0[c] = q1[c];
       }
       s0 = s1;
-      s1 = pop(todo);
+      s1 = pop_lowest(todo);
       if (s1 >= 0) load_symbols(first + s1, q1);
-      int status = CC_FRAME_OK, nerr = 0;
+      int status, nerr = 0;
       {
         const int deg = DEG[s], len = LEN[s];
         // column s of the chunk arrays -> contiguous scratch (the strided reads conflict, do them once)
         if (lane < t2) {
-          CS[lane] = SV[lane * FPW + s];
-          CSL[lane] = SL[lane * FPW + s];
+          S.CS[lane] = SV[lane * FPW + s];
+          S.CSL[lane] = SL[lane * FPW + s];
         }
-        for (int m = lane; m < nc; m += 64) CLL[m] = LL[m * FPW + s];
         const uint32_t cll = LL[(lane < nc ? lane : 0) * FPW + s];  // log lambda_lane, read by readlane (nc <= 64)
-        // the PGZ tag runs as bounded-distance decoding: locator degree within capability
-        if (alg != CC_ALG_BM && 2 * deg > t2) status = CC_FRAME_LOCATOR;
-        if (deg < 1) status = CC_FRAME_LOCATOR;  // cyclic.h:145-147
-        if (dbg_stop == 2) status = CC_FRAME_LOCATOR;
-
-        // root search: position p is in error iff lambda(alpha^-p) = 0  (cyclic.h:126-150)
+        status = chain::locator_status(alg, deg, 0, t2, dbg_stop);
         uint32_t isroot[4] = {0, 0, 0, 0}, rank[4] = {0, 0, 0, 0};
         if (status == CC_FRAME_OK) {
-          uint32_t acc[4] = {0, 0, 0, 0}, e[4] = {0, 0, 0, 0};
-          for (int m = 0; m <= deg; ++m) {
-            const uint32_t lm = __builtin_amdgcn_readlane(cll, m);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              acc[c] ^= ex[lm + e[c]];
-              e[c] += xinv[c];
-              e[c] = umin32(e[c], e[c] - static_cast<uint32_t>(nn));
-            }
-          }
-          uint32_t count = 0;
-          const unsigned long long below = (1ull << lane) - 1ull;
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            isroot[c] = (valid[c] && acc[c] == 0) ? 1u : 0u;
-            const unsigned long long mk = __ballot(isroot[c] != 0);
-            rank[c] = count + static_cast<uint32_t>(__builtin_popcountll(mk & below));
-            count += static_cast<uint32_t>(__builtin_popcountll(mk));
-          }
-          nerr = static_cast<int>(count);
+          uint32_t acc[4] = {0, 0, 0, 0};
+          locator_at_positions(V, cll, deg, xinv, acc);
+          nerr = rank_roots(lane, valid, acc, isroot, rank);
           if (nerr != deg) status = CC_FRAME_LOCATOR;  // cyclic.h:134-143
         }
         if (dbg_stop == 3) status = CC_FRAME_LOCATOR;
-
-        // error values: bch.h:80-83 (all ones) / Forney for rs.h:41-78, one lane per located error
+        // error values: bch.h:80-83 (all ones) / Forney for rs.h:41-78
         if (status == CC_FRAME_OK && is_rs) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c)
-            if (isroot[c]) RP[rank[c]] = static_cast<uint8_t>(lane + 64 * c);
-          uint32_t om = 0;  // omega_j = sum_{m<=j} S_{j-m} lambda_m, j < deg
-          for (int m = 0; m <= deg; ++m) {
-            const uint32_t lm = __builtin_amdgcn_readlane(cll, m);
-            const bool in = lane >= m && lane < deg && lane - m < t2;
-            om ^= in ? ex[lm + CSL[in ? lane - m : 0]] : 0u;
-          }
-          const uint32_t oml = lg2[om];
-          uint32_t y = 0;
-          if (lane < deg) {
-            const uint32_t p = RP[lane], zl = TW ? (static_cast<uint32_t>(step) * p) % static_cast<uint32_t>(nn) : p;
-            const uint32_t xi = zl ? static_cast<uint32_t>(nn) - zl : 0u;  // log X^-1
-            uint32_t x2 = 2 * xi;
-            x2 = umin32(x2, x2 - static_cast<uint32_t>(nn));
-            uint32_t num = 0, den = 0, e = 0;
-            for (int j = 0; j < deg; ++j) {  // omega(X^-1)
-              num ^= ex[__builtin_amdgcn_readlane(oml, j) + e];
-              e += xi;
-              e = umin32(e, e - static_cast<uint32_t>(nn));
-            }
-            e = 0;
-            for (int m = 1; m <= deg; m += 2) {  // lambda'(X^-1) = sum_{m odd} lambda_m X^-(m-1)
-              den ^= ex[__builtin_amdgcn_readlane(cll, m) + e];
-              e += x2;
-              e = umin32(e, e - static_cast<uint32_t>(nn));
-            }
-            y = (num && den) ? ex[lg[num] + nn - lg[den]] : 0u;
-            if (TW) y = y ? ex[lg[y] + (twist * p) % static_cast<uint32_t>(nn)] : 0u;
-          }
-          VAL[lane] = static_cast<uint8_t>(y);
-#pragma unroll
-          for (int c = 0; c < 4; ++c) corr[c] = isroot[c] ? VAL[rank[c]] : 0u;
+          forney_values<TW>(V, Tb, S, lane, cll, deg, t2, nn, step, twist, isroot, rank, corr);
         } else if (status == CC_FRAME_OK) {
 #pragma unroll
           for (int c = 0; c < 4; ++c) corr[c] = isroot[c];
         }
-        // re-check (cyclic.h:243-248): decided by L = deg lambda (proof in algebraic.hip), evaluated otherwise
-        if (status == CC_FRAME_OK && len != deg) {
-          uint32_t ly[4], ev[4];
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            ly[c] = lg[corr[c]];
-            ev[c] = e0[c];
-          }
-          uint32_t mismatch = 0;
-          for (int j0 = 0; j0 < t2; j0 += 4) {
-            uint32_t packed = 0, want = 0;
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-              uint32_t term = 0;
-#pragma unroll
-              for (int c = 0; c < 4; ++c) {
-                term ^= corr[c] ? ex[ly[c] + ev[c]] : 0u;
-                ev[c] += dstep[c];
-                ev[c] = ev[c] >= static_cast<uint32_t>(nn) ? ev[c] - nn : ev[c];
-              }
-              if (j0 + jj < t2) {
-                packed |= term << (8 * jj);
-                want |= static_cast<uint32_t>(CS[j0 + jj]) << (8 * jj);
-              }
-            }
-            mismatch |= lane63(wave_xor(packed)) ^ want;
-          }
-          if (mismatch != 0) status = CC_FRAME_RECHECK;
-        }
+        // re-check: decided by L = deg lambda (proof in algebraic.hip), evaluated otherwise
+        if (status == CC_FRAME_OK && len != deg && recheck_mismatch(Tb, S.CS, corr, e0, dstep, t2, nn)) status = CC_FRAME_RECHECK;
       }
       const bool ok = status == CC_FRAME_OK;
 #pragma unroll
@@ -430,6 +544,56 @@ __host__ __device__ inline BmLayout bm_layout(int t2) {
   return c;
 }
 
+// The start of a chunk in both Berlekamp-Massey kernels, lane = frame: the lane's syndromes from HBM (keep(j, S_j);
+// UNROLL trips of the loop at a time), the mask of the frames to solve -- written to mask[chunk] and returned -- and
+// the settling of the others: a codeword is done (cyclic.h:225-231), a frame with more erasures than 2t (too_many)
+// cannot be located (bch.h:105-107).
+template <int UNROLL, class Keep>
+__device__ __forceinline__ unsigned long long chunk_prologue(const uint8_t *__restrict__ synd, int t2, unsigned long long chunk,
+                                                             int frames, int dbg_stop, bool too_many,
+                                                             unsigned long long *__restrict__ mask, int32_t *__restrict__ nerr_out,
+                                                             int32_t *__restrict__ status_out, Keep keep) {
+  const int f = threadIdx.x & 63;
+  const unsigned long long first = chunk * 64;
+  const uint8_t *src = synd + chain::synd_byte(2 * chunk + (f >> 5), f & 31, 0, t2);
+  uint32_t any = 0;
+#pragma unroll UNROLL
+  for (int j = 0; j < t2; ++j) {
+    const uint32_t v = src[j * chain::kSyndStride];
+    keep(j, v);
+    any |= v;
+  }
+  const unsigned long long smask = dbg_stop == 1 ? 0ull : __ballot(any != 0 && f < frames && !too_many);
+  if (f < frames && !((smask >> f) & 1ull)) {
+    const bool refused = any != 0 && too_many;
+    if (nerr_out) nerr_out[first + f] = refused ? -1 : 0;
+    if (status_out) status_out[first + f] = refused ? CC_FRAME_ERASURES : CC_FRAME_OK;
+  }
+  if (f == 0) mask[chunk] = smask;
+  return smask;
+}
+
+// lambda_0 .. lambda_(ncoef - 1) of a chunk as planes for the Chien kernel (chain::lamp_row), from their values as bytes
+// LV[m][64]: lane (m, half) takes the 32 bytes of coefficient m of one group as eight dwords (word j = frames 4j .. 4j+3)
+// through the butterfly, which is what puts frame f of the group on bit chain::plane_bit(f) of a plane
+__device__ __forceinline__ void export_locator_planes(const uint8_t *LV, uint4 *__restrict__ lamp, unsigned long long chunk,
+                                                      int ncoef, int nc) {
+  const int lane = threadIdx.x & 63;
+  if (lane < 2 * ncoef) {
+    const int m = lane >> 1, half = lane & 1;
+    uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (m < nc) {
+      const uint4 *row = reinterpret_cast<const uint4 *>(LV + m * 64 + 32 * half);
+      const uint4 a = row[0], b = row[1];
+      w[0] = a.x, w[1] = a.y, w[2] = a.z, w[3] = a.w, w[4] = b.x, w[5] = b.y, w[6] = b.z, w[7] = b.w;
+      bitplane::butterfly(w);
+    }
+    uint4 *dst = lamp + chain::lamp_row(2 * chunk + half, m, ncoef);
+    dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+  }
+}
+
 // Everything in the log domain (log 0 = 512, antilog table zero above 510): 12.3 KB of LDS per wavefront for 2t = 32,
 // three wavefronts per SIMD -- the stage is bound by the latency of its dependent LDS operations, so occupancy is
 // what it is sized for.
@@ -443,10 +607,10 @@ chunk_bm_kernel(const AlgebraicTables *__restrict__ T, int dbg_stop, const uint8
   if (blockIdx.x == 0 && threadIdx.x == 0) *nleft = 0;  // chunks chunk_fixl_kernel will hand on (it runs after this kernel)
   uint8_t *ex = smem;                                         // [1024]
   uint16_t *lg2 = reinterpret_cast<uint16_t *>(smem + 1024);  // [256]
-  for (int i = threadIdx.x; i < 1024; i += 256) ex[i] = i < 512 ? T->exp[i] : 0;
-  lg2[threadIdx.x] = threadIdx.x ? T->log[threadIdx.x] : kLogZero;
+  stage_ex(T, ex);
+  stage_log16(T, lg2);
   __syncthreads();
-  constexpr int FPW = 64, U = 4;  // U coefficients per trip of the two inner loops (8: measured slower)
+  constexpr int FPW = 64;
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), f = lane;
   const int nn = T->nf, t2 = T->nroots, nc = t2 + 1;
   const BmLayout lay = bm_layout(t2);
@@ -461,136 +625,26 @@ chunk_bm_kernel(const AlgebraicTables *__restrict__ T, int dbg_stop, const uint8
   for (unsigned long long chunk = wave; chunk < nchunks; chunk += nwaves) {
     const unsigned long long first = chunk * FPW;
     const int frames = static_cast<int>((B - first) < static_cast<unsigned long long>(FPW) ? (B - first) : FPW);
-    // syndromes of frame 8i + k of group g: byte 4k + i of [block of 64 groups][j][group in block][32]
-    const unsigned long long group = 2 * chunk + (f >> 5);
-    const int fi = f & 31;
-    const uint8_t *src = synd + ((group >> 6) * t2 * 64 + (group & 63)) * 32 + 4 * (fi & 7) + (fi >> 3);
-    uint32_t any = 0;
-#pragma unroll 8
-    for (int j = 0; j < t2; ++j) {
-      const uint32_t v = src[j * 2048];
-      SL[j * FPW + f] = lg2[v];
-      any |= v;
-    }
     // erasures of the lane's frame (CSR; none without the arrays): more than 2t cannot be located (bch.h:105-107)
     uint32_t rho = 0, ebase = 0;
     if (er_off != nullptr && f < frames) {
       ebase = er_off[first + f];
       rho = er_off[first + f + 1] - ebase;
     }
-    const bool too_many = rho > static_cast<uint32_t>(t2);
-    const unsigned long long smask = dbg_stop == 1 ? 0ull : __ballot(any != 0 && f < frames && !too_many);
-    const bool mine = (smask >> lane) & 1ull;
-    if (f < frames && !mine) {  // a codeword: done (cyclic.h:225-231) -- or settled as "too many erasures"
-      const bool refused = any != 0 && too_many;
-      if (nerr_out) nerr_out[first + f] = refused ? -1 : 0;
-      if (status_out) status_out[first + f] = refused ? CC_FRAME_ERASURES : CC_FRAME_OK;
-    }
-    if (lane == 0) mask[chunk] = smask;
+    const unsigned long long smask =
+        chunk_prologue<8>(synd, t2, chunk, frames, dbg_stop, rho > static_cast<uint32_t>(t2), mask, nerr_out, status_out,
+                          [&](int j, uint32_t v) { SL[j * FPW + f] = lg2[v]; });
     if (smask == 0) continue;  // wave-uniform
 
-    // Berlekamp-Massey, one lane per frame (hard_decision.h:116-155)
-    for (int m = 0; m < nc; ++m) LL[m * FPW + f] = static_cast<uint16_t>(m == 0 ? 0 : kLogZero);  // lambda = 1
-    // lambda *= (1 + alpha^p x) for every erased position p, :128-131; the recurrence then starts at i = rho with
-    // b = lambda and L = rho
-    const int rmax = static_cast<int>(wave_umax(mine ? rho : 0u));
-    for (int e = 0; e < rmax; ++e) {
-      const bool act = mine && static_cast<uint32_t>(e) < rho;
-      const uint32_t px = act ? static_cast<uint32_t>(er[ebase + e]) % static_cast<uint32_t>(nn) : 0u;
-      for (int m = e + 1; m >= 1; --m) {
-        const uint32_t nv = ex[LL[m * FPW + f]] ^ ex[LL[(m - 1) * FPW + f] + px];
-        if (act) LL[m * FPW + f] = lg2[nv];
-      }
-    }
-    for (int m = 0; m < nc; ++m) BL[m * FPW + f] = LL[m * FPW + f];
-    const int irho = static_cast<int>(rho);
-    int l = irho, shift = 0;  // b is stored unshifted; b(x) x^shift is the polynomial of the recurrence
-    int lw = rmax;            // longest register in the wavefront: max(lw, cap) after every step (cap covers all that grew)
-    for (int i = 0; i < t2; ++i) {
-      const bool started = i >= irho;  // (a lane with erasures joins at step rho)
-      shift += started ? 1 : 0;        // b = b * x, :134
-      uint32_t d = ex[SL[i * FPW + f]];
-      const int mm = i < lw ? i : lw;
-      // discrepancy :139-141; lambda_m = 0 (log 512) for m > L, and L <= i: running past mm in blocks of U adds zeros
-      for (int m0 = 1; m0 <= mm; m0 += U) {
-        uint32_t la[U], sa[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int m = m0 + u < nc ? m0 + u : nc - 1;
-          la[u] = LL[m * FPW + f];
-          sa[u] = SL[(i - m > 0 ? i - m : 0) * FPW + f];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) d ^= ex[la[u] + sa[u]];
-      }
-      const bool upd = mine && started && d != 0;
-      const bool grow = upd && 2 * l <= i + irho;  // :145
-      const uint32_t ld = lg2[d];
-      const uint32_t linv = static_cast<uint32_t>(nn) - ld;  // log of d^-1 (or nn for d = 1: wrapped below)
-      const int lnew = grow ? i + irho + 1 - l : l;
-      const int cap = static_cast<int>(wave_umax(upd ? static_cast<uint32_t>(lnew) : 0u));
-      if (__any(upd)) {
-        // lambda += d * b * x^shift, and where the register grows b := lambda_old / d; descending m so that the
-        // shifted reads of the old b (index m - shift < m) happen before that index is overwritten.
-        // U coefficients per trip, all reads before the look-ups before the writes: a read of b at m - shift
-        // always precedes the write of that index in the sequential order too.
-        for (int m1 = cap; m1 >= 0; m1 -= U) {
-          uint32_t lold[U], bt[U], nv[U], ln[U];
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            const int m = m1 - u > 0 ? m1 - u : 0, bi = m1 - u - shift;
-            lold[u] = LL[m * FPW + f];
-            bt[u] = bi >= 0 ? BL[(bi >= 0 ? bi : 0) * FPW + f] : kLogZero;
-          }
-#pragma unroll
-          for (int u = 0; u < U; ++u) nv[u] = ex[lold[u]] ^ ex[ld + bt[u]];
-#pragma unroll
-          for (int u = 0; u < U; ++u) ln[u] = lg2[nv[u]];
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            const int m = m1 - u;
-            if (m < 0) break;  // wave-uniform
-            if (upd) LL[m * FPW + f] = static_cast<uint16_t>(ln[u]);
-            if (grow) {
-              uint32_t q = lold[u] + linv;
-              q = q >= static_cast<uint32_t>(nn) ? q - nn : q;
-              BL[m * FPW + f] = static_cast<uint16_t>(lold[u] >= kLogZero ? kLogZero : q);
-            }
-          }
-        }
-      }
-      if (grow) {
-        l = lnew;
-        shift = 0;
-      }
-      lw = cap > lw ? cap : lw;
-    }
-    int deg = 0;
-    for (int m = t2; m >= 1; --m)
-      if (deg == 0 && LL[m * FPW + f] != kLogZero) deg = m;
+    int deg;
+    const int l = bm_lds<FPW>(ex, lg2, SL, LL, BL, t2, nn, (smask >> lane) & 1ull, rho, er, ebase, deg);
     if (f < frames) meta[first + f] = static_cast<uint16_t>(deg | (l << 8));
     for (int m = 0; m < nc; ++m) llg[(chunk * nc + m) * FPW + f] = LL[m * FPW + f];
-    // lambda_0 .. lambda_16 as planes for the Chien kernel ([block of 64 groups][m][group][8]): the values go to the
-    // (now free) b area as bytes [m][64]; lane (m, half) takes the 32 bytes of coefficient m of one group as eight
-    // dwords (word j = frames 4j .. 4j+3) through the butterfly, so bit 8 (f & 3) + (f >> 2) of a plane belongs to
-    // frame f of the group
-    uint8_t *LV = reinterpret_cast<uint8_t *>(BL);
+    // the values of lambda_0 .. for the plane export go to the (now free) b area as bytes [m][64]
     // (ncoef = 17 coefficients for the root search on planes, 25 for calls with erasures: bitslice.hip)
+    uint8_t *LV = reinterpret_cast<uint8_t *>(BL);
     for (int m = 0; m < ncoef && m < nc; ++m) LV[m * FPW + f] = ex[LL[m * FPW + f]];
-    if (lane < 2 * ncoef) {
-      const int m = lane >> 1, half = lane & 1;
-      uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (m < nc) {
-        const uint4 *row = reinterpret_cast<const uint4 *>(LV + m * FPW + 32 * half);
-        const uint4 a = row[0], b = row[1];
-        w[0] = a.x, w[1] = a.y, w[2] = a.z, w[3] = a.w, w[4] = b.x, w[5] = b.y, w[6] = b.z, w[7] = b.w;
-        bitplane::butterfly(w);
-      }
-      const unsigned long long g = 2 * chunk + half;
-      uint4 *dst = lamp + (((g >> 6) * ncoef + m) * 64 + (g & 63)) * 2;
-      dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
-      dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
-    }
+    export_locator_planes(LV, lamp, chunk, ncoef, nc);
   }
 }
 
@@ -621,8 +675,8 @@ chunk_bm_reg_kernel(const AlgebraicTables *__restrict__ T, int dbg_stop, const u
   if (blockIdx.x == 0 && threadIdx.x == 0) *nleft = 0;
   uint8_t *ex = smem;                                         // [1024]
   uint16_t *lg2 = reinterpret_cast<uint16_t *>(smem + 1024);  // [256]
-  for (int i = threadIdx.x; i < 1024; i += 256) ex[i] = i < 512 ? T->exp[i] : 0;
-  lg2[threadIdx.x] = threadIdx.x ? T->log[threadIdx.x] : kLogZero;
+  stage_ex(T, ex);
+  stage_log16(T, lg2);
   __syncthreads();
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), f = lane;
   const uint32_t nn = static_cast<uint32_t>(T->nf);
@@ -634,26 +688,12 @@ chunk_bm_reg_kernel(const AlgebraicTables *__restrict__ T, int dbg_stop, const u
   for (unsigned long long chunk = wave; chunk < nchunks; chunk += nwaves) {
     const unsigned long long first = chunk * FPW;
     const int frames = static_cast<int>((B - first) < static_cast<unsigned long long>(FPW) ? (B - first) : FPW);
-    const unsigned long long group = 2 * chunk + (f >> 5);
-    const int fi = f & 31;
-    const uint8_t *src = synd + ((group >> 6) * T2 * 64 + (group & 63)) * 32 + 4 * (fi & 7) + (fi >> 3);
     uint32_t sl[T2];  // log S_j
-    uint32_t any = 0;
-#pragma unroll
-    for (int j = 0; j < T2; ++j) {
-      const uint32_t v = src[j * 2048];
-      any |= v;
-      sl[j] = v;
-    }
+    const unsigned long long smask = chunk_prologue<T2>(synd, T2, chunk, frames, dbg_stop, false, mask, nerr_out, status_out,
+                                                        [&](int j, uint32_t v) { sl[j] = v; });
 #pragma unroll
     for (int j = 0; j < T2; ++j) sl[j] = lg2[sl[j]];
-    const unsigned long long smask = dbg_stop == 1 ? 0ull : __ballot(any != 0 && f < frames);
     const bool mine = (smask >> lane) & 1ull;
-    if (f < frames && !mine) {  // a codeword: done (cyclic.h:225-231)
-      if (nerr_out) nerr_out[first + f] = 0;
-      if (status_out) status_out[first + f] = CC_FRAME_OK;
-    }
-    if (lane == 0) mask[chunk] = smask;
     if (smask == 0) continue;  // wave-uniform
 
     uint32_t ll[NC], P[NC];  // log lambda_m; log of B's coefficients, renamed every step
@@ -717,31 +757,16 @@ chunk_bm_reg_kernel(const AlgebraicTables *__restrict__ T, int dbg_stop, const u
     if (f < frames) meta[first + f] = static_cast<uint16_t>(deg | (l << 8));
 #pragma unroll
     for (int m = 0; m < NC; ++m) llg[(chunk * NC + m) * FPW + f] = static_cast<uint16_t>(ll[m]);
-    // lambda_0 .. lambda_16 as planes for the Chien kernel (see chunk_bm_kernel)
+    // lambda_0 .. lambda_16 as planes for the Chien kernel
 #pragma unroll
     for (int m = 0; m < 17 && m < NC; ++m) LV[m * FPW + f] = ex[ll[m]];
-    if (lane < 2 * 17) {
-      const int m = lane >> 1, half = lane & 1;
-      uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (m < NC) {
-        const uint4 *row = reinterpret_cast<const uint4 *>(LV + m * FPW + 32 * half);
-        const uint4 a = row[0], b = row[1];
-        w[0] = a.x, w[1] = a.y, w[2] = a.z, w[3] = a.w, w[4] = b.x, w[5] = b.y, w[6] = b.z, w[7] = b.w;
-        bitplane::butterfly(w);
-      }
-      const unsigned long long g = 2 * chunk + half;
-      uint4 *dst = lamp + (((g >> 6) * 17 + m) * 64 + (g & 63)) * 2;
-      dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
-      dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
-    }
+    export_locator_planes(LV, lamp, chunk, 17, NC);
     __builtin_amdgcn_wave_barrier();
   }
 }
 
 // roots, error values, re-check and the patch of `out` (which already holds the received words), one dirty frame
-// of a 64-frame chunk at a time.  All polynomial arithmetic on logs with log 0 = 512 (no zero tests): a term
-// lambda_m X^-m is ex[log lambda_m + (m * log X^-1 mod nn)], the exponent advancing by one add + one wrap per
-// coefficient; wave-uniform coefficients come from a register by v_readlane, not from LDS.
+// of a 64-frame chunk at a time: the correction stage above on the long antilog table, exponents never wrapped.
 // IL: `out` holds symbol-interleaved blocks of depth il = alg >> 16: symbol p of frame f is byte
 // (f / il) il n + p il + f % il instead of f n + p (the depth travels in `alg`, so the kernel arguments of the plain
 // instantiations stay what they were)
@@ -754,18 +779,16 @@ chunk_fix_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t *
                  uint8_t *__restrict__ out, int32_t *__restrict__ nerr_out, int32_t *__restrict__ status_out,
                  unsigned long long B) {
   if (nleft && *nleft == 0) return;  // nothing was handed on by chunk_fixl_kernel (the usual case)
-  // exl: antilog table long enough for a Horner / Chien exponent that is never wrapped -- index = log of the
-  // coefficient (<= 254, or kLongZero for a zero coefficient) + up to 32 steps of <= 254; zero above kLongZero
-  constexpr uint32_t kLongZero = 8448, kLongSize = 16640;
+  constexpr uint32_t kLongSize = 16640;
   __shared__ __attribute__((aligned(16))) uint8_t smem[1792 + 4 * 320 + kLongSize];
   uint8_t *ex = smem;                                         // [1024]
   uint16_t *lg2 = reinterpret_cast<uint16_t *>(smem + 1024);  // [256]
-  uint8_t *lg = smem + 1536;                                  // [256] plain log table (log 0 = 0)
+  uint8_t *lg = smem + 1536;                                  // [256]
   uint8_t *exl = smem + 1792 + 4 * 320;
-  for (uint32_t i = threadIdx.x; i < kLongSize; i += 256) exl[i] = i < kLongZero ? T->exp[i % 255u] : 0;
-  for (int i = threadIdx.x; i < 1024; i += 256) ex[i] = i < 512 ? T->exp[i] : 0;
-  lg2[threadIdx.x] = threadIdx.x ? T->log[threadIdx.x] : kLogZero;
-  lg[threadIdx.x] = T->log[threadIdx.x];
+  stage_exl(T, exl, kLongSize);
+  stage_ex(T, ex);
+  stage_log16(T, lg2);
+  stage_log(T, lg);
   __syncthreads();
   unsigned long long il = 1;
   if constexpr (IL) {
@@ -778,22 +801,13 @@ chunk_fix_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t *
   const int n = T->n, nn = T->nf, t2 = T->nroots, nc = t2 + 1;
   const bool is_rs = T->family == CC_FAMILY_RS;
   uint8_t *base = smem + 1792 + wid * 320;
-  uint16_t *CSL = reinterpret_cast<uint16_t *>(base);  // u16 [64] log S_j
-  uint8_t *CS = base + 128, *RP = base + 192, *VAL = base + 256;
+  const FixScratch S{reinterpret_cast<uint16_t *>(base), base + 128, base + 192, base + 256};
+  const LogTables Tb{ex, lg2, lg};
+  const LongView V{exl};
 
-  const int r0 = T->roots_log[0];
-  const int step = t2 > 1 ? (T->roots_log[1] + nn - r0) % nn : 0;
   uint32_t e0[4], dstep[4], xinv[4];
   bool valid[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const int p = lane + 64 * c;
-    valid[c] = p < n;
-    e0[c] = static_cast<uint32_t>((r0 * p) % nn);
-    dstep[c] = static_cast<uint32_t>((step * p) % nn);
-    xinv[c] = static_cast<uint32_t>((nn - (p % nn)) % nn);
-    if (TW) xinv[c] = (static_cast<uint32_t>(nn) - dstep[c]) % static_cast<uint32_t>(nn);  // log of Z^-1
-  }
+  const int step = position_exponents<TW>(T, lane, e0, dstep, xinv, valid);
   const uint32_t twist = TW ? static_cast<uint32_t>(T->twist) : 0u;
 
   const unsigned long long nchunks = (B + 63) / 64;
@@ -804,25 +818,18 @@ chunk_fix_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t *
     const unsigned long long first = chunk * 64;
     unsigned long long todo = mask[chunk];
     if (todo == 0) continue;
-    // root masks of the chunk's two groups (bitslice_chien_kernel): word p of a group, bit 8 (f & 3) + (f >> 2) = frame f
+    // root masks of the chunk's two groups (bitslice_chien_kernel): word p of a group, one bit per frame
     uint32_t rw[2][4];
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
-      for (int c = 0; c < 4; ++c) rw[h][c] = roots[(2 * chunk + h) * 256 + lane + 64 * c];
-    auto pop = [](unsigned long long &m) {
-      const int i = m ? __builtin_ctzll(m) : -1;
-      m &= m - 1;
-      return i;
-    };
+      for (int c = 0; c < 4; ++c) rw[h][c] = roots[chain::roots_word(2 * chunk + h, lane + 64 * c)];
     auto fetch = [&](int f, uint32_t &sv, uint32_t &cll, uint32_t &md) {
-      const unsigned long long group = 2 * chunk + (f >> 5);
-      const int fi = f & 31;
-      sv = synd[((group >> 6) * t2 * 64 + (group & 63)) * 32 + 4 * (fi & 7) + (fi >> 3) + jl * 2048];
+      sv = synd[chain::synd_byte(2 * chunk + (f >> 5), f & 31, 0, t2) + jl * chain::kSyndStride];
       cll = llg[(chunk * nc + ml) * 64 + f];
       md = meta[first + f];
     };
-    int s0 = pop(todo);
+    int s0 = pop_lowest(todo);
     uint32_t sv0 = 0, cll0 = 0, md0 = 0;
     if (s0 >= 0) fetch(s0, sv0, cll0, md0);
     while (s0 >= 0) {
@@ -832,51 +839,28 @@ chunk_fix_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t *
       if constexpr (IL) fb = (frame / il) * il * n + frame % il;
       const uint32_t sv = sv0, cll = cll0;
       const int deg = __builtin_amdgcn_readfirstlane(md0) & 0xFF, len = __builtin_amdgcn_readfirstlane(md0) >> 8;
-      s0 = pop(todo);
+      s0 = pop_lowest(todo);
       if (s0 >= 0) fetch(s0, sv0, cll0, md0);  // the next frame's operands travel while this one is worked on
       uint32_t sym[4] = {0, 0, 0, 0}, corr[4] = {0, 0, 0, 0};
-      int status = CC_FRAME_OK, nerr = 0;
+      int nerr = 0;
       if (lane < t2) {
-        CS[lane] = static_cast<uint8_t>(sv);
-        CSL[lane] = lg2[sv];
+        S.CS[lane] = static_cast<uint8_t>(sv);
+        S.CSL[lane] = lg2[sv];
       }
-      // the PGZ / Euklid tags run as bounded-distance decoding: locator degree within capability, (2t + rho) / 2
       const int rho = er_off ? static_cast<int>(er_off[frame + 1] - er_off[frame]) : 0;  // wave-uniform
-      // (erasures reach this chain with the BM tag only: Euklid's integer stop rule, hard_decision.h:176, lets its locator
-      //  be one longer than the capability when rho is odd, and there its answer is not Berlekamp-Massey's)
-      if (alg != CC_ALG_BM && 2 * deg - rho > t2) status = CC_FRAME_LOCATOR;
-      if (deg < 1) status = CC_FRAME_LOCATOR;  // cyclic.h:145-147
-      if (dbg_stop == 2) status = CC_FRAME_LOCATOR;
+      int status = chain::locator_status(alg, deg, rho, t2, dbg_stop);
 
-      // root search: position p is in error iff lambda(alpha^-p) = 0  (cyclic.h:126-150)
       uint32_t isroot[4] = {0, 0, 0, 0}, rank[4] = {0, 0, 0, 0};
       if (status == CC_FRAME_OK) {
         uint32_t acc[4] = {0, 0, 0, 0};
         if (deg <= plane_deg) {  // searched on planes already (16, or 24 for calls with erasures)
-          const int fi = s & 31, bit = 8 * (fi & 3) + (fi >> 2);
+          const int bit = chain::plane_bit(s & 31);
 #pragma unroll
           for (int c = 0; c < 4; ++c) acc[c] = (((s >> 5) ? rw[1][c] : rw[0][c]) >> bit) & 1u ? 0u : 1u;
         } else {
-          uint32_t e[4] = {0, 0, 0, 0};
-          for (int m = 0; m <= deg; ++m) {
-            const uint32_t l0 = __builtin_amdgcn_readlane(cll, m), lm = l0 >= kLogZero ? kLongZero : l0;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              acc[c] ^= exl[lm + e[c]];
-              e[c] += xinv[c];
-            }
-          }
+          locator_at_positions(V, cll, deg, xinv, acc);
         }
-        uint32_t count = 0;
-        const unsigned long long below = (1ull << lane) - 1ull;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          isroot[c] = (valid[c] && acc[c] == 0) ? 1u : 0u;
-          const unsigned long long mk = __ballot(isroot[c] != 0);
-          rank[c] = count + static_cast<uint32_t>(__builtin_popcountll(mk & below));
-          count += static_cast<uint32_t>(__builtin_popcountll(mk));
-        }
-        nerr = static_cast<int>(count);
+        nerr = rank_roots(lane, valid, acc, isroot, rank);
         if (nerr != deg) status = CC_FRAME_LOCATOR;  // cyclic.h:134-143
         if (status == CC_FRAME_OK) {  // the symbols to patch: fetched now, needed after the error values
 #pragma unroll
@@ -889,76 +873,17 @@ chunk_fix_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t *
       }
       if (dbg_stop == 3) status = CC_FRAME_LOCATOR;
 
-      // error values: bch.h:80-83 (all ones) / Forney for rs.h:41-78, one lane per located error
+      // error values: bch.h:80-83 (all ones) / Forney for rs.h:41-78
       if (status == CC_FRAME_OK && is_rs) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          if (isroot[c]) RP[rank[c]] = static_cast<uint8_t>(lane + 64 * c);
-        uint32_t om = 0;  // omega_j = sum_{m<=j} S_{j-m} lambda_m, j < deg
-        for (int m = 0; m <= deg; ++m) {
-          const uint32_t lm = __builtin_amdgcn_readlane(cll, m);
-          const bool in = lane >= m && lane < deg && lane - m < t2;
-          om ^= in ? ex[lm + CSL[in ? lane - m : 0]] : 0u;
-        }
-        const uint32_t oml = lg2[om];
-        uint32_t y = 0;
-        if (lane < deg) {
-          const uint32_t p = RP[lane], zl = TW ? (static_cast<uint32_t>(step) * p) % static_cast<uint32_t>(nn) : p;
-          const uint32_t xi = zl ? static_cast<uint32_t>(nn) - zl : 0u;  // log X^-1
-          uint32_t x2 = 2 * xi;
-          x2 = umin32(x2, x2 - static_cast<uint32_t>(nn));
-          uint32_t num = 0, den = 0, e = 0;
-          for (int j = 0; j < deg; ++j) {  // omega(X^-1)
-            const uint32_t l0 = __builtin_amdgcn_readlane(oml, j);
-            num ^= exl[(l0 >= kLogZero ? kLongZero : l0) + e];
-            e += xi;
-          }
-          e = 0;
-          for (int m = 1; m <= deg; m += 2) {  // lambda'(X^-1) = sum_{m odd} lambda_m X^-(m-1)
-            const uint32_t l0 = __builtin_amdgcn_readlane(cll, m);
-            den ^= exl[(l0 >= kLogZero ? kLongZero : l0) + e];
-            e += x2;
-          }
-          y = (num && den) ? ex[lg[num] + nn - lg[den]] : 0u;
-          if (TW) y = y ? ex[lg[y] + (twist * p) % static_cast<uint32_t>(nn)] : 0u;
-        }
-        VAL[lane] = static_cast<uint8_t>(y);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) corr[c] = isroot[c] ? VAL[rank[c]] : 0u;
+        forney_values<TW>(V, Tb, S, lane, cll, deg, t2, nn, step, twist, isroot, rank, corr);
       } else if (status == CC_FRAME_OK) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) corr[c] = isroot[c];
       }
-      // re-check (cyclic.h:243-248): decided by L = deg lambda (proof in algebraic.hip; with erasures it needs the error
-      // VALUES to be the ones the syndromes determine, which a binary code's all-ones are not), evaluated otherwise
-      if (status == CC_FRAME_OK && (len != deg || (rho > 0 && !is_rs))) {
-        uint32_t ly[4], ev[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          ly[c] = lg[corr[c]];
-          ev[c] = e0[c];
-        }
-        uint32_t mismatch = 0;
-        for (int j0 = 0; j0 < t2; j0 += 4) {
-          uint32_t packed = 0, want = 0;
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) {
-            uint32_t term = 0;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              term ^= corr[c] ? ex[ly[c] + ev[c]] : 0u;
-              ev[c] += dstep[c];
-              ev[c] = ev[c] >= static_cast<uint32_t>(nn) ? ev[c] - nn : ev[c];
-            }
-            if (j0 + jj < t2) {
-              packed |= term << (8 * jj);
-              want |= static_cast<uint32_t>(CS[j0 + jj]) << (8 * jj);
-            }
-          }
-          mismatch |= lane63(wave_xor(packed)) ^ want;
-        }
-        if (mismatch != 0) status = CC_FRAME_RECHECK;
-      }
+      // re-check: decided by L = deg lambda (proof in algebraic.hip; with erasures it needs the error VALUES to be the
+      // ones the syndromes determine, which a binary code's all-ones are not), evaluated otherwise
+      if (status == CC_FRAME_OK && (len != deg || (rho > 0 && !is_rs)) && recheck_mismatch(Tb, S.CS, corr, e0, dstep, t2, nn))
+        status = CC_FRAME_RECHECK;
       const bool ok = status == CC_FRAME_OK;
 #pragma unroll
       for (int c = 0; c < 4; ++c)
@@ -996,15 +921,15 @@ chunk_fixl_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t 
                   uint8_t *__restrict__ out, int32_t *__restrict__ nerr_out, int32_t *__restrict__ status_out,
                   unsigned long long B) {
   // exl: alpha^i for i < kZ, zero from kZ on; kZ marks a zero operand (log of 0), kZ + kZ still inside the table
-  constexpr uint32_t kZ = 8448, kLongSize = 2 * kZ + 64, kN = 255;
+  constexpr uint32_t kZ = kLongZero, kLongSize = 2 * kZ + 64, kN = 255;
   __shared__ __attribute__((aligned(16))) uint8_t smem[kLongSize + 512 + 256 + 4 * 2 * MD * 64];
   uint8_t *exl = smem;
   uint16_t *lgz = reinterpret_cast<uint16_t *>(smem + kLongSize);  // [256] log, kZ for 0
   uint8_t *lg = smem + kLongSize + 512;                            // [256] plain log table (log 0 = 0)
   uint8_t *plist = smem + kLongSize + 512 + 256;                   // [wavefront][2 MD][64] error positions, symbols
-  for (uint32_t i = threadIdx.x; i < kLongSize; i += 256) exl[i] = i < kZ ? T->exp[i % 255u] : 0;
-  lgz[threadIdx.x] = static_cast<uint16_t>(threadIdx.x ? T->log[threadIdx.x] : kZ);
-  lg[threadIdx.x] = T->log[threadIdx.x];
+  stage_exl(T, exl, kLongSize);
+  stage_log16(T, lgz, kZ);
+  stage_log(T, lg);
   __syncthreads();
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), f = lane;
   const int n = T->n, t2 = T->nroots, nc = t2 + 1;
@@ -1043,14 +968,12 @@ chunk_fixl_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t 
       left[chunk] = lmask;
       if (lmask) atomicAdd(nleft, 1u);
     }
-    int status = CC_FRAME_OK;
-    if (alg != CC_ALG_BM && 2 * deg - rho > t2) status = CC_FRAME_LOCATOR;  // bounded-distance decoding (rho = 0 here: see chunk_fix_kernel)
-    if (deg < 1) status = CC_FRAME_LOCATOR;                            // cyclic.h:145-147
+    int status = chain::locator_status(alg, deg, rho, t2);
     const unsigned long long group = 2 * chunk + (f >> 5);
-    const int fi = f & 31, bit = 8 * (fi & 3) + (fi >> 2);
+    const int fi = f & 31;
     uint32_t R[8];  // bit j of R[k]: position 32 k + j is a root
 #pragma unroll
-    for (int k = 0; k < 8; ++k) R[k] = rootsT[(group * 8 + k) * 32 + bit];
+    for (int k = 0; k < 8; ++k) R[k] = rootsT[chain::rootsT_word(group, k, fi)];
     // positions n .. 255 do not exist (255: GF(256) has 255 positions; a shortened code has n < 255): a root there is
     // not counted, so a locator with one fails below
 #pragma unroll
@@ -1111,9 +1034,9 @@ chunk_fixl_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t 
         for (int u = 0; u < 4; ++u) PL[(MD + e0 + u) * 64 + lane] = static_cast<uint8_t>(sy[u]);
       }
       if (is_rs) {
-        const uint8_t *sb = synd + ((group >> 6) * t2 * 64 + (group & 63)) * 32 + 4 * (fi & 7) + (fi >> 3);
+        const uint8_t *sb = synd + chain::synd_byte(group, fi, 0, t2);
 #pragma unroll
-        for (int j = 0; j < MD; ++j) sl[j] = j < t2 ? sb[j * 2048] : 0u;
+        for (int j = 0; j < MD; ++j) sl[j] = j < t2 ? sb[j * chain::kSyndStride] : 0u;
 #pragma unroll
         for (int m = 0; m < MD + 1; ++m) ll[m] = m < nc ? llg[(chunk * nc + m) * 64 + f] : kLogZero;
       }
@@ -1229,13 +1152,10 @@ static int launch_chunk_fpw(const cc_code *code, bool float_in, const void *d_in
                             int32_t *d_status, size_t B, hipStream_t stream) {
   const int t2 = static_cast<int>(code->tab.roots.size());
   const size_t lds = 1792 + 4 * static_cast<size_t>(chunk_layout(t2, FPW).bytes);
-  const unsigned long long chunks = (B + FPW - 1) / FPW;
-  const unsigned long long blocks_needed = (chunks + 3) / 4;
   unsigned long long per_cu = (160 * 1024) / lds;
   if (per_cu > 8) per_cu = 8;
   if (per_cu < 1) per_cu = 1;
-  const unsigned long long max_grid = static_cast<unsigned long long>(code->num_cus) * per_cu;
-  const int grid = static_cast<int>(blocks_needed < max_grid ? blocks_needed : max_grid);
+  const int grid = chain::chunk_grid(code, (B + FPW - 1) / FPW, per_cu);
   const unsigned long long Bq = B;
   const int alg_arg = code->desc.algorithm | (alg_stop_stage() << 8);
   hipError_t e = hipSuccess;
@@ -1264,19 +1184,17 @@ int launch_chunk_bm(const cc_code *code, const uint8_t *d_synd, const uint16_t *
   const int t2 = static_cast<int>(code->tab.roots.size());
   const unsigned long long chunks = (B + 63) / 64;
   const int dbg_stop = alg_stop_stage();
-  const unsigned long long Bq = B, blocks_needed = (chunks + 3) / 4;
+  const unsigned long long Bq = B;
   const size_t lds = 1536 + 4 * static_cast<size_t>(bm_layout(t2).bytes);
   unsigned long long per_cu = (160 * 1024) / lds;
   if (per_cu < 1) per_cu = 1;
-  const unsigned long long max_grid = static_cast<unsigned long long>(code->num_cus) * per_cu;
-  const int grid = static_cast<int>(blocks_needed < max_grid ? blocks_needed : max_grid);
+  const int grid = chain::chunk_grid(code, chunks, per_cu);
   hipError_t e = hipSuccess;
   if (lds > 48 * 1024)
     e = hipFuncSetAttribute(reinterpret_cast<const void *>(&chunk_bm_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                             static_cast<int>(lds));
   if (e == hipSuccess) {
-    const unsigned long long reg_cap = static_cast<unsigned long long>(code->num_cus) * 3;
-    const int reg_grid = static_cast<int>(blocks_needed < reg_cap ? blocks_needed : reg_cap);
+    const int reg_grid = chain::chunk_grid(code, chunks, 3);
     if (t2 == 32 && !d_er_off)  // (with erasures the recurrence starts per lane at i = rho: the LDS form below)
       hipLaunchKernelGGL((chunk_bm_reg_kernel<32>), dim3(reg_grid), dim3(256), 0, stream, code->d_alg, dbg_stop, d_synd,
                          d_llg, d_meta, d_mask, reinterpret_cast<uint4 *>(d_lamp), d_nleft, d_nerr, d_status, Bq);
@@ -1296,48 +1214,31 @@ int launch_chunk_bm(const cc_code *code, const uint8_t *d_synd, const uint16_t *
 static int launch_chunk_bitsliced(const cc_code *code, bool float_in, const void *d_in, const uint16_t *d_er,
                                   const uint32_t *d_er_off, uint8_t *d_out, int32_t *d_nerr, int32_t *d_status, size_t B,
                                   hipStream_t stream, int il) {
-  const int t2 = static_cast<int>(code->tab.roots.size()), nc = t2 + 1;
-  const unsigned long long G = (B + 31) / 32, chunks = (B + 63) / 64;
-  const size_t G64 = static_cast<size_t>((G + 63) / 64) * 64;  // syndromes, locators and root masks are laid out in blocks of 64 groups
-  auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
-  const size_t synd_bytes = G64 * t2 * 32;
-  const size_t llg_bytes = up(static_cast<size_t>(chunks) * nc * 64 * 2), meta_bytes = up(static_cast<size_t>(chunks) * 64 * 2);
-  const size_t mask_bytes = up(static_cast<size_t>(chunks) * 8);
+  const int t2 = static_cast<int>(code->tab.roots.size());
+  const unsigned long long chunks = (B + 63) / 64;
   // calls with erasures: combined (erasure x error) locators up to degree 24 on the lane-per-frame path -- 25 coefficient
   // planes, the long instantiations of the root search and of the corrector; without erasures a correctable locator
   // has degree <= t <= 16
   const bool long_loc = d_er_off != nullptr && t2 > 16;
   const bool tw = rs_twisted(code);  // (on this chain: mu = 0, step = 1 -- bitslice_supported)
   const int ncoef = long_loc ? 25 : 17;
-  const size_t lamp_bytes = G64 * ncoef * 32, roots_bytes = G64 * 256 * 4, left_bytes = mask_bytes;
-  uint8_t *ws = nullptr;  // stream-ordered and pool-cached: no device-wide synchronisation, no allocation after the first call
-  CC_HIP_TRY(workspace_alloc(code, reinterpret_cast<void **>(&ws),
-                            synd_bytes + llg_bytes + meta_bytes + mask_bytes + lamp_bytes + 2 * roots_bytes + left_bytes + 256, stream));
-  uint8_t *d_synd = ws;
-  uint16_t *d_llg = reinterpret_cast<uint16_t *>(d_synd + synd_bytes);
-  uint16_t *d_meta = reinterpret_cast<uint16_t *>(reinterpret_cast<uint8_t *>(d_llg) + llg_bytes);
-  unsigned long long *d_mask = reinterpret_cast<unsigned long long *>(reinterpret_cast<uint8_t *>(d_meta) + meta_bytes);
-  uint8_t *d_lamp = reinterpret_cast<uint8_t *>(d_mask) + mask_bytes;
-  uint8_t *d_roots = d_lamp + lamp_bytes;
-  unsigned long long *d_left = reinterpret_cast<unsigned long long *>(d_roots + roots_bytes);
-  uint32_t *d_nleft = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(d_left) + left_bytes);
-  uint8_t *d_rootsT = reinterpret_cast<uint8_t *>(d_nleft) + 256;
+  chain::Workspace ws;
+  CC_HIP_TRY(chain::workspace(code, B, ncoef, true, stream, ws));
   // il > 1: symbol-interleaved words -- the loader of the syndrome kernel and the two correctors address
   // the blocks themselves; syndromes, locators and root masks are per frame, as ever
   const int il_arg = il > 1 ? il << 16 : 0;
-  int rc = launch_bitslice_syndromes(code, float_in, d_in, d_out, d_synd, B, stream, il);
+  int rc = launch_bitslice_syndromes(code, float_in, d_in, d_out, ws.synd, B, stream, il);
   if (rc == CC_OK) {
     const int dbg_stop = alg_stop_stage();
-    const unsigned long long Bq = B, blocks_needed = (chunks + 3) / 4;
-    rc = launch_chunk_bm(code, d_synd, d_er, d_er_off, d_llg, d_meta, d_mask, d_lamp, ncoef, d_nleft, d_nerr, d_status, B, stream);
-    if (rc == CC_OK) rc = launch_bitslice_chien(d_lamp, d_roots, B, long_loc, stream);
+    const unsigned long long Bq = B;
+    rc = launch_chunk_bm(code, ws.synd, d_er, d_er_off, ws.llg, ws.meta, ws.mask, ws.lamp, ncoef, ws.nleft, d_nerr, d_status, B, stream);
+    if (rc == CC_OK) rc = launch_bitslice_chien(ws.lamp, ws.roots, B, long_loc, stream);
     hipError_t e = hipSuccess;
     if (rc == CC_OK) {
-      const unsigned long long max_grid = static_cast<unsigned long long>(code->num_cus) * 8;
-      const int grid = static_cast<int>(blocks_needed < max_grid ? blocks_needed : max_grid);
+      const int grid = chain::chunk_grid(code, chunks, 8);
       const bool four = dbg_stop == 0;
-      if (four) {  // one lane per frame; what it cannot settle goes on through d_left
-        rc = launch_bitslice_roots_transpose(d_roots, d_rootsT, B, stream);
+      if (four) {  // one lane per frame; what it cannot settle goes on through ws.left
+        rc = launch_bitslice_roots_transpose(ws.roots, ws.rootsT, B, stream);
         if (rc == CC_OK) {
           // resident workgroups per CU: registers and LDS of the built kernels ([twisted roots][long locators])
           auto per_cu = [](auto kernel, int fallback) {
@@ -1348,11 +1249,10 @@ static int launch_chunk_bitsliced(const cc_code *code, bool float_in, const void
           static const int fixl_per_cu[2][2] = {
               {per_cu(chunk_fixl_kernel<16, false>, 3), per_cu(chunk_fixl_kernel<24, false>, 2)},
               {per_cu(chunk_fixl_kernel<16, true>, 3), per_cu(chunk_fixl_kernel<24, true>, 2)}};
-          const unsigned long long lcap = static_cast<unsigned long long>(code->num_cus) * fixl_per_cu[tw][long_loc];
-          const int lgrid = static_cast<int>(blocks_needed < lcap ? blocks_needed : lcap);
+          const int lgrid = chain::chunk_grid(code, chunks, fixl_per_cu[tw][long_loc]);
           auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(lgrid), dim3(256), 0, stream, code->d_alg, code->desc.algorithm | fixl_exp() | il_arg, d_synd,
-                               d_llg, d_meta, d_mask, reinterpret_cast<const uint32_t *>(d_rootsT), d_left, d_nleft, d_er_off,
+            hipLaunchKernelGGL(kernel, dim3(lgrid), dim3(256), 0, stream, code->d_alg, code->desc.algorithm | fixl_exp() | il_arg, ws.synd,
+                               ws.llg, ws.meta, ws.mask, reinterpret_cast<const uint32_t *>(ws.rootsT), ws.left, ws.nleft, d_er_off,
                                d_out, d_nerr, d_status, Bq);
           };
           if (il > 1)  // (no erasures: locators up to degree 16)
@@ -1367,8 +1267,8 @@ static int launch_chunk_bitsliced(const cc_code *code, bool float_in, const void
       if (rc == CC_OK && e == hipSuccess) {
         auto launch = [&](auto kernel) {
           hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, code->d_alg, code->desc.algorithm | (dbg_stop << 8) | il_arg,
-                             d_synd, d_llg, d_meta, four ? d_left : d_mask, reinterpret_cast<const uint32_t *>(d_roots),
-                             four ? d_nleft : nullptr, d_er_off, long_loc ? 24 : 16, d_out, d_nerr, d_status, Bq);
+                             ws.synd, ws.llg, ws.meta, four ? ws.left : ws.mask, reinterpret_cast<const uint32_t *>(ws.roots),
+                             four ? ws.nleft : nullptr, d_er_off, long_loc ? 24 : 16, d_out, d_nerr, d_status, Bq);
         };
         if (il > 1)
           tw ? launch(chunk_fix_kernel<true, true>) : launch(chunk_fix_kernel<false, true>);
@@ -1379,7 +1279,7 @@ static int launch_chunk_bitsliced(const cc_code *code, bool float_in, const void
     }
     if (rc == CC_OK && e != hipSuccess) rc = hip_fail(e, "algebraic chunk kernels launch");
   }
-  (void)hipFreeAsync(ws, stream);
+  (void)hipFreeAsync(ws.base, stream);
   return rc;
 }
 

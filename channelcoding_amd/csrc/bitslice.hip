@@ -25,6 +25,7 @@
 
 #include "bitplane.hpp"
 #include "cc_internal.hpp"
+#include "chunk_chain.hpp"
 
 namespace ccamd {
 namespace {
@@ -83,7 +84,7 @@ __device__ __forceinline__ void fused_syndromes4(const uint4 *__restrict__ lds, 
   for (int j = 0; j < 4; ++j) {
     if (J0 + j >= t2) break;
     if (!RAW) butterfly(s[j]);  // word k = bytes of the frames {k, 8+k, 16+k, 24+k}
-    uint4 *dst = reinterpret_cast<uint4 *>(synd + (((gg >> 6) * t2 + (J0 + j)) * 64 + (gg & 63)) * 32);
+    uint4 *dst = chain::synd_row(synd, gg, J0 + j, t2);
     dst[0] = make_uint4(s[j][0], s[j][1], s[j][2], s[j][3]);
     dst[1] = make_uint4(s[j][4], s[j][5], s[j][6], s[j][7]);
   }
@@ -503,7 +504,7 @@ __device__ __forceinline__ void chien_half(const uint4 *__restrict__ lamp, uint2
 #pragma unroll
     for (int b = 0; b < 8; ++b) T[k][b] = 0;
     if (k < MC && live) {
-      const uint4 *src = lamp + ((blk * NCOEF + (M0 + k)) * 64 + lane) * 2;
+      const uint4 *src = lamp + chain::lamp_row(g, M0 + k, NCOEF);
       const uint4 a = src[0], c = src[1];
       T[k][0] = a.x, T[k][1] = a.y, T[k][2] = a.z, T[k][3] = a.w;
       T[k][4] = c.x, T[k][5] = c.y, T[k][6] = c.z, T[k][7] = c.w;
@@ -563,7 +564,7 @@ __device__ __forceinline__ void chien_half(const uint4 *__restrict__ lamp, uint2
         for (int b = 0; b < 8; ++b) nz |= part[u][b] ^ buf[(u * 8 + b) * 64 + lane];
         out[u] = ~nz;
       }
-      if (live) masks[g * 128 + 16 * seg + batch] = make_uint2(out[0], out[1]);
+      if (live) masks[chain::roots_word(g, 32 * seg + PB * batch) / 2] = make_uint2(out[0], out[1]);
     }
   }
 }

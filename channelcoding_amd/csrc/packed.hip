@@ -23,6 +23,7 @@
 
 #include "bitplane.hpp"
 #include "cc_internal.hpp"
+#include "chunk_chain.hpp"
 #include "packed_words.hpp"
 
 namespace ccamd {
@@ -125,7 +126,7 @@ __device__ __forceinline__ void packed_syndromes4(const uint32_t *__restrict__ l
   for (int j = 0; j < 4; ++j) {
     if (J0 + j >= t2) break;
     butterfly(s[j]);  // word k = bytes of the frames {k, 8+k, 16+k, 24+k}
-    uint4 *dst = reinterpret_cast<uint4 *>(synd + (((gg >> 6) * t2 + (J0 + j)) * 64 + (gg & 63)) * 32);
+    uint4 *dst = chain::synd_row(synd, gg, J0 + j, t2);
     dst[0] = make_uint4(s[j][0], s[j][1], s[j][2], s[j][3]);
     dst[1] = make_uint4(s[j][4], s[j][5], s[j][6], s[j][7]);
   }
@@ -239,8 +240,8 @@ packed_extract_kernel(const uint8_t *__restrict__ cw, uint8_t *__restrict__ msg,
 
 // ---------------- correction, one lane per frame ----------------
 // Per frame the decisions of chunk_fixl_kernel and, for the frames it hands on, of chunk_fix_kernel (no erasures, binary
-// code), in the same order: bounded-distance rule of the PGZ / Euklid tags, deg lambda >= 1, as many roots below n as
-// the degree (cyclic.h:134-147).  Roots of locators up to degree 16 come from the plane search (rootsT), longer ones (BM
+// code), in the same order: bounded-distance rule of the PGZ / Euklid tags, deg lambda >= 1 (chain::locator_status, the
+// function those kernels call), as many roots below n as the degree (cyclic.h:134-147).  Roots of locators up to degree 16 come from the plane search (rootsT), longer ones (BM
 // tag only: the other tags refuse them by degree) are searched here over the positions below n, as chunk_fix_kernel
 // does, in a divergent table loop; the common frame is eight loads, eight XORs, eight stores.
 // The re-check (cyclic.h:243-248) that chunk_fix_kernel evaluates where L != deg lambda needs no evaluation here:
@@ -278,17 +279,13 @@ packed_fix_kernel(const AlgebraicTables *__restrict__ T, int alg, const uint8_t 
     if (dirty) {
       const uint32_t md = meta[frame];
       const int deg = md & 0xFF, len = md >> 8;
-      int status = CC_FRAME_OK;
-      if (alg != CC_ALG_BM && 2 * deg > t2) status = CC_FRAME_LOCATOR;  // bounded-distance decoding
-      if (deg < 1) status = CC_FRAME_LOCATOR;                          // cyclic.h:145-147
+      int status = chain::locator_status(alg, deg, 0, t2);
       uint32_t R[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // bit j of R[k]: position 32 k + j is a root
       uint32_t cnt = 0;
       if (status == CC_FRAME_OK) {
         if (deg <= 16) {  // searched on planes (bitslice_chien_kernel carries coefficients 0 .. 16)
-          const unsigned long long group = 2 * chunk + (f >> 5);
-          const int fi = f & 31, bit = 8 * (fi & 3) + (fi >> 2);
 #pragma unroll
-          for (int k = 0; k < 8; ++k) R[k] = rootsT[(group * 8 + k) * 32 + bit] & word_mask(k, n);
+          for (int k = 0; k < 8; ++k) R[k] = rootsT[chain::rootsT_word(2 * chunk + (f >> 5), k, f & 31)] & word_mask(k, n);
         } else {  // lambda(alpha^-p) for p < n
           for (int p = 0; p < n; ++p) {
             const uint32_t xinv = static_cast<uint32_t>((255 - p) % 255);
@@ -418,49 +415,33 @@ int launch_packed_correct(const cc_code *code, const uint8_t *d_in, uint8_t *d_o
                           size_t B, hipStream_t stream) {
   if (B == 0) return CC_OK;
   const int n = static_cast<int>(code->tab.n), P = (n + 7) / 8;
-  const int t2 = static_cast<int>(code->tab.roots.size()), nc = t2 + 1, ncoef = 17;
+  const int t2 = static_cast<int>(code->tab.roots.size()), ncoef = 17;
   const unsigned long long G = (B + 31) / 32, chunks = (B + 63) / 64, Bq = B;
-  const size_t G64 = static_cast<size_t>((G + 63) / 64) * 64;  // syndromes, locators and root masks: blocks of 64 groups
-  auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
-  const size_t synd_bytes = G64 * t2 * 32;
-  const size_t llg_bytes = up(static_cast<size_t>(chunks) * nc * 64 * 2), meta_bytes = up(static_cast<size_t>(chunks) * 64 * 2);
-  const size_t mask_bytes = up(static_cast<size_t>(chunks) * 8);
-  const size_t lamp_bytes = G64 * ncoef * 32, roots_bytes = G64 * 256 * 4;
-  uint8_t *ws = nullptr;  // stream-ordered and pool-cached, as the byte chain's
-  CC_HIP_TRY(workspace_alloc(code, reinterpret_cast<void **>(&ws),
-                            synd_bytes + llg_bytes + meta_bytes + mask_bytes + lamp_bytes + 2 * roots_bytes + 256, stream));
-  uint8_t *d_synd = ws;
-  uint16_t *d_llg = reinterpret_cast<uint16_t *>(d_synd + synd_bytes);
-  uint16_t *d_meta = reinterpret_cast<uint16_t *>(reinterpret_cast<uint8_t *>(d_llg) + llg_bytes);
-  unsigned long long *d_mask = reinterpret_cast<unsigned long long *>(reinterpret_cast<uint8_t *>(d_meta) + meta_bytes);
-  uint8_t *d_lamp = reinterpret_cast<uint8_t *>(d_mask) + mask_bytes;
-  uint8_t *d_roots = d_lamp + lamp_bytes;
-  uint8_t *d_rootsT = d_roots + roots_bytes;
-  uint32_t *d_nleft = reinterpret_cast<uint32_t *>(d_rootsT + roots_bytes);  // (the Berlekamp-Massey kernels reset it)
+  chain::Workspace ws;  // (no `left`: packed_fix_kernel settles every frame itself)
+  CC_HIP_TRY(chain::workspace(code, B, ncoef, false, stream, ws));
   const unsigned per_wg = kPackedWaves * kPackedGroups;
   hipLaunchKernelGGL(packed_syndrome_kernel, dim3(static_cast<unsigned>((G + per_wg - 1) / per_wg)), dim3(64 * kPackedWaves), 0,
-                     stream, d_in, d_synd, Bq, G, n, P, t2);
+                     stream, d_in, ws.synd, Bq, G, n, P, t2);
   hipError_t e = hipGetLastError();
   int rc = e == hipSuccess ? CC_OK : hip_fail(e, "packed syndrome kernel launch");
   if (rc == CC_OK)
-    rc = launch_chunk_bm(code, d_synd, nullptr, nullptr, d_llg, d_meta, d_mask, d_lamp, ncoef, d_nleft, d_nerr, d_status, B,
-                         stream);
-  if (rc == CC_OK) rc = launch_bitslice_chien(d_lamp, d_roots, B, false, stream);
-  if (rc == CC_OK) rc = launch_bitslice_roots_transpose(d_roots, d_rootsT, B, stream);
+    rc = launch_chunk_bm(code, ws.synd, nullptr, nullptr, ws.llg, ws.meta, ws.mask, ws.lamp, ncoef, ws.nleft, d_nerr, d_status,
+                         B, stream);
+  if (rc == CC_OK) rc = launch_bitslice_chien(ws.lamp, ws.roots, B, false, stream);
+  if (rc == CC_OK) rc = launch_bitslice_roots_transpose(ws.roots, ws.rootsT, B, stream);
   if (rc == CC_OK) {
     static const int per_cu = [] {  // resident workgroups per CU of the built kernel
       int v = 0;
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, packed_fix_kernel, 256, 0) != hipSuccess || v < 1) v = 4;
       return v;
     }();
-    const unsigned long long blocks_needed = (chunks + 3) / 4, cap = static_cast<unsigned long long>(code->num_cus) * per_cu;
-    hipLaunchKernelGGL(packed_fix_kernel, dim3(static_cast<unsigned>(blocks_needed < cap ? blocks_needed : cap)), dim3(256), 0,
-                       stream, code->d_alg, code->desc.algorithm, d_in, d_out, d_llg, d_meta, d_mask,
-                       reinterpret_cast<const uint32_t *>(d_rootsT), d_nerr, d_status, Bq, P);
+    hipLaunchKernelGGL(packed_fix_kernel, dim3(chain::chunk_grid(code, chunks, per_cu)), dim3(256), 0, stream, code->d_alg,
+                       code->desc.algorithm, d_in, d_out, ws.llg, ws.meta, ws.mask,
+                       reinterpret_cast<const uint32_t *>(ws.rootsT), d_nerr, d_status, Bq, P);
     e = hipGetLastError();
     if (e != hipSuccess) rc = hip_fail(e, "packed fix kernel launch");
   }
-  (void)hipFreeAsync(ws, stream);
+  (void)hipFreeAsync(ws.base, stream);
   return rc;
 }
 
