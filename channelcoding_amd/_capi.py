@@ -23,6 +23,7 @@ FRAME_OK, FRAME_NOT_CONVERGED, FRAME_LOCATOR, FRAME_RECHECK, FRAME_ERASURES = ra
 MC_FRAMES, MC_WORD_ERRORS, MC_BIT_ERRORS, MC_FAILURES, MC_UNDETECTED, MC_ITER_SUM, MC_CHANNEL_BIT_ERRORS = range(7)
 MC_CHANNEL_ERASURES = 7
 MC_ITER_HIST, MC_NCOUNTERS = 8, 64
+CHASE_MAX_P = 6
 HARD_ROUTE_WAVE, HARD_ROUTE_CHUNK, HARD_ROUTE_PLANES, HARD_ROUTE_LONG, HARD_ROUTE_WIDE, HARD_ROUTE_TRIALS = range(6)
 
 SOFT_ALGS = (ALG_MS, ALG_NMS, ALG_OMS, ALG_SCMS1, ALG_SCMS2, ALG_2DNMS)
@@ -92,6 +93,8 @@ _SIGNATURES = {
     "cc_correct_hard_f32_batch_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "cc_correct_soft_batch": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t]),
     "cc_correct_soft_batch_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "cc_correct_chase_batch": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, C.c_size_t]),
+    "cc_correct_chase_batch_dev": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "cc_extract_batch": (C.c_int, [_VP, _VP, _VP, C.c_size_t]),
     "cc_extract_batch_dev": (C.c_int, [_VP, _VP, _VP, C.c_size_t, _VP]),
     "cc_decode_hard_batch": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t]),
@@ -99,6 +102,7 @@ _SIGNATURES = {
     "cc_mc_run_dev": (C.c_int, [_VP, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP, _VP]),
     "cc_awgn_llr_dev": (C.c_int, [_VP, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP, _VP, _VP]),
     "cc_sigma": (C.c_double, [_VP, C.c_double]),
+    "cc_mc_run_chase_dev": (C.c_int, [_VP, C.c_uint32, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP, _VP]),
     "cc_mc_run_discrete_dev": (C.c_int, [_VP, C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP,
                                          _VP]),
     "cc_discrete_channel_dev": (C.c_int, [_VP, C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int,

@@ -99,6 +99,8 @@ def usage_text():
               "                             to the decoder. The default is 0.",
               "--p-false-alarm <value>      burst: P(symbol flagged | good state). The default is 0.",
               "--packed                     bsc: channel, decoder and counts on packed words (hard-decision algorithms).",
+              "--chase <p>                  awgn: Chase-II over the p least reliable positions, 0 .. 6 (hard-decision",
+              "                             algorithms; the log is <decoder>-chase<p>.log).",
               "--max-samples <num>          awgn / bsc / bec / burst: cap on the frames of one point.",
               "",
               "algorithm, k, and dmin can be specified multiple times.",
@@ -155,6 +157,7 @@ def main(argv=None):
     ap.add_argument("--p-detect", type=float, default=0.0, help="burst: P(flag | bad state) of the burst detector")
     ap.add_argument("--p-false-alarm", type=float, default=0.0, help="burst: P(flag | good state)")
     ap.add_argument("--packed", action="store_true", help="bsc: the route on packed words")
+    ap.add_argument("--chase", type=int, default=None, help="awgn: Chase-II with p least reliable positions")
     ap.add_argument("--help", "-h", action="store_true")
     args, unknown = ap.parse_known_args(argv)
     if args.help or unknown:
@@ -171,7 +174,13 @@ def main(argv=None):
         print("--packed goes with --simulation bsc", file=sys.stderr)
         print(usage_text())
         return 1
+    if args.chase is not None and (sim != "awgn" or not 0 <= args.chase <= 6):
+        print("--chase <0..6> goes with --simulation awgn", file=sys.stderr)
+        print(usage_text())
+        return 1
     chosen = select(args.algorithm, args.k, args.dmin)
+    if args.chase is not None:  # the hard-tag decoders of the registry
+        chosen = [c for c in chosen if not ALGORITHMS[c[0]]().soft]
     if not chosen:
         print("The selection is empty")
         print(usage_text())
@@ -195,7 +204,8 @@ def main(argv=None):
         code = build(name, k, d, args.stop_rule)
         t0 = time.perf_counter()
         if sim == "awgn":
-            res = awgn_simulation(code, seed=seed, log_dir=args.log_dir, max_samples=args.max_samples)()
+            res = awgn_simulation(code, seed=seed, log_dir=args.log_dir, max_samples=args.max_samples,
+                                  chase=args.chase)()
             frames = sum(r["frames"] for r in res)
         elif sim in ("bsc", "bec"):
             packed = dict(packed=True) if args.packed else {}

@@ -760,8 +760,11 @@ class cyclic:
         capi.check(lib.cc_extract_batch(self._h, _ptr(cw), _ptr(msg), cw.shape[0]), "cc_extract_batch")
         return msg
 
-    def correct_batch(self, b, erasures=None, want_L=False, packed=False, out=None, interleave=None):
+    def correct_batch(self, b, erasures=None, want_L=False, packed=False, out=None, interleave=None, chase=None):
         """Returns a dict: out (B,n) u8, status (B,) i32, and nerr (hard) or iters [+ L] (soft).
+        chase=p (binary BCH, hard algorithms, q <= 8, 2t <= 32): b holds float32 channel values and is decoded by
+        Chase's algorithm 2 over the p least reliable positions (cc_correct_chase_batch); the dict also carries
+        metric (B,) f32.  It does not combine with erasures, packed, interleave or want_L.
         packed=True (binary BCH codes, hard algorithms): b and out are uint8 (B, packed_bytes), see pack_bits; out= names
         the buffer the corrected packed words go to (b itself decodes in place).  The long codes (q = 9 .. 15, BM / PGZ,
         t <= 31, no erasures) are decoded from the packed words themselves in calls of device tensors of at least
@@ -769,6 +772,10 @@ class cyclic:
         interleave=I (hard algorithms): b and out are symbol-interleaved blocks of shape (B / I, n, I), see interleave();
         status, nerr and the erasure lists are per frame f = b I + j, as without it; out= as with packed=True."""
         lib = capi.lib()
+        if chase is not None:
+            if erasures is not None or want_L or packed or out is not None or interleave is not None:
+                raise TypeError("chase= does not combine with erasures, want_L, packed=True, out= or interleave=")
+            return self._chase(b, chase)
         if interleave is not None:
             if packed:
                 raise TypeError("interleave= does not combine with packed=True")
@@ -813,6 +820,38 @@ class cyclic:
                                                  _ptr(status), B), "cc_correct_hard_batch")
         return dict(out=out, status=status, nerr=nerr)
 
+    def _chase(self, b, p):
+        """correct_batch(chase=p): float32 channel values, host array or device tensor."""
+        lib = capi.lib()
+        p = int(p)
+        if p < 0:
+            raise ValueError("chase= takes p >= 0")
+        if b.shape[-1] != self.n:
+            raise CcError(capi.ERR_LENGTH, "correct_batch")
+        if _is_torch(b):
+            import torch
+            if b.dtype != torch.float32:
+                raise TypeError("chase= takes float32 channel values")
+            b = b.contiguous()
+            B, dev = b.numel() // self.n, b.device
+            out = torch.empty((B, self.n), dtype=torch.uint8, device=dev)
+            nerr = torch.empty(B, dtype=torch.int32, device=dev)
+            status = torch.empty(B, dtype=torch.int32, device=dev)
+            metric = torch.empty(B, dtype=torch.float32, device=dev)
+            capi.check(lib.cc_correct_chase_batch_dev(self._h, _ptr(b), p, _ptr(out), _ptr(nerr), _ptr(metric),
+                                                      _ptr(status), B, _stream_handle(b)), "cc_correct_chase_batch_dev")
+            return dict(out=out, status=status, nerr=nerr, metric=metric)
+        b = np.asarray(b)
+        if b.dtype.kind != "f":
+            raise TypeError("chase= takes float32 channel values")
+        B = b.size // self.n
+        y = np.ascontiguousarray(b, np.float32).reshape(B, self.n)
+        out = np.zeros((B, self.n), np.uint8)
+        nerr, status, metric = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.float32)
+        capi.check(lib.cc_correct_chase_batch(self._h, _ptr(y), p, _ptr(out), _ptr(nerr), _ptr(metric), _ptr(status), B),
+                   "cc_correct_chase_batch")
+        return dict(out=out, status=status, nerr=nerr, metric=metric)
+
     def _correct_batch_torch(self, b, erasures, want_L):
         import torch
         lib = capi.lib()
@@ -854,10 +893,15 @@ class cyclic:
             raise TypeError("hard decoding takes uint8 symbols or float32 soft values")
         return dict(out=out, status=status, nerr=nerr)
 
-    def decode_batch(self, b, erasures=None, packed=False, interleave=None):
+    def decode_batch(self, b, erasures=None, packed=False, interleave=None, chase=None):
         """decode = correct + message extraction (cyclic.h:313-327); host arrays go through cc_decode_*_batch.
+        chase=p: correct_batch(b, chase=p), then the messages of its words.
         packed=True: b, out and msg are packed uint8 words, see pack_bits.
         interleave=I: b and out are blocks of shape (B / I, n, I), msg (B / I, l, I), see interleave()."""
+        if chase is not None:
+            res = self.correct_batch(b, erasures, packed=packed, interleave=interleave, chase=chase)
+            res["msg"] = self.extract_batch(res["out"])
+            return res
         if interleave is not None:
             if packed:
                 raise TypeError("interleave= does not combine with packed=True")

@@ -756,6 +756,64 @@ int cc_correct_hard_f32_batch(const cc_code *code, const float *in, const uint16
   return hard_host(code, true, in, erasures, erasure_offsets, out, nerr, status, B);
 }
 
+/* ------------------------------ Chase-II ------------------------------ */
+
+// What the Chase calls refuse, in the order the header states, all of it before a device is asked for.
+static int chase_supported(const cc_code *code, uint32_t p) {
+  if (int rc = needs_code(code)) return rc;
+  if (code->tab.family != CC_FAMILY_BCH) {
+    set_last_error("Chase-II decoding serves binary BCH codes: this is a Reed-Solomon handle");
+    return CC_ERR_UNSUPPORTED;
+  }
+  if (code->soft) {
+    set_last_error("Chase-II decoding needs a hard-decision tag (PGZ, BM or Euklid): this is a min-sum handle");
+    return CC_ERR_UNSUPPORTED;
+  }
+  if (code->wide) {
+    set_last_error("Chase-II decoding serves GF(2^q) with q <= 8");
+    return CC_ERR_UNSUPPORTED;
+  }
+  if (2 * code->tab.t > 32) {
+    set_last_error("Chase-II decoding serves codes with 2t <= 32");
+    return CC_ERR_UNSUPPORTED;
+  }
+  if (p > CC_CHASE_MAX_P) {
+    set_last_error("Chase-II decoding: p exceeds CC_CHASE_MAX_P");
+    return CC_ERR_UNSUPPORTED;
+  }
+  if (p > code->tab.n) {
+    set_last_error("Chase-II decoding: p exceeds the frame length");
+    return CC_ERR_UNSUPPORTED;
+  }
+  if (code->device == CC_DEVICE_NONE) return CC_ERR_NO_DEVICE;
+  return CC_OK;
+}
+
+int cc_correct_chase_batch_dev(const cc_code *code, const float *d_llr, uint32_t p, uint8_t *d_out, int32_t *d_nerr,
+                               float *d_metric, int32_t *d_status, size_t B, void *stream) {
+  if (!code || (B && (!d_llr || !d_out))) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = chase_supported(code, p)) return rc;
+  DeviceGuard guard(code->device);
+  return launch_chase(code, d_llr, p, d_out, d_nerr, d_metric, d_status, B, static_cast<hipStream_t>(stream));
+}
+
+int cc_correct_chase_batch(const cc_code *code, const float *llr, uint32_t p, uint8_t *out, int32_t *nerr, float *metric,
+                           int32_t *status, size_t B) {
+  if (!code || (B && (!llr || !out))) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = chase_supported(code, p)) return rc;
+  if (B == 0) return CC_OK;
+  const size_t n = code->tab.n;
+  DeviceGuard guard(code->device);
+  const StagedStream streams[] = {stage_in(0, llr, n * sizeof(float)), stage_out(1, out, n), stage_out(2, nerr, sizeof(int32_t)),
+                                  stage_out(3, status, sizeof(int32_t)), stage_out(4, metric, sizeof(float))};
+  return staged_call(code, B, n * sizeof(float), 1, streams, 5, nullptr, nullptr,
+                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t s) {
+                       return launch_chase(code, static_cast<const float *>(d[0]), p, static_cast<uint8_t *>(d[1]),
+                                           static_cast<int32_t *>(d[2]), static_cast<float *>(d[4]),
+                                           static_cast<int32_t *>(d[3]), m, s);
+                     });
+}
+
 /* ------------------------------ encode / extract ------------------------------ */
 
 int cc_encode_batch_dev(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, void *stream) {
@@ -1322,6 +1380,17 @@ int cc_mc_run_dev(const cc_code *code, double ebno_db, uint64_t seed, uint64_t f
   DeviceGuard guard(code->device);
   return mc_run(const_cast<cc_code *>(code), ebno_db, seed, first_frame, frames, random_codewords, d_counters,
                 static_cast<hipStream_t>(stream));
+}
+
+int cc_mc_run_chase_dev(const cc_code *code, uint32_t p, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
+                        int random_codewords, uint64_t *d_counters, void *stream) {
+  if (!code || !d_counters) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = chase_supported(code, p)) return rc;
+  if (random_codewords && code->desc.coding != CC_CODING_DIVISION && code->desc.coding != CC_CODING_MULTIPLICATION)
+    return CC_ERR_INVALID_ARGUMENT;
+  DeviceGuard guard(code->device);
+  return mc_run_chase(const_cast<cc_code *>(code), p, ebno_db, seed, first_frame, frames, random_codewords, d_counters,
+                      static_cast<hipStream_t>(stream));
 }
 
 int cc_awgn_llr_dev(const cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,

@@ -200,6 +200,10 @@ bool algebraic_chunk_supported(const cc_code *code, bool erasures);
 int launch_algebraic_chunk(const cc_code *code, bool float_in, const void *d_in, const uint16_t *d_er,
                            const uint32_t *d_er_off, uint8_t *d_out, int32_t *d_nerr, int32_t *d_status, size_t B,
                            hipStream_t stream, int il = 1);
+// chase.hip: Chase-II over float channel values, binary BCH with q <= 8, 2t <= 32, p <= CC_CHASE_MAX_P <= n;
+// d_nerr, d_metric and d_status may be nullptr
+int launch_chase(const cc_code *code, const float *d_llr, unsigned p, uint8_t *d_out, int32_t *d_nerr, float *d_metric,
+                 int32_t *d_status, size_t B, hipStream_t stream);
 // bitslice.hip: syndromes of GF(2^8) codes on bit planes (32 frames per register)
 bool bitslice_supported(const cc_code *code);
 int launch_bitslice_syndromes(const cc_code *code, bool float_in, const void *d_in, uint8_t *d_out, uint8_t *d_synd, size_t B,
@@ -263,6 +267,8 @@ int launch_interleaved_extract(const cc_code *code, const void *d_cw, void *d_ms
 // mc.hip (Monte-Carlo calls on one handle must be issued on one stream at a time: they share a workspace)
 int mc_run(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
            uint64_t *d_counters, hipStream_t stream);
+int mc_run_chase(cc_code *code, unsigned p, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
+                 int random_codewords, uint64_t *d_counters, hipStream_t stream);
 int mc_awgn(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
             float *d_llr, uint8_t *d_sent, hipStream_t stream);
 int mc_run_discrete(cc_code *code, double p_error, double p_erasure, uint64_t seed, uint64_t first_frame, size_t frames,

@@ -542,6 +542,26 @@ int mc_run(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, s
   });
 }
 
+// cc_mc_run_chase_dev: the plain route above with the decoder swapped -- the channel writes floats (and counts its bit
+// errors), launch_chase decodes them into w.hard / w.nerr / w.status, the counting pass is the hard decoders' (no
+// iteration counters).  Checked by the caller: a binary BCH handle with a hard tag that launch_chase serves.
+int mc_run_chase(cc_code *code, unsigned p, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
+                 int random_codewords, uint64_t *d_counters, hipStream_t stream) {
+  if (frames == 0) return CC_OK;
+  const size_t chunk = frames < MC_CHUNK ? frames : MC_CHUNK;
+  unsigned long long *counters = reinterpret_cast<unsigned long long *>(d_counters);
+  return mc_chunked(code, frames, chunk, chunk, stream, [&](McWorkspace &w, size_t done, size_t m) -> int {
+    const uint8_t *sent;
+    int rc = transmitted_words(code, seed, first_frame + done, m, random_codewords, w.sent, w.msg, nullptr, stream, &sent);
+    if (rc != CC_OK) return rc;
+    rc = launch_awgn(code, ebno_db, seed, first_frame + done, m, w.llr, sent, stream, counters);
+    if (rc != CC_OK) return rc;
+    rc = launch_chase(code, w.llr, p, w.hard, w.nerr, nullptr, w.status, m, stream);
+    if (rc != CC_OK) return rc;
+    return launch_count(code, w, sent, m, d_counters, stream);
+  });
+}
+
 // cc_awgn_llr_dev: channel only, chunked so that the message scratch stays bounded
 int mc_awgn(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
             float *d_llr, uint8_t *d_sent, hipStream_t stream) {

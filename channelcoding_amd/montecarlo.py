@@ -147,6 +147,26 @@ class DeviceBackend:
         return counters  # stays on the device: reduced with RCCL
 
 
+class ChaseBackend(DeviceBackend):
+    """The same shard through cc_mc_run_chase_dev: Chase-II over the p least reliable positions of every frame
+    (binary BCH with a hard tag, q <= 8, 2t <= 32)."""
+
+    def __init__(self, code, p, random_codewords=False):
+        super().__init__(code, random_codewords)
+        self.p = int(p)
+        if not 0 <= self.p <= capi.CHASE_MAX_P:
+            raise ValueError("chase= takes p in 0 .. %d" % capi.CHASE_MAX_P)
+
+    def run(self, ebno_db, seed, first_frame, frames):
+        torch = self.torch
+        counters = torch.zeros(capi.MC_NCOUNTERS, dtype=torch.int64, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = capi.lib().cc_mc_run_chase_dev(self.code._h, self.p, float(ebno_db), int(seed), int(first_frame), int(frames),
+                                            int(self.random_codewords), C.c_void_p(counters.data_ptr()), stream)
+        capi.check(rc, "cc_mc_run_chase_dev")
+        return counters
+
+
 class _ShardedSimulation:
     """What the AWGN, the discrete-channel and the burst-channel ladders share: the shard of this rank, the one all-reduce per point,
     rank 0's log file (its success agreed with every rank before the first collective) and the adaptive ladder."""
@@ -234,11 +254,15 @@ class awgn_simulation(_ShardedSimulation):
     """awgn_simulation(decoder, step = 0.5, seed = 0) -- simulation.h:71-83."""
 
     def __init__(self, code, step=0.5, seed=0, random_codewords=False, backend=None, log_dir=None,
-                 max_samples=None, start=None, stop=None, samples_per_point=None):
+                 max_samples=None, start=None, stop=None, samples_per_point=None, chase=None):
         self.code = code
         self.step = float(step)
         self.seed = int(seed)
-        self.backend = backend if backend is not None else DeviceBackend(code, random_codewords)
+        # chase=p: every frame goes through Chase-II (ChaseBackend); the log name carries -chaseP
+        self.chase = None if chase is None else int(chase)
+        if backend is None:
+            backend = DeviceBackend(code, random_codewords) if chase is None else ChaseBackend(code, chase, random_codewords)
+        self.backend = backend
         self.log_dir = log_dir
         self.max_samples = max_samples
         self.samples_per_point = samples_per_point  # fixed frame count per point instead of the adaptive rule
@@ -263,7 +287,8 @@ class awgn_simulation(_ShardedSimulation):
 
     def __call__(self):
         """awgn_simulation::operator()(): the whole ladder; rank 0 writes the reference-format log."""
-        return self._ladder(self.code.to_string() + ".log", "ebno", lambda ebno: ebno)
+        suffix = "" if self.chase is None else "-chase%d" % self.chase
+        return self._ladder(self.code.to_string() + suffix + ".log", "ebno", lambda ebno: ebno)
 
 
 # ---- discrete memoryless channels (cc_mc_run_discrete_dev): the BSC and BEC the reference's README leaves as a TODO --

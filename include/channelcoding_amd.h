@@ -219,6 +219,35 @@ int cc_correct_soft_batch_dev(const cc_code *code, const float *d_llr, const uin
                               const uint32_t *d_erasure_offsets, uint8_t *d_hard, float *d_L, uint16_t *d_iters,
                               int32_t *d_status, size_t B, void *stream);
 
+/* ---- Chase-II soft-decision correct for binary BCH codes (Chase's algorithm 2).  The reference has no such decoder:
+ *      it stands between cyclic::correct_(hard_decision_tag), cyclic.h:207-252, whose bounded-distance decoding it runs
+ *      on every test pattern, and cyclic::correct_(soft_decision_tag), cyclic.h:254-267, whose input it takes.
+ *      Handles: BCH with a hard tag (PGZ, BM or Euklid -- the tag does not influence the result), q = 3..8, 2t <= 32,
+ *      full length or shortened; p = 0 .. CC_CHASE_MAX_P.  A frame is n finite floats y (NaN: unspecified; zeros,
+ *      denormals and equal magnitudes are ordinary inputs).
+ *        hard decision  z_i = (y_i < 0), so -0.0 gives 0 (cyclic.h:163-173)
+ *        reliability    key_i = bits(y_i) & 0x7fffffff compared as unsigned, ties to the lower position;
+ *                       L_0 .. L_(p-1) = the p positions with the smallest keys, in that order
+ *        test patterns  j in [0, 2^p): bit i of j flips position L_i of z
+ *        candidate      of pattern j: the unique codeword within Hamming distance t of z ^ e_j, if there is one
+ *                       (bounded distance: Berlekamp-Massey, 2 deg lambda <= 2t, deg lambda roots below n; the BM
+ *                       tag's admission of deg lambda > t does not apply; for a shortened code a word of the
+ *                       shortened code, so a locator root at a position >= n means no candidate)
+ *        metric         M(c) = float32 sum of |y_i| over the positions with c_i != z_i, from +0.0f in ascending i
+ *        winner         the candidate with the smallest M, equal M to the smallest j
+ *      Per frame: out = the winner (n bytes; z when no pattern has a candidate), nerr = positions where out differs
+ *      from z (-1), metric = M of the winner (+0.0f), status = CC_FRAME_OK (CC_FRAME_LOCATOR).  nerr, metric and
+ *      status may be NULL.
+ *      Refused before a device is asked for, in this order: NULL code / llr / out -> CC_ERR_INVALID_ARGUMENT; a
+ *      cc_minsum_create handle -> CC_ERR_INVALID_ARGUMENT; an RS handle, a min-sum handle, q > 8, 2t > 32,
+ *      p > CC_CHASE_MAX_P (or p > n) -> CC_ERR_UNSUPPORTED with cc_last_error naming which; then a CC_DEVICE_NONE
+ *      handle answers CC_ERR_NO_DEVICE.  No GMD, no erasures, no bit-per-bit or woven containers. ---- */
+#define CC_CHASE_MAX_P 6
+int cc_correct_chase_batch(const cc_code *code, const float *llr /* B*n */, uint32_t p, uint8_t *out /* B*n */,
+                           int32_t *nerr, float *metric, int32_t *status, size_t B);
+int cc_correct_chase_batch_dev(const cc_code *code, const float *d_llr, uint32_t p, uint8_t *d_out, int32_t *d_nerr,
+                               float *d_metric, int32_t *d_status, size_t B, void *stream);
+
 /* ---- decode = correct + message extraction: cyclic::decode cyclic.h:313-327 (+ free decode :42-51) ---- */
 int cc_extract_batch(const cc_code *code, const uint8_t *cw /* B*n */, uint8_t *msg /* B*l */, size_t B);
 int cc_extract_batch_dev(const cc_code *code, const uint8_t *d_cw, uint8_t *d_msg, size_t B, void *stream);
@@ -260,6 +289,13 @@ int cc_mc_run_dev(const cc_code *code, double ebno_db, uint64_t seed, uint64_t f
 int cc_awgn_llr_dev(const cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
                     int random_codewords, float *d_llr, uint8_t *d_sent, void *stream);
 double cc_sigma(const cc_code *code, double ebno_db); /* simulation.c++:83-85 */
+/* cc_mc_run_dev (simulation.c++:95-150) with the decoder swapped for cc_correct_chase_batch_dev at p: the same handles
+ * and refusals as that call (NULL code / counters first).  The counter slots are cc_mc_run_dev's; CC_MC_ITER_SUM and
+ * the histogram are not touched.  By definition the counters equal what cc_awgn_llr_dev followed by
+ * cc_correct_chase_batch_dev and a comparison with the words sent would count, and depend only on (seed, ebno, p, the
+ * set of global frames). */
+int cc_mc_run_chase_dev(const cc_code *code, uint32_t p, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
+                        int random_codewords, uint64_t *d_counters, void *stream);
 
 /* ---- batched Monte-Carlo over discrete memoryless channels: the BSC and the BEC the reference's README leaves as a
  *      TODO, both at once, and for RS codes the q-ary symmetric and the symbol erasure channel.  A symbol is erased

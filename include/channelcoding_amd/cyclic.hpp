@@ -284,6 +284,7 @@ struct batch_result {
   std::vector<uint16_t> iters;  // soft algorithms: index of the returning iteration
   std::vector<float> L;         // soft algorithms, when requested
   std::vector<uint8_t> msg;     // decode_batch: B * l message symbols
+  std::vector<float> metric;    // correct_chase_batch: sum of |y| over the positions the winner differs from sign(y) in
 };
 
 template <int Family, unsigned q, typename Capability, typename Algorithm, unsigned N, typename Coding, unsigned mu,
@@ -522,6 +523,31 @@ class primitive_bch : public code_base<CC_FAMILY_BCH, q, Capability, Sigma, N, C
 public:
   using Base::Base;
   primitive_bch() : Base() {}
+
+  // ---- Chase-II (new; cc_correct_chase_batch): the 2^p test patterns over the p least reliable values of y, each
+  // decoded to within t errors, the candidate nearest to y returned.  Hard tags, q <= 8, 2t <= 32, p <= CC_CHASE_MAX_P;
+  // throws decoding_failure when no pattern has a candidate, as correct does for a frame it cannot decode ----
+  std::vector<uint8_t> correct_chase(const std::vector<float> &y, unsigned p) const {
+    if (y.size() != N) throw std::runtime_error("Length of received sequence does not match code length");
+    std::vector<uint8_t> out(N);
+    int32_t status = CC_FRAME_OK;
+    detail::check(cc_correct_chase_batch(this->handle.get(), y.data(), p, out.data(), nullptr, nullptr, &status, 1),
+                  "cc_correct_chase_batch");
+    if (status != CC_FRAME_OK) throw decoding_failure(detail::failure_text(status));
+    return out;
+  }
+  // B frames of n values, frame-contiguous: words, nerr, status and metric of every frame (failed frames do not throw)
+  batch_result correct_chase_batch(const float *values, size_t B, unsigned p) const {
+    batch_result r;
+    r.words.resize(B * N);
+    r.status.resize(B);
+    r.nerr.resize(B);
+    r.metric.resize(B);
+    detail::check(cc_correct_chase_batch(this->handle.get(), values, p, r.words.data(), r.nerr.data(), r.metric.data(),
+                                         r.status.data(), B),
+                  "cc_correct_chase_batch");
+    return r;
+  }
 };
 
 template <unsigned q, typename Capability, typename Sigma = peterson_gorenstein_zierler_tag, unsigned N = (1u << q) - 1,
