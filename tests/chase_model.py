@@ -27,9 +27,9 @@ def hard(y):
 
 
 def least_reliable(y, count=MAX_P):
-    """(B, count) positions in the order of the contract"""
+    """(B, min(count, n)) positions in the order of the contract"""
     keys = np.ascontiguousarray(y, np.float32).view(np.uint32) & np.uint32(0x7FFFFFFF)
-    return np.argsort(keys, axis=1, kind="stable")[:, :count]
+    return np.argsort(keys, axis=1, kind="stable")[:, : min(count, keys.shape[1])]
 
 
 def metric(y, z, c):
@@ -42,8 +42,10 @@ def metric(y, z, c):
 
 
 def candidates(dec, y, max_p=MAX_P):
-    """words (B, 2^max_p, n) u8, ok (B, 2^max_p) bool, M (B, 2^max_p) f32 of every test pattern"""
+    """words (B, 2^max_p, n) u8, ok (B, 2^max_p) bool, M (B, 2^max_p) f32 of every test pattern; a frame of n < max_p
+    positions has the 2^n patterns of p = n and no more"""
     y = np.ascontiguousarray(y, np.float32).reshape(-1, dec.n)
+    max_p = min(max_p, dec.n)
     B, n, J = y.shape[0], dec.n, 1 << max_p
     z = hard(y)
     L = least_reliable(y, max_p)
@@ -64,6 +66,8 @@ def candidates(dec, y, max_p=MAX_P):
 def pick(cand, p):
     """the contract's outputs for p: out (B, n) u8, nerr (B,) i32, status (B,) i32, metric (B,) f32, winner (B,) (-1: none)"""
     J = 1 << p
+    if J > cand["ok"].shape[1]:
+        raise ValueError("p = %d asks for %d test patterns, %d were decoded" % (p, J, cand["ok"].shape[1]))
     ok, M, z = cand["ok"][:, :J], cand["M"][:, :J], cand["z"]
     B = z.shape[0]
     out, nerr = z.copy(), np.full(B, -1, np.int32)
@@ -80,4 +84,4 @@ def pick(cand, p):
 
 
 def chase(dec, y, p):
-    return pick(candidates(dec, y, max(p, 0)), p)
+    return pick(candidates(dec, y, max(p, 0)), min(p, dec.n))

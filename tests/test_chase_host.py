@@ -95,6 +95,45 @@ def test_model_against_brute_force():
     assert ties > 0  # two different candidates of one frame with one metric: the rule "smallest j" decided
 
 
+@pytest.mark.parametrize("N", [5, 6])
+def test_model_on_frames_of_at_most_six_positions(N):
+    """BCH(7,4) shortened to N = 5 and 6: p runs up to N, where the selection takes every position and the 2^N test
+    patterns are all words of length N"""
+    dec = M.decoder(3, 1, N)
+    assert (dec.n, dec.l, dec.t) == (N, N - 3, 1)
+    msgs = ((np.arange(1 << dec.l)[:, None] >> np.arange(dec.l)[None, :]) & 1).astype(np.uint8)
+    words = dec.encode(msgs)
+    assert len({w.tobytes() for w in words}) == 1 << dec.l
+    rng = np.random.default_rng(310 + N)
+    y = awgn_llr(rng, words[rng.integers(0, 1 << dec.l, 200)], dec.l / dec.n, 2.0)
+    y[150:] = rng.choice(np.array([-1.0, -0.5, -0.0, 0.0, 0.5, 0.5, 1.0], np.float32), (50, N))
+    cand = M.candidates(dec, y)
+    assert cand["L"].shape == (200, N) and cand["ok"].shape == (200, 1 << N)
+    assert all(sorted(row) == list(range(N)) for row in cand["L"].tolist())  # p = n consumes every key
+    if N < M.MAX_P:
+        with pytest.raises(ValueError, match="test patterns"):
+            M.pick(cand, N + 1)
+    won_late = failures = 0
+    for p in (0, 1, 3, N):
+        got = M.pick(cand, p)
+        whole = M.chase(dec, y, p)
+        assert all(np.array_equal(got[k], whole[k]) for k in got)
+        for f in range(y.shape[0]):
+            z, best, ncand = brute_force(words, dec.t, y[f], p)
+            if best is None:
+                assert got["status"][f] == M.FRAME_LOCATOR and got["nerr"][f] == -1 and got["winner"][f] == -1, (p, f)
+                assert np.array_equal(got["out"][f], z) and got["metric"][f].view(np.uint32) == 0, (p, f)
+                failures += 1
+                continue
+            m, j, c = best
+            assert got["status"][f] == M.FRAME_OK and np.array_equal(got["out"][f], c), (p, f)
+            assert got["metric"][f].view(np.uint32) == m.view(np.uint32), (p, f)
+            assert got["nerr"][f] == int((c != z).sum()) and got["winner"][f] == j, (p, f)
+            won_late += j > 0
+    assert won_late > 20 and failures > 0
+    assert (M.pick(cand, N)["status"] == M.FRAME_OK).all()  # some pattern of p = n is a codeword
+
+
 def test_reliability_order_ties_and_zeros():
     y = np.array([[0.5, -0.5, 0.0, 1.0, -0.0, 0.5, -1.5, 1e-40, -1e-40]], np.float32)
     assert M.least_reliable(y, 6).tolist() == [[2, 4, 7, 8, 0, 1]]
@@ -179,6 +218,12 @@ def test_refusals_and_their_order():
         for call in calls():
             assert call(code, p) == capi.ERR_UNSUPPORTED, text
             assert text in lib.cc_last_error().decode(), text
+    # p beyond the frame length, after CC_CHASE_MAX_P: BCH(7,4) shortened to five positions
+    short = cc.primitive_bch(3, cc.errors(1), BM(), n=5, **NONE)
+    for call in calls():
+        assert call(short, 6) == capi.ERR_UNSUPPORTED and "frame length" in lib.cc_last_error().decode()
+        assert call(short, 5) == capi.ERR_NO_DEVICE
+        assert call(short, 7) == capi.ERR_UNSUPPORTED and "CC_CHASE_MAX_P" in lib.cc_last_error().decode()
     # the handle is looked at before p
     rs = refused[0][0]
     for call in calls():
