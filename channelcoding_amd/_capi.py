@@ -24,6 +24,7 @@ MC_FRAMES, MC_WORD_ERRORS, MC_BIT_ERRORS, MC_FAILURES, MC_UNDETECTED, MC_ITER_SU
 MC_CHANNEL_ERASURES = 7
 MC_ITER_HIST, MC_NCOUNTERS = 8, 64
 CHASE_MAX_P = 6
+GMD_ALL = 0
 HARD_ROUTE_WAVE, HARD_ROUTE_CHUNK, HARD_ROUTE_PLANES, HARD_ROUTE_LONG, HARD_ROUTE_WIDE, HARD_ROUTE_TRIALS = range(6)
 
 SOFT_ALGS = (ALG_MS, ALG_NMS, ALG_OMS, ALG_SCMS1, ALG_SCMS2, ALG_2DNMS)
@@ -95,6 +96,8 @@ _SIGNATURES = {
     "cc_correct_soft_batch_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "cc_correct_chase_batch": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, C.c_size_t]),
     "cc_correct_chase_batch_dev": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "cc_correct_gmd_batch": (C.c_int, [_VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, C.c_size_t]),
+    "cc_correct_gmd_batch_dev": (C.c_int, [_VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "cc_extract_batch": (C.c_int, [_VP, _VP, _VP, C.c_size_t]),
     "cc_extract_batch_dev": (C.c_int, [_VP, _VP, _VP, C.c_size_t, _VP]),
     "cc_decode_hard_batch": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t]),
@@ -103,6 +106,8 @@ _SIGNATURES = {
     "cc_awgn_llr_dev": (C.c_int, [_VP, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP, _VP, _VP]),
     "cc_sigma": (C.c_double, [_VP, C.c_double]),
     "cc_mc_run_chase_dev": (C.c_int, [_VP, C.c_uint32, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP, _VP]),
+    "cc_awgn_symbols_dev": (C.c_int, [_VP, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP, _VP, _VP, _VP]),
+    "cc_mc_run_gmd_dev": (C.c_int, [_VP, C.c_uint32, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP, _VP]),
     "cc_mc_run_discrete_dev": (C.c_int, [_VP, C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP,
                                          _VP]),
     "cc_discrete_channel_dev": (C.c_int, [_VP, C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int,

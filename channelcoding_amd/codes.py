@@ -160,6 +160,28 @@ def _torch_symbol_dtypes():
     return (torch.uint8, torch.int16) + ((torch.uint16,) if hasattr(torch, "uint16") else ())
 
 
+def symbol_reliability(y, q):
+    """(B, n q) BPSK channel values (numpy array or torch tensor) -> (w, rel) for correct_batch(w, gmd=, reliability=rel):
+    bit b of symbol i is value i q + b, w_i = sum_b (y < 0) << b, and rel_i is the |y| with the smallest key
+    bits(y) & 0x7fffffff among the symbol's q bits (the rule of cc_awgn_symbols_dev)."""
+    q = int(q)
+    if not 1 <= q <= 8:
+        raise ValueError("symbol_reliability serves q = 1 .. 8")
+    if y.shape[-1] % q:
+        raise CcError(capi.ERR_LENGTH, "symbol_reliability")
+    if _is_torch(y):
+        import torch
+        v = y.to(torch.float32).reshape(-1, y.shape[-1] // q, q)
+        weights = (1 << torch.arange(q, device=v.device, dtype=torch.int32))
+        w = ((v < 0).to(torch.int32) * weights).sum(dim=2).to(torch.uint8)
+        keys = v.contiguous().view(torch.int32) & 0x7FFFFFFF  # non-negative: signed order = unsigned order
+        return w, keys.min(dim=2).values.view(torch.float32)
+    v = np.ascontiguousarray(y, np.float32).reshape(-1, y.shape[-1] // q, q)
+    w = ((v < 0).astype(np.uint32) << np.arange(q, dtype=np.uint32)).sum(axis=2).astype(np.uint8)
+    keys = v.view(np.uint32) & np.uint32(0x7FFFFFFF)
+    return w, np.ascontiguousarray(keys.min(axis=2)).view(np.float32)
+
+
 def pack_bits(a):
     """One symbol per bit, shape (..., n) -> packed uint8, shape (..., ceil(n / 8)): the coefficient of x^p in bit p & 7
     of byte p >> 3 (numpy.packbits(bitorder="little")); bit 0 of each symbol counts, pad bits are 0.  numpy arrays on the
@@ -760,8 +782,13 @@ class cyclic:
         capi.check(lib.cc_extract_batch(self._h, _ptr(cw), _ptr(msg), cw.shape[0]), "cc_extract_batch")
         return msg
 
-    def correct_batch(self, b, erasures=None, want_L=False, packed=False, out=None, interleave=None, chase=None):
+    def correct_batch(self, b, erasures=None, want_L=False, packed=False, out=None, interleave=None, chase=None, gmd=None,
+                      reliability=None):
         """Returns a dict: out (B,n) u8, status (B,) i32, and nerr (hard) or iters [+ L] (soft).
+        gmd=m, reliability=r (RS, hard algorithms, q <= 8, 2t <= 32, step = 1): b holds the received symbols, r float32
+        reliabilities of the same shape, and the frames are decoded by GMD with m trials (cc_correct_gmd_batch; gmd=True:
+        all t + 1); the dict also carries metric (B,) f32.  It does not combine with erasures, packed, interleave, want_L,
+        out= or chase=.
         chase=p (binary BCH, hard algorithms, q <= 8, 2t <= 32): b holds float32 channel values and is decoded by
         Chase's algorithm 2 over the p least reliable positions (cc_correct_chase_batch); the dict also carries
         metric (B,) f32.  It does not combine with erasures, packed, interleave or want_L.
@@ -772,6 +799,13 @@ class cyclic:
         interleave=I (hard algorithms): b and out are symbol-interleaved blocks of shape (B / I, n, I), see interleave();
         status, nerr and the erasure lists are per frame f = b I + j, as without it; out= as with packed=True."""
         lib = capi.lib()
+        if gmd is not None or reliability is not None:
+            if (erasures is not None or want_L or packed or out is not None or interleave is not None
+                    or chase is not None):
+                raise TypeError("gmd= does not combine with erasures, want_L, packed=True, out=, interleave= or chase=")
+            if gmd is None or reliability is None:
+                raise TypeError("gmd= and reliability= go together")
+            return self._gmd(b, reliability, gmd)
         if chase is not None:
             if erasures is not None or want_L or packed or out is not None or interleave is not None:
                 raise TypeError("chase= does not combine with erasures, want_L, packed=True, out= or interleave=")
@@ -852,6 +886,41 @@ class cyclic:
                    "cc_correct_chase_batch")
         return dict(out=out, status=status, nerr=nerr, metric=metric)
 
+    def _gmd(self, b, rel, m):
+        """correct_batch(gmd=m, reliability=rel): uint8 symbols and float32 reliabilities, host arrays or device tensors."""
+        lib = capi.lib()
+        if m is not True and (isinstance(m, bool) or int(m) < 1):
+            raise ValueError("gmd= takes True (all trials) or m >= 1")
+        m = capi.GMD_ALL if m is True else int(m)
+        if b.shape[-1] != self.n or tuple(rel.shape) != tuple(b.shape):
+            raise CcError(capi.ERR_LENGTH, "correct_batch")
+        if _is_torch(b) != _is_torch(rel):
+            raise TypeError("gmd= takes the symbols and the reliabilities both on the host or both on the device")
+        if _is_torch(b):
+            import torch
+            if b.dtype != torch.uint8 or rel.dtype != torch.float32 or rel.device != b.device:
+                raise TypeError("gmd= takes uint8 symbols and float32 reliabilities on one device")
+            b, rel = b.contiguous(), rel.contiguous()
+            B, dev = b.numel() // self.n, b.device
+            out = torch.empty((B, self.n), dtype=torch.uint8, device=dev)
+            nerr = torch.empty(B, dtype=torch.int32, device=dev)
+            status = torch.empty(B, dtype=torch.int32, device=dev)
+            metric = torch.empty(B, dtype=torch.float32, device=dev)
+            capi.check(lib.cc_correct_gmd_batch_dev(self._h, _ptr(b), _ptr(rel), m, _ptr(out), _ptr(nerr), _ptr(metric),
+                                                    _ptr(status), B, _stream_handle(b)), "cc_correct_gmd_batch_dev")
+            return dict(out=out, status=status, nerr=nerr, metric=metric)
+        b, rel = np.asarray(b), np.asarray(rel)
+        if b.dtype.kind != "u" or rel.dtype.kind != "f":
+            raise TypeError("gmd= takes uint8 symbols and float32 reliabilities")
+        B = b.size // self.n
+        w = np.ascontiguousarray(b, np.uint8).reshape(B, self.n)
+        r = np.ascontiguousarray(rel, np.float32).reshape(B, self.n)
+        out = np.zeros((B, self.n), np.uint8)
+        nerr, status, metric = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.float32)
+        capi.check(lib.cc_correct_gmd_batch(self._h, _ptr(w), _ptr(r), m, _ptr(out), _ptr(nerr), _ptr(metric), _ptr(status),
+                                            B), "cc_correct_gmd_batch")
+        return dict(out=out, status=status, nerr=nerr, metric=metric)
+
     def _correct_batch_torch(self, b, erasures, want_L):
         import torch
         lib = capi.lib()
@@ -893,13 +962,15 @@ class cyclic:
             raise TypeError("hard decoding takes uint8 symbols or float32 soft values")
         return dict(out=out, status=status, nerr=nerr)
 
-    def decode_batch(self, b, erasures=None, packed=False, interleave=None, chase=None):
+    def decode_batch(self, b, erasures=None, packed=False, interleave=None, chase=None, gmd=None, reliability=None):
         """decode = correct + message extraction (cyclic.h:313-327); host arrays go through cc_decode_*_batch.
         chase=p: correct_batch(b, chase=p), then the messages of its words.
+        gmd=m, reliability=r: correct_batch(b, gmd=m, reliability=r), then the messages of its words.
         packed=True: b, out and msg are packed uint8 words, see pack_bits.
         interleave=I: b and out are blocks of shape (B / I, n, I), msg (B / I, l, I), see interleave()."""
-        if chase is not None:
-            res = self.correct_batch(b, erasures, packed=packed, interleave=interleave, chase=chase)
+        if chase is not None or gmd is not None or reliability is not None:
+            res = self.correct_batch(b, erasures, packed=packed, interleave=interleave, chase=chase, gmd=gmd,
+                                     reliability=reliability)
             res["msg"] = self.extract_batch(res["out"])
             return res
         if interleave is not None:

@@ -814,6 +814,69 @@ int cc_correct_chase_batch(const cc_code *code, const float *llr, uint32_t p, ui
                      });
 }
 
+/* ------------------------------ GMD ------------------------------ */
+
+// What the GMD calls refuse, in the order the header states, all of it before a device is asked for.
+static int gmd_supported(const cc_code *code, uint32_t trials) {
+  if (int rc = needs_code(code)) return rc;
+  if (code->tab.family != CC_FAMILY_RS) {
+    set_last_error("GMD decoding serves Reed-Solomon codes: this is a BCH handle");
+    return CC_ERR_UNSUPPORTED;
+  }
+  if (code->soft) {
+    set_last_error("GMD decoding needs a hard-decision tag (PGZ, BM or Euklid): this is a min-sum handle");
+    return CC_ERR_UNSUPPORTED;
+  }
+  if (code->wide) {
+    set_last_error("GMD decoding serves GF(2^q) with q <= 8");
+    return CC_ERR_UNSUPPORTED;
+  }
+  if (2 * code->tab.t > 32) {
+    set_last_error("GMD decoding serves codes with 2t <= 32");
+    return CC_ERR_UNSUPPORTED;
+  }
+  if (code->desc.step != 1) {
+    set_last_error("GMD decoding serves roots alpha^mu .. alpha^(mu + 2t - 1): step = 1 only");
+    return CC_ERR_UNSUPPORTED;
+  }
+  if (trials > code->tab.t + 1) {
+    set_last_error("GMD decoding: trials exceeds t + 1");
+    return CC_ERR_UNSUPPORTED;
+  }
+  if (code->device == CC_DEVICE_NONE) return CC_ERR_NO_DEVICE;
+  return CC_OK;
+}
+static unsigned gmd_trials(const cc_code *code, uint32_t trials) { return trials == CC_GMD_ALL ? code->tab.t + 1 : trials; }
+
+int cc_correct_gmd_batch_dev(const cc_code *code, const uint8_t *d_words, const float *d_rel, uint32_t trials, uint8_t *d_out,
+                             int32_t *d_nerr, float *d_metric, int32_t *d_status, size_t B, void *stream) {
+  if (!code || (B && (!d_words || !d_rel || !d_out))) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = gmd_supported(code, trials)) return rc;
+  DeviceGuard guard(code->device);
+  return launch_gmd(code, d_words, d_rel, gmd_trials(code, trials), d_out, d_nerr, d_metric, d_status, B,
+                    static_cast<hipStream_t>(stream));
+}
+
+int cc_correct_gmd_batch(const cc_code *code, const uint8_t *words, const float *rel, uint32_t trials, uint8_t *out,
+                         int32_t *nerr, float *metric, int32_t *status, size_t B) {
+  if (!code || (B && (!words || !rel || !out))) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = gmd_supported(code, trials)) return rc;
+  if (B == 0) return CC_OK;
+  const size_t n = code->tab.n;
+  if (!symbols_in_field(words, B * n, code->tab.q)) return CC_ERR_NOT_IN_FIELD;
+  DeviceGuard guard(code->device);
+  const unsigned m = gmd_trials(code, trials);
+  const StagedStream streams[] = {stage_in(0, words, n), stage_in(7, rel, n * sizeof(float)), stage_out(1, out, n),
+                                  stage_out(2, nerr, sizeof(int32_t)), stage_out(3, status, sizeof(int32_t)),
+                                  stage_out(4, metric, sizeof(float))};
+  return staged_call(code, B, n * (1 + sizeof(float)), 1, streams, 6, nullptr, nullptr,
+                     [&](size_t mm, void *const *d, const uint16_t *, const uint32_t *, hipStream_t s) {
+                       return launch_gmd(code, static_cast<const uint8_t *>(d[0]), static_cast<const float *>(d[1]), m,
+                                         static_cast<uint8_t *>(d[2]), static_cast<int32_t *>(d[3]),
+                                         static_cast<float *>(d[5]), static_cast<int32_t *>(d[4]), mm, s);
+                     });
+}
+
 /* ------------------------------ encode / extract ------------------------------ */
 
 int cc_encode_batch_dev(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, void *stream) {
@@ -1391,6 +1454,24 @@ int cc_mc_run_chase_dev(const cc_code *code, uint32_t p, double ebno_db, uint64_
   DeviceGuard guard(code->device);
   return mc_run_chase(const_cast<cc_code *>(code), p, ebno_db, seed, first_frame, frames, random_codewords, d_counters,
                       static_cast<hipStream_t>(stream));
+}
+
+int cc_mc_run_gmd_dev(const cc_code *code, uint32_t trials, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
+                      int random_codewords, uint64_t *d_counters, void *stream) {
+  if (!code || !d_counters) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = gmd_supported(code, trials)) return rc;
+  DeviceGuard guard(code->device);
+  return mc_run_gmd(const_cast<cc_code *>(code), gmd_trials(code, trials), ebno_db, seed, first_frame, frames,
+                    random_codewords, d_counters, static_cast<hipStream_t>(stream));
+}
+
+int cc_awgn_symbols_dev(const cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
+                        int random_codewords, uint8_t *d_words, float *d_rel, uint8_t *d_sent, void *stream) {
+  if (!code || (frames && (!d_words || !d_rel))) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = gmd_supported(code, 1)) return rc;
+  DeviceGuard guard(code->device);
+  return mc_awgn_symbols(const_cast<cc_code *>(code), ebno_db, seed, first_frame, frames, random_codewords, d_words, d_rel,
+                         d_sent, static_cast<hipStream_t>(stream));
 }
 
 int cc_awgn_llr_dev(const cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,

@@ -204,6 +204,10 @@ int launch_algebraic_chunk(const cc_code *code, bool float_in, const void *d_in,
 // d_nerr, d_metric and d_status may be nullptr
 int launch_chase(const cc_code *code, const float *d_llr, unsigned p, uint8_t *d_out, int32_t *d_nerr, float *d_metric,
                  int32_t *d_status, size_t B, hipStream_t stream);
+// gmd.hip: GMD over received symbols and reliabilities, RS with q <= 8, 2t <= 32, step = 1, 1 <= m <= t + 1 trials
+// (DESIGN 4.12); d_nerr, d_metric and d_status may be nullptr, d_out may be d_words
+int launch_gmd(const cc_code *code, const uint8_t *d_words, const float *d_rel, unsigned m, uint8_t *d_out, int32_t *d_nerr,
+               float *d_metric, int32_t *d_status, size_t B, hipStream_t stream);
 // bitslice.hip: syndromes of GF(2^8) codes on bit planes (32 frames per register)
 bool bitslice_supported(const cc_code *code);
 int launch_bitslice_syndromes(const cc_code *code, bool float_in, const void *d_in, uint8_t *d_out, uint8_t *d_synd, size_t B,
@@ -269,6 +273,10 @@ int mc_run(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, s
            uint64_t *d_counters, hipStream_t stream);
 int mc_run_chase(cc_code *code, unsigned p, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
                  int random_codewords, uint64_t *d_counters, hipStream_t stream);
+int mc_run_gmd(cc_code *code, unsigned m, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
+               int random_codewords, uint64_t *d_counters, hipStream_t stream);
+int mc_awgn_symbols(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
+                    uint8_t *d_words, float *d_rel, uint8_t *d_sent, hipStream_t stream);
 int mc_awgn(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
             float *d_llr, uint8_t *d_sent, hipStream_t stream);
 int mc_run_discrete(cc_code *code, double p_error, double p_erasure, uint64_t seed, uint64_t first_frame, size_t frames,

@@ -582,6 +582,117 @@ int mc_awgn(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// BPSK/AWGN for the symbols of an RS code: bit b of symbol i is value v = i q + b of a frame of n q channel
+// values, drawn exactly as awgn_kernel draws value v of a frame -- Philox counter (gf_lo, gf_hi, v >> 2, 0), word v & 3 of
+// the two Box-Muller pairs, y = (1 - 2 bit) + sigma z.  What leaves the kernel is the hard symbol w_i = sum_b (y_v < 0) << b
+// and rel_i = the |y_v| with the smallest key bits(y) & 0x7fffffff among the symbol's q bits: 5 bytes per symbol, never
+// the 4 q bytes of channel values.  G = lanes per frame (power of two >= n), lane i of a group owns symbol i; a lane
+// evaluates the one to three Philox blocks its bits fall into.
+namespace {
+
+__global__ void __launch_bounds__(256)
+awgn_symbols_kernel(uint8_t *__restrict__ words, float *__restrict__ rel, const uint8_t *__restrict__ sent, int n, int q,
+                    int group_log2, unsigned long long first_frame, unsigned long long frames, float sigma, uint32_t k0,
+                    uint32_t k1, unsigned long long *__restrict__ counters) {
+  const int G = 1 << group_log2;
+  const unsigned long long tid = static_cast<unsigned long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  const unsigned long long stride = (static_cast<unsigned long long>(gridDim.x) * blockDim.x) >> group_log2;
+  const int i = static_cast<int>(tid & static_cast<unsigned long long>(G - 1));
+  unsigned cherr = 0;  // wrong bits of w against the word sent
+  for (unsigned long long f = tid >> group_log2; i < n && f < frames; f += stride) {
+    const unsigned long long gf = first_frame + f;
+    const uint32_t s = sent ? sent[f * n + i] : 0u;
+    uint32_t w = 0, best = 0xFFFFFFFFu, quad = 0xFFFFFFFFu;
+    float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int b = 0; b < q; ++b) {
+      const uint32_t v = static_cast<uint32_t>(i * q + b);
+      if ((v >> 2) != quad) {
+        quad = v >> 2;
+        const Philox p = philox4x32_10(static_cast<uint32_t>(gf), static_cast<uint32_t>(gf >> 32), quad, 0u, k0, k1);
+        box_muller(p.c[0], p.c[1], z[0], z[1]);
+        box_muller(p.c[2], p.c[3], z[2], z[3]);
+      }
+      const uint32_t k = v & 3u;
+      const float zv = k == 0 ? z[0] : k == 1 ? z[1] : k == 2 ? z[2] : z[3];
+      const bool one = (s >> b) & 1u;
+      const float x = (one ? -1.0f : 1.0f) + sigma * zv;  // BPSK 0 -> +1
+      const bool hb = x < 0.0f;
+      w |= (hb ? 1u : 0u) << b;
+      cherr += hb != one;
+      best = umin32(best, f2u(x) & 0x7FFFFFFFu);
+    }
+    words[f * n + i] = static_cast<uint8_t>(w);
+    rel[f * n + i] = u2f(best);
+  }
+  if (counters) {
+    for (int m = 32; m >= 1; m >>= 1) cherr += __shfl_xor(cherr, m, 64);
+    if ((threadIdx.x & 63) == 0 && cherr)
+      atomicAdd(&counters[CC_MC_CHANNEL_BIT_ERRORS], static_cast<unsigned long long>(cherr));
+  }
+}
+
+// w and rel for frames [first, first + frames) of the words `sent` (nullptr: the all-zero word)
+int launch_awgn_symbols(const cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
+                        uint8_t *d_words, float *d_rel, const uint8_t *sent, unsigned long long *d_counters,
+                        hipStream_t stream) {
+  const int n = static_cast<int>(code->tab.n);
+  const float sigma = static_cast<float>(cc_sigma(code, ebno_db));
+  int group_log2 = 0;
+  while ((1 << group_log2) < n) ++group_log2;
+  const unsigned long long items = static_cast<unsigned long long>(frames) << group_log2;
+  hipLaunchKernelGGL(awgn_symbols_kernel, dim3(grid_for(code, items)), dim3(256), 0, stream, d_words, d_rel, sent, n,
+                     static_cast<int>(code->tab.q), group_log2, static_cast<unsigned long long>(first_frame),
+                     static_cast<unsigned long long>(frames), sigma, static_cast<uint32_t>(seed),
+                     static_cast<uint32_t>(seed >> 32), d_counters);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "awgn symbols kernel launch");
+  return CC_OK;
+}
+
+}  // namespace
+
+// cc_mc_run_gmd_dev: channel -> launch_gmd -> the hard decoders' counting pass.  The received symbols sit in w.hard and
+// are decoded in place, the reliabilities in w.llr.  Checked by the caller: an RS handle that launch_gmd serves.
+int mc_run_gmd(cc_code *code, unsigned m, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
+               int random_codewords, uint64_t *d_counters, hipStream_t stream) {
+  if (frames == 0) return CC_OK;
+  const size_t chunk = frames < MC_CHUNK ? frames : MC_CHUNK;
+  unsigned long long *counters = reinterpret_cast<unsigned long long *>(d_counters);
+  return mc_chunked(code, frames, chunk, chunk, stream, [&](McWorkspace &w, size_t done, size_t mm) -> int {
+    const uint8_t *sent;
+    int rc = transmitted_words(code, seed, first_frame + done, mm, random_codewords, w.sent, w.msg, nullptr, stream, &sent);
+    if (rc != CC_OK) return rc;
+    rc = launch_awgn_symbols(code, ebno_db, seed, first_frame + done, mm, w.hard, w.llr, sent, counters, stream);
+    if (rc != CC_OK) return rc;
+    rc = launch_gmd(code, w.hard, w.llr, m, w.hard, w.nerr, nullptr, w.status, mm, stream);
+    if (rc != CC_OK) return rc;
+    return launch_count(code, w, sent, mm, d_counters, stream);
+  });
+}
+
+// cc_awgn_symbols_dev: channel only, chunked so that the message scratch stays bounded
+int mc_awgn_symbols(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
+                    uint8_t *d_words, float *d_rel, uint8_t *d_sent, hipStream_t stream) {
+  if (frames == 0) return CC_OK;
+  const size_t n = code->tab.n;
+  if (!random_codewords) {  // one launch, no buffer of the workspace
+    const uint8_t *sent;
+    const int rc = transmitted_words(code, seed, first_frame, frames, 0, nullptr, nullptr, d_sent, stream, &sent);
+    return rc != CC_OK ? rc
+                       : launch_awgn_symbols(code, ebno_db, seed, first_frame, frames, d_words, d_rel, sent, nullptr, stream);
+  }
+  const size_t chunk = frames < MC_CHUNK ? frames : MC_CHUNK;
+  return mc_chunked(code, frames, chunk, chunk, stream, [&](McWorkspace &w, size_t done, size_t mm) -> int {
+    const uint8_t *sent;
+    const int rc = transmitted_words(code, seed, first_frame + done, mm, 1, d_sent ? d_sent + done * n : w.sent, w.msg,
+                                     nullptr, stream, &sent);
+    return rc != CC_OK ? rc
+                       : launch_awgn_symbols(code, ebno_db, seed, first_frame + done, mm, d_words + done * n,
+                                             d_rel + done * n, sent, nullptr, stream);
+  });
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Discrete memoryless channels (BSC, BEC, both at once; for RS the q-ary symmetric and the symbol erasure channel).
 //
 //   class     symbol j of global frame gf draws u = word (j & 3) of Philox counter (gf_lo, gf_hi, j >> 2, 2):

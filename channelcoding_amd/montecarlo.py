@@ -167,6 +167,26 @@ class ChaseBackend(DeviceBackend):
         return counters
 
 
+class GmdBackend(DeviceBackend):
+    """The same shard through cc_mc_run_gmd_dev: BPSK/AWGN per symbol bit, then GMD with m trials on every frame (RS with
+    a hard tag, q <= 8, 2t <= 32, step = 1; m = True: all t + 1)."""
+
+    def __init__(self, code, m, random_codewords=False):
+        super().__init__(code, random_codewords)
+        if m is not True and (isinstance(m, bool) or int(m) < 1):
+            raise ValueError("gmd= takes True (all trials) or m >= 1")
+        self.m = capi.GMD_ALL if m is True else int(m)
+
+    def run(self, ebno_db, seed, first_frame, frames):
+        torch = self.torch
+        counters = torch.zeros(capi.MC_NCOUNTERS, dtype=torch.int64, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = capi.lib().cc_mc_run_gmd_dev(self.code._h, self.m, float(ebno_db), int(seed), int(first_frame), int(frames),
+                                          int(self.random_codewords), C.c_void_p(counters.data_ptr()), stream)
+        capi.check(rc, "cc_mc_run_gmd_dev")
+        return counters
+
+
 class _ShardedSimulation:
     """What the AWGN, the discrete-channel and the burst-channel ladders share: the shard of this rank, the one all-reduce per point,
     rank 0's log file (its success agreed with every rank before the first collective) and the adaptive ladder."""
@@ -254,14 +274,21 @@ class awgn_simulation(_ShardedSimulation):
     """awgn_simulation(decoder, step = 0.5, seed = 0) -- simulation.h:71-83."""
 
     def __init__(self, code, step=0.5, seed=0, random_codewords=False, backend=None, log_dir=None,
-                 max_samples=None, start=None, stop=None, samples_per_point=None, chase=None):
+                 max_samples=None, start=None, stop=None, samples_per_point=None, chase=None, gmd=None):
         self.code = code
         self.step = float(step)
         self.seed = int(seed)
         # chase=p: every frame goes through Chase-II (ChaseBackend); the log name carries -chaseP
         self.chase = None if chase is None else int(chase)
+        # gmd=m (RS): every frame goes through GMD with m trials (GmdBackend, True: all of them); the log name carries -gmdM
+        if gmd is not None and chase is not None:
+            raise TypeError("gmd= does not combine with chase=")
+        self.gmd = None if gmd is None else (int(code.t) + 1 if gmd is True else int(gmd))
         if backend is None:
-            backend = DeviceBackend(code, random_codewords) if chase is None else ChaseBackend(code, chase, random_codewords)
+            if gmd is not None:
+                backend = GmdBackend(code, gmd, random_codewords)
+            else:
+                backend = DeviceBackend(code, random_codewords) if chase is None else ChaseBackend(code, chase, random_codewords)
         self.backend = backend
         self.log_dir = log_dir
         self.max_samples = max_samples
@@ -288,6 +315,8 @@ class awgn_simulation(_ShardedSimulation):
     def __call__(self):
         """awgn_simulation::operator()(): the whole ladder; rank 0 writes the reference-format log."""
         suffix = "" if self.chase is None else "-chase%d" % self.chase
+        if self.gmd is not None:
+            suffix = "-gmd%d" % self.gmd
         return self._ladder(self.code.to_string() + suffix + ".log", "ebno", lambda ebno: ebno)
 
 

@@ -248,6 +248,45 @@ int cc_correct_chase_batch(const cc_code *code, const float *llr /* B*n */, uint
 int cc_correct_chase_batch_dev(const cc_code *code, const float *d_llr, uint32_t p, uint8_t *d_out, int32_t *d_nerr,
                                float *d_metric, int32_t *d_status, size_t B, void *stream);
 
+/* ---- GMD soft-decision correct for Reed-Solomon codes (Forney's generalized-minimum-distance decoding): the 0, 2, 4, ..
+ *      least reliable symbols are erased, every trial is decoded with errors and erasures, and the candidate nearest to
+ *      what was received wins.  The reference has no such decoder; it runs the errors-and-erasures decoding of
+ *      cyclic::correct_(hard_decision_tag), cyclic.h:207-252, once per trial.
+ *      Handles: RS with a hard tag (PGZ, BM or Euklid; the tag does not influence the result), q = 3..8, 2t <= 32, full
+ *      length or shortened, any mu the handle accepts, step = 1.
+ *      A frame is n received symbols w and n finite floats r.  NaN is unspecified.  Zeros, denormals, negative values
+ *      and equal magnitudes are ordinary inputs.
+ *        reliability  key_i = bits(r_i) & 0x7fffffff compared as unsigned, so the sign of r is ignored.  Ties go to the
+ *                     lower position.  E_0 .. E_(2t-1) are the 2t positions with the smallest keys, in that order.
+ *                     n >= 2t + 1 always holds.
+ *        trials       m = trials, 1 <= m <= t + 1.  CC_GMD_ALL means t + 1.  Trial tau in [0, m) erases
+ *                     {E_0 .. E_(2 tau - 1)}.
+ *        candidate    of trial tau: the unique codeword that differs from w in at most t - tau positions outside the
+ *                     erased set, if there is one.  Inside the erased set anything goes.  This is bounded distance: two
+ *                     such words would differ in <= 2t < d positions.  The BM tag's admission of deg lambda > t does not
+ *                     apply.  For a shortened code the word must belong to the shortened code, so a locator root at a
+ *                     position >= n means no candidate.  The received value at an erased position does not influence the
+ *                     candidate.
+ *        metric       M(c) is the float32 sum of |r_i| over the positions with c_i != w_i, from +0.0f in ascending i
+ *                     (no contraction, no reassociation).  The erased positions that the candidate leaves as received do
+ *                     not count.
+ *        winner       The smallest M wins.  Equal M goes to the smallest tau.
+ *      Per frame: out is the winner; it is w if no trial has a candidate.  nerr is the number of positions where
+ *      out != w, or -1.  metric is M, or +0.0f.  status is CC_FRAME_OK, or CC_FRAME_LOCATOR.  nerr, metric and status may
+ *      be NULL.  With m = t + 1 every frame has a candidate: trial t decodes on erasures alone.  With m = 1 the call is
+ *      bounded-distance hard decoding.
+ *      Refused before a device is asked for, in this order, each unsupported case with a cc_last_error text that names
+ *      it: NULL code / words / rel / out (unless B = 0) -> CC_ERR_INVALID_ARGUMENT; a cc_minsum_create handle ->
+ *      CC_ERR_INVALID_ARGUMENT; a BCH handle, a min-sum handle, q > 8, 2t > 32, step != 1, trials > t + 1 ->
+ *      CC_ERR_UNSUPPORTED; then a CC_DEVICE_NONE handle answers CC_ERR_NO_DEVICE.  The host entry answers
+ *      CC_ERR_NOT_IN_FIELD for a symbol >= 2^q, as cc_correct_hard_batch does.  No packed or interleaved form, no
+ *      caller-supplied erasures, no new cc_algorithm value. ---- */
+#define CC_GMD_ALL 0u
+int cc_correct_gmd_batch(const cc_code *code, const uint8_t *words /* B*n */, const float *rel /* B*n */, uint32_t trials,
+                         uint8_t *out /* B*n */, int32_t *nerr, float *metric, int32_t *status, size_t B);
+int cc_correct_gmd_batch_dev(const cc_code *code, const uint8_t *d_words, const float *d_rel, uint32_t trials, uint8_t *d_out,
+                             int32_t *d_nerr, float *d_metric, int32_t *d_status, size_t B, void *stream);
+
 /* ---- decode = correct + message extraction: cyclic::decode cyclic.h:313-327 (+ free decode :42-51) ---- */
 int cc_extract_batch(const cc_code *code, const uint8_t *cw /* B*n */, uint8_t *msg /* B*l */, size_t B);
 int cc_extract_batch_dev(const cc_code *code, const uint8_t *d_cw, uint8_t *d_msg, size_t B, void *stream);
@@ -296,6 +335,21 @@ double cc_sigma(const cc_code *code, double ebno_db); /* simulation.c++:83-85 */
  * set of global frames). */
 int cc_mc_run_chase_dev(const cc_code *code, uint32_t p, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
                         int random_codewords, uint64_t *d_counters, void *stream);
+/* BPSK/AWGN for the symbols of an RS code, handles and refusals as cc_correct_gmd_batch_dev.  Bit b of symbol i is value
+ * v = i q + b of a frame of n q channel values and is drawn exactly as cc_awgn_llr_dev draws value v of a frame: Philox
+ * counter (gf_lo, gf_hi, v >> 2, 0), the same Box-Muller pairing, y = (1 - 2 bit) + sigma z, sigma = cc_sigma(code, ebno).
+ * Written: w_i = sum_b (y_v < 0) << b and rel_i = the |y_v| with the smallest key among the symbol's q bits (5 bytes per
+ * symbol; the channel values themselves are never stored), and to d_sent, if not NULL, the words sent: those of
+ * cc_discrete_channel_dev for an RS handle (random_codewords != 0), or all-zero. */
+int cc_awgn_symbols_dev(const cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
+                        int random_codewords, uint8_t *d_words, float *d_rel, uint8_t *d_sent /* or NULL */, void *stream);
+/* Monte-Carlo over that channel with cc_correct_gmd_batch_dev at `trials`: refusals as that call (NULL code / counters
+ * first).  The counter slots are those of cc_mc_run_discrete_dev on an RS handle (bit errors count symbols);
+ * CC_MC_CHANNEL_BIT_ERRORS is the wrong bits of w against the word sent; CC_MC_ITER_SUM and the histogram are not touched.
+ * By definition the counters equal what cc_awgn_symbols_dev followed by cc_correct_gmd_batch_dev and a comparison with
+ * the words sent would count, and depend only on (seed, ebno, trials, the set of global frames). */
+int cc_mc_run_gmd_dev(const cc_code *code, uint32_t trials, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
+                      int random_codewords, uint64_t *d_counters, void *stream);
 
 /* ---- batched Monte-Carlo over discrete memoryless channels: the BSC and the BEC the reference's README leaves as a
  *      TODO, both at once, and for RS codes the q-ary symmetric and the symbol erasure channel.  A symbol is erased

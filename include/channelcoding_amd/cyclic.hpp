@@ -284,7 +284,8 @@ struct batch_result {
   std::vector<uint16_t> iters;  // soft algorithms: index of the returning iteration
   std::vector<float> L;         // soft algorithms, when requested
   std::vector<uint8_t> msg;     // decode_batch: B * l message symbols
-  std::vector<float> metric;    // correct_chase_batch: sum of |y| over the positions the winner differs from sign(y) in
+  std::vector<float> metric;    // correct_chase_batch: sum of |y| over the positions the winner differs from sign(y) in;
+                                // correct_gmd_batch: sum of |rel| over the positions the winner differs from the input in
 };
 
 template <int Family, unsigned q, typename Capability, typename Algorithm, unsigned N, typename Coding, unsigned mu,
@@ -558,6 +559,35 @@ class rs : public code_base<CC_FAMILY_RS, q, Capability, Sigma, N, Coding, mu, s
 public:
   using Base::Base;
   rs() : Base() {}
+
+  // ---- GMD (new; cc_correct_gmd_batch): trial tau erases the 2 tau least reliable symbols and decodes with errors and
+  // erasures, the candidate nearest to the received word in the reliabilities is returned.  Hard tags, q <= 8, 2t <= 32,
+  // step = 1, 1 <= trials <= t + 1 (CC_GMD_ALL: t + 1); throws decoding_failure when no trial has a candidate, as
+  // correct does for a frame it cannot decode ----
+  std::vector<uint8_t> correct_gmd(const std::vector<uint8_t> &word, const std::vector<float> &rel,
+                                   unsigned trials = CC_GMD_ALL) const {
+    if (word.size() != N || rel.size() != N) throw std::runtime_error("Length of received sequence does not match code length");
+    std::vector<uint8_t> out(N);
+    int32_t status = CC_FRAME_OK;
+    detail::check(cc_correct_gmd_batch(this->handle.get(), word.data(), rel.data(), trials, out.data(), nullptr, nullptr,
+                                       &status, 1),
+                  "cc_correct_gmd_batch");
+    if (status != CC_FRAME_OK) throw decoding_failure(detail::failure_text(status));
+    return out;
+  }
+  // B frames of n symbols and n reliabilities, frame-contiguous: words, nerr, status and metric of every frame (failed
+  // frames do not throw)
+  batch_result correct_gmd_batch(const uint8_t *words, const float *rel, size_t B, unsigned trials = CC_GMD_ALL) const {
+    batch_result r;
+    r.words.resize(B * N);
+    r.status.resize(B);
+    r.nerr.resize(B);
+    r.metric.resize(B);
+    detail::check(cc_correct_gmd_batch(this->handle.get(), words, rel, trials, r.words.data(), r.nerr.data(),
+                                       r.metric.data(), r.status.data(), B),
+                  "cc_correct_gmd_batch");
+    return r;
+  }
 };
 
 }  // namespace cyclic
