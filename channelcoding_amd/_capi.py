@@ -195,6 +195,13 @@ def lib():
     return _lib
 
 
+def gmd_trials(m):
+    """gmd=m as the `trials` argument of the GMD calls: True (all t + 1 trials) or m >= 1"""
+    if m is not True and (isinstance(m, bool) or int(m) < 1):
+        raise ValueError("gmd= takes True (all trials) or m >= 1")
+    return GMD_ALL if m is True else int(m)
+
+
 def check(status, where):
     if status != OK:
         raise CcError(status, where)

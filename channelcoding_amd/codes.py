@@ -854,9 +854,26 @@ class cyclic:
                                                  _ptr(status), B), "cc_correct_hard_batch")
         return dict(out=out, status=status, nerr=nerr)
 
+    def _soft_call(self, name, ins, arg):
+        """`name`(_dev for device tensors) over the contiguous inputs `ins`, B frames of n values each, with the decoder's
+        argument `arg`: allocates what the reliability-based decoders return, makes the call and returns the dict."""
+        if _is_torch(ins[0]):
+            import torch
+            B, dev = ins[0].numel() // self.n, ins[0].device
+            out = torch.empty((B, self.n), dtype=torch.uint8, device=dev)
+            nerr, status = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
+            metric = torch.empty(B, dtype=torch.float32, device=dev)
+            name, tail = name + "_dev", (_stream_handle(ins[0]),)
+        else:
+            B, tail = ins[0].size // self.n, ()
+            out = np.zeros((B, self.n), np.uint8)
+            nerr, status, metric = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.float32)
+        capi.check(getattr(capi.lib(), name)(self._h, *map(_ptr, ins), arg, _ptr(out), _ptr(nerr), _ptr(metric),
+                                             _ptr(status), B, *tail), name)
+        return dict(out=out, status=status, nerr=nerr, metric=metric)
+
     def _chase(self, b, p):
         """correct_batch(chase=p): float32 channel values, host array or device tensor."""
-        lib = capi.lib()
         p = int(p)
         if p < 0:
             raise ValueError("chase= takes p >= 0")
@@ -866,32 +883,15 @@ class cyclic:
             import torch
             if b.dtype != torch.float32:
                 raise TypeError("chase= takes float32 channel values")
-            b = b.contiguous()
-            B, dev = b.numel() // self.n, b.device
-            out = torch.empty((B, self.n), dtype=torch.uint8, device=dev)
-            nerr = torch.empty(B, dtype=torch.int32, device=dev)
-            status = torch.empty(B, dtype=torch.int32, device=dev)
-            metric = torch.empty(B, dtype=torch.float32, device=dev)
-            capi.check(lib.cc_correct_chase_batch_dev(self._h, _ptr(b), p, _ptr(out), _ptr(nerr), _ptr(metric),
-                                                      _ptr(status), B, _stream_handle(b)), "cc_correct_chase_batch_dev")
-            return dict(out=out, status=status, nerr=nerr, metric=metric)
+            return self._soft_call("cc_correct_chase_batch", [b.contiguous()], p)
         b = np.asarray(b)
         if b.dtype.kind != "f":
             raise TypeError("chase= takes float32 channel values")
-        B = b.size // self.n
-        y = np.ascontiguousarray(b, np.float32).reshape(B, self.n)
-        out = np.zeros((B, self.n), np.uint8)
-        nerr, status, metric = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.float32)
-        capi.check(lib.cc_correct_chase_batch(self._h, _ptr(y), p, _ptr(out), _ptr(nerr), _ptr(metric), _ptr(status), B),
-                   "cc_correct_chase_batch")
-        return dict(out=out, status=status, nerr=nerr, metric=metric)
+        return self._soft_call("cc_correct_chase_batch", [np.ascontiguousarray(b, np.float32)], p)
 
     def _gmd(self, b, rel, m):
         """correct_batch(gmd=m, reliability=rel): uint8 symbols and float32 reliabilities, host arrays or device tensors."""
-        lib = capi.lib()
-        if m is not True and (isinstance(m, bool) or int(m) < 1):
-            raise ValueError("gmd= takes True (all trials) or m >= 1")
-        m = capi.GMD_ALL if m is True else int(m)
+        m = capi.gmd_trials(m)
         if b.shape[-1] != self.n or tuple(rel.shape) != tuple(b.shape):
             raise CcError(capi.ERR_LENGTH, "correct_batch")
         if _is_torch(b) != _is_torch(rel):
@@ -900,26 +900,12 @@ class cyclic:
             import torch
             if b.dtype != torch.uint8 or rel.dtype != torch.float32 or rel.device != b.device:
                 raise TypeError("gmd= takes uint8 symbols and float32 reliabilities on one device")
-            b, rel = b.contiguous(), rel.contiguous()
-            B, dev = b.numel() // self.n, b.device
-            out = torch.empty((B, self.n), dtype=torch.uint8, device=dev)
-            nerr = torch.empty(B, dtype=torch.int32, device=dev)
-            status = torch.empty(B, dtype=torch.int32, device=dev)
-            metric = torch.empty(B, dtype=torch.float32, device=dev)
-            capi.check(lib.cc_correct_gmd_batch_dev(self._h, _ptr(b), _ptr(rel), m, _ptr(out), _ptr(nerr), _ptr(metric),
-                                                    _ptr(status), B, _stream_handle(b)), "cc_correct_gmd_batch_dev")
-            return dict(out=out, status=status, nerr=nerr, metric=metric)
+            return self._soft_call("cc_correct_gmd_batch", [b.contiguous(), rel.contiguous()], m)
         b, rel = np.asarray(b), np.asarray(rel)
         if b.dtype.kind != "u" or rel.dtype.kind != "f":
             raise TypeError("gmd= takes uint8 symbols and float32 reliabilities")
-        B = b.size // self.n
-        w = np.ascontiguousarray(b, np.uint8).reshape(B, self.n)
-        r = np.ascontiguousarray(rel, np.float32).reshape(B, self.n)
-        out = np.zeros((B, self.n), np.uint8)
-        nerr, status, metric = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.float32)
-        capi.check(lib.cc_correct_gmd_batch(self._h, _ptr(w), _ptr(r), m, _ptr(out), _ptr(nerr), _ptr(metric), _ptr(status),
-                                            B), "cc_correct_gmd_batch")
-        return dict(out=out, status=status, nerr=nerr, metric=metric)
+        return self._soft_call("cc_correct_gmd_batch", [np.ascontiguousarray(b, np.uint8), np.ascontiguousarray(rel, np.float32)],
+                               m)
 
     def _correct_batch_torch(self, b, erasures, want_L):
         import torch

@@ -756,37 +756,32 @@ int cc_correct_hard_f32_batch(const cc_code *code, const float *in, const uint16
   return hard_host(code, true, in, erasures, erasure_offsets, out, nerr, status, B);
 }
 
-/* ------------------------------ Chase-II ------------------------------ */
+/* ------------------------------ Chase-II, GMD ------------------------------ */
+
+static int unsupported(const std::string &why) {
+  set_last_error(why);
+  return CC_ERR_UNSUPPORTED;
+}
+
+// What both reliability-based decoders refuse first, in the order the header states; `name` decoding serves `family`.
+static int soft_decoder_supported(const cc_code *code, const std::string &name, int family) {
+  if (int rc = needs_code(code)) return rc;
+  if (code->tab.family != family)
+    return unsupported(name + (family == CC_FAMILY_BCH ? " decoding serves binary BCH codes: this is a Reed-Solomon handle"
+                                                       : " decoding serves Reed-Solomon codes: this is a BCH handle"));
+  if (code->soft)
+    return unsupported(name + " decoding needs a hard-decision tag (PGZ, BM or Euklid): this is a min-sum handle");
+  if (code->wide) return unsupported(name + " decoding serves GF(2^q) with q <= 8");
+  if (2 * code->tab.t > 32) return unsupported(name + " decoding serves codes with 2t <= 32");
+  return CC_OK;
+}
 
 // What the Chase calls refuse, in the order the header states, all of it before a device is asked for.
 static int chase_supported(const cc_code *code, uint32_t p) {
-  if (int rc = needs_code(code)) return rc;
-  if (code->tab.family != CC_FAMILY_BCH) {
-    set_last_error("Chase-II decoding serves binary BCH codes: this is a Reed-Solomon handle");
-    return CC_ERR_UNSUPPORTED;
-  }
-  if (code->soft) {
-    set_last_error("Chase-II decoding needs a hard-decision tag (PGZ, BM or Euklid): this is a min-sum handle");
-    return CC_ERR_UNSUPPORTED;
-  }
-  if (code->wide) {
-    set_last_error("Chase-II decoding serves GF(2^q) with q <= 8");
-    return CC_ERR_UNSUPPORTED;
-  }
-  if (2 * code->tab.t > 32) {
-    set_last_error("Chase-II decoding serves codes with 2t <= 32");
-    return CC_ERR_UNSUPPORTED;
-  }
-  if (p > CC_CHASE_MAX_P) {
-    set_last_error("Chase-II decoding: p exceeds CC_CHASE_MAX_P");
-    return CC_ERR_UNSUPPORTED;
-  }
-  if (p > code->tab.n) {
-    set_last_error("Chase-II decoding: p exceeds the frame length");
-    return CC_ERR_UNSUPPORTED;
-  }
-  if (code->device == CC_DEVICE_NONE) return CC_ERR_NO_DEVICE;
-  return CC_OK;
+  if (int rc = soft_decoder_supported(code, "Chase-II", CC_FAMILY_BCH)) return rc;
+  if (p > CC_CHASE_MAX_P) return unsupported("Chase-II decoding: p exceeds CC_CHASE_MAX_P");
+  if (p > code->tab.n) return unsupported("Chase-II decoding: p exceeds the frame length");
+  return code->device == CC_DEVICE_NONE ? CC_ERR_NO_DEVICE : CC_OK;
 }
 
 int cc_correct_chase_batch_dev(const cc_code *code, const float *d_llr, uint32_t p, uint8_t *d_out, int32_t *d_nerr,
@@ -814,37 +809,12 @@ int cc_correct_chase_batch(const cc_code *code, const float *llr, uint32_t p, ui
                      });
 }
 
-/* ------------------------------ GMD ------------------------------ */
-
 // What the GMD calls refuse, in the order the header states, all of it before a device is asked for.
 static int gmd_supported(const cc_code *code, uint32_t trials) {
-  if (int rc = needs_code(code)) return rc;
-  if (code->tab.family != CC_FAMILY_RS) {
-    set_last_error("GMD decoding serves Reed-Solomon codes: this is a BCH handle");
-    return CC_ERR_UNSUPPORTED;
-  }
-  if (code->soft) {
-    set_last_error("GMD decoding needs a hard-decision tag (PGZ, BM or Euklid): this is a min-sum handle");
-    return CC_ERR_UNSUPPORTED;
-  }
-  if (code->wide) {
-    set_last_error("GMD decoding serves GF(2^q) with q <= 8");
-    return CC_ERR_UNSUPPORTED;
-  }
-  if (2 * code->tab.t > 32) {
-    set_last_error("GMD decoding serves codes with 2t <= 32");
-    return CC_ERR_UNSUPPORTED;
-  }
-  if (code->desc.step != 1) {
-    set_last_error("GMD decoding serves roots alpha^mu .. alpha^(mu + 2t - 1): step = 1 only");
-    return CC_ERR_UNSUPPORTED;
-  }
-  if (trials > code->tab.t + 1) {
-    set_last_error("GMD decoding: trials exceeds t + 1");
-    return CC_ERR_UNSUPPORTED;
-  }
-  if (code->device == CC_DEVICE_NONE) return CC_ERR_NO_DEVICE;
-  return CC_OK;
+  if (int rc = soft_decoder_supported(code, "GMD", CC_FAMILY_RS)) return rc;
+  if (code->desc.step != 1) return unsupported("GMD decoding serves roots alpha^mu .. alpha^(mu + 2t - 1): step = 1 only");
+  if (trials > code->tab.t + 1) return unsupported("GMD decoding: trials exceeds t + 1");
+  return code->device == CC_DEVICE_NONE ? CC_ERR_NO_DEVICE : CC_OK;
 }
 static unsigned gmd_trials(const cc_code *code, uint32_t trials) { return trials == CC_GMD_ALL ? code->tab.t + 1 : trials; }
 

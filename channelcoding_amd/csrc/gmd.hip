@@ -6,11 +6,9 @@
 // A wavefront owns a group of F <= 64 / m frames (m = trials); lane = (frame slot, trial) = (lane / m, lane % m), the
 // lanes from F m on idle.
 //
-//   A  per frame, lane l owns the positions l + 64 c: w and r go to LDS once, the 2t syndromes of w are accumulated
-//      four per DPP reduction (S_i = sum_p w_p alpha^((mu + i) p)) and their logs written into the SL columns of the
-//      frame's m lanes -- one set serves all trials, erasing does not change the syndromes -- and E_0 .. E_(2t-1) are
-//      picked by 2t rounds of two wave-wide minima, on the key bits(r) & 0x7fffffff and, among its holders, on the
-//      position
+//   A  per frame (the steps shared with chase.hip are soft_lanes.hpp's): w and r go to LDS once, the logs of the 2t
+//      syndromes S_i = sum_p w_p alpha^((mu + i) p) into the SL columns of the frame's m lanes -- one set serves all
+//      trials, erasing does not change the syndromes -- and E_0 .. E_(2t-1) are picked on the keys of r
 //   B  per lane: bm_lds (lane_bm.hpp) with rho = 2 tau erasures E_0 .. E_(rho-1) pre-loaded, omega = S lambda mod
 //      x^deg written over the lane's S column (omega_k needs S_0 .. S_k only, so k runs downwards), then one loop over
 //      the positions 0 .. n-1 that evaluates the even and the odd part of lambda at X^-1 = alpha^-pos in the log
@@ -37,40 +35,22 @@
 //   155, the theorem every erasure decoder here rests on); its roots are positions of c's code, below n; the values
 //   outside the erased set are c - w there, e' of them non-zero.  An erased position whose value is 0 is a root that
 //   the candidate leaves as received: it counts as a root, not in nerr or in the metric.
-#include "cc_internal.hpp"
-#include "lane_bm.hpp"
-#include "wave_ops.hpp"
+#include "soft_lanes.hpp"
 
 namespace ccamd {
 namespace {
 
-// LDS writes of one lane read by another lane of the same wavefront: keep the compiler from moving them past here
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-struct GmdLayout {  // byte offsets inside one wavefront's LDS region
-  int SL, LL, BL, R, EL, W, bytes;
+// byte offsets inside one wavefront's LDS region; of the columns SL holds log S_i, then log omega_k in place (the
+// omega column), and BL log b_m, then the lane's (pos | e << 8) pairs
+struct GmdLayout : BmColumns {
+  int R, EL, W, bytes;
 };
-constexpr int kGmdTables = 1536;                               // ex [1024] + lg2 [256] u16, lg2 right behind ex
-constexpr int kGmdWaveBytes = (65536 - kGmdTables) / 4 & ~15;  // a workgroup stays within 64 KiB
 __host__ __device__ constexpr GmdLayout gmd_layout(int t2, int n, int F) {
-  const int nc = t2 + 1;
-  const int SL = 0;                    // u16 [t2][64]  log S_i, then log omega_k in place (the omega column)
-  const int LL = SL + 2 * t2 * 64;     // u16 [nc][64]  log lambda_m
-  const int BL = LL + 2 * nc * 64;     // u16 [nc][64]  log b_m, then the lane's (pos | e << 8) pairs
-  const int R = BL + 2 * nc * 64;      // f32 [F][n]    reliabilities
-  const int EL = R + 4 * F * n;        // u16 [F][t2]   E_0 .. E_(2t-1), then the winner's pairs
-  const int W = EL + 2 * F * t2;       // u8  [F][n]    received symbols, then the word to store
-  return GmdLayout{SL, LL, BL, R, EL, W, (W + F * n + 15) & ~15};  // per frame 5 n + 4 t bytes
-}
-// frames per wavefront: 64 / m, fewer where the symbols and reliabilities of that many frames do not fit
-inline int gmd_frames_per_wave(int t2, int n, int m) {
-  int F = 64 / m;
-  while (F > 1 && gmd_layout(t2, n, F).bytes > kGmdWaveBytes) --F;
-  return F;
+  const BmColumns bm = bm_columns(t2);
+  const int R = bm.end;           // f32 [F][n]   reliabilities
+  const int EL = R + 4 * F * n;   // u16 [F][t2]  E_0 .. E_(2t-1), then the winner's pairs
+  const int W = EL + 2 * F * t2;  // u8  [F][n]   received symbols, then the word to store
+  return GmdLayout{bm, R, EL, W, (W + F * n + 15) & ~15};  // per frame 5 n + 4 t bytes
 }
 
 // words / out are not __restrict__: out may be words (a group's frames are read in stage A and stored in stage C by
@@ -80,17 +60,14 @@ gmd_kernel(const AlgebraicTables *__restrict__ T, const uint8_t *words, const fl
            uint8_t *out, int32_t *__restrict__ nerr_out, float *__restrict__ metric_out, int32_t *__restrict__ status_out,
            unsigned long long B) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  uint8_t *ex = smem;                                         // [1024]
-  uint16_t *lg2 = reinterpret_cast<uint16_t *>(smem + 1024);  // [256]
-  stage_ex(T, ex);
-  stage_log16(T, lg2);
-  __syncthreads();
+  const uint8_t *ex = smem;
+  const uint16_t *lg2 = stage_tables(T, smem);
 
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int n = T->n, nn = T->nf, t2 = T->nroots, t = t2 / 2;
   const uint32_t mu = T->roots_log[0], twist = static_cast<uint32_t>(T->twist);
   const GmdLayout lay = gmd_layout(t2, n, F);
-  uint8_t *base = smem + kGmdTables + wid * lay.bytes;
+  uint8_t *base = smem + kSoftTables + wid * lay.bytes;
   uint16_t *SL = reinterpret_cast<uint16_t *>(base + lay.SL);
   uint16_t *LL = reinterpret_cast<uint16_t *>(base + lay.LL);
   uint16_t *BL = reinterpret_cast<uint16_t *>(base + lay.BL);
@@ -102,20 +79,12 @@ gmd_kernel(const AlgebraicTables *__restrict__ T, const uint8_t *words, const fl
   // positions lane + 64 c: alpha^(mu pos) and the step alpha^pos between consecutive syndromes
   bool valid[4];
   uint32_t e0[4], d1[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const int pos = lane + 64 * c;
-    valid[c] = pos < n;
-    e0[c] = (mu * static_cast<uint32_t>(pos)) % static_cast<uint32_t>(nn);
-    d1[c] = static_cast<uint32_t>(pos % nn);
-  }
+  lane_positions(lane, n, nn, mu, 1u, valid, e0, d1);
 
-  const unsigned long long ngroups = (B + F - 1) / F;
-  const unsigned long long wave = static_cast<unsigned long long>(blockIdx.x) * 4 + wid;
-  const unsigned long long nwaves = static_cast<unsigned long long>(gridDim.x) * 4;
-  for (unsigned long long group = wave; group < ngroups; group += nwaves) {
+  const GroupSteps gs = group_steps(B, F, wid);
+  for (unsigned long long group = gs.start; group < gs.count; group += gs.step) {
     const unsigned long long first = group * F;
-    const int frames = static_cast<int>((B - first) < static_cast<unsigned long long>(F) ? (B - first) : F);
+    const int frames = group_frames(B, first, F);
 
     // ---------------- A: w and r to LDS, syndromes of w, least reliable positions ----------------
     if (lane >= frames * m)  // idle lanes: S = 0, they solve nothing and write only their own columns
@@ -133,42 +102,18 @@ gmd_kernel(const AlgebraicTables *__restrict__ T, const uint8_t *words, const fl
           R[s * n + lane + 64 * c] = rv;
         }
         lw[c] = lg2[wv];  // log 0 = kLogZero: ex[kLogZero + e] = 0
-        key[c] = valid[c] ? (f2u(rv) & 0x7FFFFFFFu) : 0xFFFFFFFFu;
+        key[c] = reliability_key(valid[c], rv);
         ev[c] = e0[c];
       }
       for (int i0 = 0; i0 < t2; i0 += 4) {  // S_i0 .. S_(i0+3): four per reduction
-        uint32_t packed = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          uint32_t term = 0;
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            term ^= static_cast<uint32_t>(ex[lw[c] + ev[c]]);
-            ev[c] += d1[c];
-            ev[c] = umin32(ev[c], ev[c] - static_cast<uint32_t>(nn));
-          }
-          packed |= term << (8 * k);
-        }
-        packed = lane63(wave_xor(packed));
+        const uint32_t packed = four_syndromes(ev, d1, nn, [&](int c, uint32_t e) { return ex[lw[c] + e]; });
         if (lane < m) {
 #pragma unroll
           for (int k = 0; k < 4; ++k)
             if (i0 + k < t2) SL[(i0 + k) * 64 + s * m + lane] = lg2[(packed >> (8 * k)) & 0xFFu];
         }
       }
-      for (int i = 0; i < t2; ++i) {  // E_i: smallest key, ties to the lower position (n >= 2t + 1: there is one)
-        const uint32_t k01 = umin32(key[0], key[1]), k23 = umin32(key[2], key[3]);
-        const uint32_t kmin = lane63(wave_umin(umin32(k01, k23)));
-        uint32_t cand = 0xFFFFFFFFu;
-#pragma unroll
-        for (int c = 3; c >= 0; --c)
-          if (key[c] == kmin) cand = static_cast<uint32_t>(lane + 64 * c);
-        const uint32_t pmin = lane63(wave_umin(cand));
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          if (pmin == static_cast<uint32_t>(lane + 64 * c)) key[c] = 0xFFFFFFFFu;
-        if (lane == 0) EL[s * t2 + i] = static_cast<uint16_t>(pmin);
-      }
+      pick_least_reliable(key, lane, t2, [&](int i, uint32_t pos) { EL[s * t2 + i] = static_cast<uint16_t>(pos); });  // E_i
     }
     wave_sync();
 
@@ -187,13 +132,7 @@ gmd_kernel(const AlgebraicTables *__restrict__ T, const uint8_t *words, const fl
     }
     unsigned long long pm[4] = {0, 0, 0, 0};  // positions the trial erases
     const int rhow = static_cast<int>(wave_umax(rho));
-    for (int i = 0; i < rhow; ++i) {
-      const bool in = static_cast<uint32_t>(i) < rho;
-      const uint32_t li = EL[sl * t2 + i];
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        if (in && static_cast<int>(li >> 6) == c) pm[c] |= 1ull << (li & 63u);
-    }
+    for (int i = 0; i < rhow; ++i) mark_position(pm, static_cast<uint32_t>(i) < rho, EL[sl * t2 + i]);
 
     // roots of lambda, their values and the metric of the candidate, positions in ascending order
     const float *rrow = R + sl * n;
@@ -207,20 +146,17 @@ gmd_kernel(const AlgebraicTables *__restrict__ T, const uint8_t *words, const fl
         uint32_t even = 0, odd = 0, e = 0;
         for (int j = 0; j <= degw; j += 2) {
           even ^= ex[LL[j * 64 + lane] + e];
-          e += xinv;
-          e = umin32(e, e - static_cast<uint32_t>(nn));
+          e = addmod(e, xinv, nn);
           if (j + 1 <= degw) {  // wave-uniform
             odd ^= ex[LL[(j + 1) * 64 + lane] + e];
-            e += xinv;
-            e = umin32(e, e - static_cast<uint32_t>(nn));
+            e = addmod(e, xinv, nn);
           }
         }
         if (even == odd) {  // a root of lambda
           uint32_t num = 0, ek = 0;
           for (int k = 0; k < degw; ++k) {
             num ^= ex[SL[k * 64 + lane] + ek];
-            ek += xinv;
-            ek = umin32(ek, ek - static_cast<uint32_t>(nn));
+            ek = addmod(ek, xinv, nn);
           }
           uint32_t val = 0;
           if (num != 0 && odd != 0) {  // (odd = 0: a repeated root, the count below falls short of deg)
@@ -238,8 +174,7 @@ gmd_kernel(const AlgebraicTables *__restrict__ T, const uint8_t *words, const fl
           }
         }
         xinv = xinv == 0 ? static_cast<uint32_t>(nn) - 1u : xinv - 1u;
-        tw += twist;
-        tw = umin32(tw, tw - static_cast<uint32_t>(nn));
+        tw = addmod(tw, twist, nn);
       }
     }
 
@@ -259,10 +194,7 @@ gmd_kernel(const AlgebraicTables *__restrict__ T, const uint8_t *words, const fl
     if (mine && tau == winner) {
       const bool ok = best != 0xFFFFFFFFu;
       for (int k = 0; k < t2; ++k) EL[sl * t2 + k] = (ok && k < nroots) ? BL[k * 64 + lane] : static_cast<uint16_t>(0);
-      const unsigned long long frame = first + slot;
-      if (nerr_out) nerr_out[frame] = ok ? nz : -1;
-      if (metric_out) metric_out[frame] = ok ? M : 0.0f;
-      if (status_out) status_out[frame] = ok ? CC_FRAME_OK : CC_FRAME_LOCATOR;
+      store_verdict(nerr_out, metric_out, status_out, first + slot, ok, nz, M);
     }
     wave_sync();
     for (int s = 0; s < frames; ++s) {
@@ -288,16 +220,13 @@ int launch_gmd(const cc_code *code, const uint8_t *d_words, const float *d_rel, 
                float *d_metric, int32_t *d_status, size_t B, hipStream_t stream) {
   if (B == 0) return CC_OK;
   const int n = static_cast<int>(code->tab.n), t2 = code->h_alg.nroots;
-  const int F = gmd_frames_per_wave(t2, n, static_cast<int>(m));
-  const size_t lds = kGmdTables + 4 * static_cast<size_t>(gmd_layout(t2, n, F).bytes);
-  const unsigned long long groups = (B + F - 1) / F, wgs = (groups + 3) / 4;
-  const unsigned long long cap = static_cast<unsigned long long>(code->num_cus) * 8;
-  const dim3 grid(static_cast<unsigned>(wgs < cap ? wgs : cap));
-  hipLaunchKernelGGL(gmd_kernel, grid, dim3(256), lds, stream, code->d_alg, d_words, d_rel, static_cast<int>(m), F, d_out,
-                     d_nerr, d_metric, d_status, static_cast<unsigned long long>(B));
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "gmd kernel launch");
-  return CC_OK;
+  // 64 / m frames per wavefront, fewer where the symbols and reliabilities of that many frames do not fit
+  const int F = frames_per_wave(64 / static_cast<int>(m), [&](int f) { return gmd_layout(t2, n, f); });
+  const size_t lds = kSoftTables + 4 * static_cast<size_t>(gmd_layout(t2, n, F).bytes);
+  return launch_groups(code, B, F, "gmd kernel launch", [&](dim3 grid) {
+    hipLaunchKernelGGL(gmd_kernel, grid, dim3(256), lds, stream, code->d_alg, d_words, d_rel, static_cast<int>(m), F, d_out,
+                       d_nerr, d_metric, d_status, static_cast<unsigned long long>(B));
+  });
 }
 
 }  // namespace ccamd

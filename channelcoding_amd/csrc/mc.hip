@@ -467,6 +467,40 @@ static int launch_count(const cc_code *code, McWorkspace &w, const uint8_t *sent
   return CC_OK;
 }
 
+// One chunk of a Monte-Carlo route, frames [first, first + m): the words sent, channel(sent) writes what was received
+// into the workspace, decode() leaves its decisions in w.hard / w.status, and the counting pass compares them.
+template <class Channel, class Decode>
+static int mc_route(const cc_code *code, McWorkspace &w, uint64_t seed, uint64_t first, size_t m, int random_codewords,
+                    uint64_t *d_counters, hipStream_t stream, Channel channel, Decode decode) {
+  const uint8_t *sent;
+  int rc = transmitted_words(code, seed, first, m, random_codewords, w.sent, w.msg, nullptr, stream, &sent);
+  if (rc == CC_OK) rc = channel(sent);
+  if (rc == CC_OK) rc = decode();
+  return rc != CC_OK ? rc : launch_count(code, w, sent, m, d_counters, stream);
+}
+
+// The skeleton of a channel-only call: channel(done, m, sent) serves the frames [done, done + m) of the call.  One launch
+// and no buffer of the workspace when the all-zero word is sent, otherwise chunked so that the message scratch stays
+// bounded, the words sent into d_sent (n bytes per frame) or the workspace.
+template <class Channel>
+static int mc_channel_only(cc_code *code, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
+                           uint8_t *d_sent, hipStream_t stream, Channel channel) {
+  if (frames == 0) return CC_OK;
+  const size_t n = code->tab.n;
+  if (!random_codewords) {
+    const uint8_t *sent;
+    const int rc = transmitted_words(code, seed, first_frame, frames, 0, nullptr, nullptr, d_sent, stream, &sent);
+    return rc != CC_OK ? rc : channel(size_t(0), frames, sent);
+  }
+  const size_t chunk = frames < MC_CHUNK ? frames : MC_CHUNK;
+  return mc_chunked(code, frames, chunk, chunk, stream, [&](McWorkspace &w, size_t done, size_t m) -> int {
+    const uint8_t *sent;
+    const int rc = transmitted_words(code, seed, first_frame + done, m, 1, d_sent ? d_sent + done * n : w.sent, w.msg,
+                                     nullptr, stream, &sent);
+    return rc != CC_OK ? rc : channel(done, m, sent);
+  });
+}
+
 // The pre-check route (awgn_precheck_kernel) serves the diagonal min-sum kernels of the n = 129..256 codes and pays
 // once a fair share of the frames is clean: P(no channel error in n bits) = (1 - Q(1 / sigma))^n >= 1/4 -- from
 // ~5.7 dB on for BCH(255,231) (6 dB: 40 %, 8 dB: 91 %); below that the plain route is used, so 4 dB costs nothing.
@@ -514,18 +548,14 @@ int mc_run(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, s
   const bool precheck = mc_precheck_pays(code, ebno_db);
   unsigned long long *counters = reinterpret_cast<unsigned long long *>(d_counters);
   return mc_chunked(code, frames, chunk, chunk, stream, [&](McWorkspace &w, size_t done, size_t m) -> int {
+    if (!precheck)  // (a hard-decision decoder takes bits from the channel: the hard decisions as bytes in the same buffer)
+      return mc_route(code, w, seed, first_frame + done, m, random_codewords, d_counters, stream, [&](const uint8_t *sent) {
+        return launch_awgn(code, ebno_db, seed, first_frame + done, m, w.llr, sent, stream, counters, !code->soft);
+      }, [&] { return launch_decoder(code, w, nullptr, nullptr, m, stream); });
+    // channel + pre-check, the decoder on what is left, the counts
     const uint8_t *sent;
     int rc = transmitted_words(code, seed, first_frame + done, m, random_codewords, w.sent, w.msg, nullptr, stream, &sent);
     if (rc != CC_OK) return rc;
-    if (!precheck) {
-      // (a hard-decision decoder takes bits from the channel: the hard decisions as bytes in the same buffer)
-      rc = launch_awgn(code, ebno_db, seed, first_frame + done, m, w.llr, sent, stream, counters, !code->soft);
-      if (rc != CC_OK) return rc;
-      rc = launch_decoder(code, w, nullptr, nullptr, m, stream);
-      if (rc != CC_OK) return rc;
-      return launch_count(code, w, sent, m, d_counters, stream);
-    }
-    // channel + pre-check, the decoder on what is left, the counts
     uint32_t *ctl = w.list, *pool = w.list + 64, *list = w.list + 64 + POOL_WORDS;
     CC_HIP_TRY(hipMemsetAsync(ctl, 0, (64 + POOL_WORDS) * sizeof(uint32_t), stream));
     const float sigma = static_cast<float>(cc_sigma(code, ebno_db));
@@ -551,33 +581,18 @@ int mc_run_chase(cc_code *code, unsigned p, double ebno_db, uint64_t seed, uint6
   const size_t chunk = frames < MC_CHUNK ? frames : MC_CHUNK;
   unsigned long long *counters = reinterpret_cast<unsigned long long *>(d_counters);
   return mc_chunked(code, frames, chunk, chunk, stream, [&](McWorkspace &w, size_t done, size_t m) -> int {
-    const uint8_t *sent;
-    int rc = transmitted_words(code, seed, first_frame + done, m, random_codewords, w.sent, w.msg, nullptr, stream, &sent);
-    if (rc != CC_OK) return rc;
-    rc = launch_awgn(code, ebno_db, seed, first_frame + done, m, w.llr, sent, stream, counters);
-    if (rc != CC_OK) return rc;
-    rc = launch_chase(code, w.llr, p, w.hard, w.nerr, nullptr, w.status, m, stream);
-    if (rc != CC_OK) return rc;
-    return launch_count(code, w, sent, m, d_counters, stream);
+    return mc_route(code, w, seed, first_frame + done, m, random_codewords, d_counters, stream, [&](const uint8_t *sent) {
+      return launch_awgn(code, ebno_db, seed, first_frame + done, m, w.llr, sent, stream, counters);
+    }, [&] { return launch_chase(code, w.llr, p, w.hard, w.nerr, nullptr, w.status, m, stream); });
   });
 }
 
-// cc_awgn_llr_dev: channel only, chunked so that the message scratch stays bounded
+// cc_awgn_llr_dev: channel only
 int mc_awgn(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
             float *d_llr, uint8_t *d_sent, hipStream_t stream) {
-  if (frames == 0) return CC_OK;
-  const size_t n = code->tab.n;
-  if (!random_codewords) {  // one launch, no buffer of the workspace
-    const uint8_t *sent;
-    const int rc = transmitted_words(code, seed, first_frame, frames, 0, nullptr, nullptr, d_sent, stream, &sent);
-    return rc != CC_OK ? rc : launch_awgn(code, ebno_db, seed, first_frame, frames, d_llr, sent, stream);
-  }
-  const size_t chunk = frames < MC_CHUNK ? frames : MC_CHUNK;
-  return mc_chunked(code, frames, chunk, chunk, stream, [&](McWorkspace &w, size_t done, size_t m) -> int {
-    const uint8_t *sent;
-    const int rc = transmitted_words(code, seed, first_frame + done, m, 1, d_sent ? d_sent + done * n : w.sent, w.msg,
-                                     nullptr, stream, &sent);
-    return rc != CC_OK ? rc : launch_awgn(code, ebno_db, seed, first_frame + done, m, d_llr + done * n, sent, stream);
+  return mc_channel_only(code, seed, first_frame, frames, random_codewords, d_sent, stream,
+                         [&](size_t done, size_t m, const uint8_t *sent) {
+    return launch_awgn(code, ebno_db, seed, first_frame + done, m, d_llr + done * code->tab.n, sent, stream);
   });
 }
 
@@ -659,36 +674,20 @@ int mc_run_gmd(cc_code *code, unsigned m, double ebno_db, uint64_t seed, uint64_
   const size_t chunk = frames < MC_CHUNK ? frames : MC_CHUNK;
   unsigned long long *counters = reinterpret_cast<unsigned long long *>(d_counters);
   return mc_chunked(code, frames, chunk, chunk, stream, [&](McWorkspace &w, size_t done, size_t mm) -> int {
-    const uint8_t *sent;
-    int rc = transmitted_words(code, seed, first_frame + done, mm, random_codewords, w.sent, w.msg, nullptr, stream, &sent);
-    if (rc != CC_OK) return rc;
-    rc = launch_awgn_symbols(code, ebno_db, seed, first_frame + done, mm, w.hard, w.llr, sent, counters, stream);
-    if (rc != CC_OK) return rc;
-    rc = launch_gmd(code, w.hard, w.llr, m, w.hard, w.nerr, nullptr, w.status, mm, stream);
-    if (rc != CC_OK) return rc;
-    return launch_count(code, w, sent, mm, d_counters, stream);
+    return mc_route(code, w, seed, first_frame + done, mm, random_codewords, d_counters, stream, [&](const uint8_t *sent) {
+      return launch_awgn_symbols(code, ebno_db, seed, first_frame + done, mm, w.hard, w.llr, sent, counters, stream);
+    }, [&] { return launch_gmd(code, w.hard, w.llr, m, w.hard, w.nerr, nullptr, w.status, mm, stream); });
   });
 }
 
-// cc_awgn_symbols_dev: channel only, chunked so that the message scratch stays bounded
+// cc_awgn_symbols_dev: channel only
 int mc_awgn_symbols(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
                     uint8_t *d_words, float *d_rel, uint8_t *d_sent, hipStream_t stream) {
-  if (frames == 0) return CC_OK;
   const size_t n = code->tab.n;
-  if (!random_codewords) {  // one launch, no buffer of the workspace
-    const uint8_t *sent;
-    const int rc = transmitted_words(code, seed, first_frame, frames, 0, nullptr, nullptr, d_sent, stream, &sent);
-    return rc != CC_OK ? rc
-                       : launch_awgn_symbols(code, ebno_db, seed, first_frame, frames, d_words, d_rel, sent, nullptr, stream);
-  }
-  const size_t chunk = frames < MC_CHUNK ? frames : MC_CHUNK;
-  return mc_chunked(code, frames, chunk, chunk, stream, [&](McWorkspace &w, size_t done, size_t mm) -> int {
-    const uint8_t *sent;
-    const int rc = transmitted_words(code, seed, first_frame + done, mm, 1, d_sent ? d_sent + done * n : w.sent, w.msg,
-                                     nullptr, stream, &sent);
-    return rc != CC_OK ? rc
-                       : launch_awgn_symbols(code, ebno_db, seed, first_frame + done, mm, d_words + done * n,
-                                             d_rel + done * n, sent, nullptr, stream);
+  return mc_channel_only(code, seed, first_frame, frames, random_codewords, d_sent, stream,
+                         [&](size_t done, size_t mm, const uint8_t *sent) {
+    return launch_awgn_symbols(code, ebno_db, seed, first_frame + done, mm, d_words + done * n, d_rel + done * n, sent,
+                               nullptr, stream);
   });
 }
 
@@ -1040,9 +1039,6 @@ int mc_run_discrete(cc_code *code, double p_error, double p_erasure, uint64_t se
   const DiscreteThresholds th = discrete_thresholds(p_error, p_erasure);
   return mc_chunked(code, frames, chunk, workspace_frames_with_list(chunk), stream,
                     [&](McWorkspace &w, size_t done, size_t m) -> int {
-    const uint8_t *sent;
-    int rc = transmitted_words(code, seed, first_frame + done, m, random_codewords, w.sent, w.msg, nullptr, stream, &sent);
-    if (rc != CC_OK) return rc;
     DiscreteIO io;
     if (code->soft) {
       io.soft = w.llr;
@@ -1050,12 +1046,10 @@ int mc_run_discrete(cc_code *code, double p_error, double p_erasure, uint64_t se
       if (th.E) io = workspace_list(w, m, n);  // (no erasure can be drawn with E = 0: no list, NULL erasures)
       io.recv = reinterpret_cast<uint8_t *>(w.llr);
     }
-    rc = launch_discrete(code, th, seed, first_frame + done, m, sent, io,
-                         reinterpret_cast<unsigned long long *>(d_counters), stream);
-    if (rc != CC_OK) return rc;
-    rc = launch_decoder(code, w, io.er, io.off, m, stream);
-    if (rc != CC_OK) return rc;
-    return launch_count(code, w, sent, m, d_counters, stream);
+    return mc_route(code, w, seed, first_frame + done, m, random_codewords, d_counters, stream, [&](const uint8_t *sent) {
+      return launch_discrete(code, th, seed, first_frame + done, m, sent, io,
+                             reinterpret_cast<unsigned long long *>(d_counters), stream);
+    }, [&] { return launch_decoder(code, w, io.er, io.off, m, stream); });
   });
 }
 
@@ -1421,9 +1415,6 @@ int run_burst(cc_code *code, const cc_burst_channel &ch, const DetectorThreshold
   const size_t chunk = burst_chunk(frames, ch.interleave), n = code->tab.n;
   return mc_chunked(code, frames, chunk, det ? workspace_frames_with_list(chunk) : chunk, stream,
                     [&](McWorkspace &w, size_t done, size_t m) -> int {
-    const uint8_t *sent;
-    int rc = transmitted_words(code, seed, first_frame + done, m, random_codewords, w.sent, w.msg, nullptr, stream, &sent);
-    if (rc != CC_OK) return rc;
     BurstIO io;
     DiscreteIO list;
     io.frame_major = true;
@@ -1436,16 +1427,11 @@ int run_burst(cc_code *code, const cc_burst_channel &ch, const DetectorThreshold
         list = workspace_list(w, m, n);
       }
     }
-    rc = launch_burst(code, ch, seed, first_frame + done, m, sent, io, reinterpret_cast<unsigned long long *>(d_counters),
-                      stream, det);
-    if (rc != CC_OK) return rc;
-    if (list.er) {
-      rc = launch_flag_list(code, io.flag_fm, m, list, stream);
-      if (rc != CC_OK) return rc;
-    }
-    rc = launch_decoder(code, w, list.er, list.off, m, stream);
-    if (rc != CC_OK) return rc;
-    return launch_count(code, w, sent, m, d_counters, stream);
+    return mc_route(code, w, seed, first_frame + done, m, random_codewords, d_counters, stream, [&](const uint8_t *sent) {
+      const int rc = launch_burst(code, ch, seed, first_frame + done, m, sent, io,
+                                  reinterpret_cast<unsigned long long *>(d_counters), stream, det);
+      return rc != CC_OK || !list.er ? rc : launch_flag_list(code, io.flag_fm, m, list, stream);
+    }, [&] { return launch_decoder(code, w, list.er, list.off, m, stream); });
   });
 }
 

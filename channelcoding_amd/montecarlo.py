@@ -130,6 +130,8 @@ def shard_blocks(total, rank, world, interleave):
 class DeviceBackend:
     """Counts one shard of one Eb/N0 point on this rank's GPU through cc_mc_run_dev."""
 
+    symbol, leading = "cc_mc_run_dev", ()  # the entry point and the arguments between the handle and Eb/N0
+
     def __init__(self, code, random_codewords=False):
         import torch
         self.torch = torch
@@ -141,9 +143,9 @@ class DeviceBackend:
         torch = self.torch
         counters = torch.zeros(capi.MC_NCOUNTERS, dtype=torch.int64, device=self.device)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = capi.lib().cc_mc_run_dev(self.code._h, float(ebno_db), int(seed), int(first_frame), int(frames),
-                                      int(self.random_codewords), C.c_void_p(counters.data_ptr()), stream)
-        capi.check(rc, "cc_mc_run_dev")
+        rc = getattr(capi.lib(), self.symbol)(self.code._h, *self.leading, float(ebno_db), int(seed), int(first_frame),
+                                              int(frames), int(self.random_codewords), C.c_void_p(counters.data_ptr()), stream)
+        capi.check(rc, self.symbol)
         return counters  # stays on the device: reduced with RCCL
 
 
@@ -151,40 +153,26 @@ class ChaseBackend(DeviceBackend):
     """The same shard through cc_mc_run_chase_dev: Chase-II over the p least reliable positions of every frame
     (binary BCH with a hard tag, q <= 8, 2t <= 32)."""
 
+    symbol = "cc_mc_run_chase_dev"
+
     def __init__(self, code, p, random_codewords=False):
         super().__init__(code, random_codewords)
         self.p = int(p)
         if not 0 <= self.p <= capi.CHASE_MAX_P:
             raise ValueError("chase= takes p in 0 .. %d" % capi.CHASE_MAX_P)
-
-    def run(self, ebno_db, seed, first_frame, frames):
-        torch = self.torch
-        counters = torch.zeros(capi.MC_NCOUNTERS, dtype=torch.int64, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = capi.lib().cc_mc_run_chase_dev(self.code._h, self.p, float(ebno_db), int(seed), int(first_frame), int(frames),
-                                            int(self.random_codewords), C.c_void_p(counters.data_ptr()), stream)
-        capi.check(rc, "cc_mc_run_chase_dev")
-        return counters
+        self.leading = (self.p,)
 
 
 class GmdBackend(DeviceBackend):
     """The same shard through cc_mc_run_gmd_dev: BPSK/AWGN per symbol bit, then GMD with m trials on every frame (RS with
     a hard tag, q <= 8, 2t <= 32, step = 1; m = True: all t + 1)."""
 
+    symbol = "cc_mc_run_gmd_dev"
+
     def __init__(self, code, m, random_codewords=False):
         super().__init__(code, random_codewords)
-        if m is not True and (isinstance(m, bool) or int(m) < 1):
-            raise ValueError("gmd= takes True (all trials) or m >= 1")
-        self.m = capi.GMD_ALL if m is True else int(m)
-
-    def run(self, ebno_db, seed, first_frame, frames):
-        torch = self.torch
-        counters = torch.zeros(capi.MC_NCOUNTERS, dtype=torch.int64, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = capi.lib().cc_mc_run_gmd_dev(self.code._h, self.m, float(ebno_db), int(seed), int(first_frame), int(frames),
-                                          int(self.random_codewords), C.c_void_p(counters.data_ptr()), stream)
-        capi.check(rc, "cc_mc_run_gmd_dev")
-        return counters
+        self.m = capi.gmd_trials(m)
+        self.leading = (self.m,)
 
 
 class _ShardedSimulation:

@@ -10,11 +10,12 @@ p = 6, so `candidates` decodes all 64 once and `pick` answers every p from them.
 """
 import numpy as np
 
+import soft_model
 from checkers import BCH, BM, Oracle
 from shortened_model import Shortened
+from soft_model import FRAME_LOCATOR, FRAME_OK, metric  # noqa: F401 (the tests read them from here)
 
 MAX_P = 6
-FRAME_OK, FRAME_LOCATOR = 0, 2
 
 
 def decoder(q, t, N=None):
@@ -28,17 +29,7 @@ def hard(y):
 
 def least_reliable(y, count=MAX_P):
     """(B, min(count, n)) positions in the order of the contract"""
-    keys = np.ascontiguousarray(y, np.float32).view(np.uint32) & np.uint32(0x7FFFFFFF)
-    return np.argsort(keys, axis=1, kind="stable")[:, : min(count, keys.shape[1])]
-
-
-def metric(y, z, c):
-    """float32 sum of |y_i| over c_i != z_i, from +0.0 in ascending i; rows of 2-d inputs"""
-    terms = np.where(np.asarray(c) != np.asarray(z), np.abs(np.asarray(y, np.float32)), np.float32(0.0)).astype(np.float32)
-    acc = np.zeros(terms.shape[:-1], np.float32)
-    for i in range(terms.shape[-1]):  # one float32 add per position (adding +0.0 changes nothing)
-        acc = (acc + terms[..., i]).astype(np.float32)
-    return acc
+    return soft_model.least_reliable(y, count)
 
 
 def candidates(dec, y, max_p=MAX_P):
@@ -68,19 +59,7 @@ def pick(cand, p):
     J = 1 << p
     if J > cand["ok"].shape[1]:
         raise ValueError("p = %d asks for %d test patterns, %d were decoded" % (p, J, cand["ok"].shape[1]))
-    ok, M, z = cand["ok"][:, :J], cand["M"][:, :J], cand["z"]
-    B = z.shape[0]
-    out, nerr = z.copy(), np.full(B, -1, np.int32)
-    status, met = np.full(B, FRAME_LOCATOR, np.int32), np.zeros(B, np.float32)
-    winner = np.full(B, -1, np.int64)
-    for f in range(B):
-        js = np.flatnonzero(ok[f])
-        if js.size == 0:
-            continue
-        j = js[np.argmin(M[f, js])]  # argmin returns the first minimum: equal M goes to the smallest j
-        winner[f], out[f], met[f], status[f] = j, cand["words"][f, j], M[f, j], FRAME_OK
-        nerr[f] = int((out[f] != z[f]).sum())
-    return dict(out=out, nerr=nerr, status=status, metric=met, winner=winner)
+    return soft_model.pick(cand, J, "z")
 
 
 def chase(dec, y, p):

@@ -14,10 +14,10 @@ virtual-position rule of the shortened code is then applied to the padded word b
 import numpy as np
 
 import rs_roots_model as R
+import soft_model
 from checkers import BM, RS, Oracle
 from shortened_model import Shortened
-
-FRAME_OK, FRAME_LOCATOR = 0, 2
+from soft_model import FRAME_LOCATOR, FRAME_OK, least_reliable, metric  # noqa: F401 (the tests read them from here)
 
 
 class Decoder:
@@ -63,22 +63,6 @@ class Decoder:
         return self._Tinv(out)[0], True
 
 
-def least_reliable(r, count):
-    """(B, count) positions in the order of the contract"""
-    keys = np.ascontiguousarray(r, np.float32).view(np.uint32) & np.uint32(0x7FFFFFFF)
-    return np.argsort(keys, axis=1, kind="stable")[:, :count]
-
-
-def metric(r, w, c):
-    """float32 sum of |r_i| over c_i != w_i, from +0.0 in ascending i; rows of 2-d inputs"""
-    terms = np.where(np.asarray(c) != np.asarray(w), np.abs(np.asarray(r, np.float32)), np.float32(0.0)).astype(np.float32)
-    acc = np.zeros(terms.shape[:-1], np.float32)
-    with np.errstate(over="ignore"):
-        for i in range(terms.shape[-1]):  # one float32 add per position (adding +0.0 changes nothing)
-            acc = (acc + terms[..., i]).astype(np.float32)
-    return acc
-
-
 def candidates(dec, w, r, trials=None):
     """words (B, m, n) u8, ok (B, m) bool, M (B, m) f32 of the first m = trials (None: t + 1) trials"""
     w = np.ascontiguousarray(w, np.uint8).reshape(-1, dec.n)
@@ -105,19 +89,7 @@ def pick(cand, m):
     """the contract's outputs for m trials: out (B, n) u8, nerr, status (B,) i32, metric (B,) f32, winner (B,) (-1: none)"""
     if not 1 <= m <= cand["ok"].shape[1]:
         raise ValueError("m = %d trials asked for, %d were decoded" % (m, cand["ok"].shape[1]))
-    ok, M, w = cand["ok"][:, :m], cand["M"][:, :m], cand["w"]
-    B = w.shape[0]
-    out, nerr = w.copy(), np.full(B, -1, np.int32)
-    status, met = np.full(B, FRAME_LOCATOR, np.int32), np.zeros(B, np.float32)
-    winner = np.full(B, -1, np.int64)
-    for f in range(B):
-        ts = np.flatnonzero(ok[f])
-        if ts.size == 0:
-            continue
-        tau = ts[np.argmin(M[f, ts])]  # argmin returns the first minimum: equal M goes to the smallest tau
-        winner[f], out[f], met[f], status[f] = tau, cand["words"][f, tau], M[f, tau], FRAME_OK
-        nerr[f] = int((out[f] != w[f]).sum())
-    return dict(out=out, nerr=nerr, status=status, metric=met, winner=winner)
+    return soft_model.pick(cand, m, "w")
 
 
 def gmd(dec, w, r, m=None):
@@ -126,8 +98,8 @@ def gmd(dec, w, r, m=None):
 
 
 def frames_per_wave(t2, n, m):
-    """F of the kernel's mapping (gmd.hip: gmd_layout / gmd_frames_per_wave): the tests place batch sizes
-    around it"""
+    """F of the kernel's mapping (gmd.hip: gmd_layout, soft_lanes.hpp: frames_per_wave): the tests place batch
+    sizes around it"""
     def lds(F):
         return (128 * t2 + 2 * 128 * (t2 + 1) + 4 * F * n + 2 * F * t2 + F * n + 15) & ~15
     F = 64 // m
