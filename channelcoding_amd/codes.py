@@ -182,6 +182,53 @@ def symbol_reliability(y, q):
     return w, np.ascontiguousarray(keys.min(axis=2)).view(np.float32)
 
 
+def product_decode(rows, cols, y, p, alpha, beta):
+    """Iterative (turbo) decoding of a product code with the Chase-Pyndiah component decoder,
+    correct_batch(chase=p, soft=beta).  y: (B, n2, n1) float32 channel values, numpy array or device tensor, positive
+    meaning bit 0; every row y[b, i, :] is a received word of `rows` (n1 = rows.n), every column y[b, :, k] one of `cols`
+    (n2 = cols.n).  alpha and beta are sequences of equal length with one entry per half-iteration.  W starts at zero;
+    half-iteration h forms X = y + (alpha[h] * W), a float32 product and a float32 sum, decodes the rows of X (h even)
+    or its columns (h odd), and W becomes the ext of that pass.  Returns dict(out=, ext=, status=) of the last
+    half-iteration: out (B, n2, n1) u8 and ext (B, n2, n1) f32 in the orientation of y, status (B, n2) after a row pass
+    and (B, n1) after a column pass, one entry per component word.
+    W is not normalised and there is no default schedule: good values depend on the scaling of y.  For y = +-1 + noise
+    R. Pyndiah (IEEE Trans. Commun. 46 (8), 1998) gives for eight half-iterations alpha = 0, 0.2, 0.3, 0.5, 0.7, 0.9, 1,
+    1 and beta = 0.2, 0.4, 0.6, 0.8, 1, 1, 1, 1 -- with W normalised to mean magnitude one, so a starting point only."""
+    alpha, beta = [float(np.float32(a)) for a in alpha], [float(np.float32(b)) for b in beta]
+    if len(alpha) != len(beta) or not alpha:
+        raise ValueError("product_decode takes one alpha and one beta per half-iteration, at least one")
+    if len(y.shape) != 3 or y.shape[1] != cols.n or y.shape[2] != rows.n:
+        raise CcError(capi.ERR_LENGTH, "product_decode")
+    torch_in = _is_torch(y)
+    if torch_in:
+        import torch
+        if y.dtype != torch.float32:
+            raise TypeError("product_decode takes float32 channel values")
+        y = y.contiguous()
+        W = torch.zeros_like(y)
+        turn = lambda a: a.transpose(1, 2).contiguous()
+    else:
+        y = np.asarray(y)
+        if y.dtype.kind != "f":
+            raise TypeError("product_decode takes float32 channel values")
+        y = np.ascontiguousarray(y, np.float32)
+        W = np.zeros_like(y)
+        turn = lambda a: np.ascontiguousarray(a.transpose(0, 2, 1))
+    B, n2, n1 = y.shape
+    for h, (a, b) in enumerate(zip(alpha, beta)):
+        scaled = W * a if torch_in else W * np.float32(a)
+        X = y + scaled
+        if h % 2 == 0:
+            res = rows.correct_batch(X.reshape(B * n2, n1), chase=p, soft=b)
+            out, W = res["out"].reshape(B, n2, n1), res["ext"].reshape(B, n2, n1)
+            status = res["status"].reshape(B, n2)
+        else:
+            res = cols.correct_batch(turn(X).reshape(B * n1, n2), chase=p, soft=b)
+            out, W = turn(res["out"].reshape(B, n1, n2)), turn(res["ext"].reshape(B, n1, n2))
+            status = res["status"].reshape(B, n1)
+    return dict(out=out, ext=W, status=status)
+
+
 def pack_bits(a):
     """One symbol per bit, shape (..., n) -> packed uint8, shape (..., ceil(n / 8)): the coefficient of x^p in bit p & 7
     of byte p >> 3 (numpy.packbits(bitorder="little")); bit 0 of each symbol counts, pad bits are 0.  numpy arrays on the
@@ -783,7 +830,7 @@ class cyclic:
         return msg
 
     def correct_batch(self, b, erasures=None, want_L=False, packed=False, out=None, interleave=None, chase=None, gmd=None,
-                      reliability=None):
+                      reliability=None, soft=None):
         """Returns a dict: out (B,n) u8, status (B,) i32, and nerr (hard) or iters [+ L] (soft).
         gmd=m, reliability=r (RS, hard algorithms, q <= 8, 2t <= 32, step = 1): b holds the received symbols, r float32
         reliabilities of the same shape, and the frames are decoded by GMD with m trials (cc_correct_gmd_batch; gmd=True:
@@ -792,6 +839,9 @@ class cyclic:
         chase=p (binary BCH, hard algorithms, q <= 8, 2t <= 32): b holds float32 channel values and is decoded by
         Chase's algorithm 2 over the p least reliable positions (cc_correct_chase_batch); the dict also carries
         metric (B,) f32.  It does not combine with erasures, packed, interleave or want_L.
+        chase=p, soft=beta (beta a finite float >= 0): the same with the Chase-Pyndiah soft output
+        (cc_correct_chase_soft_batch); the dict also carries ext (B,n) f32, the extrinsic value of every bit, beta in
+        magnitude where no candidate disagrees with the decision.  soft= needs chase= and combines with nothing else.
         packed=True (binary BCH codes, hard algorithms): b and out are uint8 (B, packed_bytes), see pack_bits; out= names
         the buffer the corrected packed words go to (b itself decodes in place).  The long codes (q = 9 .. 15, BM / PGZ,
         t <= 31, no erasures) are decoded from the packed words themselves in calls of device tensors of at least
@@ -799,6 +849,8 @@ class cyclic:
         interleave=I (hard algorithms): b and out are symbol-interleaved blocks of shape (B / I, n, I), see interleave();
         status, nerr and the erasure lists are per frame f = b I + j, as without it; out= as with packed=True."""
         lib = capi.lib()
+        if soft is not None and (chase is None or gmd is not None or reliability is not None):
+            raise TypeError("soft= goes with chase= and with nothing else")
         if gmd is not None or reliability is not None:
             if (erasures is not None or want_L or packed or out is not None or interleave is not None
                     or chase is not None):
@@ -809,7 +861,7 @@ class cyclic:
         if chase is not None:
             if erasures is not None or want_L or packed or out is not None or interleave is not None:
                 raise TypeError("chase= does not combine with erasures, want_L, packed=True, out= or interleave=")
-            return self._chase(b, chase)
+            return self._chase(b, chase, soft)
         if interleave is not None:
             if packed:
                 raise TypeError("interleave= does not combine with packed=True")
@@ -854,40 +906,53 @@ class cyclic:
                                                  _ptr(status), B), "cc_correct_hard_batch")
         return dict(out=out, status=status, nerr=nerr)
 
-    def _soft_call(self, name, ins, arg):
+    def _soft_call(self, name, ins, arg, beta=None):
         """`name`(_dev for device tensors) over the contiguous inputs `ins`, B frames of n values each, with the decoder's
-        argument `arg`: allocates what the reliability-based decoders return, makes the call and returns the dict."""
+        argument `arg`: allocates what the reliability-based decoders return, makes the call and returns the dict.
+        beta: the call also takes beta after `arg` and ext (B, n) f32 after out, and the dict carries ext."""
         if _is_torch(ins[0]):
             import torch
             B, dev = ins[0].numel() // self.n, ins[0].device
             out = torch.empty((B, self.n), dtype=torch.uint8, device=dev)
             nerr, status = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
             metric = torch.empty(B, dtype=torch.float32, device=dev)
+            ext = torch.empty((B, self.n), dtype=torch.float32, device=dev) if beta is not None else None
             name, tail = name + "_dev", (_stream_handle(ins[0]),)
         else:
             B, tail = ins[0].size // self.n, ()
             out = np.zeros((B, self.n), np.uint8)
             nerr, status, metric = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.float32)
-        capi.check(getattr(capi.lib(), name)(self._h, *map(_ptr, ins), arg, _ptr(out), _ptr(nerr), _ptr(metric),
+            ext = np.zeros((B, self.n), np.float32) if beta is not None else None
+        args, outs = (arg,) if beta is None else (arg, beta), (_ptr(out),) if beta is None else (_ptr(out), _ptr(ext))
+        capi.check(getattr(capi.lib(), name)(self._h, *map(_ptr, ins), *args, *outs, _ptr(nerr), _ptr(metric),
                                              _ptr(status), B, *tail), name)
-        return dict(out=out, status=status, nerr=nerr, metric=metric)
+        res = dict(out=out, status=status, nerr=nerr, metric=metric)
+        if beta is not None:
+            res["ext"] = ext
+        return res
 
-    def _chase(self, b, p):
-        """correct_batch(chase=p): float32 channel values, host array or device tensor."""
+    def _chase(self, b, p, beta=None):
+        """correct_batch(chase=p[, soft=beta]): float32 channel values, host array or device tensor."""
         p = int(p)
         if p < 0:
             raise ValueError("chase= takes p >= 0")
+        name = "cc_correct_chase_batch"
+        if beta is not None:
+            if isinstance(beta, bool) or not isinstance(beta, (int, float, np.integer, np.floating)):
+                raise TypeError("soft= takes beta, a float")
+            with np.errstate(over="ignore"):  # (beyond float32: +inf, which the call refuses)
+                beta, name = float(np.float32(beta)), "cc_correct_chase_soft_batch"
         if b.shape[-1] != self.n:
             raise CcError(capi.ERR_LENGTH, "correct_batch")
         if _is_torch(b):
             import torch
             if b.dtype != torch.float32:
                 raise TypeError("chase= takes float32 channel values")
-            return self._soft_call("cc_correct_chase_batch", [b.contiguous()], p)
+            return self._soft_call(name, [b.contiguous()], p, beta)
         b = np.asarray(b)
         if b.dtype.kind != "f":
             raise TypeError("chase= takes float32 channel values")
-        return self._soft_call("cc_correct_chase_batch", [np.ascontiguousarray(b, np.float32)], p)
+        return self._soft_call(name, [np.ascontiguousarray(b, np.float32)], p, beta)
 
     def _gmd(self, b, rel, m):
         """correct_batch(gmd=m, reliability=rel): uint8 symbols and float32 reliabilities, host arrays or device tensors."""
@@ -948,15 +1013,16 @@ class cyclic:
             raise TypeError("hard decoding takes uint8 symbols or float32 soft values")
         return dict(out=out, status=status, nerr=nerr)
 
-    def decode_batch(self, b, erasures=None, packed=False, interleave=None, chase=None, gmd=None, reliability=None):
+    def decode_batch(self, b, erasures=None, packed=False, interleave=None, chase=None, gmd=None, reliability=None,
+                     soft=None):
         """decode = correct + message extraction (cyclic.h:313-327); host arrays go through cc_decode_*_batch.
-        chase=p: correct_batch(b, chase=p), then the messages of its words.
+        chase=p[, soft=beta]: correct_batch(b, chase=p[, soft=beta]), then the messages of its words.
         gmd=m, reliability=r: correct_batch(b, gmd=m, reliability=r), then the messages of its words.
         packed=True: b, out and msg are packed uint8 words, see pack_bits.
         interleave=I: b and out are blocks of shape (B / I, n, I), msg (B / I, l, I), see interleave()."""
-        if chase is not None or gmd is not None or reliability is not None:
+        if chase is not None or gmd is not None or reliability is not None or soft is not None:
             res = self.correct_batch(b, erasures, packed=packed, interleave=interleave, chase=chase, gmd=gmd,
-                                     reliability=reliability)
+                                     reliability=reliability, soft=soft)
             res["msg"] = self.extract_batch(res["out"])
             return res
         if interleave is not None:

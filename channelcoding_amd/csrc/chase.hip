@@ -14,6 +14,11 @@
 //   C  per frame: minimum of the metric bits over the frame's 2^p lanes (DPP inside a row of 16 lanes, a lane
 //      permute for the two steps across rows), the lowest lane among its holders wins (a ballot), its flip mask goes
 //      through LDS and all 64 lanes store out = z ^ mask
+//   D  soft output only (cc_correct_chase_soft_batch): the winner leaves the bits of M_D next to its mask,
+//      every lane with a candidate takes fm ^ mask -- where its candidate differs from the winner -- and lowers K[pos]
+//      to its metric bits at each of those positions with an LDS unsigned-minimum atomic (K is preset to all ones in
+//      stage A; the candidates of a frame that equal the winner have an empty difference), and a second store loop
+//      writes ext as stage C writes out
 //
 // A candidate exists iff the LFSR length equals deg lambda <= t and lambda has deg roots below n (for L = deg the
 // re-check of cyclic.h:243-248 cannot fail -- proof in algebraic.hip; conversely a codeword within t of the pattern
@@ -35,6 +40,24 @@ __host__ __device__ constexpr ChaseLayout chase_layout(int t2, int n, int F) {
   return ChaseLayout{bm, Y, SZ, LP, WM, (LP + 8 * F + 15) & ~15};
 }
 
+// the soft-output layout: the same arrays at the same offsets, and behind them
+struct ChaseSoftLayout : ChaseLayout {
+  int K, MD;
+};
+__host__ __device__ constexpr ChaseSoftLayout chase_soft_layout(int t2, int n, int F) {
+  const ChaseLayout h = chase_layout(t2, n, F);
+  const int K = (h.LP + 8 * F + 3) & ~3;  // u32 [F][n]   bits of the competitor metric K_i (all ones: none)
+  const int MD = K + 4 * F * n;           // u32 [F]      bits of the winner's metric M_D (all ones: no candidate)
+  return ChaseSoftLayout{{h, h.Y, h.SZ, h.LP, h.WM, (MD + 4 * F + 15) & ~15}, K, MD};
+}
+constexpr uint32_t kNoMetric = 0xFFFFFFFFu;  // above the bits of every metric, +inf included
+
+// the first argument of a parameter pack
+template <class A, class... Rest>
+__device__ __forceinline__ A first_of(A a, Rest...) {
+  return a;
+}
+
 // minimum over the 2^p lanes of a frame (aligned groups), valid in every lane of the group
 __device__ __forceinline__ uint32_t group_umin(uint32_t v, int p) {
   if (p >= 1) v = dpp_umin<0xB1, 0xF>(v);   // quad_perm [1,0,3,2]
@@ -46,12 +69,20 @@ __device__ __forceinline__ uint32_t group_umin(uint32_t v, int p) {
   return v;
 }
 
-// TR > 0: t <= TR, lambda_0 .. lambda_TR live in registers during the root search; TR = 0: read from the LDS column
-template <int TR>
+// what the soft-output instantiation takes on top: the value of a position without a competitor, and the output
+struct SoftOut {
+  float beta;
+  float *__restrict__ ext;
+};
+
+// TR > 0: t <= TR, lambda_0 .. lambda_TR live in registers during the root search; TR = 0: read from the LDS column.
+// Soft = {} is the hard-output kernel; Soft = {SoftOut} adds stage D and the output ext, with the soft layout.
+template <int TR, class... Soft>
 __global__ void __launch_bounds__(256)
 chase_kernel(const AlgebraicTables *__restrict__ T, const float *__restrict__ llr, int p, int F, uint8_t *__restrict__ out,
              int32_t *__restrict__ nerr_out, float *__restrict__ metric_out, int32_t *__restrict__ status_out,
-             unsigned long long B) {
+             unsigned long long B, Soft... soft_out) {
+  constexpr bool SOFT = sizeof...(Soft) > 0;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const uint8_t *ex = smem;
   const uint16_t *lg2 = stage_tables(T, smem);
@@ -59,13 +90,16 @@ chase_kernel(const AlgebraicTables *__restrict__ T, const float *__restrict__ ll
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int n = T->n, nn = T->nf, t2 = T->nroots, t = t2 / 2, nc = t2 + 1;
   const ChaseLayout lay = chase_layout(t2, n, F);
-  uint8_t *base = smem + kSoftTables + wid * lay.bytes;
+  const ChaseSoftLayout soft = SOFT ? chase_soft_layout(t2, n, F) : ChaseSoftLayout{};  // the same offsets, K and MD behind
+  uint8_t *base = smem + kSoftTables + wid * (SOFT ? soft.bytes : lay.bytes);
   uint16_t *SL = reinterpret_cast<uint16_t *>(base + lay.SL);
   uint16_t *LL = reinterpret_cast<uint16_t *>(base + lay.LL);
   uint16_t *BL = reinterpret_cast<uint16_t *>(base + lay.BL);
   float *Y = reinterpret_cast<float *>(base + lay.Y);
   unsigned long long *WM = reinterpret_cast<unsigned long long *>(base + lay.WM);
   uint8_t *SZ = base + lay.SZ, *LP = base + lay.LP;
+  uint32_t *K = SOFT ? reinterpret_cast<uint32_t *>(base + soft.K) : nullptr;  // the hard-output kernel has neither
+  uint32_t *MD = SOFT ? reinterpret_cast<uint32_t *>(base + soft.MD) : nullptr;
 
   const int slot = lane >> p, j = lane & ((1 << p) - 1);
   // positions lane + 64 c: alpha^pos and the step alpha^(2 pos) between consecutive odd syndromes
@@ -86,6 +120,8 @@ chase_kernel(const AlgebraicTables *__restrict__ T, const float *__restrict__ ll
       for (int c = 0; c < 4; ++c) {
         const float v = valid[c] ? src[lane + 64 * c] : 0.0f;
         if (valid[c]) Y[s * n + lane + 64 * c] = v;
+        if constexpr (SOFT)
+          if (valid[c]) K[s * n + lane + 64 * c] = kNoMetric;
         zb[c] = (valid[c] && v < 0.0f) ? 1u : 0u;                // cyclic.h:163-173
         key[c] = reliability_key(valid[c], v);
         ev[c] = e1[c];
@@ -180,9 +216,22 @@ chase_kernel(const AlgebraicTables *__restrict__ T, const float *__restrict__ ll
         WM[sl * 4 + c] = ok ? fm[c] : 0ull;
         cnt += __builtin_popcountll(fm[c]);
       }
+      if constexpr (SOFT) MD[sl] = ok ? f2u(M) : kNoMetric;
       store_verdict(nerr_out, metric_out, status_out, first + slot, ok, cnt, M);
     }
     wave_sync();
+    if constexpr (SOFT) {
+      // ---------------- D: K_i = the smallest metric among the candidates that differ from the winner at i ----------------
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        unsigned long long d = have ? fm[c] ^ WM[sl * 4 + c] : 0ull;  // set bits lie below n: fm and WM stop there
+        while (d) {
+          atomicMin(&K[sl * n + 64 * c + __builtin_ctzll(d)], mkey);
+          d &= d - 1ull;
+        }
+      }
+      wave_sync();
+    }
     for (int s = 0; s < frames; ++s) {
       uint8_t *dst = out + (first + s) * n;
 #pragma unroll
@@ -192,7 +241,26 @@ chase_kernel(const AlgebraicTables *__restrict__ T, const float *__restrict__ ll
           dst[lane + 64 * c] = static_cast<uint8_t>(z ^ static_cast<uint32_t>((WM[s * 4 + c] >> lane) & 1ull));
         }
     }
-    wave_sync();  // the next group overwrites Y, SZ, LP and WM
+    if constexpr (SOFT) {
+      const SoftOut so = first_of(soft_out...);
+      const float beta = so.beta;
+      for (int s = 0; s < frames; ++s) {
+        float *dst = so.ext + (first + s) * n;
+        const uint32_t md = MD[s];
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (valid[c]) {
+            const float y = Y[s * n + lane + 64 * c];
+            const bool one = (y < 0.0f) != (((WM[s * 4 + c] >> lane) & 1ull) != 0);  // the winner's bit
+            const uint32_t k = K[s * n + lane + 64 * c];
+            const float sgn = one ? -1.0f : 1.0f;
+            // two float32 subtractions, the products by +-1 are exact (the unit is built without contraction)
+            const float e = k == kNoMetric ? sgn * beta : sgn * (u2f(k) - u2f(md)) - y;
+            dst[lane + 64 * c] = md == kNoMetric ? 0.0f : e;
+          }
+      }
+    }
+    wave_sync();  // the next group overwrites Y, SZ, LP and WM (K and MD)
   }
 }
 
@@ -203,11 +271,32 @@ int launch_chase(const cc_code *code, const float *d_llr, unsigned p, uint8_t *d
   if (B == 0) return CC_OK;
   const int n = static_cast<int>(code->tab.n), t2 = code->h_alg.nroots;
   // 64 >> p frames per wavefront, fewer where the received values of that many frames do not fit
-  const int F = frames_per_wave(64 >> p, [&](int f) { return chase_layout(t2, n, f); });
+  const int F = chase_frames_per_wave(code, p, false);
   const size_t lds = kSoftTables + 4 * static_cast<size_t>(chase_layout(t2, n, F).bytes);
   return launch_groups(code, B, F, "chase kernel launch", [&](dim3 grid) {
     hipLaunchKernelGGL(t2 <= 6 ? chase_kernel<3> : chase_kernel<0>, grid, dim3(256), lds, stream, code->d_alg, d_llr,
                        static_cast<int>(p), F, d_out, d_nerr, d_metric, d_status, static_cast<unsigned long long>(B));
+  });
+}
+
+int chase_frames_per_wave(const cc_code *code, unsigned p, bool soft) {
+  // (2t = h_alg.nroots, which a handle without a device does not fill in)
+  const int n = static_cast<int>(code->tab.n), t2 = 2 * static_cast<int>(code->tab.t);
+  return soft ? frames_per_wave(64 >> p, [&](int f) { return chase_soft_layout(t2, n, f); })
+              : frames_per_wave(64 >> p, [&](int f) { return chase_layout(t2, n, f); });
+}
+
+int launch_chase_soft(const cc_code *code, const float *d_llr, unsigned p, float beta, uint8_t *d_out, float *d_ext,
+                      int32_t *d_nerr, float *d_metric, int32_t *d_status, size_t B, hipStream_t stream) {
+  if (B == 0) return CC_OK;
+  const int n = static_cast<int>(code->tab.n), t2 = code->h_alg.nroots;
+  // K doubles what a frame holds: about half the frames of launch_chase where its count was bounded by LDS
+  const int F = chase_frames_per_wave(code, p, true);
+  const size_t lds = kSoftTables + 4 * static_cast<size_t>(chase_soft_layout(t2, n, F).bytes);
+  return launch_groups(code, B, F, "chase soft-output kernel launch", [&](dim3 grid) {
+    hipLaunchKernelGGL((t2 <= 6 ? chase_kernel<3, SoftOut> : chase_kernel<0, SoftOut>), grid, dim3(256), lds, stream,
+                       code->d_alg, d_llr, static_cast<int>(p), F, d_out, d_nerr, d_metric, d_status,
+                       static_cast<unsigned long long>(B), SoftOut{beta, d_ext});
   });
 }
 

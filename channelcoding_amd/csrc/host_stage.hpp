@@ -269,7 +269,8 @@ inline int upload_erasures(HostStage &st, int slot, int idx, const uint16_t *era
 }
 
 // One per-frame array of a staged call.  Buffer indices (HostStage::buf[slot][idx]): 0 in, 1 out, 2 iters / nerr,
-// 3 status, 4 L / metric; 5 and 6 hold a chunk's erasure positions and offsets; 7 a second input (the reliabilities of GMD).
+// 3 status, 4 L / metric; 5 and 6 hold a chunk's erasure positions and offsets; 7 a second input (the reliabilities of GMD)
+// or a second per-symbol output (ext of the Chase soft output).
 struct StagedStream {
   int idx;
   size_t bytes;  // per frame

@@ -248,6 +248,41 @@ int cc_correct_chase_batch(const cc_code *code, const float *llr /* B*n */, uint
 int cc_correct_chase_batch_dev(const cc_code *code, const float *d_llr, uint32_t p, uint8_t *d_out, int32_t *d_nerr,
                                float *d_metric, int32_t *d_status, size_t B, void *stream);
 
+/* ---- Chase-Pyndiah soft output for binary BCH codes: cc_correct_chase_batch with a reliability per bit, the soft-in,
+ *      soft-out component decoder of a product code (R. Pyndiah, "Near-optimum decoding of product codes: block turbo
+ *      codes", IEEE Trans. Commun. 46 (8), 1998).  The reference has no such decoder.
+ *      Handles, frames and p are those of cc_correct_chase_batch, and out, nerr, metric and status are bit for bit what
+ *      cc_correct_chase_batch writes for the same input.  One output is added: ext, B*n float32.  For a frame, with the
+ *      test patterns, candidates and metrics M(c) of the Chase contract above:
+ *        D, M_D         the winner and its metric
+ *        s_i            +1.0f if D_i = 0, else -1.0f (a positive channel value means bit 0, as z_i = (y_i < 0) fixes)
+ *        competitor     K_i = min { M(c_j) : pattern j has a candidate c_j and (c_j)_i != D_i }, a minimum of float32
+ *                       values (several patterns with the same candidate change nothing)
+ *        ext_i          position i has a competitor:  s_i * (K_i - M_D) - y_i, two float32 subtractions and a sign, no
+ *                       fused operation.  This is Pyndiah's r'_i - r_i with r'_i = s_i (|R - C|^2 - |R - D|^2) / 4,
+ *                       because |R - c|^2 = |R - z|^2 + 4 M(c) for +-1 signalling
+ *                       position i has none:          s_i * beta
+ *                       no pattern has a candidate (CC_FRAME_LOCATOR):  +0.0f at every i
+ *      beta is a float32, finite and >= 0.  ext is unspecified for a frame whose winning metric is not finite; its other
+ *      four outputs stay specified.  NaN input is unspecified as before.  nerr, metric and status may be NULL; out and
+ *      ext may not.
+ *      Refused before a device is asked for, in this order: what cc_correct_chase_batch refuses short of the device, in
+ *      its order, with ext joining the NULL check; beta negative, infinite or NaN -> CC_ERR_INVALID_ARGUMENT; ext
+ *      overlapping llr (any byte of the B*n floats) -> CC_ERR_INVALID_ARGUMENT; then a CC_DEVICE_NONE handle answers
+ *      CC_ERR_NO_DEVICE.  B = 0 answers CC_OK.  No RS or GMD soft output, no extended (parity-augmented) codes, p and q
+ *      as above. ---- */
+int cc_correct_chase_soft_batch(const cc_code *code, const float *llr /* B*n */, uint32_t p, float beta,
+                                uint8_t *out /* B*n */, float *ext /* B*n */, int32_t *nerr, float *metric, int32_t *status,
+                                size_t B);
+int cc_correct_chase_soft_batch_dev(const cc_code *code, const float *d_llr, uint32_t p, float beta, uint8_t *d_out,
+                                    float *d_ext, int32_t *d_nerr, float *d_metric, int32_t *d_status, size_t B,
+                                    void *stream);
+
+/* How many frames one wavefront of cc_correct_chase_batch (soft = 0) or cc_correct_chase_soft_batch (soft != 0) decodes
+ * side by side at p: 64 >> p, fewer where the frames' values do not fit its share of LDS.  For tests and measurements
+ * that place batch sizes next to it; 0 for a call the decoder refuses.  Needs no device. */
+int cc_chase_frames_per_wavefront(const cc_code *code, uint32_t p, int soft);
+
 /* ---- GMD soft-decision correct for Reed-Solomon codes (Forney's generalized-minimum-distance decoding): the 0, 2, 4, ..
  *      least reliable symbols are erased, every trial is decoded with errors and erasures, and the candidate nearest to
  *      what was received wins.  The reference has no such decoder; it runs the errors-and-erasures decoding of

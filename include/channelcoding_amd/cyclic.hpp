@@ -286,6 +286,7 @@ struct batch_result {
   std::vector<uint8_t> msg;     // decode_batch: B * l message symbols
   std::vector<float> metric;    // correct_chase_batch: sum of |y| over the positions the winner differs from sign(y) in;
                                 // correct_gmd_batch: sum of |rel| over the positions the winner differs from the input in
+  std::vector<float> ext;       // correct_chase_soft_batch: B * n extrinsic values (positive: bit 0)
 };
 
 template <int Family, unsigned q, typename Capability, typename Algorithm, unsigned N, typename Coding, unsigned mu,
@@ -547,6 +548,35 @@ public:
     detail::check(cc_correct_chase_batch(this->handle.get(), values, p, r.words.data(), r.nerr.data(), r.metric.data(),
                                          r.status.data(), B),
                   "cc_correct_chase_batch");
+    return r;
+  }
+
+  // ---- Chase-Pyndiah soft output (new; cc_correct_chase_soft_batch): correct_chase, and per bit the extrinsic value
+  // ext_i = s_i (K_i - M_D) - y_i against the nearest candidate that disagrees with the decision at i, s_i beta where
+  // there is none (s_i = +1 for bit 0); beta finite and >= 0.  Throws decoding_failure when no pattern has a candidate ----
+  std::vector<uint8_t> correct_chase_soft(const std::vector<float> &y, unsigned p, float beta, std::vector<float> &ext) const {
+    if (y.size() != N) throw std::runtime_error("Length of received sequence does not match code length");
+    std::vector<uint8_t> out(N);
+    ext.assign(N, 0.0f);
+    int32_t status = CC_FRAME_OK;
+    detail::check(cc_correct_chase_soft_batch(this->handle.get(), y.data(), p, beta, out.data(), ext.data(), nullptr, nullptr,
+                                              &status, 1),
+                  "cc_correct_chase_soft_batch");
+    if (status != CC_FRAME_OK) throw decoding_failure(detail::failure_text(status));
+    return out;
+  }
+  // B frames of n values, frame-contiguous: words, ext, nerr, status and metric of every frame (failed frames do not
+  // throw; their ext is +0)
+  batch_result correct_chase_soft_batch(const float *values, size_t B, unsigned p, float beta) const {
+    batch_result r;
+    r.words.resize(B * N);
+    r.ext.resize(B * N);
+    r.status.resize(B);
+    r.nerr.resize(B);
+    r.metric.resize(B);
+    detail::check(cc_correct_chase_soft_batch(this->handle.get(), values, p, beta, r.words.data(), r.ext.data(),
+                                              r.nerr.data(), r.metric.data(), r.status.data(), B),
+                  "cc_correct_chase_soft_batch");
     return r;
   }
 };

@@ -10,6 +10,17 @@ decoder and to min-sum on the same values, and word error rates next to min-sum.
     python profiles/tools/chase_bench.py wer        BCH(255,231), BCH(63,45) at 4, 5 and 6 dB, 2^22 frames per point,
                                                     random codewords, one seed: chase p = 0, 4, 6 against MS<20> and
                                                     NMS<20> (alpha = 8/10)
+    python profiles/tools/chase_bench.py soft       the soft output (cc_correct_chase_soft_batch_dev) on the
+                                                    codes, p values and noise points of `rates`: legs soft p, chase p of
+                                                    this build and, with --parent-lib, chase p of the parent commit's
+                                                    library loaded next to it; alternation and timing as in `rates`, the
+                                                    legs of a p taking turns at going first;
+                                                    then the soft leg's time as a ratio to the chase leg of the same p
+    python profiles/tools/chase_bench.py product    BCH(63,45) x BCH(63,45) at 3.0 dB, 2^12 blocks from numpy seed 1:
+                                                    block errors of cc.product_decode (p = 4, Pyndiah's alpha and beta
+                                                    of six half-iterations) after every half-iteration, against hard
+                                                    decoding of rows then columns
+    --parent-lib PATH                               soft: libchannelcoding_amd.so built from the parent commit
     --frames-log2 K                                 another number of frames per leg / point
     --only p6                                       rates: only the p = 6 leg of BCH(255,231) at 4 dB, five calls (for a
                                                     rocprofv3 run of its own)
@@ -105,6 +116,120 @@ def rates(frames, only):
             del legs, keep, llr
 
 
+def frames_per_wave(code, p, soft):
+    """F of launch_chase_soft (soft) or launch_chase at p, asked of the library"""
+    from channelcoding_amd import capi
+    return capi.lib().cc_chase_frames_per_wavefront(code._h, p, int(soft))
+
+
+def parent_chase(path, code):
+    """cc_correct_chase_batch_dev of the library at `path`, on a handle that library creates from the code's descriptor"""
+    lib = C.CDLL(path)
+    h = C.c_void_p()
+    lib.cc_code_create.restype = C.c_int
+    lib.cc_code_create.argtypes = [C.c_void_p, C.c_void_p]
+    assert lib.cc_code_create(C.byref(code._desc), C.byref(h)) == 0
+    fn = lib.cc_correct_chase_batch_dev
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]
+    return lib, h, fn
+
+
+def soft(frames, parent_lib):
+    import torch
+    import channelcoding_amd as cc
+    from channelcoding_amd import capi
+    lib = capi.lib()
+    ptr = lambda x: C.c_void_p(x.data_ptr())
+    for q, t in RATE_CODES:
+        for ebno in (4.0, 6.0):
+            code = cc.primitive_bch(q, cc.errors(t), cc.berlekamp_massey_tag())
+            llr = channel(code, ebno, frames)
+            B, n = llr.shape
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            bufs = {}
+            for leg in ("soft", "chase", "parent"):
+                bufs[leg] = dict(out=torch.empty((B, n), dtype=torch.uint8, device="cuda"),
+                                 nerr=torch.empty(B, dtype=torch.int32, device="cuda"),
+                                 status=torch.empty(B, dtype=torch.int32, device="cuda"),
+                                 metric=torch.empty(B, dtype=torch.float32, device="cuda"))
+            ext = torch.empty((B, n), dtype=torch.float32, device="cuda")
+            parent = parent_chase(parent_lib, code) if parent_lib else None
+            legs = {}
+            for p in PS:
+                b = bufs["soft"]
+                legs["soft p=%d" % p] = lambda p=p, b=b: capi.check(lib.cc_correct_chase_soft_batch_dev(
+                    code._h, ptr(llr), p, 0.5, ptr(b["out"]), ptr(ext), ptr(b["nerr"]), ptr(b["metric"]), ptr(b["status"]), B,
+                    stream), "soft")
+                b = bufs["chase"]
+                legs["chase p=%d" % p] = lambda p=p, b=b: capi.check(lib.cc_correct_chase_batch_dev(
+                    code._h, ptr(llr), p, ptr(b["out"]), ptr(b["nerr"]), ptr(b["metric"]), ptr(b["status"]), B, stream), "chase")
+                if parent:
+                    b = bufs["parent"]
+                    legs["parent p=%d" % p] = lambda p=p, b=b: capi.check(parent[2](
+                        parent[1], ptr(llr), p, ptr(b["out"]), ptr(b["nerr"]), ptr(b["metric"]), ptr(b["status"]), B, stream),
+                        "parent")
+            times = {k: [] for k in legs}
+            for k, call in legs.items():  # warm-up: code objects
+                call()
+                torch.cuda.synchronize()
+                if not k.startswith("soft"):  # the three legs of a p agree on the four outputs
+                    for name, v in bufs[k.split()[0]].items():
+                        assert torch.equal(v.view(torch.uint8), bufs["soft"][name].view(torch.uint8)), (k, name)
+            names = list(legs)
+            per_p = len(names) // len(PS)
+            for run in range(3):  # the legs of a p take turns at going first, so that no leg always follows the same one
+                for g in range(0, len(names), per_p):
+                    for i in range(per_p):
+                        k = names[g + (i + run) % per_p]
+                        times[k].append(timed_ms(legs[k]))
+            print("%s  %d frames at %.0f dB" % (code.to_string(), frames, ebno), flush=True)
+            for k, ts in times.items():
+                p = int(k.split("=")[1])
+                print("  %-11s ms %8.3f - %8.3f   ns/frame %8.2f   F %2d" % (
+                    k, max(ts), min(ts), 1e6 * min(ts) / frames, frames_per_wave(code, p, k.startswith("soft"))),
+                    flush=True)
+            for p in PS:
+                s_, c_ = times["soft p=%d" % p], times["chase p=%d" % p]
+                line = "  p = %d: soft / chase = %.2f - %.2f (fastest / fastest %.2f)" % (
+                    p, min(s_) / max(c_), max(s_) / min(c_), min(s_) / min(c_))
+                if parent:
+                    a_ = times["parent p=%d" % p]
+                    inside = min(a_) <= min(c_) <= max(a_) or min(a_) <= max(c_) <= max(a_) or (min(c_) <= min(a_) and max(c_) >= max(a_))
+                    line += "; chase %.3f - %.3f ms against the parent's %.3f - %.3f ms: %s" % (
+                        max(c_), min(c_), max(a_), min(a_), "within its spread" if inside else (
+                            "FASTER than its fastest" if max(c_) < min(a_) else "SLOWER than its slowest"))
+                print(line, flush=True)
+            del legs, bufs, ext, llr
+
+
+def product(blocks):
+    import numpy as np
+    import torch
+    import channelcoding_amd as cc
+    code = cc.primitive_bch(6, cc.errors(3), cc.berlekamp_massey_tag())
+    n, l, ebno = code.n, code.l, 3.0
+    rng = np.random.default_rng(1)
+    info = rng.integers(0, 2, (blocks, l, l)).astype(np.uint8)
+    wide = code.encode_batch(info.reshape(-1, l)).reshape(blocks, l, n)
+    sent = code.encode_batch(np.ascontiguousarray(wide.transpose(0, 2, 1)).reshape(-1, l)).reshape(blocks, n, n)
+    sent = np.ascontiguousarray(sent.transpose(0, 2, 1))
+    sigma = 1.0 / np.sqrt(2.0 * (l / n) ** 2 * 10.0 ** (ebno / 10.0))
+    y = ((1.0 - 2.0 * sent.astype(np.float32)) + np.float32(sigma) * rng.standard_normal(sent.shape).astype(np.float32))
+    y = torch.from_numpy(y.astype(np.float32)).cuda()
+    truth = torch.from_numpy(sent).cuda()
+    errors = lambda out: int((out != truth).any(dim=2).any(dim=1).sum())
+    rows = code.correct_batch(y.reshape(-1, n))["out"].reshape(blocks, n, n)  # hard decoding: rows, then columns
+    cols = code.correct_batch(rows.transpose(1, 2).contiguous().reshape(-1, n))["out"].reshape(blocks, n, n).transpose(1, 2)
+    alpha, beta = (0.0, 0.2, 0.3, 0.5, 0.7, 0.9), (0.2, 0.4, 0.6, 0.8, 1.0, 1.0)
+    print("BCH(63,45) x BCH(63,45), rate %.3f, %d blocks at %.1f dB, numpy seed 1: block errors" % ((l / n) ** 2, blocks, ebno))
+    print("  channel decisions %d   hard rows %d   hard rows then columns %d" % (
+        errors((y < 0).to(torch.uint8)), errors(rows), errors(cols)), flush=True)
+    for halves in range(1, len(alpha) + 1):
+        res = cc.product_decode(code, code, y, 4, alpha[:halves], beta[:halves])
+        print("  product_decode p = 4, %d half-iterations: %d" % (halves, errors(res["out"])), flush=True)
+
+
 def wer(frames):
     import channelcoding_amd as cc
     from channelcoding_amd import capi
@@ -128,12 +253,17 @@ def wer(frames):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=("rates", "wer"))
+    ap.add_argument("what", choices=("rates", "wer", "soft", "product"))
+    ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--frames-log2", type=int, default=None)
     ap.add_argument("--only", choices=("p6",))
     a = ap.parse_args()
     if a.what == "rates":
         rates(1 << (a.frames_log2 if a.frames_log2 is not None else 20), a.only)
+    elif a.what == "soft":
+        soft(1 << (a.frames_log2 if a.frames_log2 is not None else 20), a.parent_lib)
+    elif a.what == "product":
+        product(1 << (a.frames_log2 if a.frames_log2 is not None else 12))
     else:
         wer(1 << (a.frames_log2 if a.frames_log2 is not None else 22))
 
