@@ -239,6 +239,19 @@ constexpr int diag_variant_part(int variant, int parts) {
   return order % parts;
 }
 
+// How the general diagonal kernel reduces the rows of an iteration (minsum_diag_impl.hpp, BODY), per geometry and variant:
+// the four-row bodies run where they are measured faster than the butterfly and compile without spilling
+// (profiles/r18_experiments.md, E46).  Of the two orders the unpipelined one measured faster; -DCC_DIAG_FOUR_ROW_BODY=2
+// builds the pipelined one instead, to measure it again.
+enum DiagRowBody { DIAG_ROWS_BUTTERFLY = 0, DIAG_ROWS_FOUR = 1, DIAG_ROWS_FOUR_PIPELINED = 2 };
+#ifndef CC_DIAG_FOUR_ROW_BODY
+#define CC_DIAG_FOUR_ROW_BODY 1
+#endif
+constexpr int diag_row_body(int K, int D, int LPF, int variant) {
+  const bool plain = variant == CC_ALG_MS || variant == CC_ALG_NMS || variant == CC_ALG_OMS || variant == CC_ALG_2DNMS;
+  return (K == 24 && D == 7 && LPF == 16 && plain) ? CC_DIAG_FOUR_ROW_BODY : DIAG_ROWS_BUTTERFLY;
+}
+
 // wide.hip
 int launch_wide_correct(const cc_code *code, const uint16_t *d_in, const uint16_t *d_er, const uint32_t *d_off,
                         uint16_t *d_out, int32_t *d_nerr, int32_t *d_status, size_t B, hipStream_t stream);

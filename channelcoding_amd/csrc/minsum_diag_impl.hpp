@@ -140,7 +140,7 @@ __device__ __forceinline__ uint32_t group_or(uint32_t v) {
   return LPF == 16 ? or_stage<0x140>(v) : v;
 }
 
-// Reduction of FOUR rows at once inside a 16-lane DPP row (see the TRED branch of the kernel).  In: per lane the sorted
+// Reduction of FOUR rows at once inside a 16-lane DPP row (see the four-row branch of the kernel).  In: per lane the sorted
 // pair (a1 <= a2, bit patterns of non-negative floats) and the sign word of rows 0..3.  Out: in the four lanes of bank b
 // (lanes 4b..4b+3) the row's minimum, second minimum with multiplicity and sign parity (bit 31) of ROW b.
 // One asm statement: the assembler inserts no wait states inside inline asm, so the order below keeps every register
@@ -192,11 +192,21 @@ __device__ __forceinline__ void transposed_reduce4(const uint32_t (&a1)[4], cons
       "v_min_u32_dpp %[z1], %[z1], %[z1] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
       "v_xor_b32_dpp %[zs], %[zs], %[zs] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
       "v_mov_b32_dpp %[t], %[z2] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-      "v_min3_u32 %[z2], %[h], %[z2], %[t]"
+      "v_min3_u32 %[z2], %[h], %[z2], %[t]\n\t"
+      // (the results are read through DPP next, see bank_bcast: the compiler counts no wait states from inside here)
+      "s_nop 1"
       : [x1] "=&v"(x1), [x2] "=&v"(x2), [xs] "=&v"(xs), [y1] "=&v"(y1), [y2] "=&v"(y2), [ys] "=&v"(ys), [h] "=&v"(h),
         [t] "=&v"(t), [h2] "=&v"(h2), [t2] "=&v"(t2), [z1] "=&v"(z1), [z2] "=&v"(z2), [zs] "=&v"(zs)
       : [a10] "v"(a1[0]), [a11] "v"(a1[1]), [a12] "v"(a1[2]), [a13] "v"(a1[3]), [a20] "v"(a2[0]), [a21] "v"(a2[1]),
         [a22] "v"(a2[2]), [a23] "v"(a2[3]), [s0] "v"(sg[0]), [s1] "v"(sg[1]), [s2] "v"(sg[2]), [s3] "v"(sg[3]));
+}
+
+// Bank J's value of the own 16-lane DPP row (lane 4 J of it) for all 16 lanes: v_mov_b32_dpp row_newbcast:4J.  No LDS, no
+// lgkmcnt; checked on the hardware by profiles/ubench/row_newbcast_probe.hip.  The compiler supplies the wait states
+// between a VALU write of v and this read.
+template <int J>
+__device__ __forceinline__ uint32_t bank_bcast(uint32_t v) {
+  return static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(v), 0x150 + 4 * J, 0xF, 0xF, true));
 }
 
 // |.|-modified minimum / maximum / median without the canonicalisation the compiler puts in front of fminf on a
@@ -282,8 +292,10 @@ __device__ __forceinline__ float horizontal(float m, float alpha_f, double beta_
 // other diagonal touches that column in between, so the tail takes the {cs, y} pair the head read one row earlier
 // and continues the head's running column sum in registers: per link and row one {cs, y} read, one cs' read and
 // one cs' write less, in the reference's summation order (soft_decision.h:88-95) all the same.
+// BODY: how the rows of an iteration are reduced (DiagRowBody in cc_internal.hpp): one row per butterfly all-reduce, or
+// four rows per transposed reduction, with or without the next group's fronts ahead of this group's backs.
 template <int K, int D, int VARIANT, int RB, int LPF, int CPL, int OCC, bool PARTIAL, typename PG = PairGaps<>,
-          bool SINGLE = false, bool CHAIN = false>
+          bool SINGLE = false, bool CHAIN = false, int BODY = DIAG_ROWS_BUTTERFLY>
 __global__ void __launch_bounds__(256, OCC)
 minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const uint32_t *__restrict__ colbits,
                    const float *__restrict__ llr, const uint16_t *__restrict__ er, const uint32_t *__restrict__ er_off,
@@ -570,14 +582,12 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
     //  the bit words below take the 14 registers the prefetch would hold)
     // (SINGLE: the cs' half of a cell is written by the row before, so a row's operands are fetched when it starts)
     constexpr bool PREFETCH = !(BITS1 && K * D >= 160) && !SINGLE;
-    // four rows per (transposed) reduction, see below: bit-exact and 180 instructions per iteration shorter, but
-    // measured 1.4 % SLOWER than the butterfly (profiles/r03_experiments.md, E19: the reduction was what covered the LDS
-    // latency of each row's operands; without it the schedule needs four counted waits per row) -- experiments only
-#ifdef CC_EXP_TRED
-    constexpr bool TRED = LPF == 16 && K % 4 == 0 && !SINGLE;
-#else
-    constexpr bool TRED = false;
-#endif
+    // four rows per (transposed) reduction, see below
+    constexpr bool TRED = BODY != DIAG_ROWS_BUTTERFLY;
+    static_assert(!TRED || (LPF == 16 && K % 4 == 0 && !SINGLE && !NEEDQ),
+                  "four rows per reduction: a frame per DPP row, whole row groups, plain variants (the self-correcting ones spill)");
+    // h(m) = m: the back consumes Y = (m1 ^ m2) | parity << 31 and m2, made once per group in the bank lanes
+    constexpr bool READY = TRED && VARIANT == CC_ALG_MS;
     constexpr bool EARLY_PF = TRED && PREFETCH;
     float2 cyq[D];
     float2 carry_cy[NLK ? NLK : 1];  // the head's operands of the row before: the tail's operands of this row
@@ -586,7 +596,10 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
       constexpr int row = decltype(IC)::value;
       if constexpr (QONLY) rsq = my_rows[row];
       static_for<D>([&](auto DD) {
-        constexpr int d = DD;
+        // (four-row body: the requests go out in descending slot order, so that the front's first subtraction needs the
+        //  last-issued read and ONE counted wait covers the row's operands -- LDS returns in order; issued in ascending
+        //  order, each of them got a wait of its own, 4 more per row)
+        constexpr int d = TRED ? D - 1 - DD : DD;
         if constexpr (d < 2 * NLK && (d & 1) == 0 && row >= 1) {
           cyq[d] = carry_cy[d / 2];
           return;
@@ -693,7 +706,7 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
           wset(DD, q);
           qv[d] = q;
         });
-        // TRED: nothing hides the operands' latency between two fronts (the reduction comes after the fourth), so the
+        // four-row body: nothing hides the operands' latency between two fronts (the reduction comes after the fourth), so the
         // next row's operands are requested as soon as this row's have been consumed -- the pair tracking and the sign
         // parity below (~12 instructions) run while they travel
         if constexpr (EARLY_PF) {
@@ -772,6 +785,7 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
       });
     };
     // back: r from the row's minima and parity, then the column sums (soft_decision.h:101-122, :86-98)
+    // (READY: m1v is Y ready-made, m2v the second minimum, sg0 unused)
     auto row_back = [&](auto IR, uint32_t m1v, uint32_t m2v, uint32_t sg0, float (&cn)[D]) {
       constexpr int i = decltype(IR)::value;
       float rt[QONLY ? D : 1];  // QONLY: this row's r, used for the column sums and dropped
@@ -789,7 +803,7 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
       };
       // the parity leaves the last DPP stage in a register of its own: folded into the mask below, the compiler
       // undoes the DPP form of that stage (a bit operation with three inputs takes no DPP operand)
-      asm volatile("" : "+v"(sg0));
+      if constexpr (!READY) asm volatile("" : "+v"(sg0));
       const uint32_t sign31 = sg0 & 0x80000000u;
       if constexpr (VARIANT == CC_ALG_MS || VARIANT == CC_ALG_SCMS1 || VARIANT == CC_ALG_SCMS2) {  // h(m) = m
         // exclusive minimum with the exclusive sign in TWO instructions per edge: u = med3(q, -m2, m2) is
@@ -797,10 +811,11 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
         // XOR with m1 ^ m2 swaps the two magnitudes, XOR with the row parity (bit 31) turns sign(q) into the
         // product of the OTHER signs.  A zero keeps its sign bit through med3, as it did through the old
         // (t ^ Y) + signbit(q) form; with m1 = m2 = 0 the result is +-0 either way.
-        uint32_t Y = (m1v ^ m2v) | sign31;
+        uint32_t Y = READY ? m1v : (m1v ^ m2v) | sign31;
 #ifndef CC_EXP_BITOP3_POST
         // Y in a register of its own: otherwise the compiler folds the OR into every edge's XOR (v_bitop3_b32 with three
-        // inputs, a half-rate VOP3 encoding) where a plain v_xor_b32 issues at the full rate
+        // inputs, a half-rate VOP3 encoding) where a plain v_xor_b32 issues at the full rate -- or, READY, the broadcast
+        // into all D of them (v_xor_b32_dpp; the schedule it then finds is 54 instructions per iteration longer, E46)
         asm volatile("" : "+v"(Y));
 #endif
         const float hi = u2f(m2v);
@@ -854,27 +869,52 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
       // in banks 2, 3 (and the other way round), across lane bit 2 the same again, so that bank b ends up with row b
       // alone -- DPP bank masks select the writing lanes, so "keep mine, take yours" costs no select instruction
       // (7 + 2 instructions per row PAIR and stage) -- and only two butterfly stages inside the quads remain, on one
-      // row per lane: 37 instructions per four rows instead of 80.  ds_swizzle hands a bank's result to the other
-      // three (12 per group, LDS crossbar, no memory access).
-      static_for<K / 4>([&](auto IG) {
-        constexpr int g = IG;
+      // row per lane: 37 instructions per four rows instead of 80.  Bank J's result reaches the other three through
+      // bank_bcast at the top of row J's back, and not before: per group two (three) registers wait for their backs,
+      // which is what lets the fronts of the next group run ahead of them (DIAG_ROWS_FOUR_PIPELINED) inside the
+      // register file.  Fronts read CY and the message registers only, backs write CN only; the hand-offs among the
+      // fronts (carry_cy) and among the backs (carry_sum) and the ascending row order of the column sums are those of
+      // the butterfly body.
+      constexpr int NG = K / 4;
+      uint32_t ZA[NG], ZB[NG], ZC[READY ? 1 : NG];  // per bank: READY {Y, m2}, otherwise {m1, m2, parity}
+      auto fronts = [&](auto IG) {
+        constexpr int g = decltype(IG)::value;
         uint32_t a1[4], a2[4], sg[4];
         static_for<4>([&](auto J) { row_front(std::integral_constant<int, 4 * g + J>{}, a1[J], a2[J], sg[J]); });
         uint32_t z1, z2, zs;
         transposed_reduce4(a1, a2, sg, z1, z2, zs);
-        uint32_t M1[4], M2[4], SG[4];
-        static_for<4>([&](auto J) {
-          constexpr int pat = 0x13 | (J << 7);  // bit mode: lane' = (lane & 0x13) | (J << 2): bank J of the own 16-lane row
-          M1[J] = static_cast<uint32_t>(__builtin_amdgcn_ds_swizzle(static_cast<int>(z1), pat));
-          M2[J] = static_cast<uint32_t>(__builtin_amdgcn_ds_swizzle(static_cast<int>(z2), pat));
-          SG[J] = static_cast<uint32_t>(__builtin_amdgcn_ds_swizzle(static_cast<int>(zs), pat));
-        });
+        if constexpr (READY) {
+          ZA[g] = (z1 ^ z2) | (zs & 0x80000000u);
+          ZB[g] = z2;
+        } else {
+          ZA[g] = z1;
+          ZB[g] = z2;
+          ZC[g] = zs;
+        }
+      };
+      auto backs = [&](auto IG) {
+        constexpr int g = decltype(IG)::value;
         static_for<4>([&](auto J) {
           float cn[D];
           row_cn(std::integral_constant<int, 4 * g + J>{}, cn);
-          row_back(std::integral_constant<int, 4 * g + J>{}, M1[J], M2[J], SG[J], cn);
+          const uint32_t b0 = bank_bcast<J>(ZA[g]), b1 = bank_bcast<J>(ZB[g]);
+          uint32_t b2 = 0;
+          if constexpr (!READY) b2 = bank_bcast<J>(ZC[g]);
+          row_back(std::integral_constant<int, 4 * g + J>{}, b0, b1, b2, cn);
         });
-      });
+      };
+      if constexpr (BODY == DIAG_ROWS_FOUR_PIPELINED) {
+        fronts(std::integral_constant<int, 0>{});
+        static_for<NG>([&](auto IG) {
+          if constexpr (IG + 1 < NG) fronts(std::integral_constant<int, IG + 1>{});
+          backs(IG);
+        });
+      } else {
+        static_for<NG>([&](auto IG) {
+          fronts(IG);
+          backs(IG);
+        });
+      }
     } else {
       static_for<K>([&](auto IR) {
         uint32_t m1[1], m2[1], sg[1];
@@ -1084,11 +1124,14 @@ int launch_diag_geometry(const cc_code *code, const MinSumParams &p, const float
     const size_t lds_k = (S) ? lds_s : lds;                                                                        \
     const int grid_k = (S) ? grid_s : grid;                                                                        \
     e = hipFuncSetAttribute(                                                                                       \
-        reinterpret_cast<const void *>(&minsum_diag_kernel<K, D, V, RB, LPF, CPL, O, PARTIAL, PG, S, CHAIN>),      \
+        reinterpret_cast<const void *>(&minsum_diag_kernel<K, D, V, RB, LPF, CPL, O, PARTIAL, PG, S, CHAIN,        \
+                                                           (S) ? DIAG_ROWS_BUTTERFLY : diag_row_body(K, D, LPF, V)>), \
         hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_k));                                     \
     if (e == hipSuccess)                                                                                           \
-      hipLaunchKernelGGL((minsum_diag_kernel<K, D, V, RB, LPF, CPL, O, PARTIAL, PG, S, CHAIN>), dim3(grid_k), dim3(256), lds_k, \
-                         stream, p, code->d_diag, code->d_colbits, d_llr, d_er, d_er_off, d_hard, d_L, d_iters,    \
+      hipLaunchKernelGGL((minsum_diag_kernel<K, D, V, RB, LPF, CPL, O, PARTIAL, PG, S, CHAIN,                        \
+                                             (S) ? DIAG_ROWS_BUTTERFLY : diag_row_body(K, D, LPF, V)>),               \
+                         dim3(grid_k), dim3(256), lds_k, stream, p, code->d_diag, code->d_colbits, d_llr, d_er,    \
+                         d_er_off, d_hard, d_L, d_iters,                                                           \
                          d_status, Bq);                                                                            \
   }
   // one iteration per frame by construction (stop rule O0, SURVEY F1, or Iterations == 1): the message-free kernel
