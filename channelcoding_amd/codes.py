@@ -155,9 +155,147 @@ def _erasure_csr(erasures, B, n):
     return vals, off
 
 
-def _torch_symbol_dtypes():
-    import torch
-    return (torch.uint8, torch.int16) + ((torch.uint16,) if hasattr(torch, "uint16") else ())
+def _torch_symbol_dtypes(cache=[]):
+    if not cache:
+        import torch
+        cache.append((torch.uint8, torch.int16) + ((torch.uint16,) if hasattr(torch, "uint16") else ()))
+    return cache[0]
+
+
+_TORCH_DTYPE = {}
+
+
+def _torch_dtype(dtype):
+    """the tensor type of an output of numpy type `dtype`; uint16 (iters) is int16 on the device"""
+    if not _TORCH_DTYPE:
+        import torch
+        _TORCH_DTYPE.update({np.uint8: torch.uint8, np.uint16: torch.int16, np.int32: torch.int32,
+                             np.float32: torch.float32})
+    return _TORCH_DTYPE[dtype]
+
+
+class _host:
+    """A batch call on numpy arrays: the C call as it is named, outputs zeroed, the erasure list of _erasure_csr."""
+    dev = ""
+    in_place_needs = {True: "uint8 array", False: "array of the code's symbol type"}  # by packed=
+    out_must_be = {True: "writable uint8 array of shape (B, packed_bytes)",
+                   False: "writable array of the input's shape and the code's symbol type"}
+    asarray = staticmethod(np.asarray)
+    symbols = staticmethod(lambda x, dtype, itemsize, any16: np.ascontiguousarray(x, dtype))
+
+    @staticmethod
+    def size(x):
+        return x.size
+
+    @staticmethod
+    def alloc(like, shape, dtype):
+        return np.zeros(shape, dtype or like.dtype)
+
+    @staticmethod
+    def erasure_list(like, vals, off):
+        return vals, off
+
+    @staticmethod
+    def stream(like):
+        return ()
+
+    @staticmethod
+    def is_symbols(x):
+        return isinstance(x, np.ndarray) and x.dtype.kind not in "fi"
+
+    @staticmethod
+    def is_contiguous(x, dtype):
+        return isinstance(x, np.ndarray) and x.dtype == dtype and x.flags.c_contiguous
+
+    @staticmethod
+    def is_buffer(a, like, shape):
+        return (isinstance(a, np.ndarray) and a.dtype == like.dtype and a.flags.c_contiguous and a.flags.writeable
+                and a.shape == shape)
+
+    @staticmethod
+    def as_type(x, kind, dtype):
+        x = np.asarray(x)
+        return np.ascontiguousarray(x, dtype) if x.dtype.kind == kind else None
+
+    @staticmethod
+    def channel_input(b, soft_alg):
+        """-> (which cc_correct_*_batch, its input): a signed element type holds soft values, an unsigned one symbols"""
+        signed = b.dtype.kind in "fi"
+        if soft_alg and not signed:
+            raise TypeError("min-sum needs a signed (soft) input sequence")
+        if signed:
+            return "soft" if soft_alg else "hard_f32", np.ascontiguousarray(b, np.float32)
+        return "hard", np.ascontiguousarray(b, np.uint8)
+
+
+class _device:
+    """A batch call on torch tensors: the _dev call on the current stream, outputs on the input's device."""
+    dev = "_dev"
+    in_place_needs = {True: "tensor", False: "tensor"}
+    out_must_be = {True: "uint8 tensor of shape (B, packed_bytes) on the input's device",
+                   False: "tensor of the input's shape, dtype and device"}
+    asarray = staticmethod(lambda x: x)
+    is_symbols = staticmethod(lambda x: True)  # (symbols() decides)
+
+    @staticmethod
+    def size(x):
+        return x.numel()
+
+    @staticmethod
+    def alloc(like, shape, dtype):
+        return like.new_empty(shape, dtype=_torch_dtype(dtype)) if dtype else like.new_empty(shape)
+
+    @staticmethod
+    def erasure_list(like, vals, off):
+        import torch
+        if vals.size == 0:  # an empty tensor has a null data pointer: keep the list addressable
+            vals = np.zeros(1, vals.dtype)
+        return (torch.from_numpy(vals.astype(np.int16)).to(like.device),
+                torch.from_numpy(off.astype(np.int32)).to(like.device))
+
+    @staticmethod
+    def stream(like):
+        return (_stream_handle(like),)
+
+    @staticmethod
+    def is_contiguous(x, dtype):
+        return x.is_contiguous()
+
+    @staticmethod
+    def is_buffer(a, like, shape):
+        return (_is_torch(a) and a.dtype == like.dtype and a.device == like.device and a.is_contiguous()
+                and tuple(a.shape) == shape)
+
+    @staticmethod
+    def symbols(x, dtype, itemsize, any16):
+        """x contiguous, or None where it does not hold symbols of dtype's width (any16: any 2-byte type does)"""
+        x = x.contiguous()
+        return x if x.element_size() == itemsize and (any16 or x.dtype in _torch_symbol_dtypes()) else None
+
+    @staticmethod
+    def as_type(x, kind, dtype):
+        return x.contiguous() if x.dtype == _torch_dtype(dtype) else None
+
+    @staticmethod
+    def channel_input(b, soft_alg):
+        import torch
+        if soft_alg:
+            if b.dtype != torch.float32:
+                raise TypeError("min-sum needs float32 LLRs")
+            return "soft", b.contiguous()
+        if b.dtype == torch.float32:
+            return "hard_f32", b.contiguous()
+        if b.dtype == torch.uint8:
+            return "hard", b.contiguous()
+        raise TypeError("hard decoding takes uint8 symbols or float32 soft values")
+
+
+def _side(x):
+    return _device if _is_torch(x) else _host
+
+
+_PER_FRAME = {"nerr": np.int32, "status": np.int32, "iters": np.uint16, "metric": np.float32}  # (iters: int16 in torch)
+_KEYS = ("out", "msg", "status", "nerr", "iters", "metric", "L", "ext")  # the order of a result dict
 
 
 def symbol_reliability(y, q):
@@ -564,77 +702,6 @@ class cyclic:
             raise CcError(-r, "cc_packed_map_route")
         return r
 
-    def _packed_map(self, x, which_in, name):
-        lib = capi.lib()
-        w_in, w_out = self._packed_width(which_in), self._packed_width(1 - which_in)
-        if _is_torch(x):
-            import torch
-            x = x.contiguous()
-            if x.dtype != torch.uint8 or x.shape[-1] != w_in:
-                raise CcError(capi.ERR_LENGTH, name)
-            B = x.numel() // w_in
-            out = torch.empty((B, w_out), dtype=torch.uint8, device=x.device)
-            capi.check(getattr(lib, name + "_dev")(self._h, _ptr(x), _ptr(out), B, _stream_handle(x)), name + "_dev")
-            return out
-        x = np.ascontiguousarray(x, np.uint8)
-        if x.shape[-1] != w_in:
-            raise CcError(capi.ERR_LENGTH, name)
-        x = x.reshape(-1, w_in)
-        out = np.zeros((x.shape[0], w_out), np.uint8)
-        capi.check(getattr(lib, name)(self._h, _ptr(x), _ptr(out), x.shape[0]), name)
-        return out
-
-    def _packed_correct(self, b, erasures, out=None):
-        lib = capi.lib()
-        P = self._packed_width(0)
-        if b.shape[-1] != P:
-            raise CcError(capi.ERR_LENGTH, "correct_batch")
-        if _is_torch(b):
-            import torch
-            given = b
-            if out is b and not b.is_contiguous():
-                raise TypeError("decoding in place needs a contiguous tensor")
-            b = b.contiguous()
-            if b.dtype != torch.uint8:
-                raise TypeError("packed words are uint8")
-            B = b.numel() // P
-            dev = b.device
-            er = off = None
-            if erasures is not None:
-                ev, eo = _erasure_csr(erasures, B, self.n)
-                if ev is not None:
-                    ev = ev if ev.size else np.zeros(1, ev.dtype)
-                    er = torch.from_numpy(ev.astype(np.int16)).to(dev)
-                    off = torch.from_numpy(eo.astype(np.int32)).to(dev)
-            if out is None:
-                out = torch.empty((B, P), dtype=torch.uint8, device=dev)
-            elif out is given:  # decoding in place: the (contiguous) input itself
-                out = b
-            elif not (_is_torch(out) and out.dtype == torch.uint8 and out.device == dev and out.is_contiguous()
-                      and tuple(out.shape) == (B, P)):
-                raise TypeError("out= must be a contiguous uint8 tensor of shape (B, packed_bytes) on the input's device")
-            nerr = torch.empty(B, dtype=torch.int32, device=dev)
-            status = torch.empty(B, dtype=torch.int32, device=dev)
-            capi.check(lib.cc_correct_hard_packed_batch_dev(self._h, _ptr(b), _ptr(er), _ptr(off), _ptr(out), _ptr(nerr),
-                                                            _ptr(status), B, _stream_handle(b)),
-                       "cc_correct_hard_packed_batch_dev")
-            return dict(out=out, status=status, nerr=nerr)
-        if out is b and not (isinstance(b, np.ndarray) and b.dtype == np.uint8 and b.flags.c_contiguous):
-            raise TypeError("decoding in place needs a contiguous uint8 array")
-        b = np.ascontiguousarray(b, np.uint8).reshape(-1, P)
-        B = b.shape[0]
-        er, off = _erasure_csr(erasures, B, self.n)
-        if out is None:
-            out = np.zeros((B, P), np.uint8)
-        elif not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous
-                  and out.flags.writeable and out.shape == (B, P)):
-            raise TypeError("out= must be a contiguous writable uint8 array of shape (B, packed_bytes)")
-        nerr = np.zeros(B, np.int32)
-        status = np.zeros(B, np.int32)
-        capi.check(lib.cc_correct_hard_packed_batch(self._h, _ptr(b), _ptr(er), _ptr(off), _ptr(out), _ptr(nerr),
-                                                    _ptr(status), B), "cc_correct_hard_packed_batch")
-        return dict(out=out, status=status, nerr=nerr)
-
     # ---- symbol-interleaved blocks: arrays of shape (B / I, n, I), messages (B / I, l, I) ----
     def interleaved_route(self, B, I, erasures=False):
         """1 if correct_batch(interleave=I) of B frames decodes the interleaved blocks natively, 0 if it goes through
@@ -651,183 +718,92 @@ class cyclic:
             raise CcError(-r, "cc_interleaved_map_route")
         return r
 
-    def _interleaved(self, kind, x, I, erasures=None, out=None):
-        """kind 0 = encode, 1 = extract, 2 = correct on blocks of shape (B / I, width, I)"""
-        lib = capi.lib()
-        I = int(I)
-        name = ("cc_encode_interleaved_batch", "cc_extract_interleaved_batch", "cc_correct_hard_interleaved_batch")[kind]
-        name += "_u16" if self.wide else ""
-        w_in, w_out = (self.l if kind == 0 else self.n), (self.l if kind == 1 else self.n)
-        if x.ndim != 3 or x.shape[1] != w_in or x.shape[2] != I:
-            raise CcError(capi.ERR_LENGTH, name)
-        blocks = x.shape[0]
-        B = blocks * I
-        shape = (blocks, w_out, I)
-        if _is_torch(x):
-            import torch
-            given = x
-            if out is x and not x.is_contiguous():
-                raise TypeError("decoding in place needs a contiguous tensor")
-            x = x.contiguous()
-            if x.element_size() != (2 if self.wide else 1) or x.dtype not in _torch_symbol_dtypes():
-                raise TypeError("interleave= takes uint8 symbols (16-bit integer symbols for q > 8)")
-            dev = x.device
-            if out is None:
-                out = torch.empty(shape, dtype=x.dtype, device=dev)
-            elif kind != 2:
-                raise TypeError("out= goes with correct_batch")
-            elif out is given:
-                out = x
-            elif not (_is_torch(out) and out.dtype == x.dtype and out.device == dev and out.is_contiguous()
-                      and tuple(out.shape) == shape):
-                raise TypeError("out= must be a contiguous tensor of the input's shape, dtype and device")
-            st = _stream_handle(x)
-            if kind != 2:
-                capi.check(getattr(lib, name + "_dev")(self._h, _ptr(x), _ptr(out), B, I, st), name + "_dev")
-                return out
-            er = off = None
-            if erasures is not None:
-                ev, eo = _erasure_csr(erasures, B, self.n)
-                if ev is not None:
-                    ev = ev if ev.size else np.zeros(1, ev.dtype)
-                    er = torch.from_numpy(ev.astype(np.int16)).to(dev)
-                    off = torch.from_numpy(eo.astype(np.int32)).to(dev)
-            nerr = torch.empty(B, dtype=torch.int32, device=dev)
-            status = torch.empty(B, dtype=torch.int32, device=dev)
-            capi.check(getattr(lib, name + "_dev")(self._h, _ptr(x), _ptr(er), _ptr(off), _ptr(out), _ptr(nerr), _ptr(status),
-                                                   B, I, st), name + "_dev")
-            return dict(out=out, status=status, nerr=nerr)
-        dt = np.uint16 if self.wide else np.uint8
-        if not isinstance(x, np.ndarray) or x.dtype.kind in "fi":
-            raise TypeError("interleave= takes unsigned symbols")
-        if out is x and not (x.dtype == dt and x.flags.c_contiguous):
-            raise TypeError("decoding in place needs a contiguous array of the code's symbol type")
-        x = np.ascontiguousarray(x, dt)
-        if out is None:
-            out = np.zeros(shape, dt)
-        elif kind != 2:
-            raise TypeError("out= goes with correct_batch")
-        elif not (isinstance(out, np.ndarray) and out.dtype == dt and out.flags.c_contiguous and out.flags.writeable
-                  and out.shape == shape):
-            raise TypeError("out= must be a contiguous writable array of the input's shape and the code's symbol type")
-        if kind != 2:
-            capi.check(getattr(lib, name)(self._h, _ptr(x), _ptr(out), B, I), name)
-            return out
-        er, off = _erasure_csr(erasures, B, self.n)
-        nerr = np.zeros(B, np.int32)
-        status = np.zeros(B, np.int32)
-        capi.check(getattr(lib, name)(self._h, _ptr(x), _ptr(er), _ptr(off), _ptr(out), _ptr(nerr), _ptr(status), B, I), name)
-        return dict(out=out, status=status, nerr=nerr)
-
     # ---- batch API (numpy host arrays or torch CUDA tensors) ----
-    # ---- q > 8: 16-bit symbols (numpy uint16 on the host, torch int16 / uint16 on the device) ----
-    def _wide_map(self, x, width_in, width_out, host_fn, dev_fn):
-        lib = capi.lib()
-        if _is_torch(x):
-            import torch
-            x = x.contiguous()
-            if x.element_size() != 2 or x.shape[-1] != width_in:
-                raise CcError(capi.ERR_LENGTH, dev_fn)
-            B = x.numel() // width_in
-            out = torch.empty((B, width_out), dtype=x.dtype, device=x.device)
-            capi.check(getattr(lib, dev_fn)(self._h, _ptr(x), _ptr(out), B, _stream_handle(x)), dev_fn)
-            return out
-        x = np.ascontiguousarray(x, np.uint16)
-        if x.shape[-1] != width_in:
-            raise CcError(capi.ERR_LENGTH, host_fn)
-        x = x.reshape(-1, width_in)
-        out = np.zeros((x.shape[0], width_out), np.uint16)
-        capi.check(getattr(lib, host_fn)(self._h, _ptr(x), _ptr(out), x.shape[0]), host_fn)
-        return out
+    def _batch_call(self, name, ins, B, outs, per_frame=(), args=(), tail=(), erasures=False):
+        """One batch call of the library, for host arrays and device tensors alike: `name`(handle, *ins[, erasure list],
+        *args, *outs, *per_frame, B, *tail), for tensors `name`_dev with the stream last.  ins: the contiguous inputs.
+        outs: the call's leading outputs in its order, key -> (shape, dtype), dtype None being that of ins[0]; a buffer
+        of the caller's in place of the pair is used as it is, None passes a null pointer.  per_frame: the keys of
+        _PER_FRAME that follow, (B,) each.  erasures: as correct_batch takes them, False for a call without the list.
+        Returns the dict of the outputs, in the order of _KEYS."""
+        x = ins[0]
+        side = _side(x)
+        call = [self._h] + [_ptr(a) for a in ins]
+        if erasures is not False:
+            lists = _erasure_csr(erasures, B, self.n)
+            if lists[0] is not None:
+                lists = side.erasure_list(x, *lists)
+            call += [_ptr(lists[0]), _ptr(lists[1])]
+        call += args
+        res = {k: side.alloc(x, *s) if type(s) is tuple else s for k, s in outs.items()}
+        for k in per_frame:
+            res[k] = side.alloc(x, (B,), _PER_FRAME[k])
+        call += [_ptr(a) for a in res.values()]
+        call.append(B)
+        call += tail
+        call += side.stream(x)
+        name += side.dev
+        capi.check(getattr(capi.lib(), name)(*call), name)
+        return {k: res[k] for k in _KEYS if k in res and res[k] is not None}
 
-    def _wide_correct(self, b, erasures):
-        lib = capi.lib()
-        if _is_torch(b):
-            import torch
-            b = b.contiguous()
-            if b.element_size() != 2 or b.shape[-1] != self.n:
-                raise CcError(capi.ERR_LENGTH, "correct_batch")
-            B = b.numel() // self.n
-            er = off = None
-            if erasures is not None:
-                ev, eo = _erasure_csr(erasures, B, self.n)
-                if ev is not None:
-                    ev = ev if ev.size else np.zeros(1, ev.dtype)
-                    er = torch.from_numpy(ev.astype(np.int16)).to(b.device)
-                    off = torch.from_numpy(eo.astype(np.int32)).to(b.device)
-            out = torch.empty((B, self.n), dtype=b.dtype, device=b.device)
-            nerr = torch.empty(B, dtype=torch.int32, device=b.device)
-            status = torch.empty(B, dtype=torch.int32, device=b.device)
-            capi.check(lib.cc_correct_hard_batch_u16_dev(self._h, _ptr(b), _ptr(er), _ptr(off), _ptr(out), _ptr(nerr),
-                                                         _ptr(status), B, _stream_handle(b)),
-                       "cc_correct_hard_batch_u16_dev")
-            return dict(out=out, status=status, nerr=nerr)
-        b = np.ascontiguousarray(b, np.uint16)
-        if b.shape[-1] != self.n:
-            raise CcError(capi.ERR_LENGTH, "correct_batch")
-        b = b.reshape(-1, self.n)
-        B = b.shape[0]
-        er, off = _erasure_csr(erasures, B, self.n)
-        out = np.zeros((B, self.n), np.uint16)
-        nerr = np.zeros(B, np.int32)
-        status = np.zeros(B, np.int32)
-        capi.check(lib.cc_correct_hard_batch_u16(self._h, _ptr(b), _ptr(er), _ptr(off), _ptr(out), _ptr(nerr),
-                                                 _ptr(status), B), "cc_correct_hard_batch_u16")
-        return dict(out=out, status=status, nerr=nerr)
+    def _symbols(self, op, x, which, packed, I, out=None):
+        """The symbol input of a batch call in its layout -- packed=True (uint8 words, see pack_bits), interleave=I
+        (blocks of shape (B / I, width, I)) or plain, 8-bit symbols or for q > 8 16-bit ones (numpy uint16 on the host,
+        torch int16 / uint16 on the device) -- holding codewords (which = 0) or messages (1).  Checks shape and type and
+        returns (the C name of `op`, x contiguous in the layout's type, B, the call's arguments after B, shape), with
+        shape(which) the layout's shape of B codewords / messages.  out: correct_batch's out=, for the in-place rule."""
+        side, wide, depth = _side(x), self.wide and not packed, I is not None
+        name = "cc_" + op + ("_packed_batch" if packed else "_interleaved_batch" if depth else "_batch") \
+            + ("_u16" if wide else "")
+
+        def wrong_length():
+            # named after the method, but after the C call for blocks (the fused decode apart) and packed or 16-bit maps
+            if (depth and op != "decode_hard") or (op in ("encode", "extract") and (packed or wide)):
+                return CcError(capi.ERR_LENGTH, name + (side.dev if wide and not depth else ""))
+            return CcError(capi.ERR_LENGTH, op.split("_")[0] + "_batch")
+        width = self._packed_width if packed else (self.n, self.l).__getitem__
+        w = width(which)
+        if depth:
+            I = int(I)
+            if x.ndim != 3 or x.shape[1] != w or x.shape[2] != I:
+                raise wrong_length()
+            if not side.is_symbols(x):
+                raise TypeError("interleave= takes unsigned symbols")
+        else:
+            x = side.asarray(x)
+            if x.shape[-1] != w:
+                raise wrong_length()
+        dtype, itemsize = (np.uint16, 2) if wide else (np.uint8, 1)
+        if out is x and not side.is_contiguous(x, dtype):
+            raise TypeError("decoding in place needs a contiguous " + side.in_place_needs[bool(packed)])
+        x = side.symbols(x, dtype, itemsize, wide and not depth)
+        if x is None:
+            if depth:
+                raise TypeError("interleave= takes uint8 symbols (16-bit integer symbols for q > 8)")
+            if packed and op == "correct_hard":
+                raise TypeError("packed words are uint8")
+            raise wrong_length()
+        B = side.size(x) // w
+        if depth:
+            blocks = x.shape[0]
+            return name, x, B, (I,), lambda which: (blocks, width(which), I)
+        return name, x, B, (), lambda which: (B, width(which))
+
+    def _map(self, op, x, which, packed, interleave):
+        """encode_batch (messages in, which = 1) and extract_batch (codewords in, which = 0) in every layout"""
+        if interleave is not None and packed:
+            raise TypeError("interleave= does not combine with packed=True")
+        name, x, B, tail, shape = self._symbols(op, x, which, packed, interleave)
+        return self._batch_call(name, [x], B, {"out": (shape(1 - which), None)}, tail=tail)["out"]
 
     def encode_batch(self, msg, packed=False, interleave=None):
         """packed=True: uint8 (B, packed_message_bytes) -> uint8 (B, packed_bytes), see pack_bits.
         interleave=I: symbol-interleaved blocks, (B / I, l, I) -> (B / I, n, I), see interleave()."""
-        lib = capi.lib()
-        if interleave is not None:
-            if packed:
-                raise TypeError("interleave= does not combine with packed=True")
-            return self._interleaved(0, msg, interleave)
-        if packed:
-            return self._packed_map(msg, 1, "cc_encode_packed_batch")
-        if self.wide:
-            return self._wide_map(msg, self.l, self.n, "cc_encode_batch_u16", "cc_encode_batch_u16_dev")
-        if _is_torch(msg):
-            import torch
-            msg = msg.contiguous()
-            if msg.dtype != torch.uint8 or msg.shape[-1] != self.l:
-                raise CcError(capi.ERR_LENGTH, "encode_batch")
-            B = msg.numel() // self.l
-            cw = torch.empty((B, self.n), dtype=torch.uint8, device=msg.device)
-            capi.check(lib.cc_encode_batch_dev(self._h, _ptr(msg), _ptr(cw), B, _stream_handle(msg)),
-                       "cc_encode_batch_dev")
-            return cw
-        msg = np.ascontiguousarray(msg, np.uint8)
-        if msg.shape[-1] != self.l:
-            raise CcError(capi.ERR_LENGTH, "encode_batch")  # cyclic.h:291-296
-        msg = msg.reshape(-1, self.l)
-        cw = np.zeros((msg.shape[0], self.n), np.uint8)
-        capi.check(lib.cc_encode_batch(self._h, _ptr(msg), _ptr(cw), msg.shape[0]), "cc_encode_batch")
-        return cw
+        return self._map("encode", msg, 1, packed, interleave)  # a wrong length: cyclic.h:291-296
 
     def extract_batch(self, cw, packed=False, interleave=None):
         """interleave=I: symbol-interleaved blocks, (B / I, n, I) -> (B / I, l, I), see interleave()."""
-        lib = capi.lib()
-        if interleave is not None:
-            if packed:
-                raise TypeError("interleave= does not combine with packed=True")
-            return self._interleaved(1, cw, interleave)
-        if packed:
-            return self._packed_map(cw, 0, "cc_extract_packed_batch")
-        if self.wide:
-            return self._wide_map(cw, self.n, self.l, "cc_extract_batch_u16", "cc_extract_batch_u16_dev")
-        if _is_torch(cw):
-            import torch
-            cw = cw.contiguous()
-            B = cw.numel() // self.n
-            msg = torch.empty((B, self.l), dtype=torch.uint8, device=cw.device)
-            capi.check(lib.cc_extract_batch_dev(self._h, _ptr(cw), _ptr(msg), B, _stream_handle(cw)),
-                       "cc_extract_batch_dev")
-            return msg
-        cw = np.ascontiguousarray(cw, np.uint8).reshape(-1, self.n)
-        msg = np.zeros((cw.shape[0], self.l), np.uint8)
-        capi.check(lib.cc_extract_batch(self._h, _ptr(cw), _ptr(msg), cw.shape[0]), "cc_extract_batch")
-        return msg
+        return self._map("extract", cw, 0, packed, interleave)
 
     def correct_batch(self, b, erasures=None, want_L=False, packed=False, out=None, interleave=None, chase=None, gmd=None,
                       reliability=None, soft=None):
@@ -848,7 +824,6 @@ class cyclic:
         CC_AMD_PACKED_LONG_MIN_FRAMES frames, see packed_route.
         interleave=I (hard algorithms): b and out are symbol-interleaved blocks of shape (B / I, n, I), see interleave();
         status, nerr and the erasure lists are per frame f = b I + j, as without it; out= as with packed=True."""
-        lib = capi.lib()
         if soft is not None and (chase is None or gmd is not None or reliability is not None):
             raise TypeError("soft= goes with chase= and with nothing else")
         if gmd is not None or reliability is not None:
@@ -862,156 +837,70 @@ class cyclic:
             if erasures is not None or want_L or packed or out is not None or interleave is not None:
                 raise TypeError("chase= does not combine with erasures, want_L, packed=True, out= or interleave=")
             return self._chase(b, chase, soft)
-        if interleave is not None:
-            if packed:
-                raise TypeError("interleave= does not combine with packed=True")
-            return self._interleaved(2, b, interleave, erasures, out)
-        if packed:
-            return self._packed_correct(b, erasures, out)
-        if out is not None:
+        if interleave is not None and packed:
+            raise TypeError("interleave= does not combine with packed=True")
+        if interleave is None and not packed and out is not None:
             raise TypeError("out= goes with packed=True or interleave=")
-        soft_alg = self.algorithm.soft
-        if self.wide and not soft_alg:  # (min-sum takes LLRs and returns bits whatever the symbol width)
-            return self._wide_correct(b, erasures)
-        if _is_torch(b):
-            return self._correct_batch_torch(b, erasures, want_L)
-        b = np.asarray(b)
+        side, soft_alg = _side(b), self.algorithm.soft
+        if interleave is not None or packed or (self.wide and not soft_alg):  # symbols, whatever the algorithm
+            name, x, B, tail, shape = self._symbols("correct_hard", b, 0, packed, interleave, out)
+            if out is None:
+                out = (shape(0), None)
+            elif out is b and side is _device:  # decoding in place: the (contiguous) input itself
+                out = x
+            elif not side.is_buffer(out, x, shape(0)):
+                raise TypeError("out= must be a contiguous " + side.out_must_be[bool(packed)])
+            return self._batch_call(name, [x], B, {"out": out}, ("nerr", "status"), tail=tail, erasures=erasures)
+        # (min-sum takes LLRs and returns bits whatever the symbol width)
+        b = side.asarray(b)
         if b.shape[-1] != self.n:
             raise CcError(capi.ERR_LENGTH, "correct_batch")  # cyclic.h:213-218
-        signed = b.dtype.kind in "fi"
-        B = b.size // self.n
-        er, off = _erasure_csr(erasures, B, self.n)
-        out = np.zeros((B, self.n), np.uint8)
-        status = np.zeros(B, np.int32)
+        kind, x = side.channel_input(b, soft_alg)
+        B = side.size(x) // self.n
+        outs = {"out": ((B, self.n), np.uint8)}
         if soft_alg:
-            if not signed:
-                raise TypeError("min-sum needs a signed (soft) input sequence")
-            y = np.ascontiguousarray(b, np.float32).reshape(B, self.n)
-            L = np.zeros((B, self.n), np.float32) if want_L else None
-            iters = np.zeros(B, np.uint16)
-            capi.check(lib.cc_correct_soft_batch(self._h, _ptr(y), _ptr(er), _ptr(off), _ptr(out), _ptr(L),
-                                                 _ptr(iters), _ptr(status), B), "cc_correct_soft_batch")
-            res = dict(out=out, status=status, iters=iters)
-            if want_L:
-                res["L"] = L
-            return res
-        nerr = np.zeros(B, np.int32)
-        if signed:
-            y = np.ascontiguousarray(b, np.float32).reshape(B, self.n)
-            capi.check(lib.cc_correct_hard_f32_batch(self._h, _ptr(y), _ptr(er), _ptr(off), _ptr(out), _ptr(nerr),
-                                                     _ptr(status), B), "cc_correct_hard_f32_batch")
-        else:
-            sym = np.ascontiguousarray(b, np.uint8).reshape(B, self.n)
-            capi.check(lib.cc_correct_hard_batch(self._h, _ptr(sym), _ptr(er), _ptr(off), _ptr(out), _ptr(nerr),
-                                                 _ptr(status), B), "cc_correct_hard_batch")
-        return dict(out=out, status=status, nerr=nerr)
-
-    def _soft_call(self, name, ins, arg, beta=None):
-        """`name`(_dev for device tensors) over the contiguous inputs `ins`, B frames of n values each, with the decoder's
-        argument `arg`: allocates what the reliability-based decoders return, makes the call and returns the dict.
-        beta: the call also takes beta after `arg` and ext (B, n) f32 after out, and the dict carries ext."""
-        if _is_torch(ins[0]):
-            import torch
-            B, dev = ins[0].numel() // self.n, ins[0].device
-            out = torch.empty((B, self.n), dtype=torch.uint8, device=dev)
-            nerr, status = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
-            metric = torch.empty(B, dtype=torch.float32, device=dev)
-            ext = torch.empty((B, self.n), dtype=torch.float32, device=dev) if beta is not None else None
-            name, tail = name + "_dev", (_stream_handle(ins[0]),)
-        else:
-            B, tail = ins[0].size // self.n, ()
-            out = np.zeros((B, self.n), np.uint8)
-            nerr, status, metric = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.float32)
-            ext = np.zeros((B, self.n), np.float32) if beta is not None else None
-        args, outs = (arg,) if beta is None else (arg, beta), (_ptr(out),) if beta is None else (_ptr(out), _ptr(ext))
-        capi.check(getattr(capi.lib(), name)(self._h, *map(_ptr, ins), *args, *outs, _ptr(nerr), _ptr(metric),
-                                             _ptr(status), B, *tail), name)
-        res = dict(out=out, status=status, nerr=nerr, metric=metric)
-        if beta is not None:
-            res["ext"] = ext
-        return res
+            outs["L"] = ((B, self.n), np.float32) if want_L else None
+        return self._batch_call("cc_correct_%s_batch" % kind, [x], B, outs, ("iters" if soft_alg else "nerr", "status"),
+                                erasures=erasures)
 
     def _chase(self, b, p, beta=None):
         """correct_batch(chase=p[, soft=beta]): float32 channel values, host array or device tensor."""
         p = int(p)
         if p < 0:
             raise ValueError("chase= takes p >= 0")
-        name = "cc_correct_chase_batch"
         if beta is not None:
             if isinstance(beta, bool) or not isinstance(beta, (int, float, np.integer, np.floating)):
                 raise TypeError("soft= takes beta, a float")
             with np.errstate(over="ignore"):  # (beyond float32: +inf, which the call refuses)
-                beta, name = float(np.float32(beta)), "cc_correct_chase_soft_batch"
+                beta = float(np.float32(beta))
         if b.shape[-1] != self.n:
             raise CcError(capi.ERR_LENGTH, "correct_batch")
-        if _is_torch(b):
-            import torch
-            if b.dtype != torch.float32:
-                raise TypeError("chase= takes float32 channel values")
-            return self._soft_call(name, [b.contiguous()], p, beta)
-        b = np.asarray(b)
-        if b.dtype.kind != "f":
+        side = _side(b)
+        y = side.as_type(b, "f", np.float32)
+        if y is None:
             raise TypeError("chase= takes float32 channel values")
-        return self._soft_call(name, [np.ascontiguousarray(b, np.float32)], p, beta)
+        B = side.size(y) // self.n
+        outs = {"out": ((B, self.n), np.uint8)}
+        if beta is None:
+            return self._batch_call("cc_correct_chase_batch", [y], B, outs, ("nerr", "metric", "status"), (p,))
+        outs["ext"] = ((B, self.n), np.float32)
+        return self._batch_call("cc_correct_chase_soft_batch", [y], B, outs, ("nerr", "metric", "status"), (p, beta))
 
     def _gmd(self, b, rel, m):
         """correct_batch(gmd=m, reliability=rel): uint8 symbols and float32 reliabilities, host arrays or device tensors."""
         m = capi.gmd_trials(m)
         if b.shape[-1] != self.n or tuple(rel.shape) != tuple(b.shape):
             raise CcError(capi.ERR_LENGTH, "correct_batch")
-        if _is_torch(b) != _is_torch(rel):
+        side = _side(b)
+        if side is not _side(rel):
             raise TypeError("gmd= takes the symbols and the reliabilities both on the host or both on the device")
-        if _is_torch(b):
-            import torch
-            if b.dtype != torch.uint8 or rel.dtype != torch.float32 or rel.device != b.device:
-                raise TypeError("gmd= takes uint8 symbols and float32 reliabilities on one device")
-            return self._soft_call("cc_correct_gmd_batch", [b.contiguous(), rel.contiguous()], m)
-        b, rel = np.asarray(b), np.asarray(rel)
-        if b.dtype.kind != "u" or rel.dtype.kind != "f":
-            raise TypeError("gmd= takes uint8 symbols and float32 reliabilities")
-        return self._soft_call("cc_correct_gmd_batch", [np.ascontiguousarray(b, np.uint8), np.ascontiguousarray(rel, np.float32)],
-                               m)
-
-    def _correct_batch_torch(self, b, erasures, want_L):
-        import torch
-        lib = capi.lib()
-        b = b.contiguous()
-        if b.shape[-1] != self.n:
-            raise CcError(capi.ERR_LENGTH, "correct_batch")
-        B = b.numel() // self.n
-        dev = b.device
-        er = off = None
-        if erasures is not None:
-            ev, eo = _erasure_csr(erasures, B, self.n)
-            if ev is not None:
-                if ev.size == 0:  # an empty tensor has a null data pointer: keep the list addressable
-                    ev = np.zeros(1, ev.dtype)
-                er = torch.from_numpy(ev.astype(np.int16)).to(dev)
-                off = torch.from_numpy(eo.astype(np.int32)).to(dev)
-        out = torch.empty((B, self.n), dtype=torch.uint8, device=dev)
-        status = torch.empty(B, dtype=torch.int32, device=dev)
-        st = _stream_handle(b)
-        if self.algorithm.soft:
-            if b.dtype != torch.float32:
-                raise TypeError("min-sum needs float32 LLRs")
-            L = torch.empty((B, self.n), dtype=torch.float32, device=dev) if want_L else None
-            iters = torch.empty(B, dtype=torch.int16, device=dev)
-            capi.check(lib.cc_correct_soft_batch_dev(self._h, _ptr(b), _ptr(er), _ptr(off), _ptr(out), _ptr(L),
-                                                     _ptr(iters), _ptr(status), B, st), "cc_correct_soft_batch_dev")
-            res = dict(out=out, status=status, iters=iters)
-            if want_L:
-                res["L"] = L
-            return res
-        nerr = torch.empty(B, dtype=torch.int32, device=dev)
-        if b.dtype == torch.float32:
-            capi.check(lib.cc_correct_hard_f32_batch_dev(self._h, _ptr(b), _ptr(er), _ptr(off), _ptr(out), _ptr(nerr),
-                                                         _ptr(status), B, st), "cc_correct_hard_f32_batch_dev")
-        elif b.dtype == torch.uint8:
-            capi.check(lib.cc_correct_hard_batch_dev(self._h, _ptr(b), _ptr(er), _ptr(off), _ptr(out), _ptr(nerr),
-                                                     _ptr(status), B, st), "cc_correct_hard_batch_dev")
-        else:
-            raise TypeError("hard decoding takes uint8 symbols or float32 soft values")
-        return dict(out=out, status=status, nerr=nerr)
+        w, r = side.as_type(b, "u", np.uint8), side.as_type(rel, "f", np.float32)
+        if w is None or r is None or (side is _device and r.device != w.device):
+            raise TypeError("gmd= takes uint8 symbols and float32 reliabilities"
+                            + (" on one device" if side is _device else ""))
+        B = side.size(w) // self.n
+        return self._batch_call("cc_correct_gmd_batch", [w, r], B, {"out": ((B, self.n), np.uint8)},
+                                ("nerr", "metric", "status"), (m,))
 
     def decode_batch(self, b, erasures=None, packed=False, interleave=None, chase=None, gmd=None, reliability=None,
                      soft=None):
@@ -1025,72 +914,29 @@ class cyclic:
                                      reliability=reliability, soft=soft)
             res["msg"] = self.extract_batch(res["out"])
             return res
-        if interleave is not None:
-            if packed:
-                raise TypeError("interleave= does not combine with packed=True")
-            I = int(interleave)
-            if _is_torch(b) or self.wide:
-                res = self._interleaved(2, b, I, erasures)
-                res["msg"] = self._interleaved(1, res["out"], I)
-                return res
-            if not isinstance(b, np.ndarray) or b.dtype.kind in "fi":
-                raise TypeError("interleave= takes unsigned symbols")
-            if b.ndim != 3 or b.shape[1] != self.n or b.shape[2] != I:
+        if interleave is not None and packed:
+            raise TypeError("interleave= does not combine with packed=True")
+        fused = _side(b) is _host  # the fused calls take host arrays; 16-bit blocks have none
+        if fused and (interleave is not None or packed):
+            if not self.wide or packed:
+                name, x, B, tail, shape = self._symbols("decode_hard", b, 0, packed, interleave)
+                return self._batch_call(name, [x], B, {"msg": (shape(1), None), "out": (shape(0), None)},
+                                        ("nerr", "status"), tail=tail, erasures=erasures)
+        elif fused:
+            b = np.asarray(b)
+            if b.shape[-1] != self.n:
                 raise CcError(capi.ERR_LENGTH, "decode_batch")
-            b = np.ascontiguousarray(b, np.uint8)
-            B = b.shape[0] * I
-            er, off = _erasure_csr(erasures, B, self.n)
-            msg, out = np.zeros((b.shape[0], self.l, I), np.uint8), np.zeros(b.shape, np.uint8)
-            nerr, status = np.zeros(B, np.int32), np.zeros(B, np.int32)
-            capi.check(capi.lib().cc_decode_hard_interleaved_batch(self._h, _ptr(b), _ptr(er), _ptr(off), _ptr(msg), _ptr(out),
-                                                                   _ptr(nerr), _ptr(status), B, I),
-                       "cc_decode_hard_interleaved_batch")
-            return dict(out=out, msg=msg, status=status, nerr=nerr)
-        if packed:
-            if _is_torch(b):
-                res = self._packed_correct(b, erasures)
-                res["msg"] = self.extract_batch(res["out"], packed=True)
-                return res
-            P, Pm = self._packed_width(0), self._packed_width(1)
-            b = np.ascontiguousarray(b, np.uint8)
-            if b.shape[-1] != P:
-                raise CcError(capi.ERR_LENGTH, "decode_batch")
-            b = b.reshape(-1, P)
-            B = b.shape[0]
-            er, off = _erasure_csr(erasures, B, self.n)
-            msg, out = np.zeros((B, Pm), np.uint8), np.zeros((B, P), np.uint8)
-            nerr, status = np.zeros(B, np.int32), np.zeros(B, np.int32)
-            capi.check(capi.lib().cc_decode_hard_packed_batch(self._h, _ptr(b), _ptr(er), _ptr(off), _ptr(msg), _ptr(out),
-                                                              _ptr(nerr), _ptr(status), B), "cc_decode_hard_packed_batch")
-            return dict(out=out, msg=msg, status=status, nerr=nerr)
-        if _is_torch(b):
-            res = self.correct_batch(b, erasures)
-            res["msg"] = self.extract_batch(res["out"])
-            return res
-        lib = capi.lib()
-        b = np.asarray(b)
-        if b.shape[-1] != self.n:
-            raise CcError(capi.ERR_LENGTH, "decode_batch")
-        B = b.size // self.n
-        er, off = _erasure_csr(erasures, B, self.n)
-        msg = np.zeros((B, self.l), np.uint8)
-        out = np.zeros((B, self.n), np.uint8)
-        status = np.zeros(B, np.int32)
-        if b.dtype.kind in "fi":
-            y = np.ascontiguousarray(b, np.float32).reshape(B, self.n)
-            aux = np.zeros(B, np.uint16 if self.algorithm.soft else np.int32)
-            if self.algorithm.soft:
-                capi.check(lib.cc_decode_soft_batch(self._h, _ptr(y), _ptr(er), _ptr(off), _ptr(msg), _ptr(out),
-                                                    _ptr(aux), _ptr(status), B), "cc_decode_soft_batch")
-                return dict(out=out, msg=msg, status=status, iters=aux)
-            res = self.correct_batch(y, erasures)  # a hard algorithm on channel values: bit = (x < 0), cyclic.h:163-173
-            res["msg"] = self.extract_batch(res["out"])
-            return res
-        sym = np.ascontiguousarray(b, np.uint8).reshape(B, self.n)
-        nerr = np.zeros(B, np.int32)
-        capi.check(lib.cc_decode_hard_batch(self._h, _ptr(sym), _ptr(er), _ptr(off), _ptr(msg), _ptr(out), _ptr(nerr),
-                                            _ptr(status), B), "cc_decode_hard_batch")
-        return dict(out=out, msg=msg, status=status, nerr=nerr)
+            signed = b.dtype.kind in "fi"
+            if self.algorithm.soft or not signed:
+                x = np.ascontiguousarray(b, np.float32 if signed else np.uint8)
+                B = x.size // self.n
+                return self._batch_call("cc_decode_soft_batch" if signed else "cc_decode_hard_batch", [x], B,
+                                        {"msg": ((B, self.l), np.uint8), "out": ((B, self.n), np.uint8)},
+                                        ("iters" if signed else "nerr", "status"), erasures=erasures)
+            # (a hard algorithm on channel values: bit = (x < 0), cyclic.h:163-173)
+        res = self.correct_batch(b, erasures, packed=packed, interleave=interleave)
+        res["msg"] = self.extract_batch(res["out"], packed, interleave)
+        return res
 
     # ---- single-frame API with the reference's exception behaviour ----
     _MESSAGES = {
