@@ -99,6 +99,9 @@ _SIGNATURES = {
     "cc_correct_chase_soft_batch": (C.c_int, [_VP, _VP, C.c_uint32, C.c_float, _VP, _VP, _VP, _VP, _VP, C.c_size_t]),
     "cc_correct_chase_soft_batch_dev": (C.c_int, [_VP, _VP, C.c_uint32, C.c_float, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "cc_chase_frames_per_wavefront": (C.c_int, [_VP, C.c_uint32, C.c_int]),
+    "cc_correct_chase_extended_batch": (C.c_int, [_VP, _VP, C.c_uint32, C.c_float, _VP, _VP, _VP, _VP, _VP, C.c_size_t]),
+    "cc_correct_chase_extended_batch_dev": (C.c_int, [_VP, _VP, C.c_uint32, C.c_float, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "cc_chase_extended_frames_per_wavefront": (C.c_int, [_VP, C.c_uint32, C.c_int]),
     "cc_correct_gmd_batch": (C.c_int, [_VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, C.c_size_t]),
     "cc_correct_gmd_batch_dev": (C.c_int, [_VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "cc_extract_batch": (C.c_int, [_VP, _VP, _VP, C.c_size_t]),

@@ -320,7 +320,61 @@ def symbol_reliability(y, q):
     return w, np.ascontiguousarray(keys.min(axis=2)).view(np.float32)
 
 
-def product_decode(rows, cols, y, p, alpha, beta):
+def extend(words):
+    """(..., n) words of 0/1 symbols -> (..., n + 1): the overall parity bit w_0 ^ .. ^ w_(n-1) appended, which makes a
+    codeword of a binary BCH code one of its extended code (correct_batch(chase=p, extended=True)).  numpy array or torch
+    tensor, any integer type; the result has the type of the input."""
+    if _is_torch(words):
+        import torch
+        parity = (words.to(torch.int64).sum(dim=-1, keepdim=True) & 1).to(words.dtype)
+        return torch.cat([words, parity], dim=-1)
+    words = np.asarray(words)
+    parity = (words.astype(np.int64).sum(axis=-1, keepdims=True) & 1).astype(words.dtype)
+    return np.concatenate([words, parity], axis=-1)
+
+
+def unextend(words):
+    """(..., n + 1) extended words -> (..., n): the parity column dropped (a contiguous copy)."""
+    if words.shape[-1] < 1:
+        raise CcError(capi.ERR_LENGTH, "unextend")
+    inner = words[..., :-1]
+    return inner.contiguous() if _is_torch(words) else np.ascontiguousarray(inner)
+
+
+def _product_decode_extended(rows, cols, y, p, alpha, beta):
+    """product_decode(extended=True): the same loop over the extended codes of `rows` and `cols`"""
+    if len(alpha) != len(beta) or not alpha:
+        raise ValueError("product_decode takes one alpha and one beta per half-iteration, at least one")
+    if len(y.shape) != 3 or y.shape[1] != cols.n + 1 or y.shape[2] != rows.n + 1:
+        raise CcError(capi.ERR_LENGTH, "product_decode")
+    torch_in = _is_torch(y)
+    if torch_in:
+        import torch
+        if y.dtype != torch.float32:
+            raise TypeError("product_decode takes float32 channel values")
+        y = y.contiguous()
+        W = torch.zeros_like(y)
+        turn = lambda a: a.transpose(1, 2).contiguous()
+    else:
+        y = np.asarray(y)
+        if y.dtype.kind != "f":
+            raise TypeError("product_decode takes float32 channel values")
+        y = np.ascontiguousarray(y, np.float32)
+        W = np.zeros_like(y)
+        turn = lambda a: np.ascontiguousarray(a.transpose(0, 2, 1))
+    B, n2, n1 = y.shape
+    for h, (a, b) in enumerate(zip(alpha, beta)):
+        X = y + (W * a if torch_in else W * np.float32(a))
+        code, lines, length = (rows, n2, n1) if h % 2 == 0 else (cols, n1, n2)
+        res = code.correct_batch((X if h % 2 == 0 else turn(X)).reshape(B * lines, length), chase=p, soft=b, extended=True)
+        out, W = res["out"].reshape(B, lines, length), res["ext"].reshape(B, lines, length)
+        if h % 2:
+            out, W = turn(out), turn(W)
+        status = res["status"].reshape(B, lines)
+    return dict(out=out, ext=W, status=status)
+
+
+def product_decode(rows, cols, y, p, alpha, beta, extended=False):
     """Iterative (turbo) decoding of a product code with the Chase-Pyndiah component decoder,
     correct_batch(chase=p, soft=beta).  y: (B, n2, n1) float32 channel values, numpy array or device tensor, positive
     meaning bit 0; every row y[b, i, :] is a received word of `rows` (n1 = rows.n), every column y[b, :, k] one of `cols`
@@ -331,8 +385,13 @@ def product_decode(rows, cols, y, p, alpha, beta):
     and (B, n1) after a column pass, one entry per component word.
     W is not normalised and there is no default schedule: good values depend on the scaling of y.  For y = +-1 + noise
     R. Pyndiah (IEEE Trans. Commun. 46 (8), 1998) gives for eight half-iterations alpha = 0, 0.2, 0.3, 0.5, 0.7, 0.9, 1,
-    1 and beta = 0.2, 0.4, 0.6, 0.8, 1, 1, 1, 1 -- with W normalised to mean magnitude one, so a starting point only."""
+    1 and beta = 0.2, 0.4, 0.6, 0.8, 1, 1, 1, 1 -- with W normalised to mean magnitude one, so a starting point only.
+    extended=True: the product of the two extended codes (see extend), y of shape (B, cols.n + 1, rows.n + 1); every row
+    and column goes through correct_batch(chase=p, soft=beta, extended=True), and out, ext and status are those of the
+    extended words."""
     alpha, beta = [float(np.float32(a)) for a in alpha], [float(np.float32(b)) for b in beta]
+    if extended:
+        return _product_decode_extended(rows, cols, y, p, alpha, beta)
     if len(alpha) != len(beta) or not alpha:
         raise ValueError("product_decode takes one alpha and one beta per half-iteration, at least one")
     if len(y.shape) != 3 or y.shape[1] != cols.n or y.shape[2] != rows.n:
@@ -806,7 +865,7 @@ class cyclic:
         return self._map("extract", cw, 0, packed, interleave)
 
     def correct_batch(self, b, erasures=None, want_L=False, packed=False, out=None, interleave=None, chase=None, gmd=None,
-                      reliability=None, soft=None):
+                      reliability=None, soft=None, extended=False):
         """Returns a dict: out (B,n) u8, status (B,) i32, and nerr (hard) or iters [+ L] (soft).
         gmd=m, reliability=r (RS, hard algorithms, q <= 8, 2t <= 32, step = 1): b holds the received symbols, r float32
         reliabilities of the same shape, and the frames are decoded by GMD with m trials (cc_correct_gmd_batch; gmd=True:
@@ -818,6 +877,9 @@ class cyclic:
         chase=p, soft=beta (beta a finite float >= 0): the same with the Chase-Pyndiah soft output
         (cc_correct_chase_soft_batch); the dict also carries ext (B,n) f32, the extrinsic value of every bit, beta in
         magnitude where no candidate disagrees with the decision.  soft= needs chase= and combines with nothing else.
+        chase=p, extended=True[, soft=beta]: the extended code, every word with its overall parity bit appended (see
+        extend): b, out and ext have rows of n + 1, position n carrying the parity bit, which enters the metric and
+        the soft output (cc_correct_chase_extended_batch).  extended= needs chase=.
         packed=True (binary BCH codes, hard algorithms): b and out are uint8 (B, packed_bytes), see pack_bits; out= names
         the buffer the corrected packed words go to (b itself decodes in place).  The long codes (q = 9 .. 15, BM / PGZ,
         t <= 31, no erasures) are decoded from the packed words themselves in calls of device tensors of at least
@@ -826,6 +888,8 @@ class cyclic:
         status, nerr and the erasure lists are per frame f = b I + j, as without it; out= as with packed=True."""
         if soft is not None and (chase is None or gmd is not None or reliability is not None):
             raise TypeError("soft= goes with chase= and with nothing else")
+        if extended and (chase is None or gmd is not None or reliability is not None):
+            raise TypeError("extended= goes with chase=[, soft=] and with nothing else")
         if gmd is not None or reliability is not None:
             if (erasures is not None or want_L or packed or out is not None or interleave is not None
                     or chase is not None):
@@ -836,7 +900,7 @@ class cyclic:
         if chase is not None:
             if erasures is not None or want_L or packed or out is not None or interleave is not None:
                 raise TypeError("chase= does not combine with erasures, want_L, packed=True, out= or interleave=")
-            return self._chase(b, chase, soft)
+            return self._chase(b, chase, soft, bool(extended))
         if interleave is not None and packed:
             raise TypeError("interleave= does not combine with packed=True")
         if interleave is None and not packed and out is not None:
@@ -863,8 +927,8 @@ class cyclic:
         return self._batch_call("cc_correct_%s_batch" % kind, [x], B, outs, ("iters" if soft_alg else "nerr", "status"),
                                 erasures=erasures)
 
-    def _chase(self, b, p, beta=None):
-        """correct_batch(chase=p[, soft=beta]): float32 channel values, host array or device tensor."""
+    def _chase(self, b, p, beta=None, extended=False):
+        """correct_batch(chase=p[, soft=beta][, extended=True]): float32 channel values, host array or device tensor."""
         p = int(p)
         if p < 0:
             raise ValueError("chase= takes p >= 0")
@@ -873,14 +937,19 @@ class cyclic:
                 raise TypeError("soft= takes beta, a float")
             with np.errstate(over="ignore"):  # (beyond float32: +inf, which the call refuses)
                 beta = float(np.float32(beta))
-        if b.shape[-1] != self.n:
+        w = self.n + 1 if extended else self.n
+        if b.shape[-1] != w:
             raise CcError(capi.ERR_LENGTH, "correct_batch")
         side = _side(b)
         y = side.as_type(b, "f", np.float32)
         if y is None:
             raise TypeError("chase= takes float32 channel values")
-        B = side.size(y) // self.n
-        outs = {"out": ((B, self.n), np.uint8)}
+        B = side.size(y) // w
+        outs = {"out": ((B, w), np.uint8)}
+        if extended:  # one call for both outputs: a null ext selects the hard output, and beta is then not read
+            outs["ext"] = ((B, w), np.float32) if beta is not None else None
+            return self._batch_call("cc_correct_chase_extended_batch", [y], B, outs, ("nerr", "metric", "status"),
+                                    (p, 0.0 if beta is None else beta))
         if beta is None:
             return self._batch_call("cc_correct_chase_batch", [y], B, outs, ("nerr", "metric", "status"), (p,))
         outs["ext"] = ((B, self.n), np.float32)
@@ -903,16 +972,17 @@ class cyclic:
                                 ("nerr", "metric", "status"), (m,))
 
     def decode_batch(self, b, erasures=None, packed=False, interleave=None, chase=None, gmd=None, reliability=None,
-                     soft=None):
+                     soft=None, extended=False):
         """decode = correct + message extraction (cyclic.h:313-327); host arrays go through cc_decode_*_batch.
         chase=p[, soft=beta]: correct_batch(b, chase=p[, soft=beta]), then the messages of its words.
+        chase=p, extended=True[, soft=beta]: the same on extended words; msg comes from their inner n columns.
         gmd=m, reliability=r: correct_batch(b, gmd=m, reliability=r), then the messages of its words.
         packed=True: b, out and msg are packed uint8 words, see pack_bits.
         interleave=I: b and out are blocks of shape (B / I, n, I), msg (B / I, l, I), see interleave()."""
-        if chase is not None or gmd is not None or reliability is not None or soft is not None:
+        if chase is not None or gmd is not None or reliability is not None or soft is not None or extended:
             res = self.correct_batch(b, erasures, packed=packed, interleave=interleave, chase=chase, gmd=gmd,
-                                     reliability=reliability, soft=soft)
-            res["msg"] = self.extract_batch(res["out"])
+                                     reliability=reliability, soft=soft, extended=extended)
+            res["msg"] = self.extract_batch(unextend(res["out"]) if extended else res["out"])
             return res
         if interleave is not None and packed:
             raise TypeError("interleave= does not combine with packed=True")

@@ -855,6 +855,56 @@ int cc_chase_frames_per_wavefront(const cc_code *code, uint32_t p, int soft) {
   return rc == CC_OK || rc == CC_ERR_NO_DEVICE ? chase_frames_per_wave(code, p, soft != 0) : 0;
 }
 
+// What the extended calls refuse, in the order the header states: what the Chase calls refuse short of the device, with
+// ext (soft output) beta and the overlap of the B (n + 1) floats of ext and llr, then the device.
+static int chase_extended_supported(const cc_code *code, uint32_t p, float beta, const float *llr, const float *ext, size_t B) {
+  const int rc = chase_supported(code, p);
+  if (rc != CC_OK && rc != CC_ERR_NO_DEVICE) return rc;
+  if (ext) {
+    if (!(beta >= 0.0f) || std::isinf(beta)) return CC_ERR_INVALID_ARGUMENT;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(llr), b = reinterpret_cast<uintptr_t>(ext);
+    const size_t bytes = B * (code->tab.n + 1) * sizeof(float);
+    if (bytes && a < b + bytes && b < a + bytes) return CC_ERR_INVALID_ARGUMENT;
+  }
+  return rc;
+}
+
+int cc_correct_chase_extended_batch_dev(const cc_code *code, const float *d_llr, uint32_t p, float beta, uint8_t *d_out,
+                                        float *d_ext, int32_t *d_nerr, float *d_metric, int32_t *d_status, size_t B,
+                                        void *stream) {
+  if (!code || (B && (!d_llr || !d_out))) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = chase_extended_supported(code, p, beta, d_llr, d_ext, B)) return rc;
+  DeviceGuard guard(code->device);
+  return launch_chase_extended(code, d_llr, p, beta, d_out, d_ext, d_nerr, d_metric, d_status, B,
+                               static_cast<hipStream_t>(stream));
+}
+
+int cc_correct_chase_extended_batch(const cc_code *code, const float *llr, uint32_t p, float beta, uint8_t *out, float *ext,
+                                    int32_t *nerr, float *metric, int32_t *status, size_t B) {
+  if (!code || (B && (!llr || !out))) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = chase_extended_supported(code, p, beta, llr, ext, B)) return rc;
+  if (B == 0) return CC_OK;
+  const size_t w = code->tab.n + 1;
+  DeviceGuard guard(code->device);
+  // (ext == NULL leaves the last stream out: no buffer, and the launcher's nullptr selects the hard-output kernel)
+  const StagedStream streams[] = {stage_in(0, llr, w * sizeof(float)),   stage_out(1, out, w),
+                                  stage_out(2, nerr, sizeof(int32_t)),   stage_out(3, status, sizeof(int32_t)),
+                                  stage_out(4, metric, sizeof(float)),   stage_out(7, ext, w * sizeof(float))};
+  return staged_call(code, B, w * sizeof(float), 1, streams, ext ? 6 : 5, nullptr, nullptr,
+                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t s) {
+                       return launch_chase_extended(code, static_cast<const float *>(d[0]), p, beta,
+                                                    static_cast<uint8_t *>(d[1]), static_cast<float *>(d[5]),
+                                                    static_cast<int32_t *>(d[2]), static_cast<float *>(d[4]),
+                                                    static_cast<int32_t *>(d[3]), m, s);
+                     });
+}
+
+int cc_chase_extended_frames_per_wavefront(const cc_code *code, uint32_t p, int soft) {
+  if (!code) return 0;
+  const int rc = chase_supported(code, p);
+  return rc == CC_OK || rc == CC_ERR_NO_DEVICE ? chase_frames_per_wave(code, p, soft != 0, true) : 0;
+}
+
 // What the GMD calls refuse, in the order the header states, all of it before a device is asked for.
 static int gmd_supported(const cc_code *code, uint32_t trials) {
   if (int rc = soft_decoder_supported(code, "GMD", CC_FAMILY_RS)) return rc;

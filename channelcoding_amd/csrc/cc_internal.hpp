@@ -204,12 +204,17 @@ int launch_algebraic_chunk(const cc_code *code, bool float_in, const void *d_in,
 // d_nerr, d_metric and d_status may be nullptr
 int launch_chase(const cc_code *code, const float *d_llr, unsigned p, uint8_t *d_out, int32_t *d_nerr, float *d_metric,
                  int32_t *d_status, size_t B, hipStream_t stream);
-// frames per wavefront of launch_chase (soft: of launch_chase_soft) at p: 64 >> p, fewer where LDS bounds it
-int chase_frames_per_wave(const cc_code *code, unsigned p, bool soft);
+// frames per wavefront of launch_chase (soft: of launch_chase_soft; extended: of launch_chase_extended, with d_ext for
+// soft) at p: 64 >> p, fewer where LDS bounds it
+int chase_frames_per_wave(const cc_code *code, unsigned p, bool soft, bool extended = false);
 // the same with the Chase-Pyndiah soft output d_ext (B n floats) and the value beta of a position without a competitor
 // (DESIGN 4.13); d_nerr, d_metric and d_status may be nullptr
 int launch_chase_soft(const cc_code *code, const float *d_llr, unsigned p, float beta, uint8_t *d_out, float *d_ext,
                       int32_t *d_nerr, float *d_metric, int32_t *d_status, size_t B, hipStream_t stream);
+// the extended code of the handle: rows of n + 1 values in d_llr, d_out and d_ext, position n carrying the
+// overall parity bit; d_ext == nullptr runs the hard-output kernel and beta is not read
+int launch_chase_extended(const cc_code *code, const float *d_llr, unsigned p, float beta, uint8_t *d_out, float *d_ext,
+                          int32_t *d_nerr, float *d_metric, int32_t *d_status, size_t B, hipStream_t stream);
 // gmd.hip: GMD over received symbols and reliabilities, RS with q <= 8, 2t <= 32, step = 1, 1 <= m <= t + 1 trials
 // (DESIGN 4.12); d_nerr, d_metric and d_status may be nullptr, d_out may be d_words
 int launch_gmd(const cc_code *code, const uint8_t *d_words, const float *d_rel, unsigned m, uint8_t *d_out, int32_t *d_nerr,

@@ -20,6 +20,12 @@
 //      stage A; the candidates of a frame that equal the winner have an empty difference), and a second store loop
 //      writes ext as stage C writes out
 //
+// Extended codes (cc_correct_chase_extended_batch; Ext = true): a frame is the w = n + 1 values of an inner
+// word and its overall parity bit at position n.  Position n goes to Y like any other and takes part in the two store
+// loops and in stage D, but in neither the syndromes nor the keys; stage A leaves the parity of z[0..n) in the frame's
+// spare LP byte, and after the root loop a lane sets bit n of fm and adds |y_n| -- the last addition -- where the parity
+// of its inner candidate differs from z_n.  At n = 255 position n is bit 63 of the fourth mask word: the last there is.
+//
 // A candidate exists iff the LFSR length equals deg lambda <= t and lambda has deg roots below n (for L = deg the
 // re-check of cyclic.h:243-248 cannot fail -- proof in algebraic.hip; conversely a codeword within t of the pattern
 // makes the recurrence return its locator, so L != deg or a root at a position >= n of a shortened code means none).
@@ -31,12 +37,12 @@ namespace {
 struct ChaseLayout : BmColumns {  // byte offsets inside one wavefront's LDS region (SL: of the lane's test pattern)
   int Y, SZ, LP, WM, bytes;
 };
-__host__ __device__ constexpr ChaseLayout chase_layout(int t2, int n, int F) {
+__host__ __device__ constexpr ChaseLayout chase_layout(int t2, int n, int F) {  // n: values per row
   const BmColumns bm = bm_columns(t2);
   const int Y = bm.end;                    // f32 [F][n]   received values
   const int WM = (Y + 4 * F * n + 7) & ~7;  // u64 [F][4]   flip mask of the frame's winner (zero: none)
   const int SZ = WM + 32 * F;              // u8  [F][t2]  S_m of z
-  const int LP = SZ + F * t2;              // u8  [F][8]   L_0 .. L_(p-1)
+  const int LP = SZ + F * t2;              // u8  [F][8]   L_0 .. L_(p-1), p <= 6; [7]: parity of z[0..n) (extended)
   return ChaseLayout{bm, Y, SZ, LP, WM, (LP + 8 * F + 15) & ~15};
 }
 
@@ -77,7 +83,8 @@ struct SoftOut {
 
 // TR > 0: t <= TR, lambda_0 .. lambda_TR live in registers during the root search; TR = 0: read from the LDS column.
 // Soft = {} is the hard-output kernel; Soft = {SoftOut} adds stage D and the output ext, with the soft layout.
-template <int TR, class... Soft>
+// Ext: rows of w = n + 1 values, the last one the overall parity bit of an extended code.
+template <int TR, bool Ext, class... Soft>
 __global__ void __launch_bounds__(256)
 chase_kernel(const AlgebraicTables *__restrict__ T, const float *__restrict__ llr, int p, int F, uint8_t *__restrict__ out,
              int32_t *__restrict__ nerr_out, float *__restrict__ metric_out, int32_t *__restrict__ status_out,
@@ -89,8 +96,9 @@ chase_kernel(const AlgebraicTables *__restrict__ T, const float *__restrict__ ll
 
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int n = T->n, nn = T->nf, t2 = T->nroots, t = t2 / 2, nc = t2 + 1;
-  const ChaseLayout lay = chase_layout(t2, n, F);
-  const ChaseSoftLayout soft = SOFT ? chase_soft_layout(t2, n, F) : ChaseSoftLayout{};  // the same offsets, K and MD behind
+  const int w = Ext ? n + 1 : n;  // values per row
+  const ChaseLayout lay = chase_layout(t2, w, F);
+  const ChaseSoftLayout soft = SOFT ? chase_soft_layout(t2, w, F) : ChaseSoftLayout{};  // the same offsets, K and MD behind
   uint8_t *base = smem + kSoftTables + wid * (SOFT ? soft.bytes : lay.bytes);
   uint16_t *SL = reinterpret_cast<uint16_t *>(base + lay.SL);
   uint16_t *LL = reinterpret_cast<uint16_t *>(base + lay.LL);
@@ -106,6 +114,13 @@ chase_kernel(const AlgebraicTables *__restrict__ T, const float *__restrict__ ll
   bool valid[4];
   uint32_t e1[4], d2[4];
   lane_positions(lane, n, nn, 1u, 2u, valid, e1, d2);
+  // position lane + 64 c of the row: those of the inner word and, extended, position n
+  const auto held = [&](int c) {
+    if constexpr (Ext)
+      return lane + 64 * c < w;
+    else
+      return valid[c];
+  };
 
   const GroupSteps gs = group_steps(B, F, wid);
   for (unsigned long long group = gs.start; group < gs.count; group += gs.step) {
@@ -114,17 +129,23 @@ chase_kernel(const AlgebraicTables *__restrict__ T, const float *__restrict__ ll
 
     // ---------------- A: y to LDS, syndromes of z, least reliable positions ----------------
     for (int s = 0; s < frames; ++s) {
-      const float *src = llr + (first + s) * n;
+      const float *src = llr + (first + s) * w;
       uint32_t key[4], zb[4], ev[4];
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const float v = valid[c] ? src[lane + 64 * c] : 0.0f;
-        if (valid[c]) Y[s * n + lane + 64 * c] = v;
+        const float v = held(c) ? src[lane + 64 * c] : 0.0f;
+        if (held(c)) Y[s * w + lane + 64 * c] = v;
         if constexpr (SOFT)
-          if (valid[c]) K[s * n + lane + 64 * c] = kNoMetric;
+          if (held(c)) K[s * w + lane + 64 * c] = kNoMetric;
         zb[c] = (valid[c] && v < 0.0f) ? 1u : 0u;                // cyclic.h:163-173
         key[c] = reliability_key(valid[c], v);
         ev[c] = e1[c];
+      }
+      if constexpr (Ext) {  // parity of z[0..n): one ballot per position register
+        int ones = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) ones += __builtin_popcountll(__ballot(zb[c] != 0));
+        if (lane == 0) LP[s * 8 + 7] = static_cast<uint8_t>(ones & 1);
       }
       for (int m0 = 0; m0 < t; m0 += 4) {  // S_1, S_3, ..: four per reduction
         const uint32_t packed = four_syndromes(ev, d2, nn, [&](int c, uint32_t e) { return zb[c] ? ex[e] : 0u; });
@@ -166,7 +187,7 @@ chase_kernel(const AlgebraicTables *__restrict__ T, const float *__restrict__ ll
       for (int m = 0; m <= TR; ++m) lam[m] = m < nc ? static_cast<uint32_t>(LL[m * 64 + lane]) : kLogZero;
     }
     const int degw = TR > 0 ? 0 : static_cast<int>(wave_umax(static_cast<uint32_t>(deg)));
-    const float *yrow = Y + sl * n;
+    const float *yrow = Y + sl * w;
     unsigned long long fm[4] = {0, 0, 0, 0};  // positions where the candidate differs from z
     float M = 0.0f;
     int nroots = 0;
@@ -199,6 +220,17 @@ chase_kernel(const AlgebraicTables *__restrict__ T, const float *__restrict__ ll
       }
       fm[c] = flips;
     }
+    if constexpr (Ext) {  // the candidate's parity bit against z_n
+      int inner = 0;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) inner += __builtin_popcountll(fm[c]);
+      const float yn = yrow[n];
+      const bool flip = ((static_cast<uint32_t>(LP[sl * 8 + 7]) ^ static_cast<uint32_t>(inner)) & 1u) != (yn < 0.0f ? 1u : 0u);
+      M = flip ? M + __builtin_fabsf(yn) : M;
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (flip && (n >> 6) == c) fm[c] |= 1ull << (n & 63);
+    }
 
     // ---------------- C: the closest candidate of each frame, ties to the smallest j ----------------
     const bool have = mine && len == deg && deg <= t && nroots == deg;
@@ -224,20 +256,20 @@ chase_kernel(const AlgebraicTables *__restrict__ T, const float *__restrict__ ll
       // ---------------- D: K_i = the smallest metric among the candidates that differ from the winner at i ----------------
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        unsigned long long d = have ? fm[c] ^ WM[sl * 4 + c] : 0ull;  // set bits lie below n: fm and WM stop there
+        unsigned long long d = have ? fm[c] ^ WM[sl * 4 + c] : 0ull;  // set bits lie below w: fm and WM stop there
         while (d) {
-          atomicMin(&K[sl * n + 64 * c + __builtin_ctzll(d)], mkey);
+          atomicMin(&K[sl * w + 64 * c + __builtin_ctzll(d)], mkey);
           d &= d - 1ull;
         }
       }
       wave_sync();
     }
     for (int s = 0; s < frames; ++s) {
-      uint8_t *dst = out + (first + s) * n;
+      uint8_t *dst = out + (first + s) * w;
 #pragma unroll
       for (int c = 0; c < 4; ++c)
-        if (valid[c]) {
-          const uint32_t z = Y[s * n + lane + 64 * c] < 0.0f ? 1u : 0u;
+        if (held(c)) {
+          const uint32_t z = Y[s * w + lane + 64 * c] < 0.0f ? 1u : 0u;
           dst[lane + 64 * c] = static_cast<uint8_t>(z ^ static_cast<uint32_t>((WM[s * 4 + c] >> lane) & 1ull));
         }
     }
@@ -245,14 +277,14 @@ chase_kernel(const AlgebraicTables *__restrict__ T, const float *__restrict__ ll
       const SoftOut so = first_of(soft_out...);
       const float beta = so.beta;
       for (int s = 0; s < frames; ++s) {
-        float *dst = so.ext + (first + s) * n;
+        float *dst = so.ext + (first + s) * w;
         const uint32_t md = MD[s];
 #pragma unroll
         for (int c = 0; c < 4; ++c)
-          if (valid[c]) {
-            const float y = Y[s * n + lane + 64 * c];
+          if (held(c)) {
+            const float y = Y[s * w + lane + 64 * c];
             const bool one = (y < 0.0f) != (((WM[s * 4 + c] >> lane) & 1ull) != 0);  // the winner's bit
-            const uint32_t k = K[s * n + lane + 64 * c];
+            const uint32_t k = K[s * w + lane + 64 * c];
             const float sgn = one ? -1.0f : 1.0f;
             // two float32 subtractions, the products by +-1 are exact (the unit is built without contraction)
             const float e = k == kNoMetric ? sgn * beta : sgn * (u2f(k) - u2f(md)) - y;
@@ -266,38 +298,54 @@ chase_kernel(const AlgebraicTables *__restrict__ T, const float *__restrict__ ll
 
 }  // namespace
 
-int launch_chase(const cc_code *code, const float *d_llr, unsigned p, uint8_t *d_out, int32_t *d_nerr, float *d_metric,
-                 int32_t *d_status, size_t B, hipStream_t stream) {
+// rows of n values (ext: of n + 1), hard output (d_ext null: beta is not read) or soft output
+static int launch(const cc_code *code, bool ext, const float *d_llr, unsigned p, float beta, uint8_t *d_out, float *d_ext,
+                  int32_t *d_nerr, float *d_metric, int32_t *d_status, size_t B, hipStream_t stream) {
   if (B == 0) return CC_OK;
-  const int n = static_cast<int>(code->tab.n), t2 = code->h_alg.nroots;
-  // 64 >> p frames per wavefront, fewer where the received values of that many frames do not fit
-  const int F = chase_frames_per_wave(code, p, false);
-  const size_t lds = kSoftTables + 4 * static_cast<size_t>(chase_layout(t2, n, F).bytes);
-  return launch_groups(code, B, F, "chase kernel launch", [&](dim3 grid) {
-    hipLaunchKernelGGL(t2 <= 6 ? chase_kernel<3> : chase_kernel<0>, grid, dim3(256), lds, stream, code->d_alg, d_llr,
-                       static_cast<int>(p), F, d_out, d_nerr, d_metric, d_status, static_cast<unsigned long long>(B));
+  const int w = static_cast<int>(code->tab.n) + (ext ? 1 : 0), t2 = code->h_alg.nroots;
+  const bool regs = t2 <= 6;
+  // 64 >> p frames per wavefront, fewer where the received values of that many frames do not fit; K doubles what a
+  // frame holds: about half the frames of the hard output where its count was bounded by LDS
+  const int F = chase_frames_per_wave(code, p, d_ext != nullptr, ext);
+  const int bytes = d_ext ? chase_soft_layout(t2, w, F).bytes : chase_layout(t2, w, F).bytes;
+  const size_t lds = kSoftTables + 4 * static_cast<size_t>(bytes);
+  const unsigned long long frames = B;
+  if (!d_ext)
+    return launch_groups(code, B, F, ext ? "extended chase kernel launch" : "chase kernel launch", [&](dim3 grid) {
+      const auto kernel = ext ? (regs ? chase_kernel<3, true> : chase_kernel<0, true>)
+                              : (regs ? chase_kernel<3, false> : chase_kernel<0, false>);
+      hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, code->d_alg, d_llr, static_cast<int>(p), F, d_out, d_nerr,
+                         d_metric, d_status, frames);
+    });
+  return launch_groups(code, B, F, ext ? "extended chase soft-output kernel launch" : "chase soft-output kernel launch",
+                       [&](dim3 grid) {
+    const auto kernel = ext ? (regs ? chase_kernel<3, true, SoftOut> : chase_kernel<0, true, SoftOut>)
+                            : (regs ? chase_kernel<3, false, SoftOut> : chase_kernel<0, false, SoftOut>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, code->d_alg, d_llr, static_cast<int>(p), F, d_out, d_nerr,
+                       d_metric, d_status, frames, SoftOut{beta, d_ext});
   });
 }
 
-int chase_frames_per_wave(const cc_code *code, unsigned p, bool soft) {
-  // (2t = h_alg.nroots, which a handle without a device does not fill in)
-  const int n = static_cast<int>(code->tab.n), t2 = 2 * static_cast<int>(code->tab.t);
-  return soft ? frames_per_wave(64 >> p, [&](int f) { return chase_soft_layout(t2, n, f); })
-              : frames_per_wave(64 >> p, [&](int f) { return chase_layout(t2, n, f); });
+int launch_chase(const cc_code *code, const float *d_llr, unsigned p, uint8_t *d_out, int32_t *d_nerr, float *d_metric,
+                 int32_t *d_status, size_t B, hipStream_t stream) {
+  return launch(code, false, d_llr, p, 0.0f, d_out, nullptr, d_nerr, d_metric, d_status, B, stream);
 }
 
 int launch_chase_soft(const cc_code *code, const float *d_llr, unsigned p, float beta, uint8_t *d_out, float *d_ext,
                       int32_t *d_nerr, float *d_metric, int32_t *d_status, size_t B, hipStream_t stream) {
-  if (B == 0) return CC_OK;
-  const int n = static_cast<int>(code->tab.n), t2 = code->h_alg.nroots;
-  // K doubles what a frame holds: about half the frames of launch_chase where its count was bounded by LDS
-  const int F = chase_frames_per_wave(code, p, true);
-  const size_t lds = kSoftTables + 4 * static_cast<size_t>(chase_soft_layout(t2, n, F).bytes);
-  return launch_groups(code, B, F, "chase soft-output kernel launch", [&](dim3 grid) {
-    hipLaunchKernelGGL((t2 <= 6 ? chase_kernel<3, SoftOut> : chase_kernel<0, SoftOut>), grid, dim3(256), lds, stream,
-                       code->d_alg, d_llr, static_cast<int>(p), F, d_out, d_nerr, d_metric, d_status,
-                       static_cast<unsigned long long>(B), SoftOut{beta, d_ext});
-  });
+  return launch(code, false, d_llr, p, beta, d_out, d_ext, d_nerr, d_metric, d_status, B, stream);
+}
+
+int launch_chase_extended(const cc_code *code, const float *d_llr, unsigned p, float beta, uint8_t *d_out, float *d_ext,
+                          int32_t *d_nerr, float *d_metric, int32_t *d_status, size_t B, hipStream_t stream) {
+  return launch(code, true, d_llr, p, beta, d_out, d_ext, d_nerr, d_metric, d_status, B, stream);
+}
+
+int chase_frames_per_wave(const cc_code *code, unsigned p, bool soft, bool extended) {
+  // (2t = h_alg.nroots, which a handle without a device does not fill in)
+  const int w = static_cast<int>(code->tab.n) + (extended ? 1 : 0), t2 = 2 * static_cast<int>(code->tab.t);
+  return soft ? frames_per_wave(64 >> p, [&](int f) { return chase_soft_layout(t2, w, f); })
+              : frames_per_wave(64 >> p, [&](int f) { return chase_layout(t2, w, f); });
 }
 
 }  // namespace ccamd

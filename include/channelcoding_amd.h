@@ -269,8 +269,8 @@ int cc_correct_chase_batch_dev(const cc_code *code, const float *d_llr, uint32_t
  *      Refused before a device is asked for, in this order: what cc_correct_chase_batch refuses short of the device, in
  *      its order, with ext joining the NULL check; beta negative, infinite or NaN -> CC_ERR_INVALID_ARGUMENT; ext
  *      overlapping llr (any byte of the B*n floats) -> CC_ERR_INVALID_ARGUMENT; then a CC_DEVICE_NONE handle answers
- *      CC_ERR_NO_DEVICE.  B = 0 answers CC_OK.  No RS or GMD soft output, no extended (parity-augmented) codes, p and q
- *      as above. ---- */
+ *      CC_ERR_NO_DEVICE.  B = 0 answers CC_OK.  No RS or GMD soft output; p and q as above.  Extended (parity-augmented)
+ *      codes, which product codes usually use, have a call of their own: cc_correct_chase_extended_batch. ---- */
 int cc_correct_chase_soft_batch(const cc_code *code, const float *llr /* B*n */, uint32_t p, float beta,
                                 uint8_t *out /* B*n */, float *ext /* B*n */, int32_t *nerr, float *metric, int32_t *status,
                                 size_t B);
@@ -282,6 +282,44 @@ int cc_correct_chase_soft_batch_dev(const cc_code *code, const float *d_llr, uin
  * side by side at p: 64 >> p, fewer where the frames' values do not fit its share of LDS.  For tests and measurements
  * that place batch sizes next to it; 0 for a call the decoder refuses.  Needs no device. */
 int cc_chase_frames_per_wavefront(const cc_code *code, uint32_t p, int soft);
+
+/* ---- Chase-II and Chase-Pyndiah decoding of extended BCH codes: the handle's code with one overall parity bit, the
+ *      component code of the usual product codes, e.g. eBCH(64,51) from BCH(63,51).  The reference has no such decoder.
+ *      A handle is any handle that cc_correct_chase_batch accepts (binary BCH, hard tag, q <= 8, 2t <= 32, full length
+ *      or shortened); there is no cc_desc field and no cc_algorithm value for it: the handle is the inner code and the
+ *      entry point says "extended".  With n the handle's length, the extended code is
+ *        { (c, c_0 ^ .. ^ c_(n-1)) : c in the handle's code },
+ *      a frame is n + 1 finite floats y_0 .. y_n, position n carrying the parity bit, and p <= min(CC_CHASE_MAX_P, n).
+ *        hard decision  z_i = (y_i < 0) for i = 0 .. n, so -0.0 gives 0
+ *        reliability    keys and the tie rule of cc_correct_chase_batch, but L_0 .. L_(p-1) are picked among the inner
+ *                       positions 0 .. n-1 only (flipping position n never changes what the inner decoder returns)
+ *        test patterns  j in [0, 2^p): bit i of j flips position L_i
+ *        candidate      of pattern j: (c', parity(c')) with c' the handle's codeword within Hamming distance t of
+ *                       (z ^ e_j)[0..n), if there is one -- the bounded-distance rule of cc_correct_chase_batch, a
+ *                       locator root at a position >= n of a shortened code meaning none
+ *        metric         M(c) = float32 sum of |y_i| over the positions with c_i != z_i, from +0.0f in ascending i over
+ *                       0 .. n: the parity position is added last
+ *        winner         the candidate with the smallest M, equal M to the smallest j
+ *      Per frame: out = the winner (n + 1 bytes; z with all n + 1 bits when no pattern has a candidate), nerr = positions
+ *      among the n + 1 where out differs from z (-1), metric = M of the winner (+0.0f), status = CC_FRAME_OK
+ *      (CC_FRAME_LOCATOR).  nerr, metric and status may be NULL.
+ *      ext == NULL: hard output only, beta is not examined.  ext != NULL: B*(n+1) float32, the formulas of
+ *      cc_correct_chase_soft_batch over all n + 1 positions -- K_i, ext_i = s_i * (K_i - M_D) - y_i, s_i * beta without a
+ *      competitor, +0.0f everywhere in a frame without a candidate, unspecified for a winning metric that is not
+ *      finite.  At position n the competitors are the candidates whose parity bit differs from the winner's.
+ *      Refused before a device is asked for, in this order: what cc_correct_chase_batch refuses short of the device, in
+ *      its order; with ext != NULL, beta negative, infinite or NaN -> CC_ERR_INVALID_ARGUMENT and ext overlapping llr
+ *      (any byte of the B*(n+1) floats) -> CC_ERR_INVALID_ARGUMENT; then a CC_DEVICE_NONE handle answers
+ *      CC_ERR_NO_DEVICE.  B = 0 answers CC_OK.  p = 0 is the hard decoding of extended words; q, p and the containers
+ *      are those of cc_correct_chase_batch. ---- */
+int cc_correct_chase_extended_batch(const cc_code *code, const float *llr /* B*(n+1) */, uint32_t p, float beta,
+                                    uint8_t *out /* B*(n+1) */, float *ext /* B*(n+1) or NULL */, int32_t *nerr,
+                                    float *metric, int32_t *status, size_t B);
+int cc_correct_chase_extended_batch_dev(const cc_code *code, const float *d_llr, uint32_t p, float beta, uint8_t *d_out,
+                                        float *d_ext, int32_t *d_nerr, float *d_metric, int32_t *d_status, size_t B,
+                                        void *stream);
+/* cc_chase_frames_per_wavefront for the extended call, rows of n + 1 values: soft = 0 for ext == NULL. */
+int cc_chase_extended_frames_per_wavefront(const cc_code *code, uint32_t p, int soft);
 
 /* ---- GMD soft-decision correct for Reed-Solomon codes (Forney's generalized-minimum-distance decoding): the 0, 2, 4, ..
  *      least reliable symbols are erased, every trial is decoded with errors and erasures, and the candidate nearest to

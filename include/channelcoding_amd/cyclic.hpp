@@ -286,7 +286,7 @@ struct batch_result {
   std::vector<uint8_t> msg;     // decode_batch: B * l message symbols
   std::vector<float> metric;    // correct_chase_batch: sum of |y| over the positions the winner differs from sign(y) in;
                                 // correct_gmd_batch: sum of |rel| over the positions the winner differs from the input in
-  std::vector<float> ext;       // correct_chase_soft_batch: B * n extrinsic values (positive: bit 0)
+  std::vector<float> ext;       // correct_chase_soft_batch: B * n extrinsic values (positive: bit 0); B * (n + 1) extended
 };
 
 template <int Family, unsigned q, typename Capability, typename Algorithm, unsigned N, typename Coding, unsigned mu,
@@ -577,6 +577,38 @@ public:
     detail::check(cc_correct_chase_soft_batch(this->handle.get(), values, p, beta, r.words.data(), r.ext.data(),
                                               r.nerr.data(), r.metric.data(), r.status.data(), B),
                   "cc_correct_chase_soft_batch");
+    return r;
+  }
+
+  // ---- the extended code (new; cc_correct_chase_extended_batch): every word with its overall parity bit at position N,
+  // frames and words of N + 1.  ext == nullptr: the hard output alone (beta is not read); otherwise the soft output over
+  // all N + 1 positions.  Throws decoding_failure when no pattern has a candidate ----
+  std::vector<uint8_t> correct_chase_extended(const std::vector<float> &y, unsigned p, float beta = 0.0f,
+                                              std::vector<float> *ext = nullptr) const {
+    if (y.size() != N + 1) throw std::runtime_error("Length of received sequence does not match code length");
+    std::vector<uint8_t> out(N + 1);
+    if (ext) ext->assign(N + 1, 0.0f);
+    int32_t status = CC_FRAME_OK;
+    detail::check(cc_correct_chase_extended_batch(this->handle.get(), y.data(), p, beta, out.data(),
+                                                  ext ? ext->data() : nullptr, nullptr, nullptr, &status, 1),
+                  "cc_correct_chase_extended_batch");
+    if (status != CC_FRAME_OK) throw decoding_failure(detail::failure_text(status));
+    return out;
+  }
+  // B frames of N + 1 values, frame-contiguous: words, nerr, status and metric of every frame, and ext with soft = true
+  // (failed frames do not throw; their ext is +0)
+  batch_result correct_chase_extended_batch(const float *values, size_t B, unsigned p, bool soft = false,
+                                            float beta = 0.0f) const {
+    batch_result r;
+    r.words.resize(B * (N + 1));
+    if (soft) r.ext.resize(B * (N + 1));
+    r.status.resize(B);
+    r.nerr.resize(B);
+    r.metric.resize(B);
+    detail::check(cc_correct_chase_extended_batch(this->handle.get(), values, p, beta, r.words.data(),
+                                                  soft ? r.ext.data() : nullptr, r.nerr.data(), r.metric.data(),
+                                                  r.status.data(), B),
+                  "cc_correct_chase_extended_batch");
     return r;
   }
 };

@@ -20,7 +20,22 @@ decoder and to min-sum on the same values, and word error rates next to min-sum.
                                                     block errors of cc.product_decode (p = 4, Pyndiah's alpha and beta
                                                     of six half-iterations) after every half-iteration, against hard
                                                     decoding of rows then columns
-    --parent-lib PATH                               soft: libchannelcoding_amd.so built from the parent commit
+    python profiles/tools/chase_bench.py extended   the extended call (cc_correct_chase_extended_batch_dev)
+                                                    on the codes and p values of `rates` at 4 dB: legs ext-hard p (ext
+                                                    NULL) and ext-soft p on rows of n + 1 values -- the parity value of
+                                                    the transmitted word plus noise of the same sigma appended to every
+                                                    frame -- next to chase p and soft p of this build on the n inner
+                                                    values and, with --parent-lib, chase p and soft p of the parent
+                                                    commit's library loaded next to it; alternation and timing as in
+                                                    `soft`; then the ratios extended / plain with F of both, and the
+                                                    existing calls against the parent's spread
+    python profiles/tools/chase_bench.py product-ext  eBCH(64,51) x eBCH(64,51) against BCH(63,51) x BCH(63,51) at the
+                                                    same Eb/N0 (--ebno, default 3.0 dB; each code's own rate in the noise
+                                                    variance), 2^12 blocks from numpy seed 1, the same information bits:
+                                                    block errors of cc.product_decode (p = 4, the alpha and beta of
+                                                    `product`) after every half-iteration
+    --parent-lib PATH                               soft, extended: libchannelcoding_amd.so built from the parent commit
+    --ebno DB                                       product-ext: the noise point
     --frames-log2 K                                 another number of frames per leg / point
     --only p6                                       rates: only the p = 6 leg of BCH(255,231) at 4 dB, five calls (for a
                                                     rocprofv3 run of its own)
@@ -122,16 +137,18 @@ def frames_per_wave(code, p, soft):
     return capi.lib().cc_chase_frames_per_wavefront(code._h, p, int(soft))
 
 
-def parent_chase(path, code):
-    """cc_correct_chase_batch_dev of the library at `path`, on a handle that library creates from the code's descriptor"""
+def parent_chase(path, code, soft=False):
+    """cc_correct_chase_batch_dev (soft: cc_correct_chase_soft_batch_dev) of the library at `path`, on a handle that
+    library creates from the code's descriptor"""
     lib = C.CDLL(path)
     h = C.c_void_p()
     lib.cc_code_create.restype = C.c_int
     lib.cc_code_create.argtypes = [C.c_void_p, C.c_void_p]
     assert lib.cc_code_create(C.byref(code._desc), C.byref(h)) == 0
-    fn = lib.cc_correct_chase_batch_dev
+    fn = lib.cc_correct_chase_soft_batch_dev if soft else lib.cc_correct_chase_batch_dev
     fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + ([C.c_float] if soft else []) + [C.c_void_p] * (5 if soft else 4) \
+        + [C.c_size_t, C.c_void_p]
     return lib, h, fn
 
 
@@ -203,6 +220,138 @@ def soft(frames, parent_lib):
             del legs, bufs, ext, llr
 
 
+def spread(ts):
+    return "%.3f - %.3f" % (max(ts), min(ts))
+
+
+def against(mine, theirs):
+    inside = min(theirs) <= min(mine) <= max(theirs) or min(theirs) <= max(mine) <= max(theirs) or (
+        min(mine) <= min(theirs) and max(mine) >= max(theirs))
+    return "within its spread" if inside else ("FASTER than its fastest" if max(mine) < min(theirs) else "SLOWER than its slowest")
+
+
+def extended(frames, parent_lib):
+    import torch
+    import channelcoding_amd as cc
+    from channelcoding_amd import capi
+    lib = capi.lib()
+    ptr = lambda x: C.c_void_p(x.data_ptr())
+    ebno = 4.0
+    for q, t in RATE_CODES:
+        code = cc.primitive_bch(q, cc.errors(t), cc.berlekamp_massey_tag())
+        B, n = frames, code.n
+        llr = torch.empty((B, n), dtype=torch.float32, device="cuda")
+        sent = torch.empty((B, n), dtype=torch.uint8, device="cuda")
+        capi.check(lib.cc_awgn_llr_dev(code._h, ebno, 1, 0, B, 1, ptr(llr), ptr(sent), None), "cc_awgn_llr_dev")
+        gen = torch.Generator(device="cuda").manual_seed(1)
+        parity = (sent.sum(dim=1, dtype=torch.int32) & 1).to(torch.float32)
+        yn = (1.0 - 2.0 * parity) + lib.cc_sigma(code._h, ebno) * torch.randn(B, generator=gen, device="cuda")
+        wide = torch.cat([llr, yn[:, None]], dim=1).contiguous()
+        del sent, parity, yn
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        kinds = ["ext-hard", "chase", "ext-soft", "soft"] + (["parent-chase", "parent-soft"] if parent_lib else [])
+        bufs = {}
+        for leg in kinds:
+            w = n + 1 if leg.startswith("ext") else n
+            bufs[leg] = dict(out=torch.empty((B, w), dtype=torch.uint8, device="cuda"),
+                             nerr=torch.empty(B, dtype=torch.int32, device="cuda"),
+                             status=torch.empty(B, dtype=torch.int32, device="cuda"),
+                             metric=torch.empty(B, dtype=torch.float32, device="cuda"))
+            if leg.endswith("soft"):
+                bufs[leg]["ext"] = torch.empty((B, w), dtype=torch.float32, device="cuda")
+        parents = (parent_chase(parent_lib, code), parent_chase(parent_lib, code, True)) if parent_lib else None
+        four = lambda b: (ptr(b["nerr"]), ptr(b["metric"]), ptr(b["status"]), B, stream)
+        legs = {}
+        for p in PS:
+            b = bufs["ext-hard"]
+            legs["ext-hard p=%d" % p] = lambda p=p, b=b: capi.check(lib.cc_correct_chase_extended_batch_dev(
+                code._h, ptr(wide), p, 0.5, ptr(b["out"]), None, *four(b)), "ext-hard")
+            b = bufs["chase"]
+            legs["chase p=%d" % p] = lambda p=p, b=b: capi.check(lib.cc_correct_chase_batch_dev(
+                code._h, ptr(llr), p, ptr(b["out"]), *four(b)), "chase")
+            if parents:
+                b = bufs["parent-chase"]
+                legs["parent-chase p=%d" % p] = lambda p=p, b=b: capi.check(parents[0][2](
+                    parents[0][1], ptr(llr), p, ptr(b["out"]), *four(b)), "parent-chase")
+            b = bufs["ext-soft"]
+            legs["ext-soft p=%d" % p] = lambda p=p, b=b: capi.check(lib.cc_correct_chase_extended_batch_dev(
+                code._h, ptr(wide), p, 0.5, ptr(b["out"]), ptr(b["ext"]), *four(b)), "ext-soft")
+            b = bufs["soft"]
+            legs["soft p=%d" % p] = lambda p=p, b=b: capi.check(lib.cc_correct_chase_soft_batch_dev(
+                code._h, ptr(llr), p, 0.5, ptr(b["out"]), ptr(b["ext"]), *four(b)), "soft")
+            if parents:
+                b = bufs["parent-soft"]
+                legs["parent-soft p=%d" % p] = lambda p=p, b=b: capi.check(parents[1][2](
+                    parents[1][1], ptr(llr), p, 0.5, ptr(b["out"]), ptr(b["ext"]), *four(b)), "parent-soft")
+        times = {k: [] for k in legs}
+        failed = {}
+        for k, call in legs.items():  # warm-up: code objects; the legs that must agree do
+            call()
+            torch.cuda.synchronize()
+            kind = k.split()[0]
+            failed[k] = int((bufs[kind]["status"] != 0).sum())
+            twin = {"ext-soft": "ext-hard", "parent-chase": "chase", "soft": "chase", "parent-soft": "soft"}.get(kind)
+            if twin:
+                for name, v in bufs[kind].items():
+                    if name in bufs[twin]:
+                        assert torch.equal(v.view(torch.uint8), bufs[twin][name].view(torch.uint8)), (k, name)
+        names = list(legs)
+        per_p = len(names) // len(PS)
+        for run in range(3):  # the legs of a p take turns at going first
+            for g in range(0, len(names), per_p):
+                for i in range(per_p):
+                    k = names[g + (i + run) % per_p]
+                    times[k].append(timed_ms(legs[k]))
+        print("%s and its extended code, %d frames at %.0f dB" % (code.to_string(), frames, ebno), flush=True)
+        F = lambda k, p: (lib.cc_chase_extended_frames_per_wavefront if k.startswith("ext") else lib.cc_chase_frames_per_wavefront)(
+            code._h, p, int(k.split()[0].endswith("soft")))
+        for k, ts in times.items():
+            p = int(k.split("=")[1])
+            print("  %-17s ms %8.3f - %8.3f   ns/frame %8.2f   F %2d   frames not decoded %d" % (
+                k, max(ts), min(ts), 1e6 * min(ts) / frames, F(k, p), failed[k]), flush=True)
+        for p in PS:
+            for e, c in (("ext-hard", "chase"), ("ext-soft", "soft")):
+                e_, c_ = times["%s p=%d" % (e, p)], times["%s p=%d" % (c, p)]
+                fe, fc = F(e, p), F(c, p)
+                line = "  p = %d: %s / %s = %.3f - %.3f (fastest / fastest %.3f; (n + 1) / n = %.3f); F %d against %d: %s" % (
+                    p, e, c, min(e_) / max(c_), max(e_) / min(c_), min(e_) / min(c_), (n + 1) / n, fe, fc,
+                    "the wider rows alone" if fe == fc else "the wider rows lower F")
+                if parents:
+                    a_ = times["parent-%s p=%d" % (c, p)]
+                    line += "; %s %s ms against the parent's %s ms: %s" % (c, spread(c_), spread(a_), against(c_, a_))
+                print(line, flush=True)
+        del legs, bufs, llr, wide
+
+
+def product_ext(blocks, ebno):
+    import numpy as np
+    import torch
+    import channelcoding_amd as cc
+    code = cc.primitive_bch(6, cc.errors(2), cc.berlekamp_massey_tag())
+    n, l = code.n, code.l
+    alpha, beta = (0.0, 0.2, 0.3, 0.5, 0.7, 0.9), (0.2, 0.4, 0.6, 0.8, 1.0, 1.0)
+    info = np.random.default_rng(1).integers(0, 2, (blocks, l, l)).astype(np.uint8)
+    for extended in (False, True):
+        w = n + 1 if extended else n
+        widen = cc.extend if extended else (lambda a: a)
+        wide = widen(code.encode_batch(info.reshape(-1, l))).reshape(blocks, l, w)
+        sent = widen(code.encode_batch(np.ascontiguousarray(wide.transpose(0, 2, 1)).reshape(-1, l))).reshape(blocks, w, w)
+        sent = np.ascontiguousarray(sent.transpose(0, 2, 1))
+        rate = (l / w) ** 2
+        sigma = 1.0 / np.sqrt(2.0 * rate * 10.0 ** (ebno / 10.0))
+        noise = np.random.default_rng(2).standard_normal(sent.shape).astype(np.float32)
+        y = torch.from_numpy(((1.0 - 2.0 * sent.astype(np.float32)) + np.float32(sigma) * noise).astype(np.float32)).cuda()
+        truth = torch.from_numpy(sent).cuda()
+        errors = lambda out: int((out != truth).any(dim=2).any(dim=1).sum())
+        name = "eBCH(%d,%d)" % (w, l) if extended else "BCH(%d,%d)" % (n, l)
+        print("%s x %s, rate %.4f, sigma %.4f, %d blocks at %.2f dB, numpy seeds 1 (bits) and 2 (noise): block errors" % (
+            name, name, rate, sigma, blocks, ebno))
+        print("  channel decisions %d" % errors((y < 0).to(torch.uint8)), flush=True)
+        for halves in range(1, len(alpha) + 1):
+            res = cc.product_decode(code, code, y, 4, alpha[:halves], beta[:halves], extended=extended)
+            print("  product_decode p = 4, %d half-iterations: %d" % (halves, errors(res["out"])), flush=True)
+
+
 def product(blocks):
     import numpy as np
     import torch
@@ -253,15 +402,20 @@ def wer(frames):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=("rates", "wer", "soft", "product"))
+    ap.add_argument("what", choices=("rates", "wer", "soft", "product", "extended", "product-ext"))
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--frames-log2", type=int, default=None)
     ap.add_argument("--only", choices=("p6",))
+    ap.add_argument("--ebno", type=float, default=3.0)
     a = ap.parse_args()
     if a.what == "rates":
         rates(1 << (a.frames_log2 if a.frames_log2 is not None else 20), a.only)
     elif a.what == "soft":
         soft(1 << (a.frames_log2 if a.frames_log2 is not None else 20), a.parent_lib)
+    elif a.what == "extended":
+        extended(1 << (a.frames_log2 if a.frames_log2 is not None else 20), a.parent_lib)
+    elif a.what == "product-ext":
+        product_ext(1 << (a.frames_log2 if a.frames_log2 is not None else 12), a.ebno)
     elif a.what == "product":
         product(1 << (a.frames_log2 if a.frames_log2 is not None else 12))
     else:

@@ -1,0 +1,27 @@
+"""Chase decoding of extended codes through the C++ facade (primitive_bch::correct_chase_extended /
+correct_chase_extended_batch of include/channelcoding_amd/cyclic.hpp): tests/cpp/facade_chase_extended.cpp compiles as
+plain C++14 with g++ against the C ABI, refuses to run without a GPU, and passes on one."""
+import os
+import subprocess
+
+import pytest
+
+from test_cpp_facade import ROOT, build
+
+BIN = os.path.join(ROOT, "tests", "cpp", "facade_chase_extended")
+
+
+def test_chase_extended_facade_compiles_and_fails_loudly_without_gpu():
+    build("facade_chase_extended")
+    import torch
+    if not torch.cuda.is_available():
+        out = subprocess.run([BIN], capture_output=True, text=True)
+        assert out.returncode == 1 and "no usable HIP device" in out.stderr
+
+
+@pytest.mark.gpu
+def test_chase_extended_facade_on_gpu():
+    build("facade_chase_extended")
+    out = subprocess.run([BIN], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "ALL OK" in out.stdout and out.stdout.count("ok ") >= 10
