@@ -61,6 +61,12 @@ class BurstDetector(C.Structure):
         super().__init__(C.sizeof(BurstDetector), 0, float(p_detect), float(p_false_alarm))
 
 
+class Product(C.Structure):
+    """cc_product: two handles, the extension flag and the schedule of a product code's decoder."""
+    _fields_ = [("rows", C.c_void_p), ("cols", C.c_void_p), ("extended", C.c_int), ("p", C.c_uint32),
+                ("halves", C.c_uint32), ("alpha", C.POINTER(C.c_float)), ("beta", C.POINTER(C.c_float))]
+
+
 class CcError(RuntimeError):
     def __init__(self, status, where):
         self.status = status
@@ -166,6 +172,17 @@ _SIGNATURES = {
     "cc_correct_hard_interleaved_batch_u16_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, C.c_uint32, _VP]),
     "cc_extract_interleaved_batch_u16": (C.c_int, [_VP, _VP, _VP, C.c_size_t, C.c_uint32]),
     "cc_extract_interleaved_batch_u16_dev": (C.c_int, [_VP, _VP, _VP, C.c_size_t, C.c_uint32, _VP]),
+    "cc_product_decode": (C.c_int, [C.POINTER(Product), _VP, _VP, _VP, _VP, C.c_size_t]),
+    "cc_product_decode_dev": (C.c_int, [C.POINTER(Product), _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "cc_product_encode_batch": (C.c_int, [C.POINTER(Product), _VP, _VP, C.c_size_t]),
+    "cc_product_encode_batch_dev": (C.c_int, [C.POINTER(Product), _VP, _VP, C.c_size_t, _VP]),
+    "cc_product_extract_batch": (C.c_int, [C.POINTER(Product), _VP, _VP, C.c_size_t]),
+    "cc_product_extract_batch_dev": (C.c_int, [C.POINTER(Product), _VP, _VP, C.c_size_t, _VP]),
+    "cc_product_sigma": (C.c_double, [C.POINTER(Product), C.c_double]),
+    "cc_awgn_product_dev": (C.c_int, [C.POINTER(Product), C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP,
+                                      _VP, _VP]),
+    "cc_mc_run_product_dev": (C.c_int, [C.POINTER(Product), C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP,
+                                        _VP]),
     "cc_diag_table": (C.c_int, [_VP, _VP, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                 C.POINTER(C.c_uint32)]),
     "cc_kernel_info": (C.c_int, [_VP, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),

@@ -341,32 +341,25 @@ def unextend(words):
     return inner.contiguous() if _is_torch(words) else np.ascontiguousarray(inner)
 
 
-def _product_decode_extended(rows, cols, y, p, alpha, beta):
-    """product_decode(extended=True): the same loop over the extended codes of `rows` and `cols`"""
-    if len(alpha) != len(beta) or not alpha:
-        raise ValueError("product_decode takes one alpha and one beta per half-iteration, at least one")
-    if len(y.shape) != 3 or y.shape[1] != cols.n + 1 or y.shape[2] != rows.n + 1:
-        raise CcError(capi.ERR_LENGTH, "product_decode")
+def _product_loop(rows, cols, y, p, alpha, beta, extended):
+    """the loop of product_decode over any two objects with n and correct_batch(X, chase=, soft=[, extended=True])"""
+    kw = dict(extended=True) if extended else {}
     torch_in = _is_torch(y)
     if torch_in:
-        import torch
-        if y.dtype != torch.float32:
-            raise TypeError("product_decode takes float32 channel values")
         y = y.contiguous()
+        import torch
         W = torch.zeros_like(y)
         turn = lambda a: a.transpose(1, 2).contiguous()
     else:
-        y = np.asarray(y)
-        if y.dtype.kind != "f":
-            raise TypeError("product_decode takes float32 channel values")
         y = np.ascontiguousarray(y, np.float32)
         W = np.zeros_like(y)
         turn = lambda a: np.ascontiguousarray(a.transpose(0, 2, 1))
     B, n2, n1 = y.shape
     for h, (a, b) in enumerate(zip(alpha, beta)):
-        X = y + (W * a if torch_in else W * np.float32(a))
+        scaled = W * a if torch_in else W * np.float32(a)
+        X = y + scaled
         code, lines, length = (rows, n2, n1) if h % 2 == 0 else (cols, n1, n2)
-        res = code.correct_batch((X if h % 2 == 0 else turn(X)).reshape(B * lines, length), chase=p, soft=b, extended=True)
+        res = code.correct_batch((X if h % 2 == 0 else turn(X)).reshape(B * lines, length), chase=p, soft=b, **kw)
         out, W = res["out"].reshape(B, lines, length), res["ext"].reshape(B, lines, length)
         if h % 2:
             out, W = turn(out), turn(W)
@@ -388,42 +381,27 @@ def product_decode(rows, cols, y, p, alpha, beta, extended=False):
     1 and beta = 0.2, 0.4, 0.6, 0.8, 1, 1, 1, 1 -- with W normalised to mean magnitude one, so a starting point only.
     extended=True: the product of the two extended codes (see extend), y of shape (B, cols.n + 1, rows.n + 1); every row
     and column goes through correct_batch(chase=p, soft=beta, extended=True), and out, ext and status are those of the
-    extended words."""
+    extended words.
+    Two codes of this package are decoded by one call of the library, product_code(rows, cols, extended).correct_batch
+    (cc_product_decode); any other pair of objects with n and correct_batch is looped over here.  The outputs are the
+    same bits either way."""
     alpha, beta = [float(np.float32(a)) for a in alpha], [float(np.float32(b)) for b in beta]
-    if extended:
-        return _product_decode_extended(rows, cols, y, p, alpha, beta)
+    e = 1 if extended else 0
     if len(alpha) != len(beta) or not alpha:
         raise ValueError("product_decode takes one alpha and one beta per half-iteration, at least one")
-    if len(y.shape) != 3 or y.shape[1] != cols.n or y.shape[2] != rows.n:
+    if len(y.shape) != 3 or y.shape[1] != cols.n + e or y.shape[2] != rows.n + e:
         raise CcError(capi.ERR_LENGTH, "product_decode")
-    torch_in = _is_torch(y)
-    if torch_in:
+    if _is_torch(y):
         import torch
         if y.dtype != torch.float32:
             raise TypeError("product_decode takes float32 channel values")
-        y = y.contiguous()
-        W = torch.zeros_like(y)
-        turn = lambda a: a.transpose(1, 2).contiguous()
     else:
         y = np.asarray(y)
         if y.dtype.kind != "f":
             raise TypeError("product_decode takes float32 channel values")
-        y = np.ascontiguousarray(y, np.float32)
-        W = np.zeros_like(y)
-        turn = lambda a: np.ascontiguousarray(a.transpose(0, 2, 1))
-    B, n2, n1 = y.shape
-    for h, (a, b) in enumerate(zip(alpha, beta)):
-        scaled = W * a if torch_in else W * np.float32(a)
-        X = y + scaled
-        if h % 2 == 0:
-            res = rows.correct_batch(X.reshape(B * n2, n1), chase=p, soft=b)
-            out, W = res["out"].reshape(B, n2, n1), res["ext"].reshape(B, n2, n1)
-            status = res["status"].reshape(B, n2)
-        else:
-            res = cols.correct_batch(turn(X).reshape(B * n1, n2), chase=p, soft=b)
-            out, W = turn(res["out"].reshape(B, n1, n2)), turn(res["ext"].reshape(B, n1, n2))
-            status = res["status"].reshape(B, n1)
-    return dict(out=out, ext=W, status=status)
+    if isinstance(rows, cyclic) and isinstance(cols, cyclic):
+        return product_code(rows, cols, extended).correct_batch(y, p, alpha, beta)
+    return _product_loop(rows, cols, y, p, alpha, beta, extended)
 
 
 def pack_bits(a):
@@ -1058,6 +1036,115 @@ class rs(cyclic):
 
     def __init__(self, q, capability, algorithm=None, coding="division", mu=1, step=1, **kw):
         super().__init__(q, capability, algorithm, coding, mu, step, **kw)
+
+
+class _product_handle:
+    """what cyclic._batch_call reads of a code, for a call whose first argument is a cc_product"""
+
+    def __init__(self, pc):
+        self._h, self.n = C.byref(pc), 0
+
+
+class product_code:
+    """The product of two binary BCH codes (cc_product): a block is (n2, n1) symbols whose rows are words of
+    `rows` and whose columns are words of `cols`; extended=True the product of the two extended codes, (n2 + 1, n1 + 1).
+    Both are handles correct_batch(chase=p) accepts, on one device.  n1, n2, k1, k2: lengths and message lengths of the
+    components; n = values per block, l = k1 k2 message bits per block."""
+
+    def __init__(self, rows, cols, extended=False):
+        if not isinstance(rows, cyclic) or not isinstance(cols, cyclic):
+            raise TypeError("product_code takes two codes of this package")
+        self.rows, self.cols, self.extended = rows, cols, bool(extended)
+        e = 1 if self.extended else 0
+        self.n1, self.n2, self.k1, self.k2 = rows.n + e, cols.n + e, rows.l, cols.l
+        self.n, self.l = self.n1 * self.n2, self.k1 * self.k2
+        self.rate = self.l / self.n
+
+    def to_string(self):
+        return "%sx%s%s" % (self.rows.to_string(), self.cols.to_string(), "-ext" if self.extended else "")
+
+    def _pc(self, p=0, alpha=(), beta=()):
+        """the cc_product of a call (the schedule arrays live as long as the object returned)"""
+        with np.errstate(over="ignore"):
+            alpha, beta = [float(np.float32(a)) for a in alpha], [float(np.float32(b)) for b in beta]
+        if len(alpha) != len(beta):
+            raise ValueError("one alpha and one beta per half-iteration")
+        p = int(p)
+        if p < 0:
+            raise ValueError("p >= 0")
+        fa, fb = (C.c_float * max(1, len(alpha)))(*alpha), (C.c_float * max(1, len(beta)))(*beta)
+        pc = capi.Product(self.rows._h, self.cols._h, int(self.extended), p, len(alpha), fa, fb)
+        pc._keep = (fa, fb, self.rows, self.cols)
+        return pc
+
+    def sigma(self, ebno_db):
+        return capi.lib().cc_product_sigma(C.byref(self._pc()), float(ebno_db))
+
+    def _bytes(self, x, inner, what):
+        """x as contiguous uint8 blocks of shape (B,) + inner"""
+        side = _side(x)
+        if tuple(x.shape[1:]) != inner or len(x.shape) != 3:
+            raise CcError(capi.ERR_LENGTH, what)
+        if side is _host:
+            x = np.asarray(x)
+            if x.dtype.kind not in "ub":
+                raise TypeError(what + " takes uint8 symbols")
+            return np.ascontiguousarray(x, np.uint8)
+        import torch
+        if x.dtype != torch.uint8:
+            raise TypeError(what + " takes uint8 symbols")
+        return x.contiguous()
+
+    def encode_batch(self, msg):
+        """(B, k2, k1) message bits -> (B, n2, n1) code blocks; numpy array or device tensor"""
+        msg = self._bytes(msg, (self.k2, self.k1), "encode_batch")
+        B = msg.shape[0]
+        return cyclic._batch_call(_product_handle(self._pc()), "cc_product_encode_batch", [msg], B,
+                                  {"out": ((B, self.n2, self.n1), np.uint8)})["out"]
+
+    def extract_batch(self, cw):
+        """(B, n2, n1) code blocks -> (B, k2, k1) message bits"""
+        cw = self._bytes(cw, (self.n2, self.n1), "extract_batch")
+        B = cw.shape[0]
+        return cyclic._batch_call(_product_handle(self._pc()), "cc_product_extract_batch", [cw], B,
+                                  {"msg": ((B, self.k2, self.k1), np.uint8)})["msg"]
+
+    def correct_batch(self, y, p, alpha, beta, ext=True):
+        """cc_product_decode: y (B, n2, n1) float32 -> dict(out=, status=[, ext=]) of the last of len(alpha)
+        half-iterations (see product_decode); ext=False skips the soft output: the last half-iteration then runs the
+        hard-output decoder."""
+        if not len(alpha):
+            raise ValueError("one alpha and one beta per half-iteration, at least one")
+        pc = self._pc(p, alpha, beta)
+        if len(y.shape) != 3 or tuple(y.shape[1:]) != (self.n2, self.n1):
+            raise CcError(capi.ERR_LENGTH, "correct_batch")
+        yy = _side(y).as_type(y, "f", np.float32)
+        if yy is None:
+            raise TypeError("product decoding takes float32 channel values")
+        B = yy.shape[0]
+        lines = self.n2 if pc.halves % 2 else self.n1
+        outs = {"out": ((B, self.n2, self.n1), np.uint8), "ext": ((B, self.n2, self.n1), np.float32) if ext else None,
+                "status": ((B, lines), np.int32)}
+        return cyclic._batch_call(_product_handle(pc), "cc_product_decode", [yy], B, outs)
+
+    def decode_batch(self, y, p, alpha, beta):
+        """correct_batch plus msg (B, k2, k1): the message bits of out"""
+        res = self.correct_batch(y, p, alpha, beta)
+        res["msg"] = self.extract_batch(res["out"])
+        return {k: res[k] for k in _KEYS if k in res}
+
+    def channel(self, ebno_db, seed, first_block, blocks, random_codewords=False):
+        """Blocks [first_block, first_block + blocks) of the AWGN channel on the current device (cc_awgn_product_dev):
+        dict(y=(blocks, n2, n1) float32, sent=(blocks, n2, n1) uint8) of torch tensors."""
+        import torch
+        blocks = int(blocks)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        y = torch.empty((blocks, self.n2, self.n1), dtype=torch.float32, device=dev)
+        sent = torch.empty((blocks, self.n2, self.n1), dtype=torch.uint8, device=dev)
+        rc = capi.lib().cc_awgn_product_dev(C.byref(self._pc()), float(ebno_db), int(seed), int(first_block), blocks,
+                                            int(bool(random_codewords)), _ptr(y), _ptr(sent), _stream_handle(y))
+        capi.check(rc, "cc_awgn_product_dev")
+        return dict(y=y, sent=sent)
 
 
 class min_sum_decoder(cyclic):

@@ -1550,6 +1550,131 @@ int cc_awgn_llr_dev(const cc_code *code, double ebno_db, uint64_t seed, uint64_t
                  static_cast<hipStream_t>(stream));
 }
 
+/* ------------------------------ product codes ------------------------------ */
+
+// What the product calls that read rows, cols and extended alone refuse, in the header's order: NULL handles, what the
+// Chase calls refuse short of the device at p for rows, then for cols, handles on different devices.  CC_OK or
+// CC_ERR_NO_DEVICE: the caller goes on with its own checks and answers the latter last.
+static int product_handles(const cc_product *pc, uint32_t p) {
+  if (!pc || !pc->rows || !pc->cols) return CC_ERR_INVALID_ARGUMENT;
+  int none = CC_OK;
+  for (const cc_code *code : {pc->rows, pc->cols}) {
+    const int rc = chase_supported(code, p);
+    if (rc != CC_OK && rc != CC_ERR_NO_DEVICE) return rc;
+    if (rc == CC_ERR_NO_DEVICE) none = rc;
+  }
+  if (pc->rows->device != pc->cols->device) return CC_ERR_INVALID_ARGUMENT;
+  return none;
+}
+
+static bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return a && b && a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
+}
+
+// the refusals of cc_product_decode(_dev) in the header's order; counters: the Monte-Carlo call, which has no arrays
+static int product_decode_supported(const cc_product *pc, const float *y, const uint8_t *out, const float *ext,
+                                    const int32_t *status, size_t B, bool arrays) {
+  if (!pc || !pc->rows || !pc->cols || !pc->alpha || !pc->beta) return CC_ERR_INVALID_ARGUMENT;
+  if (arrays && B && (!y || !out || !status)) return CC_ERR_INVALID_ARGUMENT;
+  if (pc->halves == 0) return CC_ERR_INVALID_ARGUMENT;
+  const int rc = product_handles(pc, pc->p);
+  if (rc != CC_OK && rc != CC_ERR_NO_DEVICE) return rc;
+  for (uint32_t h = 0; h < pc->halves; ++h)
+    if (!std::isfinite(pc->alpha[h]) || !(pc->beta[h] >= 0.0f) || !std::isfinite(pc->beta[h])) return CC_ERR_INVALID_ARGUMENT;
+  if (arrays) {
+    const size_t N = product_shape(pc).N;
+    if (ranges_overlap(y, B * N * sizeof(float), ext, B * N * sizeof(float)) ||
+        ranges_overlap(y, B * N * sizeof(float), out, B * N))
+      return CC_ERR_INVALID_ARGUMENT;
+  }
+  return rc;
+}
+
+int cc_product_decode_dev(const cc_product *pc, const float *d_y, uint8_t *d_out, float *d_ext, int32_t *d_status, size_t B,
+                          void *stream) {
+  if (int rc = product_decode_supported(pc, d_y, d_out, d_ext, d_status, B, true)) return rc;
+  DeviceGuard guard(pc->rows->device);
+  return launch_product_decode(pc, d_y, d_out, d_ext, d_status, B, static_cast<hipStream_t>(stream));
+}
+
+int cc_product_decode(const cc_product *pc, const float *y, uint8_t *out, float *ext, int32_t *status, size_t B) {
+  if (int rc = product_decode_supported(pc, y, out, ext, status, B, true)) return rc;
+  if (B == 0) return CC_OK;
+  const ProductShape s = product_shape(pc);
+  const size_t lines = (pc->halves & 1) ? s.w2 : s.w1;
+  DeviceGuard guard(pc->rows->device);
+  // a block is the frame of the chunk loop; ext == NULL leaves the last stream out and selects the hard output
+  const StagedStream streams[] = {stage_in(0, y, s.N * sizeof(float)), stage_out(1, out, s.N),
+                                  stage_out(3, status, lines * sizeof(int32_t)), stage_out(7, ext, s.N * sizeof(float))};
+  return staged_call(pc->rows, B, s.N * sizeof(float), 1, streams, ext ? 4 : 3, nullptr, nullptr,
+                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t st) {
+                       return launch_product_decode(pc, static_cast<const float *>(d[0]), static_cast<uint8_t *>(d[1]),
+                                                    static_cast<float *>(d[3]), static_cast<int32_t *>(d[2]), m, st);
+                     });
+}
+
+static int product_map_dev(const cc_product *pc, bool encode, const uint8_t *d_src, uint8_t *d_dst, size_t B, void *stream) {
+  if (!pc || !pc->rows || !pc->cols || (B && (!d_src || !d_dst))) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = product_handles(pc, 0)) return rc;
+  DeviceGuard guard(pc->rows->device);
+  return encode ? launch_product_encode(pc, d_src, d_dst, B, static_cast<hipStream_t>(stream))
+                : launch_product_extract(pc, d_src, d_dst, B, static_cast<hipStream_t>(stream));
+}
+
+static int product_map_host(const cc_product *pc, bool encode, const uint8_t *src, uint8_t *dst, size_t B) {
+  if (!pc || !pc->rows || !pc->cols || (B && (!src || !dst))) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = product_handles(pc, 0)) return rc;
+  if (B == 0) return CC_OK;
+  const ProductShape s = product_shape(pc);
+  const size_t in_w = encode ? s.k1 * s.k2 : s.N, out_w = encode ? s.N : s.k1 * s.k2;
+  if (encode && !symbols_in_field(src, B * in_w, 1)) return CC_ERR_NOT_IN_FIELD;
+  DeviceGuard guard(pc->rows->device);
+  const StagedStream streams[] = {stage_in(0, src, in_w), stage_out(1, dst, out_w)};
+  return staged_call(pc->rows, B, s.N, 1, streams, 2, nullptr, nullptr,
+                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t st) {
+                       const uint8_t *d_src = static_cast<const uint8_t *>(d[0]);
+                       uint8_t *d_dst = static_cast<uint8_t *>(d[1]);
+                       return encode ? launch_product_encode(pc, d_src, d_dst, m, st) : launch_product_extract(pc, d_src, d_dst, m, st);
+                     });
+}
+
+int cc_product_encode_batch_dev(const cc_product *pc, const uint8_t *d_msg, uint8_t *d_cw, size_t B, void *stream) {
+  return product_map_dev(pc, true, d_msg, d_cw, B, stream);
+}
+int cc_product_extract_batch_dev(const cc_product *pc, const uint8_t *d_cw, uint8_t *d_msg, size_t B, void *stream) {
+  return product_map_dev(pc, false, d_cw, d_msg, B, stream);
+}
+int cc_product_encode_batch(const cc_product *pc, const uint8_t *msg, uint8_t *cw, size_t B) {
+  return product_map_host(pc, true, msg, cw, B);
+}
+int cc_product_extract_batch(const cc_product *pc, const uint8_t *cw, uint8_t *msg, size_t B) {
+  return product_map_host(pc, false, cw, msg, B);
+}
+
+double cc_product_sigma(const cc_product *pc, double ebno_db) {
+  if (!pc || !pc->rows || !pc->cols || needs_code(pc->rows) != CC_OK || needs_code(pc->cols) != CC_OK) return 0.0;
+  const ProductShape s = product_shape(pc);
+  const double rate = static_cast<double>(s.k1 * s.k2) / static_cast<double>(s.N);
+  return 1.0 / std::sqrt(2.0 * rate * std::pow(10.0, ebno_db / 10.0));
+}
+
+int cc_awgn_product_dev(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
+                        int random_codewords, float *d_y, uint8_t *d_sent, void *stream) {
+  if (!pc || !pc->rows || !pc->cols || (blocks && !d_y)) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = product_handles(pc, 0)) return rc;
+  DeviceGuard guard(pc->rows->device);
+  return product_awgn(pc, ebno_db, seed, first_block, blocks, random_codewords, d_y, d_sent, static_cast<hipStream_t>(stream));
+}
+
+int cc_mc_run_product_dev(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
+                          int random_codewords, uint64_t *d_counters, void *stream) {
+  if (!pc || !d_counters) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = product_decode_supported(pc, nullptr, nullptr, nullptr, nullptr, blocks, false)) return rc;
+  DeviceGuard guard(pc->rows->device);
+  return mc_run_product(pc, ebno_db, seed, first_block, blocks, random_codewords, d_counters, static_cast<hipStream_t>(stream));
+}
+
 // the discrete channels serve every q <= 8 handle the decoders serve; the checks of the two entry points
 static int discrete_supported(const cc_code *code, double p_error, double p_erasure, int random_codewords) {
   if (!std::isfinite(p_error) || !std::isfinite(p_erasure) || p_error < 0.0 || p_erasure < 0.0 ||

@@ -292,6 +292,25 @@ bool interleaved_native_supported(const cc_code *code, size_t B, size_t I, bool 
 bool interleaved_encode_native(const cc_code *code, size_t I);   // where bitslice_encode_supported holds
 bool interleaved_extract_native(const cc_code *code, size_t I);  // division coding, any q
 int launch_interleaved_extract(const cc_code *code, const void *d_cw, void *d_msg, size_t B, size_t I, hipStream_t stream);
+// product.hip: product codes; pc checked by the caller (cc_product_decode_dev)
+struct ProductShape {
+  int e;                       // 1: the product of the two extended codes
+  size_t w1, w2, k1, k2, N;    // values per row and per column, message symbols per row and column, N = w1 w2
+};
+ProductShape product_shape(const cc_product *pc);
+// d_ext == nullptr: the last half-iteration runs the hard-output kernel
+int launch_product_decode(const cc_product *pc, const float *d_y, uint8_t *d_out, float *d_ext, int32_t *d_status, size_t B,
+                          hipStream_t stream);
+int launch_product_encode(const cc_product *pc, const uint8_t *d_msg, uint8_t *d_cw, size_t B, hipStream_t stream);
+int launch_product_extract(const cc_product *pc, const uint8_t *d_cw, uint8_t *d_msg, size_t B, hipStream_t stream);
+// d_sent == nullptr: the all-zero block; d_status: the last half-iteration's, (halves odd ? w2 : w1) entries per block
+int launch_product_count(const cc_product *pc, const uint8_t *d_decided, const uint8_t *d_sent, const int32_t *d_status,
+                         size_t B, uint64_t *d_counters, hipStream_t stream);
+// blocks [first_block, first_block + blocks) of the AWGN channel: d_y (blocks N floats), d_sent (nullptr: not wanted)
+int product_awgn(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
+                 int random_codewords, float *d_y, uint8_t *d_sent, hipStream_t stream);
+int mc_run_product(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
+                   int random_codewords, uint64_t *d_counters, hipStream_t stream);
 // mc.hip (Monte-Carlo calls on one handle must be issued on one stream at a time: they share a workspace)
 int mc_run(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
            uint64_t *d_counters, hipStream_t stream);
@@ -303,6 +322,12 @@ int mc_awgn_symbols(cc_code *code, double ebno_db, uint64_t seed, uint64_t first
                     uint8_t *d_words, float *d_rel, uint8_t *d_sent, hipStream_t stream);
 int mc_awgn(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
             float *d_llr, uint8_t *d_sent, hipStream_t stream);
+// the two generators of the AWGN routes for frames of any length (a block of a product code); `code` sizes the grid
+int launch_awgn_values(const cc_code *code, int n, float sigma, uint64_t seed, uint64_t first_frame, size_t frames,
+                       float *d_llr, const uint8_t *sent, hipStream_t stream, unsigned long long *d_counters = nullptr,
+                       bool hard_bytes = false);
+int launch_random_bits(const cc_code *code, int l, uint64_t seed, uint64_t first_frame, size_t frames, uint8_t *d_msg,
+                       hipStream_t stream);
 int mc_run_discrete(cc_code *code, double p_error, double p_erasure, uint64_t seed, uint64_t first_frame, size_t frames,
                     int random_codewords, uint64_t *d_counters, hipStream_t stream);
 int mc_discrete(cc_code *code, double p_error, double p_erasure, uint64_t seed, uint64_t first_frame, size_t frames,

@@ -412,17 +412,26 @@ static int mc_chunked(const cc_code *code, size_t frames, size_t chunk, size_t w
 
 constexpr size_t MC_CHUNK = size_t(1) << 20;  // ~1.6 GB of workspace for n = 255: long launches, short tails
 
-// the transmitted words of frames [first, first + frames): random messages through the device encoder
-static int launch_sent_words(const cc_code *code, uint64_t seed, uint64_t first_frame, size_t frames, uint8_t *d_sent,
-                             uint8_t *d_msg_scratch, hipStream_t stream) {
-  if (!d_sent || !d_msg_scratch) return CC_ERR_INVALID_ARGUMENT;
-  const int l = static_cast<int>(code->tab.l);
+// l random message bits for each of the frames [first, first + frames) (random_bits_kernel); `code` sizes the grid
+int launch_random_bits(const cc_code *code, int l, uint64_t seed, uint64_t first_frame, size_t frames, uint8_t *d_msg,
+                       hipStream_t stream) {
   const uint32_t k0 = static_cast<uint32_t>(seed), k1 = static_cast<uint32_t>(seed >> 32);
   int bits_log2 = 0;
   while ((16 << bits_log2) < l) ++bits_log2;
   const unsigned long long items = static_cast<unsigned long long>(frames) << bits_log2;
-  hipLaunchKernelGGL(random_bits_kernel, dim3(grid_for(code, items)), dim3(256), 0, stream, d_msg_scratch, l, bits_log2,
+  hipLaunchKernelGGL(random_bits_kernel, dim3(grid_for(code, items)), dim3(256), 0, stream, d_msg, l, bits_log2,
                      static_cast<unsigned long long>(first_frame), static_cast<unsigned long long>(frames), k0, k1);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "random bits kernel launch");
+  return CC_OK;
+}
+
+// the transmitted words of frames [first, first + frames): random messages through the device encoder
+static int launch_sent_words(const cc_code *code, uint64_t seed, uint64_t first_frame, size_t frames, uint8_t *d_sent,
+                             uint8_t *d_msg_scratch, hipStream_t stream) {
+  if (!d_sent || !d_msg_scratch) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = launch_random_bits(code, static_cast<int>(code->tab.l), seed, first_frame, frames, d_msg_scratch, stream))
+    return rc;
   return launch_encode_bits(code, d_msg_scratch, d_sent, frames, stream);
 }
 
@@ -517,12 +526,11 @@ static bool mc_precheck_pays(const cc_code *code, double ebno_db) {
   return std::pow(1.0 - pbit, static_cast<double>(n)) >= 0.25;
 }
 
-// writes y for frames [first, first + frames) of the words `sent` (nullptr: the all-zero word)
-static int launch_awgn(const cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
-                       float *d_llr, const uint8_t *sent, hipStream_t stream, unsigned long long *d_counters = nullptr,
-                       bool hard_bytes = false) {
-  const int n = static_cast<int>(code->tab.n);
-  const float sigma = static_cast<float>(cc_sigma(code, ebno_db));  // normal_distribution<float>(1.0, float(sigma))
+// y for frames [first, first + frames) of n values each at noise `sigma`, over the words `sent` (nullptr: the all-zero
+// word); `code` sizes the grid.  n is any length (a block of a product code: up to 2^16 values)
+int launch_awgn_values(const cc_code *code, int n, float sigma, uint64_t seed, uint64_t first_frame, size_t frames,
+                       float *d_llr, const uint8_t *sent, hipStream_t stream, unsigned long long *d_counters,
+                       bool hard_bytes) {
   const uint32_t k0 = static_cast<uint32_t>(seed), k1 = static_cast<uint32_t>(seed >> 32);
   int group_log2 = 0;
   while ((4 << group_log2) < n) ++group_log2;
@@ -538,6 +546,15 @@ static int launch_awgn(const cc_code *code, double ebno_db, uint64_t seed, uint6
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "awgn kernel launch");
   return CC_OK;
+}
+
+// writes y for frames [first, first + frames) of the words `sent` (nullptr: the all-zero word)
+static int launch_awgn(const cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
+                       float *d_llr, const uint8_t *sent, hipStream_t stream, unsigned long long *d_counters = nullptr,
+                       bool hard_bytes = false) {
+  const float sigma = static_cast<float>(cc_sigma(code, ebno_db));  // normal_distribution<float>(1.0, float(sigma))
+  return launch_awgn_values(code, static_cast<int>(code->tab.n), sigma, seed, first_frame, frames, d_llr, sent, stream,
+                            d_counters, hard_bytes);
 }
 
 int mc_run(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,

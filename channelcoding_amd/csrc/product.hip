@@ -1,0 +1,392 @@
+// product.hip -- product codes on the device: the launch sequences of the iterative (turbo) decoder, the
+// encoder and its inverse around the component kernels of chase.hip and encode.hip, and the small kernels between them.
+//
+// A block is y[w2][w1] in row orientation: row i is a word of `rows` (w1 = rows.n + e values), column k a word of `cols`
+// (w2 = cols.n + e), e = 1 for the product of the two extended codes.  A column-oriented array is [w1][w2].
+//
+//   mix_turn_kernel     X = y + (alpha * W), a float32 product then a float32 sum (the unit is built without
+//                       contraction), in the three shapes the loop needs.  All of them move a tile of TR rows of a
+//                       source array S[R][C] through LDS and meet the array D[C][R] turned: the source side of a tile
+//                       is one flat run of TR * C floats, the other side C runs of TR consecutive floats, and the LDS
+//                       pitch C | 1 is odd in dwords, so the turned access of a wavefront walks 64 different banks.
+//                         MIX_COLUMN  S = y and W straight (R = w2, C = w1), D = X column-oriented
+//                         MIX_ROW     S = W column-oriented (R = w1, C = w2), D = X = y + (alpha * S^T) row-oriented
+//                         TURN        D = S^T, a copy without arithmetic (adding +0.0f would turn -0.0f into +0.0f)
+//                       W == nullptr is W = +0.0f: the sum y + (alpha * 0.0f) is still formed, because the sign of a
+//                       zero of X reaches ext.
+//   resize_rows_kernel  rows of n bytes -> rows of n + 1 with the overall parity bit appended (extend on the device),
+//                       or rows of n + 1 -> rows of n (the parity bit dropped)
+//   product_count_kernel
+//                       per block the wrong bits among its N values and whether a component word of the last
+//                       half-iteration failed, into the CC_MC_* slots: one wavefront per block, the counts of a
+//                       wavefront in registers, one 64-bit atomic per wavefront and slot at the end
+//
+// The byte turns (out, the encoder's intermediate words) are launch_interleave at width 1: I = w2 or w1 <= 256.
+// No kernel here touches a value outside the B * N (B * lines) it is given.
+#include <cmath>
+#include <cstdlib>
+#include <utility>
+
+#include "cc_internal.hpp"
+
+namespace ccamd {
+namespace {
+
+constexpr int kTileFloats = 8448;  // floats of a tile in LDS: 32 rows at C = 256 with the padded pitch of 257
+
+enum MixShape { MIX_COLUMN = 0, MIX_ROW = 1, TURN = 2 };
+
+// the flat walk of the 256 threads over rows of `width`: (row, col) of element tid + 256 k, stepped without a division
+struct Walk {
+  int r, c, dr, dc, width;
+  __device__ __forceinline__ Walk(int tid, int w) : r(tid / w), c(tid % w), dr(256 / w), dc(256 % w), width(w) {}
+  __device__ __forceinline__ void next() {
+    r += dr;
+    c += dc;
+    if (c >= width) {
+      c -= width;
+      ++r;
+    }
+  }
+};
+
+// blocks of R * C floats; S, W, y, D as the shape says (see above); TR = rows of S per tile
+template <int SHAPE>
+__global__ void __launch_bounds__(256)
+mix_turn_kernel(const float *__restrict__ S, const float *__restrict__ W, const float *__restrict__ y, float alpha,
+                float *__restrict__ D, unsigned long long blocks, int R, int C, int TR) {
+  __shared__ float tile[kTileFloats];
+  const int P = C | 1, tpb = (R + TR - 1) / TR;
+  const unsigned long long N = static_cast<unsigned long long>(R) * C, total = blocks * static_cast<unsigned long long>(tpb);
+  const bool staged = SHAPE != MIX_ROW || S != nullptr;  // (MIX_ROW without W: nothing to turn)
+  for (unsigned long long t = blockIdx.x; t < total; t += gridDim.x) {
+    const unsigned long long b = t / tpb;
+    const int r0 = static_cast<int>(t % tpb) * TR, tr = R - r0 < TR ? R - r0 : TR, cnt = tr * C;
+    const unsigned long long src = b * N + static_cast<unsigned long long>(r0) * C;  // the flat run of the tile
+    if (staged) {
+      Walk w(threadIdx.x, C);
+      for (int e = threadIdx.x; e < cnt; e += 256, w.next()) {
+        float v = S[src + e];
+        if (SHAPE == MIX_COLUMN) v = v + (alpha * (W ? W[src + e] : 0.0f));
+        tile[w.r * P + w.c] = v;
+      }
+      __syncthreads();
+    }
+    // the turned side: column c of the tile is the run D[c][r0 .. r0 + tr)
+    Walk w(threadIdx.x, tr);
+    for (int o = threadIdx.x; o < cnt; o += 256, w.next()) {
+      const unsigned long long dst = b * N + static_cast<unsigned long long>(w.r) * R + r0 + w.c;
+      if (SHAPE == MIX_ROW)
+        D[dst] = y[dst] + (alpha * (staged ? tile[w.c * P + w.r] : 0.0f));
+      else
+        D[dst] = tile[w.c * P + w.r];
+    }
+    if (staged) __syncthreads();  // the tile is reused by the next trip
+  }
+}
+
+// 16 lanes per row.  APPEND: rows of n bytes -> n + 1, out[n] = the parity of the row's bits; otherwise n + 1 -> n
+template <bool APPEND>
+__global__ void __launch_bounds__(256)
+resize_rows_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, int n, unsigned long long rows) {
+  const int sl = threadIdx.x & 15;
+  const unsigned long long first = (static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x) >> 4;
+  const unsigned long long step = (static_cast<unsigned long long>(gridDim.x) * 256) >> 4;
+  const unsigned long long trips = (rows + step - 1) / step;  // the same in every lane: the shuffles below
+  const int wi = APPEND ? n : n + 1, wo = APPEND ? n + 1 : n;
+  for (unsigned long long tr = 0; tr < trips; ++tr) {
+    const unsigned long long r = first + tr * step;
+    const bool live = r < rows;
+    unsigned par = 0;
+    if (live)
+      for (int i = sl; i < n; i += 16) {
+        const uint8_t v = in[r * wi + i];
+        out[r * wo + i] = v;
+        par ^= v;
+      }
+    if (APPEND) {
+      for (int m = 8; m >= 1; m >>= 1) par ^= static_cast<unsigned>(__shfl_xor(static_cast<int>(par), m, 64));
+      if (live && sl == 0) out[r * wo + n] = static_cast<uint8_t>(par & 1u);
+    }
+  }
+}
+
+// decided: B blocks of N bytes; sent: the blocks sent (nullptr: the all-zero word); status: `lines` entries per block
+__global__ void __launch_bounds__(256)
+product_count_kernel(const uint8_t *__restrict__ decided, const uint8_t *__restrict__ sent, const int32_t *__restrict__ status,
+                     unsigned long long N, int lines, unsigned long long blocks, unsigned long long *__restrict__ counters) {
+  const int lane = threadIdx.x & 63;
+  const unsigned long long wave = static_cast<unsigned long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  const unsigned long long waves = static_cast<unsigned long long>(gridDim.x) * 4;
+  unsigned long long c_frames = 0, c_bit = 0, c_word = 0, c_fail = 0, c_und = 0;  // lane 0: of the blocks this wavefront saw
+  for (unsigned long long b = wave; b < blocks; b += waves) {
+    const uint8_t *d = decided + b * N, *s = sent ? sent + b * N : nullptr;
+    unsigned cnt = 0;
+    for (unsigned long long i = lane; i < N; i += 64) cnt += (d[i] != (s ? s[i] : 0)) ? 1u : 0u;
+    bool bad = false;
+    for (int i = lane; i < lines; i += 64) bad = bad || status[b * lines + i] != CC_FRAME_OK;
+    for (int m = 32; m >= 1; m >>= 1) cnt += static_cast<unsigned>(__shfl_xor(static_cast<int>(cnt), m, 64));
+    const bool failed = __any(bad ? 1 : 0) != 0;
+    c_frames += 1;
+    c_bit += cnt;
+    c_word += (failed || cnt) ? 1u : 0u;
+    c_fail += failed ? 1u : 0u;
+    c_und += (!failed && cnt) ? 1u : 0u;
+  }
+  if (lane == 0 && c_frames) {
+    atomicAdd(&counters[CC_MC_FRAMES], c_frames);
+    if (c_bit) atomicAdd(&counters[CC_MC_BIT_ERRORS], c_bit);
+    if (c_word) atomicAdd(&counters[CC_MC_WORD_ERRORS], c_word);
+    if (c_fail) atomicAdd(&counters[CC_MC_FAILURES], c_fail);
+    if (c_und) atomicAdd(&counters[CC_MC_UNDETECTED], c_und);
+  }
+}
+
+int launched(const char *what) {
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? hip_fail(e, what) : CC_OK;
+}
+
+unsigned grid_of(const cc_code *code, unsigned long long want) {
+  const unsigned long long cap = static_cast<unsigned long long>(code->num_cus) * 8;
+  return static_cast<unsigned>(want < 1 ? 1 : want < cap ? want : cap);
+}
+
+// S[R][C] per block against D[C][R]; see mix_turn_kernel
+int launch_mix_turn(const cc_code *code, int shape, const float *S, const float *W, const float *y, float alpha, float *D,
+                    size_t blocks, int R, int C, hipStream_t stream) {
+  if (blocks == 0) return CC_OK;
+  int TR = kTileFloats / (C | 1);
+  if (TR > R) TR = R;
+  const unsigned long long tiles = static_cast<unsigned long long>(blocks) * ((R + TR - 1) / TR);
+  const auto kernel = shape == MIX_COLUMN ? mix_turn_kernel<MIX_COLUMN> : shape == MIX_ROW ? mix_turn_kernel<MIX_ROW>
+                                                                                            : mix_turn_kernel<TURN>;
+  hipLaunchKernelGGL(kernel, dim3(grid_of(code, tiles)), dim3(256), 0, stream, S, W, y, alpha, D,
+                     static_cast<unsigned long long>(blocks), R, C, TR);
+  return launched("product mix kernel launch");
+}
+
+int launch_resize_rows(const cc_code *code, bool append, const uint8_t *in, uint8_t *out, int n, size_t rows,
+                       hipStream_t stream) {
+  if (rows == 0) return CC_OK;
+  const unsigned grid = grid_of(code, (static_cast<unsigned long long>(rows) + 15) / 16);
+  if (append)
+    hipLaunchKernelGGL(resize_rows_kernel<true>, dim3(grid), dim3(256), 0, stream, in, out, n, static_cast<unsigned long long>(rows));
+  else
+    hipLaunchKernelGGL(resize_rows_kernel<false>, dim3(grid), dim3(256), 0, stream, in, out, n, static_cast<unsigned long long>(rows));
+  return launched("product row kernel launch");
+}
+
+// bytes [blocks][R][C] -> [blocks][C][R]
+int turn_bytes(const uint8_t *in, uint8_t *out, size_t blocks, size_t R, size_t C, hipStream_t stream) {
+  return launch_interleave(in, 1, C, R, out, blocks * R, true, stream);
+}
+
+// stream-ordered scratch of one call, returned to the pool on every way out
+struct Scratch {
+  const cc_code *code;
+  hipStream_t stream;
+  void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  int used = 0;
+  Scratch(const cc_code *c, hipStream_t s) : code(c), stream(s) {}
+  ~Scratch() {
+    for (int i = 0; i < used; ++i)
+      if (p[i]) (void)hipFreeAsync(p[i], stream);
+  }
+  template <class T>
+  hipError_t get(T **out, size_t bytes) {
+    const hipError_t e = workspace_alloc(code, &p[used], bytes ? bytes : 1, stream);
+    *out = static_cast<T *>(p[used]);
+    if (e == hipSuccess) ++used;
+    return e;
+  }
+};
+
+}  // namespace
+
+ProductShape product_shape(const cc_product *pc) {
+  const size_t e = pc->extended ? 1 : 0;
+  ProductShape s;
+  s.e = static_cast<int>(e);
+  s.w1 = pc->rows->tab.n + e;
+  s.w2 = pc->cols->tab.n + e;
+  s.k1 = pc->rows->tab.l;
+  s.k2 = pc->cols->tab.l;
+  s.N = s.w1 * s.w2;
+  return s;
+}
+
+int launch_product_decode(const cc_product *pc, const float *d_y, uint8_t *d_out, float *d_ext, int32_t *d_status, size_t B,
+                          hipStream_t stream) {
+  if (B == 0) return CC_OK;
+  const cc_code *rows = pc->rows, *cols = pc->cols;
+  const ProductShape s = product_shape(pc);
+  const int w1 = static_cast<int>(s.w1), w2 = static_cast<int>(s.w2);
+  const size_t total = B * s.N;
+  const unsigned halves = pc->halves;
+  Scratch scratch(rows, stream);
+  float *X = nullptr, *W = nullptr;
+  uint8_t *O = nullptr;
+  CC_HIP_TRY(scratch.get(&X, total * sizeof(float)));
+  CC_HIP_TRY(scratch.get(&W, total * sizeof(float)));  // ext of a pass, in the orientation of that pass
+  CC_HIP_TRY(scratch.get(&O, total));                  // out of a pass that is not the caller's
+  for (unsigned h = 0; h < halves; ++h) {
+    const bool column = (h & 1) != 0, last = h + 1 == halves;
+    const float *Wp = h ? W : nullptr;
+    // X in the orientation of the pass; W is in that of the pass before
+    int rc = column ? launch_mix_turn(rows, MIX_COLUMN, d_y, Wp, nullptr, pc->alpha[h], X, B, w2, w1, stream)
+                    : launch_mix_turn(rows, MIX_ROW, Wp, nullptr, d_y, pc->alpha[h], X, B, w1, w2, stream);
+    if (rc != CC_OK) return rc;
+    const cc_code *code = column ? cols : rows;
+    const size_t words = B * (column ? s.w1 : s.w2);
+    uint8_t *out = last && !column ? d_out : O;
+    float *ext = !last ? W : !d_ext ? nullptr : column ? W : d_ext;
+    int32_t *status = last ? d_status : nullptr;
+    if (s.e)
+      rc = launch_chase_extended(code, X, pc->p, pc->beta[h], out, ext, nullptr, nullptr, status, words, stream);
+    else if (ext)
+      rc = launch_chase_soft(code, X, pc->p, pc->beta[h], out, ext, nullptr, nullptr, status, words, stream);
+    else
+      rc = launch_chase(code, X, pc->p, out, nullptr, nullptr, status, words, stream);
+    if (rc != CC_OK) return rc;
+    if (last && column) {  // back into the orientation of y
+      if ((rc = turn_bytes(O, d_out, B, s.w1, s.w2, stream)) != CC_OK) return rc;
+      if (d_ext && (rc = launch_mix_turn(rows, TURN, W, nullptr, nullptr, 0.0f, d_ext, B, w1, w2, stream)) != CC_OK) return rc;
+    }
+  }
+  return CC_OK;
+}
+
+int launch_product_encode(const cc_product *pc, const uint8_t *d_msg, uint8_t *d_cw, size_t B, hipStream_t stream) {
+  if (B == 0) return CC_OK;
+  const cc_code *rows = pc->rows, *cols = pc->cols;
+  const ProductShape s = product_shape(pc);
+  const size_t n1 = rows->tab.n, n2 = cols->tab.n;
+  Scratch scratch(rows, stream);
+  uint8_t *a = nullptr, *b = nullptr;
+  CC_HIP_TRY(scratch.get(&a, B * s.N));
+  CC_HIP_TRY(scratch.get(&b, B * s.N));
+  // the k2 information rows: [B][k2][w1] in a
+  int rc = launch_encode(rows, d_msg, s.e ? b : a, B * s.k2, stream);
+  if (rc == CC_OK && s.e) rc = launch_resize_rows(rows, true, b, a, static_cast<int>(n1), B * s.k2, stream);
+  if (rc == CC_OK) rc = turn_bytes(a, b, B, s.k2, s.w1, stream);  // [B][w1][k2] in b
+  // all w1 columns: [B][w1][w2] in a
+  if (rc == CC_OK) rc = launch_encode(cols, b, s.e ? d_cw : a, B * s.w1, stream);
+  if (rc == CC_OK && s.e) rc = launch_resize_rows(rows, true, d_cw, a, static_cast<int>(n2), B * s.w1, stream);
+  if (rc == CC_OK) rc = turn_bytes(a, d_cw, B, s.w1, s.w2, stream);
+  return rc;
+}
+
+int launch_product_extract(const cc_product *pc, const uint8_t *d_cw, uint8_t *d_msg, size_t B, hipStream_t stream) {
+  if (B == 0) return CC_OK;
+  const cc_code *rows = pc->rows, *cols = pc->cols;
+  const ProductShape s = product_shape(pc);
+  const size_t n1 = rows->tab.n, n2 = cols->tab.n;
+  Scratch scratch(rows, stream);
+  uint8_t *a = nullptr, *b = nullptr;
+  CC_HIP_TRY(scratch.get(&a, B * s.N));
+  CC_HIP_TRY(scratch.get(&b, B * s.N));
+  int rc = turn_bytes(d_cw, a, B, s.w2, s.w1, stream);  // [B][w1][w2] in a
+  if (rc == CC_OK && s.e) {
+    rc = launch_resize_rows(rows, false, a, b, static_cast<int>(n2), B * s.w1, stream);
+    std::swap(a, b);
+  }
+  if (rc == CC_OK) rc = launch_extract(cols, a, b, B * s.w1, stream);  // [B][w1][k2] in b
+  if (rc == CC_OK) rc = turn_bytes(b, a, B, s.w1, s.k2, stream);       // [B][k2][w1] in a
+  if (rc == CC_OK && s.e) {
+    rc = launch_resize_rows(rows, false, a, b, static_cast<int>(n1), B * s.k2, stream);
+    std::swap(a, b);
+  }
+  if (rc == CC_OK) rc = launch_extract(rows, a, d_msg, B * s.k2, stream);
+  return rc;
+}
+
+int launch_product_count(const cc_product *pc, const uint8_t *d_decided, const uint8_t *d_sent, const int32_t *d_status,
+                         size_t B, uint64_t *d_counters, hipStream_t stream) {
+  if (B == 0) return CC_OK;
+  const ProductShape s = product_shape(pc);
+  const int lines = static_cast<int>((pc->halves & 1) ? s.w2 : s.w1);
+  hipLaunchKernelGGL(product_count_kernel, dim3(grid_of(pc->rows, (static_cast<unsigned long long>(B) + 3) / 4)), dim3(256), 0,
+                     stream, d_decided, d_sent, d_status, static_cast<unsigned long long>(s.N), lines,
+                     static_cast<unsigned long long>(B), reinterpret_cast<unsigned long long *>(d_counters));
+  return launched("product count kernel launch");
+}
+
+// Blocks per chunk of the Monte-Carlo and channel routes: 2^24 values (CC_AMD_PRODUCT_MC_CHUNK_VALUES: tests cross a chunk
+// boundary with a small call), about 18 bytes of workspace per value, at least one block
+static size_t product_chunk_blocks(size_t N, size_t blocks) {
+  static const size_t chunk_values = [] {
+    const char *e = std::getenv("CC_AMD_PRODUCT_MC_CHUNK_VALUES");
+    const long long v = e ? std::atoll(e) : 0;
+    return v > 0 ? static_cast<size_t>(v) : size_t(1) << 24;
+  }();
+  size_t ch = chunk_values / N;
+  if (ch < 1) ch = 1;
+  return ch < blocks ? ch : blocks;
+}
+
+// the blocks sent for the global blocks [first, first + m): l = k1 k2 random bits per block through the product encoder
+static int product_sent(const cc_product *pc, uint64_t seed, uint64_t first, size_t m, uint8_t *d_msg, uint8_t *d_sent,
+                        hipStream_t stream) {
+  const ProductShape s = product_shape(pc);
+  if (int rc = launch_random_bits(pc->rows, static_cast<int>(s.k1 * s.k2), seed, first, m, d_msg, stream)) return rc;
+  return launch_product_encode(pc, d_msg, d_sent, m, stream);
+}
+
+int product_awgn(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
+                 int random_codewords, float *d_y, uint8_t *d_sent, hipStream_t stream) {
+  if (blocks == 0) return CC_OK;
+  const ProductShape s = product_shape(pc);
+  const float sigma = static_cast<float>(cc_product_sigma(pc, ebno_db));
+  const int N = static_cast<int>(s.N);
+  if (!random_codewords) {
+    if (d_sent) CC_HIP_TRY(hipMemsetAsync(d_sent, 0, blocks * s.N, stream));
+    return launch_awgn_values(pc->rows, N, sigma, seed, first_block, blocks, d_y, nullptr, stream);
+  }
+  const size_t chunk = product_chunk_blocks(s.N, blocks);
+  Scratch scratch(pc->rows, stream);
+  uint8_t *msg = nullptr, *words = nullptr;
+  CC_HIP_TRY(scratch.get(&msg, chunk * s.k1 * s.k2));
+  if (!d_sent) CC_HIP_TRY(scratch.get(&words, chunk * s.N));
+  for (size_t done = 0; done < blocks; done += chunk) {
+    const size_t m = blocks - done < chunk ? blocks - done : chunk;
+    uint8_t *sent = d_sent ? d_sent + done * s.N : words;
+    if (int rc = product_sent(pc, seed, first_block + done, m, msg, sent, stream)) return rc;
+    if (int rc = launch_awgn_values(pc->rows, N, sigma, seed, first_block + done, m, d_y + done * s.N, sent, stream)) return rc;
+  }
+  return CC_OK;
+}
+
+// channel, decoder with the hard output in its last half-iteration, count: chunk by chunk, the counters of a block a
+// function of (seed, ebno, pc, global block index) alone
+int mc_run_product(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
+                   int random_codewords, uint64_t *d_counters, hipStream_t stream) {
+  if (blocks == 0) return CC_OK;
+  const ProductShape s = product_shape(pc);
+  const float sigma = static_cast<float>(cc_product_sigma(pc, ebno_db));
+  const size_t chunk = product_chunk_blocks(s.N, blocks), lines = (pc->halves & 1) ? s.w2 : s.w1;
+  Scratch scratch(pc->rows, stream);
+  float *y = nullptr;
+  uint8_t *decided = nullptr, *sent = nullptr, *msg = nullptr;
+  int32_t *status = nullptr;
+  CC_HIP_TRY(scratch.get(&y, chunk * s.N * sizeof(float)));
+  CC_HIP_TRY(scratch.get(&decided, chunk * s.N));
+  CC_HIP_TRY(scratch.get(&status, chunk * lines * sizeof(int32_t)));
+  if (random_codewords) {
+    CC_HIP_TRY(scratch.get(&sent, chunk * s.N));
+    CC_HIP_TRY(scratch.get(&msg, chunk * s.k1 * s.k2));
+  }
+  for (size_t done = 0; done < blocks; done += chunk) {
+    const size_t m = blocks - done < chunk ? blocks - done : chunk;
+    if (random_codewords)
+      if (int rc = product_sent(pc, seed, first_block + done, m, msg, sent, stream)) return rc;
+    if (int rc = launch_awgn_values(pc->rows, static_cast<int>(s.N), sigma, seed, first_block + done, m, y, sent, stream,
+                                    reinterpret_cast<unsigned long long *>(d_counters)))
+      return rc;
+    if (int rc = launch_product_decode(pc, y, decided, nullptr, status, m, stream)) return rc;
+    if (int rc = launch_product_count(pc, decided, sent, status, m, d_counters, stream)) return rc;
+  }
+  return CC_OK;
+}
+
+}  // namespace ccamd

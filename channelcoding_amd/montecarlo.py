@@ -175,6 +175,33 @@ class GmdBackend(DeviceBackend):
         self.leading = (self.m,)
 
 
+class ProductBackend:
+    """Counts one shard of blocks of one Eb/N0 point through cc_mc_run_product_dev: a product_code decoded with len(alpha)
+    half-iterations of the Chase-Pyndiah decoder at p."""
+
+    def __init__(self, pc, p, alpha, beta, random_codewords=False):
+        import torch
+        self.torch = torch
+        self.code = pc
+        self.random_codewords = bool(random_codewords)
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.p = int(p)
+        if not 0 <= self.p <= capi.CHASE_MAX_P:
+            raise ValueError("p in 0 .. %d" % capi.CHASE_MAX_P)
+        if not len(alpha) or len(alpha) != len(beta):
+            raise ValueError("one alpha and one beta per half-iteration, at least one")
+        self.desc = pc._pc(self.p, alpha, beta)
+
+    def run(self, ebno_db, seed, first_block, blocks):
+        torch = self.torch
+        counters = torch.zeros(capi.MC_NCOUNTERS, dtype=torch.int64, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = capi.lib().cc_mc_run_product_dev(C.byref(self.desc), float(ebno_db), int(seed), int(first_block), int(blocks),
+                                              int(self.random_codewords), C.c_void_p(counters.data_ptr()), stream)
+        capi.check(rc, "cc_mc_run_product_dev")
+        return counters
+
+
 class _ShardedSimulation:
     """What the AWGN, the discrete-channel and the burst-channel ladders share: the shard of this rank, the one all-reduce per point,
     rank 0's log file (its success agreed with every rank before the first collective) and the adaptive ladder."""
@@ -306,6 +333,36 @@ class awgn_simulation(_ShardedSimulation):
         if self.gmd is not None:
             suffix = "-gmd%d" % self.gmd
         return self._ladder(self.code.to_string() + suffix + ".log", "ebno", lambda ebno: ebno)
+
+
+class product_simulation(_ShardedSimulation):
+    """The Eb/N0 ladder of a product code (codes.product_code) under the iterative decoder with the schedule alpha, beta
+    (one entry each per half-iteration; there is no default) at p Chase positions.  Frames are blocks: sharded by block,
+    wer is the block error rate, ber counts the n values of a block.  The ladder starts from ladder(pc.rate); the log
+    is <pc.to_string()>-chaseP-hH.log with H = len(alpha)."""
+
+    def __init__(self, pc, p, alpha, beta, step=0.5, seed=0, random_codewords=False, backend=None, log_dir=None,
+                 max_samples=None, start=None, stop=None, samples_per_point=None):
+        self.code = pc
+        self.p, self.halves = int(p), len(alpha)
+        if not self.halves or len(alpha) != len(beta):
+            raise ValueError("one alpha and one beta per half-iteration, at least one")
+        self.step = float(step)
+        self.seed = int(seed)
+        self.backend = backend if backend is not None else ProductBackend(pc, p, alpha, beta, random_codewords)
+        self.log_dir = log_dir
+        self.max_samples = max_samples
+        self.samples_per_point = samples_per_point
+        ref_start, _ = ladder(pc.rate, self.step)
+        self.start = ref_start if start is None else float(start)
+        self.stop = (max(8.0, self.start) + self.step / 2) if stop is None else float(stop)
+
+    points = awgn_simulation.points
+    run_point = awgn_simulation.run_point
+
+    def __call__(self):
+        name = "%s-chase%d-h%d.log" % (self.code.to_string(), self.p, self.halves)
+        return self._ladder(name, "ebno", lambda ebno: ebno)
 
 
 # ---- discrete memoryless channels (cc_mc_run_discrete_dev): the BSC and BEC the reference's README leaves as a TODO --

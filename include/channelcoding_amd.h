@@ -424,6 +424,65 @@ int cc_awgn_symbols_dev(const cc_code *code, double ebno_db, uint64_t seed, uint
 int cc_mc_run_gmd_dev(const cc_code *code, uint32_t trials, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
                       int random_codewords, uint64_t *d_counters, void *stream);
 
+/* ---- product codes (block turbo codes) of two binary BCH codes, decoded iteratively with the Chase-Pyndiah component
+ *      decoder (R. Pyndiah, IEEE Trans. Commun. 46 (8), 1998).  The reference has no such code.
+ *      With e = 1 for an extended product (else 0), w1 = rows.n + e, w2 = cols.n + e and N = w1 * w2, a block is N values
+ *      y[w2][w1]: row i is a word of `rows`, column k a word of `cols`.  k1 = rows.l and k2 = cols.l are the message
+ *      lengths; a message block is msg[k2][k1].
+ *        decode   W starts as +0.0f.  Half-iteration h = 0 .. halves - 1 forms X = y + (alpha[h] * W), a float32 product
+ *                 then a float32 sum, decodes the rows of X (h even) or its columns (h odd) with
+ *                 cc_correct_chase_soft_batch at (p, beta[h]) -- cc_correct_chase_extended_batch when `extended` -- and W
+ *                 becomes the ext of that pass.  out (B*N bytes) and ext (B*N floats) are those of the last
+ *                 half-iteration in the orientation of y; status is B*lines int32 of its component words, lines = w2
+ *                 after a row pass (halves odd) and w1 after a column pass, block by block.  ext == NULL: the last
+ *                 half-iteration runs the hard-output decoder, whose out and status are those of the soft call.
+ *        encode   the k2 message rows are encoded with `rows` (and extended), then all w1 columns with `cols` (and
+ *                 extended): every row and every column of a block is a word of its (extended) code.  extract is the
+ *                 inverse on a code block.
+ *      Refused before a device is asked for, in this order (cc_product_decode and _dev; the other calls check what they
+ *      read of it in the same order):
+ *        1. NULL pc, rows, cols, alpha, beta, y, out or status -> CC_ERR_INVALID_ARGUMENT (cc_mc_run_product_dev: NULL pc
+ *           or counters first)
+ *        2. halves == 0 -> CC_ERR_INVALID_ARGUMENT
+ *        3. what cc_correct_chase_batch refuses short of the device at p for `rows`, then for `cols`, in its order
+ *           (p > min(rows.n, cols.n) included)
+ *        4. the two handles on different devices -> CC_ERR_INVALID_ARGUMENT
+ *        5. an alpha that is not finite, a beta that is negative or not finite -> CC_ERR_INVALID_ARGUMENT
+ *        6. ext or out overlapping y -> CC_ERR_INVALID_ARGUMENT
+ *        7. a CC_DEVICE_NONE handle -> CC_ERR_NO_DEVICE
+ *      B = 0 answers CC_OK.  The encode, extract, sigma and channel calls read rows, cols and extended only. ---- */
+typedef struct cc_product {
+  const cc_code *rows, *cols;  /* handles cc_correct_chase_batch accepts; words of rows along the last axis */
+  int extended;                /* 0: rows.n x cols.n values per block; else (rows.n+1) x (cols.n+1) */
+  uint32_t p;                  /* Chase positions of every component call */
+  uint32_t halves;             /* >= 1; half-iteration h decodes rows (h even) or columns (h odd) */
+  const float *alpha, *beta;   /* halves host floats each */
+} cc_product;
+int cc_product_decode(const cc_product *pc, const float *y /* B*N */, uint8_t *out /* B*N */, float *ext /* B*N or NULL */,
+                      int32_t *status /* B*lines */, size_t B);
+int cc_product_decode_dev(const cc_product *pc, const float *d_y, uint8_t *d_out, float *d_ext /* or NULL */,
+                          int32_t *d_status, size_t B, void *stream);
+int cc_product_encode_batch(const cc_product *pc, const uint8_t *msg /* B*k2*k1 */, uint8_t *cw /* B*N */, size_t B);
+int cc_product_encode_batch_dev(const cc_product *pc, const uint8_t *d_msg, uint8_t *d_cw, size_t B, void *stream);
+int cc_product_extract_batch(const cc_product *pc, const uint8_t *cw /* B*N */, uint8_t *msg /* B*k2*k1 */, size_t B);
+int cc_product_extract_batch_dev(const cc_product *pc, const uint8_t *d_cw, uint8_t *d_msg, size_t B, void *stream);
+/* 1 / sqrt(2 R 10^(ebno/10)) with R = k1 k2 / N; 0 for a pc it cannot read */
+double cc_product_sigma(const cc_product *pc, double ebno_db);
+/* The channel of blocks [first_block, first_block + blocks): value v = i w1 + k of global block g is what cc_awgn_llr_dev
+ * draws for symbol v of frame g at cc_product_sigma -- Philox counter (g_lo, g_hi, v >> 2, 0), the same Box-Muller pairing.
+ * random_codewords: the k1 k2 message bits of block g are those of frame g of a code with l = k1 k2, sent through
+ * cc_product_encode_batch_dev; otherwise the all-zero block.  d_sent (blocks*N bytes) may be NULL. */
+int cc_awgn_product_dev(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
+                        int random_codewords, float *d_y, uint8_t *d_sent /* or NULL */, void *stream);
+/* Monte-Carlo of the product code: by definition the counters equal what cc_awgn_product_dev, cc_product_decode_dev with
+ * ext == NULL and a comparison with the blocks sent would count.  CC_MC_FRAMES counts blocks, CC_MC_BIT_ERRORS wrong bits
+ * among the N, CC_MC_FAILURES blocks with a component word of the last half-iteration whose status is not CC_FRAME_OK,
+ * CC_MC_WORD_ERRORS blocks that are wrong or failed, CC_MC_UNDETECTED blocks that are wrong and not failed,
+ * CC_MC_CHANNEL_BIT_ERRORS the channel's; CC_MC_ITER_SUM and the histogram are not touched.  The counters depend only on
+ * (seed, ebno, pc, the set of global blocks).  Calls on one `rows` handle share its workspace pool: one stream at a time. */
+int cc_mc_run_product_dev(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
+                          int random_codewords, uint64_t *d_counters, void *stream);
+
 /* ---- batched Monte-Carlo over discrete memoryless channels: the BSC and the BEC the reference's README leaves as a
  *      TODO, both at once, and for RS codes the q-ary symmetric and the symbol erasure channel.  A symbol is erased
  *      with probability p_erasure, in error with probability p_error, intact otherwise (both finite, >= 0, sum <= 1).

@@ -652,6 +652,83 @@ public:
   }
 };
 
+// ---- product codes (new; cc_product_*): the product of two primitive_bch objects, decoded iteratively with the
+// Chase-Pyndiah component decoder.  A block is n2 x n1 values (extended: (n2 + 1) x (n1 + 1)) whose rows are words of
+// Rows and whose columns are words of Cols; alpha and beta hold one value each per half-iteration.  Both objects must
+// outlive the product_code. ----
+template <typename Rows, typename Cols> class product_code {
+public:
+  product_code(const Rows &rows, const Cols &cols, bool extended = false)
+      : rows_(rows.c_handle()), cols_(cols.c_handle()), extended_(extended),
+        w1_(Rows::n + (extended ? 1 : 0)), w2_(Cols::n + (extended ? 1 : 0)),
+        k1_(rows.information_symbols()), k2_(cols.information_symbols()) {}
+
+  size_t values() const { return w1_ * w2_; }               // N, per block
+  size_t information_symbols() const { return k1_ * k2_; }  // per block
+  size_t row_length() const { return w1_; }
+  size_t column_length() const { return w2_; }
+  double sigma(double ebno_db) const {
+    const cc_product pc = descriptor(0, nullptr, nullptr, 0);
+    return cc_product_sigma(&pc, ebno_db);
+  }
+
+  // k2 x k1 message bits, row by row -> the code block
+  std::vector<uint8_t> encode(const std::vector<uint8_t> &msg) const {
+    if (msg.size() != information_symbols()) throw std::runtime_error("Source code word has wrong length");
+    return encode_batch(msg.data(), 1);
+  }
+  std::vector<uint8_t> encode_batch(const uint8_t *msg, size_t B) const {
+    std::vector<uint8_t> cw(B * values());
+    const cc_product pc = descriptor(0, nullptr, nullptr, 0);
+    const int rc = cc_product_encode_batch(&pc, msg, cw.data(), B);
+    if (rc == CC_ERR_NOT_IN_FIELD) throw std::runtime_error("Value is not an element of the field.");
+    detail::check(rc, "cc_product_encode_batch");
+    return cw;
+  }
+
+  // One block of channel values: the decided block after alpha.size() half-iterations, and its extrinsic values into
+  // *ext where ext is given.  A failed component word of the last half-iteration does not throw: its status says so in
+  // the batch form.
+  std::vector<uint8_t> correct(const std::vector<float> &y, unsigned p, const std::vector<float> &alpha,
+                               const std::vector<float> &beta, std::vector<float> *ext = nullptr) const {
+    if (y.size() != values()) throw std::runtime_error("Length of received sequence does not match code length");
+    batch_result r = correct_batch(y.data(), 1, p, alpha, beta, ext != nullptr);
+    if (ext) *ext = std::move(r.ext);
+    return std::move(r.words);
+  }
+  // B blocks, block-contiguous: words (B * N), status (B * lines: the component words of the last half-iteration, n2
+  // lines after a row pass, n1 after a column pass) and, with soft = true, ext (B * N)
+  batch_result correct_batch(const float *values_in, size_t B, unsigned p, const std::vector<float> &alpha,
+                             const std::vector<float> &beta, bool soft = true) const {
+    if (alpha.size() != beta.size() || alpha.empty())
+      throw std::runtime_error("product_code: one alpha and one beta per half-iteration, at least one");
+    const cc_product pc = descriptor(p, alpha.data(), beta.data(), static_cast<uint32_t>(alpha.size()));
+    batch_result r;
+    r.words.resize(B * values());
+    if (soft) r.ext.resize(B * values());
+    r.status.resize(B * ((alpha.size() & 1) ? w2_ : w1_));
+    detail::check(cc_product_decode(&pc, values_in, r.words.data(), soft ? r.ext.data() : nullptr, r.status.data(), B),
+                  "cc_product_decode");
+    return r;
+  }
+
+private:
+  cc_product descriptor(unsigned p, const float *alpha, const float *beta, uint32_t halves) const {
+    cc_product pc;
+    pc.rows = rows_;
+    pc.cols = cols_;
+    pc.extended = extended_ ? 1 : 0;
+    pc.p = p;
+    pc.halves = halves;
+    pc.alpha = alpha;
+    pc.beta = beta;
+    return pc;
+  }
+  const cc_code *rows_, *cols_;
+  bool extended_;
+  size_t w1_, w2_, k1_, k2_;
+};
+
 }  // namespace cyclic
 
 // ---- soft_decision.h:220-295: the free functions min_sum<R, U>(H, y, tag) on any parity-check matrix ----
