@@ -22,6 +22,8 @@
  *     void* (NULL = the null stream); they enqueue work and return without
  *     synchronising.  The plain entry points take HOST pointers, copy, run and
  *     synchronise.
+ *   - a buffer needs the natural alignment of its element type and nothing more; nothing outside
+ *     the stated extents is written, and no result depends on memory outside them.
  *   - nothing here falls back to the CPU: without a usable HIP device the
  *     create call fails with CC_ERR_NO_DEVICE.
  */
