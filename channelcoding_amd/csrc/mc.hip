@@ -1074,10 +1074,7 @@ int mc_run_discrete(cc_code *code, double p_error, double p_erasure, uint64_t se
 int mc_discrete(cc_code *code, double p_error, double p_erasure, uint64_t seed, uint64_t first_frame, size_t frames,
                 int random_codewords, uint8_t *d_recv, uint16_t *d_erasures, uint32_t *d_erasure_offsets,
                 uint8_t *d_sent, hipStream_t stream) {
-  if (frames == 0) {
-    if (d_erasure_offsets) CC_HIP_TRY(hipMemsetAsync(d_erasure_offsets, 0, sizeof(uint32_t), stream));
-    return CC_OK;
-  }
+  if (frames == 0) return CC_OK;  // nothing is written, the one word of the offsets included
   const size_t chunk = frames < DISCRETE_CHUNK ? frames : DISCRETE_CHUNK, n = code->tab.n;
   const DiscreteThresholds th = discrete_thresholds(p_error, p_erasure);
   return mc_chunked(code, frames, chunk, chunk, stream, [&](McWorkspace &w, size_t done, size_t m) -> int {
@@ -1507,13 +1504,14 @@ int mc_burst_erasure(cc_code *code, const cc_burst_channel &ch, const cc_burst_d
                      uint64_t first_frame, size_t frames, int random_codewords, uint8_t *d_recv, uint8_t *d_sent,
                      uint8_t *d_state, uint8_t *d_flag, uint16_t *d_erasures, uint32_t *d_erasure_offsets,
                      hipStream_t stream) {
+  if (frames == 0) return CC_OK;  // nothing is written, the one word of the offsets included
   const DetectorThresholds dt = detector_thresholds(det);
-  if ((dt.DB | dt.DG) != 0 && frames != 0)
+  if ((dt.DB | dt.DG) != 0)
     return burst_channel(code, ch, &dt, seed, first_frame, frames, random_codewords, d_recv, d_sent, d_state, d_flag,
                          d_erasures, d_erasure_offsets, stream);
   // nothing flagged: the errors-only channel, an empty list
   if (d_erasure_offsets) CC_HIP_TRY(hipMemsetAsync(d_erasure_offsets, 0, (frames + 1) * sizeof(uint32_t), stream));
-  if (d_flag && frames) CC_HIP_TRY(hipMemsetAsync(d_flag, 0, frames * code->tab.n, stream));
+  if (d_flag) CC_HIP_TRY(hipMemsetAsync(d_flag, 0, frames * code->tab.n, stream));
   return mc_burst(code, ch, seed, first_frame, frames, random_codewords, d_recv, d_sent, d_state, stream);
 }
 

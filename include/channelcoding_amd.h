@@ -397,6 +397,7 @@ enum {
   CC_MC_ITER_HIST = 8,   /* [8 + i] = frames that returned at iteration index i, i <= 55                  */
   CC_MC_NCOUNTERS = 64
 };
+/* d_counters needs 8-byte alignment and nothing more; every Monte-Carlo call below adds to what the slots hold. */
 int cc_mc_run_dev(const cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
                   int random_codewords, uint64_t *d_counters, void *stream);
 /* just the channel: writes y (frames*n floats) and, if not NULL, the transmitted words (frames*n bytes) */
@@ -513,7 +514,9 @@ int cc_mc_run_discrete_dev(const cc_code *code, double p_error, double p_erasure
 /* channel only: d_recv frames*n bytes; d_erasures capacity frames*n (NULL allowed iff p_erasure == 0);
  * d_erasure_offsets frames+1 words (NULL iff d_erasures is NULL): frame f's erased positions, ascending, are
  * d_erasures[off[f] .. off[f+1]); d_sent frames*n or NULL.  The offsets of one call are 32-bit: with an erasure list
- * frames*n must stay below 2^32 (CC_ERR_INVALID_ARGUMENT otherwise; split the call, each part a CSR of its own). */
+ * frames*n must stay below 2^32 (CC_ERR_INVALID_ARGUMENT otherwise; split the call, each part a CSR of its own).
+ * Only the listed entries d_erasures[0 .. off[frames]) are written: the rest of the capacity keeps what it held (the same
+ * holds for cc_burst_erasure_channel_dev).  frames = 0 answers CC_OK and writes nothing, the offsets included. */
 int cc_discrete_channel_dev(const cc_code *code, double p_error, double p_erasure, uint64_t seed,
                             uint64_t first_frame, size_t frames, int random_codewords, uint8_t *d_recv,
                             uint16_t *d_erasures, uint32_t *d_erasure_offsets, uint8_t *d_sent, void *stream);
