@@ -24,6 +24,7 @@ MC_FRAMES, MC_WORD_ERRORS, MC_BIT_ERRORS, MC_FAILURES, MC_UNDETECTED, MC_ITER_SU
 MC_CHANNEL_ERASURES = 7
 MC_ITER_HIST, MC_NCOUNTERS = 8, 64
 CHASE_MAX_P = 6
+OSD_MAX_ORDER = 2
 GMD_ALL = 0
 HARD_ROUTE_WAVE, HARD_ROUTE_CHUNK, HARD_ROUTE_PLANES, HARD_ROUTE_LONG, HARD_ROUTE_WIDE, HARD_ROUTE_TRIALS = range(6)
 
@@ -105,6 +106,9 @@ _SIGNATURES = {
     "cc_correct_chase_soft_batch": (C.c_int, [_VP, _VP, C.c_uint32, C.c_float, _VP, _VP, _VP, _VP, _VP, C.c_size_t]),
     "cc_correct_chase_soft_batch_dev": (C.c_int, [_VP, _VP, C.c_uint32, C.c_float, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "cc_chase_frames_per_wavefront": (C.c_int, [_VP, C.c_uint32, C.c_int]),
+    "cc_correct_osd_batch": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, C.c_size_t]),
+    "cc_correct_osd_batch_dev": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "cc_osd_frames_per_wavefront": (C.c_int, [_VP, C.c_uint32]),
     "cc_correct_chase_extended_batch": (C.c_int, [_VP, _VP, C.c_uint32, C.c_float, _VP, _VP, _VP, _VP, _VP, C.c_size_t]),
     "cc_correct_chase_extended_batch_dev": (C.c_int, [_VP, _VP, C.c_uint32, C.c_float, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "cc_chase_extended_frames_per_wavefront": (C.c_int, [_VP, C.c_uint32, C.c_int]),
@@ -118,6 +122,7 @@ _SIGNATURES = {
     "cc_awgn_llr_dev": (C.c_int, [_VP, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP, _VP, _VP]),
     "cc_sigma": (C.c_double, [_VP, C.c_double]),
     "cc_mc_run_chase_dev": (C.c_int, [_VP, C.c_uint32, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP, _VP]),
+    "cc_mc_run_osd_dev": (C.c_int, [_VP, C.c_uint32, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP, _VP]),
     "cc_awgn_symbols_dev": (C.c_int, [_VP, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP, _VP, _VP, _VP]),
     "cc_mc_run_gmd_dev": (C.c_int, [_VP, C.c_uint32, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP, _VP]),
     "cc_mc_run_discrete_dev": (C.c_int, [_VP, C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP,

@@ -107,6 +107,8 @@ def usage_text():
               "--packed                     bsc: channel, decoder and counts on packed words (hard-decision algorithms).",
               "--chase <p>                  awgn: Chase-II over the p least reliable positions, 0 .. 6 (hard-decision",
               "                             algorithms; the log is <decoder>-chase<p>.log).",
+              "--osd <order>                awgn: ordered-statistics decoding of order 0 .. 2 (hard-decision algorithms;",
+              "                             the log is <decoder>-osd<order>.log). It does not combine with --chase.",
               "--cols-k <num>               product: the column code's k (--k names the row code; default: the row code).",
               "--cols-dmin <num>            product: the column code's dmin (--dmin names the row code's).",
               "--extended                   product: the product of the two extended codes.",
@@ -234,6 +236,7 @@ def main(argv=None):
     ap.add_argument("--p-false-alarm", type=float, default=0.0, help="burst: P(flag | good state)")
     ap.add_argument("--packed", action="store_true", help="bsc: the route on packed words")
     ap.add_argument("--chase", type=int, default=None, help="awgn: Chase-II with p least reliable positions")
+    ap.add_argument("--osd", type=int, default=None, help="awgn: ordered-statistics decoding of this order")
     ap.add_argument("--cols-k", type=int, default=None, help="product: k of the column code")
     ap.add_argument("--cols-dmin", type=int, default=None, help="product: dmin of the column code")
     ap.add_argument("--extended", action="store_true", help="product: the two extended codes")
@@ -261,8 +264,12 @@ def main(argv=None):
         print("--chase <0..6> goes with --simulation awgn", file=sys.stderr)
         print(usage_text())
         return 1
+    if args.osd is not None and (sim != "awgn" or not 0 <= args.osd <= 2 or args.chase is not None):
+        print("--osd <0..2> goes with --simulation awgn and without --chase", file=sys.stderr)
+        print(usage_text())
+        return 1
     chosen = select(args.algorithm, args.k, args.dmin)
-    if args.chase is not None:  # the hard-tag decoders of the registry
+    if args.chase is not None or args.osd is not None:  # the hard-tag decoders of the registry
         chosen = [c for c in chosen if not ALGORITHMS[c[0]]().soft]
     if not chosen:
         print("The selection is empty")
@@ -277,7 +284,7 @@ def main(argv=None):
         t0 = time.perf_counter()
         if sim == "awgn":
             res = awgn_simulation(code, seed=seed, log_dir=args.log_dir, max_samples=args.max_samples,
-                                  chase=args.chase)()
+                                  chase=args.chase, osd=args.osd)()
             frames = sum(r["frames"] for r in res)
         elif sim in ("bsc", "bec"):
             packed = dict(packed=True) if args.packed else {}

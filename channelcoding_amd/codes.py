@@ -843,7 +843,7 @@ class cyclic:
         return self._map("extract", cw, 0, packed, interleave)
 
     def correct_batch(self, b, erasures=None, want_L=False, packed=False, out=None, interleave=None, chase=None, gmd=None,
-                      reliability=None, soft=None, extended=False):
+                      reliability=None, soft=None, extended=False, osd=None):
         """Returns a dict: out (B,n) u8, status (B,) i32, and nerr (hard) or iters [+ L] (soft).
         gmd=m, reliability=r (RS, hard algorithms, q <= 8, 2t <= 32, step = 1): b holds the received symbols, r float32
         reliabilities of the same shape, and the frames are decoded by GMD with m trials (cc_correct_gmd_batch; gmd=True:
@@ -858,12 +858,21 @@ class cyclic:
         chase=p, extended=True[, soft=beta]: the extended code, every word with its overall parity bit appended (see
         extend): b, out and ext have rows of n + 1, position n carrying the parity bit, which enters the metric and
         the soft output (cc_correct_chase_extended_batch).  extended= needs chase=.
+        osd=order (binary BCH, hard algorithms, q <= 8, any t): b holds float32 channel values and is decoded by
+        ordered-statistics decoding of order 0 .. 2 (cc_correct_osd_batch); the dict is that of chase=, status always 0.
+        It combines with nothing chase= is refused with, nor with chase=, gmd=, soft= or extended=.
         packed=True (binary BCH codes, hard algorithms): b and out are uint8 (B, packed_bytes), see pack_bits; out= names
         the buffer the corrected packed words go to (b itself decodes in place).  The long codes (q = 9 .. 15, BM / PGZ,
         t <= 31, no erasures) are decoded from the packed words themselves in calls of device tensors of at least
         CC_AMD_PACKED_LONG_MIN_FRAMES frames, see packed_route.
         interleave=I (hard algorithms): b and out are symbol-interleaved blocks of shape (B / I, n, I), see interleave();
         status, nerr and the erasure lists are per frame f = b I + j, as without it; out= as with packed=True."""
+        if osd is not None:
+            if (erasures is not None or want_L or packed or out is not None or interleave is not None or chase is not None
+                    or gmd is not None or reliability is not None or soft is not None or extended):
+                raise TypeError("osd= does not combine with erasures, want_L, packed=True, out=, interleave=, chase=, gmd=, "
+                                "reliability=, soft= or extended=")
+            return self._osd(b, osd)
         if soft is not None and (chase is None or gmd is not None or reliability is not None):
             raise TypeError("soft= goes with chase= and with nothing else")
         if extended and (chase is None or gmd is not None or reliability is not None):
@@ -933,6 +942,21 @@ class cyclic:
         outs["ext"] = ((B, self.n), np.float32)
         return self._batch_call("cc_correct_chase_soft_batch", [y], B, outs, ("nerr", "metric", "status"), (p, beta))
 
+    def _osd(self, b, order):
+        """correct_batch(osd=order): float32 channel values, host array or device tensor."""
+        order = int(order)
+        if order < 0:
+            raise ValueError("osd= takes order >= 0")
+        if b.shape[-1] != self.n:
+            raise CcError(capi.ERR_LENGTH, "correct_batch")
+        side = _side(b)
+        y = side.as_type(b, "f", np.float32)
+        if y is None:
+            raise TypeError("osd= takes float32 channel values")
+        B = side.size(y) // self.n
+        return self._batch_call("cc_correct_osd_batch", [y], B, {"out": ((B, self.n), np.uint8)},
+                                ("nerr", "metric", "status"), (order,))
+
     def _gmd(self, b, rel, m):
         """correct_batch(gmd=m, reliability=rel): uint8 symbols and float32 reliabilities, host arrays or device tensors."""
         m = capi.gmd_trials(m)
@@ -950,16 +974,17 @@ class cyclic:
                                 ("nerr", "metric", "status"), (m,))
 
     def decode_batch(self, b, erasures=None, packed=False, interleave=None, chase=None, gmd=None, reliability=None,
-                     soft=None, extended=False):
+                     soft=None, extended=False, osd=None):
         """decode = correct + message extraction (cyclic.h:313-327); host arrays go through cc_decode_*_batch.
         chase=p[, soft=beta]: correct_batch(b, chase=p[, soft=beta]), then the messages of its words.
         chase=p, extended=True[, soft=beta]: the same on extended words; msg comes from their inner n columns.
         gmd=m, reliability=r: correct_batch(b, gmd=m, reliability=r), then the messages of its words.
+        osd=order: correct_batch(b, osd=order), then the messages of its words.
         packed=True: b, out and msg are packed uint8 words, see pack_bits.
         interleave=I: b and out are blocks of shape (B / I, n, I), msg (B / I, l, I), see interleave()."""
-        if chase is not None or gmd is not None or reliability is not None or soft is not None or extended:
+        if chase is not None or gmd is not None or reliability is not None or soft is not None or extended or osd is not None:
             res = self.correct_batch(b, erasures, packed=packed, interleave=interleave, chase=chase, gmd=gmd,
-                                     reliability=reliability, soft=soft, extended=extended)
+                                     reliability=reliability, soft=soft, extended=extended, osd=osd)
             res["msg"] = self.extract_batch(unextend(res["out"]) if extended else res["out"])
             return res
         if interleave is not None and packed:

@@ -462,6 +462,11 @@ static int code_create_impl(const cc_desc *desc, const uint8_t *customH, uint32_
     CC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&code->d_parity), pt.size()));
     CC_HIP_TRY(hipMemcpy(code->d_parity, pt.data(), pt.size(), hipMemcpyHostToDevice));
   }
+  if (t.family == CC_FAMILY_BCH && !code->soft) {  // cc_correct_osd_batch: the systematic H, rows of 256 bits
+    const std::vector<unsigned long long> rows = build_osd_rows(t);
+    CC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&code->d_osd_rows), rows.size() * sizeof(unsigned long long)));
+    CC_HIP_TRY(hipMemcpy(code->d_osd_rows, rows.data(), rows.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+  }
 
   *out = code.release();
   return CC_OK;
@@ -522,6 +527,7 @@ void cc_code_destroy(cc_code *code) {
     if (code->d_diag) (void)hipFree(code->d_diag);
     if (code->d_colbits) (void)hipFree(code->d_colbits);
     if (code->d_parity) (void)hipFree(code->d_parity);
+    if (code->d_osd_rows) (void)hipFree(code->d_osd_rows);
     if (code->mc) mc_workspace_free(code->mc);
     if (code->stage) host_stage_free(code->stage);
     if (code->d_wide) (void)hipFree(code->d_wide);
@@ -853,6 +859,50 @@ int cc_chase_frames_per_wavefront(const cc_code *code, uint32_t p, int soft) {
   if (!code) return 0;
   const int rc = chase_supported(code, p);
   return rc == CC_OK || rc == CC_ERR_NO_DEVICE ? chase_frames_per_wave(code, p, soft != 0) : 0;
+}
+
+// What the OSD calls refuse, in the order the header states, all of it before a device is asked for (no 2t <= 32 limit:
+// there is no algebraic decoder behind them).
+static int osd_supported(const cc_code *code, uint32_t order) {
+  if (int rc = needs_code(code)) return rc;
+  if (code->tab.family != CC_FAMILY_BCH)
+    return unsupported("ordered-statistics decoding serves binary BCH codes: this is a Reed-Solomon handle");
+  if (code->soft)
+    return unsupported("ordered-statistics decoding needs a hard-decision tag (PGZ, BM or Euklid): this is a min-sum handle");
+  if (code->wide) return unsupported("ordered-statistics decoding serves GF(2^q) with q <= 8");
+  if (order > CC_OSD_MAX_ORDER) return unsupported("ordered-statistics decoding: order exceeds CC_OSD_MAX_ORDER");
+  return code->device == CC_DEVICE_NONE ? CC_ERR_NO_DEVICE : CC_OK;
+}
+
+int cc_correct_osd_batch_dev(const cc_code *code, const float *d_llr, uint32_t order, uint8_t *d_out, int32_t *d_nerr,
+                             float *d_metric, int32_t *d_status, size_t B, void *stream) {
+  if (!code || (B && (!d_llr || !d_out))) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = osd_supported(code, order)) return rc;
+  DeviceGuard guard(code->device);
+  return launch_osd(code, d_llr, order, d_out, d_nerr, d_metric, d_status, B, static_cast<hipStream_t>(stream));
+}
+
+int cc_correct_osd_batch(const cc_code *code, const float *llr, uint32_t order, uint8_t *out, int32_t *nerr, float *metric,
+                         int32_t *status, size_t B) {
+  if (!code || (B && (!llr || !out))) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = osd_supported(code, order)) return rc;
+  if (B == 0) return CC_OK;
+  const size_t n = code->tab.n;
+  DeviceGuard guard(code->device);
+  const StagedStream streams[] = {stage_in(0, llr, n * sizeof(float)), stage_out(1, out, n), stage_out(2, nerr, sizeof(int32_t)),
+                                  stage_out(3, status, sizeof(int32_t)), stage_out(4, metric, sizeof(float))};
+  return staged_call(code, B, n * sizeof(float), 1, streams, 5, nullptr, nullptr,
+                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t s) {
+                       return launch_osd(code, static_cast<const float *>(d[0]), order, static_cast<uint8_t *>(d[1]),
+                                         static_cast<int32_t *>(d[2]), static_cast<float *>(d[4]),
+                                         static_cast<int32_t *>(d[3]), m, s);
+                     });
+}
+
+int cc_osd_frames_per_wavefront(const cc_code *code, uint32_t order) {
+  if (!code) return 0;
+  const int rc = osd_supported(code, order);
+  return rc == CC_OK || rc == CC_ERR_NO_DEVICE ? osd_frames_per_wave(code) : 0;
 }
 
 // What the extended calls refuse, in the order the header states: what the Chase calls refuse short of the device, with
@@ -1520,6 +1570,17 @@ int cc_mc_run_chase_dev(const cc_code *code, uint32_t p, double ebno_db, uint64_
   DeviceGuard guard(code->device);
   return mc_run_chase(const_cast<cc_code *>(code), p, ebno_db, seed, first_frame, frames, random_codewords, d_counters,
                       static_cast<hipStream_t>(stream));
+}
+
+int cc_mc_run_osd_dev(const cc_code *code, uint32_t order, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
+                      int random_codewords, uint64_t *d_counters, void *stream) {
+  if (!code || !d_counters) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = osd_supported(code, order)) return rc;
+  if (random_codewords && code->desc.coding != CC_CODING_DIVISION && code->desc.coding != CC_CODING_MULTIPLICATION)
+    return CC_ERR_INVALID_ARGUMENT;
+  DeviceGuard guard(code->device);
+  return mc_run_osd(const_cast<cc_code *>(code), order, ebno_db, seed, first_frame, frames, random_codewords, d_counters,
+                    static_cast<hipStream_t>(stream));
 }
 
 int cc_mc_run_gmd_dev(const cc_code *code, uint32_t trials, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,

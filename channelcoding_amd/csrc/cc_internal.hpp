@@ -138,6 +138,8 @@ struct cc_code {
   // columns), h_alg / wide_dev carry n = N next to the field order nf, and every kernel runs on frames of N symbols;
   // min-sum runs over H[:, :N] (custom_H).  `shortened` is what tells it apart from a full-length code.
   bool shortened = false;
+  // osd.hip: the systematic parity-check matrix, u64 [k][4] (binary BCH with a hard tag, q <= 8; else nullptr)
+  unsigned long long *d_osd_rows = nullptr;
 };
 
 namespace ccamd {
@@ -215,6 +217,12 @@ int launch_chase_soft(const cc_code *code, const float *d_llr, unsigned p, float
 // overall parity bit; d_ext == nullptr runs the hard-output kernel and beta is not read
 int launch_chase_extended(const cc_code *code, const float *d_llr, unsigned p, float beta, uint8_t *d_out, float *d_ext,
                           int32_t *d_nerr, float *d_metric, int32_t *d_status, size_t B, hipStream_t stream);
+// osd.hip: ordered-statistics decoding over float channel values, binary BCH with q <= 8, order <= CC_OSD_MAX_ORDER
+// (DESIGN 4.16); d_nerr, d_metric and d_status may be nullptr
+int launch_osd(const cc_code *code, const float *d_llr, unsigned order, uint8_t *d_out, int32_t *d_nerr, float *d_metric,
+               int32_t *d_status, size_t B, hipStream_t stream);
+int osd_frames_per_wave(const cc_code *code);  // frames per wavefront of launch_osd
+std::vector<unsigned long long> build_osd_rows(const CodeTables &t);  // what d_osd_rows holds
 // gmd.hip: GMD over received symbols and reliabilities, RS with q <= 8, 2t <= 32, step = 1, 1 <= m <= t + 1 trials
 // (DESIGN 4.12); d_nerr, d_metric and d_status may be nullptr, d_out may be d_words
 int launch_gmd(const cc_code *code, const uint8_t *d_words, const float *d_rel, unsigned m, uint8_t *d_out, int32_t *d_nerr,
@@ -316,6 +324,8 @@ int mc_run(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, s
            uint64_t *d_counters, hipStream_t stream);
 int mc_run_chase(cc_code *code, unsigned p, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
                  int random_codewords, uint64_t *d_counters, hipStream_t stream);
+int mc_run_osd(cc_code *code, unsigned order, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
+               int random_codewords, uint64_t *d_counters, hipStream_t stream);
 int mc_run_gmd(cc_code *code, unsigned m, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
                int random_codewords, uint64_t *d_counters, hipStream_t stream);
 int mc_awgn_symbols(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,

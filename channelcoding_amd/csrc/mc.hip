@@ -604,6 +604,20 @@ int mc_run_chase(cc_code *code, unsigned p, double ebno_db, uint64_t seed, uint6
   });
 }
 
+// cc_mc_run_osd_dev: the same with launch_osd at `order` (every frame decodes: CC_MC_FAILURES stays 0).  Checked by the
+// caller: a binary BCH handle with a hard tag that launch_osd serves.
+int mc_run_osd(cc_code *code, unsigned order, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
+               int random_codewords, uint64_t *d_counters, hipStream_t stream) {
+  if (frames == 0) return CC_OK;
+  const size_t chunk = frames < MC_CHUNK ? frames : MC_CHUNK;
+  unsigned long long *counters = reinterpret_cast<unsigned long long *>(d_counters);
+  return mc_chunked(code, frames, chunk, chunk, stream, [&](McWorkspace &w, size_t done, size_t m) -> int {
+    return mc_route(code, w, seed, first_frame + done, m, random_codewords, d_counters, stream, [&](const uint8_t *sent) {
+      return launch_awgn(code, ebno_db, seed, first_frame + done, m, w.llr, sent, stream, counters);
+    }, [&] { return launch_osd(code, w.llr, order, w.hard, w.nerr, nullptr, w.status, m, stream); });
+  });
+}
+
 // cc_awgn_llr_dev: channel only
 int mc_awgn(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
             float *d_llr, uint8_t *d_sent, hipStream_t stream) {

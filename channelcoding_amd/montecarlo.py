@@ -163,6 +163,20 @@ class ChaseBackend(DeviceBackend):
         self.leading = (self.p,)
 
 
+class OsdBackend(DeviceBackend):
+    """The same shard through cc_mc_run_osd_dev: ordered-statistics decoding of the given order on every frame (binary
+    BCH with a hard tag, q <= 8); every frame decodes, so the failure counter stays 0."""
+
+    symbol = "cc_mc_run_osd_dev"
+
+    def __init__(self, code, order, random_codewords=False):
+        super().__init__(code, random_codewords)
+        self.order = int(order)
+        if not 0 <= self.order <= capi.OSD_MAX_ORDER:
+            raise ValueError("osd= takes an order in 0 .. %d" % capi.OSD_MAX_ORDER)
+        self.leading = (self.order,)
+
+
 class GmdBackend(DeviceBackend):
     """The same shard through cc_mc_run_gmd_dev: BPSK/AWGN per symbol bit, then GMD with m trials on every frame (RS with
     a hard tag, q <= 8, 2t <= 32, step = 1; m = True: all t + 1)."""
@@ -289,7 +303,7 @@ class awgn_simulation(_ShardedSimulation):
     """awgn_simulation(decoder, step = 0.5, seed = 0) -- simulation.h:71-83."""
 
     def __init__(self, code, step=0.5, seed=0, random_codewords=False, backend=None, log_dir=None,
-                 max_samples=None, start=None, stop=None, samples_per_point=None, chase=None, gmd=None):
+                 max_samples=None, start=None, stop=None, samples_per_point=None, chase=None, gmd=None, osd=None):
         self.code = code
         self.step = float(step)
         self.seed = int(seed)
@@ -298,10 +312,16 @@ class awgn_simulation(_ShardedSimulation):
         # gmd=m (RS): every frame goes through GMD with m trials (GmdBackend, True: all of them); the log name carries -gmdM
         if gmd is not None and chase is not None:
             raise TypeError("gmd= does not combine with chase=")
+        # osd=order: every frame goes through ordered-statistics decoding (OsdBackend); the log name carries -osdO
+        if osd is not None and (chase is not None or gmd is not None):
+            raise TypeError("osd= does not combine with chase= or gmd=")
+        self.osd = None if osd is None else int(osd)
         self.gmd = None if gmd is None else (int(code.t) + 1 if gmd is True else int(gmd))
         if backend is None:
             if gmd is not None:
                 backend = GmdBackend(code, gmd, random_codewords)
+            elif osd is not None:
+                backend = OsdBackend(code, osd, random_codewords)
             else:
                 backend = DeviceBackend(code, random_codewords) if chase is None else ChaseBackend(code, chase, random_codewords)
         self.backend = backend
@@ -332,6 +352,8 @@ class awgn_simulation(_ShardedSimulation):
         suffix = "" if self.chase is None else "-chase%d" % self.chase
         if self.gmd is not None:
             suffix = "-gmd%d" % self.gmd
+        if self.osd is not None:
+            suffix = "-osd%d" % self.osd
         return self._ladder(self.code.to_string() + suffix + ".log", "ebno", lambda ebno: ebno)
 
 

@@ -285,6 +285,43 @@ int cc_correct_chase_soft_batch_dev(const cc_code *code, const float *d_llr, uin
  * that place batch sizes next to it; 0 for a call the decoder refuses.  Needs no device. */
 int cc_chase_frames_per_wavefront(const cc_code *code, uint32_t p, int soft);
 
+/* ---- Ordered-statistics decoding of order 0 .. 2 for binary BCH codes (M. Fossorier, S. Lin, "Soft-decision decoding
+ *      of linear block codes based on ordered statistics", IEEE Trans. Inf. Theory 41 (5), 1995).  The reference has no
+ *      such decoder: it takes the input of cyclic::correct_(soft_decision_tag), cyclic.h:254-267, and needs no algebraic
+ *      decoder, so it always returns a codeword and has no 2t <= 32 limit.
+ *      Handles: BCH with a hard tag (the tag does not influence the result), q = 3..8, any t the handle can be created
+ *      with, full length or shortened; order = 0 .. CC_OSD_MAX_ORDER.  A frame is n finite floats y (NaN: unspecified;
+ *      zeros, denormals, equal magnitudes and magnitudes near FLT_MAX are ordinary inputs).  l = message symbols.
+ *        hard decision  z_i = (y_i < 0) and key_i = bits(y_i) & 0x7fffffff compared as unsigned: those of
+ *                       cc_correct_chase_batch
+ *        order          of positions: descending key, ties to the lower position: pi_0 (most reliable) .. pi_(n-1)
+ *        basis          walk pi_0, pi_1, ..: pi_j joins the basis iff, among the words of the code (the shortened code
+ *                       for a shortened handle), it is not determined by the positions already chosen -- its column of
+ *                       any generator matrix is independent of theirs; stop after l positions: B_0 .. B_(l-1) in the
+ *                       order chosen.  A property of the code, not of a particular generator matrix
+ *        test patterns  j = 0 flips nothing; j = 1 + a, a in [0, l), flips B_a (order >= 1); j = 1 + l + rank(a, b),
+ *                       a < b < l ranked lexicographically, flips B_a and B_b (order = 2; l = 1 has no pairs)
+ *        candidate      of pattern j: the unique codeword that equals z on the basis positions outside the flip set and
+ *                       the complement of z on those inside it.  Every pattern has one
+ *        metric         M(c) = float32 sum of |y_i| over the positions with c_i != z_i, from +0.0f in ascending i, no
+ *                       fused or reassociated operation: cc_correct_chase_batch's, word for word
+ *        winner         the candidate with the smallest M, equal M to the smallest j
+ *      Per frame: out = the winner (n bytes), nerr = positions where out differs from z (never -1), metric = M of the
+ *      winner, status = CC_FRAME_OK always.  nerr, metric and status may be NULL.
+ *      Refused before a device is asked for, in this order: NULL code / llr / out -> CC_ERR_INVALID_ARGUMENT; a
+ *      cc_minsum_create handle -> CC_ERR_INVALID_ARGUMENT; an RS handle, a min-sum handle, q > 8,
+ *      order > CC_OSD_MAX_ORDER -> CC_ERR_UNSUPPORTED with cc_last_error naming which; then a CC_DEVICE_NONE handle
+ *      answers CC_ERR_NO_DEVICE.  B = 0 answers CC_OK after these checks.  No order >= 3, no early termination, no soft
+ *      output, no extended codes, no erasures, no bit-per-bit or woven containers. ---- */
+#define CC_OSD_MAX_ORDER 2
+int cc_correct_osd_batch(const cc_code *code, const float *llr /* B*n */, uint32_t order, uint8_t *out /* B*n */,
+                         int32_t *nerr, float *metric, int32_t *status, size_t B);
+int cc_correct_osd_batch_dev(const cc_code *code, const float *d_llr, uint32_t order, uint8_t *d_out, int32_t *d_nerr,
+                             float *d_metric, int32_t *d_status, size_t B, void *stream);
+/* How many frames one wavefront of cc_correct_osd_batch decodes side by side (1: a wavefront owns one frame at a time);
+ * 0 for a call the decoder refuses.  Needs no device. */
+int cc_osd_frames_per_wavefront(const cc_code *code, uint32_t order);
+
 /* ---- Chase-II and Chase-Pyndiah decoding of extended BCH codes: the handle's code with one overall parity bit, the
  *      component code of the usual product codes, e.g. eBCH(64,51) from BCH(63,51).  The reference has no such decoder.
  *      A handle is any handle that cc_correct_chase_batch accepts (binary BCH, hard tag, q <= 8, 2t <= 32, full length
@@ -411,6 +448,13 @@ double cc_sigma(const cc_code *code, double ebno_db); /* simulation.c++:83-85 */
  * set of global frames). */
 int cc_mc_run_chase_dev(const cc_code *code, uint32_t p, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
                         int random_codewords, uint64_t *d_counters, void *stream);
+/* cc_mc_run_dev with the decoder swapped for cc_correct_osd_batch_dev at `order`: the same handles and refusals as that
+ * call (NULL code / counters first).  The counter slots are cc_mc_run_dev's; every frame decodes, so CC_MC_FAILURES stays
+ * 0, and CC_MC_ITER_SUM and the histogram are not touched.  By definition the counters equal what cc_awgn_llr_dev followed
+ * by cc_correct_osd_batch_dev and a comparison with the words sent would count, and depend only on (seed, ebno, order,
+ * the set of global frames). */
+int cc_mc_run_osd_dev(const cc_code *code, uint32_t order, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
+                      int random_codewords, uint64_t *d_counters, void *stream);
 /* BPSK/AWGN for the symbols of an RS code, handles and refusals as cc_correct_gmd_batch_dev.  Bit b of symbol i is value
  * v = i q + b of a frame of n q channel values and is drawn exactly as cc_awgn_llr_dev draws value v of a frame: Philox
  * counter (gf_lo, gf_hi, v >> 2, 0), the same Box-Muller pairing, y = (1 - 2 bit) + sigma z, sigma = cc_sigma(code, ebno).

@@ -551,6 +551,29 @@ public:
     return r;
   }
 
+  // ---- ordered-statistics decoding (new; cc_correct_osd_batch): the most reliable independent positions of y are
+  // re-encoded, as they are and with every flip set of at most `order` of them, the candidate nearest to y returned.
+  // Hard tags, q <= 8, any t, order <= CC_OSD_MAX_ORDER; every frame decodes to a codeword, so nothing is thrown for one ----
+  std::vector<uint8_t> correct_osd(const std::vector<float> &y, unsigned order) const {
+    if (y.size() != N) throw std::runtime_error("Length of received sequence does not match code length");
+    std::vector<uint8_t> out(N);
+    detail::check(cc_correct_osd_batch(this->handle.get(), y.data(), order, out.data(), nullptr, nullptr, nullptr, 1),
+                  "cc_correct_osd_batch");
+    return out;
+  }
+  // B frames of n values, frame-contiguous: words, nerr, status (CC_FRAME_OK) and metric of every frame
+  batch_result correct_osd_batch(const float *values, size_t B, unsigned order) const {
+    batch_result r;
+    r.words.resize(B * N);
+    r.status.resize(B);
+    r.nerr.resize(B);
+    r.metric.resize(B);
+    detail::check(cc_correct_osd_batch(this->handle.get(), values, order, r.words.data(), r.nerr.data(), r.metric.data(),
+                                       r.status.data(), B),
+                  "cc_correct_osd_batch");
+    return r;
+  }
+
   // ---- Chase-Pyndiah soft output (new; cc_correct_chase_soft_batch): correct_chase, and per bit the extrinsic value
   // ext_i = s_i (K_i - M_D) - y_i against the nearest candidate that disagrees with the decision at i, s_i beta where
   // there is none (s_i = +1 for bit 0); beta finite and >= 0.  Throws decoding_failure when no pattern has a candidate ----
