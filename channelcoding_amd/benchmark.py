@@ -32,14 +32,17 @@ erasure; the default, 0 and 0, is errors-only decoding.
 (montecarlo.product_simulation): --k and --dmin (one value each, k = 3 .. 8) name the row code, --cols-k and --cols-dmin the
 column code (default: the row code), --extended takes the two extended codes, --chase P the Chase positions (default 4),
 and --alpha a,b,... and --beta a,b,... give the schedule, one value each per half-iteration.  There is no default
-schedule.  The log is "<rows>x<cols>[-ext]-chaseP-hH.log".
+schedule.  The log is "<rows>x<cols>[-ext]-chaseP-hH.log".  With --halves H in place of --alpha / --beta the ladder runs
+H half-iterations of hard-decision row / column decoding (montecarlo.product_hard_simulation) and the log is
+"<rows>x<cols>[-ext]-hard-hH.log", with the mean of the half-iterations a block took next to wer.
 """
 import argparse
 import sys
 import time
 
 from . import codes as cc
-from .montecarlo import awgn_simulation, bitflip_simulation, burst_simulation, discrete_simulation, product_simulation
+from .montecarlo import (awgn_simulation, bitflip_simulation, burst_simulation, discrete_simulation, product_hard_simulation,
+                         product_simulation)
 
 POWERS = (5, 6, 7)
 DISTANCES = (3, 5, 7, 9)
@@ -114,6 +117,8 @@ def usage_text():
               "--extended                   product: the product of the two extended codes.",
               "--alpha <a,b,...>            product: the factor of W of every half-iteration. There is no default.",
               "--beta <a,b,...>             product: the value of a position without a competitor, per half-iteration.",
+              "--halves <num>               product: hard-decision row / column decoding with that many half-iterations,",
+              "                             in place of --alpha and --beta.",
               "--max-samples <num>          awgn / bsc / bec / burst / product: cap on the frames of one point.",
               "",
               "algorithm, k, and dmin can be specified multiple times.",
@@ -188,6 +193,25 @@ def product_arguments(args):
     return rows, cols, p, alpha, beta
 
 
+def product_hard_arguments(args):
+    """(rows (k, dmin), cols (k, dmin), halves) of --simulation product --halves H, or a message saying what is wrong"""
+    if args.alpha is not None or args.beta is not None:
+        return "--halves runs the hard-decision decoder: it does not combine with --alpha or --beta"
+    if args.halves < 1:
+        return "--halves <1..>"
+    try:
+        if not args.k or len(args.k) != 1 or not args.dmin or len(args.dmin) != 1:
+            return "--simulation product takes one --k and one --dmin"
+        rows = (int(args.k[0]), int(args.dmin[0]))
+    except ValueError:
+        return "--k and --dmin take numbers"
+    cols = (rows[0] if args.cols_k is None else args.cols_k, rows[1] if args.cols_dmin is None else args.cols_dmin)
+    for k, d in (rows, cols):
+        if not 3 <= k <= 8 or d < 3 or d % 2 == 0:
+            return "--simulation product takes k = 3 .. 8 and an odd dmin >= 3"
+    return rows, cols, args.halves
+
+
 def build_product(rows, cols, extended, device=None):
     kw = {} if device is None else {"device": device}
     make = lambda k, d: cc.primitive_bch(k, cc.dmin(d), cc.berlekamp_massey_tag(), **kw)
@@ -195,17 +219,21 @@ def build_product(rows, cols, extended, device=None):
 
 
 def product_main(args):
-    parsed = product_arguments(args)
+    hard = getattr(args, "halves", None) is not None
+    parsed = product_hard_arguments(args) if hard else product_arguments(args)
     if isinstance(parsed, str):
         print(parsed, file=sys.stderr)
         print(usage_text())
         return 1
-    rows, cols, p, alpha, beta = parsed
     seed = time.time_ns() if args.seed_time else args.seed
     dist = join_ranks()
-    pc = build_product(rows, cols, args.extended)
+    pc = build_product(parsed[0], parsed[1], args.extended)
     t0 = time.perf_counter()
-    res = product_simulation(pc, p, alpha, beta, seed=seed, log_dir=args.log_dir, max_samples=args.max_samples)()
+    if hard:
+        res = product_hard_simulation(pc, parsed[2], seed=seed, log_dir=args.log_dir, max_samples=args.max_samples)()
+    else:
+        rows, cols, p, alpha, beta = parsed
+        res = product_simulation(pc, p, alpha, beta, seed=seed, log_dir=args.log_dir, max_samples=args.max_samples)()
     if not dist or dist.get_rank() == 0:
         print("%s: %d blocks in %.2f s" % (pc.to_string(), sum(r["frames"] for r in res), time.perf_counter() - t0), flush=True)
     if dist:
@@ -242,6 +270,7 @@ def main(argv=None):
     ap.add_argument("--extended", action="store_true", help="product: the two extended codes")
     ap.add_argument("--alpha", default=None, help="product: a,b,... one per half-iteration")
     ap.add_argument("--beta", default=None, help="product: a,b,... one per half-iteration")
+    ap.add_argument("--halves", type=int, default=None, help="product: hard-decision decoding, this many half-iterations")
     ap.add_argument("--help", "-h", action="store_true")
     args, unknown = ap.parse_known_args(argv)
     if args.help or unknown:

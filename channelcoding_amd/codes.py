@@ -1158,6 +1158,34 @@ class product_code:
         res["msg"] = self.extract_batch(res["out"])
         return {k: res[k] for k in _KEYS if k in res}
 
+    def _pc_hard(self, halves):
+        """the cc_product of the hard-decision calls: they read rows, cols, extended and halves alone"""
+        halves = int(halves)
+        if halves < 1:
+            raise ValueError("halves >= 1")
+        pc = capi.Product(self.rows._h, self.cols._h, int(self.extended), 0, halves, None, None)
+        pc._keep = (self.rows, self.cols)
+        return pc
+
+    def correct_hard_batch(self, z, halves):
+        """cc_product_decode_hard: z (B, n2, n1) uint8 hard decisions -> dict(out=, nflip=, last=, status=) after
+        `halves` half-iterations of bounded-distance row / column decoding; numpy array or device tensor."""
+        pc = self._pc_hard(halves)
+        z = self._bytes(z, (self.n2, self.n1), "correct_hard_batch")
+        B = z.shape[0]
+        side = _side(z)
+        res = {"out": side.alloc(z, (B, self.n2, self.n1), np.uint8)}
+        for k in ("nflip", "last", "status"):
+            res[k] = side.alloc(z, (B,), np.int32)
+        cyclic._batch_call(_product_handle(pc), "cc_product_decode_hard", [z], B, res)
+        return res
+
+    def decode_hard_batch(self, z, halves):
+        """correct_hard_batch plus msg (B, k2, k1): the message bits of out"""
+        res = self.correct_hard_batch(z, halves)
+        res["msg"] = self.extract_batch(res["out"])
+        return res
+
     def channel(self, ebno_db, seed, first_block, blocks, random_codewords=False):
         """Blocks [first_block, first_block + blocks) of the AWGN channel on the current device (cc_awgn_product_dev):
         dict(y=(blocks, n2, n1) float32, sent=(blocks, n2, n1) uint8) of torch tensors."""

@@ -319,6 +319,38 @@ int product_awgn(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t f
                  int random_codewords, float *d_y, uint8_t *d_sent, hipStream_t stream);
 int mc_run_product(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
                    int random_codewords, uint64_t *d_counters, hipStream_t stream);
+// blocks per chunk of the product Monte-Carlo and channel routes, and the blocks sent for the global blocks
+// [first, first + m) (d_msg: m k1 k2 bytes of scratch)
+size_t product_chunk_blocks(size_t N, size_t blocks);
+int product_sent(const cc_product *pc, uint64_t seed, uint64_t first, size_t m, uint8_t *d_msg, uint8_t *d_sent,
+                 hipStream_t stream);
+// stream-ordered scratch of one product call, returned to the pool of `code` on every way out
+struct WorkspaceScratch {
+  const cc_code *code;
+  hipStream_t stream;
+  void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  int used = 0;
+  WorkspaceScratch(const cc_code *c, hipStream_t s) : code(c), stream(s) {}
+  WorkspaceScratch(const WorkspaceScratch &) = delete;
+  WorkspaceScratch &operator=(const WorkspaceScratch &) = delete;
+  ~WorkspaceScratch() {
+    for (int i = 0; i < used; ++i)
+      if (p[i]) (void)hipFreeAsync(p[i], stream);
+  }
+  template <class T>
+  hipError_t get(T **out, size_t bytes) {
+    const hipError_t e = workspace_alloc(code, &p[used], bytes ? bytes : 1, stream);
+    *out = static_cast<T *>(p[used]);
+    if (e == hipSuccess) ++used;
+    return e;
+  }
+};
+// product_hard.hip: iterated bounded-distance decoding on hard decisions; pc checked by the caller
+// (cc_product_decode_hard_dev).  d_out may be d_in; d_nflip, d_last and d_status (one per block) may be nullptr
+int launch_product_hard(const cc_product *pc, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip, int32_t *d_last,
+                        int32_t *d_status, size_t B, hipStream_t stream);
+int mc_run_product_hard(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
+                        int random_codewords, uint64_t *d_counters, hipStream_t stream);
 // mc.hip (Monte-Carlo calls on one handle must be issued on one stream at a time: they share a workspace)
 int mc_run(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
            uint64_t *d_counters, hipStream_t stream);

@@ -182,26 +182,6 @@ int turn_bytes(const uint8_t *in, uint8_t *out, size_t blocks, size_t R, size_t 
   return launch_interleave(in, 1, C, R, out, blocks * R, true, stream);
 }
 
-// stream-ordered scratch of one call, returned to the pool on every way out
-struct Scratch {
-  const cc_code *code;
-  hipStream_t stream;
-  void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  int used = 0;
-  Scratch(const cc_code *c, hipStream_t s) : code(c), stream(s) {}
-  ~Scratch() {
-    for (int i = 0; i < used; ++i)
-      if (p[i]) (void)hipFreeAsync(p[i], stream);
-  }
-  template <class T>
-  hipError_t get(T **out, size_t bytes) {
-    const hipError_t e = workspace_alloc(code, &p[used], bytes ? bytes : 1, stream);
-    *out = static_cast<T *>(p[used]);
-    if (e == hipSuccess) ++used;
-    return e;
-  }
-};
-
 }  // namespace
 
 ProductShape product_shape(const cc_product *pc) {
@@ -224,7 +204,7 @@ int launch_product_decode(const cc_product *pc, const float *d_y, uint8_t *d_out
   const int w1 = static_cast<int>(s.w1), w2 = static_cast<int>(s.w2);
   const size_t total = B * s.N;
   const unsigned halves = pc->halves;
-  Scratch scratch(rows, stream);
+  WorkspaceScratch scratch(rows, stream);
   float *X = nullptr, *W = nullptr;
   uint8_t *O = nullptr;
   CC_HIP_TRY(scratch.get(&X, total * sizeof(float)));
@@ -262,7 +242,7 @@ int launch_product_encode(const cc_product *pc, const uint8_t *d_msg, uint8_t *d
   const cc_code *rows = pc->rows, *cols = pc->cols;
   const ProductShape s = product_shape(pc);
   const size_t n1 = rows->tab.n, n2 = cols->tab.n;
-  Scratch scratch(rows, stream);
+  WorkspaceScratch scratch(rows, stream);
   uint8_t *a = nullptr, *b = nullptr;
   CC_HIP_TRY(scratch.get(&a, B * s.N));
   CC_HIP_TRY(scratch.get(&b, B * s.N));
@@ -282,7 +262,7 @@ int launch_product_extract(const cc_product *pc, const uint8_t *d_cw, uint8_t *d
   const cc_code *rows = pc->rows, *cols = pc->cols;
   const ProductShape s = product_shape(pc);
   const size_t n1 = rows->tab.n, n2 = cols->tab.n;
-  Scratch scratch(rows, stream);
+  WorkspaceScratch scratch(rows, stream);
   uint8_t *a = nullptr, *b = nullptr;
   CC_HIP_TRY(scratch.get(&a, B * s.N));
   CC_HIP_TRY(scratch.get(&b, B * s.N));
@@ -314,7 +294,7 @@ int launch_product_count(const cc_product *pc, const uint8_t *d_decided, const u
 
 // Blocks per chunk of the Monte-Carlo and channel routes: 2^24 values (CC_AMD_PRODUCT_MC_CHUNK_VALUES: tests cross a chunk
 // boundary with a small call), about 18 bytes of workspace per value, at least one block
-static size_t product_chunk_blocks(size_t N, size_t blocks) {
+size_t product_chunk_blocks(size_t N, size_t blocks) {
   static const size_t chunk_values = [] {
     const char *e = std::getenv("CC_AMD_PRODUCT_MC_CHUNK_VALUES");
     const long long v = e ? std::atoll(e) : 0;
@@ -326,7 +306,7 @@ static size_t product_chunk_blocks(size_t N, size_t blocks) {
 }
 
 // the blocks sent for the global blocks [first, first + m): l = k1 k2 random bits per block through the product encoder
-static int product_sent(const cc_product *pc, uint64_t seed, uint64_t first, size_t m, uint8_t *d_msg, uint8_t *d_sent,
+int product_sent(const cc_product *pc, uint64_t seed, uint64_t first, size_t m, uint8_t *d_msg, uint8_t *d_sent,
                         hipStream_t stream) {
   const ProductShape s = product_shape(pc);
   if (int rc = launch_random_bits(pc->rows, static_cast<int>(s.k1 * s.k2), seed, first, m, d_msg, stream)) return rc;
@@ -344,7 +324,7 @@ int product_awgn(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t f
     return launch_awgn_values(pc->rows, N, sigma, seed, first_block, blocks, d_y, nullptr, stream);
   }
   const size_t chunk = product_chunk_blocks(s.N, blocks);
-  Scratch scratch(pc->rows, stream);
+  WorkspaceScratch scratch(pc->rows, stream);
   uint8_t *msg = nullptr, *words = nullptr;
   CC_HIP_TRY(scratch.get(&msg, chunk * s.k1 * s.k2));
   if (!d_sent) CC_HIP_TRY(scratch.get(&words, chunk * s.N));
@@ -365,7 +345,7 @@ int mc_run_product(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t
   const ProductShape s = product_shape(pc);
   const float sigma = static_cast<float>(cc_product_sigma(pc, ebno_db));
   const size_t chunk = product_chunk_blocks(s.N, blocks), lines = (pc->halves & 1) ? s.w2 : s.w1;
-  Scratch scratch(pc->rows, stream);
+  WorkspaceScratch scratch(pc->rows, stream);
   float *y = nullptr;
   uint8_t *decided = nullptr, *sent = nullptr, *msg = nullptr;
   int32_t *status = nullptr;

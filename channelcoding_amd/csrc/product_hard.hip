@@ -1,0 +1,450 @@
+// product_hard.hip -- iterated bounded-distance decoding (iBDD) of product codes on hard decisions, all half-iterations
+// of a block in one launch.  The contract is stated at cc_product_decode_hard in the public header; here
+// is how it is mapped.
+//
+// A block lives in LDS as bits from its load to its store: X[w2][P] dwords, bit k & 31 of X[i][k >> 5] = x(i, k), the
+// pitch P = ceil(w1 / 32) | 1 odd so that the lanes of a row pass walk different banks.  X0 is the block as it was
+// loaded (nflip = popcount(X ^ X0) at the end), ctl holds last, the status flag and nflip.
+//
+//   WG = false  a block whose longer side is <= 64 lines belongs to one wavefront, a workgroup carries four blocks, and
+//               a line is one 64-bit register
+//   WG = true   up to 256 lines: a workgroup of 256 threads per block, a line is four 64-bit registers
+//
+// Every line keeps its state in LDS: the t odd syndromes and the parity of its bits, computed from the bits once after the
+// load (one lane per line, both directions) and updated on every flip -- bit (i, k) adds alpha^(j k) to row i and
+// alpha^(j i) to column k, with LDS atomics.  `status` and the test for a clean line then cost nothing, and a wavefront
+// none of whose lines has a non-zero syndrome skips the decoder.
+//
+// One lane owns one line of the current pass:
+//   syndromes  the odd ones from the line's state, S_2j = S_j^2 in the log domain, as logs into the lane's LDS column
+//   bm_lds     lane_bm.hpp's recurrence
+//   roots      one locator at a time, all 64 lanes evaluating it at alpha^-pos for the positions lane + 64 c, a ballot
+//              per 64 positions giving the owner lane its flip mask: 4 (deg + 1) look-ups per line that needs it in
+//              place of n (deg + 1) in every lane.  A candidate exists iff L = deg lambda <= t and lambda has deg roots
+//              below n, as in chase.hip
+//   the rule   plain: the candidate; extended: the candidate iff d_H + (parity differs) <= t
+//   flips      behind a barrier, so that no line sees another line's corrections of the same pass: a row lane rewrites
+//              its own dwords, a column lane XORs bits into shared dwords with LDS atomics; the line's own state
+//              becomes zero (it is a word now), the crossing lines' states take the updates
+// A block stops after two successive passes without a change: every later pass would see the same state and change
+// nothing either, so `last`, out and status cannot show it.
+//
+// Global traffic per block: N bytes in (a ballot per 64 bytes makes the bits), N bytes out, three int32.
+#include <mutex>
+
+#include "soft_lanes.hpp"
+
+namespace ccamd {
+namespace {
+
+constexpr int kHardTables = 2 * kSoftTables;  // the tables of `rows`, then those of `cols`
+
+template <int NC>
+__device__ __forceinline__ bool any_bit(const unsigned long long (&m)[NC]) {
+  unsigned long long o = 0;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) o |= m[c];
+  return o != 0;
+}
+template <int NC>
+__device__ __forceinline__ int count_bits(const unsigned long long (&m)[NC]) {
+  int cnt = 0;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) cnt += __builtin_popcountll(m[c]);
+  return cnt;
+}
+
+// the bits of line `line` of X: row `line` (w1 bits, PD dwords) or column `line` (w2 bits)
+template <int NC>
+__device__ __forceinline__ void gather_line(const uint32_t *X, int P, int PD, int w2, bool column, bool have, int line,
+                                            unsigned long long (&lb)[NC]) {
+#pragma unroll
+  for (int c = 0; c < NC; ++c) lb[c] = 0;
+  if (!have) return;
+  if (!column) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const uint32_t lo = 2 * c < PD ? X[line * P + 2 * c] : 0u, hi = 2 * c + 1 < PD ? X[line * P + 2 * c + 1] : 0u;
+      lb[c] = static_cast<unsigned long long>(lo) | (static_cast<unsigned long long>(hi) << 32);
+    }
+  } else {
+    const int kw = line >> 5, kb = line & 31;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int stop = w2 - 64 * c < 64 ? w2 - 64 * c : 64;
+      unsigned long long acc = 0;
+#pragma unroll 8
+      for (int b = 0; b < stop; ++b)
+        acc |= static_cast<unsigned long long>((X[(64 * c + b) * P + kw] >> kb) & 1u) << b;
+      lb[c] = acc;
+    }
+  }
+}
+
+// S_j of the positions 0 .. n-1 of a line
+template <int NC>
+__device__ __forceinline__ uint32_t line_syndrome(const uint8_t *ex, const unsigned long long (&lb)[NC], int n, int nn, int j) {
+  const uint32_t step = static_cast<uint32_t>(j) % static_cast<uint32_t>(nn);
+  uint32_t s = 0, ev = 0;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int stop = n - 64 * c < 64 ? n - 64 * c : 64;
+#pragma unroll 8
+    for (int b = 0; b < stop; ++b) {  // (unrolled: eight look-ups in flight, the exponent chain is arithmetic alone)
+      s ^= ((lb[c] >> b) & 1ull) ? static_cast<uint32_t>(ex[ev]) : 0u;
+      ev = addmod(ev, step, nn);
+    }
+  }
+  return s;
+}
+
+// the LDS of one block, in dwords: X and X0 [w2][P], ctl [4], then the state of every line as bytes -- the t odd
+// syndromes S_1, S_3, .. and in slot t the parity of all its bits -- at a pitch of whole dwords, rows then columns
+struct HardBlock {
+  int P, pitch_r, pitch_c, dwords;
+};
+__host__ __device__ constexpr HardBlock hard_block(int w1, int w2, int tr, int tc) {
+  const int P = ((w1 + 31) >> 5) | 1, pitch_r = (tr + 4) & ~3, pitch_c = (tc + 4) & ~3;
+  return HardBlock{P, pitch_r, pitch_c, 2 * w2 * P + 4 + (w2 * pitch_r + w1 * pitch_c) / 4};
+}
+
+template <bool WG>
+__global__ void __launch_bounds__(256)
+product_hard_kernel(const AlgebraicTables *__restrict__ Tr, const AlgebraicTables *__restrict__ Tc, const uint8_t *in,
+                    uint8_t *out, int32_t *__restrict__ nflip_out, int32_t *__restrict__ last_out,
+                    int32_t *__restrict__ status_out, unsigned long long B, int halves, int e, int col_bytes) {
+  constexpr int NC = WG ? 4 : 1;
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  stage_ex(Tr, smem);
+  stage_log16(Tr, reinterpret_cast<uint16_t *>(smem + 1024));
+  stage_ex(Tc, smem + kSoftTables);
+  stage_log16(Tc, reinterpret_cast<uint16_t *>(smem + kSoftTables + 1024));
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int line = WG ? static_cast<int>(threadIdx.x) : lane, threads = WG ? 256 : 64;
+  const int n1 = Tr->n, n2 = Tc->n, w1 = n1 + e, w2 = n2 + e;
+  const int PD = (w1 + 31) >> 5, P = PD | 1, chunks = (w1 + 63) >> 6;
+  const unsigned long long N = static_cast<unsigned long long>(w1) * w2;
+  const int nnr = Tr->nf, nnc = Tc->nf, tr = Tr->nroots / 2, tc = Tc->nroots / 2;
+  const HardBlock lay = hard_block(w1, w2, tr, tc);
+  const int pitch_r = lay.pitch_r, pitch_c = lay.pitch_c;
+  uint8_t *colbase = smem + kHardTables + wid * col_bytes;
+  uint32_t *X = reinterpret_cast<uint32_t *>(smem + kHardTables + 4 * col_bytes) + (WG ? 0 : wid * lay.dwords);
+  uint32_t *X0 = X + w2 * P, *ctl = X0 + w2 * P;  // ctl: [0] last, [1] a line that is no word, [2] nflip
+  uint8_t *SR = reinterpret_cast<uint8_t *>(ctl + 4), *SC = SR + w2 * pitch_r;
+  const auto sync = [] {
+    if constexpr (WG)
+      __syncthreads();
+    else
+      wave_sync();
+  };
+  const int row0 = WG ? wid : 0, row_step = WG ? 4 : 1;  // the rows a wavefront loads and stores
+
+  const unsigned long long start = WG ? blockIdx.x : blockIdx.x * 4ull + wid, stride = WG ? gridDim.x : gridDim.x * 4ull;
+  for (unsigned long long b = start; b < B; b += stride) {
+    // ---------------- load: bytes -> bits ----------------
+    const uint8_t *src = in + b * N;
+    // (U rows at a time: all their loads are issued before the first ballot waits for one)
+    constexpr int U = WG ? 4 : 8;
+    for (int r = row0; r < w2; r += row_step * U) {
+      uint32_t v[U][NC];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const int rr = r + u * row_step, col = 64 * c + lane;
+          v[u][c] = (rr < w2 && col < w1) ? src[static_cast<unsigned long long>(rr) * w1 + col] : 0u;
+        }
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const int rr = r + u * row_step;
+          const unsigned long long m = __ballot((v[u][c] & 1u) != 0);
+          if (rr < w2 && lane < 2 && 2 * c + lane < PD) {
+            const uint32_t d = static_cast<uint32_t>(lane ? m >> 32 : m);
+            X[rr * P + 2 * c + lane] = d;
+            X0[rr * P + 2 * c + lane] = d;
+          }
+        }
+    }
+    if (line < 4) ctl[line] = 0;
+    sync();
+
+    // ---------------- the state of every line: odd syndromes and parity, from the bits, once ----------------
+    for (int dir = 0; dir < 2; ++dir) {
+      const bool column = dir != 0;
+      const uint8_t *ex = smem + (column ? kSoftTables : 0);
+      const int n = column ? n2 : n1, nn = column ? nnc : nnr, t = column ? tc : tr;
+      const bool have_line = line < (column ? w1 : w2);
+      unsigned long long lb[NC];
+      gather_line<NC>(X, P, PD, w2, column, have_line, line, lb);
+      if (have_line) {
+        uint8_t *S = (column ? SC : SR) + line * (column ? pitch_c : pitch_r);
+        for (int m = 0; m < t; ++m) S[m] = static_cast<uint8_t>(line_syndrome<NC>(ex, lb, n, nn, 2 * m + 1));
+        S[t] = static_cast<uint8_t>(count_bits<NC>(lb) & 1);
+      }
+    }
+    sync();
+
+    // ---------------- the half-iterations ----------------
+    for (int h = 0; h < halves; ++h) {
+      const bool column = (h & 1) != 0;
+      const uint8_t *ex = smem + (column ? kSoftTables : 0);
+      const uint16_t *lg2 = reinterpret_cast<const uint16_t *>(ex + 1024);
+      const int n = column ? n2 : n1, nn = column ? nnc : nnr, t = column ? tc : tr, t2 = 2 * t;
+      const BmColumns bm = bm_columns(t2);
+      uint16_t *SL = reinterpret_cast<uint16_t *>(colbase + bm.SL);
+      uint16_t *LL = reinterpret_cast<uint16_t *>(colbase + bm.LL);
+      uint16_t *BL = reinterpret_cast<uint16_t *>(colbase + bm.BL);
+      const bool have_line = line < (column ? w1 : w2);
+      uint8_t *S = (column ? SC : SR) + line * (column ? pitch_c : pitch_r);
+
+      // (a lane without a line: syndromes zero, its column holds log 0)
+      bool nz = false;
+      for (int m = 0; m < t; ++m) {
+        const uint32_t s = have_line ? S[m] : 0u;
+        SL[2 * m * 64 + lane] = lg2[s];
+        nz = nz || s != 0;
+      }
+      const uint32_t par = (e && have_line) ? S[t] : 0u;  // parity of the n + 1 bits of the line
+      const bool mine = have_line && nz;
+
+      unsigned long long fm[NC];  // positions the line changes at
+#pragma unroll
+      for (int c = 0; c < NC; ++c) fm[c] = 0;
+      bool have = false;
+      if (__any(mine ? 1 : 0)) {
+        for (int m = 2; m <= t2; m += 2) {  // S_m = S_(m/2)^2
+          const uint32_t ls = SL[(m / 2 - 1) * 64 + lane];
+          SL[(m - 1) * 64 + lane] = static_cast<uint16_t>(ls >= kLogZero ? kLogZero : addmod(ls, ls, nn));
+        }
+        int deg;
+        const int len = bm_lds<64>(ex, lg2, SL, LL, BL, t2, nn, mine, 0u, nullptr, 0u, deg);
+        const bool viable = mine && len == deg && deg <= t;
+        wave_sync();  // the locators are read across lanes below
+        // the roots of one locator at a time, by all 64 lanes: lane l evaluates it at the positions l + 64 c
+        int nroots = -1;
+        unsigned long long todo = __ballot(viable ? 1 : 0);
+        while (todo) {
+          const int L = __builtin_ctzll(todo);
+          todo &= todo - 1ull;
+          const int dL = __builtin_amdgcn_readlane(deg, L);
+          int found = 0;
+#pragma unroll
+          for (int c = 0; c < NC; ++c) {
+            const int pos = lane + 64 * c;
+            const uint32_t xinv = pos == 0 ? 0u : static_cast<uint32_t>(nn - pos);  // log of alpha^-pos (pos < n <= nn)
+            uint32_t acc = 0, ev = 0;
+            if (pos < n)
+              for (int m = 0; m <= dL; ++m) {
+                acc ^= ex[LL[m * 64 + L] + ev];
+                ev = addmod(ev, xinv, nn);
+              }
+            const unsigned long long roots = __ballot((pos < n && acc == 0) ? 1 : 0);
+            if (lane == L) fm[c] = roots;
+            found += __builtin_popcountll(roots);
+          }
+          if (lane == L) nroots = found;
+        }
+        have = viable && nroots == deg;
+        if (!have) {
+#pragma unroll
+          for (int c = 0; c < NC; ++c) fm[c] = 0;
+        }
+      }
+      // the inner candidate: the line itself where its syndromes are zero, else what the locator gave
+      const bool cand = have_line && (!nz || have);
+      if (e) {  // bounded distance in the extended code: d_H over the n inner positions plus the parity position
+        const int cnt = count_bits<NC>(fm);
+        const bool pflip = ((par ^ static_cast<uint32_t>(cnt)) & 1u) != 0;  // parity(c') != w_n
+        const bool take = cand && cnt + (pflip ? 1 : 0) <= t;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          if (!take) fm[c] = 0;
+          if (take && pflip && (n >> 6) == c) fm[c] |= 1ull << (n & 63);
+        }
+      }
+      const bool changed = any_bit<NC>(fm);
+      sync();  // every line of the pass has been read
+      if (changed) {
+        // the line becomes a word of its code: its own state is zero; every flipped bit is position `line` of a line
+        // of the other direction, whose state takes alpha^(j line) and the parity
+        for (int m = 0; m <= t; ++m) S[m] = 0;
+        const uint8_t *exo = smem + (column ? 0 : kSoftTables);
+        uint32_t *So = reinterpret_cast<uint32_t *>(column ? SR : SC);
+        const int no = column ? n1 : n2, nno = column ? nnr : nnc, to = column ? tr : tc, pitch_o = column ? pitch_r : pitch_c;
+        const uint32_t step2 = line < no ? addmod(line, line, nno) : 0u;
+        const int kw = line >> 5;
+        const uint32_t bit = 1u << (line & 31);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          if (!column) {
+            if (2 * c < PD) X[line * P + 2 * c] ^= static_cast<uint32_t>(fm[c]);
+            if (2 * c + 1 < PD) X[line * P + 2 * c + 1] ^= static_cast<uint32_t>(fm[c] >> 32);
+          }
+          unsigned long long m = fm[c];
+          while (m) {
+            const int k = 64 * c + __builtin_ctzll(m);
+            m &= m - 1ull;
+            if (column) atomicXor(&X[k * P + kw], bit);
+            if (line < no) {
+              uint32_t ev = static_cast<uint32_t>(line);
+              for (int j = 0; j < to; ++j) {
+                const int idx = k * pitch_o + j;
+                atomicXor(&So[idx >> 2], static_cast<uint32_t>(exo[ev]) << (8 * (idx & 3)));
+                ev = addmod(ev, step2, nno);
+              }
+            }
+            if (e) {
+              const int idx = k * pitch_o + to;
+              atomicXor(&So[idx >> 2], 1u << (8 * (idx & 3)));
+            }
+          }
+        }
+        atomicMax(&ctl[0], static_cast<uint32_t>(h + 1));
+      }
+      sync();
+      if (h + 1 - static_cast<int>(ctl[0]) >= 2) break;  // a fixed point; the same value in every lane of the block
+    }
+
+    // ---------------- status: every row and every column a word of its code ----------------
+    bool bad = false;
+    if (line < w2)
+      for (int m = 0; m < tr + e; ++m) bad = bad || SR[line * pitch_r + m] != 0;
+    if (line < w1)
+      for (int m = 0; m < tc + e; ++m) bad = bad || SC[line * pitch_c + m] != 0;
+    if (bad) atomicOr(&ctl[1], 1u);
+    uint32_t diff = 0;
+    for (int i = line; i < w2 * PD; i += threads) {
+      const int r = i / PD, d = i - r * PD;
+      diff += static_cast<uint32_t>(__builtin_popcount(X[r * P + d] ^ X0[r * P + d]));
+    }
+    if (diff) atomicAdd(&ctl[2], diff);
+    sync();
+
+    // ---------------- store: bits -> bytes ----------------
+    uint8_t *dst = out + b * N;
+    for (int r = row0; r < w2; r += row_step)
+      for (int c = 0; c < chunks; ++c) {
+        const int col = 64 * c + lane;
+        if (col < w1) dst[static_cast<unsigned long long>(r) * w1 + col] = static_cast<uint8_t>((X[r * P + (col >> 5)] >> (col & 31)) & 1u);
+      }
+    if (line == 0) {
+      if (nflip_out) nflip_out[b] = static_cast<int32_t>(ctl[2]);
+      if (last_out) last_out[b] = static_cast<int32_t>(ctl[0]);
+      if (status_out) status_out[b] = ctl[1] ? CC_FRAME_NOT_CONVERGED : CC_FRAME_OK;
+    }
+    sync();  // the next block overwrites X, X0 and ctl
+  }
+}
+
+// decided: B blocks of N bytes; sent: the blocks sent (nullptr: the all-zero block); status and last: one per block.
+// One wavefront per block as in product_count_kernel; the histogram slot of a block takes one atomic of its own.
+__global__ void __launch_bounds__(256)
+product_hard_count_kernel(const uint8_t *__restrict__ decided, const uint8_t *__restrict__ sent, const int32_t *__restrict__ status,
+                          const int32_t *__restrict__ last, unsigned long long N, unsigned long long blocks,
+                          unsigned long long *__restrict__ counters) {
+  const int lane = threadIdx.x & 63;
+  const unsigned long long wave = static_cast<unsigned long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  const unsigned long long waves = static_cast<unsigned long long>(gridDim.x) * 4;
+  unsigned long long c_frames = 0, c_bit = 0, c_word = 0, c_fail = 0, c_und = 0, c_iter = 0;
+  for (unsigned long long b = wave; b < blocks; b += waves) {
+    const uint8_t *d = decided + b * N, *s = sent ? sent + b * N : nullptr;
+    unsigned cnt = 0;
+    for (unsigned long long i = lane; i < N; i += 64) cnt += (d[i] != (s ? s[i] : 0)) ? 1u : 0u;
+    for (int m = 32; m >= 1; m >>= 1) cnt += static_cast<unsigned>(__shfl_xor(static_cast<int>(cnt), m, 64));
+    const bool failed = status[b] != CC_FRAME_OK;
+    const int32_t it = last[b];
+    c_frames += 1;
+    c_bit += cnt;
+    c_word += (failed || cnt) ? 1u : 0u;
+    c_fail += failed ? 1u : 0u;
+    c_und += (!failed && cnt) ? 1u : 0u;
+    c_iter += static_cast<unsigned long long>(it);
+    if (lane == 0) atomicAdd(&counters[CC_MC_ITER_HIST + (it < 55 ? it : 55)], 1ull);
+  }
+  if (lane == 0 && c_frames) {
+    atomicAdd(&counters[CC_MC_FRAMES], c_frames);
+    if (c_bit) atomicAdd(&counters[CC_MC_BIT_ERRORS], c_bit);
+    if (c_word) atomicAdd(&counters[CC_MC_WORD_ERRORS], c_word);
+    if (c_fail) atomicAdd(&counters[CC_MC_FAILURES], c_fail);
+    if (c_und) atomicAdd(&counters[CC_MC_UNDETECTED], c_und);
+    if (c_iter) atomicAdd(&counters[CC_MC_ITER_SUM], c_iter);
+  }
+}
+
+}  // namespace
+
+int launch_product_hard(const cc_product *pc, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip, int32_t *d_last,
+                        int32_t *d_status, size_t B, hipStream_t stream) {
+  if (B == 0) return CC_OK;
+  const cc_code *rows = pc->rows, *cols = pc->cols;
+  const ProductShape s = product_shape(pc);
+  const int w1 = static_cast<int>(s.w1), w2 = static_cast<int>(s.w2);
+  const bool wg = (w1 > w2 ? w1 : w2) > 64;
+  const int t2 = rows->h_alg.nroots > cols->h_alg.nroots ? rows->h_alg.nroots : cols->h_alg.nroots;
+  const int col_bytes = bm_columns(t2).end;
+  const int block_bytes = 4 * hard_block(w1, w2, rows->h_alg.nroots / 2, cols->h_alg.nroots / 2).dwords;
+  const size_t lds = kHardTables + 4 * static_cast<size_t>(col_bytes) + (wg ? 1 : 4) * static_cast<size_t>(block_bytes);
+  if (lds > 64 * 1024) {  // once per device: 2t = 32 next to a block of 256 lines asks for more than the default limit
+    static std::mutex lock;
+    static unsigned long long done = 0;
+    const unsigned dev = static_cast<unsigned>(rows->device) & 63u;
+    std::lock_guard<std::mutex> g(lock);
+    if (!((done >> dev) & 1ull)) {
+      const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&product_hard_kernel<true>),
+                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      if (attr != hipSuccess) return hip_fail(attr, "product hard kernel LDS attribute");
+      done |= 1ull << dev;
+    }
+  }
+  const unsigned long long want = wg ? B : (static_cast<unsigned long long>(B) + 3) / 4;
+  const unsigned long long cap = static_cast<unsigned long long>(rows->num_cus) * 8;
+  const dim3 grid(static_cast<unsigned>(want < cap ? want : cap));
+  const auto kernel = wg ? product_hard_kernel<true> : product_hard_kernel<false>;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, rows->d_alg, cols->d_alg, d_in, d_out, d_nflip, d_last, d_status,
+                     static_cast<unsigned long long>(B), static_cast<int>(pc->halves), s.e, col_bytes);
+  const hipError_t err = hipGetLastError();
+  return err != hipSuccess ? hip_fail(err, "product hard kernel launch") : CC_OK;
+}
+
+// channel with the hard decision z = (y < 0) written as bytes by the channel launch itself, the decoder in place, count:
+// chunk by chunk, the counters of a block a function of (seed, ebno, pc, global block index) alone
+int mc_run_product_hard(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
+                        int random_codewords, uint64_t *d_counters, hipStream_t stream) {
+  if (blocks == 0) return CC_OK;
+  const ProductShape s = product_shape(pc);
+  const float sigma = static_cast<float>(cc_product_sigma(pc, ebno_db));
+  const size_t chunk = product_chunk_blocks(s.N, blocks);
+  WorkspaceScratch scratch(pc->rows, stream);
+  uint8_t *z = nullptr, *sent = nullptr, *msg = nullptr;
+  int32_t *status = nullptr, *last = nullptr;
+  CC_HIP_TRY(scratch.get(&z, chunk * s.N));
+  CC_HIP_TRY(scratch.get(&status, chunk * sizeof(int32_t)));
+  CC_HIP_TRY(scratch.get(&last, chunk * sizeof(int32_t)));
+  if (random_codewords) {
+    CC_HIP_TRY(scratch.get(&sent, chunk * s.N));
+    CC_HIP_TRY(scratch.get(&msg, chunk * s.k1 * s.k2));
+  }
+  for (size_t done = 0; done < blocks; done += chunk) {
+    const size_t m = blocks - done < chunk ? blocks - done : chunk;
+    if (random_codewords)
+      if (int rc = product_sent(pc, seed, first_block + done, m, msg, sent, stream)) return rc;
+    if (int rc = launch_awgn_values(pc->rows, static_cast<int>(s.N), sigma, seed, first_block + done, m,
+                                    reinterpret_cast<float *>(z), sent, stream,
+                                    reinterpret_cast<unsigned long long *>(d_counters), true))
+      return rc;
+    if (int rc = launch_product_hard(pc, z, z, nullptr, last, status, m, stream)) return rc;
+    const unsigned long long want = (static_cast<unsigned long long>(m) + 3) / 4, cap = static_cast<unsigned long long>(pc->rows->num_cus) * 8;
+    hipLaunchKernelGGL(product_hard_count_kernel, dim3(static_cast<unsigned>(want < cap ? want : cap)), dim3(256), 0, stream, z,
+                       sent, status, last, static_cast<unsigned long long>(s.N), static_cast<unsigned long long>(m),
+                       reinterpret_cast<unsigned long long *>(d_counters));
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return hip_fail(err, "product hard count kernel launch");
+  }
+  return CC_OK;
+}
+
+}  // namespace ccamd

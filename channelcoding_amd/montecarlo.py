@@ -216,6 +216,29 @@ class ProductBackend:
         return counters
 
 
+class ProductHardBackend:
+    """Counts one shard of blocks of one Eb/N0 point through cc_mc_run_product_hard_dev: a product_code decoded with
+    `halves` half-iterations of bounded-distance row / column decoding on the hard decisions of the channel."""
+
+    def __init__(self, pc, halves, random_codewords=False):
+        import torch
+        self.torch = torch
+        self.code = pc
+        self.random_codewords = bool(random_codewords)
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.desc = pc._pc_hard(halves)
+
+    def run(self, ebno_db, seed, first_block, blocks):
+        torch = self.torch
+        counters = torch.zeros(capi.MC_NCOUNTERS, dtype=torch.int64, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = capi.lib().cc_mc_run_product_hard_dev(C.byref(self.desc), float(ebno_db), int(seed), int(first_block),
+                                                   int(blocks), int(self.random_codewords),
+                                                   C.c_void_p(counters.data_ptr()), stream)
+        capi.check(rc, "cc_mc_run_product_hard_dev")
+        return counters
+
+
 class _ShardedSimulation:
     """What the AWGN, the discrete-channel and the burst-channel ladders share: the shard of this rank, the one all-reduce per point,
     rank 0's log file (its success agreed with every rank before the first collective) and the adaptive ladder."""
@@ -264,10 +287,10 @@ class _ShardedSimulation:
         v = t.cpu().tolist()
         return bool(v[0]), int(v[1]) | (int(v[2]) << 32)
 
-    def _ladder(self, log_name, column, row_value, header_note=""):
+    def _ladder(self, log_name, column, row_value, header_note="", row_note=None):
         """Every point of self.points() with the adaptive sample count; rank 0 writes the reference-format log
         `log_name` whose first column, headed `column`, shows row_value(point); header_note is appended to the header
-        line."""
+        line and row_note(res), where given, to the line of a point."""
         dist = self._dist()
         rank = dist.get_rank() if dist else 0
         log, error = None, None
@@ -292,7 +315,7 @@ class _ShardedSimulation:
             results.append(res)
             wer = res["wer"]
             if log:
-                log.write("%7s %s\n" % ("%.6g" % row_value(point), "%16.15e" % res["wer"]))
+                log.write("%7s %s%s\n" % ("%.6g" % row_value(point), "%16.15e" % res["wer"], row_note(res) if row_note else ""))
                 log.flush()
         if log:
             log.close()
@@ -385,6 +408,40 @@ class product_simulation(_ShardedSimulation):
     def __call__(self):
         name = "%s-chase%d-h%d.log" % (self.code.to_string(), self.p, self.halves)
         return self._ladder(name, "ebno", lambda ebno: ebno)
+
+
+class product_hard_simulation(_ShardedSimulation):
+    """The Eb/N0 ladder of a product code under `halves` half-iterations of hard-decision row / column decoding
+    (cc_mc_run_product_hard_dev): the ladder and the sharding by block of product_simulation.  The log is
+    <pc.to_string()>-hard-h<halves>.log; next to wer it shows the mean of `last`, the half-iterations a block took to
+    its final state (CC_MC_ITER_SUM over the blocks)."""
+
+    def __init__(self, pc, halves, step=0.5, seed=0, random_codewords=False, backend=None, log_dir=None,
+                 max_samples=None, start=None, stop=None, samples_per_point=None):
+        self.code = pc
+        self.halves = int(halves)
+        if self.halves < 1:
+            raise ValueError("halves >= 1")
+        self.step = float(step)
+        self.seed = int(seed)
+        self.backend = backend if backend is not None else ProductHardBackend(pc, self.halves, random_codewords)
+        self.log_dir = log_dir
+        self.max_samples = max_samples
+        self.samples_per_point = samples_per_point
+        ref_start, _ = ladder(pc.rate, self.step)
+        self.start = ref_start if start is None else float(start)
+        self.stop = (max(8.0, self.start) + self.step / 2) if stop is None else float(stop)
+
+    points = awgn_simulation.points
+
+    def run_point(self, ebno_db, frames, point_index=0):
+        res = awgn_simulation.run_point(self, ebno_db, frames, point_index)
+        res["mean_last"] = res["iter_sum"] / max(1, res["frames"])
+        return res
+
+    def __call__(self):
+        name = "%s-hard-h%d.log" % (self.code.to_string(), self.halves)
+        return self._ladder(name, "ebno", lambda ebno: ebno, " %12s" % "mean_last", lambda res: " %12.6f" % res["mean_last"])
 
 
 # ---- discrete memoryless channels (cc_mc_run_discrete_dev): the BSC and BEC the reference's README leaves as a TODO --

@@ -530,6 +530,56 @@ int cc_awgn_product_dev(const cc_product *pc, double ebno_db, uint64_t seed, uin
 int cc_mc_run_product_dev(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
                           int random_codewords, uint64_t *d_counters, void *stream);
 
+/* ---- iterated bounded-distance decoding (iBDD) of a product code on hard decisions: the decoder of deployed high-rate
+ *      systems and the baseline a block turbo result is held against.  One launch runs all half-iterations of a batch.
+ *      Of pc only rows, cols, extended and halves are read; p, alpha and beta are not examined and may be 0 / NULL.
+ *      e, w1, w2, N and the block [w2][w1] are those of cc_product_decode; `in` holds bytes 0 / 1 (the host form answers
+ *      CC_ERR_NOT_IN_FIELD for another value, as cc_correct_hard_batch does; a device buffer with other values is
+ *      unspecified).
+ *        iteration   x_0 = in.  Half-iteration h = 0 .. halves - 1 takes the rows (h even) or the columns (h odd) of x_h:
+ *                    every line w of n + e bits, n the line's handle length, is decoded from x_h -- no line sees another
+ *                    line's corrections within the same pass, and the lines of a pass are disjoint, so their order cannot
+ *                    show.
+ *        candidate   c' is the handle's codeword within Hamming distance t of w[0..n), if there is one: the candidate
+ *                    rule of cc_correct_chase_batch -- bounded distance (deg lambda <= t, all roots below n; the BM
+ *                    tag's admission of deg lambda > t does not apply, a locator root at a position >= n of a shortened
+ *                    code means no candidate).  The hard tag of the handle does not influence the result.
+ *        plain       with a candidate the line becomes c'; without one it stays.
+ *        extended    d = d_H(c', w[0..n)) + (parity(c') != w_n).  The line becomes (c', parity(c')) iff a candidate
+ *                    exists and d <= t -- bounded-distance decoding of the extended code, whose distance is 2t + 2 --
+ *                    otherwise it stays, parity bit included.  (Not what cc_correct_chase_extended_batch does at p = 0:
+ *                    that call accepts every inner candidate.)
+ *        outputs     out = x_halves (B*N bytes).  nflip = d_H(out, in) over the N positions.  last = the largest h + 1
+ *                    with x_(h+1) != x_h, 0 if nothing ever changed.  status = CC_FRAME_OK iff every row and every
+ *                    column of out is a word of its code (extended where `extended`; the shortened code for a shortened
+ *                    handle), else CC_FRAME_NOT_CONVERGED.  nflip, last and status (B int32 each) may be NULL.
+ *      The device may stop working on a block that has reached a fixed point (two successive passes without a change,
+ *      or all line syndromes zero); no output shows whether it did.  out == in is allowed.
+ *      Refused before a device is asked for, in this order:
+ *        1. NULL pc, rows, cols, in or out -> CC_ERR_INVALID_ARGUMENT (in / out unless B = 0;
+ *           cc_mc_run_product_hard_dev: NULL pc or counters first)
+ *        2. halves == 0 -> CC_ERR_INVALID_ARGUMENT
+ *        3. what cc_correct_chase_batch refuses at p = 0 for `rows`, then for `cols`, in its order and with its texts
+ *        4. the two handles on different devices -> CC_ERR_INVALID_ARGUMENT
+ *        5. out overlapping in other than out == in -> CC_ERR_INVALID_ARGUMENT
+ *        6. a CC_DEVICE_NONE handle -> CC_ERR_NO_DEVICE
+ *      B = 0 answers CC_OK after these checks.  Buffers: natural alignment only, and nothing outside the stated extents
+ *      is read into a result or written.  No RS components, no erasures between passes, no q > 8. ---- */
+int cc_product_decode_hard(const cc_product *pc, const uint8_t *in /* B*N */, uint8_t *out /* B*N */,
+                           int32_t *nflip /* B or NULL */, int32_t *last /* B or NULL */, int32_t *status /* B or NULL */,
+                           size_t B);
+int cc_product_decode_hard_dev(const cc_product *pc, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip, int32_t *d_last,
+                               int32_t *d_status, size_t B, void *stream);
+/* Monte-Carlo of the hard decoder: by definition the counters equal what cc_awgn_product_dev at cc_product_sigma, the hard
+ * decision z = (y < 0), cc_product_decode_hard_dev and a comparison with the blocks sent would count.  CC_MC_FRAMES counts
+ * blocks, CC_MC_BIT_ERRORS wrong bits among the N, CC_MC_FAILURES blocks whose status is not CC_FRAME_OK,
+ * CC_MC_WORD_ERRORS blocks that are wrong or failed, CC_MC_UNDETECTED blocks that are wrong and converged,
+ * CC_MC_CHANNEL_BIT_ERRORS the channel's, CC_MC_ITER_SUM the sum of `last`, and CC_MC_ITER_HIST + min(last, 55) takes one
+ * per block.  The counters depend only on (seed, ebno, pc, the set of global blocks).  Chunking and workspace follow
+ * cc_mc_run_product_dev: the `rows` handle's pool, one stream at a time. */
+int cc_mc_run_product_hard_dev(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
+                               int random_codewords, uint64_t *d_counters, void *stream);
+
 /* ---- batched Monte-Carlo over discrete memoryless channels: the BSC and the BEC the reference's README leaves as a
  *      TODO, both at once, and for RS codes the q-ary symmetric and the symbol erasure channel.  A symbol is erased
  *      with probability p_erasure, in error with probability p_error, intact otherwise (both finite, >= 0, sum <= 1).

@@ -676,7 +676,7 @@ public:
 };
 
 // ---- product codes (new; cc_product_*): the product of two primitive_bch objects, decoded iteratively with the
-// Chase-Pyndiah component decoder.  A block is n2 x n1 values (extended: (n2 + 1) x (n1 + 1)) whose rows are words of
+// Chase-Pyndiah component decoder, or on hard decisions by bounded-distance row / column decoding (correct_hard).  A block is n2 x n1 values (extended: (n2 + 1) x (n1 + 1)) whose rows are words of
 // Rows and whose columns are words of Cols; alpha and beta hold one value each per half-iteration.  Both objects must
 // outlive the product_code. ----
 template <typename Rows, typename Cols> class product_code {
@@ -732,6 +732,27 @@ public:
     r.status.resize(B * ((alpha.size() & 1) ? w2_ : w1_));
     detail::check(cc_product_decode(&pc, values_in, r.words.data(), soft ? r.ext.data() : nullptr, r.status.data(), B),
                   "cc_product_decode");
+    return r;
+  }
+
+  // Iterated bounded-distance decoding on hard decisions (cc_product_decode_hard): B blocks of N bits (bytes 0 / 1),
+  // `halves` half-iterations of row / column decoding.  words (B * N), and per block nflip (bits changed), last (the
+  // last half-iteration that changed the block, 0: none) and status (CC_FRAME_OK: every row and column is a word).
+  struct hard_result {
+    std::vector<uint8_t> words;
+    std::vector<int32_t> nflip, last, status;
+  };
+  hard_result correct_hard(const uint8_t *words, size_t B, uint32_t halves) const {
+    if (halves == 0) throw std::runtime_error("product_code: at least one half-iteration");
+    const cc_product pc = descriptor(0, nullptr, nullptr, halves);
+    hard_result r;
+    r.words.resize(B * values());
+    r.nflip.resize(B);
+    r.last.resize(B);
+    r.status.resize(B);
+    const int rc = cc_product_decode_hard(&pc, words, r.words.data(), r.nflip.data(), r.last.data(), r.status.data(), B);
+    if (rc == CC_ERR_NOT_IN_FIELD) throw std::runtime_error("Value is not an element of the field.");
+    detail::check(rc, "cc_product_decode_hard");
     return r;
   }
 
