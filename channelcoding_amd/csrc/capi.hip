@@ -1549,13 +1549,18 @@ static int mc_supported(const cc_code *code) {
   return CC_OK;
 }
 
+// random codewords go through the device encoder, which serves the two polynomial codings
+static int mc_random_codewords(const cc_code *code, int random_codewords) {
+  if (random_codewords && code->desc.coding != CC_CODING_DIVISION && code->desc.coding != CC_CODING_MULTIPLICATION)
+    return CC_ERR_INVALID_ARGUMENT;
+  return CC_OK;
+}
+
 int cc_mc_run_dev(const cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
                   int random_codewords, uint64_t *d_counters, void *stream) {
   if (!code || !d_counters) return CC_ERR_INVALID_ARGUMENT;
-  const int rc = mc_supported(code);
-  if (rc != CC_OK) return rc;
-  if (random_codewords && code->desc.coding != CC_CODING_DIVISION && code->desc.coding != CC_CODING_MULTIPLICATION)
-    return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = mc_supported(code)) return rc;
+  if (int rc = mc_random_codewords(code, random_codewords)) return rc;
   DeviceGuard guard(code->device);
   return mc_run(const_cast<cc_code *>(code), ebno_db, seed, first_frame, frames, random_codewords, d_counters,
                 static_cast<hipStream_t>(stream));
@@ -1565,8 +1570,7 @@ int cc_mc_run_chase_dev(const cc_code *code, uint32_t p, double ebno_db, uint64_
                         int random_codewords, uint64_t *d_counters, void *stream) {
   if (!code || !d_counters) return CC_ERR_INVALID_ARGUMENT;
   if (int rc = chase_supported(code, p)) return rc;
-  if (random_codewords && code->desc.coding != CC_CODING_DIVISION && code->desc.coding != CC_CODING_MULTIPLICATION)
-    return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = mc_random_codewords(code, random_codewords)) return rc;
   DeviceGuard guard(code->device);
   return mc_run_chase(const_cast<cc_code *>(code), p, ebno_db, seed, first_frame, frames, random_codewords, d_counters,
                       static_cast<hipStream_t>(stream));
@@ -1576,8 +1580,7 @@ int cc_mc_run_osd_dev(const cc_code *code, uint32_t order, double ebno_db, uint6
                       int random_codewords, uint64_t *d_counters, void *stream) {
   if (!code || !d_counters) return CC_ERR_INVALID_ARGUMENT;
   if (int rc = osd_supported(code, order)) return rc;
-  if (random_codewords && code->desc.coding != CC_CODING_DIVISION && code->desc.coding != CC_CODING_MULTIPLICATION)
-    return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = mc_random_codewords(code, random_codewords)) return rc;
   DeviceGuard guard(code->device);
   return mc_run_osd(const_cast<cc_code *>(code), order, ebno_db, seed, first_frame, frames, random_codewords, d_counters,
                     static_cast<hipStream_t>(stream));

@@ -311,46 +311,18 @@ int launch_product_decode(const cc_product *pc, const float *d_y, uint8_t *d_out
                           hipStream_t stream);
 int launch_product_encode(const cc_product *pc, const uint8_t *d_msg, uint8_t *d_cw, size_t B, hipStream_t stream);
 int launch_product_extract(const cc_product *pc, const uint8_t *d_cw, uint8_t *d_msg, size_t B, hipStream_t stream);
-// d_sent == nullptr: the all-zero block; d_status: the last half-iteration's, (halves odd ? w2 : w1) entries per block
-int launch_product_count(const cc_product *pc, const uint8_t *d_decided, const uint8_t *d_sent, const int32_t *d_status,
-                         size_t B, uint64_t *d_counters, hipStream_t stream);
 // blocks [first_block, first_block + blocks) of the AWGN channel: d_y (blocks N floats), d_sent (nullptr: not wanted)
 int product_awgn(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
                  int random_codewords, float *d_y, uint8_t *d_sent, hipStream_t stream);
 int mc_run_product(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
                    int random_codewords, uint64_t *d_counters, hipStream_t stream);
-// blocks per chunk of the product Monte-Carlo and channel routes, and the blocks sent for the global blocks
-// [first, first + m) (d_msg: m k1 k2 bytes of scratch)
-size_t product_chunk_blocks(size_t N, size_t blocks);
-int product_sent(const cc_product *pc, uint64_t seed, uint64_t first, size_t m, uint8_t *d_msg, uint8_t *d_sent,
-                 hipStream_t stream);
-// stream-ordered scratch of one product call, returned to the pool of `code` on every way out
-struct WorkspaceScratch {
-  const cc_code *code;
-  hipStream_t stream;
-  void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  int used = 0;
-  WorkspaceScratch(const cc_code *c, hipStream_t s) : code(c), stream(s) {}
-  WorkspaceScratch(const WorkspaceScratch &) = delete;
-  WorkspaceScratch &operator=(const WorkspaceScratch &) = delete;
-  ~WorkspaceScratch() {
-    for (int i = 0; i < used; ++i)
-      if (p[i]) (void)hipFreeAsync(p[i], stream);
-  }
-  template <class T>
-  hipError_t get(T **out, size_t bytes) {
-    const hipError_t e = workspace_alloc(code, &p[used], bytes ? bytes : 1, stream);
-    *out = static_cast<T *>(p[used]);
-    if (e == hipSuccess) ++used;
-    return e;
-  }
-};
+// the same route around launch_product_hard (below): the channel's hard decisions, decoded in place, one status per block
+int mc_run_product_hard(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
+                        int random_codewords, uint64_t *d_counters, hipStream_t stream);
 // product_hard.hip: iterated bounded-distance decoding on hard decisions; pc checked by the caller
 // (cc_product_decode_hard_dev).  d_out may be d_in; d_nflip, d_last and d_status (one per block) may be nullptr
 int launch_product_hard(const cc_product *pc, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip, int32_t *d_last,
                         int32_t *d_status, size_t B, hipStream_t stream);
-int mc_run_product_hard(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
-                        int random_codewords, uint64_t *d_counters, hipStream_t stream);
 // mc.hip (Monte-Carlo calls on one handle must be issued on one stream at a time: they share a workspace)
 int mc_run(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
            uint64_t *d_counters, hipStream_t stream);
@@ -364,10 +336,12 @@ int mc_awgn_symbols(cc_code *code, double ebno_db, uint64_t seed, uint64_t first
                     uint8_t *d_words, float *d_rel, uint8_t *d_sent, hipStream_t stream);
 int mc_awgn(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
             float *d_llr, uint8_t *d_sent, hipStream_t stream);
-// the two generators of the AWGN routes for frames of any length (a block of a product code); `code` sizes the grid
+// the generators of the AWGN routes for frames of any length (a block of a product code); `code` sizes the grid.
+// launch_awgn_values writes y, launch_awgn_hard its hard decisions (y < 0) as bytes
 int launch_awgn_values(const cc_code *code, int n, float sigma, uint64_t seed, uint64_t first_frame, size_t frames,
-                       float *d_llr, const uint8_t *sent, hipStream_t stream, unsigned long long *d_counters = nullptr,
-                       bool hard_bytes = false);
+                       float *d_llr, const uint8_t *sent, hipStream_t stream, unsigned long long *d_counters = nullptr);
+int launch_awgn_hard(const cc_code *code, int n, float sigma, uint64_t seed, uint64_t first_frame, size_t frames,
+                     uint8_t *d_hard, const uint8_t *sent, hipStream_t stream, unsigned long long *d_counters = nullptr);
 int launch_random_bits(const cc_code *code, int l, uint64_t seed, uint64_t first_frame, size_t frames, uint8_t *d_msg,
                        hipStream_t stream);
 int mc_run_discrete(cc_code *code, double p_error, double p_erasure, uint64_t seed, uint64_t first_frame, size_t frames,

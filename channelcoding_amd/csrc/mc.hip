@@ -14,6 +14,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 
 #include "cc_internal.hpp"
 #include "philox.hpp"
@@ -61,7 +62,7 @@ random_bits_kernel(uint8_t *__restrict__ msg, int l, int group_log2, unsigned lo
 // takes from the channel: a quarter of the bytes written here and read by the syndrome kernel
 template <bool HARD>
 __global__ void __launch_bounds__(256)
-awgn_kernel(float *__restrict__ llr, const uint8_t *__restrict__ sent, int n, int group_log2,
+awgn_kernel(std::conditional_t<HARD, uint8_t, float> *__restrict__ out, const uint8_t *__restrict__ sent, int n, int group_log2,
             unsigned long long first_frame, unsigned long long frames, float sigma, uint32_t k0, uint32_t k1,
             unsigned long long *__restrict__ counters) {
   const int G = 1 << group_log2;
@@ -77,7 +78,7 @@ awgn_kernel(float *__restrict__ llr, const uint8_t *__restrict__ sent, int n, in
     float z[4];
     box_muller(p.c[0], p.c[1], z[0], z[1]);
     box_muller(p.c[2], p.c[3], z[2], z[3]);
-    float *dst = llr + f * n + 4 * qd;
+    auto *dst = out + f * n + 4 * qd;
     const uint8_t *src = sent ? sent + f * n + 4 * qd : nullptr;
     if (4 * qd + 4 <= n) {
       float x[4];
@@ -87,10 +88,9 @@ awgn_kernel(float *__restrict__ llr, const uint8_t *__restrict__ sent, int n, in
         x[s] = (one ? -1.0f : 1.0f) + sigma * z[s];  // BPSK 0 -> +1
         cherr += (x[s] < 0.0f) != one;
       }
-      if (HARD) {
-        uint8_t *hd = reinterpret_cast<uint8_t *>(llr) + f * n + 4 * qd;
+      if constexpr (HARD) {
 #pragma unroll
-        for (int s = 0; s < 4; ++s) hd[s] = x[s] < 0.0f ? 1 : 0;
+        for (int s = 0; s < 4; ++s) dst[s] = x[s] < 0.0f ? 1 : 0;
       } else {
         // frames are n floats apart, so dst is 4-byte aligned only: four dword stores the compiler may merge
         dst[0] = x[0];
@@ -103,7 +103,7 @@ awgn_kernel(float *__restrict__ llr, const uint8_t *__restrict__ sent, int n, in
         const bool one = src && src[s];
         const float x = (one ? -1.0f : 1.0f) + sigma * z[s];
         cherr += (x < 0.0f) != one;
-        if (HARD) reinterpret_cast<uint8_t *>(llr)[f * n + 4 * qd + s] = x < 0.0f ? 1 : 0;
+        if constexpr (HARD) dst[s] = x < 0.0f ? 1 : 0;
         else dst[s] = x;
       }
     }
@@ -315,6 +315,8 @@ struct McWorkspace {
   std::mutex lock;
   size_t chunk = 0;
   float *llr = nullptr;
+  // the received buffer as bytes: what a hard-decision decoder takes from the channel sits in the same 4 n bytes per frame
+  uint8_t *received_bytes() const { return reinterpret_cast<uint8_t *>(llr); }
   uint8_t *sent = nullptr, *msg = nullptr, *hard = nullptr;
   uint16_t *iters = nullptr;
   int32_t *status = nullptr, *nerr = nullptr;
@@ -457,7 +459,7 @@ static int transmitted_words(const cc_code *code, uint64_t seed, uint64_t first_
 static int launch_decoder(const cc_code *code, McWorkspace &w, const uint16_t *er, const uint32_t *off, size_t m,
                           hipStream_t stream) {
   if (code->soft) return launch_minsum(code, w.llr, nullptr, nullptr, w.hard, nullptr, w.iters, w.status, m, stream);
-  const uint8_t *recv = reinterpret_cast<const uint8_t *>(w.llr);
+  const uint8_t *recv = w.received_bytes();
   if (er && code->desc.algorithm == CC_ALG_PGZ)  // the BCH two-trial rule, as cc_correct_hard_batch_dev
     return launch_pgz_erasures(code, recv, er, off, w.hard, w.nerr, w.status, m, stream);
   return launch_algebraic(code, false, recv, er, off, w.hard, w.nerr, w.status, m, stream);
@@ -526,50 +528,63 @@ static bool mc_precheck_pays(const cc_code *code, double ebno_db) {
   return std::pow(1.0 - pbit, static_cast<double>(n)) >= 0.25;
 }
 
-// y for frames [first, first + frames) of n values each at noise `sigma`, over the words `sent` (nullptr: the all-zero
-// word); `code` sizes the grid.  n is any length (a block of a product code: up to 2^16 values)
-int launch_awgn_values(const cc_code *code, int n, float sigma, uint64_t seed, uint64_t first_frame, size_t frames,
-                       float *d_llr, const uint8_t *sent, hipStream_t stream, unsigned long long *d_counters,
-                       bool hard_bytes) {
+// The one launcher of awgn_kernel, for frames [first, first + frames) of n values each at noise `sigma` over the words
+// `sent` (nullptr: the all-zero word): T = float writes y, T = uint8_t its hard decisions.  `code` sizes the grid; n is
+// any length (a block of a product code: up to 2^16 values)
+template <class T>
+static int launch_awgn_kernel(const cc_code *code, int n, float sigma, uint64_t seed, uint64_t first_frame, size_t frames,
+                              T *d_out, const uint8_t *sent, hipStream_t stream, unsigned long long *d_counters) {
+  constexpr bool hard = std::is_same<T, uint8_t>::value;
   const uint32_t k0 = static_cast<uint32_t>(seed), k1 = static_cast<uint32_t>(seed >> 32);
   int group_log2 = 0;
   while ((4 << group_log2) < n) ++group_log2;
   const unsigned long long items = static_cast<unsigned long long>(frames) << group_log2;
-  if (hard_bytes)
-    hipLaunchKernelGGL(awgn_kernel<true>, dim3(grid_for(code, items)), dim3(256), 0, stream, d_llr, sent, n, group_log2,
-                       static_cast<unsigned long long>(first_frame), static_cast<unsigned long long>(frames), sigma, k0,
-                       k1, d_counters);
-  else
-    hipLaunchKernelGGL(awgn_kernel<false>, dim3(grid_for(code, items)), dim3(256), 0, stream, d_llr, sent, n, group_log2,
-                       static_cast<unsigned long long>(first_frame), static_cast<unsigned long long>(frames), sigma, k0,
-                       k1, d_counters);
+  hipLaunchKernelGGL(awgn_kernel<hard>, dim3(grid_for(code, items)), dim3(256), 0, stream, d_out, sent, n, group_log2,
+                     static_cast<unsigned long long>(first_frame), static_cast<unsigned long long>(frames), sigma, k0, k1,
+                     d_counters);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "awgn kernel launch");
   return CC_OK;
 }
-
-// writes y for frames [first, first + frames) of the words `sent` (nullptr: the all-zero word)
-static int launch_awgn(const cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
-                       float *d_llr, const uint8_t *sent, hipStream_t stream, unsigned long long *d_counters = nullptr,
-                       bool hard_bytes = false) {
-  const float sigma = static_cast<float>(cc_sigma(code, ebno_db));  // normal_distribution<float>(1.0, float(sigma))
-  return launch_awgn_values(code, static_cast<int>(code->tab.n), sigma, seed, first_frame, frames, d_llr, sent, stream,
-                            d_counters, hard_bytes);
+int launch_awgn_values(const cc_code *code, int n, float sigma, uint64_t seed, uint64_t first_frame, size_t frames,
+                       float *d_llr, const uint8_t *sent, hipStream_t stream, unsigned long long *d_counters) {
+  return launch_awgn_kernel(code, n, sigma, seed, first_frame, frames, d_llr, sent, stream, d_counters);
+}
+int launch_awgn_hard(const cc_code *code, int n, float sigma, uint64_t seed, uint64_t first_frame, size_t frames,
+                     uint8_t *d_hard, const uint8_t *sent, hipStream_t stream, unsigned long long *d_counters) {
+  return launch_awgn_kernel(code, n, sigma, seed, first_frame, frames, d_hard, sent, stream, d_counters);
 }
 
-int mc_run(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
-           uint64_t *d_counters, hipStream_t stream) {
+// writes y (a float buffer) or its hard decisions (a byte buffer) for frames [first, first + frames) of the words `sent`
+// (nullptr: the all-zero word)
+template <class T>
+static int launch_awgn(const cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, T *d_out,
+                       const uint8_t *sent, hipStream_t stream, unsigned long long *d_counters = nullptr) {
+  const float sigma = static_cast<float>(cc_sigma(code, ebno_db));  // normal_distribution<float>(1.0, float(sigma))
+  return launch_awgn_kernel(code, static_cast<int>(code->tab.n), sigma, seed, first_frame, frames, d_out, sent, stream,
+                            d_counters);
+}
+
+// A Monte-Carlo call over an AWGN-type channel: chunks of MC_CHUNK frames through mc_route, channel(w, first, m, sent)
+// and decode(w, m) being the launches of the chunk that starts at the global frame `first`.
+template <class Channel, class Decode>
+static int mc_run_awgn(cc_code *code, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
+                       uint64_t *d_counters, hipStream_t stream, Channel channel, Decode decode) {
   if (frames == 0) return CC_OK;
   const size_t chunk = frames < MC_CHUNK ? frames : MC_CHUNK;
+  return mc_chunked(code, frames, chunk, chunk, stream, [&](McWorkspace &w, size_t done, size_t m) -> int {
+    return mc_route(code, w, seed, first_frame + done, m, random_codewords, d_counters, stream,
+                    [&](const uint8_t *sent) { return channel(w, first_frame + done, m, sent); }, [&] { return decode(w, m); });
+  });
+}
+
+// The route of mc_run where mc_precheck_pays: channel + pre-check, the decoder on what is left, the counts
+static int mc_run_precheck(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
+                           int random_codewords, uint64_t *d_counters, hipStream_t stream) {
+  const size_t chunk = frames < MC_CHUNK ? frames : MC_CHUNK;
   const int n = static_cast<int>(code->tab.n);
-  const bool precheck = mc_precheck_pays(code, ebno_db);
   unsigned long long *counters = reinterpret_cast<unsigned long long *>(d_counters);
   return mc_chunked(code, frames, chunk, chunk, stream, [&](McWorkspace &w, size_t done, size_t m) -> int {
-    if (!precheck)  // (a hard-decision decoder takes bits from the channel: the hard decisions as bytes in the same buffer)
-      return mc_route(code, w, seed, first_frame + done, m, random_codewords, d_counters, stream, [&](const uint8_t *sent) {
-        return launch_awgn(code, ebno_db, seed, first_frame + done, m, w.llr, sent, stream, counters, !code->soft);
-      }, [&] { return launch_decoder(code, w, nullptr, nullptr, m, stream); });
-    // channel + pre-check, the decoder on what is left, the counts
     const uint8_t *sent;
     int rc = transmitted_words(code, seed, first_frame + done, m, random_codewords, w.sent, w.msg, nullptr, stream, &sent);
     if (rc != CC_OK) return rc;
@@ -589,33 +604,40 @@ int mc_run(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, s
   });
 }
 
+int mc_run(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
+           uint64_t *d_counters, hipStream_t stream) {
+  if (frames && mc_precheck_pays(code, ebno_db))
+    return mc_run_precheck(code, ebno_db, seed, first_frame, frames, random_codewords, d_counters, stream);
+  unsigned long long *counters = reinterpret_cast<unsigned long long *>(d_counters);
+  return mc_run_awgn(code, seed, first_frame, frames, random_codewords, d_counters, stream,
+                     [&](McWorkspace &w, uint64_t first, size_t m, const uint8_t *sent) {
+    // (a hard-decision decoder takes bits from the channel: the hard decisions as bytes in the same buffer)
+    return code->soft ? launch_awgn(code, ebno_db, seed, first, m, w.llr, sent, stream, counters)
+                      : launch_awgn(code, ebno_db, seed, first, m, w.received_bytes(), sent, stream, counters);
+  }, [&](McWorkspace &w, size_t m) { return launch_decoder(code, w, nullptr, nullptr, m, stream); });
+}
+
 // cc_mc_run_chase_dev: the plain route above with the decoder swapped -- the channel writes floats (and counts its bit
 // errors), launch_chase decodes them into w.hard / w.nerr / w.status, the counting pass is the hard decoders' (no
 // iteration counters).  Checked by the caller: a binary BCH handle with a hard tag that launch_chase serves.
 int mc_run_chase(cc_code *code, unsigned p, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
                  int random_codewords, uint64_t *d_counters, hipStream_t stream) {
-  if (frames == 0) return CC_OK;
-  const size_t chunk = frames < MC_CHUNK ? frames : MC_CHUNK;
   unsigned long long *counters = reinterpret_cast<unsigned long long *>(d_counters);
-  return mc_chunked(code, frames, chunk, chunk, stream, [&](McWorkspace &w, size_t done, size_t m) -> int {
-    return mc_route(code, w, seed, first_frame + done, m, random_codewords, d_counters, stream, [&](const uint8_t *sent) {
-      return launch_awgn(code, ebno_db, seed, first_frame + done, m, w.llr, sent, stream, counters);
-    }, [&] { return launch_chase(code, w.llr, p, w.hard, w.nerr, nullptr, w.status, m, stream); });
-  });
+  return mc_run_awgn(code, seed, first_frame, frames, random_codewords, d_counters, stream,
+                     [&](McWorkspace &w, uint64_t first, size_t m, const uint8_t *sent) {
+    return launch_awgn(code, ebno_db, seed, first, m, w.llr, sent, stream, counters);
+  }, [&](McWorkspace &w, size_t m) { return launch_chase(code, w.llr, p, w.hard, w.nerr, nullptr, w.status, m, stream); });
 }
 
 // cc_mc_run_osd_dev: the same with launch_osd at `order` (every frame decodes: CC_MC_FAILURES stays 0).  Checked by the
 // caller: a binary BCH handle with a hard tag that launch_osd serves.
 int mc_run_osd(cc_code *code, unsigned order, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
                int random_codewords, uint64_t *d_counters, hipStream_t stream) {
-  if (frames == 0) return CC_OK;
-  const size_t chunk = frames < MC_CHUNK ? frames : MC_CHUNK;
   unsigned long long *counters = reinterpret_cast<unsigned long long *>(d_counters);
-  return mc_chunked(code, frames, chunk, chunk, stream, [&](McWorkspace &w, size_t done, size_t m) -> int {
-    return mc_route(code, w, seed, first_frame + done, m, random_codewords, d_counters, stream, [&](const uint8_t *sent) {
-      return launch_awgn(code, ebno_db, seed, first_frame + done, m, w.llr, sent, stream, counters);
-    }, [&] { return launch_osd(code, w.llr, order, w.hard, w.nerr, nullptr, w.status, m, stream); });
-  });
+  return mc_run_awgn(code, seed, first_frame, frames, random_codewords, d_counters, stream,
+                     [&](McWorkspace &w, uint64_t first, size_t m, const uint8_t *sent) {
+    return launch_awgn(code, ebno_db, seed, first, m, w.llr, sent, stream, counters);
+  }, [&](McWorkspace &w, size_t m) { return launch_osd(code, w.llr, order, w.hard, w.nerr, nullptr, w.status, m, stream); });
 }
 
 // cc_awgn_llr_dev: channel only
@@ -701,14 +723,11 @@ int launch_awgn_symbols(const cc_code *code, double ebno_db, uint64_t seed, uint
 // are decoded in place, the reliabilities in w.llr.  Checked by the caller: an RS handle that launch_gmd serves.
 int mc_run_gmd(cc_code *code, unsigned m, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames,
                int random_codewords, uint64_t *d_counters, hipStream_t stream) {
-  if (frames == 0) return CC_OK;
-  const size_t chunk = frames < MC_CHUNK ? frames : MC_CHUNK;
   unsigned long long *counters = reinterpret_cast<unsigned long long *>(d_counters);
-  return mc_chunked(code, frames, chunk, chunk, stream, [&](McWorkspace &w, size_t done, size_t mm) -> int {
-    return mc_route(code, w, seed, first_frame + done, mm, random_codewords, d_counters, stream, [&](const uint8_t *sent) {
-      return launch_awgn_symbols(code, ebno_db, seed, first_frame + done, mm, w.hard, w.llr, sent, counters, stream);
-    }, [&] { return launch_gmd(code, w.hard, w.llr, m, w.hard, w.nerr, nullptr, w.status, mm, stream); });
-  });
+  return mc_run_awgn(code, seed, first_frame, frames, random_codewords, d_counters, stream,
+                     [&](McWorkspace &w, uint64_t first, size_t mm, const uint8_t *sent) {
+    return launch_awgn_symbols(code, ebno_db, seed, first, mm, w.hard, w.llr, sent, counters, stream);
+  }, [&](McWorkspace &w, size_t mm) { return launch_gmd(code, w.hard, w.llr, m, w.hard, w.nerr, nullptr, w.status, mm, stream); });
 }
 
 // cc_awgn_symbols_dev: channel only
@@ -1003,7 +1022,7 @@ struct DiscreteIO {
 // w.list.
 DiscreteIO workspace_list(McWorkspace &w, size_t m, size_t n) {
   DiscreteIO io;
-  io.er = reinterpret_cast<uint16_t *>(reinterpret_cast<uint8_t *>(w.llr) + ((m * n + 15) & ~size_t(15)));
+  io.er = reinterpret_cast<uint16_t *>(w.received_bytes() + ((m * n + 15) & ~size_t(15)));
   io.off = w.list;
   io.tiles = w.list + m + 1;
   io.count = reinterpret_cast<uint32_t *>(w.nerr);
@@ -1075,7 +1094,7 @@ int mc_run_discrete(cc_code *code, double p_error, double p_erasure, uint64_t se
       io.soft = w.llr;
     } else {
       if (th.E) io = workspace_list(w, m, n);  // (no erasure can be drawn with E = 0: no list, NULL erasures)
-      io.recv = reinterpret_cast<uint8_t *>(w.llr);
+      io.recv = w.received_bytes();
     }
     return mc_route(code, w, seed, first_frame + done, m, random_codewords, d_counters, stream, [&](const uint8_t *sent) {
       return launch_discrete(code, th, seed, first_frame + done, m, sent, io,
@@ -1449,7 +1468,7 @@ int run_burst(cc_code *code, const cc_burst_channel &ch, const DetectorThreshold
     if (code->soft) {
       io.soft = w.llr;
     } else {
-      io.recv = reinterpret_cast<uint8_t *>(w.llr);
+      io.recv = w.received_bytes();
       if (det) {
         io.flag_fm = w.hard;
         list = workspace_list(w, m, n);

@@ -19,12 +19,14 @@
 //   product_count_kernel
 //                       per block the wrong bits among its N values and whether a component word of the last
 //                       half-iteration failed, into the CC_MC_* slots: one wavefront per block, the counts of a
-//                       wavefront in registers, one 64-bit atomic per wavefront and slot at the end
+//                       wavefront in registers, one 64-bit atomic per wavefront and slot at the end; for the
+//                       hard-decision decoder (product_hard.hip) also the half-iterations the blocks took
 //
 // The byte turns (out, the encoder's intermediate words) are launch_interleave at width 1: I = w2 or w1 <= 256.
 // No kernel here touches a value outside the B * N (B * lines) it is given.
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 #include <utility>
 
 #include "cc_internal.hpp"
@@ -111,14 +113,18 @@ resize_rows_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, in
   }
 }
 
-// decided: B blocks of N bytes; sent: the blocks sent (nullptr: the all-zero word); status: `lines` entries per block
+// decided: B blocks of N bytes; sent: the blocks sent (nullptr: the all-zero word); status: `lines` entries per block;
+// last: the half-iterations a block took, one per block, into CC_MC_ITER_SUM and the histogram slot of the block (one
+// atomic of its own), or nullptr: both are left alone
 __global__ void __launch_bounds__(256)
 product_count_kernel(const uint8_t *__restrict__ decided, const uint8_t *__restrict__ sent, const int32_t *__restrict__ status,
-                     unsigned long long N, int lines, unsigned long long blocks, unsigned long long *__restrict__ counters) {
+                     const int32_t *__restrict__ last, unsigned long long N, int lines, unsigned long long blocks,
+                     unsigned long long *__restrict__ counters) {
   const int lane = threadIdx.x & 63;
   const unsigned long long wave = static_cast<unsigned long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
   const unsigned long long waves = static_cast<unsigned long long>(gridDim.x) * 4;
-  unsigned long long c_frames = 0, c_bit = 0, c_word = 0, c_fail = 0, c_und = 0;  // lane 0: of the blocks this wavefront saw
+  // lane 0: of the blocks this wavefront saw
+  unsigned long long c_frames = 0, c_bit = 0, c_word = 0, c_fail = 0, c_und = 0, c_iter = 0;
   for (unsigned long long b = wave; b < blocks; b += waves) {
     const uint8_t *d = decided + b * N, *s = sent ? sent + b * N : nullptr;
     unsigned cnt = 0;
@@ -132,6 +138,11 @@ product_count_kernel(const uint8_t *__restrict__ decided, const uint8_t *__restr
     c_word += (failed || cnt) ? 1u : 0u;
     c_fail += failed ? 1u : 0u;
     c_und += (!failed && cnt) ? 1u : 0u;
+    if (last) {
+      const int32_t it = last[b];
+      c_iter += static_cast<unsigned long long>(it);
+      if (lane == 0) atomicAdd(&counters[CC_MC_ITER_HIST + (it < 55 ? it : 55)], 1ull);
+    }
   }
   if (lane == 0 && c_frames) {
     atomicAdd(&counters[CC_MC_FRAMES], c_frames);
@@ -139,6 +150,7 @@ product_count_kernel(const uint8_t *__restrict__ decided, const uint8_t *__restr
     if (c_word) atomicAdd(&counters[CC_MC_WORD_ERRORS], c_word);
     if (c_fail) atomicAdd(&counters[CC_MC_FAILURES], c_fail);
     if (c_und) atomicAdd(&counters[CC_MC_UNDETECTED], c_und);
+    if (c_iter) atomicAdd(&counters[CC_MC_ITER_SUM], c_iter);
   }
 }
 
@@ -182,6 +194,28 @@ int turn_bytes(const uint8_t *in, uint8_t *out, size_t blocks, size_t R, size_t 
   return launch_interleave(in, 1, C, R, out, blocks * R, true, stream);
 }
 
+// stream-ordered scratch of one call, returned to the pool on every way out
+struct Scratch {
+  const cc_code *code;
+  hipStream_t stream;
+  void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  int used = 0;
+  Scratch(const cc_code *c, hipStream_t s) : code(c), stream(s) {}
+  Scratch(const Scratch &) = delete;
+  Scratch &operator=(const Scratch &) = delete;
+  ~Scratch() {
+    for (int i = 0; i < used; ++i)
+      if (p[i]) (void)hipFreeAsync(p[i], stream);
+  }
+  template <class T>
+  hipError_t get(T **out, size_t bytes) {
+    const hipError_t e = workspace_alloc(code, &p[used], bytes ? bytes : 1, stream);
+    *out = static_cast<T *>(p[used]);
+    if (e == hipSuccess) ++used;
+    return e;
+  }
+};
+
 }  // namespace
 
 ProductShape product_shape(const cc_product *pc) {
@@ -204,7 +238,7 @@ int launch_product_decode(const cc_product *pc, const float *d_y, uint8_t *d_out
   const int w1 = static_cast<int>(s.w1), w2 = static_cast<int>(s.w2);
   const size_t total = B * s.N;
   const unsigned halves = pc->halves;
-  WorkspaceScratch scratch(rows, stream);
+  Scratch scratch(rows, stream);
   float *X = nullptr, *W = nullptr;
   uint8_t *O = nullptr;
   CC_HIP_TRY(scratch.get(&X, total * sizeof(float)));
@@ -242,7 +276,7 @@ int launch_product_encode(const cc_product *pc, const uint8_t *d_msg, uint8_t *d
   const cc_code *rows = pc->rows, *cols = pc->cols;
   const ProductShape s = product_shape(pc);
   const size_t n1 = rows->tab.n, n2 = cols->tab.n;
-  WorkspaceScratch scratch(rows, stream);
+  Scratch scratch(rows, stream);
   uint8_t *a = nullptr, *b = nullptr;
   CC_HIP_TRY(scratch.get(&a, B * s.N));
   CC_HIP_TRY(scratch.get(&b, B * s.N));
@@ -262,7 +296,7 @@ int launch_product_extract(const cc_product *pc, const uint8_t *d_cw, uint8_t *d
   const cc_code *rows = pc->rows, *cols = pc->cols;
   const ProductShape s = product_shape(pc);
   const size_t n1 = rows->tab.n, n2 = cols->tab.n;
-  WorkspaceScratch scratch(rows, stream);
+  Scratch scratch(rows, stream);
   uint8_t *a = nullptr, *b = nullptr;
   CC_HIP_TRY(scratch.get(&a, B * s.N));
   CC_HIP_TRY(scratch.get(&b, B * s.N));
@@ -281,20 +315,20 @@ int launch_product_extract(const cc_product *pc, const uint8_t *d_cw, uint8_t *d
   return rc;
 }
 
-int launch_product_count(const cc_product *pc, const uint8_t *d_decided, const uint8_t *d_sent, const int32_t *d_status,
-                         size_t B, uint64_t *d_counters, hipStream_t stream) {
+// d_sent == nullptr: the all-zero block; d_status: `lines` entries per block; d_last: one per block or nullptr
+static int launch_product_count(const cc_product *pc, const uint8_t *d_decided, const uint8_t *d_sent, const int32_t *d_status,
+                                const int32_t *d_last, size_t lines, size_t B, uint64_t *d_counters, hipStream_t stream) {
   if (B == 0) return CC_OK;
-  const ProductShape s = product_shape(pc);
-  const int lines = static_cast<int>((pc->halves & 1) ? s.w2 : s.w1);
   hipLaunchKernelGGL(product_count_kernel, dim3(grid_of(pc->rows, (static_cast<unsigned long long>(B) + 3) / 4)), dim3(256), 0,
-                     stream, d_decided, d_sent, d_status, static_cast<unsigned long long>(s.N), lines,
-                     static_cast<unsigned long long>(B), reinterpret_cast<unsigned long long *>(d_counters));
+                     stream, d_decided, d_sent, d_status, d_last, static_cast<unsigned long long>(product_shape(pc).N),
+                     static_cast<int>(lines), static_cast<unsigned long long>(B),
+                     reinterpret_cast<unsigned long long *>(d_counters));
   return launched("product count kernel launch");
 }
 
 // Blocks per chunk of the Monte-Carlo and channel routes: 2^24 values (CC_AMD_PRODUCT_MC_CHUNK_VALUES: tests cross a chunk
 // boundary with a small call), about 18 bytes of workspace per value, at least one block
-size_t product_chunk_blocks(size_t N, size_t blocks) {
+static size_t product_chunk_blocks(size_t N, size_t blocks) {
   static const size_t chunk_values = [] {
     const char *e = std::getenv("CC_AMD_PRODUCT_MC_CHUNK_VALUES");
     const long long v = e ? std::atoll(e) : 0;
@@ -306,7 +340,7 @@ size_t product_chunk_blocks(size_t N, size_t blocks) {
 }
 
 // the blocks sent for the global blocks [first, first + m): l = k1 k2 random bits per block through the product encoder
-int product_sent(const cc_product *pc, uint64_t seed, uint64_t first, size_t m, uint8_t *d_msg, uint8_t *d_sent,
+static int product_sent(const cc_product *pc, uint64_t seed, uint64_t first, size_t m, uint8_t *d_msg, uint8_t *d_sent,
                         hipStream_t stream) {
   const ProductShape s = product_shape(pc);
   if (int rc = launch_random_bits(pc->rows, static_cast<int>(s.k1 * s.k2), seed, first, m, d_msg, stream)) return rc;
@@ -324,7 +358,7 @@ int product_awgn(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t f
     return launch_awgn_values(pc->rows, N, sigma, seed, first_block, blocks, d_y, nullptr, stream);
   }
   const size_t chunk = product_chunk_blocks(s.N, blocks);
-  WorkspaceScratch scratch(pc->rows, stream);
+  Scratch scratch(pc->rows, stream);
   uint8_t *msg = nullptr, *words = nullptr;
   CC_HIP_TRY(scratch.get(&msg, chunk * s.k1 * s.k2));
   if (!d_sent) CC_HIP_TRY(scratch.get(&words, chunk * s.N));
@@ -337,36 +371,68 @@ int product_awgn(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t f
   return CC_OK;
 }
 
-// channel, decoder with the hard output in its last half-iteration, count: chunk by chunk, the counters of a block a
-// function of (seed, ebno, pc, global block index) alone
-int mc_run_product(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
-                   int random_codewords, uint64_t *d_counters, hipStream_t stream) {
+// One Monte-Carlo route for both decoders, chunk by chunk: the blocks sent, the channel, decode(m, received, decided,
+// status, last), the count.  The counters of a block are a function of (seed, ebno, pc, global block index) alone.
+// T = float: the channel writes y, the decoder its decisions next to it.  T = uint8_t: the channel launch writes the hard
+// decisions z = (y < 0) itself, the decoder runs in place and reports `last`.  lines: status entries per block.
+template <class T, class Decode>
+static int mc_product_route(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
+                            int random_codewords, size_t lines, uint64_t *d_counters, hipStream_t stream, Decode decode) {
+  constexpr bool hard = std::is_same<T, uint8_t>::value;
   if (blocks == 0) return CC_OK;
   const ProductShape s = product_shape(pc);
   const float sigma = static_cast<float>(cc_product_sigma(pc, ebno_db));
-  const size_t chunk = product_chunk_blocks(s.N, blocks), lines = (pc->halves & 1) ? s.w2 : s.w1;
-  WorkspaceScratch scratch(pc->rows, stream);
-  float *y = nullptr;
+  const size_t chunk = product_chunk_blocks(s.N, blocks);
+  Scratch scratch(pc->rows, stream);
+  T *received = nullptr;
   uint8_t *decided = nullptr, *sent = nullptr, *msg = nullptr;
-  int32_t *status = nullptr;
-  CC_HIP_TRY(scratch.get(&y, chunk * s.N * sizeof(float)));
-  CC_HIP_TRY(scratch.get(&decided, chunk * s.N));
+  int32_t *status = nullptr, *last = nullptr;
+  CC_HIP_TRY(scratch.get(&received, chunk * s.N * sizeof(T)));
+  if constexpr (hard)
+    decided = received;
+  else
+    CC_HIP_TRY(scratch.get(&decided, chunk * s.N));
   CC_HIP_TRY(scratch.get(&status, chunk * lines * sizeof(int32_t)));
+  if (hard) CC_HIP_TRY(scratch.get(&last, chunk * sizeof(int32_t)));
   if (random_codewords) {
     CC_HIP_TRY(scratch.get(&sent, chunk * s.N));
     CC_HIP_TRY(scratch.get(&msg, chunk * s.k1 * s.k2));
   }
+  unsigned long long *counters = reinterpret_cast<unsigned long long *>(d_counters);
   for (size_t done = 0; done < blocks; done += chunk) {
     const size_t m = blocks - done < chunk ? blocks - done : chunk;
     if (random_codewords)
       if (int rc = product_sent(pc, seed, first_block + done, m, msg, sent, stream)) return rc;
-    if (int rc = launch_awgn_values(pc->rows, static_cast<int>(s.N), sigma, seed, first_block + done, m, y, sent, stream,
-                                    reinterpret_cast<unsigned long long *>(d_counters)))
-      return rc;
-    if (int rc = launch_product_decode(pc, y, decided, nullptr, status, m, stream)) return rc;
-    if (int rc = launch_product_count(pc, decided, sent, status, m, d_counters, stream)) return rc;
+    int rc;
+    if constexpr (hard)
+      rc = launch_awgn_hard(pc->rows, static_cast<int>(s.N), sigma, seed, first_block + done, m, received, sent, stream, counters);
+    else
+      rc = launch_awgn_values(pc->rows, static_cast<int>(s.N), sigma, seed, first_block + done, m, received, sent, stream, counters);
+    if (rc != CC_OK) return rc;
+    if ((rc = decode(m, received, decided, status, last)) != CC_OK) return rc;
+    if ((rc = launch_product_count(pc, decided, sent, status, last, lines, m, d_counters, stream)) != CC_OK) return rc;
   }
   return CC_OK;
+}
+
+// the turbo decoder with the hard output in its last half-iteration, whose component words give the status
+int mc_run_product(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
+                   int random_codewords, uint64_t *d_counters, hipStream_t stream) {
+  const ProductShape s = product_shape(pc);
+  return mc_product_route<float>(pc, ebno_db, seed, first_block, blocks, random_codewords, (pc->halves & 1) ? s.w2 : s.w1,
+                                 d_counters, stream,
+                                 [&](size_t m, const float *y, uint8_t *decided, int32_t *status, int32_t *) {
+    return launch_product_decode(pc, y, decided, nullptr, status, m, stream);
+  });
+}
+
+// the hard-decision decoder (product_hard.hip), one status per block
+int mc_run_product_hard(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
+                        int random_codewords, uint64_t *d_counters, hipStream_t stream) {
+  return mc_product_route<uint8_t>(pc, ebno_db, seed, first_block, blocks, random_codewords, 1, d_counters, stream,
+                                   [&](size_t m, const uint8_t *z, uint8_t *decided, int32_t *status, int32_t *last) {
+    return launch_product_hard(pc, z, decided, nullptr, last, status, m, stream);
+  });
 }
 
 }  // namespace ccamd

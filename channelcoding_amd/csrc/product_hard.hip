@@ -340,41 +340,6 @@ product_hard_kernel(const AlgebraicTables *__restrict__ Tr, const AlgebraicTable
   }
 }
 
-// decided: B blocks of N bytes; sent: the blocks sent (nullptr: the all-zero block); status and last: one per block.
-// One wavefront per block as in product_count_kernel; the histogram slot of a block takes one atomic of its own.
-__global__ void __launch_bounds__(256)
-product_hard_count_kernel(const uint8_t *__restrict__ decided, const uint8_t *__restrict__ sent, const int32_t *__restrict__ status,
-                          const int32_t *__restrict__ last, unsigned long long N, unsigned long long blocks,
-                          unsigned long long *__restrict__ counters) {
-  const int lane = threadIdx.x & 63;
-  const unsigned long long wave = static_cast<unsigned long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
-  const unsigned long long waves = static_cast<unsigned long long>(gridDim.x) * 4;
-  unsigned long long c_frames = 0, c_bit = 0, c_word = 0, c_fail = 0, c_und = 0, c_iter = 0;
-  for (unsigned long long b = wave; b < blocks; b += waves) {
-    const uint8_t *d = decided + b * N, *s = sent ? sent + b * N : nullptr;
-    unsigned cnt = 0;
-    for (unsigned long long i = lane; i < N; i += 64) cnt += (d[i] != (s ? s[i] : 0)) ? 1u : 0u;
-    for (int m = 32; m >= 1; m >>= 1) cnt += static_cast<unsigned>(__shfl_xor(static_cast<int>(cnt), m, 64));
-    const bool failed = status[b] != CC_FRAME_OK;
-    const int32_t it = last[b];
-    c_frames += 1;
-    c_bit += cnt;
-    c_word += (failed || cnt) ? 1u : 0u;
-    c_fail += failed ? 1u : 0u;
-    c_und += (!failed && cnt) ? 1u : 0u;
-    c_iter += static_cast<unsigned long long>(it);
-    if (lane == 0) atomicAdd(&counters[CC_MC_ITER_HIST + (it < 55 ? it : 55)], 1ull);
-  }
-  if (lane == 0 && c_frames) {
-    atomicAdd(&counters[CC_MC_FRAMES], c_frames);
-    if (c_bit) atomicAdd(&counters[CC_MC_BIT_ERRORS], c_bit);
-    if (c_word) atomicAdd(&counters[CC_MC_WORD_ERRORS], c_word);
-    if (c_fail) atomicAdd(&counters[CC_MC_FAILURES], c_fail);
-    if (c_und) atomicAdd(&counters[CC_MC_UNDETECTED], c_und);
-    if (c_iter) atomicAdd(&counters[CC_MC_ITER_SUM], c_iter);
-  }
-}
-
 }  // namespace
 
 int launch_product_hard(const cc_product *pc, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip, int32_t *d_last,
@@ -408,43 +373,6 @@ int launch_product_hard(const cc_product *pc, const uint8_t *d_in, uint8_t *d_ou
                      static_cast<unsigned long long>(B), static_cast<int>(pc->halves), s.e, col_bytes);
   const hipError_t err = hipGetLastError();
   return err != hipSuccess ? hip_fail(err, "product hard kernel launch") : CC_OK;
-}
-
-// channel with the hard decision z = (y < 0) written as bytes by the channel launch itself, the decoder in place, count:
-// chunk by chunk, the counters of a block a function of (seed, ebno, pc, global block index) alone
-int mc_run_product_hard(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
-                        int random_codewords, uint64_t *d_counters, hipStream_t stream) {
-  if (blocks == 0) return CC_OK;
-  const ProductShape s = product_shape(pc);
-  const float sigma = static_cast<float>(cc_product_sigma(pc, ebno_db));
-  const size_t chunk = product_chunk_blocks(s.N, blocks);
-  WorkspaceScratch scratch(pc->rows, stream);
-  uint8_t *z = nullptr, *sent = nullptr, *msg = nullptr;
-  int32_t *status = nullptr, *last = nullptr;
-  CC_HIP_TRY(scratch.get(&z, chunk * s.N));
-  CC_HIP_TRY(scratch.get(&status, chunk * sizeof(int32_t)));
-  CC_HIP_TRY(scratch.get(&last, chunk * sizeof(int32_t)));
-  if (random_codewords) {
-    CC_HIP_TRY(scratch.get(&sent, chunk * s.N));
-    CC_HIP_TRY(scratch.get(&msg, chunk * s.k1 * s.k2));
-  }
-  for (size_t done = 0; done < blocks; done += chunk) {
-    const size_t m = blocks - done < chunk ? blocks - done : chunk;
-    if (random_codewords)
-      if (int rc = product_sent(pc, seed, first_block + done, m, msg, sent, stream)) return rc;
-    if (int rc = launch_awgn_values(pc->rows, static_cast<int>(s.N), sigma, seed, first_block + done, m,
-                                    reinterpret_cast<float *>(z), sent, stream,
-                                    reinterpret_cast<unsigned long long *>(d_counters), true))
-      return rc;
-    if (int rc = launch_product_hard(pc, z, z, nullptr, last, status, m, stream)) return rc;
-    const unsigned long long want = (static_cast<unsigned long long>(m) + 3) / 4, cap = static_cast<unsigned long long>(pc->rows->num_cus) * 8;
-    hipLaunchKernelGGL(product_hard_count_kernel, dim3(static_cast<unsigned>(want < cap ? want : cap)), dim3(256), 0, stream, z,
-                       sent, status, last, static_cast<unsigned long long>(s.N), static_cast<unsigned long long>(m),
-                       reinterpret_cast<unsigned long long *>(d_counters));
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return hip_fail(err, "product hard count kernel launch");
-  }
-  return CC_OK;
 }
 
 }  // namespace ccamd

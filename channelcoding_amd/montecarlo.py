@@ -131,6 +131,7 @@ class DeviceBackend:
     """Counts one shard of one Eb/N0 point on this rank's GPU through cc_mc_run_dev."""
 
     symbol, leading = "cc_mc_run_dev", ()  # the entry point and the arguments between the handle and Eb/N0
+    desc = None  # the cc_product of a product backend: the call takes it by reference in place of the handle
 
     def __init__(self, code, random_codewords=False):
         import torch
@@ -139,11 +140,15 @@ class DeviceBackend:
         self.random_codewords = bool(random_codewords)
         self.device = torch.device("cuda", torch.cuda.current_device())
 
+    def target(self):
+        """The first argument of the call."""
+        return self.code._h if self.desc is None else C.byref(self.desc)
+
     def run(self, ebno_db, seed, first_frame, frames):
         torch = self.torch
         counters = torch.zeros(capi.MC_NCOUNTERS, dtype=torch.int64, device=self.device)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = getattr(capi.lib(), self.symbol)(self.code._h, *self.leading, float(ebno_db), int(seed), int(first_frame),
+        rc = getattr(capi.lib(), self.symbol)(self.target(), *self.leading, float(ebno_db), int(seed), int(first_frame),
                                               int(frames), int(self.random_codewords), C.c_void_p(counters.data_ptr()), stream)
         capi.check(rc, self.symbol)
         return counters  # stays on the device: reduced with RCCL
@@ -189,16 +194,14 @@ class GmdBackend(DeviceBackend):
         self.leading = (self.m,)
 
 
-class ProductBackend:
+class ProductBackend(DeviceBackend):
     """Counts one shard of blocks of one Eb/N0 point through cc_mc_run_product_dev: a product_code decoded with len(alpha)
     half-iterations of the Chase-Pyndiah decoder at p."""
 
+    symbol = "cc_mc_run_product_dev"
+
     def __init__(self, pc, p, alpha, beta, random_codewords=False):
-        import torch
-        self.torch = torch
-        self.code = pc
-        self.random_codewords = bool(random_codewords)
-        self.device = torch.device("cuda", torch.cuda.current_device())
+        super().__init__(pc, random_codewords)
         self.p = int(p)
         if not 0 <= self.p <= capi.CHASE_MAX_P:
             raise ValueError("p in 0 .. %d" % capi.CHASE_MAX_P)
@@ -206,37 +209,16 @@ class ProductBackend:
             raise ValueError("one alpha and one beta per half-iteration, at least one")
         self.desc = pc._pc(self.p, alpha, beta)
 
-    def run(self, ebno_db, seed, first_block, blocks):
-        torch = self.torch
-        counters = torch.zeros(capi.MC_NCOUNTERS, dtype=torch.int64, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = capi.lib().cc_mc_run_product_dev(C.byref(self.desc), float(ebno_db), int(seed), int(first_block), int(blocks),
-                                              int(self.random_codewords), C.c_void_p(counters.data_ptr()), stream)
-        capi.check(rc, "cc_mc_run_product_dev")
-        return counters
 
-
-class ProductHardBackend:
+class ProductHardBackend(DeviceBackend):
     """Counts one shard of blocks of one Eb/N0 point through cc_mc_run_product_hard_dev: a product_code decoded with
     `halves` half-iterations of bounded-distance row / column decoding on the hard decisions of the channel."""
 
-    def __init__(self, pc, halves, random_codewords=False):
-        import torch
-        self.torch = torch
-        self.code = pc
-        self.random_codewords = bool(random_codewords)
-        self.device = torch.device("cuda", torch.cuda.current_device())
-        self.desc = pc._pc_hard(halves)
+    symbol = "cc_mc_run_product_hard_dev"
 
-    def run(self, ebno_db, seed, first_block, blocks):
-        torch = self.torch
-        counters = torch.zeros(capi.MC_NCOUNTERS, dtype=torch.int64, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = capi.lib().cc_mc_run_product_hard_dev(C.byref(self.desc), float(ebno_db), int(seed), int(first_block),
-                                                   int(blocks), int(self.random_codewords),
-                                                   C.c_void_p(counters.data_ptr()), stream)
-        capi.check(rc, "cc_mc_run_product_hard_dev")
-        return counters
+    def __init__(self, pc, halves, random_codewords=False):
+        super().__init__(pc, random_codewords)
+        self.desc = pc._pc_hard(halves)
 
 
 class _ShardedSimulation:
@@ -322,36 +304,19 @@ class _ShardedSimulation:
         return results
 
 
-class awgn_simulation(_ShardedSimulation):
-    """awgn_simulation(decoder, step = 0.5, seed = 0) -- simulation.h:71-83."""
+class _EbnoLadder(_ShardedSimulation):
+    """What the three Eb/N0 ladders share: step, seed, backend, log directory and the caps, the points from
+    ladder(code.rate) (simulation.c++:105-107) unless start / stop say otherwise, and the counters of a point."""
 
-    def __init__(self, code, step=0.5, seed=0, random_codewords=False, backend=None, log_dir=None,
-                 max_samples=None, start=None, stop=None, samples_per_point=None, chase=None, gmd=None, osd=None):
+    def __init__(self, code, backend, step, seed, log_dir, max_samples, start, stop, samples_per_point):
         self.code = code
         self.step = float(step)
         self.seed = int(seed)
-        # chase=p: every frame goes through Chase-II (ChaseBackend); the log name carries -chaseP
-        self.chase = None if chase is None else int(chase)
-        # gmd=m (RS): every frame goes through GMD with m trials (GmdBackend, True: all of them); the log name carries -gmdM
-        if gmd is not None and chase is not None:
-            raise TypeError("gmd= does not combine with chase=")
-        # osd=order: every frame goes through ordered-statistics decoding (OsdBackend); the log name carries -osdO
-        if osd is not None and (chase is not None or gmd is not None):
-            raise TypeError("osd= does not combine with chase= or gmd=")
-        self.osd = None if osd is None else int(osd)
-        self.gmd = None if gmd is None else (int(code.t) + 1 if gmd is True else int(gmd))
-        if backend is None:
-            if gmd is not None:
-                backend = GmdBackend(code, gmd, random_codewords)
-            elif osd is not None:
-                backend = OsdBackend(code, osd, random_codewords)
-            else:
-                backend = DeviceBackend(code, random_codewords) if chase is None else ChaseBackend(code, chase, random_codewords)
         self.backend = backend
         self.log_dir = log_dir
         self.max_samples = max_samples
         self.samples_per_point = samples_per_point  # fixed frame count per point instead of the adaptive rule
-        ref_start, _ = ladder(code.rate, self.step)  # simulation.c++:105-107
+        ref_start, _ = ladder(code.rate, self.step)
         self.start = ref_start if start is None else float(start)
         self.stop = (max(8.0, self.start) + self.step / 2) if stop is None else float(stop)
 
@@ -370,6 +335,31 @@ class awgn_simulation(_ShardedSimulation):
         res["ber"] = res["bit_errors"] / max(1, res["frames"] * self.code.n)
         return res
 
+
+class awgn_simulation(_EbnoLadder):
+    """awgn_simulation(decoder, step = 0.5, seed = 0) -- simulation.h:71-83."""
+
+    def __init__(self, code, step=0.5, seed=0, random_codewords=False, backend=None, log_dir=None,
+                 max_samples=None, start=None, stop=None, samples_per_point=None, chase=None, gmd=None, osd=None):
+        # chase=p: every frame goes through Chase-II (ChaseBackend); the log name carries -chaseP
+        self.chase = None if chase is None else int(chase)
+        # gmd=m (RS): every frame goes through GMD with m trials (GmdBackend, True: all of them); the log name carries -gmdM
+        if gmd is not None and chase is not None:
+            raise TypeError("gmd= does not combine with chase=")
+        # osd=order: every frame goes through ordered-statistics decoding (OsdBackend); the log name carries -osdO
+        if osd is not None and (chase is not None or gmd is not None):
+            raise TypeError("osd= does not combine with chase= or gmd=")
+        self.osd = None if osd is None else int(osd)
+        self.gmd = None if gmd is None else (int(code.t) + 1 if gmd is True else int(gmd))
+        if backend is None:
+            if gmd is not None:
+                backend = GmdBackend(code, gmd, random_codewords)
+            elif osd is not None:
+                backend = OsdBackend(code, osd, random_codewords)
+            else:
+                backend = DeviceBackend(code, random_codewords) if chase is None else ChaseBackend(code, chase, random_codewords)
+        super().__init__(code, backend, step, seed, log_dir, max_samples, start, stop, samples_per_point)
+
     def __call__(self):
         """awgn_simulation::operator()(): the whole ladder; rank 0 writes the reference-format log."""
         suffix = "" if self.chase is None else "-chase%d" % self.chase
@@ -380,7 +370,7 @@ class awgn_simulation(_ShardedSimulation):
         return self._ladder(self.code.to_string() + suffix + ".log", "ebno", lambda ebno: ebno)
 
 
-class product_simulation(_ShardedSimulation):
+class product_simulation(_EbnoLadder):
     """The Eb/N0 ladder of a product code (codes.product_code) under the iterative decoder with the schedule alpha, beta
     (one entry each per half-iteration; there is no default) at p Chase positions.  Frames are blocks: sharded by block,
     wer is the block error rate, ber counts the n values of a block.  The ladder starts from ladder(pc.rate); the log
@@ -388,29 +378,19 @@ class product_simulation(_ShardedSimulation):
 
     def __init__(self, pc, p, alpha, beta, step=0.5, seed=0, random_codewords=False, backend=None, log_dir=None,
                  max_samples=None, start=None, stop=None, samples_per_point=None):
-        self.code = pc
         self.p, self.halves = int(p), len(alpha)
         if not self.halves or len(alpha) != len(beta):
             raise ValueError("one alpha and one beta per half-iteration, at least one")
-        self.step = float(step)
-        self.seed = int(seed)
-        self.backend = backend if backend is not None else ProductBackend(pc, p, alpha, beta, random_codewords)
-        self.log_dir = log_dir
-        self.max_samples = max_samples
-        self.samples_per_point = samples_per_point
-        ref_start, _ = ladder(pc.rate, self.step)
-        self.start = ref_start if start is None else float(start)
-        self.stop = (max(8.0, self.start) + self.step / 2) if stop is None else float(stop)
-
-    points = awgn_simulation.points
-    run_point = awgn_simulation.run_point
+        if backend is None:
+            backend = ProductBackend(pc, p, alpha, beta, random_codewords)
+        super().__init__(pc, backend, step, seed, log_dir, max_samples, start, stop, samples_per_point)
 
     def __call__(self):
         name = "%s-chase%d-h%d.log" % (self.code.to_string(), self.p, self.halves)
         return self._ladder(name, "ebno", lambda ebno: ebno)
 
 
-class product_hard_simulation(_ShardedSimulation):
+class product_hard_simulation(_EbnoLadder):
     """The Eb/N0 ladder of a product code under `halves` half-iterations of hard-decision row / column decoding
     (cc_mc_run_product_hard_dev): the ladder and the sharding by block of product_simulation.  The log is
     <pc.to_string()>-hard-h<halves>.log; next to wer it shows the mean of `last`, the half-iterations a block took to
@@ -418,24 +398,15 @@ class product_hard_simulation(_ShardedSimulation):
 
     def __init__(self, pc, halves, step=0.5, seed=0, random_codewords=False, backend=None, log_dir=None,
                  max_samples=None, start=None, stop=None, samples_per_point=None):
-        self.code = pc
         self.halves = int(halves)
         if self.halves < 1:
             raise ValueError("halves >= 1")
-        self.step = float(step)
-        self.seed = int(seed)
-        self.backend = backend if backend is not None else ProductHardBackend(pc, self.halves, random_codewords)
-        self.log_dir = log_dir
-        self.max_samples = max_samples
-        self.samples_per_point = samples_per_point
-        ref_start, _ = ladder(pc.rate, self.step)
-        self.start = ref_start if start is None else float(start)
-        self.stop = (max(8.0, self.start) + self.step / 2) if stop is None else float(stop)
-
-    points = awgn_simulation.points
+        if backend is None:
+            backend = ProductHardBackend(pc, self.halves, random_codewords)
+        super().__init__(pc, backend, step, seed, log_dir, max_samples, start, stop, samples_per_point)
 
     def run_point(self, ebno_db, frames, point_index=0):
-        res = awgn_simulation.run_point(self, ebno_db, frames, point_index)
+        res = super().run_point(ebno_db, frames, point_index)
         res["mean_last"] = res["iter_sum"] / max(1, res["frames"])
         return res
 

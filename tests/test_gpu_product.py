@@ -459,6 +459,32 @@ def test_mc_counters_against_channel_model_and_count(rq_rt, cq_ct, ebno, blocks,
     assert np.array_equal(shards, mc(pc, 4, ebno, seed, 0, blocks, random_codewords))
 
 
+@pytest.mark.parametrize("random_codewords", [True, False], ids=["random", "zero"])
+def test_mc_count_walks_more_than_64_status_entries_of_a_block(random_codewords):
+    """BCH(127,120) x BCH(15,7) at p = 0: after two half-iterations a block has 127 status entries, the columns decoded
+    with the t = 2 code, which does fail -- the count kernel's second trip over a block's entries, a partial one of 63.
+    After one half-iteration there are 15.  Eb/N0 and seed were chosen with the model on the CPU so that some blocks fail
+    at entries >= 64 alone and some at entries < 64 alone (13 and 17 of 64 on awgn_model's channel values); a count that
+    stops after the first 64 entries gets CC_MC_FAILURES and CC_MC_UNDETECTED wrong."""
+    rq_rt, cq_ct, ebno, seed, blocks = (7, 1), (4, 2), 5.0, 2027, 64
+    pc = cc.product_code(*handles(rq_rt, cq_ct))
+    ch = pc.channel(ebno, seed, 0, blocks, random_codewords)
+    y, sent = ch["y"].cpu().numpy(), ch["sent"].cpu().numpy()
+    assert bool(sent.any()) == random_codewords
+    steps = model_steps(M.decoder(*rq_rt), M.decoder(*cq_ct), y, False, p=0, alpha=ALPHA[:2], beta=BETA[:2])
+    assert steps[0]["status"].shape == (blocks, 15) and steps[1]["status"].shape == (blocks, 127)
+    bad = steps[1]["status"] != M.FRAME_OK
+    early, late = bad[:, :64].any(axis=1), bad[:, 64:].any(axis=1)
+    print("blocks failing at entries >= 64 alone", int((late & ~early).sum()), "at entries < 64 alone", int((early & ~late).sum()))
+    assert (late & ~early).any() and (early & ~late).any()
+    for halves in (2, 1):
+        last = steps[halves - 1]
+        expect = counted(last["out"], last["status"], sent, y)
+        got = mc(pc, halves, ebno, seed, 0, blocks, random_codewords, p=0)
+        assert np.array_equal(got, expect), (halves, got[:8], expect[:8])
+    assert expect[capi.MC_FAILURES] == 0  # (one half-iteration: a full-length t = 1 code decodes every word)
+
+
 def test_mc_across_a_chunk_boundary_equals_the_composition():
     """chunks of 100 blocks (the value is read once, so in a process of its own): 512 blocks cross five boundaries"""
     run_child(
