@@ -11,7 +11,17 @@ What the batches are chosen for, and where a condition cannot hold (test_model_b
   batches of those codes have no failed word, and none is asserted.
 - positions with a competitor and positions with +-beta: a code of length 7 or 8 has 16 words and p = 4 gives 16 test
   patterns, whose candidates differ from the winner at every position; +-beta is asserted for the longer components.
-- the block errors fall from the first half-iteration to the last: every case."""
+- the block errors fall from the first half-iteration to the last: every case.
+
+Which case gives which tiling of mix_turn_kernel and of the byte turn (rows per tile = 8448 // (C | 1), capped at R;
+tilings() computes them, test_tilings_of_the_cases holds them):
+- one tile, the whole block: 7_4x15_11, 63_45x63_45 (134 rows would fit), e256_239xe8_4 and its turn, the models' own two
+  cases, every Monte-Carlo code;
+- eight even tiles of 32 rows: e256_239xe256_239;
+- two tiles, the last one short: 255_239x63_57 (63 x 255) has 33 + 30 rows of y in a column pass and in the byte turn,
+  134 + 121 in a row pass and in the turn of `ext`; 63_57x255_239 (255 x 63) has them the other way round;
+- more tiles than the largest grid has workgroups, two a block: test_grid_stride_over_the_tiles_of_a_block;
+- more blocks than the largest grid has workgroups, a tile each: test_grid_stride_trips_of_the_small_kernels."""
 import ctypes as C
 import functools
 import os
@@ -41,12 +51,31 @@ pytestmark = pytest.mark.gpu
 # holds what it was chosen for), blocks, seed
 CASES = {
     "7_4x15_11": ((3, 1), (4, 1), False, 2.0, 67, 11),           # 15 x 7: narrower than any tile, odd, non-square
-    "63_45x63_45": ((6, 3), (6, 3), False, 2.5, 8, 12),          # more than one tile a side, ragged edge, t = 3
+    "63_45x63_45": ((6, 3), (6, 3), False, 2.5, 8, 12),          # one tile of 63 odd rows, eight blocks, t = 3: words fail
     "e256_239xe8_4": ((8, 2), (3, 1), True, 3.5, 16, 13),        # 8 x 256: the 256 side along the rows
     "e8_4xe256_239": ((3, 1), (8, 2), True, 3.5, 16, 14),        # 256 x 8: its turn
-    "e256_239xe256_239": ((8, 2), (8, 2), True, 4.5, 2, 15),     # a full block, 64 Ki values
+    "e256_239xe256_239": ((8, 2), (8, 2), True, 4.5, 2, 15),     # a full block, 64 Ki values: eight even tiles
+    "255_239x63_57": ((8, 2), (6, 1), False, 4.0, 3, 21),        # 63 x 255: two ragged tiles in every shape
+    "63_57x255_239": ((6, 1), (8, 2), False, 4.0, 3, 22),        # 255 x 63: its turn
 }
+RAGGED = ("255_239x63_57", "63_57x255_239")
 HALVES = (1, 2, 3, 4)
+TILE = 8448  # values of a tile in LDS, of mix_turn_kernel and of the byte turn alike
+
+
+def tiles_of(R, C):
+    """the rows of the tiles a source array [R][C] is cut into: 8448 // (C | 1) rows a tile, capped at R, the rest last"""
+    TR = min(TILE // (C | 1), R)
+    return [TR] * (R // TR) + ([R % TR] if R % TR else [])
+
+
+def tilings(name):
+    """the tiles of a block in the three shapes of a decode: X of a column pass from y [w2][w1], X of a row pass and a last
+    `ext` from the column-oriented [w1][w2], and the byte turn of a last column pass's `out`, w2 positions of w1"""
+    (rq, _), (cq, _), extended = CASES[name][:3]
+    e = 1 if extended else 0
+    w1, w2 = (1 << rq) - 1 + e, (1 << cq) - 1 + e
+    return dict(mix_column=tiles_of(w2, w1), mix_row_and_turn=tiles_of(w1, w2), byte_turn=tiles_of(w2, w1))
 
 
 def can_fail(qt):
@@ -139,6 +168,23 @@ def test_model_batches_are_not_degenerate(name):
             assert plain.any(), (name, h)
 
 
+def test_tilings_of_the_cases():
+    """what the head of the file says of the tiles, from the launch arithmetic; the two ragged cases have a short last
+    tile in every shape, so a later change of the tile size cannot make them even without this test failing"""
+    for name in sorted(CASES):
+        t = tilings(name)
+        print(name, t)
+        if name in RAGGED:
+            for shape, rows in t.items():
+                assert len(rows) == 2 and 0 < rows[-1] < rows[0], (name, shape, rows)  # R % TR != 0
+        elif name == "e256_239xe256_239":
+            assert all(rows == [32] * 8 for rows in t.values())
+        else:
+            assert all(len(rows) == 1 for rows in t.values()), (name, t)
+    assert tilings("255_239x63_57") == dict(mix_column=[33, 30], mix_row_and_turn=[134, 121], byte_turn=[33, 30])
+    assert tilings("63_57x255_239") == dict(mix_column=[134, 121], mix_row_and_turn=[33, 30], byte_turn=[134, 121])
+
+
 @pytest.mark.parametrize("halves", HALVES)
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_device_equals_model(name, halves):
@@ -211,6 +257,39 @@ def test_grid_stride_trips_of_the_small_kernels():
     assert (steps[2]["out"] != sent[pick]).any(axis=(1, 2)).sum() < (steps[0]["out"] != sent[pick]).any(axis=(1, 2)).sum()
 
 
+def test_grid_stride_over_the_tiles_of_a_block():
+    """BCH(255,239) x BCH(63,57), two ragged tiles a block in every shape, with 77 more blocks than half the largest grid
+    (8 workgroups per compute unit): more tiles than workgroups, so a workgroup comes back for tiles t >= gridDim.x and
+    splits those into block t / 2 and tile t % 2, a short tile after a full one in the same LDS.
+    The model decodes a prefix, a stretch around an odd cut and the suffix; the blocks before and from the cut, decoded on
+    their own, equal the whole."""
+    import torch
+    name = "255_239x63_57"
+    pc = product_of(name)
+    rows, cols = M.decoder(8, 2), M.decoder(6, 1)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    B = 8 * cus // 2 + 77
+    assert all(len(t) == 2 for t in tilings(name).values()) and 2 * B > 8 * cus
+    rng = np.random.default_rng(78)
+    few = encode_blocks(rows, cols, rng.integers(0, 2, (16, cols.l, rows.l)).astype(np.uint8), False)
+    sent = few[rng.integers(0, 16, B)]
+    y = awgn_llr(rng, sent, rows.l * cols.l / sent[0].size, CASES[name][3])
+    yd = torch.from_numpy(y).cuda()
+    cut = (B // 2) | 1
+    pick = np.concatenate([np.arange(6), np.arange(cut - 4, cut + 4), np.arange(B - 6, B)])
+    steps = model_steps(rows, cols, y[pick], False, alpha=ALPHA[:3], beta=BETA[:3])
+    wrong = [int((s["out"] != sent[pick]).sum()) for s in steps]
+    print("blocks", B, "picked", pick.size, "bit errors of the model after each half-iteration", wrong)
+    assert wrong[2] < wrong[0]
+    for halves in (2, 3):
+        whole = pc.correct_batch(yd, P, ALPHA[:halves], BETA[:halves])
+        whole = {k: v.cpu().numpy() for k, v in whole.items()}
+        same({k: v[pick] for k, v in whole.items()}, steps[halves - 1], halves)
+        for lo, hi in ((0, cut), (cut, B)):
+            part = pc.correct_batch(yd[lo:hi], P, ALPHA[:halves], BETA[:halves])
+            same({k: v.cpu().numpy() for k, v in part.items()}, {k: v[lo:hi] for k, v in whole.items()}, (halves, lo))
+
+
 def test_handles_on_different_devices_are_refused_and_an_empty_batch_is_fine():
     """refusal 4 of the header needs a handle with a device, so it is tested here: after what the Chase call refuses for
     either handle, before the schedule"""
@@ -262,7 +341,7 @@ def test_signed_zeros_in_y_with_a_negative_and_a_zero_first_alpha(alpha0):
         same(got, steps[halves - 1], (alpha0, halves))
 
 
-@pytest.mark.parametrize("name", ["7_4x15_11", "63_45x63_45", "e8_4xe256_239"])
+@pytest.mark.parametrize("name", ["7_4x15_11", "63_45x63_45", "e8_4xe256_239", "255_239x63_57", "63_57x255_239"])
 def test_without_ext_the_hard_output_call_gives_the_same_out_and_status(name):
     import torch
     rows, cols, sent, y, steps = case(name)
@@ -383,8 +462,45 @@ def test_encode_equals_the_helper_construction_and_extract_inverts_it(rq_rt, cq_
     assert torch.equal(pc.extract_batch(pc.encode_batch(torch.from_numpy(msg).cuda())).cpu(), torch.from_numpy(msg))
 
 
+def test_encode_and_extract_over_several_trips_of_the_row_kernel():
+    """eBCH(8,4)^2 with an odd number of blocks, three times 32 per compute unit and 77 more: the row kernel that appends
+    (encode) or drops (extract) the parity bit walks 4 B and then 8 B rows, 16 rows a workgroup and at most 8 workgroups per
+    compute unit, so both launches make more than two trips and the last is partial -- rows that are not live next to
+    rows that shuffle.  Every block against the helper construction of one of 256 distinct messages."""
+    import torch
+    r, c = handles((3, 1), (3, 1))
+    pc = cc.product_code(r, c, extended=True)
+    rows = M.decoder(3, 1)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    B = 3 * 32 * cus + 77
+    per_trip = 16 * 8 * cus
+    assert B % 2 == 1 and 4 * B > 2 * per_trip and (4 * B) % per_trip and (8 * B) % per_trip
+    rng = np.random.default_rng(79)
+    few_msg = ((rng.choice(1 << 16, 256, replace=False)[:, None] >> np.arange(16)[None, :]) & 1).astype(np.uint8).reshape(256, 4, 4)
+    few = encode_blocks(rows, rows, few_msg, True)
+    idx = rng.integers(0, 256, B)
+    msg, want = few_msg[idx], few[idx]
+    wm, m = guarded(torch, msg.size, torch.uint8)
+    m.copy_(torch.from_numpy(msg).cuda().reshape(-1))
+    wc, cw = guarded(torch, B * pc.n, torch.uint8)
+    desc = pc._pc()
+    capi.check(capi.lib().cc_product_encode_batch_dev(C.byref(desc), ptr(m), ptr(cw), B, None), "cc_product_encode_batch_dev")
+    torch.cuda.synchronize()
+    assert guards_intact(torch, wc) and guards_intact(torch, wm)
+    got = cw.cpu().numpy().reshape(B, pc.n2, pc.n1)
+    differ = np.flatnonzero((got != want).any(axis=(1, 2)))
+    assert differ.size == 0, ("blocks that differ", differ[:8], differ.size)
+    assert syndromes_vanish(r, got.reshape(-1, pc.n1), True)
+    assert syndromes_vanish(c, np.ascontiguousarray(got.transpose(0, 2, 1)).reshape(-1, pc.n2), True)
+    wb, back = guarded(torch, msg.size, torch.uint8)
+    capi.check(capi.lib().cc_product_extract_batch_dev(C.byref(desc), ptr(cw), ptr(back), B, None), "cc_product_extract_batch_dev")
+    torch.cuda.synchronize()
+    assert guards_intact(torch, wb) and guards_intact(torch, wc)
+    assert np.array_equal(back.cpu().numpy().reshape(msg.shape), msg)
+
+
 # ---- channel ----
-CHANNEL = [((3, 1), (4, 1), False, 300), ((6, 2), (6, 2), True, 40)]  # 15 x 7 and 64 x 64 blocks
+CHANNEL =[((3, 1), (4, 1), False, 300), ((6, 2), (6, 2), True, 40)]  # 15 x 7 and 64 x 64 blocks
 
 
 @pytest.mark.parametrize("rq_rt,cq_ct,extended,blocks", CHANNEL)
@@ -483,6 +599,46 @@ def test_mc_count_walks_more_than_64_status_entries_of_a_block(random_codewords)
         got = mc(pc, halves, ebno, seed, 0, blocks, random_codewords, p=0)
         assert np.array_equal(got, expect), (halves, got[:8], expect[:8])
     assert expect[capi.MC_FAILURES] == 0  # (one half-iteration: a full-length t = 1 code decodes every word)
+
+
+@pytest.mark.parametrize("random_codewords", [True, False], ids=["random", "zero"])
+def test_mc_count_of_several_blocks_per_wavefront(random_codewords):
+    """BCH(7,4)^2 with three times as many blocks as the count kernel's largest grid has wavefronts (8 workgroups of four
+    per compute unit) and 77 more, one chunk: every wavefront sums three or four blocks in registers before its atomics.
+    Want = the composition on the device (the decode call is held to the model by the tests above): channel, the decode
+    call without ext, the counter definitions.  A perfect code has no failed word, so CC_MC_FAILURES is zero here and
+    every wrong block undetected.  Three shards of unequal size sum to the whole."""
+    import torch
+    pc = cc.product_code(*handles((3, 1), (3, 1)))
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    blocks = 3 * 32 * cus + 77
+    assert blocks * pc.n < 1 << 24  # one chunk
+    seed, first, ebno, halves = 2028, (1 << 33) + 5, 2.0, 3
+    ch = pc.channel(ebno, seed, first, blocks, random_codewords)
+    assert bool(ch["sent"].any()) == random_codewords
+    res = pc.correct_batch(ch["y"], P, ALPHA[:halves], BETA[:halves], ext=False)
+    wrong = (res["out"] != ch["sent"]).reshape(blocks, -1).sum(dim=1)
+    failed = (res["status"] != 0).any(dim=1)
+    want = np.zeros(capi.MC_NCOUNTERS, np.int64)
+    want[capi.MC_FRAMES] = blocks
+    want[capi.MC_WORD_ERRORS] = int((failed | (wrong > 0)).sum())
+    want[capi.MC_BIT_ERRORS] = int(wrong.sum())
+    want[capi.MC_FAILURES] = int(failed.sum())
+    want[capi.MC_UNDETECTED] = int((~failed & (wrong > 0)).sum())
+    want[capi.MC_CHANNEL_BIT_ERRORS] = int(((ch["y"] < 0) != (ch["sent"] != 0)).sum())
+    print("counters", want[:7])
+    assert want[capi.MC_WORD_ERRORS] > 0 and want[capi.MC_UNDETECTED] > 0 and want[capi.MC_BIT_ERRORS] > want[capi.MC_WORD_ERRORS]
+    wc, counters = guarded(torch, capi.MC_NCOUNTERS, torch.int64)
+    counters.zero_()
+    desc = pc._pc(P, ALPHA[:halves], BETA[:halves])
+    rc = capi.lib().cc_mc_run_product_dev(C.byref(desc), ebno, seed, first, blocks, int(random_codewords), ptr(counters), None)
+    capi.check(rc, "cc_mc_run_product_dev")
+    torch.cuda.synchronize()
+    assert guards_intact(torch, wc)
+    assert np.array_equal(counters.cpu().numpy(), want), (counters.cpu().numpy()[:8], want[:8])
+    a, b = blocks // 5, blocks // 2 + 1
+    shards = sum(mc(pc, halves, ebno, seed, first + lo, hi - lo, random_codewords) for lo, hi in ((0, a), (a, b), (b, blocks)))
+    assert np.array_equal(shards, want)
 
 
 def test_mc_across_a_chunk_boundary_equals_the_composition():

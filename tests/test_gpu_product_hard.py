@@ -16,7 +16,14 @@ they are chosen for).  The shapes, the smallest at which each mapping of the ker
   255_239x255_239           bit index no multiple of 32
   e256_239xe256_239 (_noisy)  the full block, converging and not
   255_131x15_11             2t = 32 on one side: the largest Berlekamp-Massey columns
-  255_131x255_239           2t = 32 next to a block of 255 lines: more LDS than the default limit of a workgroup"""
+  255_131x255_239           2t = 32 next to a block of 255 lines: more LDS than the default limit of a workgroup
+Past the first block of a workgroup (TRIPS there, sized from the device's compute units) and past 8 half-iterations
+(LONG there):
+  127_113x7_4 and its turn  twice the largest grid of the workgroup-per-block kernel and 77 more: a second and a third
+                            block in the same LDS, wavefronts without a line
+  63_45x63_45 (trips)       the same for a wavefront of the other kernel, 63 of 64 lanes, t = 3
+  15_11x15_11 (long)        56, 57 and 60 half-iterations, blocks in a cycle with `last` = halves; in the Monte-Carlo
+                            route the last histogram slot at 55 and 60, and three blocks per wavefront of the count"""
 import ctypes as C
 import os
 import subprocess
@@ -30,7 +37,8 @@ from channelcoding_amd import capi
 from channelcoding_amd.montecarlo import ProductHardBackend
 import product_hard_model as PH
 from test_gpu_chase_soft import GUARD, SENTINEL, guarded, guards_intact  # noqa: F401
-from test_product_hard_host import CASES, HALVES, case, encode_blocks, model_outputs
+from test_product_hard_host import (CASES, HALVES, LONG_HALVES, TRIP_HALVES, TRIPS, case, encode_blocks, long_case,
+                                    long_outputs, model_outputs, trips_batch, trips_batch_is_not_degenerate)
 
 pytestmark = pytest.mark.gpu
 
@@ -124,6 +132,54 @@ def test_grid_stride_and_several_blocks_per_workgroup():
 
 def product_of_codes(r, c, extended, tag="bm"):
     return cc.product_code(handle(*r, tag=tag), handle(*c, tag=tag), extended=extended)
+
+
+def whole_equals_model_and_parts_equal_whole(name):
+    """a batch of tests/test_product_hard_host.py's TRIPS at this device's grid: the whole call against the model on the
+    picked blocks, and the blocks before and from the odd cut, decoded on their own (as other workgroups' first, second
+    or third block), against the whole"""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    batch = trips_batch(name, cus)
+    trips_batch_is_not_degenerate(name, batch)
+    r, c = TRIPS[name][:2]
+    pc = product_of_codes(r + (None,), c + (None,), False)
+    z, pick, cut = batch["z"], batch["pick"], batch["cut"]
+    assert z.shape[0] > 2 * batch["cap"] and z.shape[1:] == (pc.n2, pc.n1)
+    zd = torch.from_numpy(z).cuda()
+    whole = {k: v.cpu().numpy() for k, v in pc.correct_hard_batch(zd, TRIP_HALVES).items()}
+    same({k: v[pick] for k, v in whole.items()}, batch["want"], (name, "whole"))
+    for lo, hi in ((0, cut), (cut, z.shape[0])):
+        part = pc.correct_hard_batch(zd[lo:hi], TRIP_HALVES)
+        same({k: v.cpu().numpy() for k, v in part.items()}, {k: v[lo:hi] for k, v in whole.items()}, (name, lo))
+
+
+@pytest.mark.parametrize("name", ["127_113x7_4", "7_4x127_113"])
+def test_second_and_third_block_of_a_workgroup(name):
+    """the workgroup-per-block kernel with twice as many blocks as its largest grid (8 workgroups per compute unit) and
+    77 more: every workgroup decodes a second block, and 77 a third, over the X, X0, ctl, line states and
+    Berlekamp-Massey columns of the one before.  7 x 127 leaves two of the four wavefronts without a line in either pass,
+    three in the row pass, and the second one lane short in the column pass; 127 x 7 is its turn."""
+    whole_equals_model_and_parts_equal_whole(name)
+
+
+def test_second_and_third_block_of_a_wavefront_at_full_width():
+    """the wavefront-per-block kernel at 63 lines of t = 3 with twice as many blocks as the largest grid has wavefronts
+    and 77 more: 63 of 64 lanes have a line, the Berlekamp-Massey columns are six deep, and a wavefront meets all of it
+    again from the block before"""
+    whole_equals_model_and_parts_equal_whole("63_45x63_45")
+
+
+@pytest.mark.parametrize("halves", LONG_HALVES)
+def test_many_half_iterations(halves):
+    """BCH(15,11)^2 through 56, 57 and 60 half-iterations: blocks in a cycle change up to the last pass (`last` ==
+    halves, far above the 8 of the other tests), settled blocks stop early; separate buffers and in place"""
+    dec, z, xs = long_case()
+    want = long_outputs(halves)
+    assert (want["last"] == halves).sum() >= 5 and (want["last"] <= 8).sum() >= 5
+    pc = product_of_codes((4, 1, None), (4, 1, None), False)
+    same(decode_dev(pc, z, halves), want, (halves, "separate"))
+    same(decode_dev(pc, z, halves, in_place=True), want, (halves, "in place"))
 
 
 @pytest.mark.parametrize("name", ["15_11x15_7", "e16_11xe32_26", "255_239x255_239"])
@@ -310,6 +366,85 @@ def test_mc_counters_against_channel_model_and_count(q, t, extended, ebno, block
     cut = blocks // 3
     shards = mc(pc, 6, ebno, seed, first, cut, random_codewords) + mc(pc, 6, ebno, seed, first + cut, blocks - cut, random_codewords)
     assert np.array_equal(shards, mc(pc, 6, ebno, seed, first, blocks, random_codewords))
+
+
+def mc_between_guards(pc, halves, ebno, seed, first, blocks, random_codewords):
+    """cc_mc_run_product_hard_dev itself, the 64 counters between guard elements: a histogram slot past the last would
+    land in them"""
+    import torch
+    wc, counters = guarded(torch, capi.MC_NCOUNTERS, torch.int64)
+    counters.zero_()
+    desc = pc._pc_hard(halves)
+    rc = capi.lib().cc_mc_run_product_hard_dev(C.byref(desc), ebno, seed, first, blocks, int(random_codewords), ptr(counters), None)
+    capi.check(rc, "cc_mc_run_product_hard_dev")
+    torch.cuda.synchronize()
+    assert guards_intact(torch, wc)
+    return counters.cpu().numpy()
+
+
+@pytest.mark.parametrize("random_codewords", [True, False], ids=["random", "zero"])
+def test_mc_counters_at_and_beyond_the_last_histogram_slot(random_codewords):
+    """BCH(15,11)^2 at an Eb/N0 where a fifth of the blocks end in a cycle (chosen with the model on awgn_model's channel
+    values): after 60 half-iterations those blocks have `last` = 60 and share the last slot, 55, of the histogram with
+    nothing else, while CC_MC_ITER_SUM takes the 60; after 55 the same blocks have `last` = 55, the slot's own value.
+    The counters lie between guard elements."""
+    pc = product_of_codes((4, 1, None), (4, 1, None), False)
+    dec = PH.decoder(4, 1)
+    seed, first, ebno, blocks = 2026, (1 << 33) + 5, 3.5, 512
+    ch = pc.channel(ebno, seed, first, blocks, random_codewords)
+    y, sent = ch["y"].cpu().numpy(), ch["sent"].cpu().numpy()
+    assert bool(sent.any()) == random_codewords
+    z = (y < 0).astype(np.uint8)
+    xs = PH.steps(dec, dec, z, 60, False)
+    top = capi.MC_ITER_HIST + 55
+    assert top + 1 == capi.MC_NCOUNTERS
+    for halves in (60, 55):
+        want = PH.outputs(dec, dec, z, xs, halves, False)
+        expect = counted(want, sent, y)
+        print(halves, "half-iterations: blocks in the last slot", expect[top], "sum of last", expect[capi.MC_ITER_SUM])
+        assert (want["last"] == halves).sum() >= 5 and expect[top] == (want["last"] >= 55).sum() > 0
+        assert expect[capi.MC_ITER_HIST: top + 1].sum() == blocks and np.count_nonzero(expect[capi.MC_ITER_HIST:]) >= 3
+        if halves > 55:
+            assert expect[capi.MC_ITER_SUM] > 55 * expect[top]  # the sum is not clamped
+        got = mc_between_guards(pc, halves, ebno, seed, first, blocks, random_codewords)
+        assert np.array_equal(got, expect), (halves, got, expect)
+        assert np.array_equal(mc(pc, halves, ebno, seed, first, blocks, random_codewords), expect)
+
+
+@pytest.mark.parametrize("random_codewords", [True, False], ids=["random", "zero"])
+def test_mc_count_of_several_blocks_per_wavefront(random_codewords):
+    """BCH(7,4)^2 with three times as many blocks as the count kernel's largest grid has wavefronts (8 workgroups of four
+    per compute unit) and 77 more, one chunk: every wavefront sums three or four blocks in registers before its atomics.
+    Want = the composition on the device (the decode call is held to the model by the tests above): channel, hard
+    decisions, the decode call, the counter definitions.  Three shards of unequal size sum to the whole."""
+    import torch
+    pc = product_of_codes((3, 1, None), (3, 1, None), False)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    blocks = 3 * 32 * cus + 77
+    assert blocks * pc.n < 1 << 24  # one chunk
+    seed, first, ebno, halves = 2028, (1 << 33) + 5, 3.0, 5
+    ch = pc.channel(ebno, seed, first, blocks, random_codewords)
+    assert bool(ch["sent"].any()) == random_codewords
+    res = pc.correct_hard_batch((ch["y"] < 0).to(torch.uint8), halves)
+    wrong = (res["out"] != ch["sent"]).reshape(blocks, -1).sum(dim=1)
+    failed = res["status"] != 0
+    want = np.zeros(capi.MC_NCOUNTERS, np.int64)
+    want[capi.MC_FRAMES] = blocks
+    want[capi.MC_WORD_ERRORS] = int((failed | (wrong > 0)).sum())
+    want[capi.MC_BIT_ERRORS] = int(wrong.sum())
+    want[capi.MC_FAILURES] = int(failed.sum())
+    want[capi.MC_UNDETECTED] = int((~failed & (wrong > 0)).sum())
+    want[capi.MC_CHANNEL_BIT_ERRORS] = int(((ch["y"] < 0) != (ch["sent"] != 0)).sum())
+    want[capi.MC_ITER_SUM] = int(res["last"].sum())
+    want[capi.MC_ITER_HIST:] = torch.bincount(res["last"].clamp(max=55).long(), minlength=56).cpu().numpy()
+    print("counters", want[:7], "histogram", want[capi.MC_ITER_HIST: capi.MC_ITER_HIST + halves + 1])
+    assert want[capi.MC_WORD_ERRORS] > 0 and want[capi.MC_FAILURES] > 0 and want[capi.MC_UNDETECTED] > 0
+    assert np.count_nonzero(want[capi.MC_ITER_HIST:]) >= 3 and want[capi.MC_ITER_HIST:].sum() == blocks
+    got = mc_between_guards(pc, halves, ebno, seed, first, blocks, random_codewords)
+    assert np.array_equal(got, want), (got, want)
+    a, b = blocks // 5, blocks // 2 + 1
+    shards = sum(mc(pc, halves, ebno, seed, first + lo, hi - lo, random_codewords) for lo, hi in ((0, a), (a, b), (b, blocks)))
+    assert np.array_equal(shards, want)
 
 
 def test_mc_across_a_chunk_boundary_equals_the_composition():

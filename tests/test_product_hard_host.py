@@ -2,7 +2,8 @@
 CC_DEVICE_NONE handles: the symbols are declared, bound and exported; every refusal in the order the header states; the
 model of tests/product_hard_model.py against brute force on BCH(7,4)^2 and eBCH(8,4)^2; the fixed point; product_code's
 TypeErrors and ValueErrors; product_hard_simulation's log name, ladder and sharding over a stub; the benchmark's options;
-and what the batches of tests/test_gpu_product_hard.py are chosen for, decoded by the model alone.
+and what the batches of tests/test_gpu_product_hard.py are chosen for, decoded by the model alone: CASES, TRIPS (later
+blocks of a workgroup) and LONG (many half-iterations).
 
 What the batches are chosen for, and where a condition cannot hold (test_model_batches_are_not_degenerate):
 - a block that converges to a wrong block needs miscorrections that agree along rows and columns: the 15 x 15 batch has
@@ -76,6 +77,77 @@ def case(name):
 def model_outputs(name, halves, blocks=slice(None)):
     rows, cols, extended, sent, z, xs, _ = case(name)
     return PH.outputs(rows, cols, z[blocks], [x[blocks] for x in xs], halves, extended)
+
+
+# ---- batches past the first trip of a workgroup (tests/test_gpu_product_hard.py decodes them on the device) ----
+# name: rows (q, t), cols (q, t), flips in 256 of the BSC chosen with the model, blocks the largest grid holds per compute
+# unit (8 workgroups of one block, or of four wavefronts with a block each)
+TRIPS = {
+    "127_113x7_4": ((7, 2), (3, 1), 7, 8),     # 7 x 127: two wavefronts of the workgroup have no line in either pass
+    "7_4x127_113": ((3, 1), (7, 2), 7, 8),     # 127 x 7: its turn, the second wavefront one lane short in the row pass
+    "63_45x63_45": ((6, 3), (6, 3), 14, 32),   # a wavefront per block at full width, t = 3
+}
+TRIP_HALVES = 5
+
+
+def trips_batch(name, cus):
+    """2 * capacity + 77 blocks for a device of `cus` compute units, so that every workgroup (wavefront) of the largest
+    grid decodes a second and a third block in the LDS the first left behind, and the model's outputs and trace on a picked
+    subset: a prefix, a stretch around an odd cut past the capacity, the suffix"""
+    (rq, rt), (cq, ct), flips, per_cu = TRIPS[name]
+    rows, cols = PH.decoder(rq, rt), PH.decoder(cq, ct)
+    cap = per_cu * cus
+    B = 2 * cap + 77
+    rng = np.random.default_rng(77)
+    few = encode_blocks(rows, cols, rng.integers(0, 2, (256, cols.l, rows.l)).astype(np.uint8), False)
+    z = few[rng.integers(0, 256, B)]
+    z ^= rng.integers(0, 256, z.shape, dtype=np.uint8) < flips
+    cut = (cap + cap // 3) | 1
+    pick = np.unique(np.concatenate([np.arange(50), np.arange(cut - 25, cut + 25), np.arange(B - 50, B)]))
+    trace = []
+    xs = PH.steps(rows, cols, z[pick], TRIP_HALVES, False, trace)
+    want = PH.outputs(rows, cols, z[pick], xs, TRIP_HALVES, False)
+    return dict(rows=rows, cols=cols, z=z, cap=cap, cut=cut, pick=pick, want=want, trace=trace)
+
+
+def trips_batch_is_not_degenerate(name, batch):
+    """among the picked blocks that are no workgroup's first: `last` takes three values, both statuses occur, and where a
+    component can be without a candidate (t = 3: 16 % of the syndromes are decodable) a line is"""
+    late = batch["pick"] >= batch["cap"]
+    want = batch["want"]
+    lasts, statuses = set(want["last"][late].tolist()), set(want["status"][late].tolist())
+    stuck = sum(int((~tr["cand"].reshape(late.size, -1)[late]).sum()) for tr in batch["trace"])
+    print(name, "blocks", batch["z"].shape[0], "picked", late.size, "past the first trip", int(late.sum()), "last",
+          sorted(lasts), "not converged", int((want["status"][late] != PH.FRAME_OK).sum()), "lines without a candidate", stuck)
+    assert late.sum() >= 100 and late.size <= 150
+    assert len(lasts) >= 3, lasts
+    assert statuses == {PH.FRAME_OK, PH.FRAME_NOT_CONVERGED}, statuses
+    if name == "63_45x63_45":
+        assert stuck > 0
+
+
+# ---- many half-iterations: `last` beyond the 8 of CASES, at and around the last slot of the Monte-Carlo histogram ----
+LONG = ((4, 1), 0.06, 64, 7)  # BCH(15,11)^2, plain: (q, t) of both sides, BSC flip probability, blocks, seed
+LONG_HALVES = (56, 57, 60)
+
+
+@functools.lru_cache(maxsize=None)
+def long_case():
+    """the decoder, the received blocks and the model's steps x_1 .. x_60, made once"""
+    (q, t), p, blocks, seed = LONG
+    dec = PH.decoder(q, t)
+    rng = np.random.default_rng(seed)
+    sent = encode_blocks(dec, dec, rng.integers(0, 2, (blocks, dec.l, dec.l)).astype(np.uint8), False)
+    z = sent ^ (rng.random(sent.shape) < p).astype(np.uint8)
+    xs = PH.steps(dec, dec, z, max(LONG_HALVES), False)
+    for a in [z] + xs:
+        a.setflags(write=False)
+    return dec, z, xs
+
+
+def long_outputs(halves):
+    dec, z, xs = long_case()
+    return PH.outputs(dec, dec, z, xs, halves, False)
 
 
 def bch(q, t, **kw):
@@ -395,3 +467,23 @@ def test_model_batches_are_not_degenerate():
     # the two ends of the full block: everything converges at p = 0.008, nothing at 0.012
     assert (model_outputs("e256_239xe256_239", HALVES)["status"] == PH.FRAME_OK).all()
     assert (model_outputs("e256_239xe256_239_noisy", HALVES)["status"] != PH.FRAME_OK).all()
+
+
+@pytest.mark.parametrize("name", sorted(TRIPS))
+def test_trip_batches_are_not_degenerate(name):
+    """at the 256 compute units of an MI355X; the GPU test asserts the same at the count of the device it runs on"""
+    trips_batch_is_not_degenerate(name, trips_batch(name, 256))
+
+
+def test_long_batch_cycles_to_the_last_half_iteration_and_settles_early():
+    """BCH(15,11)^2 at p = 0.06: blocks that never settle change in every pass up to the last, whichever it is, and are
+    not converged; others reach a fixed point within a few passes.  56, 57 and 60 half-iterations lie on both sides of
+    the clamp of the Monte-Carlo histogram (slot 55) and end on a row and on a column pass."""
+    for halves in LONG_HALVES:
+        got = long_outputs(halves)
+        cycling = got["last"] == halves
+        early = (got["last"] >= 2) & (got["last"] <= 8) & (got["status"] == PH.FRAME_OK)
+        print(halves, "half-iterations: last == halves in", int(cycling.sum()), "blocks, settled with 2 <= last <= 8 in",
+              int(early.sum()), "of", got["last"].size)
+        assert cycling.sum() >= 5 and early.sum() >= 5
+        assert (got["status"][cycling] == PH.FRAME_NOT_CONVERGED).all()

@@ -1,7 +1,8 @@
 """CPU-side checks of the product-code calls on CC_DEVICE_NONE handles: the symbols are declared, bound and
 exported; every refusal of cc_product_decode(_dev) and its relatives in the order the header states; product_code's
 attributes, shapes and TypeErrors; cc_product_sigma against the formula; product_simulation's ladder, log name and
-sharding over a stub backend; the benchmark's options."""
+sharding over a stub backend; the benchmark's options; what the ragged-tile batches of tests/test_gpu_product.py are chosen
+for, decoded by the model alone."""
 import ctypes as C
 import os
 import re
@@ -273,6 +274,17 @@ def test_benchmark_options():
     assert ap(["--alpha", "0", "--beta", "1", "--cols-k", "4", "--cols-dmin", "3", "--chase", "2"]) == ((6, 7), (4, 3), 2, [0.0], [1.0])
     pc = benchmark.build_product((6, 7), (4, 3), True, device=capi.DEVICE_NONE)
     assert pc.to_string() == "(63, 45, 7)-BMx(15, 11, 3)-BM-ext"
+
+
+@pytest.mark.parametrize("name", ["255_239x63_57", "63_57x255_239"])
+def test_ragged_tile_batches_hold_what_they_are_chosen_for(name):
+    """the two cases of tests/test_gpu_product.py with a short last tile, by the model alone: the conditions of its
+    test_model_batches_are_not_degenerate, and a tiling with R % TR != 0 in every shape"""
+    import test_gpu_product as G
+    assert name in G.RAGGED
+    G.test_model_batches_are_not_degenerate(name)
+    for shape, rows in G.tilings(name).items():
+        assert len(rows) == 2 and 0 < rows[-1] < rows[0], (shape, rows)
 
 
 def benchmark_args(argv):
