@@ -11,7 +11,7 @@ from ._capi import CcError
 from .codes import (berlekamp_massey_tag, bsc_packed_channel, burst_channel, burst_erasure_channel, cyclic, decoding_failure, deinterleave, dmin, errors, euklid_tag, extend, interleave, min_sum, min_sum_decoder, min_sum_tag,
                     normalized_2d_min_sum_tag, normalized_min_sum_tag, offset_min_sum_tag, pack_bits,
                     peterson_gorenstein_zierler_tag, primitive_bch, product_code, product_decode, rs, self_correcting_1_min_sum_tag,
-                    self_correcting_2_min_sum_tag, symbol_reliability, unextend, unpack_bits)
+                    self_correcting_2_min_sum_tag, staircase_code, symbol_reliability, unextend, unpack_bits)
 
 __all__ = [
     "capi", "CcError", "cyclic", "primitive_bch", "rs", "errors", "dmin", "decoding_failure",
@@ -20,4 +20,5 @@ __all__ = [
     "self_correcting_2_min_sum_tag", "normalized_2d_min_sum_tag", "min_sum", "min_sum_decoder",
     "pack_bits", "unpack_bits", "interleave", "deinterleave", "burst_channel", "burst_erasure_channel",
     "bsc_packed_channel", "symbol_reliability", "product_decode", "extend", "unextend", "product_code",
+    "staircase_code",
 ]

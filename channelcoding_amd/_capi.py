@@ -68,6 +68,15 @@ class Product(C.Structure):
                 ("halves", C.c_uint32), ("alpha", C.POINTER(C.c_float)), ("beta", C.POINTER(C.c_float))]
 
 
+class Staircase(C.Structure):
+    """cc_staircase: the component handle, the extension flag, the stream length and the decoder's window and iterations."""
+    _fields_ = [("code", C.c_void_p), ("extended", C.c_int), ("blocks", C.c_uint32), ("window", C.c_uint32),
+                ("iters", C.c_uint32)]
+
+
+STAIRCASE_MAX_WINDOW = 16
+
+
 class CcError(RuntimeError):
     def __init__(self, status, where):
         self.status = status
@@ -188,6 +197,18 @@ _SIGNATURES = {
                                       _VP, _VP]),
     "cc_mc_run_product_dev": (C.c_int, [C.POINTER(Product), C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP,
                                         _VP]),
+    "cc_staircase_encode_batch": (C.c_int, [C.POINTER(Staircase), _VP, _VP, C.c_size_t]),
+    "cc_staircase_encode_batch_dev": (C.c_int, [C.POINTER(Staircase), _VP, _VP, C.c_size_t, _VP]),
+    "cc_staircase_extract_batch": (C.c_int, [C.POINTER(Staircase), _VP, _VP, C.c_size_t]),
+    "cc_staircase_extract_batch_dev": (C.c_int, [C.POINTER(Staircase), _VP, _VP, C.c_size_t, _VP]),
+    "cc_staircase_decode": (C.c_int, [C.POINTER(Staircase), _VP, _VP, _VP, _VP, C.c_size_t]),
+    "cc_staircase_decode_dev": (C.c_int, [C.POINTER(Staircase), _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "cc_staircase_sigma": (C.c_double, [C.POINTER(Staircase), C.c_double]),
+    "cc_staircase_lds_bytes": (C.c_size_t, [C.POINTER(Staircase)]),
+    "cc_awgn_staircase_dev": (C.c_int, [C.POINTER(Staircase), C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP,
+                                        _VP, _VP]),
+    "cc_mc_run_staircase_dev": (C.c_int, [C.POINTER(Staircase), C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP,
+                                          _VP]),
     "cc_product_decode_hard": (C.c_int, [C.POINTER(Product), _VP, _VP, _VP, _VP, _VP, C.c_size_t]),
     "cc_product_decode_hard_dev": (C.c_int, [C.POINTER(Product), _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "cc_mc_run_product_hard_dev": (C.c_int, [C.POINTER(Product), C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int,

@@ -1,6 +1,6 @@
 """Command line of the reference's simulation driver (src/simulation/benchmark.c++) on the GPU path.
 
-    python -m channelcoding_amd.benchmark [--simulation awgn|bitflip|bsc|bec|burst|product] [--algorithm NAME|all]...
+    python -m channelcoding_amd.benchmark [--simulation awgn|bitflip|bsc|bec|burst|product|staircase] [--algorithm NAME|all]...
                                           [--k 5|6|7|all]... [--dmin 3|5|7|9|11|all]... [--seed N | --seed-time]
                                           [--threads N] [--log-dir DIR] [--p VALUE]... [--max-samples N]
                                           [--interleave I] [--p-gb VALUE] [--p-bg VALUE] [--p-good VALUE]
@@ -35,6 +35,13 @@ and --alpha a,b,... and --beta a,b,... give the schedule, one value each per hal
 schedule.  The log is "<rows>x<cols>[-ext]-chaseP-hH.log".  With --halves H in place of --alpha / --beta the ladder runs
 H half-iterations of hard-decision row / column decoding (montecarlo.product_hard_simulation) and the log is
 "<rows>x<cols>[-ext]-hard-hH.log", with the mean of the half-iterations a block took next to wer.
+
+--simulation staircase --blocks L --window W --iters I [--extended] is the Eb/N0 ladder of a staircase code under its
+sliding-window hard-decision decoder (montecarlo.staircase_simulation): --k and --dmin (one value each, k = 3 .. 8) name
+the component code -- with --extended its extended code, otherwise the code shortened by one position, so that a line has
+an even number of bits -- streams of L blocks, a window of W = 2 .. 16 blocks and I iterations per window position.  There
+is no default for the three.  ber is taken over the blocks decoded with a full window; the log is
+"staircase(<code>[-ext], L=.., W=.., I=..).log".
 """
 import argparse
 import sys
@@ -42,7 +49,7 @@ import time
 
 from . import codes as cc
 from .montecarlo import (awgn_simulation, bitflip_simulation, burst_simulation, discrete_simulation, product_hard_simulation,
-                         product_simulation)
+                         product_simulation, staircase_simulation)
 
 POWERS = (5, 6, 7)
 DISTANCES = (3, 5, 7, 9)
@@ -86,7 +93,7 @@ def reported_distances():
 
 
 def usage_text():
-    lines = ["--simulation [awgn|bitflip|bsc|bec|burst|product]",
+    lines = ["--simulation [awgn|bitflip|bsc|bec|burst|product|staircase]",
              "                             Choose the simulation to run. The default is AWGN.",
              "--algorithm <name>           Choose algorithm:"]
     lines += ["  " + a for a in ALGORITHMS]
@@ -119,7 +126,10 @@ def usage_text():
               "--beta <a,b,...>             product: the value of a position without a competitor, per half-iteration.",
               "--halves <num>               product: hard-decision row / column decoding with that many half-iterations,",
               "                             in place of --alpha and --beta.",
-              "--max-samples <num>          awgn / bsc / bec / burst / product: cap on the frames of one point.",
+              "--blocks <num>               staircase: blocks per stream. There is no default.",
+              "--window <num>               staircase: the decoder's window in blocks, 2 .. 16. There is no default.",
+              "--iters <num>                staircase: iterations per window position. There is no default.",
+              "--max-samples <num>          awgn / bsc / bec / burst / product / staircase: cap on the frames of one point.",
               "",
               "algorithm, k, and dmin can be specified multiple times.",
               "For all other options, giving them multiple times results in the last value being used."]
@@ -242,6 +252,59 @@ def product_main(args):
     return 0
 
 
+def staircase_arguments(args):
+    """(k, dmin, blocks, window, iters) of --simulation staircase, or a message saying what is wrong"""
+    if args.alpha is not None or args.beta is not None or args.halves is not None or args.cols_k is not None \
+            or args.cols_dmin is not None or args.chase is not None or args.osd is not None:
+        return "--simulation staircase takes --k, --dmin, --blocks, --window, --iters and --extended"
+    try:
+        if not args.k or len(args.k) != 1 or not args.dmin or len(args.dmin) != 1:
+            return "--simulation staircase takes one --k and one --dmin"
+        k, d = int(args.k[0]), int(args.dmin[0])
+    except ValueError:
+        return "--k and --dmin take numbers"
+    if not 3 <= k <= 8 or d < 3 or d % 2 == 0:
+        return "--simulation staircase takes k = 3 .. 8 and an odd dmin >= 3"
+    if args.blocks is None or args.window is None or args.iters is None:
+        return "--simulation staircase needs --blocks, --window and --iters: there is no default"
+    if args.blocks < 1 or not 2 <= args.window <= cc.capi.STAIRCASE_MAX_WINDOW or args.iters < 1:
+        return "--blocks <1..> --window <2..%d> --iters <1..>" % cc.capi.STAIRCASE_MAX_WINDOW
+    return k, d, args.blocks, args.window, args.iters
+
+
+def build_staircase(k, d, blocks, window, iters, extended, device=None):
+    """the component shortened by one position where the line would otherwise have an odd number of bits"""
+    kw = {} if device is None else {"device": device}
+    n = (1 << k) - 1
+    if not extended:
+        kw["n"] = n - 1
+    return cc.staircase_code(cc.primitive_bch(k, cc.dmin(d), cc.berlekamp_massey_tag(), **kw), blocks, window, iters,
+                             extended=extended)
+
+
+def staircase_main(args):
+    parsed = staircase_arguments(args)
+    if isinstance(parsed, str):
+        print(parsed, file=sys.stderr)
+        print(usage_text())
+        return 1
+    seed = time.time_ns() if args.seed_time else args.seed
+    dist = join_ranks()
+    try:
+        sc = build_staircase(*parsed, args.extended)
+    except ValueError as err:
+        print("--simulation staircase: %s" % err, file=sys.stderr)
+        return 1
+    t0 = time.perf_counter()
+    res = staircase_simulation(sc, seed=seed, log_dir=args.log_dir, max_samples=args.max_samples)()
+    if not dist or dist.get_rank() == 0:
+        print("%s: %d streams in %.2f s" % (sc.to_string(), sum(r["frames"] for r in res), time.perf_counter() - t0), flush=True)
+    if dist:
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="channelcoding_amd.benchmark", add_help=False)
     ap.add_argument("--simulation", "-simulation", default="awgn")
@@ -271,6 +334,9 @@ def main(argv=None):
     ap.add_argument("--alpha", default=None, help="product: a,b,... one per half-iteration")
     ap.add_argument("--beta", default=None, help="product: a,b,... one per half-iteration")
     ap.add_argument("--halves", type=int, default=None, help="product: hard-decision decoding, this many half-iterations")
+    ap.add_argument("--blocks", type=int, default=None, help="staircase: blocks per stream")
+    ap.add_argument("--window", type=int, default=None, help="staircase: window of the decoder in blocks")
+    ap.add_argument("--iters", type=int, default=None, help="staircase: iterations per window position")
     ap.add_argument("--help", "-h", action="store_true")
     args, unknown = ap.parse_known_args(argv)
     if args.help or unknown:
@@ -281,6 +347,8 @@ def main(argv=None):
     sim = args.simulation.lower()
     if sim == "product":
         return product_main(args)
+    if sim == "staircase":
+        return staircase_main(args)
     if sim not in ("awgn", "bitflip", "bsc", "bec", "burst"):
         print("Don't know the simulation type '%s'" % sim, file=sys.stderr)
         print(usage_text())

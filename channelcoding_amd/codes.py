@@ -1200,6 +1200,109 @@ class product_code:
         return dict(y=y, sent=sent)
 
 
+class staircase_code:
+    """A staircase code of one binary BCH component (cc_staircase): a stream is (blocks, m, m) bits, line j
+    of step i runs down column j of block i - 1 and along row j of block i and is a word of `code` (extended=True: of
+    its extended code); block 0 is the zero block.  `code` is a handle correct_batch(chase=0) accepts with n + e even.
+    window (blocks, the zero block included) and iters are the sliding-window decoder's.  m: block side, k_b: message
+    bits per row, rate = k_b / m."""
+
+    def __init__(self, code, blocks, window, iters, extended=False):
+        if not isinstance(code, cyclic):
+            raise TypeError("staircase_code takes a code of this package")
+        self.code, self.extended = code, bool(extended)
+        self.blocks, self.window, self.iters = int(blocks), int(window), int(iters)
+        if self.blocks < 1:
+            raise ValueError("blocks >= 1")
+        if not 2 <= self.window <= capi.STAIRCASE_MAX_WINDOW:
+            raise ValueError("window = 2 .. %d" % capi.STAIRCASE_MAX_WINDOW)
+        if self.iters < 1:
+            raise ValueError("iters >= 1")
+        e = 1 if self.extended else 0
+        if (code.n + e) % 2:
+            raise ValueError("n + e must be even: a line splits into two halves of m bits")
+        self.m = (code.n + e) // 2
+        self.k_b = self.m - ((code.n - code.l) + e)
+        if self.k_b < 1:
+            raise ValueError("the parity bits of a line leave no message bit in a row of m")
+        self.n, self.l = self.blocks * self.m * self.m, self.blocks * self.m * self.k_b
+        self.rate = self.k_b / self.m
+
+    def to_string(self):
+        return "staircase(%s%s, L=%d, W=%d, I=%d)" % (self.code.to_string(), "-ext" if self.extended else "", self.blocks,
+                                                      self.window, self.iters)
+
+    def _sc(self):
+        sc = capi.Staircase(self.code._h, int(self.extended), self.blocks, self.window, self.iters)
+        sc._keep = self.code
+        return sc
+
+    def sigma(self, ebno_db):
+        return capi.lib().cc_staircase_sigma(C.byref(self._sc()), float(ebno_db))
+
+    def lds_bytes(self):
+        """LDS of one workgroup of the decoder"""
+        return capi.lib().cc_staircase_lds_bytes(C.byref(self._sc()))
+
+    def _bytes(self, x, inner, what):
+        """x as contiguous uint8 streams of shape (B,) + inner"""
+        if tuple(x.shape[1:]) != inner or len(x.shape) != 4:
+            raise CcError(capi.ERR_LENGTH, what)
+        if _side(x) is _host:
+            x = np.asarray(x)
+            if x.dtype.kind not in "ub":
+                raise TypeError(what + " takes uint8 symbols")
+            return np.ascontiguousarray(x, np.uint8)
+        import torch
+        if x.dtype != torch.uint8:
+            raise TypeError(what + " takes uint8 symbols")
+        return x.contiguous()
+
+    def encode_batch(self, msg):
+        """(B, blocks, m, k_b) message bits -> (B, blocks, m, m) code streams; numpy array or device tensor"""
+        msg = self._bytes(msg, (self.blocks, self.m, self.k_b), "encode_batch")
+        B = msg.shape[0]
+        return cyclic._batch_call(_product_handle(self._sc()), "cc_staircase_encode_batch", [msg], B,
+                                  {"out": ((B, self.blocks, self.m, self.m), np.uint8)})["out"]
+
+    def extract_batch(self, cw):
+        """(B, blocks, m, m) code streams -> (B, blocks, m, k_b) message bits"""
+        cw = self._bytes(cw, (self.blocks, self.m, self.m), "extract_batch")
+        B = cw.shape[0]
+        return cyclic._batch_call(_product_handle(self._sc()), "cc_staircase_extract_batch", [cw], B,
+                                  {"msg": ((B, self.blocks, self.m, self.k_b), np.uint8)})["msg"]
+
+    def correct_batch(self, z):
+        """cc_staircase_decode: z (B, blocks, m, m) uint8 hard decisions -> (out, nflip, status) of the sliding-window
+        decoder; numpy array or device tensor."""
+        z = self._bytes(z, (self.blocks, self.m, self.m), "correct_batch")
+        B = z.shape[0]
+        side = _side(z)
+        res = {"out": side.alloc(z, (B, self.blocks, self.m, self.m), np.uint8), "nflip": side.alloc(z, (B,), np.int32),
+               "status": side.alloc(z, (B,), np.int32)}
+        cyclic._batch_call(_product_handle(self._sc()), "cc_staircase_decode", [z], B, res)
+        return res["out"], res["nflip"], res["status"]
+
+    def decode_batch(self, z):
+        """correct_batch, then the message bits of out: (msg, nflip, status)"""
+        out, nflip, status = self.correct_batch(z)
+        return self.extract_batch(out), nflip, status
+
+    def channel(self, ebno_db, seed, first_stream, streams, random_codewords=False):
+        """Streams [first_stream, first_stream + streams) of the AWGN channel on the current device, as hard decisions
+        (cc_awgn_staircase_dev): dict(z=, sent=) of (streams, blocks, m, m) uint8 torch tensors."""
+        import torch
+        streams = int(streams)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        shape = (streams, self.blocks, self.m, self.m)
+        z = torch.empty(shape, dtype=torch.uint8, device=dev)
+        sent = torch.empty(shape, dtype=torch.uint8, device=dev)
+        rc = capi.lib().cc_awgn_staircase_dev(C.byref(self._sc()), float(ebno_db), int(seed), int(first_stream), streams,
+                                              int(bool(random_codewords)), _ptr(z), _ptr(sent), _stream_handle(z))
+        capi.check(rc, "cc_awgn_staircase_dev")
+        return dict(z=z, sent=sent)
+
+
 class min_sum_decoder(cyclic):
     """The free functions min_sum<R, U>(H, y, tag) of soft_decision.h:220-295 bound to one parity-check matrix
     (any rows x cols 0/1 matrix, cols <= 2048; cc_minsum_create).  correct_batch(), correct(), H(), to_string()

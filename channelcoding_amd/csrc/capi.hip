@@ -1787,6 +1787,130 @@ int cc_mc_run_product_hard_dev(const cc_product *pc, double ebno_db, uint64_t se
                              static_cast<hipStream_t>(stream));
 }
 
+/* ------------------------------ staircase codes ------------------------------ */
+
+// The refusals of the staircase calls in the header's order.  decode: window and iters are read, and in / out hold
+// streams of the same extent; arrays: the call has in / out at all.  CC_OK or CC_ERR_NO_DEVICE is answered last.
+static int staircase_supported(const cc_staircase *sc, bool decode, bool arrays, const uint8_t *in, const uint8_t *out,
+                               size_t B) {
+  if (!sc || !sc->code) return CC_ERR_INVALID_ARGUMENT;
+  if (arrays && B && (!in || !out)) return CC_ERR_INVALID_ARGUMENT;
+  if (sc->blocks == 0) return CC_ERR_INVALID_ARGUMENT;
+  if (decode && (sc->window < 2 || sc->window > CC_STAIRCASE_MAX_WINDOW || sc->iters == 0)) return CC_ERR_INVALID_ARGUMENT;
+  const unsigned long long e = sc->extended ? 1 : 0, n = sc->code->tab.n, m = (n + e) / 2;
+  if (static_cast<unsigned long long>(sc->blocks) * m * m >= (1ull << 32)) return CC_ERR_INVALID_ARGUMENT;
+  const int rc = chase_supported(sc->code, 0);
+  if (rc != CC_OK && rc != CC_ERR_NO_DEVICE) return rc;
+  if ((n + e) & 1ull) {
+    set_last_error("staircase code: n + e is odd, a line does not split into two halves of m bits");
+    return CC_ERR_INVALID_ARGUMENT;
+  }
+  if ((n - sc->code->tab.l) + e >= m) {
+    set_last_error("staircase code: r = (n - l) + e parity bits per line leave no message bit in a row of m");
+    return CC_ERR_INVALID_ARGUMENT;
+  }
+  if (decode && arrays && in != out) {
+    const size_t bytes = B * staircase_shape(sc).N;
+    if (ranges_overlap(in, bytes, out, bytes)) return CC_ERR_INVALID_ARGUMENT;
+  }
+  return rc;
+}
+
+int cc_staircase_decode_dev(const cc_staircase *sc, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip, int32_t *d_status,
+                            size_t B, void *stream) {
+  if (int rc = staircase_supported(sc, true, true, d_in, d_out, B)) return rc;
+  DeviceGuard guard(sc->code->device);
+  return launch_staircase_decode(sc, d_in, d_out, d_nflip, d_status, B, static_cast<hipStream_t>(stream));
+}
+
+int cc_staircase_decode(const cc_staircase *sc, const uint8_t *in, uint8_t *out, int32_t *nflip, int32_t *status, size_t B) {
+  if (int rc = staircase_supported(sc, true, true, in, out, B)) return rc;
+  if (B == 0) return CC_OK;
+  const StaircaseShape s = staircase_shape(sc);
+  if (!symbols_in_field(in, B * s.N, 1)) return CC_ERR_NOT_IN_FIELD;
+  DeviceGuard guard(sc->code->device);
+  // a stream is the frame of the chunk loop
+  const StagedStream streams[] = {stage_in(0, in, s.N), stage_out(1, out, s.N), stage_out(2, nflip, sizeof(int32_t)),
+                                  stage_out(3, status, sizeof(int32_t))};
+  return staged_call(sc->code, B, s.N, 1, streams, 4, nullptr, nullptr,
+                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t st) {
+                       return launch_staircase_decode(sc, static_cast<const uint8_t *>(d[0]), static_cast<uint8_t *>(d[1]),
+                                                      static_cast<int32_t *>(d[2]), static_cast<int32_t *>(d[3]), m, st);
+                     });
+}
+
+static int staircase_map_dev(const cc_staircase *sc, bool encode, const uint8_t *d_src, uint8_t *d_dst, size_t B, void *stream) {
+  if (int rc = staircase_supported(sc, false, true, d_src, d_dst, B)) return rc;
+  DeviceGuard guard(sc->code->device);
+  return encode ? launch_staircase_encode(sc, d_src, d_dst, B, static_cast<hipStream_t>(stream))
+                : launch_staircase_extract(sc, d_src, d_dst, B, static_cast<hipStream_t>(stream));
+}
+
+static int staircase_map_host(const cc_staircase *sc, bool encode, const uint8_t *src, uint8_t *dst, size_t B) {
+  if (int rc = staircase_supported(sc, false, true, src, dst, B)) return rc;
+  if (B == 0) return CC_OK;
+  const StaircaseShape s = staircase_shape(sc);
+  const size_t in_w = encode ? s.K : s.N, out_w = encode ? s.N : s.K;
+  if (!symbols_in_field(src, B * in_w, 1)) return CC_ERR_NOT_IN_FIELD;
+  DeviceGuard guard(sc->code->device);
+  const StagedStream streams[] = {stage_in(0, src, in_w), stage_out(1, dst, out_w)};
+  return staged_call(sc->code, B, 3 * s.N, 1, streams, 2, nullptr, nullptr,
+                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t st) {
+                       const uint8_t *d_src = static_cast<const uint8_t *>(d[0]);
+                       uint8_t *d_dst = static_cast<uint8_t *>(d[1]);
+                       return encode ? launch_staircase_encode(sc, d_src, d_dst, m, st) : launch_staircase_extract(sc, d_src, d_dst, m, st);
+                     });
+}
+
+int cc_staircase_encode_batch_dev(const cc_staircase *sc, const uint8_t *d_msg, uint8_t *d_cw, size_t B, void *stream) {
+  return staircase_map_dev(sc, true, d_msg, d_cw, B, stream);
+}
+int cc_staircase_extract_batch_dev(const cc_staircase *sc, const uint8_t *d_cw, uint8_t *d_msg, size_t B, void *stream) {
+  return staircase_map_dev(sc, false, d_cw, d_msg, B, stream);
+}
+int cc_staircase_encode_batch(const cc_staircase *sc, const uint8_t *msg, uint8_t *cw, size_t B) {
+  return staircase_map_host(sc, true, msg, cw, B);
+}
+int cc_staircase_extract_batch(const cc_staircase *sc, const uint8_t *cw, uint8_t *msg, size_t B) {
+  return staircase_map_host(sc, false, cw, msg, B);
+}
+
+// an sc whose shape can be read: a code behind the handle, q <= 8, n + e even, r < m, at least one block
+static bool staircase_readable(const cc_staircase *sc) {
+  if (!sc || !sc->code || needs_code(sc->code) != CC_OK || sc->code->wide || sc->blocks == 0) return false;
+  const size_t e = sc->extended ? 1 : 0, n = sc->code->tab.n;
+  return ((n + e) & 1) == 0 && (n - sc->code->tab.l) + e < (n + e) / 2;
+}
+
+double cc_staircase_sigma(const cc_staircase *sc, double ebno_db) {
+  if (!staircase_readable(sc)) return 0.0;
+  const StaircaseShape s = staircase_shape(sc);
+  const double rate = 1.0 - static_cast<double>(s.r) / static_cast<double>(s.m);
+  return 1.0 / std::sqrt(2.0 * rate * std::pow(10.0, ebno_db / 10.0));
+}
+
+size_t cc_staircase_lds_bytes(const cc_staircase *sc) {
+  if (!staircase_readable(sc) || sc->window < 2 || sc->window > CC_STAIRCASE_MAX_WINDOW) return 0;
+  return staircase_lds_bytes(sc);
+}
+
+int cc_awgn_staircase_dev(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64_t first_stream, size_t streams,
+                          int random_codewords, uint8_t *d_z, uint8_t *d_sent, void *stream) {
+  if (!sc || !sc->code || (streams && !d_z)) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = staircase_supported(sc, false, false, nullptr, nullptr, streams)) return rc;
+  DeviceGuard guard(sc->code->device);
+  return staircase_awgn(sc, ebno_db, seed, first_stream, streams, random_codewords, d_z, d_sent, static_cast<hipStream_t>(stream));
+}
+
+int cc_mc_run_staircase_dev(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64_t first_stream, size_t streams,
+                            int random_codewords, uint64_t *d_counters, void *stream) {
+  if (!sc || !sc->code || !d_counters) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = staircase_supported(sc, true, false, nullptr, nullptr, streams)) return rc;
+  DeviceGuard guard(sc->code->device);
+  return mc_run_staircase(sc, ebno_db, seed, first_stream, streams, random_codewords, d_counters,
+                          static_cast<hipStream_t>(stream));
+}
+
 // the discrete channels serve every q <= 8 handle the decoders serve; the checks of the two entry points
 static int discrete_supported(const cc_code *code, double p_error, double p_erasure, int random_codewords) {
   if (!std::isfinite(p_error) || !std::isfinite(p_erasure) || p_error < 0.0 || p_erasure < 0.0 ||

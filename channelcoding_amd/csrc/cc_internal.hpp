@@ -153,6 +153,28 @@ inline hipError_t workspace_alloc(const cc_code *code, void **p, size_t bytes, h
   return code->pool ? hipMallocFromPoolAsync(p, bytes, code->pool, stream) : hipMallocAsync(p, bytes, stream);
 }
 
+// stream-ordered scratch of one call, returned to the pool on every way out
+struct Scratch {
+  const cc_code *code;
+  hipStream_t stream;
+  void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  int used = 0;
+  Scratch(const cc_code *c, hipStream_t s) : code(c), stream(s) {}
+  Scratch(const Scratch &) = delete;
+  Scratch &operator=(const Scratch &) = delete;
+  ~Scratch() {
+    for (int i = 0; i < used; ++i)
+      if (p[i]) (void)hipFreeAsync(p[i], stream);
+  }
+  template <class T>
+  hipError_t get(T **out, size_t bytes) {
+    const hipError_t e = workspace_alloc(code, &p[used], bytes ? bytes : 1, stream);
+    *out = static_cast<T *>(p[used]);
+    if (e == hipSuccess) ++used;
+    return e;
+  }
+};
+
 void set_last_error(const std::string &s);
 int hip_fail(hipError_t e, const char *what);
 
@@ -306,6 +328,8 @@ struct ProductShape {
   size_t w1, w2, k1, k2, N;    // values per row and per column, message symbols per row and column, N = w1 w2
 };
 ProductShape product_shape(const cc_product *pc);
+// blocks (of N values) per chunk of the Monte-Carlo and channel routes of product.hip and staircase.hip
+size_t product_chunk_blocks(size_t N, size_t blocks, size_t at_least = 1);
 // d_ext == nullptr: the last half-iteration runs the hard-output kernel
 int launch_product_decode(const cc_product *pc, const float *d_y, uint8_t *d_out, float *d_ext, int32_t *d_status, size_t B,
                           hipStream_t stream);
@@ -323,6 +347,24 @@ int mc_run_product_hard(const cc_product *pc, double ebno_db, uint64_t seed, uin
 // (cc_product_decode_hard_dev).  d_out may be d_in; d_nflip, d_last and d_status (one per block) may be nullptr
 int launch_product_hard(const cc_product *pc, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip, int32_t *d_last,
                         int32_t *d_status, size_t B, hipStream_t stream);
+// staircase.hip: staircase codes of one component code; sc checked by the caller (capi.hip)
+struct StaircaseShape {
+  int e;                       // 1: lines of the extended code
+  size_t m, r, kb, L, N, K;    // block side, parity bits and message bits per row, blocks, L m m code bits, L m kb message bits
+};
+StaircaseShape staircase_shape(const cc_staircase *sc);
+size_t staircase_lds_bytes(const cc_staircase *sc);  // LDS of a workgroup of the decoder
+// d_out may be d_in; d_nflip and d_status (one per stream) may be nullptr
+int launch_staircase_decode(const cc_staircase *sc, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip, int32_t *d_status,
+                            size_t B, hipStream_t stream);
+int launch_staircase_encode(const cc_staircase *sc, const uint8_t *d_msg, uint8_t *d_cw, size_t B, hipStream_t stream);
+int launch_staircase_extract(const cc_staircase *sc, const uint8_t *d_cw, uint8_t *d_msg, size_t B, hipStream_t stream);
+// streams [first_stream, first_stream + streams) of the AWGN channel as hard decisions; d_sent (nullptr: not wanted)
+int staircase_awgn(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64_t first_stream, size_t streams,
+                   int random_codewords, uint8_t *d_z, uint8_t *d_sent, hipStream_t stream);
+// product.hip: the Monte-Carlo route of the product codes with a stream as the block; counts over the blocks 1 .. L_c
+int mc_run_staircase(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64_t first_stream, size_t streams,
+                     int random_codewords, uint64_t *d_counters, hipStream_t stream);
 // mc.hip (Monte-Carlo calls on one handle must be issued on one stream at a time: they share a workspace)
 int mc_run(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
            uint64_t *d_counters, hipStream_t stream);

@@ -21,6 +21,8 @@
 //                       half-iteration failed, into the CC_MC_* slots: one wavefront per block, the counts of a
 //                       wavefront in registers, one 64-bit atomic per wavefront and slot at the end; for the
 //                       hard-decision decoder (product_hard.hip) also the half-iterations the blocks took
+//                       and for a route that compares only the leading values of a block (the counted blocks of a
+//                       staircase stream, staircase.hip) the channel's flips among them
 //
 // The byte turns (out, the encoder's intermediate words) are launch_interleave at width 1: I = w2 or w1 <= 256.
 // No kernel here touches a value outside the B * N (B * lines) it is given.
@@ -117,18 +119,25 @@ resize_rows_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, in
 // last: the half-iterations a block took, one per block, into CC_MC_ITER_SUM and the histogram slot of the block (one
 // atomic of its own), or nullptr: both are left alone
 __global__ void __launch_bounds__(256)
-product_count_kernel(const uint8_t *__restrict__ decided, const uint8_t *__restrict__ sent, const int32_t *__restrict__ status,
-                     const int32_t *__restrict__ last, unsigned long long N, int lines, unsigned long long blocks,
-                     unsigned long long *__restrict__ counters) {
+product_count_kernel(const uint8_t *__restrict__ decided, const uint8_t *__restrict__ sent, const uint8_t *__restrict__ received,
+                     const int32_t *__restrict__ status, const int32_t *__restrict__ last, unsigned long long N,
+                     unsigned long long Ncount, int lines, unsigned long long blocks, unsigned long long *__restrict__ counters) {
   const int lane = threadIdx.x & 63;
   const unsigned long long wave = static_cast<unsigned long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
   const unsigned long long waves = static_cast<unsigned long long>(gridDim.x) * 4;
   // lane 0: of the blocks this wavefront saw
-  unsigned long long c_frames = 0, c_bit = 0, c_word = 0, c_fail = 0, c_und = 0, c_iter = 0;
+  unsigned long long c_frames = 0, c_bit = 0, c_word = 0, c_fail = 0, c_und = 0, c_iter = 0, c_chan = 0;
   for (unsigned long long b = wave; b < blocks; b += waves) {
     const uint8_t *d = decided + b * N, *s = sent ? sent + b * N : nullptr;
     unsigned cnt = 0;
-    for (unsigned long long i = lane; i < N; i += 64) cnt += (d[i] != (s ? s[i] : 0)) ? 1u : 0u;
+    for (unsigned long long i = lane; i < Ncount; i += 64) cnt += (d[i] != (s ? s[i] : 0)) ? 1u : 0u;
+    if (received) {  // the channel's flips among the values compared (a route whose channel launch does not count them)
+      const uint8_t *z = received + b * N;
+      unsigned flips = 0;
+      for (unsigned long long i = lane; i < Ncount; i += 64) flips += (z[i] != (s ? s[i] : 0)) ? 1u : 0u;
+      for (int m = 32; m >= 1; m >>= 1) flips += static_cast<unsigned>(__shfl_xor(static_cast<int>(flips), m, 64));
+      c_chan += flips;
+    }
     bool bad = false;
     for (int i = lane; i < lines; i += 64) bad = bad || status[b * lines + i] != CC_FRAME_OK;
     for (int m = 32; m >= 1; m >>= 1) cnt += static_cast<unsigned>(__shfl_xor(static_cast<int>(cnt), m, 64));
@@ -151,6 +160,7 @@ product_count_kernel(const uint8_t *__restrict__ decided, const uint8_t *__restr
     if (c_fail) atomicAdd(&counters[CC_MC_FAILURES], c_fail);
     if (c_und) atomicAdd(&counters[CC_MC_UNDETECTED], c_und);
     if (c_iter) atomicAdd(&counters[CC_MC_ITER_SUM], c_iter);
+    if (c_chan) atomicAdd(&counters[CC_MC_CHANNEL_BIT_ERRORS], c_chan);
   }
 }
 
@@ -193,28 +203,6 @@ int launch_resize_rows(const cc_code *code, bool append, const uint8_t *in, uint
 int turn_bytes(const uint8_t *in, uint8_t *out, size_t blocks, size_t R, size_t C, hipStream_t stream) {
   return launch_interleave(in, 1, C, R, out, blocks * R, true, stream);
 }
-
-// stream-ordered scratch of one call, returned to the pool on every way out
-struct Scratch {
-  const cc_code *code;
-  hipStream_t stream;
-  void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  int used = 0;
-  Scratch(const cc_code *c, hipStream_t s) : code(c), stream(s) {}
-  Scratch(const Scratch &) = delete;
-  Scratch &operator=(const Scratch &) = delete;
-  ~Scratch() {
-    for (int i = 0; i < used; ++i)
-      if (p[i]) (void)hipFreeAsync(p[i], stream);
-  }
-  template <class T>
-  hipError_t get(T **out, size_t bytes) {
-    const hipError_t e = workspace_alloc(code, &p[used], bytes ? bytes : 1, stream);
-    *out = static_cast<T *>(p[used]);
-    if (e == hipSuccess) ++used;
-    return e;
-  }
-};
 
 }  // namespace
 
@@ -315,26 +303,42 @@ int launch_product_extract(const cc_product *pc, const uint8_t *d_cw, uint8_t *d
   return rc;
 }
 
-// d_sent == nullptr: the all-zero block; d_status: `lines` entries per block; d_last: one per block or nullptr
-static int launch_product_count(const cc_product *pc, const uint8_t *d_decided, const uint8_t *d_sent, const int32_t *d_status,
-                                const int32_t *d_last, size_t lines, size_t B, uint64_t *d_counters, hipStream_t stream) {
+// What a Monte-Carlo route knows of its blocks: the handle that sizes grids and owns the workspace pool, the values and
+// message bits of a block, how many leading values the count compares, the channel's sigma and the chunk's floor.  in_place: the hard
+// decisions are decoded where the channel launch wrote them and that launch counts its flips (over all N values);
+// otherwise the decoder writes next to them and the count kernel counts the flips among the values it compares.
+struct BlockRoute {
+  const cc_code *code;
+  size_t N, K, Ncount;
+  float sigma;
+  bool in_place;
+  size_t chunk_floor;  // blocks a chunk should hold at least (product_chunk_blocks)
+};
+
+// d_sent == nullptr: the all-zero block; d_received: nullptr unless the count takes the channel's flips; d_status: `lines`
+// entries per block; d_last: one per block or nullptr
+static int launch_block_count(const BlockRoute &r, const uint8_t *d_decided, const uint8_t *d_sent, const uint8_t *d_received,
+                              const int32_t *d_status, const int32_t *d_last, size_t lines, size_t B, uint64_t *d_counters,
+                              hipStream_t stream) {
   if (B == 0) return CC_OK;
-  hipLaunchKernelGGL(product_count_kernel, dim3(grid_of(pc->rows, (static_cast<unsigned long long>(B) + 3) / 4)), dim3(256), 0,
-                     stream, d_decided, d_sent, d_status, d_last, static_cast<unsigned long long>(product_shape(pc).N),
-                     static_cast<int>(lines), static_cast<unsigned long long>(B),
+  hipLaunchKernelGGL(product_count_kernel, dim3(grid_of(r.code, (static_cast<unsigned long long>(B) + 3) / 4)), dim3(256), 0,
+                     stream, d_decided, d_sent, d_received, d_status, d_last, static_cast<unsigned long long>(r.N),
+                     static_cast<unsigned long long>(r.Ncount), static_cast<int>(lines), static_cast<unsigned long long>(B),
                      reinterpret_cast<unsigned long long *>(d_counters));
   return launched("product count kernel launch");
 }
 
 // Blocks per chunk of the Monte-Carlo and channel routes: 2^24 values (CC_AMD_PRODUCT_MC_CHUNK_VALUES: tests cross a chunk
-// boundary with a small call), about 18 bytes of workspace per value, at least one block
-static size_t product_chunk_blocks(size_t N, size_t blocks) {
-  static const size_t chunk_values = [] {
+// boundary with a small call), about 18 bytes of workspace per value, at least one block.  at_least: a route whose decoder
+// gives a block to one workgroup for milliseconds (a staircase stream) asks for that many blocks per chunk so that a chunk
+// fills the device; the environment's value, where given, is taken as it is.
+size_t product_chunk_blocks(size_t N, size_t blocks, size_t at_least) {
+  static const long long given = [] {
     const char *e = std::getenv("CC_AMD_PRODUCT_MC_CHUNK_VALUES");
-    const long long v = e ? std::atoll(e) : 0;
-    return v > 0 ? static_cast<size_t>(v) : size_t(1) << 24;
+    return e ? std::atoll(e) : 0ll;
   }();
-  size_t ch = chunk_values / N;
+  size_t ch = (given > 0 ? static_cast<size_t>(given) : size_t(1) << 24) / N;
+  if (given <= 0 && ch < at_least) ch = at_least;
   if (ch < 1) ch = 1;
   return ch < blocks ? ch : blocks;
 }
@@ -371,57 +375,66 @@ int product_awgn(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t f
   return CC_OK;
 }
 
-// One Monte-Carlo route for both decoders, chunk by chunk: the blocks sent, the channel, decode(m, received, decided,
-// status, last), the count.  The counters of a block are a function of (seed, ebno, pc, global block index) alone.
-// T = float: the channel writes y, the decoder its decisions next to it.  T = uint8_t: the channel launch writes the hard
-// decisions z = (y < 0) itself, the decoder runs in place and reports `last`.  lines: status entries per block.
-template <class T, class Decode>
-static int mc_product_route(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
-                            int random_codewords, size_t lines, uint64_t *d_counters, hipStream_t stream, Decode decode) {
+// One Monte-Carlo route for the decoders of blocks, chunk by chunk: the blocks sent (sent_of(first, m, msg, sent)), the
+// channel, decode(m, received, decided, status, last), the count.  The counters of a block are a function of (seed, ebno,
+// the code, global block index) alone.  T = float: the channel writes y, the decoder its decisions next to it.
+// T = uint8_t: the channel launch writes the hard decisions z = (y < 0) itself and the decoder reports `last` (or leaves
+// it alone: wants_last).  lines: status entries per block.
+template <class T, class SentOf, class Decode>
+static int mc_block_route(const BlockRoute &r, uint64_t seed, uint64_t first_block, size_t blocks, int random_codewords,
+                          size_t lines, bool wants_last, uint64_t *d_counters, hipStream_t stream, SentOf sent_of, Decode decode) {
   constexpr bool hard = std::is_same<T, uint8_t>::value;
   if (blocks == 0) return CC_OK;
-  const ProductShape s = product_shape(pc);
-  const float sigma = static_cast<float>(cc_product_sigma(pc, ebno_db));
-  const size_t chunk = product_chunk_blocks(s.N, blocks);
-  Scratch scratch(pc->rows, stream);
+  const size_t chunk = product_chunk_blocks(r.N, blocks, r.chunk_floor);
+  const bool in_place = hard && r.in_place;
+  Scratch scratch(r.code, stream);
   T *received = nullptr;
   uint8_t *decided = nullptr, *sent = nullptr, *msg = nullptr;
   int32_t *status = nullptr, *last = nullptr;
-  CC_HIP_TRY(scratch.get(&received, chunk * s.N * sizeof(T)));
-  if constexpr (hard)
-    decided = received;
+  CC_HIP_TRY(scratch.get(&received, chunk * r.N * sizeof(T)));
+  if (in_place)
+    decided = reinterpret_cast<uint8_t *>(received);
   else
-    CC_HIP_TRY(scratch.get(&decided, chunk * s.N));
+    CC_HIP_TRY(scratch.get(&decided, chunk * r.N));
   CC_HIP_TRY(scratch.get(&status, chunk * lines * sizeof(int32_t)));
-  if (hard) CC_HIP_TRY(scratch.get(&last, chunk * sizeof(int32_t)));
+  if (wants_last) CC_HIP_TRY(scratch.get(&last, chunk * sizeof(int32_t)));
   if (random_codewords) {
-    CC_HIP_TRY(scratch.get(&sent, chunk * s.N));
-    CC_HIP_TRY(scratch.get(&msg, chunk * s.k1 * s.k2));
+    CC_HIP_TRY(scratch.get(&sent, chunk * r.N));
+    CC_HIP_TRY(scratch.get(&msg, chunk * r.K));
   }
-  unsigned long long *counters = reinterpret_cast<unsigned long long *>(d_counters);
+  // (the channel launch counts its flips over all N values; a route that compares fewer leaves them to the count)
+  const bool channel_counts = !hard || in_place;
+  unsigned long long *counters = channel_counts ? reinterpret_cast<unsigned long long *>(d_counters) : nullptr;
   for (size_t done = 0; done < blocks; done += chunk) {
     const size_t m = blocks - done < chunk ? blocks - done : chunk;
     if (random_codewords)
-      if (int rc = product_sent(pc, seed, first_block + done, m, msg, sent, stream)) return rc;
+      if (int rc = sent_of(first_block + done, m, msg, sent)) return rc;
     int rc;
     if constexpr (hard)
-      rc = launch_awgn_hard(pc->rows, static_cast<int>(s.N), sigma, seed, first_block + done, m, received, sent, stream, counters);
+      rc = launch_awgn_hard(r.code, static_cast<int>(r.N), r.sigma, seed, first_block + done, m, received, sent, stream, counters);
     else
-      rc = launch_awgn_values(pc->rows, static_cast<int>(s.N), sigma, seed, first_block + done, m, received, sent, stream, counters);
+      rc = launch_awgn_values(r.code, static_cast<int>(r.N), r.sigma, seed, first_block + done, m, received, sent, stream, counters);
     if (rc != CC_OK) return rc;
     if ((rc = decode(m, received, decided, status, last)) != CC_OK) return rc;
-    if ((rc = launch_product_count(pc, decided, sent, status, last, lines, m, d_counters, stream)) != CC_OK) return rc;
+    const uint8_t *flips = channel_counts ? nullptr : reinterpret_cast<const uint8_t *>(received);
+    if ((rc = launch_block_count(r, decided, sent, flips, status, last, lines, m, d_counters, stream)) != CC_OK) return rc;
   }
   return CC_OK;
+}
+
+static BlockRoute product_route(const cc_product *pc, double ebno_db) {
+  const ProductShape s = product_shape(pc);
+  return BlockRoute{pc->rows, s.N, s.k1 * s.k2, s.N, static_cast<float>(cc_product_sigma(pc, ebno_db)), true, 1};
 }
 
 // the turbo decoder with the hard output in its last half-iteration, whose component words give the status
 int mc_run_product(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
                    int random_codewords, uint64_t *d_counters, hipStream_t stream) {
   const ProductShape s = product_shape(pc);
-  return mc_product_route<float>(pc, ebno_db, seed, first_block, blocks, random_codewords, (pc->halves & 1) ? s.w2 : s.w1,
-                                 d_counters, stream,
-                                 [&](size_t m, const float *y, uint8_t *decided, int32_t *status, int32_t *) {
+  const auto sent_of = [&](uint64_t first, size_t m, uint8_t *msg, uint8_t *sent) { return product_sent(pc, seed, first, m, msg, sent, stream); };
+  return mc_block_route<float>(product_route(pc, ebno_db), seed, first_block, blocks, random_codewords,
+                               (pc->halves & 1) ? s.w2 : s.w1, false, d_counters, stream, sent_of,
+                               [&](size_t m, const float *y, uint8_t *decided, int32_t *status, int32_t *) {
     return launch_product_decode(pc, y, decided, nullptr, status, m, stream);
   });
 }
@@ -429,9 +442,31 @@ int mc_run_product(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t
 // the hard-decision decoder (product_hard.hip), one status per block
 int mc_run_product_hard(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
                         int random_codewords, uint64_t *d_counters, hipStream_t stream) {
-  return mc_product_route<uint8_t>(pc, ebno_db, seed, first_block, blocks, random_codewords, 1, d_counters, stream,
-                                   [&](size_t m, const uint8_t *z, uint8_t *decided, int32_t *status, int32_t *last) {
+  const auto sent_of = [&](uint64_t first, size_t m, uint8_t *msg, uint8_t *sent) { return product_sent(pc, seed, first, m, msg, sent, stream); };
+  return mc_block_route<uint8_t>(product_route(pc, ebno_db), seed, first_block, blocks, random_codewords, 1, true, d_counters,
+                                 stream, sent_of,
+                                 [&](size_t m, const uint8_t *z, uint8_t *decided, int32_t *status, int32_t *last) {
     return launch_product_hard(pc, z, decided, nullptr, last, status, m, stream);
+  });
+}
+
+// the staircase decoder (staircase.hip) through the same route, a stream as the block: one status per stream, the count
+// over the blocks that were decoded with a full window ahead of them
+int mc_run_staircase(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64_t first_stream, size_t streams,
+                     int random_codewords, uint64_t *d_counters, hipStream_t stream) {
+  const StaircaseShape s = staircase_shape(sc);
+  const size_t counted = s.L >= sc->window ? s.L - sc->window + 1 : s.L;
+  // a chunk of a stream per compute unit where that stays within 2^28 values (2^27 at m = 128, L = 32)
+  const size_t fit = (size_t(1) << 28) / s.N, cus = static_cast<size_t>(sc->code->num_cus);
+  const BlockRoute route{sc->code, s.N, s.K, counted * s.m * s.m, static_cast<float>(cc_staircase_sigma(sc, ebno_db)), false,
+                         fit < cus ? fit : cus};
+  const auto sent_of = [&](uint64_t first, size_t m, uint8_t *msg, uint8_t *sent) {
+    if (int rc = launch_random_bits(sc->code, static_cast<int>(s.K), seed, first, m, msg, stream)) return rc;
+    return launch_staircase_encode(sc, msg, sent, m, stream);
+  };
+  return mc_block_route<uint8_t>(route, seed, first_stream, streams, random_codewords, 1, false, d_counters, stream, sent_of,
+                                 [&](size_t m, const uint8_t *z, uint8_t *decided, int32_t *status, int32_t *) {
+    return launch_staircase_decode(sc, z, decided, nullptr, status, m, stream);
   });
 }
 

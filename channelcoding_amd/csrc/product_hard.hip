@@ -32,27 +32,12 @@
 // Global traffic per block: N bytes in (a ballot per 64 bytes makes the bits), N bytes out, three int32.
 #include <mutex>
 
-#include "soft_lanes.hpp"
+#include "hard_lines.hpp"
 
 namespace ccamd {
 namespace {
 
 constexpr int kHardTables = 2 * kSoftTables;  // the tables of `rows`, then those of `cols`
-
-template <int NC>
-__device__ __forceinline__ bool any_bit(const unsigned long long (&m)[NC]) {
-  unsigned long long o = 0;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) o |= m[c];
-  return o != 0;
-}
-template <int NC>
-__device__ __forceinline__ int count_bits(const unsigned long long (&m)[NC]) {
-  int cnt = 0;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) cnt += __builtin_popcountll(m[c]);
-  return cnt;
-}
 
 // the bits of line `line` of X: row `line` (w1 bits, PD dwords) or column `line` (w2 bits)
 template <int NC>
@@ -79,23 +64,6 @@ __device__ __forceinline__ void gather_line(const uint32_t *X, int P, int PD, in
       lb[c] = acc;
     }
   }
-}
-
-// S_j of the positions 0 .. n-1 of a line
-template <int NC>
-__device__ __forceinline__ uint32_t line_syndrome(const uint8_t *ex, const unsigned long long (&lb)[NC], int n, int nn, int j) {
-  const uint32_t step = static_cast<uint32_t>(j) % static_cast<uint32_t>(nn);
-  uint32_t s = 0, ev = 0;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int stop = n - 64 * c < 64 ? n - 64 * c : 64;
-#pragma unroll 8
-    for (int b = 0; b < stop; ++b) {  // (unrolled: eight look-ups in flight, the exponent chain is arithmetic alone)
-      s ^= ((lb[c] >> b) & 1ull) ? static_cast<uint32_t>(ex[ev]) : 0u;
-      ev = addmod(ev, step, nn);
-    }
-  }
-  return s;
 }
 
 // the LDS of one block, in dwords: X and X0 [w2][P], ctl [4], then the state of every line as bytes -- the t odd
@@ -193,79 +161,16 @@ product_hard_kernel(const AlgebraicTables *__restrict__ Tr, const AlgebraicTable
       const bool column = (h & 1) != 0;
       const uint8_t *ex = smem + (column ? kSoftTables : 0);
       const uint16_t *lg2 = reinterpret_cast<const uint16_t *>(ex + 1024);
-      const int n = column ? n2 : n1, nn = column ? nnc : nnr, t = column ? tc : tr, t2 = 2 * t;
-      const BmColumns bm = bm_columns(t2);
+      const int n = column ? n2 : n1, nn = column ? nnc : nnr, t = column ? tc : tr;
+      const BmColumns bm = bm_columns(2 * t);
       uint16_t *SL = reinterpret_cast<uint16_t *>(colbase + bm.SL);
       uint16_t *LL = reinterpret_cast<uint16_t *>(colbase + bm.LL);
       uint16_t *BL = reinterpret_cast<uint16_t *>(colbase + bm.BL);
       const bool have_line = line < (column ? w1 : w2);
       uint8_t *S = (column ? SC : SR) + line * (column ? pitch_c : pitch_r);
 
-      // (a lane without a line: syndromes zero, its column holds log 0)
-      bool nz = false;
-      for (int m = 0; m < t; ++m) {
-        const uint32_t s = have_line ? S[m] : 0u;
-        SL[2 * m * 64 + lane] = lg2[s];
-        nz = nz || s != 0;
-      }
-      const uint32_t par = (e && have_line) ? S[t] : 0u;  // parity of the n + 1 bits of the line
-      const bool mine = have_line && nz;
-
       unsigned long long fm[NC];  // positions the line changes at
-#pragma unroll
-      for (int c = 0; c < NC; ++c) fm[c] = 0;
-      bool have = false;
-      if (__any(mine ? 1 : 0)) {
-        for (int m = 2; m <= t2; m += 2) {  // S_m = S_(m/2)^2
-          const uint32_t ls = SL[(m / 2 - 1) * 64 + lane];
-          SL[(m - 1) * 64 + lane] = static_cast<uint16_t>(ls >= kLogZero ? kLogZero : addmod(ls, ls, nn));
-        }
-        int deg;
-        const int len = bm_lds<64>(ex, lg2, SL, LL, BL, t2, nn, mine, 0u, nullptr, 0u, deg);
-        const bool viable = mine && len == deg && deg <= t;
-        wave_sync();  // the locators are read across lanes below
-        // the roots of one locator at a time, by all 64 lanes: lane l evaluates it at the positions l + 64 c
-        int nroots = -1;
-        unsigned long long todo = __ballot(viable ? 1 : 0);
-        while (todo) {
-          const int L = __builtin_ctzll(todo);
-          todo &= todo - 1ull;
-          const int dL = __builtin_amdgcn_readlane(deg, L);
-          int found = 0;
-#pragma unroll
-          for (int c = 0; c < NC; ++c) {
-            const int pos = lane + 64 * c;
-            const uint32_t xinv = pos == 0 ? 0u : static_cast<uint32_t>(nn - pos);  // log of alpha^-pos (pos < n <= nn)
-            uint32_t acc = 0, ev = 0;
-            if (pos < n)
-              for (int m = 0; m <= dL; ++m) {
-                acc ^= ex[LL[m * 64 + L] + ev];
-                ev = addmod(ev, xinv, nn);
-              }
-            const unsigned long long roots = __ballot((pos < n && acc == 0) ? 1 : 0);
-            if (lane == L) fm[c] = roots;
-            found += __builtin_popcountll(roots);
-          }
-          if (lane == L) nroots = found;
-        }
-        have = viable && nroots == deg;
-        if (!have) {
-#pragma unroll
-          for (int c = 0; c < NC; ++c) fm[c] = 0;
-        }
-      }
-      // the inner candidate: the line itself where its syndromes are zero, else what the locator gave
-      const bool cand = have_line && (!nz || have);
-      if (e) {  // bounded distance in the extended code: d_H over the n inner positions plus the parity position
-        const int cnt = count_bits<NC>(fm);
-        const bool pflip = ((par ^ static_cast<uint32_t>(cnt)) & 1u) != 0;  // parity(c') != w_n
-        const bool take = cand && cnt + (pflip ? 1 : 0) <= t;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          if (!take) fm[c] = 0;
-          if (take && pflip && (n >> 6) == c) fm[c] |= 1ull << (n & 63);
-        }
-      }
+      line_flips<NC>(ex, lg2, SL, LL, BL, S, have_line, lane, n, nn, t, e, fm);
       const bool changed = any_bit<NC>(fm);
       sync();  // every line of the pass has been read
       if (changed) {

@@ -1,0 +1,416 @@
+// staircase.hip -- staircase codes of one binary BCH component: the sliding-window iterated
+// bounded-distance decoder of a whole stream in one launch, and the block-by-block encoder.  The contract is stated at
+// cc_staircase in the public header; here is how it is mapped.
+//
+// One workgroup of 256 threads owns a stream from its first block to its last.  The window is a ring of W tiles in LDS:
+// block i lives in tile i mod W as bits, m rows of P dwords, P = ceil(m / 32) | 1 odd (product_hard.hip's tile).  Tile 0
+// starts as B_0 = 0.  Next to every tile lies the state of the step of the same number: for each of its m lines the t odd
+// syndromes and the parity of the line's bits, at a pitch of whole dwords.  W states, not W - 1: step b is no longer
+// decoded at position b, but block b still changes there (the lines of step b + 1 run down its columns), and `status` needs
+// the syndromes of step b when block b leaves.
+//
+//   entering   a block is loaded through ballots (64 bytes -> one 64-bit mask); the state of its step is computed once,
+//              one lane per line, from the column of the block before and the row of the block itself
+//   half-pass  the lines of the steps top - h, top - h - 2, .. are dealt to the 256 lanes, trip after trip; a lane decodes
+//              its line from the line's state alone (hard_lines.hpp: syndromes -> lane_bm -> wavefront-shared root search
+//              -> the d <= t rule), never from the bits.  The steps of a half-pass share no bit, and a flip touches the
+//              states of the two neighbouring steps only, which are not in this half-pass: so a trip may apply its flips
+//              at once -- no line of the half-pass, in this trip or a later one, can see them -- and one barrier closes
+//              the half-pass.  A flip of B_i[r][c] adds alpha^(j c) to line r of step i (parity alone for the parity
+//              column) and alpha^(j (m - e + r)) to line c of step i + 1 where that step is resident, with LDS atomics.
+//   B_0        a line of step 1 whose flips reach a position of the zero block stays
+//   leaving    the state of step b gives its part of `status`, the tile goes out as bytes and is compared with `in` on
+//              the way (still intact for that block, in place too)
+// A position stops after two successive half-passes without a change: the state then repeats, no output can show it.
+#include <mutex>
+
+#include "hard_lines.hpp"
+
+namespace ccamd {
+namespace {
+
+// the LDS of a workgroup behind the tables and the four sets of Berlekamp-Massey columns, in dwords: ctl [4], W tiles
+// [m][P], W step states [m][pitch bytes]
+struct StairLayout {
+  int P, pitch, tile, state, dwords;
+};
+__host__ __device__ constexpr StairLayout stair_layout(int m, int t, int W) {
+  const int P = ((m + 31) >> 5) | 1, pitch = (t + 4) & ~3;
+  return StairLayout{P, pitch, m * P, m * pitch / 4, 4 + W * (m * P + m * pitch / 4)};
+}
+constexpr size_t stair_lds_bytes(int m, int t, int W) {
+  return kSoftTables + 4 * static_cast<size_t>(bm_columns(2 * t).end) + 4 * static_cast<size_t>(stair_layout(m, t, W).dwords);
+}
+// no admitted shape exceeds m = 128 (q <= 8) with t = 16 (2t <= 32) and sixteen blocks
+static_assert(stair_lds_bytes(128, 16, CC_STAIRCASE_MAX_WINDOW) <= 160 * 1024, "the window must fit the LDS of a workgroup");
+
+// bits [lo, hi) of a 64-bit word, 0 <= lo, hi <= 64
+__device__ __forceinline__ unsigned long long bit_range(int lo, int hi) {
+  const unsigned long long upto_hi = hi >= 64 ? ~0ull : (1ull << hi) - 1ull, upto_lo = lo >= 64 ? ~0ull : (1ull << lo) - 1ull;
+  return hi > lo ? upto_hi & ~upto_lo : 0ull;
+}
+__device__ __forceinline__ int clamp64(int v) { return v < 0 ? 0 : v > 64 ? 64 : v; }
+
+// NC = 1: lines of up to 64 bits (m <= 32); NC = 4: up to 256 bits
+template <int NC>
+__global__ void __launch_bounds__(256)
+staircase_kernel(const AlgebraicTables *__restrict__ T, const uint8_t *in, uint8_t *out, int32_t *__restrict__ nflip_out,
+                 int32_t *__restrict__ status_out, unsigned long long B, int L, int W, int iters, int e, int col_bytes) {
+  constexpr int CB = NC == 1 ? 1 : 2;  // 64-byte chunks of a row of a block
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const uint8_t *ex = smem;
+  const uint16_t *lg2 = stage_tables(T, smem);
+
+  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n = T->n, nn = T->nf, t = T->nroots / 2, m = (n + e) >> 1, me = m - e;
+  const int PD = (m + 31) >> 5;
+  const StairLayout lay = stair_layout(m, t, W);
+  const int P = lay.P, pitch = lay.pitch;
+  const unsigned long long mm = static_cast<unsigned long long>(m) * m, N = mm * L;
+  uint8_t *colbase = smem + kSoftTables + wid * col_bytes;
+  const BmColumns bm = bm_columns(2 * t);
+  uint16_t *SL = reinterpret_cast<uint16_t *>(colbase + bm.SL);
+  uint16_t *LL = reinterpret_cast<uint16_t *>(colbase + bm.LL);
+  uint16_t *BL = reinterpret_cast<uint16_t *>(colbase + bm.BL);
+  uint32_t *ctl = reinterpret_cast<uint32_t *>(smem + kSoftTables + 4 * col_bytes);  // [0] last half-pass that changed, + 1
+  uint32_t *ring = ctl + 4;                                                          // [1] a line that is no word, [2] nflip
+  uint8_t *states = reinterpret_cast<uint8_t *>(ring + W * lay.tile);
+  const auto tile = [&](int blk) { return ring + (blk % W) * lay.tile; };
+  const auto state = [&](int step) { return states + (step % W) * (4 * lay.state); };
+  const int pw = (m - 1) >> 5, pb = (m - 1) & 31;  // the parity column of a block
+
+  // a flip at position `pos` of line `line` of the step whose states are S32 (pos < 0: the parity position)
+  const auto flip_state = [&](uint32_t *S32, int line, int pos) {
+    if (pos >= 0) {
+      const uint32_t step2 = addmod(pos, pos, nn);
+      uint32_t ev = static_cast<uint32_t>(pos);
+      for (int k = 0; k < t; ++k) {
+        const int idx = line * pitch + k;
+        atomicXor(&S32[idx >> 2], static_cast<uint32_t>(ex[ev]) << (8 * (idx & 3)));
+        ev = addmod(ev, step2, nn);
+      }
+    }
+    if (e) {
+      const int idx = line * pitch + t;
+      atomicXor(&S32[idx >> 2], 1u << (8 * (idx & 3)));
+    }
+  };
+
+  for (unsigned long long s = blockIdx.x; s < B; s += gridDim.x) {
+    const uint8_t *src = in + s * N;
+    uint8_t *dst = out + s * N;
+
+    // block `blk` leaves: step blk's part of the status, bits -> bytes, its part of nflip
+    const auto retire = [&](int blk) {
+      const uint8_t *S = state(blk);
+      bool bad = false;
+      if (tid < m)
+        for (int k = 0; k < t + e; ++k) bad = bad || S[tid * pitch + k] != 0;
+      if (bad) atomicOr(&ctl[1], 1u);
+      const uint32_t *X = tile(blk);
+      const unsigned long long off = static_cast<unsigned long long>(blk - 1) * mm;
+      uint32_t diff = 0;
+      for (int r = wid; r < m; r += 4)
+#pragma unroll
+        for (int c = 0; c < CB; ++c) {
+          const int col = 64 * c + lane;
+          if (col < m) {
+            const unsigned long long at = off + static_cast<unsigned long long>(r) * m + col;
+            const uint32_t bit = (X[r * P + (col >> 5)] >> (col & 31)) & 1u;
+            diff += (src[at] & 1u) != bit ? 1u : 0u;
+            dst[at] = static_cast<uint8_t>(bit);
+          }
+        }
+      if (diff) atomicAdd(&ctl[2], diff);
+    };
+
+    for (int i = tid; i < lay.tile; i += 256) ring[i] = 0;  // B_0
+    if (tid < 4) ctl[tid] = 0;
+    const int b_last = L >= W ? L - W + 1 : 0;
+    int loaded = 0;
+    for (int b = 0; b <= b_last; ++b) {
+      const int top = b + W - 1 < L ? b + W - 1 : L;
+      // ---------------- the blocks that enter: bytes -> bits ----------------
+      for (int blk = loaded + 1; blk <= top; ++blk) {
+        const uint8_t *sb = src + static_cast<unsigned long long>(blk - 1) * mm;
+        uint32_t *X = tile(blk);
+        constexpr int U = 4;  // (U rows at a time: all their loads are issued before the first ballot waits for one)
+        for (int r = wid; r < m; r += 4 * U) {
+          uint32_t v[U][CB];
+#pragma unroll
+          for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int c = 0; c < CB; ++c) {
+              const int rr = r + 4 * u, col = 64 * c + lane;
+              v[u][c] = (rr < m && col < m) ? sb[static_cast<unsigned long long>(rr) * m + col] : 0u;
+            }
+#pragma unroll
+          for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int c = 0; c < CB; ++c) {
+              const int rr = r + 4 * u;
+              const unsigned long long mask = __ballot((v[u][c] & 1u) != 0);
+              if (rr < m && lane < 2 && 2 * c + lane < PD) X[rr * P + 2 * c + lane] = static_cast<uint32_t>(lane ? mask >> 32 : mask);
+            }
+        }
+      }
+      if (tid == 0) ctl[0] = 0;
+      __syncthreads();
+      // ---------------- the state of every line of the steps that enter, from the bits, once ----------------
+      for (int g = tid; g < (top - loaded) * m; g += 256) {
+        const int sidx = g / m, j = g - sidx * m, i = loaded + 1 + sidx;
+        const uint32_t *Xi = tile(i) + j * P, *Xp = tile(i - 1) + (j >> 5);
+        const int jb = j & 31;
+        unsigned long long lb[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const int r1 = clamp64(me - 64 * c), c1 = clamp64(n - 64 * c);
+          unsigned long long acc = 0;
+#pragma unroll 8
+          for (int k = 0; k < r1; ++k) {  // row j of the block itself
+            const int pos = 64 * c + k;
+            acc |= static_cast<unsigned long long>((Xi[pos >> 5] >> (pos & 31)) & 1u) << k;
+          }
+#pragma unroll 8
+          for (int k = r1; k < c1; ++k)  // column j of the block before
+            acc |= static_cast<unsigned long long>((Xp[(64 * c + k - me) * P] >> jb) & 1u) << k;
+          if (e && (n >> 6) == c) acc |= static_cast<unsigned long long>((Xi[pw] >> pb) & 1u) << (n & 63);
+          lb[c] = acc;
+        }
+        uint8_t *S = state(i) + j * pitch;
+        for (int k = 0; k < t; ++k) S[k] = static_cast<uint8_t>(line_syndrome<NC>(ex, lb, n, nn, 2 * k + 1));
+        S[t] = static_cast<uint8_t>(count_bits<NC>(lb) & 1);
+      }
+      loaded = top;
+      __syncthreads();
+
+      // ---------------- the half-passes of this position ----------------
+      for (int h = 0; h < 2 * iters; ++h) {
+        const int i0 = top - (h & 1);
+        const int total = i0 > b ? ((i0 - b - 1) / 2 + 1) * m : 0;  // lines of the steps i0, i0 - 2, .. > b
+        for (int base = 0; base < total; base += 256) {
+          if (base + 64 * wid >= total) continue;  // a wavefront without a line in this trip
+          const int g = base + tid;
+          const bool have_line = g < total;
+          const int sidx = have_line ? g / m : 0, j = have_line ? g - sidx * m : 0, i = i0 - 2 * sidx;
+          uint8_t *S = state(i) + j * pitch;
+          unsigned long long fm[NC];  // positions the line changes at
+          line_flips<NC>(ex, lg2, SL, LL, BL, S, have_line, lane, n, nn, t, e, fm);
+          if (i == 1) {  // the zero block stays zero: the line keeps its bits
+            bool reaches = false;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) reaches = reaches || (fm[c] & bit_range(clamp64(me - 64 * c), clamp64(n - 64 * c))) != 0;
+            if (reaches) {
+#pragma unroll
+              for (int c = 0; c < NC; ++c) fm[c] = 0;
+            }
+          }
+          if (any_bit<NC>(fm)) {
+            // the line becomes a word of its code: its own state is zero; a flipped bit of the row half is also a bit of
+            // the next step, one of the column half a bit of the step before
+            for (int k = 0; k <= t; ++k) S[k] = 0;
+            uint32_t *Xi = tile(i), *Xp = tile(i - 1);
+            uint32_t *Sn = reinterpret_cast<uint32_t *>(state(i + 1)), *Sp = reinterpret_cast<uint32_t *>(state(i - 1));
+            const bool next = i + 1 <= top;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+              unsigned long long mask = fm[c];
+              while (mask) {
+                const int p = 64 * c + __builtin_ctzll(mask);
+                mask &= mask - 1ull;
+                if (p < me || p == n) {  // B_i[j][col]
+                  const int col = p < me ? p : m - 1;
+                  atomicXor(&Xi[j * P + (col >> 5)], 1u << (col & 31));
+                  if (next) flip_state(Sn, col, me + j);
+                } else {  // B_(i-1)[a][j], i - 1 >= 1 by the rule above
+                  const int a = p - me;
+                  atomicXor(&Xp[a * P + (j >> 5)], 1u << (j & 31));
+                  flip_state(Sp, a, j < me ? j : -1);
+                }
+              }
+            }
+            atomicMax(&ctl[0], static_cast<uint32_t>(h + 1));
+          }
+          wave_sync();  // the next trip reuses the wavefront's columns
+        }
+        __syncthreads();
+        if (h + 1 - static_cast<int>(ctl[0]) >= 2) break;  // a fixed point; the same value in every lane of the workgroup
+      }
+      if (b < b_last) {  // block b is final; its tile and state are the next block's
+        if (b >= 1) retire(b);
+        __syncthreads();
+      }
+    }
+    for (int blk = b_last > 1 ? b_last : 1; blk <= L; ++blk) retire(blk);
+    __syncthreads();
+    if (tid == 0) {
+      if (nflip_out) nflip_out[s] = static_cast<int32_t>(ctl[2]);
+      if (status_out) status_out[s] = ctl[1] ? CC_FRAME_NOT_CONVERGED : CC_FRAME_OK;
+    }
+    __syncthreads();  // the next stream overwrites the ring and ctl
+  }
+}
+
+// ---------------- the encoder's two small kernels: a thread per (stream, line) ----------------
+// messages of step i: the k_b message bits of row j of block i, then column j of block i - 1 of the code stream
+__global__ void __launch_bounds__(256)
+staircase_gather_kernel(const uint8_t *__restrict__ msg, const uint8_t *__restrict__ cw, uint8_t *__restrict__ lines, unsigned long long B,
+                        int L, int i, int m, int kb) {
+  const unsigned long long total = B * m;
+  for (unsigned long long g = blockIdx.x * 256ull + threadIdx.x; g < total; g += gridDim.x * 256ull) {
+    const unsigned long long s = g / m;
+    const int j = static_cast<int>(g - s * m);
+    uint8_t *dst = lines + g * (kb + m);
+    const uint8_t *src = msg + ((s * L + (i - 1)) * m + j) * kb;
+    for (int a = 0; a < kb; ++a) dst[a] = src[a] & 1u;
+    const uint8_t *prev = i > 1 ? cw + (s * L + (i - 2)) * m * m : nullptr;  // B_0 = 0
+    for (int a = 0; a < m; ++a) dst[kb + a] = prev ? prev[static_cast<unsigned long long>(a) * m + j] : 0;
+  }
+}
+// the first m - e positions of the encoded lines become the rows of block i; extended: the parity of the n inner bits
+__global__ void __launch_bounds__(256)
+staircase_scatter_kernel(const uint8_t *__restrict__ words, uint8_t *__restrict__ cw, unsigned long long B, int L, int i, int m, int n,
+                         int e) {
+  const unsigned long long total = B * m;
+  for (unsigned long long g = blockIdx.x * 256ull + threadIdx.x; g < total; g += gridDim.x * 256ull) {
+    const unsigned long long s = g / m;
+    const int j = static_cast<int>(g - s * m);
+    const uint8_t *w = words + g * n;
+    uint8_t *row = cw + ((s * L + (i - 1)) * m + j) * m;
+    for (int a = 0; a < m - e; ++a) row[a] = w[a];
+    if (e) {
+      uint32_t par = 0;
+      for (int a = 0; a < n; ++a) par ^= w[a];
+      row[m - 1] = static_cast<uint8_t>(par & 1u);
+    }
+  }
+}
+// message bits of a code stream: the columns n - l .. m - 1 - e of every row
+__global__ void __launch_bounds__(256)
+staircase_extract_kernel(const uint8_t *__restrict__ cw, uint8_t *__restrict__ msg, unsigned long long rows, int m, int first, int kb) {
+  const unsigned long long total = rows * kb;
+  for (unsigned long long g = blockIdx.x * 256ull + threadIdx.x; g < total; g += gridDim.x * 256ull) {
+    const unsigned long long r = g / kb;
+    msg[g] = cw[r * m + first + (g - r * kb)];
+  }
+}
+
+unsigned flat_grid(const cc_code *code, unsigned long long items) {
+  const unsigned long long want = (items + 255) / 256, cap = static_cast<unsigned long long>(code->num_cus) * 8;
+  return static_cast<unsigned>(want < 1 ? 1 : want < cap ? want : cap);
+}
+
+}  // namespace
+
+StaircaseShape staircase_shape(const cc_staircase *sc) {
+  StaircaseShape s;
+  s.e = sc->extended ? 1 : 0;
+  const size_t n = sc->code->tab.n, l = sc->code->tab.l;
+  s.m = (n + s.e) / 2;
+  s.r = (n - l) + s.e;
+  s.kb = s.m > s.r ? s.m - s.r : 0;
+  s.L = sc->blocks;
+  s.N = s.L * s.m * s.m;
+  s.K = s.L * s.m * s.kb;
+  return s;
+}
+
+size_t staircase_lds_bytes(const cc_staircase *sc) {
+  const StaircaseShape s = staircase_shape(sc);
+  return stair_lds_bytes(static_cast<int>(s.m), static_cast<int>(sc->code->tab.roots.size()) / 2, static_cast<int>(sc->window));
+}
+
+int launch_staircase_decode(const cc_staircase *sc, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip, int32_t *d_status,
+                            size_t B, hipStream_t stream) {
+  if (B == 0) return CC_OK;
+  const cc_code *code = sc->code;
+  const StaircaseShape s = staircase_shape(sc);
+  const bool wide = 2 * s.m > 64;
+  const int col_bytes = bm_columns(static_cast<int>(code->tab.roots.size()) & ~1).end;
+  const size_t lds = staircase_lds_bytes(sc);
+  if (lds > 64 * 1024) {  // once per device and kernel: a long window of large blocks asks for more than the default limit
+    static std::mutex lock;
+    static unsigned long long done[2] = {0, 0};
+    const unsigned dev = static_cast<unsigned>(code->device) & 63u;
+    std::lock_guard<std::mutex> g(lock);
+    if (!((done[wide] >> dev) & 1ull)) {
+      const void *fn = wide ? reinterpret_cast<const void *>(&staircase_kernel<4>) : reinterpret_cast<const void *>(&staircase_kernel<1>);
+      const hipError_t attr = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      if (attr != hipSuccess) return hip_fail(attr, "staircase kernel LDS attribute");
+      done[wide] |= 1ull << dev;
+    }
+  }
+  const unsigned long long cap = static_cast<unsigned long long>(code->num_cus) * 8;
+  const dim3 grid(static_cast<unsigned>(B < cap ? B : cap));
+  const auto kernel = wide ? staircase_kernel<4> : staircase_kernel<1>;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, code->d_alg, d_in, d_out, d_nflip, d_status,
+                     static_cast<unsigned long long>(B), static_cast<int>(s.L), static_cast<int>(sc->window),
+                     static_cast<int>(sc->iters), s.e, col_bytes);
+  const hipError_t err = hipGetLastError();
+  return err != hipSuccess ? hip_fail(err, "staircase kernel launch") : CC_OK;
+}
+
+// block after block: the messages of a step gathered, the handle's systematic encoder, the rows scattered
+int launch_staircase_encode(const cc_staircase *sc, const uint8_t *d_msg, uint8_t *d_cw, size_t B, hipStream_t stream) {
+  if (B == 0) return CC_OK;
+  const cc_code *code = sc->code;
+  const StaircaseShape s = staircase_shape(sc);
+  const size_t n = code->tab.n, l = code->tab.l, lines = B * s.m;
+  Scratch scratch(code, stream);
+  uint8_t *msgs = nullptr, *words = nullptr;
+  CC_HIP_TRY(scratch.get(&msgs, lines * l));
+  CC_HIP_TRY(scratch.get(&words, lines * n));
+  const dim3 grid(flat_grid(code, lines));
+  for (size_t i = 1; i <= s.L; ++i) {
+    hipLaunchKernelGGL(staircase_gather_kernel, grid, dim3(256), 0, stream, d_msg, d_cw, msgs, static_cast<unsigned long long>(B),
+                       static_cast<int>(s.L), static_cast<int>(i), static_cast<int>(s.m), static_cast<int>(s.kb));
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return hip_fail(err, "staircase gather kernel launch");
+    if (int rc = launch_encode(code, msgs, words, lines, stream)) return rc;
+    hipLaunchKernelGGL(staircase_scatter_kernel, grid, dim3(256), 0, stream, words, d_cw, static_cast<unsigned long long>(B),
+                       static_cast<int>(s.L), static_cast<int>(i), static_cast<int>(s.m), static_cast<int>(n), s.e);
+    err = hipGetLastError();
+    if (err != hipSuccess) return hip_fail(err, "staircase scatter kernel launch");
+  }
+  return CC_OK;
+}
+
+int launch_staircase_extract(const cc_staircase *sc, const uint8_t *d_cw, uint8_t *d_msg, size_t B, hipStream_t stream) {
+  if (B == 0) return CC_OK;
+  const StaircaseShape s = staircase_shape(sc);
+  const unsigned long long rows = static_cast<unsigned long long>(B) * s.L * s.m;
+  hipLaunchKernelGGL(staircase_extract_kernel, dim3(flat_grid(sc->code, rows * s.kb)), dim3(256), 0, stream, d_cw, d_msg, rows,
+                     static_cast<int>(s.m), static_cast<int>(sc->code->tab.n - sc->code->tab.l), static_cast<int>(s.kb));
+  const hipError_t err = hipGetLastError();
+  return err != hipSuccess ? hip_fail(err, "staircase extract kernel launch") : CC_OK;
+}
+
+// streams [first_stream, first_stream + streams) of the channel as hard decisions, in the chunks of the product routes
+// (product_chunk_blocks): random messages, the encoder, launch_awgn_hard at N = L m m values per stream
+int staircase_awgn(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64_t first_stream, size_t streams,
+                   int random_codewords, uint8_t *d_z, uint8_t *d_sent, hipStream_t stream) {
+  if (streams == 0) return CC_OK;
+  const cc_code *code = sc->code;
+  const StaircaseShape s = staircase_shape(sc);
+  const float sigma = static_cast<float>(cc_staircase_sigma(sc, ebno_db));
+  const int N = static_cast<int>(s.N);
+  if (!random_codewords) {
+    if (d_sent) CC_HIP_TRY(hipMemsetAsync(d_sent, 0, streams * s.N, stream));
+    return launch_awgn_hard(code, N, sigma, seed, first_stream, streams, d_z, nullptr, stream);
+  }
+  const size_t chunk = product_chunk_blocks(s.N, streams);
+  Scratch scratch(code, stream);
+  uint8_t *msg = nullptr, *words = nullptr;
+  CC_HIP_TRY(scratch.get(&msg, chunk * s.K));
+  if (!d_sent) CC_HIP_TRY(scratch.get(&words, chunk * s.N));
+  for (size_t done = 0; done < streams; done += chunk) {
+    const size_t m = streams - done < chunk ? streams - done : chunk;
+    uint8_t *sent = d_sent ? d_sent + done * s.N : words;
+    if (int rc = launch_random_bits(code, static_cast<int>(s.K), seed, first_stream + done, m, msg, stream)) return rc;
+    if (int rc = launch_staircase_encode(sc, msg, sent, m, stream)) return rc;
+    if (int rc = launch_awgn_hard(code, N, sigma, seed, first_stream + done, m, d_z + done * s.N, sent, stream)) return rc;
+  }
+  return CC_OK;
+}
+
+}  // namespace ccamd

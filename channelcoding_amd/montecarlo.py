@@ -221,6 +221,17 @@ class ProductHardBackend(DeviceBackend):
         self.desc = pc._pc_hard(halves)
 
 
+class StaircaseBackend(DeviceBackend):
+    """Counts one shard of streams of one Eb/N0 point through cc_mc_run_staircase_dev: a staircase_code under its
+    sliding-window decoder on the hard decisions of the channel; bit errors are those of the counted blocks."""
+
+    symbol = "cc_mc_run_staircase_dev"
+
+    def __init__(self, sc, random_codewords=False):
+        super().__init__(sc, random_codewords)
+        self.desc = sc._sc()
+
+
 class _ShardedSimulation:
     """What the AWGN, the discrete-channel and the burst-channel ladders share: the shard of this rank, the one all-reduce per point,
     rank 0's log file (its success agreed with every rank before the first collective) and the adaptive ladder."""
@@ -413,6 +424,29 @@ class product_hard_simulation(_EbnoLadder):
     def __call__(self):
         name = "%s-hard-h%d.log" % (self.code.to_string(), self.halves)
         return self._ladder(name, "ebno", lambda ebno: ebno, " %12s" % "mean_last", lambda res: " %12.6f" % res["mean_last"])
+
+
+class staircase_simulation(_EbnoLadder):
+    """The Eb/N0 ladder of a staircase code (codes.staircase_code) under its sliding-window decoder
+    (cc_mc_run_staircase_dev).  Frames are streams: sharded by stream, wer is the rate of streams that are wrong in a
+    counted block or did not converge, and ber is taken over the counted blocks 1 .. L_c alone (L_c = blocks - window + 1,
+    or blocks for a stream shorter than the window) -- the figure that does not depend on the stream length.  The log is
+    <sc.to_string()>.log."""
+
+    def __init__(self, sc, step=0.5, seed=0, random_codewords=False, backend=None, log_dir=None, max_samples=None,
+                 start=None, stop=None, samples_per_point=None):
+        self.counted_blocks = sc.blocks - sc.window + 1 if sc.blocks >= sc.window else sc.blocks
+        if backend is None:
+            backend = StaircaseBackend(sc, random_codewords)
+        super().__init__(sc, backend, step, seed, log_dir, max_samples, start, stop, samples_per_point)
+
+    def run_point(self, ebno_db, frames, point_index=0):
+        res = super().run_point(ebno_db, frames, point_index)
+        res["ber"] = res["bit_errors"] / max(1, res["frames"] * self.counted_blocks * self.code.m * self.code.m)
+        return res
+
+    def __call__(self):
+        return self._ladder(self.code.to_string() + ".log", "ebno", lambda ebno: ebno)
 
 
 # ---- discrete memoryless channels (cc_mc_run_discrete_dev): the BSC and BEC the reference's README leaves as a TODO --

@@ -580,6 +580,89 @@ int cc_product_decode_hard_dev(const cc_product *pc, const uint8_t *d_in, uint8_
 int cc_mc_run_product_hard_dev(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
                                int random_codewords, uint64_t *d_counters, void *stream);
 
+/* ---- staircase codes (B. Smith et al., J. Lightwave Technol. 30 (1), 2012) of one binary BCH component code, decoded
+ *      through a sliding window with the line rule of cc_product_decode_hard.  The reference has no such code.
+ *      `code` is a handle cc_correct_chase_batch accepts at p = 0; e = 1 for the extended flavour (else 0); n + e must be
+ *      even, m = (n + e) / 2 is the block side, r = (n - l) + e the parity bits of a line, r < m.  A stream is `blocks`
+ *      = L blocks B_1 .. B_L of m x m bits, bytes 0 / 1, [L][m][m]; B_0 is the all-zero block, known to both ends and
+ *      neither stored nor sent.  Step i (1 <= i <= L) has m lines; line j of step i is a word of n + e = 2m bits of the
+ *      (extended, shortened) component code in the handle's own numbering (coefficient p of the word, parity low):
+ *        position p, 0 <= p < m - e        B_i[j][p]
+ *        position m - e + a, 0 <= a < m    B_(i-1)[a][j]
+ *        position n (e = 1 only)           B_i[j][m - 1], the overall parity bit as in the extended Chase calls
+ *      Columns 0 .. n - l - 1 of a block (and m - 1 when extended) carry parity, columns n - l .. m - 1 - e the message:
+ *      k_b = m - r bits per row, a message stream is [L][m][k_b].  The rate is R = 1 - r / m.
+ *        encode    for i = 1 .. L and every j the message of cc_encode_batch (division coding: message in positions
+ *                  n - l .. n - 1) is the k_b message bits of row j of block i followed by column j of B_(i-1); positions
+ *                  0 .. m - e - 1 of the word become row j of B_i, and B_i[j][m - 1] the parity of the n inner bits when
+ *                  extended.  extract is the inverse on a code stream.
+ *        decode    window = W blocks, B_0 included; iters = I.  State x = (B_0 = 0, the received blocks).  Window positions
+ *                  b = 0 .. b_last = max(0, L - W + 1); at position b the window holds the blocks b .. top = min(b + W - 1,
+ *                  L) and the steps b + 1 .. top.  Position b runs the half-passes h = 0 .. 2I - 1; half-pass h takes the
+ *                  steps i of the window with (top - i) = h (mod 2), which share no bit: every line of them is decoded
+ *                  from the state at the start of the half-pass and all flips are applied together.  A half-pass without
+ *                  a step (W = 2, h odd) does nothing.
+ *        line      the rule of cc_product_decode_hard, word for word: the inner candidate is the handle's codeword within
+ *                  distance t of the n inner positions (the hard tag plays no part); plain: the line becomes it;
+ *                  extended: iff d_H + (parity differs) <= t, else the line stays.
+ *        B_0       a line of step 1 whose accepted word would set a bit of B_0 stays as it is.
+ *        outputs   after position b < b_last block b is final, after b_last every block.  out = the final blocks 1 .. L;
+ *                  nflip = d_H(out, in); status = CC_FRAME_OK iff every line of every step 1 .. L of out is a word of its
+ *                  code (step 1 against the zero block), else CC_FRAME_NOT_CONVERGED.  nflip and status (B int32 each)
+ *                  may be NULL.  out == in is allowed.
+ *      The device may stop a position at a fixed point (two successive half-passes without a change) and skips clean
+ *      lines; no output shows either.
+ *      Refused before a device is asked for, in this order (the calls without in / out or without window / iters skip
+ *      what they do not read):
+ *        1. NULL sc, code, in or out (in / out unless B = 0) -> CC_ERR_INVALID_ARGUMENT
+ *        2. blocks == 0, window < 2 or > CC_STAIRCASE_MAX_WINDOW, iters == 0, or L m m >= 2^32 -> CC_ERR_INVALID_ARGUMENT
+ *        3. what cc_correct_chase_batch refuses at p = 0, in its order and with its texts
+ *        4. n + e odd, or r >= m -> CC_ERR_INVALID_ARGUMENT with cc_last_error naming which
+ *        5. out overlapping in other than out == in -> CC_ERR_INVALID_ARGUMENT
+ *        6. a CC_DEVICE_NONE handle -> CC_ERR_NO_DEVICE
+ *      B = 0 answers CC_OK after these checks.  The host forms answer CC_ERR_NOT_IN_FIELD for a byte above 1.  Buffers:
+ *      natural alignment only, nothing outside the stated extents is read into a result or written.  No RS components,
+ *      no q > 8, no soft information, no termination, no window carried between calls. ---- */
+#define CC_STAIRCASE_MAX_WINDOW 16
+typedef struct cc_staircase {
+  const cc_code *code;   /* a handle cc_correct_chase_batch accepts */
+  int extended;          /* 0: lines of n = 2m bits; else of n + 1 = 2m bits */
+  uint32_t blocks;       /* L >= 1 */
+  uint32_t window;       /* W = 2 .. CC_STAIRCASE_MAX_WINDOW blocks, B_0 included (decode only) */
+  uint32_t iters;        /* I >= 1: 2 I half-passes per window position (decode only) */
+} cc_staircase;
+int cc_staircase_encode_batch(const cc_staircase *sc, const uint8_t *msg /* B*L*m*k_b */, uint8_t *cw /* B*L*m*m */, size_t B);
+int cc_staircase_encode_batch_dev(const cc_staircase *sc, const uint8_t *d_msg, uint8_t *d_cw, size_t B, void *stream);
+int cc_staircase_extract_batch(const cc_staircase *sc, const uint8_t *cw /* B*L*m*m */, uint8_t *msg /* B*L*m*k_b */, size_t B);
+int cc_staircase_extract_batch_dev(const cc_staircase *sc, const uint8_t *d_cw, uint8_t *d_msg, size_t B, void *stream);
+int cc_staircase_decode(const cc_staircase *sc, const uint8_t *in /* B*L*m*m */, uint8_t *out /* B*L*m*m */,
+                        int32_t *nflip /* B or NULL */, int32_t *status /* B or NULL */, size_t B);
+int cc_staircase_decode_dev(const cc_staircase *sc, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip, int32_t *d_status,
+                            size_t B, void *stream);
+/* 1 / sqrt(2 R 10^(ebno/10)) with R = 1 - r / m (the zero block is not counted); 0 for an sc it cannot read */
+double cc_staircase_sigma(const cc_staircase *sc, double ebno_db);
+/* LDS bytes of one workgroup of the decoder for sc (tables, Berlekamp-Massey columns, the ring of `window` blocks and the
+ * line states); 0 for an sc it cannot read.  At most 160 KiB for everything the interface admits. */
+size_t cc_staircase_lds_bytes(const cc_staircase *sc);
+/* The channel of streams [first_stream, first_stream + streams): the hard decisions z = (y < 0), bytes 0 / 1, where value
+ * v of global stream g is what cc_awgn_product_dev draws for value v of block g, at cc_staircase_sigma.  random_codewords:
+ * the L m k_b message bits of stream g are those of frame g of a code with l = L m k_b, sent through
+ * cc_staircase_encode_batch_dev; otherwise the all-zero stream.  d_sent (streams*L*m*m bytes) may be NULL. */
+int cc_awgn_staircase_dev(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64_t first_stream, size_t streams,
+                          int random_codewords, uint8_t *d_z, uint8_t *d_sent /* or NULL */, void *stream);
+/* Monte-Carlo of the staircase decoder: by definition the counters equal what cc_awgn_staircase_dev, cc_staircase_decode_dev
+ * and a comparison with the streams sent would count over the *counted blocks* 1 .. L_c, L_c = L - W + 1 if L >= W, else L:
+ * the blocks that were decoded with a full window ahead of them (the last W - 1 blocks of an unterminated stream are
+ * protected less by construction and would dominate every curve).  CC_MC_FRAMES counts streams, CC_MC_BIT_ERRORS wrong
+ * bits over the counted blocks, CC_MC_CHANNEL_BIT_ERRORS the channel's flips over the counted blocks, CC_MC_FAILURES
+ * streams whose status is not CC_FRAME_OK, CC_MC_WORD_ERRORS streams wrong in a counted block or failed,
+ * CC_MC_UNDETECTED streams wrong in a counted block with status CC_FRAME_OK; CC_MC_ITER_SUM and the histogram are not
+ * touched.  The counters depend only on (seed, ebno, sc, the set of global streams).  NULL sc, code or counters first, then
+ * the refusals of cc_staircase_decode_dev.  Chunking and workspace follow cc_mc_run_product_dev: the handle's pool, one
+ * stream at a time. */
+int cc_mc_run_staircase_dev(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64_t first_stream, size_t streams,
+                            int random_codewords, uint64_t *d_counters, void *stream);
+
 /* ---- batched Monte-Carlo over discrete memoryless channels: the BSC and the BEC the reference's README leaves as a
  *      TODO, both at once, and for RS codes the q-ary symmetric and the symbol erasure channel.  A symbol is erased
  *      with probability p_erasure, in error with probability p_error, intact otherwise (both finite, >= 0, sum <= 1).

@@ -773,6 +773,92 @@ private:
   size_t w1_, w2_, k1_, k2_;
 };
 
+// ---- staircase codes (new; cc_staircase_*): streams of `blocks` blocks of m x m bits, m = (n + e) / 2, whose lines --
+// column j of block i - 1 followed by row j of block i -- are words of Code (extended = true: of its extended code),
+// decoded through a sliding window of `window` blocks with `iters` iterations per window position.  The Code object must
+// outlive the staircase_code. ----
+template <typename Code> class staircase_code {
+public:
+  staircase_code(const Code &code, uint32_t blocks, uint32_t window, uint32_t iters, bool extended = false)
+      : code_(code.c_handle()), extended_(extended), blocks_(blocks), window_(window), iters_(iters),
+        m_((Code::n + (extended ? 1 : 0)) / 2),
+        kb_(m_ - ((Code::n - code.information_symbols()) + (extended ? 1 : 0))) {
+    if ((Code::n + (extended ? 1 : 0)) % 2 || (Code::n - code.information_symbols()) + (extended ? 1 : 0) >= m_)
+      throw std::runtime_error("staircase_code: n + e must be even and leave a message bit in a row of (n + e) / 2");
+    if (blocks == 0 || window < 2 || window > CC_STAIRCASE_MAX_WINDOW || iters == 0)
+      throw std::runtime_error("staircase_code: blocks >= 1, window = 2 .. 16, iters >= 1");
+  }
+
+  size_t block_side() const { return m_; }
+  size_t values() const { return blocks_ * m_ * m_; }                // per stream
+  size_t information_symbols() const { return blocks_ * m_ * kb_; }  // per stream
+  double rate() const { return static_cast<double>(kb_) / static_cast<double>(m_); }
+  double sigma(double ebno_db) const {
+    const cc_staircase sc = descriptor();
+    return cc_staircase_sigma(&sc, ebno_db);
+  }
+
+  // blocks x m x k_b message bits -> the code stream, blocks x m x m
+  std::vector<uint8_t> encode(const std::vector<uint8_t> &msg) const {
+    if (msg.size() != information_symbols()) throw std::runtime_error("Source code word has wrong length");
+    return encode_batch(msg.data(), 1);
+  }
+  std::vector<uint8_t> encode_batch(const uint8_t *msg, size_t B) const {
+    std::vector<uint8_t> cw(B * values());
+    const cc_staircase sc = descriptor();
+    const int rc = cc_staircase_encode_batch(&sc, msg, cw.data(), B);
+    if (rc == CC_ERR_NOT_IN_FIELD) throw std::runtime_error("Value is not an element of the field.");
+    detail::check(rc, "cc_staircase_encode_batch");
+    return cw;
+  }
+  // the message bits of a code stream
+  std::vector<uint8_t> extract(const std::vector<uint8_t> &cw) const {
+    if (cw.size() != values()) throw std::runtime_error("Length of received sequence does not match code length");
+    return extract_batch(cw.data(), 1);
+  }
+  std::vector<uint8_t> extract_batch(const uint8_t *cw, size_t B) const {
+    std::vector<uint8_t> msg(B * information_symbols());
+    const cc_staircase sc = descriptor();
+    const int rc = cc_staircase_extract_batch(&sc, cw, msg.data(), B);
+    if (rc == CC_ERR_NOT_IN_FIELD) throw std::runtime_error("Value is not an element of the field.");
+    detail::check(rc, "cc_staircase_extract_batch");
+    return msg;
+  }
+
+  // The sliding-window decoder on hard decisions (cc_staircase_decode): B streams of bits (bytes 0 / 1).  words
+  // (B * values()), and per stream nflip (bits changed) and status (CC_FRAME_OK: every line of every step is a word).
+  struct hard_result {
+    std::vector<uint8_t> words;
+    std::vector<int32_t> nflip, status;
+  };
+  hard_result correct_hard(const uint8_t *words, size_t B) const {
+    const cc_staircase sc = descriptor();
+    hard_result r;
+    r.words.resize(B * values());
+    r.nflip.resize(B);
+    r.status.resize(B);
+    const int rc = cc_staircase_decode(&sc, words, r.words.data(), r.nflip.data(), r.status.data(), B);
+    if (rc == CC_ERR_NOT_IN_FIELD) throw std::runtime_error("Value is not an element of the field.");
+    detail::check(rc, "cc_staircase_decode");
+    return r;
+  }
+
+private:
+  cc_staircase descriptor() const {
+    cc_staircase sc;
+    sc.code = code_;
+    sc.extended = extended_ ? 1 : 0;
+    sc.blocks = blocks_;
+    sc.window = window_;
+    sc.iters = iters_;
+    return sc;
+  }
+  const cc_code *code_;
+  bool extended_;
+  uint32_t blocks_, window_, iters_;
+  size_t m_, kb_;
+};
+
 }  // namespace cyclic
 
 // ---- soft_decision.h:220-295: the free functions min_sum<R, U>(H, y, tag) on any parity-check matrix ----
