@@ -276,15 +276,20 @@ constexpr int diag_variant_part(int variant, int parts) {
 
 // How the general diagonal kernel reduces the rows of an iteration (minsum_diag_impl.hpp, BODY), per geometry and variant:
 // the four-row bodies run where they are measured faster than the butterfly and compile without spilling
-// (profiles/r18_experiments.md, E46).  Of the two orders the unpipelined one measured faster; -DCC_DIAG_FOUR_ROW_BODY=2
-// builds the pipelined one instead, to measure it again.
-enum DiagRowBody { DIAG_ROWS_BUTTERFLY = 0, DIAG_ROWS_FOUR = 1, DIAG_ROWS_FOUR_PIPELINED = 2 };
-#ifndef CC_DIAG_FOUR_ROW_BODY
-#define CC_DIAG_FOUR_ROW_BODY 1
-#endif
+// (profiles/r18_experiments.md, E46).  Three orders of the four-row body: group by group (fronts, reduction, backs),
+// pipelined (the fronts of group g + 1 as a block ahead of the backs of group g), and zipped (the backs of group g and
+// the fronts of group g + 1 row by row, so that every LDS request has a whole row of the other kind between itself and
+// its counted wait; profiles/r24_experiments.md, E47).  -DCC_DIAG_FOUR_ROW_BODY=1 / 2 / 3 builds one of them for all four
+// plain variants, to measure it again; without the switch each variant takes the order that passed the bar.
+enum DiagRowBody { DIAG_ROWS_BUTTERFLY = 0, DIAG_ROWS_FOUR = 1, DIAG_ROWS_FOUR_PIPELINED = 2, DIAG_ROWS_FOUR_ZIPPED = 3 };
 constexpr int diag_row_body(int K, int D, int LPF, int variant) {
   const bool plain = variant == CC_ALG_MS || variant == CC_ALG_NMS || variant == CC_ALG_OMS || variant == CC_ALG_2DNMS;
-  return (K == 24 && D == 7 && LPF == 16 && plain) ? CC_DIAG_FOUR_ROW_BODY : DIAG_ROWS_BUTTERFLY;
+  if (!(K == 24 && D == 7 && LPF == 16 && plain)) return DIAG_ROWS_BUTTERFLY;
+#ifdef CC_DIAG_FOUR_ROW_BODY
+  return CC_DIAG_FOUR_ROW_BODY;
+#else
+  return DIAG_ROWS_FOUR_ZIPPED;
+#endif
 }
 
 // wide.hip

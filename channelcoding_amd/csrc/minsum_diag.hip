@@ -239,7 +239,10 @@ std::string minsum_diag_name(const cc_code *code) {
   // (the message-free kernel of one-iteration calls always reduces row by row)
   const int body = diag_row_body(static_cast<int>(g->k), g->D, g->LPF, code->desc.algorithm);
   return "minsum_diag_kernel<K=" + std::to_string(g->k) + ",D=" + std::to_string(g->D) + ",LPF=" + std::to_string(g->LPF) +
-         (body == DIAG_ROWS_FOUR_PIPELINED ? ",four-row-pipelined>" : body == DIAG_ROWS_FOUR ? ",four-row>" : ",row-pipelined>");
+         (body == DIAG_ROWS_FOUR_ZIPPED      ? ",four-row-zipped>"
+          : body == DIAG_ROWS_FOUR_PIPELINED ? ",four-row-pipelined>"
+          : body == DIAG_ROWS_FOUR           ? ",four-row>"
+                                             : ",row-pipelined>");
 }
 
 size_t minsum_diag_lds_bytes(const DiagGeometry &g) {

@@ -293,7 +293,8 @@ __device__ __forceinline__ float horizontal(float m, float alpha_f, double beta_
 // and continues the head's running column sum in registers: per link and row one {cs, y} read, one cs' read and
 // one cs' write less, in the reference's summation order (soft_decision.h:88-95) all the same.
 // BODY: how the rows of an iteration are reduced (DiagRowBody in cc_internal.hpp): one row per butterfly all-reduce, or
-// four rows per transposed reduction, with or without the next group's fronts ahead of this group's backs.
+// four rows per transposed reduction -- group by group, with the next group's fronts ahead of this group's backs, or
+// with the two zipped row by row.
 template <int K, int D, int VARIANT, int RB, int LPF, int CPL, int OCC, bool PARTIAL, typename PG = PairGaps<>,
           bool SINGLE = false, bool CHAIN = false, int BODY = DIAG_ROWS_BUTTERFLY>
 __global__ void __launch_bounds__(256, OCC)
@@ -628,7 +629,9 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
     float Tloc[D];  // SINGLE: q, then r, of the row in hand (nothing is kept across rows)
     // ---- a row in three parts, so that the reduction between them can serve one row (butterfly) or four (transposed) ----
     // front: operands, q = (cs - r) + y, the lane's two smallest magnitudes and its sign parity
-    auto row_front = [&](auto IR, uint32_t &o1, uint32_t &o2, uint32_t &os) {
+    // mid(): what the zipped four-row body runs between the request of the next row's operands and this row's pair
+    // tracking (a back of the group before); nothing everywhere else
+    auto row_front = [&](auto IR, uint32_t &o1, uint32_t &o2, uint32_t &os, auto &&mid) {
       constexpr int i = decltype(IR)::value;
       if constexpr (!PREFETCH) fetch(IR);
       // q, then r, of this row's edges: the message registers, or temporaries when nothing is kept
@@ -717,6 +720,7 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
           if constexpr (i + 1 < K) fetch(std::integral_constant<int, i + 1>{});
           asm volatile("" ::: "memory");
         }
+        mid();
         static_for<D>([&](auto DD) {
           constexpr int d = DD;
           const float q = qv[d];
@@ -877,10 +881,13 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
       // the butterfly body.
       constexpr int NG = K / 4;
       uint32_t ZA[NG], ZB[NG], ZC[READY ? 1 : NG];  // per bank: READY {Y, m2}, otherwise {m1, m2, parity}
-      auto fronts = [&](auto IG) {
+      // (mid(J): see row_front)
+      auto fronts = [&](auto IG, auto &&mid) {
         constexpr int g = decltype(IG)::value;
         uint32_t a1[4], a2[4], sg[4];
-        static_for<4>([&](auto J) { row_front(std::integral_constant<int, 4 * g + J>{}, a1[J], a2[J], sg[J]); });
+        static_for<4>([&](auto J) {
+          row_front(std::integral_constant<int, 4 * g + J>{}, a1[J], a2[J], sg[J], [&] { mid(J); });
+        });
         uint32_t z1, z2, zs;
         transposed_reduce4(a1, a2, sg, z1, z2, zs);
         if constexpr (READY) {
@@ -903,22 +910,58 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
           row_back(std::integral_constant<int, 4 * g + J>{}, b0, b1, b2, cn);
         });
       };
-      if constexpr (BODY == DIAG_ROWS_FOUR_PIPELINED) {
-        fronts(std::integral_constant<int, 0>{});
+      auto alone = [](auto) {};
+      if constexpr (BODY == DIAG_ROWS_FOUR_ZIPPED) {
+        // Backs of group g and fronts of group g + 1 row by row.  At two waves per SIMD an LDS round trip takes about as
+        // long as a dozen instructions of the wavefront issue, and in the orders above a row's requests sit 4 to 13
+        // instructions in front of a wait for ALL of them (E47).  Here step J = 0..3 of a group runs, with b = row J of
+        // group g and f = row J of group g + 1:
+        //   q(f)             behind a wait that leaves the stores of the back before and the cs' of b in flight
+        //   request {cs, y}  of the row after f
+        //   r(b)             from bank J's broadcast
+        //   sums, stores(b)  behind a wait that leaves the {cs, y} just requested in flight
+        //   request cs'      of the row after b -- behind b's stores in program order: it reads what other lanes stored
+        //   pairs, parity(f)
+        // so every request has a row of the other kind between itself and its wait (~35 instructions), and at most
+        // 5 stores + 5 cs' + 5 {cs, y} = 15 LDS instructions are in flight, what the 4-bit lgkmcnt can count.  The
+        // compiler works the counted waits out by itself from the program order, which the scheduling barriers pin.
+        // Fronts of group 0 and backs of the last group run alone; the stop scan rewrites the cs halves, and no request
+        // crosses it (row K - 1 has no successor to request).
+        float cn[D];
+        auto back_step = [&](auto IG, auto J) {
+          constexpr int i = 4 * decltype(IG)::value + decltype(J)::value;
+          __builtin_amdgcn_sched_barrier(0);
+          const uint32_t b0 = bank_bcast<J>(ZA[IG]), b1 = bank_bcast<J>(ZB[IG]);
+          uint32_t b2 = 0;
+          if constexpr (!READY) b2 = bank_bcast<J>(ZC[IG]);
+          row_back(std::integral_constant<int, i>{}, b0, b1, b2, cn);
+          if constexpr (i + 1 < K) row_cn(std::integral_constant<int, i + 1>{}, cn);
+          asm volatile("" ::: "memory");
+          __builtin_amdgcn_sched_barrier(0);
+        };
+        fronts(std::integral_constant<int, 0>{}, alone);
+        row_cn(std::integral_constant<int, 0>{}, cn);
+        asm volatile("" ::: "memory");
+        static_for<NG - 1>([&](auto IG) {
+          fronts(std::integral_constant<int, IG + 1>{}, [&](auto J) { back_step(IG, J); });
+        });
+        static_for<4>([&](auto J) { back_step(std::integral_constant<int, NG - 1>{}, J); });
+      } else if constexpr (BODY == DIAG_ROWS_FOUR_PIPELINED) {
+        fronts(std::integral_constant<int, 0>{}, alone);
         static_for<NG>([&](auto IG) {
-          if constexpr (IG + 1 < NG) fronts(std::integral_constant<int, IG + 1>{});
+          if constexpr (IG + 1 < NG) fronts(std::integral_constant<int, IG + 1>{}, alone);
           backs(IG);
         });
       } else {
         static_for<NG>([&](auto IG) {
-          fronts(IG);
+          fronts(IG, alone);
           backs(IG);
         });
       }
     } else {
       static_for<K>([&](auto IR) {
         uint32_t m1[1], m2[1], sg[1];
-        row_front(IR, m1[0], m2[0], sg[0]);
+        row_front(IR, m1[0], m2[0], sg[0], [] {});
         float cn[D];
         row_cn(IR, cn);
 #ifndef CC_EXP_NO_REDUCE

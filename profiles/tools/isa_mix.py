@@ -2,7 +2,7 @@
 """Instruction mix of a kernel's hottest loop from hipcc -S output.
 
     hipcc ... --cuda-device-only -S file.hip -o file.s
-    python profiles/tools/isa_mix.py file.s <mangled-name-substring> [--all]
+    python profiles/tools/isa_mix.py file.s <mangled-name-substring> [--all] [--lds]
 
 Finds the function whose label contains the substring, takes its longest basic-block run that ends in a backward
 branch (the min-sum iteration body is one straight-line block of 24 unrolled rows) -- or the whole function with
@@ -10,6 +10,7 @@ branch (the min-sum iteration body is one straight-line block of 24 unrolled row
   valu_full  : v_add/sub/mul/fma/fmac_f32 (any encoding without DPP/SDWA), v_and/or/xor_b32, v_add/sub_u32, v_mov_b32
   valu_half  : every other VALU instruction (min/max/med3, shifts, bfi, DPP, SDWA, compares, conversions ...)
   lds, salu, vmem, waitcnt, nop
+With --lds it also prints the block's LDS request-to-wait strip and its summary (lds_strip below).
 """
 import json
 import re
@@ -54,6 +55,86 @@ def blocks(lines):
     yield cur_label, cur
 
 
+def lgkmcnt_of(text):
+    """The lgkmcnt of an s_waitcnt line, or None when it does not wait on that counter."""
+    m = re.search(r"lgkmcnt\((\d+)\)", text)
+    return int(m.group(1)) if m else None
+
+
+def lds_strip(ins):
+    """LDS request-to-wait distances of a straight-line block, ins = [(opcode, line), ...].
+
+    Returns (strip, summary).  The strip is a list of tokens in program order: a run of LDS instructions as
+    'ds_read_b64 x5' (runs of different opcodes joined by ' + '), an s_waitcnt by its operands ('lgkmcnt(0)'), 's_nop',
+    and the NUMBER of other instructions between two of those as a decimal string.  LDS operations of a wavefront
+    return in order, so s_waitcnt lgkmcnt(N) covers every LDS instruction except the N issued last before it; the
+    distance of a read group (a run of LDS instructions with a ds_read in it) is the number of other instructions --
+    neither LDS nor s_waitcnt nor s_nop -- between its last instruction and the first wait that covers it.  Groups that
+    no wait of the block covers (their wait sits behind the backward branch) are left out of the summary."""
+    strip, other = [], 0
+    groups = []   # [index of the group's last LDS instruction, it holds a read, other instructions before it]
+    waits = []    # (LDS instructions before it, other instructions before it, lgkmcnt)
+    n_lds = n_other = 0
+    run = []      # opcodes of the LDS run in hand
+
+    def close_run():
+        if run:
+            parts, k = [], 0
+            while k < len(run):
+                j = k
+                while j < len(run) and run[j] == run[k]:
+                    j += 1
+                parts.append("%s x%d" % (run[k], j - k))
+                k = j
+            strip.append(" + ".join(parts))
+            groups.append((n_lds, any(op.startswith("ds_read") for op in run), n_other))
+            del run[:]
+
+    def close_other():
+        nonlocal other
+        if other:
+            strip.append(str(other))
+            other = 0
+
+    for op, text in ins:
+        if op.startswith("ds_"):
+            close_other()
+            run.append(op)
+            n_lds += 1
+            continue
+        close_run()
+        if op.startswith("s_waitcnt"):
+            close_other()
+            strip.append(" ".join(text.split()[1:]))
+            c = lgkmcnt_of(text)
+            if c is not None:
+                waits.append((n_lds, n_other, c))
+        elif op.startswith("s_nop"):
+            close_other()
+            strip.append("s_nop")
+        else:
+            other += 1
+            n_other += 1
+    close_run()
+    close_other()
+    dist = []
+    for last, has_read, at in groups:
+        if not has_read:
+            continue
+        cover = next((w for w in waits if w[0] >= last and w[0] - last >= w[2]), None)
+        if cover is not None:
+            dist.append(cover[1] - at)
+    dist.sort()
+    summary = {
+        "waits_on_lgkmcnt": len(waits),
+        "waits_lgkmcnt_0": sum(1 for w in waits if w[2] == 0),
+        "read_groups_covered": len(dist),
+        "distance_min": dist[0] if dist else None,
+        "distance_median": (dist[(len(dist) - 1) // 2] + dist[len(dist) // 2]) / 2 if dist else None,
+    }
+    return strip, summary
+
+
 def main():
     path, key = sys.argv[1], sys.argv[2]
     whole = "--all" in sys.argv
@@ -76,6 +157,10 @@ def main():
     mix["total"] = len(ins)
     mix["dpp"] = sum(1 for op, t in ins if "_dpp" in op or "quad_perm" in t or " row_" in t)
     print(json.dumps(mix, indent=1, sort_keys=True))
+    if "--lds" in sys.argv:
+        strip, summary = lds_strip(ins)
+        print(" | ".join(strip))
+        print(json.dumps(summary, indent=1, sort_keys=True))
 
 
 if __name__ == "__main__":
