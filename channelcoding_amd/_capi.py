@@ -75,6 +75,7 @@ class Staircase(C.Structure):
 
 
 STAIRCASE_MAX_WINDOW = 16
+PRODUCT_SR_MAX_LEVELS = 15
 
 
 class CcError(RuntimeError):
@@ -213,6 +214,10 @@ _SIGNATURES = {
     "cc_product_decode_hard_dev": (C.c_int, [C.POINTER(Product), _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "cc_mc_run_product_hard_dev": (C.c_int, [C.POINTER(Product), C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int,
                                              _VP, _VP]),
+    "cc_product_decode_sr": (C.c_int, [C.POINTER(Product), _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t]),
+    "cc_product_decode_sr_dev": (C.c_int, [C.POINTER(Product), _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "cc_mc_run_product_sr_dev": (C.c_int, [C.POINTER(Product), _VP, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int,
+                                           _VP, _VP]),
     "cc_diag_table": (C.c_int, [_VP, _VP, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                 C.POINTER(C.c_uint32)]),
     "cc_kernel_info": (C.c_int, [_VP, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),

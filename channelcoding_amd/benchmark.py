@@ -34,7 +34,9 @@ column code (default: the row code), --extended takes the two extended codes, --
 and --alpha a,b,... and --beta a,b,... give the schedule, one value each per half-iteration.  There is no default
 schedule.  The log is "<rows>x<cols>[-ext]-chaseP-hH.log".  With --halves H in place of --alpha / --beta the ladder runs
 H half-iterations of hard-decision row / column decoding (montecarlo.product_hard_simulation) and the log is
-"<rows>x<cols>[-ext]-hard-hH.log", with the mean of the half-iterations a block took next to wer.
+"<rows>x<cols>[-ext]-hard-hH.log", with the mean of the half-iterations a block took next to wer.  With --weights a,b,...
+in place of all three the ladder runs iBDD with scaled reliability (montecarlo.product_sr_simulation), one weight per
+half-iteration (inf is a weight), and the log is "<rows>x<cols>[-ext]-srH.log".
 
 --simulation staircase --blocks L --window W --iters I [--extended] is the Eb/N0 ladder of a staircase code under its
 sliding-window hard-decision decoder (montecarlo.staircase_simulation): --k and --dmin (one value each, k = 3 .. 8) name
@@ -49,7 +51,7 @@ import time
 
 from . import codes as cc
 from .montecarlo import (awgn_simulation, bitflip_simulation, burst_simulation, discrete_simulation, product_hard_simulation,
-                         product_simulation, staircase_simulation)
+                         product_simulation, product_sr_simulation, staircase_simulation)
 
 POWERS = (5, 6, 7)
 DISTANCES = (3, 5, 7, 9)
@@ -126,6 +128,8 @@ def usage_text():
               "--beta <a,b,...>             product: the value of a position without a competitor, per half-iteration.",
               "--halves <num>               product: hard-decision row / column decoding with that many half-iterations,",
               "                             in place of --alpha and --beta.",
+              "--weights <a,b,...>          product: iBDD with scaled reliability, one weight per half-iteration (inf is",
+              "                             one), in place of --alpha, --beta and --halves.",
               "--blocks <num>               staircase: blocks per stream. There is no default.",
               "--window <num>               staircase: the decoder's window in blocks, 2 .. 16. There is no default.",
               "--iters <num>                staircase: iterations per window position. There is no default.",
@@ -222,6 +226,30 @@ def product_hard_arguments(args):
     return rows, cols, args.halves
 
 
+def product_sr_arguments(args):
+    """(rows (k, dmin), cols (k, dmin), weights) of --simulation product --weights a,b,..., or a message saying what is
+    wrong"""
+    if args.alpha is not None or args.beta is not None or args.halves is not None:
+        return "--weights runs iBDD with scaled reliability: it does not combine with --alpha, --beta or --halves"
+    try:
+        if not args.k or len(args.k) != 1 or not args.dmin or len(args.dmin) != 1:
+            return "--simulation product takes one --k and one --dmin"
+        rows = (int(args.k[0]), int(args.dmin[0]))
+    except ValueError:
+        return "--k and --dmin take numbers"
+    try:
+        weights = [float(v) for v in args.weights.split(",")]
+    except ValueError:
+        return "--weights takes numbers, one per half-iteration"
+    if any(w != w or w < 0 for w in weights):
+        return "--weights takes weights >= 0 (inf is one)"
+    cols = (rows[0] if args.cols_k is None else args.cols_k, rows[1] if args.cols_dmin is None else args.cols_dmin)
+    for k, d in (rows, cols):
+        if not 3 <= k <= 8 or d < 3 or d % 2 == 0:
+            return "--simulation product takes k = 3 .. 8 and an odd dmin >= 3"
+    return rows, cols, weights
+
+
 def build_product(rows, cols, extended, device=None):
     kw = {} if device is None else {"device": device}
     make = lambda k, d: cc.primitive_bch(k, cc.dmin(d), cc.berlekamp_massey_tag(), **kw)
@@ -229,8 +257,9 @@ def build_product(rows, cols, extended, device=None):
 
 
 def product_main(args):
-    hard = getattr(args, "halves", None) is not None
-    parsed = product_hard_arguments(args) if hard else product_arguments(args)
+    sr = getattr(args, "weights", None) is not None
+    hard = not sr and getattr(args, "halves", None) is not None
+    parsed = product_sr_arguments(args) if sr else product_hard_arguments(args) if hard else product_arguments(args)
     if isinstance(parsed, str):
         print(parsed, file=sys.stderr)
         print(usage_text())
@@ -239,7 +268,9 @@ def product_main(args):
     dist = join_ranks()
     pc = build_product(parsed[0], parsed[1], args.extended)
     t0 = time.perf_counter()
-    if hard:
+    if sr:
+        res = product_sr_simulation(pc, parsed[2], seed=seed, log_dir=args.log_dir, max_samples=args.max_samples)()
+    elif hard:
         res = product_hard_simulation(pc, parsed[2], seed=seed, log_dir=args.log_dir, max_samples=args.max_samples)()
     else:
         rows, cols, p, alpha, beta = parsed
@@ -334,6 +365,7 @@ def main(argv=None):
     ap.add_argument("--alpha", default=None, help="product: a,b,... one per half-iteration")
     ap.add_argument("--beta", default=None, help="product: a,b,... one per half-iteration")
     ap.add_argument("--halves", type=int, default=None, help="product: hard-decision decoding, this many half-iterations")
+    ap.add_argument("--weights", default=None, help="product: iBDD-SR, a,b,... one weight per half-iteration")
     ap.add_argument("--blocks", type=int, default=None, help="staircase: blocks per stream")
     ap.add_argument("--window", type=int, default=None, help="staircase: window of the decoder in blocks")
     ap.add_argument("--iters", type=int, default=None, help="staircase: iterations per window position")

@@ -756,16 +756,16 @@ class cyclic:
         return r
 
     # ---- batch API (numpy host arrays or torch CUDA tensors) ----
-    def _batch_call(self, name, ins, B, outs, per_frame=(), args=(), tail=(), erasures=False):
-        """One batch call of the library, for host arrays and device tensors alike: `name`(handle, *ins[, erasure list],
-        *args, *outs, *per_frame, B, *tail), for tensors `name`_dev with the stream last.  ins: the contiguous inputs.
+    def _batch_call(self, name, ins, B, outs, per_frame=(), args=(), tail=(), erasures=False, head=()):
+        """One batch call of the library, for host arrays and device tensors alike: `name`(handle, *head, *ins[, erasure
+        list], *args, *outs, *per_frame, B, *tail), for tensors `name`_dev with the stream last.  ins: the contiguous inputs.
         outs: the call's leading outputs in its order, key -> (shape, dtype), dtype None being that of ins[0]; a buffer
         of the caller's in place of the pair is used as it is, None passes a null pointer.  per_frame: the keys of
         _PER_FRAME that follow, (B,) each.  erasures: as correct_batch takes them, False for a call without the list.
         Returns the dict of the outputs, in the order of _KEYS."""
         x = ins[0]
         side = _side(x)
-        call = [self._h] + [_ptr(a) for a in ins]
+        call = [self._h] + list(head) + [_ptr(a) for a in ins]
         if erasures is not False:
             lists = _erasure_csr(erasures, B, self.n)
             if lists[0] is not None:
@@ -1063,6 +1063,16 @@ class rs(cyclic):
         super().__init__(q, capability, algorithm, coding, mu, step, **kw)
 
 
+def _sr_weights(weights):
+    """the weights of an iBDD-SR call as C floats, one per half-iteration and at least one (inf is a weight; what the
+    library refuses -- NaN, a negative weight, too many distinct ones -- is left to it)"""
+    with np.errstate(over="ignore"):
+        w = [float(np.float32(a)) for a in weights]
+    if not w:
+        raise ValueError("one weight per half-iteration, at least one")
+    return (C.c_float * len(w))(*w)
+
+
 class _product_handle:
     """what cyclic._batch_call reads of a code, for a call whose first argument is a cc_product"""
 
@@ -1183,6 +1193,32 @@ class product_code:
     def decode_hard_batch(self, z, halves):
         """correct_hard_batch plus msg (B, k2, k1): the message bits of out"""
         res = self.correct_hard_batch(z, halves)
+        res["msg"] = self.extract_batch(res["out"])
+        return res
+
+    def correct_sr_batch(self, y, weights):
+        """cc_product_decode_sr: y (B, n2, n1) float32 channel values -> dict(out=, nflip=, last=, status=) after
+        len(weights) half-iterations of iBDD with scaled reliability, weights[h] the threshold below which |y| yields to
+        the component decoder in half-iteration h (inf: always); numpy array or device tensor."""
+        fw = _sr_weights(weights)
+        pc = self._pc_hard(len(fw))
+        pc._keep += (fw,)
+        if len(y.shape) != 3 or tuple(y.shape[1:]) != (self.n2, self.n1):
+            raise CcError(capi.ERR_LENGTH, "correct_sr_batch")
+        yy = _side(y).as_type(y, "f", np.float32)
+        if yy is None:
+            raise TypeError("product decoding takes float32 channel values")
+        B = yy.shape[0]
+        side = _side(yy)
+        res = {"out": side.alloc(yy, (B, self.n2, self.n1), np.uint8)}
+        for k in ("nflip", "last", "status"):
+            res[k] = side.alloc(yy, (B,), np.int32)
+        cyclic._batch_call(_product_handle(pc), "cc_product_decode_sr", [yy], B, res, head=[fw])
+        return res
+
+    def decode_sr_batch(self, y, weights):
+        """correct_sr_batch plus msg (B, k2, k1): the message bits of out"""
+        res = self.correct_sr_batch(y, weights)
         res["msg"] = self.extract_batch(res["out"])
         return res
 

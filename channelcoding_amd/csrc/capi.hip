@@ -1787,6 +1787,59 @@ int cc_mc_run_product_hard_dev(const cc_product *pc, double ebno_db, uint64_t se
                              static_cast<hipStream_t>(stream));
 }
 
+// the refusals of cc_product_decode_sr(_dev) in the header's order, and the schedule of the weights; the Monte-Carlo call
+// has no arrays
+static int product_sr_supported(const cc_product *pc, const float *weights, const float *y, const uint8_t *out, size_t B,
+                                bool arrays, SrSchedule *sched) {
+  if (!pc || !pc->rows || !pc->cols || !weights) return CC_ERR_INVALID_ARGUMENT;
+  if (arrays && B && (!y || !out)) return CC_ERR_INVALID_ARGUMENT;
+  if (pc->halves == 0) return CC_ERR_INVALID_ARGUMENT;
+  const int rc = product_handles(pc, 0);
+  if (rc != CC_OK && rc != CC_ERR_NO_DEVICE) return rc;
+  if (int bad = product_sr_schedule(weights, pc->halves, sched)) return bad;
+  if (arrays) {
+    const size_t N = product_shape(pc).N;
+    if (ranges_overlap(y, B * N * sizeof(float), out, B * N)) return CC_ERR_INVALID_ARGUMENT;
+  }
+  return rc;
+}
+
+int cc_product_decode_sr_dev(const cc_product *pc, const float *weights, const float *d_y, uint8_t *d_out, int32_t *d_nflip,
+                             int32_t *d_last, int32_t *d_status, size_t B, void *stream) {
+  SrSchedule sched;
+  if (int rc = product_sr_supported(pc, weights, d_y, d_out, B, true, &sched)) return rc;
+  DeviceGuard guard(pc->rows->device);
+  return launch_product_sr(pc, sched, d_y, d_out, d_nflip, d_last, d_status, B, static_cast<hipStream_t>(stream));
+}
+
+int cc_product_decode_sr(const cc_product *pc, const float *weights, const float *y, uint8_t *out, int32_t *nflip,
+                         int32_t *last, int32_t *status, size_t B) {
+  SrSchedule sched;
+  if (int rc = product_sr_supported(pc, weights, y, out, B, true, &sched)) return rc;
+  if (B == 0) return CC_OK;
+  const ProductShape s = product_shape(pc);
+  DeviceGuard guard(pc->rows->device);
+  // a block is the frame of the chunk loop
+  const StagedStream streams[] = {stage_in(0, y, s.N * sizeof(float)), stage_out(1, out, s.N), stage_out(2, nflip, sizeof(int32_t)),
+                                  stage_out(3, status, sizeof(int32_t)), stage_out(4, last, sizeof(int32_t))};
+  return staged_call(pc->rows, B, s.N * sizeof(float), 1, streams, 5, nullptr, nullptr,
+                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t st) {
+                       return launch_product_sr(pc, sched, static_cast<const float *>(d[0]), static_cast<uint8_t *>(d[1]),
+                                                static_cast<int32_t *>(d[2]), static_cast<int32_t *>(d[4]),
+                                                static_cast<int32_t *>(d[3]), m, st);
+                     });
+}
+
+int cc_mc_run_product_sr_dev(const cc_product *pc, const float *weights, double ebno_db, uint64_t seed, uint64_t first_block,
+                             size_t blocks, int random_codewords, uint64_t *d_counters, void *stream) {
+  if (!pc || !weights || !d_counters) return CC_ERR_INVALID_ARGUMENT;
+  SrSchedule sched;
+  if (int rc = product_sr_supported(pc, weights, nullptr, nullptr, blocks, false, &sched)) return rc;
+  DeviceGuard guard(pc->rows->device);
+  return mc_run_product_sr(pc, sched, ebno_db, seed, first_block, blocks, random_codewords, d_counters,
+                           static_cast<hipStream_t>(stream));
+}
+
 /* ------------------------------ staircase codes ------------------------------ */
 
 // The refusals of the staircase calls in the header's order.  decode: window and iters are read, and in / out hold

@@ -352,6 +352,23 @@ int mc_run_product_hard(const cc_product *pc, double ebno_db, uint64_t seed, uin
 // (cc_product_decode_hard_dev).  d_out may be d_in; d_nflip, d_last and d_status (one per block) may be nullptr
 int launch_product_hard(const cc_product *pc, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip, int32_t *d_last,
                         int32_t *d_status, size_t B, hipStream_t stream);
+// product_sr.hip: iBDD with scaled reliability.  The schedule of a call: the distinct weights in rising
+// order, the position of every half-iteration's weight among them, and the first half-iteration from which the levels
+// repeat with period two (the early stop's bound)
+struct SrSchedule {
+  int D = 0;
+  float u[CC_PRODUCT_SR_MAX_LEVELS] = {};
+  std::vector<uint8_t> level;
+  uint32_t stop_from = 0;
+};
+// refusal 5 of cc_product_decode_sr (a NaN or negative weight, too many distinct ones, with cc_last_error), else the schedule
+int product_sr_schedule(const float *weights, uint32_t halves, SrSchedule *s);
+// pc checked by the caller; d_nflip, d_last and d_status (one per block) may be nullptr
+int launch_product_sr(const cc_product *pc, const SrSchedule &sched, const float *d_y, uint8_t *d_out, int32_t *d_nflip,
+                      int32_t *d_last, int32_t *d_status, size_t B, hipStream_t stream);
+// product.hip: the float route around launch_product_sr, one status and one `last` per block
+int mc_run_product_sr(const cc_product *pc, const SrSchedule &sched, double ebno_db, uint64_t seed, uint64_t first_block,
+                      size_t blocks, int random_codewords, uint64_t *d_counters, hipStream_t stream);
 // staircase.hip: staircase codes of one component code; sc checked by the caller (capi.hip)
 struct StaircaseShape {
   int e;                       // 1: lines of the extended code

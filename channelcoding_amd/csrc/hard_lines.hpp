@@ -1,5 +1,6 @@
-// hard_lines.hpp -- what the iterated bounded-distance decoders share (product_hard.hip, staircase.hip):
-// a line of up to 64 NC bits held by one lane, its syndromes from the bits, and the line rule of
+// hard_lines.hpp -- what the iterated bounded-distance decoders share (product_hard.hip, product_sr.hip, staircase.hip;
+// DESIGN 4.17 - 4.19): a line of up to 64 NC bits held by one lane, gathered from a bit tile, its syndromes from the
+// bits, and the line rule of
 // cc_product_decode_hard -- from the line's state in LDS (t odd syndromes, then the parity of all its bits) to the
 // positions at which the line changes.  The rule is spelled out here only.
 #pragma once
@@ -21,6 +22,34 @@ __device__ __forceinline__ int count_bits(const unsigned long long (&m)[NC]) {
 #pragma unroll
   for (int c = 0; c < NC; ++c) cnt += __builtin_popcountll(m[c]);
   return cnt;
+}
+
+// the bits of line `line` of a bit tile X[w2][P] (bit k & 31 of X[i][k >> 5] = x(i, k)): row `line` (w1 bits, PD dwords)
+// or column `line` (w2 bits)
+template <int NC>
+__device__ __forceinline__ void gather_line(const uint32_t *X, int P, int PD, int w2, bool column, bool have, int line,
+                                            unsigned long long (&lb)[NC]) {
+#pragma unroll
+  for (int c = 0; c < NC; ++c) lb[c] = 0;
+  if (!have) return;
+  if (!column) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const uint32_t lo = 2 * c < PD ? X[line * P + 2 * c] : 0u, hi = 2 * c + 1 < PD ? X[line * P + 2 * c + 1] : 0u;
+      lb[c] = static_cast<unsigned long long>(lo) | (static_cast<unsigned long long>(hi) << 32);
+    }
+  } else {
+    const int kw = line >> 5, kb = line & 31;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int stop = w2 - 64 * c < 64 ? w2 - 64 * c : 64;
+      unsigned long long acc = 0;
+#pragma unroll 8
+      for (int b = 0; b < stop; ++b)
+        acc |= static_cast<unsigned long long>((X[(64 * c + b) * P + kw] >> kb) & 1u) << b;
+      lb[c] = acc;
+    }
+  }
 }
 
 // S_j of the positions 0 .. n-1 of a line

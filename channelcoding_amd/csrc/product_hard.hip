@@ -39,33 +39,6 @@ namespace {
 
 constexpr int kHardTables = 2 * kSoftTables;  // the tables of `rows`, then those of `cols`
 
-// the bits of line `line` of X: row `line` (w1 bits, PD dwords) or column `line` (w2 bits)
-template <int NC>
-__device__ __forceinline__ void gather_line(const uint32_t *X, int P, int PD, int w2, bool column, bool have, int line,
-                                            unsigned long long (&lb)[NC]) {
-#pragma unroll
-  for (int c = 0; c < NC; ++c) lb[c] = 0;
-  if (!have) return;
-  if (!column) {
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const uint32_t lo = 2 * c < PD ? X[line * P + 2 * c] : 0u, hi = 2 * c + 1 < PD ? X[line * P + 2 * c + 1] : 0u;
-      lb[c] = static_cast<unsigned long long>(lo) | (static_cast<unsigned long long>(hi) << 32);
-    }
-  } else {
-    const int kw = line >> 5, kb = line & 31;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int stop = w2 - 64 * c < 64 ? w2 - 64 * c : 64;
-      unsigned long long acc = 0;
-#pragma unroll 8
-      for (int b = 0; b < stop; ++b)
-        acc |= static_cast<unsigned long long>((X[(64 * c + b) * P + kw] >> kb) & 1u) << b;
-      lb[c] = acc;
-    }
-  }
-}
-
 // the LDS of one block, in dwords: X and X0 [w2][P], ctl [4], then the state of every line as bytes -- the t odd
 // syndromes S_1, S_3, .. and in slot t the parity of all its bits -- at a pitch of whole dwords, rows then columns
 struct HardBlock {

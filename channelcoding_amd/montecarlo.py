@@ -221,6 +221,20 @@ class ProductHardBackend(DeviceBackend):
         self.desc = pc._pc_hard(halves)
 
 
+class ProductSrBackend(DeviceBackend):
+    """Counts one shard of blocks of one Eb/N0 point through cc_mc_run_product_sr_dev: a product_code decoded with
+    len(weights) half-iterations of iBDD with scaled reliability (codes.product_code.correct_sr_batch)."""
+
+    symbol = "cc_mc_run_product_sr_dev"
+
+    def __init__(self, pc, weights, random_codewords=False):
+        from .codes import _sr_weights
+        super().__init__(pc, random_codewords)
+        self.weights = _sr_weights(weights)
+        self.desc = pc._pc_hard(len(self.weights))
+        self.leading = (self.weights,)
+
+
 class StaircaseBackend(DeviceBackend):
     """Counts one shard of streams of one Eb/N0 point through cc_mc_run_staircase_dev: a staircase_code under its
     sliding-window decoder on the hard decisions of the channel; bit errors are those of the counted blocks."""
@@ -423,6 +437,26 @@ class product_hard_simulation(_EbnoLadder):
 
     def __call__(self):
         name = "%s-hard-h%d.log" % (self.code.to_string(), self.halves)
+        return self._ladder(name, "ebno", lambda ebno: ebno, " %12s" % "mean_last", lambda res: " %12.6f" % res["mean_last"])
+
+
+class product_sr_simulation(product_hard_simulation):
+    """The Eb/N0 ladder of a product code under iBDD with scaled reliability (cc_mc_run_product_sr_dev), one weight per
+    half-iteration: ladder, sharding by block and the mean_last column of product_hard_simulation.  The log is
+    <pc.to_string()>-sr<halves>.log."""
+
+    def __init__(self, pc, weights, step=0.5, seed=0, random_codewords=False, backend=None, log_dir=None,
+                 max_samples=None, start=None, stop=None, samples_per_point=None):
+        self.weights = [float(w) for w in weights]
+        if not self.weights:
+            raise ValueError("one weight per half-iteration, at least one")
+        if backend is None:
+            backend = ProductSrBackend(pc, self.weights, random_codewords)
+        super().__init__(pc, len(self.weights), step, seed, random_codewords, backend, log_dir, max_samples, start, stop,
+                         samples_per_point)
+
+    def __call__(self):
+        name = "%s-sr%d.log" % (self.code.to_string(), self.halves)
         return self._ladder(name, "ebno", lambda ebno: ebno, " %12s" % "mean_last", lambda res: " %12.6f" % res["mean_last"])
 
 

@@ -580,6 +580,60 @@ int cc_product_decode_hard_dev(const cc_product *pc, const uint8_t *d_in, uint8_
 int cc_mc_run_product_hard_dev(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
                                int random_codewords, uint64_t *d_counters, void *stream);
 
+/* ---- iBDD with scaled reliability (iBDD-SR; A. Sheikh, A. Graell i Amat, G. Liva, IEEE Trans. Commun. 67 (12), 2019) of
+ *      a product code: one bounded-distance decode per line on hard decisions as in cc_product_decode_hard, whose verdict
+ *      is weighed against the channel value of every bit, sign(w_h u + y).  One launch runs all half-iterations of a
+ *      batch.  Of pc only rows, cols, extended and halves are read; e, w1, w2, N and the block [w2][w1] are those of
+ *      cc_product_decode.  `weights` holds `halves` host floats, also in the _dev forms.
+ *        channel     z = (y < 0) as bytes 0 / 1, so -0.0 gives 0.  Bit v is weak in half-iteration h iff
+ *                    fabsf(y_v) < weights[h], compared in float32: a NaN decides as 0 and is never weak, an infinite
+ *                    weight makes every bit of finite y weak, a zero weight makes no bit weak.
+ *        iteration   x_0 = z.  Half-iteration h = 0 .. halves - 1 takes the rows (h even) or the columns (h odd) of x_h.
+ *                    Every line is decoded from x_h by the line rule of cc_product_decode_hard, word for word (the
+ *                    candidate within distance t of the n inner positions; for an extended line also
+ *                    d_H + (parity differs) <= t); no line sees another line's result of the same pass.
+ *        taken word  For a line with taken word c (the n + e bits, parity included) and every position p of it:
+ *                    x_(h+1)(p) = c(p) where c(p) == z(p) or p is weak in h, and x_(h+1)(p) = z(p) otherwise -- the tie
+ *                    |y| == w included: the sum is zero and the channel decides.  A line whose syndromes are zero is its
+ *                    own taken word (with its parity bit mended where extended) and goes through the same formula; it
+ *                    changes where a bit that differs from z is no longer weak, which only happens under a schedule that
+ *                    is not non-decreasing.
+ *        fallback    For a line without a taken word (no candidate, or refused by d > t), x_(h+1)(p) = z(p) at every
+ *                    position of the line: corrections the other direction made earlier are lost there.
+ *        outputs     out = x_halves (B*N bytes).  nflip = d_H(out, z).  last = the largest h + 1 with x_(h+1) != x_h, 0 if
+ *                    there is none.  status = CC_FRAME_OK iff every row and every column of out is a word of its
+ *                    (extended, shortened) code, else CC_FRAME_NOT_CONVERGED.  nflip, last and status (B int32 each) may
+ *                    be NULL.
+ *      The device may stop working on a block only where no output can show it: after two successive passes without a
+ *      change, once every later half-iteration repeats the weight of the one two before it.
+ *      Refused before a device is asked for, in this order:
+ *        1. NULL pc, rows, cols, weights, y or out -> CC_ERR_INVALID_ARGUMENT (y / out unless B = 0;
+ *           cc_mc_run_product_sr_dev: NULL pc, weights or counters first)
+ *        2. halves == 0 -> CC_ERR_INVALID_ARGUMENT
+ *        3. what cc_product_decode_hard refuses for `rows`, then for `cols`, with its texts
+ *        4. the two handles on different devices -> CC_ERR_INVALID_ARGUMENT
+ *        5. a weight that is NaN or negative (-0.0 is not), or more than CC_PRODUCT_SR_MAX_LEVELS distinct values among
+ *           the weights -> CC_ERR_INVALID_ARGUMENT, cc_last_error naming which
+ *        6. out overlapping y -> CC_ERR_INVALID_ARGUMENT
+ *        7. a CC_DEVICE_NONE handle -> CC_ERR_NO_DEVICE
+ *      B = 0 answers CC_OK after these checks.  Buffers: natural alignment only, and nothing outside the stated extents
+ *      is read into a result or written.  A call with more than 128 half-iterations takes `halves` bytes from the `rows`
+ *      handle's workspace pool.  No staircase codes yet, no per-bit weights, no RS components, no q > 8, and no weight
+ *      optimisation: the schedule is the caller's. ---- */
+#define CC_PRODUCT_SR_MAX_LEVELS 15
+int cc_product_decode_sr(const cc_product *pc, const float *weights /* halves, host */, const float *y /* B*N */,
+                         uint8_t *out /* B*N */, int32_t *nflip /* B or NULL */, int32_t *last /* B or NULL */,
+                         int32_t *status /* B or NULL */, size_t B);
+int cc_product_decode_sr_dev(const cc_product *pc, const float *weights /* host */, const float *d_y, uint8_t *d_out,
+                             int32_t *d_nflip, int32_t *d_last, int32_t *d_status, size_t B, void *stream);
+/* Monte-Carlo of iBDD-SR: by definition the counters equal what cc_awgn_product_dev at cc_product_sigma,
+ * cc_product_decode_sr_dev and a comparison with the blocks sent would count.  The counters mean what they mean in
+ * cc_mc_run_product_hard_dev (CC_MC_CHANNEL_BIT_ERRORS from z, CC_MC_ITER_SUM the sum of `last`, CC_MC_ITER_HIST +
+ * min(last, 55)) and depend only on (seed, ebno, pc, weights, the set of global blocks).  Chunking and workspace follow
+ * cc_mc_run_product_dev: the `rows` handle's pool, one stream at a time. */
+int cc_mc_run_product_sr_dev(const cc_product *pc, const float *weights /* host */, double ebno_db, uint64_t seed,
+                             uint64_t first_block, size_t blocks, int random_codewords, uint64_t *d_counters, void *stream);
+
 /* ---- staircase codes (B. Smith et al., J. Lightwave Technol. 30 (1), 2012) of one binary BCH component code, decoded
  *      through a sliding window with the line rule of cc_product_decode_hard.  The reference has no such code.
  *      `code` is a handle cc_correct_chase_batch accepts at p = 0; e = 1 for the extended flavour (else 0); n + e must be

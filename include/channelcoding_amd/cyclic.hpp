@@ -756,6 +756,22 @@ public:
     return r;
   }
 
+  // iBDD with scaled reliability (cc_product_decode_sr): B blocks of N channel values, one weight per half-iteration
+  // (infinity is a weight: every bit yields to the component decoder); the result is that of correct_hard, nflip
+  // counted against the hard decisions of y.
+  hard_result correct_sr(const std::vector<float> &weights, const float *y, size_t B) const {
+    if (weights.empty()) throw std::runtime_error("product_code: one weight per half-iteration, at least one");
+    const cc_product pc = descriptor(0, nullptr, nullptr, static_cast<uint32_t>(weights.size()));
+    hard_result r;
+    r.words.resize(B * values());
+    r.nflip.resize(B);
+    r.last.resize(B);
+    r.status.resize(B);
+    detail::check(cc_product_decode_sr(&pc, weights.data(), y, r.words.data(), r.nflip.data(), r.last.data(), r.status.data(), B),
+                  "cc_product_decode_sr");
+    return r;
+  }
+
 private:
   cc_product descriptor(unsigned p, const float *alpha, const float *beta, uint32_t halves) const {
     cc_product pc;
