@@ -314,8 +314,8 @@ force_erasures_kernel(const T *__restrict__ in, const uint16_t *__restrict__ er,
 
 template <typename T>
 __global__ void __launch_bounds__(256)
-select_trial_kernel(const T *__restrict__ in, const uint16_t *__restrict__ er, const uint32_t *__restrict__ er_off,
-                    T *__restrict__ out0, int32_t *__restrict__ nerr0, int32_t *__restrict__ st0, const T *__restrict__ out1,
+select_trial_kernel(const T *in, const uint16_t *__restrict__ er, const uint32_t *__restrict__ er_off, T *out,
+                    const T *out0, int32_t *__restrict__ nerr0, int32_t *__restrict__ st0, const T *__restrict__ out1,
                     const int32_t *__restrict__ nerr1, const int32_t *__restrict__ st1, uint32_t n, uint32_t t2,
                     unsigned long long B) {
   const int lane = threadIdx.x & 63;
@@ -325,7 +325,11 @@ select_trial_kernel(const T *__restrict__ in, const uint16_t *__restrict__ er, c
     uint32_t ne = 0;  // the erased positions force_erasures_kernel took: those inside the frame
     for (uint32_t base = er_off[f], end = er_off[f + 1]; base < end; base += 64)  // wave-uniform trip count
       ne += __builtin_popcountll(__ballot(base + lane < end && er[base + lane] < n));
-    if (ne == 0) continue;  // trial 0 decoded the untouched word: the plain path (bch.h:100-101)
+    if (ne == 0) {  // trial 0 decoded the untouched word: the plain path (bch.h:100-101)
+      if (out0 != out)
+        for (uint32_t p = lane; p < n; p += 64) out[f * n + p] = out0[f * n + p];
+      continue;
+    }
     const int s0 = st0[f], s1 = st1[f], e0 = nerr0[f], e1 = nerr1[f];
     int pick, status;
     if (ne > t2) {
@@ -340,7 +344,7 @@ select_trial_kernel(const T *__restrict__ in, const uint16_t *__restrict__ er, c
     }
     for (uint32_t p = lane; p < n; p += 64) {
       const T v = pick < 0 ? in[f * n + p] : (pick == 1 ? out1[f * n + p] : out0[f * n + p]);
-      out0[f * n + p] = v;
+      out[f * n + p] = v;
     }
     if (lane == 0) {
       nerr0[f] = pick < 0 ? -1 : (pick == 1 ? e1 : e0);
@@ -365,11 +369,14 @@ int launch_pgz_erasures(const cc_code *code, const T *d_in, const uint16_t *d_er
   const int grid = code->num_cus * 8;
   hipLaunchKernelGGL(force_erasures_kernel<T>, dim3(grid), dim3(256), 0, stream, d_in, d_er, d_er_off, in0, in1,
                      static_cast<uint32_t>(n), Bq);
-  int rc = decode(in0, d_out, nerr0, st0);
+  // out == in: a frame that fails both trials returns the word received, which trial 0 must not have overwritten -- it
+  // then decodes its copy in place and select_trial_kernel writes every frame of d_out
+  T *out0 = d_out == d_in ? in0 : d_out;
+  int rc = decode(in0, out0, nerr0, st0);
   if (rc == CC_OK) rc = decode(in1, out1, nerr1, st1);
   if (rc == CC_OK) {
-    hipLaunchKernelGGL(select_trial_kernel<T>, dim3(grid), dim3(256), 0, stream, d_in, d_er, d_er_off, d_out, nerr0, st0,
-                       out1, nerr1, st1, static_cast<uint32_t>(n), t2, Bq);
+    hipLaunchKernelGGL(select_trial_kernel<T>, dim3(grid), dim3(256), 0, stream, d_in, d_er, d_er_off, d_out, out0, nerr0,
+                       st0, out1, nerr1, st1, static_cast<uint32_t>(n), t2, Bq);
     if (hipGetLastError() != hipSuccess) rc = CC_ERR_HIP;
   }
   (void)hipFreeAsync(in0, stream);

@@ -33,11 +33,12 @@ struct WideScratch {
 
 // TW: an RS code with roots alpha^(mu + i step) other than alpha^1 .. alpha^2t (algebraic.hip): the locator
 // of position p is Z = alpha^(step p) -- roots tested at Z^-1, erasure pre-load with Z -- and Forney's quotient is scaled
-// by alpha^(twist p); TW = false is the code as it was
+// by alpha^(twist p); TW = false is the code as it was.  out may be in (no __restrict__ on the two): a lane reads a symbol
+// before it writes it, and every later pass reads what the first wrote, the symbol itself
 template <bool TW>
 __global__ void __launch_bounds__(256)
-wide_correct_kernel(WideTables T, int alg, const uint16_t *__restrict__ in, const uint16_t *__restrict__ er,
-                    const uint32_t *__restrict__ er_off, uint16_t *__restrict__ out, int32_t *__restrict__ nerr_out,
+wide_correct_kernel(WideTables T, int alg, const uint16_t *in, const uint16_t *__restrict__ er,
+                    const uint32_t *__restrict__ er_off, uint16_t *out, int32_t *__restrict__ nerr_out,
                     int32_t *__restrict__ status_out, unsigned long long B) {
   __shared__ WideScratch scratch[4];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;

@@ -831,7 +831,8 @@ int cc_mc_run_burst_erasure_dev(const cc_code *code, const cc_burst_channel *ch,
  *      erasures; division_tag coding.  The byte entry points above return CC_ERR_UNSUPPORTED on such a handle and
  *      these return it on a q <= 8 handle.  Min-sum serves BCH codes up to q = 11 (n <= 2047) through the byte entry points
  *      (bits and LLRs have no symbol width); the Monte-Carlo calls do not apply, but for the two on packed words below
- *      (cc_mc_run_bsc_packed_dev, cc_bsc_packed_channel_dev), which serve every binary BCH code. ---- */
+ *      (cc_mc_run_bsc_packed_dev, cc_bsc_packed_channel_dev), which serve every binary BCH code.  As in the byte calls,
+ *      out may be the same buffer as in (decoding in place), with or without an erasure list. ---- */
 int cc_encode_batch_u16(const cc_code *code, const uint16_t *msg /* B*l */, uint16_t *cw /* B*n */, size_t B);
 int cc_encode_batch_u16_dev(const cc_code *code, const uint16_t *d_msg, uint16_t *d_cw, size_t B, void *stream);
 int cc_correct_hard_batch_u16(const cc_code *code, const uint16_t *in /* B*n symbols */, const uint16_t *erasures,

@@ -210,12 +210,17 @@ def test_two_pass_route(kind):
 
 
 # ------------------------------------------------ hard decoding ------------------------------------------------
+def symbol_type(o):
+    """bytes up to GF(2^8), 16-bit symbols beyond (the _u16 entry points)"""
+    return np.uint16 if o.q > 8 else np.uint8
+
+
 def corrupted(o, B, seed):
     """B codewords with 0 .. t + 2 symbol errors each (test_in_place_calls); the first frame is clean"""
     from test_gpu_algebraic import corrupt
     rng = np.random.default_rng(seed)
     hi = 2 if o.family == BCH else 1 << o.q
-    cw = o.encode(rng.integers(0, hi, (B, o.l)).astype(np.uint8))
+    cw = o.encode(rng.integers(0, hi, (B, o.l)).astype(symbol_type(o))).astype(symbol_type(o))
     ne = rng.integers(0, o.t + 3, B)
     ne[0] = 0
     if B >= 2:
@@ -225,16 +230,20 @@ def corrupted(o, B, seed):
 
 def hard_expected(o, alg, rx, per=None):
     """The oracle's answer in the form of the header: out = the corrected word, the (hard-decided) input where the frame
-    fails; nerr = the count, -1 where it fails; status = the oracle's (check_against_oracle, test_gpu_algebraic.py)."""
+    fails; nerr = the count, -1 where it fails; status = the oracle's (check_against_oracle, test_gpu_algebraic.py).
+    o: checkers.Oracle, or a model that takes one erasure list per frame (checkers.WideOracle, shortened_model.Shortened)."""
     B = rx.shape[0]
     if per is None:
-        out, nerr, st, _ = o.correct_hard(alg, rx)
-    else:
+        out, nerr, st = o.correct_hard(alg, rx)[:3]
+    elif isinstance(o, Oracle):
         rows = [o.correct_hard(alg, rx[f], per[f]) for f in range(B)]
         out, nerr, st = (np.concatenate([r[i] for r in rows]) for i in range(3))
+    else:
+        out, nerr, st = o.correct_hard(alg, rx, per)[:3]
     sym = (rx < 0).astype(np.uint8) if rx.dtype == np.float32 else rx
     ok = st == 0
-    return np.where(ok[:, None], out, sym).astype(np.uint8), np.where(ok, nerr, -1).astype(np.int32), st.astype(np.int32)
+    return (np.where(ok[:, None], out, sym).astype(symbol_type(o)), np.where(ok, nerr, -1).astype(np.int32),
+            st.astype(np.int32))
 
 
 def status_check(st, exact):
@@ -319,7 +328,7 @@ def erased(o, B, seed, most):
     """codewords with 0 .. most erased (zeroed) positions and errors up to one beyond what then can be corrected"""
     rng = np.random.default_rng(seed)
     hi = 2 if o.family == BCH else 1 << o.q
-    rx = o.encode(rng.integers(0, hi, (B, o.l)).astype(np.uint8))
+    rx = o.encode(rng.integers(0, hi, (B, o.l)).astype(symbol_type(o))).astype(symbol_type(o))
     per, pos, off = erasure_lists(rng, B, o.n, most)
     for f, er in enumerate(per):
         rx[f, er] = 0
@@ -344,12 +353,9 @@ def test_hard_decoding_with_erasures_on_the_plane_chain(alg):
     hard_check(code, alg, rx, want, ("planes + erasures", alg), csr=csr)
 
 
-def test_hard_decoding_by_two_trials():
-    """BCH(63,45), PGZ tag with erasures (bch.h:97-149): workspace stands in for the count and status the caller leaves out"""
+def two_trials_batch(B=9):
+    """BCH(63,45) words for the two-trial rule: (oracle, received words, erasure lists, CSR)"""
     o = oracle(BCH, 6, 3)
-    code = hard_code(BCH, 6, 3, PGZ)
-    B = 9
-    assert code.hard_route(B, True) == TRIALS
     rng = np.random.default_rng(909)
     rx = o.encode(rng.integers(0, 2, (B, o.l)).astype(np.uint8))
     per, pos, off = erasure_lists(rng, B, o.n, 7)
@@ -359,9 +365,31 @@ def test_hard_decoding_by_two_trials():
     for f in range(B):
         for p in rng.choice(o.n, int(rng.integers(0, 4)), replace=False):
             rx[f, p] ^= 1
+    return o, rx, per, (pos, off)
+
+
+def test_hard_decoding_by_two_trials():
+    """BCH(63,45), PGZ tag with erasures (bch.h:97-149): workspace stands in for the count and status the caller leaves out"""
+    code = hard_code(BCH, 6, 3, PGZ)
+    B = 9
+    assert code.hard_route(B, True) == TRIALS
+    o, rx, per, csr = two_trials_batch(B)
     want = hard_expected(o, PGZ, rx, per)
     hard_outcomes(want[2], B)
-    hard_check(code, PGZ, rx, want, "two trials", csr=(pos, off), exact=True)
+    hard_check(code, PGZ, rx, want, "two trials", csr=csr, exact=True)
+
+
+def test_hard_decoding_by_two_trials_in_place():
+    """out == in: the first trial decodes a copy in workspace, so a frame that fails (here: more than 2t erasures) still
+    returns the word received -- with what it held at the erased positions, which the trials overwrite"""
+    code = hard_code(BCH, 6, 3, PGZ)
+    B = 9
+    assert code.hard_route(B, True) == TRIALS
+    o, rx, per, csr = two_trials_batch(B)
+    want = hard_expected(o, PGZ, rx, per)
+    hard_outcomes(want[2], B)
+    assert any(want[2][f] != 0 and rx[f, per[f]].any() for f in range(B) if per[f]) and (want[0] != rx).any()
+    hard_check(code, PGZ, rx, want, "two trials in place", csr=csr, exact=True, in_place=True)
 
 
 @pytest.mark.parametrize("route,family,q,t,B", [(PLANES, RS, 8, 16, 257), (WAVE, BCH, 6, 3, 5)])
@@ -378,11 +406,12 @@ def test_hard_decoding_in_place(route, family, q, t, B):
 
 # ------------------------------------------------ encode, extract, decode ------------------------------------------------
 def messages(o, B, seed):
-    """random field elements; the first message all zero, the second all n"""
-    msg = np.random.default_rng(seed).integers(0, o.n + 1, (B, o.l)).astype(np.uint8)
+    """random field elements; the first message all zero, the second all 2^q - 1"""
+    top = (1 << o.q) - 1
+    msg = np.random.default_rng(seed).integers(0, top + 1, (B, o.l)).astype(symbol_type(o))
     msg[0] = 0
     if B >= 2:
-        msg[1] = o.n
+        msg[1] = top
     return msg
 
 
@@ -391,7 +420,7 @@ def map_check(code, fn, src, want, what, tail=()):
 
     def call(p):
         return fn(code._h, p["src"], p["dst"], B, *tail, p["stream"])
-    check_call(call, {"src": src}, {"dst": (np.uint8, want.size)}, {"dst": want}, what=what)
+    check_call(call, {"src": src}, {"dst": (want.dtype, want.size)}, {"dst": want}, what=what)
 
 
 # how launch_encode (csrc/encode.hip) chooses: the GF(2^8) interpolation encoder where bitslice_encode_supported, which

@@ -1,8 +1,9 @@
 """The buffer contract of the channel-only calls -- cc_awgn_llr_dev, cc_awgn_symbols_dev, cc_awgn_product_dev,
 cc_discrete_channel_dev, cc_burst_channel_dev, cc_burst_erasure_channel_dev, cc_bsc_packed_channel_dev -- and of the
-counters of the eight Monte-Carlo calls, under the harness of tests/guarded_buffers.py: every output of exactly the stated
-extent at the least alignment of its element type, between sentinel guards, every subset of the optional outputs absent in
-turn.  These calls read no caller buffer, so there is no poison to compare.
+counters of the Monte-Carlo calls (the first eight and the four routes added since), under the harness of
+tests/guarded_buffers.py: every output of exactly the stated extent at the least alignment of its element type, between
+sentinel guards, every subset of the optional outputs absent in turn.  These calls read no caller buffer, so there is no
+poison to compare.
 
 Expected values: the discrete, burst and packed outputs are bit for bit those of the host models (test_discrete_host,
 burst_model, burst_erasure_model, cc.pack_bits of the discrete model), the words sent the plain-C oracle's encoding of the
@@ -681,7 +682,101 @@ def working_point(c, frames, what):
 
 
 MC_EBNO = {"minsum": 3.0, "bm": 3.0, "chase": 2.0, "gmd": 4.0, "product": 3.0}
-MC_ROUTES = ["minsum", "bm", "chase", "gmd", "product", "discrete", "burst", "burst-erasure", "packed"]
+
+
+# The routes added since -- ordered statistics, iBDD and iBDD-SR of a product code, staircase codes: the same preload and
+# guards.  Their counts are the models' (osd_model, product_hard_model, product_sr_model, staircase_model) on the values the
+# route's own channel call writes; the point of each is chosen with the models alone, on the channel of awgn_model over the
+# words the host encoders send (`predicted`, which tests/test_buffer_cases_host.py asserts without a device): every route
+# that can fail has 0 < failures < frames, and ordered statistics, which cannot, 0 < word errors < frames.
+LATER = {
+    "osd": dict(q=4, t=2, order=1, ebno=1.0, frames=300),
+    "product-hard": dict(q=4, t=1, halves=6, ebno=4.5, frames=256),
+    "product-sr": dict(q=4, t=1, halves=6, ebno=3.5, frames=256),
+    "staircase": dict(q=4, t=1, N=14, L=9, W=4, I=2, ebno=5.0, frames=256),  # m = 7: blocks of 49 bits, six of nine counted
+}
+
+
+def sigma_of(rate, ebno):
+    """simulation.c++:83-85 in double, as the launchers pass it: rounded to float32"""
+    return float(np.float32(1.0 / np.sqrt(2.0 * rate * 10.0 ** (ebno / 10.0))))
+
+
+def later_weights(route):
+    from test_product_sr_host import RISING
+    return RISING[:LATER[route]["halves"]]
+
+
+def later_sent(route):
+    """the words, blocks or streams the route's channel sends for random codewords, from the host encoders"""
+    import product_hard_model as PH
+    import staircase_model as SM
+    from test_product_hard_host import encode_blocks
+    c = LATER[route]
+    frames = c["frames"]
+    if route == "osd":
+        return sent_words(Bch15, MC_SEED, MC_FIRST, frames, True)
+    if route == "staircase":
+        dec = SM.decoder(c["q"], c["t"], c["N"])
+        _, m, _, kb = SM.shape(dec, False)
+        msg = bch_message_bits(MC_SEED, MC_FIRST, frames, c["L"] * m * kb).reshape(frames, c["L"], m, kb)
+        return np.asarray(SM.encode(dec, msg, False), np.uint8)
+    dec = PH.decoder(c["q"], c["t"])
+    msg = bch_message_bits(MC_SEED, MC_FIRST, frames, dec.l * dec.l).reshape(frames, dec.l, dec.l)
+    return encode_blocks(dec, dec, msg, False)
+
+
+def later_rate(route):
+    import product_hard_model as PH
+    import staircase_model as SM
+    c = LATER[route]
+    if route == "osd":
+        return Bch15.l / Bch15.n
+    if route == "staircase":
+        _, m, r, _ = SM.shape(SM.decoder(c["q"], c["t"], c["N"]), False)
+        return 1.0 - r / m
+    dec = PH.decoder(c["q"], c["t"])
+    return (dec.l / dec.n) ** 2
+
+
+def later_count(route, y, sent):
+    """the counters of the header for the channel values y (staircase: the hard decisions z) and the words sent"""
+    import osd_model
+    import product_hard_model as PH
+    import product_sr_model as SR
+    import staircase_model as SM
+    from test_gpu_osd import counted as osd_counted
+    from test_gpu_product_hard import counted as product_counted
+    from test_gpu_staircase import counted as staircase_counted
+    c = LATER[route]
+    if route == "osd":
+        return osd_counted(osd_model.osd(osd_model.decoder(c["q"], c["t"]), y, c["order"])["out"], sent, y)
+    if route == "staircase":
+        dec = SM.decoder(c["q"], c["t"], c["N"])
+        return staircase_counted(SM.decode(dec, y, c["W"], c["I"], False), sent, y, c["L"], c["W"])
+    dec = PH.decoder(c["q"], c["t"])
+    if route == "product-hard":
+        return product_counted(PH.decode(dec, dec, (y < 0).astype(np.uint8), c["halves"], False), sent, y)
+    return product_counted(SR.decode(dec, dec, y, later_weights(route), False), sent, y)
+
+
+@functools.lru_cache(maxsize=None)
+def later_predicted(route):
+    """the counts on the float64 channel model over the host encoders' words: no device"""
+    c, sent = LATER[route], later_sent(route)
+    frames = c["frames"]
+    y = awgn_reference(sent[0].size, sigma_of(later_rate(route), c["ebno"]), MC_SEED, MC_FIRST, frames, sent.reshape(frames, -1))
+    y = y.astype(np.float32).reshape(sent.shape)
+    return later_count(route, (y < 0).astype(np.uint8) if route == "staircase" else y, sent)
+
+
+def later_point(c, frames, route, what=""):
+    if route != "osd":
+        return working_point(c, frames, (route, what))
+    assert c[capi.MC_FRAMES] == frames and c[capi.MC_FAILURES] == 0 and 0 < c[capi.MC_WORD_ERRORS] < frames, (route, what, c[:8])
+
+
+MC_ROUTES = ["minsum", "bm", "chase", "gmd", "product", "discrete", "burst", "burst-erasure", "packed"] + list(LATER)
 
 
 @pytest.mark.parametrize("route", MC_ROUTES)
@@ -744,13 +839,50 @@ def test_monte_carlo_counters(route):
                 return lib().cc_mc_run_burst_dev(code._h, C.byref(chan), MC_SEED, first, frames, 1, p["counters"], p["stream"])
             return lib().cc_mc_run_burst_erasure_dev(code._h, C.byref(chan), C.byref(det), MC_SEED, first, frames, 1,
                                                      p["counters"], p["stream"])
+    elif route in LATER:
+        c = LATER[route]
+        frames, ebno = c["frames"], c["ebno"]
+        later_point(later_predicted(route), frames, route, "predicted")
+        if route == "osd":
+            code, untouched = bch(cc.berlekamp_massey_tag()), [capi.MC_FAILURES] + NOT_TOUCHED
+            (y, sent), _ = awgn_frames(code, ebno, frames)
+
+            def call(p):
+                return lib().cc_mc_run_osd_dev(code._h, c["order"], ebno, MC_SEED, MC_FIRST, frames, 1, p["counters"], p["stream"])
+        elif route == "staircase":
+            from channelcoding_amd.codes import staircase_code
+            sc, untouched = staircase_code(cc.primitive_bch(c["q"], cc.errors(c["t"]), cc.berlekamp_massey_tag(), n=c["N"]),
+                                           c["L"], c["W"], c["I"]), NOT_TOUCHED
+            ch = sc.channel(ebno, MC_SEED, MC_FIRST, frames, True)
+            y, sent, desc = ch["z"].cpu().numpy(), ch["sent"].cpu().numpy(), sc._sc()
+
+            def call(p):
+                return lib().cc_mc_run_staircase_dev(C.byref(desc), ebno, MC_SEED, MC_FIRST, frames, 1, p["counters"], p["stream"])
+        else:  # (iBDD and iBDD-SR count iterations: CC_MC_ITER_SUM and the histogram are theirs)
+            from channelcoding_amd.codes import _sr_weights
+            mk = lambda: cc.primitive_bch(c["q"], cc.errors(c["t"]), cc.berlekamp_massey_tag())  # noqa: E731
+            pc = cc.product_code(mk(), mk())
+            ch = pc.channel(ebno, MC_SEED, MC_FIRST, frames, True)
+            y, sent, desc = ch["y"].cpu().numpy(), ch["sent"].cpu().numpy(), pc._pc_hard(c["halves"])
+            weights = _sr_weights(later_weights(route))
+
+            def call(p):
+                if route == "product-hard":
+                    return lib().cc_mc_run_product_hard_dev(C.byref(desc), ebno, MC_SEED, MC_FIRST, frames, 1, p["counters"],
+                                                            p["stream"])
+                return lib().cc_mc_run_product_sr_dev(C.byref(desc), weights, ebno, MC_SEED, MC_FIRST, frames, 1, p["counters"],
+                                                      p["stream"])
+        assert np.array_equal(sent, later_sent(route).reshape(sent.shape))  # the host encoders send the same words
+        counts = later_count(route, y, sent)
+        if route != "osd" and route != "staircase":
+            assert counts[capi.MC_ITER_SUM] > 0 and counts[capi.MC_ITER_HIST:].sum() == frames
     else:
         code, counts = bch(cc.berlekamp_massey_tag()), count_packed()
         untouched = NOT_TOUCHED + [capi.MC_CHANNEL_ERASURES]
 
         def call(p):
             return lib().cc_mc_run_bsc_packed_dev(code._h, PACKED_POINT, MC_SEED, MC_FIRST, frames, 1, p["counters"], p["stream"])
-    working_point(counts, frames, route)
+    (later_point if route in LATER else working_point)(counts, frames, route)
     assert not counts[untouched].any() and (counts >= 0).all()
     assert (PRELOAD[0] & np.uint64(0xFFFFFFFF)) + np.uint64(frames) > np.uint64(0xFFFFFFFF)  # the frame count carries
     want = PRELOAD + counts.astype(np.uint64)
