@@ -292,6 +292,21 @@ constexpr int diag_row_body(int K, int D, int LPF, int variant) {
 #endif
 }
 
+// Whether the general diagonal kernel makes a finished frame's result from the registers its stop scan left and sets the
+// next frame up in one batch (minsum_diag_impl.hpp, REGSW; profiles/r25_experiments.md, E48), per geometry and variant.
+// The path holds up to 3 CPL values across the switch; it is taken wherever the compiler fits them into the registers
+// the instantiation had (vgpr_count, spilled registers and scratch bytes of the code objects, no one above the
+// column-by-column path's).  Not so: BCH(127,99), which spills already (one or two spilled registers more in every
+// variant), and five self-correcting instantiations of the 8-lane geometries (one register, or four bytes of scratch,
+// more).  The message-free kernel always takes it.
+constexpr bool diag_switch_from_registers(int K, int D, int LPF, int variant) {
+  if (LPF != 8) return true;
+  if (K == 28 && D == 7) return false;
+  if (variant == CC_ALG_SCMS2) return !((K == 21 && D == 6) || (K == 10 && D == 1) || (K == 8 && D == 1));
+  if (variant == CC_ALG_SCMS1) return !((K == 20 && D == 1) || (K == 24 && D == 4));
+  return true;
+}
+
 // wide.hip
 int launch_wide_correct(const cc_code *code, const uint16_t *d_in, const uint16_t *d_er, const uint32_t *d_off,
                         uint16_t *d_out, int32_t *d_nerr, int32_t *d_status, size_t B, hipStream_t stream);

@@ -979,8 +979,11 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
     // must keep every column's reads behind the previous column's writes -- it cannot tell the addresses apart -- and
     // the scan pays one LDS round trip per column, 16 per iteration (round 2: 8 % of the kernel's time).  The check
     // masks come along unconditionally (one v_cndmask per column instead of a read under EXEC = hard decision).
+    // The scan leaves what it read -- the new column sums and the channel values of the owned columns -- to the frame
+    // switch below, which makes a finished frame's result from them instead of reading the cells back (REGSW).
+    constexpr bool REGSW = SINGLE || diag_switch_from_registers(K, D, LPF, VARIANT);
+    float cnv[CPL], yc[CPL];
     auto stop_scan = [&](auto ORC) {
-      float cnv[CPL], yc[CPL];
       uint32_t cb[CPL];
 #pragma unroll
       for (int c = 0; c < CPL; ++c) {
@@ -1019,6 +1022,14 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
     bool ok;
     if (SINGLE && p.stop_rule == CC_STOP_AS_SHIPPED) {
       ok = true;  // no test at all, and nothing to move
+      // the cells {cs', y} of the owned columns for the frame switch, all reads behind one wait
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) {
+        const float2 cy = *reinterpret_cast<const float2 *>(cy_base + (col0 + LPF * c) * 8);
+        cnv[c] = cy.x;
+        yc[c] = cy.y;
+      }
+      asm volatile("" ::: "memory");
     } else if (p.stop_rule == CC_STOP_PUBLISHED) {
       stop_scan(std::true_type{});
       ok = group_or<LPF>(acc) == 0;
@@ -1038,27 +1049,64 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
       active = frame < B;
       uint8_t *hp = hard + done * n + lam;
       float *Lp = Lout ? Lout + done * n + lam : nullptr;
-      // column by column: result of the decided frame out of LDS, the next frame's channel value in, result to
-      // HBM -- nothing is held in registers across columns.  The wait comes before the first store: the next frame
-      // was staged a whole frame ago and nothing else of this wave is in flight, so it is free.
       // first pass of two: a frame that has not stopped is handed on (nothing of it is written here)
-      const bool handed = SINGLE && p.first_pass != 0 && !ok;
-      auto emit = [&](int c, float L) {
-        if (handed) return;
+      bool handed = false;
+      if constexpr (SINGLE) handed = p.first_pass != 0 && !ok;
+      // one column of the result; only the last owned column can lie beyond the frame
+      auto emit_col = [&](int c, float L, bool want_L) {
         if (c < CPL - 1 || lam + LPF * c < n) {
           hp[LPF * c] = (L < 0.0f) ? 1 : 0;
-          if (Lp) Lp[LPF * c] = L;
+          if (want_L) Lp[LPF * c] = L;
         }
       };
-      if (active) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      // REGSW: result of the decided frame from the registers the stop scan left (SINGLE under the as-shipped rule: from
+      // the batch read in its place).  L = cs + y is the same single addition of the same two operands as reading the
+      // cell back -- the scan stored cs := cnv[c] into the cell, and y is what the scan read FROM the cell (erased
+      // positions included: they were zeroed in the cell at set-up) and nothing has written since.  No LDS access, no
+      // wait.  Whether L is wanted is the same for the whole call: one branch around the columns, not one per column.
+      auto emit = [&](auto WANT_L) {
 #pragma unroll
-        for (int c = 0; c < CPL; ++c) {
-          const float2 cy = *reinterpret_cast<const float2 *>(cy_base + (col0 + LPF * c) * 8);  // {cs (new), y}
-          float y = staged(c) + 0.0f;  // -0.0f -> +0.0f
-          if (c == CPL - 1 && lam + LPF * c >= n) y = 0.0f;
-          *reinterpret_cast<float2 *>(cy_base + (col0 + LPF * c) * 8) = make_cell(0.0f, y);
-          emit(c, cy.x + cy.y);
+        for (int c = 0; c < CPL; ++c) emit_col(c, cnv[c] + yc[c], decltype(WANT_L)::value);
+      };
+      auto emit_frame = [&] {
+        if (handed) return;
+        if (Lout) emit(std::true_type{});
+        else emit(std::false_type{});
+      };
+      if (active) {
+        if constexpr (!REGSW) {
+          // column by column: result of the decided frame out of LDS, the next frame's channel value in, result to
+          // HBM -- nothing is held in registers across columns (the instantiations that have no register to spare:
+          // diag_switch_from_registers in cc_internal.hpp)
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+          for (int c = 0; c < CPL; ++c) {
+            const float2 cy = *reinterpret_cast<const float2 *>(cy_base + (col0 + LPF * c) * 8);  // {cs (new), y}
+            float y = staged(c) + 0.0f;  // -0.0f -> +0.0f
+            if (c == CPL - 1 && lam + LPF * c >= n) y = 0.0f;
+            *reinterpret_cast<float2 *>(cy_base + (col0 + LPF * c) * 8) = make_cell(0.0f, y);
+            emit_col(c, cy.x + cy.y, Lp != nullptr);
+          }
+        } else {
+          // The next frame was staged a whole frame ago and nothing else of this wave is in flight, so this wait is
+          // free.  All its channel values are requested first; the results go out to HBM while they travel, and ONE
+          // wait stands before the cells are written: the last-requested value is consumed first, and LDS returns in
+          // order.  (The message-free kernel sends the results off before the requests: their registers are then free
+          // for the channel values, which keeps it at the register count it had; it has the occupancy to hide the one
+          // wait.)
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          if constexpr (SINGLE) emit_frame();
+          float ys[CPL];
+#pragma unroll
+          for (int c = 0; c < CPL; ++c) ys[c] = staged(c);
+          asm volatile("" ::: "memory");
+          if constexpr (!SINGLE) emit_frame();
+#pragma unroll
+          for (int c = CPL - 1; c >= 0; --c) {
+            float y = ys[c] + 0.0f;  // -0.0f -> +0.0f
+            if (c == CPL - 1 && lam + LPF * c >= n) y = 0.0f;
+            *reinterpret_cast<float2 *>(cy_base + (col0 + LPF * c) * 8) = make_cell(0.0f, y);
+          }
         }
         if (er_off != nullptr) {  // cyclic.h:259-262
           for (uint32_t e = er_off[frame]; e < er_off[frame + 1]; ++e) {
@@ -1072,11 +1120,13 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
           for (int r = lam; r < K; r += LPF) my_rows[r] = make_uint2(0u, 0u);
         if constexpr (BITS1) static_for<NW>([&](auto Wd) { SW[Wd] = 0u; ZW[Wd] = 0xFFFFFFFFu; });
         it = 0;
+      } else if constexpr (REGSW) {
+        emit_frame();
       } else {
 #pragma unroll
         for (int c = 0; c < CPL; ++c) {
           const float2 cy = *reinterpret_cast<const float2 *>(cy_base + (col0 + LPF * c) * 8);
-          emit(c, cy.x + cy.y);
+          emit_col(c, cy.x + cy.y, Lp != nullptr);
         }
       }
       if (lam == 0) {
