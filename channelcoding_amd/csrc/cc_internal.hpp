@@ -307,6 +307,15 @@ constexpr bool diag_switch_from_registers(int K, int D, int LPF, int variant) {
   return true;
 }
 
+// The check masks of the columns in the diagonal kernel's LDS (minsum_diag_impl.hpp, CB128; profiles/r26_experiments.md):
+// with 16 lanes per frame a lane's CPL masks lie together, 20 words from the next lane's, and the stop scan reads them
+// four at a time; otherwise one word per column, column-linear.  Kernel and launcher size the area by the same function.
+constexpr int DIAG_CB_LANE_WORDS = 20;
+constexpr bool diag_check_masks_per_lane(int LPF, int CPL) { return LPF == 16 && CPL == 16; }
+constexpr int diag_check_mask_bytes(int LPF, int CPL) {
+  return diag_check_masks_per_lane(LPF, CPL) ? 16 * DIAG_CB_LANE_WORDS * 4 : 256 * 4;
+}
+
 // wide.hip
 int launch_wide_correct(const cc_code *code, const uint16_t *d_in, const uint16_t *d_er, const uint32_t *d_off,
                         uint16_t *d_out, int32_t *d_nerr, int32_t *d_status, size_t B, hipStream_t stream);

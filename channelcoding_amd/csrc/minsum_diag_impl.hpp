@@ -334,12 +334,22 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
   const int fl = lane / LPF, lam = lane & (LPF - 1);
   char *cy_base = smem + wid * WAVE_BYTES;
   char *cn_lane = cy_base + CY_BYTES + ((fl >> 1) - fl) * RC * 8 + (fl & 1) * 4;  // + aCY[d] -> CN slot
-  uint32_t *cbits = reinterpret_cast<uint32_t *>(smem + 4 * WAVE_BYTES);  // [256] per workgroup
+  // check masks of the columns, per workgroup.  CB128 (16 lanes per frame): laid out per lane, cb16[lam][c] at a lane
+  // stride of DIAG_CB_LANE_WORDS = 20 words, so that the stop scan fetches a lane's 16 masks with four ds_read_b128 instead
+  // of 16 ds_read_b32 -- the 16 lanes of a b128 lane group hold 16 different lam (or the same address as another frame's
+  // lane: a broadcast), which start at the banks 20 lam mod 64, all multiples of four and all different: no conflict.
+  // Otherwise [256], column-linear.
+  constexpr bool CB128 = diag_check_masks_per_lane(LPF, CPL);
+  constexpr int CB_BYTES = diag_check_mask_bytes(LPF, CPL);
+  uint32_t *cbits = reinterpret_cast<uint32_t *>(smem + 4 * WAVE_BYTES);
   // STG[c][lane]: channel values of the frame each group decodes NEXT, written by global_load_lds (no VGPR on the
   // way) while the current frame iterates; CPL x 256 bytes per wavefront
-  char *stg = smem + 4 * WAVE_BYTES + 1024 + wid * (CPL * 256);
+  char *stg = smem + 4 * WAVE_BYTES + CB_BYTES + wid * (CPL * 256);
   const uint32_t stg_lds = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(reinterpret_cast<size_t>(stg)));
-  cbits[threadIdx.x] = colbits[threadIdx.x];
+  if constexpr (CB128)
+    cbits[(threadIdx.x & 15) * DIAG_CB_LANE_WORDS + (threadIdx.x >> 4)] = colbits[threadIdx.x];
+  else
+    cbits[threadIdx.x] = colbits[threadIdx.x];
   constexpr bool POOL = !SINGLE && LPF == 16;  // how frames are dealt, see below
   __shared__ unsigned wg_next;  // (round-3 deal) ordinal of the workgroup's next unassigned frame (see take_frame below)
   if (!POOL && threadIdx.x == 0) wg_next = 2 * 4 * (64 / LPF);  // every lane group starts with two frames of its own
@@ -772,6 +782,11 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
       }
     };
     // column sums accumulated so far, requested before the reduction so that their latency hides behind it
+    // ROW0_FRESH: row 0 is the first contributor of every column it touches (rows add in ascending order, and no column
+    // of the band wraps around: the launcher checks max diagonal + K - 1 < n), and the stop scan -- or the clear in front
+    // of the first frame -- left cs' = +0.0f in all of them, so row 0 takes the constant in place of the read.  PARTIAL
+    // geometries keep the read (their empty slots accumulate in the scratch columns), SINGLE has no cs' area.
+    constexpr bool ROW0_FRESH = !SINGLE && !PARTIAL;
     auto row_cn = [&](auto IR, float (&cn)[D]) {
       constexpr int i = decltype(IR)::value;
       static_for<D>([&](auto DD) {
@@ -780,6 +795,8 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
           cn[d] = carry_sum[d / 2];  // the head added to this column in row i - 1 and kept the sum
         else if constexpr (SINGLE)
           cn[d] = cell_cs(cyq[d]);
+        else if constexpr (ROW0_FRESH && i == 0)
+          cn[d] = 0.0f;  // no read: see ROW0_FRESH (the addition stays: +0.0f + r is not r for r = -0.0f)
         else
 #ifdef CC_EXP_NO_CNR
           asm volatile("" : "=v"(cn[d]));
@@ -995,7 +1012,17 @@ minsum_diag_kernel(MinSumParams p, const uint16_t *__restrict__ diag_s, const ui
           cnv[c] = *reinterpret_cast<const float *>(cn_lane + (col0 + LPF * c) * 8);
           yc[c] = *reinterpret_cast<const float *>(cy_base + (col0 + LPF * c) * 8 + 4);
         }
-        cb[c] = cbits[lam + LPF * c];
+        if constexpr (CB128) {
+          if (c % 4 == 0) {  // masks of the columns c .. c + 3 in one ds_read_b128
+            const uint4 m4 = *reinterpret_cast<const uint4 *>(cbits + lam * DIAG_CB_LANE_WORDS + c);
+            cb[c] = m4.x;
+            cb[c + 1] = m4.y;
+            cb[c + 2] = m4.z;
+            cb[c + 3] = m4.w;
+          }
+        } else {
+          cb[c] = cbits[lam + LPF * c];
+        }
       }
       asm volatile("" ::: "memory");
 #pragma unroll
@@ -1184,6 +1211,14 @@ int launch_diag_geometry(const cc_code *code, const MinSumParams &p, const float
   constexpr int FPW = 64 / LPF;
   if (!(code->tab.n > static_cast<unsigned>(LPF * (CPL - 1)) && code->tab.n <= static_cast<unsigned>(LPF * CPL))) {
     set_last_error("minsum_diag: only the last owned column of a lane may lie beyond the frame");
+    return CC_ERR_UNSUPPORTED;
+  }
+  // row 0 adds to columns nobody has added to in this iteration (ROW0_FRESH in the kernel) only if no column of the
+  // band wraps around: row i of diagonal s sits in column s + i
+  unsigned top_diag = 0;
+  for (unsigned s : code->tab.row0_support) top_diag = s > top_diag ? s : top_diag;
+  if (top_diag + K - 1 >= code->tab.n) {
+    set_last_error("minsum_diag: a diagonal of the band wraps around the frame");
     return CC_ERR_UNSUPPORTED;
   }
   if (p.pool == nullptr || B >= (1ull << 32)) {  // (frame ordinals are 32-bit words: B / S + 2 W_s GPW + draws)
