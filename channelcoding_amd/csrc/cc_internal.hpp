@@ -184,6 +184,28 @@ int hip_fail(hipError_t e, const char *what);
     if (_e != hipSuccess) return ccamd::hip_fail(_e, #expr); \
   } while (0)
 
+// A kernel's opt-in to `bytes` of dynamic LDS, beyond the default limit of 64 KiB: once per device, the launcher keeping
+// one static LdsOptIn per kernel.  The lock is held across check, call and mark.
+struct LdsOptIn {
+  std::mutex lock;
+  unsigned long long done = 0;  // bit d: set on device d
+};
+inline int lds_opt_in(const void *kernel, LdsOptIn &once, int device, int bytes, const char *what) {
+  const unsigned dev = static_cast<unsigned>(device) & 63u;
+  std::lock_guard<std::mutex> g(once.lock);
+  if (!((once.done >> dev) & 1ull)) {
+    const hipError_t attr = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (attr != hipSuccess) return hip_fail(attr, what);
+    once.done |= 1ull << dev;
+  }
+  return CC_OK;
+}
+// a grid of `want` workgroups, at most eight per CU and at least one
+inline unsigned capped_grid(const cc_code *code, unsigned long long want) {
+  const unsigned long long cap = static_cast<unsigned long long>(code->num_cus) * 8;
+  return static_cast<unsigned>(want < 1 ? 1 : want < cap ? want : cap);
+}
+
 // minsum.hip
 int launch_minsum(const cc_code *code, const float *d_llr, const uint16_t *d_er, const uint32_t *d_er_off,
                   uint8_t *d_hard, float *d_L, uint16_t *d_iters, int32_t *d_status, size_t B, hipStream_t stream);

@@ -311,18 +311,10 @@ int launch_packed_long_correct(const cc_code *code, const uint8_t *d_in, uint8_t
     set_last_error("packed_long_correct_kernel: tables beyond the LDS of a CU");
     return CC_ERR_UNSUPPORTED;
   }
-  {  // once per device: the kernel may ask for all of a CU's LDS
-    static std::mutex lock;
-    static unsigned long long done = 0;
-    const unsigned dev = static_cast<unsigned>(code->device) & 63u;
-    std::lock_guard<std::mutex> g(lock);
-    if (!((done >> dev) & 1ull)) {
-      const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&packed_long_correct_kernel),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (attr != hipSuccess) return hip_fail(attr, "packed_long_correct_kernel LDS attribute");
-      done |= 1ull << dev;
-    }
-  }
+  static LdsOptIn once;  // the kernel may ask for all of a CU's LDS
+  if (int rc = lds_opt_in(reinterpret_cast<const void *>(&packed_long_correct_kernel), once, code->device, 160 * 1024,
+                          "packed_long_correct_kernel LDS attribute"))
+    return rc;
   // resident workgroups per CU: by LDS, and by the 16 wavefronts per CU that 128 registers per lane leave
   size_t resident = (160 * 1024) / lds;
   if (resident > static_cast<size_t>(kLongMaxWaves / waves)) resident = kLongMaxWaves / waves;

@@ -2,9 +2,13 @@
 // of a block in one launch.  The contract is stated at cc_product_decode_hard in the public header; here
 // is how it is mapped.
 //
-// A block lives in LDS as bits from its load to its store: X[w2][P] dwords, bit k & 31 of X[i][k >> 5] = x(i, k), the
-// pitch P = ceil(w1 / 32) | 1 odd so that the lanes of a row pass walk different banks.  X0 is the block as it was
-// loaded (nflip = popcount(X ^ X0) at the end), ctl holds last, the status flag and nflip.
+// This kernel is spelled out on purpose: what product_sr.hip takes from hard_lines.hpp as product_frame, load_bit_rows,
+// apply_flips and product_finish stands here in the kernel's own text, because each of those helpers moves the 143 / 214
+// scalars this kernel keeps in VGPR lanes, and 1 .. 3 % of a call with them (profiles/r27_ibdd_block_frame.txt).  A
+// change to the crossing update, the load or the end of a block in hard_lines.hpp has to be made here too.
+//
+// A block lives in LDS as bits from its load to its store, in hard_lines.hpp's tile: X, and X0, the block as it was
+// loaded (nflip = popcount(X ^ X0) at the end); ctl holds last, the status flag and nflip.
 //
 //   WG = false  a block whose longer side is <= 64 lines belongs to one wavefront, a workgroup carries four blocks, and
 //               a line is one 64-bit register
@@ -30,24 +34,10 @@
 // nothing either, so `last`, out and status cannot show it.
 //
 // Global traffic per block: N bytes in (a ballot per 64 bytes makes the bits), N bytes out, three int32.
-#include <mutex>
-
 #include "hard_lines.hpp"
 
 namespace ccamd {
 namespace {
-
-constexpr int kHardTables = 2 * kSoftTables;  // the tables of `rows`, then those of `cols`
-
-// the LDS of one block, in dwords: X and X0 [w2][P], ctl [4], then the state of every line as bytes -- the t odd
-// syndromes S_1, S_3, .. and in slot t the parity of all its bits -- at a pitch of whole dwords, rows then columns
-struct HardBlock {
-  int P, pitch_r, pitch_c, dwords;
-};
-__host__ __device__ constexpr HardBlock hard_block(int w1, int w2, int tr, int tc) {
-  const int P = ((w1 + 31) >> 5) | 1, pitch_r = (tr + 4) & ~3, pitch_c = (tc + 4) & ~3;
-  return HardBlock{P, pitch_r, pitch_c, 2 * w2 * P + 4 + (w2 * pitch_r + w1 * pitch_c) / 4};
-}
 
 template <bool WG>
 __global__ void __launch_bounds__(256)
@@ -68,18 +58,12 @@ product_hard_kernel(const AlgebraicTables *__restrict__ Tr, const AlgebraicTable
   const int PD = (w1 + 31) >> 5, P = PD | 1, chunks = (w1 + 63) >> 6;
   const unsigned long long N = static_cast<unsigned long long>(w1) * w2;
   const int nnr = Tr->nf, nnc = Tc->nf, tr = Tr->nroots / 2, tc = Tc->nroots / 2;
-  const HardBlock lay = hard_block(w1, w2, tr, tc);
+  const ProductBlock lay = product_block(w1, w2, tr, tc, 2, 1);  // the tiles X and X0, one copy of the states
   const int pitch_r = lay.pitch_r, pitch_c = lay.pitch_c;
   uint8_t *colbase = smem + kHardTables + wid * col_bytes;
   uint32_t *X = reinterpret_cast<uint32_t *>(smem + kHardTables + 4 * col_bytes) + (WG ? 0 : wid * lay.dwords);
   uint32_t *X0 = X + w2 * P, *ctl = X0 + w2 * P;  // ctl: [0] last, [1] a line that is no word, [2] nflip
   uint8_t *SR = reinterpret_cast<uint8_t *>(ctl + 4), *SC = SR + w2 * pitch_r;
-  const auto sync = [] {
-    if constexpr (WG)
-      __syncthreads();
-    else
-      wave_sync();
-  };
   const int row0 = WG ? wid : 0, row_step = WG ? 4 : 1;  // the rows a wavefront loads and stores
 
   const unsigned long long start = WG ? blockIdx.x : blockIdx.x * 4ull + wid, stride = WG ? gridDim.x : gridDim.x * 4ull;
@@ -111,7 +95,7 @@ product_hard_kernel(const AlgebraicTables *__restrict__ Tr, const AlgebraicTable
         }
     }
     if (line < 4) ctl[line] = 0;
-    sync();
+    block_sync<WG>();
 
     // ---------------- the state of every line: odd syndromes and parity, from the bits, once ----------------
     for (int dir = 0; dir < 2; ++dir) {
@@ -127,7 +111,7 @@ product_hard_kernel(const AlgebraicTables *__restrict__ Tr, const AlgebraicTable
         S[t] = static_cast<uint8_t>(count_bits<NC>(lb) & 1);
       }
     }
-    sync();
+    block_sync<WG>();
 
     // ---------------- the half-iterations ----------------
     for (int h = 0; h < halves; ++h) {
@@ -145,10 +129,10 @@ product_hard_kernel(const AlgebraicTables *__restrict__ Tr, const AlgebraicTable
       unsigned long long fm[NC];  // positions the line changes at
       line_flips<NC>(ex, lg2, SL, LL, BL, S, have_line, lane, n, nn, t, e, fm);
       const bool changed = any_bit<NC>(fm);
-      sync();  // every line of the pass has been read
+      block_sync<WG>();  // every line of the pass has been read
       if (changed) {
         // the line becomes a word of its code: its own state is zero; every flipped bit is position `line` of a line
-        // of the other direction, whose state takes alpha^(j line) and the parity
+        // of the other direction, whose state takes alpha^(j line) and the parity (hard_lines.hpp: apply_flips)
         for (int m = 0; m <= t; ++m) S[m] = 0;
         const uint8_t *exo = smem + (column ? 0 : kSoftTables);
         uint32_t *So = reinterpret_cast<uint32_t *>(column ? SR : SC);
@@ -183,7 +167,7 @@ product_hard_kernel(const AlgebraicTables *__restrict__ Tr, const AlgebraicTable
         }
         atomicMax(&ctl[0], static_cast<uint32_t>(h + 1));
       }
-      sync();
+      block_sync<WG>();
       if (h + 1 - static_cast<int>(ctl[0]) >= 2) break;  // a fixed point; the same value in every lane of the block
     }
 
@@ -200,7 +184,7 @@ product_hard_kernel(const AlgebraicTables *__restrict__ Tr, const AlgebraicTable
       diff += static_cast<uint32_t>(__builtin_popcount(X[r * P + d] ^ X0[r * P + d]));
     }
     if (diff) atomicAdd(&ctl[2], diff);
-    sync();
+    block_sync<WG>();
 
     // ---------------- store: bits -> bytes ----------------
     uint8_t *dst = out + b * N;
@@ -209,12 +193,8 @@ product_hard_kernel(const AlgebraicTables *__restrict__ Tr, const AlgebraicTable
         const int col = 64 * c + lane;
         if (col < w1) dst[static_cast<unsigned long long>(r) * w1 + col] = static_cast<uint8_t>((X[r * P + (col >> 5)] >> (col & 31)) & 1u);
       }
-    if (line == 0) {
-      if (nflip_out) nflip_out[b] = static_cast<int32_t>(ctl[2]);
-      if (last_out) last_out[b] = static_cast<int32_t>(ctl[0]);
-      if (status_out) status_out[b] = ctl[1] ? CC_FRAME_NOT_CONVERGED : CC_FRAME_OK;
-    }
-    sync();  // the next block overwrites X, X0 and ctl
+    if (line == 0) store_results(nflip_out, last_out, status_out, b, ctl);
+    block_sync<WG>();  // the next block overwrites X, X0 and ctl
   }
 }
 
@@ -223,32 +203,18 @@ product_hard_kernel(const AlgebraicTables *__restrict__ Tr, const AlgebraicTable
 int launch_product_hard(const cc_product *pc, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip, int32_t *d_last,
                         int32_t *d_status, size_t B, hipStream_t stream) {
   if (B == 0) return CC_OK;
-  const cc_code *rows = pc->rows, *cols = pc->cols;
-  const ProductShape s = product_shape(pc);
-  const int w1 = static_cast<int>(s.w1), w2 = static_cast<int>(s.w2);
-  const bool wg = (w1 > w2 ? w1 : w2) > 64;
-  const int t2 = rows->h_alg.nroots > cols->h_alg.nroots ? rows->h_alg.nroots : cols->h_alg.nroots;
-  const int col_bytes = bm_columns(t2).end;
-  const int block_bytes = 4 * hard_block(w1, w2, rows->h_alg.nroots / 2, cols->h_alg.nroots / 2).dwords;
-  const size_t lds = kHardTables + 4 * static_cast<size_t>(col_bytes) + (wg ? 1 : 4) * static_cast<size_t>(block_bytes);
-  if (lds > 64 * 1024) {  // once per device: 2t = 32 next to a block of 256 lines asks for more than the default limit
-    static std::mutex lock;
-    static unsigned long long done = 0;
-    const unsigned dev = static_cast<unsigned>(rows->device) & 63u;
-    std::lock_guard<std::mutex> g(lock);
-    if (!((done >> dev) & 1ull)) {
-      const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&product_hard_kernel<true>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (attr != hipSuccess) return hip_fail(attr, "product hard kernel LDS attribute");
-      done |= 1ull << dev;
-    }
+  const cc_code *rows = pc->rows;
+  const ProductLaunch pl = product_launch(pc, 2, 1);
+  if (pl.lds > 64 * 1024) {  // 2t = 32 next to a block of 256 lines asks for more than the default limit
+    static LdsOptIn once;
+    if (int rc = lds_opt_in(reinterpret_cast<const void *>(&product_hard_kernel<true>), once, rows->device, 160 * 1024,
+                            "product hard kernel LDS attribute"))
+      return rc;
   }
-  const unsigned long long want = wg ? B : (static_cast<unsigned long long>(B) + 3) / 4;
-  const unsigned long long cap = static_cast<unsigned long long>(rows->num_cus) * 8;
-  const dim3 grid(static_cast<unsigned>(want < cap ? want : cap));
-  const auto kernel = wg ? product_hard_kernel<true> : product_hard_kernel<false>;
-  hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, rows->d_alg, cols->d_alg, d_in, d_out, d_nflip, d_last, d_status,
-                     static_cast<unsigned long long>(B), static_cast<int>(pc->halves), s.e, col_bytes);
+  const dim3 grid(capped_grid(rows, pl.wg ? B : (static_cast<unsigned long long>(B) + 3) / 4));
+  const auto kernel = pl.wg ? product_hard_kernel<true> : product_hard_kernel<false>;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), pl.lds, stream, rows->d_alg, pc->cols->d_alg, d_in, d_out, d_nflip, d_last,
+                     d_status, static_cast<unsigned long long>(B), static_cast<int>(pc->halves), pl.e, pl.col_bytes);
   const hipError_t err = hipGetLastError();
   return err != hipSuccess ? hip_fail(err, "product hard kernel launch") : CC_OK;
 }

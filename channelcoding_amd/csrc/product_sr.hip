@@ -1,10 +1,10 @@
 // product_sr.hip -- iterated bounded-distance decoding with scaled reliability (iBDD-SR) of product codes, all
 // half-iterations of a block in one launch.  The contract is stated at cc_product_decode_sr in the public
-// header; the data path and the two shapes (WG = false: a wavefront per block up to 64 lines, four blocks per workgroup;
-// WG = true: a workgroup per block up to 256 lines) are those of product_hard.hip, and the line rule is hard_lines.hpp's
-// line_flips, untouched.  Here is what differs.
+// header.  The block's frame and its two shapes, the line rule (line_flips, untouched), the flips into a tile and into
+// the crossing lines' states and the end of a block are hard_lines.hpp's, shared with product_hard.hip.  Here is what
+// differs.
 //
-// Tiles of one block, each [w2][P] dwords at the odd pitch of product_hard.hip:
+// Tiles of one block, each [w2][P] dwords at hard_lines.hpp's odd pitch:
 //   Z     the hard decisions z = (y < 0), as loaded
 //   Dif   x_h ^ z: what the block differs from the channel in.  out = Z ^ Dif, nflip = popcount(Dif)
 //   Pl    up to four bit planes of a bit's level c = #{j : !(|y| < u_j)} over the sorted distinct weights u_0 < .. < u_(D-1)
@@ -23,8 +23,6 @@
 // one of the two quiet passes and changes nothing either.  Under (0, 0, inf, inf) stop_from is 2.
 //
 // Global traffic per block: 4 N bytes in, N bytes out, three int32.
-#include <mutex>
-
 #include "hard_lines.hpp"
 
 namespace ccamd {
@@ -65,8 +63,7 @@ int product_sr_schedule(const float *weights, uint32_t halves, SrSchedule *s) {
 
 namespace {
 
-constexpr int kHardTables = 2 * kSoftTables;  // the tables of `rows`, then those of `cols`
-constexpr uint32_t kArgHalves = 128;          // half-iterations whose levels travel in the kernel's arguments
+constexpr uint32_t kArgHalves = 128;  // half-iterations whose levels travel in the kernel's arguments
 // The largest admitted case, 256 x 256 lines with 2t = 32 both ways and four planes: tables 3072, Berlekamp-Massey
 // columns 50176, seven tiles 64512, ctl 16, states and their copy 20480 = 138256 bytes
 constexpr size_t kProductSrLds = 160 * 1024;
@@ -76,17 +73,6 @@ struct SrArgs {
   int D, np, stop_from;
   uint32_t lv[kArgHalves / 8];  // four bits per half-iteration
 };
-
-// the LDS of one block, in dwords: Dif, Z, Wk and np planes [w2][P], ctl [4], the line states of product_hard.hip (bytes
-// at a pitch of whole dwords, rows then columns) and their copy as computed from z
-struct SrBlock {
-  int P, pitch_r, pitch_c, tile, states, dwords;
-};
-__host__ __device__ constexpr SrBlock sr_block(int w1, int w2, int tr, int tc, int np) {
-  const int P = ((w1 + 31) >> 5) | 1, pitch_r = (tr + 4) & ~3, pitch_c = (tc + 4) & ~3;
-  const int states = (w2 * pitch_r + w1 * pitch_c) / 4;
-  return SrBlock{P, pitch_r, pitch_c, w2 * P, states, (3 + np) * w2 * P + 4 + 2 * states};
-}
 
 // 32 bits of the weak tile: level <= T, the level's bits in np planes a tile apart
 __device__ __forceinline__ uint32_t weak_bits(const uint32_t *Pl, int tile, int np, int T) {
@@ -115,44 +101,22 @@ product_sr_kernel(const AlgebraicTables *__restrict__ Tr, const AlgebraicTables 
                   const uint8_t *__restrict__ d_lv) {
   constexpr int NC = WG ? 4 : 1;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  stage_ex(Tr, smem);
-  stage_log16(Tr, reinterpret_cast<uint16_t *>(smem + 1024));
-  stage_ex(Tc, smem + kSoftTables);
-  stage_log16(Tc, reinterpret_cast<uint16_t *>(smem + kSoftTables + 1024));
-  __syncthreads();
-
-  const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int line = WG ? static_cast<int>(threadIdx.x) : lane, threads = WG ? 256 : 64;
-  const int n1 = Tr->n, n2 = Tc->n, w1 = n1 + e, w2 = n2 + e;
-  const int PD = (w1 + 31) >> 5, P = PD | 1, chunks = (w1 + 63) >> 6;
-  const unsigned long long N = static_cast<unsigned long long>(w1) * w2;
-  const int nnr = Tr->nf, nnc = Tc->nf, tr = Tr->nroots / 2, tc = Tc->nroots / 2;
   const int np = a.np, D = a.D;
-  const SrBlock lay = sr_block(w1, w2, tr, tc, np);
-  const int pitch_r = lay.pitch_r, pitch_c = lay.pitch_c, tile = lay.tile;
-  uint8_t *colbase = smem + kHardTables + wid * col_bytes;
-  uint32_t *Dif = reinterpret_cast<uint32_t *>(smem + kHardTables + 4 * col_bytes) + (WG ? 0 : wid * lay.dwords);
-  uint32_t *Z = Dif + tile, *Wk = Z + tile, *Pl = Wk + tile;
-  uint32_t *ctl = Pl + np * tile;  // ctl: [0] last, [1] a line that is no word, [2] nflip
-  uint8_t *SR = reinterpret_cast<uint8_t *>(ctl + 4), *SC = SR + w2 * pitch_r;
-  const int s0 = 4 * lay.states;  // from a line's state to its copy
-  const auto sync = [] {
-    if constexpr (WG)
-      __syncthreads();
-    else
-      wave_sync();
-  };
+  // the LDS of one block: the tiles Dif, Z, Wk and np planes, ctl, the line states and their copy as computed from z
+  const ProductFrame f = product_frame<WG>(Tr, Tc, smem, e, col_bytes, 3 + np, 2);
+  const int lane = f.lane, line = f.line, w1 = f.w1, w2 = f.w2, PD = f.PD, P = f.P, row_step = f.row_step;
+  const int tile = w2 * P;
+  uint32_t *Dif = f.tiles, *Z = Dif + tile, *Wk = Z + tile, *Pl = Wk + tile, *ctl = f.ctl;
+  const int s0 = f.states;  // from a line's state to its copy
   const auto level = [&](int h) -> int {
     return d_lv ? static_cast<int>(d_lv[h]) : static_cast<int>((a.lv[h >> 3] >> (4 * (h & 7))) & 15u);
   };
-  const int row0 = WG ? wid : 0, row_step = WG ? 4 : 1;  // the rows a wavefront loads and stores
 
-  const unsigned long long start = WG ? blockIdx.x : blockIdx.x * 4ull + wid, stride = WG ? gridDim.x : gridDim.x * 4ull;
-  for (unsigned long long b = start; b < B; b += stride) {
+  for (unsigned long long b = f.start; b < B; b += f.stride) {
     // ---------------- load: floats -> the bits of z and of the level ----------------
-    const float *src = in + b * N;
+    const float *src = in + b * f.N;
     constexpr int U = 4;
-    for (int r = row0; r < w2; r += row_step * U) {
+    for (int r = f.row0; r < w2; r += row_step * U) {
       float v[U][NC];
 #pragma unroll
       for (int u = 0; u < U; ++u)
@@ -171,68 +135,59 @@ product_sr_kernel(const AlgebraicTables *__restrict__ Tr, const AlgebraicTables 
           int lev = 0;
           for (int j = 0; j < D; ++j) lev += (mag < a.u[j]) ? 0 : 1;
           if (!valid) lev = 0;
-          const bool store = rr < w2 && lane < 2 && 2 * c + lane < PD;
-          const int at = rr * P + 2 * c + lane;
+          const int at = rr * P;
           const unsigned long long m = __ballot(valid && v[u][c] < 0.0f);
-          if (store) {
-            Z[at] = static_cast<uint32_t>(lane ? m >> 32 : m);
-            Dif[at] = 0u;
+          if (rr < w2) {
+            store_ballot(Z + at, PD, lane, c, m);
+            store_ballot(Dif + at, PD, lane, c, 0ull);
           }
           for (int p = 0; p < np; ++p) {
             const unsigned long long mp = __ballot(((lev >> p) & 1) != 0);
-            if (store) Pl[p * tile + at] = static_cast<uint32_t>(lane ? mp >> 32 : mp);
+            if (rr < w2) store_ballot(Pl + p * tile + at, PD, lane, c, mp);
           }
         }
     }
     if (line < 4) ctl[line] = 0;
-    sync();
+    block_sync<WG>();
 
     // ---------------- the state of every line from z, kept twice; the weak bits of the first pass ----------------
     for (int dir = 0; dir < 2; ++dir) {
-      const bool column = dir != 0;
-      const uint8_t *ex = smem + (column ? kSoftTables : 0);
-      const int n = column ? n2 : n1, nn = column ? nnc : nnr, t = column ? tc : tr;
-      const bool have_line = line < (column ? w1 : w2);
+      const Side s = side_of(f, dir != 0);
+      const bool have_line = line < s.lines;
       unsigned long long lb[NC];
-      gather_line<NC>(Z, P, PD, w2, column, have_line, line, lb);
+      gather_line<NC>(Z, P, PD, w2, dir != 0, have_line, line, lb);
       if (have_line) {
-        uint8_t *S = (column ? SC : SR) + line * (column ? pitch_c : pitch_r);
-        for (int m = 0; m <= t; ++m) {
-          const uint8_t s = m < t ? static_cast<uint8_t>(line_syndrome<NC>(ex, lb, n, nn, 2 * m + 1))
-                                  : static_cast<uint8_t>(count_bits<NC>(lb) & 1);
-          S[m] = s;
-          S[s0 + m] = s;
+        uint8_t *S = s.S + line * s.pitch;
+        for (int m = 0; m <= s.t; ++m) {
+          const uint8_t v = m < s.t ? static_cast<uint8_t>(line_syndrome<NC>(s.ex, lb, s.n, s.nn, 2 * m + 1))
+                                    : static_cast<uint8_t>(count_bits<NC>(lb) & 1);
+          S[m] = v;
+          S[s0 + m] = v;
         }
       }
     }
     int lev = level(0);
-    for (int i = line; i < w2 * PD; i += threads) {
-      const int at = (i / PD) * P + i % PD;
-      Wk[at] = weak_bits(Pl + at, tile, np, lev);
-    }
-    sync();
+    each_tile_dword(f, [&](int at) { Wk[at] = weak_bits(Pl + at, tile, np, lev); });
+    block_sync<WG>();
 
     // ---------------- the half-iterations ----------------
     for (int h = 0; h < halves; ++h) {
       const bool column = (h & 1) != 0;
-      const uint8_t *ex = smem + (column ? kSoftTables : 0);
-      const uint16_t *lg2 = reinterpret_cast<const uint16_t *>(ex + 1024);
-      const int n = column ? n2 : n1, nn = column ? nnc : nnr, t = column ? tc : tr;
-      const BmColumns bm = bm_columns(2 * t);
-      uint16_t *SL = reinterpret_cast<uint16_t *>(colbase + bm.SL);
-      uint16_t *LL = reinterpret_cast<uint16_t *>(colbase + bm.LL);
-      uint16_t *BL = reinterpret_cast<uint16_t *>(colbase + bm.BL);
-      const bool have_line = line < (column ? w1 : w2);
-      uint8_t *S = (column ? SC : SR) + line * (column ? pitch_c : pitch_r);
+      const Side s = side_of(f, column), o = side_of(f, !column);
+      const uint8_t *ex = s.ex;
+      const int n = s.n, nn = s.nn, t = s.t;
+      const BmColumns bm = bm_columns(2 * s.t);
+      uint16_t *SL = reinterpret_cast<uint16_t *>(f.cols + bm.SL);
+      uint16_t *LL = reinterpret_cast<uint16_t *>(f.cols + bm.LL);
+      uint16_t *BL = reinterpret_cast<uint16_t *>(f.cols + bm.BL);
+      const bool have_line = line < s.lines;
+      uint8_t *S = s.S + line * s.pitch;
 
       unsigned long long fm[NC];  // positions the line rule changes at
-      line_flips<NC>(ex, lg2, SL, LL, BL, S, have_line, lane, n, nn, t, e, fm);
+      line_flips<NC>(ex, s.lg2, SL, LL, BL, S, have_line, lane, n, nn, t, e, fm);
       // a taken word exists: the line itself where its syndromes are zero (line_flips then mends at most the parity bit),
       // else a candidate that was not refused, which flips at least one bit
-      bool nz = false;
-      if (have_line)
-        for (int m = 0; m < t; ++m) nz = nz || S[m] != 0;
-      const bool taken = have_line && (!nz || any_bit<NC>(fm));
+      const bool taken = have_line && (!state_nonzero(S, t) || any_bit<NC>(fm));
       unsigned long long d[NC], wk[NC], flip[NC];
       gather_line<NC>(Dif, P, PD, w2, column, have_line, line, d);
       gather_line<NC>(Wk, P, PD, w2, column, have_line, line, wk);
@@ -242,7 +197,7 @@ product_sr_kernel(const AlgebraicTables *__restrict__ Tr, const AlgebraicTables 
         fm[c] ^= flip[c];  // where taken: the positions at which the new line differs from the word
       }
       const bool changed = any_bit<NC>(flip);
-      sync();  // every line of the pass has been read
+      block_sync<WG>();  // every line of the pass has been read
       if (changed) {
         // the line's own state: that of the reverted positions, or that of the z line
         if (taken) {
@@ -266,39 +221,7 @@ product_sr_kernel(const AlgebraicTables *__restrict__ Tr, const AlgebraicTables 
         } else {
           for (int m = 0; m <= t; ++m) S[m] = S[s0 + m];
         }
-        // every flipped bit is position `line` of a line of the other direction, whose state takes alpha^(j line) and
-        // the parity
-        const uint8_t *exo = smem + (column ? 0 : kSoftTables);
-        uint32_t *So = reinterpret_cast<uint32_t *>(column ? SR : SC);
-        const int no = column ? n1 : n2, nno = column ? nnr : nnc, to = column ? tr : tc, pitch_o = column ? pitch_r : pitch_c;
-        const uint32_t step2 = line < no ? addmod(line, line, nno) : 0u;
-        const int kw = line >> 5;
-        const uint32_t bit = 1u << (line & 31);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          if (!column) {
-            if (2 * c < PD) Dif[line * P + 2 * c] ^= static_cast<uint32_t>(flip[c]);
-            if (2 * c + 1 < PD) Dif[line * P + 2 * c + 1] ^= static_cast<uint32_t>(flip[c] >> 32);
-          }
-          unsigned long long m = flip[c];
-          while (m) {
-            const int k = 64 * c + __builtin_ctzll(m);
-            m &= m - 1ull;
-            if (column) atomicXor(&Dif[k * P + kw], bit);
-            if (line < no) {
-              uint32_t ev = static_cast<uint32_t>(line);
-              for (int j = 0; j < to; ++j) {
-                const int idx = k * pitch_o + j;
-                atomicXor(&So[idx >> 2], static_cast<uint32_t>(exo[ev]) << (8 * (idx & 3)));
-                ev = addmod(ev, step2, nno);
-              }
-            }
-            if (e) {
-              const int idx = k * pitch_o + to;
-              atomicXor(&So[idx >> 2], 1u << (8 * (idx & 3)));
-            }
-          }
-        }
+        apply_flips<NC>(Dif, f, column, flip, o, e);
         atomicMax(&ctl[0], static_cast<uint32_t>(h + 1));
       }
       // the weak bits of the next pass (those of this one have been gathered)
@@ -306,57 +229,17 @@ product_sr_kernel(const AlgebraicTables *__restrict__ Tr, const AlgebraicTables 
         const int next = level(h + 1);
         if (next != lev) {
           lev = next;
-          for (int i = line; i < w2 * PD; i += threads) {
-            const int at = (i / PD) * P + i % PD;
-            Wk[at] = weak_bits(Pl + at, tile, np, lev);
-          }
+          each_tile_dword(f, [&](int at) { Wk[at] = weak_bits(Pl + at, tile, np, lev); });
         }
       }
-      sync();
+      block_sync<WG>();
       // two quiet passes whose levels every later pass repeats; the same value in every lane of the block
       if (h > a.stop_from && h + 1 - static_cast<int>(ctl[0]) >= 2) break;
     }
 
-    // ---------------- status: every row and every column a word of its code ----------------
-    bool bad = false;
-    if (line < w2)
-      for (int m = 0; m < tr + e; ++m) bad = bad || SR[line * pitch_r + m] != 0;
-    if (line < w1)
-      for (int m = 0; m < tc + e; ++m) bad = bad || SC[line * pitch_c + m] != 0;
-    if (bad) atomicOr(&ctl[1], 1u);
-    uint32_t diff = 0;
-    for (int i = line; i < w2 * PD; i += threads) diff += static_cast<uint32_t>(__builtin_popcount(Dif[(i / PD) * P + i % PD]));
-    if (diff) atomicAdd(&ctl[2], diff);
-    sync();
-
-    // ---------------- store: bits -> bytes ----------------
-    uint8_t *dst = out + b * N;
-    for (int r = row0; r < w2; r += row_step)
-      for (int c = 0; c < chunks; ++c) {
-        const int col = 64 * c + lane;
-        if (col < w1) {
-          const int at = r * P + (col >> 5);
-          dst[static_cast<unsigned long long>(r) * w1 + col] = static_cast<uint8_t>(((Z[at] ^ Dif[at]) >> (col & 31)) & 1u);
-        }
-      }
-    if (line == 0) {
-      if (nflip_out) nflip_out[b] = static_cast<int32_t>(ctl[2]);
-      if (last_out) last_out[b] = static_cast<int32_t>(ctl[0]);
-      if (status_out) status_out[b] = ctl[1] ? CC_FRAME_NOT_CONVERGED : CC_FRAME_OK;
-    }
-    sync();  // the next block overwrites the tiles, the states and ctl
+    product_finish<WG>(f, b, e, out, nflip_out, last_out, status_out, [&](int at) { return Dif[at]; },
+                       [&](int at) { return Z[at] ^ Dif[at]; });
   }
-}
-
-size_t sr_lds_bytes(const cc_product *pc, int np, int *col_bytes) {
-  const cc_code *rows = pc->rows, *cols = pc->cols;
-  const ProductShape s = product_shape(pc);
-  const int w1 = static_cast<int>(s.w1), w2 = static_cast<int>(s.w2);
-  const bool wg = (w1 > w2 ? w1 : w2) > 64;
-  const int t2 = rows->h_alg.nroots > cols->h_alg.nroots ? rows->h_alg.nroots : cols->h_alg.nroots;
-  *col_bytes = bm_columns(t2).end;
-  const int block_bytes = 4 * sr_block(w1, w2, rows->h_alg.nroots / 2, cols->h_alg.nroots / 2, np).dwords;
-  return kHardTables + 4 * static_cast<size_t>(*col_bytes) + (wg ? 1 : 4) * static_cast<size_t>(block_bytes);
 }
 
 }  // namespace
@@ -365,8 +248,6 @@ int launch_product_sr(const cc_product *pc, const SrSchedule &sched, const float
                       int32_t *d_last, int32_t *d_status, size_t B, hipStream_t stream) {
   if (B == 0) return CC_OK;
   const cc_code *rows = pc->rows;
-  const ProductShape s = product_shape(pc);
-  const bool wg = (s.w1 > s.w2 ? s.w1 : s.w2) > 64;
   const uint32_t halves = pc->halves;
   SrArgs a{};
   a.D = sched.D;
@@ -391,27 +272,17 @@ int launch_product_sr(const cc_product *pc, const SrSchedule &sched, const float
   }
   pack(0);
 
-  int col_bytes;
-  const size_t lds = sr_lds_bytes(pc, a.np, &col_bytes);
-  if (lds > 64 * 1024) {  // once per device and shape: more than the default limit
-    static std::mutex lock;
-    static unsigned long long done[2] = {0, 0};
-    const unsigned dev = static_cast<unsigned>(rows->device) & 63u;
-    std::lock_guard<std::mutex> g(lock);
-    if (!((done[wg] >> dev) & 1ull)) {
-      const void *fn = wg ? reinterpret_cast<const void *>(&product_sr_kernel<true>)
-                          : reinterpret_cast<const void *>(&product_sr_kernel<false>);
-      const hipError_t attr = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kProductSrLds));
-      if (attr != hipSuccess) return hip_fail(attr, "product sr kernel LDS attribute");
-      done[wg] |= 1ull << dev;
-    }
+  const ProductLaunch pl = product_launch(pc, 3 + a.np, 2);
+  const auto kernel = pl.wg ? product_sr_kernel<true> : product_sr_kernel<false>;
+  if (pl.lds > 64 * 1024) {  // more than the default limit
+    static LdsOptIn once[2];
+    if (int rc = lds_opt_in(reinterpret_cast<const void *>(kernel), once[pl.wg], rows->device, static_cast<int>(kProductSrLds),
+                            "product sr kernel LDS attribute"))
+      return rc;
   }
-  const unsigned long long want = wg ? B : (static_cast<unsigned long long>(B) + 3) / 4;
-  const unsigned long long cap = static_cast<unsigned long long>(rows->num_cus) * 8;
-  const dim3 grid(static_cast<unsigned>(want < cap ? want : cap));
-  const auto kernel = wg ? product_sr_kernel<true> : product_sr_kernel<false>;
-  hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, rows->d_alg, pc->cols->d_alg, d_y, d_out, d_nflip, d_last, d_status,
-                     static_cast<unsigned long long>(B), static_cast<int>(halves), s.e, col_bytes, a,
+  const dim3 grid(capped_grid(rows, pl.wg ? B : (static_cast<unsigned long long>(B) + 3) / 4));
+  hipLaunchKernelGGL(kernel, grid, dim3(256), pl.lds, stream, rows->d_alg, pc->cols->d_alg, d_y, d_out, d_nflip, d_last, d_status,
+                     static_cast<unsigned long long>(B), static_cast<int>(halves), pl.e, pl.col_bytes, a,
                      static_cast<const uint8_t *>(d_lv));
   const hipError_t err = hipGetLastError();
   return err != hipSuccess ? hip_fail(err, "product sr kernel launch") : CC_OK;

@@ -2,12 +2,14 @@
 // bounded-distance decoder of a whole stream in one launch, and the block-by-block encoder.  The contract is stated at
 // cc_staircase in the public header; here is how it is mapped.
 //
+// What it shares with the product decoders is hard_lines.hpp's: the tile and the state of a line, the line rule, what a
+// flipped bit adds to the state of a crossing line, the load through ballots.  Here is what differs.
+//
 // One workgroup of 256 threads owns a stream from its first block to its last.  The window is a ring of W tiles in LDS:
-// block i lives in tile i mod W as bits, m rows of P dwords, P = ceil(m / 32) | 1 odd (product_hard.hip's tile).  Tile 0
-// starts as B_0 = 0.  Next to every tile lies the state of the step of the same number: for each of its m lines the t odd
-// syndromes and the parity of the line's bits, at a pitch of whole dwords.  W states, not W - 1: step b is no longer
-// decoded at position b, but block b still changes there (the lines of step b + 1 run down its columns), and `status` needs
-// the syndromes of step b when block b leaves.
+// block i lives in tile i mod W as bits, m rows of P = tile_pitch(m) dwords.  Tile 0 starts as B_0 = 0.  Next to every
+// tile lies the state of the step of the same number, one line state for each of its m lines.  W states, not W - 1:
+// step b is no longer decoded at position b, but block b still changes there (the lines of step b + 1 run down its
+// columns), and `status` needs the syndromes of step b when block b leaves.
 //
 //   entering   a block is loaded through ballots (64 bytes -> one 64-bit mask); the state of its step is computed once,
 //              one lane per line, from the column of the block before and the row of the block itself
@@ -22,8 +24,6 @@
 //   leaving    the state of step b gives its part of `status`, the tile goes out as bytes and is compared with `in` on
 //              the way (still intact for that block, in place too)
 // A position stops after two successive half-passes without a change: the state then repeats, no output can show it.
-#include <mutex>
-
 #include "hard_lines.hpp"
 
 namespace ccamd {
@@ -35,7 +35,7 @@ struct StairLayout {
   int P, pitch, tile, state, dwords;
 };
 __host__ __device__ constexpr StairLayout stair_layout(int m, int t, int W) {
-  const int P = ((m + 31) >> 5) | 1, pitch = (t + 4) & ~3;
+  const int P = tile_pitch(m), pitch = state_pitch(t);
   return StairLayout{P, pitch, m * P, m * pitch / 4, 4 + W * (m * P + m * pitch / 4)};
 }
 constexpr size_t stair_lds_bytes(int m, int t, int W) {
@@ -79,34 +79,13 @@ staircase_kernel(const AlgebraicTables *__restrict__ T, const uint8_t *in, uint8
   const auto state = [&](int step) { return states + (step % W) * (4 * lay.state); };
   const int pw = (m - 1) >> 5, pb = (m - 1) & 31;  // the parity column of a block
 
-  // a flip at position `pos` of line `line` of the step whose states are S32 (pos < 0: the parity position)
-  const auto flip_state = [&](uint32_t *S32, int line, int pos) {
-    if (pos >= 0) {
-      const uint32_t step2 = addmod(pos, pos, nn);
-      uint32_t ev = static_cast<uint32_t>(pos);
-      for (int k = 0; k < t; ++k) {
-        const int idx = line * pitch + k;
-        atomicXor(&S32[idx >> 2], static_cast<uint32_t>(ex[ev]) << (8 * (idx & 3)));
-        ev = addmod(ev, step2, nn);
-      }
-    }
-    if (e) {
-      const int idx = line * pitch + t;
-      atomicXor(&S32[idx >> 2], 1u << (8 * (idx & 3)));
-    }
-  };
-
   for (unsigned long long s = blockIdx.x; s < B; s += gridDim.x) {
     const uint8_t *src = in + s * N;
     uint8_t *dst = out + s * N;
 
     // block `blk` leaves: step blk's part of the status, bits -> bytes, its part of nflip
     const auto retire = [&](int blk) {
-      const uint8_t *S = state(blk);
-      bool bad = false;
-      if (tid < m)
-        for (int k = 0; k < t + e; ++k) bad = bad || S[tid * pitch + k] != 0;
-      if (bad) atomicOr(&ctl[1], 1u);
+      if (tid < m && state_nonzero(state(blk) + tid * pitch, t + e)) atomicOr(&ctl[1], 1u);
       const uint32_t *X = tile(blk);
       const unsigned long long off = static_cast<unsigned long long>(blk - 1) * mm;
       uint32_t diff = 0;
@@ -134,25 +113,7 @@ staircase_kernel(const AlgebraicTables *__restrict__ T, const uint8_t *in, uint8
       for (int blk = loaded + 1; blk <= top; ++blk) {
         const uint8_t *sb = src + static_cast<unsigned long long>(blk - 1) * mm;
         uint32_t *X = tile(blk);
-        constexpr int U = 4;  // (U rows at a time: all their loads are issued before the first ballot waits for one)
-        for (int r = wid; r < m; r += 4 * U) {
-          uint32_t v[U][CB];
-#pragma unroll
-          for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int c = 0; c < CB; ++c) {
-              const int rr = r + 4 * u, col = 64 * c + lane;
-              v[u][c] = (rr < m && col < m) ? sb[static_cast<unsigned long long>(rr) * m + col] : 0u;
-            }
-#pragma unroll
-          for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int c = 0; c < CB; ++c) {
-              const int rr = r + 4 * u;
-              const unsigned long long mask = __ballot((v[u][c] & 1u) != 0);
-              if (rr < m && lane < 2 && 2 * c + lane < PD) X[rr * P + 2 * c + lane] = static_cast<uint32_t>(lane ? mask >> 32 : mask);
-            }
-        }
+        load_bit_rows<4, CB>(sb, m, m, wid, 4, lane, [&](int r, int c, unsigned long long mask) { store_ballot(X + r * P, PD, lane, c, mask); });
       }
       if (tid == 0) ctl[0] = 0;
       __syncthreads();
@@ -177,9 +138,7 @@ staircase_kernel(const AlgebraicTables *__restrict__ T, const uint8_t *in, uint8
           if (e && (n >> 6) == c) acc |= static_cast<unsigned long long>((Xi[pw] >> pb) & 1u) << (n & 63);
           lb[c] = acc;
         }
-        uint8_t *S = state(i) + j * pitch;
-        for (int k = 0; k < t; ++k) S[k] = static_cast<uint8_t>(line_syndrome<NC>(ex, lb, n, nn, 2 * k + 1));
-        S[t] = static_cast<uint8_t>(count_bits<NC>(lb) & 1);
+        line_state<NC>(state(i) + j * pitch, ex, lb, n, nn, t);
       }
       loaded = top;
       __syncthreads();
@@ -221,11 +180,12 @@ staircase_kernel(const AlgebraicTables *__restrict__ T, const uint8_t *in, uint8
                 if (p < me || p == n) {  // B_i[j][col]
                   const int col = p < me ? p : m - 1;
                   atomicXor(&Xi[j * P + (col >> 5)], 1u << (col & 31));
-                  if (next) flip_state(Sn, col, me + j);
+                  if (next) flip_state(Sn, ex, col, pitch, me + j, odd_step(me + j, nn), t, nn, e);
                 } else {  // B_(i-1)[a][j], i - 1 >= 1 by the rule above
                   const int a = p - me;
                   atomicXor(&Xp[a * P + (j >> 5)], 1u << (j & 31));
-                  flip_state(Sp, a, j < me ? j : -1);
+                  const int pos = j < me ? j : -1;
+                  flip_state(Sp, ex, a, pitch, pos, odd_step(pos, nn), t, nn, e);
                 }
               }
             }
@@ -243,10 +203,7 @@ staircase_kernel(const AlgebraicTables *__restrict__ T, const uint8_t *in, uint8
     }
     for (int blk = b_last > 1 ? b_last : 1; blk <= L; ++blk) retire(blk);
     __syncthreads();
-    if (tid == 0) {
-      if (nflip_out) nflip_out[s] = static_cast<int32_t>(ctl[2]);
-      if (status_out) status_out[s] = ctl[1] ? CC_FRAME_NOT_CONVERGED : CC_FRAME_OK;
-    }
+    if (tid == 0) store_results(nflip_out, nullptr, status_out, s, ctl);
     __syncthreads();  // the next stream overwrites the ring and ctl
   }
 }
@@ -295,10 +252,7 @@ staircase_extract_kernel(const uint8_t *__restrict__ cw, uint8_t *__restrict__ m
   }
 }
 
-unsigned flat_grid(const cc_code *code, unsigned long long items) {
-  const unsigned long long want = (items + 255) / 256, cap = static_cast<unsigned long long>(code->num_cus) * 8;
-  return static_cast<unsigned>(want < 1 ? 1 : want < cap ? want : cap);
-}
+unsigned flat_grid(const cc_code *code, unsigned long long items) { return capped_grid(code, (items + 255) / 256); }
 
 }  // namespace
 
@@ -328,22 +282,13 @@ int launch_staircase_decode(const cc_staircase *sc, const uint8_t *d_in, uint8_t
   const bool wide = 2 * s.m > 64;
   const int col_bytes = bm_columns(static_cast<int>(code->tab.roots.size()) & ~1).end;
   const size_t lds = staircase_lds_bytes(sc);
-  if (lds > 64 * 1024) {  // once per device and kernel: a long window of large blocks asks for more than the default limit
-    static std::mutex lock;
-    static unsigned long long done[2] = {0, 0};
-    const unsigned dev = static_cast<unsigned>(code->device) & 63u;
-    std::lock_guard<std::mutex> g(lock);
-    if (!((done[wide] >> dev) & 1ull)) {
-      const void *fn = wide ? reinterpret_cast<const void *>(&staircase_kernel<4>) : reinterpret_cast<const void *>(&staircase_kernel<1>);
-      const hipError_t attr = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (attr != hipSuccess) return hip_fail(attr, "staircase kernel LDS attribute");
-      done[wide] |= 1ull << dev;
-    }
-  }
-  const unsigned long long cap = static_cast<unsigned long long>(code->num_cus) * 8;
-  const dim3 grid(static_cast<unsigned>(B < cap ? B : cap));
   const auto kernel = wide ? staircase_kernel<4> : staircase_kernel<1>;
-  hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, code->d_alg, d_in, d_out, d_nflip, d_status,
+  if (lds > 64 * 1024) {  // a long window of large blocks asks for more than the default limit
+    static LdsOptIn once[2];
+    if (int rc = lds_opt_in(reinterpret_cast<const void *>(kernel), once[wide], code->device, 160 * 1024, "staircase kernel LDS attribute"))
+      return rc;
+  }
+  hipLaunchKernelGGL(kernel, dim3(capped_grid(code, B)), dim3(256), lds, stream, code->d_alg, d_in, d_out, d_nflip, d_status,
                      static_cast<unsigned long long>(B), static_cast<int>(s.L), static_cast<int>(sc->window),
                      static_cast<int>(sc->iters), s.e, col_bytes);
   const hipError_t err = hipGetLastError();
