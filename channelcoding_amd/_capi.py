@@ -210,6 +210,13 @@ _SIGNATURES = {
                                         _VP, _VP]),
     "cc_mc_run_staircase_dev": (C.c_int, [C.POINTER(Staircase), C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, _VP,
                                           _VP]),
+    "cc_staircase_decode_sr": (C.c_int, [C.POINTER(Staircase), _VP, _VP, _VP, _VP, _VP, C.c_size_t]),
+    "cc_staircase_decode_sr_dev": (C.c_int, [C.POINTER(Staircase), _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "cc_staircase_sr_lds_bytes": (C.c_size_t, [C.POINTER(Staircase), _VP]),
+    "cc_awgn_staircase_values_dev": (C.c_int, [C.POINTER(Staircase), C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int,
+                                               _VP, _VP, _VP]),
+    "cc_mc_run_staircase_sr_dev": (C.c_int, [C.POINTER(Staircase), _VP, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t,
+                                             C.c_int, _VP, _VP]),
     "cc_product_decode_hard": (C.c_int, [C.POINTER(Product), _VP, _VP, _VP, _VP, _VP, C.c_size_t]),
     "cc_product_decode_hard_dev": (C.c_int, [C.POINTER(Product), _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "cc_mc_run_product_hard_dev": (C.c_int, [C.POINTER(Product), C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int,

@@ -43,7 +43,9 @@ sliding-window hard-decision decoder (montecarlo.staircase_simulation): --k and 
 the component code -- with --extended its extended code, otherwise the code shortened by one position, so that a line has
 an even number of bits -- streams of L blocks, a window of W = 2 .. 16 blocks and I iterations per window position.  There
 is no default for the three.  ber is taken over the blocks decoded with a full window; the log is
-"staircase(<code>[-ext], L=.., W=.., I=..).log".
+"staircase(<code>[-ext], L=.., W=.., I=..).log".  With --weights a,b,... the ladder runs the window decoder with scaled
+reliability (montecarlo.staircase_sr_simulation), exactly 2 I weights, one per half-pass of a window position (inf is a
+weight), and the log is "staircase(<code>[-ext], L=.., W=.., I=..)-sr.log".
 """
 import argparse
 import sys
@@ -51,7 +53,8 @@ import time
 
 from . import codes as cc
 from .montecarlo import (awgn_simulation, bitflip_simulation, burst_simulation, discrete_simulation, product_hard_simulation,
-                         product_simulation, product_sr_simulation, staircase_simulation)
+                         product_simulation, product_sr_simulation, staircase_simulation,
+                         staircase_sr_simulation)
 
 POWERS = (5, 6, 7)
 DISTANCES = (3, 5, 7, 9)
@@ -130,6 +133,8 @@ def usage_text():
               "                             in place of --alpha and --beta.",
               "--weights <a,b,...>          product: iBDD with scaled reliability, one weight per half-iteration (inf is",
               "                             one), in place of --alpha, --beta and --halves.",
+              "                             staircase: the window decoder with scaled reliability, exactly 2 * iters",
+              "                             weights, one per half-pass of a window position.",
               "--blocks <num>               staircase: blocks per stream. There is no default.",
               "--window <num>               staircase: the decoder's window in blocks, 2 .. 16. There is no default.",
               "--iters <num>                staircase: iterations per window position. There is no default.",
@@ -303,6 +308,23 @@ def staircase_arguments(args):
     return k, d, args.blocks, args.window, args.iters
 
 
+def staircase_sr_arguments(args):
+    """(k, dmin, blocks, window, iters, weights) of --simulation staircase --weights a,b,..., or a message saying what is
+    wrong"""
+    parsed = staircase_arguments(args)
+    if isinstance(parsed, str):
+        return parsed
+    try:
+        weights = [float(v) for v in args.weights.split(",")]
+    except ValueError:
+        return "--weights takes numbers, one per half-pass"
+    if any(w != w or w < 0 for w in weights):
+        return "--weights takes weights >= 0 (inf is one)"
+    if len(weights) != 2 * parsed[4]:
+        return "--weights takes one weight per half-pass of a window position: 2 * iters = %d" % (2 * parsed[4])
+    return parsed + (weights,)
+
+
 def build_staircase(k, d, blocks, window, iters, extended, device=None):
     """the component shortened by one position where the line would otherwise have an odd number of bits"""
     kw = {} if device is None else {"device": device}
@@ -314,7 +336,8 @@ def build_staircase(k, d, blocks, window, iters, extended, device=None):
 
 
 def staircase_main(args):
-    parsed = staircase_arguments(args)
+    sr = getattr(args, "weights", None) is not None
+    parsed = staircase_sr_arguments(args) if sr else staircase_arguments(args)
     if isinstance(parsed, str):
         print(parsed, file=sys.stderr)
         print(usage_text())
@@ -322,12 +345,15 @@ def staircase_main(args):
     seed = time.time_ns() if args.seed_time else args.seed
     dist = join_ranks()
     try:
-        sc = build_staircase(*parsed, args.extended)
+        sc = build_staircase(*parsed[:5], args.extended)
     except ValueError as err:
         print("--simulation staircase: %s" % err, file=sys.stderr)
         return 1
     t0 = time.perf_counter()
-    res = staircase_simulation(sc, seed=seed, log_dir=args.log_dir, max_samples=args.max_samples)()
+    if sr:
+        res = staircase_sr_simulation(sc, parsed[5], seed=seed, log_dir=args.log_dir, max_samples=args.max_samples)()
+    else:
+        res = staircase_simulation(sc, seed=seed, log_dir=args.log_dir, max_samples=args.max_samples)()
     if not dist or dist.get_rank() == 0:
         print("%s: %d streams in %.2f s" % (sc.to_string(), sum(r["frames"] for r in res), time.perf_counter() - t0), flush=True)
     if dist:
@@ -365,7 +391,8 @@ def main(argv=None):
     ap.add_argument("--alpha", default=None, help="product: a,b,... one per half-iteration")
     ap.add_argument("--beta", default=None, help="product: a,b,... one per half-iteration")
     ap.add_argument("--halves", type=int, default=None, help="product: hard-decision decoding, this many half-iterations")
-    ap.add_argument("--weights", default=None, help="product: iBDD-SR, a,b,... one weight per half-iteration")
+    ap.add_argument("--weights", default=None, help="product: iBDD-SR, a,b,... one weight per half-iteration; staircase: the window decoder with scaled "
+                         "reliability, exactly 2 * iters weights")
     ap.add_argument("--blocks", type=int, default=None, help="staircase: blocks per stream")
     ap.add_argument("--window", type=int, default=None, help="staircase: window of the decoder in blocks")
     ap.add_argument("--iters", type=int, default=None, help="staircase: iterations per window position")

@@ -1276,9 +1276,18 @@ class staircase_code:
     def sigma(self, ebno_db):
         return capi.lib().cc_staircase_sigma(C.byref(self._sc()), float(ebno_db))
 
-    def lds_bytes(self):
-        """LDS of one workgroup of the decoder"""
-        return capi.lib().cc_staircase_lds_bytes(C.byref(self._sc()))
+    def lds_bytes(self, weights=None):
+        """LDS of one workgroup of the decoder; with weights (2 * iters of them), of the soft-aided decoder under them"""
+        if weights is None:
+            return capi.lib().cc_staircase_lds_bytes(C.byref(self._sc()))
+        return capi.lib().cc_staircase_sr_lds_bytes(C.byref(self._sc()), self._weights(weights))
+
+    def _weights(self, weights):
+        """the weights of an iBDD-SR call as C floats: one per half-pass of a window position"""
+        fw = _sr_weights(weights)
+        if len(fw) != 2 * self.iters:
+            raise ValueError("one weight per half-pass of a window position: 2 * iters = %d" % (2 * self.iters))
+        return fw
 
     def _bytes(self, x, inner, what):
         """x as contiguous uint8 streams of shape (B,) + inner"""
@@ -1324,15 +1333,48 @@ class staircase_code:
         out, nflip, status = self.correct_batch(z)
         return self.extract_batch(out), nflip, status
 
-    def channel(self, ebno_db, seed, first_stream, streams, random_codewords=False):
+    def correct_sr_batch(self, y, weights):
+        """cc_staircase_decode_sr: y (B, blocks, m, m) float32 channel values -> dict(out=, nflip=, status=) of the
+        sliding-window decoder with scaled reliability, weights[h] the threshold below which |y| yields to the component
+        decoder in half-pass h of every window position (inf: always), 2 * iters of them; numpy array or device tensor."""
+        fw = self._weights(weights)
+        sc = self._sc()
+        sc._keep = (self.code, fw)
+        if len(y.shape) != 4 or tuple(y.shape[1:]) != (self.blocks, self.m, self.m):
+            raise CcError(capi.ERR_LENGTH, "correct_sr_batch")
+        yy = _side(y).as_type(y, "f", np.float32)
+        if yy is None:
+            raise TypeError("staircase decoding with scaled reliability takes float32 channel values")
+        B = yy.shape[0]
+        side = _side(yy)
+        res = {"out": side.alloc(yy, (B, self.blocks, self.m, self.m), np.uint8), "nflip": side.alloc(yy, (B,), np.int32),
+               "status": side.alloc(yy, (B,), np.int32)}
+        cyclic._batch_call(_product_handle(sc), "cc_staircase_decode_sr", [yy], B, res, head=[fw])
+        return res
+
+    def decode_sr_batch(self, y, weights):
+        """correct_sr_batch plus msg (B, blocks, m, k_b): the message bits of out"""
+        res = self.correct_sr_batch(y, weights)
+        res["msg"] = self.extract_batch(res["out"])
+        return res
+
+    def channel(self, ebno_db, seed, first_stream, streams, random_codewords=False, values=False):
         """Streams [first_stream, first_stream + streams) of the AWGN channel on the current device, as hard decisions
-        (cc_awgn_staircase_dev): dict(z=, sent=) of (streams, blocks, m, m) uint8 torch tensors."""
+        (cc_awgn_staircase_dev): dict(z=, sent=) of (streams, blocks, m, m) uint8 torch tensors.  values=True: the channel
+        values whose signs they are (cc_awgn_staircase_values_dev), dict(y= float32, sent=)."""
         import torch
         streams = int(streams)
         dev = torch.device("cuda", torch.cuda.current_device())
         shape = (streams, self.blocks, self.m, self.m)
-        z = torch.empty(shape, dtype=torch.uint8, device=dev)
         sent = torch.empty(shape, dtype=torch.uint8, device=dev)
+        if values:
+            y = torch.empty(shape, dtype=torch.float32, device=dev)
+            rc = capi.lib().cc_awgn_staircase_values_dev(C.byref(self._sc()), float(ebno_db), int(seed), int(first_stream),
+                                                         streams, int(bool(random_codewords)), _ptr(y), _ptr(sent),
+                                                         _stream_handle(y))
+            capi.check(rc, "cc_awgn_staircase_values_dev")
+            return dict(y=y, sent=sent)
+        z = torch.empty(shape, dtype=torch.uint8, device=dev)
         rc = capi.lib().cc_awgn_staircase_dev(C.byref(self._sc()), float(ebno_db), int(seed), int(first_stream), streams,
                                               int(bool(random_codewords)), _ptr(z), _ptr(sent), _stream_handle(z))
         capi.check(rc, "cc_awgn_staircase_dev")

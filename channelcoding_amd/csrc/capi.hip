@@ -1964,6 +1964,82 @@ int cc_mc_run_staircase_dev(const cc_staircase *sc, double ebno_db, uint64_t see
                           static_cast<hipStream_t>(stream));
 }
 
+// The refusals of cc_staircase_decode_sr(_dev) in the header's order, and the schedule of the weights; the Monte-Carlo
+// call has no arrays
+static int staircase_sr_supported(const cc_staircase *sc, const float *weights, const float *y, const uint8_t *out, size_t B,
+                                  bool arrays, SrSchedule *sched) {
+  if (!sc || !sc->code || !weights) return CC_ERR_INVALID_ARGUMENT;
+  if (arrays && B && (!y || !out)) return CC_ERR_INVALID_ARGUMENT;
+  if (sc->iters > UINT32_MAX / 2) return CC_ERR_INVALID_ARGUMENT;  // 2 iters half-passes
+  const int rc = staircase_supported(sc, true, false, nullptr, nullptr, B);  // the numbers, the handle, the shape
+  if (rc != CC_OK && rc != CC_ERR_NO_DEVICE) return rc;
+  if (int bad = product_sr_schedule(weights, 2 * sc->iters, sched)) return bad;
+  const size_t lds = staircase_sr_lds_bytes(sc, sched->D);
+  if (lds > 160 * 1024) {
+    set_last_error("cc_staircase_decode_sr: the window asks for " + std::to_string(lds) + " bytes of LDS, a workgroup has " +
+                   std::to_string(160 * 1024));
+    return CC_ERR_UNSUPPORTED;
+  }
+  if (arrays) {
+    const size_t N = staircase_shape(sc).N;
+    if (ranges_overlap(y, B * N * sizeof(float), out, B * N)) return CC_ERR_INVALID_ARGUMENT;
+  }
+  return rc;
+}
+
+int cc_staircase_decode_sr_dev(const cc_staircase *sc, const float *weights, const float *d_y, uint8_t *d_out, int32_t *d_nflip,
+                               int32_t *d_status, size_t B, void *stream) {
+  SrSchedule sched;
+  if (int rc = staircase_sr_supported(sc, weights, d_y, d_out, B, true, &sched)) return rc;
+  DeviceGuard guard(sc->code->device);
+  return launch_staircase_sr(sc, sched, d_y, d_out, d_nflip, d_status, B, static_cast<hipStream_t>(stream));
+}
+
+int cc_staircase_decode_sr(const cc_staircase *sc, const float *weights, const float *y, uint8_t *out, int32_t *nflip,
+                           int32_t *status, size_t B) {
+  SrSchedule sched;
+  if (int rc = staircase_sr_supported(sc, weights, y, out, B, true, &sched)) return rc;
+  if (B == 0) return CC_OK;
+  const StaircaseShape s = staircase_shape(sc);
+  DeviceGuard guard(sc->code->device);
+  // a stream is the frame of the chunk loop
+  const StagedStream streams[] = {stage_in(0, y, s.N * sizeof(float)), stage_out(1, out, s.N), stage_out(2, nflip, sizeof(int32_t)),
+                                  stage_out(3, status, sizeof(int32_t))};
+  return staged_call(sc->code, B, s.N * sizeof(float), 1, streams, 4, nullptr, nullptr,
+                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t st) {
+                       return launch_staircase_sr(sc, sched, static_cast<const float *>(d[0]), static_cast<uint8_t *>(d[1]),
+                                                  static_cast<int32_t *>(d[2]), static_cast<int32_t *>(d[3]), m, st);
+                     });
+}
+
+size_t cc_staircase_sr_lds_bytes(const cc_staircase *sc, const float *weights) {
+  if (!staircase_readable(sc) || !weights || sc->window < 2 || sc->window > CC_STAIRCASE_MAX_WINDOW || sc->iters == 0 ||
+      sc->iters > UINT32_MAX / 2)
+    return 0;
+  SrSchedule sched;
+  if (product_sr_schedule(weights, 2 * sc->iters, &sched) != CC_OK) return 0;
+  return staircase_sr_lds_bytes(sc, sched.D);
+}
+
+int cc_awgn_staircase_values_dev(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64_t first_stream, size_t streams,
+                                 int random_codewords, float *d_y, uint8_t *d_sent, void *stream) {
+  if (!sc || !sc->code || (streams && !d_y)) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = staircase_supported(sc, false, false, nullptr, nullptr, streams)) return rc;
+  DeviceGuard guard(sc->code->device);
+  return staircase_awgn_values(sc, ebno_db, seed, first_stream, streams, random_codewords, d_y, d_sent,
+                               static_cast<hipStream_t>(stream));
+}
+
+int cc_mc_run_staircase_sr_dev(const cc_staircase *sc, const float *weights, double ebno_db, uint64_t seed, uint64_t first_stream,
+                               size_t streams, int random_codewords, uint64_t *d_counters, void *stream) {
+  if (!sc || !sc->code || !weights || !d_counters) return CC_ERR_INVALID_ARGUMENT;
+  SrSchedule sched;
+  if (int rc = staircase_sr_supported(sc, weights, nullptr, nullptr, streams, false, &sched)) return rc;
+  DeviceGuard guard(sc->code->device);
+  return mc_run_staircase_sr(sc, sched, ebno_db, seed, first_stream, streams, random_codewords, d_counters,
+                             static_cast<hipStream_t>(stream));
+}
+
 // the discrete channels serve every q <= 8 handle the decoders serve; the checks of the two entry points
 static int discrete_supported(const cc_code *code, double p_error, double p_erasure, int random_codewords) {
   if (!std::isfinite(p_error) || !std::isfinite(p_erasure) || p_error < 0.0 || p_erasure < 0.0 ||

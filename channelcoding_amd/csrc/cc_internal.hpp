@@ -433,6 +433,18 @@ int staircase_awgn(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64
 // product.hip: the Monte-Carlo route of the product codes with a stream as the block; counts over the blocks 1 .. L_c
 int mc_run_staircase(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64_t first_stream, size_t streams,
                      int random_codewords, uint64_t *d_counters, hipStream_t stream);
+// staircase.hip: the same streams as channel values y; their signs are the bytes of staircase_awgn
+int staircase_awgn_values(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64_t first_stream, size_t streams,
+                          int random_codewords, float *d_y, uint8_t *d_sent, hipStream_t stream);
+// staircase_sr.hip: iBDD-SR through the window; sc and the schedule (product_sr_schedule at 2 iters
+// half-passes) checked by the caller.  LDS of a workgroup under D distinct weights; d_nflip and d_status may be nullptr
+size_t staircase_sr_lds_bytes(const cc_staircase *sc, int D);
+int launch_staircase_sr(const cc_staircase *sc, const SrSchedule &sched, const float *d_y, uint8_t *d_out, int32_t *d_nflip,
+                        int32_t *d_status, size_t B, hipStream_t stream);
+// product.hip: the float route around launch_staircase_sr; counts over the blocks 1 .. L_c, the channel's flips from the
+// signs of y among them
+int mc_run_staircase_sr(const cc_staircase *sc, const SrSchedule &sched, double ebno_db, uint64_t seed, uint64_t first_stream,
+                        size_t streams, int random_codewords, uint64_t *d_counters, hipStream_t stream);
 // mc.hip (Monte-Carlo calls on one handle must be issued on one stream at a time: they share a workspace)
 int mc_run(cc_code *code, double ebno_db, uint64_t seed, uint64_t first_frame, size_t frames, int random_codewords,
            uint64_t *d_counters, hipStream_t stream);

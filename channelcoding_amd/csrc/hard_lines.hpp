@@ -1,7 +1,8 @@
-// hard_lines.hpp -- what the iterated bounded-distance decoders share (product_hard.hip, product_sr.hip, staircase.hip;
-// DESIGN 4.17 - 4.19).  Each of these is spelled out here only:
+// hard_lines.hpp -- what the iterated bounded-distance decoders share (product_hard.hip, product_sr.hip, staircase.hip,
+// staircase_sr.hip).  Each of these is spelled out here only:
 //   layout      tile_pitch, state_pitch; product_block, the LDS of one block of a product code
-//   a line      up to 64 NC bits held by one lane: gather_line from a bit tile, line_syndrome and line_state from the bits
+//   a line      up to 64 NC bits held by one lane: gather_line from a bit tile, line_syndrome and line_state from the bits;
+//               bit_range and clamp64 for the two halves of a staircase line
 //   the rule    line_flips, the line rule of cc_product_decode_hard: from the line's state in LDS (t odd syndromes, then
 //               the parity of all its bits) to the positions at which the line changes
 //   flips       flip_state, what one flipped bit adds to the state of the line that crosses it; apply_flips, a row or
@@ -68,6 +69,13 @@ __device__ __forceinline__ int count_bits(const unsigned long long (&m)[NC]) {
   for (int c = 0; c < NC; ++c) cnt += __builtin_popcountll(m[c]);
   return cnt;
 }
+
+// bits [lo, hi) of a 64-bit word, 0 <= lo, hi <= 64
+__device__ __forceinline__ unsigned long long bit_range(int lo, int hi) {
+  const unsigned long long upto_hi = hi >= 64 ? ~0ull : (1ull << hi) - 1ull, upto_lo = lo >= 64 ? ~0ull : (1ull << lo) - 1ull;
+  return hi > lo ? upto_hi & ~upto_lo : 0ull;
+}
+__device__ __forceinline__ int clamp64(int v) { return v < 0 ? 0 : v > 64 ? 64 : v; }
 
 // the bits of line `line` of a bit tile X[w2][P] (bit k & 31 of X[i][k >> 5] = x(i, k)): row `line` (w1 bits, PD dwords)
 // or column `line` (w2 bits)

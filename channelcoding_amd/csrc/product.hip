@@ -117,9 +117,12 @@ resize_rows_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, in
 
 // decided: B blocks of N bytes; sent: the blocks sent (nullptr: the all-zero word); status: `lines` entries per block;
 // last: the half-iterations a block took, one per block, into CC_MC_ITER_SUM and the histogram slot of the block (one
-// atomic of its own), or nullptr: both are left alone
+// atomic of its own), or nullptr: both are left alone; received: what the channel gave, hard decisions or y itself
+__device__ __forceinline__ unsigned decision(uint8_t z) { return z; }
+__device__ __forceinline__ unsigned decision(float y) { return y < 0.0f ? 1u : 0u; }
+template <class R>
 __global__ void __launch_bounds__(256)
-product_count_kernel(const uint8_t *__restrict__ decided, const uint8_t *__restrict__ sent, const uint8_t *__restrict__ received,
+product_count_kernel(const uint8_t *__restrict__ decided, const uint8_t *__restrict__ sent, const R *__restrict__ received,
                      const int32_t *__restrict__ status, const int32_t *__restrict__ last, unsigned long long N,
                      unsigned long long Ncount, int lines, unsigned long long blocks, unsigned long long *__restrict__ counters) {
   const int lane = threadIdx.x & 63;
@@ -132,9 +135,9 @@ product_count_kernel(const uint8_t *__restrict__ decided, const uint8_t *__restr
     unsigned cnt = 0;
     for (unsigned long long i = lane; i < Ncount; i += 64) cnt += (d[i] != (s ? s[i] : 0)) ? 1u : 0u;
     if (received) {  // the channel's flips among the values compared (a route whose channel launch does not count them)
-      const uint8_t *z = received + b * N;
+      const R *z = received + b * N;
       unsigned flips = 0;
-      for (unsigned long long i = lane; i < Ncount; i += 64) flips += (z[i] != (s ? s[i] : 0)) ? 1u : 0u;
+      for (unsigned long long i = lane; i < Ncount; i += 64) flips += (decision(z[i]) != (s ? s[i] : 0u)) ? 1u : 0u;
       for (int m = 32; m >= 1; m >>= 1) flips += static_cast<unsigned>(__shfl_xor(static_cast<int>(flips), m, 64));
       c_chan += flips;
     }
@@ -317,11 +320,12 @@ struct BlockRoute {
 
 // d_sent == nullptr: the all-zero block; d_received: nullptr unless the count takes the channel's flips; d_status: `lines`
 // entries per block; d_last: one per block or nullptr
-static int launch_block_count(const BlockRoute &r, const uint8_t *d_decided, const uint8_t *d_sent, const uint8_t *d_received,
+template <class R>
+static int launch_block_count(const BlockRoute &r, const uint8_t *d_decided, const uint8_t *d_sent, const R *d_received,
                               const int32_t *d_status, const int32_t *d_last, size_t lines, size_t B, uint64_t *d_counters,
                               hipStream_t stream) {
   if (B == 0) return CC_OK;
-  hipLaunchKernelGGL(product_count_kernel, dim3(grid_of(r.code, (static_cast<unsigned long long>(B) + 3) / 4)), dim3(256), 0,
+  hipLaunchKernelGGL(product_count_kernel<R>, dim3(grid_of(r.code, (static_cast<unsigned long long>(B) + 3) / 4)), dim3(256), 0,
                      stream, d_decided, d_sent, d_received, d_status, d_last, static_cast<unsigned long long>(r.N),
                      static_cast<unsigned long long>(r.Ncount), static_cast<int>(lines), static_cast<unsigned long long>(B),
                      reinterpret_cast<unsigned long long *>(d_counters));
@@ -403,7 +407,7 @@ static int mc_block_route(const BlockRoute &r, uint64_t seed, uint64_t first_blo
     CC_HIP_TRY(scratch.get(&msg, chunk * r.K));
   }
   // (the channel launch counts its flips over all N values; a route that compares fewer leaves them to the count)
-  const bool channel_counts = !hard || in_place;
+  const bool channel_counts = hard ? in_place : r.Ncount == r.N;
   unsigned long long *counters = channel_counts ? reinterpret_cast<unsigned long long *>(d_counters) : nullptr;
   for (size_t done = 0; done < blocks; done += chunk) {
     const size_t m = blocks - done < chunk ? blocks - done : chunk;
@@ -416,7 +420,7 @@ static int mc_block_route(const BlockRoute &r, uint64_t seed, uint64_t first_blo
       rc = launch_awgn_values(r.code, static_cast<int>(r.N), r.sigma, seed, first_block + done, m, received, sent, stream, counters);
     if (rc != CC_OK) return rc;
     if ((rc = decode(m, received, decided, status, last)) != CC_OK) return rc;
-    const uint8_t *flips = channel_counts ? nullptr : reinterpret_cast<const uint8_t *>(received);
+    const T *flips = channel_counts ? nullptr : received;
     if ((rc = launch_block_count(r, decided, sent, flips, status, last, lines, m, d_counters, stream)) != CC_OK) return rc;
   }
   return CC_OK;
@@ -463,21 +467,37 @@ int mc_run_product_sr(const cc_product *pc, const SrSchedule &sched, double ebno
 
 // the staircase decoder (staircase.hip) through the same route, a stream as the block: one status per stream, the count
 // over the blocks that were decoded with a full window ahead of them
-int mc_run_staircase(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64_t first_stream, size_t streams,
-                     int random_codewords, uint64_t *d_counters, hipStream_t stream) {
+static BlockRoute staircase_route(const cc_staircase *sc, double ebno_db) {
   const StaircaseShape s = staircase_shape(sc);
   const size_t counted = s.L >= sc->window ? s.L - sc->window + 1 : s.L;
   // a chunk of a stream per compute unit where that stays within 2^28 values (2^27 at m = 128, L = 32)
   const size_t fit = (size_t(1) << 28) / s.N, cus = static_cast<size_t>(sc->code->num_cus);
-  const BlockRoute route{sc->code, s.N, s.K, counted * s.m * s.m, static_cast<float>(cc_staircase_sigma(sc, ebno_db)), false,
-                         fit < cus ? fit : cus};
-  const auto sent_of = [&](uint64_t first, size_t m, uint8_t *msg, uint8_t *sent) {
-    if (int rc = launch_random_bits(sc->code, static_cast<int>(s.K), seed, first, m, msg, stream)) return rc;
+  return BlockRoute{sc->code, s.N, s.K, counted * s.m * s.m, static_cast<float>(cc_staircase_sigma(sc, ebno_db)), false,
+                    fit < cus ? fit : cus};
+}
+static auto staircase_sent_of(const cc_staircase *sc, uint64_t seed, hipStream_t stream) {
+  return [=](uint64_t first, size_t m, uint8_t *msg, uint8_t *sent) {
+    if (int rc = launch_random_bits(sc->code, static_cast<int>(staircase_shape(sc).K), seed, first, m, msg, stream)) return rc;
     return launch_staircase_encode(sc, msg, sent, m, stream);
   };
-  return mc_block_route<uint8_t>(route, seed, first_stream, streams, random_codewords, 1, false, d_counters, stream, sent_of,
+}
+int mc_run_staircase(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64_t first_stream, size_t streams,
+                     int random_codewords, uint64_t *d_counters, hipStream_t stream) {
+  return mc_block_route<uint8_t>(staircase_route(sc, ebno_db), seed, first_stream, streams, random_codewords, 1, false, d_counters,
+                                 stream, staircase_sent_of(sc, seed, stream),
                                  [&](size_t m, const uint8_t *z, uint8_t *decided, int32_t *status, int32_t *) {
     return launch_staircase_decode(sc, z, decided, nullptr, status, m, stream);
+  });
+}
+
+// the soft-aided decoder of the same streams (staircase_sr.hip): the channel's floats, whose signs give the channel's
+// flips over the counted blocks
+int mc_run_staircase_sr(const cc_staircase *sc, const SrSchedule &sched, double ebno_db, uint64_t seed, uint64_t first_stream,
+                        size_t streams, int random_codewords, uint64_t *d_counters, hipStream_t stream) {
+  return mc_block_route<float>(staircase_route(sc, ebno_db), seed, first_stream, streams, random_codewords, 1, false, d_counters,
+                               stream, staircase_sent_of(sc, seed, stream),
+                               [&](size_t m, const float *y, uint8_t *decided, int32_t *status, int32_t *) {
+    return launch_staircase_sr(sc, sched, y, decided, nullptr, status, m, stream);
   });
 }
 

@@ -23,7 +23,7 @@
 // one of the two quiet passes and changes nothing either.  Under (0, 0, inf, inf) stop_from is 2.
 //
 // Global traffic per block: 4 N bytes in, N bytes out, three int32.
-#include "hard_lines.hpp"
+#include "sr_levels.hpp"
 
 namespace ccamd {
 
@@ -63,35 +63,9 @@ int product_sr_schedule(const float *weights, uint32_t halves, SrSchedule *s) {
 
 namespace {
 
-constexpr uint32_t kArgHalves = 128;  // half-iterations whose levels travel in the kernel's arguments
 // The largest admitted case, 256 x 256 lines with 2t = 32 both ways and four planes: tables 3072, Berlekamp-Massey
 // columns 50176, seven tiles 64512, ctl 16, states and their copy 20480 = 138256 bytes
 constexpr size_t kProductSrLds = 160 * 1024;
-
-struct SrArgs {
-  float u[CC_PRODUCT_SR_MAX_LEVELS];
-  int D, np, stop_from;
-  uint32_t lv[kArgHalves / 8];  // four bits per half-iteration
-};
-
-// 32 bits of the weak tile: level <= T, the level's bits in np planes a tile apart
-__device__ __forceinline__ uint32_t weak_bits(const uint32_t *Pl, int tile, int np, int T) {
-  uint32_t gt = 0, eq = ~0u;
-  for (int j = np - 1; j >= 0; --j) {
-    const uint32_t p = Pl[j * tile];
-    if ((T >> j) & 1) {
-      eq &= p;
-    } else {
-      gt |= eq & p;
-      eq &= ~p;
-    }
-  }
-  return ~gt;
-}
-
-__global__ void __launch_bounds__(128) sr_levels_kernel(uint8_t *dst, SrArgs a, uint32_t count) {
-  if (threadIdx.x < count) dst[threadIdx.x] = static_cast<uint8_t>((a.lv[threadIdx.x >> 3] >> (4 * (threadIdx.x & 7))) & 15u);
-}
 
 template <bool WG>
 __global__ void __launch_bounds__(256)
@@ -108,9 +82,7 @@ product_sr_kernel(const AlgebraicTables *__restrict__ Tr, const AlgebraicTables 
   const int tile = w2 * P;
   uint32_t *Dif = f.tiles, *Z = Dif + tile, *Wk = Z + tile, *Pl = Wk + tile, *ctl = f.ctl;
   const int s0 = f.states;  // from a line's state to its copy
-  const auto level = [&](int h) -> int {
-    return d_lv ? static_cast<int>(d_lv[h]) : static_cast<int>((a.lv[h >> 3] >> (4 * (h & 7))) & 15u);
-  };
+  const auto level = [&](int h) { return sr_level(a, d_lv, h); };
 
   for (unsigned long long b = f.start; b < B; b += f.stride) {
     // ---------------- load: floats -> the bits of z and of the level ----------------
@@ -249,28 +221,11 @@ int launch_product_sr(const cc_product *pc, const SrSchedule &sched, const float
   if (B == 0) return CC_OK;
   const cc_code *rows = pc->rows;
   const uint32_t halves = pc->halves;
-  SrArgs a{};
-  a.D = sched.D;
-  a.stop_from = static_cast<int>(sched.stop_from);
-  for (a.np = 1; (1 << a.np) <= sched.D; ++a.np) {}  // the levels 0 .. D
-  for (int j = 0; j < sched.D; ++j) a.u[j] = sched.u[j];
-  const auto pack = [&](uint32_t from) {
-    for (uint32_t &w : a.lv) w = 0;
-    for (uint32_t h = from; h < halves && h < from + kArgHalves; ++h)
-      a.lv[(h - from) >> 3] |= static_cast<uint32_t>(sched.level[h]) << (4 * ((h - from) & 7));
-  };
-  // more half-iterations than the arguments hold: their levels go to the workspace, 128 per launch of a copy kernel
+  // more half-iterations than the arguments hold: their levels go to the workspace (sr_levels.hpp)
   Scratch scratch(rows, stream);
+  SrArgs a;
   uint8_t *d_lv = nullptr;
-  if (halves > kArgHalves) {
-    CC_HIP_TRY(scratch.get(&d_lv, halves));
-    for (uint32_t from = 0; from < halves; from += kArgHalves) {
-      pack(from);
-      hipLaunchKernelGGL(sr_levels_kernel, dim3(1), dim3(128), 0, stream, d_lv + from, a,
-                         halves - from < kArgHalves ? halves - from : kArgHalves);
-    }
-  }
-  pack(0);
+  if (int rc = sr_arguments(sched, halves, scratch, stream, &a, &d_lv)) return rc;
 
   const ProductLaunch pl = product_launch(pc, 3 + a.np, 2);
   const auto kernel = pl.wg ? product_sr_kernel<true> : product_sr_kernel<false>;

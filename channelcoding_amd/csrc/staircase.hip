@@ -24,6 +24,8 @@
 //   leaving    the state of step b gives its part of `status`, the tile goes out as bytes and is compared with `in` on
 //              the way (still intact for that block, in place too)
 // A position stops after two successive half-passes without a change: the state then repeats, no output can show it.
+#include <type_traits>
+
 #include "hard_lines.hpp"
 
 namespace ccamd {
@@ -43,13 +45,6 @@ constexpr size_t stair_lds_bytes(int m, int t, int W) {
 }
 // no admitted shape exceeds m = 128 (q <= 8) with t = 16 (2t <= 32) and sixteen blocks
 static_assert(stair_lds_bytes(128, 16, CC_STAIRCASE_MAX_WINDOW) <= 160 * 1024, "the window must fit the LDS of a workgroup");
-
-// bits [lo, hi) of a 64-bit word, 0 <= lo, hi <= 64
-__device__ __forceinline__ unsigned long long bit_range(int lo, int hi) {
-  const unsigned long long upto_hi = hi >= 64 ? ~0ull : (1ull << hi) - 1ull, upto_lo = lo >= 64 ? ~0ull : (1ull << lo) - 1ull;
-  return hi > lo ? upto_hi & ~upto_lo : 0ull;
-}
-__device__ __forceinline__ int clamp64(int v) { return v < 0 ? 0 : v > 64 ? 64 : v; }
 
 // NC = 1: lines of up to 64 bits (m <= 32); NC = 4: up to 256 bits
 template <int NC>
@@ -330,18 +325,26 @@ int launch_staircase_extract(const cc_staircase *sc, const uint8_t *d_cw, uint8_
   return err != hipSuccess ? hip_fail(err, "staircase extract kernel launch") : CC_OK;
 }
 
-// streams [first_stream, first_stream + streams) of the channel as hard decisions, in the chunks of the product routes
-// (product_chunk_blocks): random messages, the encoder, launch_awgn_hard at N = L m m values per stream
-int staircase_awgn(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64_t first_stream, size_t streams,
-                   int random_codewords, uint8_t *d_z, uint8_t *d_sent, hipStream_t stream) {
+// streams [first_stream, first_stream + streams) of the channel, in the chunks of the product routes
+// (product_chunk_blocks): random messages, the encoder, then at N = L m m values per stream launch_awgn_hard (T = uint8_t:
+// the hard decisions) or launch_awgn_values (T = float: y itself, whose signs they are)
+template <class T>
+static int staircase_channel(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64_t first_stream, size_t streams,
+                             int random_codewords, T *d_recv, uint8_t *d_sent, hipStream_t stream) {
   if (streams == 0) return CC_OK;
   const cc_code *code = sc->code;
   const StaircaseShape s = staircase_shape(sc);
   const float sigma = static_cast<float>(cc_staircase_sigma(sc, ebno_db));
   const int N = static_cast<int>(s.N);
+  const auto draw = [&](uint64_t first, size_t m, T *recv, const uint8_t *sent) {
+    if constexpr (std::is_same<T, float>::value)
+      return launch_awgn_values(code, N, sigma, seed, first, m, recv, sent, stream);
+    else
+      return launch_awgn_hard(code, N, sigma, seed, first, m, recv, sent, stream);
+  };
   if (!random_codewords) {
     if (d_sent) CC_HIP_TRY(hipMemsetAsync(d_sent, 0, streams * s.N, stream));
-    return launch_awgn_hard(code, N, sigma, seed, first_stream, streams, d_z, nullptr, stream);
+    return draw(first_stream, streams, d_recv, nullptr);
   }
   const size_t chunk = product_chunk_blocks(s.N, streams);
   Scratch scratch(code, stream);
@@ -353,9 +356,18 @@ int staircase_awgn(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64
     uint8_t *sent = d_sent ? d_sent + done * s.N : words;
     if (int rc = launch_random_bits(code, static_cast<int>(s.K), seed, first_stream + done, m, msg, stream)) return rc;
     if (int rc = launch_staircase_encode(sc, msg, sent, m, stream)) return rc;
-    if (int rc = launch_awgn_hard(code, N, sigma, seed, first_stream + done, m, d_z + done * s.N, sent, stream)) return rc;
+    if (int rc = draw(first_stream + done, m, d_recv + done * s.N, sent)) return rc;
   }
   return CC_OK;
+}
+
+int staircase_awgn(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64_t first_stream, size_t streams,
+                   int random_codewords, uint8_t *d_z, uint8_t *d_sent, hipStream_t stream) {
+  return staircase_channel(sc, ebno_db, seed, first_stream, streams, random_codewords, d_z, d_sent, stream);
+}
+int staircase_awgn_values(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64_t first_stream, size_t streams,
+                          int random_codewords, float *d_y, uint8_t *d_sent, hipStream_t stream) {
+  return staircase_channel(sc, ebno_db, seed, first_stream, streams, random_codewords, d_y, d_sent, stream);
 }
 
 }  // namespace ccamd

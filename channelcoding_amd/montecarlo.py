@@ -246,6 +246,19 @@ class StaircaseBackend(DeviceBackend):
         self.desc = sc._sc()
 
 
+class StaircaseSrBackend(DeviceBackend):
+    """Counts one shard of streams of one Eb/N0 point through cc_mc_run_staircase_sr_dev: a staircase_code under its
+    sliding-window decoder with scaled reliability (codes.staircase_code.correct_sr_batch), 2 * iters weights."""
+
+    symbol = "cc_mc_run_staircase_sr_dev"
+
+    def __init__(self, sc, weights, random_codewords=False):
+        super().__init__(sc, random_codewords)
+        self.weights = sc._weights(weights)
+        self.desc = sc._sc()
+        self.leading = (self.weights,)
+
+
 class _ShardedSimulation:
     """What the AWGN, the discrete-channel and the burst-channel ladders share: the shard of this rank, the one all-reduce per point,
     rank 0's log file (its success agreed with every rank before the first collective) and the adaptive ladder."""
@@ -481,6 +494,24 @@ class staircase_simulation(_EbnoLadder):
 
     def __call__(self):
         return self._ladder(self.code.to_string() + ".log", "ebno", lambda ebno: ebno)
+
+
+class staircase_sr_simulation(staircase_simulation):
+    """The Eb/N0 ladder of a staircase code under its sliding-window decoder with scaled reliability
+    (cc_mc_run_staircase_sr_dev), one weight per half-pass of a window position: ladder, sharding by stream, wer and the
+    ber over the counted blocks of staircase_simulation.  The log is <sc.to_string()>-sr.log."""
+
+    def __init__(self, sc, weights, step=0.5, seed=0, random_codewords=False, backend=None, log_dir=None, max_samples=None,
+                 start=None, stop=None, samples_per_point=None):
+        self.weights = [float(w) for w in weights]
+        if len(self.weights) != 2 * sc.iters:
+            raise ValueError("one weight per half-pass of a window position: 2 * iters = %d" % (2 * sc.iters))
+        if backend is None:
+            backend = StaircaseSrBackend(sc, self.weights, random_codewords)
+        super().__init__(sc, step, seed, random_codewords, backend, log_dir, max_samples, start, stop, samples_per_point)
+
+    def __call__(self):
+        return self._ladder(self.code.to_string() + "-sr.log", "ebno", lambda ebno: ebno)
 
 
 # ---- discrete memoryless channels (cc_mc_run_discrete_dev): the BSC and BEC the reference's README leaves as a TODO --

@@ -618,8 +618,8 @@ int cc_mc_run_product_hard_dev(const cc_product *pc, double ebno_db, uint64_t se
  *        7. a CC_DEVICE_NONE handle -> CC_ERR_NO_DEVICE
  *      B = 0 answers CC_OK after these checks.  Buffers: natural alignment only, and nothing outside the stated extents
  *      is read into a result or written.  A call with more than 128 half-iterations takes `halves` bytes from the `rows`
- *      handle's workspace pool.  No staircase codes yet, no per-bit weights, no RS components, no q > 8, and no weight
- *      optimisation: the schedule is the caller's. ---- */
+ *      handle's workspace pool.  Staircase codes: cc_staircase_decode_sr.  No per-bit weights, no RS components, no q > 8,
+ *      and no weight optimisation: the schedule is the caller's. ---- */
 #define CC_PRODUCT_SR_MAX_LEVELS 15
 int cc_product_decode_sr(const cc_product *pc, const float *weights /* halves, host */, const float *y /* B*N */,
                          uint8_t *out /* B*N */, int32_t *nflip /* B or NULL */, int32_t *last /* B or NULL */,
@@ -676,7 +676,7 @@ int cc_mc_run_product_sr_dev(const cc_product *pc, const float *weights /* host 
  *        6. a CC_DEVICE_NONE handle -> CC_ERR_NO_DEVICE
  *      B = 0 answers CC_OK after these checks.  The host forms answer CC_ERR_NOT_IN_FIELD for a byte above 1.  Buffers:
  *      natural alignment only, nothing outside the stated extents is read into a result or written.  No RS components,
- *      no q > 8, no soft information, no termination, no window carried between calls. ---- */
+ *      no q > 8, no termination, no window carried between calls.  Soft-aided decoding: cc_staircase_decode_sr. ---- */
 #define CC_STAIRCASE_MAX_WINDOW 16
 typedef struct cc_staircase {
   const cc_code *code;   /* a handle cc_correct_chase_batch accepts */
@@ -716,6 +716,71 @@ int cc_awgn_staircase_dev(const cc_staircase *sc, double ebno_db, uint64_t seed,
  * stream at a time. */
 int cc_mc_run_staircase_dev(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64_t first_stream, size_t streams,
                             int random_codewords, uint64_t *d_counters, void *stream);
+
+/* ---- iBDD with scaled reliability (cc_product_decode_sr) of a staircase code through the sliding window of
+ *      cc_staircase_decode.  Of sc the fields code, extended, blocks, window and iters are read.  e, m, r, k_b, the
+ *      stream [L][m][m], the numbering of a line of a step, the window positions b = 0 .. b_last, top, the half-pass
+ *      schedule (the steps i with (top - i) = h mod 2) and the finality of block b are those of cc_staircase_decode, word
+ *      for word.  `weights` holds 2 * iters host floats, also in the _dev forms; weights[h] belongs to half-pass h of
+ *      every window position.
+ *        channel     y is [B][L][m][m] float32 and z = (y < 0) as bytes 0 / 1.  A bit is weak in half-pass h iff
+ *                    fabsf(y) < weights[h], compared in float32; NaN, -0.0, +-inf, a zero weight and an infinite weight
+ *                    behave as in cc_product_decode_sr.  B_0 is z = 0 and is never weak.
+ *        state       x = (B_0 = 0, z).  A block that enters the window enters as z.
+ *        half-pass   every line of the active steps is decoded from the state at the start of the half-pass by the line
+ *                    rule of cc_product_decode_hard.  A taken word c is the line itself where its syndromes are zero,
+ *                    with the parity bit mended where extended.  No line sees another line's result of the same
+ *                    half-pass.
+ *        B_0         a line of step 1 whose taken word differs from the line at a position of B_0 has no taken word: it
+ *                    takes the fallback.
+ *        taken word  at every position p of the 2m positions of the line, x'(p) = c(p) where c(p) == z(p) or p is weak in
+ *                    h, and x'(p) = z(p) otherwise; the tie |y| == w reverts.
+ *        fallback    no candidate, a candidate refused by d > t, or the B_0 rule: x'(p) = z(p) on the whole line, the
+ *                    column half in block i - 1 included.
+ *                    Clean lines are not inert: the formula runs for every line of every active step in every half-pass.
+ *        outputs     out = the final blocks 1 .. L as bytes; nflip = d_H(out, z); status as in cc_staircase_decode (every
+ *                    line of every step of out is a word of its code, step 1 against the zero block).  nflip and status
+ *                    (B int32 each) may be NULL.  out may not overlap y.
+ *      The device may stop a position only where no output can show it: after two successive half-passes without a
+ *      change (one without a step, W = 2 and h odd, is one), once every later half-pass of the schedule repeats the
+ *      weight of the one two before it.
+ *      Refused before a device is asked for, in this order:
+ *        1. NULL sc, code, weights, y or out -> CC_ERR_INVALID_ARGUMENT (y / out unless B = 0;
+ *           cc_mc_run_staircase_sr_dev: NULL sc, code, weights or counters first)
+ *        2. step 2 of cc_staircase_decode, or 2 * iters not representable in 32 bits -> CC_ERR_INVALID_ARGUMENT
+ *        3. what cc_correct_chase_batch refuses at p = 0, in its order and with its texts
+ *        4. n + e odd, or r >= m -> CC_ERR_INVALID_ARGUMENT with the texts of cc_staircase_decode
+ *        5. what cc_product_decode_sr refuses of `halves` = 2 * iters weights, with its texts: a NaN or negative weight
+ *           (-0.0 is not), or more than CC_PRODUCT_SR_MAX_LEVELS distinct values
+ *        6. a shape whose window does not fit the 160 KiB of LDS of a workgroup (cc_staircase_sr_lds_bytes; m = 128
+ *           through W = 16 is one) -> CC_ERR_UNSUPPORTED, cc_last_error naming the bytes asked for
+ *        7. out overlapping y -> CC_ERR_INVALID_ARGUMENT
+ *        8. a CC_DEVICE_NONE handle -> CC_ERR_NO_DEVICE
+ *      B = 0 answers CC_OK after these checks.  Buffers: natural alignment only, nothing outside the stated extents is
+ *      read into a result or written.  A call with more than 128 half-passes takes 2 * iters bytes from the handle's
+ *      workspace pool.  No weights per window slot or per bit, no weight optimisation, no RS components, no q > 8, no
+ *      termination, no window carried between calls. ---- */
+int cc_staircase_decode_sr(const cc_staircase *sc, const float *weights /* 2*iters, host */, const float *y /* B*L*m*m */,
+                           uint8_t *out /* B*L*m*m */, int32_t *nflip /* B or NULL */, int32_t *status /* B or NULL */, size_t B);
+int cc_staircase_decode_sr_dev(const cc_staircase *sc, const float *weights /* host */, const float *d_y, uint8_t *d_out,
+                               int32_t *d_nflip, int32_t *d_status, size_t B, void *stream);
+/* LDS bytes of one workgroup of cc_staircase_decode_sr for sc under `weights` (2 * iters host floats): tables,
+ * Berlekamp-Massey columns, per block of the window the tiles Z, x ^ z, the weak bits and ceil(log2(D + 1)) level planes for
+ * D distinct weights, and the line states twice.  Above 160 KiB the decoder refuses the shape.  0 for an sc or weights it
+ * cannot read. */
+size_t cc_staircase_sr_lds_bytes(const cc_staircase *sc, const float *weights);
+/* cc_awgn_staircase_dev with the channel values themselves: d_y (streams*L*m*m floats) receives the y whose signs are the
+ * bytes cc_awgn_staircase_dev writes; value v of global stream g is what cc_awgn_product_dev draws for value v of block g.
+ * d_sent may be NULL. */
+int cc_awgn_staircase_values_dev(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64_t first_stream, size_t streams,
+                                 int random_codewords, float *d_y, uint8_t *d_sent /* or NULL */, void *stream);
+/* Monte-Carlo of cc_staircase_decode_sr: by definition the counters equal what cc_awgn_staircase_values_dev,
+ * cc_staircase_decode_sr_dev and a comparison with the streams sent would count over the counted blocks 1 .. L_c.  The
+ * counters mean what they mean in cc_mc_run_staircase_dev, CC_MC_CHANNEL_BIT_ERRORS from the signs of y over the counted
+ * blocks; CC_MC_ITER_SUM and the histogram are not touched.  They depend only on (seed, ebno, sc, weights, the set of global
+ * streams).  Chunking and workspace follow cc_mc_run_staircase_dev. */
+int cc_mc_run_staircase_sr_dev(const cc_staircase *sc, const float *weights /* host */, double ebno_db, uint64_t seed,
+                               uint64_t first_stream, size_t streams, int random_codewords, uint64_t *d_counters, void *stream);
 
 /* ---- batched Monte-Carlo over discrete memoryless channels: the BSC and the BEC the reference's README leaves as a
  *      TODO, both at once, and for RS codes the q-ary symmetric and the symbol erasure channel.  A symbol is erased

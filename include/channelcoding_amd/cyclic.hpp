@@ -859,6 +859,22 @@ public:
     return r;
   }
 
+  // The same window with scaled reliability (cc_staircase_decode_sr): B streams of channel values, 2 * iters weights,
+  // one per half-pass of a window position (infinity is a weight: every bit yields to the component decoder); nflip is
+  // counted against the hard decisions of y.
+  hard_result correct_sr(const std::vector<float> &weights, const float *y, size_t B) const {
+    if (weights.size() != 2 * static_cast<size_t>(iters_))
+      throw std::runtime_error("staircase_code: one weight per half-pass of a window position, 2 * iters");
+    const cc_staircase sc = descriptor();
+    hard_result r;
+    r.words.resize(B * values());
+    r.nflip.resize(B);
+    r.status.resize(B);
+    detail::check(cc_staircase_decode_sr(&sc, weights.data(), y, r.words.data(), r.nflip.data(), r.status.data(), B),
+                  "cc_staircase_decode_sr");
+    return r;
+  }
+
 private:
   cc_staircase descriptor() const {
     cc_staircase sc;
