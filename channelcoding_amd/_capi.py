@@ -221,6 +221,11 @@ _SIGNATURES = {
     "cc_product_decode_hard_dev": (C.c_int, [C.POINTER(Product), _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "cc_mc_run_product_hard_dev": (C.c_int, [C.POINTER(Product), C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int,
                                              _VP, _VP]),
+    "cc_product_decode_anchor": (C.c_int, [C.POINTER(Product), C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t]),
+    "cc_product_decode_anchor_dev": (C.c_int, [C.POINTER(Product), C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t,
+                                               _VP]),
+    "cc_mc_run_product_anchor_dev": (C.c_int, [C.POINTER(Product), C.c_uint32, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t,
+                                               C.c_int, _VP, _VP]),
     "cc_product_decode_sr": (C.c_int, [C.POINTER(Product), _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t]),
     "cc_product_decode_sr_dev": (C.c_int, [C.POINTER(Product), _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "cc_mc_run_product_sr_dev": (C.c_int, [C.POINTER(Product), _VP, C.c_double, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int,

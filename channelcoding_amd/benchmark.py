@@ -34,7 +34,10 @@ column code (default: the row code), --extended takes the two extended codes, --
 and --alpha a,b,... and --beta a,b,... give the schedule, one value each per half-iteration.  There is no default
 schedule.  The log is "<rows>x<cols>[-ext]-chaseP-hH.log".  With --halves H in place of --alpha / --beta the ladder runs
 H half-iterations of hard-decision row / column decoding (montecarlo.product_hard_simulation) and the log is
-"<rows>x<cols>[-ext]-hard-hH.log", with the mean of the half-iterations a block took next to wer.  With --weights a,b,...
+"<rows>x<cols>[-ext]-hard-hH.log", with the mean of the half-iterations a block took next to wer.  With --anchor DELTA next
+to --halves H the half-iterations are those of anchor decoding (montecarlo.product_anchor_simulation): a converged line is
+taken back after DELTA conflicts in one pass; there is no default, and the log is "<rows>x<cols>[-ext]-anchorDELTA-hH.log".
+With --weights a,b,...
 in place of all three the ladder runs iBDD with scaled reliability (montecarlo.product_sr_simulation), one weight per
 half-iteration (inf is a weight), and the log is "<rows>x<cols>[-ext]-srH.log".
 
@@ -52,8 +55,8 @@ import sys
 import time
 
 from . import codes as cc
-from .montecarlo import (awgn_simulation, bitflip_simulation, burst_simulation, discrete_simulation, product_hard_simulation,
-                         product_simulation, product_sr_simulation, staircase_simulation,
+from .montecarlo import (awgn_simulation, bitflip_simulation, burst_simulation, discrete_simulation,
+                         product_anchor_simulation, product_hard_simulation, product_simulation, product_sr_simulation, staircase_simulation,
                          staircase_sr_simulation)
 
 POWERS = (5, 6, 7)
@@ -131,6 +134,8 @@ def usage_text():
               "--beta <a,b,...>             product: the value of a position without a competitor, per half-iteration.",
               "--halves <num>               product: hard-decision row / column decoding with that many half-iterations,",
               "                             in place of --alpha and --beta.",
+              "--anchor <delta>             product: with --halves, anchor decoding: a converged line is taken back after",
+              "                             delta >= 1 conflicts in one pass. There is no default.",
               "--weights <a,b,...>          product: iBDD with scaled reliability, one weight per half-iteration (inf is",
               "                             one), in place of --alpha, --beta and --halves.",
               "                             staircase: the window decoder with scaled reliability, exactly 2 * iters",
@@ -231,6 +236,21 @@ def product_hard_arguments(args):
     return rows, cols, args.halves
 
 
+def product_anchor_arguments(args):
+    """(rows (k, dmin), cols (k, dmin), halves, delta) of --simulation product --halves H --anchor DELTA, or a message
+    saying what is wrong"""
+    if getattr(args, "halves", None) is None:
+        return "--anchor goes with --halves: anchor decoding runs that many half-iterations"
+    if getattr(args, "weights", None) is not None:
+        return "--anchor does not combine with --weights"
+    parsed = product_hard_arguments(args)
+    if isinstance(parsed, str):
+        return parsed
+    if not 1 <= args.anchor < 1 << 32:
+        return "--anchor <1..>"
+    return parsed + (args.anchor,)
+
+
 def product_sr_arguments(args):
     """(rows (k, dmin), cols (k, dmin), weights) of --simulation product --weights a,b,..., or a message saying what is
     wrong"""
@@ -262,9 +282,11 @@ def build_product(rows, cols, extended, device=None):
 
 
 def product_main(args):
-    sr = getattr(args, "weights", None) is not None
-    hard = not sr and getattr(args, "halves", None) is not None
-    parsed = product_sr_arguments(args) if sr else product_hard_arguments(args) if hard else product_arguments(args)
+    anchor = getattr(args, "anchor", None) is not None
+    sr = not anchor and getattr(args, "weights", None) is not None
+    hard = not anchor and not sr and getattr(args, "halves", None) is not None
+    parsed = product_anchor_arguments(args) if anchor else product_sr_arguments(args) if sr \
+        else product_hard_arguments(args) if hard else product_arguments(args)
     if isinstance(parsed, str):
         print(parsed, file=sys.stderr)
         print(usage_text())
@@ -273,7 +295,9 @@ def product_main(args):
     dist = join_ranks()
     pc = build_product(parsed[0], parsed[1], args.extended)
     t0 = time.perf_counter()
-    if sr:
+    if anchor:
+        res = product_anchor_simulation(pc, parsed[3], parsed[2], seed=seed, log_dir=args.log_dir, max_samples=args.max_samples)()
+    elif sr:
         res = product_sr_simulation(pc, parsed[2], seed=seed, log_dir=args.log_dir, max_samples=args.max_samples)()
     elif hard:
         res = product_hard_simulation(pc, parsed[2], seed=seed, log_dir=args.log_dir, max_samples=args.max_samples)()
@@ -391,6 +415,7 @@ def main(argv=None):
     ap.add_argument("--alpha", default=None, help="product: a,b,... one per half-iteration")
     ap.add_argument("--beta", default=None, help="product: a,b,... one per half-iteration")
     ap.add_argument("--halves", type=int, default=None, help="product: hard-decision decoding, this many half-iterations")
+    ap.add_argument("--anchor", type=int, default=None, help="product: with --halves, anchor decoding at this delta")
     ap.add_argument("--weights", default=None, help="product: iBDD-SR, a,b,... one weight per half-iteration; staircase: the window decoder with scaled "
                          "reliability, exactly 2 * iters weights")
     ap.add_argument("--blocks", type=int, default=None, help="staircase: blocks per stream")

@@ -1073,6 +1073,16 @@ def _sr_weights(weights):
     return (C.c_float * len(w))(*w)
 
 
+def _anchor_delta(delta):
+    """delta of the anchor decoder as the uint32 of the C calls"""
+    if isinstance(delta, bool) or int(delta) != delta:
+        raise TypeError("delta takes an integer")
+    delta = int(delta)
+    if not 1 <= delta < 1 << 32:
+        raise ValueError("delta = 1 .. 2^32 - 1")
+    return delta
+
+
 class _product_handle:
     """what cyclic._batch_call reads of a code, for a call whose first argument is a cc_product"""
 
@@ -1193,6 +1203,28 @@ class product_code:
     def decode_hard_batch(self, z, halves):
         """correct_hard_batch plus msg (B, k2, k1): the message bits of out"""
         res = self.correct_hard_batch(z, halves)
+        res["msg"] = self.extract_batch(res["out"])
+        return res
+
+    def correct_anchor_batch(self, z, delta, halves):
+        """cc_product_decode_anchor: z (B, n2, n1) uint8 hard decisions -> dict(out=, nflip=, last=, status=, nback=,
+        nconf=) after `halves` half-iterations of anchor decoding: a correction that meets a converged crossing line is
+        refused (nconf counts them), a converged line with `delta` >= 1 conflicts in one pass is taken back (nback).
+        There is no default for delta; numpy array or device tensor."""
+        delta = _anchor_delta(delta)
+        pc = self._pc_hard(halves)
+        z = self._bytes(z, (self.n2, self.n1), "correct_anchor_batch")
+        B = z.shape[0]
+        side = _side(z)
+        res = {"out": side.alloc(z, (B, self.n2, self.n1), np.uint8)}
+        for k in ("nflip", "last", "status", "nback", "nconf"):
+            res[k] = side.alloc(z, (B,), np.int32)
+        cyclic._batch_call(_product_handle(pc), "cc_product_decode_anchor", [z], B, res, head=[delta])
+        return res
+
+    def decode_anchor_batch(self, z, delta, halves):
+        """correct_anchor_batch plus msg (B, k2, k1): the message bits of out"""
+        res = self.correct_anchor_batch(z, delta, halves)
         res["msg"] = self.extract_batch(res["out"])
         return res
 

@@ -1739,11 +1739,17 @@ int cc_mc_run_product_dev(const cc_product *pc, double ebno_db, uint64_t seed, u
   return mc_run_product(pc, ebno_db, seed, first_block, blocks, random_codewords, d_counters, static_cast<hipStream_t>(stream));
 }
 
-// the refusals of cc_product_decode_hard(_dev) in the header's order; the Monte-Carlo call has no arrays
-static int product_hard_supported(const cc_product *pc, const uint8_t *in, const uint8_t *out, size_t B, bool arrays) {
+// the refusals of cc_product_decode_hard(_dev) in the header's order; the Monte-Carlo call has no arrays.  delta: that of
+// the anchor calls, refused at 0 right behind the half-iterations
+static int product_hard_supported(const cc_product *pc, const uint8_t *in, const uint8_t *out, size_t B, bool arrays,
+                                  const uint32_t *delta = nullptr) {
   if (!pc || !pc->rows || !pc->cols) return CC_ERR_INVALID_ARGUMENT;
   if (arrays && B && (!in || !out)) return CC_ERR_INVALID_ARGUMENT;
   if (pc->halves == 0) return CC_ERR_INVALID_ARGUMENT;
+  if (delta && *delta == 0) {
+    set_last_error("cc_product_decode_anchor: delta is 0, an anchor is backtracked after delta >= 1 conflicts");
+    return CC_ERR_INVALID_ARGUMENT;
+  }
   const int rc = product_handles(pc, 0);
   if (rc != CC_OK && rc != CC_ERR_NO_DEVICE) return rc;
   if (arrays && in != out) {
@@ -1785,6 +1791,43 @@ int cc_mc_run_product_hard_dev(const cc_product *pc, double ebno_db, uint64_t se
   DeviceGuard guard(pc->rows->device);
   return mc_run_product_hard(pc, ebno_db, seed, first_block, blocks, random_codewords, d_counters,
                              static_cast<hipStream_t>(stream));
+}
+
+int cc_product_decode_anchor_dev(const cc_product *pc, uint32_t delta, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip,
+                                 int32_t *d_last, int32_t *d_status, int32_t *d_nback, int32_t *d_nconf, size_t B, void *stream) {
+  if (int rc = product_hard_supported(pc, d_in, d_out, B, true, &delta)) return rc;
+  DeviceGuard guard(pc->rows->device);
+  return launch_product_anchor(pc, delta, d_in, d_out, d_nflip, d_last, d_status, d_nback, d_nconf, B,
+                               static_cast<hipStream_t>(stream));
+}
+
+int cc_product_decode_anchor(const cc_product *pc, uint32_t delta, const uint8_t *in, uint8_t *out, int32_t *nflip,
+                             int32_t *last, int32_t *status, int32_t *nback, int32_t *nconf, size_t B) {
+  if (int rc = product_hard_supported(pc, in, out, B, true, &delta)) return rc;
+  if (B == 0) return CC_OK;
+  const ProductShape s = product_shape(pc);
+  if (!symbols_in_field(in, B * s.N, 1)) return CC_ERR_NOT_IN_FIELD;
+  DeviceGuard guard(pc->rows->device);
+  // a block is the frame of the chunk loop
+  const StagedStream streams[] = {stage_in(0, in, s.N), stage_out(1, out, s.N), stage_out(2, nflip, sizeof(int32_t)),
+                                  stage_out(3, status, sizeof(int32_t)), stage_out(4, last, sizeof(int32_t)),
+                                  stage_out(5, nback, sizeof(int32_t)), stage_out(6, nconf, sizeof(int32_t))};
+  return staged_call(pc->rows, B, s.N, 1, streams, 7, nullptr, nullptr,
+                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t st) {
+                       return launch_product_anchor(pc, delta, static_cast<const uint8_t *>(d[0]), static_cast<uint8_t *>(d[1]),
+                                                    static_cast<int32_t *>(d[2]), static_cast<int32_t *>(d[4]),
+                                                    static_cast<int32_t *>(d[3]), static_cast<int32_t *>(d[5]),
+                                                    static_cast<int32_t *>(d[6]), m, st);
+                     });
+}
+
+int cc_mc_run_product_anchor_dev(const cc_product *pc, uint32_t delta, double ebno_db, uint64_t seed, uint64_t first_block,
+                                 size_t blocks, int random_codewords, uint64_t *d_counters, void *stream) {
+  if (!pc || !d_counters) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = product_hard_supported(pc, nullptr, nullptr, blocks, false, &delta)) return rc;
+  DeviceGuard guard(pc->rows->device);
+  return mc_run_product_anchor(pc, delta, ebno_db, seed, first_block, blocks, random_codewords, d_counters,
+                               static_cast<hipStream_t>(stream));
 }
 
 // the refusals of cc_product_decode_sr(_dev) in the header's order, and the schedule of the weights; the Monte-Carlo call

@@ -398,6 +398,13 @@ int mc_run_product_hard(const cc_product *pc, double ebno_db, uint64_t seed, uin
 // (cc_product_decode_hard_dev).  d_out may be d_in; d_nflip, d_last and d_status (one per block) may be nullptr
 int launch_product_hard(const cc_product *pc, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip, int32_t *d_last,
                         int32_t *d_status, size_t B, hipStream_t stream);
+// product_anchor.hip: anchor decoding on hard decisions; pc and delta >= 1 checked by the caller
+// (cc_product_decode_anchor_dev).  d_out may be d_in; the five int32 outputs (one per block) may be nullptr
+int launch_product_anchor(const cc_product *pc, uint32_t delta, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip,
+                          int32_t *d_last, int32_t *d_status, int32_t *d_nback, int32_t *d_nconf, size_t B, hipStream_t stream);
+// product.hip: the route of mc_run_product_hard around launch_product_anchor
+int mc_run_product_anchor(const cc_product *pc, uint32_t delta, double ebno_db, uint64_t seed, uint64_t first_block,
+                          size_t blocks, int random_codewords, uint64_t *d_counters, hipStream_t stream);
 // product_sr.hip: iBDD with scaled reliability.  The schedule of a call: the distinct weights in rising
 // order, the position of every half-iteration's weight among them, and the first half-iteration from which the levels
 // repeat with period two (the early stop's bound)

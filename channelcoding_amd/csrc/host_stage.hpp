@@ -269,8 +269,9 @@ inline int upload_erasures(HostStage &st, int slot, int idx, const uint16_t *era
 }
 
 // One per-frame array of a staged call.  Buffer indices (HostStage::buf[slot][idx]): 0 in, 1 out, 2 iters / nerr,
-// 3 status, 4 L / metric; 5 and 6 hold a chunk's erasure positions and offsets; 7 a second input (the reliabilities of GMD)
-// or a second per-symbol output (ext of the Chase soft output).
+// 3 status, 4 L / metric; 5 and 6 hold a chunk's erasure positions and offsets (in a call without erasure lists they are
+// free: nback and nconf of the anchor decoder); 7 a second input (the reliabilities of GMD) or a second per-symbol output
+// (ext of the Chase soft output).
 struct StagedStream {
   int idx;
   size_t bytes;  // per frame
@@ -279,7 +280,7 @@ struct StagedStream {
 };
 inline StagedStream stage_in(int idx, const void *host, size_t bytes) { return {idx, bytes, true, const_cast<void *>(host)}; }
 inline StagedStream stage_out(int idx, void *host, size_t bytes) { return {idx, bytes, false, host}; }
-constexpr int kMaxStagedStreams = 6;
+constexpr int kMaxStagedStreams = 7;
 
 // The chunk loop of every host-pointer entry point: B frames in chunks of chunk_frames(chunk_width, B), cut down to
 // a multiple of `granule` frames (an interleaving block is never split) and never less than one granule.  For each

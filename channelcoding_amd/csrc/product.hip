@@ -454,6 +454,17 @@ int mc_run_product_hard(const cc_product *pc, double ebno_db, uint64_t seed, uin
   });
 }
 
+// the anchor decoder (product_anchor.hip) on the same hard decisions, decoded in place
+int mc_run_product_anchor(const cc_product *pc, uint32_t delta, double ebno_db, uint64_t seed, uint64_t first_block,
+                          size_t blocks, int random_codewords, uint64_t *d_counters, hipStream_t stream) {
+  const auto sent_of = [&](uint64_t first, size_t m, uint8_t *msg, uint8_t *sent) { return product_sent(pc, seed, first, m, msg, sent, stream); };
+  return mc_block_route<uint8_t>(product_route(pc, ebno_db), seed, first_block, blocks, random_codewords, 1, true, d_counters,
+                                 stream, sent_of,
+                                 [&](size_t m, const uint8_t *z, uint8_t *decided, int32_t *status, int32_t *last) {
+    return launch_product_anchor(pc, delta, z, decided, nullptr, last, status, nullptr, nullptr, m, stream);
+  });
+}
+
 // the soft-aided hard-decision decoder (product_sr.hip): the channel's floats, one status and one `last` per block
 int mc_run_product_sr(const cc_product *pc, const SrSchedule &sched, double ebno_db, uint64_t seed, uint64_t first_block,
                       size_t blocks, int random_codewords, uint64_t *d_counters, hipStream_t stream) {

@@ -221,6 +221,21 @@ class ProductHardBackend(DeviceBackend):
         self.desc = pc._pc_hard(halves)
 
 
+class ProductAnchorBackend(DeviceBackend):
+    """Counts one shard of blocks of one Eb/N0 point through cc_mc_run_product_anchor_dev: a product_code decoded with
+    `halves` half-iterations of anchor decoding at `delta` (codes.product_code.correct_anchor_batch) on the hard decisions
+    of the channel."""
+
+    symbol = "cc_mc_run_product_anchor_dev"
+
+    def __init__(self, pc, delta, halves, random_codewords=False):
+        from .codes import _anchor_delta
+        super().__init__(pc, random_codewords)
+        self.delta = _anchor_delta(delta)
+        self.desc = pc._pc_hard(halves)
+        self.leading = (self.delta,)
+
+
 class ProductSrBackend(DeviceBackend):
     """Counts one shard of blocks of one Eb/N0 point through cc_mc_run_product_sr_dev: a product_code decoded with
     len(weights) half-iterations of iBDD with scaled reliability (codes.product_code.correct_sr_batch)."""
@@ -450,6 +465,26 @@ class product_hard_simulation(_EbnoLadder):
 
     def __call__(self):
         name = "%s-hard-h%d.log" % (self.code.to_string(), self.halves)
+        return self._ladder(name, "ebno", lambda ebno: ebno, " %12s" % "mean_last", lambda res: " %12.6f" % res["mean_last"])
+
+
+class product_anchor_simulation(product_hard_simulation):
+    """The Eb/N0 ladder of a product code under `halves` half-iterations of anchor decoding at `delta`
+    (cc_mc_run_product_anchor_dev; there is no default for delta): ladder, sharding by block and the mean_last column of
+    product_hard_simulation.  The log is <pc.to_string()>-anchor<delta>-h<halves>.log."""
+
+    def __init__(self, pc, delta, halves, step=0.5, seed=0, random_codewords=False, backend=None, log_dir=None,
+                 max_samples=None, start=None, stop=None, samples_per_point=None):
+        from .codes import _anchor_delta
+        self.delta = _anchor_delta(delta)
+        if int(halves) < 1:
+            raise ValueError("halves >= 1")
+        if backend is None:
+            backend = ProductAnchorBackend(pc, self.delta, halves, random_codewords)
+        super().__init__(pc, halves, step, seed, random_codewords, backend, log_dir, max_samples, start, stop, samples_per_point)
+
+    def __call__(self):
+        name = "%s-anchor%d-h%d.log" % (self.code.to_string(), self.delta, self.halves)
         return self._ladder(name, "ebno", lambda ebno: ebno, " %12s" % "mean_last", lambda res: " %12.6f" % res["mean_last"])
 
 

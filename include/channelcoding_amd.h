@@ -580,6 +580,76 @@ int cc_product_decode_hard_dev(const cc_product *pc, const uint8_t *d_in, uint8_
 int cc_mc_run_product_hard_dev(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
                                int random_codewords, uint64_t *d_counters, void *stream);
 
+/* ---- anchor decoding of a product code (C. Haeger and H. Pfister, "Approaching miscorrection-free performance of product
+ *      codes with anchor decoding", IEEE Trans. Commun. 66 (7), 2018, in a parallel schedule): iBDD on hard decisions with
+ *      miscorrection control -- a line's correction is refused where it conflicts with a converged crossing line, and a
+ *      converged line that collects conflicts is taken back.  One launch runs all half-iterations of a batch.
+ *      Of `cc_product` only `rows`, `cols`, `extended` and `halves` are read. e, w1, w2, N and the block `[w2][w1]` are
+ *      those of `cc_product_decode_hard`. `in` holds bytes 0 / 1. `delta` >= 1 is a call argument, not a struct member:
+ *      `sizeof(cc_product)` stays as it is.
+ *
+ *      State per line. Each row and each column has:
+ *      - an anchor flag A, initially 0;
+ *      - a hold flag H, initially 0;
+ *      - a record R, the set of positions it flipped when it became an anchor, initially empty.
+ *
+ *      Half-iteration h takes the rows (h even) or the columns (h odd) of x_h. Call them the lines, and the other
+ *      direction the crossing lines. Everything in step 1 is decided from the state at the start of the pass.
+ *
+ *      1. A line is treated in this order:
+ *         - An anchor is skipped.
+ *         - A held line clears its hold flag and is otherwise skipped.
+ *         - Every other line gets its taken word from the line rule of `cc_product_decode_hard`, word for word. That is
+ *           the candidate within t of the n inner positions, and for an extended line d <= t. A line with zero syndromes
+ *           is its own taken word, with its parity bit mended where extended.
+ *         - Let E be the set of positions where the taken word differs from the line, so |E| <= t. A line without a
+ *           taken word stays.
+ *         - If no crossing line at a position of E is an anchor, the flips of E are applied, A becomes 1 and R = E. A
+ *           clean line becomes an anchor with an empty record.
+ *         - Otherwise the line stays. It is refused: every crossing anchor at a position of E counts one conflict for
+ *           this pass, and `nconf` takes one.
+ *      2. Behind all lines, every crossing anchor with at least `delta` conflicts in this pass is backtracked:
+ *         - the bits of its record are flipped back;
+ *         - its A becomes 0, its R becomes empty, and its H becomes 1, so it sits out its next pass;
+ *         - `nback` takes one;
+ *         - every line that holds a flipped-back bit loses its anchor flag and its record; its earlier flips stay.
+ *         - Conflict counts do not survive the pass.
+ *         - A bit flipped back lies in a crossing anchor, and step 1 cannot have flipped a bit in a crossing anchor. The
+ *           two sets of changes are therefore disjoint and their order cannot show.
+ *
+ *      Outputs.
+ *      - `out` = x_halves.
+ *      - `nflip` = d_H(out, in).
+ *      - `last` = the largest h + 1 with x_(h+1) != x_h, or 0 if there is none. This counts bits, not flags.
+ *      - `status` is as in `cc_product_decode_hard`.
+ *      - `nback` and `nconf` are int32 per block.
+ *      - All five int32 outputs may be NULL.
+ *      - `out == in` is allowed.
+ *
+ *      Early stop. The device may stop a block only where no output can show it. Two successive passes that change
+ *      nothing of the state -- no bit, no anchor flag, no hold flag, no record -- are a fixed point. That does not follow
+ *      from "no bit changed". A quiet pass can still turn clean lines into anchors or consume a hold.
+ *
+ *      Refusals. These come in the order of `cc_product_decode_hard`, with one addition: `delta == 0` gives
+ *      `CC_ERR_INVALID_ARGUMENT` with a text, directly after the `halves == 0` check. B = 0 answers `CC_OK` after the
+ *      checks.
+ *
+ *      The host form answers CC_ERR_NOT_IN_FIELD for a byte above 1, as cc_product_decode_hard does.  Buffers: natural
+ *      alignment only, and nothing outside the stated extents is read into a result or written.  Not here: staircase
+ *      codes, the paper's sequential schedule and its post-processing of stall patterns, conflict counts carried across
+ *      passes, any combination with iBDD-SR weights, RS components, q > 8. ---- */
+int cc_product_decode_anchor(const cc_product *pc, uint32_t delta, const uint8_t *in /* B*N */, uint8_t *out /* B*N */,
+                             int32_t *nflip /* B or NULL */, int32_t *last /* B or NULL */, int32_t *status /* B or NULL */,
+                             int32_t *nback /* B or NULL */, int32_t *nconf /* B or NULL */, size_t B);
+int cc_product_decode_anchor_dev(const cc_product *pc, uint32_t delta, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip,
+                                 int32_t *d_last, int32_t *d_status, int32_t *d_nback, int32_t *d_nconf, size_t B,
+                                 void *stream);
+/* Monte-Carlo of the anchor decoder: by definition the counters equal what cc_awgn_product_dev at cc_product_sigma, the
+ * hard decision z = (y < 0), cc_product_decode_anchor_dev and the count of cc_mc_run_product_hard_dev would give: the same
+ * counters, chunks and workspace pool, depending only on (seed, ebno, pc, delta, the set of global blocks). */
+int cc_mc_run_product_anchor_dev(const cc_product *pc, uint32_t delta, double ebno_db, uint64_t seed, uint64_t first_block,
+                                 size_t blocks, int random_codewords, uint64_t *d_counters, void *stream);
+
 /* ---- iBDD with scaled reliability (iBDD-SR; A. Sheikh, A. Graell i Amat, G. Liva, IEEE Trans. Commun. 67 (12), 2019) of
  *      a product code: one bounded-distance decode per line on hard decisions as in cc_product_decode_hard, whose verdict
  *      is weighed against the channel value of every bit, sign(w_h u + y).  One launch runs all half-iterations of a

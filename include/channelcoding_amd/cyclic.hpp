@@ -756,6 +756,27 @@ public:
     return r;
   }
 
+  // Anchor decoding on hard decisions (cc_product_decode_anchor): correct_hard with miscorrection control.  A correction
+  // that meets a converged crossing line is refused (nconf per block), a converged line with delta >= 1 conflicts in one
+  // pass is taken back (nback per block).
+  struct anchor_result {
+    std::vector<uint8_t> words;
+    std::vector<int32_t> nflip, last, status, nback, nconf;
+  };
+  anchor_result correct_anchor(const uint8_t *words, size_t B, uint32_t delta, uint32_t halves) const {
+    if (halves == 0) throw std::runtime_error("product_code: at least one half-iteration");
+    if (delta == 0) throw std::runtime_error("product_code: delta >= 1");
+    const cc_product pc = descriptor(0, nullptr, nullptr, halves);
+    anchor_result r;
+    r.words.resize(B * values());
+    for (std::vector<int32_t> *v : {&r.nflip, &r.last, &r.status, &r.nback, &r.nconf}) v->resize(B);
+    const int rc = cc_product_decode_anchor(&pc, delta, words, r.words.data(), r.nflip.data(), r.last.data(), r.status.data(),
+                                            r.nback.data(), r.nconf.data(), B);
+    if (rc == CC_ERR_NOT_IN_FIELD) throw std::runtime_error("Value is not an element of the field.");
+    detail::check(rc, "cc_product_decode_anchor");
+    return r;
+  }
+
   // iBDD with scaled reliability (cc_product_decode_sr): B blocks of N channel values, one weight per half-iteration
   // (infinity is a weight: every bit yields to the component decoder); the result is that of correct_hard, nflip
   // counted against the hard decisions of y.
