@@ -1885,23 +1885,40 @@ int cc_mc_run_product_sr_dev(const cc_product *pc, const float *weights, double 
 
 /* ------------------------------ staircase codes ------------------------------ */
 
+// The shape rules of a staircase, each stated here only: the rules that sc breaks, as a set.  windowed: the window is
+// read too.  Without a code of q <= 8 behind the handle no length can be read: the two rules of the lengths are not asked.
+enum : unsigned { kStairNoCode = 1, kStairNoBlock = 2, kStairWindow = 4, kStairOdd = 8, kStairNoMessage = 16 };
+static unsigned staircase_broken(const cc_staircase *sc, bool windowed) {
+  if (!sc) return kStairNoCode;
+  unsigned broken = 0;
+  if (sc->blocks == 0) broken |= kStairNoBlock;
+  if (windowed && (sc->window < 2 || sc->window > CC_STAIRCASE_MAX_WINDOW)) broken |= kStairWindow;
+  if (!sc->code || sc->code->matrix_only || sc->code->wide) return broken | kStairNoCode;
+  const size_t e = sc->extended ? 1 : 0, n = sc->code->tab.n, m = (n + e) / 2;
+  if ((n + e) & 1) broken |= kStairOdd;
+  if ((n - sc->code->tab.l) + e >= m) broken |= kStairNoMessage;
+  return broken;
+}
+
 // The refusals of the staircase calls in the header's order.  decode: window and iters are read, and in / out hold
 // streams of the same extent; arrays: the call has in / out at all.  CC_OK or CC_ERR_NO_DEVICE is answered last.
 static int staircase_supported(const cc_staircase *sc, bool decode, bool arrays, const uint8_t *in, const uint8_t *out,
                                size_t B) {
   if (!sc || !sc->code) return CC_ERR_INVALID_ARGUMENT;
   if (arrays && B && (!in || !out)) return CC_ERR_INVALID_ARGUMENT;
-  if (sc->blocks == 0) return CC_ERR_INVALID_ARGUMENT;
-  if (decode && (sc->window < 2 || sc->window > CC_STAIRCASE_MAX_WINDOW || sc->iters == 0)) return CC_ERR_INVALID_ARGUMENT;
+  // (a handle without a code of q <= 8 breaks no other rule here: chase_supported refuses it below, with its text)
+  const unsigned broken = staircase_broken(sc, decode);
+  if (broken & kStairNoBlock) return CC_ERR_INVALID_ARGUMENT;
+  if ((broken & kStairWindow) || (decode && sc->iters == 0)) return CC_ERR_INVALID_ARGUMENT;
   const unsigned long long e = sc->extended ? 1 : 0, n = sc->code->tab.n, m = (n + e) / 2;
   if (static_cast<unsigned long long>(sc->blocks) * m * m >= (1ull << 32)) return CC_ERR_INVALID_ARGUMENT;
   const int rc = chase_supported(sc->code, 0);
   if (rc != CC_OK && rc != CC_ERR_NO_DEVICE) return rc;
-  if ((n + e) & 1ull) {
+  if (broken & kStairOdd) {
     set_last_error("staircase code: n + e is odd, a line does not split into two halves of m bits");
     return CC_ERR_INVALID_ARGUMENT;
   }
-  if ((n - sc->code->tab.l) + e >= m) {
+  if (broken & kStairNoMessage) {
     set_last_error("staircase code: r = (n - l) + e parity bits per line leave no message bit in a row of m");
     return CC_ERR_INVALID_ARGUMENT;
   }
@@ -1971,23 +1988,21 @@ int cc_staircase_extract_batch(const cc_staircase *sc, const uint8_t *cw, uint8_
   return staircase_map_host(sc, false, cw, msg, B);
 }
 
-// an sc whose shape can be read: a code behind the handle, q <= 8, n + e even, r < m, at least one block
-static bool staircase_readable(const cc_staircase *sc) {
-  if (!sc || !sc->code || needs_code(sc->code) != CC_OK || sc->code->wide || sc->blocks == 0) return false;
-  const size_t e = sc->extended ? 1 : 0, n = sc->code->tab.n;
-  return ((n + e) & 1) == 0 && (n - sc->code->tab.l) + e < (n + e) / 2;
+// an sc whose shape can be read; a handle without a code leaves needs_code's text as the last error
+static bool staircase_readable(const cc_staircase *sc, bool windowed) {
+  if (sc && sc->code) (void)needs_code(sc->code);
+  return staircase_broken(sc, windowed) == 0;
 }
 
 double cc_staircase_sigma(const cc_staircase *sc, double ebno_db) {
-  if (!staircase_readable(sc)) return 0.0;
+  if (!staircase_readable(sc, false)) return 0.0;
   const StaircaseShape s = staircase_shape(sc);
   const double rate = 1.0 - static_cast<double>(s.r) / static_cast<double>(s.m);
   return 1.0 / std::sqrt(2.0 * rate * std::pow(10.0, ebno_db / 10.0));
 }
 
 size_t cc_staircase_lds_bytes(const cc_staircase *sc) {
-  if (!staircase_readable(sc) || sc->window < 2 || sc->window > CC_STAIRCASE_MAX_WINDOW) return 0;
-  return staircase_lds_bytes(sc);
+  return staircase_readable(sc, true) ? staircase_lds_bytes(sc) : 0;
 }
 
 int cc_awgn_staircase_dev(const cc_staircase *sc, double ebno_db, uint64_t seed, uint64_t first_stream, size_t streams,
@@ -2056,9 +2071,7 @@ int cc_staircase_decode_sr(const cc_staircase *sc, const float *weights, const f
 }
 
 size_t cc_staircase_sr_lds_bytes(const cc_staircase *sc, const float *weights) {
-  if (!staircase_readable(sc) || !weights || sc->window < 2 || sc->window > CC_STAIRCASE_MAX_WINDOW || sc->iters == 0 ||
-      sc->iters > UINT32_MAX / 2)
-    return 0;
+  if (!staircase_readable(sc, true) || !weights || sc->iters == 0 || sc->iters > UINT32_MAX / 2) return 0;
   SrSchedule sched;
   if (product_sr_schedule(weights, 2 * sc->iters, &sched) != CC_OK) return 0;
   return staircase_sr_lds_bytes(sc, sched.D);

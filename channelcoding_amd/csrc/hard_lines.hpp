@@ -1,8 +1,9 @@
 // hard_lines.hpp -- what the iterated bounded-distance decoders share (product_hard.hip, product_sr.hip, staircase.hip,
 // staircase_sr.hip).  Each of these is spelled out here only:
 //   layout      tile_pitch, state_pitch; product_block, the LDS of one block of a product code
-//   a line      up to 64 NC bits held by one lane: gather_line from a bit tile, line_syndrome and line_state from the bits;
-//               bit_range and clamp64 for the two halves of a staircase line
+//   a line      up to 64 NC bits held by one lane: gather_line from a bit tile, line_syndrome and line_state from the bits,
+//               add_positions (what a set of positions adds to a state); bit_range and clamp64 for the two halves of a
+//               staircase line
 //   the rule    line_flips, the line rule of cc_product_decode_hard: from the line's state in LDS (t odd syndromes, then
 //               the parity of all its bits) to the positions at which the line changes
 //   flips       flip_state, what one flipped bit adds to the state of the line that crosses it; apply_flips, a row or
@@ -12,7 +13,7 @@
 //   a product   Side, one direction of a product block, and side_of; ProductFrame and product_frame, the preamble of a
 //               product kernel; block_sync, each_tile_dword, product_finish; on the host product_launch (shape, LDS bytes)
 // product_hard.hip uses the layout, the line, the rule, block_sync and store_results and keeps the rest in its own text:
-// its header says why.
+// its header says why.  The sliding window of the two staircase decoders stands on top of this in stair_frame.hpp.
 #pragma once
 #include "soft_lanes.hpp"
 
@@ -126,6 +127,31 @@ template <int NC>
 __device__ __forceinline__ void line_state(uint8_t *S, const uint8_t *ex, const unsigned long long (&lb)[NC], int n, int nn, int t) {
   for (int m = 0; m < t; ++m) S[m] = static_cast<uint8_t>(line_syndrome<NC>(ex, lb, n, nn, 2 * m + 1));
   S[t] = static_cast<uint8_t>(count_bits<NC>(lb) & 1);
+}
+// what the positions `mask` of a line add to its state: alpha^(j k) for the t odd j where k < n, and the parity; onto:
+// added to the state S holds, else S becomes the state of these positions alone
+template <int NC>
+__device__ __forceinline__ void add_positions(uint8_t *S, const uint8_t *ex, const unsigned long long (&mask)[NC], int n, int nn, int t,
+                                              bool onto) {
+  if (!onto)
+    for (int j = 0; j < t; ++j) S[j] = 0;
+  const uint8_t par = static_cast<uint8_t>(count_bits<NC>(mask) & 1);
+  S[t] = onto ? S[t] ^ par : par;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    unsigned long long m = mask[c];
+    while (m) {
+      const int k = 64 * c + __builtin_ctzll(m);
+      m &= m - 1ull;
+      if (k >= n) continue;
+      const uint32_t step2 = addmod(k, k, nn);
+      uint32_t ev = static_cast<uint32_t>(k);
+      for (int j = 0; j < t; ++j) {
+        S[j] ^= ex[ev];
+        ev = addmod(ev, step2, nn);
+      }
+    }
+  }
 }
 // the status scan: one of the first `count` bytes of a line's state is not zero
 __device__ __forceinline__ bool state_nonzero(const uint8_t *S, int count) {

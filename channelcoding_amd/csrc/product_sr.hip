@@ -173,23 +173,7 @@ product_sr_kernel(const AlgebraicTables *__restrict__ Tr, const AlgebraicTables 
       if (changed) {
         // the line's own state: that of the reverted positions, or that of the z line
         if (taken) {
-          for (int m = 0; m < t; ++m) S[m] = 0;
-          S[t] = static_cast<uint8_t>(count_bits<NC>(fm) & 1);
-#pragma unroll
-          for (int c = 0; c < NC; ++c) {
-            unsigned long long m = fm[c];
-            while (m) {
-              const int k = 64 * c + __builtin_ctzll(m);
-              m &= m - 1ull;
-              if (k >= n) continue;
-              const uint32_t step2 = addmod(k, k, nn);
-              uint32_t ev = static_cast<uint32_t>(k);
-              for (int j = 0; j < t; ++j) {
-                S[j] ^= ex[ev];
-                ev = addmod(ev, step2, nn);
-              }
-            }
-          }
+          add_positions<NC>(S, ex, fm, n, nn, t, false);
         } else {
           for (int m = 0; m <= t; ++m) S[m] = S[s0 + m];
         }

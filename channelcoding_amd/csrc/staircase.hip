@@ -3,7 +3,9 @@
 // cc_staircase in the public header; here is how it is mapped.
 //
 // What it shares with the product decoders is hard_lines.hpp's: the tile and the state of a line, the line rule, what a
-// flipped bit adds to the state of a crossing line, the load through ballots.  Here is what differs.
+// flipped bit adds to the state of a crossing line, the load through ballots.  The window itself -- layout, frame, the
+// walk's arithmetic, the line of a step, the flips, leaving -- is stair_frame.hpp's, shared with staircase_sr.hip; the
+// loops and the line step stand below.  Here is how it is laid out.
 //
 // One workgroup of 256 threads owns a stream from its first block to its last.  The window is a ring of W tiles in LDS:
 // block i lives in tile i mod W as bits, m rows of P = tile_pitch(m) dwords.  Tile 0 starts as B_0 = 0.  Next to every
@@ -26,25 +28,14 @@
 // A position stops after two successive half-passes without a change: the state then repeats, no output can show it.
 #include <type_traits>
 
-#include "hard_lines.hpp"
+#include "stair_frame.hpp"
 
 namespace ccamd {
 namespace {
 
-// the LDS of a workgroup behind the tables and the four sets of Berlekamp-Massey columns, in dwords: ctl [4], W tiles
-// [m][P], W step states [m][pitch bytes]
-struct StairLayout {
-  int P, pitch, tile, state, dwords;
-};
-__host__ __device__ constexpr StairLayout stair_layout(int m, int t, int W) {
-  const int P = tile_pitch(m), pitch = state_pitch(t);
-  return StairLayout{P, pitch, m * P, m * pitch / 4, 4 + W * (m * P + m * pitch / 4)};
-}
-constexpr size_t stair_lds_bytes(int m, int t, int W) {
-  return kSoftTables + 4 * static_cast<size_t>(bm_columns(2 * t).end) + 4 * static_cast<size_t>(stair_layout(m, t, W).dwords);
-}
-// no admitted shape exceeds m = 128 (q <= 8) with t = 16 (2t <= 32) and sixteen blocks
-static_assert(stair_lds_bytes(128, 16, CC_STAIRCASE_MAX_WINDOW) <= 160 * 1024, "the window must fit the LDS of a workgroup");
+// one tile per slot, one copy of the states; no admitted shape exceeds m = 128 (q <= 8) with t = 16 (2t <= 32) and
+// sixteen blocks
+static_assert(stair_lds_bytes(128, 16, CC_STAIRCASE_MAX_WINDOW, 1, 1) <= 160 * 1024, "the window must fit the LDS of a workgroup");
 
 // NC = 1: lines of up to 64 bits (m <= 32); NC = 4: up to 256 bits
 template <int NC>
@@ -53,153 +44,73 @@ staircase_kernel(const AlgebraicTables *__restrict__ T, const uint8_t *in, uint8
                  int32_t *__restrict__ status_out, unsigned long long B, int L, int W, int iters, int e, int col_bytes) {
   constexpr int CB = NC == 1 ? 1 : 2;  // 64-byte chunks of a row of a block
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  const uint8_t *ex = smem;
-  const uint16_t *lg2 = stage_tables(T, smem);
-
-  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int n = T->n, nn = T->nf, t = T->nroots / 2, m = (n + e) >> 1, me = m - e;
-  const int PD = (m + 31) >> 5;
-  const StairLayout lay = stair_layout(m, t, W);
-  const int P = lay.P, pitch = lay.pitch;
-  const unsigned long long mm = static_cast<unsigned long long>(m) * m, N = mm * L;
-  uint8_t *colbase = smem + kSoftTables + wid * col_bytes;
-  const BmColumns bm = bm_columns(2 * t);
-  uint16_t *SL = reinterpret_cast<uint16_t *>(colbase + bm.SL);
-  uint16_t *LL = reinterpret_cast<uint16_t *>(colbase + bm.LL);
-  uint16_t *BL = reinterpret_cast<uint16_t *>(colbase + bm.BL);
-  uint32_t *ctl = reinterpret_cast<uint32_t *>(smem + kSoftTables + 4 * col_bytes);  // [0] last half-pass that changed, + 1
-  uint32_t *ring = ctl + 4;                                                          // [1] a line that is no word, [2] nflip
-  uint8_t *states = reinterpret_cast<uint8_t *>(ring + W * lay.tile);
-  const auto tile = [&](int blk) { return ring + (blk % W) * lay.tile; };
-  const auto state = [&](int step) { return states + (step % W) * (4 * lay.state); };
-  const int pw = (m - 1) >> 5, pb = (m - 1) & 31;  // the parity column of a block
+  const StairFrame f = stair_frame(T, smem, W, e, col_bytes, 1, 1);
+  const int tid = f.tid, m = f.m;
 
   for (unsigned long long s = blockIdx.x; s < B; s += gridDim.x) {
-    const uint8_t *src = in + s * N;
-    uint8_t *dst = out + s * N;
-
-    // block `blk` leaves: step blk's part of the status, bits -> bytes, its part of nflip
+    const uint8_t *src = in + s * f.mm * L;
+    uint8_t *dst = out + s * f.mm * L;
+    // block `blk` leaves: its bits as bytes, compared with `in` on the way
     const auto retire = [&](int blk) {
-      if (tid < m && state_nonzero(state(blk) + tid * pitch, t + e)) atomicOr(&ctl[1], 1u);
-      const uint32_t *X = tile(blk);
-      const unsigned long long off = static_cast<unsigned long long>(blk - 1) * mm;
-      uint32_t diff = 0;
-      for (int r = wid; r < m; r += 4)
-#pragma unroll
-        for (int c = 0; c < CB; ++c) {
-          const int col = 64 * c + lane;
-          if (col < m) {
-            const unsigned long long at = off + static_cast<unsigned long long>(r) * m + col;
-            const uint32_t bit = (X[r * P + (col >> 5)] >> (col & 31)) & 1u;
-            diff += (src[at] & 1u) != bit ? 1u : 0u;
-            dst[at] = static_cast<uint8_t>(bit);
-          }
-        }
-      if (diff) atomicAdd(&ctl[2], diff);
+      const uint32_t *X = f.tile(blk);
+      const uint8_t *sb = src + static_cast<unsigned long long>(blk - 1) * f.mm;
+      stair_retire<CB>(f, blk, dst, [&](int at) { return X[at]; },
+                       [&](int r, int col, uint32_t bit) { return (sb[static_cast<unsigned long long>(r) * m + col] & 1u) != bit; });
     };
 
-    for (int i = tid; i < lay.tile; i += 256) ring[i] = 0;  // B_0
-    if (tid < 4) ctl[tid] = 0;
-    const int b_last = L >= W ? L - W + 1 : 0;
+    for (int i = tid; i < f.tl; i += 256) f.ring[i] = 0;  // B_0
+    if (tid < 4) f.ctl[tid] = 0;
+    const int b_last = stair_last(L, W);
     int loaded = 0;
     for (int b = 0; b <= b_last; ++b) {
-      const int top = b + W - 1 < L ? b + W - 1 : L;
+      const int top = stair_top(b, L, W);
       // ---------------- the blocks that enter: bytes -> bits ----------------
       for (int blk = loaded + 1; blk <= top; ++blk) {
-        const uint8_t *sb = src + static_cast<unsigned long long>(blk - 1) * mm;
-        uint32_t *X = tile(blk);
-        load_bit_rows<4, CB>(sb, m, m, wid, 4, lane, [&](int r, int c, unsigned long long mask) { store_ballot(X + r * P, PD, lane, c, mask); });
+        const uint8_t *sb = src + static_cast<unsigned long long>(blk - 1) * f.mm;
+        uint32_t *X = f.tile(blk);
+        load_bit_rows<4, CB>(sb, m, m, f.wid, 4, f.lane, [&](int r, int c, unsigned long long mask) { store_ballot(X + r * f.P, f.PD, f.lane, c, mask); });
       }
-      if (tid == 0) ctl[0] = 0;
+      if (tid == 0) f.ctl[0] = 0;
       __syncthreads();
       // ---------------- the state of every line of the steps that enter, from the bits, once ----------------
       for (int g = tid; g < (top - loaded) * m; g += 256) {
-        const int sidx = g / m, j = g - sidx * m, i = loaded + 1 + sidx;
-        const uint32_t *Xi = tile(i) + j * P, *Xp = tile(i - 1) + (j >> 5);
-        const int jb = j & 31;
+        const StairLine ln = stair_deal(g, (top - loaded) * m, m, loaded + 1, 1);
         unsigned long long lb[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          const int r1 = clamp64(me - 64 * c), c1 = clamp64(n - 64 * c);
-          unsigned long long acc = 0;
-#pragma unroll 8
-          for (int k = 0; k < r1; ++k) {  // row j of the block itself
-            const int pos = 64 * c + k;
-            acc |= static_cast<unsigned long long>((Xi[pos >> 5] >> (pos & 31)) & 1u) << k;
-          }
-#pragma unroll 8
-          for (int k = r1; k < c1; ++k)  // column j of the block before
-            acc |= static_cast<unsigned long long>((Xp[(64 * c + k - me) * P] >> jb) & 1u) << k;
-          if (e && (n >> 6) == c) acc |= static_cast<unsigned long long>((Xi[pw] >> pb) & 1u) << (n & 63);
-          lb[c] = acc;
-        }
-        line_state<NC>(state(i) + j * pitch, ex, lb, n, nn, t);
+        gather_step_line<NC>(f, f.tile(ln.i), f.tile(ln.i - 1), ln.j, lb);
+        line_state<NC>(f.state(ln.i) + ln.j * f.pitch, f.ex, lb, f.n, f.nn, f.t);
       }
       loaded = top;
       __syncthreads();
 
       // ---------------- the half-passes of this position ----------------
       for (int h = 0; h < 2 * iters; ++h) {
-        const int i0 = top - (h & 1);
-        const int total = i0 > b ? ((i0 - b - 1) / 2 + 1) * m : 0;  // lines of the steps i0, i0 - 2, .. > b
+        const int i0 = top - (h & 1), total = stair_half_lines(i0, b, m);
         for (int base = 0; base < total; base += 256) {
-          if (base + 64 * wid >= total) continue;  // a wavefront without a line in this trip
-          const int g = base + tid;
-          const bool have_line = g < total;
-          const int sidx = have_line ? g / m : 0, j = have_line ? g - sidx * m : 0, i = i0 - 2 * sidx;
-          uint8_t *S = state(i) + j * pitch;
+          if (base + 64 * f.wid >= total) continue;  // a wavefront without a line in this trip
+          const StairLine ln = stair_deal(base + tid, total, m, i0, -2);
+          uint8_t *S = f.state(ln.i) + ln.j * f.pitch;
           unsigned long long fm[NC];  // positions the line changes at
-          line_flips<NC>(ex, lg2, SL, LL, BL, S, have_line, lane, n, nn, t, e, fm);
-          if (i == 1) {  // the zero block stays zero: the line keeps its bits
-            bool reaches = false;
+          line_flips<NC>(f.ex, f.lg2, f.SL, f.LL, f.BL, S, ln.have, f.lane, f.n, f.nn, f.t, e, fm);
+          if (ln.i == 1 && reaches_zero_block<NC>(f, fm)) {  // the zero block stays zero: the line keeps its bits
 #pragma unroll
-            for (int c = 0; c < NC; ++c) reaches = reaches || (fm[c] & bit_range(clamp64(me - 64 * c), clamp64(n - 64 * c))) != 0;
-            if (reaches) {
-#pragma unroll
-              for (int c = 0; c < NC; ++c) fm[c] = 0;
-            }
+            for (int c = 0; c < NC; ++c) fm[c] = 0;
           }
           if (any_bit<NC>(fm)) {
-            // the line becomes a word of its code: its own state is zero; a flipped bit of the row half is also a bit of
-            // the next step, one of the column half a bit of the step before
-            for (int k = 0; k <= t; ++k) S[k] = 0;
-            uint32_t *Xi = tile(i), *Xp = tile(i - 1);
-            uint32_t *Sn = reinterpret_cast<uint32_t *>(state(i + 1)), *Sp = reinterpret_cast<uint32_t *>(state(i - 1));
-            const bool next = i + 1 <= top;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-              unsigned long long mask = fm[c];
-              while (mask) {
-                const int p = 64 * c + __builtin_ctzll(mask);
-                mask &= mask - 1ull;
-                if (p < me || p == n) {  // B_i[j][col]
-                  const int col = p < me ? p : m - 1;
-                  atomicXor(&Xi[j * P + (col >> 5)], 1u << (col & 31));
-                  if (next) flip_state(Sn, ex, col, pitch, me + j, odd_step(me + j, nn), t, nn, e);
-                } else {  // B_(i-1)[a][j], i - 1 >= 1 by the rule above
-                  const int a = p - me;
-                  atomicXor(&Xp[a * P + (j >> 5)], 1u << (j & 31));
-                  const int pos = j < me ? j : -1;
-                  flip_state(Sp, ex, a, pitch, pos, odd_step(pos, nn), t, nn, e);
-                }
-              }
-            }
-            atomicMax(&ctl[0], static_cast<uint32_t>(h + 1));
+            // the line becomes a word of its code: its own state is zero
+            for (int k = 0; k <= f.t; ++k) S[k] = 0;
+            stair_flips<NC>(f, f.tile(ln.i), f.tile(ln.i - 1), ln.i, ln.j, top, h, fm);
           }
           wave_sync();  // the next trip reuses the wavefront's columns
         }
         __syncthreads();
-        if (h + 1 - static_cast<int>(ctl[0]) >= 2) break;  // a fixed point; the same value in every lane of the workgroup
+        if (stair_quiet(f, h)) break;  // a fixed point
       }
       if (b < b_last) {  // block b is final; its tile and state are the next block's
         if (b >= 1) retire(b);
         __syncthreads();
       }
     }
-    for (int blk = b_last > 1 ? b_last : 1; blk <= L; ++blk) retire(blk);
-    __syncthreads();
-    if (tid == 0) store_results(nflip_out, nullptr, status_out, s, ctl);
-    __syncthreads();  // the next stream overwrites the ring and ctl
+    stair_finish(f, L, s, nflip_out, status_out, retire);
   }
 }
 
@@ -264,28 +175,23 @@ StaircaseShape staircase_shape(const cc_staircase *sc) {
   return s;
 }
 
-size_t staircase_lds_bytes(const cc_staircase *sc) {
-  const StaircaseShape s = staircase_shape(sc);
-  return stair_lds_bytes(static_cast<int>(s.m), static_cast<int>(sc->code->tab.roots.size()) / 2, static_cast<int>(sc->window));
-}
+size_t staircase_lds_bytes(const cc_staircase *sc) { return stair_launch(sc, 1, 1).lds; }
 
 int launch_staircase_decode(const cc_staircase *sc, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip, int32_t *d_status,
                             size_t B, hipStream_t stream) {
   if (B == 0) return CC_OK;
   const cc_code *code = sc->code;
   const StaircaseShape s = staircase_shape(sc);
-  const bool wide = 2 * s.m > 64;
-  const int col_bytes = bm_columns(static_cast<int>(code->tab.roots.size()) & ~1).end;
-  const size_t lds = staircase_lds_bytes(sc);
-  const auto kernel = wide ? staircase_kernel<4> : staircase_kernel<1>;
-  if (lds > 64 * 1024) {  // a long window of large blocks asks for more than the default limit
+  const StairLaunch sl = stair_launch(sc, 1, 1);
+  const auto kernel = sl.wide ? staircase_kernel<4> : staircase_kernel<1>;
+  if (sl.lds > 64 * 1024) {  // a long window of large blocks asks for more than the default limit
     static LdsOptIn once[2];
-    if (int rc = lds_opt_in(reinterpret_cast<const void *>(kernel), once[wide], code->device, 160 * 1024, "staircase kernel LDS attribute"))
+    if (int rc = lds_opt_in(reinterpret_cast<const void *>(kernel), once[sl.wide], code->device, 160 * 1024, "staircase kernel LDS attribute"))
       return rc;
   }
-  hipLaunchKernelGGL(kernel, dim3(capped_grid(code, B)), dim3(256), lds, stream, code->d_alg, d_in, d_out, d_nflip, d_status,
+  hipLaunchKernelGGL(kernel, dim3(capped_grid(code, B)), dim3(256), sl.lds, stream, code->d_alg, d_in, d_out, d_nflip, d_status,
                      static_cast<unsigned long long>(B), static_cast<int>(s.L), static_cast<int>(sc->window),
-                     static_cast<int>(sc->iters), s.e, col_bytes);
+                     static_cast<int>(sc->iters), s.e, sl.col_bytes);
   const hipError_t err = hipGetLastError();
   return err != hipSuccess ? hip_fail(err, "staircase kernel launch") : CC_OK;
 }

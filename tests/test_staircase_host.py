@@ -37,6 +37,13 @@ CASES = {
     "m127": ((8, 2, 254), False, 4, 1, 9, 0.0033, 8, 7),
     "m128e": ((8, 2, None), True, 3, 2, 4, 0.003, 4, 7),
     "m128e_t15_w16": ((8, 15, None), True, 16, 1, 17, 0.04, 2, 7),
+    # block sides between the chunk boundaries of a line: a 64-bit chunk holds bits of both halves, and the row half ends
+    # inside a dword.  m40: chunk 0 is 40 row + 24 column bits, the second dword of a row 8 bits wide; m80: three dwords
+    # per row, chunk 1 is 16 row + 48 column bits; m48e (shortened and extended, m - e = 47): the parity position n = 95
+    # is bit 31 of chunk 1
+    "m40": ((7, 2, 80), False, 4, 2, 9, 0.015, 8, 7),
+    "m80": ((8, 2, 160), False, 4, 2, 9, 0.008, 8, 7),
+    "m48e": ((7, 2, 95), True, 4, 2, 9, 0.014, 8, 11),
 }
 # the two smallest tiles through every window, iteration count and stream length: L < W - 1 (one position, a short
 # window), L = W - 1, L = W (the first slide), L = 2W + 1 (the ring wraps twice)
@@ -368,10 +375,12 @@ def test_model_batches_are_not_degenerate():
             assert s["refused"] > 0, (name, s)  # an extended line whose candidate d <= t refuses
         else:
             assert s["refused"] == 0
-            if name in ("m7", "m15", "m31"):  # every plain case is shortened by one: a root at the virtual position
+            if name in ("m7", "m15", "m31"):  # plain cases shortened by one: a root at the virtual position
                 assert s["virtual"] > 0, (name, s)
     assert stats["m7"]["zero_rule"] > 0 and stats["m8e"]["zero_rule"] > 0  # a line the B_0 rule keeps, plain and extended
     assert sum(s["zero_rule"] for s in stats.values()) >= 5
+    for name in ("m40", "m80", "m48e"):  # and where a chunk of the line holds both halves
+        assert stats[name]["zero_rule"] > 0, (name, stats[name])
     assert stats["m128e_t15_w16"]["converged"] >= 1
 
 

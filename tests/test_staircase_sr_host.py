@@ -55,6 +55,10 @@ CASES = {
     "m127": ((8, 2, 254), False, 4, 9, 8, 7, 0.0033),
     "m128e": ((8, 2, None), True, 3, 4, 4, 7, 0.003),
     "m128e_t15_w4": ((8, 15, None), True, 4, 5, 4, 7, 0.04),
+    # block sides between the chunk boundaries of a line (tests/test_staircase_host.py says what each is there for)
+    "m40": ((7, 2, 80), False, 4, 9, 8, 7, 0.015),
+    "m80": ((8, 2, 160), False, 4, 9, 8, 7, 0.008),
+    "m48e": ((7, 2, 95), True, 4, 9, 8, 11, 0.014),
 }
 SWEEP_TILES = {"m7": ((4, 1, 14), False, 0.05), "m8e": ((4, 1, None), True, 0.045)}
 SWEEP_WINDOWS = (2, 3, 4, 16)
