@@ -1,8 +1,9 @@
 // capi.hip -- the extern "C" boundary of libchannelcoding_amd.so.
 // Every function mirrors a member of the reference's cyclic<>/primitive_bch/rs
-// API (see include/channelcoding_amd.h for the file:line map).  Host-pointer
-// entry points stage through device memory and call the _dev ones; there is no
-// CPU decode path in this library.
+// API (see include/channelcoding_amd.h for the file:line map).  A host-pointer
+// entry point and its _dev twin are one definition (`Where`, run_call below):
+// the host form stages through device memory; there is no CPU decode path in
+// this library.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -40,6 +41,34 @@ struct DeviceGuard {
     if (switched) (void)hipSetDevice(prev);
   }
 };
+
+// An entry point X and its twin X_dev share one definition: the argument checks in the order the header states, the
+// typed list of the call's arrays and the launch.  `Where` says on which side it runs: X_dev on the caller's device
+// arrays and stream, X on host arrays.  What only the host form can check (symbols_in_field, erasures_in_range: the
+// values are in host memory) stands in the definition under `at.host && B`; an empty host call ends in run_call.
+struct Where {
+  bool host;
+  hipStream_t stream;
+};
+constexpr Where kFromHost{true, nullptr};
+Where on_device(void *stream) { return {false, static_cast<hipStream_t>(stream)}; }
+
+// The last step of a definition: launch on the B frames of the caller's device arrays, or on staged chunks of the
+// caller's host arrays (chunk_width, granule, csr and the launch's arguments: staged_call in host_stage.hpp).  `code`
+// names the device and owns the staging.
+template <class Erasures, class Launch, class... T>
+int run_call(const cc_code *code, Where at, size_t B, size_t chunk_width, size_t granule, Erasures csr, Launch launch,
+             Arr<T>... arrays) {
+  if (at.host && B == 0) return CC_OK;
+  DeviceGuard guard(code->device);
+  if (at.host) return staged_call(code, B, chunk_width, granule, csr, launch, arrays...);
+  return launch_on<Erasures>(launch, B, at.stream, csr.erasures, csr.offsets, arrays.host...);
+}
+
+bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return a && b && a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
+}
 
 bool is_soft(int alg) { return alg >= CC_ALG_MS && alg <= CC_ALG_2DNMS; }
 bool is_hard(int alg) { return alg >= CC_ALG_PGZ && alg <= CC_ALG_EUKLID; }
@@ -596,24 +625,8 @@ double cc_sigma(const cc_code *c, double ebno_db) {
 
 /* ------------------------------ soft decode ------------------------------ */
 
-int cc_correct_soft_batch_dev(const cc_code *code, const float *d_llr, const uint16_t *d_erasures,
-                              const uint32_t *d_erasure_offsets, uint8_t *d_hard, float *d_L, uint16_t *d_iters,
-                              int32_t *d_status, size_t B, void *stream) {
-  if (!code || (B && (!d_llr || !d_hard))) return CC_ERR_INVALID_ARGUMENT;
-  if ((d_erasures == nullptr) != (d_erasure_offsets == nullptr)) return CC_ERR_INVALID_ARGUMENT;
-  if (!code->soft) {
-    set_last_error("code was created with a hard-decision algorithm; use cc_correct_hard_f32_batch");
-    return CC_ERR_INVALID_ARGUMENT;
-  }
-  if (code->device == CC_DEVICE_NONE) return CC_ERR_NO_DEVICE;
-  DeviceGuard guard(code->device);
-  return launch_minsum(code, d_llr, d_erasures, d_erasure_offsets, d_hard, d_L, d_iters, d_status, B,
-                       static_cast<hipStream_t>(stream));
-}
-
-int cc_correct_soft_batch(const cc_code *code, const float *llr, const uint16_t *erasures,
-                          const uint32_t *erasure_offsets, uint8_t *hard, float *L, uint16_t *iters, int32_t *status,
-                          size_t B) {
+static int soft_call(const cc_code *code, Where at, const float *llr, const uint16_t *erasures, const uint32_t *erasure_offsets,
+                     uint8_t *hard, float *L, uint16_t *iters, int32_t *status, size_t B) {
   if (!code || (B && (!llr || !hard))) return CC_ERR_INVALID_ARGUMENT;
   if ((erasures == nullptr) != (erasure_offsets == nullptr)) return CC_ERR_INVALID_ARGUMENT;
   if (!code->soft) {
@@ -621,21 +634,27 @@ int cc_correct_soft_batch(const cc_code *code, const float *llr, const uint16_t 
     return CC_ERR_INVALID_ARGUMENT;
   }
   if (code->device == CC_DEVICE_NONE) return CC_ERR_NO_DEVICE;
-  if (B == 0) return CC_OK;
   const size_t n = code->tab.n;
-  if (!erasures_in_range(erasures, erasure_offsets, B, n)) return CC_ERR_INVALID_ARGUMENT;
-  DeviceGuard guard(code->device);
-  // (iters and status get device buffers whether wanted or not: the kernels write them; L only when wanted)
-  const StagedStream streams[] = {stage_in(0, llr, n * sizeof(float)), stage_out(1, hard, n), stage_out(2, iters, sizeof(uint16_t)),
-                                  stage_out(3, status, sizeof(int32_t)), stage_out(4, L, n * sizeof(float))};
-  return staged_call(code, B, n * sizeof(float), 1, streams, L ? 5 : 4, erasures, erasure_offsets,
-                     [&](size_t m, void *const *d, const uint16_t *d_er, const uint32_t *d_off, hipStream_t s) {
-                       return launch_minsum(code, static_cast<const float *>(d[0]), d_er, d_off, static_cast<uint8_t *>(d[1]),
-                                            static_cast<float *>(d[4]), static_cast<uint16_t *>(d[2]),
-                                            static_cast<int32_t *>(d[3]), m, s);
-                     });
+  if (at.host && B && !erasures_in_range(erasures, erasure_offsets, B, n)) return CC_ERR_INVALID_ARGUMENT;
+  // (L == NULL selects the kernels without the a-posteriori output)
+  return run_call(code, at, B, n * sizeof(float), 1, Csr{erasures, erasure_offsets},
+                  [&](size_t m, hipStream_t s, const uint16_t *d_er, const uint32_t *d_off, const float *d_llr, uint8_t *d_hard,
+                      float *d_L, uint16_t *d_iters, int32_t *d_status) {
+                    return launch_minsum(code, d_llr, d_er, d_off, d_hard, d_L, d_iters, d_status, m, s);
+                  },
+                  array_in(llr, n), array_out(hard, n), array_out_if_wanted(L, n), array_out(iters, 1), array_out(status, 1));
 }
 
+int cc_correct_soft_batch_dev(const cc_code *code, const float *d_llr, const uint16_t *d_erasures,
+                              const uint32_t *d_erasure_offsets, uint8_t *d_hard, float *d_L, uint16_t *d_iters,
+                              int32_t *d_status, size_t B, void *stream) {
+  return soft_call(code, on_device(stream), d_llr, d_erasures, d_erasure_offsets, d_hard, d_L, d_iters, d_status, B);
+}
+int cc_correct_soft_batch(const cc_code *code, const float *llr, const uint16_t *erasures,
+                          const uint32_t *erasure_offsets, uint8_t *hard, float *L, uint16_t *iters, int32_t *status,
+                          size_t B) {
+  return soft_call(code, kFromHost, llr, erasures, erasure_offsets, hard, L, iters, status, B);
+}
 
 /* ------------------------------ hard decode ------------------------------ */
 
@@ -663,21 +682,6 @@ static int hard_supported(const cc_code *code, bool erasures) {
   }
   if (code->device == CC_DEVICE_NONE) return CC_ERR_NO_DEVICE;
   return CC_OK;
-}
-
-int cc_correct_hard_batch_dev(const cc_code *code, const uint8_t *d_in, const uint16_t *d_erasures,
-                              const uint32_t *d_erasure_offsets, uint8_t *d_out, int32_t *d_nerr, int32_t *d_status,
-                              size_t B, void *stream) {
-  if (!code || (B && (!d_in || !d_out))) return CC_ERR_INVALID_ARGUMENT;
-  if ((d_erasures == nullptr) != (d_erasure_offsets == nullptr)) return CC_ERR_INVALID_ARGUMENT;
-  const int rc = hard_supported(code, d_erasures != nullptr);
-  if (rc != CC_OK) return rc;
-  DeviceGuard guard(code->device);
-  if (d_erasures && code->desc.algorithm == CC_ALG_PGZ)
-    return launch_pgz_erasures(code, d_in, d_erasures, d_erasure_offsets, d_out, d_nerr, d_status, B,
-                               static_cast<hipStream_t>(stream));
-  return launch_algebraic(code, false, d_in, d_erasures, d_erasure_offsets, d_out, d_nerr, d_status, B,
-                          static_cast<hipStream_t>(stream));
 }
 
 int cc_hard_route(const cc_code *code, size_t B, int with_erasures) {
@@ -719,47 +723,45 @@ static int hard_dev(const cc_code *code, bool float_in, const void *d_in, const 
   return rc;
 }
 
-int cc_correct_hard_f32_batch_dev(const cc_code *code, const float *d_in, const uint16_t *d_erasures,
-                                  const uint32_t *d_erasure_offsets, uint8_t *d_out, int32_t *d_nerr,
-                                  int32_t *d_status, size_t B, void *stream) {
-  if (!code || (B && (!d_in || !d_out))) return CC_ERR_INVALID_ARGUMENT;
-  if ((d_erasures == nullptr) != (d_erasure_offsets == nullptr)) return CC_ERR_INVALID_ARGUMENT;
-  const int rc = hard_supported(code, d_erasures != nullptr);
-  if (rc != CC_OK) return rc;
-  DeviceGuard guard(code->device);
-  return hard_dev(code, true, d_in, d_erasures, d_erasure_offsets, d_out, d_nerr, d_status, B,
-                  static_cast<hipStream_t>(stream));
-}
-
-static int hard_host(const cc_code *code, bool float_in, const void *in, const uint16_t *erasures,
+// cc_correct_hard_batch(_dev) and cc_correct_hard_f32_batch(_dev).  `in` is the one array of this file that is staged
+// untyped: n bytes or n floats per frame, which hard_dev reads by float_in; it travels as the bytes it is made of.
+static int hard_call(const cc_code *code, Where at, bool float_in, const void *in_raw, const uint16_t *erasures,
                      const uint32_t *erasure_offsets, uint8_t *out, int32_t *nerr, int32_t *status, size_t B) {
-  if (!code || (B && (!in || !out))) return CC_ERR_INVALID_ARGUMENT;
+  if (!code || (B && (!in_raw || !out))) return CC_ERR_INVALID_ARGUMENT;
   if ((erasures == nullptr) != (erasure_offsets == nullptr)) return CC_ERR_INVALID_ARGUMENT;
   const int rc = hard_supported(code, erasures != nullptr);
   if (rc != CC_OK) return rc;
-  if (B == 0) return CC_OK;
-  const size_t n = code->tab.n;
-  if (!float_in && !symbols_in_field(static_cast<const uint8_t *>(in), B * n, code->tab.q)) return CC_ERR_NOT_IN_FIELD;
-  if (!erasures_in_range(erasures, erasure_offsets, B, n)) return CC_ERR_INVALID_ARGUMENT;
-  DeviceGuard guard(code->device);
-  const size_t esz = float_in ? sizeof(float) : 1;
-  const StagedStream streams[] = {stage_in(0, in, n * esz), stage_out(1, out, n), stage_out(2, nerr, sizeof(int32_t)),
-                                  stage_out(3, status, sizeof(int32_t))};
-  return staged_call(code, B, n * esz, 1, streams, 4, erasures, erasure_offsets,
-                     [&](size_t m, void *const *d, const uint16_t *d_er, const uint32_t *d_off, hipStream_t s) {
-                       return hard_dev(code, float_in, d[0], d_er, d_off, static_cast<uint8_t *>(d[1]),
-                                       static_cast<int32_t *>(d[2]), static_cast<int32_t *>(d[3]), m, s);
-                     });
+  const size_t n = code->tab.n, esz = float_in ? sizeof(float) : 1;
+  const uint8_t *bytes = static_cast<const uint8_t *>(in_raw);
+  if (at.host && B) {
+    if (!float_in && !symbols_in_field(bytes, B * n, code->tab.q)) return CC_ERR_NOT_IN_FIELD;
+    if (!erasures_in_range(erasures, erasure_offsets, B, n)) return CC_ERR_INVALID_ARGUMENT;
+  }
+  return run_call(code, at, B, n * esz, 1, Csr{erasures, erasure_offsets},
+                  [&](size_t m, hipStream_t s, const uint16_t *d_er, const uint32_t *d_off, const uint8_t *d_in, uint8_t *d_out,
+                      int32_t *d_nerr, int32_t *d_status) {
+                    return hard_dev(code, float_in, d_in, d_er, d_off, d_out, d_nerr, d_status, m, s);
+                  },
+                  array_in(bytes, n * esz), array_out(out, n), array_out(nerr, 1), array_out(status, 1));
 }
 
+int cc_correct_hard_batch_dev(const cc_code *code, const uint8_t *d_in, const uint16_t *d_erasures,
+                              const uint32_t *d_erasure_offsets, uint8_t *d_out, int32_t *d_nerr, int32_t *d_status,
+                              size_t B, void *stream) {
+  return hard_call(code, on_device(stream), false, d_in, d_erasures, d_erasure_offsets, d_out, d_nerr, d_status, B);
+}
 int cc_correct_hard_batch(const cc_code *code, const uint8_t *in, const uint16_t *erasures,
                           const uint32_t *erasure_offsets, uint8_t *out, int32_t *nerr, int32_t *status, size_t B) {
-  return hard_host(code, false, in, erasures, erasure_offsets, out, nerr, status, B);
+  return hard_call(code, kFromHost, false, in, erasures, erasure_offsets, out, nerr, status, B);
 }
-
+int cc_correct_hard_f32_batch_dev(const cc_code *code, const float *d_in, const uint16_t *d_erasures,
+                                  const uint32_t *d_erasure_offsets, uint8_t *d_out, int32_t *d_nerr,
+                                  int32_t *d_status, size_t B, void *stream) {
+  return hard_call(code, on_device(stream), true, d_in, d_erasures, d_erasure_offsets, d_out, d_nerr, d_status, B);
+}
 int cc_correct_hard_f32_batch(const cc_code *code, const float *in, const uint16_t *erasures,
                               const uint32_t *erasure_offsets, uint8_t *out, int32_t *nerr, int32_t *status, size_t B) {
-  return hard_host(code, true, in, erasures, erasure_offsets, out, nerr, status, B);
+  return hard_call(code, kFromHost, true, in, erasures, erasure_offsets, out, nerr, status, B);
 }
 
 /* ------------------------------ Chase-II, GMD ------------------------------ */
@@ -790,29 +792,26 @@ static int chase_supported(const cc_code *code, uint32_t p) {
   return code->device == CC_DEVICE_NONE ? CC_ERR_NO_DEVICE : CC_OK;
 }
 
-int cc_correct_chase_batch_dev(const cc_code *code, const float *d_llr, uint32_t p, uint8_t *d_out, int32_t *d_nerr,
-                               float *d_metric, int32_t *d_status, size_t B, void *stream) {
-  if (!code || (B && (!d_llr || !d_out))) return CC_ERR_INVALID_ARGUMENT;
-  if (int rc = chase_supported(code, p)) return rc;
-  DeviceGuard guard(code->device);
-  return launch_chase(code, d_llr, p, d_out, d_nerr, d_metric, d_status, B, static_cast<hipStream_t>(stream));
-}
-
-int cc_correct_chase_batch(const cc_code *code, const float *llr, uint32_t p, uint8_t *out, int32_t *nerr, float *metric,
-                           int32_t *status, size_t B) {
+static int chase_call(const cc_code *code, Where at, const float *llr, uint32_t p, uint8_t *out, int32_t *nerr, float *metric,
+                      int32_t *status, size_t B) {
   if (!code || (B && (!llr || !out))) return CC_ERR_INVALID_ARGUMENT;
   if (int rc = chase_supported(code, p)) return rc;
-  if (B == 0) return CC_OK;
   const size_t n = code->tab.n;
-  DeviceGuard guard(code->device);
-  const StagedStream streams[] = {stage_in(0, llr, n * sizeof(float)), stage_out(1, out, n), stage_out(2, nerr, sizeof(int32_t)),
-                                  stage_out(3, status, sizeof(int32_t)), stage_out(4, metric, sizeof(float))};
-  return staged_call(code, B, n * sizeof(float), 1, streams, 5, nullptr, nullptr,
-                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t s) {
-                       return launch_chase(code, static_cast<const float *>(d[0]), p, static_cast<uint8_t *>(d[1]),
-                                           static_cast<int32_t *>(d[2]), static_cast<float *>(d[4]),
-                                           static_cast<int32_t *>(d[3]), m, s);
-                     });
+  return run_call(code, at, B, n * sizeof(float), 1, NoCsr{},
+                  [&](size_t m, hipStream_t s, const float *d_llr, uint8_t *d_out, int32_t *d_nerr, float *d_metric,
+                      int32_t *d_status) {
+                    return launch_chase(code, d_llr, p, d_out, d_nerr, d_metric, d_status, m, s);
+                  },
+                  array_in(llr, n), array_out(out, n), array_out(nerr, 1), array_out(metric, 1), array_out(status, 1));
+}
+
+int cc_correct_chase_batch_dev(const cc_code *code, const float *d_llr, uint32_t p, uint8_t *d_out, int32_t *d_nerr,
+                               float *d_metric, int32_t *d_status, size_t B, void *stream) {
+  return chase_call(code, on_device(stream), d_llr, p, d_out, d_nerr, d_metric, d_status, B);
+}
+int cc_correct_chase_batch(const cc_code *code, const float *llr, uint32_t p, uint8_t *out, int32_t *nerr, float *metric,
+                           int32_t *status, size_t B) {
+  return chase_call(code, kFromHost, llr, p, out, nerr, metric, status, B);
 }
 
 // What the soft-output calls refuse, in the order the header states: what the Chase calls refuse short of the device,
@@ -821,39 +820,35 @@ static int chase_soft_supported(const cc_code *code, uint32_t p, float beta, con
   const int rc = chase_supported(code, p);
   if (rc != CC_OK && rc != CC_ERR_NO_DEVICE) return rc;
   if (!(beta >= 0.0f) || std::isinf(beta)) return CC_ERR_INVALID_ARGUMENT;
-  const uintptr_t a = reinterpret_cast<uintptr_t>(llr), b = reinterpret_cast<uintptr_t>(ext);
   const size_t bytes = B * code->tab.n * sizeof(float);
-  if (bytes && a < b + bytes && b < a + bytes) return CC_ERR_INVALID_ARGUMENT;
+  if (ranges_overlap(llr, bytes, ext, bytes)) return CC_ERR_INVALID_ARGUMENT;
   return rc;
+}
+
+static int chase_soft_call(const cc_code *code, Where at, const float *llr, uint32_t p, float beta, uint8_t *out, float *ext,
+                           int32_t *nerr, float *metric, int32_t *status, size_t B) {
+  if (!code || (B && (!llr || !out || !ext))) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = chase_soft_supported(code, p, beta, llr, ext, B)) return rc;
+  const size_t n = code->tab.n;
+  return run_call(code, at, B, n * sizeof(float), 1, NoCsr{},
+                  [&](size_t m, hipStream_t s, const float *d_llr, uint8_t *d_out, float *d_ext, int32_t *d_nerr, float *d_metric,
+                      int32_t *d_status) {
+                    return launch_chase_soft(code, d_llr, p, beta, d_out, d_ext, d_nerr, d_metric, d_status, m, s);
+                  },
+                  array_in(llr, n), array_out(out, n), array_out(ext, n), array_out(nerr, 1), array_out(metric, 1),
+                  array_out(status, 1));
 }
 
 int cc_correct_chase_soft_batch_dev(const cc_code *code, const float *d_llr, uint32_t p, float beta, uint8_t *d_out,
                                     float *d_ext, int32_t *d_nerr, float *d_metric, int32_t *d_status, size_t B,
                                     void *stream) {
-  if (!code || (B && (!d_llr || !d_out || !d_ext))) return CC_ERR_INVALID_ARGUMENT;
-  if (int rc = chase_soft_supported(code, p, beta, d_llr, d_ext, B)) return rc;
-  DeviceGuard guard(code->device);
-  return launch_chase_soft(code, d_llr, p, beta, d_out, d_ext, d_nerr, d_metric, d_status, B,
-                           static_cast<hipStream_t>(stream));
+  return chase_soft_call(code, on_device(stream), d_llr, p, beta, d_out, d_ext, d_nerr, d_metric, d_status, B);
 }
-
 int cc_correct_chase_soft_batch(const cc_code *code, const float *llr, uint32_t p, float beta, uint8_t *out, float *ext,
                                 int32_t *nerr, float *metric, int32_t *status, size_t B) {
-  if (!code || (B && (!llr || !out || !ext))) return CC_ERR_INVALID_ARGUMENT;
-  if (int rc = chase_soft_supported(code, p, beta, llr, ext, B)) return rc;
-  if (B == 0) return CC_OK;
-  const size_t n = code->tab.n;
-  DeviceGuard guard(code->device);
-  const StagedStream streams[] = {stage_in(0, llr, n * sizeof(float)),   stage_out(1, out, n),
-                                  stage_out(2, nerr, sizeof(int32_t)),   stage_out(3, status, sizeof(int32_t)),
-                                  stage_out(4, metric, sizeof(float)),   stage_out(7, ext, n * sizeof(float))};
-  return staged_call(code, B, n * sizeof(float), 1, streams, 6, nullptr, nullptr,
-                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t s) {
-                       return launch_chase_soft(code, static_cast<const float *>(d[0]), p, beta, static_cast<uint8_t *>(d[1]),
-                                                static_cast<float *>(d[5]), static_cast<int32_t *>(d[2]),
-                                                static_cast<float *>(d[4]), static_cast<int32_t *>(d[3]), m, s);
-                     });
+  return chase_soft_call(code, kFromHost, llr, p, beta, out, ext, nerr, metric, status, B);
 }
+
 
 int cc_chase_frames_per_wavefront(const cc_code *code, uint32_t p, int soft) {
   if (!code) return 0;
@@ -874,29 +869,26 @@ static int osd_supported(const cc_code *code, uint32_t order) {
   return code->device == CC_DEVICE_NONE ? CC_ERR_NO_DEVICE : CC_OK;
 }
 
-int cc_correct_osd_batch_dev(const cc_code *code, const float *d_llr, uint32_t order, uint8_t *d_out, int32_t *d_nerr,
-                             float *d_metric, int32_t *d_status, size_t B, void *stream) {
-  if (!code || (B && (!d_llr || !d_out))) return CC_ERR_INVALID_ARGUMENT;
-  if (int rc = osd_supported(code, order)) return rc;
-  DeviceGuard guard(code->device);
-  return launch_osd(code, d_llr, order, d_out, d_nerr, d_metric, d_status, B, static_cast<hipStream_t>(stream));
-}
-
-int cc_correct_osd_batch(const cc_code *code, const float *llr, uint32_t order, uint8_t *out, int32_t *nerr, float *metric,
-                         int32_t *status, size_t B) {
+static int osd_call(const cc_code *code, Where at, const float *llr, uint32_t order, uint8_t *out, int32_t *nerr, float *metric,
+                    int32_t *status, size_t B) {
   if (!code || (B && (!llr || !out))) return CC_ERR_INVALID_ARGUMENT;
   if (int rc = osd_supported(code, order)) return rc;
-  if (B == 0) return CC_OK;
   const size_t n = code->tab.n;
-  DeviceGuard guard(code->device);
-  const StagedStream streams[] = {stage_in(0, llr, n * sizeof(float)), stage_out(1, out, n), stage_out(2, nerr, sizeof(int32_t)),
-                                  stage_out(3, status, sizeof(int32_t)), stage_out(4, metric, sizeof(float))};
-  return staged_call(code, B, n * sizeof(float), 1, streams, 5, nullptr, nullptr,
-                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t s) {
-                       return launch_osd(code, static_cast<const float *>(d[0]), order, static_cast<uint8_t *>(d[1]),
-                                         static_cast<int32_t *>(d[2]), static_cast<float *>(d[4]),
-                                         static_cast<int32_t *>(d[3]), m, s);
-                     });
+  return run_call(code, at, B, n * sizeof(float), 1, NoCsr{},
+                  [&](size_t m, hipStream_t s, const float *d_llr, uint8_t *d_out, int32_t *d_nerr, float *d_metric,
+                      int32_t *d_status) {
+                    return launch_osd(code, d_llr, order, d_out, d_nerr, d_metric, d_status, m, s);
+                  },
+                  array_in(llr, n), array_out(out, n), array_out(nerr, 1), array_out(metric, 1), array_out(status, 1));
+}
+
+int cc_correct_osd_batch_dev(const cc_code *code, const float *d_llr, uint32_t order, uint8_t *d_out, int32_t *d_nerr,
+                             float *d_metric, int32_t *d_status, size_t B, void *stream) {
+  return osd_call(code, on_device(stream), d_llr, order, d_out, d_nerr, d_metric, d_status, B);
+}
+int cc_correct_osd_batch(const cc_code *code, const float *llr, uint32_t order, uint8_t *out, int32_t *nerr, float *metric,
+                         int32_t *status, size_t B) {
+  return osd_call(code, kFromHost, llr, order, out, nerr, metric, status, B);
 }
 
 int cc_osd_frames_per_wavefront(const cc_code *code, uint32_t order) {
@@ -912,42 +904,37 @@ static int chase_extended_supported(const cc_code *code, uint32_t p, float beta,
   if (rc != CC_OK && rc != CC_ERR_NO_DEVICE) return rc;
   if (ext) {
     if (!(beta >= 0.0f) || std::isinf(beta)) return CC_ERR_INVALID_ARGUMENT;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(llr), b = reinterpret_cast<uintptr_t>(ext);
     const size_t bytes = B * (code->tab.n + 1) * sizeof(float);
-    if (bytes && a < b + bytes && b < a + bytes) return CC_ERR_INVALID_ARGUMENT;
+    if (ranges_overlap(llr, bytes, ext, bytes)) return CC_ERR_INVALID_ARGUMENT;
   }
   return rc;
+}
+
+static int chase_extended_call(const cc_code *code, Where at, const float *llr, uint32_t p, float beta, uint8_t *out, float *ext,
+                               int32_t *nerr, float *metric, int32_t *status, size_t B) {
+  if (!code || (B && (!llr || !out))) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = chase_extended_supported(code, p, beta, llr, ext, B)) return rc;
+  const size_t w = code->tab.n + 1;
+  // (ext == NULL selects the hard-output kernel)
+  return run_call(code, at, B, w * sizeof(float), 1, NoCsr{},
+                  [&](size_t m, hipStream_t s, const float *d_llr, uint8_t *d_out, float *d_ext, int32_t *d_nerr, float *d_metric,
+                      int32_t *d_status) {
+                    return launch_chase_extended(code, d_llr, p, beta, d_out, d_ext, d_nerr, d_metric, d_status, m, s);
+                  },
+                  array_in(llr, w), array_out(out, w), array_out_if_wanted(ext, w), array_out(nerr, 1), array_out(metric, 1),
+                  array_out(status, 1));
 }
 
 int cc_correct_chase_extended_batch_dev(const cc_code *code, const float *d_llr, uint32_t p, float beta, uint8_t *d_out,
                                         float *d_ext, int32_t *d_nerr, float *d_metric, int32_t *d_status, size_t B,
                                         void *stream) {
-  if (!code || (B && (!d_llr || !d_out))) return CC_ERR_INVALID_ARGUMENT;
-  if (int rc = chase_extended_supported(code, p, beta, d_llr, d_ext, B)) return rc;
-  DeviceGuard guard(code->device);
-  return launch_chase_extended(code, d_llr, p, beta, d_out, d_ext, d_nerr, d_metric, d_status, B,
-                               static_cast<hipStream_t>(stream));
+  return chase_extended_call(code, on_device(stream), d_llr, p, beta, d_out, d_ext, d_nerr, d_metric, d_status, B);
 }
-
 int cc_correct_chase_extended_batch(const cc_code *code, const float *llr, uint32_t p, float beta, uint8_t *out, float *ext,
                                     int32_t *nerr, float *metric, int32_t *status, size_t B) {
-  if (!code || (B && (!llr || !out))) return CC_ERR_INVALID_ARGUMENT;
-  if (int rc = chase_extended_supported(code, p, beta, llr, ext, B)) return rc;
-  if (B == 0) return CC_OK;
-  const size_t w = code->tab.n + 1;
-  DeviceGuard guard(code->device);
-  // (ext == NULL leaves the last stream out: no buffer, and the launcher's nullptr selects the hard-output kernel)
-  const StagedStream streams[] = {stage_in(0, llr, w * sizeof(float)),   stage_out(1, out, w),
-                                  stage_out(2, nerr, sizeof(int32_t)),   stage_out(3, status, sizeof(int32_t)),
-                                  stage_out(4, metric, sizeof(float)),   stage_out(7, ext, w * sizeof(float))};
-  return staged_call(code, B, w * sizeof(float), 1, streams, ext ? 6 : 5, nullptr, nullptr,
-                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t s) {
-                       return launch_chase_extended(code, static_cast<const float *>(d[0]), p, beta,
-                                                    static_cast<uint8_t *>(d[1]), static_cast<float *>(d[5]),
-                                                    static_cast<int32_t *>(d[2]), static_cast<float *>(d[4]),
-                                                    static_cast<int32_t *>(d[3]), m, s);
-                     });
+  return chase_extended_call(code, kFromHost, llr, p, beta, out, ext, nerr, metric, status, B);
 }
+
 
 int cc_chase_extended_frames_per_wavefront(const cc_code *code, uint32_t p, int soft) {
   if (!code) return 0;
@@ -964,80 +951,62 @@ static int gmd_supported(const cc_code *code, uint32_t trials) {
 }
 static unsigned gmd_trials(const cc_code *code, uint32_t trials) { return trials == CC_GMD_ALL ? code->tab.t + 1 : trials; }
 
-int cc_correct_gmd_batch_dev(const cc_code *code, const uint8_t *d_words, const float *d_rel, uint32_t trials, uint8_t *d_out,
-                             int32_t *d_nerr, float *d_metric, int32_t *d_status, size_t B, void *stream) {
-  if (!code || (B && (!d_words || !d_rel || !d_out))) return CC_ERR_INVALID_ARGUMENT;
-  if (int rc = gmd_supported(code, trials)) return rc;
-  DeviceGuard guard(code->device);
-  return launch_gmd(code, d_words, d_rel, gmd_trials(code, trials), d_out, d_nerr, d_metric, d_status, B,
-                    static_cast<hipStream_t>(stream));
-}
-
-int cc_correct_gmd_batch(const cc_code *code, const uint8_t *words, const float *rel, uint32_t trials, uint8_t *out,
-                         int32_t *nerr, float *metric, int32_t *status, size_t B) {
+static int gmd_call(const cc_code *code, Where at, const uint8_t *words, const float *rel, uint32_t trials, uint8_t *out,
+                    int32_t *nerr, float *metric, int32_t *status, size_t B) {
   if (!code || (B && (!words || !rel || !out))) return CC_ERR_INVALID_ARGUMENT;
   if (int rc = gmd_supported(code, trials)) return rc;
-  if (B == 0) return CC_OK;
   const size_t n = code->tab.n;
-  if (!symbols_in_field(words, B * n, code->tab.q)) return CC_ERR_NOT_IN_FIELD;
-  DeviceGuard guard(code->device);
-  const unsigned m = gmd_trials(code, trials);
-  const StagedStream streams[] = {stage_in(0, words, n), stage_in(7, rel, n * sizeof(float)), stage_out(1, out, n),
-                                  stage_out(2, nerr, sizeof(int32_t)), stage_out(3, status, sizeof(int32_t)),
-                                  stage_out(4, metric, sizeof(float))};
-  return staged_call(code, B, n * (1 + sizeof(float)), 1, streams, 6, nullptr, nullptr,
-                     [&](size_t mm, void *const *d, const uint16_t *, const uint32_t *, hipStream_t s) {
-                       return launch_gmd(code, static_cast<const uint8_t *>(d[0]), static_cast<const float *>(d[1]), m,
-                                         static_cast<uint8_t *>(d[2]), static_cast<int32_t *>(d[3]),
-                                         static_cast<float *>(d[5]), static_cast<int32_t *>(d[4]), mm, s);
-                     });
+  if (at.host && B && !symbols_in_field(words, B * n, code->tab.q)) return CC_ERR_NOT_IN_FIELD;
+  const unsigned tr = gmd_trials(code, trials);
+  return run_call(code, at, B, n * (1 + sizeof(float)), 1, NoCsr{},  // (a chunk is sized by words and rel together)
+                  [&](size_t m, hipStream_t s, const uint8_t *d_words, const float *d_rel, uint8_t *d_out, int32_t *d_nerr,
+                      float *d_metric, int32_t *d_status) {
+                    return launch_gmd(code, d_words, d_rel, tr, d_out, d_nerr, d_metric, d_status, m, s);
+                  },
+                  array_in(words, n), array_in(rel, n), array_out(out, n), array_out(nerr, 1), array_out(metric, 1),
+                  array_out(status, 1));
+}
+
+int cc_correct_gmd_batch_dev(const cc_code *code, const uint8_t *d_words, const float *d_rel, uint32_t trials, uint8_t *d_out,
+                             int32_t *d_nerr, float *d_metric, int32_t *d_status, size_t B, void *stream) {
+  return gmd_call(code, on_device(stream), d_words, d_rel, trials, d_out, d_nerr, d_metric, d_status, B);
+}
+int cc_correct_gmd_batch(const cc_code *code, const uint8_t *words, const float *rel, uint32_t trials, uint8_t *out,
+                         int32_t *nerr, float *metric, int32_t *status, size_t B) {
+  return gmd_call(code, kFromHost, words, rel, trials, out, nerr, metric, status, B);
 }
 
 /* ------------------------------ encode / extract ------------------------------ */
 
-int cc_encode_batch_dev(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, void *stream) {
-  if (!code || (B && (!d_msg || !d_cw))) return CC_ERR_INVALID_ARGUMENT;
-  if (needs_code(code) != CC_OK) return CC_ERR_INVALID_ARGUMENT;
-  if (int rc = not_wide(code)) return rc;
-  if (code->device == CC_DEVICE_NONE) return CC_ERR_NO_DEVICE;
-  DeviceGuard guard(code->device);
-  return launch_encode(code, d_msg, d_cw, B, static_cast<hipStream_t>(stream));
-}
-
-int cc_extract_batch_dev(const cc_code *code, const uint8_t *d_cw, uint8_t *d_msg, size_t B, void *stream) {
-  if (!code || (B && (!d_cw || !d_msg))) return CC_ERR_INVALID_ARGUMENT;
-  if (needs_code(code) != CC_OK) return CC_ERR_INVALID_ARGUMENT;
-  if (int rc = not_wide(code)) return rc;
-  if (code->device == CC_DEVICE_NONE) return CC_ERR_NO_DEVICE;
-  DeviceGuard guard(code->device);
-  return launch_extract(code, d_cw, d_msg, B, static_cast<hipStream_t>(stream));
-}
-
-static int byte_map_host(const cc_code *code, bool encode, const uint8_t *src, uint8_t *dst, size_t B) {
+// cc_encode_batch(_dev) and cc_extract_batch(_dev)
+static int byte_map_call(const cc_code *code, Where at, bool encode, const uint8_t *src, uint8_t *dst, size_t B) {
   if (!code || (B && (!src || !dst))) return CC_ERR_INVALID_ARGUMENT;
   if (needs_code(code) != CC_OK) return CC_ERR_INVALID_ARGUMENT;
   if (int rc = not_wide(code)) return rc;
   if (code->device == CC_DEVICE_NONE) return CC_ERR_NO_DEVICE;
-  if (B == 0) return CC_OK;
   const size_t n = code->tab.n, l = code->tab.l;
   const size_t in_w = encode ? l : n, out_w = encode ? n : l;
-  if (encode && !symbols_in_field(src, B * in_w, code->tab.q)) return CC_ERR_NOT_IN_FIELD;
-  DeviceGuard guard(code->device);
-  const StagedStream streams[] = {stage_in(0, src, in_w), stage_out(1, dst, out_w)};
-  return staged_call(code, B, n, 1, streams, 2, nullptr, nullptr,
-                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t s) {
-                       const uint8_t *d_src = static_cast<const uint8_t *>(d[0]);
-                       uint8_t *d_dst = static_cast<uint8_t *>(d[1]);
-                       return encode ? launch_encode(code, d_src, d_dst, m, s) : launch_extract(code, d_src, d_dst, m, s);
-                     });
+  if (at.host && B && encode && !symbols_in_field(src, B * in_w, code->tab.q)) return CC_ERR_NOT_IN_FIELD;
+  return run_call(code, at, B, n, 1, NoCsr{},
+                  [&](size_t m, hipStream_t s, const uint8_t *d_src, uint8_t *d_dst) {
+                    return encode ? launch_encode(code, d_src, d_dst, m, s) : launch_extract(code, d_src, d_dst, m, s);
+                  },
+                  array_in(src, in_w), array_out(dst, out_w));
 }
 
+int cc_encode_batch_dev(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, void *stream) {
+  return byte_map_call(code, on_device(stream), true, d_msg, d_cw, B);
+}
+int cc_extract_batch_dev(const cc_code *code, const uint8_t *d_cw, uint8_t *d_msg, size_t B, void *stream) {
+  return byte_map_call(code, on_device(stream), false, d_cw, d_msg, B);
+}
 int cc_encode_batch(const cc_code *code, const uint8_t *msg, uint8_t *cw, size_t B) {
-  return byte_map_host(code, true, msg, cw, B);
+  return byte_map_call(code, kFromHost, true, msg, cw, B);
 }
 int cc_extract_batch(const cc_code *code, const uint8_t *cw, uint8_t *msg, size_t B) {
-  return byte_map_host(code, false, cw, msg, B);
+  return byte_map_call(code, kFromHost, false, cw, msg, B);
 }
+
 
 /* ------------------------------ decode = correct + extract ------------------------------ */
 
@@ -1111,75 +1080,62 @@ static int wide_correct_ready(const cc_code *code, bool erasures) {
   return wide_ready(code);
 }
 
-int cc_encode_batch_u16_dev(const cc_code *code, const uint16_t *d_msg, uint16_t *d_cw, size_t B, void *stream) {
-  if (!code || (B && (!d_msg || !d_cw))) return CC_ERR_INVALID_ARGUMENT;
+// cc_encode_batch_u16(_dev) and cc_extract_batch_u16(_dev)
+static int wide_map_call(const cc_code *code, Where at, bool encode, const uint16_t *src, uint16_t *dst, size_t B) {
+  if (!code || (B && (!src || !dst))) return CC_ERR_INVALID_ARGUMENT;
   if (int rc = wide_ready(code)) return rc;
-  DeviceGuard guard(code->device);
-  return launch_wide_encode(code, d_msg, d_cw, B, static_cast<hipStream_t>(stream));
+  const size_t n = code->tab.n, l = code->tab.l;
+  const size_t in_w = encode ? l : n, out_w = encode ? n : l;
+  if (at.host && B && encode && !symbols_in_field(src, B * in_w, code->tab.q)) return CC_ERR_NOT_IN_FIELD;
+  return run_call(code, at, B, n * sizeof(uint16_t), 1, NoCsr{},
+                  [&](size_t m, hipStream_t s, const uint16_t *d_src, uint16_t *d_dst) {
+                    return encode ? launch_wide_encode(code, d_src, d_dst, m, s) : launch_wide_extract(code, d_src, d_dst, m, s);
+                  },
+                  array_in(src, in_w), array_out(dst, out_w));
 }
 
+int cc_encode_batch_u16_dev(const cc_code *code, const uint16_t *d_msg, uint16_t *d_cw, size_t B, void *stream) {
+  return wide_map_call(code, on_device(stream), true, d_msg, d_cw, B);
+}
 int cc_extract_batch_u16_dev(const cc_code *code, const uint16_t *d_cw, uint16_t *d_msg, size_t B, void *stream) {
-  if (!code || (B && (!d_cw || !d_msg))) return CC_ERR_INVALID_ARGUMENT;
-  if (int rc = wide_ready(code)) return rc;
-  DeviceGuard guard(code->device);
-  return launch_wide_extract(code, d_cw, d_msg, B, static_cast<hipStream_t>(stream));
+  return wide_map_call(code, on_device(stream), false, d_cw, d_msg, B);
+}
+int cc_encode_batch_u16(const cc_code *code, const uint16_t *msg, uint16_t *cw, size_t B) {
+  return wide_map_call(code, kFromHost, true, msg, cw, B);
+}
+int cc_extract_batch_u16(const cc_code *code, const uint16_t *cw, uint16_t *msg, size_t B) {
+  return wide_map_call(code, kFromHost, false, cw, msg, B);
+}
+
+static int wide_correct_call(const cc_code *code, Where at, const uint16_t *words, const uint16_t *erasures,
+                             const uint32_t *erasure_offsets, uint16_t *out, int32_t *nerr, int32_t *status, size_t B) {
+  if (!code || (B && (!words || !out))) return CC_ERR_INVALID_ARGUMENT;
+  if ((erasures == nullptr) != (erasure_offsets == nullptr)) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = wide_correct_ready(code, erasures != nullptr)) return rc;
+  const size_t n = code->tab.n;
+  if (at.host && B) {
+    if (!symbols_in_field(words, B * n, code->tab.q)) return CC_ERR_NOT_IN_FIELD;
+    if (!erasures_in_range(erasures, erasure_offsets, B, n)) return CC_ERR_INVALID_ARGUMENT;
+  }
+  return run_call(code, at, B, n * sizeof(uint16_t), 1, Csr{erasures, erasure_offsets},
+                  [&](size_t m, hipStream_t s, const uint16_t *d_er, const uint32_t *d_off, const uint16_t *d_words, uint16_t *d_out,
+                      int32_t *d_nerr, int32_t *d_status) {
+                    return launch_wide_correct(code, d_words, d_er, d_off, d_out, d_nerr, d_status, m, s);
+                  },
+                  array_in(words, n), array_out(out, n), array_out(nerr, 1), array_out(status, 1));
 }
 
 int cc_correct_hard_batch_u16_dev(const cc_code *code, const uint16_t *d_in, const uint16_t *d_erasures,
                                   const uint32_t *d_erasure_offsets, uint16_t *d_out, int32_t *d_nerr,
                                   int32_t *d_status, size_t B, void *stream) {
-  if (!code || (B && (!d_in || !d_out))) return CC_ERR_INVALID_ARGUMENT;
-  if ((d_erasures == nullptr) != (d_erasure_offsets == nullptr)) return CC_ERR_INVALID_ARGUMENT;
-  if (int rc = wide_correct_ready(code, d_erasures != nullptr)) return rc;
-  DeviceGuard guard(code->device);
-  return launch_wide_correct(code, d_in, d_erasures, d_erasure_offsets, d_out, d_nerr, d_status, B,
-                             static_cast<hipStream_t>(stream));
+  return wide_correct_call(code, on_device(stream), d_in, d_erasures, d_erasure_offsets, d_out, d_nerr, d_status, B);
 }
-
-// host pointers: same chunked staging as the byte entry points; kind 0 = encode, 1 = extract
-static int wide_map_host(const cc_code *code, int kind, const uint16_t *src, uint16_t *dst, size_t B) {
-  if (!code || (B && (!src || !dst))) return CC_ERR_INVALID_ARGUMENT;
-  if (int rc = wide_ready(code)) return rc;
-  if (B == 0) return CC_OK;
-  const size_t n = code->tab.n, l = code->tab.l;
-  const size_t in_w = kind == 0 ? l : n, out_w = kind == 0 ? n : l;
-  if (kind == 0 && !symbols_in_field(src, B * in_w, code->tab.q)) return CC_ERR_NOT_IN_FIELD;
-  DeviceGuard guard(code->device);
-  const StagedStream streams[] = {stage_in(0, src, in_w * 2), stage_out(1, dst, out_w * 2)};
-  return staged_call(code, B, n * 2, 1, streams, 2, nullptr, nullptr,
-                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t s) {
-                       const uint16_t *d_src = static_cast<const uint16_t *>(d[0]);
-                       uint16_t *d_dst = static_cast<uint16_t *>(d[1]);
-                       return kind == 0 ? launch_wide_encode(code, d_src, d_dst, m, s) : launch_wide_extract(code, d_src, d_dst, m, s);
-                     });
-}
-
-int cc_encode_batch_u16(const cc_code *code, const uint16_t *msg, uint16_t *cw, size_t B) {
-  return wide_map_host(code, 0, msg, cw, B);
-}
-int cc_extract_batch_u16(const cc_code *code, const uint16_t *cw, uint16_t *msg, size_t B) {
-  return wide_map_host(code, 1, cw, msg, B);
-}
-
 int cc_correct_hard_batch_u16(const cc_code *code, const uint16_t *in, const uint16_t *erasures,
                               const uint32_t *erasure_offsets, uint16_t *out, int32_t *nerr, int32_t *status,
                               size_t B) {
-  if (!code || (B && (!in || !out))) return CC_ERR_INVALID_ARGUMENT;
-  if ((erasures == nullptr) != (erasure_offsets == nullptr)) return CC_ERR_INVALID_ARGUMENT;
-  if (int rc = wide_correct_ready(code, erasures != nullptr)) return rc;
-  if (B == 0) return CC_OK;
-  const size_t n = code->tab.n;
-  if (!symbols_in_field(in, B * n, code->tab.q)) return CC_ERR_NOT_IN_FIELD;
-  if (!erasures_in_range(erasures, erasure_offsets, B, n)) return CC_ERR_INVALID_ARGUMENT;
-  DeviceGuard guard(code->device);
-  const StagedStream streams[] = {stage_in(0, in, n * 2), stage_out(1, out, n * 2), stage_out(2, nerr, sizeof(int32_t)),
-                                  stage_out(3, status, sizeof(int32_t))};
-  return staged_call(code, B, n * 2, 1, streams, 4, erasures, erasure_offsets,
-                     [&](size_t m, void *const *d, const uint16_t *d_er, const uint32_t *d_off, hipStream_t s) {
-                       return launch_wide_correct(code, static_cast<const uint16_t *>(d[0]), d_er, d_off, static_cast<uint16_t *>(d[1]),
-                                                  static_cast<int32_t *>(d[2]), static_cast<int32_t *>(d[3]), m, s);
-                     });
+  return wide_correct_call(code, kFromHost, in, erasures, erasure_offsets, out, nerr, status, B);
 }
+
 
 /* ------------------------------ packed bits (packed.hip) ------------------------------ */
 
@@ -1279,73 +1235,63 @@ int cc_packed_map_route(const cc_code *code, int which) {
   return (which == 0 ? packed_encode_native(code) : packed_extract_native(code)) ? 1 : 0;
 }
 
-int cc_encode_packed_batch_dev(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, void *stream) {
-  if (!code || (B && (!d_msg || !d_cw))) return CC_ERR_INVALID_ARGUMENT;
+// cc_encode_packed_batch(_dev) and cc_extract_packed_batch(_dev); kind as plain_route_dev.  A chunk is sized by the
+// symbols, not by the packed words: the generic route's workspace is what a chunk costs.
+static int packed_map_call(const cc_code *code, Where at, int kind, const uint8_t *src, uint8_t *dst, size_t B) {
+  if (!code || (B && (!src || !dst))) return CC_ERR_INVALID_ARGUMENT;
   if (int rc = packed_ready(code)) return rc;
-  DeviceGuard guard(code->device);
-  return packed_map_dev(code, 0, d_msg, d_cw, B, static_cast<hipStream_t>(stream));
+  const size_t n = code->tab.n, l = code->tab.l;
+  return run_call(code, at, B, n * (code->wide ? 2 : 1), 1, NoCsr{},
+                  [&](size_t m, hipStream_t s, const uint8_t *d_src, uint8_t *d_dst) {
+                    return packed_map_dev(code, kind, d_src, d_dst, m, s);
+                  },
+                  array_in(src, packed_width(kind == 0 ? l : n)), array_out(dst, packed_width(kind == 1 ? l : n)));
 }
 
+int cc_encode_packed_batch_dev(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, void *stream) {
+  return packed_map_call(code, on_device(stream), 0, d_msg, d_cw, B);
+}
 int cc_extract_packed_batch_dev(const cc_code *code, const uint8_t *d_cw, uint8_t *d_msg, size_t B, void *stream) {
-  if (!code || (B && (!d_cw || !d_msg))) return CC_ERR_INVALID_ARGUMENT;
-  if (int rc = packed_ready(code)) return rc;
-  DeviceGuard guard(code->device);
-  return packed_map_dev(code, 1, d_cw, d_msg, B, static_cast<hipStream_t>(stream));
+  return packed_map_call(code, on_device(stream), 1, d_cw, d_msg, B);
+}
+int cc_encode_packed_batch(const cc_code *code, const uint8_t *msg, uint8_t *cw, size_t B) {
+  return packed_map_call(code, kFromHost, 0, msg, cw, B);
+}
+int cc_extract_packed_batch(const cc_code *code, const uint8_t *cw, uint8_t *msg, size_t B) {
+  return packed_map_call(code, kFromHost, 1, cw, msg, B);
+}
+
+static int packed_correct_call(const cc_code *code, Where at, const uint8_t *words, const uint16_t *erasures,
+                               const uint32_t *erasure_offsets, uint8_t *out, int32_t *nerr, int32_t *status, size_t B) {
+  if (!code || (B && (!words || !out))) return CC_ERR_INVALID_ARGUMENT;
+  if ((erasures == nullptr) != (erasure_offsets == nullptr)) return CC_ERR_INVALID_ARGUMENT;
+  if (int rc = packed_hard_supported(code, erasures != nullptr)) return rc;
+  const size_t n = code->tab.n, w = packed_width(n);
+  if (at.host && B && !erasures_in_range(erasures, erasure_offsets, B, n)) return CC_ERR_INVALID_ARGUMENT;
+  // a chunk is sized by the symbols, as in packed_map_call.  A 16-bit handle's call that takes the native route
+  // (packed_long.hip) has no workspace: the route is decided once, for the B frames of the call as
+  // cc_packed_route(code, B) reports it, its chunks are sized by the packed words and every chunk, a short last one
+  // included, runs the native kernel.
+  const bool long_native = !erasures && code->wide && packed_native_supported(code, B);
+  return run_call(code, at, B, long_native ? w : n * (code->wide ? 2 : 1), 1, Csr{erasures, erasure_offsets},
+                  [&](size_t m, hipStream_t s, const uint16_t *d_er, const uint32_t *d_off, const uint8_t *d_words, uint8_t *d_out,
+                      int32_t *d_nerr, int32_t *d_status) {
+                    if (long_native) return launch_packed_long_correct(code, d_words, d_out, d_nerr, d_status, m, s);
+                    return packed_correct_dev(code, d_words, d_er, d_off, d_out, d_nerr, d_status, m, s);
+                  },
+                  array_in(words, w), array_out(out, w), array_out(nerr, 1), array_out(status, 1));
 }
 
 int cc_correct_hard_packed_batch_dev(const cc_code *code, const uint8_t *d_in, const uint16_t *d_erasures,
                                      const uint32_t *d_erasure_offsets, uint8_t *d_out, int32_t *d_nerr,
                                      int32_t *d_status, size_t B, void *stream) {
-  if (!code || (B && (!d_in || !d_out))) return CC_ERR_INVALID_ARGUMENT;
-  if ((d_erasures == nullptr) != (d_erasure_offsets == nullptr)) return CC_ERR_INVALID_ARGUMENT;
-  if (int rc = packed_hard_supported(code, d_erasures != nullptr)) return rc;
-  DeviceGuard guard(code->device);
-  return packed_correct_dev(code, d_in, d_erasures, d_erasure_offsets, d_out, d_nerr, d_status, B,
-                            static_cast<hipStream_t>(stream));
-}
-
-// host pointers: the chunked staging of the byte entry points; kind as plain_route_dev
-static int packed_host(const cc_code *code, int kind, const uint8_t *src, const uint16_t *erasures,
-                       const uint32_t *erasure_offsets, uint8_t *dst, int32_t *nerr, int32_t *status, size_t B) {
-  if (!code || (B && (!src || !dst))) return CC_ERR_INVALID_ARGUMENT;
-  if ((erasures == nullptr) != (erasure_offsets == nullptr)) return CC_ERR_INVALID_ARGUMENT;
-  if (int rc = kind == 2 ? packed_hard_supported(code, erasures != nullptr) : packed_ready(code)) return rc;
-  if (B == 0) return CC_OK;
-  const size_t n = code->tab.n, l = code->tab.l;
-  const size_t in_w = packed_width(kind == 0 ? l : n), out_w = packed_width(kind == 1 ? l : n);
-  if (!erasures_in_range(erasures, erasure_offsets, B, n)) return CC_ERR_INVALID_ARGUMENT;
-  DeviceGuard guard(code->device);
-  const StagedStream streams[] = {stage_in(0, src, in_w), stage_out(1, dst, out_w), stage_out(2, nerr, sizeof(int32_t)),
-                                  stage_out(3, status, sizeof(int32_t))};
-  // a chunk is sized by the symbols, not by the packed words: the generic route's workspace is what a chunk costs.
-  // A 16-bit handle's call that takes the native route (packed_long.hip) has no such workspace: the route is decided
-  // once, for the B frames of the call as cc_packed_route(code, B) reports it, its chunks are sized by the packed words
-  // and every chunk, a short last one included, runs the native kernel.
-  const bool long_native = kind == 2 && !erasures && code->wide && packed_native_supported(code, B);
-  return staged_call(code, B, long_native ? in_w : n * (code->wide ? 2 : 1), 1, streams, kind == 2 ? 4 : 2, erasures,
-                     erasure_offsets,
-                     [&](size_t m, void *const *d, const uint16_t *d_er, const uint32_t *d_off, hipStream_t s) {
-                       const uint8_t *d_src = static_cast<const uint8_t *>(d[0]);
-                       uint8_t *d_dst = static_cast<uint8_t *>(d[1]);
-                       if (kind != 2) return packed_map_dev(code, kind, d_src, d_dst, m, s);
-                       if (long_native)
-                         return launch_packed_long_correct(code, d_src, d_dst, static_cast<int32_t *>(d[2]),
-                                                           static_cast<int32_t *>(d[3]), m, s);
-                       return packed_correct_dev(code, d_src, d_er, d_off, d_dst, static_cast<int32_t *>(d[2]),
-                                                 static_cast<int32_t *>(d[3]), m, s);
-                     });
-}
-
-int cc_encode_packed_batch(const cc_code *code, const uint8_t *msg, uint8_t *cw, size_t B) {
-  return packed_host(code, 0, msg, nullptr, nullptr, cw, nullptr, nullptr, B);
-}
-int cc_extract_packed_batch(const cc_code *code, const uint8_t *cw, uint8_t *msg, size_t B) {
-  return packed_host(code, 1, cw, nullptr, nullptr, msg, nullptr, nullptr, B);
+  return packed_correct_call(code, on_device(stream), d_in, d_erasures, d_erasure_offsets, d_out, d_nerr, d_status, B);
 }
 int cc_correct_hard_packed_batch(const cc_code *code, const uint8_t *in, const uint16_t *erasures,
                                  const uint32_t *erasure_offsets, uint8_t *out, int32_t *nerr, int32_t *status, size_t B) {
-  return packed_host(code, 2, in, erasures, erasure_offsets, out, nerr, status, B);
+  return packed_correct_call(code, kFromHost, in, erasures, erasure_offsets, out, nerr, status, B);
 }
+
 
 int cc_decode_hard_packed_batch(const cc_code *code, const uint8_t *in, const uint16_t *erasures,
                                 const uint32_t *erasure_offsets, uint8_t *msg, uint8_t *words, int32_t *nerr,
@@ -1432,93 +1378,90 @@ static int interleaved_dev(const cc_code *code, int kind, const void *d_src, con
       d_off, d_nerr, d_status, B, stream);
 }
 
-// the _dev entry points: null pointers, the new refusals, the plain call's refusals, the call
-static int interleaved_entry_dev(const cc_code *code, int kind, int width, const void *d_src, const uint16_t *d_er,
-                                 const uint32_t *d_off, void *d_dst, int32_t *d_nerr, int32_t *d_status, size_t B, uint32_t I,
-                                 void *stream) {
-  if (!code || (B && (!d_src || !d_dst))) return CC_ERR_INVALID_ARGUMENT;
-  if ((d_er == nullptr) != (d_off == nullptr)) return CC_ERR_INVALID_ARGUMENT;
+// The six interleaved pairs: null pointers, the new refusals, the plain call's refusals; on host pointers the plain
+// call's checks of symbol values against the field and of erasure positions against n (the order of the symbols does
+// not matter to them), and chunks of whole blocks.  src and dst hold symbols of `width` bytes and travel as bytes, as
+// interleaved_dev takes them.
+static int interleaved_call(const cc_code *code, Where at, int kind, int width, const void *src_raw, const uint16_t *erasures,
+                            const uint32_t *erasure_offsets, void *dst_raw, int32_t *nerr, int32_t *status, size_t B, uint32_t I) {
+  if (!code || (B && (!src_raw || !dst_raw))) return CC_ERR_INVALID_ARGUMENT;
+  if ((erasures == nullptr) != (erasure_offsets == nullptr)) return CC_ERR_INVALID_ARGUMENT;
   if (int rc = interleave_args(code, B, I)) return rc;
-  if (int rc = interleaved_ready(code, kind, width, d_er != nullptr)) return rc;
-  DeviceGuard guard(code->device);
-  return interleaved_dev(code, kind, d_src, d_er, d_off, d_dst, d_nerr, d_status, B, I, static_cast<hipStream_t>(stream));
+  if (int rc = interleaved_ready(code, kind, width, erasures != nullptr)) return rc;
+  const size_t n = code->tab.n, l = code->tab.l, w = static_cast<size_t>(width);
+  const size_t in_w = kind == 0 ? l : n, out_w = kind == 1 ? l : n;
+  if (at.host && B) {
+    if (kind != 1 && !(width == 2 ? symbols_in_field(static_cast<const uint16_t *>(src_raw), B * in_w, code->tab.q)
+                                  : symbols_in_field(static_cast<const uint8_t *>(src_raw), B * in_w, code->tab.q)))
+      return CC_ERR_NOT_IN_FIELD;
+    if (!erasures_in_range(erasures, erasure_offsets, B, n)) return CC_ERR_INVALID_ARGUMENT;
+  }
+  const Arr<const uint8_t> src = array_in(static_cast<const uint8_t *>(src_raw), in_w * w);
+  const Arr<uint8_t> dst = array_out(static_cast<uint8_t *>(dst_raw), out_w * w);
+  if (kind != 2)  // encode and extract have no nerr and no status
+    return run_call(code, at, B, n * w, I, NoCsr{},
+                    [&](size_t m, hipStream_t s, const uint8_t *d_src, uint8_t *d_dst) {
+                      return interleaved_dev(code, kind, d_src, nullptr, nullptr, d_dst, nullptr, nullptr, m, I, s);
+                    },
+                    src, dst);
+  return run_call(code, at, B, n * w, I, Csr{erasures, erasure_offsets},
+                  [&](size_t m, hipStream_t s, const uint16_t *d_er, const uint32_t *d_off, const uint8_t *d_src, uint8_t *d_dst,
+                      int32_t *d_nerr, int32_t *d_status) {
+                    return interleaved_dev(code, kind, d_src, d_er, d_off, d_dst, d_nerr, d_status, m, I, s);
+                  },
+                  src, dst, array_out(nerr, 1), array_out(status, 1));
 }
 
 int cc_encode_interleaved_batch_dev(const cc_code *code, const uint8_t *d_msg, uint8_t *d_cw, size_t B, uint32_t interleave,
                                     void *stream) {
-  return interleaved_entry_dev(code, 0, 1, d_msg, nullptr, nullptr, d_cw, nullptr, nullptr, B, interleave, stream);
+  return interleaved_call(code, on_device(stream), 0, 1, d_msg, nullptr, nullptr, d_cw, nullptr, nullptr, B, interleave);
 }
 int cc_extract_interleaved_batch_dev(const cc_code *code, const uint8_t *d_cw, uint8_t *d_msg, size_t B, uint32_t interleave,
                                      void *stream) {
-  return interleaved_entry_dev(code, 1, 1, d_cw, nullptr, nullptr, d_msg, nullptr, nullptr, B, interleave, stream);
+  return interleaved_call(code, on_device(stream), 1, 1, d_cw, nullptr, nullptr, d_msg, nullptr, nullptr, B, interleave);
 }
 int cc_correct_hard_interleaved_batch_dev(const cc_code *code, const uint8_t *d_in, const uint16_t *d_erasures,
                                           const uint32_t *d_erasure_offsets, uint8_t *d_out, int32_t *d_nerr,
                                           int32_t *d_status, size_t B, uint32_t interleave, void *stream) {
-  return interleaved_entry_dev(code, 2, 1, d_in, d_erasures, d_erasure_offsets, d_out, d_nerr, d_status, B, interleave, stream);
+  return interleaved_call(code, on_device(stream), 2, 1, d_in, d_erasures, d_erasure_offsets, d_out, d_nerr, d_status, B, interleave);
 }
 int cc_encode_interleaved_batch_u16_dev(const cc_code *code, const uint16_t *d_msg, uint16_t *d_cw, size_t B,
                                         uint32_t interleave, void *stream) {
-  return interleaved_entry_dev(code, 0, 2, d_msg, nullptr, nullptr, d_cw, nullptr, nullptr, B, interleave, stream);
+  return interleaved_call(code, on_device(stream), 0, 2, d_msg, nullptr, nullptr, d_cw, nullptr, nullptr, B, interleave);
 }
 int cc_extract_interleaved_batch_u16_dev(const cc_code *code, const uint16_t *d_cw, uint16_t *d_msg, size_t B,
                                          uint32_t interleave, void *stream) {
-  return interleaved_entry_dev(code, 1, 2, d_cw, nullptr, nullptr, d_msg, nullptr, nullptr, B, interleave, stream);
+  return interleaved_call(code, on_device(stream), 1, 2, d_cw, nullptr, nullptr, d_msg, nullptr, nullptr, B, interleave);
 }
 int cc_correct_hard_interleaved_batch_u16_dev(const cc_code *code, const uint16_t *d_in, const uint16_t *d_erasures,
                                               const uint32_t *d_erasure_offsets, uint16_t *d_out, int32_t *d_nerr,
                                               int32_t *d_status, size_t B, uint32_t interleave, void *stream) {
-  return interleaved_entry_dev(code, 2, 2, d_in, d_erasures, d_erasure_offsets, d_out, d_nerr, d_status, B, interleave, stream);
-}
-
-// host pointers: the chunked staging of the plain entry points, a chunk being whole blocks; the checks of symbol
-// values against the field and of erasure positions against n are the plain call's (the order of the symbols does not
-// matter to them)
-static int interleaved_host(const cc_code *code, int kind, int width, const void *src, const uint16_t *erasures,
-                            const uint32_t *erasure_offsets, void *dst, int32_t *nerr, int32_t *status, size_t B, uint32_t I) {
-  if (!code || (B && (!src || !dst))) return CC_ERR_INVALID_ARGUMENT;
-  if ((erasures == nullptr) != (erasure_offsets == nullptr)) return CC_ERR_INVALID_ARGUMENT;
-  if (int rc = interleave_args(code, B, I)) return rc;
-  if (int rc = interleaved_ready(code, kind, width, erasures != nullptr)) return rc;
-  if (B == 0) return CC_OK;
-  const size_t n = code->tab.n, l = code->tab.l, w = static_cast<size_t>(width);
-  const size_t in_w = kind == 0 ? l : n, out_w = kind == 1 ? l : n;
-  if (kind != 1 && !(width == 2 ? symbols_in_field(static_cast<const uint16_t *>(src), B * in_w, code->tab.q)
-                                : symbols_in_field(static_cast<const uint8_t *>(src), B * in_w, code->tab.q)))
-    return CC_ERR_NOT_IN_FIELD;
-  if (!erasures_in_range(erasures, erasure_offsets, B, n)) return CC_ERR_INVALID_ARGUMENT;
-  DeviceGuard guard(code->device);
-  const StagedStream streams[] = {stage_in(0, src, in_w * w), stage_out(1, dst, out_w * w), stage_out(2, nerr, sizeof(int32_t)),
-                                  stage_out(3, status, sizeof(int32_t))};
-  return staged_call(code, B, n * w, I, streams, kind == 2 ? 4 : 2, erasures, erasure_offsets,  // chunks of whole blocks
-                     [&](size_t m, void *const *d, const uint16_t *d_er, const uint32_t *d_off, hipStream_t s) {
-                       return interleaved_dev(code, kind, d[0], d_er, d_off, d[1], static_cast<int32_t *>(d[2]),
-                                              static_cast<int32_t *>(d[3]), m, I, s);
-                     });
+  return interleaved_call(code, on_device(stream), 2, 2, d_in, d_erasures, d_erasure_offsets, d_out, d_nerr, d_status, B, interleave);
 }
 
 int cc_encode_interleaved_batch(const cc_code *code, const uint8_t *msg, uint8_t *cw, size_t B, uint32_t interleave) {
-  return interleaved_host(code, 0, 1, msg, nullptr, nullptr, cw, nullptr, nullptr, B, interleave);
+  return interleaved_call(code, kFromHost, 0, 1, msg, nullptr, nullptr, cw, nullptr, nullptr, B, interleave);
 }
 int cc_extract_interleaved_batch(const cc_code *code, const uint8_t *cw, uint8_t *msg, size_t B, uint32_t interleave) {
-  return interleaved_host(code, 1, 1, cw, nullptr, nullptr, msg, nullptr, nullptr, B, interleave);
+  return interleaved_call(code, kFromHost, 1, 1, cw, nullptr, nullptr, msg, nullptr, nullptr, B, interleave);
 }
 int cc_correct_hard_interleaved_batch(const cc_code *code, const uint8_t *in, const uint16_t *erasures,
                                       const uint32_t *erasure_offsets, uint8_t *out, int32_t *nerr, int32_t *status, size_t B,
                                       uint32_t interleave) {
-  return interleaved_host(code, 2, 1, in, erasures, erasure_offsets, out, nerr, status, B, interleave);
+  return interleaved_call(code, kFromHost, 2, 1, in, erasures, erasure_offsets, out, nerr, status, B, interleave);
 }
 int cc_encode_interleaved_batch_u16(const cc_code *code, const uint16_t *msg, uint16_t *cw, size_t B, uint32_t interleave) {
-  return interleaved_host(code, 0, 2, msg, nullptr, nullptr, cw, nullptr, nullptr, B, interleave);
+  return interleaved_call(code, kFromHost, 0, 2, msg, nullptr, nullptr, cw, nullptr, nullptr, B, interleave);
 }
 int cc_extract_interleaved_batch_u16(const cc_code *code, const uint16_t *cw, uint16_t *msg, size_t B, uint32_t interleave) {
-  return interleaved_host(code, 1, 2, cw, nullptr, nullptr, msg, nullptr, nullptr, B, interleave);
+  return interleaved_call(code, kFromHost, 1, 2, cw, nullptr, nullptr, msg, nullptr, nullptr, B, interleave);
 }
 int cc_correct_hard_interleaved_batch_u16(const cc_code *code, const uint16_t *in, const uint16_t *erasures,
                                           const uint32_t *erasure_offsets, uint16_t *out, int32_t *nerr, int32_t *status,
                                           size_t B, uint32_t interleave) {
-  return interleaved_host(code, 2, 2, in, erasures, erasure_offsets, out, nerr, status, B, interleave);
+  return interleaved_call(code, kFromHost, 2, 2, in, erasures, erasure_offsets, out, nerr, status, B, interleave);
 }
+
 
 int cc_decode_hard_interleaved_batch(const cc_code *code, const uint8_t *in, const uint16_t *erasures,
                                      const uint32_t *erasure_offsets, uint8_t *msg, uint8_t *words, int32_t *nerr,
@@ -1631,11 +1574,6 @@ static int product_handles(const cc_product *pc, uint32_t p) {
   return none;
 }
 
-static bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return a && b && a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
-}
-
 // the refusals of cc_product_decode(_dev) in the header's order; counters: the Monte-Carlo call, which has no arrays
 static int product_decode_supported(const cc_product *pc, const float *y, const uint8_t *out, const float *ext,
                                     const int32_t *status, size_t B, bool arrays) {
@@ -1655,66 +1593,54 @@ static int product_decode_supported(const cc_product *pc, const float *y, const 
   return rc;
 }
 
+// (in the product and staircase calls a block / a stream is the frame of the chunk loop)
+static int product_decode_call(const cc_product *pc, Where at, const float *y, uint8_t *out, float *ext, int32_t *status, size_t B) {
+  if (int rc = product_decode_supported(pc, y, out, ext, status, B, true)) return rc;
+  const ProductShape sh = product_shape(pc);
+  const size_t lines = (pc->halves & 1) ? sh.w2 : sh.w1;
+  // (ext == NULL selects the hard output)
+  return run_call(pc->rows, at, B, sh.N * sizeof(float), 1, NoCsr{},
+                  [&](size_t m, hipStream_t s, const float *d_y, uint8_t *d_out, float *d_ext, int32_t *d_status) {
+                    return launch_product_decode(pc, d_y, d_out, d_ext, d_status, m, s);
+                  },
+                  array_in(y, sh.N), array_out(out, sh.N), array_out_if_wanted(ext, sh.N), array_out(status, lines));
+}
+
 int cc_product_decode_dev(const cc_product *pc, const float *d_y, uint8_t *d_out, float *d_ext, int32_t *d_status, size_t B,
                           void *stream) {
-  if (int rc = product_decode_supported(pc, d_y, d_out, d_ext, d_status, B, true)) return rc;
-  DeviceGuard guard(pc->rows->device);
-  return launch_product_decode(pc, d_y, d_out, d_ext, d_status, B, static_cast<hipStream_t>(stream));
+  return product_decode_call(pc, on_device(stream), d_y, d_out, d_ext, d_status, B);
 }
-
 int cc_product_decode(const cc_product *pc, const float *y, uint8_t *out, float *ext, int32_t *status, size_t B) {
-  if (int rc = product_decode_supported(pc, y, out, ext, status, B, true)) return rc;
-  if (B == 0) return CC_OK;
-  const ProductShape s = product_shape(pc);
-  const size_t lines = (pc->halves & 1) ? s.w2 : s.w1;
-  DeviceGuard guard(pc->rows->device);
-  // a block is the frame of the chunk loop; ext == NULL leaves the last stream out and selects the hard output
-  const StagedStream streams[] = {stage_in(0, y, s.N * sizeof(float)), stage_out(1, out, s.N),
-                                  stage_out(3, status, lines * sizeof(int32_t)), stage_out(7, ext, s.N * sizeof(float))};
-  return staged_call(pc->rows, B, s.N * sizeof(float), 1, streams, ext ? 4 : 3, nullptr, nullptr,
-                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t st) {
-                       return launch_product_decode(pc, static_cast<const float *>(d[0]), static_cast<uint8_t *>(d[1]),
-                                                    static_cast<float *>(d[3]), static_cast<int32_t *>(d[2]), m, st);
-                     });
+  return product_decode_call(pc, kFromHost, y, out, ext, status, B);
 }
 
-static int product_map_dev(const cc_product *pc, bool encode, const uint8_t *d_src, uint8_t *d_dst, size_t B, void *stream) {
-  if (!pc || !pc->rows || !pc->cols || (B && (!d_src || !d_dst))) return CC_ERR_INVALID_ARGUMENT;
-  if (int rc = product_handles(pc, 0)) return rc;
-  DeviceGuard guard(pc->rows->device);
-  return encode ? launch_product_encode(pc, d_src, d_dst, B, static_cast<hipStream_t>(stream))
-                : launch_product_extract(pc, d_src, d_dst, B, static_cast<hipStream_t>(stream));
-}
-
-static int product_map_host(const cc_product *pc, bool encode, const uint8_t *src, uint8_t *dst, size_t B) {
+// cc_product_encode_batch(_dev) and cc_product_extract_batch(_dev)
+static int product_map_call(const cc_product *pc, Where at, bool encode, const uint8_t *src, uint8_t *dst, size_t B) {
   if (!pc || !pc->rows || !pc->cols || (B && (!src || !dst))) return CC_ERR_INVALID_ARGUMENT;
   if (int rc = product_handles(pc, 0)) return rc;
-  if (B == 0) return CC_OK;
-  const ProductShape s = product_shape(pc);
-  const size_t in_w = encode ? s.k1 * s.k2 : s.N, out_w = encode ? s.N : s.k1 * s.k2;
-  if (encode && !symbols_in_field(src, B * in_w, 1)) return CC_ERR_NOT_IN_FIELD;
-  DeviceGuard guard(pc->rows->device);
-  const StagedStream streams[] = {stage_in(0, src, in_w), stage_out(1, dst, out_w)};
-  return staged_call(pc->rows, B, s.N, 1, streams, 2, nullptr, nullptr,
-                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t st) {
-                       const uint8_t *d_src = static_cast<const uint8_t *>(d[0]);
-                       uint8_t *d_dst = static_cast<uint8_t *>(d[1]);
-                       return encode ? launch_product_encode(pc, d_src, d_dst, m, st) : launch_product_extract(pc, d_src, d_dst, m, st);
-                     });
+  const ProductShape sh = product_shape(pc);
+  const size_t in_w = encode ? sh.k1 * sh.k2 : sh.N, out_w = encode ? sh.N : sh.k1 * sh.k2;
+  if (at.host && B && encode && !symbols_in_field(src, B * in_w, 1)) return CC_ERR_NOT_IN_FIELD;
+  return run_call(pc->rows, at, B, sh.N, 1, NoCsr{},
+                  [&](size_t m, hipStream_t s, const uint8_t *d_src, uint8_t *d_dst) {
+                    return encode ? launch_product_encode(pc, d_src, d_dst, m, s) : launch_product_extract(pc, d_src, d_dst, m, s);
+                  },
+                  array_in(src, in_w), array_out(dst, out_w));
 }
 
 int cc_product_encode_batch_dev(const cc_product *pc, const uint8_t *d_msg, uint8_t *d_cw, size_t B, void *stream) {
-  return product_map_dev(pc, true, d_msg, d_cw, B, stream);
+  return product_map_call(pc, on_device(stream), true, d_msg, d_cw, B);
 }
 int cc_product_extract_batch_dev(const cc_product *pc, const uint8_t *d_cw, uint8_t *d_msg, size_t B, void *stream) {
-  return product_map_dev(pc, false, d_cw, d_msg, B, stream);
+  return product_map_call(pc, on_device(stream), false, d_cw, d_msg, B);
 }
 int cc_product_encode_batch(const cc_product *pc, const uint8_t *msg, uint8_t *cw, size_t B) {
-  return product_map_host(pc, true, msg, cw, B);
+  return product_map_call(pc, kFromHost, true, msg, cw, B);
 }
 int cc_product_extract_batch(const cc_product *pc, const uint8_t *cw, uint8_t *msg, size_t B) {
-  return product_map_host(pc, false, cw, msg, B);
+  return product_map_call(pc, kFromHost, false, cw, msg, B);
 }
+
 
 double cc_product_sigma(const cc_product *pc, double ebno_db) {
   if (!pc || !pc->rows || !pc->cols || needs_code(pc->rows) != CC_OK || needs_code(pc->cols) != CC_OK) return 0.0;
@@ -1759,30 +1685,26 @@ static int product_hard_supported(const cc_product *pc, const uint8_t *in, const
   return rc;
 }
 
-int cc_product_decode_hard_dev(const cc_product *pc, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip, int32_t *d_last,
-                               int32_t *d_status, size_t B, void *stream) {
-  if (int rc = product_hard_supported(pc, d_in, d_out, B, true)) return rc;
-  DeviceGuard guard(pc->rows->device);
-  return launch_product_hard(pc, d_in, d_out, d_nflip, d_last, d_status, B, static_cast<hipStream_t>(stream));
+static int product_hard_call(const cc_product *pc, Where at, const uint8_t *words, uint8_t *out, int32_t *nflip, int32_t *last,
+                             int32_t *status, size_t B) {
+  if (int rc = product_hard_supported(pc, words, out, B, true)) return rc;
+  const size_t N = product_shape(pc).N;
+  if (at.host && B && !symbols_in_field(words, B * N, 1)) return CC_ERR_NOT_IN_FIELD;
+  return run_call(pc->rows, at, B, N, 1, NoCsr{},
+                  [&](size_t m, hipStream_t s, const uint8_t *d_words, uint8_t *d_out, int32_t *d_nflip, int32_t *d_last,
+                      int32_t *d_status) { return launch_product_hard(pc, d_words, d_out, d_nflip, d_last, d_status, m, s); },
+                  array_in(words, N), array_out(out, N), array_out(nflip, 1), array_out(last, 1), array_out(status, 1));
 }
 
+int cc_product_decode_hard_dev(const cc_product *pc, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip, int32_t *d_last,
+                               int32_t *d_status, size_t B, void *stream) {
+  return product_hard_call(pc, on_device(stream), d_in, d_out, d_nflip, d_last, d_status, B);
+}
 int cc_product_decode_hard(const cc_product *pc, const uint8_t *in, uint8_t *out, int32_t *nflip, int32_t *last,
                            int32_t *status, size_t B) {
-  if (int rc = product_hard_supported(pc, in, out, B, true)) return rc;
-  if (B == 0) return CC_OK;
-  const ProductShape s = product_shape(pc);
-  if (!symbols_in_field(in, B * s.N, 1)) return CC_ERR_NOT_IN_FIELD;
-  DeviceGuard guard(pc->rows->device);
-  // a block is the frame of the chunk loop
-  const StagedStream streams[] = {stage_in(0, in, s.N), stage_out(1, out, s.N), stage_out(2, nflip, sizeof(int32_t)),
-                                  stage_out(3, status, sizeof(int32_t)), stage_out(4, last, sizeof(int32_t))};
-  return staged_call(pc->rows, B, s.N, 1, streams, 5, nullptr, nullptr,
-                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t st) {
-                       return launch_product_hard(pc, static_cast<const uint8_t *>(d[0]), static_cast<uint8_t *>(d[1]),
-                                                  static_cast<int32_t *>(d[2]), static_cast<int32_t *>(d[4]),
-                                                  static_cast<int32_t *>(d[3]), m, st);
-                     });
+  return product_hard_call(pc, kFromHost, in, out, nflip, last, status, B);
 }
+
 
 int cc_mc_run_product_hard_dev(const cc_product *pc, double ebno_db, uint64_t seed, uint64_t first_block, size_t blocks,
                                int random_codewords, uint64_t *d_counters, void *stream) {
@@ -1793,33 +1715,29 @@ int cc_mc_run_product_hard_dev(const cc_product *pc, double ebno_db, uint64_t se
                              static_cast<hipStream_t>(stream));
 }
 
-int cc_product_decode_anchor_dev(const cc_product *pc, uint32_t delta, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip,
-                                 int32_t *d_last, int32_t *d_status, int32_t *d_nback, int32_t *d_nconf, size_t B, void *stream) {
-  if (int rc = product_hard_supported(pc, d_in, d_out, B, true, &delta)) return rc;
-  DeviceGuard guard(pc->rows->device);
-  return launch_product_anchor(pc, delta, d_in, d_out, d_nflip, d_last, d_status, d_nback, d_nconf, B,
-                               static_cast<hipStream_t>(stream));
+static int product_anchor_call(const cc_product *pc, Where at, uint32_t delta, const uint8_t *words, uint8_t *out, int32_t *nflip,
+                               int32_t *last, int32_t *status, int32_t *nback, int32_t *nconf, size_t B) {
+  if (int rc = product_hard_supported(pc, words, out, B, true, &delta)) return rc;
+  const size_t N = product_shape(pc).N;
+  if (at.host && B && !symbols_in_field(words, B * N, 1)) return CC_ERR_NOT_IN_FIELD;
+  return run_call(pc->rows, at, B, N, 1, NoCsr{},
+                  [&](size_t m, hipStream_t s, const uint8_t *d_words, uint8_t *d_out, int32_t *d_nflip, int32_t *d_last,
+                      int32_t *d_status, int32_t *d_nback, int32_t *d_nconf) {
+                    return launch_product_anchor(pc, delta, d_words, d_out, d_nflip, d_last, d_status, d_nback, d_nconf, m, s);
+                  },
+                  array_in(words, N), array_out(out, N), array_out(nflip, 1), array_out(last, 1), array_out(status, 1),
+                  array_out(nback, 1), array_out(nconf, 1));
 }
 
+int cc_product_decode_anchor_dev(const cc_product *pc, uint32_t delta, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip,
+                                 int32_t *d_last, int32_t *d_status, int32_t *d_nback, int32_t *d_nconf, size_t B, void *stream) {
+  return product_anchor_call(pc, on_device(stream), delta, d_in, d_out, d_nflip, d_last, d_status, d_nback, d_nconf, B);
+}
 int cc_product_decode_anchor(const cc_product *pc, uint32_t delta, const uint8_t *in, uint8_t *out, int32_t *nflip,
                              int32_t *last, int32_t *status, int32_t *nback, int32_t *nconf, size_t B) {
-  if (int rc = product_hard_supported(pc, in, out, B, true, &delta)) return rc;
-  if (B == 0) return CC_OK;
-  const ProductShape s = product_shape(pc);
-  if (!symbols_in_field(in, B * s.N, 1)) return CC_ERR_NOT_IN_FIELD;
-  DeviceGuard guard(pc->rows->device);
-  // a block is the frame of the chunk loop
-  const StagedStream streams[] = {stage_in(0, in, s.N), stage_out(1, out, s.N), stage_out(2, nflip, sizeof(int32_t)),
-                                  stage_out(3, status, sizeof(int32_t)), stage_out(4, last, sizeof(int32_t)),
-                                  stage_out(5, nback, sizeof(int32_t)), stage_out(6, nconf, sizeof(int32_t))};
-  return staged_call(pc->rows, B, s.N, 1, streams, 7, nullptr, nullptr,
-                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t st) {
-                       return launch_product_anchor(pc, delta, static_cast<const uint8_t *>(d[0]), static_cast<uint8_t *>(d[1]),
-                                                    static_cast<int32_t *>(d[2]), static_cast<int32_t *>(d[4]),
-                                                    static_cast<int32_t *>(d[3]), static_cast<int32_t *>(d[5]),
-                                                    static_cast<int32_t *>(d[6]), m, st);
-                     });
+  return product_anchor_call(pc, kFromHost, delta, in, out, nflip, last, status, nback, nconf, B);
 }
+
 
 int cc_mc_run_product_anchor_dev(const cc_product *pc, uint32_t delta, double ebno_db, uint64_t seed, uint64_t first_block,
                                  size_t blocks, int random_codewords, uint64_t *d_counters, void *stream) {
@@ -1847,31 +1765,27 @@ static int product_sr_supported(const cc_product *pc, const float *weights, cons
   return rc;
 }
 
-int cc_product_decode_sr_dev(const cc_product *pc, const float *weights, const float *d_y, uint8_t *d_out, int32_t *d_nflip,
-                             int32_t *d_last, int32_t *d_status, size_t B, void *stream) {
-  SrSchedule sched;
-  if (int rc = product_sr_supported(pc, weights, d_y, d_out, B, true, &sched)) return rc;
-  DeviceGuard guard(pc->rows->device);
-  return launch_product_sr(pc, sched, d_y, d_out, d_nflip, d_last, d_status, B, static_cast<hipStream_t>(stream));
-}
-
-int cc_product_decode_sr(const cc_product *pc, const float *weights, const float *y, uint8_t *out, int32_t *nflip,
-                         int32_t *last, int32_t *status, size_t B) {
+static int product_sr_call(const cc_product *pc, Where at, const float *weights, const float *y, uint8_t *out, int32_t *nflip,
+                           int32_t *last, int32_t *status, size_t B) {
   SrSchedule sched;
   if (int rc = product_sr_supported(pc, weights, y, out, B, true, &sched)) return rc;
-  if (B == 0) return CC_OK;
-  const ProductShape s = product_shape(pc);
-  DeviceGuard guard(pc->rows->device);
-  // a block is the frame of the chunk loop
-  const StagedStream streams[] = {stage_in(0, y, s.N * sizeof(float)), stage_out(1, out, s.N), stage_out(2, nflip, sizeof(int32_t)),
-                                  stage_out(3, status, sizeof(int32_t)), stage_out(4, last, sizeof(int32_t))};
-  return staged_call(pc->rows, B, s.N * sizeof(float), 1, streams, 5, nullptr, nullptr,
-                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t st) {
-                       return launch_product_sr(pc, sched, static_cast<const float *>(d[0]), static_cast<uint8_t *>(d[1]),
-                                                static_cast<int32_t *>(d[2]), static_cast<int32_t *>(d[4]),
-                                                static_cast<int32_t *>(d[3]), m, st);
-                     });
+  const size_t N = product_shape(pc).N;
+  return run_call(pc->rows, at, B, N * sizeof(float), 1, NoCsr{},
+                  [&](size_t m, hipStream_t s, const float *d_y, uint8_t *d_out, int32_t *d_nflip, int32_t *d_last, int32_t *d_status) {
+                    return launch_product_sr(pc, sched, d_y, d_out, d_nflip, d_last, d_status, m, s);
+                  },
+                  array_in(y, N), array_out(out, N), array_out(nflip, 1), array_out(last, 1), array_out(status, 1));
 }
+
+int cc_product_decode_sr_dev(const cc_product *pc, const float *weights, const float *d_y, uint8_t *d_out, int32_t *d_nflip,
+                             int32_t *d_last, int32_t *d_status, size_t B, void *stream) {
+  return product_sr_call(pc, on_device(stream), weights, d_y, d_out, d_nflip, d_last, d_status, B);
+}
+int cc_product_decode_sr(const cc_product *pc, const float *weights, const float *y, uint8_t *out, int32_t *nflip,
+                         int32_t *last, int32_t *status, size_t B) {
+  return product_sr_call(pc, kFromHost, weights, y, out, nflip, last, status, B);
+}
+
 
 int cc_mc_run_product_sr_dev(const cc_product *pc, const float *weights, double ebno_db, uint64_t seed, uint64_t first_block,
                              size_t blocks, int random_codewords, uint64_t *d_counters, void *stream) {
@@ -1929,64 +1843,52 @@ static int staircase_supported(const cc_staircase *sc, bool decode, bool arrays,
   return rc;
 }
 
+static int staircase_decode_call(const cc_staircase *sc, Where at, const uint8_t *words, uint8_t *out, int32_t *nflip,
+                                 int32_t *status, size_t B) {
+  if (int rc = staircase_supported(sc, true, true, words, out, B)) return rc;
+  const size_t N = staircase_shape(sc).N;
+  if (at.host && B && !symbols_in_field(words, B * N, 1)) return CC_ERR_NOT_IN_FIELD;
+  return run_call(sc->code, at, B, N, 1, NoCsr{},
+                  [&](size_t m, hipStream_t s, const uint8_t *d_words, uint8_t *d_out, int32_t *d_nflip, int32_t *d_status) {
+                    return launch_staircase_decode(sc, d_words, d_out, d_nflip, d_status, m, s);
+                  },
+                  array_in(words, N), array_out(out, N), array_out(nflip, 1), array_out(status, 1));
+}
+
 int cc_staircase_decode_dev(const cc_staircase *sc, const uint8_t *d_in, uint8_t *d_out, int32_t *d_nflip, int32_t *d_status,
                             size_t B, void *stream) {
-  if (int rc = staircase_supported(sc, true, true, d_in, d_out, B)) return rc;
-  DeviceGuard guard(sc->code->device);
-  return launch_staircase_decode(sc, d_in, d_out, d_nflip, d_status, B, static_cast<hipStream_t>(stream));
+  return staircase_decode_call(sc, on_device(stream), d_in, d_out, d_nflip, d_status, B);
 }
-
 int cc_staircase_decode(const cc_staircase *sc, const uint8_t *in, uint8_t *out, int32_t *nflip, int32_t *status, size_t B) {
-  if (int rc = staircase_supported(sc, true, true, in, out, B)) return rc;
-  if (B == 0) return CC_OK;
-  const StaircaseShape s = staircase_shape(sc);
-  if (!symbols_in_field(in, B * s.N, 1)) return CC_ERR_NOT_IN_FIELD;
-  DeviceGuard guard(sc->code->device);
-  // a stream is the frame of the chunk loop
-  const StagedStream streams[] = {stage_in(0, in, s.N), stage_out(1, out, s.N), stage_out(2, nflip, sizeof(int32_t)),
-                                  stage_out(3, status, sizeof(int32_t))};
-  return staged_call(sc->code, B, s.N, 1, streams, 4, nullptr, nullptr,
-                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t st) {
-                       return launch_staircase_decode(sc, static_cast<const uint8_t *>(d[0]), static_cast<uint8_t *>(d[1]),
-                                                      static_cast<int32_t *>(d[2]), static_cast<int32_t *>(d[3]), m, st);
-                     });
+  return staircase_decode_call(sc, kFromHost, in, out, nflip, status, B);
 }
 
-static int staircase_map_dev(const cc_staircase *sc, bool encode, const uint8_t *d_src, uint8_t *d_dst, size_t B, void *stream) {
-  if (int rc = staircase_supported(sc, false, true, d_src, d_dst, B)) return rc;
-  DeviceGuard guard(sc->code->device);
-  return encode ? launch_staircase_encode(sc, d_src, d_dst, B, static_cast<hipStream_t>(stream))
-                : launch_staircase_extract(sc, d_src, d_dst, B, static_cast<hipStream_t>(stream));
-}
-
-static int staircase_map_host(const cc_staircase *sc, bool encode, const uint8_t *src, uint8_t *dst, size_t B) {
+// cc_staircase_encode_batch(_dev) and cc_staircase_extract_batch(_dev); a chunk is sized by three times the stream
+static int staircase_map_call(const cc_staircase *sc, Where at, bool encode, const uint8_t *src, uint8_t *dst, size_t B) {
   if (int rc = staircase_supported(sc, false, true, src, dst, B)) return rc;
-  if (B == 0) return CC_OK;
-  const StaircaseShape s = staircase_shape(sc);
-  const size_t in_w = encode ? s.K : s.N, out_w = encode ? s.N : s.K;
-  if (!symbols_in_field(src, B * in_w, 1)) return CC_ERR_NOT_IN_FIELD;
-  DeviceGuard guard(sc->code->device);
-  const StagedStream streams[] = {stage_in(0, src, in_w), stage_out(1, dst, out_w)};
-  return staged_call(sc->code, B, 3 * s.N, 1, streams, 2, nullptr, nullptr,
-                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t st) {
-                       const uint8_t *d_src = static_cast<const uint8_t *>(d[0]);
-                       uint8_t *d_dst = static_cast<uint8_t *>(d[1]);
-                       return encode ? launch_staircase_encode(sc, d_src, d_dst, m, st) : launch_staircase_extract(sc, d_src, d_dst, m, st);
-                     });
+  const StaircaseShape sh = staircase_shape(sc);
+  const size_t in_w = encode ? sh.K : sh.N, out_w = encode ? sh.N : sh.K;
+  if (at.host && B && !symbols_in_field(src, B * in_w, 1)) return CC_ERR_NOT_IN_FIELD;
+  return run_call(sc->code, at, B, 3 * sh.N, 1, NoCsr{},
+                  [&](size_t m, hipStream_t s, const uint8_t *d_src, uint8_t *d_dst) {
+                    return encode ? launch_staircase_encode(sc, d_src, d_dst, m, s) : launch_staircase_extract(sc, d_src, d_dst, m, s);
+                  },
+                  array_in(src, in_w), array_out(dst, out_w));
 }
 
 int cc_staircase_encode_batch_dev(const cc_staircase *sc, const uint8_t *d_msg, uint8_t *d_cw, size_t B, void *stream) {
-  return staircase_map_dev(sc, true, d_msg, d_cw, B, stream);
+  return staircase_map_call(sc, on_device(stream), true, d_msg, d_cw, B);
 }
 int cc_staircase_extract_batch_dev(const cc_staircase *sc, const uint8_t *d_cw, uint8_t *d_msg, size_t B, void *stream) {
-  return staircase_map_dev(sc, false, d_cw, d_msg, B, stream);
+  return staircase_map_call(sc, on_device(stream), false, d_cw, d_msg, B);
 }
 int cc_staircase_encode_batch(const cc_staircase *sc, const uint8_t *msg, uint8_t *cw, size_t B) {
-  return staircase_map_host(sc, true, msg, cw, B);
+  return staircase_map_call(sc, kFromHost, true, msg, cw, B);
 }
 int cc_staircase_extract_batch(const cc_staircase *sc, const uint8_t *cw, uint8_t *msg, size_t B) {
-  return staircase_map_host(sc, false, cw, msg, B);
+  return staircase_map_call(sc, kFromHost, false, cw, msg, B);
 }
+
 
 // an sc whose shape can be read; a handle without a code leaves needs_code's text as the last error
 static bool staircase_readable(const cc_staircase *sc, bool windowed) {
@@ -2045,30 +1947,27 @@ static int staircase_sr_supported(const cc_staircase *sc, const float *weights, 
   return rc;
 }
 
-int cc_staircase_decode_sr_dev(const cc_staircase *sc, const float *weights, const float *d_y, uint8_t *d_out, int32_t *d_nflip,
-                               int32_t *d_status, size_t B, void *stream) {
-  SrSchedule sched;
-  if (int rc = staircase_sr_supported(sc, weights, d_y, d_out, B, true, &sched)) return rc;
-  DeviceGuard guard(sc->code->device);
-  return launch_staircase_sr(sc, sched, d_y, d_out, d_nflip, d_status, B, static_cast<hipStream_t>(stream));
-}
-
-int cc_staircase_decode_sr(const cc_staircase *sc, const float *weights, const float *y, uint8_t *out, int32_t *nflip,
-                           int32_t *status, size_t B) {
+static int staircase_sr_call(const cc_staircase *sc, Where at, const float *weights, const float *y, uint8_t *out, int32_t *nflip,
+                             int32_t *status, size_t B) {
   SrSchedule sched;
   if (int rc = staircase_sr_supported(sc, weights, y, out, B, true, &sched)) return rc;
-  if (B == 0) return CC_OK;
-  const StaircaseShape s = staircase_shape(sc);
-  DeviceGuard guard(sc->code->device);
-  // a stream is the frame of the chunk loop
-  const StagedStream streams[] = {stage_in(0, y, s.N * sizeof(float)), stage_out(1, out, s.N), stage_out(2, nflip, sizeof(int32_t)),
-                                  stage_out(3, status, sizeof(int32_t))};
-  return staged_call(sc->code, B, s.N * sizeof(float), 1, streams, 4, nullptr, nullptr,
-                     [&](size_t m, void *const *d, const uint16_t *, const uint32_t *, hipStream_t st) {
-                       return launch_staircase_sr(sc, sched, static_cast<const float *>(d[0]), static_cast<uint8_t *>(d[1]),
-                                                  static_cast<int32_t *>(d[2]), static_cast<int32_t *>(d[3]), m, st);
-                     });
+  const size_t N = staircase_shape(sc).N;
+  return run_call(sc->code, at, B, N * sizeof(float), 1, NoCsr{},
+                  [&](size_t m, hipStream_t s, const float *d_y, uint8_t *d_out, int32_t *d_nflip, int32_t *d_status) {
+                    return launch_staircase_sr(sc, sched, d_y, d_out, d_nflip, d_status, m, s);
+                  },
+                  array_in(y, N), array_out(out, N), array_out(nflip, 1), array_out(status, 1));
 }
+
+int cc_staircase_decode_sr_dev(const cc_staircase *sc, const float *weights, const float *d_y, uint8_t *d_out, int32_t *d_nflip,
+                               int32_t *d_status, size_t B, void *stream) {
+  return staircase_sr_call(sc, on_device(stream), weights, d_y, d_out, d_nflip, d_status, B);
+}
+int cc_staircase_decode_sr(const cc_staircase *sc, const float *weights, const float *y, uint8_t *out, int32_t *nflip,
+                           int32_t *status, size_t B) {
+  return staircase_sr_call(sc, kFromHost, weights, y, out, nflip, status, B);
+}
+
 
 size_t cc_staircase_sr_lds_bytes(const cc_staircase *sc, const float *weights) {
   if (!staircase_readable(sc, true) || !weights || sc->iters == 0 || sc->iters > UINT32_MAX / 2) return 0;

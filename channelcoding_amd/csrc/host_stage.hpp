@@ -5,12 +5,13 @@
 
 #include <algorithm>
 #include <atomic>
-#include <cassert>
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "cc_internal.hpp"
@@ -268,37 +269,72 @@ inline int upload_erasures(HostStage &st, int slot, int idx, const uint16_t *era
   return CC_OK;
 }
 
-// One per-frame array of a staged call.  Buffer indices (HostStage::buf[slot][idx]): 0 in, 1 out, 2 iters / nerr,
-// 3 status, 4 L / metric; 5 and 6 hold a chunk's erasure positions and offsets (in a call without erasure lists they are
-// free: nback and nconf of the anchor decoder); 7 a second input (the reliabilities of GMD) or a second per-symbol output
-// (ext of the Chase soft output).
-struct StagedStream {
-  int idx;
-  size_t bytes;  // per frame
-  bool in;       // host -> device before the launch; otherwise device -> host behind it
-  void *host;    // the caller's array; an output may be null: the kernels write it, nobody receives it
+// One per-frame array of a call, typed as its launcher takes it: `per_frame` elements of T per frame.  An entry point
+// lists its arrays in the order of its launch callable's pointers; the staging buffer of an array is its position in
+// that list (HostStage::buf[slot][position]), so no call site names a buffer.
+template <class T>
+struct Arr {
+  T *host;  // the caller's array
+  size_t per_frame;
+  bool in;      // host -> device before the launch; otherwise device -> host behind it
+  bool staged;  // has a device buffer; false: the launch sees nullptr
 };
-inline StagedStream stage_in(int idx, const void *host, size_t bytes) { return {idx, bytes, true, const_cast<void *>(host)}; }
-inline StagedStream stage_out(int idx, void *host, size_t bytes) { return {idx, bytes, false, host}; }
-constexpr int kMaxStagedStreams = 7;
+template <class T>
+Arr<const T> array_in(const T *p, size_t per_frame) { return {p, per_frame, true, true}; }
+// an output the kernels write whether or not the caller wants it back: a buffer even when p is null (iters, nerr, status ...)
+template <class T>
+Arr<T> array_out(T *p, size_t per_frame) { return {p, per_frame, false, true}; }
+// an output whose absence selects another kernel: p == nullptr means no buffer, and the launch sees nullptr (L, ext)
+template <class T>
+Arr<T> array_out_if_wanted(T *p, size_t per_frame) { return {p, per_frame, false, p != nullptr}; }
+
+// The erasure lists of a call that takes them (both null: this call has none), and the mark of a call that never does.
+// A chunk's lists go to the two staging buffers behind the call's arrays.
+struct Csr {
+  const uint16_t *erasures;
+  const uint32_t *offsets;
+  static constexpr size_t buffers = 2;
+};
+struct NoCsr {
+  static constexpr const uint16_t *erasures = nullptr;
+  static constexpr const uint32_t *offsets = nullptr;
+  static constexpr size_t buffers = 0;
+};
+// launch(m, stream, d_er, d_off, pointers...) of a call with erasure lists, launch(m, stream, pointers...) of one without
+template <class Erasures, class Launch, class... P>
+int launch_on(Launch &launch, size_t m, hipStream_t stream, const uint16_t *d_er, const uint32_t *d_off, P... pointers) {
+  if constexpr (Erasures::buffers != 0)
+    return launch(m, stream, d_er, d_off, pointers...);
+  else
+    return launch(m, stream, pointers...);
+}
 
 // The chunk loop of every host-pointer entry point: B frames in chunks of chunk_frames(chunk_width, B), cut down to
 // a multiple of `granule` frames (an interleaving block is never split) and never less than one granule.  For each
-// chunk launch(m, d, d_er, d_off, stream) gets its frame count, the device buffers of `streams` in their order, the
-// chunk's erasure lists (null without erasures) and the stream to enqueue on, and returns a status.
+// chunk the launch gets its frame count, the stream to enqueue on, the chunk's erasure lists (a call with a Csr; null
+// where it has none) and one typed device pointer per array, in the order the arrays are listed, and returns a status.
 // What the loop keeps, and a change to it must keep:
 //  - retire(slot) before the slot's buffers are touched: the chunk that used them two turns ago is home, its staged
 //    results are in the caller's arrays, and get() may free and reallocate;
 //  - every way out drains both streams (StageLock's destructor): no copy is left that writes to caller memory;
 //  - a call of more than two chunks starts on fresh streams (HostStage::fresh_streams);
 //  - dma_ready is asked once per caller array, not once per chunk;
-//  - every stream listed gets a device buffer whether or not the caller wants it back.
-// `count` says how many of the N streams listed take part (an optional last one, such as L, is left out by it).
-template <size_t N, typename Launch>
-int staged_call(const cc_code *code, size_t B, size_t chunk_width, size_t granule, const StagedStream (&streams)[N], int count,
-                const uint16_t *erasures, const uint32_t *offsets, Launch &&launch) {
-  static_assert(N <= kMaxStagedStreams, "direct[] and d[] below hold kMaxStagedStreams entries");
-  assert(count >= 0 && static_cast<size_t>(count) <= N);
+//  - the erasure lists of a chunk are indexed by their GLOBAL offsets (the shifted base of upload_erasures);
+//  - every array listed by array_in() or array_out() gets a device buffer whether or not the caller wants it back;
+//    array_out_if_wanted() alone leaves one out.
+template <class Erasures, class Launch, class... T, size_t... I>
+int staged_call_at(std::index_sequence<I...>, const cc_code *code, size_t B, size_t chunk_width, size_t granule,
+                   Erasures csr, Launch &launch, const Arr<T> &...arrays) {
+  constexpr size_t N = sizeof...(T);
+  static_assert(N >= 1 && N + Erasures::buffers <= std::extent<decltype(HostStage::buf), 1>::value,
+                "one staging buffer per array and two for the erasure lists: HostStage::buf has no more");
+  struct Staged {
+    void *host;
+    size_t bytes;  // per frame
+    bool in, staged;
+  };
+  const Staged streams[N] = {
+      {const_cast<void *>(static_cast<const void *>(arrays.host)), arrays.per_frame * sizeof(T), arrays.in, arrays.staged}...};
   StageLock sl(code);
   if (sl.rc != CC_OK) return sl.rc;
   HostStage &st = *sl.st;
@@ -308,32 +344,39 @@ int staged_call(const cc_code *code, size_t B, size_t chunk_width, size_t granul
     if (int rc = st.fresh_streams()) return rc;
   // pageable caller memory goes through the page-locked ring (HostStage::upload / download); buffers the DMA engines
   // reach themselves (hipHostMalloc, hipHostRegister) are used in place
-  bool direct[kMaxStagedStreams];
-  for (int i = 0; i < count; ++i) direct[i] = streams[i].host && HostStage::dma_ready(streams[i].host);
+  bool direct[N];
+  for (size_t i = 0; i < N; ++i) direct[i] = streams[i].staged && streams[i].host && HostStage::dma_ready(streams[i].host);
   size_t k = 0;
   for (size_t c0 = 0; c0 < B; c0 += CH, ++k) {
     const int slot = static_cast<int>(k & 1);
     const size_t m = B - c0 < CH ? B - c0 : CH;
     if (int rc = st.retire(slot)) return rc;
-    void *d[kMaxStagedStreams] = {};
+    void *d[N] = {};
     const uint16_t *d_er = nullptr;
     const uint32_t *d_off = nullptr;
-    for (int i = 0; i < count; ++i)
-      if (int rc = st.get(slot, streams[i].idx, m * streams[i].bytes, &d[i])) return rc;
-    for (int i = 0; i < count; ++i) {
-      const StagedStream &s = streams[i];
+    for (size_t i = 0; i < N; ++i)
+      if (streams[i].staged)
+        if (int rc = st.get(slot, static_cast<int>(i), m * streams[i].bytes, &d[i])) return rc;
+    for (size_t i = 0; i < N; ++i) {
+      const Staged &s = streams[i];
       if (!s.in) continue;
-      if (int rc = st.upload(slot, s.idx, d[i], static_cast<const char *>(s.host) + c0 * s.bytes, m * s.bytes, direct[i])) return rc;
+      if (int rc = st.upload(slot, static_cast<int>(i), d[i], static_cast<const char *>(s.host) + c0 * s.bytes, m * s.bytes, direct[i]))
+        return rc;
     }
-    if (int rc = upload_erasures(st, slot, 5, erasures, offsets, c0, m, &d_er, &d_off)) return rc;
-    if (int rc = launch(m, d, d_er, d_off, st.stream[slot])) return rc;
-    for (int i = 0; i < count; ++i) {
-      const StagedStream &s = streams[i];
-      if (s.in || !s.host) continue;
-      if (int rc = st.download(slot, s.idx, static_cast<char *>(s.host) + c0 * s.bytes, d[i], m * s.bytes, direct[i])) return rc;
+    if (int rc = upload_erasures(st, slot, static_cast<int>(N), csr.erasures, csr.offsets, c0, m, &d_er, &d_off)) return rc;
+    if (int rc = launch_on<Erasures>(launch, m, st.stream[slot], d_er, d_off, static_cast<T *>(d[I])...)) return rc;
+    for (size_t i = 0; i < N; ++i) {
+      const Staged &s = streams[i];
+      if (s.in || !s.staged || !s.host) continue;
+      if (int rc = st.download(slot, static_cast<int>(i), static_cast<char *>(s.host) + c0 * s.bytes, d[i], m * s.bytes, direct[i]))
+        return rc;
     }
   }
   return st.drain();
+}
+template <class Erasures, class Launch, class... T>
+int staged_call(const cc_code *code, size_t B, size_t chunk_width, size_t granule, Erasures csr, Launch launch, Arr<T>... arrays) {
+  return staged_call_at(std::index_sequence_for<T...>(), code, B, chunk_width, granule, csr, launch, arrays...);
 }
 
 }  // namespace ccamd
